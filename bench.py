@@ -21,6 +21,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra
 objects: "roofline" (screening kernel, HBM-bound; algorithmic bytes = 4.125 B
 per screened base at h=3) and "cpu_baseline" (the C oracle timed on a bounded
 sample of the same draft + filter on the host; N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed (its edit records; with --screen-only the bitmap) as
+DIR/<name>.npy, float32 / float64, at most 64 MB: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -73,6 +76,9 @@ def parse():
                     help="skip ntedit_hip_reserve in the set-up: the first step then pays the context's buffer allocations")
     ap.add_argument("--shared-filter", action="store_true",
                     help="use the multi-GPU filter path (torch-owned filter tensor + broadcast) even with 1 rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, "
+                         "at most 64 MB in all; see dump_edits / dump_screen)")
     return ap.parse_args()
 
 
@@ -472,16 +478,91 @@ def shard_batch(job, pol, rank, world, k, torch):
             pieces)
 
 
+DUMP_LIMIT = 64_000_000  # bytes of .npy files --dump-outputs writes at most (all ranks together)
+DUMP_SEED = 20251033      # the fixed sample of a larger output
+STATS_FIELDS = ("bases", "absent_kmers", "events")  # (the applied-edit counters are filled in by rendering only)
+NPY_HEADER = 128          # bytes np.save puts in front of a small array's data
+RECORD_BYTES = 3 * 8 + 6 * 4 + 2 * 3 * 4  # one record's share of the edit_* arrays, its bases aside
+
+
+def _save(out_dir, prefix, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
+def dump_edits(out_dir, recs, pool, stats, n_contigs, prefix="", limit=DUMP_LIMIT):
+    """--dump-outputs of the polish path: what ntedit_hip_polish_batch hands its caller, the batch's edit records
+    (_lib.EDIT_DTYPE, the _changes.tsv rows) and the bases of its insertions / deletions.
+      stats             float64 [3]: the result counters of STATS_FIELDS
+      edits_per_contig  float64 [n_contigs]: records per entry, over ALL records
+      edits_per_kind    float64 [5]: records per kind (_lib.EDIT_SUB .. EDIT_SNV_KEPT; 0 unused), over ALL records
+      edit_index        float64 [S]: which records follow, in order (all of them, or a fixed seeded sample when they
+                        would not fit in `limit`), then one array per record field of those S records:
+      edit_contig, edit_draft_pos (float64); edit_len, edit_support, edit_kind, edit_draft_base, edit_new_base,
+      edit_n_alt (float32); edit_alt_base, edit_alt_support (float32 [S, 3]);
+      edit_bases        float32: the inserted / deleted bases (byte values) of those records that are insertions or
+                        deletions, edit_len of them per record, one record after the other"""
+    import numpy as np
+    from ntedit_amd import _lib
+    n = len(recs)
+    head = {"stats": np.array([float(getattr(stats, f)) for f in STATS_FIELDS], dtype=np.float64),
+            "edits_per_contig": np.bincount(recs["contig"].astype(np.int64), minlength=n_contigs).astype(np.float64),
+            "edits_per_kind": np.bincount(recs["kind"], minlength=5).astype(np.float64)}
+    carry = (recs["kind"] == _lib.EDIT_INS) | (recs["kind"] == _lib.EDIT_DEL)
+    cost = RECORD_BYTES + 4 * np.where(carry, recs["len"], 0).astype(np.int64)
+    room = limit - sum(a.nbytes for a in head.values()) - 16 * NPY_HEADER
+    if int(cost.sum()) <= room:
+        idx = np.arange(n)
+    else:  # the longest prefix of a seeded permutation that fits
+        order = np.random.default_rng(DUMP_SEED).permutation(n)
+        idx = np.sort(order[:int(np.searchsorted(np.cumsum(cost[order]), room, side="right"))])
+    s = recs[idx]
+    lens = np.where(carry[idx], s["len"], 0).astype(np.int64)
+    starts = np.repeat(s["bases_off"].astype(np.int64) - (np.cumsum(lens) - lens), lens)
+    at = starts + np.arange(int(lens.sum()))
+    body = {"edit_index": idx.astype(np.float64), "edit_contig": s["contig"].astype(np.float64),
+            "edit_draft_pos": s["draft_pos"].astype(np.float64)}
+    for f in ("len", "support", "kind", "draft_base", "new_base", "n_alt", "alt_base", "alt_support"):
+        body["edit_" + f] = s[f].astype(np.float32)
+    body["edit_bases"] = np.frombuffer(pool, dtype=np.uint8)[at].astype(np.float32)
+    _save(out_dir, prefix, {**head, **body})
+
+
+def dump_screen(out_dir, words, n, prefix="", limit=DUMP_LIMIT):
+    """--dump-outputs of --screen-only: the screening bitmap of the n-byte batch (one bit per position, set where the
+    k-mer starting there is absent from the filter: Stats.absent_kmers counts them).
+      screen_absent_per_block  float64: set bits per 65536 positions, over the whole batch
+      screen_word_index        float64 [S]: 64-bit words of the bitmap (all of them, or a fixed seeded sample)
+      screen_word_lo / _hi     float64 [S]: their low / high 32 bits"""
+    import numpy as np
+    words = np.ascontiguousarray(words[:(n + 63) // 64]).view(np.uint64).copy()
+    if n % 64:
+        words[-1] &= np.uint64((1 << (n % 64)) - 1)
+    pop = np.bitwise_count(words)
+    per_block = np.add.reduceat(pop, np.arange(0, len(words), 1024), dtype=np.int64).astype(np.float64) \
+        if len(words) else np.zeros(0)
+    cap = max(0, (limit - per_block.nbytes - 4 * NPY_HEADER) // 24)
+    nw = len(words)
+    idx = np.arange(nw) if nw <= cap else np.sort(np.random.default_rng(DUMP_SEED).choice(nw, cap, replace=False))
+    w = words[idx]
+    _save(out_dir, prefix, {"screen_absent_per_block": per_block, "screen_word_index": idx.astype(np.float64),
+                            "screen_word_lo": (w & np.uint64(0xFFFFFFFF)).astype(np.float64),
+                            "screen_word_hi": (w >> np.uint64(32)).astype(np.float64)})
+
+
 LAST_RANK_SECONDS = []  # per rank: its own seconds of the last timed_steps() (the value is the slowest rank's, barrier included)
 
 
-def timed_steps(step, steps, world, dev, torch, dist):
-    """K steps bracketed by barrier + synchronize on both sides; returns (max-over-ranks seconds, per-step stats)"""
+def timed_steps(step, steps, world, dev, torch, dist, keep_last=False):
+    """K steps bracketed by barrier + synchronize on both sides; returns (max-over-ranks seconds, per-step stats).
+    keep_last: the last step keeps its result for --dump-outputs (freed after the clock instead of inside it)"""
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    out = [step() for _ in range(steps)]
+    out = [step(keep=keep_last and i == steps - 1) for i in range(steps)]
     torch.cuda.synchronize()
     own = time.perf_counter() - t0  # this rank's own time, before it waits for the others
     if world > 1:
@@ -581,8 +662,10 @@ def main():
     if args.screen_only:
         bitmap = torch.zeros((my_bytes + 63) // 64 + 1, dtype=torch.int64, device=dev)
 
+    kept = []  # --dump-outputs: the last timed step's result
+
     def make_step(batch, offs, lens, nbytes, check_halos=None):
-        def step():
+        def step(keep=False):
             if args.screen_only:
                 return None, pol.screen_device(batch.data_ptr(), nbytes, bitmap.data_ptr())
             res = pol.polish_batch(None, offs, lens, device_ptr=batch.data_ptr(), n=nbytes)
@@ -594,7 +677,10 @@ def main():
                 # load none is expected -- a draft whose serial run ends early in a contig, as the reference's does
                 # at false-positive rates of several percent, makes every later cut of that contig one)
                 cuts_rejected[0] = int((~ok).sum())
-            res.free()
+            if keep:
+                kept.append(res)
+            else:
+                res.free()
             launches[0] = max(1, int(st.screen_launches))
             return st, st.ms_screen
         return step
@@ -603,7 +689,26 @@ def main():
     warm = make_step(my_batch, my_offs, my_lens, my_bytes, my_halos)
     for i in range(args.warmup):
         (warm if i == 0 and not args.screen_only else step)()
-    elapsed, stats = timed_steps(step, args.steps, world, dev, torch, dist)
+    elapsed, stats = timed_steps(step, args.steps, world, dev, torch, dist, keep_last=bool(args.dump_outputs))
+    if args.dump_outputs:
+        # (each rank its own share; at N>1 as rank<r>_<name>.npy, entries in the draft's contig numbering)
+        prefix = "rank%d_" % rank if world > 1 else ""
+        limit = DUMP_LIMIT // world
+        if args.screen_only:
+            dump_screen(args.dump_outputs, bitmap.cpu().numpy(), my_bytes, prefix, limit)
+        else:
+            res = kept.pop()
+            host = my_batch.cpu().numpy()
+            segments, n_entries = None, len(job.lens)
+            if world > 1:
+                mine = [q for q in pieces if q.owner == rank]
+                segments = [(q.start, int(h), 0) for q, h in zip(mine, my_halos)]
+            recs, pool = res.edits(host, my_offs, my_lens, segments)
+            if world > 1:
+                recs["contig"] = np.array([q.contig for q in mine], dtype=np.uint32)[recs["contig"]]
+            dump_edits(args.dump_outputs, recs, pool, res.stats(), n_entries, prefix, limit)
+            res.free()
+            del host
     rank_ms_per_step = [round(x / args.steps * 1e3, 3) for x in LAST_RANK_SECONDS]
     screen_ms = [ms for _, ms in stats]
     machine_ms = [st.ms_machine for st, _ in stats if st is not None]

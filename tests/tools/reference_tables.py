@@ -1,12 +1,13 @@
-"""What /root/reference/ntedit.cpp itself holds and a test can pin (VERDICT r5 "next" 2): the candidate tables
+"""What the reference's ntedit.cpp itself holds and a test can pin (VERDICT r5 "next" 2): the candidate tables
 (num_tries :172, polish_bases_array / snv_bases_array :176-199, multi_possible_bases :203-348), the opt:: defaults
 (:99-133), the literals of the _changes.tsv and _variants.vcf headers (:2165-2211) and of the default output prefix
-(:2496-2502).  extract(path) parses the reference's SOURCE TEXT (in the build container only) into canonical sections;
-the repository keeps their SHA-256 (tests/golden/reference_tables.json: hashes, not text), so that the GPU tier -- where
-/root/reference does not exist -- can still check the product against what the reference holds.
+(:2496-2502).  extract(path) parses the reference's SOURCE TEXT into canonical sections; the repository keeps their
+SHA-256 and those of the texts derived() builds from them (tests/golden/reference_tables.json: hashes, not text), so that
+the tests can check the product against what the reference holds without the reference.
 
-    python tests/tools/reference_tables.py            # prints the sections' hashes
-    python tests/tools/reference_tables.py --write    # (re)writes tests/golden/reference_tables.json
+    python tests/tools/reference_tables.py <ntedit.cpp>            # prints the hashes
+    python tests/tools/reference_tables.py <ntedit.cpp> --check    # fails if the committed hashes differ
+    python tests/tools/reference_tables.py <ntedit.cpp> --write    # (re)writes tests/golden/reference_tables.json
 """
 import hashlib
 import json
@@ -15,7 +16,6 @@ import os
 import re
 import sys
 
-REFERENCE = "/root/reference/ntedit.cpp"
 GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "reference_tables.json")
 LETTERS = "ATCGRYSWKMBDHVN"
 
@@ -47,7 +47,7 @@ def _literals(text):
     return out
 
 
-def extract(path=REFERENCE):
+def extract(path):
     """-> dict of canonical section texts"""
     src = open(path, encoding="utf-8", errors="replace").read()
     sec = {}
@@ -137,18 +137,36 @@ def vcf_header(lits, program, draft, date="00000000"):
     return "\n".join([lits[0], lits[1] + date, lits[2] + program, lits[3] + draft, lits[4], lits[5], lits[6]]) + "\n"
 
 
+def derived(sec):
+    """whole texts the product and the oracle must reproduce, built from the sections: the four tables as one dump, the
+    _changes.tsv header lines at k=25 / 3 hashes (plain and counting filter), the _variants.vcf header of a draft
+    named some/draft.fa (fileDate 00000000)"""
+    tl = json.loads(sec["tsv_header_literals"])
+    vl = json.loads(sec["vcf_header_literals"])
+    return {"tables_text": tables_text(sec), "tsv_header_25_3": tsv_header(tl, 25, 3, False),
+            "tsv_header_25_3_counting": tsv_header(tl, 25, 3, True),
+            "vcf_header_some_draft": vcf_header(vl, sec["program"].strip(), "some/draft.fa")}
+
+
 def hashes(sec):
-    return {k: hashlib.sha256(v.encode()).hexdigest() for k, v in sorted(sec.items())}
+    return {k: hashlib.sha256(v.encode()).hexdigest() for k, v in sorted({**sec, **derived(sec)}.items())}
 
 
 if __name__ == "__main__":
-    s = extract()
+    paths = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if len(paths) != 1:
+        sys.exit(__doc__)
+    s = extract(paths[0])
     h = hashes(s)
     print(json.dumps(h, indent=1))
+    if "--check" in sys.argv:  # the committed hashes are still those of the reference's text
+        if json.load(open(GOLDEN))["sha256"] != h:
+            sys.exit("tests/golden/reference_tables.json is stale: python tests/tools/reference_tables.py --write")
     if "--write" in sys.argv:
         os.makedirs(os.path.dirname(GOLDEN), exist_ok=True)
         with open(GOLDEN, "w") as f:
             json.dump({"source": "sha256 of the canonical sections tests/tools/reference_tables.py extracts from the reference's "
-                                 "ntedit.cpp (lines 99-133, 172, 176-199, 203-348, 2165-2211, 2496-2502); hashes only, no text",
+                                 "ntedit.cpp (lines 99-133, 172, 176-199, 203-348, 2165-2211, 2496-2502) and of the texts "
+                                 "derived() builds from them; hashes only, no text",
                        "sha256": h}, f, indent=1)
             f.write("\n")
