@@ -124,6 +124,35 @@ int ntedit_hip_filter_save_file(const ntedit_hip_ctx* ctx, int slot, const char*
 
 int ntedit_hip_set_params(ntedit_hip_ctx* ctx, const ntedit_hip_params* p);
 
+/* Reads k-mer filter build (ntedit-make-reads-bf; the reference runs ntHits / ntStat on the CPU for this step, and this is
+ * neither of them).  k-mers, hashes and slots are those of ntedit_hip_filter_insert: runs of k bytes of ACGTacgt, no
+ * k-mer across a byte of anything else, canonical ntHash, h hashes.
+ *   pass 1  ntedit_hip_sketch_count: a count-min sketch of `counters` 8-bit counters (btllib's counting-filter layout,
+ *           counter hv_i % counters): every k-mer occurrence adds 1 to ALL h of its counters, saturating at 255.
+ *           (Plain count-min, not btllib's conservative update: each counter ends at min(255, occurrences that hit
+ *           it), whatever the order of the atomics.)
+ *   pass 2  ntedit_hip_filter_insert_solid: est(x) = min of x's h sketch counters; every k-mer with est(x) >= cmin
+ *           (1..255) sets its h bits in a plain filter slot (ntedit_hip_filter_alloc), or raises its h counters of a
+ *           counting slot (ntedit_hip_filter_alloc_counting) to est(x) (max).  The slot's k and hash_num must be the
+ *           sketch's.  Results are bit-for-bit independent of batching and order.
+ * Batches follow ntedit_hip_filter_insert (host or device bytes, reads separated by e.g. '\n'; device batches
+ * 16-byte aligned).  The sketch is held per context beside the two filter slots, on the device that is current on the
+ * calling thread at ntedit_hip_sketch_alloc -- every call on a context makes its device current, so after
+ * ntedit_hip_create on the same thread that is the context's.  Free it with ntedit_hip_sketch_free before
+ * ntedit_hip_destroy.  Messages of these calls: ntedit_hip_reads_last_error() (ntedit_hip_last_error() belongs to
+ * the context's own calls). */
+int ntedit_hip_sketch_alloc(ntedit_hip_ctx* ctx, uint64_t counters, uint32_t hash_num, uint32_t k); /* counters: rounded up to a multiple of 8 */
+int ntedit_hip_sketch_count(ntedit_hip_ctx* ctx, const char* bases, uint64_t n, int on_device);
+int ntedit_hip_sketch_occupancy(ntedit_hip_ctx* ctx, uint64_t* nonzero, uint64_t* counters);
+int ntedit_hip_sketch_download(ntedit_hip_ctx* ctx, uint8_t* counters);
+int ntedit_hip_sketch_save_file(ntedit_hip_ctx* ctx, const char* path); /* as a counting filter file */
+void ntedit_hip_sketch_free(ntedit_hip_ctx* ctx);
+/* a zeroed counting filter (one 8-bit counter per byte, nbytes rounded up to a multiple of 8) in a filter slot */
+int ntedit_hip_filter_alloc_counting(ntedit_hip_ctx* ctx, int slot, uint64_t nbytes, uint32_t hash_num, uint32_t k);
+int ntedit_hip_filter_insert_solid(ntedit_hip_ctx* ctx, int slot, const char* bases, uint64_t n, int on_device, uint32_t cmin);
+const char* ntedit_hip_reads_last_error(const ntedit_hip_ctx* ctx);
+
+
 /* ---- hot path ------------------------------------------------------------
  * Batch layout: `bases` holds the contigs of the batch; contig i occupies
  * bases[offsets[i] .. offsets[i]+lens[i]) and every contig is followed by at

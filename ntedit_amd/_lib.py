@@ -109,6 +109,9 @@ EXPORTS = [
     "ntedit_hip_host_alloc", "ntedit_hip_host_free", "ntedit_hip_bind_near_device", "ntedit_hip_set_tuning", "ntedit_hip_build_id", "ntedit_hip_device_tables", "ntedit_hip_packed_size", "ntedit_hip_pack_bases",
     "ntedit_hip_fasta_load", "ntedit_hip_fasta_open", "ntedit_hip_fasta_read", "ntedit_hip_fasta_count", "ntedit_hip_fasta_blob", "ntedit_hip_fasta_record",
     "ntedit_hip_fasta_free", "ntedit_hip_result_cuts_ok", "ntedit_hip_reserve",
+    "ntedit_hip_sketch_alloc", "ntedit_hip_sketch_count", "ntedit_hip_sketch_occupancy", "ntedit_hip_sketch_download",
+    "ntedit_hip_sketch_save_file", "ntedit_hip_sketch_free", "ntedit_hip_filter_alloc_counting",
+    "ntedit_hip_filter_insert_solid", "ntedit_hip_reads_last_error",
 ]
 
 _lib = None
@@ -197,5 +200,17 @@ def load():
                                             ctypes.POINTER(u64)]
     lib.ntedit_hip_fasta_free.argtypes = [vp]
     lib.ntedit_hip_fasta_free.restype = None
+    # reads k-mer filter build (ntedit-make-reads-bf)
+    lib.ntedit_hip_sketch_alloc.argtypes = [vp, u64, u32, u32]
+    lib.ntedit_hip_sketch_count.argtypes = [vp, vp, u64, ci]
+    lib.ntedit_hip_sketch_occupancy.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.ntedit_hip_sketch_download.argtypes = [vp, vp]
+    lib.ntedit_hip_sketch_save_file.argtypes = [vp, ctypes.c_char_p]
+    lib.ntedit_hip_sketch_free.argtypes = [vp]
+    lib.ntedit_hip_sketch_free.restype = None
+    lib.ntedit_hip_filter_alloc_counting.argtypes = [vp, ci, u64, u32, u32]
+    lib.ntedit_hip_filter_insert_solid.argtypes = [vp, ci, vp, u64, ci, u32]
+    lib.ntedit_hip_reads_last_error.argtypes = [vp]
+    lib.ntedit_hip_reads_last_error.restype = ctypes.c_char_p
     _lib = lib
     return lib

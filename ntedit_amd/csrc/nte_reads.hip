@@ -1,0 +1,645 @@
+// nte_reads.hip -- gfx950 kernels and C ABI of the reads k-mer filter build (ntedit-make-reads-bf).
+//
+//   k_count<H, POW2>          pass 1: every k-mer of a batch of reads increments all h of its counters in a
+//                             count-min sketch of 8-bit counters, saturating at 255
+//   k_solid<H, POW2, COUNTS>  pass 2: est(x) = min of x's h sketch counters; a k-mer with est(x) >= cmin sets its h
+//                             bits in a plain output filter, or raises its h counters of a counting output filter to
+//                             est(x) (byte atomic max)
+//   k_nonzero                 non-zero counters of the sketch (occupancy)
+//
+// k-mers, hashes and slots are the filter build's (k_screen<., ., true> in nte_kernels.hip): runs of k bytes of
+// ACGTacgt, canonical base fh + rh, hash_extend, filter_slot.  Every result is independent of the order in which the
+// atomics land: a counter ends at min(255, occurrences that hit it), a bit is an OR, a counting output is a max.
+//
+// gfx950 has no byte atomics: both byte updates are 32-bit compare-and-swap loops on the containing word, entered
+// only when a plain read of the word says the byte still has to change (a saturated poly-A counter, a solid k-mer's
+// bits already set, a counter already at est(x)).  Counters only grow, so a stale read can never skip an update that
+// was due: it can only cost one extra CAS.
+//
+// This unit does not see the context's internals (nte_api.hip): the sketch lives in a small per-context state of its
+// own, the output filter is reached through the public calls (ntedit_hip_filter_device_ptr / _info / _set_filter).
+// That keeps nte_api.hip and the kernels it compiles -- and with them ntedit_hip_build_id() -- unchanged.
+#include "nte_common.h"
+
+#include "../../include/ntedit_hip.h"
+#include "../host/bfio.h"
+#include "../host/params.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace nte;
+
+namespace {
+
+// Tile: 256 threads x 64 consecutive k-mer starts; the tile's bytes (+ k - 1 halo) are staged once, coalesced 16 B
+// per lane, as one 2-bit code (or RD_BAD) per byte in LDS.  Rows of 64 codes are padded to 68 bytes so that the
+// per-thread streams (lane stride = one row) fall into different banks.
+constexpr int RD_TPB = 256;
+constexpr int RD_L = 64;
+constexpr int RD_TILE = RD_TPB * RD_L;
+constexpr int RD_MAXK = 200;
+constexpr int RD_LDS_BYTES = ((RD_TILE + RD_MAXK + 63) / 64) * 68 + 16;
+constexpr u8 RD_BAD = CODE_BAD;
+
+__device__ __forceinline__ u32
+rd_lds(u32 x)
+{
+	return x + ((x >> 6) << 2);
+}
+
+struct RdFilter // one filter as the reads kernels address it
+{
+	u32* words;
+	Filter f; // geometry only (f.data unused)
+};
+
+// prologue shared by both kernels: seed tables + LUT in LDS, the tile's codes staged
+__device__ __forceinline__ void
+rd_stage(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, u64* s_tab, u8* s_lut, u8* s_codes)
+{
+	const u32 tid = threadIdx.x;
+	if (tid < TAB_WORDS) {
+		s_tab[tid] = tabs[tid];
+	}
+	{
+		const u8 code = char_code((u8)tid);
+		s_lut[tid] = code <= 3 ? code : RD_BAD; // k-mers of ACGTacgt only (as the filter build)
+	}
+	__syncthreads();
+	const u64 tile_base = (u64)blockIdx.x * RD_TILE;
+	const u32 n_chunks = (RD_TILE + k - 1 + 15) / 16;
+	for (u32 c = tid; c < n_chunks; c += RD_TPB) {
+		const u64 g = tile_base + (u64)c * 16;
+		u32 w[4];
+		if (g + 16 <= n) {
+			const uint4 v = *reinterpret_cast<const uint4*>(seq + g);
+			w[0] = v.x;
+			w[1] = v.y;
+			w[2] = v.z;
+			w[3] = v.w;
+		} else {
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				u32 x = 0;
+#pragma unroll
+				for (int b = 0; b < 4; b++) {
+					const u64 gg = g + q * 4 + b;
+					x |= (u32)(gg < n ? seq[gg] : (u8)'\n') << (8 * b);
+				}
+				w[q] = x;
+			}
+		}
+#pragma unroll
+		for (int q = 0; q < 4; q++) {
+			const u32 x = w[q];
+			const u32 codes = (u32)s_lut[x & 0xFF] | ((u32)s_lut[(x >> 8) & 0xFF] << 8) |
+			                  ((u32)s_lut[(x >> 16) & 0xFF] << 16) | ((u32)s_lut[x >> 24] << 24);
+			*reinterpret_cast<u32*>(&s_codes[rd_lds(c * 16 + q * 4)]) = codes;
+		}
+	}
+	__syncthreads();
+}
+
+template<bool POW2>
+__device__ __forceinline__ u64
+rd_slot(const Filter& f, u64 hv)
+{
+	return POW2 ? (hv & f.mask) : filter_slot(f, hv);
+}
+
+// saturating +1 of byte s of the counter array
+__device__ __forceinline__ void
+sat_inc(u32* words, u64 s)
+{
+	u32* w = words + (s >> 2);
+	const u32 sh = (u32)(s & 3) * 8;
+	u32 old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	while (((old >> sh) & 0xFFu) != 0xFFu) {
+		const u32 prev = atomicCAS(w, old, old + (1u << sh));
+		if (prev == old) {
+			break;
+		}
+		old = prev;
+	}
+}
+
+// byte s of the counter array := max(byte, v)
+__device__ __forceinline__ void
+byte_max(u32* words, u64 s, u32 v)
+{
+	u32* w = words + (s >> 2);
+	const u32 sh = (u32)(s & 3) * 8;
+	u32 old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	while (((old >> sh) & 0xFFu) < v) {
+		const u32 prev = atomicCAS(w, old, (old & ~(0xFFu << sh)) | (v << sh));
+		if (prev == old) {
+			break;
+		}
+		old = prev;
+	}
+}
+
+// ------------------------------------------------------------------ k_count / k_solid
+// One thread walks 64 consecutive k-mer starts of the tile.  The hash state is exact once k codes of ACGT have
+// entered since the last RD_BAD (an RD_BAD code has zero seeds both ways, so it leaves nothing behind).
+template<int H, bool POW2, int PASS> // PASS 0: k_count; 1: k_solid into bits; 2: k_solid into counters
+__device__ __forceinline__ void
+rd_walk(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, const DevParams& p, RdFilter sk, RdFilter out, u32 cmin)
+{
+	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
+	__shared__ u8 s_lut[256];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[RD_LDS_BYTES];
+	rd_stage(seq, n, k, tabs, s_tab, s_lut, s_codes);
+
+	const u32 x0 = threadIdx.x * RD_L;
+	HashState hs = { 0, 0 };
+	u32 good = 0;
+	for (u32 i = 0; i < k; i++) {
+		const u8 in = s_codes[rd_lds(x0 + i)];
+		hash_roll(hs, s_tab, RD_BAD, in);
+		good = in == RD_BAD ? 0 : good + 1;
+	}
+	const u8* sk_bytes = reinterpret_cast<const u8*>(sk.words);
+	for (u32 j = 0; j < RD_L; j++) {
+		if (good >= k) {
+			const u64 base = hs.fh + hs.rh;
+			u64 hv[H];
+#pragma unroll
+			for (int i = 0; i < H; i++) {
+				hv[i] = hash_extend(base, p, i);
+			}
+			if (PASS == 0) {
+#pragma unroll
+				for (int i = 0; i < H; i++) {
+					sat_inc(sk.words, rd_slot<POW2>(sk.f, hv[i]));
+				}
+			} else {
+				u32 est = 255;
+#pragma unroll
+				for (int i = 0; i < H; i++) {
+					const u32 c = sk_bytes[rd_slot<POW2>(sk.f, hv[i])];
+					est = c < est ? c : est;
+				}
+				if (est >= cmin) {
+#pragma unroll
+					for (int i = 0; i < H; i++) {
+						const u64 s = filter_slot(out.f, hv[i]);
+						if (PASS == 1) {
+							u32* w = out.words + (s >> 5);
+							const u32 bit = 1u << (s & 31);
+							if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) {
+								atomicOr(w, bit);
+							}
+						} else {
+							byte_max(out.words, s, est);
+						}
+					}
+				}
+			}
+		}
+		const u8 o = s_codes[rd_lds(x0 + j)];
+		const u8 in = s_codes[rd_lds(x0 + j + k)];
+		hash_roll(hs, s_tab, o, in);
+		good = in == RD_BAD ? 0 : good + 1;
+	}
+}
+
+template<int H, bool POW2>
+__global__ __launch_bounds__(RD_TPB) void
+k_count(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk)
+{
+	rd_walk<H, POW2, 0>(seq, n, k, tabs, p, sk, sk, 0);
+}
+
+template<int H, bool POW2, bool COUNTS>
+__global__ __launch_bounds__(RD_TPB) void
+k_solid(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk, RdFilter out, u32 cmin)
+{
+	rd_walk<H, POW2, COUNTS ? 2 : 1>(seq, n, k, tabs, p, sk, out, cmin);
+}
+
+// non-zero bytes of an array of n_words 64-bit words (allocations are whole words, zero behind the counters)
+__global__ __launch_bounds__(256) void
+k_nonzero(const u64* __restrict__ w, u64 n_words, unsigned long long* total)
+{
+	__shared__ unsigned long long s_sum[256];
+	unsigned long long acc = 0;
+	for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (u64)gridDim.x * 256) {
+		u64 x = w[i];
+		x |= x >> 4;
+		x |= x >> 2;
+		x |= x >> 1;
+		acc += __popcll(x & 0x0101010101010101ULL);
+	}
+	s_sum[threadIdx.x] = acc;
+	__syncthreads();
+	for (u32 s = 128; s > 0; s >>= 1) {
+		if (threadIdx.x < s) {
+			s_sum[threadIdx.x] += s_sum[threadIdx.x + s];
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		atomicAdd(total, s_sum[0]);
+	}
+}
+
+// ------------------------------------------------------------------ host side
+struct ReadsState
+{
+	const ntedit_hip_ctx* owner = nullptr;
+	int device = 0;
+	hipStream_t stream = nullptr;
+	u8* sketch = nullptr; // counters, zero-filled up to a whole 64-bit word
+	u64 counters = 0;
+	u32 hash_num = 0, k = 0;
+	DevParams dp;
+	u64* d_tab = nullptr;
+	u8* d_seq = nullptr; // staging of host batches (grow-only)
+	u64 seq_cap = 0;
+	unsigned long long* d_total = nullptr;
+	std::string err;
+};
+
+std::mutex g_reads_mu;
+std::vector<ReadsState*> g_reads;       // one per context that holds a sketch
+std::vector<std::pair<const ntedit_hip_ctx*, std::string>> g_reads_err; // last failure per context
+
+int
+rfail(const ntedit_hip_ctx* c, int code, const char* fmt, ...)
+{
+	char buf[512];
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(buf, sizeof buf, fmt, ap);
+	va_end(ap);
+	std::lock_guard<std::mutex> lk(g_reads_mu);
+	for (auto& e : g_reads_err) {
+		if (e.first == c) {
+			e.second = buf;
+			return code;
+		}
+	}
+	g_reads_err.emplace_back(c, buf);
+	return code;
+}
+
+#define RD_TRY(ctx, expr)                                                                        \
+	do {                                                                                         \
+		hipError_t e_ = (expr);                                                                  \
+		if (e_ != hipSuccess) {                                                                  \
+			return rfail((ctx), NTEDIT_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));        \
+		}                                                                                        \
+	} while (0)
+
+ReadsState*
+find_state(const ntedit_hip_ctx* c)
+{
+	std::lock_guard<std::mutex> lk(g_reads_mu);
+	for (ReadsState* s : g_reads) {
+		if (s->owner == c) {
+			return s;
+		}
+	}
+	return nullptr;
+}
+
+void
+release_state(ReadsState* s)
+{
+	(void)hipSetDevice(s->device);
+	if (s->stream) {
+		(void)hipStreamSynchronize(s->stream);
+		(void)hipStreamDestroy(s->stream);
+	}
+	for (void* p : { (void*)s->sketch, (void*)s->d_tab, (void*)s->d_seq, (void*)s->d_total }) {
+		if (p) {
+			(void)hipFree(p);
+		}
+	}
+	delete s;
+}
+
+Filter
+geometry(u64 slots, u32 hash_num, bool counting)
+{
+	Filter f;
+	f.data = nullptr;
+	filter_set_size(f, slots);
+	f.hash_num = hash_num;
+	f.counting = counting ? 1 : 0;
+	return f;
+}
+
+// the batch in HBM (host batches are copied into the state's staging buffer)
+int
+stage(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int on_device, const u8** d_seq)
+{
+	if (on_device == NTEDIT_HIP_BASES_DEVICE) {
+		if ((uintptr_t)bases & 15) {
+			return rfail(c, NTEDIT_E_ARG, "reads: device batches must be 16-byte aligned");
+		}
+		*d_seq = (const u8*)bases;
+		return 0;
+	}
+	if (on_device != NTEDIT_HIP_BASES_HOST) {
+		return rfail(c, NTEDIT_E_ARG, "reads: bases must be host or device bytes");
+	}
+	if (n > s->seq_cap) {
+		if (s->d_seq) {
+			RD_TRY(c, hipFree(s->d_seq));
+			s->d_seq = nullptr;
+			s->seq_cap = 0;
+		}
+		RD_TRY(c, hipMalloc((void**)&s->d_seq, n + 64));
+		s->seq_cap = n;
+	}
+	RD_TRY(c, hipMemcpyAsync(s->d_seq, bases, n, hipMemcpyHostToDevice, s->stream));
+	*d_seq = s->d_seq;
+	return 0;
+}
+
+template<bool POW2, int PASS>
+void
+launch_walk(ReadsState* s, const u8* d_seq, u64 n, u64 tiles, RdFilter sk, RdFilter out, u32 cmin)
+{
+	dim3 grid((unsigned)tiles), block(RD_TPB);
+#define RD_LAUNCH(H)                                                                                               \
+	case H:                                                                                                        \
+		if (PASS == 0) {                                                                                           \
+			hipLaunchKernelGGL((k_count<H, POW2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, s->dp, sk); \
+		} else {                                                                                                   \
+			hipLaunchKernelGGL((k_solid<H, POW2, PASS == 2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, \
+			                   s->dp, sk, out, cmin);                                                              \
+		}                                                                                                          \
+		break
+	switch (s->hash_num) {
+		RD_LAUNCH(1);
+		RD_LAUNCH(2);
+		RD_LAUNCH(3);
+		RD_LAUNCH(4);
+		RD_LAUNCH(5);
+		RD_LAUNCH(6);
+		RD_LAUNCH(7);
+		RD_LAUNCH(8);
+	default:
+		break;
+	}
+#undef RD_LAUNCH
+}
+
+int
+run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int on_device, int pass, RdFilter out, u32 cmin)
+{
+	RD_TRY(c, hipSetDevice(s->device));
+	if (n == 0) {
+		return 0;
+	}
+	const u64 tiles = (n + RD_TILE - 1) / RD_TILE;
+	if (tiles > 0x7FFFFFFFull) {
+		return rfail(c, NTEDIT_E_ARG, "reads: batch too large");
+	}
+	const u8* d_seq = nullptr;
+	int rc = stage(c, s, bases, n, on_device, &d_seq);
+	if (rc) {
+		return rc;
+	}
+	RdFilter sk;
+	sk.words = (u32*)s->sketch;
+	sk.f = geometry(s->counters, s->hash_num, true);
+	const bool pow2 = sk.f.mask != 0;
+	if (pass == 0) {
+		pow2 ? launch_walk<true, 0>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 0>(s, d_seq, n, tiles, sk, out, cmin);
+	} else if (pass == 1) {
+		pow2 ? launch_walk<true, 1>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 1>(s, d_seq, n, tiles, sk, out, cmin);
+	} else {
+		pow2 ? launch_walk<true, 2>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 2>(s, d_seq, n, tiles, sk, out, cmin);
+	}
+	RD_TRY(c, hipGetLastError());
+	RD_TRY(c, hipStreamSynchronize(s->stream));
+	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+const char*
+ntedit_hip_reads_last_error(const ntedit_hip_ctx* c)
+{
+	std::lock_guard<std::mutex> lk(g_reads_mu);
+	for (auto& e : g_reads_err) {
+		if (e.first == c) {
+			return e.second.c_str();
+		}
+	}
+	return "";
+}
+
+int
+ntedit_hip_sketch_alloc(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	if (counters == 0 || hash_num == 0 || hash_num > MAX_HASHES || k < 12 || k > RD_MAXK) {
+		return rfail(c, NTEDIT_E_ARG, "sketch_alloc: %llu counters, hash_num = %u, k = %u: needs counters > 0, hash_num in [1, %u] and k in [12, %u]",
+		             (unsigned long long)counters, hash_num, k, MAX_HASHES, RD_MAXK);
+	}
+	ntedit_hip_sketch_free(c);
+	int device = 0;
+	RD_TRY(c, hipGetDevice(&device));
+	ReadsState* s = new ReadsState();
+	s->owner = c;
+	s->device = device;
+	s->counters = (counters + 7) / 8 * 8; // btllib rounds a counting filter up to whole 64-bit words
+	s->hash_num = hash_num;
+	s->k = k;
+	ntedit_hip_params hp;
+	nte_host::params_default(&hp);
+	int rc = nte_host::make_dev_params(hp, k, hash_num, false, &s->dp);
+	u64 tab[TAB_WORDS];
+	build_seed_tables(k, tab);
+	hipError_t e = rc ? hipSuccess : hipStreamCreate(&s->stream);
+	if (e == hipSuccess && !rc) {
+		e = hipMalloc((void**)&s->sketch, s->counters);
+	}
+	if (e == hipSuccess && !rc) {
+		e = hipMalloc((void**)&s->d_tab, sizeof tab);
+	}
+	if (e == hipSuccess && !rc) {
+		e = hipMalloc((void**)&s->d_total, 8);
+	}
+	if (e == hipSuccess && !rc) {
+		e = hipMemsetAsync(s->sketch, 0, s->counters, s->stream);
+	}
+	if (e == hipSuccess && !rc) {
+		e = hipMemcpyAsync(s->d_tab, tab, sizeof tab, hipMemcpyHostToDevice, s->stream);
+	}
+	if (e == hipSuccess && !rc) {
+		e = hipStreamSynchronize(s->stream);
+	}
+	if (rc || e != hipSuccess) {
+		release_state(s);
+		if (rc) {
+			return rfail(c, rc, "sketch_alloc: unsupported k / hash_num");
+		}
+		return rfail(c, NTEDIT_E_DEVICE, "sketch_alloc: %llu counters: %s", (unsigned long long)counters, hipGetErrorString(e));
+	}
+	std::lock_guard<std::mutex> lk(g_reads_mu);
+	g_reads.push_back(s);
+	return 0;
+}
+
+void
+ntedit_hip_sketch_free(ntedit_hip_ctx* c)
+{
+	ReadsState* s = nullptr;
+	{
+		std::lock_guard<std::mutex> lk(g_reads_mu);
+		for (size_t i = 0; i < g_reads.size(); i++) {
+			if (g_reads[i]->owner == c) {
+				s = g_reads[i];
+				g_reads.erase(g_reads.begin() + (long)i);
+				break;
+			}
+		}
+	}
+	if (s) {
+		release_state(s);
+	}
+}
+
+int
+ntedit_hip_sketch_count(ntedit_hip_ctx* c, const char* bases, uint64_t n, int on_device)
+{
+	ReadsState* s = find_state(c);
+	if (!c || !bases) {
+		return c ? rfail(c, NTEDIT_E_ARG, "sketch_count: bad argument") : NTEDIT_E_ARG;
+	}
+	if (!s) {
+		return rfail(c, NTEDIT_E_ARG, "sketch_count: no sketch (ntedit_hip_sketch_alloc)");
+	}
+	RdFilter none = {};
+	return run_pass(c, s, bases, n, on_device, 0, none, 0);
+}
+
+int
+ntedit_hip_sketch_occupancy(ntedit_hip_ctx* c, uint64_t* nonzero, uint64_t* counters)
+{
+	ReadsState* s = find_state(c);
+	if (!s || !nonzero) {
+		return c ? rfail(c, NTEDIT_E_ARG, "sketch_occupancy: bad argument or no sketch") : NTEDIT_E_ARG;
+	}
+	RD_TRY(c, hipSetDevice(s->device));
+	RD_TRY(c, hipMemsetAsync(s->d_total, 0, 8, s->stream));
+	hipLaunchKernelGGL(k_nonzero, dim3(1024), dim3(256), 0, s->stream, (const u64*)s->sketch, s->counters / 8, s->d_total);
+	RD_TRY(c, hipGetLastError());
+	unsigned long long h = 0;
+	RD_TRY(c, hipMemcpyAsync(&h, s->d_total, 8, hipMemcpyDeviceToHost, s->stream));
+	RD_TRY(c, hipStreamSynchronize(s->stream));
+	*nonzero = h;
+	if (counters) {
+		*counters = s->counters;
+	}
+	return 0;
+}
+
+int
+ntedit_hip_sketch_download(ntedit_hip_ctx* c, uint8_t* counters)
+{
+	ReadsState* s = find_state(c);
+	if (!s || !counters) {
+		return c ? rfail(c, NTEDIT_E_ARG, "sketch_download: bad argument or no sketch") : NTEDIT_E_ARG;
+	}
+	RD_TRY(c, hipSetDevice(s->device));
+	RD_TRY(c, hipMemcpy(counters, s->sketch, s->counters, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int
+ntedit_hip_sketch_save_file(ntedit_hip_ctx* c, const char* path)
+{
+	ReadsState* s = find_state(c);
+	if (!s || !path) {
+		return c ? rfail(c, NTEDIT_E_ARG, "sketch_save_file: bad argument or no sketch") : NTEDIT_E_ARG;
+	}
+	std::vector<u8> host(s->counters);
+	int rc = ntedit_hip_sketch_download(c, host.data());
+	if (rc) {
+		return rc;
+	}
+	nte_host::BfHeader h;
+	h.bytes = s->counters;
+	h.hash_num = s->hash_num;
+	h.k = s->k;
+	h.counting = true;
+	if (nte_host::bf_save(path, h, host.data())) {
+		return rfail(c, NTEDIT_E_IO, "`%s': cannot write", path);
+	}
+	return 0;
+}
+
+int
+ntedit_hip_filter_alloc_counting(ntedit_hip_ctx* c, int slot, uint64_t nbytes, uint32_t hash_num, uint32_t k)
+{
+	if (!c || slot < 0 || slot > 1 || nbytes == 0 || hash_num == 0 || hash_num > MAX_HASHES) {
+		return c ? rfail(c, NTEDIT_E_ARG, "filter_alloc_counting: bad argument") : NTEDIT_E_ARG;
+	}
+	nbytes = (nbytes + 7) / 8 * 8; // as ntedit_hip_filter_alloc (btllib: whole 64-bit words)
+	// calloc'd pages are the kernel's zero page until written: the upload reads them without committing memory
+	void* zeros = calloc(nbytes, 1);
+	if (!zeros) {
+		return rfail(c, NTEDIT_E_ARG, "filter_alloc_counting: %llu bytes of host memory", (unsigned long long)nbytes);
+	}
+	const int rc = ntedit_hip_set_filter(c, slot, (const uint8_t*)zeros, nbytes, hash_num, k, 1);
+	free(zeros);
+	if (rc) {
+		return rfail(c, rc, "filter_alloc_counting: %s", ntedit_hip_last_error(c));
+	}
+	return 0;
+}
+
+int
+ntedit_hip_filter_insert_solid(ntedit_hip_ctx* c, int slot, const char* bases, uint64_t n, int on_device, uint32_t cmin)
+{
+	if (!c || !bases || slot < 0 || slot > 1) {
+		return c ? rfail(c, NTEDIT_E_ARG, "filter_insert_solid: bad argument") : NTEDIT_E_ARG;
+	}
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: no sketch (ntedit_hip_sketch_alloc)");
+	}
+	if (cmin < 1 || cmin > 255) {
+		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: cmin = %u: needs 1 <= cmin <= 255", cmin);
+	}
+	uint32_t k = 0, hash_num = 0;
+	uint64_t nbytes = 0;
+	int counting = 0;
+	void* data = ntedit_hip_filter_device_ptr(c, slot);
+	if (!data || ntedit_hip_filter_info(c, slot, &k, &hash_num, &nbytes, &counting) != 0) {
+		return rfail(c, NTEDIT_E_NOFILTER, "filter_insert_solid: filter slot %d not set", slot);
+	}
+	if (k != s->k || hash_num != s->hash_num) {
+		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: the filter has k = %u, hash_num = %u, the sketch k = %u, hash_num = %u",
+		             k, hash_num, s->k, s->hash_num);
+	}
+	hipPointerAttribute_t attr;
+	RD_TRY(c, hipPointerGetAttributes(&attr, data));
+	if (attr.device != s->device) {
+		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: the filter is on device %d, the sketch on device %d", attr.device, s->device);
+	}
+	RdFilter out;
+	out.words = (u32*)data;
+	out.f = geometry(counting ? nbytes : nbytes * 8, hash_num, counting != 0);
+	return run_pass(c, s, bases, n, on_device, counting ? 2 : 1, out, cmin);
+}
+
+} // extern "C"

@@ -1,0 +1,510 @@
+// make_reads_bf.cpp -- `ntedit-make-reads-bf`: the k-mer filter of a read set, built on one MI355X, for `ntedit -r`.
+//
+//   --reads FILE [FILE ...]  -k K  -c CMIN  [--counts]  [--hashes 3]  [--fpr 0.01]
+//   (--bf BYTES | --num_elements N)  [--sketch_bytes S]  [-o reads_kK.bf]  [-t THREADS]
+//
+// The reference leaves this step to ntHits / ntStat on the CPU (ntedit-make: `nthits -c<cutoff> --outbloom`;
+// ntedit_run_pipeline.smk: `ntstat filter -cmin C`).  This tool is neither: it counts in a plain count-min sketch of
+// 8-bit counters (pass 1, ntedit_hip_sketch_count) and keeps the k-mers whose estimate -- the minimum of their h
+// counters -- is at least CMIN (pass 2, ntedit_hip_filter_insert_solid), so its counts and its sizing differ from
+// theirs.  The output is a btllib-format filter that ntedit -r loads unchanged: a plain Bloom filter, or with --counts
+// a counting filter holding each solid k-mer's estimate (for ntedit -p / -q).  Both passes read the inputs (FASTA or
+// FASTQ, plain or gzip) through FastaReader, in bounded batches double-buffered through page-locked memory: a second
+// thread parses the next batch while the GPU works on the current one.
+#include "../../include/ntedit_hip.h"
+#include "fasta.h"
+
+#include <chrono>
+#include <cerrno>
+#include <cmath>
+#include <condition_variable>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <ctime>
+#include <deque>
+#include <iostream>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+static void
+log_info(const std::string& msg)
+{
+	// btllib::log_info: "[<local time>] [INFO] <msg>" on stderr
+	char ts[64];
+	time_t now = time(nullptr);
+	strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", localtime(&now));
+	std::cerr << "[" << ts << "] [INFO] " << msg << std::endl;
+}
+
+// as ntedit-make-genome-bf (ntedit_make_genome_bf.cpp:41-47)
+static uint64_t
+get_bf_size(uint64_t num_elements, double num_hashes, double fpr)
+{
+	const double r = -num_hashes / log(1.0 - exp(log(fpr) / num_hashes));
+	const uint64_t m = (uint64_t)(ceil((double)num_elements * r) / 8u);
+	return m;
+}
+
+// default sketch: 16 output bytes' worth of counters, within [64 MiB, 32 GiB]
+static const uint64_t SKETCH_PER_OUTPUT_BYTE = 16;
+static const uint64_t SKETCH_MIN = 64ull << 20;
+static const uint64_t SKETCH_MAX = 32ull << 30;
+static const uint64_t BATCH_DEFAULT = 256ull << 20;
+
+static void
+usage(const char* why)
+{
+	if (why) {
+		std::cerr << why << std::endl;
+	}
+	std::cerr
+	    << "Usage: make_reads_bf [--help] --reads VAR... -k VAR -c VAR [--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] "
+	       "[--num_elements VAR] [--sketch_bytes VAR] [-o VAR] [-t VAR]\n\n"
+	       "Builds the k-mer filter of a read set on the GPU: pass 1 counts every k-mer in a count-min sketch of 8-bit\n"
+	       "counters, pass 2 keeps the k-mers whose estimate (the minimum of their counters) is at least -c.  Neither\n"
+	       "ntHits nor ntStat: the counts (plain count-min, no conservative update) and the sizing are this tool's own.\n\n"
+	       "Optional arguments:\n"
+	       "  -h, --help      shows help message and exits\n"
+	       "  --reads         Input reads, FASTA or FASTQ, plain or gzip [nargs: 1 or more] [required]\n"
+	       "  -k              k-mer size (bp), 12 to 200 [required]\n"
+	       "  -c              Minimum k-mer count (cmin), 1 to 255 [required]\n"
+	       "  --counts        Write a counting filter (each solid k-mer's estimate) for ntedit -p / -q\n"
+	       "  --hashes        Number of hash functions, 1 to 8 [default: 3]\n"
+	       "  --fpr           False positive rate for Bloom filter (with --num_elements) [default: 0.01]\n"
+	       "  --bf            Output filter size in bytes\n"
+	       "  --num_elements  Approximate number of solid k-mers (output size through the genome tool's formula)\n"
+	       "                  (one of --bf / --num_elements is required)\n"
+	       "  --sketch_bytes  Counters of the count-min sketch [default: 16 x the output bytes, 64 MiB to 32 GiB]\n"
+	       "  -o              Name for output filter [default: \"reads_k<K>.bf\"]\n"
+	       "  -t              Number of threads (accepted; the k-mers are counted on the GPU) [default: 12]\n";
+}
+
+static bool
+is_option(const char* a)
+{
+	return a[0] == '-' && a[1] != 0 && !(a[1] >= '0' && a[1] <= '9');
+}
+
+// a whole non-negative decimal number, or false
+static bool
+parse_u64(const char* s, uint64_t* out)
+{
+	if (!s || !*s || *s == '-' || *s == '+') {
+		return false;
+	}
+	char* end = nullptr;
+	errno = 0;
+	const unsigned long long v = strtoull(s, &end, 10);
+	if (errno || *end) {
+		return false;
+	}
+	*out = v;
+	return true;
+}
+
+// page-locked batch buffers: the parser fills one while the GPU works on the other
+struct Batch
+{
+	char* p = nullptr;
+	size_t cap = 0, len = 0;
+	uint64_t bases = 0;
+	bool last = false;
+};
+
+class BatchFeeder
+{
+  public:
+	BatchFeeder(const std::vector<std::string>& files, unsigned k, size_t batch_bytes)
+	    : files_(files), k_(k), batch_bytes_(batch_bytes)
+	{
+		for (Batch& b : bufs_) {
+			free_.push_back(&b);
+		}
+		th_ = std::thread([this] { run_(); });
+	}
+	~BatchFeeder()
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			stop_ = true;
+		}
+		cv_.notify_all();
+		th_.join();
+		for (Batch& b : bufs_) {
+			ntedit_hip_host_free(b.p);
+		}
+	}
+	// the next filled batch (last = true: the input ends with it); nullptr after an error
+	Batch* take()
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		cv_.wait(lk, [this] { return !full_.empty() || failed_; });
+		if (failed_) {
+			return nullptr;
+		}
+		Batch* b = full_.front();
+		full_.pop_front();
+		return b;
+	}
+	void give_back(Batch* b)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			free_.push_back(b);
+		}
+		cv_.notify_all();
+	}
+	const std::string& error() const { return err_; }
+
+  private:
+	Batch* get_free_()
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		cv_.wait(lk, [this] { return !free_.empty() || stop_; });
+		if (stop_) {
+			return nullptr;
+		}
+		Batch* b = free_.front();
+		free_.pop_front();
+		b->len = 0;
+		b->bases = 0;
+		b->last = false;
+		return b;
+	}
+	void put_full_(Batch* b)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			full_.push_back(b);
+		}
+		cv_.notify_all();
+	}
+	void fail_(const std::string& why)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			err_ = why;
+			failed_ = true;
+		}
+		cv_.notify_all();
+	}
+	bool reserve_(Batch* b, size_t need)
+	{
+		if (need <= b->cap) {
+			return true;
+		}
+		const size_t cap = need > batch_bytes_ ? need : batch_bytes_;
+		char* p = (char*)ntedit_hip_host_alloc(cap);
+		if (!p) {
+			return false;
+		}
+		if (b->len) {
+			memcpy(p, b->p, b->len);
+		}
+		ntedit_hip_host_free(b->p);
+		b->p = p;
+		b->cap = cap;
+		return true;
+	}
+	void run_()
+	{
+		Batch* b = get_free_();
+		std::string hdr, seq;
+		for (const std::string& f : files_) {
+			if (!b) {
+				return;
+			}
+			nte_host::FastaReader reader(f.c_str());
+			if (!reader.ok()) {
+				fail_("cannot open " + f);
+				return;
+			}
+			for (;;) {
+				seq.clear();
+				if (!reader.next(hdr, seq)) {
+					break;
+				}
+				if (seq.size() < k_) { // no k-mer in it
+					continue;
+				}
+				// reads are separated by '\n' (no k-mer spans a separator)
+				if (b->len && b->len + seq.size() + 1 > batch_bytes_) {
+					put_full_(b);
+					if (!(b = get_free_())) {
+						return;
+					}
+				}
+				if (!reserve_(b, b->len + seq.size() + 1)) {
+					fail_("cannot allocate page-locked host memory");
+					return;
+				}
+				memcpy(b->p + b->len, seq.data(), seq.size());
+				b->p[b->len + seq.size()] = '\n';
+				b->len += seq.size() + 1;
+				b->bases += seq.size();
+			}
+			if (reader.io_error()) {
+				fail_(f + ": " + reader.io_error_text());
+				return;
+			}
+		}
+		if (b) {
+			b->last = true;
+			put_full_(b);
+		}
+	}
+
+	std::vector<std::string> files_;
+	unsigned k_;
+	size_t batch_bytes_;
+	Batch bufs_[2];
+	std::deque<Batch*> free_, full_;
+	bool stop_ = false, failed_ = false;
+	std::string err_;
+	std::mutex mu_;
+	std::condition_variable cv_;
+	std::thread th_;
+};
+
+static void
+die(ntedit_hip_ctx* ctx, const std::string& why)
+{
+	std::cerr << "make_reads_bf: error: " << why << std::endl;
+	if (ctx) {
+		ntedit_hip_sketch_free(ctx);
+		ntedit_hip_destroy(ctx);
+	}
+	exit(1);
+}
+
+// one pass over every input file; pass 1 counts, pass 2 inserts the solid k-mers
+static void
+run_pass(ntedit_hip_ctx* ctx, int pass, const std::vector<std::string>& files, unsigned k, size_t batch_bytes, unsigned cmin)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	uint64_t bases = 0;
+	double gpu_ms = 0.0;
+	{
+		BatchFeeder feed(files, k, batch_bytes);
+		for (;;) {
+			Batch* b = feed.take();
+			if (!b) {
+				die(ctx, feed.error());
+			}
+			const auto g0 = std::chrono::steady_clock::now();
+			int rc = 0;
+			if (b->len) { // (an input without any read of k bases ends in an empty batch)
+				rc = pass == 1 ? ntedit_hip_sketch_count(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
+				               : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, b->p, b->len, NTEDIT_HIP_BASES_HOST, cmin);
+			}
+			if (rc) {
+				die(ctx, ntedit_hip_reads_last_error(ctx));
+			}
+			gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
+			bases += b->bases;
+			const bool last = b->last;
+			feed.give_back(b);
+			if (last) {
+				break;
+			}
+		}
+	}
+	const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	char line[256];
+	snprintf(line, sizeof line, "Pass %d (%s): %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", pass,
+	         pass == 1 ? "count" : "solid k-mers", (unsigned long long)bases, ms, ms > 0 ? bases / ms / 1e6 : 0.0, gpu_ms,
+	         gpu_ms > 0 ? bases / gpu_ms / 1e6 : 0.0);
+	log_info(line);
+}
+
+int
+main(int argc, char** argv)
+{
+	std::vector<std::string> read_files;
+	uint64_t k = 0, cmin = 0, hashes = 3, num_threads = 12, bf_bytes = 0, num_elements = 0, sketch_bytes = 0;
+	uint64_t batch_bytes = BATCH_DEFAULT;
+	bool have_k = false, have_c = false, have_bf = false, have_ne = false, counts = false;
+	double fpr = 0.01;
+	std::string out_file, sketch_out;
+	for (int i = 1; i < argc; i++) {
+		const std::string a = argv[i];
+		auto value = [&](const char* name) -> const char* {
+			if (i + 1 >= argc) {
+				usage((std::string("Too few arguments for '") + name + "'.").c_str());
+				exit(1);
+			}
+			return argv[++i];
+		};
+		auto number = [&](const char* name) -> uint64_t {
+			const char* v = value(name);
+			uint64_t x = 0;
+			if (!parse_u64(v, &x)) {
+				usage((std::string(name) + ": not a number: '" + v + "'").c_str());
+				exit(1);
+			}
+			return x;
+		};
+		if (a == "-h" || a == "--help") {
+			usage(nullptr);
+			return 0;
+		} else if (a == "--reads") {
+			while (i + 1 < argc && !is_option(argv[i + 1])) {
+				read_files.push_back(argv[++i]);
+			}
+		} else if (a == "-k") {
+			k = number("-k");
+			have_k = true;
+		} else if (a == "-c") {
+			cmin = number("-c");
+			have_c = true;
+		} else if (a == "--counts") {
+			counts = true;
+		} else if (a == "--hashes") {
+			hashes = number("--hashes");
+		} else if (a == "--fpr") {
+			char* end = nullptr;
+			const char* v = value("--fpr");
+			fpr = strtod(v, &end);
+			if (*end || !(fpr > 0.0 && fpr < 1.0)) {
+				usage((std::string("--fpr: needs a number between 0 and 1: '") + v + "'").c_str());
+				return 1;
+			}
+		} else if (a == "--bf") {
+			bf_bytes = number("--bf");
+			have_bf = true;
+		} else if (a == "--num_elements") {
+			num_elements = number("--num_elements");
+			have_ne = true;
+		} else if (a == "--sketch_bytes") {
+			sketch_bytes = number("--sketch_bytes");
+		} else if (a == "--batch_bytes") { // (not in the usage text: tests force many small batches with it)
+			batch_bytes = number("--batch_bytes");
+		} else if (a == "--save_sketch") { // (not in the usage text: tests compare the sketch itself)
+			sketch_out = value("--save_sketch");
+		} else if (a == "-o") {
+			out_file = value("-o");
+		} else if (a == "-t") {
+			num_threads = number("-t");
+		} else {
+			usage(("Unknown argument: " + a).c_str());
+			return 1;
+		}
+	}
+	if (read_files.empty()) {
+		usage("--reads: 1 or more argument(s) expected. 0 provided.");
+		return 1;
+	}
+	if (!have_k) {
+		usage("-k: required.");
+		return 1;
+	}
+	if (k < 12 || k > 200) {
+		usage(("-k " + std::to_string(k) + ": k must be between 12 and 200.").c_str());
+		return 1;
+	}
+	if (!have_c) {
+		usage("-c: required.");
+		return 1;
+	}
+	if (cmin < 1 || cmin > 255) {
+		usage(("-c " + std::to_string(cmin) + ": the minimum count must be between 1 and 255.").c_str());
+		return 1;
+	}
+	if (hashes < 1 || hashes > 8) {
+		usage(("--hashes " + std::to_string(hashes) + ": the number of hash functions must be between 1 and 8.").c_str());
+		return 1;
+	}
+	if (!have_bf && !have_ne) {
+		usage("--bf or --num_elements: one of them is required (no automatic sizing from a k-mer histogram).");
+		return 1;
+	}
+	if (batch_bytes < 4096) {
+		usage("--batch_bytes: at least 4096.");
+		return 1;
+	}
+	if (out_file.empty()) {
+		out_file = "reads_k" + std::to_string(k) + ".bf";
+	}
+
+	std::cout << "Parameters:" << std::endl;
+	std::cout << "\t\t--reads ";
+	for (const std::string& r : read_files) {
+		std::cout << r << " ";
+	}
+	std::cout << std::endl;
+	std::cout << "\t\t-t " << num_threads << std::endl;
+	std::cout << "\t\t-k " << k << std::endl;
+	std::cout << "\t\t-c " << cmin << std::endl;
+	std::cout << "\t\t--fpr " << fpr << std::endl;
+	std::cout << "\t\t--hashes " << hashes << std::endl;
+	std::cout << "\t\t-o " << out_file << std::endl;
+	if (counts) {
+		std::cout << "\t\t--counts" << std::endl;
+	}
+	uint64_t bf_size;
+	if (have_bf) {
+		bf_size = bf_bytes;
+		std::cout << "\t\t--bf " << bf_size << std::endl;
+	} else {
+		std::cout << "\t\t--num_elements " << num_elements << std::endl;
+		bf_size = get_bf_size(num_elements, (double)hashes, fpr);
+	}
+	if (bf_size == 0) {
+		usage("The output filter would be empty (--bf 0 or --num_elements too small).");
+		return 1;
+	}
+	std::cout << "BF size (bytes): " << bf_size << std::endl;
+	if (sketch_bytes == 0) {
+		sketch_bytes = bf_size > SKETCH_MAX / SKETCH_PER_OUTPUT_BYTE ? SKETCH_MAX : bf_size * SKETCH_PER_OUTPUT_BYTE;
+		sketch_bytes = sketch_bytes < SKETCH_MIN ? SKETCH_MIN : sketch_bytes;
+	}
+	std::cout << "Sketch size (counters): " << sketch_bytes << std::endl;
+
+	ntedit_hip_ctx* ctx = nullptr;
+	if (ntedit_hip_create(0, &ctx) != 0) {
+		std::cerr << "make_reads_bf: error: " << (ctx ? ntedit_hip_last_error(ctx) : "no HIP device") << std::endl;
+		return 1;
+	}
+	if (ntedit_hip_sketch_alloc(ctx, sketch_bytes, (uint32_t)hashes, (uint32_t)k) != 0) {
+		die(ctx, ntedit_hip_reads_last_error(ctx));
+	}
+	const size_t batch = (size_t)batch_bytes;
+	log_info("Pass 1: counting k-mers");
+	run_pass(ctx, 1, read_files, (unsigned)k, batch, (unsigned)cmin);
+	uint64_t nonzero = 0, counters = 0;
+	if (ntedit_hip_sketch_occupancy(ctx, &nonzero, &counters) != 0) {
+		die(ctx, ntedit_hip_reads_last_error(ctx));
+	}
+	std::cout << "Sketch occupancy: " << nonzero << " / " << counters << " counters ("
+	          << (double)nonzero / (double)counters << ")" << std::endl;
+	if (!sketch_out.empty() && ntedit_hip_sketch_save_file(ctx, sketch_out.c_str()) != 0) {
+		die(ctx, ntedit_hip_reads_last_error(ctx));
+	}
+
+	const int rc = counts ? ntedit_hip_filter_alloc_counting(ctx, NTEDIT_FILTER_PRIMARY, bf_size, (uint32_t)hashes, (uint32_t)k)
+	                      : ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, (uint32_t)hashes, (uint32_t)k);
+	if (rc != 0) {
+		die(ctx, counts ? ntedit_hip_reads_last_error(ctx) : ntedit_hip_last_error(ctx));
+	}
+	log_info("Pass 2: inserting k-mers seen at least " + std::to_string(cmin) + " times");
+	run_pass(ctx, 2, read_files, (unsigned)k, batch, (unsigned)cmin);
+	ntedit_hip_sketch_free(ctx);
+
+	uint64_t occupied = 0, slots = 0;
+	if (ntedit_hip_filter_occupancy(ctx, NTEDIT_FILTER_PRIMARY, &occupied, &slots) != 0) {
+		die(ctx, ntedit_hip_last_error(ctx));
+	}
+	// btllib get_fpr(): occupancy ^ hash_num
+	std::cout << "Bloom filter FPR: " << pow((double)occupied / (double)slots, (double)hashes) << std::endl;
+
+	log_info(counts ? "Saving counting Bloom filter" : "Saving Bloom filter");
+	if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, out_file.c_str()) != 0) {
+		die(ctx, "cannot write " + out_file);
+	}
+	log_info("Done!");
+	ntedit_hip_destroy(ctx);
+	return 0;
+}
