@@ -151,6 +151,22 @@ void ntedit_hip_sketch_free(ntedit_hip_ctx* ctx);
 int ntedit_hip_filter_alloc_counting(ntedit_hip_ctx* ctx, int slot, uint64_t nbytes, uint32_t hash_num, uint32_t k);
 int ntedit_hip_filter_insert_solid(ntedit_hip_ctx* ctx, int slot, const char* bases, uint64_t n, int on_device, uint32_t cmin);
 const char* ntedit_hip_reads_last_error(const ntedit_hip_ctx* ctx);
+/* k-mer histogram of the read set, from the sketch (after pass 1 over the same inputs; --solid / --hist of the tool):
+ *   ntedit_hip_sketch_histogram takes batches exactly as ntedit_hip_sketch_count and adds 1 to bin est(x) of the
+ *           context's histogram for every k-mer occurrence x: occ[e] = occurrences whose estimate is e (e in 0..255;
+ *           after pass 1 over the same inputs occ[0] = 0).  ntedit_hip_sketch_alloc zeroes it.  Integer sums: the
+ *           result is bit-for-bit independent of batching, input form and order.
+ * Two host-only calls (no device needed; failures are reported by ntedit_hip_reads_last_error(NULL)):
+ *   ntedit_hip_reads_hist_summary: F1 = sum of occ[e] over e = 0..255 (the number of k-mer occurrences);
+ *           f[c] = (occ[c] + c/2) / c in integer arithmetic for c = 1..255, f[0] = 0 (bin 255 means "255 or more",
+ *           so f[255] is an upper bound on the distinct k-mers in it); F0 = sum of f[c].
+ *   ntedit_hip_reads_solid_cutoff: the smallest c in [1, 253] with f[c+1] > f[c] (strictly), the first valley after
+ *           the error peak; NTEDIT_E_ARG when there is none.  This is the project's own rule, not ntStat's model fit,
+ *           and the counts are count-min estimates, not ntCard's. */
+int ntedit_hip_sketch_histogram(ntedit_hip_ctx* ctx, const char* bases, uint64_t n, int on_device);
+int ntedit_hip_sketch_histogram_download(ntedit_hip_ctx* ctx, uint64_t occ[256]);
+int ntedit_hip_reads_hist_summary(const uint64_t occ[256], uint64_t f[256], uint64_t* F0, uint64_t* F1);
+int ntedit_hip_reads_solid_cutoff(const uint64_t f[256], uint32_t* cmin);
 
 
 /* ---- hot path ------------------------------------------------------------

@@ -111,7 +111,8 @@ EXPORTS = [
     "ntedit_hip_fasta_free", "ntedit_hip_result_cuts_ok", "ntedit_hip_reserve",
     "ntedit_hip_sketch_alloc", "ntedit_hip_sketch_count", "ntedit_hip_sketch_occupancy", "ntedit_hip_sketch_download",
     "ntedit_hip_sketch_save_file", "ntedit_hip_sketch_free", "ntedit_hip_filter_alloc_counting",
-    "ntedit_hip_filter_insert_solid", "ntedit_hip_reads_last_error",
+    "ntedit_hip_filter_insert_solid", "ntedit_hip_reads_last_error", "ntedit_hip_sketch_histogram",
+    "ntedit_hip_sketch_histogram_download", "ntedit_hip_reads_hist_summary", "ntedit_hip_reads_solid_cutoff",
 ]
 
 _lib = None
@@ -212,5 +213,9 @@ def load():
     lib.ntedit_hip_filter_insert_solid.argtypes = [vp, ci, vp, u64, ci, u32]
     lib.ntedit_hip_reads_last_error.argtypes = [vp]
     lib.ntedit_hip_reads_last_error.restype = ctypes.c_char_p
+    lib.ntedit_hip_sketch_histogram.argtypes = [vp, vp, u64, ci]
+    lib.ntedit_hip_sketch_histogram_download.argtypes = [vp, vp]
+    lib.ntedit_hip_reads_hist_summary.argtypes = [vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.ntedit_hip_reads_solid_cutoff.argtypes = [vp, ctypes.POINTER(u32)]
     _lib = lib
     return lib

@@ -5,6 +5,8 @@
 //   k_solid<H, POW2, COUNTS>  pass 2: est(x) = min of x's h sketch counters; a k-mer with est(x) >= cmin sets its h
 //                             bits in a plain output filter, or raises its h counters of a counting output filter to
 //                             est(x) (byte atomic max)
+//   k_hist<H, POW2>           histogram pass: bin est(x) of a 256-bin histogram of every k-mer occurrence, summed in
+//                             per-wave LDS sub-histograms and flushed once per block (one 64-bit add per non-zero bin)
 //   k_nonzero                 non-zero counters of the sketch (occupancy)
 //
 // k-mers, hashes and slots are the filter build's (k_screen<., ., true> in nte_kernels.hip): runs of k bytes of
@@ -60,7 +62,7 @@ struct RdFilter // one filter as the reads kernels address it
 	Filter f; // geometry only (f.data unused)
 };
 
-// prologue shared by both kernels: seed tables + LUT in LDS, the tile's codes staged
+// prologue shared by the walking kernels: seed tables + LUT in LDS, the tile's codes staged
 __device__ __forceinline__ void
 rd_stage(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, u64* s_tab, u8* s_lut, u8* s_codes)
 {
@@ -146,12 +148,28 @@ byte_max(u32* words, u64 s, u32 v)
 	}
 }
 
-// ------------------------------------------------------------------ k_count / k_solid
+// est(x): the minimum of x's h sketch counters (k_solid, k_hist)
+template<int H, bool POW2>
+__device__ __forceinline__ u32
+rd_est(const u8* sk_bytes, const Filter& f, const u64 (&hv)[H])
+{
+	u32 est = 255;
+#pragma unroll
+	for (int i = 0; i < H; i++) {
+		const u32 c = sk_bytes[rd_slot<POW2>(f, hv[i])];
+		est = c < est ? c : est;
+	}
+	return est;
+}
+
+// ------------------------------------------------------------------ k_count / k_solid / k_hist
 // One thread walks 64 consecutive k-mer starts of the tile.  The hash state is exact once k codes of ACGT have
 // entered since the last RD_BAD (an RD_BAD code has zero seeds both ways, so it leaves nothing behind).
-template<int H, bool POW2, int PASS> // PASS 0: k_count; 1: k_solid into bits; 2: k_solid into counters
+// PASS 0: k_count; 1: k_solid into bits; 2: k_solid into counters; 3: k_hist into s_hist (this wave's 256 bins)
+template<int H, bool POW2, int PASS>
 __device__ __forceinline__ void
-rd_walk(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, const DevParams& p, RdFilter sk, RdFilter out, u32 cmin)
+rd_walk(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, const DevParams& p, RdFilter sk, RdFilter out, u32 cmin,
+        u32* s_hist)
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
@@ -180,13 +198,10 @@ rd_walk(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, 
 				for (int i = 0; i < H; i++) {
 					sat_inc(sk.words, rd_slot<POW2>(sk.f, hv[i]));
 				}
+			} else if (PASS == 3) {
+				atomicAdd(&s_hist[rd_est<H, POW2>(sk_bytes, sk.f, hv)], 1u);
 			} else {
-				u32 est = 255;
-#pragma unroll
-				for (int i = 0; i < H; i++) {
-					const u32 c = sk_bytes[rd_slot<POW2>(sk.f, hv[i])];
-					est = c < est ? c : est;
-				}
+				const u32 est = rd_est<H, POW2>(sk_bytes, sk.f, hv);
 				if (est >= cmin) {
 #pragma unroll
 					for (int i = 0; i < H; i++) {
@@ -215,14 +230,42 @@ template<int H, bool POW2>
 __global__ __launch_bounds__(RD_TPB) void
 k_count(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk)
 {
-	rd_walk<H, POW2, 0>(seq, n, k, tabs, p, sk, sk, 0);
+	rd_walk<H, POW2, 0>(seq, n, k, tabs, p, sk, sk, 0, nullptr);
 }
 
 template<int H, bool POW2, bool COUNTS>
 __global__ __launch_bounds__(RD_TPB) void
 k_solid(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk, RdFilter out, u32 cmin)
 {
-	rd_walk<H, POW2, COUNTS ? 2 : 1>(seq, n, k, tabs, p, sk, out, cmin);
+	rd_walk<H, POW2, COUNTS ? 2 : 1>(seq, n, k, tabs, p, sk, out, cmin, nullptr);
+}
+
+// Occurrences crowd into a few bins near the coverage peak, so each wave adds into a sub-histogram of its own: a
+// block's adds are one LDS atomic per k-mer, and its global traffic one 64-bit add per non-zero bin.  A tile holds
+// 16384 k-mer starts, so 32-bit bins cannot overflow.  The sums are integers: the result is independent of order.
+constexpr int RD_HIST_BINS = 256;
+constexpr int RD_HIST_SUBS = RD_TPB / 64;
+
+template<int H, bool POW2>
+__global__ __launch_bounds__(RD_TPB) void
+k_hist(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk, unsigned long long* hist)
+{
+	__shared__ u32 s_hist[RD_HIST_SUBS * RD_HIST_BINS];
+	for (u32 i = threadIdx.x; i < RD_HIST_SUBS * RD_HIST_BINS; i += RD_TPB) {
+		s_hist[i] = 0;
+	}
+	// (rd_stage's barriers order the zeroing before any add)
+	rd_walk<H, POW2, 3>(seq, n, k, tabs, p, sk, sk, 0, s_hist + (threadIdx.x / 64) * RD_HIST_BINS);
+	__syncthreads();
+	static_assert(RD_TPB == RD_HIST_BINS, "one thread per bin flushes");
+	u32 sum = 0;
+#pragma unroll
+	for (int w = 0; w < RD_HIST_SUBS; w++) {
+		sum += s_hist[w * RD_HIST_BINS + threadIdx.x];
+	}
+	if (sum) {
+		atomicAdd(&hist[threadIdx.x], (unsigned long long)sum);
+	}
 }
 
 // non-zero bytes of an array of n_words 64-bit words (allocations are whole words, zero behind the counters)
@@ -265,6 +308,7 @@ struct ReadsState
 	u8* d_seq = nullptr; // staging of host batches (grow-only)
 	u64 seq_cap = 0;
 	unsigned long long* d_total = nullptr;
+	unsigned long long* d_hist = nullptr; // 256 bins of k_hist (zeroed at ntedit_hip_sketch_alloc)
 	std::string err;
 };
 
@@ -319,7 +363,7 @@ release_state(ReadsState* s)
 		(void)hipStreamSynchronize(s->stream);
 		(void)hipStreamDestroy(s->stream);
 	}
-	for (void* p : { (void*)s->sketch, (void*)s->d_tab, (void*)s->d_seq, (void*)s->d_total }) {
+	for (void* p : { (void*)s->sketch, (void*)s->d_tab, (void*)s->d_seq, (void*)s->d_total, (void*)s->d_hist }) {
 		if (p) {
 			(void)hipFree(p);
 		}
@@ -373,8 +417,11 @@ launch_walk(ReadsState* s, const u8* d_seq, u64 n, u64 tiles, RdFilter sk, RdFil
 	dim3 grid((unsigned)tiles), block(RD_TPB);
 #define RD_LAUNCH(H)                                                                                               \
 	case H:                                                                                                        \
-		if (PASS == 0) {                                                                                           \
+		if constexpr (PASS == 0) {                                                                                 \
 			hipLaunchKernelGGL((k_count<H, POW2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, s->dp, sk); \
+		} else if constexpr (PASS == 3) {                                                                          \
+			hipLaunchKernelGGL((k_hist<H, POW2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, s->dp, sk,  \
+			                   s->d_hist);                                                                         \
 		} else {                                                                                                   \
 			hipLaunchKernelGGL((k_solid<H, POW2, PASS == 2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, \
 			                   s->dp, sk, out, cmin);                                                              \
@@ -419,8 +466,10 @@ run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int o
 		pow2 ? launch_walk<true, 0>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 0>(s, d_seq, n, tiles, sk, out, cmin);
 	} else if (pass == 1) {
 		pow2 ? launch_walk<true, 1>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 1>(s, d_seq, n, tiles, sk, out, cmin);
-	} else {
+	} else if (pass == 2) {
 		pow2 ? launch_walk<true, 2>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 2>(s, d_seq, n, tiles, sk, out, cmin);
+	} else {
+		pow2 ? launch_walk<true, 3>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 3>(s, d_seq, n, tiles, sk, out, cmin);
 	}
 	RD_TRY(c, hipGetLastError());
 	RD_TRY(c, hipStreamSynchronize(s->stream));
@@ -478,7 +527,13 @@ ntedit_hip_sketch_alloc(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num,
 		e = hipMalloc((void**)&s->d_total, 8);
 	}
 	if (e == hipSuccess && !rc) {
+		e = hipMalloc((void**)&s->d_hist, 256 * sizeof(unsigned long long));
+	}
+	if (e == hipSuccess && !rc) {
 		e = hipMemsetAsync(s->sketch, 0, s->counters, s->stream);
+	}
+	if (e == hipSuccess && !rc) {
+		e = hipMemsetAsync(s->d_hist, 0, 256 * sizeof(unsigned long long), s->stream);
 	}
 	if (e == hipSuccess && !rc) {
 		e = hipMemcpyAsync(s->d_tab, tab, sizeof tab, hipMemcpyHostToDevice, s->stream);
@@ -529,6 +584,66 @@ ntedit_hip_sketch_count(ntedit_hip_ctx* c, const char* bases, uint64_t n, int on
 	}
 	RdFilter none = {};
 	return run_pass(c, s, bases, n, on_device, 0, none, 0);
+}
+
+int
+ntedit_hip_sketch_histogram(ntedit_hip_ctx* c, const char* bases, uint64_t n, int on_device)
+{
+	ReadsState* s = find_state(c);
+	if (!c || !bases) {
+		return c ? rfail(c, NTEDIT_E_ARG, "sketch_histogram: bad argument") : NTEDIT_E_ARG;
+	}
+	if (!s) {
+		return rfail(c, NTEDIT_E_ARG, "sketch_histogram: no sketch (ntedit_hip_sketch_alloc)");
+	}
+	RdFilter none = {};
+	return run_pass(c, s, bases, n, on_device, 3, none, 0);
+}
+
+int
+ntedit_hip_sketch_histogram_download(ntedit_hip_ctx* c, uint64_t occ[256])
+{
+	ReadsState* s = find_state(c);
+	if (!s || !occ) {
+		return c ? rfail(c, NTEDIT_E_ARG, "sketch_histogram_download: bad argument or no sketch") : NTEDIT_E_ARG;
+	}
+	static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit bins");
+	RD_TRY(c, hipSetDevice(s->device));
+	RD_TRY(c, hipMemcpy(occ, s->d_hist, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int
+ntedit_hip_reads_hist_summary(const uint64_t occ[256], uint64_t f[256], uint64_t* F0, uint64_t* F1)
+{
+	if (!occ || !f || !F0 || !F1) {
+		return rfail(nullptr, NTEDIT_E_ARG, "reads_hist_summary: bad argument");
+	}
+	uint64_t f0 = 0, f1 = occ[0];
+	f[0] = 0;
+	for (uint64_t c = 1; c < 256; c++) {
+		f1 += occ[c];
+		f[c] = (occ[c] + c / 2) / c;
+		f0 += f[c];
+	}
+	*F0 = f0;
+	*F1 = f1;
+	return 0;
+}
+
+int
+ntedit_hip_reads_solid_cutoff(const uint64_t f[256], uint32_t* cmin)
+{
+	if (!f || !cmin) {
+		return rfail(nullptr, NTEDIT_E_ARG, "reads_solid_cutoff: bad argument");
+	}
+	for (uint32_t c = 1; c <= 253; c++) {
+		if (f[c + 1] > f[c]) {
+			*cmin = c;
+			return 0;
+		}
+	}
+	return rfail(nullptr, NTEDIT_E_ARG, "reads_solid_cutoff: the k-mer histogram has no valley (no c in [1, 253] with f[c+1] > f[c])");
 }
 
 int

@@ -1,7 +1,7 @@
 // make_reads_bf.cpp -- `ntedit-make-reads-bf`: the k-mer filter of a read set, built on one MI355X, for `ntedit -r`.
 //
-//   --reads FILE [FILE ...]  -k K  -c CMIN  [--counts]  [--hashes 3]  [--fpr 0.01]
-//   (--bf BYTES | --num_elements N)  [--sketch_bytes S]  [-o reads_kK.bf]  [-t THREADS]
+//   --reads FILE [FILE ...]  -k K  (-c CMIN | --solid)  [--hist FILE]  [--counts]  [--hashes 3]  [--fpr 0.01]
+//   [--bf BYTES | --num_elements N]  [--sketch_bytes S]  [-o reads_kK.bf]  [-t THREADS]
 //
 // The reference leaves this step to ntHits / ntStat on the CPU (ntedit-make: `nthits -c<cutoff> --outbloom`;
 // ntedit_run_pipeline.smk: `ntstat filter -cmin C`).  This tool is neither: it counts in a plain count-min sketch of
@@ -11,6 +11,11 @@
 // a counting filter holding each solid k-mer's estimate (for ntedit -p / -q).  Both passes read the inputs (FASTA or
 // FASTQ, plain or gzip) through FastaReader, in bounded batches double-buffered through page-locked memory: a second
 // thread parses the next batch while the GPU works on the current one.
+//
+// With --solid or --hist a histogram pass runs between the two (ntedit_hip_sketch_histogram): the k-mer histogram of
+// the sketch's estimates, in place of the reference's ntCard run.  --hist writes it in ntCard's text format, --solid
+// takes CMIN from its first valley (ntedit_hip_reads_solid_cutoff), and without --bf / --num_elements the output is
+// sized from it: --num_elements N with N = the distinct k-mers the histogram puts at CMIN or above.
 #include "../../include/ntedit_hip.h"
 #include "fasta.h"
 
@@ -28,6 +33,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <sys/stat.h>
 
 static void
 log_info(const std::string& msg)
@@ -48,8 +55,10 @@ get_bf_size(uint64_t num_elements, double num_hashes, double fpr)
 	return m;
 }
 
-// default sketch: 16 output bytes' worth of counters, within [64 MiB, 32 GiB]
+// default sketch: 16 output bytes' worth of counters, within [64 MiB, 32 GiB]; sized from the histogram (the output
+// size not known yet): one counter per input byte, a gzip file counted at 4 x its size, within the same bounds
 static const uint64_t SKETCH_PER_OUTPUT_BYTE = 16;
+static const uint64_t GZIP_INPUT_FACTOR = 4;
 static const uint64_t SKETCH_MIN = 64ull << 20;
 static const uint64_t SKETCH_MAX = 32ull << 30;
 static const uint64_t BATCH_DEFAULT = 256ull << 20;
@@ -61,23 +70,31 @@ usage(const char* why)
 		std::cerr << why << std::endl;
 	}
 	std::cerr
-	    << "Usage: make_reads_bf [--help] --reads VAR... -k VAR -c VAR [--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] "
-	       "[--num_elements VAR] [--sketch_bytes VAR] [-o VAR] [-t VAR]\n\n"
+	    << "Usage: make_reads_bf [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] [--counts] [--hashes VAR] "
+	       "[--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [-o VAR] [-t VAR]\n\n"
 	       "Builds the k-mer filter of a read set on the GPU: pass 1 counts every k-mer in a count-min sketch of 8-bit\n"
 	       "counters, pass 2 keeps the k-mers whose estimate (the minimum of their counters) is at least -c.  Neither\n"
-	       "ntHits nor ntStat: the counts (plain count-min, no conservative update) and the sizing are this tool's own.\n\n"
+	       "ntHits nor ntStat: the counts (plain count-min, no conservative update) and the sizing are this tool's own.\n"
+	       "With --solid or --hist a histogram pass between them gathers the k-mer histogram of the estimates.  Neither\n"
+	       "ntCard nor ntStat: --solid's cutoff is the first c with f[c+1] > f[c], this tool's own rule, not a model fit.\n\n"
 	       "Optional arguments:\n"
 	       "  -h, --help      shows help message and exits\n"
 	       "  --reads         Input reads, FASTA or FASTQ, plain or gzip [nargs: 1 or more] [required]\n"
 	       "  -k              k-mer size (bp), 12 to 200 [required]\n"
-	       "  -c              Minimum k-mer count (cmin), 1 to 255 [required]\n"
+	       "  -c              Minimum k-mer count (cmin), 1 to 255 [required, unless --solid]\n"
+	       "  --solid         Take cmin from the k-mer histogram: the first c with f[c+1] > f[c] (the valley after\n"
+	       "                  the error peak); refused when there is none\n"
+	       "  --hist          Write the k-mer histogram to this file, in ntCard's text format (F1, F0, then c and f[c]\n"
+	       "                  for c = 1 to 255; the last bin counts 255 or more, ntCard stops at 64)\n"
 	       "  --counts        Write a counting filter (each solid k-mer's estimate) for ntedit -p / -q\n"
 	       "  --hashes        Number of hash functions, 1 to 8 [default: 3]\n"
 	       "  --fpr           False positive rate for Bloom filter (with --num_elements) [default: 0.01]\n"
 	       "  --bf            Output filter size in bytes\n"
 	       "  --num_elements  Approximate number of solid k-mers (output size through the genome tool's formula)\n"
-	       "                  (one of --bf / --num_elements is required)\n"
-	       "  --sketch_bytes  Counters of the count-min sketch [default: 16 x the output bytes, 64 MiB to 32 GiB]\n"
+	       "                  (one of --bf / --num_elements is required, unless --solid or --hist: then by default\n"
+	       "                  --num_elements is the number of k-mers the histogram puts at cmin or above)\n"
+	       "  --sketch_bytes  Counters of the count-min sketch [default: 16 x the output bytes, or sized from the\n"
+	       "                  histogram one per input byte (gzip: 4 x), 64 MiB to 32 GiB]\n"
 	       "  -o              Name for output filter [default: \"reads_k<K>.bf\"]\n"
 	       "  -t              Number of threads (accepted; the k-mers are counted on the GPU) [default: 12]\n";
 }
@@ -280,9 +297,16 @@ die(ntedit_hip_ctx* ctx, const std::string& why)
 	exit(1);
 }
 
-// one pass over every input file; pass 1 counts, pass 2 inserts the solid k-mers
+enum Pass
+{
+	PASS_COUNT,  // pass 1: count every k-mer into the sketch
+	PASS_HIST,   // histogram pass (--solid / --hist): bin every k-mer's estimate
+	PASS_SOLID,  // pass 2: insert the k-mers whose estimate is >= cmin
+};
+
+// one pass over every input file
 static void
-run_pass(ntedit_hip_ctx* ctx, int pass, const std::vector<std::string>& files, unsigned k, size_t batch_bytes, unsigned cmin)
+run_pass(ntedit_hip_ctx* ctx, Pass pass, const std::vector<std::string>& files, unsigned k, size_t batch_bytes, unsigned cmin)
 {
 	const auto t0 = std::chrono::steady_clock::now();
 	uint64_t bases = 0;
@@ -297,8 +321,10 @@ run_pass(ntedit_hip_ctx* ctx, int pass, const std::vector<std::string>& files, u
 			const auto g0 = std::chrono::steady_clock::now();
 			int rc = 0;
 			if (b->len) { // (an input without any read of k bases ends in an empty batch)
-				rc = pass == 1 ? ntedit_hip_sketch_count(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
-				               : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, b->p, b->len, NTEDIT_HIP_BASES_HOST, cmin);
+				rc = pass == PASS_COUNT  ? ntedit_hip_sketch_count(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
+				     : pass == PASS_HIST ? ntedit_hip_sketch_histogram(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
+				                         : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, b->p, b->len,
+				                                                          NTEDIT_HIP_BASES_HOST, cmin);
 			}
 			if (rc) {
 				die(ctx, ntedit_hip_reads_last_error(ctx));
@@ -314,10 +340,49 @@ run_pass(ntedit_hip_ctx* ctx, int pass, const std::vector<std::string>& files, u
 	}
 	const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	char line[256];
-	snprintf(line, sizeof line, "Pass %d (%s): %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", pass,
-	         pass == 1 ? "count" : "solid k-mers", (unsigned long long)bases, ms, ms > 0 ? bases / ms / 1e6 : 0.0, gpu_ms,
+	static const char* const names[] = { "1 (count)", "H (histogram)", "2 (solid k-mers)" };
+	snprintf(line, sizeof line, "Pass %s: %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", names[pass],
+	         (unsigned long long)bases, ms, ms > 0 ? bases / ms / 1e6 : 0.0, gpu_ms,
 	         gpu_ms > 0 ? bases / gpu_ms / 1e6 : 0.0);
 	log_info(line);
+}
+
+// the default sketch when the output is sized from the histogram: one counter per input byte (gzip: 4 x its size);
+// an input that cannot be read counts 0 here and fails in pass 1
+static uint64_t
+input_bytes(const std::vector<std::string>& files)
+{
+	uint64_t total = 0;
+	for (const std::string& f : files) {
+		struct stat st;
+		if (stat(f.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
+			continue;
+		}
+		unsigned char magic[2] = { 0, 0 };
+		FILE* fp = fopen(f.c_str(), "rb");
+		const bool gz = fp && fread(magic, 1, 2, fp) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+		if (fp) {
+			fclose(fp);
+		}
+		total += (uint64_t)st.st_size * (gz ? GZIP_INPUT_FACTOR : 1);
+	}
+	return total;
+}
+
+// ntCard's histogram file: "F1\t<n>", "F0\t<n>", then "c\tf[c]" for c = 1..255 (zeros included)
+static bool
+write_hist(const std::string& path, const uint64_t f[256], uint64_t F0, uint64_t F1)
+{
+	FILE* fp = fopen(path.c_str(), "w");
+	if (!fp) {
+		return false;
+	}
+	fprintf(fp, "F1\t%llu\nF0\t%llu\n", (unsigned long long)F1, (unsigned long long)F0);
+	for (int c = 1; c < 256; c++) {
+		fprintf(fp, "%d\t%llu\n", c, (unsigned long long)f[c]);
+	}
+	const bool ok = !ferror(fp);
+	return fclose(fp) == 0 && ok;
 }
 
 int
@@ -326,9 +391,9 @@ main(int argc, char** argv)
 	std::vector<std::string> read_files;
 	uint64_t k = 0, cmin = 0, hashes = 3, num_threads = 12, bf_bytes = 0, num_elements = 0, sketch_bytes = 0;
 	uint64_t batch_bytes = BATCH_DEFAULT;
-	bool have_k = false, have_c = false, have_bf = false, have_ne = false, counts = false;
+	bool have_k = false, have_c = false, have_bf = false, have_ne = false, counts = false, solid = false;
 	double fpr = 0.01;
-	std::string out_file, sketch_out;
+	std::string out_file, sketch_out, hist_out;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto value = [&](const char* name) -> const char* {
@@ -360,6 +425,10 @@ main(int argc, char** argv)
 		} else if (a == "-c") {
 			cmin = number("-c");
 			have_c = true;
+		} else if (a == "--solid") {
+			solid = true;
+		} else if (a == "--hist") {
+			hist_out = value("--hist");
 		} else if (a == "--counts") {
 			counts = true;
 		} else if (a == "--hashes") {
@@ -405,11 +474,15 @@ main(int argc, char** argv)
 		usage(("-k " + std::to_string(k) + ": k must be between 12 and 200.").c_str());
 		return 1;
 	}
-	if (!have_c) {
-		usage("-c: required.");
+	if (solid && have_c) {
+		usage("--solid and -c: give one of them (--solid takes the minimum count from the k-mer histogram).");
 		return 1;
 	}
-	if (cmin < 1 || cmin > 255) {
+	if (!have_c && !solid) {
+		usage("-c: required (or --solid).");
+		return 1;
+	}
+	if (have_c && (cmin < 1 || cmin > 255)) {
 		usage(("-c " + std::to_string(cmin) + ": the minimum count must be between 1 and 255.").c_str());
 		return 1;
 	}
@@ -417,8 +490,11 @@ main(int argc, char** argv)
 		usage(("--hashes " + std::to_string(hashes) + ": the number of hash functions must be between 1 and 8.").c_str());
 		return 1;
 	}
-	if (!have_bf && !have_ne) {
-		usage("--bf or --num_elements: one of them is required (no automatic sizing from a k-mer histogram).");
+	const bool gather_hist = solid || !hist_out.empty();
+	const bool size_from_hist = !have_bf && !have_ne;
+	if (size_from_hist && !gather_hist) {
+		usage("--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter from the k-mer "
+		      "histogram).");
 		return 1;
 	}
 	if (batch_bytes < 4096) {
@@ -437,28 +513,44 @@ main(int argc, char** argv)
 	std::cout << std::endl;
 	std::cout << "\t\t-t " << num_threads << std::endl;
 	std::cout << "\t\t-k " << k << std::endl;
-	std::cout << "\t\t-c " << cmin << std::endl;
+	if (solid) {
+		std::cout << "\t\t--solid" << std::endl;
+	} else {
+		std::cout << "\t\t-c " << cmin << std::endl;
+	}
+	if (!hist_out.empty()) {
+		std::cout << "\t\t--hist " << hist_out << std::endl;
+	}
 	std::cout << "\t\t--fpr " << fpr << std::endl;
 	std::cout << "\t\t--hashes " << hashes << std::endl;
 	std::cout << "\t\t-o " << out_file << std::endl;
 	if (counts) {
 		std::cout << "\t\t--counts" << std::endl;
 	}
-	uint64_t bf_size;
+	uint64_t bf_size = 0;
 	if (have_bf) {
 		bf_size = bf_bytes;
 		std::cout << "\t\t--bf " << bf_size << std::endl;
-	} else {
+	} else if (have_ne) {
 		std::cout << "\t\t--num_elements " << num_elements << std::endl;
 		bf_size = get_bf_size(num_elements, (double)hashes, fpr);
 	}
-	if (bf_size == 0) {
+	if (!size_from_hist && bf_size == 0) {
 		usage("The output filter would be empty (--bf 0 or --num_elements too small).");
 		return 1;
 	}
-	std::cout << "BF size (bytes): " << bf_size << std::endl;
+	if (size_from_hist) {
+		std::cout << "BF size (bytes): from the k-mer histogram" << std::endl;
+	} else {
+		std::cout << "BF size (bytes): " << bf_size << std::endl;
+	}
 	if (sketch_bytes == 0) {
-		sketch_bytes = bf_size > SKETCH_MAX / SKETCH_PER_OUTPUT_BYTE ? SKETCH_MAX : bf_size * SKETCH_PER_OUTPUT_BYTE;
+		if (size_from_hist) {
+			sketch_bytes = input_bytes(read_files);
+			sketch_bytes = sketch_bytes > SKETCH_MAX ? SKETCH_MAX : sketch_bytes;
+		} else {
+			sketch_bytes = bf_size > SKETCH_MAX / SKETCH_PER_OUTPUT_BYTE ? SKETCH_MAX : bf_size * SKETCH_PER_OUTPUT_BYTE;
+		}
 		sketch_bytes = sketch_bytes < SKETCH_MIN ? SKETCH_MIN : sketch_bytes;
 	}
 	std::cout << "Sketch size (counters): " << sketch_bytes << std::endl;
@@ -473,7 +565,7 @@ main(int argc, char** argv)
 	}
 	const size_t batch = (size_t)batch_bytes;
 	log_info("Pass 1: counting k-mers");
-	run_pass(ctx, 1, read_files, (unsigned)k, batch, (unsigned)cmin);
+	run_pass(ctx, PASS_COUNT, read_files, (unsigned)k, batch, (unsigned)cmin);
 	uint64_t nonzero = 0, counters = 0;
 	if (ntedit_hip_sketch_occupancy(ctx, &nonzero, &counters) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));
@@ -484,13 +576,56 @@ main(int argc, char** argv)
 		die(ctx, ntedit_hip_reads_last_error(ctx));
 	}
 
+	if (gather_hist) {
+		log_info("Histogram pass: the k-mer histogram of the sketch's estimates");
+		run_pass(ctx, PASS_HIST, read_files, (unsigned)k, batch, (unsigned)cmin);
+		uint64_t occ[256], f[256], F0 = 0, F1 = 0;
+		if (ntedit_hip_sketch_histogram_download(ctx, occ) != 0) {
+			die(ctx, ntedit_hip_reads_last_error(ctx));
+		}
+		if (ntedit_hip_reads_hist_summary(occ, f, &F0, &F1) != 0) {
+			die(ctx, ntedit_hip_reads_last_error(nullptr));
+		}
+		log_info("k-mer histogram: F1 = " + std::to_string(F1) + " (k-mers), F0 = " + std::to_string(F0) +
+		         " (distinct k-mers)");
+		// written first: a refused --solid still leaves the histogram to look at
+		if (!hist_out.empty()) {
+			if (!write_hist(hist_out, f, F0, F1)) {
+				die(ctx, "cannot write " + hist_out);
+			}
+			log_info("Histogram written to " + hist_out);
+		}
+		if (solid) {
+			uint32_t c = 0;
+			if (ntedit_hip_reads_solid_cutoff(f, &c) != 0) {
+				die(ctx, "--solid: the k-mer histogram has no valley after the error peak (no c with f[c+1] > f[c]); "
+				         "pass -c");
+			}
+			cmin = c;
+			log_info("--solid: minimum k-mer count " + std::to_string(cmin));
+		}
+		if (size_from_hist) {
+			num_elements = 0;
+			for (uint64_t c = cmin; c < 256; c++) {
+				num_elements += f[c];
+			}
+			bf_size = get_bf_size(num_elements, (double)hashes, fpr);
+			log_info("Sized from the k-mer histogram: --num_elements " + std::to_string(num_elements) + " (k-mers at " +
+			         std::to_string(cmin) + " or above), " + std::to_string(bf_size) + " bytes");
+			if (bf_size == 0) {
+				die(ctx, "The output filter would be empty (no k-mer at the minimum count or above).");
+			}
+			std::cout << "BF size (bytes): " << bf_size << std::endl;
+		}
+	}
+
 	const int rc = counts ? ntedit_hip_filter_alloc_counting(ctx, NTEDIT_FILTER_PRIMARY, bf_size, (uint32_t)hashes, (uint32_t)k)
 	                      : ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, (uint32_t)hashes, (uint32_t)k);
 	if (rc != 0) {
 		die(ctx, counts ? ntedit_hip_reads_last_error(ctx) : ntedit_hip_last_error(ctx));
 	}
 	log_info("Pass 2: inserting k-mers seen at least " + std::to_string(cmin) + " times");
-	run_pass(ctx, 2, read_files, (unsigned)k, batch, (unsigned)cmin);
+	run_pass(ctx, PASS_SOLID, read_files, (unsigned)k, batch, (unsigned)cmin);
 	ntedit_hip_sketch_free(ctx);
 
 	uint64_t occupied = 0, slots = 0;
