@@ -167,6 +167,57 @@ int ntedit_hip_sketch_histogram(ntedit_hip_ctx* ctx, const char* bases, uint64_t
 int ntedit_hip_sketch_histogram_download(ntedit_hip_ctx* ctx, uint64_t occ[256]);
 int ntedit_hip_reads_hist_summary(const uint64_t occ[256], uint64_t f[256], uint64_t* F0, uint64_t* F1);
 int ntedit_hip_reads_solid_cutoff(const uint64_t f[256], uint32_t* cmin);
+/* Sharded builds (ntedit_amd/make_reads.py: each process counts its share of the reads, then the results merge):
+ *   ntedit_hip_sketch_set_device adopts `counters` bytes of device memory, owned by the caller, as the context's
+ *           sketch (counters a multiple of 8, the pointer 16-byte aligned; the caller zeroes it).  It replaces a sketch
+ *           the context held; ntedit_hip_sketch_free then releases the state but never adopted memory.
+ *   ntedit_hip_sketch_info: the sketch's counters, hash_num and k.
+ *   ntedit_hip_merge_bytes folds n_src chunks of n device bytes, srcs[i * n .. (i + 1) * n), into dst[0 .. n): OP_SAT_ADD
+ *           = min(255, sum) per byte (sketches), OP_OR (plain filters), OP_MAX (counting filters).  dst may be the first
+ *           chunk.  On the device of dst; returns once the merge is done.  The identities
+ *           min(255, sum_r min(255, c_r)) = min(255, sum_r c_r), OR of bits and max of estimates make the merge of
+ *           per-process results over any split of the reads the one-process result.
+ *   ntedit_hip_reads_pass: one pass of the tool (COUNT: pass 1, HIST: the histogram pass, SOLID: pass 2 into the
+ *           primary slot, as ntedit_hip_filter_insert_solid) over n byte ranges [begins[i], ends[i]) of files[i],
+ *           parsed as FASTA / FASTQ, plain or gzip, and fed to the GPU in batches of about batch_bytes.  A range owns
+ *           the records whose first byte lies in it; ends[i] = ~0 and begins[i] = 0 read a whole file (the only form
+ *           a gzip file takes).  starts[i] (may be NULL) receives where range i's first record starts (0 for
+ *           begins[i] = 0; a range past byte 0 moves forward to a line that starts with '>' in FASTA, or with '@'
+ *           and whose line + 2 starts with '+' in FASTQ), nexts[i] (may be NULL) where its reader stopped: the
+ *           first record start at or past ends[i], the end of the file, or ~0 after a record that failed to parse.
+ *           Consecutive ranges of a file read it as one reader would exactly when nexts[i] = starts[i + 1].
+ * Host-only calls of the tool (no device; failures through ntedit_hip_reads_last_error(NULL)):
+ *   ntedit_hip_reads_range_text: the reads of one range, each followed by '\n', into out[0 .. cap) (*len: the bytes
+ *           they take; NTEDIT_E_OVERFLOW when that is more than cap), *reads: their number, *start / *next as above.
+ *   ntedit_hip_reads_bf_size: ntedit-make-genome-bf's output bytes for num_elements at fpr.
+ *   ntedit_hip_reads_default_sketch: the tool's default sketch counters, 16 per output byte, or with bf_bytes = 0
+ *           (sized from the histogram) one per input byte with gzip files at 4 x their size; within [64 MiB, 32 GiB].
+ *   ntedit_hip_reads_is_gzip: 1 if the file starts with the gzip magic.
+ *   ntedit_hip_reads_write_hist: the --hist file (ntCard's text format) of f, F0, F1. */
+#define NTEDIT_MERGE_SAT_ADD 0
+#define NTEDIT_MERGE_OR 1
+#define NTEDIT_MERGE_MAX 2
+#define NTEDIT_READS_PASS_COUNT 0
+#define NTEDIT_READS_PASS_HIST 1
+#define NTEDIT_READS_PASS_SOLID 2
+typedef struct ntedit_hip_reads_pass_stats
+{
+	uint64_t bases;  /* bases of the reads of k bases or more */
+	double ms_wall;  /* the pass, parsing included */
+	double ms_gpu;   /* the library's GPU calls */
+} ntedit_hip_reads_pass_stats;
+int ntedit_hip_sketch_set_device(ntedit_hip_ctx* ctx, void* device_counters, uint64_t counters, uint32_t hash_num, uint32_t k);
+int ntedit_hip_sketch_info(ntedit_hip_ctx* ctx, uint64_t* counters, uint32_t* hash_num, uint32_t* k);
+int ntedit_hip_merge_bytes(ntedit_hip_ctx* ctx, void* dst, const void* srcs, uint32_t n_src, uint64_t n, int op);
+int ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, const uint64_t* begins, const uint64_t* ends,
+                          uint32_t n, uint64_t batch_bytes, uint32_t cmin, ntedit_hip_reads_pass_stats* stats,
+                          uint64_t* starts, uint64_t* nexts);
+int ntedit_hip_reads_range_text(const char* path, uint64_t begin, uint64_t end, char* out, uint64_t cap, uint64_t* len,
+                                uint64_t* reads, uint64_t* start, uint64_t* next);
+uint64_t ntedit_hip_reads_bf_size(uint64_t num_elements, uint32_t hash_num, double fpr);
+uint64_t ntedit_hip_reads_default_sketch(const char* const* files, uint32_t n, uint64_t bf_bytes);
+int ntedit_hip_reads_is_gzip(const char* path);
+int ntedit_hip_reads_write_hist(const char* path, const uint64_t f[256], uint64_t F0, uint64_t F1);
 
 
 /* ---- hot path ------------------------------------------------------------

@@ -62,6 +62,15 @@ class Stats(ctypes.Structure):
     ]
 
 
+class ReadsPassStats(ctypes.Structure):
+    """ntedit_hip_reads_pass_stats"""
+    _fields_ = [("bases", ctypes.c_uint64), ("ms_wall", ctypes.c_double), ("ms_gpu", ctypes.c_double)]
+
+
+MERGE_SAT_ADD, MERGE_OR, MERGE_MAX = 0, 1, 2
+READS_PASS_COUNT, READS_PASS_HIST, READS_PASS_SOLID = 0, 1, 2
+
+
 class Segment(ctypes.Structure):
     """ntedit_hip_segment: a batch entry that is one segment of a contig cut for multi-GPU sharding"""
     _fields_ = [("pos_offset", ctypes.c_uint32), ("halo", ctypes.c_uint32), ("flags", ctypes.c_uint32),
@@ -113,6 +122,9 @@ EXPORTS = [
     "ntedit_hip_sketch_save_file", "ntedit_hip_sketch_free", "ntedit_hip_filter_alloc_counting",
     "ntedit_hip_filter_insert_solid", "ntedit_hip_reads_last_error", "ntedit_hip_sketch_histogram",
     "ntedit_hip_sketch_histogram_download", "ntedit_hip_reads_hist_summary", "ntedit_hip_reads_solid_cutoff",
+    "ntedit_hip_sketch_set_device", "ntedit_hip_sketch_info", "ntedit_hip_merge_bytes", "ntedit_hip_reads_pass",
+    "ntedit_hip_reads_range_text", "ntedit_hip_reads_bf_size", "ntedit_hip_reads_default_sketch",
+    "ntedit_hip_reads_is_gzip", "ntedit_hip_reads_write_hist",
 ]
 
 _lib = None
@@ -217,5 +229,18 @@ def load():
     lib.ntedit_hip_sketch_histogram_download.argtypes = [vp, vp]
     lib.ntedit_hip_reads_hist_summary.argtypes = [vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.ntedit_hip_reads_solid_cutoff.argtypes = [vp, ctypes.POINTER(u32)]
+    pu64 = ctypes.POINTER(u64)
+    lib.ntedit_hip_sketch_set_device.argtypes = [vp, vp, u64, u32, u32]
+    lib.ntedit_hip_sketch_info.argtypes = [vp, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    lib.ntedit_hip_merge_bytes.argtypes = [vp, vp, vp, u32, u64, ci]
+    lib.ntedit_hip_reads_pass.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_char_p), pu64, pu64, u32, u64, u32,
+                                          ctypes.POINTER(ReadsPassStats), pu64, pu64]
+    lib.ntedit_hip_reads_range_text.argtypes = [ctypes.c_char_p, u64, u64, vp, u64, pu64, pu64, pu64, pu64]
+    lib.ntedit_hip_reads_bf_size.argtypes = [u64, u32, ctypes.c_double]
+    lib.ntedit_hip_reads_bf_size.restype = u64
+    lib.ntedit_hip_reads_default_sketch.argtypes = [ctypes.POINTER(ctypes.c_char_p), u32, u64]
+    lib.ntedit_hip_reads_default_sketch.restype = u64
+    lib.ntedit_hip_reads_is_gzip.argtypes = [ctypes.c_char_p]
+    lib.ntedit_hip_reads_write_hist.argtypes = [ctypes.c_char_p, vp, u64, u64]
     _lib = lib
     return lib

@@ -8,6 +8,8 @@
 //   k_hist<H, POW2>           histogram pass: bin est(x) of a 256-bin histogram of every k-mer occurrence, summed in
 //                             per-wave LDS sub-histograms and flushed once per block (one 64-bit add per non-zero bin)
 //   k_nonzero                 non-zero counters of the sketch (occupancy)
+//   k_merge<OP>               n_src equal byte chunks folded into one: saturating add (sketches), OR (plain filters),
+//                             max (counting filters) -- the merge of a sharded build
 //
 // k-mers, hashes and slots are the filter build's (k_screen<., ., true> in nte_kernels.hip): runs of k bytes of
 // ACGTacgt, canonical base fh + rh, hash_extend, filter_slot.  Every result is independent of the order in which the
@@ -294,6 +296,72 @@ k_nonzero(const u64* __restrict__ w, u64 n_words, unsigned long long* total)
 	}
 }
 
+// ------------------------------------------------------------------ k_merge
+// A pure stream of (n_src + 1) * n bytes: each lane moves 16 bytes per load / store, four 32-bit words of four bytes.
+// gfx950 has no byte-SIMD add or max, so both work on the packed words with borrow/carry tricks (no byte crosses
+// into its neighbour):
+//   t     = (a & 0x7F..) + (b & 0x7F..) ^ ((a ^ b) & 0x80..)           bytewise a + b mod 256
+//   carry = ((a & b) | ((a | b) & ~t)) & 0x80..                         the bytes that overflowed (full-adder carry out)
+//   sat   = t | (carry >> 7) * 0xFF
+//   d     = ((a | 0x80..) - (b & 0x7F..)) ^ ((a ^ ~b) & 0x80..)        bytewise a - b mod 256
+//   lt    = ((~a & b) | ((~a | b) & d)) & 0x80..                        the bytes with a < b (borrow out)
+//   max   = (a & ~m) | (b & m), m = (lt >> 7) * 0xFF
+constexpr u32 MG_HI = 0x80808080u, MG_LO = 0x7F7F7F7Fu;
+
+template<int OP>
+__host__ __device__ __forceinline__ u32
+merge_word(u32 a, u32 b)
+{
+	if (OP == NTEDIT_MERGE_SAT_ADD) {
+		const u32 t = ((a & MG_LO) + (b & MG_LO)) ^ ((a ^ b) & MG_HI);
+		const u32 carry = ((a & b) | ((a | b) & ~t)) & MG_HI;
+		return t | ((carry >> 7) * 0xFFu);
+	} else if (OP == NTEDIT_MERGE_OR) {
+		return a | b;
+	} else {
+		const u32 d = ((a | MG_HI) - (b & MG_LO)) ^ ((a ^ ~b) & MG_HI);
+		const u32 lt = ((~a & b) | ((~a | b) & d)) & MG_HI;
+		const u32 m = (lt >> 7) * 0xFFu;
+		return (a & ~m) | (b & m);
+	}
+}
+
+constexpr int MG_TPB = 256;
+
+// dst[0 .. n) = fold of srcs[i * n + x] over i.  VEC: dst and every chunk are 16-byte aligned, so [0, n & ~15) moves in
+// 16-byte vectors and the last n % 16 bytes one by one; otherwise every byte goes one by one.  dst may alias chunk 0
+// (each byte is read by the thread that writes it).
+template<int OP, bool VEC>
+__global__ __launch_bounds__(MG_TPB) void
+k_merge(u8* dst, const u8* srcs, u32 n_src, u64 n)
+{
+	const u64 stride = (u64)gridDim.x * MG_TPB;
+	const u64 tid = (u64)blockIdx.x * MG_TPB + threadIdx.x;
+	u64 tail = 0;
+	if (VEC) {
+		const u64 n16 = n / 16;
+		for (u64 v = tid; v < n16; v += stride) {
+			uint4 acc = reinterpret_cast<const uint4*>(srcs)[v];
+			for (u32 i = 1; i < n_src; i++) {
+				const uint4 x = reinterpret_cast<const uint4*>(srcs + (u64)i * n)[v];
+				acc.x = merge_word<OP>(acc.x, x.x);
+				acc.y = merge_word<OP>(acc.y, x.y);
+				acc.z = merge_word<OP>(acc.z, x.z);
+				acc.w = merge_word<OP>(acc.w, x.w);
+			}
+			reinterpret_cast<uint4*>(dst)[v] = acc;
+		}
+		tail = n16 * 16;
+	}
+	for (u64 x = tail + tid; x < n; x += stride) {
+		u32 acc = srcs[x];
+		for (u32 i = 1; i < n_src; i++) {
+			acc = merge_word<OP>(acc, srcs[(u64)i * n + x]) & 0xFFu;
+		}
+		dst[x] = (u8)acc;
+	}
+}
+
 // ------------------------------------------------------------------ host side
 struct ReadsState
 {
@@ -301,6 +369,7 @@ struct ReadsState
 	int device = 0;
 	hipStream_t stream = nullptr;
 	u8* sketch = nullptr; // counters, zero-filled up to a whole 64-bit word
+	bool adopted = false; // the sketch is the caller's memory (ntedit_hip_sketch_set_device)
 	u64 counters = 0;
 	u32 hash_num = 0, k = 0;
 	DevParams dp;
@@ -319,7 +388,7 @@ std::vector<std::pair<const ntedit_hip_ctx*, std::string>> g_reads_err; // last 
 int
 rfail(const ntedit_hip_ctx* c, int code, const char* fmt, ...)
 {
-	char buf[512];
+	char buf[1024];
 	va_list ap;
 	va_start(ap, fmt);
 	vsnprintf(buf, sizeof buf, fmt, ap);
@@ -363,7 +432,7 @@ release_state(ReadsState* s)
 		(void)hipStreamSynchronize(s->stream);
 		(void)hipStreamDestroy(s->stream);
 	}
-	for (void* p : { (void*)s->sketch, (void*)s->d_tab, (void*)s->d_seq, (void*)s->d_total, (void*)s->d_hist }) {
+	for (void* p : { s->adopted ? nullptr : (void*)s->sketch, (void*)s->d_tab, (void*)s->d_seq, (void*)s->d_total, (void*)s->d_hist }) {
 		if (p) {
 			(void)hipFree(p);
 		}
@@ -478,6 +547,15 @@ run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int o
 
 } // namespace
 
+namespace nte_reads {
+// the failures of the host side (reads_pass.cpp) go to the same store as this unit's
+int
+set_error(const ntedit_hip_ctx* c, int code, const std::string& why)
+{
+	return rfail(c, code, "%s", why.c_str());
+}
+} // namespace nte_reads
+
 extern "C" {
 
 const char*
@@ -492,8 +570,91 @@ ntedit_hip_reads_last_error(const ntedit_hip_ctx* c)
 	return "";
 }
 
+static int make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, void* adopt);
+
 int
 ntedit_hip_sketch_alloc(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k)
+{
+	return make_state(c, counters, hash_num, k, nullptr);
+}
+
+int
+ntedit_hip_sketch_set_device(ntedit_hip_ctx* c, void* device_counters, uint64_t counters, uint32_t hash_num, uint32_t k)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	if (!device_counters || ((uintptr_t)device_counters & 15) || counters % 8) {
+		return rfail(c, NTEDIT_E_ARG, "sketch_set_device: needs a 16-byte aligned device pointer and a multiple of 8 counters");
+	}
+	return make_state(c, counters, hash_num, k, device_counters);
+}
+
+int
+ntedit_hip_sketch_info(ntedit_hip_ctx* c, uint64_t* counters, uint32_t* hash_num, uint32_t* k)
+{
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return c ? rfail(c, NTEDIT_E_ARG, "sketch_info: no sketch") : NTEDIT_E_ARG;
+	}
+	if (counters) {
+		*counters = s->counters;
+	}
+	if (hash_num) {
+		*hash_num = s->hash_num;
+	}
+	if (k) {
+		*k = s->k;
+	}
+	return 0;
+}
+
+int
+ntedit_hip_merge_bytes(ntedit_hip_ctx* c, void* dst, const void* srcs, uint32_t n_src, uint64_t n, int op)
+{
+	if (!c || !dst || !srcs || n_src == 0 || op < NTEDIT_MERGE_SAT_ADD || op > NTEDIT_MERGE_MAX) {
+		return c ? rfail(c, NTEDIT_E_ARG, "merge_bytes: bad argument") : NTEDIT_E_ARG;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	hipPointerAttribute_t attr;
+	RD_TRY(c, hipPointerGetAttributes(&attr, dst));
+	if (attr.type != hipMemoryTypeDevice) {
+		return rfail(c, NTEDIT_E_ARG, "merge_bytes: dst is not device memory");
+	}
+	RD_TRY(c, hipSetDevice(attr.device));
+	const bool vec = (((uintptr_t)dst | (uintptr_t)srcs) & 15) == 0 && (n % 16 == 0 || n_src == 1);
+	const u64 items = vec ? n / 16 + n % 16 : n;
+	int cus = 256;
+	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, attr.device);
+	const u64 want = (items + MG_TPB - 1) / MG_TPB, cap = (u64)cus * 8;
+	const dim3 grid((unsigned)(want < cap ? want : cap)), block(MG_TPB);
+	u8* d = (u8*)dst;
+	const u8* sp = (const u8*)srcs;
+#define MG_LAUNCH(OP)                                                                              \
+	case OP:                                                                                       \
+		if (vec) {                                                                                 \
+			hipLaunchKernelGGL((k_merge<OP, true>), grid, block, 0, nullptr, d, sp, n_src, n);   \
+		} else {                                                                                   \
+			hipLaunchKernelGGL((k_merge<OP, false>), grid, block, 0, nullptr, d, sp, n_src, n);  \
+		}                                                                                          \
+		break
+	switch (op) {
+		MG_LAUNCH(NTEDIT_MERGE_SAT_ADD);
+		MG_LAUNCH(NTEDIT_MERGE_OR);
+		MG_LAUNCH(NTEDIT_MERGE_MAX);
+	default:
+		break;
+	}
+#undef MG_LAUNCH
+	RD_TRY(c, hipGetLastError());
+	RD_TRY(c, hipStreamSynchronize(nullptr));
+	return 0;
+}
+
+static int
+make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, void* adopt)
 {
 	if (!c) {
 		return NTEDIT_E_ARG;
@@ -509,6 +670,8 @@ ntedit_hip_sketch_alloc(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num,
 	s->owner = c;
 	s->device = device;
 	s->counters = (counters + 7) / 8 * 8; // btllib rounds a counting filter up to whole 64-bit words
+	s->adopted = adopt != nullptr;
+	s->sketch = (u8*)adopt;
 	s->hash_num = hash_num;
 	s->k = k;
 	ntedit_hip_params hp;
@@ -517,7 +680,7 @@ ntedit_hip_sketch_alloc(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num,
 	u64 tab[TAB_WORDS];
 	build_seed_tables(k, tab);
 	hipError_t e = rc ? hipSuccess : hipStreamCreate(&s->stream);
-	if (e == hipSuccess && !rc) {
+	if (e == hipSuccess && !rc && !adopt) {
 		e = hipMalloc((void**)&s->sketch, s->counters);
 	}
 	if (e == hipSuccess && !rc) {
@@ -529,7 +692,7 @@ ntedit_hip_sketch_alloc(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num,
 	if (e == hipSuccess && !rc) {
 		e = hipMalloc((void**)&s->d_hist, 256 * sizeof(unsigned long long));
 	}
-	if (e == hipSuccess && !rc) {
+	if (e == hipSuccess && !rc && !adopt) {
 		e = hipMemsetAsync(s->sketch, 0, s->counters, s->stream);
 	}
 	if (e == hipSuccess && !rc) {

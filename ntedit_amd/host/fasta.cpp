@@ -5,7 +5,9 @@
 #include <cctype>
 #include <cstdlib>
 #include <cstring>
+#include <fcntl.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 namespace nte_host {
 
@@ -29,11 +31,21 @@ FastaReader::data_(int s) const
 }
 
 FastaReader::FastaReader(const char* path)
+  : FastaReader(path, 0, ~0ull)
+{
+}
+
+FastaReader::FastaReader(const char* path, unsigned long long begin, unsigned long long limit)
   : f_(nullptr)
   , gz_(nullptr)
   , buf_(nullptr)
   , begin_(0)
   , end_(0)
+  , base_(begin)
+  , done_(0)
+  , limit_(limit)
+  , rec_start_(0)
+  , next_start_(~0ull)
   , eof_(false)
   , last_char_(0)
   , hit_nl_(false)
@@ -51,14 +63,23 @@ FastaReader::FastaReader(const char* path)
 		slot_crc_[i] = slot_isize_[i] = 0;
 	}
 	struct stat st;
-	if (!g_gzip_through_zlib.load() && stat(path, &st) == 0 && S_ISREG(st.st_mode)) {
+	if (begin > 0) {
+		// (a range of a plain file: zlib passes it through from the descriptor's position)
+		const int fd = open(path, O_RDONLY);
+		if (fd >= 0 && lseek(fd, (off_t)begin, SEEK_SET) == (off_t)begin) {
+			f_ = gzdopen(fd, "r");
+		}
+		if (!f_ && fd >= 0) {
+			close(fd);
+		}
+	} else if (!g_gzip_through_zlib.load() && stat(path, &st) == 0 && S_ISREG(st.st_mode)) {
 		gz_ = new Gunzip();
 		if (!gz_->open(path)) {
 			delete gz_; // not a gzip stream (or not readable: gzopen says so below)
 			gz_ = nullptr;
 		}
 	}
-	if (!gz_) {
+	if (!gz_ && begin == 0) {
 		f_ = gzopen(path, "r");
 	}
 	if (f_ || gz_) {
@@ -225,6 +246,7 @@ FastaReader::fill_()
 	std::unique_lock<std::mutex> lk(mu_);
 	for (;;) {
 		if (cur_ >= 0) {
+			done_ += (unsigned long long)slot_len_[cur_];
 			tail_++; // the block the parser has finished with goes back to the I/O thread
 			cur_ = -1;
 			cv_.notify_all();
@@ -300,12 +322,19 @@ FastaReader::next(std::string& header, std::string& seq)
 		while ((c = getc_()) != -1 && c != '>' && c != '@') {
 		}
 		if (c == -1) {
+			next_start_ = here_();
 			return false;
 		}
 		last_char_ = c;
+		rec_start_ = here_() - 1;
+	}
+	if (rec_start_ >= limit_) {
+		next_start_ = rec_start_;
+		return false;
 	}
 	line_.clear();
 	if (!getline_(line_, 0, false) && eof_) {
+		next_start_ = here_();
 		return false;
 	}
 	// name = up to the first whitespace character; if that character was not the newline,
@@ -337,6 +366,7 @@ FastaReader::next(std::string& header, std::string& seq)
 	}
 	if (c == '>' || c == '@') {
 		last_char_ = c;
+		rec_start_ = here_() - 1;
 	}
 	if (c == '+') {
 		// FASTQ: skip the rest of the '+' line, then quality lines until there are as many
@@ -346,6 +376,7 @@ FastaReader::next(std::string& header, std::string& seq)
 		getline_(line_, 0, false);
 		if (!hit_nl_) {
 			failed_ = true; // kseq_read() = -2 (no quality string): the reference stops reading
+			next_start_ = ~0ull;
 			seq.resize(base);
 			return false;
 		}
@@ -355,6 +386,7 @@ FastaReader::next(std::string& header, std::string& seq)
 		last_char_ = 0;
 		if (line_.size() != want) {
 			failed_ = true; // kseq_read() = -2 (truncated quality string)
+			next_start_ = ~0ull;
 			seq.resize(base);
 			return false;
 		}

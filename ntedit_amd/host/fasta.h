@@ -23,6 +23,9 @@ class FastaReader
 {
   public:
 	explicit FastaReader(const char* path);
+	// a byte range of a plain file: reading starts at byte `begin` (the caller puts it on a record start), and next()
+	// stops before the first record whose first byte lies at or past `limit`
+	FastaReader(const char* path, unsigned long long begin, unsigned long long limit);
 	~FastaReader();
 	bool ok() const { return f_ != nullptr || gz_ != nullptr; }
 	// set once the input turned out to be unreadable half-way (corrupt or truncated .gz, I/O error): next()
@@ -33,6 +36,9 @@ class FastaReader
 	// reads the next record; header = name [+ " " + comment]; the sequence is APPENDED to seq
 	// (so a batch can be assembled without an intermediate copy); false at EOF
 	bool next(std::string& header, std::string& seq);
+	// once next() has returned false: the offset of the first byte of the record it stopped before (the limit's), the
+	// offset of the end of the input if it ran out first, ~0 if a record failed to parse (plain files: file offsets)
+	unsigned long long next_start() const { return next_start_; }
 
   private:
 	bool fill_();
@@ -47,6 +53,9 @@ class FastaReader
 	unsigned char* buf_; // the block being parsed
 
 	int begin_, end_;
+	unsigned long long base_, done_; // offset of the first byte read; bytes of the blocks the parser is through with
+	unsigned long long limit_, rec_start_, next_start_;
+	unsigned long long here_() const { return base_ + done_ + (unsigned long long)begin_; }
 	bool eof_;
 	int last_char_;
 	bool hit_nl_, failed_;

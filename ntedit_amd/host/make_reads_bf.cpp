@@ -10,31 +10,24 @@
 // theirs.  The output is a btllib-format filter that ntedit -r loads unchanged: a plain Bloom filter, or with --counts
 // a counting filter holding each solid k-mer's estimate (for ntedit -p / -q).  Both passes read the inputs (FASTA or
 // FASTQ, plain or gzip) through FastaReader, in bounded batches double-buffered through page-locked memory: a second
-// thread parses the next batch while the GPU works on the current one.
+// thread parses the next batch while the GPU works on the current one (ntedit_hip_reads_pass, reads_pass.cpp, which
+// the sharded driver ntedit_amd/make_reads.py runs over byte ranges of the same files).
 //
 // With --solid or --hist a histogram pass runs between the two (ntedit_hip_sketch_histogram): the k-mer histogram of
 // the sketch's estimates, in place of the reference's ntCard run.  --hist writes it in ntCard's text format, --solid
 // takes CMIN from its first valley (ntedit_hip_reads_solid_cutoff), and without --bf / --num_elements the output is
 // sized from it: --num_elements N with N = the distinct k-mers the histogram puts at CMIN or above.
 #include "../../include/ntedit_hip.h"
-#include "fasta.h"
 
-#include <chrono>
 #include <cerrno>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
-#include <deque>
 #include <iostream>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
-
-#include <sys/stat.h>
 
 static void
 log_info(const std::string& msg)
@@ -46,21 +39,7 @@ log_info(const std::string& msg)
 	std::cerr << "[" << ts << "] [INFO] " << msg << std::endl;
 }
 
-// as ntedit-make-genome-bf (ntedit_make_genome_bf.cpp:41-47)
-static uint64_t
-get_bf_size(uint64_t num_elements, double num_hashes, double fpr)
-{
-	const double r = -num_hashes / log(1.0 - exp(log(fpr) / num_hashes));
-	const uint64_t m = (uint64_t)(ceil((double)num_elements * r) / 8u);
-	return m;
-}
-
-// default sketch: 16 output bytes' worth of counters, within [64 MiB, 32 GiB]; sized from the histogram (the output
-// size not known yet): one counter per input byte, a gzip file counted at 4 x its size, within the same bounds
-static const uint64_t SKETCH_PER_OUTPUT_BYTE = 16;
-static const uint64_t GZIP_INPUT_FACTOR = 4;
-static const uint64_t SKETCH_MIN = 64ull << 20;
-static const uint64_t SKETCH_MAX = 32ull << 30;
+// (the sizing, the passes and the --hist writer live in the library: reads_pass.cpp, shared with the sharded driver)
 static const uint64_t BATCH_DEFAULT = 256ull << 20;
 
 static void
@@ -122,170 +101,6 @@ parse_u64(const char* s, uint64_t* out)
 	return true;
 }
 
-// page-locked batch buffers: the parser fills one while the GPU works on the other
-struct Batch
-{
-	char* p = nullptr;
-	size_t cap = 0, len = 0;
-	uint64_t bases = 0;
-	bool last = false;
-};
-
-class BatchFeeder
-{
-  public:
-	BatchFeeder(const std::vector<std::string>& files, unsigned k, size_t batch_bytes)
-	    : files_(files), k_(k), batch_bytes_(batch_bytes)
-	{
-		for (Batch& b : bufs_) {
-			free_.push_back(&b);
-		}
-		th_ = std::thread([this] { run_(); });
-	}
-	~BatchFeeder()
-	{
-		{
-			std::lock_guard<std::mutex> lk(mu_);
-			stop_ = true;
-		}
-		cv_.notify_all();
-		th_.join();
-		for (Batch& b : bufs_) {
-			ntedit_hip_host_free(b.p);
-		}
-	}
-	// the next filled batch (last = true: the input ends with it); nullptr after an error
-	Batch* take()
-	{
-		std::unique_lock<std::mutex> lk(mu_);
-		cv_.wait(lk, [this] { return !full_.empty() || failed_; });
-		if (failed_) {
-			return nullptr;
-		}
-		Batch* b = full_.front();
-		full_.pop_front();
-		return b;
-	}
-	void give_back(Batch* b)
-	{
-		{
-			std::lock_guard<std::mutex> lk(mu_);
-			free_.push_back(b);
-		}
-		cv_.notify_all();
-	}
-	const std::string& error() const { return err_; }
-
-  private:
-	Batch* get_free_()
-	{
-		std::unique_lock<std::mutex> lk(mu_);
-		cv_.wait(lk, [this] { return !free_.empty() || stop_; });
-		if (stop_) {
-			return nullptr;
-		}
-		Batch* b = free_.front();
-		free_.pop_front();
-		b->len = 0;
-		b->bases = 0;
-		b->last = false;
-		return b;
-	}
-	void put_full_(Batch* b)
-	{
-		{
-			std::lock_guard<std::mutex> lk(mu_);
-			full_.push_back(b);
-		}
-		cv_.notify_all();
-	}
-	void fail_(const std::string& why)
-	{
-		{
-			std::lock_guard<std::mutex> lk(mu_);
-			err_ = why;
-			failed_ = true;
-		}
-		cv_.notify_all();
-	}
-	bool reserve_(Batch* b, size_t need)
-	{
-		if (need <= b->cap) {
-			return true;
-		}
-		const size_t cap = need > batch_bytes_ ? need : batch_bytes_;
-		char* p = (char*)ntedit_hip_host_alloc(cap);
-		if (!p) {
-			return false;
-		}
-		if (b->len) {
-			memcpy(p, b->p, b->len);
-		}
-		ntedit_hip_host_free(b->p);
-		b->p = p;
-		b->cap = cap;
-		return true;
-	}
-	void run_()
-	{
-		Batch* b = get_free_();
-		std::string hdr, seq;
-		for (const std::string& f : files_) {
-			if (!b) {
-				return;
-			}
-			nte_host::FastaReader reader(f.c_str());
-			if (!reader.ok()) {
-				fail_("cannot open " + f);
-				return;
-			}
-			for (;;) {
-				seq.clear();
-				if (!reader.next(hdr, seq)) {
-					break;
-				}
-				if (seq.size() < k_) { // no k-mer in it
-					continue;
-				}
-				// reads are separated by '\n' (no k-mer spans a separator)
-				if (b->len && b->len + seq.size() + 1 > batch_bytes_) {
-					put_full_(b);
-					if (!(b = get_free_())) {
-						return;
-					}
-				}
-				if (!reserve_(b, b->len + seq.size() + 1)) {
-					fail_("cannot allocate page-locked host memory");
-					return;
-				}
-				memcpy(b->p + b->len, seq.data(), seq.size());
-				b->p[b->len + seq.size()] = '\n';
-				b->len += seq.size() + 1;
-				b->bases += seq.size();
-			}
-			if (reader.io_error()) {
-				fail_(f + ": " + reader.io_error_text());
-				return;
-			}
-		}
-		if (b) {
-			b->last = true;
-			put_full_(b);
-		}
-	}
-
-	std::vector<std::string> files_;
-	unsigned k_;
-	size_t batch_bytes_;
-	Batch bufs_[2];
-	std::deque<Batch*> free_, full_;
-	bool stop_ = false, failed_ = false;
-	std::string err_;
-	std::mutex mu_;
-	std::condition_variable cv_;
-	std::thread th_;
-};
-
 static void
 die(ntedit_hip_ctx* ctx, const std::string& why)
 {
@@ -297,92 +112,28 @@ die(ntedit_hip_ctx* ctx, const std::string& why)
 	exit(1);
 }
 
-enum Pass
-{
-	PASS_COUNT,  // pass 1: count every k-mer into the sketch
-	PASS_HIST,   // histogram pass (--solid / --hist): bin every k-mer's estimate
-	PASS_SOLID,  // pass 2: insert the k-mers whose estimate is >= cmin
-};
-
-// one pass over every input file
+// one pass over every input file, whole (ntedit_hip_reads_pass)
 static void
-run_pass(ntedit_hip_ctx* ctx, Pass pass, const std::vector<std::string>& files, unsigned k, size_t batch_bytes, unsigned cmin)
+run_pass(ntedit_hip_ctx* ctx, int pass, const std::vector<std::string>& files, size_t batch_bytes, unsigned cmin)
 {
-	const auto t0 = std::chrono::steady_clock::now();
-	uint64_t bases = 0;
-	double gpu_ms = 0.0;
-	{
-		BatchFeeder feed(files, k, batch_bytes);
-		for (;;) {
-			Batch* b = feed.take();
-			if (!b) {
-				die(ctx, feed.error());
-			}
-			const auto g0 = std::chrono::steady_clock::now();
-			int rc = 0;
-			if (b->len) { // (an input without any read of k bases ends in an empty batch)
-				rc = pass == PASS_COUNT  ? ntedit_hip_sketch_count(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
-				     : pass == PASS_HIST ? ntedit_hip_sketch_histogram(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
-				                         : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, b->p, b->len,
-				                                                          NTEDIT_HIP_BASES_HOST, cmin);
-			}
-			if (rc) {
-				die(ctx, ntedit_hip_reads_last_error(ctx));
-			}
-			gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
-			bases += b->bases;
-			const bool last = b->last;
-			feed.give_back(b);
-			if (last) {
-				break;
-			}
-		}
+	std::vector<const char*> paths;
+	for (const std::string& f : files) {
+		paths.push_back(f.c_str());
 	}
-	const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	const std::vector<uint64_t> begins(files.size(), 0), ends(files.size(), ~0ull);
+	ntedit_hip_reads_pass_stats st;
+	if (ntedit_hip_reads_pass(ctx, pass, paths.data(), begins.data(), ends.data(), (uint32_t)files.size(), batch_bytes,
+	                          cmin, &st, nullptr, nullptr) != 0) {
+		die(ctx, ntedit_hip_reads_last_error(ctx));
+	}
+	const uint64_t bases = st.bases;
+	const double ms = st.ms_wall, gpu_ms = st.ms_gpu;
 	char line[256];
 	static const char* const names[] = { "1 (count)", "H (histogram)", "2 (solid k-mers)" };
 	snprintf(line, sizeof line, "Pass %s: %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", names[pass],
 	         (unsigned long long)bases, ms, ms > 0 ? bases / ms / 1e6 : 0.0, gpu_ms,
 	         gpu_ms > 0 ? bases / gpu_ms / 1e6 : 0.0);
 	log_info(line);
-}
-
-// the default sketch when the output is sized from the histogram: one counter per input byte (gzip: 4 x its size);
-// an input that cannot be read counts 0 here and fails in pass 1
-static uint64_t
-input_bytes(const std::vector<std::string>& files)
-{
-	uint64_t total = 0;
-	for (const std::string& f : files) {
-		struct stat st;
-		if (stat(f.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
-			continue;
-		}
-		unsigned char magic[2] = { 0, 0 };
-		FILE* fp = fopen(f.c_str(), "rb");
-		const bool gz = fp && fread(magic, 1, 2, fp) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-		if (fp) {
-			fclose(fp);
-		}
-		total += (uint64_t)st.st_size * (gz ? GZIP_INPUT_FACTOR : 1);
-	}
-	return total;
-}
-
-// ntCard's histogram file: "F1\t<n>", "F0\t<n>", then "c\tf[c]" for c = 1..255 (zeros included)
-static bool
-write_hist(const std::string& path, const uint64_t f[256], uint64_t F0, uint64_t F1)
-{
-	FILE* fp = fopen(path.c_str(), "w");
-	if (!fp) {
-		return false;
-	}
-	fprintf(fp, "F1\t%llu\nF0\t%llu\n", (unsigned long long)F1, (unsigned long long)F0);
-	for (int c = 1; c < 256; c++) {
-		fprintf(fp, "%d\t%llu\n", c, (unsigned long long)f[c]);
-	}
-	const bool ok = !ferror(fp);
-	return fclose(fp) == 0 && ok;
 }
 
 int
@@ -533,7 +284,7 @@ main(int argc, char** argv)
 		std::cout << "\t\t--bf " << bf_size << std::endl;
 	} else if (have_ne) {
 		std::cout << "\t\t--num_elements " << num_elements << std::endl;
-		bf_size = get_bf_size(num_elements, (double)hashes, fpr);
+		bf_size = ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr);
 	}
 	if (!size_from_hist && bf_size == 0) {
 		usage("The output filter would be empty (--bf 0 or --num_elements too small).");
@@ -545,13 +296,11 @@ main(int argc, char** argv)
 		std::cout << "BF size (bytes): " << bf_size << std::endl;
 	}
 	if (sketch_bytes == 0) {
-		if (size_from_hist) {
-			sketch_bytes = input_bytes(read_files);
-			sketch_bytes = sketch_bytes > SKETCH_MAX ? SKETCH_MAX : sketch_bytes;
-		} else {
-			sketch_bytes = bf_size > SKETCH_MAX / SKETCH_PER_OUTPUT_BYTE ? SKETCH_MAX : bf_size * SKETCH_PER_OUTPUT_BYTE;
+		std::vector<const char*> paths;
+		for (const std::string& f : read_files) {
+			paths.push_back(f.c_str());
 		}
-		sketch_bytes = sketch_bytes < SKETCH_MIN ? SKETCH_MIN : sketch_bytes;
+		sketch_bytes = ntedit_hip_reads_default_sketch(paths.data(), (uint32_t)paths.size(), size_from_hist ? 0 : bf_size);
 	}
 	std::cout << "Sketch size (counters): " << sketch_bytes << std::endl;
 
@@ -565,7 +314,7 @@ main(int argc, char** argv)
 	}
 	const size_t batch = (size_t)batch_bytes;
 	log_info("Pass 1: counting k-mers");
-	run_pass(ctx, PASS_COUNT, read_files, (unsigned)k, batch, (unsigned)cmin);
+	run_pass(ctx, NTEDIT_READS_PASS_COUNT, read_files, batch, (unsigned)cmin);
 	uint64_t nonzero = 0, counters = 0;
 	if (ntedit_hip_sketch_occupancy(ctx, &nonzero, &counters) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));
@@ -578,7 +327,7 @@ main(int argc, char** argv)
 
 	if (gather_hist) {
 		log_info("Histogram pass: the k-mer histogram of the sketch's estimates");
-		run_pass(ctx, PASS_HIST, read_files, (unsigned)k, batch, (unsigned)cmin);
+		run_pass(ctx, NTEDIT_READS_PASS_HIST, read_files, batch, (unsigned)cmin);
 		uint64_t occ[256], f[256], F0 = 0, F1 = 0;
 		if (ntedit_hip_sketch_histogram_download(ctx, occ) != 0) {
 			die(ctx, ntedit_hip_reads_last_error(ctx));
@@ -590,7 +339,7 @@ main(int argc, char** argv)
 		         " (distinct k-mers)");
 		// written first: a refused --solid still leaves the histogram to look at
 		if (!hist_out.empty()) {
-			if (!write_hist(hist_out, f, F0, F1)) {
+			if (ntedit_hip_reads_write_hist(hist_out.c_str(), f, F0, F1) != 0) {
 				die(ctx, "cannot write " + hist_out);
 			}
 			log_info("Histogram written to " + hist_out);
@@ -609,7 +358,7 @@ main(int argc, char** argv)
 			for (uint64_t c = cmin; c < 256; c++) {
 				num_elements += f[c];
 			}
-			bf_size = get_bf_size(num_elements, (double)hashes, fpr);
+			bf_size = ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr);
 			log_info("Sized from the k-mer histogram: --num_elements " + std::to_string(num_elements) + " (k-mers at " +
 			         std::to_string(cmin) + " or above), " + std::to_string(bf_size) + " bytes");
 			if (bf_size == 0) {
@@ -625,7 +374,7 @@ main(int argc, char** argv)
 		die(ctx, counts ? ntedit_hip_reads_last_error(ctx) : ntedit_hip_last_error(ctx));
 	}
 	log_info("Pass 2: inserting k-mers seen at least " + std::to_string(cmin) + " times");
-	run_pass(ctx, PASS_SOLID, read_files, (unsigned)k, batch, (unsigned)cmin);
+	run_pass(ctx, NTEDIT_READS_PASS_SOLID, read_files, batch, (unsigned)cmin);
 	ntedit_hip_sketch_free(ctx);
 
 	uint64_t occupied = 0, slots = 0;

@@ -1,0 +1,494 @@
+// reads_pass.cpp -- the host side of the reads k-mer filter build, shared by ntedit-make-reads-bf and the sharded driver
+// (ntedit_amd/make_reads.py): one pass over a list of byte ranges of the input files, parsed by FastaReader into bounded
+// batches double-buffered through page-locked memory (a second thread parses the next batch while the GPU works on the
+// current one); the tool's sizing; its --hist writer.
+//
+// A range [begin, end) of a file owns the records whose first byte lies in it.  A range that starts past byte 0 first
+// moves forward to the first record start: a line that starts with '>' in a FASTA file, or in a FASTQ file a line that
+// starts with '@' whose line + 2 starts with '+' (unambiguous for 4-line FASTQ).  The parser then runs with kseq's rules
+// and stops before the first record that starts at or past `end`; where it stopped is reported (`nexts`), as is where
+// the range started (`starts`).  Only when every range's stop is the next range's start did the ranges parse the file
+// exactly as one reader would: the driver checks that after pass 1 (multi-line FASTQ can break it).  Gzip files are
+// single units.
+#include "../../include/ntedit_hip.h"
+#include "fasta.h"
+
+#include <chrono>
+#include <cmath>
+#include <condition_variable>
+#include <cstdio>
+#include <cstring>
+#include <deque>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include <sys/stat.h>
+
+namespace nte_reads {
+int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+}
+
+namespace {
+
+const uint64_t WHOLE = ~0ull; // `end` of a range that runs to the end of its file
+
+// default sketch: 16 output bytes' worth of counters, within [64 MiB, 32 GiB]; sized from the histogram (the output
+// size not known yet): one counter per input byte, a gzip file counted at 4 x its size, within the same bounds
+const uint64_t SKETCH_PER_OUTPUT_BYTE = 16;
+const uint64_t GZIP_INPUT_FACTOR = 4;
+const uint64_t SKETCH_MIN = 64ull << 20;
+const uint64_t SKETCH_MAX = 32ull << 30;
+
+int
+pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
+{
+	return nte_reads::set_error(c, code, why); // (ntedit_hip_reads_last_error's store, nte_reads.hip)
+}
+
+bool
+is_gzip(const char* path)
+{
+	unsigned char magic[2] = { 0, 0 };
+	FILE* fp = fopen(path, "rb");
+	const bool gz = fp && fread(magic, 1, 2, fp) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+	if (fp) {
+		fclose(fp);
+	}
+	return gz;
+}
+
+// the first record start at or past `begin` (> 0) of a plain file, or its size when there is none
+bool
+find_record_start(const char* path, uint64_t begin, uint64_t* out, std::string* why)
+{
+	FILE* fp = fopen(path, "rb");
+	if (!fp) {
+		*why = std::string("cannot open ") + path;
+		return false;
+	}
+	std::vector<char> buf(1 << 16);
+	setvbuf(fp, buf.data(), _IOFBF, buf.size());
+	// the file's kind: its first '>' or '@' (where kseq's first record starts)
+	int c, kind = 0;
+	while ((c = getc(fp)) != EOF) {
+		if (c == '>' || c == '@') {
+			kind = c;
+			break;
+		}
+	}
+	struct stat st;
+	*out = fstat(fileno(fp), &st) == 0 ? (uint64_t)st.st_size : 0;
+	if (!kind || fseeko(fp, (off_t)(begin - 1), SEEK_SET) != 0) {
+		fclose(fp);
+		return true;
+	}
+	// the first characters of the last three line starts at or past begin
+	uint64_t at[3] = { 0, 0, 0 };
+	int first[3] = { 0, 0, 0 }, n = 0;
+	int prev = getc(fp);
+	for (uint64_t p = begin;; p++) {
+		c = getc(fp);
+		if (prev == '\n') {
+			if (kind == '>' && c == '>') {
+				*out = p;
+				break;
+			}
+			if (n == 3) {
+				at[0] = at[1], at[1] = at[2], first[0] = first[1], first[1] = first[2];
+				n = 2;
+			}
+			at[n] = p, first[n] = c, n++;
+			if (n == 3 && first[0] == '@' && first[2] == '+') {
+				*out = at[0];
+				break;
+			}
+		}
+		if (c == EOF) {
+			break;
+		}
+		prev = c;
+	}
+	fclose(fp);
+	return true;
+}
+
+// every record of one range, in order: seq(record) for each; *start / *next as ntedit_hip_reads_pass reports them
+bool
+read_range(const char* path, uint64_t begin, uint64_t end, const std::function<bool(const std::string&)>& seq_fn,
+           uint64_t* start, uint64_t* next, std::string* why)
+{
+	uint64_t s = 0;
+	if (begin > 0 || end != WHOLE) {
+		struct stat st;
+		if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) {
+			*why = std::string("cannot open ") + path + " (a range needs a regular file)";
+			return false;
+		}
+		if (is_gzip(path)) {
+			*why = std::string(path) + ": a gzip file is read whole, not in ranges";
+			return false;
+		}
+		if (begin > 0 && !find_record_start(path, begin, &s, why)) {
+			return false;
+		}
+	}
+	*start = s;
+	if (s >= end) {
+		*next = s; // no record starts in the range
+		return true;
+	}
+	nte_host::FastaReader reader(path, s, end);
+	if (!reader.ok()) {
+		*why = std::string("cannot open ") + path;
+		return false;
+	}
+	std::string hdr, seq;
+	for (;;) {
+		seq.clear();
+		if (!reader.next(hdr, seq)) {
+			break;
+		}
+		if (!seq_fn(seq)) {
+			return false;
+		}
+	}
+	if (reader.io_error()) {
+		*why = std::string(path) + ": " + reader.io_error_text();
+		return false;
+	}
+	*next = reader.next_start();
+	return true;
+}
+
+struct Range
+{
+	const char* path;
+	uint64_t begin, end;
+};
+
+// page-locked batch buffers: the parser fills one while the GPU works on the other
+struct Batch
+{
+	char* p = nullptr;
+	size_t cap = 0, len = 0;
+	uint64_t bases = 0;
+	bool last = false;
+};
+
+class BatchFeeder
+{
+  public:
+	BatchFeeder(const std::vector<Range>& ranges, unsigned k, size_t batch_bytes, uint64_t* starts, uint64_t* nexts)
+	    : ranges_(ranges), k_(k), batch_bytes_(batch_bytes), starts_(starts), nexts_(nexts)
+	{
+		for (Batch& b : bufs_) {
+			free_.push_back(&b);
+		}
+		th_ = std::thread([this] { run_(); });
+	}
+	~BatchFeeder()
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			stop_ = true;
+		}
+		cv_.notify_all();
+		th_.join();
+		for (Batch& b : bufs_) {
+			ntedit_hip_host_free(b.p);
+		}
+	}
+	// the next filled batch (last = true: the input ends with it); nullptr after an error
+	Batch* take()
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		cv_.wait(lk, [this] { return !full_.empty() || failed_; });
+		if (failed_) {
+			return nullptr;
+		}
+		Batch* b = full_.front();
+		full_.pop_front();
+		return b;
+	}
+	void give_back(Batch* b)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			free_.push_back(b);
+		}
+		cv_.notify_all();
+	}
+	const std::string& error() const { return err_; }
+
+  private:
+	Batch* get_free_()
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		cv_.wait(lk, [this] { return !free_.empty() || stop_; });
+		if (stop_) {
+			return nullptr;
+		}
+		Batch* b = free_.front();
+		free_.pop_front();
+		b->len = 0;
+		b->bases = 0;
+		b->last = false;
+		return b;
+	}
+	void put_full_(Batch* b)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			full_.push_back(b);
+		}
+		cv_.notify_all();
+	}
+	void fail_(const std::string& why)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			err_ = why;
+			failed_ = true;
+		}
+		cv_.notify_all();
+	}
+	bool reserve_(Batch* b, size_t need)
+	{
+		if (need <= b->cap) {
+			return true;
+		}
+		const size_t cap = need > batch_bytes_ ? need : batch_bytes_;
+		char* p = (char*)ntedit_hip_host_alloc(cap);
+		if (!p) {
+			return false;
+		}
+		if (b->len) {
+			memcpy(p, b->p, b->len);
+		}
+		ntedit_hip_host_free(b->p);
+		b->p = p;
+		b->cap = cap;
+		return true;
+	}
+	// one read into the batch; false: stop (stopped, or failed)
+	bool add_(Batch*& b, const std::string& seq)
+	{
+		if (seq.size() < k_) { // no k-mer in it
+			return true;
+		}
+		// reads are separated by '\n' (no k-mer spans a separator)
+		if (b->len && b->len + seq.size() + 1 > batch_bytes_) {
+			put_full_(b);
+			if (!(b = get_free_())) {
+				return false;
+			}
+		}
+		if (!reserve_(b, b->len + seq.size() + 1)) {
+			fail_("cannot allocate page-locked host memory");
+			return false;
+		}
+		memcpy(b->p + b->len, seq.data(), seq.size());
+		b->p[b->len + seq.size()] = '\n';
+		b->len += seq.size() + 1;
+		b->bases += seq.size();
+		return true;
+	}
+	void run_()
+	{
+		Batch* b = get_free_();
+		for (size_t i = 0; i < ranges_.size(); i++) {
+			if (!b) {
+				return;
+			}
+			const Range& r = ranges_[i];
+			uint64_t start = 0, next = 0;
+			bool stopped = false;
+			std::string why;
+			auto add = [&](const std::string& seq) {
+				stopped = !add_(b, seq);
+				return !stopped;
+			};
+			const bool ok = read_range(r.path, r.begin, r.end, add, &start, &next, &why);
+			if (stopped) {
+				return; // (add_ failed the feeder, or it is being torn down)
+			}
+			if (!ok) {
+				fail_(why);
+				return;
+			}
+			if (starts_) {
+				starts_[i] = start;
+			}
+			if (nexts_) {
+				nexts_[i] = next;
+			}
+		}
+		if (b) {
+			b->last = true;
+			put_full_(b);
+		}
+	}
+
+	std::vector<Range> ranges_;
+	unsigned k_;
+	size_t batch_bytes_;
+	uint64_t *starts_, *nexts_;
+	Batch bufs_[2];
+	std::deque<Batch*> free_, full_;
+	bool stop_ = false, failed_ = false;
+	std::string err_;
+	std::mutex mu_;
+	std::condition_variable cv_;
+	std::thread th_;
+};
+
+} // namespace
+
+extern "C" {
+
+int
+ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, const uint64_t* begins, const uint64_t* ends,
+                      uint32_t n, uint64_t batch_bytes, uint32_t cmin, ntedit_hip_reads_pass_stats* stats,
+                      uint64_t* starts, uint64_t* nexts)
+{
+	if (!ctx || (n && (!files || !begins || !ends)) || batch_bytes < 4096 ||
+	    (pass != NTEDIT_READS_PASS_COUNT && pass != NTEDIT_READS_PASS_HIST && pass != NTEDIT_READS_PASS_SOLID)) {
+		return pfail(ctx, NTEDIT_E_ARG, "reads_pass: bad argument");
+	}
+	std::vector<Range> ranges(n);
+	for (uint32_t i = 0; i < n; i++) {
+		if (!files[i] || begins[i] > ends[i]) {
+			return pfail(ctx, NTEDIT_E_ARG, "reads_pass: bad range " + std::to_string(i));
+		}
+		ranges[i] = Range{ files[i], begins[i], ends[i] };
+	}
+	uint64_t counters = 0;
+	uint32_t hash_num = 0, k = 0;
+	if (ntedit_hip_sketch_info(ctx, &counters, &hash_num, &k) != 0) {
+		return pfail(ctx, NTEDIT_E_ARG, "reads_pass: no sketch (ntedit_hip_sketch_alloc / _set_device)");
+	}
+	const auto t0 = std::chrono::steady_clock::now();
+	uint64_t bases = 0;
+	double gpu_ms = 0.0;
+	{
+		BatchFeeder feed(ranges, k, (size_t)batch_bytes, starts, nexts);
+		for (;;) {
+			Batch* b = feed.take();
+			if (!b) {
+				return pfail(ctx, NTEDIT_E_IO, feed.error());
+			}
+			const auto g0 = std::chrono::steady_clock::now();
+			int rc = 0;
+			if (b->len) { // (an input without any read of k bases ends in an empty batch)
+				rc = pass == NTEDIT_READS_PASS_COUNT  ? ntedit_hip_sketch_count(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
+				     : pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_sketch_histogram(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
+				                                      : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, b->p,
+				                                                                       b->len, NTEDIT_HIP_BASES_HOST, cmin);
+			}
+			if (rc) {
+				return pfail(ctx, rc, ntedit_hip_reads_last_error(ctx));
+			}
+			gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
+			bases += b->bases;
+			const bool last = b->last;
+			feed.give_back(b);
+			if (last) {
+				break;
+			}
+		}
+	}
+	if (stats) {
+		stats->bases = bases;
+		stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		stats->ms_gpu = gpu_ms;
+	}
+	return 0;
+}
+
+int
+ntedit_hip_reads_range_text(const char* path, uint64_t begin, uint64_t end, char* out, uint64_t cap, uint64_t* len,
+                            uint64_t* reads, uint64_t* start, uint64_t* next)
+{
+	if (!path || !len || !reads || !start || !next || begin > end || (cap && !out)) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_range_text: bad argument");
+	}
+	uint64_t used = 0, count = 0;
+	std::string why;
+	const bool ok = read_range(path, begin, end, [&](const std::string& seq) {
+		if (used + seq.size() + 1 <= cap) {
+			memcpy(out + used, seq.data(), seq.size());
+			out[used + seq.size()] = '\n';
+		}
+		used += seq.size() + 1;
+		count++;
+		return true;
+	}, start, next, &why);
+	if (!ok) {
+		return pfail(nullptr, NTEDIT_E_IO, why);
+	}
+	*len = used;
+	*reads = count;
+	return used > cap ? NTEDIT_E_OVERFLOW : 0;
+}
+
+// as ntedit-make-genome-bf (ntedit_make_genome_bf.cpp:41-47)
+uint64_t
+ntedit_hip_reads_bf_size(uint64_t num_elements, uint32_t hash_num, double fpr)
+{
+	const double h = (double)hash_num;
+	const double r = -h / log(1.0 - exp(log(fpr) / h));
+	return (uint64_t)(ceil((double)num_elements * r) / 8u);
+}
+
+uint64_t
+ntedit_hip_reads_default_sketch(const char* const* files, uint32_t n, uint64_t bf_bytes)
+{
+	uint64_t counters = 0;
+	if (bf_bytes) {
+		counters = bf_bytes > SKETCH_MAX / SKETCH_PER_OUTPUT_BYTE ? SKETCH_MAX : bf_bytes * SKETCH_PER_OUTPUT_BYTE;
+	} else {
+		// an input that cannot be read counts 0 here and fails in pass 1
+		for (uint32_t i = 0; i < n; i++) {
+			struct stat st;
+			if (!files || !files[i] || stat(files[i], &st) != 0 || !S_ISREG(st.st_mode)) {
+				continue;
+			}
+			counters += (uint64_t)st.st_size * (is_gzip(files[i]) ? GZIP_INPUT_FACTOR : 1);
+		}
+		counters = counters > SKETCH_MAX ? SKETCH_MAX : counters;
+	}
+	return counters < SKETCH_MIN ? SKETCH_MIN : counters;
+}
+
+int
+ntedit_hip_reads_is_gzip(const char* path)
+{
+	return path && is_gzip(path) ? 1 : 0;
+}
+
+// ntCard's histogram file: "F1\t<n>", "F0\t<n>", then "c\tf[c]" for c = 1..255 (zeros included)
+int
+ntedit_hip_reads_write_hist(const char* path, const uint64_t f[256], uint64_t F0, uint64_t F1)
+{
+	if (!path || !f) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_write_hist: bad argument");
+	}
+	FILE* fp = fopen(path, "w");
+	if (!fp) {
+		return pfail(nullptr, NTEDIT_E_IO, std::string("cannot write ") + path);
+	}
+	fprintf(fp, "F1\t%llu\nF0\t%llu\n", (unsigned long long)F1, (unsigned long long)F0);
+	for (int c = 1; c < 256; c++) {
+		fprintf(fp, "%d\t%llu\n", c, (unsigned long long)f[c]);
+	}
+	const bool ok = !ferror(fp);
+	if (fclose(fp) != 0 || !ok) {
+		return pfail(nullptr, NTEDIT_E_IO, std::string("cannot write ") + path);
+	}
+	return 0;
+}
+
+} // extern "C"
