@@ -13,19 +13,15 @@ import pytest
 
 import helpers as H
 from test_gpu_reads_bf import (HASHES, K, NTEDIT, TOOL, _missing_kmers, awkward, blob_of, kmer_hashes,
-                               model_bf, model_counts, model_estimates, model_sketch, rounded, simulate_reads,
-                               write_fastq, write_large_reads)
+                               model_bf, model_counts, model_estimates, model_occ, model_sketch, rounded,
+                               simulate_reads, write_fastq, write_large_reads)
 
 pytestmark = pytest.mark.gpu
 
 _ = awkward  # the module-scoped fixture, shared
 
 
-# ------------------------------------------------------------------ the histogram model
-def model_occ(hv, sketch):
-    return np.bincount(model_estimates(hv, sketch), minlength=256).astype(np.uint64)
-
-
+# ------------------------------------------------------------------ the histogram model (and reads_model.model_occ)
 def model_summary(occ):
     c = np.arange(1, 256, dtype=np.uint64)
     f = np.zeros(256, dtype=np.uint64)
