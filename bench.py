@@ -14,13 +14,22 @@ event-free boundaries, greedy LPT over the pieces), each rank polishes its
 pieces against an identical filter that rank 0 builds and broadcasts once over
 RCCL (the path's single collective, untimed set-up).  No communication inside
 the timed region; value = the whole draft's bases / the slowest rank's time.
-A second, weak-scaling figure (every rank polishes the whole 3 Gbp draft) is
-measured right behind it and reported as "weak".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra
-objects: "roofline" (screening kernel, HBM-bound; algorithmic bytes = 4.125 B
-per screened base at h=3) and "cpu_baseline" (the C oracle timed on a bounded
-sample of the same draft + filter on the host; N=1 only).
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the workload's config) with an extra object "roofline"
+(screening kernel, HBM-bound; algorithmic bytes = 4.125 B per screened base at
+h=3), computed from the timed steps' own timers.
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps,
+--dump-outputs.  Whatever takes runs of its own comes with --full:
+  "weak"                  N>1: every rank polishes the whole 3 Gbp draft
+                          (weak scaling), measured right behind the strong figure
+  roofline.random_gather_probes_per_s  a random-gather micro-benchmark
+  "kernel_region_host*", "end_to_end*"  N=1: the batch from host memory, and
+                          the `ntedit` binary end to end (measured_regions)
+  "cpu_baseline"          N=1: the C oracle timed on a bounded sample of the
+                          same draft + filter on the host
+The --no-* options below leave out single parts of --full.
 
 --dump-outputs DIR writes what the last timed step computed (its edit records; with --screen-only the bitmap) as
 DIR/<name>.npy, float32 / float64, at most 64 MB: the inputs are seeded, so two builds can be compared output for output.
@@ -46,21 +55,24 @@ def parse():
     ap.add_argument("--filter-bytes", type=int, default=1 << 32)
     ap.add_argument("--k", type=int, default=25)
     ap.add_argument("--hashes", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the weak-scaling leg (N>1), the random-gather "
+                         "roofline, the host-buffer and end-to-end regions and the CPU baseline (N=1)")
     ap.add_argument("--cpu-sample-bases", type=float, default=30e6)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the multi-threaded CPU baseline (default min(64, cores))")
     ap.add_argument("--cpu-mt-seconds", type=float, default=12.0, help="target duration of the multi-threaded CPU baseline")
-    ap.add_argument("--no-gather", action="store_true")
+    ap.add_argument("--no-gather", action="store_true", help="--full without the random-gather micro-benchmark")
     ap.add_argument("--screen-only", action="store_true", help="time only the screening kernel (profiling aid)")
     ap.add_argument("--start-grid", type=int, default=0, help="event start grid override (tuning)")
     ap.add_argument("--screen-mode", type=int, default=0, help="0 auto, 1 direct gather, 2 L2-partitioned")
     ap.add_argument("--contig-len", type=int, default=0, help="contigs of exactly this many bases (configs[2]: 100000)")
-    ap.add_argument("--no-weak", action="store_true", help="skip the weak-scaling leg at N>1")
+    ap.add_argument("--no-weak", action="store_true", help="--full without the weak-scaling leg at N>1")
     ap.add_argument("--e2e-gzip", action="store_true", help="also run the end-to-end region on the draft as ONE gzip stream (level 6), "
                     "inflated by host/gunzip.cpp and, for comparison, by zlib")
     ap.add_argument("--e2e-bgzf", action="store_true", help="also run the end-to-end region on a BGZF-compressed draft")
-    ap.add_argument("--no-e2e", action="store_true", help="of the two extra regions, skip the end-to-end one (the `ntedit` binary)")
-    ap.add_argument("--no-regions", action="store_true", help="skip the host-buffer and end-to-end regions (N=1)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the end-to-end region (the `ntedit` binary)")
+    ap.add_argument("--no-regions", action="store_true", help="--full without the host-buffer and end-to-end regions (N=1)")
     ap.add_argument("--snv", action="store_true",
                     help="N=1 side line: -s 1 (every position re-assessed, ntedit.cpp:1806,1865; -i/-d 0)")
     ap.add_argument("--counting", action="store_true",
@@ -79,7 +91,10 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, "
                          "at most 64 MB in all; see dump_edits / dump_screen)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if (args.e2e_gzip or args.e2e_bgzf) and not args.full:
+        ap.error("--e2e-gzip / --e2e-bgzf extend the end-to-end region, which only --full measures")
+    return args
 
 
 def usable_cpus():
@@ -648,10 +663,11 @@ def main():
         my_bases, n_cut = job.n_bases, 0
     my_bytes = int(my_batch.numel())
     torch.cuda.synchronize()
+    weak_leg = args.full and world > 1 and not args.no_weak and not args.screen_only
     # start-up, untimed like the filter load: this rank's buffers + one internal warm-up batch (ntedit_hip_reserve)
     t_reserve = time.perf_counter()
     if not args.no_reserve:
-        nres = max(my_bytes, int(job.n_bytes)) if (world > 1 and not args.no_weak) else my_bytes
+        nres = max(my_bytes, int(job.n_bytes)) if weak_leg else my_bytes
         pol.reserve(nres, len(job.lens) + 64, on_device=1)
     t_reserve = time.perf_counter() - t_reserve
     t_setup = time.perf_counter() - t_setup
@@ -729,9 +745,9 @@ def main():
         rejected_total = int(rj.item())
     total_bases = sum(shard_bases)
 
-    # ---- weak-scaling leg: every rank polishes the whole draft
+    # ---- weak-scaling leg (--full): every rank polishes the whole draft
     weak = None
-    if world > 1 and not args.no_weak and not args.screen_only:
+    if weak_leg:
         wstep = make_step(job.batch, job.offsets, job.lens, job.n_bytes)
         wstep()
         w_elapsed, _ = timed_steps(wstep, args.steps, world, dev, torch, dist)
@@ -854,7 +870,7 @@ def main():
                              "skipped_as_overtaken": int(last.events_skipped),
                              "deferred_to_sweep_pass": int(last.events_deferred)}
         pps = None
-        if not args.no_gather:
+        if args.full and not args.no_gather:
             try:
                 pps, gms = pol.gather_bench(args.filter_bytes if args.filter_bytes & (args.filter_bytes - 1) == 0
                                             else 1 << 32, 4_000_000_000)
@@ -887,9 +903,9 @@ def main():
             except Exception:
                 pass
             out["roofline"]["machine"] = mach
-        if world == 1 and not args.no_regions and not args.screen_only:
+        if args.full and world == 1 and not args.no_regions and not args.screen_only:
             out.update(measured_regions(job, pol, args))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(job, pol, args)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -6,6 +6,7 @@ import sys
 import zlib
 
 import numpy as np
+import pytest
 
 import helpers as H
 
@@ -143,3 +144,21 @@ def test_dump_screen(tmp_path):
     assert np.unpackbits(full[-1:].view(np.uint8), bitorder="little").sum() == bits[(len(idx) - 1) * 64:].sum()
     bench.dump_screen(str(tmp_path / "s"), words, n, limit=64 << 10)
     assert sum(_npy_sizes(tmp_path / "s").values()) <= 64 << 10
+
+
+def _parse(monkeypatch, *argv):
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench.parse()
+
+
+def test_a_plain_run_leaves_the_extra_measurements_to_full(monkeypatch):
+    assert not _parse(monkeypatch, "--gpus", "1", "--steps", "20", "--warmup", "5").full
+    a = _parse(monkeypatch, "--full", "--no-cpu-baseline", "--e2e-bgzf")
+    assert a.full and a.no_cpu_baseline and a.e2e_bgzf
+
+
+def test_compressed_end_to_end_options_need_full(monkeypatch, capsys):
+    for opt in ("--e2e-gzip", "--e2e-bgzf"):
+        with pytest.raises(SystemExit) as e:
+            _parse(monkeypatch, opt)
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the CLI by hand on the bench inputs (no parent process holding the GPU), free / bound to either NUMA node
 cd "$GRAFT_REPO_ROOT" || exit 1
-NTEDIT_BENCH_KEEP_E2E=1 timeout 400 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-gather 2>&1 | grep "kept in" > /tmp/kept.txt
+NTEDIT_BENCH_KEEP_E2E=1 timeout 400 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-gather 2>&1 | grep "kept in" > /tmp/kept.txt
 W=$(sed 's/.*kept in //' /tmp/kept.txt); echo "work=$W"; ls $W | head
 lscpu | grep -i "numa\|socket" | head -8
 for d in /sys/class/drm/card*/device; do echo "$d $(cat $d/numa_node 2>/dev/null) $(cat $d/vendor 2>/dev/null)"; done | head -12
