@@ -218,6 +218,73 @@ uint64_t ntedit_hip_reads_bf_size(uint64_t num_elements, uint32_t hash_num, doub
 uint64_t ntedit_hip_reads_default_sketch(const char* const* files, uint32_t n, uint64_t bf_bytes);
 int ntedit_hip_reads_is_gzip(const char* path);
 int ntedit_hip_reads_write_hist(const char* path, const uint64_t f[256], uint64_t F0, uint64_t F1);
+/* The resident store: the reads kept in HBM, packed, so that the passes after pass 1 do not parse the inputs again.
+ *   ntedit_hip_resident_begin (after ntedit_hip_sketch_alloc): from now on every ntedit_hip_sketch_count batch is
+ *           also packed into the context's store, 3 bits per base: per 16 bytes of the batch one u32 of 2-bit codes
+ *           (ACGT, case folded) and one u16 of validity bits (1 for ACGTacgt, 0 for any other byte, the separators
+ *           between reads included), batch boundaries kept.  While the stored bytes stay within cap_bytes; a batch that
+ *           would pass the cap, or a device allocation that fails, releases the whole store (state OVER_CAP /
+ *           NO_MEMORY), and the later passes have to read the inputs again.  Restarts an existing store.
+ *   ntedit_hip_resident_info: its state (NTEDIT_RESIDENT_*), batches, bytes of those batches (their `n`,
+ *           separators included), device bytes it holds, and the cap.
+ *   ntedit_hip_resident_histogram / _insert_solid: the histogram pass and pass 2 (as ntedit_hip_sketch_histogram
+ *           and ntedit_hip_filter_insert_solid over the same batches) over every stored batch, each launched with its
+ *           own n.  The kernels stage the same codes either way, so histogram and filter bytes are identical to those
+ *           of the byte batches.  NTEDIT_E_ARG unless the state is ON.
+ *   ntedit_hip_resident_free: releases it (ntedit_hip_sketch_free does too). */
+#define NTEDIT_RESIDENT_OFF 0
+#define NTEDIT_RESIDENT_ON 1
+#define NTEDIT_RESIDENT_OVER_CAP 2
+#define NTEDIT_RESIDENT_NO_MEMORY 3
+typedef struct ntedit_hip_resident_stats
+{
+	int state;
+	uint64_t batches;
+	uint64_t bases;  /* bytes of the stored batches (reads and separators) */
+	uint64_t bytes;  /* device bytes held */
+	uint64_t cap;
+} ntedit_hip_resident_stats;
+int ntedit_hip_resident_begin(ntedit_hip_ctx* ctx, uint64_t cap_bytes);
+int ntedit_hip_resident_info(ntedit_hip_ctx* ctx, ntedit_hip_resident_stats* st);
+int ntedit_hip_resident_histogram(ntedit_hip_ctx* ctx);
+int ntedit_hip_resident_insert_solid(ntedit_hip_ctx* ctx, int slot, uint32_t cmin);
+void ntedit_hip_resident_free(ntedit_hip_ctx* ctx);
+/* The whole filter build of ntedit-make-reads-bf, shared by it and `ntedit --reads`: the sketch (sketch_counters, as
+ * sized by the caller), pass 1, with solid or hist_path the histogram pass (the --hist file, the --solid cutoff, and
+ * with bf_bytes = 0 the output size from the histogram), the output filter allocated in the PRIMARY slot (counting
+ * with `counts`), pass 2, the sketch freed.  With use_store the reads are kept resident from pass 1 (cap: store_cap
+ * bytes) and the later passes read the store; past the cap they read the files, as without it.  Console lines go to
+ * log(user, to_stdout, line): to_stdout = 0 for a timestamped information line, 1 for a line of standard output.  On
+ * failure the message is ntedit_hip_reads_last_error(ctx); the sketch and the store are freed either way. */
+typedef struct ntedit_hip_reads_build_args
+{
+	const char* const* files;
+	uint32_t n_files;
+	uint32_t k, hash_num;
+	uint32_t cmin;            /* unless solid */
+	int solid;                /* cmin from the histogram (ntedit_hip_reads_solid_cutoff) */
+	int counts;               /* a counting output filter */
+	uint64_t bf_bytes;        /* 0: --num_elements from the histogram (needs solid or hist_path) */
+	double fpr;
+	uint64_t sketch_counters;
+	uint64_t batch_bytes;
+	const char* hist_path;    /* NULL: none */
+	const char* sketch_path;  /* NULL: none (the sketch after pass 1, as a counting filter file) */
+	int use_store;
+	uint64_t store_cap;
+	void (*log)(void* user, int to_stdout, const char* line);
+	void* user;
+} ntedit_hip_reads_build_args;
+typedef struct ntedit_hip_reads_build_result
+{
+	uint32_t cmin;                        /* the one pass 2 used */
+	uint64_t bf_bytes;                    /* the output filter's size */
+	ntedit_hip_reads_pass_stats pass[3];  /* by NTEDIT_READS_PASS_* (HIST zero when it did not run) */
+	int store_state;                      /* after pass 1 (OFF without use_store) */
+	uint64_t store_bytes;                 /* device bytes the store held after pass 1 */
+	double ms_total;
+} ntedit_hip_reads_build_result;
+int ntedit_hip_reads_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res);
 
 
 /* ---- hot path ------------------------------------------------------------

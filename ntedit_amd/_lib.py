@@ -69,6 +69,32 @@ class ReadsPassStats(ctypes.Structure):
 
 MERGE_SAT_ADD, MERGE_OR, MERGE_MAX = 0, 1, 2
 READS_PASS_COUNT, READS_PASS_HIST, READS_PASS_SOLID = 0, 1, 2
+RESIDENT_OFF, RESIDENT_ON, RESIDENT_OVER_CAP, RESIDENT_NO_MEMORY = 0, 1, 2, 3
+
+
+class ResidentStats(ctypes.Structure):
+    """ntedit_hip_resident_stats"""
+    _fields_ = [("state", ctypes.c_int), ("batches", ctypes.c_uint64), ("bases", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("cap", ctypes.c_uint64)]
+
+
+READS_LOG_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
+
+
+class ReadsBuildArgs(ctypes.Structure):
+    """ntedit_hip_reads_build_args"""
+    _fields_ = [("files", ctypes.POINTER(ctypes.c_char_p)), ("n_files", ctypes.c_uint32), ("k", ctypes.c_uint32),
+                ("hash_num", ctypes.c_uint32), ("cmin", ctypes.c_uint32), ("solid", ctypes.c_int),
+                ("counts", ctypes.c_int), ("bf_bytes", ctypes.c_uint64), ("fpr", ctypes.c_double),
+                ("sketch_counters", ctypes.c_uint64), ("batch_bytes", ctypes.c_uint64), ("hist_path", ctypes.c_char_p),
+                ("sketch_path", ctypes.c_char_p), ("use_store", ctypes.c_int), ("store_cap", ctypes.c_uint64),
+                ("log", READS_LOG_FN), ("user", ctypes.c_void_p)]
+
+
+class ReadsBuildResult(ctypes.Structure):
+    """ntedit_hip_reads_build_result"""
+    _fields_ = [("cmin", ctypes.c_uint32), ("bf_bytes", ctypes.c_uint64), ("passes", ReadsPassStats * 3),
+                ("store_state", ctypes.c_int), ("store_bytes", ctypes.c_uint64), ("ms_total", ctypes.c_double)]
 
 
 class Segment(ctypes.Structure):
@@ -125,6 +151,8 @@ EXPORTS = [
     "ntedit_hip_sketch_set_device", "ntedit_hip_sketch_info", "ntedit_hip_merge_bytes", "ntedit_hip_reads_pass",
     "ntedit_hip_reads_range_text", "ntedit_hip_reads_bf_size", "ntedit_hip_reads_default_sketch",
     "ntedit_hip_reads_is_gzip", "ntedit_hip_reads_write_hist",
+    "ntedit_hip_resident_begin", "ntedit_hip_resident_info", "ntedit_hip_resident_histogram",
+    "ntedit_hip_resident_insert_solid", "ntedit_hip_resident_free", "ntedit_hip_reads_build",
 ]
 
 _lib = None
@@ -242,5 +270,13 @@ def load():
     lib.ntedit_hip_reads_default_sketch.restype = u64
     lib.ntedit_hip_reads_is_gzip.argtypes = [ctypes.c_char_p]
     lib.ntedit_hip_reads_write_hist.argtypes = [ctypes.c_char_p, vp, u64, u64]
+    # the resident store and the shared build (ntedit --reads)
+    lib.ntedit_hip_resident_begin.argtypes = [vp, u64]
+    lib.ntedit_hip_resident_info.argtypes = [vp, ctypes.POINTER(ResidentStats)]
+    lib.ntedit_hip_resident_histogram.argtypes = [vp]
+    lib.ntedit_hip_resident_insert_solid.argtypes = [vp, ci, u32]
+    lib.ntedit_hip_resident_free.argtypes = [vp]
+    lib.ntedit_hip_resident_free.restype = None
+    lib.ntedit_hip_reads_build.argtypes = [vp, ctypes.POINTER(ReadsBuildArgs), ctypes.POINTER(ReadsBuildResult)]
     _lib = lib
     return lib

@@ -7,6 +7,9 @@
 //                             est(x) (byte atomic max)
 //   k_hist<H, POW2>           histogram pass: bin est(x) of a 256-bin histogram of every k-mer occurrence, summed in
 //                             per-wave LDS sub-histograms and flushed once per block (one 64-bit add per non-zero bin)
+//   k_pack                    after k_count, when the context keeps the reads resident: a batch packed into the store,
+//                             per 16 bases one u32 of 2-bit codes and one u16 of validity bits (3 bits per base)
+//   k_hist / k_solid <.., PACKED = true>  the same passes staged from a stored batch instead of its bytes
 //   k_nonzero                 non-zero counters of the sketch (occupancy)
 //   k_merge<OP>               n_src equal byte chunks folded into one: saturating add (sketches), OR (plain filters),
 //                             max (counting filters) -- the merge of a sharded build
@@ -64,21 +67,59 @@ struct RdFilter // one filter as the reads kernels address it
 	Filter f; // geometry only (f.data unused)
 };
 
-// prologue shared by the walking kernels: seed tables + LUT in LDS, the tile's codes staged
+// One stored batch of the resident store: group g holds bases [16 g, 16 g + 16) of the batch's bytes, base j of the
+// group in bits 2j..2j+1 of codes[g] (0..3 = ACGT, case folded) and bit j of valid[g] (1: one of ACGTacgt; 0: anything
+// else, the '\n' between reads included, and every position past n).  groups = ceil(n / 16), both arrays that long.
+struct RdPacked
+{
+	const u32* codes;
+	const u16* valid;
+};
+
+// prologue shared by the walking kernels: seed tables + LUT in LDS, the tile's codes staged -- from the batch's bytes,
+// or (PACKED) from its stored groups: the same LDS codes either way, RD_BAD where a base is not ACGTacgt or lies past n
+template<bool PACKED>
 __device__ __forceinline__ void
-rd_stage(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, u64* s_tab, u8* s_lut, u8* s_codes)
+rd_stage(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __restrict__ tabs, u64* s_tab, u8* s_lut,
+         u8* s_codes)
 {
 	const u32 tid = threadIdx.x;
 	if (tid < TAB_WORDS) {
 		s_tab[tid] = tabs[tid];
 	}
-	{
+	if (!PACKED) {
 		const u8 code = char_code((u8)tid);
 		s_lut[tid] = code <= 3 ? code : RD_BAD; // k-mers of ACGTacgt only (as the filter build)
 	}
 	__syncthreads();
 	const u64 tile_base = (u64)blockIdx.x * RD_TILE;
 	const u32 n_chunks = (RD_TILE + k - 1 + 15) / 16;
+	if (PACKED) {
+		// one group of 16 bases per lane: 6 bytes in, 16 LDS codes out (RD_TILE is a multiple of 16, so a tile starts
+		// on a group); groups past the batch are all RD_BAD, as the byte path pads with '\n'
+		const u64 groups = (n + 15) / 16;
+		for (u32 c = tid; c < n_chunks; c += RD_TPB) {
+			const u64 g = tile_base / 16 + c;
+			u32 codes = 0, valid = 0;
+			if (g < groups) {
+				codes = pk.codes[g];
+				valid = pk.valid[g];
+			}
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				u32 x = 0;
+#pragma unroll
+				for (int b = 0; b < 4; b++) {
+					const int j = q * 4 + b;
+					const u32 code = (valid >> j) & 1u ? (codes >> (2 * j)) & 3u : (u32)RD_BAD;
+					x |= code << (8 * b);
+				}
+				*reinterpret_cast<u32*>(&s_codes[rd_lds(c * 16 + q * 4)]) = x;
+			}
+		}
+		__syncthreads();
+		return;
+	}
 	for (u32 c = tid; c < n_chunks; c += RD_TPB) {
 		const u64 g = tile_base + (u64)c * 16;
 		u32 w[4];
@@ -168,15 +209,15 @@ rd_est(const u8* sk_bytes, const Filter& f, const u64 (&hv)[H])
 // One thread walks 64 consecutive k-mer starts of the tile.  The hash state is exact once k codes of ACGT have
 // entered since the last RD_BAD (an RD_BAD code has zero seeds both ways, so it leaves nothing behind).
 // PASS 0: k_count; 1: k_solid into bits; 2: k_solid into counters; 3: k_hist into s_hist (this wave's 256 bins)
-template<int H, bool POW2, int PASS>
+template<int H, bool POW2, int PASS, bool PACKED = false>
 __device__ __forceinline__ void
-rd_walk(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, const DevParams& p, RdFilter sk, RdFilter out, u32 cmin,
-        u32* s_hist)
+rd_walk(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __restrict__ tabs, const DevParams& p, RdFilter sk,
+        RdFilter out, u32 cmin, u32* s_hist)
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
 	__shared__ __attribute__((aligned(16))) u8 s_codes[RD_LDS_BYTES];
-	rd_stage(seq, n, k, tabs, s_tab, s_lut, s_codes);
+	rd_stage<PACKED>(seq, pk, n, k, tabs, s_tab, s_lut, s_codes);
 
 	const u32 x0 = threadIdx.x * RD_L;
 	HashState hs = { 0, 0 };
@@ -232,14 +273,15 @@ template<int H, bool POW2>
 __global__ __launch_bounds__(RD_TPB) void
 k_count(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk)
 {
-	rd_walk<H, POW2, 0>(seq, n, k, tabs, p, sk, sk, 0, nullptr);
+	rd_walk<H, POW2, 0>(seq, RdPacked{}, n, k, tabs, p, sk, sk, 0, nullptr);
 }
 
-template<int H, bool POW2, bool COUNTS>
+template<int H, bool POW2, bool COUNTS, bool PACKED>
 __global__ __launch_bounds__(RD_TPB) void
-k_solid(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk, RdFilter out, u32 cmin)
+k_solid(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk,
+        RdFilter out, u32 cmin)
 {
-	rd_walk<H, POW2, COUNTS ? 2 : 1>(seq, n, k, tabs, p, sk, out, cmin, nullptr);
+	rd_walk<H, POW2, COUNTS ? 2 : 1, PACKED>(seq, pk, n, k, tabs, p, sk, out, cmin, nullptr);
 }
 
 // Occurrences crowd into a few bins near the coverage peak, so each wave adds into a sub-histogram of its own: a
@@ -248,16 +290,17 @@ k_solid(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, 
 constexpr int RD_HIST_BINS = 256;
 constexpr int RD_HIST_SUBS = RD_TPB / 64;
 
-template<int H, bool POW2>
+template<int H, bool POW2, bool PACKED>
 __global__ __launch_bounds__(RD_TPB) void
-k_hist(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk, unsigned long long* hist)
+k_hist(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk,
+       unsigned long long* hist)
 {
 	__shared__ u32 s_hist[RD_HIST_SUBS * RD_HIST_BINS];
 	for (u32 i = threadIdx.x; i < RD_HIST_SUBS * RD_HIST_BINS; i += RD_TPB) {
 		s_hist[i] = 0;
 	}
 	// (rd_stage's barriers order the zeroing before any add)
-	rd_walk<H, POW2, 3>(seq, n, k, tabs, p, sk, sk, 0, s_hist + (threadIdx.x / 64) * RD_HIST_BINS);
+	rd_walk<H, POW2, 3, PACKED>(seq, pk, n, k, tabs, p, sk, sk, 0, s_hist + (threadIdx.x / 64) * RD_HIST_BINS);
 	__syncthreads();
 	static_assert(RD_TPB == RD_HIST_BINS, "one thread per bin flushes");
 	u32 sum = 0;
@@ -267,6 +310,40 @@ k_hist(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, D
 	}
 	if (sum) {
 		atomicAdd(&hist[threadIdx.x], (unsigned long long)sum);
+	}
+}
+
+// One thread per group of 16 bases of a batch of n bytes: its codes and validity bits (RdPacked).  Bytes past n are
+// invalid, so the last group's tail reads nothing of the batch.
+__global__ __launch_bounds__(256) void
+k_pack(const u8* __restrict__ seq, u64 n, u32* __restrict__ codes, u16* __restrict__ valid)
+{
+	const u64 groups = (n + 15) / 16;
+	for (u64 g = (u64)blockIdx.x * 256 + threadIdx.x; g < groups; g += (u64)gridDim.x * 256) {
+		const u64 at = g * 16;
+		u32 c = 0, v = 0;
+		if (at + 16 <= n && ((uintptr_t)(seq + at) & 15) == 0) {
+			const uint4 w = *reinterpret_cast<const uint4*>(seq + at);
+			const u32 words[4] = { w.x, w.y, w.z, w.w };
+#pragma unroll
+			for (int j = 0; j < 16; j++) {
+				const u8 code = char_code((u8)(words[j / 4] >> (8 * (j % 4))));
+				if (code <= 3) {
+					c |= (u32)code << (2 * j);
+					v |= 1u << j;
+				}
+			}
+		} else {
+			for (int j = 0; j < 16 && at + j < n; j++) {
+				const u8 code = char_code(seq[at + j]);
+				if (code <= 3) {
+					c |= (u32)code << (2 * j);
+					v |= 1u << j;
+				}
+			}
+		}
+		codes[g] = c;
+		valid[g] = (u16)v;
 	}
 }
 
@@ -378,8 +455,49 @@ struct ReadsState
 	u64 seq_cap = 0;
 	unsigned long long* d_total = nullptr;
 	unsigned long long* d_hist = nullptr; // 256 bins of k_hist (zeroed at ntedit_hip_sketch_alloc)
+	// the resident store (ntedit_hip_resident_begin): every batch of pass 1, packed, while it stays within store_cap
+	struct Stored
+	{
+		void* mem; // codes (groups u32, padded to 16 bytes), then valid (groups u16)
+		u64 n;
+	};
+	std::vector<Stored> store;
+	u64 store_bytes = 0, store_cap = 0;
+	int store_state = NTEDIT_RESIDENT_OFF;
 	std::string err;
 };
+
+u64
+stored_groups(u64 n)
+{
+	return (n + 15) / 16;
+}
+
+u64
+stored_bytes(u64 n)
+{
+	return (stored_groups(n) * 4 + 15) / 16 * 16 + stored_groups(n) * 2;
+}
+
+RdPacked
+stored_view(const ReadsState::Stored& b)
+{
+	RdPacked pk;
+	pk.codes = (const u32*)b.mem;
+	pk.valid = (const u16*)((const u8*)b.mem + (stored_groups(b.n) * 4 + 15) / 16 * 16);
+	return pk;
+}
+
+void
+drop_store(ReadsState* s, int state)
+{
+	for (ReadsState::Stored& b : s->store) {
+		(void)hipFree(b.mem);
+	}
+	s->store.clear();
+	s->store_bytes = 0;
+	s->store_state = state;
+}
 
 std::mutex g_reads_mu;
 std::vector<ReadsState*> g_reads;       // one per context that holds a sketch
@@ -432,6 +550,7 @@ release_state(ReadsState* s)
 		(void)hipStreamSynchronize(s->stream);
 		(void)hipStreamDestroy(s->stream);
 	}
+	drop_store(s, NTEDIT_RESIDENT_OFF);
 	for (void* p : { s->adopted ? nullptr : (void*)s->sketch, (void*)s->d_tab, (void*)s->d_seq, (void*)s->d_total, (void*)s->d_hist }) {
 		if (p) {
 			(void)hipFree(p);
@@ -479,21 +598,22 @@ stage(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int on_d
 	return 0;
 }
 
-template<bool POW2, int PASS>
+template<bool POW2, int PASS, bool PACKED>
 void
-launch_walk(ReadsState* s, const u8* d_seq, u64 n, u64 tiles, RdFilter sk, RdFilter out, u32 cmin)
+launch_walk(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, RdFilter sk, RdFilter out, u32 cmin)
 {
+	static_assert(!(PACKED && PASS == 0), "pass 1 reads bytes");
 	dim3 grid((unsigned)tiles), block(RD_TPB);
 #define RD_LAUNCH(H)                                                                                               \
 	case H:                                                                                                        \
 		if constexpr (PASS == 0) {                                                                                 \
 			hipLaunchKernelGGL((k_count<H, POW2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, s->dp, sk); \
 		} else if constexpr (PASS == 3) {                                                                          \
-			hipLaunchKernelGGL((k_hist<H, POW2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, s->dp, sk,  \
-			                   s->d_hist);                                                                         \
+			hipLaunchKernelGGL((k_hist<H, POW2, PACKED>), grid, block, 0, s->stream, d_seq, pk, n, s->k, s->d_tab, \
+			                   s->dp, sk, s->d_hist);                                                              \
 		} else {                                                                                                   \
-			hipLaunchKernelGGL((k_solid<H, POW2, PASS == 2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, \
-			                   s->dp, sk, out, cmin);                                                              \
+			hipLaunchKernelGGL((k_solid<H, POW2, PASS == 2, PACKED>), grid, block, 0, s->stream, d_seq, pk, n, s->k, \
+			                   s->d_tab, s->dp, sk, out, cmin);                                                    \
 		}                                                                                                          \
 		break
 	switch (s->hash_num) {
@@ -509,6 +629,60 @@ launch_walk(ReadsState* s, const u8* d_seq, u64 n, u64 tiles, RdFilter sk, RdFil
 		break;
 	}
 #undef RD_LAUNCH
+}
+
+RdFilter
+sketch_view(const ReadsState* s)
+{
+	RdFilter sk;
+	sk.words = (u32*)s->sketch;
+	sk.f = geometry(s->counters, s->hash_num, true);
+	return sk;
+}
+
+template<bool PACKED>
+void
+launch_pass(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, int pass, RdFilter out, u32 cmin)
+{
+	const RdFilter sk = sketch_view(s);
+	const bool pow2 = sk.f.mask != 0;
+	if (pass == 1) {
+		pow2 ? launch_walk<true, 1, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin)
+		     : launch_walk<false, 1, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin);
+	} else if (pass == 2) {
+		pow2 ? launch_walk<true, 2, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin)
+		     : launch_walk<false, 2, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin);
+	} else if (pass == 3) {
+		pow2 ? launch_walk<true, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin)
+		     : launch_walk<false, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin);
+	} else if constexpr (!PACKED) {
+		pow2 ? launch_walk<true, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin)
+		     : launch_walk<false, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin);
+	}
+}
+
+// after k_count: the batch packed into the resident store, or the store dropped when it would pass its cap or an
+// allocation fails (the later passes then read the inputs again)
+void
+store_batch(ReadsState* s, const u8* d_seq, u64 n)
+{
+	const u64 bytes = stored_bytes(n);
+	if (s->store_bytes + bytes > s->store_cap) {
+		drop_store(s, NTEDIT_RESIDENT_OVER_CAP);
+		return;
+	}
+	ReadsState::Stored b = { nullptr, n };
+	if (hipMalloc(&b.mem, bytes) != hipSuccess) {
+		(void)hipGetLastError(); // (a failed allocation leaves no error behind for the next check)
+		drop_store(s, NTEDIT_RESIDENT_NO_MEMORY);
+		return;
+	}
+	s->store.push_back(b);
+	s->store_bytes += bytes;
+	const RdPacked pk = stored_view(b);
+	const u64 groups = stored_groups(n), want = (groups + 255) / 256;
+	hipLaunchKernelGGL(k_pack, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, s->stream, d_seq, n,
+	                   (u32*)pk.codes, (u16*)pk.valid);
 }
 
 int
@@ -527,21 +701,58 @@ run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int o
 	if (rc) {
 		return rc;
 	}
-	RdFilter sk;
-	sk.words = (u32*)s->sketch;
-	sk.f = geometry(s->counters, s->hash_num, true);
-	const bool pow2 = sk.f.mask != 0;
-	if (pass == 0) {
-		pow2 ? launch_walk<true, 0>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 0>(s, d_seq, n, tiles, sk, out, cmin);
-	} else if (pass == 1) {
-		pow2 ? launch_walk<true, 1>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 1>(s, d_seq, n, tiles, sk, out, cmin);
-	} else if (pass == 2) {
-		pow2 ? launch_walk<true, 2>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 2>(s, d_seq, n, tiles, sk, out, cmin);
-	} else {
-		pow2 ? launch_walk<true, 3>(s, d_seq, n, tiles, sk, out, cmin) : launch_walk<false, 3>(s, d_seq, n, tiles, sk, out, cmin);
-	}
+	launch_pass<false>(s, d_seq, RdPacked{}, n, tiles, pass, out, cmin);
 	RD_TRY(c, hipGetLastError());
+	if (pass == 0 && s->store_state == NTEDIT_RESIDENT_ON) {
+		store_batch(s, d_seq, n);
+		RD_TRY(c, hipGetLastError());
+	}
 	RD_TRY(c, hipStreamSynchronize(s->stream));
+	return 0;
+}
+
+// the histogram pass or pass 2 over every stored batch, each launched with its own n as it was counted
+int
+run_store_pass(const ntedit_hip_ctx* c, ReadsState* s, int pass, RdFilter out, u32 cmin)
+{
+	RD_TRY(c, hipSetDevice(s->device));
+	if (s->store_state != NTEDIT_RESIDENT_ON) {
+		return rfail(c, NTEDIT_E_ARG, "resident_pass: the context holds no complete resident store");
+	}
+	for (const ReadsState::Stored& b : s->store) {
+		const u64 tiles = (b.n + RD_TILE - 1) / RD_TILE;
+		launch_pass<true>(s, nullptr, stored_view(b), b.n, tiles, pass, out, cmin);
+		RD_TRY(c, hipGetLastError());
+	}
+	RD_TRY(c, hipStreamSynchronize(s->stream));
+	return 0;
+}
+
+// the output filter of pass 2 (filter_insert_solid and the store's pass 2 check it alike)
+int
+solid_target(const ntedit_hip_ctx* c, const ReadsState* s, int slot, u32 cmin, const char* what, RdFilter* out)
+{
+	if (cmin < 1 || cmin > 255) {
+		return rfail(c, NTEDIT_E_ARG, "%s: cmin = %u: needs 1 <= cmin <= 255", what, cmin);
+	}
+	uint32_t k = 0, hash_num = 0;
+	uint64_t nbytes = 0;
+	int counting = 0;
+	void* data = ntedit_hip_filter_device_ptr(c, slot);
+	if (!data || ntedit_hip_filter_info(c, slot, &k, &hash_num, &nbytes, &counting) != 0) {
+		return rfail(c, NTEDIT_E_NOFILTER, "%s: filter slot %d not set", what, slot);
+	}
+	if (k != s->k || hash_num != s->hash_num) {
+		return rfail(c, NTEDIT_E_ARG, "%s: the filter has k = %u, hash_num = %u, the sketch k = %u, hash_num = %u", what,
+		             k, hash_num, s->k, s->hash_num);
+	}
+	hipPointerAttribute_t attr;
+	RD_TRY(c, hipPointerGetAttributes(&attr, data));
+	if (attr.device != s->device) {
+		return rfail(c, NTEDIT_E_ARG, "%s: the filter is on device %d, the sketch on device %d", what, attr.device, s->device);
+	}
+	out->words = (u32*)data;
+	out->f = geometry(counting ? nbytes : nbytes * 8, hash_num, counting != 0);
 	return 0;
 }
 
@@ -895,29 +1106,84 @@ ntedit_hip_filter_insert_solid(ntedit_hip_ctx* c, int slot, const char* bases, u
 	if (!s) {
 		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: no sketch (ntedit_hip_sketch_alloc)");
 	}
-	if (cmin < 1 || cmin > 255) {
-		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: cmin = %u: needs 1 <= cmin <= 255", cmin);
+	RdFilter out;
+	const int rc = solid_target(c, s, slot, cmin, "filter_insert_solid", &out);
+	if (rc) {
+		return rc;
 	}
-	uint32_t k = 0, hash_num = 0;
-	uint64_t nbytes = 0;
-	int counting = 0;
-	void* data = ntedit_hip_filter_device_ptr(c, slot);
-	if (!data || ntedit_hip_filter_info(c, slot, &k, &hash_num, &nbytes, &counting) != 0) {
-		return rfail(c, NTEDIT_E_NOFILTER, "filter_insert_solid: filter slot %d not set", slot);
+	return run_pass(c, s, bases, n, on_device, out.f.counting ? 2 : 1, out, cmin);
+}
+
+int
+ntedit_hip_resident_begin(ntedit_hip_ctx* c, uint64_t cap_bytes)
+{
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return c ? rfail(c, NTEDIT_E_ARG, "resident_begin: no sketch (ntedit_hip_sketch_alloc)") : NTEDIT_E_ARG;
 	}
-	if (k != s->k || hash_num != s->hash_num) {
-		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: the filter has k = %u, hash_num = %u, the sketch k = %u, hash_num = %u",
-		             k, hash_num, s->k, s->hash_num);
+	RD_TRY(c, hipSetDevice(s->device));
+	RD_TRY(c, hipStreamSynchronize(s->stream));
+	drop_store(s, NTEDIT_RESIDENT_ON);
+	s->store_cap = cap_bytes;
+	return 0;
+}
+
+int
+ntedit_hip_resident_info(ntedit_hip_ctx* c, ntedit_hip_resident_stats* st)
+{
+	ReadsState* s = find_state(c);
+	if (!s || !st) {
+		return c ? rfail(c, NTEDIT_E_ARG, "resident_info: bad argument or no sketch") : NTEDIT_E_ARG;
 	}
-	hipPointerAttribute_t attr;
-	RD_TRY(c, hipPointerGetAttributes(&attr, data));
-	if (attr.device != s->device) {
-		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid: the filter is on device %d, the sketch on device %d", attr.device, s->device);
+	st->state = s->store_state;
+	st->batches = s->store.size();
+	st->bases = 0;
+	for (const ReadsState::Stored& b : s->store) {
+		st->bases += b.n;
+	}
+	st->bytes = s->store_bytes;
+	st->cap = s->store_cap;
+	return 0;
+}
+
+int
+ntedit_hip_resident_histogram(ntedit_hip_ctx* c)
+{
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return c ? rfail(c, NTEDIT_E_ARG, "resident_histogram: no sketch (ntedit_hip_sketch_alloc)") : NTEDIT_E_ARG;
+	}
+	RdFilter none = {};
+	return run_store_pass(c, s, 3, none, 0);
+}
+
+int
+ntedit_hip_resident_insert_solid(ntedit_hip_ctx* c, int slot, uint32_t cmin)
+{
+	if (!c || slot < 0 || slot > 1) {
+		return c ? rfail(c, NTEDIT_E_ARG, "resident_insert_solid: bad argument") : NTEDIT_E_ARG;
+	}
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return rfail(c, NTEDIT_E_ARG, "resident_insert_solid: no sketch (ntedit_hip_sketch_alloc)");
 	}
 	RdFilter out;
-	out.words = (u32*)data;
-	out.f = geometry(counting ? nbytes : nbytes * 8, hash_num, counting != 0);
-	return run_pass(c, s, bases, n, on_device, counting ? 2 : 1, out, cmin);
+	const int rc = solid_target(c, s, slot, cmin, "resident_insert_solid", &out);
+	if (rc) {
+		return rc;
+	}
+	return run_store_pass(c, s, out.f.counting ? 2 : 1, out, cmin);
+}
+
+void
+ntedit_hip_resident_free(ntedit_hip_ctx* c)
+{
+	ReadsState* s = find_state(c);
+	if (s) {
+		(void)hipSetDevice(s->device);
+		(void)hipStreamSynchronize(s->stream);
+		drop_store(s, NTEDIT_RESIDENT_OFF);
+	}
 }
 
 } // extern "C"

@@ -22,6 +22,7 @@
 #include <mutex>
 #include <sys/stat.h>
 #include <thread>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,7 +42,7 @@ static const char USAGE[] = PROGRAM
     " Options:\n"
     "	-t,	number of host threads rendering the output (contigs are polished on the GPU)\n"
     "	-f,	draft genome assembly (FASTA, Multi-FASTA, and/or gzipped compatible), REQUIRED\n"
-    "	-r,	Bloom filter (BF) or counting BF (CBF) file (btllib format, e.g. from ntStat v1.0.0+), REQUIRED\n"
+    "	-r,	Bloom filter (BF) or counting BF (CBF) file (btllib format, e.g. from ntStat v1.0.0+), REQUIRED unless --reads\n"
     "	-e,	secondary BF with k-mers to reject, OPTIONAL\n"
     "	-b,	output file prefix, OPTIONAL\n"
     "	-z,	minimum contig length [default=100]\n"
@@ -66,6 +67,22 @@ static const char USAGE[] = PROGRAM
     "	--shard I/N,	polish share I of N of the contigs, split by BASES (greedy longest-first over whole contigs, the\n"
     "			same on every process); writes <prefix>.index.tsv for `python -m ntedit_amd.merge`.\n"
     "			(`python -m ntedit_amd.run` is the full multi-GPU driver: one filter broadcast, large contigs cut)\n"
+    "\n Polishing straight from reads (--reads replaces -r; the filter is the one ntedit-make-reads-bf builds with the\n"
+    " same settings, built on the GPU into the context that polishes, no filter file needed):\n"
+    "	--reads FILE...,	input reads, FASTA or FASTQ, plain or gzip (1 or more files)\n"
+    "	-k,	k-mer size (bp), 12 to 200, REQUIRED with --reads (accepted and ignored without it)\n"
+    "	--cutoff C,	minimum k-mer count of the filter, 1 to 255 (ntedit-make-reads-bf -c)\n"
+    "	--solid,	take the minimum count from the k-mer histogram instead (give --cutoff or --solid)\n"
+    "	--counts,	build a counting filter (enables -p / -q)\n"
+    "	--hashes H,	number of hash functions, 1 to 8 [default=3]\n"
+    "	--fpr F,	false positive rate of the filter (with --num_elements) [default=0.01]\n"
+    "	--bf BYTES,	filter size in bytes\n"
+    "	--num_elements N,	approximate number of solid k-mers (one of --bf / --num_elements is required, unless\n"
+    "			--solid or --hist: then the filter is sized from the k-mer histogram)\n"
+    "	--sketch_bytes S,	counters of the count-min sketch [default: as ntedit-make-reads-bf]\n"
+    "	--hist FILE,	write the k-mer histogram (ntCard's text format)\n"
+    "	--save_bf FILE,	write the filter that was built (the same bytes as ntedit-make-reads-bf -o); its name is the\n"
+    "			_r part of the default prefix [default name: reads_k<K>.bf, not written]\n"
     "	--help,		display this message and exit \n"
     "	--version,	output version information and exit\n\n";
 
@@ -82,7 +99,19 @@ enum
 	OPT_EVENT_BUDGET,
 	OPT_NO_MAP,
 	OPT_PACK,
-	OPT_TUNE
+	OPT_TUNE,
+	OPT_CUTOFF,
+	OPT_SOLID,
+	OPT_COUNTS,
+	OPT_HASHES,
+	OPT_FPR,
+	OPT_BF,
+	OPT_NUM_ELEMENTS,
+	OPT_SKETCH_BYTES,
+	OPT_HIST,
+	OPT_SAVE_BF,
+	OPT_READS_BATCH,
+	OPT_STORE_CAP
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -116,6 +145,19 @@ static const struct option longopts[] = {
 	{ "no-map", no_argument, nullptr, OPT_NO_MAP }, // tests: plain FASTA through the streaming reader as well
 	{ "pack", no_argument, nullptr, OPT_PACK }, // batches cross PCIe in the packed form (off: packing costs the reader stage more than the link saves)
 	{ "report", no_argument, nullptr, OPT_REPORT },
+	// --reads (taken out of argv before getopt: it takes one or more files) and the reads filter's options
+	{ "cutoff", required_argument, nullptr, OPT_CUTOFF },
+	{ "solid", no_argument, nullptr, OPT_SOLID },
+	{ "counts", no_argument, nullptr, OPT_COUNTS },
+	{ "hashes", required_argument, nullptr, OPT_HASHES },
+	{ "fpr", required_argument, nullptr, OPT_FPR },
+	{ "bf", required_argument, nullptr, OPT_BF },
+	{ "num_elements", required_argument, nullptr, OPT_NUM_ELEMENTS },
+	{ "sketch_bytes", required_argument, nullptr, OPT_SKETCH_BYTES },
+	{ "hist", required_argument, nullptr, OPT_HIST },
+	{ "save_bf", required_argument, nullptr, OPT_SAVE_BF },
+	{ "batch_bytes", required_argument, nullptr, OPT_READS_BATCH }, // tests: many small read batches
+	{ "resident_cap", required_argument, nullptr, OPT_STORE_CAP }, // tests: the resident store's cap (0: off)
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -149,6 +191,45 @@ parse(int c, const char* arg, T& out)
 		exit(EXIT_FAILURE);
 	}
 }
+
+// a whole non-negative decimal number of a long option, or exit
+static uint64_t
+parse_count(const char* name, const char* arg)
+{
+	char* end = nullptr;
+	errno = 0;
+	const unsigned long long v = arg && *arg && *arg != '-' && *arg != '+' ? strtoull(arg, &end, 10) : 0;
+	if (!arg || !*arg || *arg == '-' || *arg == '+' || errno || *end) {
+		fprintf(stderr, PROGRAM ": invalid option: `%s %s'\n", name, arg ? arg : "");
+		exit(EXIT_FAILURE);
+	}
+	return v;
+}
+
+static void
+refuse(const std::string& why)
+{
+	fprintf(stderr, PROGRAM ": error: %s\nTry `" PROGRAM " --help' for more information.\n", why.c_str());
+	exit(EXIT_FAILURE);
+}
+
+// the reads filter build's console lines (ntedit_hip_reads_build_args.log), as ntedit-make-reads-bf prints them
+static void
+reads_log(void*, int to_stdout, const char* line)
+{
+	if (to_stdout) {
+		printf("%s\n", line);
+		fflush(stdout);
+		return;
+	}
+	char ts[64];
+	time_t now = time(nullptr);
+	strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", localtime(&now));
+	fprintf(stderr, "[%s] [INFO] %s\n", ts, line);
+}
+
+// the resident store's default cap: 48 GiB of packed reads (128 Gbases at 3 bits per base)
+static const uint64_t RESIDENT_CAP_DEFAULT = 48ull << 30;
 
 struct Batch
 {
@@ -254,6 +335,30 @@ main(int argc, char** argv)
 	unsigned shard_i = 0, shard_n = 1;
 	bool die = false, no_map = false, no_pack = true;
 	std::vector<std::pair<std::string, unsigned long long>> tunes;
+	// --reads FILE...: the files up to the next option (taken out here, getopt takes one argument per option)
+	std::vector<std::string> read_files;
+	bool reads_mode = false;
+	std::vector<char*> args;
+	for (int i = 0; i < argc; i++) {
+		if (i > 0 && strcmp(argv[i], "--reads") == 0) {
+			reads_mode = true;
+			while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] != 0)) {
+				read_files.push_back(argv[++i]);
+			}
+			continue;
+		}
+		args.push_back(argv[i]);
+	}
+	args.push_back(nullptr);
+	argc = (int)args.size() - 1;
+	argv = args.data();
+	std::string k_arg, hist_out, save_bf;
+	bool have_k = false, have_cutoff = false, solid = false, counts = false, have_bf = false, have_ne = false;
+	bool shard_given = false;
+	uint64_t cutoff = 0, hashes = 3, bf_bytes = 0, num_elements = 0, sketch_bytes = 0, reads_batch = 256ull << 20;
+	uint64_t store_cap = RESIDENT_CAP_DEFAULT;
+	double fpr = 0.01;
+	std::vector<std::string> reads_only; // reads options given (refused without --reads)
 	for (int c; (c = getopt_long(argc, argv, shortopts, longopts, nullptr)) != -1;) {
 		switch (c) {
 		case '?':
@@ -326,7 +431,66 @@ main(int argc, char** argv)
 			parse(c, optarg, p.max_threshold);
 			break;
 		case 'k':
-			break; // accepted and ignored (the reference rejects it: no `case 'k'`, ntedit.cpp:2360-2363)
+			// without --reads: accepted and ignored (the reference rejects it: no `case 'k'`, ntedit.cpp:2360-2363)
+			k_arg = optarg;
+			have_k = true;
+			break;
+		case OPT_CUTOFF:
+			cutoff = parse_count("--cutoff", optarg);
+			have_cutoff = true;
+			reads_only.push_back("--cutoff");
+			break;
+		case OPT_SOLID:
+			solid = true;
+			reads_only.push_back("--solid");
+			break;
+		case OPT_COUNTS:
+			counts = true;
+			reads_only.push_back("--counts");
+			break;
+		case OPT_HASHES:
+			hashes = parse_count("--hashes", optarg);
+			reads_only.push_back("--hashes");
+			break;
+		case OPT_FPR: {
+			char* end = nullptr;
+			fpr = strtod(optarg, &end);
+			if (*end || !(fpr > 0.0 && fpr < 1.0)) {
+				refuse(std::string("--fpr ") + optarg + ": needs a number between 0 and 1");
+			}
+			reads_only.push_back("--fpr");
+			break;
+		}
+		case OPT_BF:
+			bf_bytes = parse_count("--bf", optarg);
+			have_bf = true;
+			reads_only.push_back("--bf");
+			break;
+		case OPT_NUM_ELEMENTS:
+			num_elements = parse_count("--num_elements", optarg);
+			have_ne = true;
+			reads_only.push_back("--num_elements");
+			break;
+		case OPT_SKETCH_BYTES:
+			sketch_bytes = parse_count("--sketch_bytes", optarg);
+			reads_only.push_back("--sketch_bytes");
+			break;
+		case OPT_HIST:
+			hist_out = optarg;
+			reads_only.push_back("--hist");
+			break;
+		case OPT_SAVE_BF:
+			save_bf = optarg;
+			reads_only.push_back("--save_bf");
+			break;
+		case OPT_READS_BATCH:
+			reads_batch = parse_count("--batch_bytes", optarg);
+			reads_only.push_back("--batch_bytes");
+			break;
+		case OPT_STORE_CAP:
+			store_cap = parse_count("--resident_cap", optarg);
+			reads_only.push_back("--resident_cap");
+			break;
 		case OPT_GPU:
 			parse(c, optarg, gpu);
 			break;
@@ -345,6 +509,7 @@ main(int argc, char** argv)
 				fprintf(stderr, PROGRAM ": invalid option: `--shard %s'\n", optarg);
 				exit(EXIT_FAILURE);
 			}
+			shard_given = true;
 			break;
 		case OPT_REPORT:
 			report = 1;
@@ -393,7 +558,59 @@ main(int argc, char** argv)
 	} else {
 		die_unreadable(draft);
 	}
-	if (bf.empty()) {
+	if (reads_mode) {
+		// every refusal of --reads before the device is opened and before any file is written
+		if (!bf.empty()) {
+			refuse("--reads and -r: give one of them (--reads builds the filter that -r would load)");
+		}
+		if (read_files.empty()) {
+			refuse("--reads: 1 or more files expected");
+		}
+		if (shard_given) {
+			refuse("--reads and --shard: every shard would build the whole filter again; build it once with "
+			       "ntedit-make-reads-bf and give each shard -r");
+		}
+		if (!have_k) {
+			refuse("-k: required with --reads");
+		}
+		uint64_t kv = 0;
+		{
+			char* end = nullptr;
+			errno = 0;
+			kv = strtoull(k_arg.c_str(), &end, 10);
+			if (k_arg.empty() || k_arg[0] == '-' || k_arg[0] == '+' || errno || *end || kv < 12 || kv > 200) {
+				refuse("-k " + k_arg + ": k must be between 12 and 200");
+			}
+		}
+		if (have_cutoff && solid) {
+			refuse("--cutoff and --solid: give one of them (--solid takes the minimum count from the k-mer histogram)");
+		}
+		if (!have_cutoff && !solid) {
+			refuse("--cutoff or --solid: one of them is required with --reads");
+		}
+		if (have_cutoff && (cutoff < 1 || cutoff > 255)) {
+			refuse("--cutoff " + std::to_string(cutoff) + ": the minimum count must be between 1 and 255");
+		}
+		if (hashes < 1 || hashes > 8) {
+			refuse("--hashes " + std::to_string(hashes) + ": the number of hash functions must be between 1 and 8");
+		}
+		if (!have_bf && !have_ne && !solid && hist_out.empty()) {
+			refuse("--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter from the "
+			       "k-mer histogram)");
+		}
+		if ((have_bf && bf_bytes == 0) ||
+		    (!have_bf && have_ne && ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr) == 0)) {
+			refuse("--bf / --num_elements: the filter would be empty");
+		}
+		if (reads_batch < 4096) {
+			refuse("--batch_bytes: at least 4096");
+		}
+		for (const std::string& r : read_files) {
+			die_unreadable(r);
+		}
+	} else if (!reads_only.empty()) {
+		refuse(reads_only[0] + ": only with --reads");
+	} else if (bf.empty()) {
 		fprintf(stderr, PROGRAM ": error: need to specify the Bloom filter file (-r)\n");
 		die = true;
 	} else {
@@ -475,10 +692,66 @@ main(int argc, char** argv)
 		_exit(EXIT_FAILURE); // (_exit: the side thread above may still be running)
 	};
 	time(&rawtime);
-	printf("---------- loading Bloom filter from file           : %s\n", ctime(&rawtime));
-	if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_PRIMARY, bf.c_str()) != 0) {
-		fprintf(stderr, PROGRAM ": error: Bloom filter file supplied (-r) is incorrect. (%s)\n", ntedit_hip_last_error(ctx));
-		fatal();
+	if (reads_mode) {
+		// the filter ntedit-make-reads-bf would write, built into the primary slot (reads_pass.cpp); the reads stay
+		// resident in HBM after pass 1 unless they would pass store_cap, so that the later passes do not parse them again
+		printf("---------- building Bloom filter from reads         : %s\n", ctime(&rawtime));
+		fflush(stdout);
+		std::vector<const char*> paths;
+		for (const std::string& r : read_files) {
+			paths.push_back(r.c_str());
+		}
+		const uint32_t kv = (uint32_t)strtoul(k_arg.c_str(), nullptr, 10);
+		const bool size_from_hist = !have_bf && !have_ne;
+		const uint64_t bf_size = have_bf ? bf_bytes : have_ne ? ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr) : 0;
+		if (sketch_bytes == 0) {
+			sketch_bytes = ntedit_hip_reads_default_sketch(paths.data(), (uint32_t)paths.size(), size_from_hist ? 0 : bf_size);
+		}
+		printf("BF size (bytes): ");
+		if (size_from_hist) {
+			printf("from the k-mer histogram\n");
+		} else {
+			printf("%llu\n", (unsigned long long)bf_size);
+		}
+		printf("Sketch size (counters): %llu\n", (unsigned long long)sketch_bytes);
+		ntedit_hip_reads_build_args ba = {};
+		ba.files = paths.data();
+		ba.n_files = (uint32_t)paths.size();
+		ba.k = kv;
+		ba.hash_num = (uint32_t)hashes;
+		ba.cmin = (uint32_t)cutoff;
+		ba.solid = solid;
+		ba.counts = counts;
+		ba.bf_bytes = bf_size;
+		ba.fpr = fpr;
+		ba.sketch_counters = sketch_bytes;
+		ba.batch_bytes = reads_batch;
+		ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
+		ba.use_store = 1;
+		ba.store_cap = store_cap;
+		ba.log = reads_log;
+		ntedit_hip_reads_build_result br;
+		if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
+			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_reads_last_error(ctx));
+			fatal();
+		}
+		printf("Reads filter built in %.1f ms (minimum count %u; the histogram pass and pass 2 read %s)\n", br.ms_total,
+		       br.cmin, br.store_state == NTEDIT_RESIDENT_ON ? "the resident store" : "the files");
+		if (!save_bf.empty()) {
+			if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, save_bf.c_str()) != 0) {
+				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_bf.c_str());
+				fatal();
+			}
+			printf("Bloom filter saved to %s\n", save_bf.c_str());
+		}
+		// (the _r part of the default prefix: the name ntedit-make-reads-bf would have written it under)
+		bf = save_bf.empty() ? "reads_k" + std::to_string(kv) + ".bf" : save_bf;
+	} else {
+		printf("---------- loading Bloom filter from file           : %s\n", ctime(&rawtime));
+		if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_PRIMARY, bf.c_str()) != 0) {
+			fprintf(stderr, PROGRAM ": error: Bloom filter file supplied (-r) is incorrect. (%s)\n", ntedit_hip_last_error(ctx));
+			fatal();
+		}
 	}
 	uint32_t k = 0, h = 0;
 	uint64_t nbytes = 0;

@@ -112,28 +112,15 @@ die(ntedit_hip_ctx* ctx, const std::string& why)
 	exit(1);
 }
 
-// one pass over every input file, whole (ntedit_hip_reads_pass)
+// the build's console lines (ntedit_hip_reads_build_args.log)
 static void
-run_pass(ntedit_hip_ctx* ctx, int pass, const std::vector<std::string>& files, size_t batch_bytes, unsigned cmin)
+log_line(void*, int to_stdout, const char* line)
 {
-	std::vector<const char*> paths;
-	for (const std::string& f : files) {
-		paths.push_back(f.c_str());
+	if (to_stdout) {
+		std::cout << line << std::endl;
+	} else {
+		log_info(line);
 	}
-	const std::vector<uint64_t> begins(files.size(), 0), ends(files.size(), ~0ull);
-	ntedit_hip_reads_pass_stats st;
-	if (ntedit_hip_reads_pass(ctx, pass, paths.data(), begins.data(), ends.data(), (uint32_t)files.size(), batch_bytes,
-	                          cmin, &st, nullptr, nullptr) != 0) {
-		die(ctx, ntedit_hip_reads_last_error(ctx));
-	}
-	const uint64_t bases = st.bases;
-	const double ms = st.ms_wall, gpu_ms = st.ms_gpu;
-	char line[256];
-	static const char* const names[] = { "1 (count)", "H (histogram)", "2 (solid k-mers)" };
-	snprintf(line, sizeof line, "Pass %s: %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", names[pass],
-	         (unsigned long long)bases, ms, ms > 0 ? bases / ms / 1e6 : 0.0, gpu_ms,
-	         gpu_ms > 0 ? bases / gpu_ms / 1e6 : 0.0);
-	log_info(line);
 }
 
 int
@@ -309,73 +296,30 @@ main(int argc, char** argv)
 		std::cerr << "make_reads_bf: error: " << (ctx ? ntedit_hip_last_error(ctx) : "no HIP device") << std::endl;
 		return 1;
 	}
-	if (ntedit_hip_sketch_alloc(ctx, sketch_bytes, (uint32_t)hashes, (uint32_t)k) != 0) {
+	// sketch, pass 1, the histogram pass, the output filter, pass 2 (reads_pass.cpp, shared with `ntedit --reads`)
+	std::vector<const char*> paths;
+	for (const std::string& f : read_files) {
+		paths.push_back(f.c_str());
+	}
+	ntedit_hip_reads_build_args ba = {};
+	ba.files = paths.data();
+	ba.n_files = (uint32_t)paths.size();
+	ba.k = (uint32_t)k;
+	ba.hash_num = (uint32_t)hashes;
+	ba.cmin = (uint32_t)cmin;
+	ba.solid = solid;
+	ba.counts = counts;
+	ba.bf_bytes = size_from_hist ? 0 : bf_size;
+	ba.fpr = fpr;
+	ba.sketch_counters = sketch_bytes;
+	ba.batch_bytes = batch_bytes;
+	ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
+	ba.sketch_path = sketch_out.empty() ? nullptr : sketch_out.c_str();
+	ba.log = log_line;
+	ntedit_hip_reads_build_result br;
+	if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));
 	}
-	const size_t batch = (size_t)batch_bytes;
-	log_info("Pass 1: counting k-mers");
-	run_pass(ctx, NTEDIT_READS_PASS_COUNT, read_files, batch, (unsigned)cmin);
-	uint64_t nonzero = 0, counters = 0;
-	if (ntedit_hip_sketch_occupancy(ctx, &nonzero, &counters) != 0) {
-		die(ctx, ntedit_hip_reads_last_error(ctx));
-	}
-	std::cout << "Sketch occupancy: " << nonzero << " / " << counters << " counters ("
-	          << (double)nonzero / (double)counters << ")" << std::endl;
-	if (!sketch_out.empty() && ntedit_hip_sketch_save_file(ctx, sketch_out.c_str()) != 0) {
-		die(ctx, ntedit_hip_reads_last_error(ctx));
-	}
-
-	if (gather_hist) {
-		log_info("Histogram pass: the k-mer histogram of the sketch's estimates");
-		run_pass(ctx, NTEDIT_READS_PASS_HIST, read_files, batch, (unsigned)cmin);
-		uint64_t occ[256], f[256], F0 = 0, F1 = 0;
-		if (ntedit_hip_sketch_histogram_download(ctx, occ) != 0) {
-			die(ctx, ntedit_hip_reads_last_error(ctx));
-		}
-		if (ntedit_hip_reads_hist_summary(occ, f, &F0, &F1) != 0) {
-			die(ctx, ntedit_hip_reads_last_error(nullptr));
-		}
-		log_info("k-mer histogram: F1 = " + std::to_string(F1) + " (k-mers), F0 = " + std::to_string(F0) +
-		         " (distinct k-mers)");
-		// written first: a refused --solid still leaves the histogram to look at
-		if (!hist_out.empty()) {
-			if (ntedit_hip_reads_write_hist(hist_out.c_str(), f, F0, F1) != 0) {
-				die(ctx, "cannot write " + hist_out);
-			}
-			log_info("Histogram written to " + hist_out);
-		}
-		if (solid) {
-			uint32_t c = 0;
-			if (ntedit_hip_reads_solid_cutoff(f, &c) != 0) {
-				die(ctx, "--solid: the k-mer histogram has no valley after the error peak (no c with f[c+1] > f[c]); "
-				         "pass -c");
-			}
-			cmin = c;
-			log_info("--solid: minimum k-mer count " + std::to_string(cmin));
-		}
-		if (size_from_hist) {
-			num_elements = 0;
-			for (uint64_t c = cmin; c < 256; c++) {
-				num_elements += f[c];
-			}
-			bf_size = ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr);
-			log_info("Sized from the k-mer histogram: --num_elements " + std::to_string(num_elements) + " (k-mers at " +
-			         std::to_string(cmin) + " or above), " + std::to_string(bf_size) + " bytes");
-			if (bf_size == 0) {
-				die(ctx, "The output filter would be empty (no k-mer at the minimum count or above).");
-			}
-			std::cout << "BF size (bytes): " << bf_size << std::endl;
-		}
-	}
-
-	const int rc = counts ? ntedit_hip_filter_alloc_counting(ctx, NTEDIT_FILTER_PRIMARY, bf_size, (uint32_t)hashes, (uint32_t)k)
-	                      : ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, (uint32_t)hashes, (uint32_t)k);
-	if (rc != 0) {
-		die(ctx, counts ? ntedit_hip_reads_last_error(ctx) : ntedit_hip_last_error(ctx));
-	}
-	log_info("Pass 2: inserting k-mers seen at least " + std::to_string(cmin) + " times");
-	run_pass(ctx, NTEDIT_READS_PASS_SOLID, read_files, batch, (unsigned)cmin);
-	ntedit_hip_sketch_free(ctx);
 
 	uint64_t occupied = 0, slots = 0;
 	if (ntedit_hip_filter_occupancy(ctx, NTEDIT_FILTER_PRIMARY, &occupied, &slots) != 0) {

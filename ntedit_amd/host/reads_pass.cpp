@@ -21,6 +21,7 @@
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -468,6 +469,193 @@ ntedit_hip_reads_is_gzip(const char* path)
 {
 	return path && is_gzip(path) ? 1 : 0;
 }
+
+} // extern "C"
+
+namespace {
+
+struct BuildLog
+{
+	const ntedit_hip_reads_build_args* a;
+	void info(const std::string& s) const
+	{
+		if (a->log) {
+			a->log(a->user, 0, s.c_str());
+		}
+	}
+	void out(const std::string& s) const
+	{
+		if (a->log) {
+			a->log(a->user, 1, s.c_str());
+		}
+	}
+};
+
+// the tool's line of one pass (the large-run tests read it)
+void
+log_pass(const BuildLog& lg, int pass, const ntedit_hip_reads_pass_stats& st)
+{
+	static const char* const names[] = { "1 (count)", "H (histogram)", "2 (solid k-mers)" };
+	char line[256];
+	snprintf(line, sizeof line, "Pass %s: %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", names[pass],
+	         (unsigned long long)st.bases, st.ms_wall, st.ms_wall > 0 ? st.bases / st.ms_wall / 1e6 : 0.0, st.ms_gpu,
+	         st.ms_gpu > 0 ? st.bases / st.ms_gpu / 1e6 : 0.0);
+	lg.info(line);
+}
+
+// one pass, over the files whole or over the resident store (the store's bases: pass 1's)
+int
+build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, bool from_store, uint32_t cmin,
+           uint64_t store_reads_bases, ntedit_hip_reads_pass_stats* st)
+{
+	if (from_store) {
+		const auto t0 = std::chrono::steady_clock::now();
+		const int rc = pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_resident_histogram(ctx)
+		                                              : ntedit_hip_resident_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, cmin);
+		st->bases = store_reads_bases;
+		st->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		st->ms_gpu = st->ms_wall;
+		return rc;
+	}
+	const std::vector<uint64_t> begins(a->n_files, 0), ends(a->n_files, WHOLE);
+	return ntedit_hip_reads_pass(ctx, pass, a->files, begins.data(), ends.data(), a->n_files, a->batch_bytes, cmin, st,
+	                             nullptr, nullptr);
+}
+
+int
+build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r)
+{
+	const BuildLog lg{ a };
+	uint32_t cmin = a->cmin;
+	if (ntedit_hip_sketch_alloc(ctx, a->sketch_counters, a->hash_num, a->k) != 0) {
+		return NTEDIT_E_DEVICE; // (the message is sketch_alloc's)
+	}
+	if (a->use_store && ntedit_hip_resident_begin(ctx, a->store_cap) != 0) {
+		return NTEDIT_E_DEVICE;
+	}
+	lg.info("Pass 1: counting k-mers");
+	if (build_pass(ctx, a, NTEDIT_READS_PASS_COUNT, false, cmin, 0, &r->pass[NTEDIT_READS_PASS_COUNT]) != 0) {
+		return NTEDIT_E_IO;
+	}
+	log_pass(lg, NTEDIT_READS_PASS_COUNT, r->pass[NTEDIT_READS_PASS_COUNT]);
+	uint64_t nonzero = 0, counters = 0;
+	if (ntedit_hip_sketch_occupancy(ctx, &nonzero, &counters) != 0) {
+		return NTEDIT_E_DEVICE;
+	}
+	{
+		std::ostringstream o;
+		o << "Sketch occupancy: " << nonzero << " / " << counters << " counters (" << (double)nonzero / (double)counters << ")";
+		lg.out(o.str());
+	}
+	if (a->sketch_path && ntedit_hip_sketch_save_file(ctx, a->sketch_path) != 0) {
+		return NTEDIT_E_IO;
+	}
+	bool from_store = false;
+	if (a->use_store) {
+		ntedit_hip_resident_stats ss;
+		if (ntedit_hip_resident_info(ctx, &ss) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
+		r->store_state = ss.state;
+		r->store_bytes = ss.bytes;
+		from_store = ss.state == NTEDIT_RESIDENT_ON;
+		const std::string later = a->solid || a->hist_path ? "the histogram pass and pass 2" : "pass 2";
+		if (from_store) {
+			lg.info("Resident store: " + std::to_string(ss.batches) + " batches, " + std::to_string(ss.bytes) +
+			        " bytes of HBM (3 bits per base); " + later + " read it");
+		} else {
+			lg.info(std::string("Resident store: released (") +
+			        (ss.state == NTEDIT_RESIDENT_OVER_CAP ? "the reads would pass its cap of " + std::to_string(ss.cap) + " bytes"
+			                                                 : std::string("a device allocation failed")) +
+			        "); " + later + " read the files");
+		}
+	}
+	const uint64_t reads_bases = r->pass[NTEDIT_READS_PASS_COUNT].bases;
+	uint64_t bf_size = a->bf_bytes;
+	if (a->solid || a->hist_path) {
+		lg.info("Histogram pass: the k-mer histogram of the sketch's estimates");
+		if (build_pass(ctx, a, NTEDIT_READS_PASS_HIST, from_store, cmin, reads_bases, &r->pass[NTEDIT_READS_PASS_HIST]) != 0) {
+			return NTEDIT_E_IO;
+		}
+		log_pass(lg, NTEDIT_READS_PASS_HIST, r->pass[NTEDIT_READS_PASS_HIST]);
+		uint64_t occ[256], f[256], F0 = 0, F1 = 0;
+		if (ntedit_hip_sketch_histogram_download(ctx, occ) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
+		ntedit_hip_reads_hist_summary(occ, f, &F0, &F1);
+		lg.info("k-mer histogram: F1 = " + std::to_string(F1) + " (k-mers), F0 = " + std::to_string(F0) + " (distinct k-mers)");
+		// written first: a refused --solid still leaves the histogram to look at
+		if (a->hist_path) {
+			if (ntedit_hip_reads_write_hist(a->hist_path, f, F0, F1) != 0) {
+				return pfail(ctx, NTEDIT_E_IO, std::string("cannot write ") + a->hist_path);
+			}
+			lg.info(std::string("Histogram written to ") + a->hist_path);
+		}
+		if (a->solid) {
+			uint32_t c = 0;
+			if (ntedit_hip_reads_solid_cutoff(f, &c) != 0) {
+				return pfail(ctx, NTEDIT_E_ARG, "--solid: the k-mer histogram has no valley after the error peak (no c with "
+				                                "f[c+1] > f[c]); pass -c");
+			}
+			cmin = c;
+			lg.info("--solid: minimum k-mer count " + std::to_string(cmin));
+		}
+		if (a->bf_bytes == 0) {
+			uint64_t num_elements = 0;
+			for (uint64_t c = cmin; c < 256; c++) {
+				num_elements += f[c];
+			}
+			bf_size = ntedit_hip_reads_bf_size(num_elements, a->hash_num, a->fpr);
+			lg.info("Sized from the k-mer histogram: --num_elements " + std::to_string(num_elements) + " (k-mers at " +
+			        std::to_string(cmin) + " or above), " + std::to_string(bf_size) + " bytes");
+			if (bf_size == 0) {
+				return pfail(ctx, NTEDIT_E_ARG, "The output filter would be empty (no k-mer at the minimum count or above).");
+			}
+			lg.out("BF size (bytes): " + std::to_string(bf_size));
+		}
+	}
+	if (bf_size == 0) {
+		return pfail(ctx, NTEDIT_E_ARG, "The output filter would be empty (--bf 0 or --num_elements too small).");
+	}
+	if (a->counts) {
+		if (ntedit_hip_filter_alloc_counting(ctx, NTEDIT_FILTER_PRIMARY, bf_size, a->hash_num, a->k) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
+	} else if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, a->hash_num, a->k) != 0) {
+		return pfail(ctx, NTEDIT_E_DEVICE, ntedit_hip_last_error(ctx));
+	}
+	lg.info("Pass 2: inserting k-mers seen at least " + std::to_string(cmin) + " times");
+	if (build_pass(ctx, a, NTEDIT_READS_PASS_SOLID, from_store, cmin, reads_bases, &r->pass[NTEDIT_READS_PASS_SOLID]) != 0) {
+		return NTEDIT_E_IO;
+	}
+	log_pass(lg, NTEDIT_READS_PASS_SOLID, r->pass[NTEDIT_READS_PASS_SOLID]);
+	r->cmin = cmin;
+	r->bf_bytes = bf_size;
+	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int
+ntedit_hip_reads_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r)
+{
+	if (!ctx || !a || !r || (a->n_files && !a->files) || a->batch_bytes < 4096 || (!a->solid && (a->cmin < 1 || a->cmin > 255)) ||
+	    (a->bf_bytes == 0 && !a->solid && !a->hist_path)) {
+		return pfail(ctx, NTEDIT_E_ARG, "reads_build: bad argument");
+	}
+	*r = ntedit_hip_reads_build_result();
+	const auto t0 = std::chrono::steady_clock::now();
+	const int rc = build(ctx, a, r);
+	ntedit_hip_sketch_free(ctx); // (the store with it)
+	r->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return rc;
+}
+
+} // extern "C"
+
+extern "C" {
 
 // ntCard's histogram file: "F1\t<n>", "F0\t<n>", then "c\tf[c]" for c = 1..255 (zeros included)
 int
