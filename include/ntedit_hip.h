@@ -219,7 +219,9 @@ uint64_t ntedit_hip_reads_default_sketch(const char* const* files, uint32_t n, u
 int ntedit_hip_reads_is_gzip(const char* path);
 int ntedit_hip_reads_write_hist(const char* path, const uint64_t f[256], uint64_t F0, uint64_t F1);
 /* The resident store: the reads kept in HBM, packed, so that the passes after pass 1 do not parse the inputs again.
- *   ntedit_hip_resident_begin (after ntedit_hip_sketch_alloc): from now on every ntedit_hip_sketch_count batch is
+ *   ntedit_hip_resident_begin (after ntedit_hip_sketch_alloc or ntedit_hip_sketch_set_device; the store is the
+ *           library's own device memory either way, and a new sketch or ntedit_hip_sketch_free releases it): from now
+ *           on every ntedit_hip_sketch_count batch is
  *           also packed into the context's store, 3 bits per base: per 16 bytes of the batch one u32 of 2-bit codes
  *           (ACGT, case folded) and one u16 of validity bits (1 for ACGTacgt, 0 for any other byte, the separators
  *           between reads included), batch boundaries kept.  While the stored bytes stay within cap_bytes; a batch that

@@ -1119,7 +1119,7 @@ ntedit_hip_resident_begin(ntedit_hip_ctx* c, uint64_t cap_bytes)
 {
 	ReadsState* s = find_state(c);
 	if (!s) {
-		return c ? rfail(c, NTEDIT_E_ARG, "resident_begin: no sketch (ntedit_hip_sketch_alloc)") : NTEDIT_E_ARG;
+		return c ? rfail(c, NTEDIT_E_ARG, "resident_begin: no sketch (ntedit_hip_sketch_alloc / _set_device)") : NTEDIT_E_ARG;
 	}
 	RD_TRY(c, hipSetDevice(s->device));
 	RD_TRY(c, hipStreamSynchronize(s->stream));
@@ -1151,7 +1151,7 @@ ntedit_hip_resident_histogram(ntedit_hip_ctx* c)
 {
 	ReadsState* s = find_state(c);
 	if (!s) {
-		return c ? rfail(c, NTEDIT_E_ARG, "resident_histogram: no sketch (ntedit_hip_sketch_alloc)") : NTEDIT_E_ARG;
+		return c ? rfail(c, NTEDIT_E_ARG, "resident_histogram: no sketch (ntedit_hip_sketch_alloc / _set_device)") : NTEDIT_E_ARG;
 	}
 	RdFilter none = {};
 	return run_store_pass(c, s, 3, none, 0);
@@ -1165,7 +1165,7 @@ ntedit_hip_resident_insert_solid(ntedit_hip_ctx* c, int slot, uint32_t cmin)
 	}
 	ReadsState* s = find_state(c);
 	if (!s) {
-		return rfail(c, NTEDIT_E_ARG, "resident_insert_solid: no sketch (ntedit_hip_sketch_alloc)");
+		return rfail(c, NTEDIT_E_ARG, "resident_insert_solid: no sketch (ntedit_hip_sketch_alloc / _set_device)");
 	}
 	RdFilter out;
 	const int rc = solid_target(c, s, slot, cmin, "resident_insert_solid", &out);

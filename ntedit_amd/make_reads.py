@@ -14,7 +14,8 @@ one-process sketch.  The histogram pass sums 256 integer bins; pass 2 writes per
 or max (--counts) into the one-process filter.  The output is byte-identical to the binary's for every world size and
 partition, or the run is refused: after pass 1 every range's stop must be the next range's start (see
 ntedit_hip_reads_pass), which multi-line FASTQ can break -- then nothing is written and --no-split is the way out.
-Only rank 0 writes files.
+Only rank 0 writes files.  The per-rank build is build_rank, which `python -m ntedit_amd.run --reads` shares: there it
+keeps the reads resident in HBM after pass 1 and builds into the context that then polishes.
 """
 import ctypes
 import os
@@ -30,6 +31,7 @@ WHOLE = (1 << 64) - 1  # `end` of a unit that is a whole file
 GZIP_WEIGHT = 4  # a gzip byte weighs as much as 4 plain ones (the binary's default sketch counts it so)
 ROUND_BYTES = 256 << 20  # exchange rounds: at most this many bytes per peer and round, whatever the array size
 BATCH_DEFAULT = 256 << 20
+RESIDENT_CAP_DEFAULT = 48 << 30  # the resident store's cap of `ntedit --reads` (128 Gbases at 3 bits per base)
 PASS_NAMES = {_lib.READS_PASS_COUNT: "1 (count)", _lib.READS_PASS_HIST: "H (histogram)",
               _lib.READS_PASS_SOLID: "2 (solid k-mers)"}
 
@@ -229,17 +231,17 @@ def log_info(msg):
 
 
 class Builder:
-    """one rank's state: its context, its units, the process group"""
+    """one rank's state: the context it builds in (a Polisher's, owned by the caller), the process group, and what the
+    build measured (passes, exchanges)"""
 
-    def __init__(self, a, rank, world, local, group):
-        from .polisher import Polisher
-        self.a, self.rank, self.world, self.group = a, rank, world, group
-        self.pol = Polisher(local)
-        self.lib, self.h = self.pol._lib, self.pol._h
+    def __init__(self, a, rank, world, pol, group, name="make_reads"):
+        self.a, self.rank, self.world, self.group, self.name = a, rank, world, group, name
+        self.lib, self.h = pol._lib, pol._h
         self.xbytes, self.xsec = 0, 0.0
+        self.passes, self.exchanges = {}, []
 
     def fail(self, what):
-        raise RuntimeError("%s: %s" % (what, self.lib.ntedit_hip_reads_last_error(self.h).decode()))
+        raise RuntimeError("%s: %s: %s" % (self.name, what, self.lib.ntedit_hip_reads_last_error(self.h).decode()))
 
     def run_pass(self, which, units, cmin=0):
         n = len(units)
@@ -251,12 +253,25 @@ class Builder:
         st = _lib.ReadsPassStats()
         if self.lib.ntedit_hip_reads_pass(self.h, which, files, begins, ends, n, self.a["batch_bytes"], cmin,
                                           ctypes.byref(st), starts, nexts) != 0:
-            self.fail("make_reads: pass " + PASS_NAMES[which])
-        ms, g = st.ms_wall, st.ms_gpu
-        log_info("rank %d/%d: Pass %s: %d bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s), %d ranges"
-                 % (self.rank, self.world, PASS_NAMES[which], st.bases, ms, st.bases / ms / 1e6 if ms > 0 else 0.0, g,
-                    st.bases / g / 1e6 if g > 0 else 0.0, n))
+            self.fail("pass " + PASS_NAMES[which])
+        self._log_pass(which, st.bases, st.ms_wall, st.ms_gpu, "%d ranges" % n)
         return [(u.file, u.begin, starts[i], nexts[i]) for i, u in enumerate(units)]
+
+    def store_pass(self, which, bases, batches, slot=0, cmin=0):
+        """the histogram pass or pass 2 over the resident store (bases: pass 1's, which the store holds)"""
+        t0 = time.perf_counter()
+        rc = (self.lib.ntedit_hip_resident_histogram(self.h) if which == _lib.READS_PASS_HIST
+              else self.lib.ntedit_hip_resident_insert_solid(self.h, slot, cmin))
+        if rc != 0:
+            self.fail("pass " + PASS_NAMES[which])
+        ms = (time.perf_counter() - t0) * 1e3
+        self._log_pass(which, bases, ms, ms, "%d batches of the resident store" % batches)
+
+    def _log_pass(self, which, bases, ms, g, what):
+        self.passes[PASS_NAMES[which][0]] = dict(bases=bases, ms=round(ms, 3), gpu_ms=round(g, 3))
+        log_info("rank %d/%d: Pass %s: %d bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s), %s"
+                 % (self.rank, self.world, PASS_NAMES[which], bases, ms, bases / ms / 1e6 if ms > 0 else 0.0, g,
+                    bases / g / 1e6 if g > 0 else 0.0, what))
 
     # ------------------------------------------------------------------ collectives (gloo: through host memory)
     def _gloo(self):
@@ -298,7 +313,7 @@ class Builder:
             torch.cuda.synchronize()
             dst = view[r, o:o + p]
             if self.lib.ntedit_hip_merge_bytes(self.h, dst.data_ptr(), recv.data_ptr(), w, p, op) != 0:
-                self.fail("make_reads: merge")
+                self.fail("merge")
             del send, recv
         for o in range(0, s, ROUND_BYTES):
             p = min(ROUND_BYTES, s - o)
@@ -317,32 +332,48 @@ class Builder:
         moved = 2 * (w - 1) * s  # bytes this rank sent: its w - 1 foreign chunks, then its own chunk to w - 1 peers
         self.xbytes += moved
         self.xsec += sec
+        what = {0: "sat-add", 1: "or", 2: "max"}[op]
+        self.exchanges.append(dict(op=what, bytes=t.numel(), sent=moved, ms=round(sec * 1e3, 3)))
         log_info("rank %d/%d: exchange %s of %d bytes: %d bytes sent, %.1f ms (%s)"
-                 % (r, w, {0: "sat-add", 1: "or", 2: "max"}[op], t.numel(), moved, sec * 1e3,
-                    "gloo via host" if gloo else "rccl"))
+                 % (r, w, what, t.numel(), moved, sec * 1e3, "gloo via host" if gloo else "rccl"))
 
     def all_reduce_hist(self, occ):
         import torch
         import torch.distributed as dist
         if self.group is None:
             return occ
+        t0 = time.perf_counter()
         t = torch.from_numpy(occ.astype(np.int64))
         if not self._gloo():
             t = t.cuda()
         dist.all_reduce(t)
-        return t.cpu().numpy().astype(np.uint64)
+        out = t.cpu().numpy().astype(np.uint64)
+        self.exchanges.append(dict(op="sum", bytes=occ.nbytes, sent=occ.nbytes,
+                                   ms=round((time.perf_counter() - t0) * 1e3, 3)))
+        return out
 
     def padded(self, nbytes):
         q = 16 * self.world
         return -(-nbytes // q) * q
 
-    def close(self):
-        self.lib.ntedit_hip_sketch_free(self.h)
-        self.pol.close()
+
+STORE_STATES = {_lib.RESIDENT_OFF: "off", _lib.RESIDENT_ON: "on", _lib.RESIDENT_OVER_CAP: "over cap",
+                _lib.RESIDENT_NO_MEMORY: "no memory"}
 
 
-def build(a, lib, rank, world, local, group):
+def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RESIDENT_CAP_DEFAULT, name="make_reads"):
+    """One rank's share of the reads filter build, the same for every driver: the plan, pass 1 over this rank's units
+    into an adopted sketch, the cut-point check, the sketch merge, with --solid / --hist the histogram pass (rank 0
+    writes --hist), pass 2 into an adopted filter in `slot` of pol's context, the filter merge.  On return every rank
+    holds the whole filter there and the sketch is freed.  With use_store the reads of pass 1 stay resident in HBM
+    (ntedit_hip_resident_begin, up to store_cap bytes) and the later passes read the store; a rank whose store was
+    released reads its ranges again, with the same result.  ntedit_hip_reads_pass fills the PRIMARY slot, so that is
+    the only slot a build can fill.
+    -> (the filter tensor, which the caller keeps alive while the slot is in use, a report dict)"""
     import torch
+    if slot != 0:
+        raise ValueError("build_rank: pass 2 from the files fills the PRIMARY slot (0) only")
+    lib = pol._lib
     bf, sketch = sizes(lib, a)
     facts = file_facts(lib, a["reads"])
     units, owner = plan(a["reads"], facts, world, split=not a["no_split"])
@@ -352,15 +383,35 @@ def build(a, lib, rank, world, local, group):
         log_info("%d ranks, %d units (%d input files), sketch %d counters, %s" %
                  (world, len(units), len(a["reads"]), sketch,
                   "output from the k-mer histogram" if a["size_from_hist"] else "output %d bytes" % bf))
-    b = Builder(a, rank, world, local, group)
+    b = Builder(a, rank, world, pol, group, name)
+    rep = dict(units=len(mine), store=dict(used=False, state="not asked", batches=0, bytes=0, fallback=False))
     try:
         k, hashes = a["k"], a["hashes"]
         counters = (sketch + 7) // 8 * 8
         sk = torch.zeros(b.padded(counters), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         if lib.ntedit_hip_sketch_set_device(b.h, sk.data_ptr(), counters, hashes, k) != 0:
-            b.fail("make_reads: sketch")
+            b.fail("sketch")
+        if use_store and lib.ntedit_hip_resident_begin(b.h, store_cap) != 0:
+            b.fail("resident store")
         cut = b.run_pass(_lib.READS_PASS_COUNT, mine)
+        from_store, batches = False, 0
+        if use_store:
+            st = _lib.ResidentStats()
+            if lib.ntedit_hip_resident_info(b.h, ctypes.byref(st)) != 0:
+                b.fail("resident store")
+            from_store, batches = st.state == _lib.RESIDENT_ON, st.batches
+            rep["store"] = dict(used=from_store, state=STORE_STATES.get(st.state, str(st.state)), batches=st.batches,
+                                bytes=st.bytes, fallback=not from_store)
+            later = "the histogram pass and pass 2" if a["gather_hist"] else "pass 2"
+            if from_store:
+                log_info("rank %d/%d: Resident store: %d batches, %d bytes of HBM (3 bits per base); %s read it"
+                         % (rank, world, st.batches, st.bytes, later))
+            else:
+                log_info("rank %d/%d: Resident store: released (%s); %s read this rank's ranges again"
+                         % (rank, world, "the reads would pass its cap of %d bytes" % st.cap
+                            if st.state == _lib.RESIDENT_OVER_CAP else "a device allocation failed", later))
+        bases = b.passes["1"]["bases"]
         brk = check_cuts([c for part in b.all_gather_object(cut) for c in part])
         if brk is not None:
             f, b0, b1, nxt, start = brk
@@ -371,10 +422,13 @@ def build(a, lib, rank, world, local, group):
         b.merge(sk, _lib.MERGE_SAT_ADD)
         cmin = a["cmin"] or 0
         if a["gather_hist"]:
-            b.run_pass(_lib.READS_PASS_HIST, mine)
+            if from_store:
+                b.store_pass(_lib.READS_PASS_HIST, bases, batches)
+            else:
+                b.run_pass(_lib.READS_PASS_HIST, mine)
             occ = np.zeros(256, dtype=np.uint64)
             if lib.ntedit_hip_sketch_histogram_download(b.h, occ.ctypes.data_as(ctypes.c_void_p)) != 0:
-                b.fail("make_reads: histogram")
+                b.fail("histogram")
             occ = b.all_reduce_hist(occ)
             f = np.zeros(256, dtype=np.uint64)
             F0, F1 = ctypes.c_uint64(), ctypes.c_uint64()
@@ -406,24 +460,39 @@ def build(a, lib, rank, world, local, group):
         nbytes = (bf + 7) // 8 * 8
         out = torch.zeros(b.padded(nbytes), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
-        b.pol.set_filter_device(out.data_ptr(), nbytes, hashes, k, slot=0, counting=a["counts"])
-        b.run_pass(_lib.READS_PASS_SOLID, mine, cmin)
-        lib.ntedit_hip_sketch_free(b.h)
+        pol.set_filter_device(out.data_ptr(), nbytes, hashes, k, slot=slot, counting=a["counts"])
+        if from_store:
+            b.store_pass(_lib.READS_PASS_SOLID, bases, batches, slot, cmin)
+        else:
+            b.run_pass(_lib.READS_PASS_SOLID, mine, cmin)
+        lib.ntedit_hip_sketch_free(b.h)  # (the store with it)
         del sk
         b.merge(out, _lib.MERGE_MAX if a["counts"] else _lib.MERGE_OR)
+    finally:
+        lib.ntedit_hip_sketch_free(b.h)
+    rep.update(cmin=cmin, filter_bytes=nbytes, passes=b.passes, exchanges=b.exchanges, exchange_bytes=b.xbytes,
+               exchange_ms=round(b.xsec * 1e3, 3))
+    return out, rep
+
+
+def build(a, lib, rank, world, local, group):
+    from .polisher import Polisher
+    pol = Polisher(local)
+    try:
+        out, rep = build_rank(pol, a, rank, world, group)
         if rank == 0:
-            occupied, slots = b.pol.filter_occupancy(0)
-            print("Bloom filter FPR: %g" % ((occupied / slots) ** hashes), flush=True)
-            if lib.ntedit_hip_filter_save_file(b.h, 0, a["out"].encode()) != 0:
+            occupied, slots = pol.filter_occupancy(0)
+            print("Bloom filter FPR: %g" % ((occupied / slots) ** a["hashes"]), flush=True)
+            if lib.ntedit_hip_filter_save_file(pol._h, 0, a["out"].encode()) != 0:
                 raise RuntimeError("cannot write " + a["out"])
             log_info("rank 0: filter (%d bytes) written to %s; exchanges %d bytes sent in %.1f ms"
-                     % (nbytes, a["out"], b.xbytes, b.xsec * 1e3))
+                     % (rep["filter_bytes"], a["out"], rep["exchange_bytes"], rep["exchange_ms"]))
         if group is not None:
             import torch.distributed as dist
             dist.barrier()
         del out
     finally:
-        b.close()
+        pol.close()
     return 0
 
 

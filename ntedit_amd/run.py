@@ -1,4 +1,5 @@
 """python -m ntedit_amd.run -f draft.fa[.gz] -r solid.bf [-e repeat.bf] [-b prefix] [ntedit flags]
+python -m ntedit_amd.run -f draft.fa[.gz] --reads FILE... -k K (--cutoff C | --solid) [reads flags] [ntedit flags]
 
 The multi-GPU driver of the hot path: one process per GPU, launched with
 
@@ -14,6 +15,11 @@ straight into its page-locked batch, polishes them through the C ABI (ntedit_amd
 their offsets in <prefix>_edited.fa / _changes.tsv / _variants.vcf itself (dist.gather_parallel): no rank holds the
 draft, no rank reads another rank's output.  Byte-identical to the single-GPU `ntedit` binary's output (and to the
 reference at -t 1).
+
+With --reads instead of -r (the reads options of `ntedit --reads`, with their meaning and refusals, and --no-split of
+ntedit_amd.make_reads) every rank builds its share of the reads filter in HBM, the reads it parsed in pass 1 kept
+resident there for the later passes, into the context that then polishes (make_reads.build_rank); the merges leave the
+whole filter on every rank: no filter file, no broadcast.  The outputs are those of `ntedit --reads` with the same flags.
 
 What the reference does instead: readAndCorrect's OpenMP loop (ntedit.cpp:2213-2252), contigs handed to threads one
 at a time, output in completion order."""
@@ -214,11 +220,31 @@ class HipBackend:
         return bad, sizes
 
 
+class Refused(Exception):
+    pass
+
+
+# the reads options of `ntedit --reads` (+ make_reads' --no-split): (flag, dest), in the order a refusal names them
+READS_OPTIONS = [("--cutoff", "cutoff"), ("--solid", "solid"), ("--counts", "counts"), ("--hashes", "hashes"),
+                 ("--fpr", "fpr"), ("--bf", "bf_bytes"), ("--num_elements", "num_elements"),
+                 ("--sketch_bytes", "sketch_bytes"), ("--hist", "hist"), ("--save_bf", "save_bf"),
+                 ("--batch_bytes", "batch_bytes"), ("--resident_cap", "resident_cap"), ("--no-split", "no_split")]
+
+
+def _count(name, v):
+    """a whole non-negative decimal number (ntedit's parse_count)"""
+    if not v or not v.isdigit():
+        raise Refused("invalid option: `%s %s'" % (name, v))
+    return int(v)
+
+
 def parse(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    reads_mode = "--reads" in argv
     ap = argparse.ArgumentParser(prog="python -m ntedit_amd.run", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-f", dest="draft", required=True)
-    ap.add_argument("-r", dest="bf", required=True)
+    ap.add_argument("-r", dest="bf", required=not reads_mode)
     ap.add_argument("-e", dest="bfrep")
     ap.add_argument("-b", dest="prefix")
     ap.add_argument("-l", dest="annot")
@@ -236,19 +262,135 @@ def parse(argv=None):
     ap.add_argument("-p", dest="min_threshold", type=int, default=1)
     ap.add_argument("-q", dest="max_threshold", type=int, default=255)
     ap.add_argument("-t", dest="threads", type=int, default=0, help="host threads rendering the output")
-    ap.add_argument("-k", dest="k_ignored", type=int, help="ignored: k comes from the filter")
+    ap.add_argument("-k", dest="k_ignored", type=str if reads_mode else int,
+                    help="ignored: k comes from the filter (with --reads: the k-mer size, 12 to 200, required)")
     ap.add_argument("--seg-bases", type=int, default=None,
                     help="cut contigs longer than 1.5x this (default: an eighth of a GPU's share, 1-32 Mbp)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--report", action="store_true")
-    return ap.parse_args(argv)
+    g = ap.add_argument_group("polishing straight from reads (--reads replaces -r; the options of `ntedit --reads`, "
+                              "the same filter; every rank builds its share and holds the whole filter)")
+    g.add_argument("--reads", nargs="*", metavar="FILE", help="input reads, FASTA or FASTQ, plain or gzip")
+    g.add_argument("--cutoff", metavar="C", help="minimum k-mer count of the filter, 1 to 255")
+    g.add_argument("--solid", action="store_true", help="take the minimum count from the k-mer histogram instead")
+    g.add_argument("--counts", action="store_true", help="build a counting filter (enables -p / -q)")
+    g.add_argument("--hashes", metavar="H", help="number of hash functions, 1 to 8 [3]")
+    g.add_argument("--fpr", metavar="F", help="false positive rate of the filter (with --num_elements) [0.01]")
+    g.add_argument("--bf", dest="bf_bytes", metavar="BYTES", help="filter size in bytes")
+    g.add_argument("--num_elements", metavar="N", help="approximate number of solid k-mers")
+    g.add_argument("--sketch_bytes", metavar="S", help="counters of the count-min sketch")
+    g.add_argument("--hist", metavar="FILE", help="write the k-mer histogram (rank 0)")
+    g.add_argument("--save_bf", metavar="FILE", help="write the filter that was built (rank 0); the _r part of the "
+                                                     "default prefix [reads_k<K>.bf, not written]")
+    g.add_argument("--no-split", dest="no_split", action="store_true",
+                   help="read every input file whole (by one rank); gzip files always are")
+    g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
+    g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
+    args = ap.parse_args(argv)
+    args.reads_args = reads_args(args) if reads_mode else None
+    if not reads_mode:
+        for flag, dest in READS_OPTIONS:
+            if getattr(args, dest) not in (None, False):
+                raise Refused(flag + ": only with --reads")
+    return args
+
+
+def reads_args(args):
+    """the refusals of `ntedit --reads` (host/main.cpp), in its order, before any device or file is touched; -> the
+    argument dict of ntedit_amd.make_reads.build_rank"""
+    from . import _lib
+    from .make_reads import BATCH_DEFAULT, RESIDENT_CAP_DEFAULT
+    if args.bf is not None:
+        raise Refused("--reads and -r: give one of them (--reads builds the filter that -r would load)")
+    if not args.reads:
+        raise Refused("--reads: 1 or more files expected")
+    if args.k_ignored is None:
+        raise Refused("-k: required with --reads")
+    k = args.k_ignored
+    if not k.isdigit() or not 12 <= int(k) <= 200:
+        raise Refused("-k %s: k must be between 12 and 200" % k)
+    a = dict(reads=list(args.reads), k=int(k), cmin=None, solid=args.solid, hist=args.hist or "", counts=args.counts,
+             hashes=3, fpr=0.01, bf=None, num_elements=None, sketch_bytes=0, batch_bytes=BATCH_DEFAULT,
+             no_split=args.no_split, store_cap=RESIDENT_CAP_DEFAULT)
+    if args.cutoff is not None:
+        a["cmin"] = _count("--cutoff", args.cutoff)
+    if args.hashes is not None:
+        a["hashes"] = _count("--hashes", args.hashes)
+    if args.fpr is not None:
+        try:
+            a["fpr"] = float(args.fpr)
+        except ValueError:
+            a["fpr"] = float("nan")
+        if not (0.0 < a["fpr"] < 1.0):
+            raise Refused("--fpr %s: needs a number between 0 and 1" % args.fpr)
+    for flag, key, dest in (("--bf", "bf", "bf_bytes"), ("--num_elements", "num_elements", "num_elements"),
+                            ("--sketch_bytes", "sketch_bytes", "sketch_bytes"),
+                            ("--batch_bytes", "batch_bytes", "batch_bytes"), ("--resident_cap", "store_cap", "resident_cap")):
+        if getattr(args, dest) is not None:
+            a[key] = _count(flag, getattr(args, dest))
+    if a["cmin"] is not None and a["solid"]:
+        raise Refused("--cutoff and --solid: give one of them (--solid takes the minimum count from the k-mer histogram)")
+    if a["cmin"] is None and not a["solid"]:
+        raise Refused("--cutoff or --solid: one of them is required with --reads")
+    if a["cmin"] is not None and not 1 <= a["cmin"] <= 255:
+        raise Refused("--cutoff %d: the minimum count must be between 1 and 255" % a["cmin"])
+    if not 1 <= a["hashes"] <= 8:
+        raise Refused("--hashes %d: the number of hash functions must be between 1 and 8" % a["hashes"])
+    a["gather_hist"] = a["solid"] or bool(a["hist"])
+    a["size_from_hist"] = a["bf"] is None and a["num_elements"] is None
+    if a["size_from_hist"] and not a["gather_hist"]:
+        raise Refused("--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter from "
+                      "the k-mer histogram)")
+    if (a["bf"] == 0 or (a["bf"] is None and a["num_elements"] is not None and
+                         _lib.load().ntedit_hip_reads_bf_size(a["num_elements"], a["hashes"], a["fpr"]) == 0)):
+        raise Refused("--bf / --num_elements: the filter would be empty")
+    if a["batch_bytes"] < 4096:
+        raise Refused("--batch_bytes: at least 4096")
+    for path in [args.draft] + a["reads"]:
+        try:
+            open(path, "rb").close()
+        except OSError as e:
+            raise Refused("`%s': %s" % (path, e.strerror)) from None
+    return a
+
+
+def build_from_reads(pol, args, rank, world):
+    """--reads: this rank's share of the reads filter, built into the PRIMARY slot of pol's context with the reads kept
+    resident in HBM (make_reads.build_rank); every rank then holds the whole filter: no file, no broadcast.  Rank 0
+    writes --save_bf.  The sketch and the store are freed, and torch's cache of them released, before the polish
+    reserves its buffers.  -> the report of the build, or None after a refusal (on every rank alike)"""
+    import torch
+    import torch.distributed as dist
+    from . import make_reads
+    a = args.reads_args
+    group = dist.group.WORLD if dist.is_initialized() else None
+    try:
+        buf, rep = make_reads.build_rank(pol, a, rank, world, group, slot=0, use_store=True, store_cap=a["store_cap"],
+                                         name="run")
+    except make_reads.Refused as e:
+        sys.stderr.write("python -m ntedit_amd.run: error: %s\n" % e)
+        return None
+    ndist._keep(pol, 0, buf)
+    torch.cuda.empty_cache()
+    if rank == 0:
+        make_reads.log_info("rank 0: filter (%d bytes) built from the reads in HBM, minimum count %d; exchanges %d "
+                            "bytes sent in %.1f ms" % (rep["filter_bytes"], rep["cmin"], rep["exchange_bytes"],
+                                                       rep["exchange_ms"]))
+        if args.save_bf:
+            pol.filter_save_file(args.save_bf, 0)
+            make_reads.log_info("Bloom filter saved to " + args.save_bf)
+    return rep
 
 
 def main(argv=None):
     import ctypes
     import torch
     import torch.distributed as dist
-    args = parse(argv)
+    try:
+        args = parse(argv)
+    except Refused as e:
+        sys.stderr.write("python -m ntedit_amd.run: error: %s\n" % e)
+        return 1
     rank, world, local = ndist.env_rank()
     if not torch.cuda.is_available():
         sys.stderr.write("ntEdit v2.1.1: error: no HIP device (this build has no CPU path)\n")
@@ -268,7 +410,16 @@ def main(argv=None):
     pol = Polisher(local)
     pol._lib.ntedit_hip_bind_near_device(local)  # host threads and buffers on the socket this rank's GPU hangs off
     t0 = time.perf_counter()
-    ndist.load_and_broadcast_filter(pol, args.bf, 0, 0)
+    reads = None
+    if args.reads_args is not None:
+        reads = build_from_reads(pol, args, rank, world)
+        if reads is None:
+            pol.close()
+            if dist.is_initialized():
+                dist.destroy_process_group()
+            return 1
+    else:
+        ndist.load_and_broadcast_filter(pol, args.bf, 0, 0)
     if args.bfrep:
         ndist.load_and_broadcast_filter(pol, args.bfrep, 0, 1)
     t_filter = time.perf_counter() - t0
@@ -293,8 +444,10 @@ def main(argv=None):
         pol._lib.ntedit_hip_set_host_threads(args.threads)
     prefix = args.prefix
     if not prefix:  # ntedit.cpp:2496-2502
+        # (with --reads the _r part is what `ntedit --reads` puts there: the --save_bf name or reads_k<K>.bf)
+        bf_name = args.bf if reads is None else (args.save_bf or "reads_k%d.bf" % k)
         prefix = "%s_k%d_z%d_r%s_i%d_d%d_m%d" % (os.path.basename(args.draft), k, p.min_contig_len,
-                                                  os.path.basename(args.bf), p.max_insertions, p.max_deletions, p.mode)
+                                                  os.path.basename(bf_name), p.max_insertions, p.max_deletions, p.mode)
     annot = ctypes.c_void_p()
     if args.annot:
         if pol._lib.ntedit_hip_annot_load(args.annot.encode(), ctypes.byref(annot)):
@@ -338,9 +491,10 @@ def main(argv=None):
         n_seg = sum(1 for q in mine if q.n_seg > 1)
         sys.stdout.write('{"rank": %d, "world": %d, "pieces": %d, "segments": %d, "bases": %d, "reruns": %d, '
                          '"gpu_ms": %.3f, "filter_s": %.3f, "index_s": %.3f, "draft_bases_total": %d, "draft_bytes_read": %d, '
-                         '"reserve_s": %.3f, "run_s": %.3f, "phases_s": %s}\n' %
+                         '"reserve_s": %.3f, "run_s": %.3f, "phases_s": %s%s}\n' %
                          (rank, world, len(mine), n_seg, backend.bases, backend.n_rerun, backend.ms_gpu, t_filter,
-                          t_read, total, draft.bytes_read, t_reserve, t_run, json.dumps(ndist.LAST_PHASES)))
+                          t_read, total, draft.bytes_read, t_reserve, t_run, json.dumps(ndist.LAST_PHASES),
+                          "" if reads is None else ', "reads": ' + json.dumps(reads)))
         sys.stdout.flush()
     if annot.value:
         pol._lib.ntedit_hip_annot_free(annot)
