@@ -257,7 +257,24 @@ void ntedit_hip_resident_free(ntedit_hip_ctx* ctx);
  * with `counts`), pass 2, the sketch freed.  With use_store the reads are kept resident from pass 1 (cap: store_cap
  * bytes) and the later passes read the store; past the cap they read the files, as without it.  Console lines go to
  * log(user, to_stdout, line): to_stdout = 0 for a timestamped information line, 1 for a line of standard output.  On
- * failure the message is ntedit_hip_reads_last_error(ctx); the sketch and the store are freed either way. */
+ * failure the message is ntedit_hip_reads_last_error(ctx); the sketch and the store are freed either way.
+ *
+ * ntedit_hip_reads_build is four stages in a row, exported for the sharded build (ntedit_amd/make_reads.py), which
+ * walks the same four with its merges in between.  There `begins` / `ends` are set: files[i] is read in the byte range
+ * [begins[i], ends[i]) (as ntedit_hip_reads_pass), the sketch and the PRIMARY filter are the device memory the caller
+ * adopted (ntedit_hip_sketch_set_device, ntedit_hip_set_filter_device) instead of the library's own, and the pass and
+ * store lines carry "rank <rank>/<world>: " and what was read.  The stages hand their state on in the result:
+ *   ntedit_hip_reads_stage_count: the sketch, the store's begin, pass 1 (starts / nexts as ntedit_hip_reads_pass
+ *           reports them, may be NULL), the store's state and its lines.  Zeroes *res first.
+ *   ntedit_hip_reads_stage_histogram: the histogram pass, from the store or over the same ranges; occ[256] as
+ *           ntedit_hip_sketch_histogram_download.
+ *   ntedit_hip_reads_stage_decide: host only, no context.  From occ (the caller's own or the sum over the ranks; NULL
+ *           when no histogram was gathered) to res->cmin and res->bf_bytes: the histogram's lines, the --hist file
+ *           (written before a refused --solid: it is left to look at), the --solid cutoff, the size from the
+ *           histogram, and the refusals (NTEDIT_E_ARG; the message is ntedit_hip_reads_last_error(NULL)).  Only
+ *           rank 0 writes --hist and logs; every rank reaches the same refusal.
+ *   ntedit_hip_reads_stage_insert: the filter of res->bf_bytes, pass 2 with res->cmin from the store or over the
+ *           ranges, the sketch and the store freed. */
 typedef struct ntedit_hip_reads_build_args
 {
 	const char* const* files;
@@ -276,6 +293,9 @@ typedef struct ntedit_hip_reads_build_args
 	uint64_t store_cap;
 	void (*log)(void* user, int to_stdout, const char* line);
 	void* user;
+	const uint64_t* begins;   /* NULL: the files whole, one process; else a rank's share of a sharded build */
+	const uint64_t* ends;
+	uint32_t rank, world;
 } ntedit_hip_reads_build_args;
 typedef struct ntedit_hip_reads_build_result
 {
@@ -285,8 +305,51 @@ typedef struct ntedit_hip_reads_build_result
 	int store_state;                      /* after pass 1 (OFF without use_store) */
 	uint64_t store_bytes;                 /* device bytes the store held after pass 1 */
 	double ms_total;
+	uint64_t store_batches;               /* batches it held after pass 1 */
 } ntedit_hip_reads_build_result;
 int ntedit_hip_reads_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res);
+int ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res,
+                                 uint64_t* starts, uint64_t* nexts);
+int ntedit_hip_reads_stage_histogram(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args,
+                                     ntedit_hip_reads_build_result* res, uint64_t occ[256]);
+int ntedit_hip_reads_stage_decide(const ntedit_hip_reads_build_args* args, const uint64_t occ[256], ntedit_hip_reads_build_result* res);
+int ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res);
+/* The reads options of the four front ends (ntedit-make-reads-bf and python -m ntedit_amd.make_reads: the TOOL dialect,
+ * "-c", sentences; ntedit --reads and python -m ntedit_amd.run --reads: the POLISHER dialect, "--cutoff"), checked in one
+ * place.  Host only, no device.  The options come as their text (NULL: not given).  With final = 0 only the options
+ * given so far are checked for what is refused at the option itself (a malformed number, --fpr), so that a front end
+ * can ask while it walks its arguments; with final = 1 every rule, in that dialect's order: -k required and 12..200,
+ * the cutoff xor --solid and 1..255, hashes 1..8, a size unless the histogram gives it, the filter would be empty,
+ * batch_bytes >= 4096.  Returns 0 and the normalised arguments, or the first refusal: NTEDIT_READS_REFUSED,
+ * NTEDIT_READS_NOT_A_NUMBER (a malformed number), NTEDIT_READS_EMPTY (TOOL dialect: the filter would be empty; the
+ * tool prints its parameters before it says so, and *out is filled), its message in ntedit_hip_reads_last_error(NULL). */
+#define NTEDIT_READS_DIALECT_TOOL 0
+#define NTEDIT_READS_DIALECT_POLISHER 1
+#define NTEDIT_READS_REFUSED 1
+#define NTEDIT_READS_NOT_A_NUMBER 2
+#define NTEDIT_READS_EMPTY 3
+#define NTEDIT_READS_BATCH_DEFAULT (256ull << 20)
+#define NTEDIT_READS_RESIDENT_CAP_DEFAULT (48ull << 30) /* 128 Gbases at 3 bits per base */
+#define NTEDIT_READS_GZIP_WEIGHT 4 /* a gzip byte counts as 4 plain ones (default sketch, the sharded partition) */
+typedef struct ntedit_hip_reads_options
+{
+	const char *k, *cutoff, *hashes, *fpr, *bf, *num_elements, *sketch_bytes, *batch_bytes, *store_cap, *threads;
+	int solid, hist;
+	const char* const* files; /* for the default sketch */
+	uint32_t n_files;
+} ntedit_hip_reads_options;
+typedef struct ntedit_hip_reads_rules
+{
+	uint32_t k, cmin, hash_num; /* cmin 0: --solid */
+	double fpr;
+	uint64_t bf_bytes;          /* --bf, or from --num_elements; 0: sized from the histogram */
+	uint64_t num_elements;
+	uint64_t sketch_bytes;      /* as given (0: default) */
+	uint64_t sketch_counters;   /* the sketch to allocate */
+	uint64_t batch_bytes, store_cap, threads;
+	int gather_hist, size_from_hist;
+} ntedit_hip_reads_rules;
+int ntedit_hip_reads_options_check(const ntedit_hip_reads_options* opts, int dialect, int final, ntedit_hip_reads_rules* out);
 
 
 /* ---- hot path ------------------------------------------------------------

@@ -88,13 +88,39 @@ class ReadsBuildArgs(ctypes.Structure):
                 ("counts", ctypes.c_int), ("bf_bytes", ctypes.c_uint64), ("fpr", ctypes.c_double),
                 ("sketch_counters", ctypes.c_uint64), ("batch_bytes", ctypes.c_uint64), ("hist_path", ctypes.c_char_p),
                 ("sketch_path", ctypes.c_char_p), ("use_store", ctypes.c_int), ("store_cap", ctypes.c_uint64),
-                ("log", READS_LOG_FN), ("user", ctypes.c_void_p)]
+                ("log", READS_LOG_FN), ("user", ctypes.c_void_p), ("begins", ctypes.POINTER(ctypes.c_uint64)),
+                ("ends", ctypes.POINTER(ctypes.c_uint64)), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32)]
 
 
 class ReadsBuildResult(ctypes.Structure):
     """ntedit_hip_reads_build_result"""
     _fields_ = [("cmin", ctypes.c_uint32), ("bf_bytes", ctypes.c_uint64), ("passes", ReadsPassStats * 3),
-                ("store_state", ctypes.c_int), ("store_bytes", ctypes.c_uint64), ("ms_total", ctypes.c_double)]
+                ("store_state", ctypes.c_int), ("store_bytes", ctypes.c_uint64), ("ms_total", ctypes.c_double),
+                ("store_batches", ctypes.c_uint64)]
+
+
+# the reads-option rules (ntedit_hip_reads_options_check) and the header's defaults
+READS_DIALECT_TOOL, READS_DIALECT_POLISHER = 0, 1
+READS_REFUSED, READS_NOT_A_NUMBER, READS_EMPTY = 1, 2, 3
+READS_BATCH_DEFAULT, READS_RESIDENT_CAP_DEFAULT, READS_GZIP_WEIGHT = 256 << 20, 48 << 30, 4
+READS_OPTION_TEXTS = ("k", "cutoff", "hashes", "fpr", "bf", "num_elements", "sketch_bytes", "batch_bytes", "store_cap",
+                      "threads")
+
+
+class ReadsOptions(ctypes.Structure):
+    """ntedit_hip_reads_options"""
+    _fields_ = ([(name, ctypes.c_char_p) for name in READS_OPTION_TEXTS] +
+                [("solid", ctypes.c_int), ("hist", ctypes.c_int), ("files", ctypes.POINTER(ctypes.c_char_p)),
+                 ("n_files", ctypes.c_uint32)])
+
+
+class ReadsRules(ctypes.Structure):
+    """ntedit_hip_reads_rules"""
+    _fields_ = [("k", ctypes.c_uint32), ("cmin", ctypes.c_uint32), ("hash_num", ctypes.c_uint32),
+                ("fpr", ctypes.c_double), ("bf_bytes", ctypes.c_uint64), ("num_elements", ctypes.c_uint64),
+                ("sketch_bytes", ctypes.c_uint64), ("sketch_counters", ctypes.c_uint64),
+                ("batch_bytes", ctypes.c_uint64), ("store_cap", ctypes.c_uint64), ("threads", ctypes.c_uint64),
+                ("gather_hist", ctypes.c_int), ("size_from_hist", ctypes.c_int)]
 
 
 class Segment(ctypes.Structure):
@@ -104,7 +130,7 @@ class Segment(ctypes.Structure):
 
 
 SEG_NO_HEADER, SEG_NO_NEWLINE, SEG_SKIP = 1, 2, 4
-E_SEGMENT = -7
+E_ARG, E_SEGMENT = -1, -7
 EDIT_SUB, EDIT_INS, EDIT_DEL, EDIT_SNV_KEPT = 1, 2, 3, 4
 
 
@@ -153,6 +179,8 @@ EXPORTS = [
     "ntedit_hip_reads_is_gzip", "ntedit_hip_reads_write_hist",
     "ntedit_hip_resident_begin", "ntedit_hip_resident_info", "ntedit_hip_resident_histogram",
     "ntedit_hip_resident_insert_solid", "ntedit_hip_resident_free", "ntedit_hip_reads_build",
+    "ntedit_hip_reads_stage_count", "ntedit_hip_reads_stage_histogram", "ntedit_hip_reads_stage_decide",
+    "ntedit_hip_reads_stage_insert", "ntedit_hip_reads_options_check",
 ]
 
 _lib = None
@@ -277,6 +305,12 @@ def load():
     lib.ntedit_hip_resident_insert_solid.argtypes = [vp, ci, u32]
     lib.ntedit_hip_resident_free.argtypes = [vp]
     lib.ntedit_hip_resident_free.restype = None
-    lib.ntedit_hip_reads_build.argtypes = [vp, ctypes.POINTER(ReadsBuildArgs), ctypes.POINTER(ReadsBuildResult)]
+    args, res = ctypes.POINTER(ReadsBuildArgs), ctypes.POINTER(ReadsBuildResult)
+    lib.ntedit_hip_reads_build.argtypes = [vp, args, res]
+    lib.ntedit_hip_reads_stage_count.argtypes = [vp, args, res, pu64, pu64]
+    lib.ntedit_hip_reads_stage_histogram.argtypes = [vp, args, res, vp]
+    lib.ntedit_hip_reads_stage_decide.argtypes = [args, vp, res]
+    lib.ntedit_hip_reads_stage_insert.argtypes = [vp, args, res]
+    lib.ntedit_hip_reads_options_check.argtypes = [ctypes.POINTER(ReadsOptions), ci, ci, ctypes.POINTER(ReadsRules)]
     _lib = lib
     return lib

@@ -34,15 +34,16 @@ def env_rank():
             int(os.environ.get("LOCAL_RANK", "0")))
 
 
-def init_process_group(backend=None):
+def init_process_group(backend=None, port=29511, single=False):
+    """the process group of the launcher's ranks (single: of one rank too, which still exercises the collective path)"""
     import torch
     import torch.distributed as dist
     rank, world, local = env_rank()
-    if world > 1 and not dist.is_initialized():
+    if (world > 1 or single) and not dist.is_initialized():
         if backend is None:
             backend = "nccl" if torch.cuda.is_available() else "gloo"
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29511")
+        os.environ.setdefault("MASTER_PORT", str(port))
         if backend == "nccl":
             torch.cuda.set_device(local)
         dist.init_process_group(backend=backend, rank=rank, world_size=world)

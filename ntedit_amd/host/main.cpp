@@ -14,6 +14,7 @@
 #include "../../include/ntedit_hip.h"
 #include "fasta.h"
 #include "fasta_map.h"
+#include "log_info.h"
 
 #include <algorithm>
 #include <chrono>
@@ -192,20 +193,6 @@ parse(int c, const char* arg, T& out)
 	}
 }
 
-// a whole non-negative decimal number of a long option, or exit
-static uint64_t
-parse_count(const char* name, const char* arg)
-{
-	char* end = nullptr;
-	errno = 0;
-	const unsigned long long v = arg && *arg && *arg != '-' && *arg != '+' ? strtoull(arg, &end, 10) : 0;
-	if (!arg || !*arg || *arg == '-' || *arg == '+' || errno || *end) {
-		fprintf(stderr, PROGRAM ": invalid option: `%s %s'\n", name, arg ? arg : "");
-		exit(EXIT_FAILURE);
-	}
-	return v;
-}
-
 static void
 refuse(const std::string& why)
 {
@@ -213,23 +200,22 @@ refuse(const std::string& why)
 	exit(EXIT_FAILURE);
 }
 
-// the reads filter build's console lines (ntedit_hip_reads_build_args.log), as ntedit-make-reads-bf prints them
-static void
-reads_log(void*, int to_stdout, const char* line)
+// the reads options through the library's rules (reads_options.cpp); a refusal ends the run, in the words and the form it
+// always had: a malformed number as getopt's invalid options are
+static ntedit_hip_reads_rules
+reads_rules(const ntedit_hip_reads_options& ro, int final)
 {
-	if (to_stdout) {
-		printf("%s\n", line);
-		fflush(stdout);
-		return;
+	ntedit_hip_reads_rules rr;
+	const int rc = ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_POLISHER, final, &rr);
+	if (rc == NTEDIT_READS_NOT_A_NUMBER) {
+		fprintf(stderr, PROGRAM ": %s\n", ntedit_hip_reads_last_error(nullptr));
+		exit(EXIT_FAILURE);
 	}
-	char ts[64];
-	time_t now = time(nullptr);
-	strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", localtime(&now));
-	fprintf(stderr, "[%s] [INFO] %s\n", ts, line);
+	if (rc != 0) {
+		refuse(ntedit_hip_reads_last_error(nullptr));
+	}
+	return rr;
 }
-
-// the resident store's default cap: 48 GiB of packed reads (128 Gbases at 3 bits per base)
-static const uint64_t RESIDENT_CAP_DEFAULT = 48ull << 30;
 
 struct Batch
 {
@@ -337,6 +323,7 @@ main(int argc, char** argv)
 	std::vector<std::pair<std::string, unsigned long long>> tunes;
 	// --reads FILE...: the files up to the next option (taken out here, getopt takes one argument per option)
 	std::vector<std::string> read_files;
+	std::vector<const char*> paths;
 	bool reads_mode = false;
 	std::vector<char*> args;
 	for (int i = 0; i < argc; i++) {
@@ -352,13 +339,17 @@ main(int argc, char** argv)
 	args.push_back(nullptr);
 	argc = (int)args.size() - 1;
 	argv = args.data();
-	std::string k_arg, hist_out, save_bf;
-	bool have_k = false, have_cutoff = false, solid = false, counts = false, have_bf = false, have_ne = false;
-	bool shard_given = false;
-	uint64_t cutoff = 0, hashes = 3, bf_bytes = 0, num_elements = 0, sketch_bytes = 0, reads_batch = 256ull << 20;
-	uint64_t store_cap = RESIDENT_CAP_DEFAULT;
-	double fpr = 0.01;
+	std::string hist_out, save_bf;
+	bool counts = false, shard_given = false;
+	ntedit_hip_reads_options ro = {}; // the reads options as given; refused at the option where the rules say so
+	ntedit_hip_reads_rules rr = {};
 	std::vector<std::string> reads_only; // reads options given (refused without --reads)
+	// a reads option with a value: its text to the rules, which refuse at the option what they refuse there
+	auto reads_option = [&](const char* name, const char** text) {
+		*text = optarg;
+		reads_only.push_back(name);
+		reads_rules(ro, 0);
+	};
 	for (int c; (c = getopt_long(argc, argv, shortopts, longopts, nullptr)) != -1;) {
 		switch (c) {
 		case '?':
@@ -432,16 +423,13 @@ main(int argc, char** argv)
 			break;
 		case 'k':
 			// without --reads: accepted and ignored (the reference rejects it: no `case 'k'`, ntedit.cpp:2360-2363)
-			k_arg = optarg;
-			have_k = true;
+			ro.k = optarg;
 			break;
 		case OPT_CUTOFF:
-			cutoff = parse_count("--cutoff", optarg);
-			have_cutoff = true;
-			reads_only.push_back("--cutoff");
+			reads_option("--cutoff", &ro.cutoff);
 			break;
 		case OPT_SOLID:
-			solid = true;
+			ro.solid = 1;
 			reads_only.push_back("--solid");
 			break;
 		case OPT_COUNTS:
@@ -449,34 +437,23 @@ main(int argc, char** argv)
 			reads_only.push_back("--counts");
 			break;
 		case OPT_HASHES:
-			hashes = parse_count("--hashes", optarg);
-			reads_only.push_back("--hashes");
+			reads_option("--hashes", &ro.hashes);
 			break;
-		case OPT_FPR: {
-			char* end = nullptr;
-			fpr = strtod(optarg, &end);
-			if (*end || !(fpr > 0.0 && fpr < 1.0)) {
-				refuse(std::string("--fpr ") + optarg + ": needs a number between 0 and 1");
-			}
-			reads_only.push_back("--fpr");
+		case OPT_FPR:
+			reads_option("--fpr", &ro.fpr);
 			break;
-		}
 		case OPT_BF:
-			bf_bytes = parse_count("--bf", optarg);
-			have_bf = true;
-			reads_only.push_back("--bf");
+			reads_option("--bf", &ro.bf);
 			break;
 		case OPT_NUM_ELEMENTS:
-			num_elements = parse_count("--num_elements", optarg);
-			have_ne = true;
-			reads_only.push_back("--num_elements");
+			reads_option("--num_elements", &ro.num_elements);
 			break;
 		case OPT_SKETCH_BYTES:
-			sketch_bytes = parse_count("--sketch_bytes", optarg);
-			reads_only.push_back("--sketch_bytes");
+			reads_option("--sketch_bytes", &ro.sketch_bytes);
 			break;
 		case OPT_HIST:
 			hist_out = optarg;
+			ro.hist = 1;
 			reads_only.push_back("--hist");
 			break;
 		case OPT_SAVE_BF:
@@ -484,12 +461,10 @@ main(int argc, char** argv)
 			reads_only.push_back("--save_bf");
 			break;
 		case OPT_READS_BATCH:
-			reads_batch = parse_count("--batch_bytes", optarg);
-			reads_only.push_back("--batch_bytes");
+			reads_option("--batch_bytes", &ro.batch_bytes);
 			break;
 		case OPT_STORE_CAP:
-			store_cap = parse_count("--resident_cap", optarg);
-			reads_only.push_back("--resident_cap");
+			reads_option("--resident_cap", &ro.store_cap);
 			break;
 		case OPT_GPU:
 			parse(c, optarg, gpu);
@@ -570,41 +545,12 @@ main(int argc, char** argv)
 			refuse("--reads and --shard: every shard would build the whole filter again; build it once with "
 			       "ntedit-make-reads-bf and give each shard -r");
 		}
-		if (!have_k) {
-			refuse("-k: required with --reads");
+		for (const std::string& r : read_files) {
+			paths.push_back(r.c_str());
 		}
-		uint64_t kv = 0;
-		{
-			char* end = nullptr;
-			errno = 0;
-			kv = strtoull(k_arg.c_str(), &end, 10);
-			if (k_arg.empty() || k_arg[0] == '-' || k_arg[0] == '+' || errno || *end || kv < 12 || kv > 200) {
-				refuse("-k " + k_arg + ": k must be between 12 and 200");
-			}
-		}
-		if (have_cutoff && solid) {
-			refuse("--cutoff and --solid: give one of them (--solid takes the minimum count from the k-mer histogram)");
-		}
-		if (!have_cutoff && !solid) {
-			refuse("--cutoff or --solid: one of them is required with --reads");
-		}
-		if (have_cutoff && (cutoff < 1 || cutoff > 255)) {
-			refuse("--cutoff " + std::to_string(cutoff) + ": the minimum count must be between 1 and 255");
-		}
-		if (hashes < 1 || hashes > 8) {
-			refuse("--hashes " + std::to_string(hashes) + ": the number of hash functions must be between 1 and 8");
-		}
-		if (!have_bf && !have_ne && !solid && hist_out.empty()) {
-			refuse("--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter from the "
-			       "k-mer histogram)");
-		}
-		if ((have_bf && bf_bytes == 0) ||
-		    (!have_bf && have_ne && ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr) == 0)) {
-			refuse("--bf / --num_elements: the filter would be empty");
-		}
-		if (reads_batch < 4096) {
-			refuse("--batch_bytes: at least 4096");
-		}
+		ro.files = paths.data(); // (for the default sketch: their sizes)
+		ro.n_files = (uint32_t)paths.size();
+		rr = reads_rules(ro, 1);
 		for (const std::string& r : read_files) {
 			die_unreadable(r);
 		}
@@ -697,39 +643,29 @@ main(int argc, char** argv)
 		// resident in HBM after pass 1 unless they would pass store_cap, so that the later passes do not parse them again
 		printf("---------- building Bloom filter from reads         : %s\n", ctime(&rawtime));
 		fflush(stdout);
-		std::vector<const char*> paths;
-		for (const std::string& r : read_files) {
-			paths.push_back(r.c_str());
-		}
-		const uint32_t kv = (uint32_t)strtoul(k_arg.c_str(), nullptr, 10);
-		const bool size_from_hist = !have_bf && !have_ne;
-		const uint64_t bf_size = have_bf ? bf_bytes : have_ne ? ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr) : 0;
-		if (sketch_bytes == 0) {
-			sketch_bytes = ntedit_hip_reads_default_sketch(paths.data(), (uint32_t)paths.size(), size_from_hist ? 0 : bf_size);
-		}
 		printf("BF size (bytes): ");
-		if (size_from_hist) {
+		if (rr.size_from_hist) {
 			printf("from the k-mer histogram\n");
 		} else {
-			printf("%llu\n", (unsigned long long)bf_size);
+			printf("%llu\n", (unsigned long long)rr.bf_bytes);
 		}
-		printf("Sketch size (counters): %llu\n", (unsigned long long)sketch_bytes);
+		printf("Sketch size (counters): %llu\n", (unsigned long long)rr.sketch_counters);
 		ntedit_hip_reads_build_args ba = {};
 		ba.files = paths.data();
 		ba.n_files = (uint32_t)paths.size();
-		ba.k = kv;
-		ba.hash_num = (uint32_t)hashes;
-		ba.cmin = (uint32_t)cutoff;
-		ba.solid = solid;
+		ba.k = rr.k;
+		ba.hash_num = rr.hash_num;
+		ba.cmin = rr.cmin;
+		ba.solid = ro.solid;
 		ba.counts = counts;
-		ba.bf_bytes = bf_size;
-		ba.fpr = fpr;
-		ba.sketch_counters = sketch_bytes;
-		ba.batch_bytes = reads_batch;
+		ba.bf_bytes = rr.bf_bytes;
+		ba.fpr = rr.fpr;
+		ba.sketch_counters = rr.sketch_counters;
+		ba.batch_bytes = rr.batch_bytes;
 		ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
 		ba.use_store = 1;
-		ba.store_cap = store_cap;
-		ba.log = reads_log;
+		ba.store_cap = rr.store_cap;
+		ba.log = nte_host::reads_log;
 		ntedit_hip_reads_build_result br;
 		if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_reads_last_error(ctx));
@@ -745,7 +681,7 @@ main(int argc, char** argv)
 			printf("Bloom filter saved to %s\n", save_bf.c_str());
 		}
 		// (the _r part of the default prefix: the name ntedit-make-reads-bf would have written it under)
-		bf = save_bf.empty() ? "reads_k" + std::to_string(kv) + ".bf" : save_bf;
+		bf = save_bf.empty() ? "reads_k" + std::to_string(rr.k) + ".bf" : save_bf;
 	} else {
 		printf("---------- loading Bloom filter from file           : %s\n", ctime(&rawtime));
 		if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_PRIMARY, bf.c_str()) != 0) {

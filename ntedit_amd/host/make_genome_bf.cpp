@@ -9,6 +9,7 @@
 // (ntedit_hip_filter_insert).  -t is accepted; the k-mers are hashed on the GPU.
 #include "../../include/ntedit_hip.h"
 #include "fasta.h"
+#include "log_info.h"
 
 #include <cmath>
 #include <cstdio>
@@ -19,15 +20,7 @@
 #include <string>
 #include <vector>
 
-static void
-log_info(const std::string& msg)
-{
-	// btllib::log_info: "[<local time>] [INFO] <msg>" on stderr
-	char ts[64];
-	time_t now = time(nullptr);
-	strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", localtime(&now));
-	std::cerr << "[" << ts << "] [INFO] " << msg << std::endl;
-}
+using nte_host::log_info;
 
 // ntedit_make_genome_bf.cpp:41-47 (Broder & Mitzenmacher 2004, via ntHits)
 static uint64_t

@@ -18,8 +18,8 @@
 // takes CMIN from its first valley (ntedit_hip_reads_solid_cutoff), and without --bf / --num_elements the output is
 // sized from it: --num_elements N with N = the distinct k-mers the histogram puts at CMIN or above.
 #include "../../include/ntedit_hip.h"
+#include "log_info.h"
 
-#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -29,19 +29,10 @@
 #include <string>
 #include <vector>
 
-static void
-log_info(const std::string& msg)
-{
-	// btllib::log_info: "[<local time>] [INFO] <msg>" on stderr
-	char ts[64];
-	time_t now = time(nullptr);
-	strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", localtime(&now));
-	std::cerr << "[" << ts << "] [INFO] " << msg << std::endl;
-}
+using nte_host::log_info;
 
-// (the sizing, the passes and the --hist writer live in the library: reads_pass.cpp, shared with the sharded driver)
-static const uint64_t BATCH_DEFAULT = 256ull << 20;
-
+// (the option rules, the sizing, the passes and the --hist writer live in the library: reads_options.cpp and
+// reads_pass.cpp, shared with the sharded driver and `ntedit --reads`)
 static void
 usage(const char* why)
 {
@@ -84,23 +75,6 @@ is_option(const char* a)
 	return a[0] == '-' && a[1] != 0 && !(a[1] >= '0' && a[1] <= '9');
 }
 
-// a whole non-negative decimal number, or false
-static bool
-parse_u64(const char* s, uint64_t* out)
-{
-	if (!s || !*s || *s == '-' || *s == '+') {
-		return false;
-	}
-	char* end = nullptr;
-	errno = 0;
-	const unsigned long long v = strtoull(s, &end, 10);
-	if (errno || *end) {
-		return false;
-	}
-	*out = v;
-	return true;
-}
-
 static void
 die(ntedit_hip_ctx* ctx, const std::string& why)
 {
@@ -112,25 +86,13 @@ die(ntedit_hip_ctx* ctx, const std::string& why)
 	exit(1);
 }
 
-// the build's console lines (ntedit_hip_reads_build_args.log)
-static void
-log_line(void*, int to_stdout, const char* line)
-{
-	if (to_stdout) {
-		std::cout << line << std::endl;
-	} else {
-		log_info(line);
-	}
-}
-
 int
 main(int argc, char** argv)
 {
-	std::vector<std::string> read_files;
-	uint64_t k = 0, cmin = 0, hashes = 3, num_threads = 12, bf_bytes = 0, num_elements = 0, sketch_bytes = 0;
-	uint64_t batch_bytes = BATCH_DEFAULT;
-	bool have_k = false, have_c = false, have_bf = false, have_ne = false, counts = false, solid = false;
-	double fpr = 0.01;
+	std::vector<const char*> paths;
+	ntedit_hip_reads_options ro = {};
+	ntedit_hip_reads_rules rr;
+	bool counts = false;
 	std::string out_file, sketch_out, hist_out;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
@@ -141,155 +103,107 @@ main(int argc, char** argv)
 			}
 			return argv[++i];
 		};
-		auto number = [&](const char* name) -> uint64_t {
-			const char* v = value(name);
-			uint64_t x = 0;
-			if (!parse_u64(v, &x)) {
-				usage((std::string(name) + ": not a number: '" + v + "'").c_str());
+		// an option of the shared rules: what they refuse at the option itself is refused here
+		auto given = [&](const char* name, const char*& text) {
+			text = value(name);
+			if (ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_TOOL, 0, &rr) != 0) {
+				usage(ntedit_hip_reads_last_error(nullptr));
 				exit(1);
 			}
-			return x;
 		};
 		if (a == "-h" || a == "--help") {
 			usage(nullptr);
 			return 0;
 		} else if (a == "--reads") {
 			while (i + 1 < argc && !is_option(argv[i + 1])) {
-				read_files.push_back(argv[++i]);
+				paths.push_back(argv[++i]);
 			}
 		} else if (a == "-k") {
-			k = number("-k");
-			have_k = true;
+			given("-k", ro.k);
 		} else if (a == "-c") {
-			cmin = number("-c");
-			have_c = true;
+			given("-c", ro.cutoff);
 		} else if (a == "--solid") {
-			solid = true;
+			ro.solid = 1;
 		} else if (a == "--hist") {
 			hist_out = value("--hist");
 		} else if (a == "--counts") {
 			counts = true;
 		} else if (a == "--hashes") {
-			hashes = number("--hashes");
+			given("--hashes", ro.hashes);
 		} else if (a == "--fpr") {
-			char* end = nullptr;
-			const char* v = value("--fpr");
-			fpr = strtod(v, &end);
-			if (*end || !(fpr > 0.0 && fpr < 1.0)) {
-				usage((std::string("--fpr: needs a number between 0 and 1: '") + v + "'").c_str());
-				return 1;
-			}
+			given("--fpr", ro.fpr);
 		} else if (a == "--bf") {
-			bf_bytes = number("--bf");
-			have_bf = true;
+			given("--bf", ro.bf);
 		} else if (a == "--num_elements") {
-			num_elements = number("--num_elements");
-			have_ne = true;
+			given("--num_elements", ro.num_elements);
 		} else if (a == "--sketch_bytes") {
-			sketch_bytes = number("--sketch_bytes");
+			given("--sketch_bytes", ro.sketch_bytes);
 		} else if (a == "--batch_bytes") { // (not in the usage text: tests force many small batches with it)
-			batch_bytes = number("--batch_bytes");
+			given("--batch_bytes", ro.batch_bytes);
 		} else if (a == "--save_sketch") { // (not in the usage text: tests compare the sketch itself)
 			sketch_out = value("--save_sketch");
 		} else if (a == "-o") {
 			out_file = value("-o");
 		} else if (a == "-t") {
-			num_threads = number("-t");
+			given("-t", ro.threads);
 		} else {
 			usage(("Unknown argument: " + a).c_str());
 			return 1;
 		}
 	}
-	if (read_files.empty()) {
+	if (paths.empty()) {
 		usage("--reads: 1 or more argument(s) expected. 0 provided.");
 		return 1;
 	}
-	if (!have_k) {
-		usage("-k: required.");
-		return 1;
-	}
-	if (k < 12 || k > 200) {
-		usage(("-k " + std::to_string(k) + ": k must be between 12 and 200.").c_str());
-		return 1;
-	}
-	if (solid && have_c) {
-		usage("--solid and -c: give one of them (--solid takes the minimum count from the k-mer histogram).");
-		return 1;
-	}
-	if (!have_c && !solid) {
-		usage("-c: required (or --solid).");
-		return 1;
-	}
-	if (have_c && (cmin < 1 || cmin > 255)) {
-		usage(("-c " + std::to_string(cmin) + ": the minimum count must be between 1 and 255.").c_str());
-		return 1;
-	}
-	if (hashes < 1 || hashes > 8) {
-		usage(("--hashes " + std::to_string(hashes) + ": the number of hash functions must be between 1 and 8.").c_str());
-		return 1;
-	}
-	const bool gather_hist = solid || !hist_out.empty();
-	const bool size_from_hist = !have_bf && !have_ne;
-	if (size_from_hist && !gather_hist) {
-		usage("--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter from the k-mer "
-		      "histogram).");
-		return 1;
-	}
-	if (batch_bytes < 4096) {
-		usage("--batch_bytes: at least 4096.");
+	ro.hist = !hist_out.empty();
+	ro.files = paths.data();
+	ro.n_files = (uint32_t)paths.size();
+	const int refused = ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_TOOL, 1, &rr);
+	if (refused && refused != NTEDIT_READS_EMPTY) {
+		usage(ntedit_hip_reads_last_error(nullptr));
 		return 1;
 	}
 	if (out_file.empty()) {
-		out_file = "reads_k" + std::to_string(k) + ".bf";
+		out_file = "reads_k" + std::to_string(rr.k) + ".bf";
 	}
 
 	std::cout << "Parameters:" << std::endl;
 	std::cout << "\t\t--reads ";
-	for (const std::string& r : read_files) {
+	for (const char* r : paths) {
 		std::cout << r << " ";
 	}
 	std::cout << std::endl;
-	std::cout << "\t\t-t " << num_threads << std::endl;
-	std::cout << "\t\t-k " << k << std::endl;
-	if (solid) {
+	std::cout << "\t\t-t " << rr.threads << std::endl;
+	std::cout << "\t\t-k " << rr.k << std::endl;
+	if (ro.solid) {
 		std::cout << "\t\t--solid" << std::endl;
 	} else {
-		std::cout << "\t\t-c " << cmin << std::endl;
+		std::cout << "\t\t-c " << rr.cmin << std::endl;
 	}
 	if (!hist_out.empty()) {
 		std::cout << "\t\t--hist " << hist_out << std::endl;
 	}
-	std::cout << "\t\t--fpr " << fpr << std::endl;
-	std::cout << "\t\t--hashes " << hashes << std::endl;
+	std::cout << "\t\t--fpr " << rr.fpr << std::endl;
+	std::cout << "\t\t--hashes " << rr.hash_num << std::endl;
 	std::cout << "\t\t-o " << out_file << std::endl;
 	if (counts) {
 		std::cout << "\t\t--counts" << std::endl;
 	}
-	uint64_t bf_size = 0;
-	if (have_bf) {
-		bf_size = bf_bytes;
-		std::cout << "\t\t--bf " << bf_size << std::endl;
-	} else if (have_ne) {
-		std::cout << "\t\t--num_elements " << num_elements << std::endl;
-		bf_size = ntedit_hip_reads_bf_size(num_elements, (uint32_t)hashes, fpr);
+	if (ro.bf) {
+		std::cout << "\t\t--bf " << rr.bf_bytes << std::endl;
+	} else if (ro.num_elements) {
+		std::cout << "\t\t--num_elements " << rr.num_elements << std::endl;
 	}
-	if (!size_from_hist && bf_size == 0) {
-		usage("The output filter would be empty (--bf 0 or --num_elements too small).");
+	if (refused) { // (the output filter would be empty)
+		usage(ntedit_hip_reads_last_error(nullptr));
 		return 1;
 	}
-	if (size_from_hist) {
+	if (rr.size_from_hist) {
 		std::cout << "BF size (bytes): from the k-mer histogram" << std::endl;
 	} else {
-		std::cout << "BF size (bytes): " << bf_size << std::endl;
+		std::cout << "BF size (bytes): " << rr.bf_bytes << std::endl;
 	}
-	if (sketch_bytes == 0) {
-		std::vector<const char*> paths;
-		for (const std::string& f : read_files) {
-			paths.push_back(f.c_str());
-		}
-		sketch_bytes = ntedit_hip_reads_default_sketch(paths.data(), (uint32_t)paths.size(), size_from_hist ? 0 : bf_size);
-	}
-	std::cout << "Sketch size (counters): " << sketch_bytes << std::endl;
+	std::cout << "Sketch size (counters): " << rr.sketch_counters << std::endl;
 
 	ntedit_hip_ctx* ctx = nullptr;
 	if (ntedit_hip_create(0, &ctx) != 0) {
@@ -297,25 +211,21 @@ main(int argc, char** argv)
 		return 1;
 	}
 	// sketch, pass 1, the histogram pass, the output filter, pass 2 (reads_pass.cpp, shared with `ntedit --reads`)
-	std::vector<const char*> paths;
-	for (const std::string& f : read_files) {
-		paths.push_back(f.c_str());
-	}
 	ntedit_hip_reads_build_args ba = {};
 	ba.files = paths.data();
 	ba.n_files = (uint32_t)paths.size();
-	ba.k = (uint32_t)k;
-	ba.hash_num = (uint32_t)hashes;
-	ba.cmin = (uint32_t)cmin;
-	ba.solid = solid;
+	ba.k = rr.k;
+	ba.hash_num = rr.hash_num;
+	ba.cmin = rr.cmin;
+	ba.solid = ro.solid;
 	ba.counts = counts;
-	ba.bf_bytes = size_from_hist ? 0 : bf_size;
-	ba.fpr = fpr;
-	ba.sketch_counters = sketch_bytes;
-	ba.batch_bytes = batch_bytes;
+	ba.bf_bytes = rr.bf_bytes;
+	ba.fpr = rr.fpr;
+	ba.sketch_counters = rr.sketch_counters;
+	ba.batch_bytes = rr.batch_bytes;
 	ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
 	ba.sketch_path = sketch_out.empty() ? nullptr : sketch_out.c_str();
-	ba.log = log_line;
+	ba.log = nte_host::reads_log;
 	ntedit_hip_reads_build_result br;
 	if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));
@@ -326,7 +236,7 @@ main(int argc, char** argv)
 		die(ctx, ntedit_hip_last_error(ctx));
 	}
 	// btllib get_fpr(): occupancy ^ hash_num
-	std::cout << "Bloom filter FPR: " << pow((double)occupied / (double)slots, (double)hashes) << std::endl;
+	std::cout << "Bloom filter FPR: " << pow((double)occupied / (double)slots, (double)rr.hash_num) << std::endl;
 
 	log_info(counts ? "Saving counting Bloom filter" : "Saving Bloom filter");
 	if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, out_file.c_str()) != 0) {

@@ -1,0 +1,131 @@
+// reads_options.cpp -- the rules of the reads options, once for the four front ends that take them: ntedit-make-reads-bf
+// and python -m ntedit_amd.make_reads (the TOOL dialect: -c, sentences that end in a period), ntedit --reads and
+// python -m ntedit_amd.run --reads (the POLISHER dialect: --cutoff, "with --reads").  Host only.  A front end keeps how it
+// walks its arguments and what only it has; what is refused, in which order and in which words is here.
+#include "../../include/ntedit_hip.h"
+
+#include <cerrno>
+#include <cstdlib>
+#include <string>
+
+namespace nte_reads {
+int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+}
+
+namespace {
+
+// a whole non-negative decimal number, or false
+bool
+parse_u64(const char* s, uint64_t* out)
+{
+	if (!*s || *s == '-' || *s == '+') {
+		return false;
+	}
+	char* end = nullptr;
+	errno = 0;
+	const unsigned long long v = strtoull(s, &end, 10);
+	if (errno || *end) {
+		return false;
+	}
+	*out = v;
+	return true;
+}
+
+} // namespace
+
+extern "C" int
+ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, int final, ntedit_hip_reads_rules* r)
+{
+	if (!o || !r || (o->n_files && !o->files) ||
+	    (dialect != NTEDIT_READS_DIALECT_TOOL && dialect != NTEDIT_READS_DIALECT_POLISHER)) {
+		return nte_reads::set_error(nullptr, NTEDIT_E_ARG, "reads_options_check: bad argument");
+	}
+	const bool tool = dialect == NTEDIT_READS_DIALECT_TOOL;
+	const std::string cut = tool ? "-c" : "--cutoff", dot = tool ? "." : "", with_reads = tool ? "." : " with --reads";
+	auto refuse = [](int code, const std::string& why) { return nte_reads::set_error(nullptr, code, why); };
+	// an option's number; true: malformed, and refused in the dialect's words
+	auto malformed = [&](const std::string& name, const char* text, uint64_t* out) {
+		if (!text || parse_u64(text, out)) {
+			return false;
+		}
+		refuse(0, tool ? name + ": not a number: '" + text + "'" : "invalid option: `" + name + " " + text + "'");
+		return true;
+	};
+	*r = ntedit_hip_reads_rules();
+	r->hash_num = 3;
+	r->fpr = 0.01;
+	r->batch_bytes = NTEDIT_READS_BATCH_DEFAULT;
+	r->store_cap = NTEDIT_READS_RESIDENT_CAP_DEFAULT;
+	r->threads = 12;
+	uint64_t k = 0, cmin = 0, hashes = r->hash_num;
+	// -k: the tool refuses a malformed one at the option, the polisher takes it as out of range
+	if (final && !o->k) {
+		return refuse(NTEDIT_READS_REFUSED, "-k: required" + with_reads);
+	}
+	if (o->k) {
+		if (tool && malformed("-k", o->k, &k)) {
+			return NTEDIT_READS_NOT_A_NUMBER;
+		}
+		if (final && (!parse_u64(o->k, &k) || k < 12 || k > 200)) {
+			return refuse(NTEDIT_READS_REFUSED, "-k " + (tool ? std::to_string(k) : std::string(o->k)) + ": k must be between 12 and 200" + dot);
+		}
+	}
+	// what is refused at the option itself
+	if (malformed(cut, o->cutoff, &cmin) || malformed("--hashes", o->hashes, &hashes)) {
+		return NTEDIT_READS_NOT_A_NUMBER;
+	}
+	if (o->fpr) {
+		char* end = nullptr;
+		r->fpr = strtod(o->fpr, &end);
+		if (!*o->fpr || *end || !(r->fpr > 0.0 && r->fpr < 1.0)) {
+			return refuse(NTEDIT_READS_REFUSED, tool ? std::string("--fpr: needs a number between 0 and 1: '") + o->fpr + "'"
+			                                         : std::string("--fpr ") + o->fpr + ": needs a number between 0 and 1");
+		}
+	}
+	if (malformed("--bf", o->bf, &r->bf_bytes) || malformed("--num_elements", o->num_elements, &r->num_elements) ||
+	    malformed("--sketch_bytes", o->sketch_bytes, &r->sketch_bytes) || malformed("--batch_bytes", o->batch_bytes, &r->batch_bytes) ||
+	    malformed("--resident_cap", o->store_cap, &r->store_cap) || malformed("-t", o->threads, &r->threads)) {
+		return NTEDIT_READS_NOT_A_NUMBER;
+	}
+	if (!final) {
+		return 0;
+	}
+	// the rules between the options
+	if (o->cutoff && o->solid) {
+		return refuse(NTEDIT_READS_REFUSED, (tool ? "--solid and -c" : "--cutoff and --solid") +
+		                                        std::string(": give one of them (--solid takes the minimum count from the k-mer histogram)") + dot);
+	}
+	if (!o->cutoff && !o->solid) {
+		return refuse(NTEDIT_READS_REFUSED, tool ? "-c: required (or --solid)." : "--cutoff or --solid: one of them is required with --reads");
+	}
+	if (o->cutoff && (cmin < 1 || cmin > 255)) {
+		return refuse(NTEDIT_READS_REFUSED, cut + " " + std::to_string(cmin) + ": the minimum count must be between 1 and 255" + dot);
+	}
+	if (hashes < 1 || hashes > 8) {
+		return refuse(NTEDIT_READS_REFUSED, "--hashes " + std::to_string(hashes) + ": the number of hash functions must be between 1 and 8" + dot);
+	}
+	r->k = (uint32_t)k;
+	r->cmin = (uint32_t)cmin;
+	r->hash_num = (uint32_t)hashes;
+	r->gather_hist = o->solid || o->hist;
+	r->size_from_hist = !o->bf && !o->num_elements;
+	if (r->size_from_hist && !r->gather_hist) {
+		return refuse(NTEDIT_READS_REFUSED, "--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter "
+		                                    "from the k-mer histogram)" + dot);
+	}
+	if (!o->bf && o->num_elements) {
+		r->bf_bytes = ntedit_hip_reads_bf_size(r->num_elements, r->hash_num, r->fpr);
+	}
+	const bool empty = !r->size_from_hist && r->bf_bytes == 0;
+	if (empty && !tool) {
+		return refuse(NTEDIT_READS_REFUSED, "--bf / --num_elements: the filter would be empty");
+	}
+	if (r->batch_bytes < 4096) {
+		return refuse(NTEDIT_READS_REFUSED, "--batch_bytes: at least 4096" + dot);
+	}
+	if (empty) { // (the tool has printed its parameters by then)
+		return refuse(NTEDIT_READS_EMPTY, "The output filter would be empty (--bf 0 or --num_elements too small).");
+	}
+	r->sketch_counters = r->sketch_bytes ? r->sketch_bytes : ntedit_hip_reads_default_sketch(o->files, o->n_files, r->bf_bytes);
+	return 0;
+}

@@ -1,7 +1,7 @@
 // reads_pass.cpp -- the host side of the reads k-mer filter build, shared by ntedit-make-reads-bf and the sharded driver
 // (ntedit_amd/make_reads.py): one pass over a list of byte ranges of the input files, parsed by FastaReader into bounded
 // batches double-buffered through page-locked memory (a second thread parses the next batch while the GPU works on the
-// current one); the tool's sizing; its --hist writer.
+// current one); the tool's sizing; its --hist writer; and the build itself, in four stages that both walk.
 //
 // A range [begin, end) of a file owns the records whose first byte lies in it.  A range that starts past byte 0 first
 // moves forward to the first record start: a line that starts with '>' in a FASTA file, or in a FASTQ file a line that
@@ -39,7 +39,6 @@ const uint64_t WHOLE = ~0ull; // `end` of a range that runs to the end of its fi
 // default sketch: 16 output bytes' worth of counters, within [64 MiB, 32 GiB]; sized from the histogram (the output
 // size not known yet): one counter per input byte, a gzip file counted at 4 x its size, within the same bounds
 const uint64_t SKETCH_PER_OUTPUT_BYTE = 16;
-const uint64_t GZIP_INPUT_FACTOR = 4;
 const uint64_t SKETCH_MIN = 64ull << 20;
 const uint64_t SKETCH_MAX = 32ull << 30;
 
@@ -457,7 +456,7 @@ ntedit_hip_reads_default_sketch(const char* const* files, uint32_t n, uint64_t b
 			if (!files || !files[i] || stat(files[i], &st) != 0 || !S_ISREG(st.st_mode)) {
 				continue;
 			}
-			counters += (uint64_t)st.st_size * (is_gzip(files[i]) ? GZIP_INPUT_FACTOR : 1);
+			counters += (uint64_t)st.st_size * (is_gzip(files[i]) ? NTEDIT_READS_GZIP_WEIGHT : 1);
 		}
 		counters = counters > SKETCH_MAX ? SKETCH_MAX : counters;
 	}
@@ -474,164 +473,68 @@ ntedit_hip_reads_is_gzip(const char* path)
 
 namespace {
 
+// the build's console lines; a rank's share of a sharded build (ranges) names the rank on its pass and store lines, and
+// only rank 0 (the one process of an unsharded build is rank 0) says what every rank decides alike
 struct BuildLog
 {
 	const ntedit_hip_reads_build_args* a;
-	void info(const std::string& s) const
+	bool first_only = false;
+	bool ranged() const { return a->begins != nullptr; }
+	void rank_info(const std::string& s) const
 	{
-		if (a->log) {
-			a->log(a->user, 0, s.c_str());
-		}
+		info(ranged() ? "rank " + std::to_string(a->rank) + "/" + std::to_string(a->world) + ": " + s : s);
 	}
-	void out(const std::string& s) const
+	void info(const std::string& s) const { line(0, s); }
+	void out(const std::string& s) const { line(1, s); }
+	void line(int to_stdout, const std::string& s) const
 	{
-		if (a->log) {
-			a->log(a->user, 1, s.c_str());
+		if (a->log && !(first_only && a->rank != 0)) {
+			a->log(a->user, to_stdout, s.c_str());
 		}
 	}
 };
 
-// the tool's line of one pass (the large-run tests read it)
-void
-log_pass(const BuildLog& lg, int pass, const ntedit_hip_reads_pass_stats& st)
+// one pass, over the ranges (the files whole) or over the resident store (the store's bases: pass 1's), and its line
+// (the large-run tests read it)
+int
+build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, ntedit_hip_reads_build_result* r, uint64_t* starts,
+           uint64_t* nexts)
 {
 	static const char* const names[] = { "1 (count)", "H (histogram)", "2 (solid k-mers)" };
+	const BuildLog lg{ a };
+	ntedit_hip_reads_pass_stats& st = r->pass[pass];
+	std::string what;
+	int rc;
+	if (pass != NTEDIT_READS_PASS_COUNT && r->store_state == NTEDIT_RESIDENT_ON) {
+		const auto t0 = std::chrono::steady_clock::now();
+		rc = pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_resident_histogram(ctx)
+		                                    : ntedit_hip_resident_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, r->cmin);
+		st.bases = r->pass[NTEDIT_READS_PASS_COUNT].bases;
+		st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		st.ms_gpu = st.ms_wall;
+		what = std::to_string(r->store_batches) + " batches of the resident store";
+	} else {
+		const std::vector<uint64_t> begins(a->n_files, 0), ends(a->n_files, WHOLE);
+		rc = ntedit_hip_reads_pass(ctx, pass, a->files, lg.ranged() ? a->begins : begins.data(), lg.ranged() ? a->ends : ends.data(),
+		                           a->n_files, a->batch_bytes, r->cmin, &st, starts, nexts);
+		what = std::to_string(a->n_files) + " ranges";
+	}
+	if (rc != 0) {
+		return NTEDIT_E_IO; // (the message is the pass's)
+	}
 	char line[256];
 	snprintf(line, sizeof line, "Pass %s: %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", names[pass],
 	         (unsigned long long)st.bases, st.ms_wall, st.ms_wall > 0 ? st.bases / st.ms_wall / 1e6 : 0.0, st.ms_gpu,
 	         st.ms_gpu > 0 ? st.bases / st.ms_gpu / 1e6 : 0.0);
-	lg.info(line);
-}
-
-// one pass, over the files whole or over the resident store (the store's bases: pass 1's)
-int
-build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, bool from_store, uint32_t cmin,
-           uint64_t store_reads_bases, ntedit_hip_reads_pass_stats* st)
-{
-	if (from_store) {
-		const auto t0 = std::chrono::steady_clock::now();
-		const int rc = pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_resident_histogram(ctx)
-		                                              : ntedit_hip_resident_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, cmin);
-		st->bases = store_reads_bases;
-		st->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-		st->ms_gpu = st->ms_wall;
-		return rc;
-	}
-	const std::vector<uint64_t> begins(a->n_files, 0), ends(a->n_files, WHOLE);
-	return ntedit_hip_reads_pass(ctx, pass, a->files, begins.data(), ends.data(), a->n_files, a->batch_bytes, cmin, st,
-	                             nullptr, nullptr);
-}
-
-int
-build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r)
-{
-	const BuildLog lg{ a };
-	uint32_t cmin = a->cmin;
-	if (ntedit_hip_sketch_alloc(ctx, a->sketch_counters, a->hash_num, a->k) != 0) {
-		return NTEDIT_E_DEVICE; // (the message is sketch_alloc's)
-	}
-	if (a->use_store && ntedit_hip_resident_begin(ctx, a->store_cap) != 0) {
-		return NTEDIT_E_DEVICE;
-	}
-	lg.info("Pass 1: counting k-mers");
-	if (build_pass(ctx, a, NTEDIT_READS_PASS_COUNT, false, cmin, 0, &r->pass[NTEDIT_READS_PASS_COUNT]) != 0) {
-		return NTEDIT_E_IO;
-	}
-	log_pass(lg, NTEDIT_READS_PASS_COUNT, r->pass[NTEDIT_READS_PASS_COUNT]);
-	uint64_t nonzero = 0, counters = 0;
-	if (ntedit_hip_sketch_occupancy(ctx, &nonzero, &counters) != 0) {
-		return NTEDIT_E_DEVICE;
-	}
-	{
-		std::ostringstream o;
-		o << "Sketch occupancy: " << nonzero << " / " << counters << " counters (" << (double)nonzero / (double)counters << ")";
-		lg.out(o.str());
-	}
-	if (a->sketch_path && ntedit_hip_sketch_save_file(ctx, a->sketch_path) != 0) {
-		return NTEDIT_E_IO;
-	}
-	bool from_store = false;
-	if (a->use_store) {
-		ntedit_hip_resident_stats ss;
-		if (ntedit_hip_resident_info(ctx, &ss) != 0) {
-			return NTEDIT_E_DEVICE;
-		}
-		r->store_state = ss.state;
-		r->store_bytes = ss.bytes;
-		from_store = ss.state == NTEDIT_RESIDENT_ON;
-		const std::string later = a->solid || a->hist_path ? "the histogram pass and pass 2" : "pass 2";
-		if (from_store) {
-			lg.info("Resident store: " + std::to_string(ss.batches) + " batches, " + std::to_string(ss.bytes) +
-			        " bytes of HBM (3 bits per base); " + later + " read it");
-		} else {
-			lg.info(std::string("Resident store: released (") +
-			        (ss.state == NTEDIT_RESIDENT_OVER_CAP ? "the reads would pass its cap of " + std::to_string(ss.cap) + " bytes"
-			                                                 : std::string("a device allocation failed")) +
-			        "); " + later + " read the files");
-		}
-	}
-	const uint64_t reads_bases = r->pass[NTEDIT_READS_PASS_COUNT].bases;
-	uint64_t bf_size = a->bf_bytes;
-	if (a->solid || a->hist_path) {
-		lg.info("Histogram pass: the k-mer histogram of the sketch's estimates");
-		if (build_pass(ctx, a, NTEDIT_READS_PASS_HIST, from_store, cmin, reads_bases, &r->pass[NTEDIT_READS_PASS_HIST]) != 0) {
-			return NTEDIT_E_IO;
-		}
-		log_pass(lg, NTEDIT_READS_PASS_HIST, r->pass[NTEDIT_READS_PASS_HIST]);
-		uint64_t occ[256], f[256], F0 = 0, F1 = 0;
-		if (ntedit_hip_sketch_histogram_download(ctx, occ) != 0) {
-			return NTEDIT_E_DEVICE;
-		}
-		ntedit_hip_reads_hist_summary(occ, f, &F0, &F1);
-		lg.info("k-mer histogram: F1 = " + std::to_string(F1) + " (k-mers), F0 = " + std::to_string(F0) + " (distinct k-mers)");
-		// written first: a refused --solid still leaves the histogram to look at
-		if (a->hist_path) {
-			if (ntedit_hip_reads_write_hist(a->hist_path, f, F0, F1) != 0) {
-				return pfail(ctx, NTEDIT_E_IO, std::string("cannot write ") + a->hist_path);
-			}
-			lg.info(std::string("Histogram written to ") + a->hist_path);
-		}
-		if (a->solid) {
-			uint32_t c = 0;
-			if (ntedit_hip_reads_solid_cutoff(f, &c) != 0) {
-				return pfail(ctx, NTEDIT_E_ARG, "--solid: the k-mer histogram has no valley after the error peak (no c with "
-				                                "f[c+1] > f[c]); pass -c");
-			}
-			cmin = c;
-			lg.info("--solid: minimum k-mer count " + std::to_string(cmin));
-		}
-		if (a->bf_bytes == 0) {
-			uint64_t num_elements = 0;
-			for (uint64_t c = cmin; c < 256; c++) {
-				num_elements += f[c];
-			}
-			bf_size = ntedit_hip_reads_bf_size(num_elements, a->hash_num, a->fpr);
-			lg.info("Sized from the k-mer histogram: --num_elements " + std::to_string(num_elements) + " (k-mers at " +
-			        std::to_string(cmin) + " or above), " + std::to_string(bf_size) + " bytes");
-			if (bf_size == 0) {
-				return pfail(ctx, NTEDIT_E_ARG, "The output filter would be empty (no k-mer at the minimum count or above).");
-			}
-			lg.out("BF size (bytes): " + std::to_string(bf_size));
-		}
-	}
-	if (bf_size == 0) {
-		return pfail(ctx, NTEDIT_E_ARG, "The output filter would be empty (--bf 0 or --num_elements too small).");
-	}
-	if (a->counts) {
-		if (ntedit_hip_filter_alloc_counting(ctx, NTEDIT_FILTER_PRIMARY, bf_size, a->hash_num, a->k) != 0) {
-			return NTEDIT_E_DEVICE;
-		}
-	} else if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, a->hash_num, a->k) != 0) {
-		return pfail(ctx, NTEDIT_E_DEVICE, ntedit_hip_last_error(ctx));
-	}
-	lg.info("Pass 2: inserting k-mers seen at least " + std::to_string(cmin) + " times");
-	if (build_pass(ctx, a, NTEDIT_READS_PASS_SOLID, from_store, cmin, reads_bases, &r->pass[NTEDIT_READS_PASS_SOLID]) != 0) {
-		return NTEDIT_E_IO;
-	}
-	log_pass(lg, NTEDIT_READS_PASS_SOLID, r->pass[NTEDIT_READS_PASS_SOLID]);
-	r->cmin = cmin;
-	r->bf_bytes = bf_size;
+	lg.rank_info(lg.ranged() ? line + (", " + what) : line);
 	return 0;
+}
+
+bool
+bad_build_args(const ntedit_hip_reads_build_args* a, const ntedit_hip_reads_build_result* r)
+{
+	return !a || !r || (a->n_files && !a->files) || (a->begins && !a->ends) || a->batch_bytes < 4096 ||
+	       (!a->solid && (a->cmin < 1 || a->cmin > 255)) || (a->bf_bytes == 0 && !a->solid && !a->hist_path);
 }
 
 } // namespace
@@ -639,17 +542,162 @@ build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_read
 extern "C" {
 
 int
+ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r,
+                             uint64_t* starts, uint64_t* nexts)
+{
+	if (!ctx || bad_build_args(a, r)) {
+		return pfail(ctx, NTEDIT_E_ARG, "reads_stage_count: bad argument");
+	}
+	const BuildLog lg{ a };
+	*r = ntedit_hip_reads_build_result();
+	if (!lg.ranged() && ntedit_hip_sketch_alloc(ctx, a->sketch_counters, a->hash_num, a->k) != 0) {
+		return NTEDIT_E_DEVICE; // (the message is sketch_alloc's)
+	}
+	if (a->use_store && ntedit_hip_resident_begin(ctx, a->store_cap) != 0) {
+		return NTEDIT_E_DEVICE;
+	}
+	lg.rank_info("Pass 1: counting k-mers");
+	if (build_pass(ctx, a, NTEDIT_READS_PASS_COUNT, r, starts, nexts) != 0) {
+		return NTEDIT_E_IO;
+	}
+	if (a->use_store) {
+		ntedit_hip_resident_stats ss;
+		if (ntedit_hip_resident_info(ctx, &ss) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
+		r->store_state = ss.state;
+		r->store_bytes = ss.bytes;
+		r->store_batches = ss.batches;
+		const std::string later = a->solid || a->hist_path ? "the histogram pass and pass 2" : "pass 2";
+		if (ss.state == NTEDIT_RESIDENT_ON) {
+			lg.rank_info("Resident store: " + std::to_string(ss.batches) + " batches, " + std::to_string(ss.bytes) +
+			             " bytes of HBM (3 bits per base); " + later + " read it");
+		} else {
+			lg.rank_info(std::string("Resident store: released (") +
+			             (ss.state == NTEDIT_RESIDENT_OVER_CAP ? "the reads would pass its cap of " + std::to_string(ss.cap) + " bytes"
+			                                                      : std::string("a device allocation failed")) +
+			             "); " + later + " read the files");
+		}
+	}
+	return 0;
+}
+
+int
+ntedit_hip_reads_stage_histogram(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r,
+                                 uint64_t occ[256])
+{
+	if (!ctx || bad_build_args(a, r) || !occ) {
+		return pfail(ctx, NTEDIT_E_ARG, "reads_stage_histogram: bad argument");
+	}
+	const BuildLog lg{ a };
+	lg.rank_info("Histogram pass: the k-mer histogram of the sketch's estimates");
+	if (build_pass(ctx, a, NTEDIT_READS_PASS_HIST, r, nullptr, nullptr) != 0) {
+		return NTEDIT_E_IO;
+	}
+	return ntedit_hip_sketch_histogram_download(ctx, occ) != 0 ? NTEDIT_E_DEVICE : 0;
+}
+
+int
+ntedit_hip_reads_stage_decide(const ntedit_hip_reads_build_args* a, const uint64_t occ[256], ntedit_hip_reads_build_result* r)
+{
+	if (bad_build_args(a, r) || (!occ && (a->solid || a->bf_bytes == 0))) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_stage_decide: bad argument");
+	}
+	const BuildLog lg{ a, true };
+	r->cmin = a->cmin;
+	r->bf_bytes = a->bf_bytes;
+	if (occ) {
+		uint64_t f[256], F0 = 0, F1 = 0;
+		ntedit_hip_reads_hist_summary(occ, f, &F0, &F1);
+		lg.info("k-mer histogram: F1 = " + std::to_string(F1) + " (k-mers), F0 = " + std::to_string(F0) + " (distinct k-mers)");
+		// written first: a refused --solid still leaves the histogram to look at
+		if (a->hist_path && a->rank == 0) {
+			if (ntedit_hip_reads_write_hist(a->hist_path, f, F0, F1) != 0) {
+				return pfail(nullptr, NTEDIT_E_IO, std::string("cannot write ") + a->hist_path);
+			}
+			lg.info(std::string("Histogram written to ") + a->hist_path);
+		}
+		if (a->solid) {
+			if (ntedit_hip_reads_solid_cutoff(f, &r->cmin) != 0) {
+				return pfail(nullptr, NTEDIT_E_ARG, "--solid: the k-mer histogram has no valley after the error peak (no c with "
+				                                    "f[c+1] > f[c]); pass -c");
+			}
+			lg.info("--solid: minimum k-mer count " + std::to_string(r->cmin));
+		}
+		if (a->bf_bytes == 0) {
+			uint64_t num_elements = 0;
+			for (uint64_t c = r->cmin; c < 256; c++) {
+				num_elements += f[c];
+			}
+			r->bf_bytes = ntedit_hip_reads_bf_size(num_elements, a->hash_num, a->fpr);
+			lg.info("Sized from the k-mer histogram: --num_elements " + std::to_string(num_elements) + " (k-mers at " +
+			        std::to_string(r->cmin) + " or above), " + std::to_string(r->bf_bytes) + " bytes");
+			if (r->bf_bytes == 0) {
+				return pfail(nullptr, NTEDIT_E_ARG, "The output filter would be empty (no k-mer at the minimum count or above).");
+			}
+			lg.out("BF size (bytes): " + std::to_string(r->bf_bytes));
+		}
+	}
+	if (r->bf_bytes == 0) {
+		return pfail(nullptr, NTEDIT_E_ARG, "The output filter would be empty (--bf 0 or --num_elements too small).");
+	}
+	return 0;
+}
+
+int
+ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r)
+{
+	if (!ctx || bad_build_args(a, r) || r->bf_bytes == 0 || r->cmin < 1 || r->cmin > 255) {
+		return pfail(ctx, NTEDIT_E_ARG, "reads_stage_insert: bad argument");
+	}
+	const BuildLog lg{ a };
+	if (lg.ranged()) { // (the filter is the one the caller adopted in the PRIMARY slot)
+	} else if (a->counts) {
+		if (ntedit_hip_filter_alloc_counting(ctx, NTEDIT_FILTER_PRIMARY, r->bf_bytes, a->hash_num, a->k) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
+	} else if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, r->bf_bytes, a->hash_num, a->k) != 0) {
+		return pfail(ctx, NTEDIT_E_DEVICE, ntedit_hip_last_error(ctx));
+	}
+	lg.rank_info("Pass 2: inserting k-mers seen at least " + std::to_string(r->cmin) + " times");
+	const int rc = build_pass(ctx, a, NTEDIT_READS_PASS_SOLID, r, nullptr, nullptr);
+	ntedit_hip_sketch_free(ctx); // (the store with it)
+	return rc;
+}
+
+int
 ntedit_hip_reads_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r)
 {
-	if (!ctx || !a || !r || (a->n_files && !a->files) || a->batch_bytes < 4096 || (!a->solid && (a->cmin < 1 || a->cmin > 255)) ||
-	    (a->bf_bytes == 0 && !a->solid && !a->hist_path)) {
-		return pfail(ctx, NTEDIT_E_ARG, "reads_build: bad argument");
-	}
-	*r = ntedit_hip_reads_build_result();
 	const auto t0 = std::chrono::steady_clock::now();
-	const int rc = build(ctx, a, r);
-	ntedit_hip_sketch_free(ctx); // (the store with it)
-	r->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	uint64_t occ[256], nonzero = 0, counters = 0;
+	const bool hist = a && (a->solid || a->hist_path);
+	int rc = ntedit_hip_reads_stage_count(ctx, a, r, nullptr, nullptr);
+	if (rc == 0 && ntedit_hip_sketch_occupancy(ctx, &nonzero, &counters) != 0) {
+		rc = NTEDIT_E_DEVICE;
+	}
+	if (rc == 0) {
+		std::ostringstream o;
+		o << "Sketch occupancy: " << nonzero << " / " << counters << " counters (" << (double)nonzero / (double)counters << ")";
+		BuildLog{ a }.out(o.str());
+		if (a->sketch_path && ntedit_hip_sketch_save_file(ctx, a->sketch_path) != 0) {
+			rc = NTEDIT_E_IO;
+		}
+	}
+	if (rc == 0 && hist) {
+		rc = ntedit_hip_reads_stage_histogram(ctx, a, r, occ);
+	}
+	if (rc == 0 && (rc = ntedit_hip_reads_stage_decide(a, hist ? occ : nullptr, r)) != 0) {
+		pfail(ctx, rc, ntedit_hip_reads_last_error(nullptr)); // (the message of a call without a context, to the context's)
+	}
+	if (rc == 0) {
+		rc = ntedit_hip_reads_stage_insert(ctx, a, r);
+	}
+	if (ctx) {
+		ntedit_hip_sketch_free(ctx); // (the store with it)
+	}
+	if (r) {
+		r->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	}
 	return rc;
 }
 

@@ -28,12 +28,9 @@ from . import _lib
 from . import dist as ndist
 
 WHOLE = (1 << 64) - 1  # `end` of a unit that is a whole file
-GZIP_WEIGHT = 4  # a gzip byte weighs as much as 4 plain ones (the binary's default sketch counts it so)
 ROUND_BYTES = 256 << 20  # exchange rounds: at most this many bytes per peer and round, whatever the array size
-BATCH_DEFAULT = 256 << 20
-RESIDENT_CAP_DEFAULT = 48 << 30  # the resident store's cap of `ntedit --reads` (128 Gbases at 3 bits per base)
-PASS_NAMES = {_lib.READS_PASS_COUNT: "1 (count)", _lib.READS_PASS_HIST: "H (histogram)",
-              _lib.READS_PASS_SOLID: "2 (solid k-mers)"}
+BATCH_DEFAULT = _lib.READS_BATCH_DEFAULT
+RESIDENT_CAP_DEFAULT = _lib.READS_RESIDENT_CAP_DEFAULT  # the resident store's cap of `ntedit --reads`
 
 USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] "
          "[--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [-o VAR] [-t VAR] "
@@ -53,17 +50,33 @@ def _is_option(a):
     return len(a) > 1 and a[0] == "-" and not a[1].isdigit()
 
 
-def _u64(name, v):
-    if not v or not v.isdigit():
-        raise Refused("%s: not a number: '%s'" % (name, v))
-    return int(v)
+def check_options(dialect, given, final, reads=(), solid=False, hist=""):
+    """The library's reads-option rules (ntedit_hip_reads_options_check) over the option texts given so far (name ->
+    text).  final: every rule, and the argument dict of build_rank; else only what is refused at the option itself.
+    Refused with the library's message; the tool's "would be empty" is kept in the dict for sizes() to refuse."""
+    lib = _lib.load()
+    files = (ctypes.c_char_p * max(1, len(reads)))(*[os.fsencode(f) for f in reads])
+    o = _lib.ReadsOptions(solid=solid, hist=bool(hist), files=files, n_files=len(reads),
+                          **{name: os.fsencode(text) for name, text in given.items()})
+    r = _lib.ReadsRules()
+    rc = lib.ntedit_hip_reads_options_check(o, dialect, int(final), r)
+    why = os.fsdecode(lib.ntedit_hip_reads_last_error(None)) if rc else None
+    if rc not in (0, _lib.READS_EMPTY):
+        raise Refused(why)
+    return dict(reads=list(reads), k=r.k, cmin=r.cmin if "cutoff" in given else None, solid=solid, hist=hist,
+                hashes=r.hash_num, fpr=r.fpr, bf=r.bf_bytes if "bf" in given else None,
+                num_elements=r.num_elements if "num_elements" in given else None, sketch_bytes=r.sketch_bytes,
+                batch_bytes=r.batch_bytes, store_cap=r.store_cap, threads=r.threads, gather_hist=bool(r.gather_hist),
+                size_from_hist=bool(r.size_from_hist), bf_bytes=r.bf_bytes, sketch=r.sketch_counters, empty=why)
 
 
 def parse(argv):
-    """ntedit-make-reads-bf's argument rules and messages (host/make_reads_bf.cpp), checked in the same order"""
-    a = dict(reads=[], k=None, cmin=None, solid=False, hist="", counts=False, hashes=3, fpr=0.01, bf=None,
-             num_elements=None, sketch_bytes=0, out="", threads=12, batch_bytes=BATCH_DEFAULT, no_split=False,
-             backend=None, help=False)
+    """ntedit-make-reads-bf's arguments, walked as it walks them (host/make_reads_bf.cpp); the rules are the library's"""
+    texts = {"-k": "k", "-c": "cutoff", "--hashes": "hashes", "--fpr": "fpr", "--bf": "bf",
+             "--num_elements": "num_elements", "--sketch_bytes": "sketch_bytes", "-t": "threads",
+             "--batch_bytes": "batch_bytes"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
+    own = dict(counts=False, out="", no_split=False, backend=None, help=False)
+    given, reads, solid, hist = {}, [], False, ""
     i = 0
     while i < len(argv):
         x = argv[i]
@@ -76,91 +89,42 @@ def parse(argv):
             return argv[i]
 
         if x in ("-h", "--help"):
-            a["help"] = True
-            return a
+            return dict(own, help=True)
         elif x == "--reads":
             while i + 1 < len(argv) and not _is_option(argv[i + 1]):
                 i += 1
-                a["reads"].append(argv[i])
-        elif x == "-k":
-            a["k"] = _u64("-k", value("-k"))
-        elif x == "-c":
-            a["cmin"] = _u64("-c", value("-c"))
+                reads.append(argv[i])
+        elif x in texts:
+            given[texts[x]] = value(x)
+            check_options(_lib.READS_DIALECT_TOOL, given, False)
         elif x == "--solid":
-            a["solid"] = True
+            solid = True
         elif x == "--hist":
-            a["hist"] = value("--hist")
+            hist = value("--hist")
         elif x == "--counts":
-            a["counts"] = True
-        elif x == "--hashes":
-            a["hashes"] = _u64("--hashes", value("--hashes"))
-        elif x == "--fpr":
-            v = value("--fpr")
-            try:
-                a["fpr"] = float(v)
-            except ValueError:
-                a["fpr"] = float("nan")
-            if not (0.0 < a["fpr"] < 1.0):
-                raise Refused("--fpr: needs a number between 0 and 1: '%s'" % v)
-        elif x == "--bf":
-            a["bf"] = _u64("--bf", value("--bf"))
-        elif x == "--num_elements":
-            a["num_elements"] = _u64("--num_elements", value("--num_elements"))
-        elif x == "--sketch_bytes":
-            a["sketch_bytes"] = _u64("--sketch_bytes", value("--sketch_bytes"))
-        elif x == "--batch_bytes":  # (not in the usage text: tests force many small batches with it)
-            a["batch_bytes"] = _u64("--batch_bytes", value("--batch_bytes"))
+            own["counts"] = True
         elif x == "-o":
-            a["out"] = value("-o")
-        elif x == "-t":
-            a["threads"] = _u64("-t", value("-t"))
+            own["out"] = value("-o")
         elif x == "--no-split":
-            a["no_split"] = True
+            own["no_split"] = True
         elif x == "--backend":
-            a["backend"] = value("--backend")
+            own["backend"] = value("--backend")
         else:
             raise Refused("Unknown argument: " + x)
         i += 1
-    if not a["reads"]:
+    if not reads:
         raise Refused("--reads: 1 or more argument(s) expected. 0 provided.")
-    if a["k"] is None:
-        raise Refused("-k: required.")
-    if not 12 <= a["k"] <= 200:
-        raise Refused("-k %d: k must be between 12 and 200." % a["k"])
-    if a["solid"] and a["cmin"] is not None:
-        raise Refused("--solid and -c: give one of them (--solid takes the minimum count from the k-mer histogram).")
-    if a["cmin"] is None and not a["solid"]:
-        raise Refused("-c: required (or --solid).")
-    if a["cmin"] is not None and not 1 <= a["cmin"] <= 255:
-        raise Refused("-c %d: the minimum count must be between 1 and 255." % a["cmin"])
-    if not 1 <= a["hashes"] <= 8:
-        raise Refused("--hashes %d: the number of hash functions must be between 1 and 8." % a["hashes"])
-    a["gather_hist"] = a["solid"] or bool(a["hist"])
-    a["size_from_hist"] = a["bf"] is None and a["num_elements"] is None
-    if a["size_from_hist"] and not a["gather_hist"]:
-        raise Refused("--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter "
-                      "from the k-mer histogram).")
-    if a["batch_bytes"] < 4096:
-        raise Refused("--batch_bytes: at least 4096.")
+    a = dict(check_options(_lib.READS_DIALECT_TOOL, given, True, reads, solid, hist), **own)
     if not a["out"]:
         a["out"] = "reads_k%d.bf" % a["k"]
     return a
 
 
 def sizes(lib, a):
-    """(output bytes or 0 when the histogram sizes it, sketch counters): the binary's sizing, through its own calls"""
-    bf = 0
-    if a["bf"] is not None:
-        bf = a["bf"]
-    elif a["num_elements"] is not None:
-        bf = lib.ntedit_hip_reads_bf_size(a["num_elements"], a["hashes"], a["fpr"])
-    if not a["size_from_hist"] and bf == 0:
-        raise Refused("The output filter would be empty (--bf 0 or --num_elements too small).")
-    sketch = a["sketch_bytes"]
-    if sketch == 0:
-        files = (ctypes.c_char_p * len(a["reads"]))(*[f.encode() for f in a["reads"]])
-        sketch = lib.ntedit_hip_reads_default_sketch(files, len(a["reads"]), 0 if a["size_from_hist"] else bf)
-    return bf, sketch
+    """(output bytes or 0 when the histogram sizes it, sketch counters): the binary's sizing, as the rules gave it"""
+    if a["empty"]:
+        raise Refused(a["empty"])
+    return a["bf_bytes"], a["sketch"]
 
 
 # ---------------------------------------------------------------------------------- partition
@@ -196,7 +160,7 @@ def file_facts(lib, paths):
 def plan(paths, facts, world, split=True):
     """The same units on every rank, from the file facts alone: gzip files whole, plain files cut into ranges of about a
     quarter of a rank's share; then owner[u] for every unit, longest first (dist.lpt_assign).  -> (units, owner)"""
-    weights = [n * (GZIP_WEIGHT if gz else 1) for n, gz in facts]
+    weights = [n * (_lib.READS_GZIP_WEIGHT if gz else 1) for n, gz in facts]
     target = max(1, -(-sum(weights) // (4 * world)))
     units = []
     for i, (p, (n, gz)) in enumerate(zip(paths, facts)):
@@ -231,47 +195,17 @@ def log_info(msg):
 
 
 class Builder:
-    """one rank's state: the context it builds in (a Polisher's, owned by the caller), the process group, and what the
-    build measured (passes, exchanges)"""
+    """one rank's state: the context it builds in (a Polisher's, owned by the caller), the process group, and what its
+    exchanges measured"""
 
     def __init__(self, a, rank, world, pol, group, name="make_reads"):
         self.a, self.rank, self.world, self.group, self.name = a, rank, world, group, name
         self.lib, self.h = pol._lib, pol._h
         self.xbytes, self.xsec = 0, 0.0
-        self.passes, self.exchanges = {}, []
+        self.exchanges = []
 
     def fail(self, what):
         raise RuntimeError("%s: %s: %s" % (self.name, what, self.lib.ntedit_hip_reads_last_error(self.h).decode()))
-
-    def run_pass(self, which, units, cmin=0):
-        n = len(units)
-        files = (ctypes.c_char_p * max(n, 1))(*[u.path.encode() for u in units])
-        begins = (ctypes.c_uint64 * max(n, 1))(*[u.begin for u in units])
-        ends = (ctypes.c_uint64 * max(n, 1))(*[u.end for u in units])
-        starts = (ctypes.c_uint64 * max(n, 1))()
-        nexts = (ctypes.c_uint64 * max(n, 1))()
-        st = _lib.ReadsPassStats()
-        if self.lib.ntedit_hip_reads_pass(self.h, which, files, begins, ends, n, self.a["batch_bytes"], cmin,
-                                          ctypes.byref(st), starts, nexts) != 0:
-            self.fail("pass " + PASS_NAMES[which])
-        self._log_pass(which, st.bases, st.ms_wall, st.ms_gpu, "%d ranges" % n)
-        return [(u.file, u.begin, starts[i], nexts[i]) for i, u in enumerate(units)]
-
-    def store_pass(self, which, bases, batches, slot=0, cmin=0):
-        """the histogram pass or pass 2 over the resident store (bases: pass 1's, which the store holds)"""
-        t0 = time.perf_counter()
-        rc = (self.lib.ntedit_hip_resident_histogram(self.h) if which == _lib.READS_PASS_HIST
-              else self.lib.ntedit_hip_resident_insert_solid(self.h, slot, cmin))
-        if rc != 0:
-            self.fail("pass " + PASS_NAMES[which])
-        ms = (time.perf_counter() - t0) * 1e3
-        self._log_pass(which, bases, ms, ms, "%d batches of the resident store" % batches)
-
-    def _log_pass(self, which, bases, ms, g, what):
-        self.passes[PASS_NAMES[which][0]] = dict(bases=bases, ms=round(ms, 3), gpu_ms=round(g, 3))
-        log_info("rank %d/%d: Pass %s: %d bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s), %s"
-                 % (self.rank, self.world, PASS_NAMES[which], bases, ms, bases / ms / 1e6 if ms > 0 else 0.0, g,
-                    bases / g / 1e6 if g > 0 else 0.0, what))
 
     # ------------------------------------------------------------------ collectives (gloo: through host memory)
     def _gloo(self):
@@ -357,18 +291,21 @@ class Builder:
         return -(-nbytes // q) * q
 
 
-STORE_STATES = {_lib.RESIDENT_OFF: "off", _lib.RESIDENT_ON: "on", _lib.RESIDENT_OVER_CAP: "over cap",
-                _lib.RESIDENT_NO_MEMORY: "no memory"}
+@_lib.READS_LOG_FN
+def _log_line(user, to_stdout, line):
+    """the stages' console lines (a sharded build keeps its standard output for its results)"""
+    log_info(line.decode())
 
 
 def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RESIDENT_CAP_DEFAULT, name="make_reads"):
-    """One rank's share of the reads filter build, the same for every driver: the plan, pass 1 over this rank's units
-    into an adopted sketch, the cut-point check, the sketch merge, with --solid / --hist the histogram pass (rank 0
-    writes --hist), pass 2 into an adopted filter in `slot` of pol's context, the filter merge.  On return every rank
-    holds the whole filter there and the sketch is freed.  With use_store the reads of pass 1 stay resident in HBM
-    (ntedit_hip_resident_begin, up to store_cap bytes) and the later passes read the store; a rank whose store was
-    released reads its ranges again, with the same result.  ntedit_hip_reads_pass fills the PRIMARY slot, so that is
-    the only slot a build can fill.
+    """One rank's share of the reads filter build, the same for every driver: the stages of ntedit_hip_reads_build with
+    the merges in between.  The plan, the count stage over this rank's units into an adopted sketch, the cut-point
+    check, the sketch merge, with --solid / --hist the histogram stage and the sum of the ranks' bins, the decide stage
+    (rank 0 writes --hist), the insert stage into an adopted filter in `slot` of pol's context, the filter merge.  On
+    return every rank holds the whole filter there and the sketch is freed.  With use_store the reads of pass 1 stay
+    resident in HBM (up to store_cap bytes) and the later passes read the store; a rank whose store was released
+    reads its ranges again, with the same result.  The stages fill the PRIMARY slot, so that is the only slot a build
+    can fill.
     -> (the filter tensor, which the caller keeps alive while the slot is in use, a report dict)"""
     import torch
     if slot != 0:
@@ -384,7 +321,16 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
                  (world, len(units), len(a["reads"]), sketch,
                   "output from the k-mer histogram" if a["size_from_hist"] else "output %d bytes" % bf))
     b = Builder(a, rank, world, pol, group, name)
-    rep = dict(units=len(mine), store=dict(used=False, state="not asked", batches=0, bytes=0, fallback=False))
+    n = len(mine)
+    u64s = ctypes.c_uint64 * max(n, 1)
+    starts, nexts = u64s(), u64s()
+    args = _lib.ReadsBuildArgs(
+        files=(ctypes.c_char_p * max(n, 1))(*[u.path.encode() for u in mine]), n_files=n,
+        begins=u64s(*[u.begin for u in mine]), ends=u64s(*[u.end for u in mine]), rank=rank, world=world, k=a["k"],
+        hash_num=a["hashes"], cmin=a["cmin"] or 0, solid=a["solid"], counts=a["counts"], bf_bytes=bf, fpr=a["fpr"],
+        batch_bytes=a["batch_bytes"], hist_path=a["hist"].encode() or None, use_store=use_store, store_cap=store_cap,
+        log=_log_line)
+    res = _lib.ReadsBuildResult()
     try:
         k, hashes = a["k"], a["hashes"]
         counters = (sketch + 7) // 8 * 8
@@ -392,26 +338,9 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         torch.cuda.synchronize()
         if lib.ntedit_hip_sketch_set_device(b.h, sk.data_ptr(), counters, hashes, k) != 0:
             b.fail("sketch")
-        if use_store and lib.ntedit_hip_resident_begin(b.h, store_cap) != 0:
-            b.fail("resident store")
-        cut = b.run_pass(_lib.READS_PASS_COUNT, mine)
-        from_store, batches = False, 0
-        if use_store:
-            st = _lib.ResidentStats()
-            if lib.ntedit_hip_resident_info(b.h, ctypes.byref(st)) != 0:
-                b.fail("resident store")
-            from_store, batches = st.state == _lib.RESIDENT_ON, st.batches
-            rep["store"] = dict(used=from_store, state=STORE_STATES.get(st.state, str(st.state)), batches=st.batches,
-                                bytes=st.bytes, fallback=not from_store)
-            later = "the histogram pass and pass 2" if a["gather_hist"] else "pass 2"
-            if from_store:
-                log_info("rank %d/%d: Resident store: %d batches, %d bytes of HBM (3 bits per base); %s read it"
-                         % (rank, world, st.batches, st.bytes, later))
-            else:
-                log_info("rank %d/%d: Resident store: released (%s); %s read this rank's ranges again"
-                         % (rank, world, "the reads would pass its cap of %d bytes" % st.cap
-                            if st.state == _lib.RESIDENT_OVER_CAP else "a device allocation failed", later))
-        bases = b.passes["1"]["bases"]
+        if lib.ntedit_hip_reads_stage_count(b.h, args, res, starts, nexts) != 0:
+            b.fail("pass 1 (count)")
+        cut = [(u.file, u.begin, starts[i], nexts[i]) for i, u in enumerate(mine)]
         brk = check_cuts([c for part in b.all_gather_object(cut) for c in part])
         if brk is not None:
             f, b0, b1, nxt, start = brk
@@ -420,57 +349,33 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
                           "--no-split, which reads every file whole.  No output was written."
                           % (a["reads"][f], b0, b1, "(a failed record)" if nxt == WHOLE else nxt, start))
         b.merge(sk, _lib.MERGE_SAT_ADD)
-        cmin = a["cmin"] or 0
+        occ = None
         if a["gather_hist"]:
-            if from_store:
-                b.store_pass(_lib.READS_PASS_HIST, bases, batches)
-            else:
-                b.run_pass(_lib.READS_PASS_HIST, mine)
             occ = np.zeros(256, dtype=np.uint64)
-            if lib.ntedit_hip_sketch_histogram_download(b.h, occ.ctypes.data_as(ctypes.c_void_p)) != 0:
-                b.fail("histogram")
+            if lib.ntedit_hip_reads_stage_histogram(b.h, args, res, occ.ctypes.data) != 0:
+                b.fail("pass H (histogram)")
             occ = b.all_reduce_hist(occ)
-            f = np.zeros(256, dtype=np.uint64)
-            F0, F1 = ctypes.c_uint64(), ctypes.c_uint64()
-            lib.ntedit_hip_reads_hist_summary(occ.ctypes.data_as(ctypes.c_void_p), f.ctypes.data_as(ctypes.c_void_p),
-                                              ctypes.byref(F0), ctypes.byref(F1))
-            if rank == 0:
-                log_info("k-mer histogram: F1 = %d (k-mers), F0 = %d (distinct k-mers)" % (F1.value, F0.value))
-                if a["hist"]:
-                    if lib.ntedit_hip_reads_write_hist(a["hist"].encode(), f.ctypes.data_as(ctypes.c_void_p), F0.value,
-                                                       F1.value) != 0:
-                        raise RuntimeError("cannot write " + a["hist"])
-                    log_info("Histogram written to " + a["hist"])
-            if a["solid"]:
-                c = ctypes.c_uint32()
-                if lib.ntedit_hip_reads_solid_cutoff(f.ctypes.data_as(ctypes.c_void_p), ctypes.byref(c)) != 0:
-                    raise Refused("--solid: the k-mer histogram has no valley after the error peak (no c with f[c+1] "
-                                  "> f[c]); pass -c")
-                cmin = c.value
-                if rank == 0:
-                    log_info("--solid: minimum k-mer count %d" % cmin)
-            if a["size_from_hist"]:
-                ne = int(f[cmin:].sum())
-                bf = lib.ntedit_hip_reads_bf_size(ne, hashes, a["fpr"])
-                if rank == 0:
-                    log_info("Sized from the k-mer histogram: --num_elements %d (k-mers at %d or above), %d bytes"
-                             % (ne, cmin, bf))
-                if bf == 0:
-                    raise Refused("The output filter would be empty (no k-mer at the minimum count or above).")
-        nbytes = (bf + 7) // 8 * 8
+        rc = lib.ntedit_hip_reads_stage_decide(args, None if occ is None else occ.ctypes.data, res)
+        if rc != 0:
+            why = lib.ntedit_hip_reads_last_error(None).decode()
+            raise Refused(why) if rc == _lib.E_ARG else RuntimeError(why)
+        nbytes = (res.bf_bytes + 7) // 8 * 8
         out = torch.zeros(b.padded(nbytes), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         pol.set_filter_device(out.data_ptr(), nbytes, hashes, k, slot=slot, counting=a["counts"])
-        if from_store:
-            b.store_pass(_lib.READS_PASS_SOLID, bases, batches, slot, cmin)
-        else:
-            b.run_pass(_lib.READS_PASS_SOLID, mine, cmin)
-        lib.ntedit_hip_sketch_free(b.h)  # (the store with it)
+        if lib.ntedit_hip_reads_stage_insert(b.h, args, res) != 0:  # (it frees the sketch, and the store with it)
+            b.fail("pass 2 (solid k-mers)")
         del sk
         b.merge(out, _lib.MERGE_MAX if a["counts"] else _lib.MERGE_OR)
     finally:
         lib.ntedit_hip_sketch_free(b.h)
-    rep.update(cmin=cmin, filter_bytes=nbytes, passes=b.passes, exchanges=b.exchanges, exchange_bytes=b.xbytes,
+    on = res.store_state == _lib.RESIDENT_ON
+    passes = {key: dict(bases=p.bases, ms=round(p.ms_wall, 3), gpu_ms=round(p.ms_gpu, 3))
+              for key, p in zip("1H2", res.passes) if key != "H" or a["gather_hist"]}
+    rep = dict(units=n, store=dict(used=on, state=("off", "on", "over cap", "no memory")[res.store_state] if use_store
+                                   else "not asked", batches=res.store_batches, bytes=res.store_bytes,
+                                   fallback=use_store and not on),
+               cmin=res.cmin, filter_bytes=nbytes, passes=passes, exchanges=b.exchanges, exchange_bytes=b.xbytes,
                exchange_ms=round(b.xsec * 1e3, 3))
     return out, rep
 
@@ -498,21 +403,20 @@ def build(a, lib, rank, world, local, group):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
+    # torch's HIP runtime first, as in ntedit_amd.run: the library then binds to the runtime torch brought in
+    # (loaded the other way round, the library's context cannot see the device in a torch.distributed.run child)
+    import torch
+    import torch.distributed as dist
     try:
         a = parse(argv)
         if a["help"]:
             sys.stderr.write(USAGE)
             return 0
-        # torch's HIP runtime first, as in ntedit_amd.run: the library then binds to the runtime torch brought in
-        # (loaded the other way round, the library's context cannot see the device in a torch.distributed.run child)
-        import torch  # noqa: F401  (no device is touched here)
         lib = _lib.load()
         sizes(lib, a)  # (the empty-output refusal comes before any device)
     except Refused as e:
         sys.stderr.write("%s\n%s" % (e, USAGE))
         return 1
-    import torch
-    import torch.distributed as dist
     if not torch.cuda.is_available():
         sys.stderr.write("make_reads: error: no HIP device (this build has no CPU path)\n")
         return 1
@@ -522,9 +426,7 @@ def main(argv=None):
     torch.cuda.set_device(local)
     group = None
     if world > 1 or "RANK" in os.environ or a["backend"]:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29517")
-        dist.init_process_group(backend=a["backend"] or "nccl", rank=rank, world_size=world)
+        ndist.init_process_group(a["backend"] or "nccl", port=29517, single=True)
         group = dist.group.WORLD
     try:
         return build(a, lib, rank, world, local, group)

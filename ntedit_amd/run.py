@@ -32,7 +32,8 @@ import time
 
 import numpy as np
 
-from . import dist as ndist
+from . import _lib, dist as ndist, make_reads
+from .make_reads import Refused, log_info
 from .polisher import Polisher, default_params, pack_batch
 
 
@@ -42,7 +43,6 @@ def read_fasta_fast(path, min_len=0, threads=0):
     ntedit.cpp:2223-2230 -- gzip / BGZF told apart by their magic bytes, FASTQ, CR line ends, NUL bytes, text in
     front of the first header).  Raises on an unreadable, corrupt or truncated file instead of returning a shorter
     draft."""
-    from . import _lib
     lib = _lib.load()
     h = ctypes.c_void_p()
     err = ctypes.create_string_buffer(512)
@@ -113,7 +113,6 @@ class Draft:
     library; nothing changes for the caller."""
 
     def __init__(self, path, min_len=0, threads=0):
-        from . import _lib
         self._lib = _lib.load()
         self._h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)
@@ -220,22 +219,11 @@ class HipBackend:
         return bad, sizes
 
 
-class Refused(Exception):
-    pass
-
-
 # the reads options of `ntedit --reads` (+ make_reads' --no-split): (flag, dest), in the order a refusal names them
 READS_OPTIONS = [("--cutoff", "cutoff"), ("--solid", "solid"), ("--counts", "counts"), ("--hashes", "hashes"),
                  ("--fpr", "fpr"), ("--bf", "bf_bytes"), ("--num_elements", "num_elements"),
                  ("--sketch_bytes", "sketch_bytes"), ("--hist", "hist"), ("--save_bf", "save_bf"),
                  ("--batch_bytes", "batch_bytes"), ("--resident_cap", "resident_cap"), ("--no-split", "no_split")]
-
-
-def _count(name, v):
-    """a whole non-negative decimal number (ntedit's parse_count)"""
-    if not v or not v.isdigit():
-        raise Refused("invalid option: `%s %s'" % (name, v))
-    return int(v)
 
 
 def parse(argv=None):
@@ -296,56 +284,18 @@ def parse(argv=None):
 
 
 def reads_args(args):
-    """the refusals of `ntedit --reads` (host/main.cpp), in its order, before any device or file is touched; -> the
-    argument dict of ntedit_amd.make_reads.build_rank"""
-    from . import _lib
-    from .make_reads import BATCH_DEFAULT, RESIDENT_CAP_DEFAULT
+    """the refusals of `ntedit --reads` (host/main.cpp), in its order, before any device or file is touched: what only a
+    front end has here, the rules of the options in the library; -> the argument dict of make_reads.build_rank"""
     if args.bf is not None:
         raise Refused("--reads and -r: give one of them (--reads builds the filter that -r would load)")
     if not args.reads:
         raise Refused("--reads: 1 or more files expected")
-    if args.k_ignored is None:
-        raise Refused("-k: required with --reads")
-    k = args.k_ignored
-    if not k.isdigit() or not 12 <= int(k) <= 200:
-        raise Refused("-k %s: k must be between 12 and 200" % k)
-    a = dict(reads=list(args.reads), k=int(k), cmin=None, solid=args.solid, hist=args.hist or "", counts=args.counts,
-             hashes=3, fpr=0.01, bf=None, num_elements=None, sketch_bytes=0, batch_bytes=BATCH_DEFAULT,
-             no_split=args.no_split, store_cap=RESIDENT_CAP_DEFAULT)
-    if args.cutoff is not None:
-        a["cmin"] = _count("--cutoff", args.cutoff)
-    if args.hashes is not None:
-        a["hashes"] = _count("--hashes", args.hashes)
-    if args.fpr is not None:
-        try:
-            a["fpr"] = float(args.fpr)
-        except ValueError:
-            a["fpr"] = float("nan")
-        if not (0.0 < a["fpr"] < 1.0):
-            raise Refused("--fpr %s: needs a number between 0 and 1" % args.fpr)
-    for flag, key, dest in (("--bf", "bf", "bf_bytes"), ("--num_elements", "num_elements", "num_elements"),
-                            ("--sketch_bytes", "sketch_bytes", "sketch_bytes"),
-                            ("--batch_bytes", "batch_bytes", "batch_bytes"), ("--resident_cap", "store_cap", "resident_cap")):
-        if getattr(args, dest) is not None:
-            a[key] = _count(flag, getattr(args, dest))
-    if a["cmin"] is not None and a["solid"]:
-        raise Refused("--cutoff and --solid: give one of them (--solid takes the minimum count from the k-mer histogram)")
-    if a["cmin"] is None and not a["solid"]:
-        raise Refused("--cutoff or --solid: one of them is required with --reads")
-    if a["cmin"] is not None and not 1 <= a["cmin"] <= 255:
-        raise Refused("--cutoff %d: the minimum count must be between 1 and 255" % a["cmin"])
-    if not 1 <= a["hashes"] <= 8:
-        raise Refused("--hashes %d: the number of hash functions must be between 1 and 8" % a["hashes"])
-    a["gather_hist"] = a["solid"] or bool(a["hist"])
-    a["size_from_hist"] = a["bf"] is None and a["num_elements"] is None
-    if a["size_from_hist"] and not a["gather_hist"]:
-        raise Refused("--bf or --num_elements: one of them is required (or --solid / --hist, which size the filter from "
-                      "the k-mer histogram)")
-    if (a["bf"] == 0 or (a["bf"] is None and a["num_elements"] is not None and
-                         _lib.load().ntedit_hip_reads_bf_size(a["num_elements"], a["hashes"], a["fpr"]) == 0)):
-        raise Refused("--bf / --num_elements: the filter would be empty")
-    if a["batch_bytes"] < 4096:
-        raise Refused("--batch_bytes: at least 4096")
+    given = {name: getattr(args, dest) for name, dest in
+             (("k", "k_ignored"), ("cutoff", "cutoff"), ("hashes", "hashes"), ("fpr", "fpr"), ("bf", "bf_bytes"),
+              ("num_elements", "num_elements"), ("sketch_bytes", "sketch_bytes"), ("batch_bytes", "batch_bytes"),
+              ("store_cap", "resident_cap")) if getattr(args, dest) is not None}
+    a = make_reads.check_options(_lib.READS_DIALECT_POLISHER, given, True, args.reads, args.solid, args.hist or "")
+    a.update(counts=args.counts, no_split=args.no_split)
     for path in [args.draft] + a["reads"]:
         try:
             open(path, "rb").close()
@@ -361,24 +311,22 @@ def build_from_reads(pol, args, rank, world):
     reserves its buffers.  -> the report of the build, or None after a refusal (on every rank alike)"""
     import torch
     import torch.distributed as dist
-    from . import make_reads
     a = args.reads_args
     group = dist.group.WORLD if dist.is_initialized() else None
     try:
         buf, rep = make_reads.build_rank(pol, a, rank, world, group, slot=0, use_store=True, store_cap=a["store_cap"],
                                          name="run")
-    except make_reads.Refused as e:
+    except Refused as e:
         sys.stderr.write("python -m ntedit_amd.run: error: %s\n" % e)
         return None
     ndist._keep(pol, 0, buf)
     torch.cuda.empty_cache()
     if rank == 0:
-        make_reads.log_info("rank 0: filter (%d bytes) built from the reads in HBM, minimum count %d; exchanges %d "
-                            "bytes sent in %.1f ms" % (rep["filter_bytes"], rep["cmin"], rep["exchange_bytes"],
-                                                       rep["exchange_ms"]))
+        log_info("rank 0: filter (%d bytes) built from the reads in HBM, minimum count %d; exchanges %d bytes sent in "
+                 "%.1f ms" % (rep["filter_bytes"], rep["cmin"], rep["exchange_bytes"], rep["exchange_ms"]))
         if args.save_bf:
             pol.filter_save_file(args.save_bf, 0)
-            make_reads.log_info("Bloom filter saved to " + args.save_bf)
+            log_info("Bloom filter saved to " + args.save_bf)
     return rep
 
 
@@ -400,13 +348,9 @@ def main(argv=None):
         # so the N > 1 path of this driver can be run on a one-GPU box; its timings then say nothing about N GPUs)
         local = local % torch.cuda.device_count()
     torch.cuda.set_device(local)
-    if world > 1:
-        ndist.init_process_group(args.backend or "nccl")
-    elif args.backend:
-        # a one-rank group still exercises the collective path (the round-end GPU test does this)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29513")
-        dist.init_process_group(backend=args.backend, rank=0, world_size=1)
+    if world > 1 or args.backend:
+        # (a one-rank group still exercises the collective path: the round-end GPU test does this)
+        ndist.init_process_group(args.backend or "nccl", port=29511 if world > 1 else 29513, single=True)
     pol = Polisher(local)
     pol._lib.ntedit_hip_bind_near_device(local)  # host threads and buffers on the socket this rank's GPU hangs off
     t0 = time.perf_counter()
