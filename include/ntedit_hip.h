@@ -296,6 +296,7 @@ typedef struct ntedit_hip_reads_build_args
 	const uint64_t* begins;   /* NULL: the files whole, one process; else a rank's share of a sharded build */
 	const uint64_t* ends;
 	uint32_t rank, world;
+	int device_parse;         /* --gpu_parse: plain files are parsed on the device (ntedit_hip_reads_parse_device) */
 } ntedit_hip_reads_build_args;
 typedef struct ntedit_hip_reads_build_result
 {
@@ -337,6 +338,7 @@ typedef struct ntedit_hip_reads_options
 	int solid, hist;
 	const char* const* files; /* for the default sketch */
 	uint32_t n_files;
+	int gpu_parse;
 } ntedit_hip_reads_options;
 typedef struct ntedit_hip_reads_rules
 {
@@ -348,8 +350,63 @@ typedef struct ntedit_hip_reads_rules
 	uint64_t sketch_counters;   /* the sketch to allocate */
 	uint64_t batch_bytes, store_cap, threads;
 	int gather_hist, size_from_hist;
+	int gpu_parse;
 } ntedit_hip_reads_rules;
 int ntedit_hip_reads_options_check(const ntedit_hip_reads_options* opts, int dialect, int final, ntedit_hip_reads_rules* out);
+/* --gpu_parse: plain (not gzip) read files parsed on the device.  The host ships raw file bytes, cut at record starts
+ * into chunks of about batch_bytes; kernels (nte_reads_parse.hip) make of each chunk, in HBM, exactly the batch text the
+ * host parser makes -- every read of k bases or more followed by '\n', in file order -- and that text goes to the passes
+ * as a device batch.  A parallel parser cannot follow kseq's rules on arbitrary input, so it verifies a clean grammar
+ * (nte_reads_grammar.h: no '\r', no empty line; FASTA: '>' lines are headers, every other line is sequence and starts
+ * with none of '>', '+', '@'; FASTQ: 4 lines per record, '@', sequence, '+', a quality line as long as the sequence) and
+ * reports a chunk that breaks it unclean; from the first unclean chunk of a range on, the rest of that range goes to the
+ * host parser, from that chunk's first byte.  A clean chunk has exactly the host parser's text, so no output changes.
+ *   ntedit_hip_reads_parse_device: one chunk.  raw: n_raw host or device bytes (device: 16-byte aligned) that start at
+ *           a record start; text_device: 16-byte aligned device memory of text_cap >= n_raw bytes (the text is never
+ *           longer than the raw bytes).  res->clean = 1 and the text's length, reads and bases, or clean = 0 and
+ *           `broken`, the rules found broken (NTEDIT_PARSE_BAD_*; the device stops at what it finds first, so on an
+ *           unclean chunk it may name fewer rules than the model), the text then undefined.  At most 2^31 - 1 bytes and
+ *           one line per 8 raw bytes (+ 1), else unclean.  Scratch is the context's, grows only, and is released by
+ *           ntedit_hip_sketch_free.
+ *   ntedit_hip_reads_parse_model: the same grammar functions run serially on the host (no device; failures through
+ *           ntedit_hip_reads_last_error(NULL)): the text into out[0 .. cap), NTEDIT_E_OVERFLOW when it does not fit.
+ *   ntedit_hip_reads_set_device_parse: the context's setting that ntedit_hip_reads_pass follows (the stage calls set it
+ *           from args->device_parse); gzip files stay with the host parser either way.
+ *   ntedit_hip_reads_parse_info: the last pass of the context: chunks parsed on the device, chunks handed to the host
+ *           parser after an unclean one, the raw bytes shipped, the text bytes made, milliseconds in the parse kernels. */
+#define NTEDIT_PARSE_TILE 16384
+#define NTEDIT_PARSE_BAD_FIRST 1
+#define NTEDIT_PARSE_BAD_CR 2
+#define NTEDIT_PARSE_BAD_EMPTY 4
+#define NTEDIT_PARSE_BAD_SEQ_START 8
+#define NTEDIT_PARSE_BAD_FQ_LINES 16
+#define NTEDIT_PARSE_BAD_FQ_HEADER 32
+#define NTEDIT_PARSE_BAD_FQ_PLUS 64
+#define NTEDIT_PARSE_BAD_FQ_QUAL 128
+#define NTEDIT_PARSE_BAD_TABLE 256
+#define NTEDIT_PARSE_BAD_SIZE 512
+typedef struct ntedit_hip_reads_parse_result
+{
+	int clean;        /* 1: in the clean grammar, the text is the host parser's; 0: not */
+	uint32_t broken;  /* 0 when clean */
+	int kind;         /* the chunk's first byte */
+	uint64_t text_len, reads, bases, lines;
+} ntedit_hip_reads_parse_result;
+typedef struct ntedit_hip_reads_parse_stats
+{
+	uint64_t device_chunks;   /* clean chunks, parsed on the device */
+	uint64_t fallback_chunks; /* unclean chunks: each sends the rest of its range to the host parser */
+	uint64_t raw_bytes;       /* shipped to the device */
+	uint64_t text_bytes;      /* made there */
+	double ms_kernels;
+	uint32_t broken;          /* the rules the unclean chunks broke */
+	uint32_t host_files;      /* gzip ranges, left to the host parser */
+} ntedit_hip_reads_parse_stats;
+int ntedit_hip_reads_parse_device(ntedit_hip_ctx* ctx, const char* raw, uint64_t n_raw, int on_device, uint32_t k, char* text_device,
+                                  uint64_t text_cap, ntedit_hip_reads_parse_result* res);
+int ntedit_hip_reads_parse_model(const char* raw, uint64_t n_raw, uint32_t k, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res);
+int ntedit_hip_reads_set_device_parse(ntedit_hip_ctx* ctx, int on);
+int ntedit_hip_reads_parse_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_parse_stats* st);
 
 
 /* ---- hot path ------------------------------------------------------------

@@ -89,7 +89,8 @@ class ReadsBuildArgs(ctypes.Structure):
                 ("sketch_counters", ctypes.c_uint64), ("batch_bytes", ctypes.c_uint64), ("hist_path", ctypes.c_char_p),
                 ("sketch_path", ctypes.c_char_p), ("use_store", ctypes.c_int), ("store_cap", ctypes.c_uint64),
                 ("log", READS_LOG_FN), ("user", ctypes.c_void_p), ("begins", ctypes.POINTER(ctypes.c_uint64)),
-                ("ends", ctypes.POINTER(ctypes.c_uint64)), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32)]
+                ("ends", ctypes.POINTER(ctypes.c_uint64)), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32),
+                ("device_parse", ctypes.c_int)]
 
 
 class ReadsBuildResult(ctypes.Structure):
@@ -111,7 +112,7 @@ class ReadsOptions(ctypes.Structure):
     """ntedit_hip_reads_options"""
     _fields_ = ([(name, ctypes.c_char_p) for name in READS_OPTION_TEXTS] +
                 [("solid", ctypes.c_int), ("hist", ctypes.c_int), ("files", ctypes.POINTER(ctypes.c_char_p)),
-                 ("n_files", ctypes.c_uint32)])
+                 ("n_files", ctypes.c_uint32), ("gpu_parse", ctypes.c_int)])
 
 
 class ReadsRules(ctypes.Structure):
@@ -120,7 +121,27 @@ class ReadsRules(ctypes.Structure):
                 ("fpr", ctypes.c_double), ("bf_bytes", ctypes.c_uint64), ("num_elements", ctypes.c_uint64),
                 ("sketch_bytes", ctypes.c_uint64), ("sketch_counters", ctypes.c_uint64),
                 ("batch_bytes", ctypes.c_uint64), ("store_cap", ctypes.c_uint64), ("threads", ctypes.c_uint64),
-                ("gather_hist", ctypes.c_int), ("size_from_hist", ctypes.c_int)]
+                ("gather_hist", ctypes.c_int), ("size_from_hist", ctypes.c_int), ("gpu_parse", ctypes.c_int)]
+
+
+# --gpu_parse (ntedit_hip_reads_parse_device / _model): the tile size and the rules of the clean grammar
+PARSE_TILE = 16384
+PARSE_BAD = dict(first=1, cr=2, empty=4, seq_start=8, fq_lines=16, fq_header=32, fq_plus=64, fq_qual=128, table=256,
+                 size=512)
+
+
+class ReadsParseResult(ctypes.Structure):
+    """ntedit_hip_reads_parse_result"""
+    _fields_ = [("clean", ctypes.c_int), ("broken", ctypes.c_uint32), ("kind", ctypes.c_int),
+                ("text_len", ctypes.c_uint64), ("reads", ctypes.c_uint64), ("bases", ctypes.c_uint64),
+                ("lines", ctypes.c_uint64)]
+
+
+class ReadsParseStats(ctypes.Structure):
+    """ntedit_hip_reads_parse_stats"""
+    _fields_ = [("device_chunks", ctypes.c_uint64), ("fallback_chunks", ctypes.c_uint64),
+                ("raw_bytes", ctypes.c_uint64), ("text_bytes", ctypes.c_uint64), ("ms_kernels", ctypes.c_double),
+                ("broken", ctypes.c_uint32), ("host_files", ctypes.c_uint32)]
 
 
 class Segment(ctypes.Structure):
@@ -181,6 +202,8 @@ EXPORTS = [
     "ntedit_hip_resident_insert_solid", "ntedit_hip_resident_free", "ntedit_hip_reads_build",
     "ntedit_hip_reads_stage_count", "ntedit_hip_reads_stage_histogram", "ntedit_hip_reads_stage_decide",
     "ntedit_hip_reads_stage_insert", "ntedit_hip_reads_options_check",
+    "ntedit_hip_reads_parse_device", "ntedit_hip_reads_parse_model", "ntedit_hip_reads_set_device_parse",
+    "ntedit_hip_reads_parse_info",
 ]
 
 _lib = None
@@ -312,5 +335,11 @@ def load():
     lib.ntedit_hip_reads_stage_decide.argtypes = [args, vp, res]
     lib.ntedit_hip_reads_stage_insert.argtypes = [vp, args, res]
     lib.ntedit_hip_reads_options_check.argtypes = [ctypes.POINTER(ReadsOptions), ci, ci, ctypes.POINTER(ReadsRules)]
+    # --gpu_parse
+    pres = ctypes.POINTER(ReadsParseResult)
+    lib.ntedit_hip_reads_parse_device.argtypes = [vp, vp, u64, ci, u32, vp, u64, pres]
+    lib.ntedit_hip_reads_parse_model.argtypes = [vp, u64, u32, vp, u64, pres]
+    lib.ntedit_hip_reads_set_device_parse.argtypes = [vp, ci]
+    lib.ntedit_hip_reads_parse_info.argtypes = [vp, ctypes.POINTER(ReadsParseStats)]
     _lib = lib
     return lib

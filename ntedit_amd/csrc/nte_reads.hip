@@ -759,6 +759,7 @@ solid_target(const ntedit_hip_ctx* c, const ReadsState* s, int slot, u32 cmin, c
 } // namespace
 
 namespace nte_reads {
+void parse_release(const ntedit_hip_ctx* c);
 // the failures of the host side (reads_pass.cpp) go to the same store as this unit's
 int
 set_error(const ntedit_hip_ctx* c, int code, const std::string& why)
@@ -930,6 +931,7 @@ make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, 
 void
 ntedit_hip_sketch_free(ntedit_hip_ctx* c)
 {
+	nte_reads::parse_release(c); // (the device parser's scratch, nte_reads_parse.hip)
 	ReadsState* s = nullptr;
 	{
 		std::lock_guard<std::mutex> lk(g_reads_mu);

@@ -1,0 +1,879 @@
+// nte_reads_parse.hip -- gfx950 kernels and C ABI of --gpu_parse: raw FASTA / FASTQ bytes in HBM to the batch text the
+// host parser (reads_pass.cpp) hands the reads kernels -- every read of k bases or more followed by '\n', in file order.
+// The grammar (line class, clean predicate, kept rule) is nte_reads_grammar.h; a chunk that breaks it is reported
+// unclean and left to the host parser.  ntedit_hip_reads_parse_model is the serial host model of the same functions.
+//
+// Phases, ordered by kernel boundaries on one stream (no hand-off between workgroups inside a launch):
+//   k_rp_tiles       per tile of 16 KiB (16-byte loads per lane): its number of '\n', and whether it holds a '\r'
+//   scan             tile counts -> the line index at each tile start; their total is read back (the one host sync
+//                    in the middle: it sizes the later grids, and a chunk over the line table's bound stops here)
+//   k_rp_line_ends   the tiles again: a '\n' at p with line index L = tile base + rank in the tile -> line_end[L] = p
+//   k_rp_classify    one lane per line: class and grammar checks (violations OR into one status word), and per line
+//                    (record heads, sequence bytes) packed in 64 bits
+//   scan             over the lines: each line's record and its offset in the record's sequence
+//   k_rp_heads / k_rp_records   each record's head line and length; kept records emit (1, length + 1)
+//   scan             over the records: each kept record's offset in the text
+//   k_rp_line_out    each sequence line's offset in the text, and the '\n' behind each kept record
+//   k_rp_copy        byte-parallel over the raw tiles: each lane finds the line of its 16 bytes from the tile base and
+//                    the newline ranks, and writes them to that line's place (a line longer than a tile costs what
+//                    its bytes cost)
+// The scans are count / scan / write over blocks of 2048 items (as k_count_starts / k_scan_counts / k_write_starts).
+//
+// Like nte_reads.hip this unit is outside KSRC and sees no context internals: its state hangs off the context pointer.
+#include "nte_common.h"
+#include "nte_reads_grammar.h"
+
+#include "../../include/ntedit_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace nte;
+using namespace nte_parse;
+
+namespace nte_reads {
+int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+}
+
+namespace {
+
+constexpr int RP_TPB = 256;
+constexpr int RP_TILE = 16384;
+constexpr int RP_IT = RP_TILE / (RP_TPB * 16);
+constexpr int SC_ITEMS = 8;
+constexpr int SC_BLOCK = RP_TPB * SC_ITEMS;
+constexpr u32 RP_NONE = 0xFFFFFFFFu; // line_out of a line that is not copied
+
+static_assert(NTEDIT_PARSE_TILE == RP_TILE, "the header names the tile size");
+static_assert(NTEDIT_PARSE_BAD_FIRST == RP_BAD_FIRST && NTEDIT_PARSE_BAD_CR == RP_BAD_CR && NTEDIT_PARSE_BAD_EMPTY == RP_BAD_EMPTY &&
+                  NTEDIT_PARSE_BAD_SEQ_START == RP_BAD_SEQ_START && NTEDIT_PARSE_BAD_FQ_LINES == RP_BAD_FQ_LINES &&
+                  NTEDIT_PARSE_BAD_FQ_HEADER == RP_BAD_FQ_HEADER && NTEDIT_PARSE_BAD_FQ_PLUS == RP_BAD_FQ_PLUS &&
+                  NTEDIT_PARSE_BAD_FQ_QUAL == RP_BAD_FQ_QUAL && NTEDIT_PARSE_BAD_TABLE == RP_BAD_TABLE &&
+                  NTEDIT_PARSE_BAD_SIZE == RP_BAD_SIZE,
+              "the header names the grammar's rules");
+
+struct RpInfo // the small result the device keeps per chunk
+{
+	u32 broken;
+	u32 kind;
+	u32 last_nl; // the chunk's last byte is '\n'
+	u32 pad;
+	u64 newlines;
+	u64 records; // hi: kept records, lo: text bytes
+};
+
+__host__ __device__ __forceinline__ u32
+lo32(u64 x)
+{
+	return (u32)x;
+}
+
+__host__ __device__ __forceinline__ u32
+hi32(u64 x)
+{
+	return (u32)(x >> 32);
+}
+
+// the 16 raw bytes at `off` (a multiple of 16; raw is 16-byte aligned); bytes past n read as 0
+__device__ __forceinline__ uint4
+rp_load16(const u8* __restrict__ raw, u64 n, u64 off)
+{
+	if (off + 16 <= n) {
+		return *reinterpret_cast<const uint4*>(raw + off);
+	}
+	u32 w[4] = { 0, 0, 0, 0 };
+	for (int b = 0; b < 16; b++) {
+		if (off + b < n) {
+			w[b >> 2] |= (u32)raw[off + b] << (8 * (b & 3));
+		}
+	}
+	return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// bit b set: byte b of the word equals ch (exact per byte: no carry crosses a byte)
+__device__ __forceinline__ u32
+rp_eq4(u32 w, u32 ch)
+{
+	const u32 x = w ^ (ch * 0x01010101u);
+	const u32 t = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu); // 0x80 in every zero byte of x
+	return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u);
+}
+
+__device__ __forceinline__ u32
+rp_eq16(uint4 v, u32 ch)
+{
+	return rp_eq4(v.x, ch) | (rp_eq4(v.y, ch) << 4) | (rp_eq4(v.z, ch) << 8) | (rp_eq4(v.w, ch) << 12);
+}
+
+// bytes past n must not count as newlines: they read as 0, and '\n' != 0
+
+// the newline masks of this lane's RP_IT pieces of the tile (piece j: bytes [j * 4096 + tid * 16, + 16) of the tile),
+// and for each piece the number of newlines of the tile before it (byte order is (j, tid) order)
+__device__ __forceinline__ void
+rp_tile_ranks(const u8* __restrict__ raw, u64 n, u64 tile_off, u32 (&mask)[RP_IT], u32 (&before)[RP_IT], uint4 (&bytes)[RP_IT])
+{
+	__shared__ u32 s_seg[RP_IT * (RP_TPB / 64)];
+	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	u32 in_wave[RP_IT];
+#pragma unroll
+	for (int j = 0; j < RP_IT; j++) {
+		bytes[j] = rp_load16(raw, n, tile_off + (u64)j * (RP_TPB * 16) + tid * 16);
+		mask[j] = rp_eq16(bytes[j], '\n');
+		const u32 c = __popc(mask[j]);
+		u32 incl = c;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const u32 up = __shfl_up(incl, d, 64);
+			if (lane >= (u32)d) {
+				incl += up;
+			}
+		}
+		in_wave[j] = incl - c;
+		if (lane == 63) {
+			s_seg[j * (RP_TPB / 64) + wave] = incl;
+		}
+	}
+	__syncthreads();
+#pragma unroll
+	for (int j = 0; j < RP_IT; j++) {
+		u32 base = 0;
+		const u32 me = j * (RP_TPB / 64) + wave;
+		for (u32 q = 0; q < me; q++) {
+			base += s_seg[q];
+		}
+		before[j] = base + in_wave[j];
+	}
+}
+
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_tiles(const u8* __restrict__ raw, u64 n, u64* __restrict__ tile_nl, RpInfo* info)
+{
+	__shared__ u32 s_cnt;
+	const u32 tid = threadIdx.x;
+	if (tid == 0) {
+		s_cnt = 0;
+	}
+	__syncthreads();
+	const u64 tile_off = (u64)blockIdx.x * RP_TILE;
+	u32 cnt = 0, cr = 0;
+#pragma unroll
+	for (int j = 0; j < RP_IT; j++) {
+		const uint4 v = rp_load16(raw, n, tile_off + (u64)j * (RP_TPB * 16) + tid * 16);
+		cnt += __popc(rp_eq16(v, '\n'));
+		cr |= rp_eq16(v, '\r');
+	}
+	if (cnt) {
+		atomicAdd(&s_cnt, cnt);
+	}
+	if (cr) {
+		atomicOr(&info->broken, (u32)RP_BAD_CR);
+	}
+	__syncthreads();
+	if (tid == 0) {
+		tile_nl[blockIdx.x] = s_cnt;
+		if (blockIdx.x == 0) {
+			info->kind = raw[0];
+			info->last_nl = raw[n - 1] == '\n';
+		}
+	}
+}
+
+// ------------------------------------------------------------------ exclusive scan of 64-bit items
+__device__ __forceinline__ u64
+block_excl_scan(u64 v, u64* total)
+{
+	__shared__ u64 s_wave[RP_TPB / 64];
+	const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	u64 incl = v;
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const u32 up_lo = __shfl_up((u32)incl, d, 64), up_hi = __shfl_up((u32)(incl >> 32), d, 64);
+		if (lane >= (u32)d) {
+			incl += ((u64)up_hi << 32) | up_lo;
+		}
+	}
+	__syncthreads(); // (a caller's loop may still be reading s_wave of the round before)
+	if (lane == 63) {
+		s_wave[wave] = incl;
+	}
+	__syncthreads();
+	u64 base = 0, all = 0;
+#pragma unroll
+	for (u32 w = 0; w < RP_TPB / 64; w++) {
+		base += w < wave ? s_wave[w] : 0;
+		all += s_wave[w];
+	}
+	*total = all;
+	return base + incl - v;
+}
+
+__global__ __launch_bounds__(RP_TPB) void
+k_scan_sums(const u64* __restrict__ in, u64 n, u64* __restrict__ bsum)
+{
+	const u64 at = (u64)blockIdx.x * SC_BLOCK + (u64)threadIdx.x * SC_ITEMS;
+	u64 t = 0;
+#pragma unroll
+	for (int i = 0; i < SC_ITEMS; i++) {
+		t += at + i < n ? in[at + i] : 0;
+	}
+	u64 total;
+	(void)block_excl_scan(t, &total);
+	if (threadIdx.x == 0) {
+		bsum[blockIdx.x] = total;
+	}
+}
+
+// one workgroup: bsum[0 .. nb) to its exclusive scan in place, the grand total to *total
+__global__ __launch_bounds__(RP_TPB) void
+k_scan_top(u64* __restrict__ bsum, u64 nb, u64* __restrict__ total)
+{
+	u64 carry = 0;
+	for (u64 base = 0; base < nb; base += RP_TPB) {
+		const u64 i = base + threadIdx.x;
+		const u64 v = i < nb ? bsum[i] : 0;
+		u64 all;
+		const u64 ex = block_excl_scan(v, &all);
+		if (i < nb) {
+			bsum[i] = carry + ex;
+		}
+		carry += all;
+	}
+	if (threadIdx.x == 0) {
+		*total = carry;
+	}
+}
+
+// out may be in
+__global__ __launch_bounds__(RP_TPB) void
+k_scan_write(const u64* in, u64 n, const u64* __restrict__ bsum, u64* out)
+{
+	const u64 at = (u64)blockIdx.x * SC_BLOCK + (u64)threadIdx.x * SC_ITEMS;
+	u64 v[SC_ITEMS], t = 0;
+#pragma unroll
+	for (int i = 0; i < SC_ITEMS; i++) {
+		v[i] = at + i < n ? in[at + i] : 0;
+		t += v[i];
+	}
+	u64 total;
+	u64 run = block_excl_scan(t, &total) + bsum[blockIdx.x];
+#pragma unroll
+	for (int i = 0; i < SC_ITEMS; i++) {
+		if (at + i < n) {
+			out[at + i] = run;
+		}
+		run += v[i];
+	}
+}
+
+// ------------------------------------------------------------------ lines
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_line_ends(const u8* __restrict__ raw, u64 n, const u64* __restrict__ tile_base, u32* __restrict__ line_end, u64 n_lines,
+               const RpInfo* __restrict__ info)
+{
+	u32 mask[RP_IT], before[RP_IT];
+	uint4 bytes[RP_IT];
+	const u64 tile_off = (u64)blockIdx.x * RP_TILE;
+	rp_tile_ranks(raw, n, tile_off, mask, before, bytes);
+	const u64 base = tile_base[blockIdx.x];
+#pragma unroll
+	for (int j = 0; j < RP_IT; j++) {
+		const u64 off = tile_off + (u64)j * (RP_TPB * 16) + threadIdx.x * 16;
+		u64 line = base + before[j];
+		for (u32 m = mask[j]; m; m &= m - 1) {
+			if (line < n_lines) {
+				line_end[line] = (u32)(off + (u32)__ffs(m) - 1);
+			}
+			line++;
+		}
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0 && !info->last_nl) {
+		line_end[n_lines - 1] = (u32)n; // the last line's virtual end
+	}
+}
+
+__device__ __forceinline__ u32
+rp_line_start(const u32* __restrict__ line_end, u64 line)
+{
+	return line ? line_end[line - 1] + 1 : 0;
+}
+
+// per line: its class, and (record heads << 32 | sequence bytes) for the scan
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_classify(const u8* __restrict__ raw, u64 n, const u32* __restrict__ line_end, u64 n_lines, u8* __restrict__ cls,
+              u64* __restrict__ val, RpInfo* info)
+{
+	const u64 line = (u64)blockIdx.x * RP_TPB + threadIdx.x;
+	if (line >= n_lines) {
+		return;
+	}
+	const int kind = (int)info->kind;
+	const u32 s = rp_line_start(line_end, line), e = line_end[line];
+	const u32 len = e - s;
+	u32 broken = line == 0 ? rp_chunk_broken(kind, n, n_lines) : 0;
+	const int c = rp_line_class(kind, line, len ? (int)raw[s] : -1, &broken);
+	if (kind == '@' && line % 4 == 3) {
+		const u32 seq_len = line_end[line - 2] - rp_line_start(line_end, line - 2);
+		broken |= rp_quality_broken(seq_len, len);
+	}
+	cls[line] = (u8)c;
+	val[line] = c == RP_HEADER ? 1ull << 32 : c == RP_SEQ ? (u64)len : 0ull;
+	if (broken) {
+		atomicOr(&info->broken, broken);
+	}
+}
+
+// sr[L]: hi = record heads before line L, lo = sequence bytes before it; sr[n_lines] = (records, sequence bytes)
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_heads(const u8* __restrict__ cls, const u64* __restrict__ sr, u64 n_lines, u32* __restrict__ head_line)
+{
+	const u64 line = (u64)blockIdx.x * RP_TPB + threadIdx.x;
+	if (line < n_lines && cls[line] == RP_HEADER) {
+		head_line[hi32(sr[line])] = (u32)line;
+	}
+	if (line == 0) {
+		head_line[hi32(sr[n_lines])] = (u32)n_lines;
+	}
+}
+
+// per record r: (1 << 32 | length + 1) when it is kept, else 0 (and 0 for r at or past the number of records)
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_records(const u64* __restrict__ sr, const u32* __restrict__ head_line, u64 n_lines, u32 k, u64* __restrict__ rec)
+{
+	const u64 r = (u64)blockIdx.x * RP_TPB + threadIdx.x;
+	if (r >= n_lines) {
+		return;
+	}
+	u64 v = 0;
+	if (r < hi32(sr[n_lines])) {
+		const u32 len = lo32(sr[head_line[r + 1]]) - lo32(sr[head_line[r]]);
+		if (rp_record_kept(len, k)) {
+			v = (1ull << 32) | ((u64)len + 1);
+		}
+	}
+	rec[r] = v;
+}
+
+// rec[r]: hi = kept records before r, lo = their text bytes: record r's place.  Each sequence line's place, the '\n'
+// behind each kept record, and the chunk's totals.
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_line_out(const u8* __restrict__ cls, const u64* __restrict__ sr, const u32* __restrict__ head_line, const u64* __restrict__ rec,
+              u64 n_lines, u32* __restrict__ line_out, u8* __restrict__ text, u64 text_cap, RpInfo* info)
+{
+	const u64 line = (u64)blockIdx.x * RP_TPB + threadIdx.x;
+	if (line >= n_lines) {
+		return;
+	}
+	if (line == 0) {
+		info->records = rec[n_lines];
+	}
+	const u32 c = cls[line];
+	u32 out = RP_NONE;
+	if (c == RP_SEQ && hi32(sr[line]) > 0) {
+		const u32 r = hi32(sr[line]) - 1;
+		if (rec[r + 1] != rec[r]) {
+			out = lo32(rec[r]) + (lo32(sr[line]) - lo32(sr[head_line[r]]));
+		}
+	} else if (c == RP_HEADER) {
+		const u32 r = hi32(sr[line]);
+		if (rec[r + 1] != rec[r]) {
+			const u64 at = (u64)lo32(rec[r + 1]) - 1;
+			if (at < text_cap) {
+				text[at] = '\n';
+			}
+		}
+	}
+	line_out[line] = out;
+}
+
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_copy(const u8* __restrict__ raw, u64 n, const u64* __restrict__ tile_base, const u32* __restrict__ line_end,
+          const u32* __restrict__ line_out, u64 n_lines, u8* __restrict__ text, u64 text_cap)
+{
+	u32 mask[RP_IT], before[RP_IT];
+	uint4 bytes[RP_IT];
+	const u64 tile_off = (u64)blockIdx.x * RP_TILE;
+	rp_tile_ranks(raw, n, tile_off, mask, before, bytes);
+	const u64 base = tile_base[blockIdx.x];
+#pragma unroll
+	for (int j = 0; j < RP_IT; j++) {
+		const u64 off = tile_off + (u64)j * (RP_TPB * 16) + threadIdx.x * 16;
+		if (off >= n) {
+			continue;
+		}
+		u64 line = base + before[j];
+		if (line >= n_lines) {
+			continue;
+		}
+		const u32 w[4] = { bytes[j].x, bytes[j].y, bytes[j].z, bytes[j].w };
+		u32 out = line_out[line];
+		// text position of raw byte p of this line: p + delta (32-bit wrap-around is exact: the result is in range)
+		u32 delta = out - rp_line_start(line_end, line);
+		const u32 m = mask[j];
+#pragma unroll
+		for (int b = 0; b < 16; b++) {
+			if (off + b >= n) {
+				break;
+			}
+			if ((m >> b) & 1u) {
+				line++;
+				if (line >= n_lines) {
+					break;
+				}
+				out = line_out[line];
+				delta = out - (u32)(off + b + 1);
+				continue;
+			}
+			if (out != RP_NONE) {
+				const u32 at = (u32)(off + b) + delta;
+				if (at < text_cap) {
+					text[at] = (u8)(w[b >> 2] >> (8 * (b & 3)));
+				}
+			}
+		}
+	}
+}
+
+// ------------------------------------------------------------------ host side
+struct ParseState
+{
+	const ntedit_hip_ctx* owner = nullptr;
+	int on = 0; // ntedit_hip_reads_set_device_parse
+	ntedit_hip_reads_parse_stats info = {};
+	// device scratch, grow-only, released by ntedit_hip_sketch_free
+	int device = -1;
+	hipStream_t stream = nullptr, copy_stream = nullptr;
+	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr }, copied[2] = { nullptr, nullptr };
+	u8* d_raw[2] = { nullptr, nullptr };
+	u64 raw_cap[2] = { 0, 0 };
+	u8* d_text = nullptr;
+	u64 text_cap = 0;
+	u8* d_table = nullptr; // the line table and the scans' block sums, for chunks of up to table_raw bytes
+	u64 table_raw = 0;
+	RpInfo* d_info = nullptr;
+	RpInfo* h_info = nullptr; // page-locked
+};
+
+std::mutex g_parse_mu;
+std::vector<ParseState*> g_parse;
+
+ParseState*
+parse_state(const ntedit_hip_ctx* c, bool create)
+{
+	std::lock_guard<std::mutex> lk(g_parse_mu);
+	for (ParseState* s : g_parse) {
+		if (s->owner == c) {
+			return s;
+		}
+	}
+	if (!create) {
+		return nullptr;
+	}
+	ParseState* s = new ParseState();
+	s->owner = c;
+	g_parse.push_back(s);
+	return s;
+}
+
+int
+pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
+{
+	return nte_reads::set_error(c, code, why);
+}
+
+#define RP_TRY(ctx, expr)                                                                         \
+	do {                                                                                          \
+		hipError_t e_ = (expr);                                                                   \
+		if (e_ != hipSuccess) {                                                                   \
+			return pfail((ctx), NTEDIT_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
+		}                                                                                         \
+	} while (0)
+
+void
+release_scratch(ParseState* s)
+{
+	if (s->device < 0) {
+		return;
+	}
+	(void)hipSetDevice(s->device);
+	for (hipStream_t st : { s->stream, s->copy_stream }) {
+		if (st) {
+			(void)hipStreamSynchronize(st);
+			(void)hipStreamDestroy(st);
+		}
+	}
+	for (hipEvent_t e : { s->ev[0], s->ev[1], s->ev[2], s->ev[3], s->copied[0], s->copied[1] }) {
+		if (e) {
+			(void)hipEventDestroy(e);
+		}
+	}
+	for (void* p : { (void*)s->d_raw[0], (void*)s->d_raw[1], (void*)s->d_text, (void*)s->d_table, (void*)s->d_info }) {
+		if (p) {
+			(void)hipFree(p);
+		}
+	}
+	if (s->h_info) {
+		(void)hipHostFree(s->h_info);
+	}
+	const ntedit_hip_ctx* owner = s->owner;
+	const int on = s->on;
+	const ntedit_hip_reads_parse_stats info = s->info;
+	*s = ParseState();
+	s->owner = owner;
+	s->on = on;
+	s->info = info;
+}
+
+int
+ensure_device(const ntedit_hip_ctx* c, ParseState* s)
+{
+	if (s->device >= 0) {
+		RP_TRY(c, hipSetDevice(s->device));
+		return 0;
+	}
+	int device = 0;
+	RP_TRY(c, hipGetDevice(&device));
+	s->device = device;
+	RP_TRY(c, hipStreamCreate(&s->stream));
+	RP_TRY(c, hipStreamCreate(&s->copy_stream));
+	for (hipEvent_t& e : s->ev) {
+		RP_TRY(c, hipEventCreate(&e));
+	}
+	for (hipEvent_t& e : s->copied) {
+		RP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+	}
+	RP_TRY(c, hipMalloc((void**)&s->d_info, sizeof(RpInfo)));
+	RP_TRY(c, hipHostMalloc((void**)&s->h_info, sizeof(RpInfo), hipHostMallocDefault));
+	return 0;
+}
+
+int
+grow(const ntedit_hip_ctx* c, u8** p, u64* cap, u64 need)
+{
+	if (need <= *cap && *p) {
+		return 0;
+	}
+	if (*p) {
+		RP_TRY(c, hipFree(*p));
+		*p = nullptr;
+		*cap = 0;
+	}
+	const u64 want = (need + (1u << 20)) / 16 * 16;
+	RP_TRY(c, hipMalloc((void**)p, want + RP_TILE));
+	*cap = want;
+	return 0;
+}
+
+u64
+up256(u64 x)
+{
+	return (x + 255) / 256 * 256;
+}
+
+// the line table of a chunk of up to n raw bytes, carved from one allocation
+struct Table
+{
+	u64 *tile, *sr, *rec, *bsum;
+	u32 *line_end, *head_line, *line_out;
+	u8* cls;
+	u64 bytes;
+};
+
+Table
+carve(u8* base, u64 n_raw)
+{
+	const u64 tiles = (n_raw + RP_TILE - 1) / RP_TILE + 1, lines = rp_max_lines(n_raw) + 2;
+	const u64 blocks = (lines > tiles ? lines : tiles) / SC_BLOCK + 2;
+	Table t;
+	u64 at = 0;
+	auto take = [&](u64 bytes) {
+		u8* p = base + at;
+		at += up256(bytes);
+		return p;
+	};
+	t.tile = (u64*)take(tiles * 8);
+	t.sr = (u64*)take(lines * 8);
+	t.rec = (u64*)take(lines * 8);
+	t.bsum = (u64*)take(blocks * 8);
+	t.line_end = (u32*)take(lines * 4);
+	t.head_line = (u32*)take(lines * 4);
+	t.line_out = (u32*)take(lines * 4);
+	t.cls = take(lines);
+	t.bytes = at;
+	return t;
+}
+
+// data[0 .. n) to its exclusive scan in place, data[n] = the total
+void
+scan(ParseState* s, u64* data, u64 n, u64* bsum)
+{
+	const u64 nb = (n + SC_BLOCK - 1) / SC_BLOCK;
+	hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nb), dim3(RP_TPB), 0, s->stream, data, n, bsum);
+	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(RP_TPB), 0, s->stream, bsum, nb, data + n);
+	hipLaunchKernelGGL(k_scan_write, dim3((unsigned)nb), dim3(RP_TPB), 0, s->stream, data, n, bsum, data);
+}
+
+int
+parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, u32 k, u8* d_text, u64 text_cap,
+                ntedit_hip_reads_parse_result* res)
+{
+	*res = ntedit_hip_reads_parse_result();
+	if (n == 0) {
+		res->clean = 1;
+		return 0;
+	}
+	if (n >= RP_MAX_RAW) {
+		res->broken = RP_BAD_SIZE;
+		return 0;
+	}
+	if (n > s->table_raw || !s->d_table) {
+		const u64 want = n + (1u << 20);
+		if (s->d_table) {
+			RP_TRY(c, hipFree(s->d_table));
+			s->d_table = nullptr;
+			s->table_raw = 0;
+		}
+		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
+		s->table_raw = want;
+	}
+	const Table t = carve(s->d_table, s->table_raw);
+	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
+	RP_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
+	RP_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	hipLaunchKernelGGL(k_rp_tiles, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, s->d_info);
+	scan(s, t.tile, tiles, t.bsum);
+	RP_TRY(c, hipGetLastError());
+	RP_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	RP_TRY(c, hipMemcpyAsync(&s->h_info->newlines, t.tile + tiles, 8, hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, 16, hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipStreamSynchronize(s->stream));
+	float ms = 0;
+	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	s->info.ms_kernels += ms;
+	const u64 lines = s->h_info->newlines + (s->h_info->last_nl ? 0 : 1);
+	res->kind = (int)s->h_info->kind;
+	res->lines = lines;
+	// what is known by now ends the chunk here: over the table's bound nothing more may run
+	res->broken = s->h_info->broken | rp_chunk_broken(res->kind, n, lines);
+	if (res->broken) {
+		return 0;
+	}
+	const unsigned line_blocks = (unsigned)((lines + RP_TPB - 1) / RP_TPB);
+	RP_TRY(c, hipEventRecord(s->ev[2], s->stream));
+	hipLaunchKernelGGL(k_rp_line_ends, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, lines, s->d_info);
+	hipLaunchKernelGGL(k_rp_classify, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, d_raw, n, t.line_end, lines, t.cls, t.sr, s->d_info);
+	scan(s, t.sr, lines, t.bsum);
+	hipLaunchKernelGGL(k_rp_heads, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, lines, t.head_line);
+	hipLaunchKernelGGL(k_rp_records, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.sr, t.head_line, lines, k, t.rec);
+	scan(s, t.rec, lines, t.bsum);
+	hipLaunchKernelGGL(k_rp_line_out, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, t.head_line, t.rec, lines, t.line_out,
+	                   d_text, text_cap, s->d_info);
+	hipLaunchKernelGGL(k_rp_copy, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out, lines,
+	                   d_text, text_cap);
+	RP_TRY(c, hipGetLastError());
+	RP_TRY(c, hipEventRecord(s->ev[3], s->stream));
+	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(RpInfo), hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipStreamSynchronize(s->stream));
+	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+	s->info.ms_kernels += ms;
+	res->broken = s->h_info->broken;
+	if (res->broken) {
+		return 0;
+	}
+	res->clean = 1;
+	res->text_len = lo32(s->h_info->records);
+	res->reads = hi32(s->h_info->records);
+	res->bases = res->text_len - res->reads;
+	return 0;
+}
+
+} // namespace
+
+// what the pass loop of reads_pass.cpp needs beyond the public calls: the two raw buffers and the copy stream
+namespace nte_reads {
+
+void
+parse_release(const ntedit_hip_ctx* c)
+{
+	ParseState* s = parse_state(c, false);
+	if (s) {
+		release_scratch(s);
+	}
+}
+
+int
+parse_is_on(const ntedit_hip_ctx* c)
+{
+	ParseState* s = parse_state(c, false);
+	return s ? s->on : 0;
+}
+
+ntedit_hip_reads_parse_stats*
+parse_info(const ntedit_hip_ctx* c)
+{
+	return &parse_state(c, true)->info;
+}
+
+// host chunk -> raw buffer `which`, on the copy stream; returns at once
+int
+parse_copy_begin(const ntedit_hip_ctx* c, int which, const char* host, uint64_t n)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, &s->d_raw[which], &s->raw_cap[which], n);
+	}
+	if (rc) {
+		return rc;
+	}
+	if (n) {
+		RP_TRY(c, hipMemcpyAsync(s->d_raw[which], host, n, hipMemcpyHostToDevice, s->copy_stream));
+	}
+	RP_TRY(c, hipEventRecord(s->copied[which], s->copy_stream));
+	return 0;
+}
+
+int
+parse_copy_wait(const ntedit_hip_ctx* c, int which)
+{
+	ParseState* s = parse_state(c, false);
+	if (s && s->copied[which]) {
+		RP_TRY(c, hipEventSynchronize(s->copied[which]));
+	}
+	return 0;
+}
+
+// waits for that copy, then parses the buffer into the context's text buffer (*text: where, 16-byte aligned)
+int
+parse_copied(const ntedit_hip_ctx* c, int which, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, &s->d_text, &s->text_cap, n);
+	}
+	if (rc) {
+		return rc;
+	}
+	RP_TRY(c, hipEventSynchronize(s->copied[which]));
+	*text = (const char*)s->d_text;
+	return parse_on_device(c, s, s->d_raw[which], n, k, s->d_text, s->text_cap, res);
+}
+
+} // namespace nte_reads
+
+extern "C" {
+
+int
+ntedit_hip_reads_set_device_parse(ntedit_hip_ctx* c, int on)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	parse_state(c, true)->on = on ? 1 : 0;
+	return 0;
+}
+
+int
+ntedit_hip_reads_parse_info(ntedit_hip_ctx* c, ntedit_hip_reads_parse_stats* st)
+{
+	if (!c || !st) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_parse_info: bad argument") : NTEDIT_E_ARG;
+	}
+	*st = parse_state(c, true)->info;
+	return 0;
+}
+
+int
+ntedit_hip_reads_parse_device(ntedit_hip_ctx* c, const char* raw, uint64_t n_raw, int on_device, uint32_t k, char* text_device,
+                              uint64_t text_cap, ntedit_hip_reads_parse_result* res)
+{
+	if (!c || !res || (n_raw && (!raw || !text_device)) || k == 0 ||
+	    (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE)) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_parse_device: bad argument") : NTEDIT_E_ARG;
+	}
+	if (((uintptr_t)text_device & 15) || (on_device == NTEDIT_HIP_BASES_DEVICE && ((uintptr_t)raw & 15))) {
+		return pfail(c, NTEDIT_E_ARG, "reads_parse_device: device buffers must be 16-byte aligned");
+	}
+	if (text_cap < n_raw) {
+		return pfail(c, NTEDIT_E_ARG, "reads_parse_device: text_cap must be at least n_raw (the text is never longer than the raw bytes)");
+	}
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc) {
+		return rc;
+	}
+	const u8* d_raw = (const u8*)raw;
+	if (on_device == NTEDIT_HIP_BASES_HOST && n_raw) {
+		if ((rc = grow(c, &s->d_raw[0], &s->raw_cap[0], n_raw)) != 0) {
+			return rc;
+		}
+		RP_TRY(c, hipMemcpyAsync(s->d_raw[0], raw, n_raw, hipMemcpyHostToDevice, s->stream));
+		d_raw = s->d_raw[0];
+	}
+	return parse_on_device(c, s, d_raw, n_raw, k, (u8*)text_device, text_cap, res);
+}
+
+// the serial model: the same grammar functions, one line after the other
+int
+ntedit_hip_reads_parse_model(const char* raw, uint64_t n_raw, uint32_t k, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res)
+{
+	if (!res || (n_raw && !raw) || (cap && !out) || k == 0) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_parse_model: bad argument");
+	}
+	*res = ntedit_hip_reads_parse_result();
+	if (n_raw == 0) {
+		res->clean = 1;
+		return 0;
+	}
+	const int kind = (unsigned char)raw[0];
+	uint32_t broken = memchr(raw, '\r', n_raw) ? (uint32_t)RP_BAD_CR : 0u;
+	uint64_t lines = 0, used = 0, reads = 0, bases = 0, seq_len = 0;
+	std::string cur;
+	bool open = false;
+	auto flush = [&]() {
+		if (open && rp_record_kept(cur.size(), k)) {
+			if (used + cur.size() + 1 <= cap) {
+				memcpy(out + used, cur.data(), cur.size());
+				out[used + cur.size()] = '\n';
+			}
+			used += cur.size() + 1;
+			reads++;
+			bases += cur.size();
+		}
+		cur.clear();
+	};
+	for (uint64_t s = 0; s < n_raw; lines++) {
+		const char* nl = (const char*)memchr(raw + s, '\n', n_raw - s);
+		const uint64_t e = nl ? (uint64_t)(nl - raw) : n_raw;
+		const int c = rp_line_class(kind, lines, e > s ? (int)(unsigned char)raw[s] : -1, &broken);
+		if (c == RP_HEADER) {
+			flush();
+			open = true;
+		} else if (c == RP_SEQ) {
+			cur.append(raw + s, e - s);
+			seq_len = e - s;
+		} else if (kind == '@' && lines % 4 == 3) {
+			broken |= rp_quality_broken(seq_len, e - s);
+		}
+		s = e + 1;
+	}
+	flush();
+	broken |= rp_chunk_broken(kind, n_raw, lines);
+	res->kind = kind;
+	res->lines = lines;
+	res->broken = broken;
+	if (broken) {
+		return 0;
+	}
+	res->clean = 1;
+	res->text_len = used;
+	res->reads = reads;
+	res->bases = bases;
+	return used > cap ? NTEDIT_E_OVERFLOW : 0;
+}
+
+} // extern "C"

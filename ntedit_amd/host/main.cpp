@@ -84,6 +84,8 @@ static const char USAGE[] = PROGRAM
     "	--hist FILE,	write the k-mer histogram (ntCard's text format)\n"
     "	--save_bf FILE,	write the filter that was built (the same bytes as ntedit-make-reads-bf -o); its name is the\n"
     "			_r part of the default prefix [default name: reads_k<K>.bf, not written]\n"
+    "	--gpu_parse,	parse plain (not gzip) read files on the GPU: the host ships raw file bytes (same outputs;\n"
+    "			gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with the host parser)\n"
     "	--help,		display this message and exit \n"
     "	--version,	output version information and exit\n\n";
 
@@ -112,7 +114,8 @@ enum
 	OPT_HIST,
 	OPT_SAVE_BF,
 	OPT_READS_BATCH,
-	OPT_STORE_CAP
+	OPT_STORE_CAP,
+	OPT_GPU_PARSE
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -159,6 +162,7 @@ static const struct option longopts[] = {
 	{ "save_bf", required_argument, nullptr, OPT_SAVE_BF },
 	{ "batch_bytes", required_argument, nullptr, OPT_READS_BATCH }, // tests: many small read batches
 	{ "resident_cap", required_argument, nullptr, OPT_STORE_CAP }, // tests: the resident store's cap (0: off)
+	{ "gpu_parse", no_argument, nullptr, OPT_GPU_PARSE },
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -466,6 +470,10 @@ main(int argc, char** argv)
 		case OPT_STORE_CAP:
 			reads_option("--resident_cap", &ro.store_cap);
 			break;
+		case OPT_GPU_PARSE:
+			ro.gpu_parse = 1;
+			reads_only.push_back("--gpu_parse");
+			break;
 		case OPT_GPU:
 			parse(c, optarg, gpu);
 			break;
@@ -665,6 +673,7 @@ main(int argc, char** argv)
 		ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
 		ba.use_store = 1;
 		ba.store_cap = rr.store_cap;
+		ba.device_parse = rr.gpu_parse;
 		ba.log = nte_host::reads_log;
 		ntedit_hip_reads_build_result br;
 		if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {

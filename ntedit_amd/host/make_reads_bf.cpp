@@ -41,7 +41,7 @@ usage(const char* why)
 	}
 	std::cerr
 	    << "Usage: make_reads_bf [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] [--counts] [--hashes VAR] "
-	       "[--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [-o VAR] [-t VAR]\n\n"
+	       "[--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] [-t VAR]\n\n"
 	       "Builds the k-mer filter of a read set on the GPU: pass 1 counts every k-mer in a count-min sketch of 8-bit\n"
 	       "counters, pass 2 keeps the k-mers whose estimate (the minimum of their counters) is at least -c.  Neither\n"
 	       "ntHits nor ntStat: the counts (plain count-min, no conservative update) and the sizing are this tool's own.\n"
@@ -65,6 +65,9 @@ usage(const char* why)
 	       "                  --num_elements is the number of k-mers the histogram puts at cmin or above)\n"
 	       "  --sketch_bytes  Counters of the count-min sketch [default: 16 x the output bytes, or sized from the\n"
 	       "                  histogram one per input byte (gzip: 4 x), 64 MiB to 32 GiB]\n"
+	       "  --gpu_parse     Parse plain (not gzip) read files on the GPU: the host ships raw file bytes.  The output is\n"
+	       "                  the same; gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with\n"
+	       "                  the host parser\n"
 	       "  -o              Name for output filter [default: \"reads_k<K>.bf\"]\n"
 	       "  -t              Number of threads (accepted; the k-mers are counted on the GPU) [default: 12]\n";
 }
@@ -126,6 +129,8 @@ main(int argc, char** argv)
 			ro.solid = 1;
 		} else if (a == "--hist") {
 			hist_out = value("--hist");
+		} else if (a == "--gpu_parse") {
+			ro.gpu_parse = 1;
 		} else if (a == "--counts") {
 			counts = true;
 		} else if (a == "--hashes") {
@@ -189,6 +194,9 @@ main(int argc, char** argv)
 	if (counts) {
 		std::cout << "\t\t--counts" << std::endl;
 	}
+	if (rr.gpu_parse) {
+		std::cout << "\t\t--gpu_parse" << std::endl;
+	}
 	if (ro.bf) {
 		std::cout << "\t\t--bf " << rr.bf_bytes << std::endl;
 	} else if (ro.num_elements) {
@@ -226,6 +234,7 @@ main(int argc, char** argv)
 	ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
 	ba.sketch_path = sketch_out.empty() ? nullptr : sketch_out.c_str();
 	ba.log = nte_host::reads_log;
+	ba.device_parse = rr.gpu_parse;
 	ntedit_hip_reads_build_result br;
 	if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));

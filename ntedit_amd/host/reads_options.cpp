@@ -57,6 +57,7 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 	r->batch_bytes = NTEDIT_READS_BATCH_DEFAULT;
 	r->store_cap = NTEDIT_READS_RESIDENT_CAP_DEFAULT;
 	r->threads = 12;
+	r->gpu_parse = o->gpu_parse ? 1 : 0; // (the one rule about it, "only with --reads", is the polisher front ends': they know)
 	uint64_t k = 0, cmin = 0, hashes = r->hash_num;
 	// -k: the tool refuses a malformed one at the option, the polisher takes it as out of range
 	if (final && !o->k) {

@@ -26,10 +26,18 @@
 #include <thread>
 #include <vector>
 
+#include <fcntl.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 namespace nte_reads {
 int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+// --gpu_parse (nte_reads_parse.hip): the context's setting and counters, its two raw buffers and its copy stream
+int parse_is_on(const ntedit_hip_ctx* c);
+ntedit_hip_reads_parse_stats* parse_info(const ntedit_hip_ctx* c);
+int parse_copy_begin(const ntedit_hip_ctx* c, int which, const char* host, uint64_t n);
+int parse_copy_wait(const ntedit_hip_ctx* c, int which);
+int parse_copied(const ntedit_hip_ctx* c, int which, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res);
 }
 
 namespace {
@@ -118,9 +126,9 @@ find_record_start(const char* path, uint64_t begin, uint64_t* out, std::string* 
 // every record of one range, in order: seq(record) for each; *start / *next as ntedit_hip_reads_pass reports them
 bool
 read_range(const char* path, uint64_t begin, uint64_t end, const std::function<bool(const std::string&)>& seq_fn,
-           uint64_t* start, uint64_t* next, std::string* why)
+           uint64_t* start, uint64_t* next, std::string* why, bool exact = false)
 {
-	uint64_t s = 0;
+	uint64_t s = exact ? begin : 0; // exact: begin is a record start (where --gpu_parse hands a range back)
 	if (begin > 0 || end != WHOLE) {
 		struct stat st;
 		if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) {
@@ -131,7 +139,7 @@ read_range(const char* path, uint64_t begin, uint64_t end, const std::function<b
 			*why = std::string(path) + ": a gzip file is read whole, not in ranges";
 			return false;
 		}
-		if (begin > 0 && !find_record_start(path, begin, &s, why)) {
+		if (begin > 0 && !exact && !find_record_start(path, begin, &s, why)) {
 			return false;
 		}
 	}
@@ -167,6 +175,7 @@ struct Range
 {
 	const char* path;
 	uint64_t begin, end;
+	bool exact = false; // begin is a record start: no search for one
 };
 
 // page-locked batch buffers: the parser fills one while the GPU works on the other
@@ -311,7 +320,7 @@ class BatchFeeder
 				stopped = !add_(b, seq);
 				return !stopped;
 			};
-			const bool ok = read_range(r.path, r.begin, r.end, add, &start, &next, &why);
+			const bool ok = read_range(r.path, r.begin, r.end, add, &start, &next, &why, r.exact);
 			if (stopped) {
 				return; // (add_ failed the feeder, or it is being torn down)
 			}
@@ -338,6 +347,241 @@ class BatchFeeder
 	uint64_t *starts_, *nexts_;
 	Batch bufs_[2];
 	std::deque<Batch*> free_, full_;
+	bool stop_ = false, failed_ = false;
+	std::string err_;
+	std::mutex mu_;
+	std::condition_variable cv_;
+	std::thread th_;
+};
+
+
+// ------------------------------------------------------------------ --gpu_parse: raw chunks instead of parsed batches
+const size_t NONE = ~(size_t)0;
+const size_t RAW_CHUNK_MAX = 1u << 30; // (the device parser takes chunks below 2^31 bytes)
+const unsigned RAW_READERS = 4;        // threads that pread slices of one chunk
+const size_t RAW_SLICE_MIN = 4u << 20;
+
+// the last record start in buf(0, n) by find_record_start's rule for a chunk of this kind: '>' at a line start, or an
+// '@' line whose line + 2 (inside the buffer) starts with '+'; NONE when there is none
+size_t
+last_record_start(const char* buf, size_t n, int kind)
+{
+	if (kind == '>') {
+		for (size_t end = n; end > 1;) {
+			const char* q = (const char*)memrchr(buf + 1, '>', end - 1);
+			if (!q) {
+				break;
+			}
+			if (q[-1] == '\n') {
+				return (size_t)(q - buf);
+			}
+			end = (size_t)(q - buf);
+		}
+		return NONE;
+	}
+	size_t l1 = NONE, l2 = NONE; // the starts of the two lines behind the current one
+	for (size_t end = n; end >= 2;) {
+		const char* q = (const char*)memrchr(buf, '\n', end - 1);
+		if (!q) {
+			break;
+		}
+		const size_t cur = (size_t)(q - buf) + 1;
+		if (l2 != NONE && buf[cur] == '@' && buf[l2] == '+') {
+			return cur;
+		}
+		l2 = l1;
+		l1 = cur;
+		end = cur;
+	}
+	return NONE;
+}
+
+// file bytes [off, off + n) into p, by a few threads: raw reading has no order
+bool
+pread_all(int fd, char* p, uint64_t off, size_t n)
+{
+	auto slice = [fd](char* q, uint64_t at, size_t len) {
+		while (len) {
+			const ssize_t got = pread(fd, q, len, (off_t)at);
+			if (got <= 0) {
+				return false;
+			}
+			q += got, at += (uint64_t)got, len -= (size_t)got;
+		}
+		return true;
+	};
+	const size_t parts = n / RAW_SLICE_MIN < RAW_READERS ? (n / RAW_SLICE_MIN ? n / RAW_SLICE_MIN : 1) : RAW_READERS;
+	if (parts == 1) {
+		return slice(p, off, n);
+	}
+	std::vector<std::thread> th;
+	std::vector<char> ok(parts, 0);
+	for (size_t i = 0; i < parts; i++) {
+		const size_t a = n * i / parts, b = n * (i + 1) / parts;
+		th.emplace_back([&, i, a, b] { ok[i] = slice(p + a, off + a, b - a); });
+	}
+	bool all = true;
+	for (size_t i = 0; i < parts; i++) {
+		th[i].join();
+		all = all && ok[i];
+	}
+	return all;
+}
+
+// The bytes [start, stop) of one plain file (start a record start, stop a record start or the file's end) as chunks of
+// about batch_bytes raw bytes, each cut at its last record start, the tail carried into the next; double-buffered through
+// page-locked memory as BatchFeeder's batches are.  A chunk without a record start past its first byte grows by another
+// batch_bytes (a record longer than a batch).
+struct RawChunk
+{
+	char* p = nullptr;
+	size_t cap = 0, len = 0;
+	uint64_t off = 0; // of its first byte in the file
+	bool last = false;
+};
+
+class RawFeeder
+{
+  public:
+	RawFeeder(const char* path, uint64_t start, uint64_t stop, size_t batch_bytes)
+	    : path_(path), pos_(start), stop_at_(stop), batch_bytes_(batch_bytes < RAW_CHUNK_MAX ? batch_bytes : RAW_CHUNK_MAX)
+	{
+		for (RawChunk& b : bufs_) {
+			free_.push_back(&b);
+		}
+		th_ = std::thread([this] { run_(); });
+	}
+	~RawFeeder()
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			stop_ = true;
+		}
+		cv_.notify_all();
+		th_.join();
+		for (RawChunk& b : bufs_) {
+			ntedit_hip_host_free(b.p);
+		}
+	}
+	RawChunk* take()
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		cv_.wait(lk, [this] { return !full_.empty() || failed_; });
+		if (full_.empty()) {
+			return nullptr;
+		}
+		RawChunk* b = full_.front();
+		full_.pop_front();
+		return b;
+	}
+	void give_back(RawChunk* b)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			free_.push_back(b);
+		}
+		cv_.notify_all();
+	}
+	const std::string& error() const { return err_; }
+
+  private:
+	void fail_(const std::string& why)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			err_ = why;
+			failed_ = true;
+		}
+		cv_.notify_all();
+	}
+	bool reserve_(RawChunk* b, size_t need, size_t keep)
+	{
+		if (need <= b->cap) {
+			return true;
+		}
+		char* p = (char*)ntedit_hip_host_alloc(need);
+		if (!p) {
+			return false;
+		}
+		if (keep) {
+			memcpy(p, b->p, keep);
+		}
+		ntedit_hip_host_free(b->p);
+		b->p = p;
+		b->cap = need;
+		return true;
+	}
+	void run_()
+	{
+		const int fd = open(path_, O_RDONLY);
+		if (fd < 0) {
+			fail_(std::string("cannot open ") + path_);
+			return;
+		}
+		std::vector<char> tail;
+		while (pos_ < stop_at_) {
+			RawChunk* b;
+			{
+				std::unique_lock<std::mutex> lk(mu_);
+				cv_.wait(lk, [this] { return !free_.empty() || stop_; });
+				if (stop_) {
+					break;
+				}
+				b = free_.front();
+				free_.pop_front();
+			}
+			size_t have = tail.size(), want = batch_bytes_ > have ? batch_bytes_ : have + batch_bytes_;
+			bool ok = reserve_(b, want, 0);
+			if (ok && have) {
+				memcpy(b->p, tail.data(), have);
+			}
+			size_t cut = NONE;
+			while (ok) {
+				if ((uint64_t)want > stop_at_ - pos_) {
+					want = (size_t)(stop_at_ - pos_);
+				}
+				if (!pread_all(fd, b->p + have, pos_ + have, want - have)) {
+					fail_(std::string(path_) + ": read error");
+					close(fd);
+					return;
+				}
+				have = want;
+				if (pos_ + have == stop_at_) {
+					cut = have; // the range's last chunk ends where the range does
+					break;
+				}
+				const int kind = (unsigned char)b->p[0];
+				cut = kind == '>' || kind == '@' ? last_record_start(b->p, have, kind) : have; // (neither: unclean anyway)
+				if (cut != NONE) {
+					break;
+				}
+				want = have + batch_bytes_;
+				ok = reserve_(b, want, have);
+			}
+			if (!ok) {
+				fail_("cannot allocate page-locked host memory");
+				close(fd);
+				return;
+			}
+			tail.assign(b->p + cut, b->p + have);
+			b->len = cut;
+			b->off = pos_;
+			pos_ += cut;
+			b->last = pos_ >= stop_at_;
+			{
+				std::lock_guard<std::mutex> lk(mu_);
+				full_.push_back(b);
+			}
+			cv_.notify_all();
+		}
+		close(fd);
+	}
+
+	const char* path_;
+	uint64_t pos_, stop_at_;
+	size_t batch_bytes_;
+	RawChunk bufs_[2];
+	std::deque<RawChunk*> free_, full_;
 	bool stop_ = false, failed_ = false;
 	std::string err_;
 	std::mutex mu_;
@@ -373,21 +617,22 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 	const auto t0 = std::chrono::steady_clock::now();
 	uint64_t bases = 0;
 	double gpu_ms = 0.0;
-	{
-		BatchFeeder feed(ranges, k, (size_t)batch_bytes, starts, nexts);
+	// one batch of text, host or device, through the pass's kernels
+	auto run_batch = [&](const char* text, uint64_t len, int where) {
+		return pass == NTEDIT_READS_PASS_COUNT  ? ntedit_hip_sketch_count(ctx, text, len, where)
+		       : pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_sketch_histogram(ctx, text, len, where)
+		                                        : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, text, len, where, cmin);
+	};
+	// the host parser over some ranges (all of them, without --gpu_parse)
+	auto host_pass = [&](const std::vector<Range>& rs, uint64_t* rs_starts, uint64_t* rs_nexts) {
+		BatchFeeder feed(rs, k, (size_t)batch_bytes, rs_starts, rs_nexts);
 		for (;;) {
 			Batch* b = feed.take();
 			if (!b) {
 				return pfail(ctx, NTEDIT_E_IO, feed.error());
 			}
 			const auto g0 = std::chrono::steady_clock::now();
-			int rc = 0;
-			if (b->len) { // (an input without any read of k bases ends in an empty batch)
-				rc = pass == NTEDIT_READS_PASS_COUNT  ? ntedit_hip_sketch_count(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
-				     : pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_sketch_histogram(ctx, b->p, b->len, NTEDIT_HIP_BASES_HOST)
-				                                      : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, b->p,
-				                                                                       b->len, NTEDIT_HIP_BASES_HOST, cmin);
-			}
+			const int rc = b->len ? run_batch(b->p, b->len, NTEDIT_HIP_BASES_HOST) : 0; // (an input without any read of k bases ends in an empty batch)
 			if (rc) {
 				return pfail(ctx, rc, ntedit_hip_reads_last_error(ctx));
 			}
@@ -396,7 +641,112 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 			const bool last = b->last;
 			feed.give_back(b);
 			if (last) {
-				break;
+				return 0;
+			}
+		}
+	};
+	if (!nte_reads::parse_is_on(ctx)) {
+		const int rc = host_pass(ranges, starts, nexts);
+		if (rc) {
+			return rc;
+		}
+	} else {
+		ntedit_hip_reads_parse_stats& info = *nte_reads::parse_info(ctx);
+		info = ntedit_hip_reads_parse_stats();
+		for (uint32_t i = 0; i < n; i++) {
+			const Range& r = ranges[i];
+			struct stat sb;
+			const bool regular = stat(r.path, &sb) == 0 && S_ISREG(sb.st_mode);
+			if (!regular || is_gzip(r.path)) { // a gzip file (or what the host parser will refuse in its own words)
+				info.host_files++;
+				const int rc = host_pass({ r }, starts ? starts + i : nullptr, nexts ? nexts + i : nullptr);
+				if (rc) {
+					return rc;
+				}
+				continue;
+			}
+			// the range's first record start as the host parser finds it, and where its last chunk ends: the first
+			// record start at or past `end` by the same rule
+			const uint64_t size = (uint64_t)sb.st_size;
+			uint64_t start = 0, stop = size;
+			std::string why;
+			if ((r.begin > 0 && !find_record_start(r.path, r.begin, &start, &why)) ||
+			    (r.end < size && r.end > 0 && !find_record_start(r.path, r.end, &stop, &why))) {
+				return pfail(ctx, NTEDIT_E_IO, why);
+			}
+			if (starts) {
+				starts[i] = start;
+			}
+			if (start >= r.end || start >= size) {
+				if (nexts) {
+					nexts[i] = start; // no record starts in the range
+				}
+				continue;
+			}
+			uint64_t handed_back = WHOLE; // where an unclean chunk started
+			{
+				RawFeeder feed(r.path, start, stop, (size_t)batch_bytes);
+				RawChunk* cur = feed.take();
+				int which = 0;
+				if (!cur) {
+					return pfail(ctx, NTEDIT_E_IO, feed.error());
+				}
+				if (nte_reads::parse_copy_begin(ctx, which, cur->p, cur->len) != 0) {
+					return NTEDIT_E_DEVICE;
+				}
+				while (cur) {
+					// the copy of chunk i + 1 runs while chunk i is parsed and counted
+					RawChunk* next = nullptr;
+					if (!cur->last) {
+						if (!(next = feed.take())) {
+							(void)nte_reads::parse_copy_wait(ctx, which);
+							return pfail(ctx, NTEDIT_E_IO, feed.error());
+						}
+						if (nte_reads::parse_copy_begin(ctx, which ^ 1, next->p, next->len) != 0) {
+							(void)nte_reads::parse_copy_wait(ctx, which);
+							return NTEDIT_E_DEVICE;
+						}
+					}
+					const auto g0 = std::chrono::steady_clock::now();
+					const char* text = nullptr;
+					ntedit_hip_reads_parse_result res;
+					int rc = nte_reads::parse_copied(ctx, which, cur->len, k, &text, &res);
+					const uint64_t off = cur->off, len = cur->len;
+					feed.give_back(cur); // (its copy is done: the reader may fill it again)
+					if (rc == 0 && res.clean && res.text_len) {
+						rc = run_batch(text, res.text_len, NTEDIT_HIP_BASES_DEVICE);
+					}
+					if (rc) {
+						(void)nte_reads::parse_copy_wait(ctx, which ^ 1);
+						return pfail(ctx, rc, ntedit_hip_reads_last_error(ctx));
+					}
+					gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
+					if (!res.clean) {
+						info.fallback_chunks++;
+						info.broken |= res.broken;
+						handed_back = off;
+						(void)nte_reads::parse_copy_wait(ctx, which ^ 1); // (before the feeder frees the buffer it reads)
+						break;
+					}
+					info.device_chunks++;
+					info.raw_bytes += len;
+					info.text_bytes += res.text_len;
+					bases += res.bases;
+					cur = next;
+					which ^= 1;
+				}
+			}
+			if (handed_back != WHOLE) {
+				// the rest of the range, from that chunk's first byte, with kseq's rules
+				Range rest = r;
+				rest.begin = handed_back;
+				rest.exact = true;
+				const int rc = host_pass({ rest }, nullptr, nexts ? nexts + i : nullptr);
+				if (rc) {
+					return rc;
+				}
+			} else if (nexts) {
+				nexts[i] = stop;
 			}
 		}
 	}
@@ -505,7 +855,8 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 	ntedit_hip_reads_pass_stats& st = r->pass[pass];
 	std::string what;
 	int rc;
-	if (pass != NTEDIT_READS_PASS_COUNT && r->store_state == NTEDIT_RESIDENT_ON) {
+	const bool read_files = pass == NTEDIT_READS_PASS_COUNT || r->store_state != NTEDIT_RESIDENT_ON;
+	if (!read_files) {
 		const auto t0 = std::chrono::steady_clock::now();
 		rc = pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_resident_histogram(ctx)
 		                                    : ntedit_hip_resident_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, r->cmin);
@@ -527,6 +878,32 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 	         (unsigned long long)st.bases, st.ms_wall, st.ms_wall > 0 ? st.bases / st.ms_wall / 1e6 : 0.0, st.ms_gpu,
 	         st.ms_gpu > 0 ? st.bases / st.ms_gpu / 1e6 : 0.0);
 	lg.rank_info(lg.ranged() ? line + (", " + what) : line);
+	ntedit_hip_reads_parse_stats ps;
+	if (a->device_parse && read_files && ntedit_hip_reads_parse_info(ctx, &ps) == 0) {
+		// the pass's one line about --gpu_parse (the tests read it)
+		std::string l = "--gpu_parse: " + std::to_string(ps.device_chunks) + " chunks parsed on the device (" + std::to_string(ps.raw_bytes) +
+		                " raw bytes, " + std::to_string(ps.text_bytes) + " text bytes, ";
+		snprintf(line, sizeof line, "%.1f ms in the parse kernels)", ps.ms_kernels);
+		l += line;
+		if (ps.fallback_chunks) {
+			static const char* const rules[] = { "the first byte is neither '>' nor '@'", "a carriage return", "an empty line",
+				                                 "a sequence line that starts with '>', '+' or '@'", "FASTQ lines not a multiple of 4",
+				                                 "a FASTQ header without '@'", "a FASTQ line 3 without '+'",
+				                                 "a quality line not as long as its sequence", "more than one line per 8 bytes",
+				                                 "a chunk of 2 GiB or more" };
+			std::string whys;
+			for (int b = 0; b < 10; b++) {
+				if (ps.broken & (1u << b)) {
+					whys += (whys.empty() ? "" : "; ") + std::string(rules[b]);
+				}
+			}
+			l += ", " + std::to_string(ps.fallback_chunks) + " unclean chunks sent the rest of their ranges to the host parser (" + whys + ")";
+		}
+		if (ps.host_files) {
+			l += ", " + std::to_string(ps.host_files) + " gzip inputs stay with the host parser";
+		}
+		lg.rank_info(l);
+	}
 	return 0;
 }
 
@@ -550,6 +927,7 @@ ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_a
 	}
 	const BuildLog lg{ a };
 	*r = ntedit_hip_reads_build_result();
+	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
 	if (!lg.ranged() && ntedit_hip_sketch_alloc(ctx, a->sketch_counters, a->hash_num, a->k) != 0) {
 		return NTEDIT_E_DEVICE; // (the message is sketch_alloc's)
 	}
@@ -590,6 +968,7 @@ ntedit_hip_reads_stage_histogram(ntedit_hip_ctx* ctx, const ntedit_hip_reads_bui
 		return pfail(ctx, NTEDIT_E_ARG, "reads_stage_histogram: bad argument");
 	}
 	const BuildLog lg{ a };
+	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
 	lg.rank_info("Histogram pass: the k-mer histogram of the sketch's estimates");
 	if (build_pass(ctx, a, NTEDIT_READS_PASS_HIST, r, nullptr, nullptr) != 0) {
 		return NTEDIT_E_IO;
@@ -659,6 +1038,7 @@ ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_
 	} else if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, r->bf_bytes, a->hash_num, a->k) != 0) {
 		return pfail(ctx, NTEDIT_E_DEVICE, ntedit_hip_last_error(ctx));
 	}
+	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
 	lg.rank_info("Pass 2: inserting k-mers seen at least " + std::to_string(r->cmin) + " times");
 	const int rc = build_pass(ctx, a, NTEDIT_READS_PASS_SOLID, r, nullptr, nullptr);
 	ntedit_hip_sketch_free(ctx); // (the store with it)

@@ -33,11 +33,12 @@ BATCH_DEFAULT = _lib.READS_BATCH_DEFAULT
 RESIDENT_CAP_DEFAULT = _lib.READS_RESIDENT_CAP_DEFAULT  # the resident store's cap of `ntedit --reads`
 
 USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] "
-         "[--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [-o VAR] [-t VAR] "
-         "[--no-split] [--backend VAR]\n\n"
+         "[--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] "
+         "[-t VAR] [--no-split] [--backend VAR]\n\n"
          "ntedit-make-reads-bf on N processes (python -m torch.distributed.run --nproc-per-node N -m "
          "ntedit_amd.make_reads ...): the same flags, the same output bytes.\n"
          "  --no-split      read every input file whole (by one process); gzip files always are\n"
+         "  --gpu_parse     parse plain (not gzip) read files on the GPU: the host ships raw file bytes; same output\n"
          "  --backend       torch.distributed backend (default nccl = RCCL; gloo: N ranks may share a GPU)\n"
          "ntedit-make-reads-bf --help describes the other flags.\n")
 
@@ -50,13 +51,13 @@ def _is_option(a):
     return len(a) > 1 and a[0] == "-" and not a[1].isdigit()
 
 
-def check_options(dialect, given, final, reads=(), solid=False, hist=""):
+def check_options(dialect, given, final, reads=(), solid=False, hist="", gpu_parse=False):
     """The library's reads-option rules (ntedit_hip_reads_options_check) over the option texts given so far (name ->
     text).  final: every rule, and the argument dict of build_rank; else only what is refused at the option itself.
     Refused with the library's message; the tool's "would be empty" is kept in the dict for sizes() to refuse."""
     lib = _lib.load()
     files = (ctypes.c_char_p * max(1, len(reads)))(*[os.fsencode(f) for f in reads])
-    o = _lib.ReadsOptions(solid=solid, hist=bool(hist), files=files, n_files=len(reads),
+    o = _lib.ReadsOptions(solid=solid, hist=bool(hist), files=files, n_files=len(reads), gpu_parse=bool(gpu_parse),
                           **{name: os.fsencode(text) for name, text in given.items()})
     r = _lib.ReadsRules()
     rc = lib.ntedit_hip_reads_options_check(o, dialect, int(final), r)
@@ -67,7 +68,8 @@ def check_options(dialect, given, final, reads=(), solid=False, hist=""):
                 hashes=r.hash_num, fpr=r.fpr, bf=r.bf_bytes if "bf" in given else None,
                 num_elements=r.num_elements if "num_elements" in given else None, sketch_bytes=r.sketch_bytes,
                 batch_bytes=r.batch_bytes, store_cap=r.store_cap, threads=r.threads, gather_hist=bool(r.gather_hist),
-                size_from_hist=bool(r.size_from_hist), bf_bytes=r.bf_bytes, sketch=r.sketch_counters, empty=why)
+                size_from_hist=bool(r.size_from_hist), bf_bytes=r.bf_bytes, sketch=r.sketch_counters, empty=why,
+                gpu_parse=bool(r.gpu_parse))
 
 
 def parse(argv):
@@ -76,7 +78,7 @@ def parse(argv):
              "--num_elements": "num_elements", "--sketch_bytes": "sketch_bytes", "-t": "threads",
              "--batch_bytes": "batch_bytes"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
     own = dict(counts=False, out="", no_split=False, backend=None, help=False)
-    given, reads, solid, hist = {}, [], False, ""
+    given, reads, solid, hist, gpu_parse = {}, [], False, "", False
     i = 0
     while i < len(argv):
         x = argv[i]
@@ -101,6 +103,8 @@ def parse(argv):
             solid = True
         elif x == "--hist":
             hist = value("--hist")
+        elif x == "--gpu_parse":
+            gpu_parse = True
         elif x == "--counts":
             own["counts"] = True
         elif x == "-o":
@@ -114,7 +118,7 @@ def parse(argv):
         i += 1
     if not reads:
         raise Refused("--reads: 1 or more argument(s) expected. 0 provided.")
-    a = dict(check_options(_lib.READS_DIALECT_TOOL, given, True, reads, solid, hist), **own)
+    a = dict(check_options(_lib.READS_DIALECT_TOOL, given, True, reads, solid, hist, gpu_parse), **own)
     if not a["out"]:
         a["out"] = "reads_k%d.bf" % a["k"]
     return a
@@ -329,8 +333,17 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         begins=u64s(*[u.begin for u in mine]), ends=u64s(*[u.end for u in mine]), rank=rank, world=world, k=a["k"],
         hash_num=a["hashes"], cmin=a["cmin"] or 0, solid=a["solid"], counts=a["counts"], bf_bytes=bf, fpr=a["fpr"],
         batch_bytes=a["batch_bytes"], hist_path=a["hist"].encode() or None, use_store=use_store, store_cap=store_cap,
-        log=_log_line)
+        log=_log_line, device_parse=bool(a.get("gpu_parse")))
     res = _lib.ReadsBuildResult()
+    parsed = {}
+
+    def note_parse(key):
+        # --gpu_parse: what the pass that just ran parsed where (ntedit_hip_reads_parse_info: the last pass)
+        st = _lib.ReadsParseStats()
+        if a.get("gpu_parse") and lib.ntedit_hip_reads_parse_info(b.h, st) == 0:
+            parsed[key] = dict(device_chunks=st.device_chunks, fallback_chunks=st.fallback_chunks,
+                               raw_bytes=st.raw_bytes, text_bytes=st.text_bytes, kernel_ms=round(st.ms_kernels, 3),
+                               broken=st.broken, host_files=st.host_files)
     try:
         k, hashes = a["k"], a["hashes"]
         counters = (sketch + 7) // 8 * 8
@@ -340,6 +353,7 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
             b.fail("sketch")
         if lib.ntedit_hip_reads_stage_count(b.h, args, res, starts, nexts) != 0:
             b.fail("pass 1 (count)")
+        note_parse("1")
         cut = [(u.file, u.begin, starts[i], nexts[i]) for i, u in enumerate(mine)]
         brk = check_cuts([c for part in b.all_gather_object(cut) for c in part])
         if brk is not None:
@@ -354,6 +368,8 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
             occ = np.zeros(256, dtype=np.uint64)
             if lib.ntedit_hip_reads_stage_histogram(b.h, args, res, occ.ctypes.data) != 0:
                 b.fail("pass H (histogram)")
+            if res.store_state != _lib.RESIDENT_ON:
+                note_parse("H")
             occ = b.all_reduce_hist(occ)
         rc = lib.ntedit_hip_reads_stage_decide(args, None if occ is None else occ.ctypes.data, res)
         if rc != 0:
@@ -365,6 +381,8 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         pol.set_filter_device(out.data_ptr(), nbytes, hashes, k, slot=slot, counting=a["counts"])
         if lib.ntedit_hip_reads_stage_insert(b.h, args, res) != 0:  # (it frees the sketch, and the store with it)
             b.fail("pass 2 (solid k-mers)")
+        if res.store_state != _lib.RESIDENT_ON:
+            note_parse("2")
         del sk
         b.merge(out, _lib.MERGE_MAX if a["counts"] else _lib.MERGE_OR)
     finally:
@@ -377,6 +395,8 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
                                    fallback=use_store and not on),
                cmin=res.cmin, filter_bytes=nbytes, passes=passes, exchanges=b.exchanges, exchange_bytes=b.xbytes,
                exchange_ms=round(b.xsec * 1e3, 3))
+    if a.get("gpu_parse"):
+        rep["parse"] = parsed
     return out, rep
 
 

@@ -223,7 +223,8 @@ class HipBackend:
 READS_OPTIONS = [("--cutoff", "cutoff"), ("--solid", "solid"), ("--counts", "counts"), ("--hashes", "hashes"),
                  ("--fpr", "fpr"), ("--bf", "bf_bytes"), ("--num_elements", "num_elements"),
                  ("--sketch_bytes", "sketch_bytes"), ("--hist", "hist"), ("--save_bf", "save_bf"),
-                 ("--batch_bytes", "batch_bytes"), ("--resident_cap", "resident_cap"), ("--no-split", "no_split")]
+                 ("--batch_bytes", "batch_bytes"), ("--resident_cap", "resident_cap"), ("--no-split", "no_split"),
+                 ("--gpu_parse", "gpu_parse")]
 
 
 def parse(argv=None):
@@ -272,6 +273,8 @@ def parse(argv=None):
                                                      "default prefix [reads_k<K>.bf, not written]")
     g.add_argument("--no-split", dest="no_split", action="store_true",
                    help="read every input file whole (by one rank); gzip files always are")
+    g.add_argument("--gpu_parse", action="store_true",
+                   help="parse plain (not gzip) read files on the GPU: the host ships raw file bytes; same outputs")
     g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
     g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
     args = ap.parse_args(argv)
@@ -294,7 +297,8 @@ def reads_args(args):
              (("k", "k_ignored"), ("cutoff", "cutoff"), ("hashes", "hashes"), ("fpr", "fpr"), ("bf", "bf_bytes"),
               ("num_elements", "num_elements"), ("sketch_bytes", "sketch_bytes"), ("batch_bytes", "batch_bytes"),
               ("store_cap", "resident_cap")) if getattr(args, dest) is not None}
-    a = make_reads.check_options(_lib.READS_DIALECT_POLISHER, given, True, args.reads, args.solid, args.hist or "")
+    a = make_reads.check_options(_lib.READS_DIALECT_POLISHER, given, True, args.reads, args.solid, args.hist or "",
+                                 args.gpu_parse)
     a.update(counts=args.counts, no_split=args.no_split)
     for path in [args.draft] + a["reads"]:
         try:
