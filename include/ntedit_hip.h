@@ -682,7 +682,12 @@ void ntedit_hip_fasta_free(ntedit_hip_fasta* f);
  *               partitioned screening), "bin_cap_percent" (record-run capacity in percent of the expectation: forces the
  *               overflow list), "bin_ovf_cap" (entries of the overflow list: forces a list that runs out, i.e. record chunks
  *               screened again by the direct kernel), "bin_fallback" (1: the direct kernel, like "screen_mode" 1), "bin_scatter"
- *               (1: the barrier-free partition kernel, kept as the second implementation the tests compare),
+ *               (1: the barrier-free partition kernel, kept as the second implementation the tests compare; 1024 slices at
+ *               most), "bin_slice_log2" (log2 of the slots of a filter slice instead of 2 MiB's, doubled until the partition
+ *               kernel has rings for every slice: many slices of a small filter), "bin_ring" (the default partition kernel:
+ *               8 = its 2048-slice layout with rings of 8 slots whatever the number of slices, 16 = only its 1024-slice layout),
+ *               "bin_wide_min_run" (records a (slice, workgroup) pair must expect before a filter is cut into more than 1024
+ *               slices; 0: 4096),
  *               "force_xcc" (x + 1: the probe stage behaves as if every wavefront ran on XCD x), "bin_timing",
  *               "candmap" (1: with -s 1 on a plain filter the first probes of every position's substitution candidates go
  *               through the partitioned pipeline before k_assess; exact, measured slower, off), "h2d_fixed_schedule" (1: a

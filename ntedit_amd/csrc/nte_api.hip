@@ -133,6 +133,9 @@ struct ntedit_hip_ctx
 		u32 force_rounds = 0;     // event rounds whatever the number of events (tests: small inputs)
 		u32 bin_scatter = 0;      // partition kernel: 0 barrier-phased (k_wc_scatter_b), 1 barrier-free (k_wc_scatter)
 		u32 probe_parts_log2 = ~0u; // probe stage: slices probed in 2^x parts (~0: by slice size)
+		u32 bin_slice_log2 = 0;   // log2 of the slots of a filter slice (0: 2 MiB), doubled until the partition kernel has rings for all slices (tests: many slices of a small filter)
+		u32 bin_wide_min_run = 0; // records a (slice, workgroup) pair must expect for more than 1024 slices (0: WCB_WIDE_MIN_RUN; tests: both sides of the rule on a small batch)
+		u32 bin_ring = 0;         // k_wc_scatter_b: 8 = the wide layout (8-slot rings) whatever the slices, 16 = never (1024 slices at most), 0: wide beyond 1024 slices
 	} tune;
 	DevBuf ev_cover, ev_before, ev_flags, ev_list, ev_bmax; // event rounds
 	u32 cu_count = 256;

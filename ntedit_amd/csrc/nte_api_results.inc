@@ -530,6 +530,12 @@ ntedit_hip_set_tuning(ntedit_hip_ctx* c, const char* key, uint64_t value)
 		t.bin_scatter = (u32)value;
 	} else if (k == "probe_parts_log2") {
 		t.probe_parts_log2 = (u32)value;
+	} else if (k == "bin_slice_log2") {
+		t.bin_slice_log2 = (u32)value;
+	} else if (k == "bin_wide_min_run") {
+		t.bin_wide_min_run = (u32)value;
+	} else if (k == "bin_ring") {
+		t.bin_ring = (u32)value;
 	} else if (k == "bin_fallback") {
 		t.bin_fallback = value != 0;
 	} else if (k == "bin_ovf_cap") {

@@ -94,21 +94,53 @@ launch_screen(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u64* d
 // fabric's ~51 G requests/s) and the batch is large enough to fill the persistent partition kernel.
 // slices of the partitioned pipeline for filter f and a batch of n positions (bits_per_pos: 1 for the screening, 4 for the
 // candidate map of -s 1); false: beyond what the record format / the LDS can do
+// slices the partition kernel that will run has rings for: the barrier-phased kernel of the screening takes 2048 in its
+// wide layout; the barrier-free kernel ("bin_scatter" 1), the candidate map and a forced 16-slot ring ("bin_ring" 16) 1024
+u32
+wc_max_slices(const ntedit_hip_ctx* c, bool gate)
+{
+	return gate || c->tune.bin_scatter == 1 || c->tune.bin_ring == 16 ? (u32)WC_MAX_SLICES : (u32)WCB_WIDE_SLICES;
+}
+
+// k_wc_scatter_b's wide layout (8-slot rings, 32-bit state words): beyond 1024 slices, or when asked for ("bin_ring" 8)
+bool
+wc_wide(const ntedit_hip_ctx* c, u32 n_slices, bool gate)
+{
+	return !gate && c->tune.bin_scatter != 1 && c->tune.bin_ring != 16 && (n_slices > (u32)WC_MAX_SLICES || c->tune.bin_ring == 8);
+}
+
 bool
 binned_geometry(const ntedit_hip_ctx* c, const Filter& f, u64 n, u32 bits_per_pos, u32* slice_log2, u32* n_slices)
 {
 	if (f.hash_num == 0) {
 		return false;
 	}
-	// slices of 2 MiB of filter (2^24 bit slots, 2^21 counters) while it has at most WC_MAX_SLICES of them, 4 MiB up to
-	// 4 GiB; beyond that the slices outgrow an XCD's L2 and the probe stage walks them in parts of 4 MiB (probe_parts_log2)
+	// slices of 2 MiB of filter (2^24 bit slots, 2^21 counters) while the partition kernel has rings for all of them -- up
+	// to 4 GiB with the default kernel: half of an XCD's L2 for the slice, the rest for its record stream and the bitmap --;
+	// beyond that the slices double until they are few enough, and the probe stage walks those beyond 4 MiB in parts of 4 MiB
+	// (probe_parts_log2)
+	const bool gate = bits_per_pos != 1;
+	u64 max_slices = wc_max_slices(c, gate);
+	// (More than 1,024 slices pay when the runs are long.  Measured at a 4 GiB filter, h = 3: 3 Gbp, runs of 17 k records,
+	// 127 -> 122 ms per step; 375 Mbp, 2.1 k, no difference; 250 Mbp of counters, 1.4 k, 42.9 -> 43.5: the probe stage walks a
+	// run in steps of 512 records and every slice switch has a fixed cost.  Below 4 k records per run: the 1,024 of before.)
+	const u64 min_run = c->tune.bin_wide_min_run ? c->tune.bin_wide_min_run : WCB_WIDE_MIN_RUN;
+	if (!c->tune.bin_slice_log2 && c->tune.bin_ring != 8 && n * f.hash_num < min_run * WCB_WIDE_SLICES * c->cu_count &&
+	    max_slices > (u64)WC_MAX_SLICES) {
+		max_slices = WC_MAX_SLICES;
+	}
 	u32 slog = f.counting ? 21 : 24;
+	if (c->tune.bin_slice_log2) { // tests: many slices of a small filter
+		slog = c->tune.bin_slice_log2 < 8 ? 8 : (c->tune.bin_slice_log2 < 30 ? c->tune.bin_slice_log2 : 30);
+	}
 	u64 ns = (f.bits + (1ULL << slog) - 1) >> slog;
-	while (ns > (u64)WC_MAX_SLICES) {
+	while (ns > max_slices) {
 		slog++;
 		ns = (f.bits + (1ULL << slog) - 1) >> slog;
 	}
-	if (slog > (f.counting ? 27u : 30u) || n * bits_per_pos >= (1ULL << (63 - slog)) || wc_lds_bytes(c->dp.k) + 1024 > c->lds_per_block) {
+	// (the LDS of the kernel that will run: k_wc_scatter's grows with k, k_wc_scatter_b's holds the codes of any k)
+	const size_t lds = c->tune.bin_scatter == 1 && !gate ? wc_lds_bytes(c->dp.k) + 1024 : WCB_LDS_BYTES + WCB_LDS_STATIC;
+	if (slog > (f.counting ? 27u : 30u) || n * bits_per_pos >= (1ULL << (63 - slog)) || lds > c->lds_per_block) {
 		return false; // (beyond 128 GiB of filter: the direct kernel)
 	}
 	*slice_log2 = slog;
@@ -238,7 +270,7 @@ struct WcPlan
 };
 
 WcPlan
-plan_wc(const ntedit_hip_ctx* c, u64 kmers, u32 hash_num, u32 n_slices)
+plan_wc(const ntedit_hip_ctx* c, u64 kmers, u32 hash_num, u32 n_slices, bool gate = false)
 {
 	WcPlan w;
 	w.n_wtiles = (kmers + WC_WTILE - 1) / WC_WTILE;
@@ -263,7 +295,7 @@ plan_wc(const ntedit_hip_ctx* c, u64 kmers, u32 hash_num, u32 n_slices)
 		cap = mean * c->tune.bin_cap_percent / 100.0 + 8.0; // tests: force the overflow path
 	}
 	u64 capi = ((u64)cap + WC_GROUP - 1) / WC_GROUP * WC_GROUP;
-	const u64 max_run = c->tune.bin_scatter == 1 ? WC_MAX_RUN : WCB_MAX_RUN;
+	const u64 max_run = gate ? WCB_MAX_RUN : c->tune.bin_scatter == 1 ? WC_MAX_RUN : wc_wide(c, n_slices, false) ? WCB_WIDE_MAX_RUN : WCB_MAX_RUN;
 	w.short_runs = !c->tune.bin_cap_percent && capi > max_run;
 	if (capi > max_run) {
 		capi = max_run; // (what does not fit goes through the overflow list)
@@ -288,12 +320,21 @@ template<int H, bool POW2>
 int
 launch_wc(ntedit_hip_ctx* c, hipStream_t stream, const WcArgs& w)
 {
+	// (the rings of the kernel that runs must cover the slices: binned_geometry and this agree on the kernel)
+	const bool wide = wc_wide(c, w.b.n_slices, false);
+	if (w.b.n_slices > (wide ? (u32)WCB_WIDE_SLICES : (u32)WC_MAX_SLICES)) {
+		return fail(c, NTEDIT_E_ARG, "binned screening: %u slices are more than the partition kernel has rings for", w.b.n_slices);
+	}
 	// (per device: the attribute belongs to the function ON the current device)
 	if (c->tune.bin_scatter == 1) {
 		const size_t lds = wc_lds_bytes(w.b.p.k);
 		HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wc_scatter<H, POW2>),
 		                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 		hipLaunchKernelGGL((k_wc_scatter<H, POW2>), dim3(w.n_wg), dim3(WC_TPB), lds, stream, w);
+	} else if (wide) {
+		HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wc_scatter_b<H, POW2, 0, true>),
+		                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)WCB_LDS_BYTES));
+		hipLaunchKernelGGL((k_wc_scatter_b<H, POW2, 0, true>), dim3(w.n_wg), dim3(WCB_TPB), WCB_LDS_BYTES, stream, w);
 	} else {
 		HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wc_scatter_b<H, POW2>),
 		                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)WCB_LDS_BYTES));
@@ -357,7 +398,7 @@ binned_buffers(ntedit_hip_ctx* c, const Filter& f, u64 span, u32 n_slices, u32 p
 			room = (u64)(free_b + c->bin_records.cap + c->bin_ovf.cap) / 5 * 2;
 		}
 		auto bytes_of = [&](u64 kmers, bool* short_runs) {
-			const WcPlan pl = plan_wc(c, kmers, hn, n_slices);
+			const WcPlan pl = plan_wc(c, kmers, hn, n_slices, records_per_kmer != 0);
 			*short_runs = pl.short_runs;
 			return pl.record_bytes + (u64)ovf_capacity(c, kmers, hn) * sizeof(WcOvf);
 		};
@@ -380,7 +421,7 @@ binned_buffers(ntedit_hip_ctx* c, const Filter& f, u64 span, u32 n_slices, u32 p
 			chunk = v;
 		}
 	}
-	const WcPlan plan0 = plan_wc(c, span < chunk ? span : chunk, hn, n_slices);
+	const WcPlan plan0 = plan_wc(c, span < chunk ? span : chunk, hn, n_slices, records_per_kmer != 0);
 	const size_t ctl_words = CTL_WORK + ((size_t)n_slices << plog) + 1;
 	int rc;
 	if (!c->bin_state.p) {
@@ -510,7 +551,7 @@ run_screen_binned(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u6
 			HIP_TRY(c, hipEventCreate(&e));
 			c->bin_ev.push_back(e);
 		}
-		const WcPlan plan = plan_wc(c, end - begin, hn, n_slices);
+		const WcPlan plan = plan_wc(c, end - begin, hn, n_slices, gate);
 		// (the buffer was sized for the largest chunk; a chunk gets what its own size asks for)
 		u32 ovf_cap = ovf_capacity(c, end - begin, hn);
 		if ((u64)ovf_cap * sizeof(WcOvf) > c->bin_ovf.cap) {
@@ -595,8 +636,8 @@ run_screen_binned(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u6
 			(void)hipEventElapsedTime(&t_probe, tev[2], tev[3]);
 			u32 ovf_n = 0;
 			(void)hipMemcpy(&ovf_n, d_ovf_count, 4, hipMemcpyDeviceToHost);
-			fprintf(stderr, "[ntedit_hip] binned chunk %llu k-mers, %u slices of 2^%u bits probed in %u part(s), %u x %u-record runs per slice (%.2f GB), %u overflow records: partition %.3f ms, probe %.3f ms (stages timed alone)\n",
-			        (unsigned long long)(end - begin), n_slices, slog, 1u << plog, plan.n_wg, plan.cap, plan.record_bytes / 1e9, ovf_n, t_part, t_probe);
+			fprintf(stderr, "[ntedit_hip] binned chunk %llu k-mers, %u slices of 2^%u bits (rings of %u) probed in %u part(s), %u x %u-record runs per slice (%.2f GB), %u overflow records: partition %.3f ms, probe %.3f ms (stages timed alone)\n",
+			        (unsigned long long)(end - begin), n_slices, slog, c->tune.bin_scatter == 1 || !wc_wide(c, n_slices, gate) ? (u32)WC_CAP : (u32)WCB_WIDE_CAP, 1u << plog, plan.n_wg, plan.cap, plan.record_bytes / 1e9, ovf_n, t_part, t_probe);
 		}
 		begin = end;
 	}

@@ -33,7 +33,8 @@
 //                 another half, so no wavefront ever blocks another (progress: the oldest group of a half that
 //                 has not left can always be completed by the lanes that own its indices, and flushed).
 //   k_bin_probe   every XCD takes slices from a shared counter and walks the runs of its current
-//                 slice: the slice's 2-4 MiB of filter stay in that XCD's L2 (nte_kernels.hip).
+//                 slice: the slice's 2 MiB of filter (4 MiB parts of the slices of filters beyond 4 GiB) stay in that
+//                 XCD's L2 (nte_kernels.hip).
 //   k_ovf_probe   the overflow list, probed directly.
 //
 // Bit-exact by construction: the same hashes, the same records, only their order inside a slice
@@ -61,7 +62,10 @@ constexpr int WC_WTILE = 64 * WC_L;          // k-mer starts per wavefront tile
 constexpr int WC_GROUP = 8;                  // records per flushed group (64 bytes)
 constexpr int WC_CAP = NTE_WC_CAP;           // ring slots per slice (8 or 16)
 constexpr int WC_CARRY = NTE_WC_CARRY;       // completed groups a lane can hold until its next round
-constexpr int WC_MAX_SLICES = 1024;
+constexpr int WC_MAX_SLICES = 1024;           // slices of k_wc_scatter and of k_wc_scatter_b with rings of WC_CAP slots
+constexpr int WCB_WIDE_SLICES = 2048;         // slices of k_wc_scatter_b<.., WIDE>: rings of WCB_WIDE_CAP slots in the same LDS
+constexpr int WCB_WIDE_CAP = 8;
+constexpr u32 WCB_WIDE_MIN_RUN = 4096;        // records a (slice, workgroup) pair must expect for the host to cut a filter into more than WC_MAX_SLICES
 constexpr u64 WC_EMPTY = WC_EMPTY_REC;       // never a record: the position bits of a record are never all ones
 constexpr u64 WC_GEN = ~WC_REC_POS_MASK;     // generation bit of a ring slot; stays in the stored record
 static_assert(WC_L % 4 == 0 && (WC_R == 1 || WC_R == 2 || WC_R == 4), "rounds work on 32-bit words of 4 codes");
@@ -451,6 +455,9 @@ k_wc_scatter(WcArgs a)
 // A slice that gets more than a ring-full in one round (low-complexity sequence) stores the excess directly.  The
 // barriers make every slot of a group valid by construction: no generation bits, no waiting, no retries -- at the
 // price of 16 wavefronts marching in step.  Same records, same runs, same fill[] as k_wc_scatter.
+// WIDE: 2048 slices instead of 1024 in the same LDS (a 4 GiB filter in slices of 2 MiB, which leave half of an XCD's L2 to
+// the record stream and the bitmap atomics): rings of 8 slots -- a slice's ninth record of a round is stored directly, as
+// its seventeenth is otherwise -- and a 32-bit state word per slice (below).
 constexpr int WCB_TPB = 1024;
 constexpr int WCB_L = 16;                      // k-mer starts per thread per tile
 constexpr int WCB_TILE = WCB_TPB * WCB_L;      // = SCREEN_TILE
@@ -464,12 +471,36 @@ wcb_round(int h)
 {
 	return h <= 2 ? 2 : (h == 3 ? NTE_WCB_R3 : 1);
 }
-constexpr int WCB_MAX_TOKENS = WCB_TPB * 6 / WC_GROUP + 8; // (R x H <= 6)
+// tokens of a round: a group per 8 records on average (R x H <= 6: 768) + what the LDS has left -- with 2048 slices and
+// h = 5 the groups that complete in one round are 640 +- 21
+constexpr int WCB_MAX_TOKENS = WCB_TPB * 6 / WC_GROUP + 8 + 256;
 static_assert(WCB_TILE == SCREEN_TILE && WCB_TILE % WC_WTILE == 0, "tiles of the two partition kernels nest");
 constexpr size_t WCB_LDS_BYTES = WC_LDS_RING + (size_t)WC_MAX_SLICES * 8 + (size_t)WCB_MAX_TOKENS * 4 + SCREEN_LDS_BYTES;
-// a token: slice << 22 | first << 19 | index of the record that completed the group (< 2^19: WCB_MAX_RUN); first =
-// first lane of the group whose record is still in the ring (the ones below were stored directly)
-constexpr u32 WCB_MAX_RUN = (1u << 19) - 16;
+constexpr size_t WCB_LDS_STATIC = ((size_t)TAB_WORDS * 8 + 256 + 8 + 15) / 16 * 16; // s_tab, s_lut, s_ntok
+static_assert((size_t)WCB_WIDE_SLICES * WCB_WIDE_CAP * 8 == WC_LDS_RING && (size_t)WCB_WIDE_SLICES * 4 == (size_t)WC_MAX_SLICES * 8,
+              "the wide layout (8-slot rings, 32-bit state words) takes the LDS of the narrow one");
+// (SCREEN_LDS_BYTES holds the codes of k = SCREEN_MAXK: the worst case is the only case)
+static_assert(WCB_LDS_BYTES + WCB_LDS_STATIC + 1024 <= 160 * 1024, "k_wc_scatter_b: LDS of a CU, with 1 KiB to spare");
+// a token: slice | first << IDX | index of the record that completed the group (< 2^IDX: the run limit), slice above
+// them; first = first lane of the group whose record is still in the ring (the ones below were stored directly).
+// IDX = 19 with 10 slice bits, 18 with the 11 of the wide layout.
+constexpr u32
+wcb_idx_bits(bool wide)
+{
+	return wide ? 18u : 19u;
+}
+constexpr u32 WCB_MAX_RUN = (1u << wcb_idx_bits(false)) - 16;
+constexpr u32 WCB_WIDE_MAX_RUN = (1u << wcb_idx_bits(true)) - 16;
+static_assert(10 + 3 + wcb_idx_bits(false) <= 32 && 11 + 3 + wcb_idx_bits(true) <= 32 && WC_MAX_SLICES <= 1 << 10 && WCB_WIDE_SLICES <= 1 << 11,
+              "a token is one 32-bit word");
+// The wide layout's state word: tail in the low WCB_TAIL_BITS, head modulo 2^WCB_HEAD_BITS above it (a carry out of bit
+// 31 is lost, harmlessly).  A lane that draws an index >= cap takes its increment back, so the tail never passes cap + the
+// records of one round, however often a draft repeats a k-mer; the head trails the tail by at most a round's records + a
+// ring, so the tail and the head's low bits give the whole head.
+constexpr u32 WCB_TAIL_BITS = 19, WCB_HEAD_BITS = 32 - WCB_TAIL_BITS;
+constexpr u32 WCB_TAIL_MASK = (1u << WCB_TAIL_BITS) - 1, WCB_HEAD_MASK = (1u << WCB_HEAD_BITS) - 1;
+static_assert(WCB_WIDE_MAX_RUN + WCB_TPB * 6 < (1u << WCB_TAIL_BITS), "tail: a full run and one round of over-draws");
+static_assert(WCB_TPB * 6 + WCB_WIDE_CAP + WC_GROUP < (1u << WCB_HEAD_BITS), "head: tail - head within the modulus");
 
 // MODE 1 (round 6; -s 1 on a plain filter): instead of the H probes of every k-mer, the FIRST probe of the k-mers that the
 // three substitution candidates of a position make of it (the k-mer with its last base replaced, ntedit.cpp:1916-1934;
@@ -478,18 +509,22 @@ constexpr u32 WCB_MAX_RUN = (1u << 19) - 16;
 // screening's (record position = 4 * position + candidate, the probe stage ORs the bits that ARE set into the
 // candidate map), they cost an eighth of that; k_assess then probes on from the second hash for the candidates
 // that are left.  H = 3 records per position; positions whose last base is no A/C/G/T get all four bits (unknown).
-template<int H, bool POW2, int MODE = 0>
+template<int H, bool POW2, int MODE = 0, bool WIDE = false>
 __global__ __launch_bounds__(WCB_TPB) void
 k_wc_scatter_b(WcArgs a)
 {
 	static_assert(MODE == 0 || H == 3, "the candidate map: three candidates per position");
 	constexpr int R = wcb_round(H); // k-mer starts per thread and round
 	constexpr int N = R * H;        // records per thread and round
+	constexpr int CAP = WIDE ? WCB_WIDE_CAP : WC_CAP; // ring slots per slice
+	constexpr u32 IDX = wcb_idx_bits(WIDE);           // index bits of a token
 	extern __shared__ __attribute__((aligned(16))) u8 s_dyn[];
 	u64* s_ring = reinterpret_cast<u64*>(s_dyn);
 	// per slice, one 64-bit word: low half = tail (index the next record of this pair gets), high half = head
 	// (records of the run that are in memory).  One returning 64-bit LDS atomic hands a record both.
+	// WIDE: one 32-bit word, {head modulo 2^13, tail} (WCB_TAIL_BITS above), in the same place.
 	unsigned long long* s_state = reinterpret_cast<unsigned long long*>(s_dyn + WC_LDS_RING);
+	u32* s_state32 = reinterpret_cast<u32*>(s_dyn + WC_LDS_RING);
 	u32* s_tok = reinterpret_cast<u32*>(s_state + WC_MAX_SLICES);
 	u8* s_codes = reinterpret_cast<u8*>(s_tok + WCB_MAX_TOKENS);
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
@@ -508,7 +543,11 @@ k_wc_scatter_b(WcArgs a)
 		s_ntok[tid] = 0;
 	}
 	for (u32 b = tid; b < nsl; b += WCB_TPB) {
-		s_state[b] = 0;
+		if (WIDE) {
+			s_state32[b] = 0;
+		} else {
+			s_state[b] = 0;
+		}
 	}
 	__syncthreads();
 
@@ -598,9 +637,15 @@ k_wc_scatter_b(WcArgs a)
 			bool have[N];
 #pragma unroll
 			for (int x = 0; x < N; x++) {
-				const unsigned long long st = have0[x / H] ? atomicAdd(&s_state[bin[x]], 1ULL) : 0ULL;
-				G[x] = (u32)st;
-				hd[x] = (u32)(st >> 32);
+				if (WIDE) {
+					const u32 st = have0[x / H] ? atomicAdd(&s_state32[bin[x]], 1u) : 0u;
+					G[x] = st & WCB_TAIL_MASK;
+					hd[x] = G[x] - ((G[x] - (st >> WCB_TAIL_BITS)) & WCB_HEAD_MASK);
+				} else {
+					const unsigned long long st = have0[x / H] ? atomicAdd(&s_state[bin[x]], 1ULL) : 0ULL;
+					G[x] = (u32)st;
+					hd[x] = (u32)(st >> 32);
+				}
 				have[x] = have0[x / H] && G[x] < cap;
 			}
 			{
@@ -611,6 +656,9 @@ k_wc_scatter_b(WcArgs a)
 				for (int x = 0; x < N; x++) {
 					over[x] = have0[x / H] && G[x] >= cap;
 					any_over |= over[x];
+					if (WIDE && over[x]) {
+						atomicSub(&s_state32[bin[x]], 1u); // (the tail stays at cap + what is being drawn right now)
+					}
 				}
 				if (__any(any_over)) {
 #pragma unroll
@@ -625,11 +673,11 @@ k_wc_scatter_b(WcArgs a)
 #pragma unroll
 			for (int x = 0; x < N; x++) {
 				dend[x] = 0;
-				const u32 lim = (hd[x] & ~(u32)(WC_GROUP - 1)) + WC_CAP;
+				const u32 lim = (hd[x] & ~(u32)(WC_GROUP - 1)) + CAP;
 				const bool in_ring = have[x] && G[x] < lim;
 				u64* run = records + (u64)(bin[x] * n_wg + blockIdx.x) * cap;
 				if (in_ring) {
-					s_ring[(size_t)bin[x] * WC_CAP + (G[x] & (WC_CAP - 1))] = rec[x];
+					s_ring[(size_t)bin[x] * CAP + (G[x] & (CAP - 1))] = rec[x];
 				} else if (have[x]) {
 					// more than a ring-full for this slice in one round: straight to memory
 					run[G[x]] = rec[x];
@@ -651,7 +699,7 @@ k_wc_scatter_b(WcArgs a)
 					if ((tokm[x] >> lane_id) & 1) {
 						const u32 g0 = G[x] + 1 - WC_GROUP;
 						const u32 first = hd[x] > g0 ? hd[x] - g0 : 0;
-						s_tok[base_idx + (u32)__popcll(tokm[x] & ((1ULL << lane_id) - 1))] = (bin[x] << 22) | (first << 19) | G[x];
+						s_tok[base_idx + (u32)__popcll(tokm[x] & ((1ULL << lane_id) - 1))] = (bin[x] << (IDX + 3)) | (first << IDX) | G[x];
 					}
 					base_idx += (u32)__popcll(tokm[x]);
 				}
@@ -665,19 +713,27 @@ k_wc_scatter_b(WcArgs a)
 			const u32 lane = tid & (WC_GROUP - 1);
 			for (u32 w = tid / WC_GROUP; w < nt; w += WCB_TPB / WC_GROUP) {
 				const u32 t = s_tok[w];
-				const u32 tb = t >> 22, first = (t >> 19) & 7u;
-				const u32 Gi = ((t & 0x7FFFFu) & ~(u32)(WC_GROUP - 1)) + lane;
+				const u32 tb = t >> (IDX + 3), first = (t >> IDX) & 7u;
+				const u32 Gi = ((t & ((1u << IDX) - 1u)) & ~(u32)(WC_GROUP - 1)) + lane;
 				if (lane >= first) {
-					records[(u64)(tb * n_wg + blockIdx.x) * cap + Gi] = s_ring[(size_t)tb * WC_CAP + (Gi & (WC_CAP - 1))];
+					records[(u64)(tb * n_wg + blockIdx.x) * cap + Gi] = s_ring[(size_t)tb * CAP + (Gi & (CAP - 1))];
 				}
 				if (lane == 0) {
-					atomicAdd(&s_state[tb], (unsigned long long)(WC_GROUP - first) << 32);
+					if (WIDE) {
+						atomicAdd(&s_state32[tb], (u32)(WC_GROUP - first) << WCB_TAIL_BITS);
+					} else {
+						atomicAdd(&s_state[tb], (unsigned long long)(WC_GROUP - first) << 32);
+					}
 				}
 			}
 #pragma unroll
 			for (int x = 0; x < N; x++) {
 				if (dend[x]) {
-					atomicAdd(&s_state[bin[x]], 1ULL << 32);
+					if (WIDE) {
+						atomicAdd(&s_state32[bin[x]], 1u << WCB_TAIL_BITS);
+					} else {
+						atomicAdd(&s_state[bin[x]], 1ULL << 32);
+					}
 				}
 			}
 			lds_barrier();
@@ -689,17 +745,24 @@ k_wc_scatter_b(WcArgs a)
 	{
 		const u32 j = tid & (WC_GROUP - 1);
 		for (u32 b = tid / WC_GROUP; b < nsl; b += WCB_TPB / WC_GROUP) {
-			const unsigned long long st = s_state[b];
-			u32 tl = (u32)st;
-			const u32 hdm = (u32)(st >> 32); // everything below is in memory
+			u32 tl, hdm; // tail; head: everything below is in memory
+			if (WIDE) {
+				const u32 st = s_state32[b];
+				tl = st & WCB_TAIL_MASK; // (every over-draw has been taken back: <= cap)
+				hdm = tl - ((tl - (st >> WCB_TAIL_BITS)) & WCB_HEAD_MASK);
+			} else {
+				const unsigned long long st = s_state[b];
+				tl = (u32)st;
+				hdm = (u32)(st >> 32);
+			}
 			tl = tl < cap ? tl : cap;
 			u64* run = records + (u64)(b * n_wg + blockIdx.x) * cap;
 			const u32 g0 = hdm & ~(u32)(WC_GROUP - 1);
 #pragma unroll
-			for (int g = 0; g < WC_CAP / WC_GROUP + 1; g++) {
+			for (int g = 0; g < CAP / WC_GROUP + 1; g++) {
 				const u32 i = g0 + g * WC_GROUP + j;
 				if (i >= hdm && i < tl) {
-					run[i] = s_ring[(size_t)b * WC_CAP + (i & (WC_CAP - 1))];
+					run[i] = s_ring[(size_t)b * CAP + (i & (CAP - 1))];
 				}
 			}
 			const u32 end = (tl + WC_GROUP - 1) & ~(u32)(WC_GROUP - 1);

@@ -273,7 +273,8 @@ k_screen(
 // L2-resident by partitioning them by filter slice first:
 //   k_wc_scatter_b (default) / k_wc_scatter   (nte_bin_wc.inc) write-combining partition of the h probes of every
 //                  k-mer into {position, offset-in-slice} records, slice by slice, ONE pass over the draft
-//   k_bin_probe    every XCD walks slices one after the other: the slice's 2-4 MiB of filter stay in that XCD's L2
+//   k_bin_probe    every XCD walks slices one after the other: the slice's 2 MiB of filter (4 MiB: a filter beyond 2 GiB
+//                  under a batch too small for 2048 slices, binned_geometry) stay in that XCD's L2
 //                  while its records stream by; a zero bit ORs the k-mer's bit into the absent bitmap
 // Records are 8 bytes: (global k-mer position << slice_log2) | slot offset in slice.
 // Measured (MI355X, 3 Gbp, 4 GiB filter, h = 3): 94 ms against 176 ms for the direct kernel.
@@ -294,7 +295,9 @@ struct BinArgs
 	u64* records;    // runs of `cap` records, one per (slice, partition workgroup) pair
 };
 
-// Probe stage.  A slice's 2-4 MiB of filter fit the 4 MiB L2 of ONE XCD, so all workgroups of an XCD work on the
+// Probe stage.  A slice's 2 MiB of filter (4 MiB where the runs of 2048 slices would be short: binned_geometry) take half
+// of the 4 MiB L2 of ONE XCD (the other half serves the record stream
+// and the bitmap's atomics: a slice of 4 MiB lost a twelfth of its gathers to them), so all workgroups of an XCD work on the
 // same slice at the same time: a workgroup asks the hardware which XCD it runs on (HW_REG_XCC_ID) and draws
 // stretches of that XCD's CURRENT slice from the slice's counter, one 512-record step per wavefront.  Large
 // workgroups (16 wavefronts, two per CU) keep the draws rare (a counter that everybody on an XCD draws from serves
@@ -309,8 +312,9 @@ struct BinArgs
 // 1 = being claimed, s + 2 = slice s), [32 + s] records of slice s handed out so far.
 // A slice's records: n_wg runs of `cap` records; in the counter's coordinates every run takes capr = cap rounded up to
 // whole steps, so no step crosses runs.
-// Filters beyond 1024 x 4 MiB: the partition kernel has rings for 1024 slices (its LDS), so the slices grow past what
-// an XCD's L2 holds -- 8 MiB at 8 GiB, where half the gathers would miss.  Such a slice is probed in 2^plog PARTS of 4 MiB:
+// Filters beyond 2048 x 2 MiB: the partition kernel has rings for 2048 slices (its LDS), so the slices grow: 4 MiB up to
+// 8 GiB, then past what an XCD's L2 holds -- 8 MiB at 16 GiB, where half the gathers would miss.  Such a slice is probed in
+// 2^plog PARTS of 4 MiB:
 // the unit the XCDs claim is a (slice, part) pair, the slice's records stream by once per part and every pass probes the
 // records whose slot lies in its part (ctl[] then has one "slice" entry per pair).  Re-reading the records costs less than
 // missing the L2: 8 GiB 88 -> 6x ms, and a 16 GiB filter no longer falls back to the direct kernel (185 ms).

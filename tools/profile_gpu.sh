@@ -9,7 +9,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ARGS="${@:---bases 3e9 --steps 2 --warmup 1 --no-cpu-baseline --no-gather --no-regions --no-reserve}"  # (--no-reserve: its warm-up batch would count as a fourth, tiny launch of every kernel)
 # pass 1: kernel trace + stats (no counters)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $ROOT/bench.py $ARGS > $OUT/trace_bench.json 2> $OUT/trace.err
+# (every run under a time limit of its own; a run that fails ends the script: nothing more is started on that device)
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $ROOT/bench.py $ARGS > $OUT/trace_bench.json 2> $OUT/trace.err || { echo "profile_gpu.sh: the traced run failed ($?)"; tail -5 $OUT/trace.err; exit 1; }
 find $OUT/trace -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 # pass 2..n: PMC counters, each in its own run (kernel-trace only, as the pool requires)
 i=0
@@ -17,7 +18,7 @@ for PMC in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" \
            "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --output-format csv --pmc $PMC -d $OUT/pmc$i -o pmc -- python $ROOT/bench.py $ARGS > /dev/null 2> $OUT/pmc$i.err
+  timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv --pmc $PMC -d $OUT/pmc$i -o pmc -- python $ROOT/bench.py $ARGS > /dev/null 2> $OUT/pmc$i.err || { echo "profile_gpu.sh: counter pass $i failed ($?)"; tail -5 $OUT/pmc$i.err; exit 1; }
   f=$(find $OUT/pmc$i -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then
     python - "$f" "$OUT/pmc_summary.txt" "$PMC" <<'PY'
