@@ -150,6 +150,16 @@ void ntedit_hip_sketch_free(ntedit_hip_ctx* ctx);
 /* a zeroed counting filter (one 8-bit counter per byte, nbytes rounded up to a multiple of 8) in a filter slot */
 int ntedit_hip_filter_alloc_counting(ntedit_hip_ctx* ctx, int slot, uint64_t nbytes, uint32_t hash_num, uint32_t k);
 int ntedit_hip_filter_insert_solid(ntedit_hip_ctx* ctx, int slot, const char* bases, uint64_t n, int on_device, uint32_t cmin);
+/* Pass 2 with a reject cutoff (the -e filter, "secondary BF with k-mers to reject", built from the same walk over the
+ * reads): one kernel, one est(x) per k-mer; a k-mer with est(x) >= cmin sets its bits in the PRIMARY filter, one with
+ * est(x) >= rmin also in the SECONDARY filter.  Both slots are checked as ntedit_hip_filter_insert_solid checks its
+ * one (set, k and hash_num of the sketch, on its device), both must be plain filters, and cmin < rmin <= 255.  Each
+ * filter ends with the bytes ntedit_hip_filter_insert_solid(slot, .., its threshold) over the same batches gives it.
+ *   ntedit_hip_reads_set_reject_cutoff: the context's setting that the SOLID pass of ntedit_hip_reads_pass follows: with
+ *           rmin > 0 it runs this call with (cmin, rmin) instead of ntedit_hip_filter_insert_solid.  0 turns it off.
+ *           The setting lives with the sketch (NTEDIT_E_ARG without one) and goes with it. */
+int ntedit_hip_filter_insert_solid2(ntedit_hip_ctx* ctx, const char* bases, uint64_t n, int on_device, uint32_t cmin, uint32_t rmin);
+int ntedit_hip_reads_set_reject_cutoff(ntedit_hip_ctx* ctx, uint32_t rmin);
 const char* ntedit_hip_reads_last_error(const ntedit_hip_ctx* ctx);
 /* k-mer histogram of the read set, from the sketch (after pass 1 over the same inputs; --solid / --hist of the tool):
  *   ntedit_hip_sketch_histogram takes batches exactly as ntedit_hip_sketch_count and adds 1 to bin est(x) of the
@@ -250,6 +260,7 @@ int ntedit_hip_resident_begin(ntedit_hip_ctx* ctx, uint64_t cap_bytes);
 int ntedit_hip_resident_info(ntedit_hip_ctx* ctx, ntedit_hip_resident_stats* st);
 int ntedit_hip_resident_histogram(ntedit_hip_ctx* ctx);
 int ntedit_hip_resident_insert_solid(ntedit_hip_ctx* ctx, int slot, uint32_t cmin);
+int ntedit_hip_resident_insert_solid2(ntedit_hip_ctx* ctx, uint32_t cmin, uint32_t rmin); /* as ntedit_hip_filter_insert_solid2, over the store */
 void ntedit_hip_resident_free(ntedit_hip_ctx* ctx);
 /* The whole filter build of ntedit-make-reads-bf, shared by it and `ntedit --reads`: the sketch (sketch_counters, as
  * sized by the caller), pass 1, with solid or hist_path the histogram pass (the --hist file, the --solid cutoff, and
@@ -274,7 +285,14 @@ void ntedit_hip_resident_free(ntedit_hip_ctx* ctx);
  *           histogram, and the refusals (NTEDIT_E_ARG; the message is ntedit_hip_reads_last_error(NULL)).  Only
  *           rank 0 writes --hist and logs; every rank reaches the same refusal.
  *   ntedit_hip_reads_stage_insert: the filter of res->bf_bytes, pass 2 with res->cmin from the store or over the
- *           ranges, the sketch and the store freed. */
+ *           ranges, the sketch and the store freed.
+ * With reject_cmin > 0 the build also makes the reject filter (ntedit -e) in the SECONDARY slot: a plain filter of the
+ * k-mers with est(x) >= reject_cmin, from the same pass 2 (ntedit_hip_filter_insert_solid2).  The sketch is sized from
+ * the primary output alone, so the primary filter's bytes are those of the build without it, and the reject filter's
+ * bytes are those of a build with cmin = reject_cmin, bf_bytes = its size and the same sketch.  stage_decide resolves
+ * its size (reject_bf_bytes as given, or from the histogram the k-mers at reject_cmin or above) into
+ * res->reject_bf_bytes and refuses reject_cmin <= res->cmin; stage_insert allocates it (a sharded build: the SECONDARY
+ * filter the caller adopted).  Not with `counts`. */
 typedef struct ntedit_hip_reads_build_args
 {
 	const char* const* files;
@@ -297,6 +315,9 @@ typedef struct ntedit_hip_reads_build_args
 	const uint64_t* ends;
 	uint32_t rank, world;
 	int device_parse;         /* --gpu_parse: plain files are parsed on the device (ntedit_hip_reads_parse_device) */
+	uint32_t reject_cmin;     /* --reject_cutoff; 0: no reject filter */
+	uint64_t reject_bf_bytes; /* --reject_bf, or from --reject_num_elements; 0: from the histogram (needs solid or hist_path) */
+	uint64_t reject_num_elements; /* as given (the parameter echo) */
 } ntedit_hip_reads_build_args;
 typedef struct ntedit_hip_reads_build_result
 {
@@ -307,6 +328,7 @@ typedef struct ntedit_hip_reads_build_result
 	uint64_t store_bytes;                 /* device bytes the store held after pass 1 */
 	double ms_total;
 	uint64_t store_batches;               /* batches it held after pass 1 */
+	uint64_t reject_bf_bytes;             /* the reject filter's size (0: none) */
 } ntedit_hip_reads_build_result;
 int ntedit_hip_reads_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res);
 int ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res,
@@ -321,7 +343,9 @@ int ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_bu
  * given so far are checked for what is refused at the option itself (a malformed number, --fpr), so that a front end
  * can ask while it walks its arguments; with final = 1 every rule, in that dialect's order: -k required and 12..200,
  * the cutoff xor --solid and 1..255, hashes 1..8, a size unless the histogram gives it, the filter would be empty,
- * batch_bytes >= 4096.  Returns 0 and the normalised arguments, or the first refusal: NTEDIT_READS_REFUSED,
+ * batch_bytes >= 4096, then the reject filter's: --reject_cutoff 2..255 and above the cutoff given, not with --counts, a
+ * size (--reject_bf or --reject_num_elements) unless the histogram gives it, no size without it, not empty.  (Under
+ * --solid "above the cutoff" waits for ntedit_hip_reads_stage_decide.)  Returns 0 and the normalised arguments, or the first refusal: NTEDIT_READS_REFUSED,
  * NTEDIT_READS_NOT_A_NUMBER (a malformed number), NTEDIT_READS_EMPTY (TOOL dialect: the filter would be empty; the
  * tool prints its parameters before it says so, and *out is filled), its message in ntedit_hip_reads_last_error(NULL). */
 #define NTEDIT_READS_DIALECT_TOOL 0
@@ -339,6 +363,9 @@ typedef struct ntedit_hip_reads_options
 	const char* const* files; /* for the default sketch */
 	uint32_t n_files;
 	int gpu_parse;
+	const char *reject_cutoff, *reject_bf, *reject_num_elements;
+	int counts;     /* --counts (refused with --reject_cutoff) */
+	int reject_out; /* an output option of the reject filter was given (--reject_out / --save_reject_bf) */
 } ntedit_hip_reads_options;
 typedef struct ntedit_hip_reads_rules
 {
@@ -351,6 +378,10 @@ typedef struct ntedit_hip_reads_rules
 	uint64_t batch_bytes, store_cap, threads;
 	int gather_hist, size_from_hist;
 	int gpu_parse;
+	uint32_t reject_cmin;          /* 0: no reject filter */
+	uint64_t reject_bf_bytes;      /* --reject_bf, or from --reject_num_elements; 0: sized from the histogram */
+	uint64_t reject_num_elements;
+	int reject_size_from_hist;
 } ntedit_hip_reads_rules;
 int ntedit_hip_reads_options_check(const ntedit_hip_reads_options* opts, int dialect, int final, ntedit_hip_reads_rules* out);
 /* --gpu_parse: plain (not gzip) read files parsed on the device.  The host ships raw file bytes, cut at record starts

@@ -90,14 +90,15 @@ class ReadsBuildArgs(ctypes.Structure):
                 ("sketch_path", ctypes.c_char_p), ("use_store", ctypes.c_int), ("store_cap", ctypes.c_uint64),
                 ("log", READS_LOG_FN), ("user", ctypes.c_void_p), ("begins", ctypes.POINTER(ctypes.c_uint64)),
                 ("ends", ctypes.POINTER(ctypes.c_uint64)), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32),
-                ("device_parse", ctypes.c_int)]
+                ("device_parse", ctypes.c_int), ("reject_cmin", ctypes.c_uint32), ("reject_bf_bytes", ctypes.c_uint64),
+                ("reject_num_elements", ctypes.c_uint64)]
 
 
 class ReadsBuildResult(ctypes.Structure):
     """ntedit_hip_reads_build_result"""
     _fields_ = [("cmin", ctypes.c_uint32), ("bf_bytes", ctypes.c_uint64), ("passes", ReadsPassStats * 3),
                 ("store_state", ctypes.c_int), ("store_bytes", ctypes.c_uint64), ("ms_total", ctypes.c_double),
-                ("store_batches", ctypes.c_uint64)]
+                ("store_batches", ctypes.c_uint64), ("reject_bf_bytes", ctypes.c_uint64)]
 
 
 # the reads-option rules (ntedit_hip_reads_options_check) and the header's defaults
@@ -106,13 +107,16 @@ READS_REFUSED, READS_NOT_A_NUMBER, READS_EMPTY = 1, 2, 3
 READS_BATCH_DEFAULT, READS_RESIDENT_CAP_DEFAULT, READS_GZIP_WEIGHT = 256 << 20, 48 << 30, 4
 READS_OPTION_TEXTS = ("k", "cutoff", "hashes", "fpr", "bf", "num_elements", "sketch_bytes", "batch_bytes", "store_cap",
                       "threads")
+READS_REJECT_OPTION_TEXTS = ("reject_cutoff", "reject_bf", "reject_num_elements")
 
 
 class ReadsOptions(ctypes.Structure):
     """ntedit_hip_reads_options"""
     _fields_ = ([(name, ctypes.c_char_p) for name in READS_OPTION_TEXTS] +
                 [("solid", ctypes.c_int), ("hist", ctypes.c_int), ("files", ctypes.POINTER(ctypes.c_char_p)),
-                 ("n_files", ctypes.c_uint32), ("gpu_parse", ctypes.c_int)])
+                 ("n_files", ctypes.c_uint32), ("gpu_parse", ctypes.c_int)] +
+                [(name, ctypes.c_char_p) for name in READS_REJECT_OPTION_TEXTS] +
+                [("counts", ctypes.c_int), ("reject_out", ctypes.c_int)])
 
 
 class ReadsRules(ctypes.Structure):
@@ -121,7 +125,9 @@ class ReadsRules(ctypes.Structure):
                 ("fpr", ctypes.c_double), ("bf_bytes", ctypes.c_uint64), ("num_elements", ctypes.c_uint64),
                 ("sketch_bytes", ctypes.c_uint64), ("sketch_counters", ctypes.c_uint64),
                 ("batch_bytes", ctypes.c_uint64), ("store_cap", ctypes.c_uint64), ("threads", ctypes.c_uint64),
-                ("gather_hist", ctypes.c_int), ("size_from_hist", ctypes.c_int), ("gpu_parse", ctypes.c_int)]
+                ("gather_hist", ctypes.c_int), ("size_from_hist", ctypes.c_int), ("gpu_parse", ctypes.c_int),
+                ("reject_cmin", ctypes.c_uint32), ("reject_bf_bytes", ctypes.c_uint64),
+                ("reject_num_elements", ctypes.c_uint64), ("reject_size_from_hist", ctypes.c_int)]
 
 
 # --gpu_parse (ntedit_hip_reads_parse_device / _model): the tile size and the rules of the clean grammar
@@ -203,8 +209,11 @@ EXPORTS = [
     "ntedit_hip_reads_stage_count", "ntedit_hip_reads_stage_histogram", "ntedit_hip_reads_stage_decide",
     "ntedit_hip_reads_stage_insert", "ntedit_hip_reads_options_check",
     "ntedit_hip_reads_parse_device", "ntedit_hip_reads_parse_model", "ntedit_hip_reads_set_device_parse",
-    "ntedit_hip_reads_parse_info",
+    "ntedit_hip_reads_parse_info", "ntedit_hip_reads_set_reject_cutoff",
 ]
+# ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
+# tests/test_abi.py makes one, does not see them)
+EXPORTS_NUMBERED = ["ntedit_hip_filter_insert_solid2", "ntedit_hip_resident_insert_solid2"]
 
 _lib = None
 
@@ -341,5 +350,9 @@ def load():
     lib.ntedit_hip_reads_parse_model.argtypes = [vp, u64, u32, vp, u64, pres]
     lib.ntedit_hip_reads_set_device_parse.argtypes = [vp, ci]
     lib.ntedit_hip_reads_parse_info.argtypes = [vp, ctypes.POINTER(ReadsParseStats)]
+    # the reject filter (ntedit -e) from the same pass 2
+    lib.ntedit_hip_filter_insert_solid2.argtypes = [vp, vp, u64, ci, u32, u32]
+    lib.ntedit_hip_resident_insert_solid2.argtypes = [vp, u32, u32]
+    lib.ntedit_hip_reads_set_reject_cutoff.argtypes = [vp, u32]
     _lib = lib
     return lib

@@ -5,11 +5,13 @@
 //   k_solid<H, POW2, COUNTS>  pass 2: est(x) = min of x's h sketch counters; a k-mer with est(x) >= cmin sets its h
 //                             bits in a plain output filter, or raises its h counters of a counting output filter to
 //                             est(x) (byte atomic max)
+//   k_solid2<H, POW2>         pass 2 with a reject cutoff: one walk, one est(x); a k-mer with est(x) >= cmin sets its bits
+//                             in the plain primary output, one with est(x) >= rmin also in the plain reject output (-e)
 //   k_hist<H, POW2>           histogram pass: bin est(x) of a 256-bin histogram of every k-mer occurrence, summed in
 //                             per-wave LDS sub-histograms and flushed once per block (one 64-bit add per non-zero bin)
 //   k_pack                    after k_count, when the context keeps the reads resident: a batch packed into the store,
 //                             per 16 bases one u32 of 2-bit codes and one u16 of validity bits (3 bits per base)
-//   k_hist / k_solid <.., PACKED = true>  the same passes staged from a stored batch instead of its bytes
+//   k_hist / k_solid / k_solid2 <.., PACKED = true>  the same passes staged from a stored batch instead of its bytes
 //   k_nonzero                 non-zero counters of the sketch (occupancy)
 //   k_merge<OP>               n_src equal byte chunks folded into one: saturating add (sketches), OR (plain filters),
 //                             max (counting filters) -- the merge of a sharded build
@@ -205,14 +207,31 @@ rd_est(const u8* sk_bytes, const Filter& f, const u64 (&hv)[H])
 	return est;
 }
 
-// ------------------------------------------------------------------ k_count / k_solid / k_hist
+// the h bits of one k-mer in a plain filter (k_solid2): a plain read first, the atomic only for a bit still unset
+template<int H>
+__device__ __forceinline__ void
+rd_set_bits(const RdFilter& out, const u64 (&hv)[H])
+{
+#pragma unroll
+	for (int i = 0; i < H; i++) {
+		const u64 s = filter_slot(out.f, hv[i]);
+		u32* w = out.words + (s >> 5);
+		const u32 bit = 1u << (s & 31);
+		if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) {
+			atomicOr(w, bit);
+		}
+	}
+}
+
+// ------------------------------------------------------------------ k_count / k_solid / k_solid2 / k_hist
 // One thread walks 64 consecutive k-mer starts of the tile.  The hash state is exact once k codes of ACGT have
 // entered since the last RD_BAD (an RD_BAD code has zero seeds both ways, so it leaves nothing behind).
-// PASS 0: k_count; 1: k_solid into bits; 2: k_solid into counters; 3: k_hist into s_hist (this wave's 256 bins)
+// PASS 0: k_count; 1: k_solid into bits; 2: k_solid into counters; 3: k_hist into s_hist (this wave's 256 bins);
+// 4: k_solid2 into the bits of out (est >= cmin) and of out2 (est >= rmin)
 template<int H, bool POW2, int PASS, bool PACKED = false>
 __device__ __forceinline__ void
 rd_walk(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __restrict__ tabs, const DevParams& p, RdFilter sk,
-        RdFilter out, u32 cmin, u32* s_hist)
+        RdFilter out, u32 cmin, u32* s_hist, RdFilter out2 = RdFilter{}, u32 rmin = 0)
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
@@ -243,6 +262,14 @@ rd_walk(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __rest
 				}
 			} else if (PASS == 3) {
 				atomicAdd(&s_hist[rd_est<H, POW2>(sk_bytes, sk.f, hv)], 1u);
+			} else if (PASS == 4) {
+				const u32 est = rd_est<H, POW2>(sk_bytes, sk.f, hv);
+				if (est >= cmin) {
+					rd_set_bits<H>(out, hv);
+				}
+				if (est >= rmin) {
+					rd_set_bits<H>(out2, hv);
+				}
 			} else {
 				const u32 est = rd_est<H, POW2>(sk_bytes, sk.f, hv);
 				if (est >= cmin) {
@@ -282,6 +309,16 @@ k_solid(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __rest
         RdFilter out, u32 cmin)
 {
 	rd_walk<H, POW2, COUNTS ? 2 : 1, PACKED>(seq, pk, n, k, tabs, p, sk, out, cmin, nullptr);
+}
+
+// Pass 2 with a reject cutoff: the staging, the hash roll and the h sketch gathers of est(x) -- what bounds k_solid --
+// happen once for both outputs; two k_solid launches would do all three twice.
+template<int H, bool POW2, bool PACKED>
+__global__ __launch_bounds__(RD_TPB) void
+k_solid2(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk,
+         RdFilter out, RdFilter out2, u32 cmin, u32 rmin)
+{
+	rd_walk<H, POW2, 4, PACKED>(seq, pk, n, k, tabs, p, sk, out, cmin, nullptr, out2, rmin);
 }
 
 // Occurrences crowd into a few bins near the coverage peak, so each wave adds into a sub-histogram of its own: a
@@ -464,6 +501,7 @@ struct ReadsState
 	std::vector<Stored> store;
 	u64 store_bytes = 0, store_cap = 0;
 	int store_state = NTEDIT_RESIDENT_OFF;
+	u32 reject_cmin = 0; // ntedit_hip_reads_set_reject_cutoff: the SOLID pass of ntedit_hip_reads_pass fills both slots
 	std::string err;
 };
 
@@ -600,7 +638,8 @@ stage(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int on_d
 
 template<bool POW2, int PASS, bool PACKED>
 void
-launch_walk(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, RdFilter sk, RdFilter out, u32 cmin)
+launch_walk(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, RdFilter sk, RdFilter out, u32 cmin, RdFilter out2,
+            u32 rmin)
 {
 	static_assert(!(PACKED && PASS == 0), "pass 1 reads bytes");
 	dim3 grid((unsigned)tiles), block(RD_TPB);
@@ -608,6 +647,9 @@ launch_walk(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, RdFil
 	case H:                                                                                                        \
 		if constexpr (PASS == 0) {                                                                                 \
 			hipLaunchKernelGGL((k_count<H, POW2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, s->dp, sk); \
+		} else if constexpr (PASS == 4) {                                                                          \
+			hipLaunchKernelGGL((k_solid2<H, POW2, PACKED>), grid, block, 0, s->stream, d_seq, pk, n, s->k, s->d_tab,  \
+			                   s->dp, sk, out, out2, cmin, rmin);                                                  \
 		} else if constexpr (PASS == 3) {                                                                          \
 			hipLaunchKernelGGL((k_hist<H, POW2, PACKED>), grid, block, 0, s->stream, d_seq, pk, n, s->k, s->d_tab, \
 			                   s->dp, sk, s->d_hist);                                                              \
@@ -642,22 +684,25 @@ sketch_view(const ReadsState* s)
 
 template<bool PACKED>
 void
-launch_pass(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, int pass, RdFilter out, u32 cmin)
+launch_pass(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, int pass, RdFilter out, u32 cmin, RdFilter out2, u32 rmin)
 {
 	const RdFilter sk = sketch_view(s);
 	const bool pow2 = sk.f.mask != 0;
 	if (pass == 1) {
-		pow2 ? launch_walk<true, 1, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin)
-		     : launch_walk<false, 1, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin);
+		pow2 ? launch_walk<true, 1, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
+		     : launch_walk<false, 1, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
 	} else if (pass == 2) {
-		pow2 ? launch_walk<true, 2, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin)
-		     : launch_walk<false, 2, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin);
+		pow2 ? launch_walk<true, 2, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
+		     : launch_walk<false, 2, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
+	} else if (pass == 4) {
+		pow2 ? launch_walk<true, 4, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
+		     : launch_walk<false, 4, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
 	} else if (pass == 3) {
-		pow2 ? launch_walk<true, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin)
-		     : launch_walk<false, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin);
+		pow2 ? launch_walk<true, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
+		     : launch_walk<false, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
 	} else if constexpr (!PACKED) {
-		pow2 ? launch_walk<true, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin)
-		     : launch_walk<false, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin);
+		pow2 ? launch_walk<true, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
+		     : launch_walk<false, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
 	}
 }
 
@@ -686,7 +731,8 @@ store_batch(ReadsState* s, const u8* d_seq, u64 n)
 }
 
 int
-run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int on_device, int pass, RdFilter out, u32 cmin)
+run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int on_device, int pass, RdFilter out, u32 cmin,
+         RdFilter out2 = RdFilter{}, u32 rmin = 0)
 {
 	RD_TRY(c, hipSetDevice(s->device));
 	if (n == 0) {
@@ -701,7 +747,7 @@ run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int o
 	if (rc) {
 		return rc;
 	}
-	launch_pass<false>(s, d_seq, RdPacked{}, n, tiles, pass, out, cmin);
+	launch_pass<false>(s, d_seq, RdPacked{}, n, tiles, pass, out, cmin, out2, rmin);
 	RD_TRY(c, hipGetLastError());
 	if (pass == 0 && s->store_state == NTEDIT_RESIDENT_ON) {
 		store_batch(s, d_seq, n);
@@ -713,7 +759,7 @@ run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int o
 
 // the histogram pass or pass 2 over every stored batch, each launched with its own n as it was counted
 int
-run_store_pass(const ntedit_hip_ctx* c, ReadsState* s, int pass, RdFilter out, u32 cmin)
+run_store_pass(const ntedit_hip_ctx* c, ReadsState* s, int pass, RdFilter out, u32 cmin, RdFilter out2 = RdFilter{}, u32 rmin = 0)
 {
 	RD_TRY(c, hipSetDevice(s->device));
 	if (s->store_state != NTEDIT_RESIDENT_ON) {
@@ -721,7 +767,7 @@ run_store_pass(const ntedit_hip_ctx* c, ReadsState* s, int pass, RdFilter out, u
 	}
 	for (const ReadsState::Stored& b : s->store) {
 		const u64 tiles = (b.n + RD_TILE - 1) / RD_TILE;
-		launch_pass<true>(s, nullptr, stored_view(b), b.n, tiles, pass, out, cmin);
+		launch_pass<true>(s, nullptr, stored_view(b), b.n, tiles, pass, out, cmin, out2, rmin);
 		RD_TRY(c, hipGetLastError());
 	}
 	RD_TRY(c, hipStreamSynchronize(s->stream));
@@ -756,6 +802,27 @@ solid_target(const ntedit_hip_ctx* c, const ReadsState* s, int slot, u32 cmin, c
 	return 0;
 }
 
+// both outputs of pass 2 with a reject cutoff: PRIMARY takes cmin, SECONDARY (a plain filter) rmin
+int
+solid2_targets(const ntedit_hip_ctx* c, const ReadsState* s, u32 cmin, u32 rmin, const char* what, RdFilter* out, RdFilter* out2)
+{
+	if (!(cmin < rmin && rmin <= 255)) {
+		return rfail(c, NTEDIT_E_ARG, "%s: cmin = %u, rmin = %u: needs cmin < rmin <= 255", what, cmin, rmin);
+	}
+	int rc = solid_target(c, s, NTEDIT_FILTER_PRIMARY, cmin, what, out);
+	if (rc == 0) {
+		rc = solid_target(c, s, NTEDIT_FILTER_SECONDARY, rmin, what, out2);
+	}
+	if (rc) {
+		return rc;
+	}
+	if (out->f.counting || out2->f.counting) {
+		return rfail(c, NTEDIT_E_ARG, "%s: the %s filter is a counting filter: the reject filter and the filter built with it are plain",
+		             what, out2->f.counting ? "SECONDARY" : "PRIMARY");
+	}
+	return 0;
+}
+
 } // namespace
 
 namespace nte_reads {
@@ -765,6 +832,13 @@ int
 set_error(const ntedit_hip_ctx* c, int code, const std::string& why)
 {
 	return rfail(c, code, "%s", why.c_str());
+}
+// the context's reject cutoff (ntedit_hip_reads_set_reject_cutoff); 0: none, and none without a sketch
+uint32_t
+reject_cutoff(const ntedit_hip_ctx* c)
+{
+	const ReadsState* s = find_state(c);
+	return s ? s->reject_cmin : 0;
 }
 } // namespace nte_reads
 
@@ -1117,6 +1191,38 @@ ntedit_hip_filter_insert_solid(ntedit_hip_ctx* c, int slot, const char* bases, u
 }
 
 int
+ntedit_hip_filter_insert_solid2(ntedit_hip_ctx* c, const char* bases, uint64_t n, int on_device, uint32_t cmin, uint32_t rmin)
+{
+	if (!c || !bases) {
+		return c ? rfail(c, NTEDIT_E_ARG, "filter_insert_solid2: bad argument") : NTEDIT_E_ARG;
+	}
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return rfail(c, NTEDIT_E_ARG, "filter_insert_solid2: no sketch (ntedit_hip_sketch_alloc)");
+	}
+	RdFilter out, out2;
+	const int rc = solid2_targets(c, s, cmin, rmin, "filter_insert_solid2", &out, &out2);
+	if (rc) {
+		return rc;
+	}
+	return run_pass(c, s, bases, n, on_device, 4, out, cmin, out2, rmin);
+}
+
+int
+ntedit_hip_reads_set_reject_cutoff(ntedit_hip_ctx* c, uint32_t rmin)
+{
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return c ? rfail(c, NTEDIT_E_ARG, "reads_set_reject_cutoff: no sketch (ntedit_hip_sketch_alloc / _set_device)") : NTEDIT_E_ARG;
+	}
+	if (rmin > 255) {
+		return rfail(c, NTEDIT_E_ARG, "reads_set_reject_cutoff: rmin = %u: needs rmin <= 255", rmin);
+	}
+	s->reject_cmin = rmin;
+	return 0;
+}
+
+int
 ntedit_hip_resident_begin(ntedit_hip_ctx* c, uint64_t cap_bytes)
 {
 	ReadsState* s = find_state(c);
@@ -1175,6 +1281,24 @@ ntedit_hip_resident_insert_solid(ntedit_hip_ctx* c, int slot, uint32_t cmin)
 		return rc;
 	}
 	return run_store_pass(c, s, out.f.counting ? 2 : 1, out, cmin);
+}
+
+int
+ntedit_hip_resident_insert_solid2(ntedit_hip_ctx* c, uint32_t cmin, uint32_t rmin)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return rfail(c, NTEDIT_E_ARG, "resident_insert_solid2: no sketch (ntedit_hip_sketch_alloc / _set_device)");
+	}
+	RdFilter out, out2;
+	const int rc = solid2_targets(c, s, cmin, rmin, "resident_insert_solid2", &out, &out2);
+	if (rc) {
+		return rc;
+	}
+	return run_store_pass(c, s, 4, out, cmin, out2, rmin);
 }
 
 void

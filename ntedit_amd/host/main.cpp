@@ -86,6 +86,14 @@ static const char USAGE[] = PROGRAM
     "			_r part of the default prefix [default name: reads_k<K>.bf, not written]\n"
     "	--gpu_parse,	parse plain (not gzip) read files on the GPU: the host ships raw file bytes (same outputs;\n"
     "			gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with the host parser)\n"
+    "	--reject_cutoff R,	also build the -e filter (k-mers to reject, e.g. repeats) from the same pass over the reads: a\n"
+    "			plain filter of the k-mers seen at least R times, 2 to 255 and above the cutoff (replaces -e;\n"
+    "			not with --counts)\n"
+    "	--reject_bf BYTES,	reject filter size in bytes\n"
+    "	--reject_num_elements N,	approximate number of k-mers in the reject filter (one of the two is required with\n"
+    "			--reject_cutoff, unless --solid or --hist: then it is sized from the k-mer histogram)\n"
+    "	--save_reject_bf FILE,	write the reject filter that was built (the bytes ntedit-make-reads-bf -c R would write)\n"
+    "			[default name: reads_k<K>_reject.bf, not written]\n"
     "	--help,		display this message and exit \n"
     "	--version,	output version information and exit\n\n";
 
@@ -113,6 +121,10 @@ enum
 	OPT_SKETCH_BYTES,
 	OPT_HIST,
 	OPT_SAVE_BF,
+	OPT_REJECT_CUTOFF,
+	OPT_REJECT_BF,
+	OPT_REJECT_NUM_ELEMENTS,
+	OPT_SAVE_REJECT_BF,
 	OPT_READS_BATCH,
 	OPT_STORE_CAP,
 	OPT_GPU_PARSE
@@ -160,6 +172,10 @@ static const struct option longopts[] = {
 	{ "sketch_bytes", required_argument, nullptr, OPT_SKETCH_BYTES },
 	{ "hist", required_argument, nullptr, OPT_HIST },
 	{ "save_bf", required_argument, nullptr, OPT_SAVE_BF },
+	{ "reject_cutoff", required_argument, nullptr, OPT_REJECT_CUTOFF },
+	{ "reject_bf", required_argument, nullptr, OPT_REJECT_BF },
+	{ "reject_num_elements", required_argument, nullptr, OPT_REJECT_NUM_ELEMENTS },
+	{ "save_reject_bf", required_argument, nullptr, OPT_SAVE_REJECT_BF },
 	{ "batch_bytes", required_argument, nullptr, OPT_READS_BATCH }, // tests: many small read batches
 	{ "resident_cap", required_argument, nullptr, OPT_STORE_CAP }, // tests: the resident store's cap (0: off)
 	{ "gpu_parse", no_argument, nullptr, OPT_GPU_PARSE },
@@ -343,7 +359,7 @@ main(int argc, char** argv)
 	args.push_back(nullptr);
 	argc = (int)args.size() - 1;
 	argv = args.data();
-	std::string hist_out, save_bf;
+	std::string hist_out, save_bf, save_reject_bf;
 	bool counts = false, shard_given = false;
 	ntedit_hip_reads_options ro = {}; // the reads options as given; refused at the option where the rules say so
 	ntedit_hip_reads_rules rr = {};
@@ -464,6 +480,20 @@ main(int argc, char** argv)
 			save_bf = optarg;
 			reads_only.push_back("--save_bf");
 			break;
+		case OPT_REJECT_CUTOFF:
+			reads_option("--reject_cutoff", &ro.reject_cutoff);
+			break;
+		case OPT_REJECT_BF:
+			reads_option("--reject_bf", &ro.reject_bf);
+			break;
+		case OPT_REJECT_NUM_ELEMENTS:
+			reads_option("--reject_num_elements", &ro.reject_num_elements);
+			break;
+		case OPT_SAVE_REJECT_BF:
+			save_reject_bf = optarg;
+			ro.reject_out = 1;
+			reads_only.push_back("--save_reject_bf");
+			break;
 		case OPT_READS_BATCH:
 			reads_option("--batch_bytes", &ro.batch_bytes);
 			break;
@@ -553,9 +583,13 @@ main(int argc, char** argv)
 			refuse("--reads and --shard: every shard would build the whole filter again; build it once with "
 			       "ntedit-make-reads-bf and give each shard -r");
 		}
+		if (ro.reject_cutoff && !bfrep.empty()) {
+			refuse("--reject_cutoff and -e: give one of them (--reject_cutoff builds the filter that -e would load)");
+		}
 		for (const std::string& r : read_files) {
 			paths.push_back(r.c_str());
 		}
+		ro.counts = counts;
 		ro.files = paths.data(); // (for the default sketch: their sizes)
 		ro.n_files = (uint32_t)paths.size();
 		rr = reads_rules(ro, 1);
@@ -657,6 +691,11 @@ main(int argc, char** argv)
 		} else {
 			printf("%llu\n", (unsigned long long)rr.bf_bytes);
 		}
+		if (rr.reject_cmin && rr.reject_size_from_hist) {
+			printf("Reject BF size (bytes): from the k-mer histogram\n");
+		} else if (rr.reject_cmin) {
+			printf("Reject BF size (bytes): %llu\n", (unsigned long long)rr.reject_bf_bytes);
+		}
 		printf("Sketch size (counters): %llu\n", (unsigned long long)rr.sketch_counters);
 		ntedit_hip_reads_build_args ba = {};
 		ba.files = paths.data();
@@ -674,6 +713,9 @@ main(int argc, char** argv)
 		ba.use_store = 1;
 		ba.store_cap = rr.store_cap;
 		ba.device_parse = rr.gpu_parse;
+		ba.reject_cmin = rr.reject_cmin;
+		ba.reject_bf_bytes = rr.reject_bf_bytes;
+		ba.reject_num_elements = rr.reject_num_elements;
 		ba.log = nte_host::reads_log;
 		ntedit_hip_reads_build_result br;
 		if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
@@ -688,6 +730,19 @@ main(int argc, char** argv)
 				fatal();
 			}
 			printf("Bloom filter saved to %s\n", save_bf.c_str());
+		}
+		// the reject filter, built into the secondary slot by the same pass 2: no -e file is loaded
+		if (rr.reject_cmin) {
+			printf("Reject filter built (reject count %u, %llu bytes)\n", rr.reject_cmin, (unsigned long long)br.reject_bf_bytes);
+			if (!save_reject_bf.empty()) {
+				if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_SECONDARY, save_reject_bf.c_str()) != 0) {
+					fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_reject_bf.c_str());
+					fatal();
+				}
+				printf("Reject Bloom filter saved to %s\n", save_reject_bf.c_str());
+			}
+			// (the -e line of the parameter echo; the reference's prefix has no -e part)
+			bfrep = save_reject_bf.empty() ? "reads_k" + std::to_string(rr.k) + "_reject.bf" : save_reject_bf;
 		}
 		// (the _r part of the default prefix: the name ntedit-make-reads-bf would have written it under)
 		bf = save_bf.empty() ? "reads_k" + std::to_string(rr.k) + ".bf" : save_bf;
@@ -739,10 +794,14 @@ main(int argc, char** argv)
 
 	if (!bfrep.empty()) {
 		time(&rawtime);
-		printf("---------- loading secondary Bloom filter from file : %s\n", ctime(&rawtime));
-		if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_SECONDARY, bfrep.c_str()) != 0) {
-			fprintf(stderr, PROGRAM ": error: secondary Bloom filter file supplied (-e) is incorrect.\n");
-			fatal();
+		if (rr.reject_cmin) {
+			printf("---------- secondary Bloom filter built from reads   : %s\n", ctime(&rawtime));
+		} else {
+			printf("---------- loading secondary Bloom filter from file : %s\n", ctime(&rawtime));
+			if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_SECONDARY, bfrep.c_str()) != 0) {
+				fprintf(stderr, PROGRAM ": error: secondary Bloom filter file supplied (-e) is incorrect.\n");
+				fatal();
+			}
 		}
 		uint32_t k2 = 0;
 		ntedit_hip_filter_info(ctx, NTEDIT_FILTER_SECONDARY, &k2, nullptr, nullptr, nullptr);

@@ -2,6 +2,7 @@
 //
 //   --reads FILE [FILE ...]  -k K  (-c CMIN | --solid)  [--hist FILE]  [--counts]  [--hashes 3]  [--fpr 0.01]
 //   [--bf BYTES | --num_elements N]  [--sketch_bytes S]  [-o reads_kK.bf]  [-t THREADS]
+//   [--reject_cutoff R  [--reject_bf BYTES | --reject_num_elements N]  [--reject_out reads_kK_reject.bf]]
 //
 // The reference leaves this step to ntHits / ntStat on the CPU (ntedit-make: `nthits -c<cutoff> --outbloom`;
 // ntedit_run_pipeline.smk: `ntstat filter -cmin C`).  This tool is neither: it counts in a plain count-min sketch of
@@ -17,6 +18,9 @@
 // the sketch's estimates, in place of the reference's ntCard run.  --hist writes it in ntCard's text format, --solid
 // takes CMIN from its first valley (ntedit_hip_reads_solid_cutoff), and without --bf / --num_elements the output is
 // sized from it: --num_elements N with N = the distinct k-mers the histogram puts at CMIN or above.
+//
+// With --reject_cutoff R the same pass 2 also fills a second plain filter with the k-mers whose estimate is at least R
+// (ntedit_hip_filter_insert_solid2): the reject filter for `ntedit -e`, the file a second run with -c R would write.
 #include "../../include/ntedit_hip.h"
 #include "log_info.h"
 
@@ -41,7 +45,8 @@ usage(const char* why)
 	}
 	std::cerr
 	    << "Usage: make_reads_bf [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] [--counts] [--hashes VAR] "
-	       "[--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] [-t VAR]\n\n"
+	       "[--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] [-t VAR] "
+	       "[--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR]\n\n"
 	       "Builds the k-mer filter of a read set on the GPU: pass 1 counts every k-mer in a count-min sketch of 8-bit\n"
 	       "counters, pass 2 keeps the k-mers whose estimate (the minimum of their counters) is at least -c.  Neither\n"
 	       "ntHits nor ntStat: the counts (plain count-min, no conservative update) and the sizing are this tool's own.\n"
@@ -69,7 +74,15 @@ usage(const char* why)
 	       "                  the same; gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with\n"
 	       "                  the host parser\n"
 	       "  -o              Name for output filter [default: \"reads_k<K>.bf\"]\n"
-	       "  -t              Number of threads (accepted; the k-mers are counted on the GPU) [default: 12]\n";
+	       "  -t              Number of threads (accepted; the k-mers are counted on the GPU) [default: 12]\n"
+	       "  --reject_cutoff Also write the reject filter for ntedit -e (k-mers to reject, e.g. repeats): a plain filter of\n"
+	       "                  the k-mers seen at least this many times, 2 to 255 and above -c, from the same pass 2 (the\n"
+	       "                  file a second run with -c R would write); not with --counts\n"
+	       "  --reject_bf     Reject filter size in bytes\n"
+	       "  --reject_num_elements  Approximate number of k-mers in the reject filter (sized as --num_elements, with\n"
+	       "                  --fpr) (one of the two is required with --reject_cutoff, unless --solid or --hist: then by\n"
+	       "                  default it is the number of k-mers the histogram puts at the reject cutoff or above)\n"
+	       "  --reject_out    Name for the reject filter [default: \"reads_k<K>_reject.bf\"]\n";
 }
 
 static bool
@@ -96,7 +109,7 @@ main(int argc, char** argv)
 	ntedit_hip_reads_options ro = {};
 	ntedit_hip_reads_rules rr;
 	bool counts = false;
-	std::string out_file, sketch_out, hist_out;
+	std::string out_file, sketch_out, hist_out, reject_out;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto value = [&](const char* name) -> const char* {
@@ -147,6 +160,15 @@ main(int argc, char** argv)
 			given("--batch_bytes", ro.batch_bytes);
 		} else if (a == "--save_sketch") { // (not in the usage text: tests compare the sketch itself)
 			sketch_out = value("--save_sketch");
+		} else if (a == "--reject_cutoff") {
+			given("--reject_cutoff", ro.reject_cutoff);
+		} else if (a == "--reject_bf") {
+			given("--reject_bf", ro.reject_bf);
+		} else if (a == "--reject_num_elements") {
+			given("--reject_num_elements", ro.reject_num_elements);
+		} else if (a == "--reject_out") {
+			reject_out = value("--reject_out");
+			ro.reject_out = 1;
 		} else if (a == "-o") {
 			out_file = value("-o");
 		} else if (a == "-t") {
@@ -161,6 +183,7 @@ main(int argc, char** argv)
 		return 1;
 	}
 	ro.hist = !hist_out.empty();
+	ro.counts = counts;
 	ro.files = paths.data();
 	ro.n_files = (uint32_t)paths.size();
 	const int refused = ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_TOOL, 1, &rr);
@@ -170,6 +193,9 @@ main(int argc, char** argv)
 	}
 	if (out_file.empty()) {
 		out_file = "reads_k" + std::to_string(rr.k) + ".bf";
+	}
+	if (reject_out.empty()) {
+		reject_out = "reads_k" + std::to_string(rr.k) + "_reject.bf";
 	}
 
 	std::cout << "Parameters:" << std::endl;
@@ -202,6 +228,15 @@ main(int argc, char** argv)
 	} else if (ro.num_elements) {
 		std::cout << "\t\t--num_elements " << rr.num_elements << std::endl;
 	}
+	if (rr.reject_cmin) {
+		std::cout << "\t\t--reject_cutoff " << rr.reject_cmin << std::endl;
+		std::cout << "\t\t--reject_out " << reject_out << std::endl;
+		if (ro.reject_bf) {
+			std::cout << "\t\t--reject_bf " << rr.reject_bf_bytes << std::endl;
+		} else if (ro.reject_num_elements) {
+			std::cout << "\t\t--reject_num_elements " << rr.reject_num_elements << std::endl;
+		}
+	}
 	if (refused) { // (the output filter would be empty)
 		usage(ntedit_hip_reads_last_error(nullptr));
 		return 1;
@@ -210,6 +245,11 @@ main(int argc, char** argv)
 		std::cout << "BF size (bytes): from the k-mer histogram" << std::endl;
 	} else {
 		std::cout << "BF size (bytes): " << rr.bf_bytes << std::endl;
+	}
+	if (rr.reject_cmin && rr.reject_size_from_hist) {
+		std::cout << "Reject BF size (bytes): from the k-mer histogram" << std::endl;
+	} else if (rr.reject_cmin) {
+		std::cout << "Reject BF size (bytes): " << rr.reject_bf_bytes << std::endl;
 	}
 	std::cout << "Sketch size (counters): " << rr.sketch_counters << std::endl;
 
@@ -235,6 +275,9 @@ main(int argc, char** argv)
 	ba.sketch_path = sketch_out.empty() ? nullptr : sketch_out.c_str();
 	ba.log = nte_host::reads_log;
 	ba.device_parse = rr.gpu_parse;
+	ba.reject_cmin = rr.reject_cmin;
+	ba.reject_bf_bytes = rr.reject_bf_bytes;
+	ba.reject_num_elements = rr.reject_num_elements;
 	ntedit_hip_reads_build_result br;
 	if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));
@@ -250,6 +293,16 @@ main(int argc, char** argv)
 	log_info(counts ? "Saving counting Bloom filter" : "Saving Bloom filter");
 	if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, out_file.c_str()) != 0) {
 		die(ctx, "cannot write " + out_file);
+	}
+	if (rr.reject_cmin) {
+		if (ntedit_hip_filter_occupancy(ctx, NTEDIT_FILTER_SECONDARY, &occupied, &slots) != 0) {
+			die(ctx, ntedit_hip_last_error(ctx));
+		}
+		std::cout << "Reject Bloom filter FPR: " << pow((double)occupied / (double)slots, (double)rr.hash_num) << std::endl;
+		log_info("Saving reject Bloom filter");
+		if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_SECONDARY, reject_out.c_str()) != 0) {
+			die(ctx, "cannot write " + reject_out);
+		}
 	}
 	log_info("Done!");
 	ntedit_hip_destroy(ctx);

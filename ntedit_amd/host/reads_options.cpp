@@ -58,7 +58,7 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 	r->store_cap = NTEDIT_READS_RESIDENT_CAP_DEFAULT;
 	r->threads = 12;
 	r->gpu_parse = o->gpu_parse ? 1 : 0; // (the one rule about it, "only with --reads", is the polisher front ends': they know)
-	uint64_t k = 0, cmin = 0, hashes = r->hash_num;
+	uint64_t k = 0, cmin = 0, hashes = r->hash_num, reject = 0;
 	// -k: the tool refuses a malformed one at the option, the polisher takes it as out of range
 	if (final && !o->k) {
 		return refuse(NTEDIT_READS_REFUSED, "-k: required" + with_reads);
@@ -85,7 +85,9 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 	}
 	if (malformed("--bf", o->bf, &r->bf_bytes) || malformed("--num_elements", o->num_elements, &r->num_elements) ||
 	    malformed("--sketch_bytes", o->sketch_bytes, &r->sketch_bytes) || malformed("--batch_bytes", o->batch_bytes, &r->batch_bytes) ||
-	    malformed("--resident_cap", o->store_cap, &r->store_cap) || malformed("-t", o->threads, &r->threads)) {
+	    malformed("--resident_cap", o->store_cap, &r->store_cap) || malformed("-t", o->threads, &r->threads) ||
+	    malformed("--reject_cutoff", o->reject_cutoff, &reject) || malformed("--reject_bf", o->reject_bf, &r->reject_bf_bytes) ||
+	    malformed("--reject_num_elements", o->reject_num_elements, &r->reject_num_elements)) {
 		return NTEDIT_READS_NOT_A_NUMBER;
 	}
 	if (!final) {
@@ -123,6 +125,41 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 	}
 	if (r->batch_bytes < 4096) {
 		return refuse(NTEDIT_READS_REFUSED, "--batch_bytes: at least 4096" + dot);
+	}
+	// the reject filter (ntedit -e), built by the same pass 2
+	if (!o->reject_cutoff) {
+		const char* alone = o->reject_bf ? "--reject_bf" : o->reject_num_elements ? "--reject_num_elements" : nullptr;
+		if (alone || o->reject_out) {
+			return refuse(NTEDIT_READS_REFUSED, std::string(alone ? alone : tool ? "--reject_out" : "--save_reject_bf") +
+			                                        ": only with --reject_cutoff" + dot);
+		}
+	} else {
+		if (reject < 2 || reject > 255) {
+			return refuse(NTEDIT_READS_REFUSED, "--reject_cutoff " + std::to_string(reject) + ": the reject count must be between 2 and 255" + dot);
+		}
+		if (o->counts) {
+			return refuse(NTEDIT_READS_REFUSED, "--reject_cutoff and --counts: a counting filter needs no reject filter (ntedit -q "
+			                                    "sets the maximum count)" + dot);
+		}
+		if (o->cutoff && reject <= cmin) {
+			return refuse(NTEDIT_READS_REFUSED, "--reject_cutoff " + std::to_string(reject) + ": the reject count must be above " + cut + " " +
+			                                        std::to_string(cmin) + dot);
+		}
+		if (o->reject_bf && o->reject_num_elements) {
+			return refuse(NTEDIT_READS_REFUSED, "--reject_bf and --reject_num_elements: give one of them" + dot);
+		}
+		r->reject_cmin = (uint32_t)reject;
+		r->reject_size_from_hist = !o->reject_bf && !o->reject_num_elements;
+		if (r->reject_size_from_hist && !r->gather_hist) {
+			return refuse(NTEDIT_READS_REFUSED, "--reject_bf or --reject_num_elements: one of them is required with --reject_cutoff (or "
+			                                    "--solid / --hist, which size the reject filter from the k-mer histogram)" + dot);
+		}
+		if (o->reject_num_elements) {
+			r->reject_bf_bytes = ntedit_hip_reads_bf_size(r->reject_num_elements, r->hash_num, r->fpr);
+		}
+		if (!r->reject_size_from_hist && r->reject_bf_bytes == 0) {
+			return refuse(NTEDIT_READS_REFUSED, "--reject_bf / --reject_num_elements: the reject filter would be empty" + dot);
+		}
 	}
 	if (empty) { // (the tool has printed its parameters by then)
 		return refuse(NTEDIT_READS_EMPTY, "The output filter would be empty (--bf 0 or --num_elements too small).");

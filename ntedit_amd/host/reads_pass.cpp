@@ -1,7 +1,8 @@
 // reads_pass.cpp -- the host side of the reads k-mer filter build, shared by ntedit-make-reads-bf and the sharded driver
 // (ntedit_amd/make_reads.py): one pass over a list of byte ranges of the input files, parsed by FastaReader into bounded
 // batches double-buffered through page-locked memory (a second thread parses the next batch while the GPU works on the
-// current one); the tool's sizing; its --hist writer; and the build itself, in four stages that both walk.
+// current one); the tool's sizing; its --hist writer; and the build itself, in four stages that both walk.  With a reject
+// cutoff the build's pass 2 fills the SECONDARY slot too (the filter ntedit -e loads), from the same walk.
 //
 // A range [begin, end) of a file owns the records whose first byte lies in it.  A range that starts past byte 0 first
 // moves forward to the first record start: a line that starts with '>' in a FASTA file, or in a FASTQ file a line that
@@ -32,6 +33,7 @@
 
 namespace nte_reads {
 int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+uint32_t reject_cutoff(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_reject_cutoff (nte_reads.hip)
 // --gpu_parse (nte_reads_parse.hip): the context's setting and counters, its two raw buffers and its copy stream
 int parse_is_on(const ntedit_hip_ctx* c);
 ntedit_hip_reads_parse_stats* parse_info(const ntedit_hip_ctx* c);
@@ -617,10 +619,12 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 	const auto t0 = std::chrono::steady_clock::now();
 	uint64_t bases = 0;
 	double gpu_ms = 0.0;
-	// one batch of text, host or device, through the pass's kernels
+	// one batch of text, host or device, through the pass's kernels (SOLID with a reject cutoff set: both slots)
+	const uint32_t rmin = pass == NTEDIT_READS_PASS_SOLID ? nte_reads::reject_cutoff(ctx) : 0;
 	auto run_batch = [&](const char* text, uint64_t len, int where) {
 		return pass == NTEDIT_READS_PASS_COUNT  ? ntedit_hip_sketch_count(ctx, text, len, where)
 		       : pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_sketch_histogram(ctx, text, len, where)
+		       : rmin                           ? ntedit_hip_filter_insert_solid2(ctx, text, len, where, cmin, rmin)
 		                                        : ntedit_hip_filter_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, text, len, where, cmin);
 	};
 	// the host parser over some ranges (all of them, without --gpu_parse)
@@ -859,6 +863,7 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 	if (!read_files) {
 		const auto t0 = std::chrono::steady_clock::now();
 		rc = pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_resident_histogram(ctx)
+		     : a->reject_cmin               ? ntedit_hip_resident_insert_solid2(ctx, r->cmin, a->reject_cmin)
 		                                    : ntedit_hip_resident_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, r->cmin);
 		st.bases = r->pass[NTEDIT_READS_PASS_COUNT].bases;
 		st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -911,7 +916,8 @@ bool
 bad_build_args(const ntedit_hip_reads_build_args* a, const ntedit_hip_reads_build_result* r)
 {
 	return !a || !r || (a->n_files && !a->files) || (a->begins && !a->ends) || a->batch_bytes < 4096 ||
-	       (!a->solid && (a->cmin < 1 || a->cmin > 255)) || (a->bf_bytes == 0 && !a->solid && !a->hist_path);
+	       (!a->solid && (a->cmin < 1 || a->cmin > 255)) || (a->bf_bytes == 0 && !a->solid && !a->hist_path) ||
+	       (a->reject_cmin && (a->reject_cmin > 255 || a->counts || (a->reject_bf_bytes == 0 && !a->solid && !a->hist_path)));
 }
 
 } // namespace
@@ -979,12 +985,14 @@ ntedit_hip_reads_stage_histogram(ntedit_hip_ctx* ctx, const ntedit_hip_reads_bui
 int
 ntedit_hip_reads_stage_decide(const ntedit_hip_reads_build_args* a, const uint64_t occ[256], ntedit_hip_reads_build_result* r)
 {
-	if (bad_build_args(a, r) || (!occ && (a->solid || a->bf_bytes == 0))) {
+	if (bad_build_args(a, r) || (!occ && (a->solid || a->bf_bytes == 0 || (a->reject_cmin && a->reject_bf_bytes == 0)))) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_stage_decide: bad argument");
 	}
 	const BuildLog lg{ a, true };
 	r->cmin = a->cmin;
 	r->bf_bytes = a->bf_bytes;
+	r->reject_bf_bytes = a->reject_cmin ? a->reject_bf_bytes : 0;
+	const std::string reject = "--reject_cutoff " + std::to_string(a->reject_cmin);
 	if (occ) {
 		uint64_t f[256], F0 = 0, F1 = 0;
 		ntedit_hip_reads_hist_summary(occ, f, &F0, &F1);
@@ -1002,6 +1010,23 @@ ntedit_hip_reads_stage_decide(const ntedit_hip_reads_build_args* a, const uint64
 				                                    "f[c+1] > f[c]); pass -c");
 			}
 			lg.info("--solid: minimum k-mer count " + std::to_string(r->cmin));
+			if (a->reject_cmin && a->reject_cmin <= r->cmin) {
+				return pfail(nullptr, NTEDIT_E_ARG, reject + ": the reject count must be above the minimum count, and --solid found " +
+				                                        std::to_string(r->cmin));
+			}
+		}
+		if (a->reject_cmin && a->reject_bf_bytes == 0) {
+			uint64_t num_elements = 0;
+			for (uint64_t c = a->reject_cmin; c < 256; c++) {
+				num_elements += f[c];
+			}
+			r->reject_bf_bytes = ntedit_hip_reads_bf_size(num_elements, a->hash_num, a->fpr);
+			lg.info("Reject filter sized from the k-mer histogram: --reject_num_elements " + std::to_string(num_elements) + " (k-mers at " +
+			        std::to_string(a->reject_cmin) + " or above), " + std::to_string(r->reject_bf_bytes) + " bytes");
+			if (r->reject_bf_bytes == 0) {
+				return pfail(nullptr, NTEDIT_E_ARG, "The reject filter would be empty (no k-mer at " + reject + " or above).");
+			}
+			lg.out("Reject BF size (bytes): " + std::to_string(r->reject_bf_bytes));
 		}
 		if (a->bf_bytes == 0) {
 			uint64_t num_elements = 0;
@@ -1020,13 +1045,20 @@ ntedit_hip_reads_stage_decide(const ntedit_hip_reads_build_args* a, const uint64
 	if (r->bf_bytes == 0) {
 		return pfail(nullptr, NTEDIT_E_ARG, "The output filter would be empty (--bf 0 or --num_elements too small).");
 	}
+	if (a->reject_cmin && a->reject_cmin <= r->cmin) {
+		return pfail(nullptr, NTEDIT_E_ARG, reject + ": the reject count must be above the minimum count " + std::to_string(r->cmin));
+	}
+	if (a->reject_cmin && r->reject_bf_bytes == 0) {
+		return pfail(nullptr, NTEDIT_E_ARG, "The reject filter would be empty (--reject_bf 0 or --reject_num_elements too small).");
+	}
 	return 0;
 }
 
 int
 ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, ntedit_hip_reads_build_result* r)
 {
-	if (!ctx || bad_build_args(a, r) || r->bf_bytes == 0 || r->cmin < 1 || r->cmin > 255) {
+	if (!ctx || bad_build_args(a, r) || r->bf_bytes == 0 || r->cmin < 1 || r->cmin > 255 ||
+	    (a->reject_cmin && (r->reject_bf_bytes == 0 || a->reject_cmin <= r->cmin))) {
 		return pfail(ctx, NTEDIT_E_ARG, "reads_stage_insert: bad argument");
 	}
 	const BuildLog lg{ a };
@@ -1038,8 +1070,17 @@ ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_
 	} else if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, r->bf_bytes, a->hash_num, a->k) != 0) {
 		return pfail(ctx, NTEDIT_E_DEVICE, ntedit_hip_last_error(ctx));
 	}
+	// the reject filter: plain, same k and hash count, in the SECONDARY slot (a sharded build: the adopted one)
+	if (a->reject_cmin && !lg.ranged() &&
+	    ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_SECONDARY, r->reject_bf_bytes, a->hash_num, a->k) != 0) {
+		return pfail(ctx, NTEDIT_E_DEVICE, ntedit_hip_last_error(ctx));
+	}
+	if (a->reject_cmin && ntedit_hip_reads_set_reject_cutoff(ctx, a->reject_cmin) != 0) { // (for a pass 2 over the files)
+		return NTEDIT_E_ARG;
+	}
 	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
-	lg.rank_info("Pass 2: inserting k-mers seen at least " + std::to_string(r->cmin) + " times");
+	lg.rank_info("Pass 2: inserting k-mers seen at least " + std::to_string(r->cmin) + " times" +
+	             (a->reject_cmin ? ", and into the reject filter those seen at least " + std::to_string(a->reject_cmin) + " times" : ""));
 	const int rc = build_pass(ctx, a, NTEDIT_READS_PASS_SOLID, r, nullptr, nullptr);
 	ntedit_hip_sketch_free(ctx); // (the store with it)
 	return rc;

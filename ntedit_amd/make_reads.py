@@ -14,6 +14,8 @@ one-process sketch.  The histogram pass sums 256 integer bins; pass 2 writes per
 or max (--counts) into the one-process filter.  The output is byte-identical to the binary's for every world size and
 partition, or the run is refused: after pass 1 every range's stop must be the next range's start (see
 ntedit_hip_reads_pass), which multi-line FASTQ can break -- then nothing is written and --no-split is the way out.
+With --reject_cutoff the same pass 2 fills a second plain filter per rank (the reject filter for ntedit -e), merged by OR
+like the first and written by rank 0 to --reject_out.
 Only rank 0 writes files.  The per-rank build is build_rank, which `python -m ntedit_amd.run --reads` shares: there it
 keeps the reads resident in HBM after pass 1 and builds into the context that then polishes.
 """
@@ -34,10 +36,14 @@ RESIDENT_CAP_DEFAULT = _lib.READS_RESIDENT_CAP_DEFAULT  # the resident store's c
 
 USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] "
          "[--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] "
-         "[-t VAR] [--no-split] [--backend VAR]\n\n"
+         "[-t VAR] [--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR] [--no-split] "
+         "[--backend VAR]\n\n"
          "ntedit-make-reads-bf on N processes (python -m torch.distributed.run --nproc-per-node N -m "
          "ntedit_amd.make_reads ...): the same flags, the same output bytes.\n"
          "  --no-split      read every input file whole (by one process); gzip files always are\n"
+         "  --reject_cutoff also write the reject filter for ntedit -e (the k-mers seen at least this many times), from\n"
+         "                  the same pass 2; --reject_bf / --reject_num_elements size it, --reject_out names it\n"
+         "                  [default: reads_k<K>_reject.bf]\n"
          "  --gpu_parse     parse plain (not gzip) read files on the GPU: the host ships raw file bytes; same output\n"
          "  --backend       torch.distributed backend (default nccl = RCCL; gloo: N ranks may share a GPU)\n"
          "ntedit-make-reads-bf --help describes the other flags.\n")
@@ -51,13 +57,14 @@ def _is_option(a):
     return len(a) > 1 and a[0] == "-" and not a[1].isdigit()
 
 
-def check_options(dialect, given, final, reads=(), solid=False, hist="", gpu_parse=False):
+def check_options(dialect, given, final, reads=(), solid=False, hist="", gpu_parse=False, counts=False, reject_out=False):
     """The library's reads-option rules (ntedit_hip_reads_options_check) over the option texts given so far (name ->
     text).  final: every rule, and the argument dict of build_rank; else only what is refused at the option itself.
     Refused with the library's message; the tool's "would be empty" is kept in the dict for sizes() to refuse."""
     lib = _lib.load()
     files = (ctypes.c_char_p * max(1, len(reads)))(*[os.fsencode(f) for f in reads])
     o = _lib.ReadsOptions(solid=solid, hist=bool(hist), files=files, n_files=len(reads), gpu_parse=bool(gpu_parse),
+                          counts=bool(counts), reject_out=bool(reject_out),
                           **{name: os.fsencode(text) for name, text in given.items()})
     r = _lib.ReadsRules()
     rc = lib.ntedit_hip_reads_options_check(o, dialect, int(final), r)
@@ -69,15 +76,17 @@ def check_options(dialect, given, final, reads=(), solid=False, hist="", gpu_par
                 num_elements=r.num_elements if "num_elements" in given else None, sketch_bytes=r.sketch_bytes,
                 batch_bytes=r.batch_bytes, store_cap=r.store_cap, threads=r.threads, gather_hist=bool(r.gather_hist),
                 size_from_hist=bool(r.size_from_hist), bf_bytes=r.bf_bytes, sketch=r.sketch_counters, empty=why,
-                gpu_parse=bool(r.gpu_parse))
+                gpu_parse=bool(r.gpu_parse), reject_cmin=r.reject_cmin, reject_bf_bytes=r.reject_bf_bytes,
+                reject_num_elements=r.reject_num_elements, reject_size_from_hist=bool(r.reject_size_from_hist))
 
 
 def parse(argv):
     """ntedit-make-reads-bf's arguments, walked as it walks them (host/make_reads_bf.cpp); the rules are the library's"""
     texts = {"-k": "k", "-c": "cutoff", "--hashes": "hashes", "--fpr": "fpr", "--bf": "bf",
              "--num_elements": "num_elements", "--sketch_bytes": "sketch_bytes", "-t": "threads",
-             "--batch_bytes": "batch_bytes"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
-    own = dict(counts=False, out="", no_split=False, backend=None, help=False)
+             "--batch_bytes": "batch_bytes", "--reject_cutoff": "reject_cutoff", "--reject_bf": "reject_bf",
+             "--reject_num_elements": "reject_num_elements"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
+    own = dict(counts=False, out="", reject_out="", no_split=False, backend=None, help=False)
     given, reads, solid, hist, gpu_parse = {}, [], False, "", False
     i = 0
     while i < len(argv):
@@ -109,6 +118,8 @@ def parse(argv):
             own["counts"] = True
         elif x == "-o":
             own["out"] = value("-o")
+        elif x == "--reject_out":
+            own["reject_out"] = value("--reject_out")
         elif x == "--no-split":
             own["no_split"] = True
         elif x == "--backend":
@@ -118,9 +129,12 @@ def parse(argv):
         i += 1
     if not reads:
         raise Refused("--reads: 1 or more argument(s) expected. 0 provided.")
-    a = dict(check_options(_lib.READS_DIALECT_TOOL, given, True, reads, solid, hist, gpu_parse), **own)
+    a = dict(check_options(_lib.READS_DIALECT_TOOL, given, True, reads, solid, hist, gpu_parse, own["counts"],
+                           bool(own["reject_out"])), **own)
     if not a["out"]:
         a["out"] = "reads_k%d.bf" % a["k"]
+    if not a["reject_out"]:
+        a["reject_out"] = "reads_k%d_reject.bf" % a["k"]
     return a
 
 
@@ -309,13 +323,15 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
     return every rank holds the whole filter there and the sketch is freed.  With use_store the reads of pass 1 stay
     resident in HBM (up to store_cap bytes) and the later passes read the store; a rank whose store was released
     reads its ranges again, with the same result.  The stages fill the PRIMARY slot, so that is the only slot a build
-    can fill.
+    can fill.  With a reject cutoff (a["reject_cmin"]) the same pass 2 fills a second adopted tensor in the SECONDARY
+    slot, merged with OR as the primary is; pol keeps it alive (dist._keep).
     -> (the filter tensor, which the caller keeps alive while the slot is in use, a report dict)"""
     import torch
     if slot != 0:
         raise ValueError("build_rank: pass 2 from the files fills the PRIMARY slot (0) only")
     lib = pol._lib
     bf, sketch = sizes(lib, a)
+    reject = a.get("reject_cmin") or 0
     facts = file_facts(lib, a["reads"])
     units, owner = plan(a["reads"], facts, world, split=not a["no_split"])
     mine = [u for u, o in zip(units, owner) if o == rank]
@@ -323,7 +339,9 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
     if rank == 0:
         log_info("%d ranks, %d units (%d input files), sketch %d counters, %s" %
                  (world, len(units), len(a["reads"]), sketch,
-                  "output from the k-mer histogram" if a["size_from_hist"] else "output %d bytes" % bf))
+                  "output from the k-mer histogram" if a["size_from_hist"] else "output %d bytes" % bf) +
+                 ("" if not reject else ", reject filter at %d, %s" % (
+                     reject, "from the k-mer histogram" if a["reject_size_from_hist"] else "%d bytes" % a["reject_bf_bytes"])))
     b = Builder(a, rank, world, pol, group, name)
     n = len(mine)
     u64s = ctypes.c_uint64 * max(n, 1)
@@ -333,7 +351,8 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         begins=u64s(*[u.begin for u in mine]), ends=u64s(*[u.end for u in mine]), rank=rank, world=world, k=a["k"],
         hash_num=a["hashes"], cmin=a["cmin"] or 0, solid=a["solid"], counts=a["counts"], bf_bytes=bf, fpr=a["fpr"],
         batch_bytes=a["batch_bytes"], hist_path=a["hist"].encode() or None, use_store=use_store, store_cap=store_cap,
-        log=_log_line, device_parse=bool(a.get("gpu_parse")))
+        log=_log_line, device_parse=bool(a.get("gpu_parse")), reject_cmin=reject,
+        reject_bf_bytes=a.get("reject_bf_bytes") or 0, reject_num_elements=a.get("reject_num_elements") or 0)
     res = _lib.ReadsBuildResult()
     parsed = {}
 
@@ -379,12 +398,21 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         out = torch.zeros(b.padded(nbytes), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         pol.set_filter_device(out.data_ptr(), nbytes, hashes, k, slot=slot, counting=a["counts"])
+        out2, nbytes2 = None, 0
+        if reject:
+            nbytes2 = (res.reject_bf_bytes + 7) // 8 * 8
+            out2 = torch.zeros(b.padded(nbytes2), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            pol.set_filter_device(out2.data_ptr(), nbytes2, hashes, k, slot=1, counting=False)
+            ndist._keep(pol, 1, out2)
         if lib.ntedit_hip_reads_stage_insert(b.h, args, res) != 0:  # (it frees the sketch, and the store with it)
             b.fail("pass 2 (solid k-mers)")
         if res.store_state != _lib.RESIDENT_ON:
             note_parse("2")
         del sk
         b.merge(out, _lib.MERGE_MAX if a["counts"] else _lib.MERGE_OR)
+        if reject:
+            b.merge(out2, _lib.MERGE_OR)
     finally:
         lib.ntedit_hip_sketch_free(b.h)
     on = res.store_state == _lib.RESIDENT_ON
@@ -397,6 +425,8 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
                exchange_ms=round(b.xsec * 1e3, 3))
     if a.get("gpu_parse"):
         rep["parse"] = parsed
+    if reject:
+        rep["reject"] = dict(cutoff=reject, filter_bytes=nbytes2, merge_ms=b.exchanges[-1]["ms"] if group is not None else 0.0)
     return out, rep
 
 
@@ -412,6 +442,13 @@ def build(a, lib, rank, world, local, group):
                 raise RuntimeError("cannot write " + a["out"])
             log_info("rank 0: filter (%d bytes) written to %s; exchanges %d bytes sent in %.1f ms"
                      % (rep["filter_bytes"], a["out"], rep["exchange_bytes"], rep["exchange_ms"]))
+            if a.get("reject_cmin"):
+                occupied, slots = pol.filter_occupancy(1)
+                print("Reject Bloom filter FPR: %g" % ((occupied / slots) ** a["hashes"]), flush=True)
+                if lib.ntedit_hip_filter_save_file(pol._h, 1, a["reject_out"].encode()) != 0:
+                    raise RuntimeError("cannot write " + a["reject_out"])
+                log_info("rank 0: reject filter (%d bytes, k-mers seen at least %d times) written to %s"
+                         % (rep["reject"]["filter_bytes"], a["reject_cmin"], a["reject_out"]))
         if group is not None:
             import torch.distributed as dist
             dist.barrier()

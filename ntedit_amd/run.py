@@ -19,7 +19,8 @@ reference at -t 1).
 With --reads instead of -r (the reads options of `ntedit --reads`, with their meaning and refusals, and --no-split of
 ntedit_amd.make_reads) every rank builds its share of the reads filter in HBM, the reads it parsed in pass 1 kept
 resident there for the later passes, into the context that then polishes (make_reads.build_rank); the merges leave the
-whole filter on every rank: no filter file, no broadcast.  The outputs are those of `ntedit --reads` with the same flags.
+whole filter on every rank: no filter file, no broadcast.  With --reject_cutoff the -e filter is built by the same pass 2
+and merged the same way into every rank's SECONDARY slot.  The outputs are those of `ntedit --reads` with the same flags.
 
 What the reference does instead: readAndCorrect's OpenMP loop (ntedit.cpp:2213-2252), contigs handed to threads one
 at a time, output in completion order."""
@@ -224,7 +225,8 @@ READS_OPTIONS = [("--cutoff", "cutoff"), ("--solid", "solid"), ("--counts", "cou
                  ("--fpr", "fpr"), ("--bf", "bf_bytes"), ("--num_elements", "num_elements"),
                  ("--sketch_bytes", "sketch_bytes"), ("--hist", "hist"), ("--save_bf", "save_bf"),
                  ("--batch_bytes", "batch_bytes"), ("--resident_cap", "resident_cap"), ("--no-split", "no_split"),
-                 ("--gpu_parse", "gpu_parse")]
+                 ("--gpu_parse", "gpu_parse"), ("--reject_cutoff", "reject_cutoff"), ("--reject_bf", "reject_bf"),
+                 ("--reject_num_elements", "reject_num_elements"), ("--save_reject_bf", "save_reject_bf")]
 
 
 def parse(argv=None):
@@ -271,6 +273,13 @@ def parse(argv=None):
     g.add_argument("--hist", metavar="FILE", help="write the k-mer histogram (rank 0)")
     g.add_argument("--save_bf", metavar="FILE", help="write the filter that was built (rank 0); the _r part of the "
                                                      "default prefix [reads_k<K>.bf, not written]")
+    g.add_argument("--reject_cutoff", metavar="R", help="also build the -e filter (k-mers to reject) from the same pass over "
+                                                        "the reads: the k-mers seen at least R times, 2 to 255 and above "
+                                                        "the cutoff (replaces -e; not with --counts)")
+    g.add_argument("--reject_bf", metavar="BYTES", help="reject filter size in bytes")
+    g.add_argument("--reject_num_elements", metavar="N", help="approximate number of k-mers in the reject filter")
+    g.add_argument("--save_reject_bf", metavar="FILE", help="write the reject filter that was built (rank 0) "
+                                                            "[reads_k<K>_reject.bf, not written]")
     g.add_argument("--no-split", dest="no_split", action="store_true",
                    help="read every input file whole (by one rank); gzip files always are")
     g.add_argument("--gpu_parse", action="store_true",
@@ -293,12 +302,15 @@ def reads_args(args):
         raise Refused("--reads and -r: give one of them (--reads builds the filter that -r would load)")
     if not args.reads:
         raise Refused("--reads: 1 or more files expected")
+    if args.reject_cutoff is not None and args.bfrep is not None:
+        raise Refused("--reject_cutoff and -e: give one of them (--reject_cutoff builds the filter that -e would load)")
     given = {name: getattr(args, dest) for name, dest in
              (("k", "k_ignored"), ("cutoff", "cutoff"), ("hashes", "hashes"), ("fpr", "fpr"), ("bf", "bf_bytes"),
               ("num_elements", "num_elements"), ("sketch_bytes", "sketch_bytes"), ("batch_bytes", "batch_bytes"),
-              ("store_cap", "resident_cap")) if getattr(args, dest) is not None}
+              ("store_cap", "resident_cap"), ("reject_cutoff", "reject_cutoff"), ("reject_bf", "reject_bf"),
+              ("reject_num_elements", "reject_num_elements")) if getattr(args, dest) is not None}
     a = make_reads.check_options(_lib.READS_DIALECT_POLISHER, given, True, args.reads, args.solid, args.hist or "",
-                                 args.gpu_parse)
+                                 args.gpu_parse, args.counts, args.save_reject_bf is not None)
     a.update(counts=args.counts, no_split=args.no_split)
     for path in [args.draft] + a["reads"]:
         try:
@@ -311,7 +323,8 @@ def reads_args(args):
 def build_from_reads(pol, args, rank, world):
     """--reads: this rank's share of the reads filter, built into the PRIMARY slot of pol's context with the reads kept
     resident in HBM (make_reads.build_rank); every rank then holds the whole filter: no file, no broadcast.  Rank 0
-    writes --save_bf.  The sketch and the store are freed, and torch's cache of them released, before the polish
+    writes --save_bf.  With --reject_cutoff the merged reject filter is left in every rank's SECONDARY slot the same way
+    (rank 0 writes --save_reject_bf).  The sketch and the store are freed, and torch's cache of them released, before the polish
     reserves its buffers.  -> the report of the build, or None after a refusal (on every rank alike)"""
     import torch
     import torch.distributed as dist
@@ -331,6 +344,12 @@ def build_from_reads(pol, args, rank, world):
         if args.save_bf:
             pol.filter_save_file(args.save_bf, 0)
             log_info("Bloom filter saved to " + args.save_bf)
+        if "reject" in rep:
+            log_info("rank 0: reject filter (%d bytes) built from the same pass, reject count %d"
+                     % (rep["reject"]["filter_bytes"], rep["reject"]["cutoff"]))
+            if args.save_reject_bf:
+                pol.filter_save_file(args.save_reject_bf, 1)
+                log_info("Reject Bloom filter saved to " + args.save_reject_bf)
     return rep
 
 
