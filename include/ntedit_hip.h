@@ -438,6 +438,75 @@ int ntedit_hip_reads_parse_device(ntedit_hip_ctx* ctx, const char* raw, uint64_t
 int ntedit_hip_reads_parse_model(const char* raw, uint64_t n_raw, uint32_t k, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res);
 int ntedit_hip_reads_set_device_parse(ntedit_hip_ctx* ctx, int on);
 int ntedit_hip_reads_parse_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_parse_stats* st);
+/* --gpu_parse on BGZF reads (the output of bgzip: independent gzip members of at most 64 KiB inflated each, their
+ * compressed size in the header's 'BC' subfield, CRC-32 and ISIZE behind each).  ntedit_hip_reads_pass ships such a file
+ * compressed, kernels (nte_reads_inflate.hip; the decoder is nte_bgzf_inflate.h) inflate its members in HBM and check
+ * their CRCs there, and the inflated bytes go to the parse kernels above; they never exist on the host.  A single-stream
+ * .gz stays with the host parser.  A member the device refuses fails the pass; an unclean chunk, or a member in
+ * mid-file that is not BGZF, sends the rest of the file to the host parser from an exact record start.
+ *   ntedit_hip_bgzf_walk: the member headers of bytes[0 .. n): the members that lie completely inside (at most cap),
+ *           in_off / out_off counted from bytes[0] and from the first member's first inflated byte; *consumed: where
+ *           the next member starts.  Returns why it stopped: NTEDIT_BGZF_END (the buffer's end), _CUT (the next member
+ *           is cut off by the buffer's end), _NOT (what starts there is no BGZF member), _FULL (cap members found).
+ *   ntedit_hip_reads_inflate_device: one call inflates a set of members.  comp: host or device bytes; out_device:
+ *           device memory; every member must lie inside comp[0 .. n_comp) and out[0 .. out_cap) (else NTEDIT_E_ARG).
+ *           status[i] (host): 0, member i is inflated and its CRC-32 holds, or the reason it was refused
+ *           (NTEDIT_INFLATE_*); a refused member leaves its output bytes undefined and touches no byte outside them.
+ *   ntedit_hip_reads_inflate_model: the same decoder functions run serially on the host (no device; failures through
+ *           ntedit_hip_reads_last_error(NULL)), into host memory.
+ *   ntedit_hip_reads_last_record_start: the chunk cut's rule on the host (what RawFeeder cuts plain files by): the last
+ *           record start in buf[0 .. n) past its first byte -- '>' at a line start (kind '>'), or an '@' line whose
+ *           line + 2, inside the buffer, starts with '+' -- or NTEDIT_READS_NO_START.
+ *   ntedit_hip_reads_last_start_device: the same from the device's line table; kind is the buffer's first byte ('>' or
+ *           '@'; any other: n).  At most 2^31 - 1 bytes and one line per 8 bytes (+ 1).
+ *   ntedit_hip_reads_inflate_info: the last pass of the context. */
+#define NTEDIT_BGZF_END 0
+#define NTEDIT_BGZF_CUT 1
+#define NTEDIT_BGZF_NOT 2
+#define NTEDIT_BGZF_FULL 3
+#define NTEDIT_INFLATE_BAD_BLOCK 1
+#define NTEDIT_INFLATE_BAD_CODES 2
+#define NTEDIT_INFLATE_BAD_DIST 3
+#define NTEDIT_INFLATE_OUT_OVER 4
+#define NTEDIT_INFLATE_IN_OVER 5
+#define NTEDIT_INFLATE_SHORT_OUT 6
+#define NTEDIT_INFLATE_LEFT_IN 7
+#define NTEDIT_INFLATE_BAD_CRC 8
+#define NTEDIT_INFLATE_BAD_STORED 9
+#define NTEDIT_INFLATE_BAD_SYMBOL 10
+#define NTEDIT_READS_NO_START (~0ull)
+typedef struct ntedit_hip_bgzf_member
+{
+	uint64_t in_off;  /* of the member's DEFLATE data */
+	uint64_t out_off; /* of its inflated bytes */
+	uint32_t n_in;    /* bytes of DEFLATE data */
+	uint32_t n_out;   /* ISIZE */
+	uint32_t crc;     /* CRC-32 of the inflated bytes */
+	uint32_t reserved;
+} ntedit_hip_bgzf_member;
+typedef struct ntedit_hip_reads_inflate_stats
+{
+	uint64_t members;      /* inflated on the device */
+	uint64_t comp_bytes;   /* shipped to the device */
+	uint64_t raw_bytes;    /* inflated there */
+	double ms_kernels;     /* in the inflate and cut kernels */
+	uint32_t files;        /* BGZF files fed to the device */
+	uint32_t handed_back;  /* ... of which the host parser finished */
+	uint64_t handed_back_at; /* the inflated offset the last of those was handed back at */
+	uint64_t bad_member;   /* the first refused member's index in its file (bad_reason != 0) */
+	uint32_t bad_reason;   /* NTEDIT_INFLATE_* */
+	uint32_t reserved;
+} ntedit_hip_reads_inflate_stats;
+int ntedit_hip_bgzf_walk(const void* bytes, uint64_t n, ntedit_hip_bgzf_member* members, uint64_t cap, uint64_t* n_members,
+                         uint64_t* consumed);
+int ntedit_hip_reads_inflate_device(ntedit_hip_ctx* ctx, const void* comp, uint64_t n_comp, int on_device,
+                                    const ntedit_hip_bgzf_member* members, uint64_t n_members, void* out_device, uint64_t out_cap,
+                                    uint32_t* status);
+int ntedit_hip_reads_inflate_model(const void* comp, uint64_t n_comp, const ntedit_hip_bgzf_member* members, uint64_t n_members,
+                                   void* out, uint64_t out_cap, uint32_t* status);
+uint64_t ntedit_hip_reads_last_record_start(const char* buf, uint64_t n, int kind);
+int ntedit_hip_reads_last_start_device(ntedit_hip_ctx* ctx, const void* buf, uint64_t n, int on_device, uint64_t* cut);
+int ntedit_hip_reads_inflate_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_inflate_stats* st);
 
 
 /* ---- hot path ------------------------------------------------------------

@@ -150,6 +150,24 @@ class ReadsParseStats(ctypes.Structure):
                 ("broken", ctypes.c_uint32), ("host_files", ctypes.c_uint32)]
 
 
+class BgzfMember(ctypes.Structure):
+    """ntedit_hip_bgzf_member: one BGZF member of a buffer of compressed bytes"""
+    _fields_ = [("in_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("n_in", ctypes.c_uint32),
+                ("n_out", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ReadsInflateStats(ctypes.Structure):
+    """ntedit_hip_reads_inflate_stats: --gpu_parse on BGZF inputs, the last pass of a context"""
+    _fields_ = [("members", ctypes.c_uint64), ("comp_bytes", ctypes.c_uint64), ("raw_bytes", ctypes.c_uint64),
+                ("ms_kernels", ctypes.c_double), ("files", ctypes.c_uint32), ("handed_back", ctypes.c_uint32),
+                ("handed_back_at", ctypes.c_uint64), ("bad_member", ctypes.c_uint64), ("bad_reason", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+BGZF_END, BGZF_CUT, BGZF_NOT, BGZF_FULL = 0, 1, 2, 3
+READS_NO_START = 2 ** 64 - 1
+
+
 class Segment(ctypes.Structure):
     """ntedit_hip_segment: a batch entry that is one segment of a contig cut for multi-GPU sharding"""
     _fields_ = [("pos_offset", ctypes.c_uint32), ("halo", ctypes.c_uint32), ("flags", ctypes.c_uint32),
@@ -210,6 +228,8 @@ EXPORTS = [
     "ntedit_hip_reads_stage_insert", "ntedit_hip_reads_options_check",
     "ntedit_hip_reads_parse_device", "ntedit_hip_reads_parse_model", "ntedit_hip_reads_set_device_parse",
     "ntedit_hip_reads_parse_info", "ntedit_hip_reads_set_reject_cutoff",
+    "ntedit_hip_bgzf_walk", "ntedit_hip_reads_inflate_device", "ntedit_hip_reads_inflate_model",
+    "ntedit_hip_reads_last_record_start", "ntedit_hip_reads_last_start_device", "ntedit_hip_reads_inflate_info",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -354,5 +374,14 @@ def load():
     lib.ntedit_hip_filter_insert_solid2.argtypes = [vp, vp, u64, ci, u32, u32]
     lib.ntedit_hip_resident_insert_solid2.argtypes = [vp, u32, u32]
     lib.ntedit_hip_reads_set_reject_cutoff.argtypes = [vp, u32]
+    # --gpu_parse on BGZF reads
+    pmem = ctypes.POINTER(BgzfMember)
+    lib.ntedit_hip_bgzf_walk.argtypes = [vp, u64, pmem, u64, pu64, pu64]
+    lib.ntedit_hip_reads_inflate_device.argtypes = [vp, vp, u64, ci, pmem, u64, vp, u64, vp]
+    lib.ntedit_hip_reads_inflate_model.argtypes = [vp, u64, pmem, u64, vp, u64, vp]
+    lib.ntedit_hip_reads_last_record_start.argtypes = [vp, u64, ci]
+    lib.ntedit_hip_reads_last_record_start.restype = u64
+    lib.ntedit_hip_reads_last_start_device.argtypes = [vp, vp, u64, ci, pu64]
+    lib.ntedit_hip_reads_inflate_info.argtypes = [vp, ctypes.POINTER(ReadsInflateStats)]
     _lib = lib
     return lib

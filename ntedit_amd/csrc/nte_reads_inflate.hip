@@ -1,0 +1,679 @@
+// nte_reads_inflate.hip -- gfx950 kernels and C ABI of --gpu_parse on BGZF reads: the members of a bgzip file are
+// shipped compressed, inflated and checked against their CRC-32 in HBM, and the inflated bytes handed to the parse
+// kernels (nte_reads_parse.hip) without ever existing on the host.  The decoder is nte_bgzf_inflate.h, written once
+// for the kernel and for the serial host model (ntedit_hip_reads_inflate_model, below).
+//
+//   k_bz_inflate      one wavefront per member, four members per workgroup of 256; no wave waits for another.  The
+//                     wave's tables are its 3.6 KiB of LDS; the compressed bytes come from global memory through a 64-bit
+//                     bit buffer; the output window is the member's own output in global memory.  The CRC-32 is fused:
+//                     the wave that inflated the member has its bytes in the caches, each lane takes a contiguous piece,
+//                     and the pieces are combined in GF(2).  One status word per member, an ordinary store.
+//   k_bz_last_start   the chunk cut: over the line table of nte_reads_parse.hip, the last record start by the rule of
+//                     last_record_start (reads_pass.cpp), an atomic max over the lines; 0: none.
+//
+// Like nte_reads_parse.hip this unit is outside KSRC and sees no context internals: its state hangs off the context
+// pointer, its scratch grows only and goes with ntedit_hip_sketch_free.  It works on the parse unit's two streams.
+#include "nte_common.h"
+#include "nte_bgzf_inflate.h"
+
+#include "../../include/ntedit_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace nte;
+using namespace nte_bgzf;
+
+namespace nte_reads {
+int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+int parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream);
+int parse_lines(const ntedit_hip_ctx* c, const unsigned char* d_raw, uint64_t n, const uint32_t** line_end, uint64_t* n_lines,
+                uint32_t* broken);
+}
+
+namespace {
+
+constexpr int BZ_TPB = 256;
+constexpr int BZ_WAVES = BZ_TPB / 64;
+
+static_assert(NTEDIT_INFLATE_BAD_BLOCK == BZ_BAD_BLOCK && NTEDIT_INFLATE_BAD_CODES == BZ_BAD_CODES && NTEDIT_INFLATE_BAD_DIST == BZ_BAD_DIST &&
+                  NTEDIT_INFLATE_OUT_OVER == BZ_OUT_OVER && NTEDIT_INFLATE_IN_OVER == BZ_IN_OVER && NTEDIT_INFLATE_SHORT_OUT == BZ_SHORT_OUT &&
+                  NTEDIT_INFLATE_LEFT_IN == BZ_LEFT_IN && NTEDIT_INFLATE_BAD_CRC == BZ_BAD_CRC && NTEDIT_INFLATE_BAD_STORED == BZ_BAD_STORED &&
+                  NTEDIT_INFLATE_BAD_SYMBOL == BZ_BAD_SYMBOL,
+              "the header names the decoder's reasons");
+static_assert(sizeof(BzTables) <= 4096, "a wave's tables: 16 waves in well under 160 KiB of LDS");
+
+typedef ntedit_hip_bgzf_member Member;
+
+// the host has checked every member against n_comp and out_cap (members_fit)
+__global__ __launch_bounds__(BZ_TPB) void
+k_bz_inflate(const u8* __restrict__ comp, const Member* __restrict__ members, u32 n_members, u8* out, u32* __restrict__ status)
+{
+	__shared__ BzTables s_tables[BZ_WAVES];
+	const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const u32 m = blockIdx.x * BZ_WAVES + wave;
+	if (m >= n_members) {
+		return;
+	}
+	const Member mb = members[m];
+	u8* dst = out + mb.out_off;
+	u32 st = bz_inflate(comp + mb.in_off, mb.n_in, dst, mb.n_out, &s_tables[wave], lane, 64);
+	if (st == BZ_OK) {
+		BZ_SYNC(); // the member's bytes were stored by all lanes
+		u32 term = bz_crc_term(dst, mb.n_out, lane, 64);
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			term ^= __shfl_xor(term, d, 64);
+		}
+		if (~term != mb.crc) {
+			st = BZ_BAD_CRC;
+		}
+	}
+	if (lane == 0) {
+		status[m] = st;
+	}
+}
+
+// One lane per line L >= 1 whose first byte lies inside the buffer: a record start when it starts with '>' (FASTA), or
+// with '@' while line L + 2, inside the buffer, starts with '+' (FASTQ).  Line j exists with its first byte below n
+// exactly when j < n_lines.  *cut = the largest such start; it stays 0 when there is none (line 0 is no candidate).
+__global__ __launch_bounds__(BZ_TPB) void
+k_bz_last_start(const u8* __restrict__ raw, const u32* __restrict__ line_end, u64 n_lines, int kind, u32* cut)
+{
+	const u64 line = (u64)blockIdx.x * BZ_TPB + threadIdx.x + 1;
+	if (line >= n_lines) {
+		return;
+	}
+	const u32 s = line_end[line - 1] + 1;
+	bool start;
+	if (kind == '>') {
+		start = raw[s] == '>';
+	} else {
+		start = raw[s] == '@' && line + 2 < n_lines && raw[line_end[line + 1] + 1] == '+';
+	}
+	if (start) {
+		atomicMax(cut, s);
+	}
+}
+
+// ------------------------------------------------------------------ host side
+struct InflateState
+{
+	const ntedit_hip_ctx* owner = nullptr;
+	ntedit_hip_reads_inflate_stats info = {};
+	int device = -1;
+	hipStream_t stream = nullptr, copy_stream = nullptr; // the parse unit's
+	hipEvent_t ev[2] = { nullptr, nullptr }, copied[2] = { nullptr, nullptr };
+	// device scratch, grow-only, released by ntedit_hip_sketch_free
+	u8* d_comp[2] = { nullptr, nullptr };
+	u64 comp_cap[2] = { 0, 0 };
+	u8* d_members[2] = { nullptr, nullptr };
+	u64 members_cap[2] = { 0, 0 };
+	u8* d_raw[2] = { nullptr, nullptr }; // the inflated chunk (a carried tail, then the members) and the next one's
+	u64 raw_cap[2] = { 0, 0 };
+	int cur = 0;
+	u8* d_status = nullptr;
+	u64 status_cap = 0;
+	u32* h_status = nullptr; // page-locked
+	u64 h_status_cap = 0;
+	u32* d_cut = nullptr;
+	u32* h_cut = nullptr; // page-locked
+};
+
+std::mutex g_inflate_mu;
+std::vector<InflateState*> g_inflate;
+
+InflateState*
+inflate_state(const ntedit_hip_ctx* c, bool create)
+{
+	std::lock_guard<std::mutex> lk(g_inflate_mu);
+	for (InflateState* s : g_inflate) {
+		if (s->owner == c) {
+			return s;
+		}
+	}
+	if (!create) {
+		return nullptr;
+	}
+	InflateState* s = new InflateState();
+	s->owner = c;
+	g_inflate.push_back(s);
+	return s;
+}
+
+int
+pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
+{
+	return nte_reads::set_error(c, code, why);
+}
+
+#define BZ_TRY(ctx, expr)                                                                         \
+	do {                                                                                          \
+		hipError_t e_ = (expr);                                                                   \
+		if (e_ != hipSuccess) {                                                                   \
+			return pfail((ctx), NTEDIT_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
+		}                                                                                         \
+	} while (0)
+
+int
+ensure_device(const ntedit_hip_ctx* c, InflateState* s)
+{
+	if (s->device >= 0) {
+		BZ_TRY(c, hipSetDevice(s->device));
+		return 0;
+	}
+	void *stream = nullptr, *copy_stream = nullptr;
+	const int rc = nte_reads::parse_streams(c, &stream, &copy_stream);
+	if (rc) {
+		return rc;
+	}
+	int device = 0;
+	BZ_TRY(c, hipGetDevice(&device));
+	s->stream = (hipStream_t)stream;
+	s->copy_stream = (hipStream_t)copy_stream;
+	for (hipEvent_t& e : s->ev) {
+		BZ_TRY(c, hipEventCreate(&e));
+	}
+	for (hipEvent_t& e : s->copied) {
+		BZ_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+	}
+	BZ_TRY(c, hipMalloc((void**)&s->d_cut, sizeof(u32)));
+	BZ_TRY(c, hipHostMalloc((void**)&s->h_cut, sizeof(u32), hipHostMallocDefault));
+	s->device = device;
+	return 0;
+}
+
+// *p to at least `need` bytes, the first `keep` bytes kept (copied on the stream, which is then drained)
+int
+grow(const ntedit_hip_ctx* c, InflateState* s, u8** p, u64* cap, u64 need, u64 keep)
+{
+	if (need <= *cap && *p) {
+		return 0;
+	}
+	const u64 want = (need + need / 4 + (1u << 20)) / 256 * 256;
+	u8* q = nullptr;
+	BZ_TRY(c, hipMalloc((void**)&q, want));
+	if (*p) {
+		if (keep) {
+			BZ_TRY(c, hipMemcpyAsync(q, *p, keep, hipMemcpyDeviceToDevice, s->stream));
+		}
+		BZ_TRY(c, hipStreamSynchronize(s->stream));
+		BZ_TRY(c, hipFree(*p));
+	}
+	*p = q;
+	*cap = want;
+	return 0;
+}
+
+int
+grow_status(const ntedit_hip_ctx* c, InflateState* s, u64 n_members)
+{
+	int rc = grow(c, s, &s->d_status, &s->status_cap, n_members * 4, 0);
+	if (rc == 0 && n_members > s->h_status_cap) {
+		if (s->h_status) {
+			BZ_TRY(c, hipHostFree(s->h_status));
+			s->h_status = nullptr;
+		}
+		const u64 want = n_members + n_members / 4 + 1024;
+		BZ_TRY(c, hipHostMalloc((void**)&s->h_status, want * 4, hipHostMallocDefault));
+		s->h_status_cap = want;
+	}
+	return rc;
+}
+
+void
+release_scratch(InflateState* s)
+{
+	if (s->device < 0) {
+		return;
+	}
+	(void)hipSetDevice(s->device);
+	for (hipStream_t st : { s->stream, s->copy_stream }) {
+		if (st) {
+			(void)hipStreamSynchronize(st);
+		}
+	}
+	for (hipEvent_t e : { s->ev[0], s->ev[1], s->copied[0], s->copied[1] }) {
+		if (e) {
+			(void)hipEventDestroy(e);
+		}
+	}
+	for (void* p : { (void*)s->d_comp[0], (void*)s->d_comp[1], (void*)s->d_members[0], (void*)s->d_members[1], (void*)s->d_raw[0],
+	                 (void*)s->d_raw[1], (void*)s->d_status, (void*)s->d_cut }) {
+		if (p) {
+			(void)hipFree(p);
+		}
+	}
+	for (void* p : { (void*)s->h_status, (void*)s->h_cut }) {
+		if (p) {
+			(void)hipHostFree(p);
+		}
+	}
+	const ntedit_hip_ctx* owner = s->owner;
+	const ntedit_hip_reads_inflate_stats info = s->info;
+	*s = InflateState();
+	s->owner = owner;
+	s->info = info;
+}
+
+// every member inside its buffers: what the kernel relies on
+bool
+members_fit(const Member* m, u64 n_members, u64 n_comp, u64 out_cap)
+{
+	for (u64 i = 0; i < n_members; i++) {
+		if (m[i].in_off > n_comp || m[i].n_in > n_comp - m[i].in_off || m[i].out_off > out_cap || m[i].n_out > out_cap - m[i].out_off) {
+			return false;
+		}
+	}
+	return true;
+}
+
+// the members of d_comp (table d_members) into d_out, their statuses to s->h_status; the stream is drained
+int
+inflate_on_device(const ntedit_hip_ctx* c, InflateState* s, const u8* d_comp, const Member* d_members, u64 n_members, u8* d_out)
+{
+	if (n_members == 0) {
+		return 0;
+	}
+	int rc = grow_status(c, s, n_members);
+	if (rc) {
+		return rc;
+	}
+	BZ_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	const unsigned blocks = (unsigned)((n_members + BZ_WAVES - 1) / BZ_WAVES);
+	hipLaunchKernelGGL(k_bz_inflate, dim3(blocks), dim3(BZ_TPB), 0, s->stream, d_comp, d_members, (u32)n_members, d_out, (u32*)s->d_status);
+	BZ_TRY(c, hipGetLastError());
+	BZ_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	BZ_TRY(c, hipMemcpyAsync(s->h_status, s->d_status, n_members * 4, hipMemcpyDeviceToHost, s->stream));
+	BZ_TRY(c, hipStreamSynchronize(s->stream));
+	float ms = 0;
+	BZ_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	s->info.ms_kernels += ms;
+	return 0;
+}
+
+const char*
+reason_text(u32 st)
+{
+	static const char* const names[] = { "ok",
+		                                 "a block of type 3",
+		                                 "a bad code set",
+		                                 "a distance before the member's first byte",
+		                                 "more output than ISIZE",
+		                                 "the stream runs past the member's compressed bytes",
+		                                 "less output than ISIZE",
+		                                 "compressed bytes left over",
+		                                 "CRC-32 mismatch",
+		                                 "a stored block with a bad length",
+		                                 "bits that are no code" };
+	return st < sizeof names / sizeof names[0] ? names[st] : "unknown";
+}
+
+uint32_t
+le16(const unsigned char* d)
+{
+	return (uint32_t)d[0] | (uint32_t)d[1] << 8;
+}
+
+uint32_t
+le32(const unsigned char* d)
+{
+	return le16(d) | le16(d + 2) << 16;
+}
+
+} // namespace
+
+// what the pass loop of reads_pass.cpp needs beyond the public calls
+namespace nte_reads {
+
+void
+inflate_release(const ntedit_hip_ctx* c)
+{
+	InflateState* s = inflate_state(c, false);
+	if (s) {
+		release_scratch(s);
+	}
+}
+
+ntedit_hip_reads_inflate_stats*
+inflate_info(const ntedit_hip_ctx* c)
+{
+	return &inflate_state(c, true)->info;
+}
+
+const char*
+inflate_reason(uint32_t st)
+{
+	return reason_text(st);
+}
+
+// a chunk's compressed bytes and member table -> buffers `which`, on the copy stream; returns at once
+int
+inflate_copy_begin(const ntedit_hip_ctx* c, int which, const char* comp, uint64_t n_comp, const ntedit_hip_bgzf_member* members,
+                   uint64_t n_members)
+{
+	InflateState* s = inflate_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, s, &s->d_comp[which], &s->comp_cap[which], n_comp, 0);
+	}
+	if (rc == 0) {
+		rc = grow(c, s, &s->d_members[which], &s->members_cap[which], n_members * sizeof(Member), 0);
+	}
+	if (rc) {
+		return rc;
+	}
+	if (n_comp) {
+		BZ_TRY(c, hipMemcpyAsync(s->d_comp[which], comp, n_comp, hipMemcpyHostToDevice, s->copy_stream));
+	}
+	if (n_members) {
+		BZ_TRY(c, hipMemcpyAsync(s->d_members[which], members, n_members * sizeof(Member), hipMemcpyHostToDevice, s->copy_stream));
+	}
+	BZ_TRY(c, hipEventRecord(s->copied[which], s->copy_stream));
+	return 0;
+}
+
+int
+inflate_copy_wait(const ntedit_hip_ctx* c, int which)
+{
+	InflateState* s = inflate_state(c, false);
+	if (s && s->copied[which]) {
+		BZ_TRY(c, hipEventSynchronize(s->copied[which]));
+	}
+	return 0;
+}
+
+// Waits for that copy, then inflates its members (the host's copy of the table: `members`, checked here) behind the
+// `tail` bytes the current raw buffer already holds.  *raw: the buffer.  *bad: the first refused member, or n_members.
+int
+inflate_copied(const ntedit_hip_ctx* c, int which, uint64_t n_comp, const ntedit_hip_bgzf_member* members, uint64_t n_members,
+               uint64_t tail, uint64_t n_out, const char** raw, uint64_t* bad, uint32_t* reason)
+{
+	InflateState* s = inflate_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, s, &s->d_raw[s->cur], &s->raw_cap[s->cur], tail + n_out + 16, tail);
+	}
+	if (rc) {
+		return rc;
+	}
+	if (!members_fit(members, n_members, n_comp, n_out)) {
+		return pfail(c, NTEDIT_E_ARG, "reads_inflate: a member outside its buffers");
+	}
+	BZ_TRY(c, hipEventSynchronize(s->copied[which]));
+	*raw = (const char*)s->d_raw[s->cur];
+	*bad = n_members;
+	*reason = 0;
+	rc = inflate_on_device(c, s, s->d_comp[which], (const Member*)s->d_members[which], n_members, s->d_raw[s->cur] + tail);
+	if (rc) {
+		return rc;
+	}
+	for (uint64_t i = 0; i < n_members; i++) {
+		if (s->h_status[i]) {
+			*bad = i;
+			*reason = s->h_status[i];
+			break;
+		}
+	}
+	s->info.members += n_members;
+	s->info.comp_bytes += n_comp;
+	s->info.raw_bytes += n_out;
+	return 0;
+}
+
+// the last record start of the current raw buffer's first n bytes; *cut = 0: none.  *broken: the line table cannot
+// hold the bytes (the chunk is unclean then, whatever the cut)
+int
+inflate_last_start(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint64_t* cut, uint32_t* broken)
+{
+	InflateState* s = inflate_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc) {
+		return rc;
+	}
+	*cut = 0;
+	*broken = 0;
+	if (n < 2) {
+		return 0;
+	}
+	unsigned char kind = 0;
+	BZ_TRY(c, hipMemcpyAsync(&kind, d_raw, 1, hipMemcpyDeviceToHost, s->stream));
+	BZ_TRY(c, hipStreamSynchronize(s->stream));
+	if (kind != '>' && kind != '@') {
+		*cut = n; // (unclean anyway, as RawFeeder has it)
+		return 0;
+	}
+	BZ_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	const uint32_t* line_end = nullptr;
+	uint64_t n_lines = 0;
+	if ((rc = nte_reads::parse_lines(c, (const unsigned char*)d_raw, n, &line_end, &n_lines, broken)) != 0) {
+		return rc;
+	}
+	if (*broken) {
+		return 0;
+	}
+	BZ_TRY(c, hipMemsetAsync(s->d_cut, 0, sizeof(u32), s->stream));
+	if (n_lines > 1) {
+		const unsigned blocks = (unsigned)((n_lines - 1 + BZ_TPB - 1) / BZ_TPB);
+		hipLaunchKernelGGL(k_bz_last_start, dim3(blocks), dim3(BZ_TPB), 0, s->stream, (const u8*)d_raw, line_end, n_lines, (int)kind, s->d_cut);
+		BZ_TRY(c, hipGetLastError());
+	}
+	BZ_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	BZ_TRY(c, hipMemcpyAsync(s->h_cut, s->d_cut, sizeof(u32), hipMemcpyDeviceToHost, s->stream));
+	BZ_TRY(c, hipStreamSynchronize(s->stream));
+	float ms = 0;
+	BZ_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	s->info.ms_kernels += ms;
+	*cut = *s->h_cut;
+	return 0;
+}
+
+// the bytes [cut, total) of the current raw buffer to the front of the other one, which becomes the current
+int
+inflate_carry(const ntedit_hip_ctx* c, uint64_t cut, uint64_t total)
+{
+	InflateState* s = inflate_state(c, true);
+	const int other = s->cur ^ 1;
+	const uint64_t tail = total - cut;
+	int rc = grow(c, s, &s->d_raw[other], &s->raw_cap[other], tail + 16, 0);
+	if (rc) {
+		return rc;
+	}
+	if (tail) {
+		BZ_TRY(c, hipMemcpyAsync(s->d_raw[other], s->d_raw[s->cur] + cut, tail, hipMemcpyDeviceToDevice, s->stream));
+	}
+	s->cur = other;
+	return 0;
+}
+
+} // namespace nte_reads
+
+extern "C" {
+
+int
+ntedit_hip_reads_inflate_info(ntedit_hip_ctx* c, ntedit_hip_reads_inflate_stats* st)
+{
+	if (!c || !st) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_inflate_info: bad argument") : NTEDIT_E_ARG;
+	}
+	*st = inflate_state(c, true)->info;
+	return 0;
+}
+
+int
+ntedit_hip_reads_inflate_device(ntedit_hip_ctx* c, const void* comp, uint64_t n_comp, int on_device, const ntedit_hip_bgzf_member* members,
+                                uint64_t n_members, void* out_device, uint64_t out_cap, uint32_t* status)
+{
+	if (!c || !status || (n_members && (!members || !comp)) || (out_cap && !out_device) || n_members > 0xFFFFFFFFull ||
+	    (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE)) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_inflate_device: bad argument") : NTEDIT_E_ARG;
+	}
+	if (!members_fit(members, n_members, n_comp, out_cap)) {
+		return pfail(c, NTEDIT_E_ARG, "reads_inflate_device: a member outside comp[0 .. n_comp) or out[0 .. out_cap)");
+	}
+	InflateState* s = inflate_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc || n_members == 0) {
+		return rc;
+	}
+	const u8* d_comp = (const u8*)comp;
+	if (on_device == NTEDIT_HIP_BASES_HOST) {
+		if ((rc = grow(c, s, &s->d_comp[0], &s->comp_cap[0], n_comp, 0)) != 0) {
+			return rc;
+		}
+		if (n_comp) {
+			BZ_TRY(c, hipMemcpyAsync(s->d_comp[0], comp, n_comp, hipMemcpyHostToDevice, s->stream));
+		}
+		d_comp = s->d_comp[0];
+	}
+	if ((rc = grow(c, s, &s->d_members[0], &s->members_cap[0], n_members * sizeof(Member), 0)) != 0) {
+		return rc;
+	}
+	BZ_TRY(c, hipMemcpyAsync(s->d_members[0], members, n_members * sizeof(Member), hipMemcpyHostToDevice, s->stream));
+	if ((rc = inflate_on_device(c, s, d_comp, (const Member*)s->d_members[0], n_members, (u8*)out_device)) != 0) {
+		return rc;
+	}
+	memcpy(status, s->h_status, n_members * 4);
+	return 0;
+}
+
+// the serial model: the same header functions, one member after the other, the CRC over 64 pieces as the wave takes it
+int
+ntedit_hip_reads_inflate_model(const void* comp, uint64_t n_comp, const ntedit_hip_bgzf_member* members, uint64_t n_members, void* out,
+                               uint64_t out_cap, uint32_t* status)
+{
+	if (!status || (n_members && (!members || !comp)) || (out_cap && !out)) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_inflate_model: bad argument");
+	}
+	if (!members_fit(members, n_members, n_comp, out_cap)) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_inflate_model: a member outside comp[0 .. n_comp) or out[0 .. out_cap)");
+	}
+	BzTables* t = new BzTables();
+	for (uint64_t i = 0; i < n_members; i++) {
+		const Member& m = members[i];
+		u8* dst = (u8*)out + m.out_off;
+		u32 st = bz_inflate((const u8*)comp + m.in_off, m.n_in, dst, m.n_out, t, 0, 1);
+		if (st == BZ_OK) {
+			u32 crc = 0;
+			for (u32 lane = 0; lane < 64; lane++) {
+				crc ^= bz_crc_term(dst, m.n_out, lane, 64);
+			}
+			if (~crc != m.crc) {
+				st = BZ_BAD_CRC;
+			}
+		}
+		status[i] = st;
+	}
+	delete t;
+	return 0;
+}
+
+// BGZF (the SAM specification, section 4.1), as FastaMap::inflate_bgzf walks it: gzip members with FLG = FEXTRA and
+// an extra subfield 'B','C' of two bytes holding the member's total size - 1; CRC-32 and ISIZE close each member.
+int
+ntedit_hip_bgzf_walk(const void* bytes, uint64_t n, ntedit_hip_bgzf_member* members, uint64_t cap, uint64_t* n_members, uint64_t* consumed)
+{
+	if ((n && !bytes) || (cap && !members) || !n_members || !consumed) {
+		return pfail(nullptr, NTEDIT_E_ARG, "bgzf_walk: bad argument");
+	}
+	const unsigned char* d = (const unsigned char*)bytes;
+	uint64_t o = 0, count = 0, total = 0;
+	int rc = NTEDIT_BGZF_END;
+	while (o < n) {
+		static const unsigned char magic[4] = { 0x1f, 0x8b, 8, 4 };
+		const uint64_t left = n - o;
+		if (memcmp(d + o, magic, left < 4 ? left : 4) != 0) {
+			rc = NTEDIT_BGZF_NOT;
+			break;
+		}
+		if (left < 12) {
+			rc = NTEDIT_BGZF_CUT;
+			break;
+		}
+		const uint32_t xlen = le16(d + o + 10);
+		if (left < 12 + (uint64_t)xlen) {
+			rc = NTEDIT_BGZF_CUT;
+			break;
+		}
+		uint32_t bsize = 0;
+		bool have = false;
+		for (uint64_t x = o + 12; x + 4 <= o + 12 + xlen;) {
+			const uint32_t slen = le16(d + x + 2);
+			if (d[x] == 'B' && d[x + 1] == 'C' && slen == 2 && x + 6 <= o + 12 + xlen) {
+				bsize = le16(d + x + 4);
+				have = true;
+			}
+			x += 4 + (uint64_t)slen;
+		}
+		const uint64_t member = (uint64_t)bsize + 1;
+		if (!have || member < 12 + (uint64_t)xlen + 8) {
+			rc = NTEDIT_BGZF_NOT;
+			break;
+		}
+		if (member > left) {
+			rc = NTEDIT_BGZF_CUT;
+			break;
+		}
+		const uint32_t n_out = le32(d + o + member - 4);
+		if (n_out > 65536) {
+			rc = NTEDIT_BGZF_NOT;
+			break;
+		}
+		if (count == cap) {
+			rc = NTEDIT_BGZF_FULL;
+			break;
+		}
+		ntedit_hip_bgzf_member& m = members[count++];
+		m.in_off = o + 12 + xlen;
+		m.out_off = total;
+		m.n_in = (uint32_t)(member - 12 - xlen - 8);
+		m.n_out = n_out;
+		m.crc = le32(d + o + member - 8);
+		m.reserved = 0;
+		total += n_out;
+		o += member;
+	}
+	*n_members = count;
+	*consumed = o;
+	return rc;
+}
+
+int
+ntedit_hip_reads_last_start_device(ntedit_hip_ctx* c, const void* buf, uint64_t n, int on_device, uint64_t* cut)
+{
+	if (!c || !cut || (n && !buf) || n >= (1ull << 31) || (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) ||
+	    (on_device == NTEDIT_HIP_BASES_DEVICE && ((uintptr_t)buf & 15))) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_last_start_device: bad argument") : NTEDIT_E_ARG;
+	}
+	InflateState* s = inflate_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc) {
+		return rc;
+	}
+	const char* d_buf = (const char*)buf;
+	if (on_device == NTEDIT_HIP_BASES_HOST) {
+		if ((rc = grow(c, s, &s->d_raw[s->cur], &s->raw_cap[s->cur], n + 16, 0)) != 0) {
+			return rc;
+		}
+		if (n) {
+			BZ_TRY(c, hipMemcpyAsync(s->d_raw[s->cur], buf, n, hipMemcpyHostToDevice, s->stream));
+		}
+		d_buf = (const char*)s->d_raw[s->cur];
+	}
+	uint32_t broken = 0;
+	uint64_t at = 0;
+	if ((rc = nte_reads::inflate_last_start(c, d_buf, n, &at, &broken)) != 0) {
+		return rc;
+	}
+	if (broken) {
+		return pfail(c, NTEDIT_E_ARG, "reads_last_start_device: more than one line per 8 bytes");
+	}
+	*cut = at ? at : NTEDIT_READS_NO_START;
+	return 0;
+}
+
+} // extern "C"

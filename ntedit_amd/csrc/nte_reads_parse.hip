@@ -37,6 +37,7 @@ using namespace nte_parse;
 
 namespace nte_reads {
 int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+void inflate_release(const ntedit_hip_ctx* c); // (nte_reads_inflate.hip: its scratch works on this unit's streams)
 }
 
 namespace {
@@ -698,10 +699,88 @@ namespace nte_reads {
 void
 parse_release(const ntedit_hip_ctx* c)
 {
+	inflate_release(c);
 	ParseState* s = parse_state(c, false);
 	if (s) {
 		release_scratch(s);
 	}
+}
+
+// the inflate unit (nte_reads_inflate.hip) works on this unit's two streams ...
+int
+parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream)
+{
+	ParseState* s = parse_state(c, true);
+	const int rc = ensure_device(c, s);
+	if (rc == 0) {
+		*stream = (void*)s->stream;
+		*copy_stream = (void*)s->copy_stream;
+	}
+	return rc;
+}
+
+// ... cuts a chunk on the line table: the first phases of parse_on_device over device bytes, queued on the stream.
+// *broken: RP_BAD_SIZE / RP_BAD_TABLE when the table cannot hold the chunk (nothing is queued then).
+int
+parse_lines(const ntedit_hip_ctx* c, const unsigned char* d_raw, uint64_t n, const uint32_t** line_end, uint64_t* n_lines,
+            uint32_t* broken)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc) {
+		return rc;
+	}
+	*line_end = nullptr;
+	*n_lines = 0;
+	*broken = n >= RP_MAX_RAW ? (uint32_t)RP_BAD_SIZE : 0u;
+	if (n == 0 || *broken) {
+		return 0;
+	}
+	if (n > s->table_raw || !s->d_table) {
+		const u64 want = n + (1u << 20);
+		if (s->d_table) {
+			RP_TRY(c, hipFree(s->d_table));
+			s->d_table = nullptr;
+			s->table_raw = 0;
+		}
+		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
+		s->table_raw = want;
+	}
+	const Table t = carve(s->d_table, s->table_raw);
+	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
+	RP_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
+	hipLaunchKernelGGL(k_rp_tiles, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, s->d_info);
+	scan(s, t.tile, tiles, t.bsum);
+	RP_TRY(c, hipGetLastError());
+	RP_TRY(c, hipMemcpyAsync(&s->h_info->newlines, t.tile + tiles, 8, hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, 16, hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipStreamSynchronize(s->stream));
+	const u64 lines = s->h_info->newlines + (s->h_info->last_nl ? 0 : 1);
+	if (lines > rp_max_lines(n)) {
+		*broken = RP_BAD_TABLE;
+		return 0;
+	}
+	hipLaunchKernelGGL(k_rp_line_ends, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, lines, s->d_info);
+	RP_TRY(c, hipGetLastError());
+	*line_end = t.line_end;
+	*n_lines = lines;
+	return 0;
+}
+
+// ... and has device bytes parsed into the context's text buffer, as parse_copied does for a copied chunk
+int
+parse_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, &s->d_text, &s->text_cap, n);
+	}
+	if (rc) {
+		return rc;
+	}
+	*text = (const char*)s->d_text;
+	return parse_on_device(c, s, (const u8*)d_raw, n, k, s->d_text, s->text_cap, res);
 }
 
 int

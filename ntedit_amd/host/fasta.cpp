@@ -272,6 +272,19 @@ FastaReader::fill_()
 	return true;
 }
 
+void
+FastaReader::skip(unsigned long long n)
+{
+	while (n && ok()) {
+		if (begin_ >= end_ && !fill_()) {
+			break;
+		}
+		const unsigned long long take = n < (unsigned long long)(end_ - begin_) ? n : (unsigned long long)(end_ - begin_);
+		begin_ += (int)take;
+		n -= take;
+	}
+}
+
 int
 FastaReader::getc_()
 {

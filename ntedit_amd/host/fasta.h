@@ -39,6 +39,8 @@ class FastaReader
 	// once next() has returned false: the offset of the first byte of the record it stopped before (the limit's), the
 	// offset of the end of the input if it ran out first, ~0 if a record failed to parse (plain files: file offsets)
 	unsigned long long next_start() const { return next_start_; }
+	// before the first next(): n bytes of the (inflated) input are read and dropped; offsets keep counting them
+	void skip(unsigned long long n);
 
   private:
 	bool fill_();

@@ -84,8 +84,9 @@ static const char USAGE[] = PROGRAM
     "	--hist FILE,	write the k-mer histogram (ntCard's text format)\n"
     "	--save_bf FILE,	write the filter that was built (the same bytes as ntedit-make-reads-bf -o); its name is the\n"
     "			_r part of the default prefix [default name: reads_k<K>.bf, not written]\n"
-    "	--gpu_parse,	parse plain (not gzip) read files on the GPU: the host ships raw file bytes (same outputs;\n"
-    "			gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with the host parser)\n"
+    "	--gpu_parse,	parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes, BGZF\n"
+    "			still compressed, and the device inflates them (same outputs; single-stream gzip files and files\n"
+    "			outside the clean FASTA / 4-line FASTQ grammar stay with the host parser)\n"
     "	--reject_cutoff R,	also build the -e filter (k-mers to reject, e.g. repeats) from the same pass over the reads: a\n"
     "			plain filter of the k-mers seen at least R times, 2 to 255 and above the cutoff (replaces -e;\n"
     "			not with --counts)\n"

@@ -70,9 +70,10 @@ usage(const char* why)
 	       "                  --num_elements is the number of k-mers the histogram puts at cmin or above)\n"
 	       "  --sketch_bytes  Counters of the count-min sketch [default: 16 x the output bytes, or sized from the\n"
 	       "                  histogram one per input byte (gzip: 4 x), 64 MiB to 32 GiB]\n"
-	       "  --gpu_parse     Parse plain (not gzip) read files on the GPU: the host ships raw file bytes.  The output is\n"
-	       "                  the same; gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with\n"
-	       "                  the host parser\n"
+	       "  --gpu_parse     Parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes,\n"
+	       "                  BGZF still compressed, and the device inflates them.  The output is the same; single-stream\n"
+	       "                  gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with the host\n"
+	       "                  parser (recompress with `bgzip -@ 16 reads.fq`)\n"
 	       "  -o              Name for output filter [default: \"reads_k<K>.bf\"]\n"
 	       "  -t              Number of threads (accepted; the k-mers are counted on the GPU) [default: 12]\n"
 	       "  --reject_cutoff Also write the reject filter for ntedit -e (k-mers to reject, e.g. repeats): a plain filter of\n"

@@ -40,6 +40,17 @@ ntedit_hip_reads_parse_stats* parse_info(const ntedit_hip_ctx* c);
 int parse_copy_begin(const ntedit_hip_ctx* c, int which, const char* host, uint64_t n);
 int parse_copy_wait(const ntedit_hip_ctx* c, int which);
 int parse_copied(const ntedit_hip_ctx* c, int which, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res);
+int parse_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res);
+// --gpu_parse on BGZF files (nte_reads_inflate.hip): its counters, its two compressed buffers, the inflated chunk
+ntedit_hip_reads_inflate_stats* inflate_info(const ntedit_hip_ctx* c);
+const char* inflate_reason(uint32_t st);
+int inflate_copy_begin(const ntedit_hip_ctx* c, int which, const char* comp, uint64_t n_comp, const ntedit_hip_bgzf_member* members,
+                       uint64_t n_members);
+int inflate_copy_wait(const ntedit_hip_ctx* c, int which);
+int inflate_copied(const ntedit_hip_ctx* c, int which, uint64_t n_comp, const ntedit_hip_bgzf_member* members, uint64_t n_members,
+                   uint64_t tail, uint64_t n_out, const char** raw, uint64_t* bad, uint32_t* reason);
+int inflate_last_start(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint64_t* cut, uint32_t* broken);
+int inflate_carry(const ntedit_hip_ctx* c, uint64_t cut, uint64_t total);
 }
 
 namespace {
@@ -128,9 +139,14 @@ find_record_start(const char* path, uint64_t begin, uint64_t* out, std::string* 
 // every record of one range, in order: seq(record) for each; *start / *next as ntedit_hip_reads_pass reports them
 bool
 read_range(const char* path, uint64_t begin, uint64_t end, const std::function<bool(const std::string&)>& seq_fn,
-           uint64_t* start, uint64_t* next, std::string* why, bool exact = false)
+           uint64_t* start, uint64_t* next, std::string* why, bool exact = false, uint64_t skip = 0)
 {
 	uint64_t s = exact ? begin : 0; // exact: begin is a record start (where --gpu_parse hands a range back)
+	if (skip) {
+		// a whole gzip file from the inflated offset `skip`, a record start (where --gpu_parse hands a BGZF file back):
+		// the bytes before it are inflated and dropped
+		s = skip;
+	}
 	if (begin > 0 || end != WHOLE) {
 		struct stat st;
 		if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) {
@@ -150,11 +166,12 @@ read_range(const char* path, uint64_t begin, uint64_t end, const std::function<b
 		*next = s; // no record starts in the range
 		return true;
 	}
-	nte_host::FastaReader reader(path, s, end);
+	nte_host::FastaReader reader(path, skip ? 0 : s, end);
 	if (!reader.ok()) {
 		*why = std::string("cannot open ") + path;
 		return false;
 	}
+	reader.skip(skip);
 	std::string hdr, seq;
 	for (;;) {
 		seq.clear();
@@ -178,6 +195,7 @@ struct Range
 	const char* path;
 	uint64_t begin, end;
 	bool exact = false; // begin is a record start: no search for one
+	uint64_t skip = 0;  // of a whole gzip file: the inflated offset, a record start, the records are taken from
 };
 
 // page-locked batch buffers: the parser fills one while the GPU works on the other
@@ -322,7 +340,7 @@ class BatchFeeder
 				stopped = !add_(b, seq);
 				return !stopped;
 			};
-			const bool ok = read_range(r.path, r.begin, r.end, add, &start, &next, &why, r.exact);
+			const bool ok = read_range(r.path, r.begin, r.end, add, &start, &next, &why, r.exact, r.skip);
 			if (stopped) {
 				return; // (add_ failed the feeder, or it is being torn down)
 			}
@@ -591,9 +609,223 @@ class RawFeeder
 	std::thread th_;
 };
 
+// ------------------------------------------------------------------ --gpu_parse: BGZF files stay compressed
+// Whether the file starts with a BGZF member (bgzf_walk finds one, or finds its header and the buffer's end)
+bool
+is_bgzf(const char* path)
+{
+	unsigned char head[4096];
+	FILE* fp = fopen(path, "rb");
+	const size_t got = fp ? fread(head, 1, sizeof head, fp) : 0;
+	if (fp) {
+		fclose(fp);
+	}
+	uint64_t found = 0, used = 0;
+	const int rc = ntedit_hip_bgzf_walk(head, got, nullptr, 0, &found, &used);
+	return got >= 28 && (rc == NTEDIT_BGZF_FULL || (rc == NTEDIT_BGZF_CUT && got == sizeof head));
+}
+
+// A BGZF file as chunks of whole members whose ISIZE sum stays within batch_bytes (at least one member), compressed,
+// double-buffered through page-locked memory as RawFeeder's chunks are; nothing is inflated here.  The last chunk says
+// how the members ended: with the file, or at something that is no (whole) BGZF member.
+struct BgzfChunk
+{
+	char* p = nullptr;
+	size_t cap = 0, len = 0; // len: the compressed bytes of its members
+	ntedit_hip_bgzf_member* m = nullptr;
+	size_t m_cap = 0, n_members = 0;
+	uint64_t n_out = 0;        // their ISIZE sum
+	uint64_t first_member = 0; // the index of m[0] in the file
+	bool last = false;
+	bool whole = true; // (last) the file ended behind a whole member
+};
+
+class BgzfFeeder
+{
+  public:
+	BgzfFeeder(const char* path, size_t batch_bytes)
+	    : path_(path), batch_bytes_(batch_bytes < RAW_CHUNK_MAX ? batch_bytes : RAW_CHUNK_MAX)
+	{
+		for (BgzfChunk& b : bufs_) {
+			free_.push_back(&b);
+		}
+		th_ = std::thread([this] { run_(); });
+	}
+	~BgzfFeeder()
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			stop_ = true;
+		}
+		cv_.notify_all();
+		th_.join();
+		for (BgzfChunk& b : bufs_) {
+			ntedit_hip_host_free(b.p);
+			ntedit_hip_host_free(b.m);
+		}
+	}
+	BgzfChunk* take()
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		cv_.wait(lk, [this] { return !full_.empty() || failed_; });
+		if (full_.empty()) {
+			return nullptr;
+		}
+		BgzfChunk* b = full_.front();
+		full_.pop_front();
+		return b;
+	}
+	void give_back(BgzfChunk* b)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			free_.push_back(b);
+		}
+		cv_.notify_all();
+	}
+	const std::string& error() const { return err_; }
+
+  private:
+	void fail_(const std::string& why)
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			err_ = why;
+			failed_ = true;
+		}
+		cv_.notify_all();
+	}
+	static bool reserve_(char** p, size_t* cap, size_t need, size_t keep)
+	{
+		if (need <= *cap) {
+			return true;
+		}
+		const size_t want = need + need / 2;
+		char* q = (char*)ntedit_hip_host_alloc(want);
+		if (!q) {
+			return false;
+		}
+		if (keep) {
+			memcpy(q, *p, keep);
+		}
+		ntedit_hip_host_free(*p);
+		*p = q;
+		*cap = want;
+		return true;
+	}
+	void run_()
+	{
+		const int fd = open(path_, O_RDONLY);
+		struct stat sb;
+		if (fd < 0 || fstat(fd, &sb) != 0) {
+			if (fd >= 0) {
+				close(fd);
+			}
+			fail_(std::string("cannot open ") + path_);
+			return;
+		}
+		const uint64_t size = (uint64_t)sb.st_size;
+		const size_t slab = batch_bytes_ / 4 + (128u << 10); // compressed bytes read at a time
+		std::vector<char> carry;                              // compressed bytes read behind the last chunk's members
+		uint64_t pos = 0, member = 0;
+		for (bool done = false; !done;) {
+			BgzfChunk* b;
+			{
+				std::unique_lock<std::mutex> lk(mu_);
+				cv_.wait(lk, [this] { return !free_.empty() || stop_; });
+				if (stop_) {
+					break;
+				}
+				b = free_.front();
+				free_.pop_front();
+			}
+			size_t have = carry.size(), walked = 0;
+			bool ok = reserve_(&b->p, &b->cap, have > slab ? have : slab, 0);
+			if (ok && have) {
+				memcpy(b->p, carry.data(), have);
+			}
+			b->n_members = 0;
+			b->n_out = 0;
+			b->first_member = member;
+			b->last = false;
+			b->whole = true;
+			while (ok) {
+				ntedit_hip_bgzf_member one;
+				uint64_t found = 0, used = 0;
+				const int rc = ntedit_hip_bgzf_walk(b->p + walked, have - walked, &one, 1, &found, &used);
+				if (found) {
+					if (b->n_members && b->n_out + one.n_out > batch_bytes_) {
+						break; // the chunk is full
+					}
+					size_t m_bytes = b->m_cap * sizeof one;
+					if (!(ok = reserve_((char**)&b->m, &m_bytes, (b->n_members + 1) * sizeof one, b->n_members * sizeof one))) {
+						break;
+					}
+					b->m_cap = m_bytes / sizeof one;
+					one.in_off += walked;
+					one.out_off = b->n_out;
+					b->m[b->n_members++] = one;
+					b->n_out += one.n_out;
+					walked += (size_t)used;
+					continue;
+				}
+				if (rc == NTEDIT_BGZF_NOT || pos + have >= size) {
+					// no member starts here, or the file ends inside one
+					b->last = true;
+					b->whole = rc != NTEDIT_BGZF_NOT && have == walked;
+					break;
+				}
+				const size_t more = size - (pos + have) < slab ? (size_t)(size - (pos + have)) : slab;
+				if (!(ok = reserve_(&b->p, &b->cap, have + more, have))) {
+					break;
+				}
+				if (!pread_all(fd, b->p + have, pos + have, more)) {
+					fail_(std::string(path_) + ": read error");
+					close(fd);
+					return;
+				}
+				have += more;
+			}
+			if (!ok) {
+				fail_("cannot allocate page-locked host memory");
+				close(fd);
+				return;
+			}
+			carry.assign(b->p + walked, b->p + have);
+			b->len = walked;
+			pos += walked;
+			member += b->n_members;
+			done = b->last;
+			{
+				std::lock_guard<std::mutex> lk(mu_);
+				full_.push_back(b);
+			}
+			cv_.notify_all();
+		}
+		close(fd);
+	}
+
+	const char* path_;
+	size_t batch_bytes_;
+	BgzfChunk bufs_[2];
+	std::deque<BgzfChunk*> free_, full_;
+	bool stop_ = false, failed_ = false;
+	std::string err_;
+	std::mutex mu_;
+	std::condition_variable cv_;
+	std::thread th_;
+};
+
 } // namespace
 
 extern "C" {
+
+uint64_t
+ntedit_hip_reads_last_record_start(const char* buf, uint64_t n, int kind)
+{
+	const size_t at = buf ? last_record_start(buf, (size_t)n, kind) : NONE;
+	return at == NONE ? NTEDIT_READS_NO_START : (uint64_t)at;
+}
 
 int
 ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, const uint64_t* begins, const uint64_t* ends,
@@ -657,10 +889,125 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 	} else {
 		ntedit_hip_reads_parse_stats& info = *nte_reads::parse_info(ctx);
 		info = ntedit_hip_reads_parse_stats();
+		ntedit_hip_reads_inflate_stats& zinfo = *nte_reads::inflate_info(ctx);
+		zinfo = ntedit_hip_reads_inflate_stats();
 		for (uint32_t i = 0; i < n; i++) {
 			const Range& r = ranges[i];
 			struct stat sb;
 			const bool regular = stat(r.path, &sb) == 0 && S_ISREG(sb.st_mode);
+			if (regular && r.begin == 0 && r.end == WHOLE && is_bgzf(r.path)) {
+				// a BGZF file, whole: shipped compressed, inflated and cut on the device.  `base` is the inflated
+				// offset of the raw buffer's first byte, always a record start; `tail` the bytes carried behind a cut.
+				zinfo.files++;
+				uint64_t base = 0, tail = 0;
+				bool handed_back = false;
+				{
+					BgzfFeeder feed(r.path, (size_t)batch_bytes);
+					BgzfChunk* cur = feed.take();
+					int which = 0;
+					if (!cur) {
+						return pfail(ctx, NTEDIT_E_IO, feed.error());
+					}
+					if (nte_reads::inflate_copy_begin(ctx, which, cur->p, cur->len, cur->m, cur->n_members) != 0) {
+						return NTEDIT_E_DEVICE;
+					}
+					while (cur) {
+						// the copy of chunk i + 1 runs while chunk i is inflated, parsed and counted
+						BgzfChunk* next = nullptr;
+						if (!cur->last) {
+							if (!(next = feed.take())) {
+								(void)nte_reads::inflate_copy_wait(ctx, which);
+								return pfail(ctx, NTEDIT_E_IO, feed.error());
+							}
+							if (nte_reads::inflate_copy_begin(ctx, which ^ 1, next->p, next->len, next->m, next->n_members) != 0) {
+								(void)nte_reads::inflate_copy_wait(ctx, which);
+								return NTEDIT_E_DEVICE;
+							}
+						}
+						const auto g0 = std::chrono::steady_clock::now();
+						const char* raw = nullptr;
+						uint64_t bad = 0, cut = 0;
+						uint32_t reason = 0, broken = 0;
+						int rc = nte_reads::inflate_copied(ctx, which, cur->len, cur->m, cur->n_members, tail, cur->n_out, &raw, &bad, &reason);
+						const uint64_t total = tail + cur->n_out, first_member = cur->first_member;
+						const bool last = cur->last, whole = cur->whole;
+						feed.give_back(cur); // (its copy is done: the reader may fill it again)
+						if (rc == 0 && reason) {
+							zinfo.bad_member = first_member + bad;
+							zinfo.bad_reason = reason;
+							(void)nte_reads::inflate_copy_wait(ctx, which ^ 1);
+							return pfail(ctx, NTEDIT_E_IO, std::string(r.path) + ": BGZF member " + std::to_string(first_member + bad) +
+							                                   " is damaged (" + nte_reads::inflate_reason(reason) + ")");
+						}
+						// the chunk's cut: the end of the file's bytes, else the last record start on the device
+						if (rc == 0) {
+							if (last && whole) {
+								cut = total;
+							} else {
+								rc = nte_reads::inflate_last_start(ctx, raw, total, &cut, &broken);
+							}
+						}
+						ntedit_hip_reads_parse_result res = ntedit_hip_reads_parse_result();
+						res.clean = 1;
+						const char* text = nullptr;
+						if (rc == 0 && broken) {
+							res.clean = 0;
+							res.broken = broken;
+						} else if (rc == 0 && cut) {
+							rc = nte_reads::parse_buffer(ctx, raw, cut, k, &text, &res);
+						}
+						if (rc == 0 && res.clean && res.text_len) {
+							rc = run_batch(text, res.text_len, NTEDIT_HIP_BASES_DEVICE);
+						}
+						if (rc) {
+							(void)nte_reads::inflate_copy_wait(ctx, which ^ 1);
+							return pfail(ctx, rc, ntedit_hip_reads_last_error(ctx));
+						}
+						gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
+						if (!res.clean) {
+							info.fallback_chunks++;
+							info.broken |= res.broken;
+							handed_back = true;
+							(void)nte_reads::inflate_copy_wait(ctx, which ^ 1); // (before the feeder frees the buffer it reads)
+							break;
+						}
+						if (cut) {
+							info.device_chunks++;
+							info.raw_bytes += cut;
+							info.text_bytes += res.text_len;
+							bases += res.bases;
+						}
+						// a chunk without a record start past its first byte grows by the next one (cut = 0: all is tail)
+						if (cut && cut < total && nte_reads::inflate_carry(ctx, cut, total) != 0) {
+							(void)nte_reads::inflate_copy_wait(ctx, which ^ 1);
+							return NTEDIT_E_DEVICE;
+						}
+						base += cut;
+						tail = total - cut;
+						if (last && !whole) {
+							handed_back = true; // what follows the members is not BGZF: the host parser's, from `base`
+						}
+						cur = next;
+						which ^= 1;
+					}
+				}
+				if (starts) {
+					starts[i] = 0;
+				}
+				if (handed_back) {
+					zinfo.handed_back++;
+					zinfo.handed_back_at = base;
+					Range rest = r;
+					rest.skip = base;
+					const int rc = host_pass({ rest }, nullptr, nexts ? nexts + i : nullptr);
+					if (rc) {
+						return rc;
+					}
+				} else if (nexts) {
+					nexts[i] = base;
+				}
+				continue;
+			}
 			if (!regular || is_gzip(r.path)) { // a gzip file (or what the host parser will refuse in its own words)
 				info.host_files++;
 				const int rc = host_pass({ r }, starts ? starts + i : nullptr, nexts ? nexts + i : nullptr);
@@ -908,6 +1255,20 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 			l += ", " + std::to_string(ps.host_files) + " gzip inputs stay with the host parser";
 		}
 		lg.rank_info(l);
+		ntedit_hip_reads_inflate_stats zs;
+		if (ntedit_hip_reads_inflate_info(ctx, &zs) == 0 && zs.files) {
+			// ... and one about its BGZF inputs (the tests read it)
+			l = "--gpu_parse: BGZF: " + std::to_string(zs.members) + " members of " + std::to_string(zs.files) +
+			    (zs.files == 1 ? " file" : " files") + " inflated on the device (" + std::to_string(zs.comp_bytes) +
+			    " compressed bytes, " + std::to_string(zs.raw_bytes) + " inflated bytes, ";
+			snprintf(line, sizeof line, "%.1f ms in the inflate kernels), ", zs.ms_kernels);
+			l += line + std::to_string(zs.handed_back) + (zs.handed_back == 1 ? " file" : " files") + " handed back";
+			if (zs.handed_back) {
+				l += " to the host parser (the last at inflated offset " + std::to_string(zs.handed_back_at) + ")";
+			}
+			l += "; " + std::to_string(ps.host_files) + " gzip inputs stay with the host parser";
+			lg.rank_info(l);
+		}
 	}
 	return 0;
 }

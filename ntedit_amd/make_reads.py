@@ -44,7 +44,8 @@ USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR 
          "  --reject_cutoff also write the reject filter for ntedit -e (the k-mers seen at least this many times), from\n"
          "                  the same pass 2; --reject_bf / --reject_num_elements size it, --reject_out names it\n"
          "                  [default: reads_k<K>_reject.bf]\n"
-         "  --gpu_parse     parse plain (not gzip) read files on the GPU: the host ships raw file bytes; same output\n"
+         "  --gpu_parse     parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes,\n"
+         "                  BGZF still compressed; same output (single-stream gzip stays with the host parser)\n"
          "  --backend       torch.distributed backend (default nccl = RCCL; gloo: N ranks may share a GPU)\n"
          "ntedit-make-reads-bf --help describes the other flags.\n")
 
@@ -363,6 +364,11 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
             parsed[key] = dict(device_chunks=st.device_chunks, fallback_chunks=st.fallback_chunks,
                                raw_bytes=st.raw_bytes, text_bytes=st.text_bytes, kernel_ms=round(st.ms_kernels, 3),
                                broken=st.broken, host_files=st.host_files)
+            zs = _lib.ReadsInflateStats()  # ... and, of BGZF inputs, what it inflated on the device
+            if lib.ntedit_hip_reads_inflate_info(b.h, zs) == 0 and zs.files:
+                parsed[key]["bgzf"] = dict(files=zs.files, members=zs.members, compressed_bytes=zs.comp_bytes,
+                                           inflated_bytes=zs.raw_bytes, kernel_ms=round(zs.ms_kernels, 3),
+                                           handed_back=zs.handed_back)
     try:
         k, hashes = a["k"], a["hashes"]
         counters = (sketch + 7) // 8 * 8
