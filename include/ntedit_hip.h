@@ -507,6 +507,70 @@ int ntedit_hip_reads_inflate_model(const void* comp, uint64_t n_comp, const nted
 uint64_t ntedit_hip_reads_last_record_start(const char* buf, uint64_t n, int kind);
 int ntedit_hip_reads_last_start_device(ntedit_hip_ctx* ctx, const void* buf, uint64_t n, int on_device, uint64_t* cut);
 int ntedit_hip_reads_inflate_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_inflate_stats* st);
+/* --gpu_parse for genome FASTA (ntedit-make-genome-bf --gpu_parse, ntedit --genome --gpu_parse).  A chromosome does not
+ * fit a chunk that has to start at a record start, so a genome chunk is any run of raw bytes of a FASTA file, cut
+ * anywhere, entered in a state (nte_genome_grammar.h): at a line start, inside a '>' line, or inside a sequence line.
+ * Its text is one '\n' for every header line that begins in the chunk and the bytes of every sequence line or piece of
+ * one, in raw order; the texts of consecutive chunks, each entered with its predecessor's exit state, concatenate to the
+ * text of the whole file, whose pieces between '\n' are the records' sequences.  A chunk is clean unless it holds a
+ * '\r', an empty line that begins in it, a sequence line that begins in it with '+' or '@', is the file's first chunk
+ * and does not start with '>', has more than n / 8 + 1 lines or 2^31 bytes or more (NTEDIT_PARSE_BAD_*).
+ *   ntedit_hip_genome_parse_device: one chunk.  raw: n_raw host or device bytes (device: 16-byte aligned); text_device:
+ *           16-byte aligned device memory of text_cap >= n_raw bytes (the text is never longer than the raw bytes).
+ *           Every field of *res is filled whether the chunk is clean or not, and the text is the grammar's either way
+ *           (a small chunk of short lines is over the line bound, and chunking still never changes the text); only
+ *           with 2^31 bytes or more, or more lines than (n_raw + 2^20) / 8 + 1, the chunk is not looked at further:
+ *           `broken` and `lines` are all the result then holds.  Scratch is the context's, as for
+ *           ntedit_hip_reads_parse_device.
+ *   ntedit_hip_genome_parse_model: the same grammar functions run serially on the host (no device; failures through
+ *           ntedit_hip_reads_last_error(NULL)): the text into out[0 .. cap), NTEDIT_E_OVERFLOW when it does not fit.
+ *   ntedit_hip_genome_pass: the files, one after the other, in chunks of batch_bytes raw bytes cut wherever they end.
+ *           Plain files are read into page-locked buffers and copied while the chunk before is parsed; BGZF files are
+ *           shipped compressed in whole members and inflated on the device (ntedit_hip_reads_inflate_device).  insert
+ *           != 0: each chunk's text, behind the last k - 1 text bytes of its file before it, goes to
+ *           ntedit_hip_filter_insert(slot) as a device batch (the slot's k); insert = 0: the pass only sums the bases
+ *           (the sizing pass; no filter needed).  From the first unclean chunk of a file on, the host parser takes the
+ *           file, from the file's last known record start at or before that chunk (insertion is idempotent; the sizing
+ *           pass reads such a file again from its start); single-stream .gz files and files that do not start with '>'
+ *           take the host parser whole, and with batch_bytes 0 every file does (the pass without --gpu_parse).  A BGZF
+ *           member the inflater refuses fails the pass.  stats->bases: the bases of
+ *           all records, as ntedit-make-genome-bf prints them.
+ *   ntedit_hip_genome_pass_get_info: the last pass of the context, as a ntedit_hip_genome_pass_info. */
+#define NTEDIT_GENOME_LINE_START 0
+#define NTEDIT_GENOME_IN_HEADER 1
+#define NTEDIT_GENOME_IN_SEQ 2
+typedef struct ntedit_hip_genome_parse_result
+{
+	int clean;            /* 1: no rule is broken */
+	uint32_t broken;      /* NTEDIT_PARSE_BAD_*, 0 when clean */
+	int state_out;        /* NTEDIT_GENOME_*: the state the next chunk is entered in */
+	int reserved;
+	uint64_t text_len;
+	uint64_t bases;       /* the sequence bytes copied */
+	uint64_t lines;
+	uint64_t last_header; /* the raw offset where the last header line that begins in the chunk starts, or NTEDIT_READS_NO_START */
+} ntedit_hip_genome_parse_result;
+typedef struct ntedit_hip_genome_pass_info
+{
+	uint64_t device_chunks; /* clean chunks, parsed on the device */
+	uint64_t raw_bytes;     /* their raw (inflated) bytes */
+	uint64_t text_bytes;    /* the text made of them */
+	double ms_kernels;      /* in the parse kernels */
+	uint32_t handed_back;   /* files the host parser finished after an unclean chunk */
+	uint32_t broken;        /* the rules those chunks broke */
+	uint32_t host_files;    /* files left to the host parser whole (single-stream .gz, no '>' at the start) */
+	uint32_t bgzf_files;    /* files inflated on the device */
+	uint64_t bgzf_members;  /* ... and their members */
+} ntedit_hip_genome_pass_info;
+int ntedit_hip_genome_parse_device(ntedit_hip_ctx* ctx, const char* raw, uint64_t n_raw, int on_device, int state_in, int first_chunk,
+                                   char* text_device, uint64_t text_cap, ntedit_hip_genome_parse_result* res);
+int ntedit_hip_genome_parse_model(const char* raw, uint64_t n_raw, int state_in, int first_chunk, char* out, uint64_t cap,
+                                  ntedit_hip_genome_parse_result* res);
+int ntedit_hip_genome_pass(ntedit_hip_ctx* ctx, int slot, const char* const* files, uint32_t n, uint64_t batch_bytes, int insert,
+                           ntedit_hip_reads_pass_stats* stats);
+int ntedit_hip_genome_pass_get_info(ntedit_hip_ctx* ctx, ntedit_hip_genome_pass_info* info);
+/* the pass's information line(s), as the front ends print them: into out[0 .. cap), '\n' between lines */
+int ntedit_hip_genome_pass_line(ntedit_hip_ctx* ctx, char* out, uint64_t cap);
 
 
 /* ---- hot path ------------------------------------------------------------

@@ -165,6 +165,24 @@ class ReadsInflateStats(ctypes.Structure):
 
 
 BGZF_END, BGZF_CUT, BGZF_NOT, BGZF_FULL = 0, 1, 2, 3
+
+
+# --gpu_parse for genome FASTA (ntedit_hip_genome_parse_device / _model): the entry and exit states of a chunk
+GENOME_LINE_START, GENOME_IN_HEADER, GENOME_IN_SEQ = 0, 1, 2
+
+
+class GenomeParseResult(ctypes.Structure):
+    """ntedit_hip_genome_parse_result"""
+    _fields_ = [("clean", ctypes.c_int), ("broken", ctypes.c_uint32), ("state_out", ctypes.c_int),
+                ("reserved", ctypes.c_int), ("text_len", ctypes.c_uint64), ("bases", ctypes.c_uint64),
+                ("lines", ctypes.c_uint64), ("last_header", ctypes.c_uint64)]
+
+
+class GenomePassInfo(ctypes.Structure):
+    """ntedit_hip_genome_pass_info: the last ntedit_hip_genome_pass of a context"""
+    _fields_ = [("device_chunks", ctypes.c_uint64), ("raw_bytes", ctypes.c_uint64), ("text_bytes", ctypes.c_uint64),
+                ("ms_kernels", ctypes.c_double), ("handed_back", ctypes.c_uint32), ("broken", ctypes.c_uint32),
+                ("host_files", ctypes.c_uint32), ("bgzf_files", ctypes.c_uint32), ("bgzf_members", ctypes.c_uint64)]
 READS_NO_START = 2 ** 64 - 1
 
 
@@ -230,6 +248,8 @@ EXPORTS = [
     "ntedit_hip_reads_parse_info", "ntedit_hip_reads_set_reject_cutoff",
     "ntedit_hip_bgzf_walk", "ntedit_hip_reads_inflate_device", "ntedit_hip_reads_inflate_model",
     "ntedit_hip_reads_last_record_start", "ntedit_hip_reads_last_start_device", "ntedit_hip_reads_inflate_info",
+    "ntedit_hip_genome_parse_device", "ntedit_hip_genome_parse_model", "ntedit_hip_genome_pass",
+    "ntedit_hip_genome_pass_get_info", "ntedit_hip_genome_pass_line",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -383,5 +403,13 @@ def load():
     lib.ntedit_hip_reads_last_record_start.restype = u64
     lib.ntedit_hip_reads_last_start_device.argtypes = [vp, vp, u64, ci, pu64]
     lib.ntedit_hip_reads_inflate_info.argtypes = [vp, ctypes.POINTER(ReadsInflateStats)]
+    # --gpu_parse for genome FASTA
+    gres = ctypes.POINTER(GenomeParseResult)
+    lib.ntedit_hip_genome_parse_device.argtypes = [vp, vp, u64, ci, ci, ci, vp, u64, gres]
+    lib.ntedit_hip_genome_parse_model.argtypes = [vp, u64, ci, ci, vp, u64, gres]
+    lib.ntedit_hip_genome_pass.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_char_p), u32, u64, ci,
+                                           ctypes.POINTER(ReadsPassStats)]
+    lib.ntedit_hip_genome_pass_get_info.argtypes = [vp, ctypes.POINTER(GenomePassInfo)]
+    lib.ntedit_hip_genome_pass_line.argtypes = [vp, ctypes.c_char_p, u64]
     _lib = lib
     return lib

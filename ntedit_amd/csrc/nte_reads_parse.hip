@@ -19,9 +19,18 @@
 //                    its bytes cost)
 // The scans are count / scan / write over blocks of 2048 items (as k_count_starts / k_scan_counts / k_write_starts).
 //
+// Genome FASTA (nte_genome_grammar.h: chunks cut anywhere, entered in a state) shares the line table and the copy:
+//   k_rp_tiles, scan, k_rp_line_ends   as above
+//   k_gp_classify    one lane per line, line 0 by the entry state: class and grammar checks, the last header that
+//                    begins in the chunk (an atomic max), and per line (headers begun, text bytes) packed in 64 bits
+//   scan             over the lines: each line's place in the text
+//   k_gp_line_out    the '\n' of each header that begins in the chunk, each sequence line's place, the exit state
+//   k_rp_copy        as above
+//
 // Like nte_reads.hip this unit is outside KSRC and sees no context internals: its state hangs off the context pointer.
 #include "nte_common.h"
 #include "nte_reads_grammar.h"
+#include "nte_genome_grammar.h"
 
 #include "../../include/ntedit_hip.h"
 
@@ -64,7 +73,10 @@ struct RpInfo // the small result the device keeps per chunk
 	u32 last_nl; // the chunk's last byte is '\n'
 	u32 pad;
 	u64 newlines;
-	u64 records; // hi: kept records, lo: text bytes
+	u64 records; // hi: kept records, lo: text bytes (a genome chunk: hi: headers begun)
+	// genome chunks only
+	u32 last_header1; // 1 + the raw offset of the last header line that begins in the chunk, 0: none
+	u32 state_out;
 };
 
 __host__ __device__ __forceinline__ u32
@@ -438,12 +450,60 @@ k_rp_copy(const u8* __restrict__ raw, u64 n, const u64* __restrict__ tile_base, 
 	}
 }
 
+// ------------------------------------------------------------------ genome chunks (nte_genome_grammar.h)
+// per line: its class, and (headers begun << 32 | text bytes) for the scan
+__global__ __launch_bounds__(RP_TPB) void
+k_gp_classify(const u8* __restrict__ raw, u64 n, const u32* __restrict__ line_end, u64 n_lines, int state_in, int first_chunk,
+              u8* __restrict__ cls, u64* __restrict__ val, RpInfo* info)
+{
+	const u64 line = (u64)blockIdx.x * RP_TPB + threadIdx.x;
+	if (line >= n_lines) {
+		return;
+	}
+	const u32 s = rp_line_start(line_end, line), e = line_end[line];
+	const u32 len = e - s;
+	u32 broken = line == 0 ? gp_chunk_broken(first_chunk, (int)info->kind, n, n_lines) : 0;
+	const int c = gp_line_class(state_in, line, len ? (int)raw[s] : -1, &broken);
+	cls[line] = (u8)c;
+	val[line] = gp_line_emit(c, len);
+	if (c == RP_HEADER) {
+		atomicMax(&info->last_header1, s + 1);
+	}
+	if (broken) {
+		atomicOr(&info->broken, broken);
+	}
+}
+
+// sr[L]: hi = headers begun before line L, lo = text bytes before it: line L's place; sr[n_lines] = the totals
+__global__ __launch_bounds__(RP_TPB) void
+k_gp_line_out(const u8* __restrict__ cls, const u64* __restrict__ sr, u64 n_lines, u32* __restrict__ line_out, u8* __restrict__ text,
+              u64 text_cap, RpInfo* info)
+{
+	const u64 line = (u64)blockIdx.x * RP_TPB + threadIdx.x;
+	if (line >= n_lines) {
+		return;
+	}
+	const u32 c = cls[line];
+	if (line == 0) {
+		info->records = sr[n_lines];
+	}
+	if (line == n_lines - 1) {
+		info->state_out = (u32)gp_state_out((int)info->last_nl, (int)c);
+	}
+	const u32 at = lo32(sr[line]);
+	if (c == RP_HEADER && at < text_cap) {
+		text[at] = '\n';
+	}
+	line_out[line] = c == RP_SEQ ? at : RP_NONE;
+}
+
 // ------------------------------------------------------------------ host side
 struct ParseState
 {
 	const ntedit_hip_ctx* owner = nullptr;
 	int on = 0; // ntedit_hip_reads_set_device_parse
 	ntedit_hip_reads_parse_stats info = {};
+	ntedit_hip_genome_pass_info ginfo = {}; // ntedit_hip_genome_pass
 	// device scratch, grow-only, released by ntedit_hip_sketch_free
 	int device = -1;
 	hipStream_t stream = nullptr, copy_stream = nullptr;
@@ -452,6 +512,9 @@ struct ParseState
 	u64 raw_cap[2] = { 0, 0 };
 	u8* d_text = nullptr;
 	u64 text_cap = 0;
+	u8* d_gtext = nullptr; // a genome pass: GP_PAD bytes of carried text, then the chunk's text
+	u64 gtext_cap = 0;
+	u8* d_gstage = nullptr; // GP_PAD bytes
 	u8* d_table = nullptr; // the line table and the scans' block sums, for chunks of up to table_raw bytes
 	u64 table_raw = 0;
 	RpInfo* d_info = nullptr;
@@ -511,7 +574,8 @@ release_scratch(ParseState* s)
 			(void)hipEventDestroy(e);
 		}
 	}
-	for (void* p : { (void*)s->d_raw[0], (void*)s->d_raw[1], (void*)s->d_text, (void*)s->d_table, (void*)s->d_info }) {
+	for (void* p : { (void*)s->d_raw[0], (void*)s->d_raw[1], (void*)s->d_text, (void*)s->d_table, (void*)s->d_info, (void*)s->d_gtext,
+		                (void*)s->d_gstage }) {
 		if (p) {
 			(void)hipFree(p);
 		}
@@ -522,10 +586,12 @@ release_scratch(ParseState* s)
 	const ntedit_hip_ctx* owner = s->owner;
 	const int on = s->on;
 	const ntedit_hip_reads_parse_stats info = s->info;
+	const ntedit_hip_genome_pass_info ginfo = s->ginfo;
 	*s = ParseState();
 	s->owner = owner;
 	s->on = on;
 	s->info = info;
+	s->ginfo = ginfo;
 }
 
 int
@@ -691,6 +757,81 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 	return 0;
 }
 
+// one genome chunk of device bytes: the line table as parse_on_device builds it, then the genome phases
+int
+genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, int state_in, int first_chunk, u8* d_text, u64 text_cap,
+                 ntedit_hip_genome_parse_result* res)
+{
+	*res = ntedit_hip_genome_parse_result();
+	res->last_header = NTEDIT_READS_NO_START;
+	res->state_out = state_in;
+	if (n == 0) {
+		res->clean = 1;
+		return 0;
+	}
+	if (n >= RP_MAX_RAW) {
+		res->broken = RP_BAD_SIZE;
+		res->state_out = 0;
+		return 0;
+	}
+	if (n + GP_TABLE_SLACK > s->table_raw || !s->d_table) { // (the table holds what gp_stops lets through)
+		const u64 want = n + 2 * GP_TABLE_SLACK;
+		if (s->d_table) {
+			RP_TRY(c, hipFree(s->d_table));
+			s->d_table = nullptr;
+			s->table_raw = 0;
+		}
+		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
+		s->table_raw = want;
+	}
+	const Table t = carve(s->d_table, s->table_raw);
+	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
+	RP_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
+	RP_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	hipLaunchKernelGGL(k_rp_tiles, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, s->d_info);
+	scan(s, t.tile, tiles, t.bsum);
+	RP_TRY(c, hipGetLastError());
+	RP_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	RP_TRY(c, hipMemcpyAsync(&s->h_info->newlines, t.tile + tiles, 8, hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, 16, hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipStreamSynchronize(s->stream));
+	float ms = 0;
+	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	s->ginfo.ms_kernels += ms;
+	const u64 lines = s->h_info->newlines + (s->h_info->last_nl ? 0 : 1);
+	// over the table's bound nothing more may run
+	if (gp_stops(n, lines)) {
+		res->broken = gp_chunk_broken(0, 0, n, lines);
+		res->lines = lines;
+		res->state_out = 0;
+		return 0;
+	}
+	const unsigned line_blocks = (unsigned)((lines + RP_TPB - 1) / RP_TPB);
+	RP_TRY(c, hipEventRecord(s->ev[2], s->stream));
+	hipLaunchKernelGGL(k_rp_line_ends, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, lines, s->d_info);
+	hipLaunchKernelGGL(k_gp_classify, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, d_raw, n, t.line_end, lines, state_in, first_chunk,
+	                   t.cls, t.sr, s->d_info);
+	scan(s, t.sr, lines, t.bsum);
+	hipLaunchKernelGGL(k_gp_line_out, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, lines, t.line_out, d_text, text_cap,
+	                   s->d_info);
+	hipLaunchKernelGGL(k_rp_copy, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out, lines,
+	                   d_text, text_cap);
+	RP_TRY(c, hipGetLastError());
+	RP_TRY(c, hipEventRecord(s->ev[3], s->stream));
+	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(RpInfo), hipMemcpyDeviceToHost, s->stream));
+	RP_TRY(c, hipStreamSynchronize(s->stream));
+	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+	s->ginfo.ms_kernels += ms;
+	res->broken = s->h_info->broken;
+	res->clean = res->broken == 0;
+	res->state_out = (int)s->h_info->state_out;
+	res->text_len = lo32(s->h_info->records);
+	res->bases = res->text_len - hi32(s->h_info->records);
+	res->lines = lines;
+	res->last_header = s->h_info->last_header1 ? (u64)s->h_info->last_header1 - 1 : NTEDIT_READS_NO_START;
+	return 0;
+}
+
 } // namespace
 
 // what the pass loop of reads_pass.cpp needs beyond the public calls: the two raw buffers and the copy stream
@@ -782,6 +923,176 @@ parse_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint32_t k,
 	*text = (const char*)s->d_text;
 	return parse_on_device(c, s, (const u8*)d_raw, n, k, s->d_text, s->text_cap, res);
 }
+
+// ------------------------------------------------------------------ what genome_pass.cpp needs
+// The pass's text buffer: GP_PAD bytes that end with the last k - 1 text bytes of the file so far ('\n' before them),
+// then the chunk's text; the whole is one device batch for ntedit_hip_filter_insert.
+constexpr u64 GP_PAD = 256;
+
+ntedit_hip_genome_pass_info*
+genome_info(const ntedit_hip_ctx* c)
+{
+	return &parse_state(c, true)->ginfo;
+}
+
+int
+genome_pad(void)
+{
+	return (int)GP_PAD;
+}
+
+// a file begins: nothing is carried
+int
+genome_begin_file(const ntedit_hip_ctx* c)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, &s->d_gtext, &s->gtext_cap, GP_PAD);
+	}
+	if (rc) {
+		return rc;
+	}
+	if (!s->d_gstage) {
+		RP_TRY(c, hipMalloc((void**)&s->d_gstage, GP_PAD));
+	}
+	RP_TRY(c, hipMemsetAsync(s->d_gtext, '\n', GP_PAD, s->stream));
+	RP_TRY(c, hipStreamSynchronize(s->stream));
+	return 0;
+}
+
+// raw buffer `which` with room for n bytes (a BGZF chunk is inflated into it)
+int
+genome_raw_buffer(const ntedit_hip_ctx* c, int which, uint64_t n, char** d_raw)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, &s->d_raw[which], &s->raw_cap[which], n);
+	}
+	*d_raw = rc ? nullptr : (char*)s->d_raw[which];
+	return rc;
+}
+
+// raw buffer `which` (copied: after parse_copy_begin, waits for that copy) parsed behind the pad; *batch: the pad's first
+// byte, the text is at *batch + genome_pad()
+int
+genome_parse_buffer(const ntedit_hip_ctx* c, int which, int copied, uint64_t n, int state_in, int first_chunk, const char** batch,
+                    ntedit_hip_genome_parse_result* res)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc) {
+		return rc;
+	}
+	if (GP_PAD + n > s->gtext_cap || !s->d_gtext) {
+		// (grow frees: the pad moves with a copy through the stage)
+		u8* old = s->d_gtext;
+		s->d_gtext = nullptr;
+		s->gtext_cap = 0;
+		rc = grow(c, &s->d_gtext, &s->gtext_cap, GP_PAD + n);
+		if (rc == 0 && old) {
+			RP_TRY(c, hipMemcpy(s->d_gtext, old, GP_PAD, hipMemcpyDeviceToDevice));
+		}
+		if (old) {
+			(void)hipFree(old);
+		}
+		if (rc) {
+			return rc;
+		}
+	}
+	if (copied) {
+		RP_TRY(c, hipEventSynchronize(s->copied[which]));
+	}
+	*batch = (const char*)s->d_gtext;
+	return genome_on_device(c, s, s->d_raw[which], n, state_in, first_chunk, s->d_gtext + GP_PAD, s->gtext_cap - GP_PAD, res);
+}
+
+// the chunk's text is inserted: the pad becomes the last `keep` (< GP_PAD) bytes of pad + text, '\n' before them
+int
+genome_carry(const ntedit_hip_ctx* c, uint64_t text_len, uint32_t keep)
+{
+	ParseState* s = parse_state(c, false);
+	if (!s || !s->d_gtext || keep >= GP_PAD) {
+		return pfail(c, NTEDIT_E_ARG, "genome_carry: bad argument");
+	}
+	if (text_len) {
+		RP_TRY(c, hipMemcpyAsync(s->d_gstage, s->d_gtext + text_len, GP_PAD, hipMemcpyDeviceToDevice, s->stream));
+		RP_TRY(c, hipMemcpyAsync(s->d_gtext, s->d_gstage, GP_PAD, hipMemcpyDeviceToDevice, s->stream));
+	}
+	RP_TRY(c, hipMemsetAsync(s->d_gtext, '\n', GP_PAD - keep, s->stream));
+	RP_TRY(c, hipStreamSynchronize(s->stream));
+	return 0;
+}
+
+} // namespace nte_reads
+
+extern "C" {
+
+int
+ntedit_hip_genome_pass_get_info(ntedit_hip_ctx* c, ntedit_hip_genome_pass_info* info)
+{
+	if (!c || !info) {
+		return c ? pfail(c, NTEDIT_E_ARG, "genome_pass_get_info: bad argument") : NTEDIT_E_ARG;
+	}
+	*info = parse_state(c, true)->ginfo;
+	return 0;
+}
+
+int
+ntedit_hip_genome_parse_device(ntedit_hip_ctx* c, const char* raw, uint64_t n_raw, int on_device, int state_in, int first_chunk,
+                               char* text_device, uint64_t text_cap, ntedit_hip_genome_parse_result* res)
+{
+	if (!c || !res || (n_raw && (!raw || !text_device)) || !gp_state_ok(state_in) ||
+	    (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE)) {
+		return c ? pfail(c, NTEDIT_E_ARG, "genome_parse_device: bad argument") : NTEDIT_E_ARG;
+	}
+	if (((uintptr_t)text_device & 15) || (on_device == NTEDIT_HIP_BASES_DEVICE && ((uintptr_t)raw & 15))) {
+		return pfail(c, NTEDIT_E_ARG, "genome_parse_device: device buffers must be 16-byte aligned");
+	}
+	if (text_cap < n_raw) {
+		return pfail(c, NTEDIT_E_ARG, "genome_parse_device: text_cap must be at least n_raw (the text is never longer than the raw bytes)");
+	}
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc) {
+		return rc;
+	}
+	const u8* d_raw = (const u8*)raw;
+	if (on_device == NTEDIT_HIP_BASES_HOST && n_raw) {
+		if ((rc = grow(c, &s->d_raw[0], &s->raw_cap[0], n_raw)) != 0) {
+			return rc;
+		}
+		RP_TRY(c, hipMemcpyAsync(s->d_raw[0], raw, n_raw, hipMemcpyHostToDevice, s->stream));
+		d_raw = s->d_raw[0];
+	}
+	return genome_on_device(c, s, d_raw, n_raw, state_in, first_chunk != 0, (u8*)text_device, text_cap, res);
+}
+
+// the serial model (gp_model, nte_genome_grammar.h): the same grammar functions, one line after the other
+int
+ntedit_hip_genome_parse_model(const char* raw, uint64_t n_raw, int state_in, int first_chunk, char* out, uint64_t cap,
+                              ntedit_hip_genome_parse_result* res)
+{
+	if (!res || (n_raw && !raw) || (cap && !out) || !gp_state_ok(state_in)) {
+		return pfail(nullptr, NTEDIT_E_ARG, "genome_parse_model: bad argument");
+	}
+	GpResult m;
+	const bool fits = gp_model(raw, n_raw, state_in, first_chunk, out, cap, &m);
+	*res = ntedit_hip_genome_parse_result();
+	res->clean = m.clean;
+	res->broken = m.broken;
+	res->state_out = m.state_out;
+	res->text_len = m.text_len;
+	res->bases = m.bases;
+	res->lines = m.lines;
+	res->last_header = m.last_header;
+	return fits ? 0 : NTEDIT_E_OVERFLOW;
+}
+
+} // extern "C"
+
+namespace nte_reads {
 
 int
 parse_is_on(const ntedit_hip_ctx* c)

@@ -95,6 +95,16 @@ static const char USAGE[] = PROGRAM
     "			--reject_cutoff, unless --solid or --hist: then it is sized from the k-mer histogram)\n"
     "	--save_reject_bf FILE,	write the reject filter that was built (the bytes ntedit-make-reads-bf -c R would write)\n"
     "			[default name: reads_k<K>_reject.bf, not written]\n"
+    "\n Polishing straight from genome assemblies (--genome replaces -r; the filter is the one ntedit-make-genome-bf builds\n"
+    " with the same settings, built on the GPU into the context that polishes, no filter file needed):\n"
+    "	--genome FILE...,	genome FASTA, plain or gzip (1 or more files)\n"
+    "	-k,	k-mer size (bp), 12 to 200, REQUIRED with --genome\n"
+    "	--hashes H, --fpr F,	as above [defaults 3, 0.01]\n"
+    "	--bf BYTES | --num_elements N,	the filter's size [default: from the genome's size, as the tool sizes it]\n"
+    "	--save_bf FILE,	write the filter that was built (the same bytes as ntedit-make-genome-bf -o); its name is the _r\n"
+    "			part of the default prefix [default name: genome_bf.bf, not written]\n"
+    "	--gpu_parse,	parse plain and bgzip-compressed (BGZF) genome FASTA on the GPU, records of any length (same\n"
+    "			outputs; single-stream gzip files stay with the host parser)\n"
     "	--help,		display this message and exit \n"
     "	--version,	output version information and exit\n\n";
 
@@ -238,6 +248,85 @@ reads_rules(const ntedit_hip_reads_options& ro, int final)
 	return rr;
 }
 
+// The rules of ntedit --genome, apart from the reads options' (reads_options.cpp knows nothing of them): what is refused
+// before the device is opened and before any file is written.  The numbers arrive well-formed (reads_rules refuses a
+// malformed one at its option); -k is checked here.  Returns the refusal, or "" and the settings.
+struct GenomeRules
+{
+	uint32_t k = 0, hash_num = 3;
+	double fpr = 0.01;
+	bool have_bf = false, have_ne = false;
+	uint64_t bf_bytes = 0, num_elements = 0, batch_bytes = 256ull << 20;
+	int gpu_parse = 0;
+};
+
+static std::string
+genome_rules(const ntedit_hip_reads_options& ro, bool have_r, bool reads_mode, bool shard_given, size_t n_files,
+             const std::vector<std::string>& given, GenomeRules* g)
+{
+	static const char* const reads_only[] = { "--cutoff", "--solid", "--counts", "--hist", "--sketch_bytes", "--reject_cutoff", "--reject_bf",
+		                                      "--reject_num_elements", "--save_reject_bf", "--resident_cap" };
+	if (have_r) {
+		return "--genome and -r: give one of them (--genome builds the filter that -r would load)";
+	}
+	if (reads_mode) {
+		return "--genome and --reads: give one of them (each builds the filter that -r would load)";
+	}
+	if (shard_given) {
+		return "--genome and --shard: every shard would build the whole filter again; build it once with "
+		       "ntedit-make-genome-bf and give each shard -r";
+	}
+	if (n_files == 0) {
+		return "--genome: 1 or more files expected";
+	}
+	for (const std::string& name : given) {
+		for (const char* r : reads_only) {
+			if (name == r) {
+				return name + ": only with --reads (--genome builds the plain filter of every k-mer of the assemblies)";
+			}
+		}
+	}
+	if (!ro.k) {
+		return "-k: required with --genome";
+	}
+	char* end = nullptr;
+	const unsigned long long k = strtoull(ro.k, &end, 10);
+	if (!*ro.k || *end || ro.k[0] == '-' || k < 12 || k > 200) {
+		return std::string("-k ") + ro.k + ": k must be between 12 and 200";
+	}
+	g->k = (uint32_t)k;
+	if (ro.hashes) {
+		const unsigned long long h = strtoull(ro.hashes, nullptr, 10);
+		if (h < 1 || h > 8) {
+			return "--hashes " + std::to_string(h) + ": the number of hash functions must be between 1 and 8";
+		}
+		g->hash_num = (uint32_t)h;
+	}
+	if (ro.fpr) {
+		g->fpr = strtod(ro.fpr, nullptr);
+	}
+	if (ro.bf) {
+		g->have_bf = true;
+		g->bf_bytes = strtoull(ro.bf, nullptr, 10);
+	}
+	if (ro.num_elements) {
+		g->have_ne = true;
+		g->num_elements = strtoull(ro.num_elements, nullptr, 10);
+	}
+	if ((g->have_bf && g->bf_bytes == 0) ||
+	    (!g->have_bf && g->have_ne && ntedit_hip_reads_bf_size(g->num_elements, g->hash_num, g->fpr) == 0)) {
+		return "--bf / --num_elements: the filter would be empty";
+	}
+	if (ro.batch_bytes) {
+		g->batch_bytes = strtoull(ro.batch_bytes, nullptr, 10);
+		if (g->batch_bytes == 0) {
+			return "--batch_bytes: at least 1";
+		}
+	}
+	g->gpu_parse = ro.gpu_parse ? 1 : 0;
+	return "";
+}
+
 struct Batch
 {
 	std::string blob; // filled by the streaming reader (append per line) ...
@@ -346,12 +435,23 @@ main(int argc, char** argv)
 	std::vector<std::string> read_files;
 	std::vector<const char*> paths;
 	bool reads_mode = false;
+	// --genome FILE...: likewise
+	std::vector<std::string> genome_files;
+	bool genome_mode = false;
+	GenomeRules gr;
 	std::vector<char*> args;
 	for (int i = 0; i < argc; i++) {
 		if (i > 0 && strcmp(argv[i], "--reads") == 0) {
 			reads_mode = true;
 			while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] != 0)) {
 				read_files.push_back(argv[++i]);
+			}
+			continue;
+		}
+		if (i > 0 && strcmp(argv[i], "--genome") == 0) {
+			genome_mode = true;
+			while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] != 0)) {
+				genome_files.push_back(argv[++i]);
 			}
 			continue;
 		}
@@ -572,7 +672,17 @@ main(int argc, char** argv)
 	} else {
 		die_unreadable(draft);
 	}
-	if (reads_mode) {
+	if (genome_mode) {
+		// every refusal of --genome before the device is opened and before any file is written
+		const std::string why = genome_rules(ro, !bf.empty(), reads_mode, shard_given, genome_files.size(), reads_only, &gr);
+		if (!why.empty()) {
+			refuse(why);
+		}
+		for (const std::string& g : genome_files) {
+			die_unreadable(g);
+			paths.push_back(g.c_str());
+		}
+	} else if (reads_mode) {
 		// every refusal of --reads before the device is opened and before any file is written
 		if (!bf.empty()) {
 			refuse("--reads and -r: give one of them (--reads builds the filter that -r would load)");
@@ -598,7 +708,13 @@ main(int argc, char** argv)
 			die_unreadable(r);
 		}
 	} else if (!reads_only.empty()) {
-		refuse(reads_only[0] + ": only with --reads");
+		// (the options --genome shares with --reads say so)
+		static const char* const shared[] = { "--hashes", "--fpr", "--bf", "--num_elements", "--save_bf", "--gpu_parse", "--batch_bytes" };
+		bool both = false;
+		for (const char* o : shared) {
+			both = both || reads_only[0] == o;
+		}
+		refuse(reads_only[0] + (both ? ": only with --reads or --genome" : ": only with --reads"));
 	} else if (bf.empty()) {
 		fprintf(stderr, PROGRAM ": error: need to specify the Bloom filter file (-r)\n");
 		die = true;
@@ -681,7 +797,58 @@ main(int argc, char** argv)
 		_exit(EXIT_FAILURE); // (_exit: the side thread above may still be running)
 	};
 	time(&rawtime);
-	if (reads_mode) {
+	if (genome_mode) {
+		// the filter ntedit-make-genome-bf would write, built into the primary slot (genome_pass.cpp): sized as the tool
+		// sizes it, every k-mer of every record of k bases or more inserted; without --gpu_parse the host parser reads
+		// the files (batch_bytes 0)
+		printf("---------- building Bloom filter from genome        : %s\n", ctime(&rawtime));
+		fflush(stdout);
+		const auto g0 = std::chrono::steady_clock::now();
+		const uint64_t batch = gr.gpu_parse ? gr.batch_bytes : 0;
+		auto pass = [&](int insert) {
+			ntedit_hip_reads_pass_stats st;
+			if (ntedit_hip_genome_pass(ctx, NTEDIT_FILTER_PRIMARY, paths.data(), (uint32_t)paths.size(), batch, insert, &st) != 0) {
+				fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_reads_last_error(ctx));
+				fatal();
+			}
+			char line[1024];
+			if (gr.gpu_parse && ntedit_hip_genome_pass_line(ctx, line, sizeof line) == 0) {
+				fprintf(stderr, "%s pass: %llu bases, %.1f ms (GPU calls %.1f ms)\n%s\n", insert ? "Insert" : "Sizing",
+				        (unsigned long long)st.bases, st.ms_wall, st.ms_gpu, line);
+			}
+			return st.bases;
+		};
+		uint64_t bf_size = gr.bf_bytes;
+		if (!gr.have_bf && gr.have_ne) {
+			bf_size = ntedit_hip_reads_bf_size(gr.num_elements, gr.hash_num, gr.fpr);
+		} else if (!gr.have_bf) {
+			const uint64_t genome_size = pass(0);
+			printf("Genome size (bp): %llu\n", (unsigned long long)genome_size);
+			bf_size = ntedit_hip_reads_bf_size(genome_size, gr.hash_num, gr.fpr);
+			if (bf_size == 0) {
+				fprintf(stderr, PROGRAM ": error: --genome: no bases in the genome files: the filter would be empty\n");
+				fatal();
+			}
+		}
+		printf("BF size (bytes): %llu\n", (unsigned long long)bf_size);
+		if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, gr.hash_num, gr.k) != 0) {
+			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
+			fatal();
+		}
+		(void)pass(1);
+		ntedit_hip_sketch_free(ctx); // (the device parser's scratch: the polish sizes its own buffers next)
+		printf("Genome filter built in %.1f ms\n",
+		       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count());
+		if (!save_bf.empty()) {
+			if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, save_bf.c_str()) != 0) {
+				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_bf.c_str());
+				fatal();
+			}
+			printf("Bloom filter saved to %s\n", save_bf.c_str());
+		}
+		// (the _r part of the default prefix: the name ntedit-make-genome-bf would have written it under)
+		bf = save_bf.empty() ? "genome_bf.bf" : save_bf;
+	} else if (reads_mode) {
 		// the filter ntedit-make-reads-bf would write, built into the primary slot (reads_pass.cpp); the reads stay
 		// resident in HBM after pass 1 unless they would pass store_cap, so that the later passes do not parse them again
 		printf("---------- building Bloom filter from reads         : %s\n", ctime(&rawtime));

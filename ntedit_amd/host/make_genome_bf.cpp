@@ -4,6 +4,9 @@
 // Keeps the reference tool's command line and console output (src/ntedit_make_genome_bf.cpp:49-166):
 //   --genome FILE [FILE ...]  -k K  [--fpr 0.01] [--hashes 3] [-o genome_bf.bf]
 //   [--bf BYTES] [--num_elements N] [-t THREADS]
+// and adds --gpu_parse: the genome files are parsed (BGZF files inflated) on the GPU, the sizing pass and the insert
+// pass alike (ntedit_hip_genome_pass); the filter and the lines above are the same, one information line per pass is
+// added.
 // Sizing follows get_bf_size (ntedit_make_genome_bf.cpp:41-47); every all-ACGT k-mer of every
 // record at least k long is inserted (143-157) by the same rolling-hash kernel that screens a draft
 // (ntedit_hip_filter_insert).  -t is accepted; the k-mers are hashed on the GPU.
@@ -38,7 +41,7 @@ usage(const char* why)
 		std::cerr << why << std::endl;
 	}
 	std::cerr << "Usage: make_genome_bf [--help] --genome VAR... -k VAR [--fpr VAR] [--hashes VAR] [-o VAR] [--bf VAR] "
-	             "[--num_elements VAR] [-t VAR]\n\n"
+	             "[--num_elements VAR] [-t VAR] [--gpu_parse]\n\n"
 	             "Optional arguments:\n"
 	             "  -h, --help      shows help message and exits\n"
 	             "  --genome        Input genome fasta file [nargs: 1 or more] [required]\n"
@@ -49,7 +52,8 @@ usage(const char* why)
 	             "  --bf            Bloom filter size in bytes (optional)\n"
 	             "  --num_elements  Approximate number of elements for Bloom filter (used for calculating Bloom filter "
 	             "size, optional)\n"
-	             "  -t              Number of threads [default: 12]\n";
+	             "  -t              Number of threads [default: 12]\n"
+	             "  --gpu_parse     Parse the genome FASTA (plain or bgzip-compressed) on the GPU\n";
 }
 
 static bool
@@ -63,7 +67,8 @@ main(int argc, char** argv)
 {
 	std::vector<std::string> genome_files;
 	unsigned k = 0, hashes = 3, num_threads = 12;
-	bool have_k = false, have_bf = false, have_ne = false;
+	bool have_k = false, have_bf = false, have_ne = false, gpu_parse = false;
+	uint64_t batch_bytes = 256ull << 20; // --batch_bytes (hidden): the raw bytes of a --gpu_parse chunk
 	double fpr = 0.01;
 	uint64_t bf_bytes = 0, num_elements = 0;
 	std::string out_file = "genome_bf.bf";
@@ -100,6 +105,10 @@ main(int argc, char** argv)
 			have_ne = true;
 		} else if (a == "-t") {
 			num_threads = (unsigned)strtoul(value("-t"), nullptr, 10);
+		} else if (a == "--gpu_parse") {
+			gpu_parse = true;
+		} else if (a == "--batch_bytes") {
+			batch_bytes = strtoull(value("--batch_bytes"), nullptr, 10);
 		} else {
 			usage(("Unknown argument: " + a).c_str());
 			return 1;
@@ -111,6 +120,14 @@ main(int argc, char** argv)
 	}
 	if (!have_k) {
 		usage("-k: required.");
+		return 1;
+	}
+	if (gpu_parse && batch_bytes == 0) {
+		usage("--batch_bytes: at least 1.");
+		return 1;
+	}
+	if (gpu_parse && (k < 2 || k > 256)) {
+		usage("--gpu_parse: -k must be within [2, 256].");
 		return 1;
 	}
 
@@ -126,6 +143,30 @@ main(int argc, char** argv)
 	std::cout << "\t\t--hashes " << hashes << std::endl;
 	std::cout << "\t\t-o " << out_file << std::endl;
 
+	ntedit_hip_ctx* ctx = nullptr;
+	std::vector<const char*> paths;
+	for (const std::string& g : genome_files) {
+		paths.push_back(g.c_str());
+	}
+	// one --gpu_parse pass over the genome files, and its information line
+	auto gpu_pass = [&](int insert, ntedit_hip_reads_pass_stats* st) {
+		if (!ctx && ntedit_hip_create(0, &ctx) != 0) {
+			std::cerr << "make_genome_bf: error: " << (ctx ? ntedit_hip_last_error(ctx) : "no HIP device") << std::endl;
+			exit(1);
+		}
+		if (ntedit_hip_genome_pass(ctx, NTEDIT_FILTER_PRIMARY, paths.data(), (uint32_t)paths.size(), batch_bytes, insert, st) != 0) {
+			std::cerr << "make_genome_bf: error: " << ntedit_hip_reads_last_error(ctx) << std::endl;
+			exit(1);
+		}
+		char line[1024], times[160];
+		snprintf(times, sizeof times, "%s pass: %llu bases, %.1f ms (GPU calls %.1f ms)", insert ? "Insert" : "Sizing",
+		         (unsigned long long)st->bases, st->ms_wall, st->ms_gpu);
+		log_info(times);
+		if (ntedit_hip_genome_pass_line(ctx, line, sizeof line) == 0) {
+			log_info(line);
+		}
+	};
+
 	uint64_t bf_size;
 	if (have_bf) {
 		bf_size = bf_bytes;
@@ -136,12 +177,24 @@ main(int argc, char** argv)
 	} else {
 		std::cout << "Calculating BF size based on input genome size" << std::endl;
 		uint64_t genome_size = 0;
+		if (gpu_parse) {
+			ntedit_hip_reads_pass_stats st;
+			gpu_pass(0, &st);
+			genome_size = st.bases;
+		}
 		for (const std::string& g : genome_files) {
+			if (gpu_parse) {
+				break;
+			}
 			nte_host::FastaReader reader(g.c_str());
 			std::string hdr, seq;
 			while (reader.ok() && reader.next(hdr, seq)) {
 				genome_size += seq.size();
 				seq.clear();
+			}
+			if (reader.ok() && reader.io_error()) { // (a damaged .gz: kseq would stop silently)
+				std::cerr << "make_genome_bf: error: " << g << ": " << reader.io_error_text() << std::endl;
+				return 1;
 			}
 		}
 		std::cout << "Genome size (bp): " << genome_size << std::endl;
@@ -149,8 +202,7 @@ main(int argc, char** argv)
 	}
 	std::cout << "BF size (bytes): " << bf_size << std::endl;
 
-	ntedit_hip_ctx* ctx = nullptr;
-	if (ntedit_hip_create(0, &ctx) != 0) {
+	if (!ctx && ntedit_hip_create(0, &ctx) != 0) {
 		std::cerr << "make_genome_bf: error: " << (ctx ? ntedit_hip_last_error(ctx) : "no HIP device") << std::endl;
 		return 1;
 	}
@@ -173,7 +225,17 @@ main(int argc, char** argv)
 		}
 		blob.clear();
 	};
+	if (gpu_parse) {
+		for (const std::string& g : genome_files) {
+			log_info("Reading " + g);
+		}
+		ntedit_hip_reads_pass_stats st;
+		gpu_pass(1, &st);
+	}
 	for (const std::string& g : genome_files) {
+		if (gpu_parse) {
+			break;
+		}
 		log_info("Reading " + g);
 		nte_host::FastaReader reader(g.c_str());
 		if (!reader.ok()) {
@@ -194,6 +256,10 @@ main(int argc, char** argv)
 				flush();
 			}
 		}
+		if (reader.io_error()) { // (a damaged .gz: kseq would stop silently)
+			std::cerr << "make_genome_bf: error: " << g << ": " << reader.io_error_text() << std::endl;
+			return 1;
+		}
 	}
 	flush();
 
@@ -211,6 +277,7 @@ main(int argc, char** argv)
 		return 1;
 	}
 	log_info("Done!");
+	ntedit_hip_sketch_free(ctx); // (the device parser's scratch, if --gpu_parse made any)
 	ntedit_hip_destroy(ctx);
 	return 0;
 }
