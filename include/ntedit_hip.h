@@ -262,6 +262,28 @@ int ntedit_hip_resident_histogram(ntedit_hip_ctx* ctx);
 int ntedit_hip_resident_insert_solid(ntedit_hip_ctx* ctx, int slot, uint32_t cmin);
 int ntedit_hip_resident_insert_solid2(ntedit_hip_ctx* ctx, uint32_t cmin, uint32_t rmin); /* as ntedit_hip_filter_insert_solid2, over the store */
 void ntedit_hip_resident_free(ntedit_hip_ctx* ctx);
+/* A store that outlives its sketch: the stored codes and validity bits do not depend on k, so one pass over the read
+ * files can serve sketches at several k (ntedit --reads -k K1,K2,...: a cascade of polishing rounds).
+ *   ntedit_hip_sketch_reset: a fresh, zeroed sketch of `counters` counters, hash_num and k in place of the context's,
+ *           the library's own memory, the histogram zeroed, WITHOUT releasing the store: its batches, bytes, cap and
+ *           state stay as they are, and so does the ntedit_hip_reads_set_min_read setting (the reject cutoff goes with
+ *           the old sketch).  Without a sketch or a store to keep it is ntedit_hip_sketch_alloc.  With counters = 0 it
+ *           only releases the counters, the batch staging and the device parser's scratch: the context then holds no
+ *           sketch (every sketch call is NTEDIT_E_ARG, ntedit_hip_resident_info and _free still answer) until the next
+ *           reset.  If the new sketch cannot be allocated the store is released with the old one.
+ *           ntedit_hip_sketch_alloc, _set_device and _free release the store, as always.
+ *   ntedit_hip_resident_count: pass 1 (as ntedit_hip_sketch_count over the same batches) over every stored batch, each
+ *           launched with its own n, into the context's current sketch: k_count staged from the store.  It stores
+ *           nothing again.  The sketch equals, byte for byte, the one ntedit_hip_sketch_count fills from the batches'
+ *           bytes at that k.  NTEDIT_E_ARG unless the state is ON.
+ *   ntedit_hip_reads_set_min_read: the shortest record ntedit_hip_reads_pass keeps, host parser and --gpu_parse (plain
+ *           and BGZF) alike; 0, or a length above the sketch's k, means k, as without the call.  A read shorter than k
+ *           holds no k-mer, so a smaller length changes no sketch, histogram or filter; it makes the store hold the
+ *           reads a later sketch at a smaller k has to count.  The `bases` of the pass statistics then count the reads
+ *           of `len` bases or more.  The setting lives with the context's reads state (NTEDIT_E_ARG without a sketch). */
+int ntedit_hip_sketch_reset(ntedit_hip_ctx* ctx, uint64_t counters, uint32_t hash_num, uint32_t k);
+int ntedit_hip_resident_count(ntedit_hip_ctx* ctx);
+int ntedit_hip_reads_set_min_read(ntedit_hip_ctx* ctx, uint32_t len);
 /* The whole filter build of ntedit-make-reads-bf, shared by it and `ntedit --reads`: the sketch (sketch_counters, as
  * sized by the caller), pass 1, with solid or hist_path the histogram pass (the --hist file, the --solid cutoff, and
  * with bf_bytes = 0 the output size from the histogram), the output filter allocated in the PRIMARY slot (counting
@@ -292,7 +314,14 @@ void ntedit_hip_resident_free(ntedit_hip_ctx* ctx);
  * bytes are those of a build with cmin = reject_cmin, bf_bytes = its size and the same sketch.  stage_decide resolves
  * its size (reject_bf_bytes as given, or from the histogram the k-mers at reject_cmin or above) into
  * res->reject_bf_bytes and refuses reject_cmin <= res->cmin; stage_insert allocates it (a sharded build: the SECONDARY
- * filter the caller adopted).  Not with `counts`. */
+ * filter the caller adopted).  Not with `counts`.
+ *
+ * A build may start from the store an earlier build left (keep_store, not for a sharded build): when the context's store
+ * is ON at ntedit_hip_reads_stage_count, the sketch is made with ntedit_hip_sketch_reset, pass 1 is
+ * ntedit_hip_resident_count and no file is opened by any pass; files / min_read are then unused, and the pass lines
+ * give the store's bytes (reads and separators) as their bases.  With keep_store a build that succeeds ends with
+ * ntedit_hip_sketch_reset(ctx, 0, 0, 0) instead of ntedit_hip_sketch_free when its store is ON; a build that fails, or
+ * whose store was released, frees everything as without it. */
 typedef struct ntedit_hip_reads_build_args
 {
 	const char* const* files;
@@ -318,6 +347,8 @@ typedef struct ntedit_hip_reads_build_args
 	uint32_t reject_cmin;     /* --reject_cutoff; 0: no reject filter */
 	uint64_t reject_bf_bytes; /* --reject_bf, or from --reject_num_elements; 0: from the histogram (needs solid or hist_path) */
 	uint64_t reject_num_elements; /* as given (the parameter echo) */
+	uint32_t min_read;        /* ntedit_hip_reads_set_min_read for this build's passes over the files; 0: k */
+	int keep_store;           /* the build ends with the sketch released and the store, if it is ON, kept for the next build */
 } ntedit_hip_reads_build_args;
 typedef struct ntedit_hip_reads_build_result
 {
@@ -329,6 +360,7 @@ typedef struct ntedit_hip_reads_build_result
 	double ms_total;
 	uint64_t store_batches;               /* batches it held after pass 1 */
 	uint64_t reject_bf_bytes;             /* the reject filter's size (0: none) */
+	int from_store;                       /* 1: the build began with a store that was ON, and pass 1 read it too */
 } ntedit_hip_reads_build_result;
 int ntedit_hip_reads_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res);
 int ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* args, ntedit_hip_reads_build_result* res,

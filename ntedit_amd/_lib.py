@@ -91,14 +91,15 @@ class ReadsBuildArgs(ctypes.Structure):
                 ("log", READS_LOG_FN), ("user", ctypes.c_void_p), ("begins", ctypes.POINTER(ctypes.c_uint64)),
                 ("ends", ctypes.POINTER(ctypes.c_uint64)), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32),
                 ("device_parse", ctypes.c_int), ("reject_cmin", ctypes.c_uint32), ("reject_bf_bytes", ctypes.c_uint64),
-                ("reject_num_elements", ctypes.c_uint64)]
+                ("reject_num_elements", ctypes.c_uint64), ("min_read", ctypes.c_uint32), ("keep_store", ctypes.c_int)]
 
 
 class ReadsBuildResult(ctypes.Structure):
     """ntedit_hip_reads_build_result"""
     _fields_ = [("cmin", ctypes.c_uint32), ("bf_bytes", ctypes.c_uint64), ("passes", ReadsPassStats * 3),
                 ("store_state", ctypes.c_int), ("store_bytes", ctypes.c_uint64), ("ms_total", ctypes.c_double),
-                ("store_batches", ctypes.c_uint64), ("reject_bf_bytes", ctypes.c_uint64)]
+                ("store_batches", ctypes.c_uint64), ("reject_bf_bytes", ctypes.c_uint64),
+                ("from_store", ctypes.c_int)]
 
 
 # the reads-option rules (ntedit_hip_reads_options_check) and the header's defaults
@@ -250,6 +251,7 @@ EXPORTS = [
     "ntedit_hip_reads_last_record_start", "ntedit_hip_reads_last_start_device", "ntedit_hip_reads_inflate_info",
     "ntedit_hip_genome_parse_device", "ntedit_hip_genome_parse_model", "ntedit_hip_genome_pass",
     "ntedit_hip_genome_pass_get_info", "ntedit_hip_genome_pass_line",
+    "ntedit_hip_sketch_reset", "ntedit_hip_resident_count", "ntedit_hip_reads_set_min_read",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -411,5 +413,9 @@ def load():
                                            ctypes.POINTER(ReadsPassStats)]
     lib.ntedit_hip_genome_pass_get_info.argtypes = [vp, ctypes.POINTER(GenomePassInfo)]
     lib.ntedit_hip_genome_pass_line.argtypes = [vp, ctypes.c_char_p, u64]
+    # a store that outlives its sketch (ntedit --reads -k K1,K2,...)
+    lib.ntedit_hip_sketch_reset.argtypes = [vp, u64, u32, u32]
+    lib.ntedit_hip_resident_count.argtypes = [vp]
+    lib.ntedit_hip_reads_set_min_read.argtypes = [vp, u32]
     _lib = lib
     return lib

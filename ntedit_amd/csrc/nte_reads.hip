@@ -11,7 +11,8 @@
 //                             per-wave LDS sub-histograms and flushed once per block (one 64-bit add per non-zero bin)
 //   k_pack                    after k_count, when the context keeps the reads resident: a batch packed into the store,
 //                             per 16 bases one u32 of 2-bit codes and one u16 of validity bits (3 bits per base)
-//   k_hist / k_solid / k_solid2 <.., PACKED = true>  the same passes staged from a stored batch instead of its bytes
+//   k_count / k_hist / k_solid / k_solid2 <.., PACKED = true>  the same passes staged from a stored batch instead of
+//                             its bytes (pass 1 too: a later sketch, at another k, is counted from the store)
 //   k_nonzero                 non-zero counters of the sketch (occupancy)
 //   k_merge<OP>               n_src equal byte chunks folded into one: saturating add (sketches), OR (plain filters),
 //                             max (counting filters) -- the merge of a sharded build
@@ -296,11 +297,11 @@ rd_walk(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __rest
 	}
 }
 
-template<int H, bool POW2>
+template<int H, bool POW2, bool PACKED>
 __global__ __launch_bounds__(RD_TPB) void
-k_count(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk)
+k_count(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __restrict__ tabs, DevParams p, RdFilter sk)
 {
-	rd_walk<H, POW2, 0>(seq, RdPacked{}, n, k, tabs, p, sk, sk, 0, nullptr);
+	rd_walk<H, POW2, 0, PACKED>(seq, pk, n, k, tabs, p, sk, sk, 0, nullptr);
 }
 
 template<int H, bool POW2, bool COUNTS, bool PACKED>
@@ -502,6 +503,7 @@ struct ReadsState
 	u64 store_bytes = 0, store_cap = 0;
 	int store_state = NTEDIT_RESIDENT_OFF;
 	u32 reject_cmin = 0; // ntedit_hip_reads_set_reject_cutoff: the SOLID pass of ntedit_hip_reads_pass fills both slots
+	u32 min_read = 0;    // ntedit_hip_reads_set_min_read: the shortest record the parsers keep (0: k)
 	std::string err;
 };
 
@@ -568,8 +570,9 @@ rfail(const ntedit_hip_ctx* c, int code, const char* fmt, ...)
 		}                                                                                        \
 	} while (0)
 
+// the context's state, with its sketch or after ntedit_hip_sketch_reset released the counters and kept the store
 ReadsState*
-find_state(const ntedit_hip_ctx* c)
+find_any_state(const ntedit_hip_ctx* c)
 {
 	std::lock_guard<std::mutex> lk(g_reads_mu);
 	for (ReadsState* s : g_reads) {
@@ -578,6 +581,14 @@ find_state(const ntedit_hip_ctx* c)
 		}
 	}
 	return nullptr;
+}
+
+// ... and only while it holds a sketch: what every call that touches the counters asks for
+ReadsState*
+find_state(const ntedit_hip_ctx* c)
+{
+	ReadsState* s = find_any_state(c);
+	return s && s->sketch ? s : nullptr;
 }
 
 void
@@ -641,12 +652,12 @@ void
 launch_walk(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, RdFilter sk, RdFilter out, u32 cmin, RdFilter out2,
             u32 rmin)
 {
-	static_assert(!(PACKED && PASS == 0), "pass 1 reads bytes");
 	dim3 grid((unsigned)tiles), block(RD_TPB);
 #define RD_LAUNCH(H)                                                                                               \
 	case H:                                                                                                        \
 		if constexpr (PASS == 0) {                                                                                 \
-			hipLaunchKernelGGL((k_count<H, POW2>), grid, block, 0, s->stream, d_seq, n, s->k, s->d_tab, s->dp, sk); \
+			hipLaunchKernelGGL((k_count<H, POW2, PACKED>), grid, block, 0, s->stream, d_seq, pk, n, s->k, s->d_tab,   \
+			                   s->dp, sk);                                                                         \
 		} else if constexpr (PASS == 4) {                                                                          \
 			hipLaunchKernelGGL((k_solid2<H, POW2, PACKED>), grid, block, 0, s->stream, d_seq, pk, n, s->k, s->d_tab,  \
 			                   s->dp, sk, out, out2, cmin, rmin);                                                  \
@@ -700,9 +711,9 @@ launch_pass(ReadsState* s, const u8* d_seq, RdPacked pk, u64 n, u64 tiles, int p
 	} else if (pass == 3) {
 		pow2 ? launch_walk<true, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
 		     : launch_walk<false, 3, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
-	} else if constexpr (!PACKED) {
-		pow2 ? launch_walk<true, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
-		     : launch_walk<false, 0, false>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
+	} else {
+		pow2 ? launch_walk<true, 0, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin)
+		     : launch_walk<false, 0, PACKED>(s, d_seq, pk, n, tiles, sk, out, cmin, out2, rmin);
 	}
 }
 
@@ -757,7 +768,7 @@ run_pass(const ntedit_hip_ctx* c, ReadsState* s, const char* bases, u64 n, int o
 	return 0;
 }
 
-// the histogram pass or pass 2 over every stored batch, each launched with its own n as it was counted
+// pass 1, the histogram pass or pass 2 over every stored batch, each launched with its own n as it was stored
 int
 run_store_pass(const ntedit_hip_ctx* c, ReadsState* s, int pass, RdFilter out, u32 cmin, RdFilter out2 = RdFilter{}, u32 rmin = 0)
 {
@@ -840,6 +851,14 @@ reject_cutoff(const ntedit_hip_ctx* c)
 	const ReadsState* s = find_state(c);
 	return s ? s->reject_cmin : 0;
 }
+// the shortest record the parsers keep for a sketch at k (ntedit_hip_reads_set_min_read): never above k, so that no
+// read with a k-mer is dropped
+uint32_t
+min_read(const ntedit_hip_ctx* c, uint32_t k)
+{
+	const ReadsState* s = find_state(c);
+	return s && s->min_read && s->min_read < k ? s->min_read : k;
+}
 } // namespace nte_reads
 
 extern "C" {
@@ -856,7 +875,7 @@ ntedit_hip_reads_last_error(const ntedit_hip_ctx* c)
 	return "";
 }
 
-static int make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, void* adopt);
+static int make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, void* adopt, bool keep_store = false);
 
 int
 ntedit_hip_sketch_alloc(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k)
@@ -940,7 +959,7 @@ ntedit_hip_merge_bytes(ntedit_hip_ctx* c, void* dst, const void* srcs, uint32_t 
 }
 
 static int
-make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, void* adopt)
+make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, void* adopt, bool keep_store)
 {
 	if (!c) {
 		return NTEDIT_E_ARG;
@@ -949,12 +968,36 @@ make_state(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k, 
 		return rfail(c, NTEDIT_E_ARG, "sketch_alloc: %llu counters, hash_num = %u, k = %u: needs counters > 0, hash_num in [1, %u] and k in [12, %u]",
 		             (unsigned long long)counters, hash_num, k, MAX_HASHES, RD_MAXK);
 	}
-	ntedit_hip_sketch_free(c);
+	// ntedit_hip_sketch_reset: the store and the settings that go with the reads, not with one sketch, move to the new
+	// state (the old stream is drained first: the store's pack kernels ran on it)
+	// (every call that can fail comes before the store changes hands: a failure here leaves the old state whole)
 	int device = 0;
 	RD_TRY(c, hipGetDevice(&device));
+	ReadsState carried;
+	ReadsState* old = find_any_state(c);
+	if (old) {
+		device = old->device; // (releasing the old state makes its device current, as it always did)
+	}
+	if (old && keep_store) {
+		RD_TRY(c, hipSetDevice(old->device));
+		RD_TRY(c, hipStreamSynchronize(old->stream));
+		carried.store.swap(old->store);
+		carried.store_bytes = old->store_bytes;
+		carried.store_cap = old->store_cap;
+		carried.store_state = old->store_state;
+		carried.min_read = old->min_read;
+		old->store_bytes = 0;
+		old->store_state = NTEDIT_RESIDENT_OFF;
+	}
+	ntedit_hip_sketch_free(c);
 	ReadsState* s = new ReadsState();
 	s->owner = c;
 	s->device = device;
+	s->store.swap(carried.store);
+	s->store_bytes = carried.store_bytes;
+	s->store_cap = carried.store_cap;
+	s->store_state = carried.store_state;
+	s->min_read = carried.min_read;
 	s->counters = (counters + 7) / 8 * 8; // btllib rounds a counting filter up to whole 64-bit words
 	s->adopted = adopt != nullptr;
 	s->sketch = (u8*)adopt;
@@ -1239,7 +1282,7 @@ ntedit_hip_resident_begin(ntedit_hip_ctx* c, uint64_t cap_bytes)
 int
 ntedit_hip_resident_info(ntedit_hip_ctx* c, ntedit_hip_resident_stats* st)
 {
-	ReadsState* s = find_state(c);
+	ReadsState* s = find_any_state(c); // (the store outlives the counters: ntedit_hip_sketch_reset)
 	if (!s || !st) {
 		return c ? rfail(c, NTEDIT_E_ARG, "resident_info: bad argument or no sketch") : NTEDIT_E_ARG;
 	}
@@ -1301,10 +1344,63 @@ ntedit_hip_resident_insert_solid2(ntedit_hip_ctx* c, uint32_t cmin, uint32_t rmi
 	return run_store_pass(c, s, 4, out, cmin, out2, rmin);
 }
 
+int
+ntedit_hip_resident_count(ntedit_hip_ctx* c)
+{
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return c ? rfail(c, NTEDIT_E_ARG, "resident_count: no sketch (ntedit_hip_sketch_reset / _alloc / _set_device)") : NTEDIT_E_ARG;
+	}
+	RdFilter none = {};
+	return run_store_pass(c, s, 0, none, 0);
+}
+
+int
+ntedit_hip_sketch_reset(ntedit_hip_ctx* c, uint64_t counters, uint32_t hash_num, uint32_t k)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	if (counters == 0) {
+		// the counters alone are released: the state stays for its store, and holds no sketch until the next reset
+		nte_reads::parse_release(c);
+		ReadsState* s = find_any_state(c);
+		if (s && s->sketch) {
+			RD_TRY(c, hipSetDevice(s->device));
+			RD_TRY(c, hipStreamSynchronize(s->stream));
+			if (!s->adopted) {
+				RD_TRY(c, hipFree(s->sketch));
+			}
+			s->sketch = nullptr;
+			s->adopted = false;
+			s->counters = 0;
+			s->reject_cmin = 0;
+		}
+		if (s && s->d_seq) {
+			RD_TRY(c, hipFree(s->d_seq)); // (the staging of host batches: the polish sizes its own buffers next)
+			s->d_seq = nullptr;
+			s->seq_cap = 0;
+		}
+		return 0;
+	}
+	return make_state(c, counters, hash_num, k, nullptr, true);
+}
+
+int
+ntedit_hip_reads_set_min_read(ntedit_hip_ctx* c, uint32_t len)
+{
+	ReadsState* s = find_state(c);
+	if (!s) {
+		return c ? rfail(c, NTEDIT_E_ARG, "reads_set_min_read: no sketch (ntedit_hip_sketch_alloc / _set_device)") : NTEDIT_E_ARG;
+	}
+	s->min_read = len;
+	return 0;
+}
+
 void
 ntedit_hip_resident_free(ntedit_hip_ctx* c)
 {
-	ReadsState* s = find_state(c);
+	ReadsState* s = find_any_state(c);
 	if (s) {
 		(void)hipSetDevice(s->device);
 		(void)hipStreamSynchronize(s->stream);

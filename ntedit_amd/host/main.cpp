@@ -14,6 +14,7 @@
 #include "../../include/ntedit_hip.h"
 #include "fasta.h"
 #include "fasta_map.h"
+#include "k_list.h"
 #include "log_info.h"
 
 #include <algorithm>
@@ -72,6 +73,11 @@ static const char USAGE[] = PROGRAM
     " same settings, built on the GPU into the context that polishes, no filter file needed):\n"
     "	--reads FILE...,	input reads, FASTA or FASTQ, plain or gzip (1 or more files)\n"
     "	-k,	k-mer size (bp), 12 to 200, REQUIRED with --reads (accepted and ignored without it)\n"
+    "	-k K1,K2,...,	a list of 2 to 8 different k: polish in a cascade of rounds, in that order (needs -b).  Round i builds\n"
+    "			the filter for Ki and polishes round i-1's _edited.fa; the last round writes <prefix>_edited.fa, an\n"
+    "			earlier one <prefix>_k<Ki>_edited.fa (and _changes.tsv, _variants.vcf).  The read files are parsed\n"
+    "			once: from round 2 on every pass reads the reads kept in HBM.  --hist, --save_bf and\n"
+    "			--save_reject_bf then need {k} in the name (each round puts its k there)\n"
     "	--cutoff C,	minimum k-mer count of the filter, 1 to 255 (ntedit-make-reads-bf -c)\n"
     "	--solid,	take the minimum count from the k-mer histogram instead (give --cutoff or --solid)\n"
     "	--counts,	build a counting filter (enables -p / -q)\n"
@@ -420,9 +426,9 @@ class Channel
 int
 main(int argc, char** argv)
 {
-	ntedit_hip_params p;
-	ntedit_hip_params_default(&p);
-	std::string draft, bf, bfrep, prefix, vcf;
+	ntedit_hip_params p_given; // (the options as given: each round works on a copy)
+	ntedit_hip_params_default(&p_given);
+	std::string draft_given, bf_given, bfrep_given, prefix_given, vcf;
 	unsigned nthreads = 4, ignored_u = 0;
 	bool threads_given = false;
 	int verbose = 0, gpu = 0, report = 0;
@@ -460,10 +466,11 @@ main(int argc, char** argv)
 	args.push_back(nullptr);
 	argc = (int)args.size() - 1;
 	argv = args.data();
-	std::string hist_out, save_bf, save_reject_bf;
+	std::string hist_given, save_bf_given, save_reject_bf_given; // (as given: a round of a cascade puts its k in place of {k})
 	bool counts = false, shard_given = false;
 	ntedit_hip_reads_options ro = {}; // the reads options as given; refused at the option where the rules say so
-	ntedit_hip_reads_rules rr = {};
+	std::vector<ntedit_hip_reads_rules> rounds(1); // the rules of each round (one, unless -k is a list); zeros without --reads
+	std::vector<std::string> k_list;               // -k K1,K2,...: its k as given, in order
 	std::vector<std::string> reads_only; // reads options given (refused without --reads)
 	// a reads option with a value: its text to the rules, which refuse at the option what they refuse there
 	auto reads_option = [&](const char* name, const char** text) {
@@ -481,66 +488,66 @@ main(int argc, char** argv)
 			threads_given = true;
 			break;
 		case 'f':
-			parse(c, optarg, draft);
+			parse(c, optarg, draft_given);
 			break;
 		case 'z':
-			parse(c, optarg, p.min_contig_len);
+			parse(c, optarg, p_given.min_contig_len);
 			break;
 		case 'b':
-			parse(c, optarg, prefix);
+			parse(c, optarg, prefix_given);
 			break;
 		case 'r':
-			parse(c, optarg, bf);
+			parse(c, optarg, bf_given);
 			break;
 		case 'e':
-			parse(c, optarg, bfrep);
+			parse(c, optarg, bfrep_given);
 			break;
 		case 'd':
-			parse(c, optarg, p.max_deletions);
+			parse(c, optarg, p_given.max_deletions);
 			break;
 		case 'i':
-			parse(c, optarg, p.max_insertions);
+			parse(c, optarg, p_given.max_insertions);
 			break;
 		case 'x':
-			parse(c, optarg, p.missing_threshold);
+			parse(c, optarg, p_given.missing_threshold);
 			break;
 		case 'y':
-			parse(c, optarg, p.edit_threshold);
+			parse(c, optarg, p_given.edit_threshold);
 			break;
 		case 'X':
-			parse(c, optarg, p.missing_ratio);
-			p.use_ratio = 1;
+			parse(c, optarg, p_given.missing_ratio);
+			p_given.use_ratio = 1;
 			break;
 		case 'Y':
-			parse(c, optarg, p.edit_ratio);
-			p.use_ratio = 1;
+			parse(c, optarg, p_given.edit_ratio);
+			p_given.use_ratio = 1;
 			break;
 		case 'c':
 			parse(c, optarg, ignored_u); // overwritten by k*1.5 (ntedit.cpp:2450)
 			break;
 		case 'j':
-			parse(c, optarg, p.jump);
+			parse(c, optarg, p_given.jump);
 			break;
 		case 'm':
-			parse(c, optarg, p.mode);
+			parse(c, optarg, p_given.mode);
 			break;
 		case 's':
-			parse(c, optarg, p.snv);
+			parse(c, optarg, p_given.snv);
 			break;
 		case 'l':
 			parse(c, optarg, vcf);
 			break;
 		case 'a':
-			parse(c, optarg, p.mask);
+			parse(c, optarg, p_given.mask);
 			break;
 		case 'v':
 			parse(c, optarg, verbose);
 			break;
 		case 'p':
-			parse(c, optarg, p.min_threshold);
+			parse(c, optarg, p_given.min_threshold);
 			break;
 		case 'q':
-			parse(c, optarg, p.max_threshold);
+			parse(c, optarg, p_given.max_threshold);
 			break;
 		case 'k':
 			// without --reads: accepted and ignored (the reference rejects it: no `case 'k'`, ntedit.cpp:2360-2363)
@@ -573,12 +580,12 @@ main(int argc, char** argv)
 			reads_option("--sketch_bytes", &ro.sketch_bytes);
 			break;
 		case OPT_HIST:
-			hist_out = optarg;
+			hist_given = optarg;
 			ro.hist = 1;
 			reads_only.push_back("--hist");
 			break;
 		case OPT_SAVE_BF:
-			save_bf = optarg;
+			save_bf_given = optarg;
 			reads_only.push_back("--save_bf");
 			break;
 		case OPT_REJECT_CUTOFF:
@@ -591,7 +598,7 @@ main(int argc, char** argv)
 			reads_option("--reject_num_elements", &ro.reject_num_elements);
 			break;
 		case OPT_SAVE_REJECT_BF:
-			save_reject_bf = optarg;
+			save_reject_bf_given = optarg;
 			ro.reject_out = 1;
 			reads_only.push_back("--save_reject_bf");
 			break;
@@ -613,10 +620,10 @@ main(int argc, char** argv)
 			batch_given = true;
 			break;
 		case OPT_START_GRID:
-			parse(c, optarg, p.start_grid);
+			parse(c, optarg, p_given.start_grid);
 			break;
 		case OPT_EVENT_BUDGET:
-			parse(c, optarg, p.event_budget);
+			parse(c, optarg, p_given.event_budget);
 			break;
 		case OPT_SHARD:
 			if (sscanf(optarg, "%u/%u", &shard_i, &shard_n) != 2 || shard_n == 0 || shard_i >= shard_n) {
@@ -666,15 +673,24 @@ main(int argc, char** argv)
 	time_t rawtime;
 	time(&rawtime);
 	printf("---------- initializing                             : %s", ctime(&rawtime));
-	if (draft.empty()) {
+	if (draft_given.empty()) {
 		fprintf(stderr, PROGRAM ": error: need to specify assembly draft file (-f)\n");
 		die = true;
 	} else {
-		die_unreadable(draft);
+		die_unreadable(draft_given);
+	}
+	if (ro.k && strchr(ro.k, ',')) {
+		// every refusal of a list of k before the device is opened and before any file is written
+		const std::string why = nte_host::k_list_rules(ro.k, reads_mode, shard_given, !prefix_given.empty(),
+		                                     { { "--save_bf", save_bf_given }, { "--save_reject_bf", save_reject_bf_given }, { "--hist", hist_given } },
+		                                     &k_list);
+		if (!why.empty()) {
+			refuse(why);
+		}
 	}
 	if (genome_mode) {
 		// every refusal of --genome before the device is opened and before any file is written
-		const std::string why = genome_rules(ro, !bf.empty(), reads_mode, shard_given, genome_files.size(), reads_only, &gr);
+		const std::string why = genome_rules(ro, !bf_given.empty(), reads_mode, shard_given, genome_files.size(), reads_only, &gr);
 		if (!why.empty()) {
 			refuse(why);
 		}
@@ -684,7 +700,7 @@ main(int argc, char** argv)
 		}
 	} else if (reads_mode) {
 		// every refusal of --reads before the device is opened and before any file is written
-		if (!bf.empty()) {
+		if (!bf_given.empty()) {
 			refuse("--reads and -r: give one of them (--reads builds the filter that -r would load)");
 		}
 		if (read_files.empty()) {
@@ -694,7 +710,7 @@ main(int argc, char** argv)
 			refuse("--reads and --shard: every shard would build the whole filter again; build it once with "
 			       "ntedit-make-reads-bf and give each shard -r");
 		}
-		if (ro.reject_cutoff && !bfrep.empty()) {
+		if (ro.reject_cutoff && !bfrep_given.empty()) {
 			refuse("--reject_cutoff and -e: give one of them (--reject_cutoff builds the filter that -e would load)");
 		}
 		for (const std::string& r : read_files) {
@@ -703,7 +719,16 @@ main(int argc, char** argv)
 		ro.counts = counts;
 		ro.files = paths.data(); // (for the default sketch: their sizes)
 		ro.n_files = (uint32_t)paths.size();
-		rr = reads_rules(ro, 1);
+		if (k_list.empty()) {
+			rounds[0] = reads_rules(ro, 1);
+		} else {
+			// (every option but -k applies to every round alike; sizes taken from the histogram are found per round)
+			rounds.clear();
+			for (const std::string& kt : k_list) {
+				ro.k = kt.c_str();
+				rounds.push_back(reads_rules(ro, 1));
+			}
+		}
 		for (const std::string& r : read_files) {
 			die_unreadable(r);
 		}
@@ -715,20 +740,20 @@ main(int argc, char** argv)
 			both = both || reads_only[0] == o;
 		}
 		refuse(reads_only[0] + (both ? ": only with --reads or --genome" : ": only with --reads"));
-	} else if (bf.empty()) {
+	} else if (bf_given.empty()) {
 		fprintf(stderr, PROGRAM ": error: need to specify the Bloom filter file (-r)\n");
 		die = true;
 	} else {
-		die_unreadable(bf);
+		die_unreadable(bf_given);
 	}
-	if (!bfrep.empty()) {
-		die_unreadable(bfrep);
+	if (!bfrep_given.empty()) {
+		die_unreadable(bfrep_given);
 	}
 	if (die) {
 		fprintf(stderr, "Try `" PROGRAM " --help' for more information.\n");
 		exit(EXIT_FAILURE);
 	}
-	if (p.snv) {
+	if (p_given.snv) {
 		// ntedit.cpp:2411-2417
 		fprintf(stderr, "\nSNV mode ON\nTracking all single-base variants\nNote: -i and -d both set to 0 when -s is set to 1\n"
 		                "Consider -l clinvar.vcf to identify SNVs with putative clinical significance\n\n");
@@ -764,7 +789,7 @@ main(int argc, char** argv)
 		// bytes (3 x 1 GiB of page-locked memory and ~30 GB of device buffers for a 5 Mbp draft otherwise).  Compressed
 		// drafts keep the full size: their length is not known in advance.
 		struct stat sb;
-		FILE* probe = fopen(draft.c_str(), "rb");
+		FILE* probe = fopen(draft_given.c_str(), "rb");
 		if (probe) {
 			unsigned char magic[2] = { 0, 0 };
 			const bool gz = fread(magic, 1, 2, probe) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
@@ -796,614 +821,681 @@ main(int argc, char** argv)
 		fflush(nullptr);
 		_exit(EXIT_FAILURE); // (_exit: the side thread above may still be running)
 	};
-	time(&rawtime);
-	if (genome_mode) {
-		// the filter ntedit-make-genome-bf would write, built into the primary slot (genome_pass.cpp): sized as the tool
-		// sizes it, every k-mer of every record of k bases or more inserted; without --gpu_parse the host parser reads
-		// the files (batch_bytes 0)
-		printf("---------- building Bloom filter from genome        : %s\n", ctime(&rawtime));
-		fflush(stdout);
-		const auto g0 = std::chrono::steady_clock::now();
-		const uint64_t batch = gr.gpu_parse ? gr.batch_bytes : 0;
-		auto pass = [&](int insert) {
-			ntedit_hip_reads_pass_stats st;
-			if (ntedit_hip_genome_pass(ctx, NTEDIT_FILTER_PRIMARY, paths.data(), (uint32_t)paths.size(), batch, insert, &st) != 0) {
+	// One round: build or load the filter, echo the parameters, polish `draft_in`, write the three outputs under
+	// `prefix_in`.  A run is one round, or with --reads -k K1,K2,...,Kn a cascade of n: round i + 1 polishes round i's
+	// _edited.fa (through the file: 1/30 of the data, and every round stays byte-comparable with a stand-alone run), and
+	// from round 2 on every pass of the filter build reads the resident store that round 1 filled.
+	const size_t n_rounds = rounds.size();
+	bool store_lost = false; // a cascade's store was released (over its cap, no memory, the polish buffers): no round tries it again
+	auto polish_round = [&](size_t round, const std::string& draft_in, const std::string& prefix_in) {
+		const bool cascade = n_rounds > 1, last_round = round + 1 == n_rounds;
+		const ntedit_hip_reads_rules& rr = rounds[round];
+		const std::string& draft = draft_in;
+		ntedit_hip_params p = p_given;
+		std::string bf = bf_given, bfrep = bfrep_given, prefix = prefix_in;
+		// (with a list of k the names of the saved files carry {k}: this round's k goes there)
+		const std::string hist_out = cascade ? nte_host::with_k(hist_given, rr.k) : hist_given,
+		                  save_bf = cascade ? nte_host::with_k(save_bf_given, rr.k) : save_bf_given,
+		                  save_reject_bf = cascade ? nte_host::with_k(save_reject_bf_given, rr.k) : save_reject_bf_given;
+		bool store_held = false; // the resident store stays in HBM while this round polishes (for the next round)
+		time(&rawtime);
+		if (genome_mode) {
+			// the filter ntedit-make-genome-bf would write, built into the primary slot (genome_pass.cpp): sized as the tool
+			// sizes it, every k-mer of every record of k bases or more inserted; without --gpu_parse the host parser reads
+			// the files (batch_bytes 0)
+			printf("---------- building Bloom filter from genome        : %s\n", ctime(&rawtime));
+			fflush(stdout);
+			const auto g0 = std::chrono::steady_clock::now();
+			const uint64_t batch = gr.gpu_parse ? gr.batch_bytes : 0;
+			auto pass = [&](int insert) {
+				ntedit_hip_reads_pass_stats st;
+				if (ntedit_hip_genome_pass(ctx, NTEDIT_FILTER_PRIMARY, paths.data(), (uint32_t)paths.size(), batch, insert, &st) != 0) {
+					fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_reads_last_error(ctx));
+					fatal();
+				}
+				char line[1024];
+				if (gr.gpu_parse && ntedit_hip_genome_pass_line(ctx, line, sizeof line) == 0) {
+					fprintf(stderr, "%s pass: %llu bases, %.1f ms (GPU calls %.1f ms)\n%s\n", insert ? "Insert" : "Sizing",
+					        (unsigned long long)st.bases, st.ms_wall, st.ms_gpu, line);
+				}
+				return st.bases;
+			};
+			uint64_t bf_size = gr.bf_bytes;
+			if (!gr.have_bf && gr.have_ne) {
+				bf_size = ntedit_hip_reads_bf_size(gr.num_elements, gr.hash_num, gr.fpr);
+			} else if (!gr.have_bf) {
+				const uint64_t genome_size = pass(0);
+				printf("Genome size (bp): %llu\n", (unsigned long long)genome_size);
+				bf_size = ntedit_hip_reads_bf_size(genome_size, gr.hash_num, gr.fpr);
+				if (bf_size == 0) {
+					fprintf(stderr, PROGRAM ": error: --genome: no bases in the genome files: the filter would be empty\n");
+					fatal();
+				}
+			}
+			printf("BF size (bytes): %llu\n", (unsigned long long)bf_size);
+			if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, gr.hash_num, gr.k) != 0) {
+				fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
+				fatal();
+			}
+			(void)pass(1);
+			ntedit_hip_sketch_free(ctx); // (the device parser's scratch: the polish sizes its own buffers next)
+			printf("Genome filter built in %.1f ms\n",
+			       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count());
+			if (!save_bf.empty()) {
+				if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, save_bf.c_str()) != 0) {
+					fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_bf.c_str());
+					fatal();
+				}
+				printf("Bloom filter saved to %s\n", save_bf.c_str());
+			}
+			// (the _r part of the default prefix: the name ntedit-make-genome-bf would have written it under)
+			bf = save_bf.empty() ? "genome_bf.bf" : save_bf;
+		} else if (reads_mode) {
+			// the filter ntedit-make-reads-bf would write, built into the primary slot (reads_pass.cpp); the reads stay
+			// resident in HBM after pass 1 unless they would pass store_cap, so that the later passes do not parse them again
+			if (cascade) {
+				printf("---------- round %zu of %zu: k = %u\n", round + 1, n_rounds, rr.k);
+			}
+			printf("---------- building Bloom filter from reads         : %s\n", ctime(&rawtime));
+			fflush(stdout);
+			printf("BF size (bytes): ");
+			if (rr.size_from_hist) {
+				printf("from the k-mer histogram\n");
+			} else {
+				printf("%llu\n", (unsigned long long)rr.bf_bytes);
+			}
+			if (rr.reject_cmin && rr.reject_size_from_hist) {
+				printf("Reject BF size (bytes): from the k-mer histogram\n");
+			} else if (rr.reject_cmin) {
+				printf("Reject BF size (bytes): %llu\n", (unsigned long long)rr.reject_bf_bytes);
+			}
+			printf("Sketch size (counters): %llu\n", (unsigned long long)rr.sketch_counters);
+			ntedit_hip_reads_build_args ba = {};
+			ba.files = paths.data();
+			ba.n_files = (uint32_t)paths.size();
+			ba.k = rr.k;
+			ba.hash_num = rr.hash_num;
+			ba.cmin = rr.cmin;
+			ba.solid = ro.solid;
+			ba.counts = counts;
+			ba.bf_bytes = rr.bf_bytes;
+			ba.fpr = rr.fpr;
+			ba.sketch_counters = rr.sketch_counters;
+			ba.batch_bytes = rr.batch_bytes;
+			ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
+			ba.use_store = 1;
+			ba.store_cap = rr.store_cap;
+			ba.device_parse = rr.gpu_parse;
+			ba.reject_cmin = rr.reject_cmin;
+			ba.reject_bf_bytes = rr.reject_bf_bytes;
+			ba.reject_num_elements = rr.reject_num_elements;
+			if (cascade) {
+				// round 1 fills the store with every read a later round has to count (the shortest k decides) and every
+				// round but the last leaves it to the next; a round that finds it ON reads nothing else
+				uint32_t min_k = rr.k;
+				for (const ntedit_hip_reads_rules& other : rounds) {
+					min_k = other.k < min_k ? other.k : min_k;
+				}
+				// (every round that reads files keeps the reads of min_k bases or more: whichever round fills the store, a
+				// later round at a smaller k finds in it all it has to count)
+				ba.min_read = min_k;
+				ba.keep_store = last_round ? 0 : 1;
+				// a store that was released once is not tried again: every later round reads the files, as separate runs would
+				ba.use_store = store_lost ? 0 : 1;
+			}
+			ba.log = nte_host::reads_log;
+			ntedit_hip_reads_build_result br;
+			if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 				fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_reads_last_error(ctx));
 				fatal();
 			}
-			char line[1024];
-			if (gr.gpu_parse && ntedit_hip_genome_pass_line(ctx, line, sizeof line) == 0) {
-				fprintf(stderr, "%s pass: %llu bases, %.1f ms (GPU calls %.1f ms)\n%s\n", insert ? "Insert" : "Sizing",
-				        (unsigned long long)st.bases, st.ms_wall, st.ms_gpu, line);
+			if (br.from_store) {
+				printf("Reads filter built in %.1f ms (minimum count %u; pass 1, the histogram pass and pass 2 read the resident store)\n",
+				       br.ms_total, br.cmin);
+			} else {
+				printf("Reads filter built in %.1f ms (minimum count %u; the histogram pass and pass 2 read %s)\n", br.ms_total,
+				       br.cmin, br.store_state == NTEDIT_RESIDENT_ON ? "the resident store" : "the files");
 			}
-			return st.bases;
-		};
-		uint64_t bf_size = gr.bf_bytes;
-		if (!gr.have_bf && gr.have_ne) {
-			bf_size = ntedit_hip_reads_bf_size(gr.num_elements, gr.hash_num, gr.fpr);
-		} else if (!gr.have_bf) {
-			const uint64_t genome_size = pass(0);
-			printf("Genome size (bp): %llu\n", (unsigned long long)genome_size);
-			bf_size = ntedit_hip_reads_bf_size(genome_size, gr.hash_num, gr.fpr);
-			if (bf_size == 0) {
-				fprintf(stderr, PROGRAM ": error: --genome: no bases in the genome files: the filter would be empty\n");
+			if (cascade) {
+				printf("Round %zu of %zu: k = %u, minimum count %u, %s\n", round + 1, n_rounds, rr.k, br.cmin,
+				       br.from_store                             ? "every pass read the resident store, no read file was opened"
+				       : br.store_state == NTEDIT_RESIDENT_ON ? "pass 1 read the files and filled the resident store, the later passes read it"
+				                                                 : "every pass read the files (the resident store was released)");
+			}
+			store_held = cascade && !last_round && br.store_state == NTEDIT_RESIDENT_ON;
+			store_lost = store_lost || (cascade && br.store_state != NTEDIT_RESIDENT_ON);
+			if (!save_bf.empty()) {
+				if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, save_bf.c_str()) != 0) {
+					fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_bf.c_str());
+					fatal();
+				}
+				printf("Bloom filter saved to %s\n", save_bf.c_str());
+			}
+			// the reject filter, built into the secondary slot by the same pass 2: no -e file is loaded
+			if (rr.reject_cmin) {
+				printf("Reject filter built (reject count %u, %llu bytes)\n", rr.reject_cmin, (unsigned long long)br.reject_bf_bytes);
+				if (!save_reject_bf.empty()) {
+					if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_SECONDARY, save_reject_bf.c_str()) != 0) {
+						fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_reject_bf.c_str());
+						fatal();
+					}
+					printf("Reject Bloom filter saved to %s\n", save_reject_bf.c_str());
+				}
+				// (the -e line of the parameter echo; the reference's prefix has no -e part)
+				bfrep = save_reject_bf.empty() ? "reads_k" + std::to_string(rr.k) + "_reject.bf" : save_reject_bf;
+			}
+			// (the _r part of the default prefix: the name ntedit-make-reads-bf would have written it under)
+			bf = save_bf.empty() ? "reads_k" + std::to_string(rr.k) + ".bf" : save_bf;
+		} else {
+			printf("---------- loading Bloom filter from file           : %s\n", ctime(&rawtime));
+			if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_PRIMARY, bf.c_str()) != 0) {
+				fprintf(stderr, PROGRAM ": error: Bloom filter file supplied (-r) is incorrect. (%s)\n", ntedit_hip_last_error(ctx));
 				fatal();
 			}
 		}
-		printf("BF size (bytes): %llu\n", (unsigned long long)bf_size);
-		if (ntedit_hip_filter_alloc(ctx, NTEDIT_FILTER_PRIMARY, bf_size, gr.hash_num, gr.k) != 0) {
+		uint32_t k = 0, h = 0;
+		uint64_t nbytes = 0;
+		int counting = 0;
+		ntedit_hip_filter_info(ctx, NTEDIT_FILTER_PRIMARY, &k, &h, &nbytes, &counting);
+		printf("BLOOM::\tcounting: %s\tsize: %llu\tnumber hash functions: %u\tkmer size: %u\n", counting ? "YES" : "NO",
+		       (unsigned long long)nbytes, h, k);
+		if (!counting && p.min_threshold != 1) {
+			// ntedit.cpp:2453-2458
+			fprintf(stderr, PROGRAM ": warning: Bloom filter is not counting, min k-mer presence threshold will be set to 1.\n");
+			p.min_threshold = 1;
+		}
+		time(&rawtime);
+		printf("\n---------- verifying parameters                     : %s", ctime(&rawtime));
+		char warn[1024];
+		ntedit_hip_params_clamp(&p, warn, sizeof warn);
+		if (warn[0]) {
+			fputs(warn, stderr);
+		}
+		if (prefix.empty()) {
+			// ntedit.cpp:2496-2502
+			std::ostringstream o;
+			o << base_name(draft) << "_k" << k << "_z" << p.min_contig_len << "_r" << base_name(bf) << "_i"
+			  << p.max_insertions << "_d" << p.max_deletions << "_m" << p.mode;
+			prefix = o.str();
+		}
+		printf("\nrunning : " PROGRAM " (MI355X HIP hot path)\n -f %s\n -k %u\n -z %u\n -b %s\n -r %s\n -e %s\n -i %u\n -d %u",
+		       base_name(draft).c_str(), k, p.min_contig_len, prefix.c_str(), base_name(bf).c_str(),
+		       base_name(bfrep).c_str(), p.max_insertions, p.max_deletions);
+		if (p.use_ratio) {
+			printf("\n -X %g\n -Y %g", p.missing_ratio, p.edit_ratio);
+		} else {
+			printf("\n -x %g\n -y %g", p.missing_threshold, p.edit_threshold);
+		}
+		printf("\n -j %u\n -m %d\n -s %d\n -l %s\n -a %d\n -t %u\n -v %d\n\n", p.jump, p.mode, p.snv, base_name(vcf).c_str(),
+		       p.mask, nthreads, verbose);
+		if (counting) {
+			printf(" -p %u\n -q %u\n\n", p.min_threshold, p.max_threshold); // ntedit.cpp:2519-2522
+		}
+
+		if (!bfrep.empty()) {
+			time(&rawtime);
+			if (rr.reject_cmin) {
+				printf("---------- secondary Bloom filter built from reads   : %s\n", ctime(&rawtime));
+			} else {
+				printf("---------- loading secondary Bloom filter from file : %s\n", ctime(&rawtime));
+				if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_SECONDARY, bfrep.c_str()) != 0) {
+					fprintf(stderr, PROGRAM ": error: secondary Bloom filter file supplied (-e) is incorrect.\n");
+					fatal();
+				}
+			}
+			uint32_t k2 = 0;
+			ntedit_hip_filter_info(ctx, NTEDIT_FILTER_SECONDARY, &k2, nullptr, nullptr, nullptr);
+			if (k2 != k) {
+				fprintf(stderr, PROGRAM ": error: secondary Bloom filter k size (%u) is different than main Bloom filter k size (%u)\n", k2, k);
+				fatal();
+			}
+		}
+		if (ntedit_hip_set_params(ctx, &p) != 0) {
 			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
 			fatal();
 		}
-		(void)pass(1);
-		ntedit_hip_sketch_free(ctx); // (the device parser's scratch: the polish sizes its own buffers next)
-		printf("Genome filter built in %.1f ms\n",
-		       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count());
-		if (!save_bf.empty()) {
-			if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, save_bf.c_str()) != 0) {
-				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_bf.c_str());
+		// start-up, like the filter load: the context's buffers for the largest batch + one internal warm-up batch, so that
+		// the first polish_batch call costs what the later ones do (ntedit_hip_reserve)
+		int reserved = ntedit_hip_reserve(ctx, pin_bytes, 1u << 16, 0, no_pack ? NTEDIT_HIP_BASES_HOST : NTEDIT_HIP_BASES_PACKED);
+		if (reserved != 0 && store_held) {
+			// the store is held for the next round: when the polish buffers do not fit beside it, it goes, and the later
+			// rounds read the files
+			ntedit_hip_sketch_free(ctx);
+			store_lost = true;
+			printf("Resident store: released (the polish buffers of round %zu did not fit beside it); the later rounds read the files\n",
+			       round + 1);
+			reserved = ntedit_hip_reserve(ctx, pin_bytes, 1u << 16, 0, no_pack ? NTEDIT_HIP_BASES_HOST : NTEDIT_HIP_BASES_PACKED);
+		}
+		if (reserved != 0) {
+			// (optional: the buffers then grow on demand, inside the first calls)
+			fprintf(stderr, PROGRAM ": warning: buffers could not be sized ahead (%s); they grow on demand\n", ntedit_hip_last_error(ctx));
+		}
+		if (pin_thread.joinable()) {
+			pin_thread.join();
+		}
+
+		time(&rawtime);
+		printf("---------- reading/processing input sequence        : %s", ctime(&rawtime));
+		const auto t0 = std::chrono::steady_clock::now(); // (--report: this stamp -> "process complete")
+		const std::string fa_path = prefix + "_edited.fa", tsv_path = prefix + "_changes.tsv",
+		                  vcf_path = prefix + "_variants.vcf";
+		{
+			FILE* f = fopen(fa_path.c_str(), "wb");
+			if (!f) {
+				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", fa_path.c_str());
 				fatal();
 			}
-			printf("Bloom filter saved to %s\n", save_bf.c_str());
+			fclose(f);
 		}
-		// (the _r part of the default prefix: the name ntedit-make-genome-bf would have written it under)
-		bf = save_bf.empty() ? "genome_bf.bf" : save_bf;
-	} else if (reads_mode) {
-		// the filter ntedit-make-reads-bf would write, built into the primary slot (reads_pass.cpp); the reads stay
-		// resident in HBM after pass 1 unless they would pass store_cap, so that the later passes do not parse them again
-		printf("---------- building Bloom filter from reads         : %s\n", ctime(&rawtime));
-		fflush(stdout);
-		printf("BF size (bytes): ");
-		if (rr.size_from_hist) {
-			printf("from the k-mer histogram\n");
-		} else {
-			printf("%llu\n", (unsigned long long)rr.bf_bytes);
-		}
-		if (rr.reject_cmin && rr.reject_size_from_hist) {
-			printf("Reject BF size (bytes): from the k-mer histogram\n");
-		} else if (rr.reject_cmin) {
-			printf("Reject BF size (bytes): %llu\n", (unsigned long long)rr.reject_bf_bytes);
-		}
-		printf("Sketch size (counters): %llu\n", (unsigned long long)rr.sketch_counters);
-		ntedit_hip_reads_build_args ba = {};
-		ba.files = paths.data();
-		ba.n_files = (uint32_t)paths.size();
-		ba.k = rr.k;
-		ba.hash_num = rr.hash_num;
-		ba.cmin = rr.cmin;
-		ba.solid = ro.solid;
-		ba.counts = counts;
-		ba.bf_bytes = rr.bf_bytes;
-		ba.fpr = rr.fpr;
-		ba.sketch_counters = rr.sketch_counters;
-		ba.batch_bytes = rr.batch_bytes;
-		ba.hist_path = hist_out.empty() ? nullptr : hist_out.c_str();
-		ba.use_store = 1;
-		ba.store_cap = rr.store_cap;
-		ba.device_parse = rr.gpu_parse;
-		ba.reject_cmin = rr.reject_cmin;
-		ba.reject_bf_bytes = rr.reject_bf_bytes;
-		ba.reject_num_elements = rr.reject_num_elements;
-		ba.log = nte_host::reads_log;
-		ntedit_hip_reads_build_result br;
-		if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
-			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_reads_last_error(ctx));
+		if (ntedit_hip_write_tsv_header(tsv_path.c_str(), k, p.jump, counting) != 0) {
+			fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", tsv_path.c_str());
 			fatal();
 		}
-		printf("Reads filter built in %.1f ms (minimum count %u; the histogram pass and pass 2 read %s)\n", br.ms_total,
-		       br.cmin, br.store_state == NTEDIT_RESIDENT_ON ? "the resident store" : "the files");
-		if (!save_bf.empty()) {
-			if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_PRIMARY, save_bf.c_str()) != 0) {
-				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_bf.c_str());
-				fatal();
-			}
-			printf("Bloom filter saved to %s\n", save_bf.c_str());
+		if (ntedit_hip_write_vcf_header(vcf_path.c_str(), draft.c_str()) != 0) { // ntedit.cpp:2192-2211
+			fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", vcf_path.c_str());
+			fatal();
 		}
-		// the reject filter, built into the secondary slot by the same pass 2: no -e file is loaded
-		if (rr.reject_cmin) {
-			printf("Reject filter built (reject count %u, %llu bytes)\n", rr.reject_cmin, (unsigned long long)br.reject_bf_bytes);
-			if (!save_reject_bf.empty()) {
-				if (ntedit_hip_filter_save_file(ctx, NTEDIT_FILTER_SECONDARY, save_reject_bf.c_str()) != 0) {
-					fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", save_reject_bf.c_str());
+		ntedit_hip_annot* annot = nullptr;
+		if (!vcf.empty()) {
+			// -l: annotated variants (e.g. clinvar.vcf[.gz]), ntedit.cpp:2524-2562
+			die_unreadable(vcf);
+			if (ntedit_hip_annot_load(vcf.c_str(), &annot) != 0) {
+				fprintf(stderr, "Unable to open file\n");
+			}
+		}
+
+		// Plain multi-FASTA files are taken apart by several threads from a mapping of the file (fasta_map.h); anything
+		// else (gzip, FASTQ, CR line ends, ...) goes through the streaming reader.  --no-map forces the latter.
+		unsigned ingest_threads = threads_given ? nthreads : std::thread::hardware_concurrency();
+		if (ingest_threads > 16) {
+			ingest_threads = 16;
+		}
+		if (ingest_threads < 1) {
+			ingest_threads = 1;
+		}
+		// (BGZF members are inflated before that: compute-bound, so on more threads than the memory-bound parse)
+		unsigned inflate_threads = threads_given ? nthreads : std::thread::hardware_concurrency();
+		if (inflate_threads > 64) {
+			inflate_threads = 64;
+		}
+		const auto tm0 = std::chrono::steady_clock::now();
+		nte_host::FastaMap fmap(no_map ? "" : draft.c_str(), ingest_threads, inflate_threads);
+		const double s_index = std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
+		const double s_before_index = std::chrono::duration<double>(tm0 - t0).count();
+
+		// --shard I/N: the contigs >= -z are split by bases, greedy longest-first (the partition of
+		// ntedit_amd.dist.shard_contigs): a first pass over the draft collects the lengths
+		std::vector<uint8_t> mine; // by ordinal
+		if (shard_n > 1) {
+			std::vector<uint64_t> lens;
+			if (fmap.ok()) {
+				fmap.measure(0, fmap.records());
+				for (size_t i = 0; i < fmap.records(); i++) {
+					if (fmap.length(i) >= p.min_contig_len) {
+						lens.push_back(fmap.length(i));
+					}
+				}
+			} else {
+				nte_host::FastaReader scan(draft.c_str());
+				if (!scan.ok()) {
+					fprintf(stderr, PROGRAM ": error: `%s': cannot open\n", draft.c_str());
 					fatal();
 				}
-				printf("Reject Bloom filter saved to %s\n", save_reject_bf.c_str());
+				std::string h, sq;
+				while (scan.next(h, sq)) {
+					const void* z = memchr(sq.data(), 0, sq.size());
+					const size_t len = z ? (size_t)((const char*)z - sq.data()) : sq.size();
+					if (len >= p.min_contig_len) {
+						lens.push_back(len);
+					}
+					sq.clear();
+				}
+				if (scan.io_error()) {
+					// (a partition computed from half a draft would differ between the shards)
+					fprintf(stderr, PROGRAM ": error: `%s': %s\n", draft.c_str(), scan.io_error_text().c_str());
+					fatal();
+				}
 			}
-			// (the -e line of the parameter echo; the reference's prefix has no -e part)
-			bfrep = save_reject_bf.empty() ? "reads_k" + std::to_string(rr.k) + "_reject.bf" : save_reject_bf;
+			std::vector<uint32_t> order(lens.size());
+			for (size_t i = 0; i < order.size(); i++) {
+				order[i] = (uint32_t)i;
+			}
+			std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lens[a] > lens[b]; });
+			std::vector<uint64_t> load(shard_n, 0);
+			mine.assign(lens.size(), 0);
+			for (uint32_t i : order) {
+				unsigned best = 0;
+				for (unsigned r = 1; r < shard_n; r++) {
+					if (load[r] < load[best]) {
+						best = r;
+					}
+				}
+				load[best] += lens[i];
+				mine[i] = best == shard_i;
+			}
 		}
-		// (the _r part of the default prefix: the name ntedit-make-reads-bf would have written it under)
-		bf = save_bf.empty() ? "reads_k" + std::to_string(rr.k) + ".bf" : save_bf;
-	} else {
-		printf("---------- loading Bloom filter from file           : %s\n", ctime(&rawtime));
-		if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_PRIMARY, bf.c_str()) != 0) {
-			fprintf(stderr, PROGRAM ": error: Bloom filter file supplied (-r) is incorrect. (%s)\n", ntedit_hip_last_error(ctx));
+		// (the streaming reader and its inflate thread only when the mapped reader does not serve the run)
+		std::unique_ptr<nte_host::FastaReader> reader_p;
+		if (!fmap.ok()) {
+			reader_p.reset(new nte_host::FastaReader(draft.c_str()));
+		}
+		if (reader_p && !reader_p->ok()) {
+			fprintf(stderr, PROGRAM ": error: `%s': cannot open\n", draft.c_str());
 			fatal();
 		}
-	}
-	uint32_t k = 0, h = 0;
-	uint64_t nbytes = 0;
-	int counting = 0;
-	ntedit_hip_filter_info(ctx, NTEDIT_FILTER_PRIMARY, &k, &h, &nbytes, &counting);
-	printf("BLOOM::\tcounting: %s\tsize: %llu\tnumber hash functions: %u\tkmer size: %u\n", counting ? "YES" : "NO",
-	       (unsigned long long)nbytes, h, k);
-	if (!counting && p.min_threshold != 1) {
-		// ntedit.cpp:2453-2458
-		fprintf(stderr, PROGRAM ": warning: Bloom filter is not counting, min k-mer presence threshold will be set to 1.\n");
-		p.min_threshold = 1;
-	}
-	time(&rawtime);
-	printf("\n---------- verifying parameters                     : %s", ctime(&rawtime));
-	char warn[1024];
-	ntedit_hip_params_clamp(&p, warn, sizeof warn);
-	if (warn[0]) {
-		fputs(warn, stderr);
-	}
-	if (prefix.empty()) {
-		// ntedit.cpp:2496-2502
-		std::ostringstream o;
-		o << base_name(draft) << "_k" << k << "_z" << p.min_contig_len << "_r" << base_name(bf) << "_i"
-		  << p.max_insertions << "_d" << p.max_deletions << "_m" << p.mode;
-		prefix = o.str();
-	}
-	printf("\nrunning : " PROGRAM " (MI355X HIP hot path)\n -f %s\n -k %u\n -z %u\n -b %s\n -r %s\n -e %s\n -i %u\n -d %u",
-	       base_name(draft).c_str(), k, p.min_contig_len, prefix.c_str(), base_name(bf).c_str(),
-	       base_name(bfrep).c_str(), p.max_insertions, p.max_deletions);
-	if (p.use_ratio) {
-		printf("\n -X %g\n -Y %g", p.missing_ratio, p.edit_ratio);
-	} else {
-		printf("\n -x %g\n -y %g", p.missing_threshold, p.edit_threshold);
-	}
-	printf("\n -j %u\n -m %d\n -s %d\n -l %s\n -a %d\n -t %u\n -v %d\n\n", p.jump, p.mode, p.snv, base_name(vcf).c_str(),
-	       p.mask, nthreads, verbose);
-	if (counting) {
-		printf(" -p %u\n -q %u\n\n", p.min_threshold, p.max_threshold); // ntedit.cpp:2519-2522
-	}
-
-	if (!bfrep.empty()) {
-		time(&rawtime);
-		if (rr.reject_cmin) {
-			printf("---------- secondary Bloom filter built from reads   : %s\n", ctime(&rawtime));
-		} else {
-			printf("---------- loading secondary Bloom filter from file : %s\n", ctime(&rawtime));
-			if (ntedit_hip_load_filter_file(ctx, NTEDIT_FILTER_SECONDARY, bfrep.c_str()) != 0) {
-				fprintf(stderr, PROGRAM ": error: secondary Bloom filter file supplied (-e) is incorrect.\n");
+		FILE* index_f = nullptr;
+		if (shard_n > 1) {
+			index_f = fopen((prefix + ".index.tsv").c_str(), "wb");
+			if (!index_f) {
+				fprintf(stderr, PROGRAM ": error: cannot write `%s.index.tsv'\n", prefix.c_str());
 				fatal();
 			}
+			fprintf(index_f, "#shard %u/%u\tordinal\tfa_bytes\ttsv_bytes\tvcf_bytes\n", shard_i, shard_n);
 		}
-		uint32_t k2 = 0;
-		ntedit_hip_filter_info(ctx, NTEDIT_FILTER_SECONDARY, &k2, nullptr, nullptr, nullptr);
-		if (k2 != k) {
-			fprintf(stderr, PROGRAM ": error: secondary Bloom filter k size (%u) is different than main Bloom filter k size (%u)\n", k2, k);
-			fatal();
+		if (threads_given) {
+			ntedit_hip_set_host_threads(nthreads); // -t: contigs rendered concurrently
 		}
-	}
-	if (ntedit_hip_set_params(ctx, &p) != 0) {
-		fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
-		fatal();
-	}
-	// start-up, like the filter load: the context's buffers for the largest batch + one internal warm-up batch, so that
-	// the first polish_batch call costs what the later ones do (ntedit_hip_reserve)
-	if (ntedit_hip_reserve(ctx, pin_bytes, 1u << 16, 0, no_pack ? NTEDIT_HIP_BASES_HOST : NTEDIT_HIP_BASES_PACKED) != 0) {
-		// (optional: the buffers then grow on demand, inside the first calls)
-		fprintf(stderr, PROGRAM ": warning: buffers could not be sized ahead (%s); they grow on demand\n", ntedit_hip_last_error(ctx));
-	}
-	pin_thread.join();
+		unsigned long long n_contigs = 0, total_bases = 0;
+		double ms_gpu = 0, ms_screen = 0, ms_machine = 0, s_call = 0, s_write = 0, s_read = 0;
+		unsigned n_batches_binned = 0, n_batches_direct = 0, n_chunks_direct = 0;
+		unsigned long long n_ovf_records = 0;
+		ntedit_hip_stats tot;
+		memset(&tot, 0, sizeof tot);
 
-	time(&rawtime);
-	printf("---------- reading/processing input sequence        : %s", ctime(&rawtime));
-	const auto t0 = std::chrono::steady_clock::now(); // (--report: this stamp -> "process complete")
-	const std::string fa_path = prefix + "_edited.fa", tsv_path = prefix + "_changes.tsv",
-	                  vcf_path = prefix + "_variants.vcf";
-	{
-		FILE* f = fopen(fa_path.c_str(), "wb");
-		if (!f) {
-			fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", fa_path.c_str());
-			fatal();
+		// Batch sizes.  End to end the writer is the slowest stage (a write() per output byte into the page cache), so the
+		// run takes the writer's time plus what passes before its first byte: unless the user fixes the size, the first
+		// batches are small (128 Mbases, doubling: the writer starts after 30 ms instead of 120) and grow to 1 Gbase -- every
+		// batch costs the writer a start-up of its own (round 5: 3 Gbp in 7 batches of <= 512 Mbases 0.52 s of writer time,
+		// in 3 of 1 Gbase 0.43 s).
+		unsigned long long budget = batch_bases;
+		if (!batch_given) {
+			batch_bases = 1ull << 30;
+			budget = 1ull << 27;
 		}
-		fclose(f);
-	}
-	if (ntedit_hip_write_tsv_header(tsv_path.c_str(), k, p.jump, counting) != 0) {
-		fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", tsv_path.c_str());
-		fatal();
-	}
-	if (ntedit_hip_write_vcf_header(vcf_path.c_str(), draft.c_str()) != 0) { // ntedit.cpp:2192-2211
-		fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", vcf_path.c_str());
-		fatal();
-	}
-	ntedit_hip_annot* annot = nullptr;
-	if (!vcf.empty()) {
-		// -l: annotated variants (e.g. clinvar.vcf[.gz]), ntedit.cpp:2524-2562
-		die_unreadable(vcf);
-		if (ntedit_hip_annot_load(vcf.c_str(), &annot) != 0) {
-			fprintf(stderr, "Unable to open file\n");
+		// Three stages, one batch each at a time: this thread's reader helper parses the draft
+		// into batch N+1 while the GPU polishes batch N and the writer renders batch N-1.
+		// Output order = input order (the reference at -t 1).
+		Channel free_q, gpu_q, write_q;
+		for (Work& w : pool) {
+			free_q.push(&w);
 		}
-	}
-
-	// Plain multi-FASTA files are taken apart by several threads from a mapping of the file (fasta_map.h); anything
-	// else (gzip, FASTQ, CR line ends, ...) goes through the streaming reader.  --no-map forces the latter.
-	unsigned ingest_threads = threads_given ? nthreads : std::thread::hardware_concurrency();
-	if (ingest_threads > 16) {
-		ingest_threads = 16;
-	}
-	if (ingest_threads < 1) {
-		ingest_threads = 1;
-	}
-	// (BGZF members are inflated before that: compute-bound, so on more threads than the memory-bound parse)
-	unsigned inflate_threads = threads_given ? nthreads : std::thread::hardware_concurrency();
-	if (inflate_threads > 64) {
-		inflate_threads = 64;
-	}
-	const auto tm0 = std::chrono::steady_clock::now();
-	nte_host::FastaMap fmap(no_map ? "" : draft.c_str(), ingest_threads, inflate_threads);
-	const double s_index = std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
-	const double s_before_index = std::chrono::duration<double>(tm0 - t0).count();
-
-	// --shard I/N: the contigs >= -z are split by bases, greedy longest-first (the partition of
-	// ntedit_amd.dist.shard_contigs): a first pass over the draft collects the lengths
-	std::vector<uint8_t> mine; // by ordinal
-	if (shard_n > 1) {
-		std::vector<uint64_t> lens;
-		if (fmap.ok()) {
-			fmap.measure(0, fmap.records());
-			for (size_t i = 0; i < fmap.records(); i++) {
-				if (fmap.length(i) >= p.min_contig_len) {
-					lens.push_back(fmap.length(i));
+		for (Work& w : pool) {
+			// (address space only: pages are touched as the batch fills)
+			w.b.blob.reserve((size_t)(batch_bases < (1ull << 32) ? batch_bases : (1ull << 32)) + (1 << 20));
+			// first touch of a fresh batch buffer is a page fault per 4 KiB: ask for huge pages
+			const uintptr_t lo = ((uintptr_t)w.b.blob.data() + (2u << 20) - 1) & ~(uintptr_t)((2u << 20) - 1);
+			const uintptr_t hi = ((uintptr_t)w.b.blob.data() + w.b.blob.capacity()) & ~(uintptr_t)((2u << 20) - 1);
+			if (hi > lo) {
+				(void)madvise((void*)lo, hi - lo, MADV_HUGEPAGE);
+			}
+		}
+		std::thread reader_thread([&]() {
+			std::string hdr;
+			unsigned long long idx = 0;
+			Work* w = free_q.pop();
+			auto tr0 = std::chrono::steady_clock::now();
+			auto hand_over = [&](Work* next) {
+				if (!no_pack && w->b.size()) {
+					// (--pack.  Measured on the 3 Gbp draft: the GPU stage gains ~10 ms per 3 GB, packing costs the reader stage
+					// 0.5 s on 4 threads -- 1 GB/s per thread, a table look-up per byte -- and puts it on the critical path:
+					// 0.94 s end to end against 0.67 s.  Off by default; the packed form pays where the producer has
+					// cycles to spare or emits it directly.)
+					const uint64_t need = ntedit_hip_packed_size(w->b.size());
+					if (w->b.packed.size() < need) {
+						w->b.packed.resize(need + need / 8);
+					}
+					w->b.is_packed = ntedit_hip_pack_bases(w->b.data(), w->b.size(), w->b.packed.data(), nthreads) == 0;
 				}
-			}
-		} else {
-			nte_host::FastaReader scan(draft.c_str());
-			if (!scan.ok()) {
-				fprintf(stderr, PROGRAM ": error: `%s': cannot open\n", draft.c_str());
-				fatal();
-			}
-			std::string h, sq;
-			while (scan.next(h, sq)) {
-				const void* z = memchr(sq.data(), 0, sq.size());
-				const size_t len = z ? (size_t)((const char*)z - sq.data()) : sq.size();
-				if (len >= p.min_contig_len) {
-					lens.push_back(len);
-				}
-				sq.clear();
-			}
-			if (scan.io_error()) {
-				// (a partition computed from half a draft would differ between the shards)
-				fprintf(stderr, PROGRAM ": error: `%s': %s\n", draft.c_str(), scan.io_error_text().c_str());
-				fatal();
-			}
-		}
-		std::vector<uint32_t> order(lens.size());
-		for (size_t i = 0; i < order.size(); i++) {
-			order[i] = (uint32_t)i;
-		}
-		std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lens[a] > lens[b]; });
-		std::vector<uint64_t> load(shard_n, 0);
-		mine.assign(lens.size(), 0);
-		for (uint32_t i : order) {
-			unsigned best = 0;
-			for (unsigned r = 1; r < shard_n; r++) {
-				if (load[r] < load[best]) {
-					best = r;
-				}
-			}
-			load[best] += lens[i];
-			mine[i] = best == shard_i;
-		}
-	}
-	// (the streaming reader and its inflate thread only when the mapped reader does not serve the run)
-	std::unique_ptr<nte_host::FastaReader> reader_p;
-	if (!fmap.ok()) {
-		reader_p.reset(new nte_host::FastaReader(draft.c_str()));
-	}
-	if (reader_p && !reader_p->ok()) {
-		fprintf(stderr, PROGRAM ": error: `%s': cannot open\n", draft.c_str());
-		fatal();
-	}
-	FILE* index_f = nullptr;
-	if (shard_n > 1) {
-		index_f = fopen((prefix + ".index.tsv").c_str(), "wb");
-		if (!index_f) {
-			fprintf(stderr, PROGRAM ": error: cannot write `%s.index.tsv'\n", prefix.c_str());
-			fatal();
-		}
-		fprintf(index_f, "#shard %u/%u\tordinal\tfa_bytes\ttsv_bytes\tvcf_bytes\n", shard_i, shard_n);
-	}
-	if (threads_given) {
-		ntedit_hip_set_host_threads(nthreads); // -t: contigs rendered concurrently
-	}
-	unsigned long long n_contigs = 0, total_bases = 0;
-	double ms_gpu = 0, ms_screen = 0, ms_machine = 0, s_call = 0, s_write = 0, s_read = 0;
-	unsigned n_batches_binned = 0, n_batches_direct = 0, n_chunks_direct = 0;
-	unsigned long long n_ovf_records = 0;
-	ntedit_hip_stats tot;
-	memset(&tot, 0, sizeof tot);
-
-	// Batch sizes.  End to end the writer is the slowest stage (a write() per output byte into the page cache), so the
-	// run takes the writer's time plus what passes before its first byte: unless the user fixes the size, the first
-	// batches are small (128 Mbases, doubling: the writer starts after 30 ms instead of 120) and grow to 1 Gbase -- every
-	// batch costs the writer a start-up of its own (round 5: 3 Gbp in 7 batches of <= 512 Mbases 0.52 s of writer time,
-	// in 3 of 1 Gbase 0.43 s).
-	unsigned long long budget = batch_bases;
-	if (!batch_given) {
-		batch_bases = 1ull << 30;
-		budget = 1ull << 27;
-	}
-	// Three stages, one batch each at a time: this thread's reader helper parses the draft
-	// into batch N+1 while the GPU polishes batch N and the writer renders batch N-1.
-	// Output order = input order (the reference at -t 1).
-	Channel free_q, gpu_q, write_q;
-	for (Work& w : pool) {
-		free_q.push(&w);
-	}
-	for (Work& w : pool) {
-		// (address space only: pages are touched as the batch fills)
-		w.b.blob.reserve((size_t)(batch_bases < (1ull << 32) ? batch_bases : (1ull << 32)) + (1 << 20));
-		// first touch of a fresh batch buffer is a page fault per 4 KiB: ask for huge pages
-		const uintptr_t lo = ((uintptr_t)w.b.blob.data() + (2u << 20) - 1) & ~(uintptr_t)((2u << 20) - 1);
-		const uintptr_t hi = ((uintptr_t)w.b.blob.data() + w.b.blob.capacity()) & ~(uintptr_t)((2u << 20) - 1);
-		if (hi > lo) {
-			(void)madvise((void*)lo, hi - lo, MADV_HUGEPAGE);
-		}
-	}
-	std::thread reader_thread([&]() {
-		std::string hdr;
-		unsigned long long idx = 0;
-		Work* w = free_q.pop();
-		auto tr0 = std::chrono::steady_clock::now();
-		auto hand_over = [&](Work* next) {
-			if (!no_pack && w->b.size()) {
-				// (--pack.  Measured on the 3 Gbp draft: the GPU stage gains ~10 ms per 3 GB, packing costs the reader stage
-				// 0.5 s on 4 threads -- 1 GB/s per thread, a table look-up per byte -- and puts it on the critical path:
-				// 0.94 s end to end against 0.67 s.  Off by default; the packed form pays where the producer has
-				// cycles to spare or emits it directly.)
-				const uint64_t need = ntedit_hip_packed_size(w->b.size());
-				if (w->b.packed.size() < need) {
-					w->b.packed.resize(need + need / 8);
-				}
-				w->b.is_packed = ntedit_hip_pack_bases(w->b.data(), w->b.size(), w->b.packed.data(), nthreads) == 0;
-			}
-			s_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
-			gpu_q.push(w);
-			w = next;
-			budget = budget * 2 < batch_bases ? budget * 2 : batch_bases;
-			tr0 = std::chrono::steady_clock::now();
-		};
-		if (fmap.ok()) {
-			// ---- mapped reader: pick the records of a batch, measure / copy them concurrently
-			const size_t N = fmap.records();
-			size_t i = 0;
-			std::vector<size_t> pick;
-			std::vector<char*> dst;
-			const size_t GROUP = 1024;
-			size_t measured = 0;
-			while (i < N) {
-				Batch& b = w->b;
-				pick.clear();
-				size_t total = 0;
+				s_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
+				gpu_q.push(w);
+				w = next;
+				budget = budget * 2 < batch_bases ? budget * 2 : batch_bases;
+				tr0 = std::chrono::steady_clock::now();
+			};
+			if (fmap.ok()) {
+				// ---- mapped reader: pick the records of a batch, measure / copy them concurrently
+				const size_t N = fmap.records();
+				size_t i = 0;
+				std::vector<size_t> pick;
+				std::vector<char*> dst;
+				const size_t GROUP = 1024;
+				size_t measured = 0;
 				while (i < N) {
-					if (i >= measured) {
-						const size_t cnt = N - measured < GROUP ? N - measured : GROUP;
-						fmap.measure(measured, cnt);
-						measured += cnt;
+					Batch& b = w->b;
+					pick.clear();
+					size_t total = 0;
+					while (i < N) {
+						if (i >= measured) {
+							const size_t cnt = N - measured < GROUP ? N - measured : GROUP;
+							fmap.measure(measured, cnt);
+							measured += cnt;
+						}
+						const uint64_t len = fmap.length(i);
+						bool keep = false;
+						if (len >= p.min_contig_len) { // ntedit.cpp:2242
+							keep = shard_n == 1 || (idx < mine.size() && mine[idx]);
+						}
+						if (keep) {
+							if (len > 0xFFFFFFF0ull) {
+								fprintf(stderr, PROGRAM ": error: contig longer than 2^32 bases\n");
+								fflush(nullptr);
+								_exit(EXIT_FAILURE);
+							}
+							if (!pick.empty() && total + len + 1 > budget) {
+								break; // the batch is full: this contig opens the next one
+							}
+							b.offs.push_back(total);
+							b.lens.push_back((uint32_t)len);
+							b.names.push_back(fmap.header(i));
+							b.ordinals.push_back(idx);
+							pick.push_back(i);
+							total += len + 1;
+							total_bases += len;
+						}
+						if (len >= p.min_contig_len) {
+							idx++;
+						}
+						n_contigs++;
+						if (n_contigs % 1000000 == 0) {
+							printf("Processed %llu\n", n_contigs);
+						}
+						i++;
 					}
-					const uint64_t len = fmap.length(i);
-					bool keep = false;
-					if (len >= p.min_contig_len) { // ntedit.cpp:2242
-						keep = shard_n == 1 || (idx < mine.size() && mine[idx]);
-					}
-					if (keep) {
-						if (len > 0xFFFFFFF0ull) {
-							fprintf(stderr, PROGRAM ": error: contig longer than 2^32 bases\n");
+					if (!pick.empty()) {
+						if (!b.reserve_raw(total)) {
+							fprintf(stderr, PROGRAM ": error: out of memory for a batch of %zu bytes\n", total);
 							fflush(nullptr);
 							_exit(EXIT_FAILURE);
 						}
-						if (!pick.empty() && total + len + 1 > budget) {
-							break; // the batch is full: this contig opens the next one
+						dst.resize(pick.size());
+						for (size_t q = 0; q < pick.size(); q++) {
+							dst[q] = b.raw + b.offs[q];
+							b.raw[b.offs[q] + b.lens[q]] = '\n';
 						}
-						b.offs.push_back(total);
-						b.lens.push_back((uint32_t)len);
-						b.names.push_back(fmap.header(i));
-						b.ordinals.push_back(idx);
-						pick.push_back(i);
-						total += len + 1;
-						total_bases += len;
+						fmap.copy(pick.data(), dst.data(), pick.size());
+						b.raw_n = total;
 					}
-					if (len >= p.min_contig_len) {
-						idx++;
+					if (i < N) {
+						s_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
+						Work* nx = free_q.pop();
+						tr0 = std::chrono::steady_clock::now();
+						hand_over(nx);
 					}
-					n_contigs++;
-					if (n_contigs % 1000000 == 0) {
-						printf("Processed %llu\n", n_contigs);
-					}
-					i++;
 				}
-				if (!pick.empty()) {
-					if (!b.reserve_raw(total)) {
-						fprintf(stderr, PROGRAM ": error: out of memory for a batch of %zu bytes\n", total);
+				hand_over(nullptr);
+				gpu_q.push(nullptr);
+				return;
+			}
+			for (;;) {
+				Batch& b = w->b;
+				const size_t before = b.blob.size();
+				if (!reader_p->next(hdr, b.blob)) {
+					break;
+				}
+				n_contigs++;
+				// strings holding an embedded NUL end there in the reference (contigSeq = seq->seq.s)
+				const void* z = memchr(b.blob.data() + before, 0, b.blob.size() - before);
+				if (z) {
+					b.blob.resize((size_t)((const char*)z - b.blob.data()));
+				}
+				const size_t len = b.blob.size() - before;
+				bool keep = false;
+				if (len >= p.min_contig_len) { // ntedit.cpp:2242
+					keep = shard_n == 1 || (idx < mine.size() && mine[idx]);
+					idx++;
+				}
+				if (!keep) {
+					b.blob.resize(before);
+				} else {
+					if (len > 0xFFFFFFF0ull) {
+						fprintf(stderr, PROGRAM ": error: contig longer than 2^32 bases\n");
 						fflush(nullptr);
 						_exit(EXIT_FAILURE);
 					}
-					dst.resize(pick.size());
-					for (size_t q = 0; q < pick.size(); q++) {
-						dst[q] = b.raw + b.offs[q];
-						b.raw[b.offs[q] + b.lens[q]] = '\n';
+					if (!b.names.empty() && b.blob.size() + 1 > budget) {
+						// the batch is full: this contig opens the next one
+						s_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
+						Work* nx = free_q.pop();
+						tr0 = std::chrono::steady_clock::now();
+						nx->b.blob.assign(b.blob, before, std::string::npos);
+						b.blob.resize(before);
+						hand_over(nx);
+						Batch& nb = w->b;
+						nb.offs.push_back(0);
+						nb.lens.push_back((uint32_t)len);
+						nb.names.push_back(hdr);
+						nb.ordinals.push_back(idx - 1);
+						nb.blob.push_back('\n');
+					} else {
+						b.offs.push_back(before);
+						b.lens.push_back((uint32_t)len);
+						b.names.push_back(hdr);
+						b.ordinals.push_back(idx - 1);
+						b.blob.push_back('\n');
 					}
-					fmap.copy(pick.data(), dst.data(), pick.size());
-					b.raw_n = total;
+					total_bases += len;
 				}
-				if (i < N) {
-					s_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
-					Work* nx = free_q.pop();
-					tr0 = std::chrono::steady_clock::now();
-					hand_over(nx);
+				if (n_contigs % 1000000 == 0) {
+					printf("Processed %llu\n", n_contigs);
 				}
 			}
-			hand_over(nullptr);
+			hand_over(nullptr); // (possibly empty) last batch
 			gpu_q.push(nullptr);
-			return;
-		}
-		for (;;) {
-			Batch& b = w->b;
-			const size_t before = b.blob.size();
-			if (!reader_p->next(hdr, b.blob)) {
-				break;
-			}
-			n_contigs++;
-			// strings holding an embedded NUL end there in the reference (contigSeq = seq->seq.s)
-			const void* z = memchr(b.blob.data() + before, 0, b.blob.size() - before);
-			if (z) {
-				b.blob.resize((size_t)((const char*)z - b.blob.data()));
-			}
-			const size_t len = b.blob.size() - before;
-			bool keep = false;
-			if (len >= p.min_contig_len) { // ntedit.cpp:2242
-				keep = shard_n == 1 || (idx < mine.size() && mine[idx]);
-				idx++;
-			}
-			if (!keep) {
-				b.blob.resize(before);
-			} else {
-				if (len > 0xFFFFFFF0ull) {
-					fprintf(stderr, PROGRAM ": error: contig longer than 2^32 bases\n");
+		});
+		std::thread writer_thread([&]() {
+			while (Work* w = write_q.pop()) {
+				Batch& b = w->b;
+				auto tw0 = std::chrono::steady_clock::now();
+				std::vector<const char*> names(b.names.size());
+				for (size_t i = 0; i < b.names.size(); i++) {
+					names[i] = b.names[i].c_str();
+				}
+				ntedit_hip_write_options wo;
+				memset(&wo, 0, sizeof wo);
+				wo.fa_path = fa_path.c_str();
+				wo.tsv_path = tsv_path.c_str();
+				wo.vcf_path = vcf_path.c_str();
+				wo.append = 1;
+				wo.annot = annot;
+				std::vector<uint64_t> sizes;
+				if (index_f) {
+					sizes.assign(names.size() * 3 + 3, 0);
+					wo.out_sizes = sizes.data();
+				}
+				int rc = ntedit_hip_write_outputs_ex(w->res, b.data(), b.offs.data(), b.lens.data(), names.data(),
+				                                     (uint32_t)names.size(), &wo);
+				if (rc != 0) {
+					fprintf(stderr, PROGRAM ": error: cannot write outputs\n");
 					fflush(nullptr);
 					_exit(EXIT_FAILURE);
 				}
-				if (!b.names.empty() && b.blob.size() + 1 > budget) {
-					// the batch is full: this contig opens the next one
-					s_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
-					Work* nx = free_q.pop();
-					tr0 = std::chrono::steady_clock::now();
-					nx->b.blob.assign(b.blob, before, std::string::npos);
-					b.blob.resize(before);
-					hand_over(nx);
-					Batch& nb = w->b;
-					nb.offs.push_back(0);
-					nb.lens.push_back((uint32_t)len);
-					nb.names.push_back(hdr);
-					nb.ordinals.push_back(idx - 1);
-					nb.blob.push_back('\n');
-				} else {
-					b.offs.push_back(before);
-					b.lens.push_back((uint32_t)len);
-					b.names.push_back(hdr);
-					b.ordinals.push_back(idx - 1);
-					b.blob.push_back('\n');
+				if (index_f) {
+					for (size_t i = 0; i < names.size(); i++) {
+						fprintf(index_f, "%llu\t%llu\t%llu\t%llu\n", (unsigned long long)b.ordinals[i], (unsigned long long)sizes[3 * i],
+						        (unsigned long long)sizes[3 * i + 1], (unsigned long long)sizes[3 * i + 2]);
+					}
 				}
-				total_bases += len;
+				ntedit_hip_stats st;
+				ntedit_hip_result_stats(w->res, &st);
+				ms_gpu += st.ms_total;
+				ms_screen += st.ms_screen;
+				// (which screening kernels ran: batches on the partitioned pipeline / on the direct kernel, record chunks the direct
+				// kernel had to screen again, overflow-list entries)
+				n_batches_binned += st.screen_binned ? 1 : 0;
+				n_batches_direct += st.screen_binned ? 0 : 1;
+				n_chunks_direct += st.screen_chunks_direct;
+				n_ovf_records += st.screen_overflow_records;
+				ms_machine += st.ms_machine;
+				tot.events += st.events;
+				tot.events_applied += st.events_applied;
+				tot.absent_kmers += st.absent_kmers;
+				tot.substitutions += st.substitutions;
+				tot.insertions += st.insertions;
+				tot.deletions += st.deletions;
+				ntedit_hip_result_free(w->res);
+				w->res = nullptr;
+				b.clear();
+				s_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
+				free_q.push(w);
 			}
-			if (n_contigs % 1000000 == 0) {
-				printf("Processed %llu\n", n_contigs);
-			}
-		}
-		hand_over(nullptr); // (possibly empty) last batch
-		gpu_q.push(nullptr);
-	});
-	std::thread writer_thread([&]() {
-		while (Work* w = write_q.pop()) {
+		});
+		while (Work* w = gpu_q.pop()) {
 			Batch& b = w->b;
-			auto tw0 = std::chrono::steady_clock::now();
-			std::vector<const char*> names(b.names.size());
-			for (size_t i = 0; i < b.names.size(); i++) {
-				names[i] = b.names[i].c_str();
+			if (b.names.empty()) {
+				b.clear();
+				free_q.push(w);
+				continue;
 			}
-			ntedit_hip_write_options wo;
-			memset(&wo, 0, sizeof wo);
-			wo.fa_path = fa_path.c_str();
-			wo.tsv_path = tsv_path.c_str();
-			wo.vcf_path = vcf_path.c_str();
-			wo.append = 1;
-			wo.annot = annot;
-			std::vector<uint64_t> sizes;
-			if (index_f) {
-				sizes.assign(names.size() * 3 + 3, 0);
-				wo.out_sizes = sizes.data();
-			}
-			int rc = ntedit_hip_write_outputs_ex(w->res, b.data(), b.offs.data(), b.lens.data(), names.data(),
-			                                     (uint32_t)names.size(), &wo);
+			auto tc0 = std::chrono::steady_clock::now();
+			int rc = ntedit_hip_polish_batch(ctx, b.is_packed ? b.packed.data() : b.data(), b.size(), b.offs.data(), b.lens.data(),
+			                                 (uint32_t)b.names.size(), b.is_packed ? NTEDIT_HIP_BASES_PACKED : NTEDIT_HIP_BASES_HOST, &w->res);
 			if (rc != 0) {
-				fprintf(stderr, PROGRAM ": error: cannot write outputs\n");
+				fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
 				fflush(nullptr);
 				_exit(EXIT_FAILURE);
 			}
-			if (index_f) {
-				for (size_t i = 0; i < names.size(); i++) {
-					fprintf(index_f, "%llu\t%llu\t%llu\t%llu\n", (unsigned long long)b.ordinals[i], (unsigned long long)sizes[3 * i],
-					        (unsigned long long)sizes[3 * i + 1], (unsigned long long)sizes[3 * i + 2]);
-				}
-			}
-			ntedit_hip_stats st;
-			ntedit_hip_result_stats(w->res, &st);
-			ms_gpu += st.ms_total;
-			ms_screen += st.ms_screen;
-			// (which screening kernels ran: batches on the partitioned pipeline / on the direct kernel, record chunks the direct
-			// kernel had to screen again, overflow-list entries)
-			n_batches_binned += st.screen_binned ? 1 : 0;
-			n_batches_direct += st.screen_binned ? 0 : 1;
-			n_chunks_direct += st.screen_chunks_direct;
-			n_ovf_records += st.screen_overflow_records;
-			ms_machine += st.ms_machine;
-			tot.events += st.events;
-			tot.events_applied += st.events_applied;
-			tot.absent_kmers += st.absent_kmers;
-			tot.substitutions += st.substitutions;
-			tot.insertions += st.insertions;
-			tot.deletions += st.deletions;
-			ntedit_hip_result_free(w->res);
-			w->res = nullptr;
-			b.clear();
-			s_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
-			free_q.push(w);
+			s_call += std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count();
+			write_q.push(w);
 		}
-	});
-	while (Work* w = gpu_q.pop()) {
-		Batch& b = w->b;
-		if (b.names.empty()) {
-			b.clear();
-			free_q.push(w);
-			continue;
+		write_q.push(nullptr);
+		reader_thread.join();
+		writer_thread.join();
+		if (index_f && fclose(index_f) != 0) {
+			fprintf(stderr, PROGRAM ": error: cannot write `%s.index.tsv'\n", prefix.c_str());
+			exit(EXIT_FAILURE);
 		}
-		auto tc0 = std::chrono::steady_clock::now();
-		int rc = ntedit_hip_polish_batch(ctx, b.is_packed ? b.packed.data() : b.data(), b.size(), b.offs.data(), b.lens.data(),
-		                                 (uint32_t)b.names.size(), b.is_packed ? NTEDIT_HIP_BASES_PACKED : NTEDIT_HIP_BASES_HOST, &w->res);
-		if (rc != 0) {
-			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
+		if (reader_p && reader_p->io_error()) {
+			// a corrupt / truncated input must not pass for a (shorter) genome
+			fprintf(stderr, PROGRAM ": error: `%s': %s -- the outputs are incomplete\n", draft.c_str(), reader_p->io_error_text().c_str());
 			fflush(nullptr);
 			_exit(EXIT_FAILURE);
 		}
-		s_call += std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count();
-		write_q.push(w);
-	}
-	write_q.push(nullptr);
-	reader_thread.join();
-	writer_thread.join();
-	if (index_f && fclose(index_f) != 0) {
-		fprintf(stderr, PROGRAM ": error: cannot write `%s.index.tsv'\n", prefix.c_str());
-		exit(EXIT_FAILURE);
-	}
-	if (reader_p && reader_p->io_error()) {
-		// a corrupt / truncated input must not pass for a (shorter) genome
-		fprintf(stderr, PROGRAM ": error: `%s': %s -- the outputs are incomplete\n", draft.c_str(), reader_p->io_error_text().c_str());
-		fflush(nullptr);
-		_exit(EXIT_FAILURE);
-	}
-	auto t1 = std::chrono::steady_clock::now();
-	time(&rawtime);
-	printf("---------- process complete                         : %s", ctime(&rawtime));
-	if (report) {
-		double s = std::chrono::duration<double>(t1 - t0).count();
-		printf("{\"bases\": %llu, \"seconds\": %.6f, \"open_outputs_s\": %.3f, \"index_s\": %.3f, \"read_s\": %.3f, \"polish_call_s\": %.3f, \"write_s\": %.3f, \"gpu_ms\": %.3f, \"screen_ms\": %.3f, \"machine_ms\": %.3f, "
-		       "\"screening\": {\"batches_partitioned\": %u, \"batches_direct_kernel\": %u, \"record_chunks_rescreened_direct\": %u, \"overflow_records\": %llu}, \"events\": %llu, "
-		       "\"events_applied\": %llu, \"absent_kmers\": %llu, \"substitutions\": %llu, \"insertions\": %llu, "
-		       "\"deletions\": %llu}\n",
-		       total_bases, s, s_before_index, s_index, s_read, s_call, s_write, ms_gpu, ms_screen, ms_machine, n_batches_binned, n_batches_direct, n_chunks_direct, (unsigned long long)n_ovf_records, (unsigned long long)tot.events,
-		       (unsigned long long)tot.events_applied, (unsigned long long)tot.absent_kmers,
-		       (unsigned long long)tot.substitutions, (unsigned long long)tot.insertions,
-		       (unsigned long long)tot.deletions);
+		auto t1 = std::chrono::steady_clock::now();
+		time(&rawtime);
+		printf("---------- process complete                         : %s", ctime(&rawtime));
+		if (report) {
+			double s = std::chrono::duration<double>(t1 - t0).count();
+			printf("{\"bases\": %llu, \"seconds\": %.6f, \"open_outputs_s\": %.3f, \"index_s\": %.3f, \"read_s\": %.3f, \"polish_call_s\": %.3f, \"write_s\": %.3f, \"gpu_ms\": %.3f, \"screen_ms\": %.3f, \"machine_ms\": %.3f, "
+			       "\"screening\": {\"batches_partitioned\": %u, \"batches_direct_kernel\": %u, \"record_chunks_rescreened_direct\": %u, \"overflow_records\": %llu}, \"events\": %llu, "
+			       "\"events_applied\": %llu, \"absent_kmers\": %llu, \"substitutions\": %llu, \"insertions\": %llu, "
+			       "\"deletions\": %llu}\n",
+			       total_bases, s, s_before_index, s_index, s_read, s_call, s_write, ms_gpu, ms_screen, ms_machine, n_batches_binned, n_batches_direct, n_chunks_direct, (unsigned long long)n_ovf_records, (unsigned long long)tot.events,
+			       (unsigned long long)tot.events_applied, (unsigned long long)tot.absent_kmers,
+			       (unsigned long long)tot.substitutions, (unsigned long long)tot.insertions,
+			       (unsigned long long)tot.deletions);
+		}
+		ntedit_hip_annot_free(annot);
+		return prefix + "_edited.fa";
+	};
+	std::string round_draft = draft_given;
+	for (size_t round = 0; round < n_rounds; round++) {
+		// the last round writes under the prefix, an earlier one at Ki under <prefix>_k<Ki>
+		const bool last_round = round + 1 == n_rounds;
+		round_draft = polish_round(round, round_draft, last_round ? prefix_given : prefix_given + "_k" + std::to_string(rounds[round].k));
 	}
 	for (Work& w : pool) {
 		w.b.release_raw();
 	}
-	ntedit_hip_annot_free(annot);
 	ntedit_hip_destroy(ctx);
 	return 0;
 }

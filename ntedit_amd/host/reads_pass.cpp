@@ -34,6 +34,7 @@
 namespace nte_reads {
 int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
 uint32_t reject_cutoff(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_reject_cutoff (nte_reads.hip)
+uint32_t min_read(const ntedit_hip_ctx* c, uint32_t k); // ntedit_hip_reads_set_min_read: the shortest record kept, k at most
 // --gpu_parse (nte_reads_parse.hip): the context's setting and counters, its two raw buffers and its copy stream
 int parse_is_on(const ntedit_hip_ctx* c);
 ntedit_hip_reads_parse_stats* parse_info(const ntedit_hip_ctx* c);
@@ -848,6 +849,8 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 	if (ntedit_hip_sketch_info(ctx, &counters, &hash_num, &k) != 0) {
 		return pfail(ctx, NTEDIT_E_ARG, "reads_pass: no sketch (ntedit_hip_sketch_alloc / _set_device)");
 	}
+	// the shortest record the parsers keep: the sketch's k, or below it what ntedit_hip_reads_set_min_read asks for
+	const uint32_t keep = nte_reads::min_read(ctx, k);
 	const auto t0 = std::chrono::steady_clock::now();
 	uint64_t bases = 0;
 	double gpu_ms = 0.0;
@@ -861,7 +864,7 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 	};
 	// the host parser over some ranges (all of them, without --gpu_parse)
 	auto host_pass = [&](const std::vector<Range>& rs, uint64_t* rs_starts, uint64_t* rs_nexts) {
-		BatchFeeder feed(rs, k, (size_t)batch_bytes, rs_starts, rs_nexts);
+		BatchFeeder feed(rs, keep, (size_t)batch_bytes, rs_starts, rs_nexts);
 		for (;;) {
 			Batch* b = feed.take();
 			if (!b) {
@@ -954,7 +957,7 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 							res.clean = 0;
 							res.broken = broken;
 						} else if (rc == 0 && cut) {
-							rc = nte_reads::parse_buffer(ctx, raw, cut, k, &text, &res);
+							rc = nte_reads::parse_buffer(ctx, raw, cut, keep, &text, &res);
 						}
 						if (rc == 0 && res.clean && res.text_len) {
 							rc = run_batch(text, res.text_len, NTEDIT_HIP_BASES_DEVICE);
@@ -1061,7 +1064,7 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 					const auto g0 = std::chrono::steady_clock::now();
 					const char* text = nullptr;
 					ntedit_hip_reads_parse_result res;
-					int rc = nte_reads::parse_copied(ctx, which, cur->len, k, &text, &res);
+					int rc = nte_reads::parse_copied(ctx, which, cur->len, keep, &text, &res);
 					const uint64_t off = cur->off, len = cur->len;
 					feed.give_back(cur); // (its copy is done: the reader may fill it again)
 					if (rc == 0 && res.clean && res.text_len) {
@@ -1196,7 +1199,8 @@ struct BuildLog
 };
 
 // one pass, over the ranges (the files whole) or over the resident store (the store's bases: pass 1's), and its line
-// (the large-run tests read it)
+// (the large-run tests read it).  Pass 1 reads the store only when the build began with one (r->from_store, set by
+// stage_count from the store's state at entry); the later passes whenever the store is ON.
 int
 build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, ntedit_hip_reads_build_result* r, uint64_t* starts,
            uint64_t* nexts)
@@ -1206,13 +1210,23 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 	ntedit_hip_reads_pass_stats& st = r->pass[pass];
 	std::string what;
 	int rc;
-	const bool read_files = pass == NTEDIT_READS_PASS_COUNT || r->store_state != NTEDIT_RESIDENT_ON;
+	const bool from_store = r->from_store != 0;
+	uint64_t store_bases = 0; // of a store the build began with: its bytes, reads and separators (nobody kept its reads' bases)
+	if (from_store) {
+		ntedit_hip_resident_stats ss;
+		if (ntedit_hip_resident_info(ctx, &ss) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
+		store_bases = ss.bases;
+	}
+	const bool read_files = r->store_state != NTEDIT_RESIDENT_ON || (pass == NTEDIT_READS_PASS_COUNT && !from_store);
 	if (!read_files) {
 		const auto t0 = std::chrono::steady_clock::now();
-		rc = pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_resident_histogram(ctx)
+		rc = pass == NTEDIT_READS_PASS_COUNT  ? ntedit_hip_resident_count(ctx)
+		     : pass == NTEDIT_READS_PASS_HIST ? ntedit_hip_resident_histogram(ctx)
 		     : a->reject_cmin               ? ntedit_hip_resident_insert_solid2(ctx, r->cmin, a->reject_cmin)
 		                                    : ntedit_hip_resident_insert_solid(ctx, NTEDIT_FILTER_PRIMARY, r->cmin);
-		st.bases = r->pass[NTEDIT_READS_PASS_COUNT].bases;
+		st.bases = from_store ? store_bases : r->pass[NTEDIT_READS_PASS_COUNT].bases;
 		st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		st.ms_gpu = st.ms_wall;
 		what = std::to_string(r->store_batches) + " batches of the resident store";
@@ -1229,7 +1243,7 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 	snprintf(line, sizeof line, "Pass %s: %llu bases, %.1f ms, %.3f Gbases/s (GPU calls %.1f ms, %.3f Gbases/s)", names[pass],
 	         (unsigned long long)st.bases, st.ms_wall, st.ms_wall > 0 ? st.bases / st.ms_wall / 1e6 : 0.0, st.ms_gpu,
 	         st.ms_gpu > 0 ? st.bases / st.ms_gpu / 1e6 : 0.0);
-	lg.rank_info(lg.ranged() ? line + (", " + what) : line);
+	lg.rank_info(lg.ranged() || from_store ? line + (", " + what) : line);
 	ntedit_hip_reads_parse_stats ps;
 	if (a->device_parse && read_files && ntedit_hip_reads_parse_info(ctx, &ps) == 0) {
 		// the pass's one line about --gpu_parse (the tests read it)
@@ -1273,6 +1287,17 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 	return 0;
 }
 
+// the end of a build: the sketch freed and the store with it, or (keep_store, the build succeeded and its store is ON)
+// the counters alone released and the store kept for the next build
+void
+end_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, const ntedit_hip_reads_build_result* r, int rc)
+{
+	if (rc == 0 && a && r && a->keep_store && r->store_state == NTEDIT_RESIDENT_ON && ntedit_hip_sketch_reset(ctx, 0, 0, 0) == 0) {
+		return;
+	}
+	ntedit_hip_sketch_free(ctx);
+}
+
 bool
 bad_build_args(const ntedit_hip_reads_build_args* a, const ntedit_hip_reads_build_result* r)
 {
@@ -1295,11 +1320,27 @@ ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_a
 	const BuildLog lg{ a };
 	*r = ntedit_hip_reads_build_result();
 	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
-	if (!lg.ranged() && ntedit_hip_sketch_alloc(ctx, a->sketch_counters, a->hash_num, a->k) != 0) {
-		return NTEDIT_E_DEVICE; // (the message is sketch_alloc's)
-	}
-	if (a->use_store && ntedit_hip_resident_begin(ctx, a->store_cap) != 0) {
-		return NTEDIT_E_DEVICE;
+	// a store an earlier build left ON (keep_store): this build's three passes read it, and no file is opened
+	ntedit_hip_resident_stats at_entry;
+	const bool from_store = !lg.ranged() && a->use_store && ntedit_hip_resident_info(ctx, &at_entry) == 0 &&
+	                        at_entry.state == NTEDIT_RESIDENT_ON;
+	if (from_store) {
+		if (ntedit_hip_sketch_reset(ctx, a->sketch_counters, a->hash_num, a->k) != 0) {
+			return NTEDIT_E_DEVICE; // (the message is sketch_reset's)
+		}
+		r->from_store = 1;
+		r->store_state = at_entry.state; // (build_pass routes by both)
+		r->store_batches = at_entry.batches;
+	} else {
+		if (!lg.ranged() && ntedit_hip_sketch_alloc(ctx, a->sketch_counters, a->hash_num, a->k) != 0) {
+			return NTEDIT_E_DEVICE; // (the message is sketch_alloc's)
+		}
+		if (ntedit_hip_reads_set_min_read(ctx, a->min_read) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
+		if (a->use_store && ntedit_hip_resident_begin(ctx, a->store_cap) != 0) {
+			return NTEDIT_E_DEVICE;
+		}
 	}
 	lg.rank_info("Pass 1: counting k-mers");
 	if (build_pass(ctx, a, NTEDIT_READS_PASS_COUNT, r, starts, nexts) != 0) {
@@ -1314,7 +1355,10 @@ ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_a
 		r->store_bytes = ss.bytes;
 		r->store_batches = ss.batches;
 		const std::string later = a->solid || a->hist_path ? "the histogram pass and pass 2" : "pass 2";
-		if (ss.state == NTEDIT_RESIDENT_ON) {
+		if (from_store) {
+			lg.rank_info("Resident store: kept from the build before, " + std::to_string(ss.batches) + " batches, " + std::to_string(ss.bytes) +
+			             " bytes of HBM (3 bits per base); every pass of this build reads it, no file is opened");
+		} else if (ss.state == NTEDIT_RESIDENT_ON) {
 			lg.rank_info("Resident store: " + std::to_string(ss.batches) + " batches, " + std::to_string(ss.bytes) +
 			             " bytes of HBM (3 bits per base); " + later + " read it");
 		} else {
@@ -1443,7 +1487,7 @@ ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_
 	lg.rank_info("Pass 2: inserting k-mers seen at least " + std::to_string(r->cmin) + " times" +
 	             (a->reject_cmin ? ", and into the reject filter those seen at least " + std::to_string(a->reject_cmin) + " times" : ""));
 	const int rc = build_pass(ctx, a, NTEDIT_READS_PASS_SOLID, r, nullptr, nullptr);
-	ntedit_hip_sketch_free(ctx); // (the store with it)
+	end_build(ctx, a, r, rc);
 	return rc;
 }
 
@@ -1475,7 +1519,7 @@ ntedit_hip_reads_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a
 		rc = ntedit_hip_reads_stage_insert(ctx, a, r);
 	}
 	if (ctx) {
-		ntedit_hip_sketch_free(ctx); // (the store with it)
+		end_build(ctx, a, r, rc);
 	}
 	if (r) {
 		r->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

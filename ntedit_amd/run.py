@@ -288,6 +288,9 @@ def parse(argv=None):
     g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
     g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
     args = ap.parse_args(argv)
+    if reads_mode and args.k_ignored is not None and "," in args.k_ignored:
+        raise Refused("-k %s: a list of k (a cascade of polishing rounds) is `ntedit --reads` on one GPU; this driver "
+                      "polishes at one k" % args.k_ignored)
     args.reads_args = reads_args(args) if reads_mode else None
     if not reads_mode:
         for flag, dest in READS_OPTIONS:
