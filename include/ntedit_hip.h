@@ -894,13 +894,30 @@ void ntedit_hip_fasta_free(ntedit_hip_fasta* f);
  *               over; "defer_fail_snv": the same with -s 1, measured slower, 0), "snv_wave" (1: the events of -s 1 go to the
  *               wavefront-per-event launch; measured slower), "defer_run" (hand-over
  *               threshold of the thread-per-event launch), "assess" (the run map: 0 never, 1 always; default: with -s 1
- *               and counting filters), "machine_cfg" (0: the general instantiation of the machine kernels)
+ *               and counting filters), "machine_cfg" (0: the general instantiation of the machine kernels),
+ *               "settle" (k_settle in front of the thread-per-event launch: 0 never, 1 wherever it applies; default: see
+ *               ntedit_hip_settle_info),
+ *               "arena_chunks" (test-only: chunks of the edit-record arena in a batch's first attempt, so that a test
+ *               can make it run out and reach the retry with four times as much)
  * (The measured-and-rejected variants of round 3 -- record chunks partitioned while the previous one is probed, slices
  * probed in parts, uncached records, event rounds in pieces, a batch polished in pipeline chunks as it arrives -- are
  * gone from the library; DESIGN.md 8 keeps their numbers, the history their code.)
  * The library reads two environment variables only: NTEDIT_HIP_DEBUG (diagnostics on stderr) and
  * NTEDIT_HIP_NO_BIND (see ntedit_hip_bind_near_device). */
 int ntedit_hip_set_tuning(ntedit_hip_ctx* ctx, const char* key, uint64_t value);
+
+/* k_settle: in the configurations it restates the machine for (plain primary filter, no secondary one, no -s 1, -m 0
+ * without -a, k <= 64) the plain substitution events of a batch -- one wrong base in clean sequence -- are settled by a
+ * kernel of their own in front of the event machine's thread-per-event launch, which runs the rest.  For the context's
+ * last polish call: the events those launches were handed, the events k_settle settled, and its time (HIP events on
+ * its stream).  All zero where it did not run.  Tuning key "settle". */
+typedef struct ntedit_hip_settle_stats
+{
+	uint64_t events_seen;
+	uint64_t events_settled;
+	float ms;
+} ntedit_hip_settle_stats;
+int ntedit_hip_settle_info(ntedit_hip_ctx* ctx, ntedit_hip_settle_stats* st);
 
 /* The reference's candidate tables -- num_tries, polish_bases_array / snv_bases_array, multi_possible_bases (ntedit.cpp:172,
  * 176-199, 203-348) -- as the device code holds them (one GPU thread runs the machine's own candidate_bases /

@@ -144,6 +144,11 @@ class ReadsParseResult(ctypes.Structure):
                 ("lines", ctypes.c_uint64)]
 
 
+class SettleStats(ctypes.Structure):
+    """ntedit_hip_settle_stats"""
+    _fields_ = [("events_seen", ctypes.c_uint64), ("events_settled", ctypes.c_uint64), ("ms", ctypes.c_float)]
+
+
 class ReadsParseStats(ctypes.Structure):
     """ntedit_hip_reads_parse_stats"""
     _fields_ = [("device_chunks", ctypes.c_uint64), ("fallback_chunks", ctypes.c_uint64),
@@ -252,6 +257,7 @@ EXPORTS = [
     "ntedit_hip_genome_parse_device", "ntedit_hip_genome_parse_model", "ntedit_hip_genome_pass",
     "ntedit_hip_genome_pass_get_info", "ntedit_hip_genome_pass_line",
     "ntedit_hip_sketch_reset", "ntedit_hip_resident_count", "ntedit_hip_reads_set_min_read",
+    "ntedit_hip_settle_info",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -392,6 +398,7 @@ def load():
     lib.ntedit_hip_reads_parse_model.argtypes = [vp, u64, u32, vp, u64, pres]
     lib.ntedit_hip_reads_set_device_parse.argtypes = [vp, ci]
     lib.ntedit_hip_reads_parse_info.argtypes = [vp, ctypes.POINTER(ReadsParseStats)]
+    lib.ntedit_hip_settle_info.argtypes = [vp, ctypes.POINTER(SettleStats)]
     # the reject filter (ntedit -e) from the same pass 2
     lib.ntedit_hip_filter_insert_solid2.argtypes = [vp, vp, u64, ci, u32, u32]
     lib.ntedit_hip_resident_insert_solid2.argtypes = [vp, u32, u32]

@@ -4,6 +4,7 @@
 // to the host renderer.  No CPU compute path exists here: every entry point
 // that needs the GPU fails with NTEDIT_E_DEVICE when there is none.
 #include "nte_kernels.hip"
+#include "nte_settle.h"
 
 #include "../../include/ntedit_hip.h"
 #include "../host/bfio.h"
@@ -90,6 +91,8 @@ struct ntedit_hip_ctx
 	float last_ms = 0.f;
 	hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 	hipEvent_t ev_assess[2] = { nullptr, nullptr };
+	hipEvent_t ev_settle[2] = { nullptr, nullptr }; // around a k_settle launch
+	ntedit_hip_settle_stats settle_last = { 0, 0, 0.f }; // ntedit_hip_settle_info(): the last polish call
 	DevBuf packed; // a batch as it crossed PCIe in the packed form (NTEDIT_HIP_BASES_PACKED), before k_unpack
 	DevBuf runmap; // the absent bitmap minus the positions that cannot do anything (k_assess)
 	DevBuf candmap; // -s 1 on a plain filter: 4 bits per position, the first-probe bits of its substitution candidates (k_wc_scatter_b<3, ., 1>)
@@ -131,6 +134,8 @@ struct ntedit_hip_ctx
 		u32 snv_wave = 0;        // -s 1 with the run map: the events go to the wavefront-per-event launch (experiment)
 		u32 no_rounds = 0, no_early_copy = 0;
 		u32 force_rounds = 0;     // event rounds whatever the number of events (tests: small inputs)
+		u64 arena_chunks = 0;     // chunks of the edit-record arena in the first attempt (tests: one that runs out; 0: by batch size)
+		u32 settle = ~0u;         // k_settle in front of the thread-per-event launch: 0 never, 1 wherever it applies, ~0: auto
 		u32 bin_scatter = 0;      // partition kernel: 0 barrier-phased (k_wc_scatter_b), 1 barrier-free (k_wc_scatter)
 		u32 probe_parts_log2 = ~0u; // probe stage: slices probed in 2^x parts (~0: by slice size)
 		u32 bin_slice_log2 = 0;   // log2 of the slots of a filter slice (0: 2 MiB), doubled until the partition kernel has rings for all slices (tests: many slices of a small filter)
@@ -138,6 +143,7 @@ struct ntedit_hip_ctx
 		u32 bin_ring = 0;         // k_wc_scatter_b: 8 = the wide layout (8-slot rings) whatever the slices, 16 = never (1024 slices at most), 0: wide beyond 1024 slices
 	} tune;
 	DevBuf ev_cover, ev_before, ev_flags, ev_list, ev_bmax; // event rounds
+	DevBuf ev_rest; // the events of a round k_settle declined (nte_settle.hip)
 	u32 cu_count = 256;
 	size_t lds_per_block = 160 * 1024;
 	double alloc_ms = 0.0;            // host time spent in hipFree + hipMalloc of the grow-only buffers (ensure())

@@ -57,6 +57,12 @@ ntedit_hip_create(int device, ntedit_hip_ctx** out)
 			return NTEDIT_E_DEVICE;
 		}
 	}
+	for (auto& e : c->ev_settle) {
+		if (hipEventCreate(&e) != hipSuccess) {
+			delete c;
+			return NTEDIT_E_DEVICE;
+		}
+	}
 	{
 		std::lock_guard<std::mutex> lk(g_live_mu);
 		g_live_ctx.push_back(c);
@@ -89,7 +95,7 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 	}
 	DevBuf* bufs[] = { &c->seq,      &c->bitmap,   &c->block_counts, &c->block_offsets, &c->events,
 		               &c->first_chunk, &c->arena, &c->counters, &c->deferred,     &c->ws_nodes,      &c->ws_ov_pos,
-		               &c->ws_ov_chr, &c->ws_prev, &c->ws_lps, &c->ws_win, &c->runmap, &c->candmap, &c->packed, &c->bin_records, &c->bin_fill, &c->bin_ctl, &c->bin_ovf, &c->bin_state, &c->ev_cover, &c->ev_before, &c->ev_flags, &c->ev_list, &c->ev_bmax,       &c->offs,          &c->lens };
+		               &c->ws_ov_chr, &c->ws_prev, &c->ws_lps, &c->ws_win, &c->runmap, &c->candmap, &c->packed, &c->bin_records, &c->bin_fill, &c->bin_ctl, &c->bin_ovf, &c->bin_state, &c->ev_cover, &c->ev_before, &c->ev_flags, &c->ev_list, &c->ev_bmax, &c->ev_rest,       &c->offs,          &c->lens };
 	for (DevBuf* b : bufs) {
 		release(*b);
 	}
@@ -106,6 +112,11 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 		}
 	}
 	for (auto& e : c->ev_assess) {
+		if (e) {
+			(void)hipEventDestroy(e);
+		}
+	}
+	for (auto& e : c->ev_settle) {
 		if (e) {
 			(void)hipEventDestroy(e);
 		}

@@ -9,6 +9,14 @@
 // finish()            timings
 namespace {
 
+// k_settle runs on lists of at least this many events.  It costs a launch, a stream synchronisation and the read-back of
+// the rest count, and a short list is bound by the latency of its slowest events either way: measured on the i.i.d.
+// draft (k_settle on against off, ms per step) lists of 29 k / 59 k / 117 k events lose 0.39 / 0.39 / 0.30 ms, 292 k
+// events in contigs of 100 kbp lose 0.15, 440 k gain 0.12 and 3.26 M gain 3.9: break-even at about 350 k (DESIGN.md 8,
+// experiment 65)
+#ifndef NTE_SETTLE_MIN_EVENTS
+#define NTE_SETTLE_MIN_EVENTS 400000u
+#endif
 constexpr unsigned NTE_RESOLVE_ROUNDS = 6; // rounds of one-parked-event-per-contig re-runs before the re-runs are widened (collect())
 
 struct PolishRun
@@ -61,7 +69,8 @@ struct PolishRun
 	bool first_b = true;
 	MachineArgs keep_a; // the last chunk's launch arguments (re-runs of parked events)
 	// counters layout (bytes): [0] absent k-mers u64, [8] starts of the current chunk u64, [32] arena cursor u32,
-	// [40] status u32, [44] deferred count u32, [52] parked events u32, [60] work counter u32, [64] round list length u32
+	// [40] status u32, [44] deferred count u32, [52] parked events u32, [60] work counter u32, [64] round list length u32,
+	// [72] rest list length u32 (k_settle)
 	unsigned long long* d_counters = nullptr;
 	u32 *d_arena_next = nullptr, *d_status = nullptr, *d_ndef = nullptr, *d_list_n = nullptr;
 
@@ -205,6 +214,9 @@ PolishRun::plan()
 	if (arena_chunks * CHUNK_ITEMS * sizeof(Item) < c->arena.cap) {
 		arena_chunks = c->arena.cap / (CHUNK_ITEMS * sizeof(Item));
 	}
+	if (c->tune.arena_chunks) { // tests: an arena that runs out (the batch is run again with four times as much)
+		arena_chunks = c->tune.arena_chunks;
+	}
 	return 0;
 }
 
@@ -232,6 +244,7 @@ PolishRun::begin_attempt()
 	d_list_n = (u32*)((char*)c->counters.p + 64);
 	h2d_launches = 0;
 	status = 0;
+	c->settle_last = ntedit_hip_settle_stats{ 0, 0, 0.f };
 	ev_total = absent_total = deferred_total = skipped_total = 0;
 	ms_machine = 0.f;
 	first_b = true;
@@ -649,6 +662,13 @@ PolishRun::run_chunk_events(size_t j)
 	const u32 pm_blocks = (n32 + 1023) / 1024;
 	a.ev_cover = nullptr;
 	a.ev_flags = nullptr;
+	// k_settle in front of the thread-per-event launches: where settle_event() restates the machine (nte_settle.h)
+	// (no list of a batch is longer than n_ev: a batch below the minimum needs no rest list)
+	const bool settle = c->tune.settle != 0 && settle_applicable(a.p, a.bloom) && !c->filt[1].set && n_ev < 0xFFFFFF00ull &&
+	                    (c->tune.settle == 1 || n_ev >= NTE_SETTLE_MIN_EVENTS);
+	if (settle && (rc = ensure(c, c->ev_rest, n_ev * 4))) {
+		return rc;
+	}
 	if (rounds) {
 		if ((rc = ensure(c, c->ev_cover, n_ev * 8)) || (rc = ensure(c, c->ev_before, n_ev * 8)) ||
 		    (rc = ensure(c, c->ev_flags, n_ev)) || (rc = ensure(c, c->ev_list, n_ev * 4)) ||
@@ -690,10 +710,34 @@ PolishRun::run_chunk_events(size_t j)
 			return 0;
 		}
 		HIP_TRY(c, hipMemsetAsync(d_ndef, 0, 4, sB));
-		HIP_TRY(c, hipMemsetAsync(ra.work_counter, 0, 4, sB));
-		const u64 want = ((u64)count + MACHINE_TPB - 1) / MACHINE_TPB;
-		launch_k_machine_thread((unsigned)(want < blocks ? want : blocks), dyn_lds, sB, ra);
-		HIP_TRY(c, hipGetLastError());
+		if (settle && (c->tune.settle == 1 || count >= NTE_SETTLE_MIN_EVENTS)) {
+			// the plain substitution events of the list, settled by lanes that all ask the same question (nte_settle.hip);
+			// the thread-per-event launch runs what is left
+			u32* d_rest = (u32*)c->ev_rest.p;
+			u32* d_nrest = (u32*)((char*)c->counters.p + 72);
+			HIP_TRY(c, hipMemsetAsync(d_nrest, 0, 4, sB));
+			HIP_TRY(c, hipEventRecord(c->ev_settle[0], sB));
+			const u64 sw = ((u64)count + MACHINE_TPB - 1) / MACHINE_TPB, scap = (u64)c->cu_count * 16;
+			launch_k_settle((unsigned)(sw < scap ? sw : scap), sB, ra, d_rest, d_nrest);
+			HIP_TRY(c, hipGetLastError());
+			HIP_TRY(c, hipEventRecord(c->ev_settle[1], sB));
+			u32 n_rest = 0;
+			HIP_TRY(c, hipMemcpyAsync(&n_rest, d_nrest, 4, hipMemcpyDeviceToHost, sB));
+			HIP_TRY(c, hipStreamSynchronize(sB));
+			float t = 0.f;
+			(void)hipEventElapsedTime(&t, c->ev_settle[0], c->ev_settle[1]);
+			c->settle_last.ms += t;
+			c->settle_last.events_seen += count;
+			c->settle_last.events_settled += count - n_rest;
+			ra.ev_list = d_rest;
+			ra.n_events = n_rest;
+		}
+		if (ra.n_events) {
+			HIP_TRY(c, hipMemsetAsync(ra.work_counter, 0, 4, sB));
+			const u64 want = ((u64)ra.n_events + MACHINE_TPB - 1) / MACHINE_TPB;
+			launch_k_machine_thread((unsigned)(want < blocks ? want : blocks), dyn_lds, sB, ra);
+			HIP_TRY(c, hipGetLastError());
+		}
 		u32 h_tail[4] = { 0, 0, 0, 0 };
 		HIP_TRY(c, hipMemcpyAsync(h_tail, (char*)c->counters.p + 32, 16, hipMemcpyDeviceToHost, sB));
 		HIP_TRY(c, hipEventRecord(c->ev[5], sB));
@@ -805,9 +849,13 @@ PolishRun::run_chunk_events(size_t j)
 		    "machine %.3f ms (sweep launches %.3f ms) arena %u status %u window %u\n",
 		    j + 1, n_ch, ch.c0, ch.c1, (unsigned long long)n_ev, n_A, n_B, n_C,
 		    (unsigned long long)(rounds ? (u64)n32 - n_A - n_B - n_C : 0), n_def, p_all, p2_ms, h_tail[0], status, c->dp.node_window);
+		if (c->settle_last.events_seen) {
+			fprintf(stderr, "[ntedit_hip] k_settle: %llu of %llu events settled in %.3f ms\n", (unsigned long long)c->settle_last.events_settled,
+			        (unsigned long long)c->settle_last.events_seen, c->settle_last.ms);
+		}
 		unsigned long long pr[64];
 		machine_wave_profile(pr);
-		const unsigned long long tg = machine_thread_gathers();
+		const unsigned long long tg = machine_thread_gathers() + settle_gathers(); // (k_settle counts into the thread launches' figure)
 		if (pr[15] || tg) {
 			fprintf(stderr, "[ntedit_hip] machine filter gathers (profile build): thread-per-event launches %llu, wavefront-per-event launches %llu\n", tg, pr[15]);
 		}
@@ -1199,6 +1247,9 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		}
 	}
 	if ((rc = ensure(c, c->deferred, n_ev * 4))) {
+		return rc;
+	}
+	if (c->tune.settle != 0 && settle_applicable(c->dp, f0) && !c->filt[1].set && (rc = ensure(c, c->ev_rest, n_ev * 4))) { // (k_settle's rest list)
 		return rc;
 	}
 	if (n_ev >= (u64)c->cu_count * 8192) { // (event rounds)

@@ -398,6 +398,16 @@ ntedit_hip_last_kernel_ms(const ntedit_hip_ctx* c)
 	return c ? c->last_ms : 0.f;
 }
 
+int
+ntedit_hip_settle_info(ntedit_hip_ctx* c, ntedit_hip_settle_stats* st)
+{
+	if (!c || !st) {
+		return fail(c, NTEDIT_E_ARG, "settle_info: bad argument");
+	}
+	*st = c->settle_last;
+	return 0;
+}
+
 #ifndef NTE_BUILD_ID
 #define NTE_BUILD_ID "unknown"
 #endif
@@ -522,6 +532,10 @@ ntedit_hip_set_tuning(ntedit_hip_ctx* c, const char* key, uint64_t value)
 		t.snv_wave = (u32)value;
 	} else if (k == "force_rounds") {
 		t.force_rounds = (u32)value;
+	} else if (k == "arena_chunks") {
+		t.arena_chunks = value;
+	} else if (k == "settle") {
+		t.settle = value > 1 ? ~0u : (u32)value;
 	} else if (k == "no_rounds") {
 		t.no_rounds = (u32)value;
 	} else if (k == "no_early_copy") {

@@ -124,6 +124,12 @@ launch_k_machine_wave(unsigned blocks, size_t dyn_lds, hipStream_t stream, const
 	}
 }
 
+// k_settle (nte_settle.hip): the events of (a.ev_list, a.n_events) that are plain substitution events are settled
+// (arena chunk, first_chunk, ev_cover / ev_flags as the machine leaves them); the others are appended to rest[*n_rest]
+// (*n_rest zeroed before the launch), for the thread-per-event launch
+void launch_k_settle(unsigned blocks, hipStream_t stream, const MachineArgs& a, u32* rest, u32* n_rest);
+unsigned long long settle_gathers(); // filter gathers of k_settle since the last call (profile build; 0 otherwise)
+
 // the device code's candidate tables, raw (nte_machine_thread.hip: k_tables; 30 * 8 + 4 * 341 * 8 bytes)
 constexpr size_t TABLES_RAW_BYTES = 30 * 8 + 4 * 341 * 8;
 void launch_k_tables(hipStream_t stream, u8* out);

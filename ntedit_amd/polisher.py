@@ -339,6 +339,12 @@ class Polisher:
         self._check(self._lib.ntedit_hip_device_tables(self._h, buf, ctypes.c_uint64(len(buf)), ctypes.byref(n)), "device_tables")
         return buf.raw[:n.value].decode()
 
+    def settle_info(self):
+        """ntedit_hip_settle_info: (events seen, events settled, ms) of k_settle in the last polish_batch"""
+        st = _lib.SettleStats()
+        self._check(self._lib.ntedit_hip_settle_info(self._h, ctypes.byref(st)), "settle_info")
+        return st.events_seen, st.events_settled, st.ms
+
     def set_tuning(self, key, value):
         """Test / tuning knobs (include/ntedit_hip.h: none of them can change a result)."""
         self._check(self._lib.ntedit_hip_set_tuning(self._h, key.encode(), int(value)), "set_tuning")
