@@ -919,6 +919,66 @@ typedef struct ntedit_hip_settle_stats
 } ntedit_hip_settle_stats;
 int ntedit_hip_settle_info(ntedit_hip_ctx* ctx, ntedit_hip_settle_stats* st);
 
+/* ---- the edited draft in HBM, and the k-mer QV of a polish (no counterpart in the reference) -----------------
+ * The device applier turns a batch's result into the edited contigs in device memory: for every entry exactly the bytes
+ * ntedit_hip_write_outputs() puts between the header line and the closing newline of _edited.fa, entry after entry with
+ * one separator byte ('\n') behind each -- the layout of an input batch, so the buffer can be screened or polished as it
+ * stands.  Segments (ntedit_hip_segment) are not supported: the call takes none.
+ * ntedit_hip_set_apply(ctx, flags), for the polish calls that follow:
+ *   0                          the default: nothing of this runs
+ *   NTEDIT_HIP_APPLY_EDITED    the applier runs inside ntedit_hip_polish_batch, behind the collection of the edit records;
+ *                              the result owns the edited bases until ntedit_hip_result_free()
+ *   NTEDIT_HIP_APPLY_QV        the applier runs, the edited bases are screened against the primary filter the batch was
+ *                              polished with, and per entry the k-mer starts and the absent k-mers are counted before and
+ *                              after (ntedit_hip_result_qv); the edited bases go with the call unless APPLY_EDITED is set too
+ * A malformed arena fails the polish call with NTEDIT_E_INTERNAL (the message names the renderer's code). */
+#define NTEDIT_HIP_APPLY_EDITED 1u
+#define NTEDIT_HIP_APPLY_QV 2u
+int ntedit_hip_set_apply(ntedit_hip_ctx* ctx, uint32_t flags);
+/* The edited bases of a result polished with APPLY_EDITED (NTEDIT_E_ARG otherwise; ntedit_hip_result_last_error() says
+ * why).  *dev_ptr: device memory, 16-byte aligned, valid until ntedit_hip_result_free(); *n_bytes: its bytes, separators
+ * included; offsets_out / lens_out (n_contigs each, may be NULL): entry i is dev_ptr[offsets_out[i] .. + lens_out[i]). */
+int ntedit_hip_result_edited_device(const ntedit_hip_result* r, const char** dev_ptr, uint64_t* n_bytes, uint64_t* offsets_out, uint32_t* lens_out,
+                                    uint32_t n_contigs);
+/* the same with a download into host_buf[0 .. cap); *n_bytes = bytes needed (NTEDIT_E_OVERFLOW when cap is less) */
+int ntedit_hip_result_edited(const ntedit_hip_result* r, char* host_buf, uint64_t cap, uint64_t* n_bytes, uint64_t* offsets_out, uint32_t* lens_out,
+                             uint32_t n_contigs);
+const char* ntedit_hip_result_last_error(void);
+
+/* One row per entry of a batch polished with APPLY_QV.  kmers: the k-mer starts inside the entry whose k bytes are all
+ * A, C, G or T, in either case -- the k-mers a read set can hold.  absent: the set bits of ntedit_hip_screen's bitmap
+ * among the entry's starts [offset, offset + len - k + 1): not in the primary filter; a counting filter: below the -p
+ * threshold.  (The screening hashes k-mers that hold another IUPAC code too, with zero seeds: such a k-mer is practically
+ * always absent and no k-mer of `kmers`.  On a draft of A, C, G, T and N the two definitions are one.)  With -s 1 step 1
+ * marks every k-mer, so both screenings run again without it: the counts are those of -s 0.
+ * before: the entry as it came, after: as edited. */
+typedef struct ntedit_hip_qv_row
+{
+	uint64_t len_before, len_after;
+	uint64_t kmers_before, absent_before;
+	uint64_t kmers_after, absent_after;
+} ntedit_hip_qv_row;
+int ntedit_hip_result_qv(const ntedit_hip_result* r, ntedit_hip_qv_row* rows, uint32_t n_contigs);
+/* Merqury's consensus QV from those counts, -10 log10(1 - (1 - absent / kmers)^(1 / k)): +inf for absent == 0, NaN for
+ * kmers == 0, 0 for absent >= kmers.  Host arithmetic in double; the only place the formula lives. */
+double ntedit_hip_qv_value(uint64_t absent, uint64_t kmers, uint32_t k);
+/* <prefix>_qv.tsv as the front ends write it: the header line, and one line per row -- name, len_before, len_after,
+ * kmers_before, absent_before, qv_before, kmers_after, absent_after, qv_after; QVs with two decimals, "inf" and "NA" for
+ * the two special cases.  The last row, "#total", holds the sums. */
+const char* ntedit_hip_qv_header(void);
+int ntedit_hip_qv_format_row(const char* name, const ntedit_hip_qv_row* row, uint32_t k, char* out, uint64_t cap);
+
+/* The context's last polish call with an apply flag: HIP-event times of the applier's kernels, of the screening of the
+ * edited bases and of the count kernel (both passes), the pieces and bytes the applier wrote, the events it applied. */
+typedef struct ntedit_hip_apply_stats
+{
+	float ms_apply, ms_screen, ms_count;
+	uint64_t pieces, bytes, events_applied;
+} ntedit_hip_apply_stats;
+int ntedit_hip_apply_info(ntedit_hip_ctx* ctx, ntedit_hip_apply_stats* st);
+/* output bytes per workgroup of the applier's copy kernel (tests place edits on both sides of a tile's edge) */
+uint32_t ntedit_hip_apply_tile(void);
+
 /* The reference's candidate tables -- num_tries, polish_bases_array / snv_bases_array, multi_possible_bases (ntedit.cpp:172,
  * 176-199, 203-348) -- as the device code holds them (one GPU thread runs the machine's own candidate_bases /
  * insertion_candidate), as text: "num_tries 0 1 5 21 85 341", "polish A TCG", ..., "snv N ATCG", "multi A A AA AC ...".

@@ -149,6 +149,24 @@ class SettleStats(ctypes.Structure):
     _fields_ = [("events_seen", ctypes.c_uint64), ("events_settled", ctypes.c_uint64), ("ms", ctypes.c_float)]
 
 
+APPLY_EDITED, APPLY_QV = 1, 2
+
+
+class QvRow(ctypes.Structure):
+    """ntedit_hip_qv_row: the QV counts of one entry of a batch polished with APPLY_QV"""
+    _fields_ = [("len_before", ctypes.c_uint64), ("len_after", ctypes.c_uint64), ("kmers_before", ctypes.c_uint64),
+                ("absent_before", ctypes.c_uint64), ("kmers_after", ctypes.c_uint64), ("absent_after", ctypes.c_uint64)]
+
+
+QV_DTYPE = [(name, "<u8") for name, _ in QvRow._fields_]
+
+
+class ApplyStats(ctypes.Structure):
+    """ntedit_hip_apply_stats"""
+    _fields_ = [("ms_apply", ctypes.c_float), ("ms_screen", ctypes.c_float), ("ms_count", ctypes.c_float),
+                ("pieces", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("events_applied", ctypes.c_uint64)]
+
+
 class ReadsParseStats(ctypes.Structure):
     """ntedit_hip_reads_parse_stats"""
     _fields_ = [("device_chunks", ctypes.c_uint64), ("fallback_chunks", ctypes.c_uint64),
@@ -258,6 +276,9 @@ EXPORTS = [
     "ntedit_hip_genome_pass_get_info", "ntedit_hip_genome_pass_line",
     "ntedit_hip_sketch_reset", "ntedit_hip_resident_count", "ntedit_hip_reads_set_min_read",
     "ntedit_hip_settle_info",
+    "ntedit_hip_set_apply", "ntedit_hip_result_edited_device", "ntedit_hip_result_edited",
+    "ntedit_hip_result_last_error", "ntedit_hip_result_qv", "ntedit_hip_qv_value", "ntedit_hip_qv_header",
+    "ntedit_hip_qv_format_row", "ntedit_hip_apply_info", "ntedit_hip_apply_tile",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -424,5 +445,22 @@ def load():
     lib.ntedit_hip_sketch_reset.argtypes = [vp, u64, u32, u32]
     lib.ntedit_hip_resident_count.argtypes = [vp]
     lib.ntedit_hip_reads_set_min_read.argtypes = [vp, u32]
+    # the edited draft in HBM and the k-mer QV (nte_apply.hip)
+    pu32 = ctypes.POINTER(u32)
+    lib.ntedit_hip_set_apply.argtypes = [vp, u32]
+    lib.ntedit_hip_result_edited_device.argtypes = [vp, ctypes.POINTER(vp), pu64, vp, vp, u32]
+    lib.ntedit_hip_result_edited.argtypes = [vp, vp, u64, pu64, vp, vp, u32]
+    lib.ntedit_hip_result_last_error.argtypes = []
+    lib.ntedit_hip_result_last_error.restype = ctypes.c_char_p
+    lib.ntedit_hip_result_qv.argtypes = [vp, vp, u32]
+    lib.ntedit_hip_qv_value.argtypes = [u64, u64, u32]
+    lib.ntedit_hip_qv_value.restype = ctypes.c_double
+    lib.ntedit_hip_qv_header.argtypes = []
+    lib.ntedit_hip_qv_header.restype = ctypes.c_char_p
+    lib.ntedit_hip_qv_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(QvRow), u32, ctypes.c_char_p, u64]
+    lib.ntedit_hip_apply_info.argtypes = [vp, ctypes.POINTER(ApplyStats)]
+    lib.ntedit_hip_apply_tile.argtypes = []
+    lib.ntedit_hip_apply_tile.restype = u32
+    del pu32
     _lib = lib
     return lib

@@ -5,6 +5,7 @@
 // that needs the GPU fails with NTEDIT_E_DEVICE when there is none.
 #include "nte_kernels.hip"
 #include "nte_settle.h"
+#include "nte_apply.h"
 
 #include "../../include/ntedit_hip.h"
 #include "../host/bfio.h"
@@ -144,6 +145,11 @@ struct ntedit_hip_ctx
 	} tune;
 	DevBuf ev_cover, ev_before, ev_flags, ev_list, ev_bmax; // event rounds
 	DevBuf ev_rest; // the events of a round k_settle declined (nte_settle.hip)
+	// the device applier and the QV counts (nte_apply.hip): ntedit_hip_set_apply()
+	u32 apply_flags = 0;
+	DevBuf ap_ev, ap_place, ap_range, ap_contig, ap_tabs, ap_pieces, ap_edited, ap_bitmap, ap_rows;
+	hipEvent_t ap_evt[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+	ntedit_hip_apply_stats apply_last = { 0.f, 0.f, 0.f, 0, 0, 0 };
 	u32 cu_count = 256;
 	size_t lds_per_block = 160 * 1024;
 	double alloc_ms = 0.0;            // host time spent in hipFree + hipMalloc of the grow-only buffers (ensure())
@@ -167,6 +173,14 @@ struct ntedit_hip_result
 	bool edits_built = false;
 	std::vector<ntedit_hip_edit> edits;
 	std::string edit_pool;
+	// the applier's output (NTEDIT_HIP_APPLY_*): the edited bases in HBM, their table, the QV rows
+	u32 apply_flags = 0;
+	int device = 0;
+	DevBuf edited;
+	u64 edited_bytes = 0;
+	std::vector<uint64_t> e_offs;
+	std::vector<uint32_t> e_lens;
+	std::vector<ntedit_hip_qv_row> qv;
 };
 
 namespace {

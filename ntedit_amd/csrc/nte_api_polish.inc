@@ -103,6 +103,7 @@ struct PolishRun
 	int run_chunk_events(size_t j);
 	int collect(bool* redo);
 	int finish();
+	int apply();
 };
 
 int
@@ -1057,6 +1058,212 @@ PolishRun::finish()
 	return 0;
 }
 
+// The device applier and the QV counts (nte_apply.hip), behind everything a plain call does: the streams are idle, the
+// arena and the first-chunk table in HBM are what collect() copied (the re-runs of parked events write both on the
+// device), c->bitmap still holds step 1's answer (k_assess writes a map of its own, c->runmap).  Crosses PCIe: five
+// words of totals, the entries' offsets and lengths, the QV rows.
+int
+PolishRun::apply()
+{
+	const u32 flags = c->apply_flags;
+	r->apply_flags = flags;
+	r->device = c->device;
+	if (!flags) {
+		return 0;
+	}
+	int rc;
+	hipStream_t s = c->stream;
+	const u32 k = c->dp.k;
+	if ((flags & NTEDIT_HIP_APPLY_QV) && k > QV_MAX_K) {
+		return fail(c, NTEDIT_E_UNSUPPORTED, "apply: the QV counts take k up to %u", QV_MAX_K);
+	}
+	for (auto& e : c->ap_evt) {
+		if (!e) {
+			HIP_TRY(c, hipEventCreate(&e));
+		}
+	}
+	const u64 n_ev = ev_total;
+	const size_t nc = n_contigs;
+	// ap_tabs: out_offs u64[nc] | piece_base u64[nc + 1] | totals u64[3] | status (8 bytes) | out_lens u32[nc]
+	const size_t tabs_bytes = nc * 8 + (nc + 1) * 8 + 32 + nc * 4;
+	if ((rc = ensure(c, c->ap_ev, (size_t)(n_ev + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, c->ap_place, (size_t)(n_ev + 1) * sizeof(ApplyPlace))) ||
+	    (rc = ensure(c, c->ap_range, nc * 8)) || (rc = ensure(c, c->ap_contig, nc * sizeof(ApplyContig))) || (rc = ensure(c, c->ap_tabs, tabs_bytes))) {
+		return rc;
+	}
+	ApplyArgs a;
+	memset(&a, 0, sizeof a);
+	a.seq = d_seq;
+	a.n_seq = n;
+	a.offs = (const u64*)c->offs.p;
+	a.lens = (const u32*)c->lens.p;
+	a.n_contigs = n_contigs;
+	a.arena = (const Item*)c->arena.p;
+	a.arena_items = r->arena_items;
+	a.ev_first = (const u32*)c->first_chunk.p;
+	a.n_events = (u32)n_ev;
+	a.ev = (ApplyEvent*)c->ap_ev.p;
+	a.place = (ApplyPlace*)c->ap_place.p;
+	a.ev_begin = (u32*)c->ap_range.p;
+	a.ev_end = a.ev_begin + nc;
+	a.contig = (ApplyContig*)c->ap_contig.p;
+	a.out_offs = (u64*)c->ap_tabs.p;
+	a.piece_base = a.out_offs + nc;
+	a.totals = a.piece_base + nc + 1;
+	a.status = (u32*)(a.totals + 3);
+	a.out_lens = (u32*)(a.totals + 4);
+	HIP_TRY(c, hipMemsetAsync(a.place, 0, (size_t)(n_ev + 1) * sizeof(ApplyPlace), s));
+	HIP_TRY(c, hipMemsetAsync(a.ev_begin, 0xFF, nc * 4, s));
+	HIP_TRY(c, hipMemsetAsync(a.ev_end, 0, nc * 4, s));
+	HIP_TRY(c, hipMemsetAsync(a.totals, 0, 32, s));
+	HIP_TRY(c, hipEventRecord(c->ap_evt[0], s));
+	launch_apply_plan(s, a);
+	HIP_TRY(c, hipGetLastError());
+	u64 h_tot[4] = { 0, 0, 0, 0 };
+	HIP_TRY(c, hipMemcpyAsync(h_tot, a.totals, 32, hipMemcpyDeviceToHost, s));
+	HIP_TRY(c, hipStreamSynchronize(s));
+	const u32 st = (u32)h_tot[3];
+	if (st) {
+		const int code = (st & AP_BAD_INDEX) ? -1 : (st & AP_BAD_ORDER) ? -2 : (st & AP_BAD_COUNT) ? -3 : (st & AP_BAD_ITEM) ? -4 : (st & AP_UNFINISHED) ? -6 : 0;
+		if (!code) {
+			return fail(c, NTEDIT_E_OVERFLOW, "apply: an edited contig of 4 GiB or more");
+		}
+		return fail(c, NTEDIT_E_INTERNAL, "apply: malformed event records (the renderer's code %d)", code);
+	}
+	const u64 total_bytes = h_tot[0], total_pieces = h_tot[1];
+	DevBuf eb;
+	{
+		std::lock_guard<std::mutex> lk(c->pin_mu); // (a result that is freed hands its buffer back from another thread)
+		eb = c->ap_edited;
+		c->ap_edited = DevBuf();
+	}
+	rc = ensure(c, eb, (size_t)((total_bytes + 15) / 16 * 16 + 64));
+	if (!rc) {
+		rc = ensure(c, c->ap_pieces, (size_t)(total_pieces + 1) * sizeof(ApplyPiece));
+	}
+	if (rc) {
+		release(eb);
+		return rc;
+	}
+	a.pieces = (ApplyPiece*)c->ap_pieces.p;
+	a.out = (u8*)eb.p;
+	launch_apply_write(s, a, total_bytes, total_pieces);
+	hipError_t he = hipGetLastError();
+	if (he == hipSuccess) {
+		he = hipEventRecord(c->ap_evt[1], s);
+	}
+	r->e_offs.resize(nc);
+	r->e_lens.resize(nc);
+	if (he == hipSuccess) {
+		he = hipMemcpyAsync(r->e_offs.data(), a.out_offs, nc * 8, hipMemcpyDeviceToHost, s);
+	}
+	if (he == hipSuccess) {
+		he = hipMemcpyAsync(r->e_lens.data(), a.out_lens, nc * 4, hipMemcpyDeviceToHost, s);
+	}
+	bool qv = (flags & NTEDIT_HIP_APPLY_QV) != 0;
+	int qrc = 0;
+	float ms_rescreen = 0.f;
+	if (he == hipSuccess && qv) {
+		// before: the batch and step 1's bitmap; after: the edited bases, screened the way a batch of that size is.  With
+		// -s 1 step 1 marks every k-mer of accepted bases (k_screen: "no probe decides that"), so c->bitmap is not the plain
+		// answer: both screenings then run with the flag down, the batch's into the second bitmap first.
+		struct PlainScreen
+		{
+			ntedit_hip_ctx* c;
+			int hp_snv;
+			u32 dp_snv;
+			explicit PlainScreen(ntedit_hip_ctx* c_) : c(c_), hp_snv(c_->hp.snv), dp_snv(c_->dp.snv)
+			{
+				c->hp.snv = 0;
+				c->dp.snv = 0;
+			}
+			~PlainScreen()
+			{
+				c->hp.snv = hp_snv;
+				c->dp.snv = dp_snv;
+			}
+		} plain(c);
+		const bool rescreen = plain.dp_snv != 0;
+		const u64 nw2 = (total_bytes + 63) / 64;
+		const u64 nw_max = rescreen && n_words > nw2 ? n_words : nw2;
+		if ((qrc = ensure(c, c->ap_rows, nc * sizeof(QvRow))) == 0 && (qrc = ensure(c, c->ap_bitmap, (size_t)(nw_max + 8) * 8)) == 0 &&
+		    (qrc = bin_reset(c, s)) == 0) {
+			QvRow* rows = (QvRow*)c->ap_rows.p;
+			u64* bm2 = (u64*)c->ap_bitmap.p;
+			u32 recovered = 0;
+			const u64* bm_before = d_bitmap;
+			if (rescreen) {
+				(void)hipEventRecord(c->ap_evt[4], s);
+				qrc = launch_screen<false>(c, d_seq, n, f0, bm2, n_words);
+				(void)hipEventRecord(c->ap_evt[5], s);
+				if (!qrc) {
+					qrc = bin_recover(c, s, d_seq, n, f0, bm2, n_words, 0, n, &recovered);
+				}
+				if (!qrc && hipStreamSynchronize(s) == hipSuccess) {
+					(void)hipEventElapsedTime(&ms_rescreen, c->ap_evt[4], c->ap_evt[5]);
+				}
+				bm_before = bm2;
+			}
+			if (!qrc) {
+				(void)hipEventRecord(c->ap_evt[2], s);
+				launch_qv_rows(s, rows, a.lens, a.out_lens, n_contigs);
+				launch_qv_count(s, d_seq, n, a.offs, a.lens, n_contigs, bm_before, k, rows, 0);
+				(void)hipEventRecord(c->ap_evt[3], s);
+				qrc = rescreen ? bin_reset(c, s) : 0;
+			}
+			if (!qrc) {
+				(void)hipEventRecord(c->ap_evt[4], s);
+				qrc = launch_screen<false>(c, a.out, total_bytes, f0, bm2, nw2);
+				(void)hipEventRecord(c->ap_evt[5], s);
+			}
+			if (!qrc) {
+				qrc = bin_recover(c, s, a.out, total_bytes, f0, bm2, nw2, 0, total_bytes, &recovered);
+			}
+			if (!qrc) {
+				(void)hipEventRecord(c->ap_evt[6], s);
+				launch_qv_count(s, a.out, total_bytes, a.out_offs, a.out_lens, n_contigs, bm2, k, rows, 1);
+				(void)hipEventRecord(c->ap_evt[7], s);
+				r->qv.resize(nc);
+				he = hipMemcpyAsync(r->qv.data(), rows, nc * sizeof(QvRow), hipMemcpyDeviceToHost, s);
+			}
+		}
+	}
+	if (he == hipSuccess) {
+		he = hipStreamSynchronize(s);
+	}
+	if (he == hipSuccess) {
+		he = hipGetLastError();
+	}
+	if (he != hipSuccess || qrc) {
+		(void)hipDeviceSynchronize();
+		release(eb);
+		r->qv.clear();
+		return qrc ? qrc : fail(c, NTEDIT_E_DEVICE, "apply: %s", hipGetErrorString(he));
+	}
+	ntedit_hip_apply_stats as = { 0.f, 0.f, 0.f, total_pieces, total_bytes, h_tot[2] };
+	(void)hipEventElapsedTime(&as.ms_apply, c->ap_evt[0], c->ap_evt[1]);
+	if (qv) {
+		float t0 = 0.f, t1 = 0.f;
+		(void)hipEventElapsedTime(&as.ms_screen, c->ap_evt[4], c->ap_evt[5]);
+		as.ms_screen += ms_rescreen;
+		(void)hipEventElapsedTime(&t0, c->ap_evt[2], c->ap_evt[3]);
+		(void)hipEventElapsedTime(&t1, c->ap_evt[6], c->ap_evt[7]);
+		as.ms_count = t0 + t1;
+	}
+	c->apply_last = as;
+	r->edited_bytes = total_bytes;
+	if (flags & NTEDIT_HIP_APPLY_EDITED) {
+		r->edited = eb; // the result's own until ntedit_hip_result_free()
+	} else {
+		std::lock_guard<std::mutex> lk(c->pin_mu);
+		if (c->ap_edited.p) {
+			release(eb);
+		} else {
+			c->ap_edited = eb;
+		}
+	}
+	return 0;
+}
+
 } // namespace
 
 extern "C" int
@@ -1090,6 +1297,8 @@ ntedit_hip_polish_batch(
 	r->st.bases = n;
 	r->snv = c->hp.snv ? 1 : 0;
 	r->part_margin = c->dp.k + c->dp.max_deletions + 48; // (what an event may touch behind the end of its run)
+	r->apply_flags = c->apply_flags;
+	r->device = c->device;
 	if (n == 0 || n_contigs == 0) {
 		*out = r;
 		return 0;
@@ -1124,7 +1333,7 @@ ntedit_hip_polish_batch(
 				return run.bail(rc);
 			}
 			if (!redo) {
-				if ((rc = run.finish())) {
+				if ((rc = run.finish()) || (rc = run.apply())) {
 					return run.bail(rc);
 				}
 				break;
@@ -1273,6 +1482,16 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		}
 		const u64 win_bytes = 2 * (u64)c->dp.k + c->dp.max_deletions + 8 + 32;
 		if (win_bytes * MACHINE_TPB > 40 * 1024 && (rc = ensure(c, c->ws_win, threads * (win_bytes + 64)))) {
+			return rc;
+		}
+	}
+	if (c->apply_flags) { // (the applier: an event's summary and place, the edited bases, the piece table; the QV bitmap)
+		if ((rc = ensure(c, c->ap_ev, (size_t)(n_ev + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, c->ap_place, (size_t)(n_ev + 1) * sizeof(ApplyPlace))) ||
+		    (rc = ensure(c, c->ap_pieces, (size_t)(2 * n_ev + 2 * (u64)max_contigs + 1024) * sizeof(ApplyPiece))) ||
+		    (rc = ensure(c, c->ap_edited, (size_t)(n + n / 64 + 4096)))) {
+			return rc;
+		}
+		if ((c->apply_flags & NTEDIT_HIP_APPLY_QV) && (rc = ensure(c, c->ap_bitmap, (size_t)(n_words + n_words / 64 + 64) * 8))) {
 			return rc;
 		}
 	}

@@ -11,7 +11,132 @@ ntedit_hip_result_free(ntedit_hip_result* r)
 	// (a result may outlive its context: its pinned buffers are then released directly)
 	pin_give(r->owner, r->arena_buf);
 	pin_give(r->owner, r->first_buf);
+	if (r->edited.p) {
+		// the edited bases go back to a context that has no buffer of its own by now, or to the device
+		bool kept = false;
+		if (r->owner && ctx_alive(r->owner)) {
+			std::lock_guard<std::mutex> lk(r->owner->pin_mu);
+			if (!r->owner->ap_edited.p) {
+				r->owner->ap_edited = r->edited;
+				kept = true;
+			}
+		}
+		if (!kept) {
+			(void)hipFree(r->edited.p);
+		}
+		r->edited = DevBuf();
+	}
 	delete r;
+}
+
+static thread_local std::string g_result_err;
+
+const char*
+ntedit_hip_result_last_error(void)
+{
+	return g_result_err.c_str();
+}
+
+static int
+result_refuse(const ntedit_hip_result* r, const char* what)
+{
+	g_result_err = what;
+	if (r && r->owner && ctx_alive(r->owner)) {
+		r->owner->err = what;
+	}
+	return NTEDIT_E_ARG;
+}
+
+int
+ntedit_hip_set_apply(ntedit_hip_ctx* c, uint32_t flags)
+{
+	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV))) {
+		return fail(c, NTEDIT_E_ARG, "set_apply: unknown flag");
+	}
+	c->apply_flags = flags;
+	return 0;
+}
+
+int
+ntedit_hip_result_edited_device(const ntedit_hip_result* r, const char** dev_ptr, uint64_t* n_bytes, uint64_t* offsets_out, uint32_t* lens_out,
+                                uint32_t n_contigs)
+{
+	if (!r || !dev_ptr || !n_bytes) {
+		return result_refuse(r, "result_edited: bad argument");
+	}
+	if (!(r->apply_flags & NTEDIT_HIP_APPLY_EDITED)) {
+		return result_refuse(r, "result_edited: the batch was polished without the APPLY_EDITED flag (ntedit_hip_set_apply)");
+	}
+	if (n_contigs != r->e_offs.size() && (offsets_out || lens_out)) {
+		return result_refuse(r, "result_edited: the batch had another number of entries");
+	}
+	*dev_ptr = (const char*)r->edited.p;
+	*n_bytes = r->edited_bytes;
+	if (offsets_out && n_contigs) {
+		memcpy(offsets_out, r->e_offs.data(), (size_t)n_contigs * 8);
+	}
+	if (lens_out && n_contigs) {
+		memcpy(lens_out, r->e_lens.data(), (size_t)n_contigs * 4);
+	}
+	return 0;
+}
+
+int
+ntedit_hip_result_edited(const ntedit_hip_result* r, char* host_buf, uint64_t cap, uint64_t* n_bytes, uint64_t* offsets_out, uint32_t* lens_out,
+                         uint32_t n_contigs)
+{
+	const char* d = nullptr;
+	uint64_t nb = 0;
+	const int rc = ntedit_hip_result_edited_device(r, &d, &nb, offsets_out, lens_out, n_contigs);
+	if (rc) {
+		return rc;
+	}
+	if (n_bytes) {
+		*n_bytes = nb;
+	}
+	if (nb > cap || (nb && !host_buf)) {
+		g_result_err = "result_edited: the buffer is too small";
+		return NTEDIT_E_OVERFLOW;
+	}
+	if (nb && (hipSetDevice(r->device) != hipSuccess || hipMemcpy(host_buf, d, nb, hipMemcpyDeviceToHost) != hipSuccess)) {
+		g_result_err = "result_edited: the download failed";
+		return NTEDIT_E_DEVICE;
+	}
+	return 0;
+}
+
+int
+ntedit_hip_result_qv(const ntedit_hip_result* r, ntedit_hip_qv_row* rows, uint32_t n_contigs)
+{
+	if (!r || (n_contigs && !rows)) {
+		return result_refuse(r, "result_qv: bad argument");
+	}
+	if (!(r->apply_flags & NTEDIT_HIP_APPLY_QV)) {
+		return result_refuse(r, "result_qv: the batch was polished without the APPLY_QV flag (ntedit_hip_set_apply)");
+	}
+	if (n_contigs != r->qv.size()) {
+		return result_refuse(r, "result_qv: the batch had another number of entries");
+	}
+	if (n_contigs) {
+		memcpy(rows, r->qv.data(), (size_t)n_contigs * sizeof(ntedit_hip_qv_row));
+	}
+	return 0;
+}
+
+int
+ntedit_hip_apply_info(ntedit_hip_ctx* c, ntedit_hip_apply_stats* st)
+{
+	if (!c || !st) {
+		return fail(c, NTEDIT_E_ARG, "apply_info: bad argument");
+	}
+	*st = c->apply_last;
+	return 0;
+}
+
+uint32_t
+ntedit_hip_apply_tile(void)
+{
+	return APPLY_TILE;
 }
 
 int

@@ -18,6 +18,7 @@
 #include "log_info.h"
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -66,6 +67,10 @@ static const char USAGE[] = PROGRAM
     "	--gpu N,	HIP device index [default=0]\n"
     "	--batch-bases N,	bases per GPU batch [default: the first batch 134217728, doubling up to 536870912]\n"
     "	--tune KEY=VALUE,	library tuning knob (ntedit_hip_set_tuning; repeatable; none of them changes a result)\n"
+    "	--qv,	k-mer QV of the draft before and after the polish, against the filter the run polishes with: writes\n"
+    "			<prefix>_qv.tsv (name, len_before, len_after, kmers_before, absent_before, qv_before, kmers_after,\n"
+    "			absent_after, qv_after per contig and a last row #total) and prints one summary line.  The edited contigs are\n"
+    "			built and screened in HBM; no second pass over reads or k-mer database.  Not with --shard\n"
     "	--shard I/N,	polish share I of N of the contigs, split by BASES (greedy longest-first over whole contigs, the\n"
     "			same on every process); writes <prefix>.index.tsv for `python -m ntedit_amd.merge`.\n"
     "			(`python -m ntedit_amd.run` is the full multi-GPU driver: one filter broadcast, large contigs cut)\n"
@@ -123,6 +128,7 @@ enum
 	OPT_BATCH,
 	OPT_SHARD,
 	OPT_REPORT,
+	OPT_QV,
 	OPT_START_GRID,
 	OPT_EVENT_BUDGET,
 	OPT_NO_MAP,
@@ -178,6 +184,7 @@ static const struct option longopts[] = {
 	{ "no-map", no_argument, nullptr, OPT_NO_MAP }, // tests: plain FASTA through the streaming reader as well
 	{ "pack", no_argument, nullptr, OPT_PACK }, // batches cross PCIe in the packed form (off: packing costs the reader stage more than the link saves)
 	{ "report", no_argument, nullptr, OPT_REPORT },
+	{ "qv", no_argument, nullptr, OPT_QV },
 	// --reads (taken out of argv before getopt: it takes one or more files) and the reads filter's options
 	{ "cutoff", required_argument, nullptr, OPT_CUTOFF },
 	{ "solid", no_argument, nullptr, OPT_SOLID },
@@ -467,7 +474,7 @@ main(int argc, char** argv)
 	argc = (int)args.size() - 1;
 	argv = args.data();
 	std::string hist_given, save_bf_given, save_reject_bf_given; // (as given: a round of a cascade puts its k in place of {k})
-	bool counts = false, shard_given = false;
+	bool counts = false, shard_given = false, qv = false;
 	ntedit_hip_reads_options ro = {}; // the reads options as given; refused at the option where the rules say so
 	std::vector<ntedit_hip_reads_rules> rounds(1); // the rules of each round (one, unless -k is a list); zeros without --reads
 	std::vector<std::string> k_list;               // -k K1,K2,...: its k as given, in order
@@ -635,6 +642,9 @@ main(int argc, char** argv)
 		case OPT_REPORT:
 			report = 1;
 			break;
+		case OPT_QV:
+			qv = true;
+			break;
 		case OPT_NO_MAP:
 			no_map = true;
 			break;
@@ -678,6 +688,11 @@ main(int argc, char** argv)
 		die = true;
 	} else {
 		die_unreadable(draft_given);
+	}
+	if (qv && shard_given) {
+		// (before the device is opened and before any file is written)
+		fprintf(stderr, PROGRAM ": error: --qv and --shard: a table per shard would need a merge of its own; run --qv on the whole draft\n");
+		exit(EXIT_FAILURE);
 	}
 	if (ro.k && strchr(ro.k, ',')) {
 		// every refusal of a list of k before the device is opened and before any file is written
@@ -1056,6 +1071,10 @@ main(int argc, char** argv)
 		}
 		// start-up, like the filter load: the context's buffers for the largest batch + one internal warm-up batch, so that
 		// the first polish_batch call costs what the later ones do (ntedit_hip_reserve)
+		if (qv && ntedit_hip_set_apply(ctx, NTEDIT_HIP_APPLY_QV) != 0) {
+			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
+			fatal();
+		}
 		int reserved = ntedit_hip_reserve(ctx, pin_bytes, 1u << 16, 0, no_pack ? NTEDIT_HIP_BASES_HOST : NTEDIT_HIP_BASES_PACKED);
 		if (reserved != 0 && store_held) {
 			// the store is held for the next round: when the polish buffers do not fit beside it, it goes, and the later
@@ -1094,6 +1113,20 @@ main(int argc, char** argv)
 		if (ntedit_hip_write_vcf_header(vcf_path.c_str(), draft.c_str()) != 0) { // ntedit.cpp:2192-2211
 			fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", vcf_path.c_str());
 			fatal();
+		}
+		// --qv: <prefix>_qv.tsv, a row per written contig as the batches come back, "#total" at the end
+		const std::string qv_path = prefix + "_qv.tsv";
+		FILE* qv_f = nullptr;
+		ntedit_hip_qv_row qv_tot;
+		memset(&qv_tot, 0, sizeof qv_tot);
+		double ms_apply = 0, ms_qv_screen = 0, ms_qv_count = 0;
+		if (qv) {
+			qv_f = fopen(qv_path.c_str(), "wb");
+			if (!qv_f) {
+				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", qv_path.c_str());
+				fatal();
+			}
+			fputs(ntedit_hip_qv_header(), qv_f);
 		}
 		ntedit_hip_annot* annot = nullptr;
 		if (!vcf.empty()) {
@@ -1415,6 +1448,26 @@ main(int argc, char** argv)
 						        (unsigned long long)sizes[3 * i + 1], (unsigned long long)sizes[3 * i + 2]);
 					}
 				}
+				if (qv_f) {
+					std::vector<ntedit_hip_qv_row> rows(names.size());
+					std::string line;
+					bool ok = ntedit_hip_result_qv(w->res, rows.data(), (uint32_t)rows.size()) == 0;
+					for (size_t i = 0; ok && i < rows.size(); i++) {
+						line.resize(b.names[i].size() + 256);
+						ok = ntedit_hip_qv_format_row(names[i], &rows[i], k, &line[0], line.size()) == 0 && fputs(line.c_str(), qv_f) >= 0;
+						qv_tot.len_before += rows[i].len_before;
+						qv_tot.len_after += rows[i].len_after;
+						qv_tot.kmers_before += rows[i].kmers_before;
+						qv_tot.absent_before += rows[i].absent_before;
+						qv_tot.kmers_after += rows[i].kmers_after;
+						qv_tot.absent_after += rows[i].absent_after;
+					}
+					if (!ok) {
+						fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", qv_path.c_str());
+						fflush(nullptr);
+						_exit(EXIT_FAILURE);
+					}
+				}
 				ntedit_hip_stats st;
 				ntedit_hip_result_stats(w->res, &st);
 				ms_gpu += st.ms_total;
@@ -1455,6 +1508,14 @@ main(int argc, char** argv)
 				_exit(EXIT_FAILURE);
 			}
 			s_call += std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count();
+			if (qv) {
+				ntedit_hip_apply_stats as;
+				if (ntedit_hip_apply_info(ctx, &as) == 0) {
+					ms_apply += as.ms_apply;
+					ms_qv_screen += as.ms_screen;
+					ms_qv_count += as.ms_count;
+				}
+			}
 			write_q.push(w);
 		}
 		write_q.push(nullptr);
@@ -1473,6 +1534,42 @@ main(int argc, char** argv)
 		auto t1 = std::chrono::steady_clock::now();
 		time(&rawtime);
 		printf("---------- process complete                         : %s", ctime(&rawtime));
+		if (qv_f) {
+			char line[512];
+			bool ok = ntedit_hip_qv_format_row("#total", &qv_tot, k, line, sizeof line) == 0 && fputs(line, qv_f) >= 0;
+			ok = fclose(qv_f) == 0 && ok;
+			if (!ok) {
+				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", qv_path.c_str());
+				exit(EXIT_FAILURE);
+			}
+			auto qv_text = [&](uint64_t absent, uint64_t kmers) {
+				const double q = ntedit_hip_qv_value(absent, kmers, k);
+				char t[32];
+				if (q != q) {
+					return std::string("NA");
+				}
+				snprintf(t, sizeof t, "%.2f", q);
+				return std::string(q > 1e300 ? "inf" : t);
+			};
+			uint64_t occ = 0, slots = 0;
+			uint32_t hn = 0;
+			ntedit_hip_filter_info(ctx, NTEDIT_FILTER_PRIMARY, nullptr, &hn, nullptr, nullptr);
+			double fpr = 0;
+			if (ntedit_hip_filter_occupancy(ctx, NTEDIT_FILTER_PRIMARY, &occ, &slots) == 0 && slots) {
+				fpr = pow((double)occ / (double)slots, (double)hn);
+			}
+			printf("k-mer QV (k=%u): before %s (%llu of %llu k-mers absent), after %s (%llu of %llu); Bloom false positives make "
+			       "`absent' an undercount by about the filter's false-positive rate (occupancy^h = %.3g); table: %s\n",
+			       k, qv_text(qv_tot.absent_before, qv_tot.kmers_before).c_str(), (unsigned long long)qv_tot.absent_before,
+			       (unsigned long long)qv_tot.kmers_before, qv_text(qv_tot.absent_after, qv_tot.kmers_after).c_str(),
+			       (unsigned long long)qv_tot.absent_after, (unsigned long long)qv_tot.kmers_after, fpr, qv_path.c_str());
+		}
+		if (report && qv) {
+			printf("{\"qv\": {\"kmers_before\": %llu, \"absent_before\": %llu, \"kmers_after\": %llu, \"absent_after\": %llu, \"apply_ms\": %.3f, "
+			       "\"screen_ms\": %.3f, \"count_ms\": %.3f}}\n",
+			       (unsigned long long)qv_tot.kmers_before, (unsigned long long)qv_tot.absent_before, (unsigned long long)qv_tot.kmers_after,
+			       (unsigned long long)qv_tot.absent_after, ms_apply, ms_qv_screen, ms_qv_count);
+		}
 		if (report) {
 			double s = std::chrono::duration<double>(t1 - t0).count();
 			printf("{\"bases\": %llu, \"seconds\": %.6f, \"open_outputs_s\": %.3f, \"index_s\": %.3f, \"read_s\": %.3f, \"polish_call_s\": %.3f, \"write_s\": %.3f, \"gpu_ms\": %.3f, \"screen_ms\": %.3f, \"machine_ms\": %.3f, "

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE
+from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, APPLY_EDITED, APPLY_QV
 
 PRIMARY, SECONDARY = 0, 1
 
@@ -147,6 +147,43 @@ class Result:
         recs = np.frombuffer(ctypes.string_at(ed.value, cnt.value * dt.itemsize), dtype=dt).copy()
         need = int((recs["bases_off"].astype(np.int64) + recs["len"]).max())
         return recs, ctypes.string_at(pool.value, need)
+
+    def _result_error(self, what, rc):
+        msg = self._lib.ntedit_hip_result_last_error()
+        raise NtEditHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def edited_device(self, n_contigs):
+        """(device pointer, bytes, offsets u64, lens u32) of the edited contigs in HBM; needs set_apply(APPLY_EDITED)"""
+        ptr, nb = ctypes.c_void_p(), ctypes.c_uint64()
+        offs = np.zeros(max(n_contigs, 1), dtype=np.uint64)
+        lens = np.zeros(max(n_contigs, 1), dtype=np.uint32)
+        rc = self._lib.ntedit_hip_result_edited_device(self._h, ctypes.byref(ptr), ctypes.byref(nb),
+                                                       offs.ctypes.data_as(ctypes.c_void_p),
+                                                       lens.ctypes.data_as(ctypes.c_void_p), n_contigs)
+        if rc:
+            self._result_error("result_edited_device", rc)
+        return ptr.value or 0, nb.value, offs[:n_contigs], lens[:n_contigs]
+
+    def edited(self, n_contigs):
+        """(bytes uint8, offsets u64, lens u32): the edited contigs, downloaded -- entry i is
+        bytes[offsets[i] : offsets[i] + lens[i]], the sequence line of _edited.fa; needs set_apply(APPLY_EDITED)"""
+        _, nb, offs, lens = self.edited_device(n_contigs)
+        buf = np.zeros(max(nb, 1), dtype=np.uint8)
+        need = ctypes.c_uint64()
+        rc = self._lib.ntedit_hip_result_edited(self._h, buf.ctypes.data_as(ctypes.c_void_p), nb, ctypes.byref(need),
+                                                None, None, n_contigs)
+        if rc:
+            self._result_error("result_edited", rc)
+        return buf[:nb], offs, lens
+
+    def qv(self, n_contigs):
+        """one record per entry (dtype _lib.QV_DTYPE): lengths, k-mer starts and absent k-mers before and after;
+        needs set_apply(APPLY_QV)"""
+        rows = np.zeros(max(n_contigs, 1), dtype=np.dtype(QV_DTYPE))
+        rc = self._lib.ntedit_hip_result_qv(self._h, rows.ctypes.data_as(ctypes.c_void_p), n_contigs)
+        if rc:
+            self._result_error("result_qv", rc)
+        return rows[:n_contigs]
 
     def free(self):
         if self._h:
@@ -302,9 +339,45 @@ class Polisher:
         if rc:
             raise NtEditHipError("cannot write %s" % tsv_path)
 
-    def polish_records(self, records, out_prefix, draft_name="", annot_path=None):
+    def set_apply(self, flags):
+        """ntedit_hip_set_apply: 0, APPLY_EDITED (the result keeps the edited contigs in HBM: Result.edited()),
+        APPLY_QV (k-mer counts before and after: Result.qv()) or both, for the polish_batch calls that follow"""
+        self._check(self._lib.ntedit_hip_set_apply(self._h, int(flags)), "set_apply")
+
+    def apply_info(self):
+        """ntedit_hip_apply_info of the last polish_batch: _lib.ApplyStats"""
+        st = _lib.ApplyStats()
+        self._check(self._lib.ntedit_hip_apply_info(self._h, ctypes.byref(st)), "apply_info")
+        return st
+
+    def qv_value(self, absent, kmers, k=None):
+        if k is None:
+            k = self.filter_info(PRIMARY)[0]
+        return self._lib.ntedit_hip_qv_value(int(absent), int(kmers), int(k))
+
+    def write_qv_table(self, path, names, rows, k=None):
+        """<prefix>_qv.tsv: the header, one line per entry, the "#total" row (ntedit_hip_qv_format_row)"""
+        if k is None:
+            k = self.filter_info(PRIMARY)[0]
+        buf = ctypes.create_string_buffer(1 << 16)
+        total = _lib.QvRow()
+        with open(path, "wb") as f:
+            f.write(self._lib.ntedit_hip_qv_header())
+            for name, r in zip(names, rows):
+                row = _lib.QvRow(*[int(r[fld]) for fld, _ in _lib.QvRow._fields_])
+                for fld, _ in _lib.QvRow._fields_:
+                    setattr(total, fld, getattr(total, fld) + getattr(row, fld))
+                if self._lib.ntedit_hip_qv_format_row(bytes(name), ctypes.byref(row), k, buf, len(buf)):
+                    raise NtEditHipError("qv row of %r does not fit" % name)
+                f.write(buf.value)
+            self._lib.ntedit_hip_qv_format_row(b"#total", ctypes.byref(total), k, buf, len(buf))
+            f.write(buf.value)
+        return total
+
+    def polish_records(self, records, out_prefix, draft_name="", annot_path=None, qv=False):
         """readAndCorrect at -t 1 for an in-memory list of (header, sequence): writes
-        <prefix>_edited.fa, <prefix>_changes.tsv and <prefix>_variants.vcf; returns Stats."""
+        <prefix>_edited.fa, <prefix>_changes.tsv and <prefix>_variants.vcf; returns Stats.
+        qv: also <prefix>_qv.tsv, the k-mer QV of every contig before and after (set_apply(APPLY_QV) for this call)."""
         blob, offs, lens, names = pack_batch(records, self.params.min_contig_len)
         tsv = out_prefix + "_changes.tsv"
         fa = out_prefix + "_edited.fa"
@@ -318,8 +391,16 @@ class Polisher:
                 raise NtEditHipError("cannot read %s" % annot_path)
         # (send_packed: the batch crosses PCIe as 4-bit codes + case bits when it can; the renderer keeps the bytes)
         packed = self.pack_bases(blob) if getattr(self, "send_packed", False) and len(blob) else None
-        res = self.polish_batch(blob, offs, lens, packed=packed)
+        if qv:
+            self.set_apply(APPLY_QV)
+        try:
+            res = self.polish_batch(blob, offs, lens, packed=packed)
+        finally:
+            if qv:
+                self.set_apply(0)
         res.write(blob, offs, lens, names, fa, tsv, append=True, vcf_path=vcf, snv=bool(self.params.snv), annot=annot)
+        if qv:
+            self.write_qv_table(out_prefix + "_qv.tsv", names, res.qv(len(names)))
         if annot_path:
             self._lib.ntedit_hip_annot_free(annot)
         st = res.stats()

@@ -259,6 +259,7 @@ def parse(argv=None):
                     help="cut contigs longer than 1.5x this (default: an eighth of a GPU's share, 1-32 Mbp)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--report", action="store_true")
+    ap.add_argument("--qv", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     g = ap.add_argument_group("polishing straight from reads (--reads replaces -r; the options of `ntedit --reads`, "
                               "the same filter; every rank builds its share and holds the whole filter)")
     g.add_argument("--reads", nargs="*", metavar="FILE", help="input reads, FASTA or FASTQ, plain or gzip")
@@ -288,6 +289,9 @@ def parse(argv=None):
     g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
     g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
     args = ap.parse_args(argv)
+    if args.qv:
+        raise Refused("--qv: this driver cuts large contigs into segments, and per-contig rows over cut contigs are out of "
+                      "scope; run `ntedit --qv` on one GPU")
     if reads_mode and args.k_ignored is not None and "," in args.k_ignored:
         raise Refused("-k %s: a list of k (a cascade of polishing rounds) is `ntedit --reads` on one GPU; this driver "
                       "polishes at one k" % args.k_ignored)
