@@ -979,6 +979,47 @@ int ntedit_hip_apply_info(ntedit_hip_ctx* ctx, ntedit_hip_apply_stats* st);
 /* output bytes per workgroup of the applier's copy kernel (tests place edits on both sides of a tile's edge) */
 uint32_t ntedit_hip_apply_tile(void);
 
+/* ---- k-mer completeness of a polish: the draft's distinct k-mers that the filter holds (no counterpart in the reference)
+ * Linear counting on the device.  R is the PRIMARY filter, plain, of 8 x bytes bits and h hashes.  A k-mer
+ * is k bytes of ACGTacgt inside one entry (the `kmers` of ntedit_hip_qv_row); it is present iff its bit in the screening's
+ * absent bitmap is clear (-s 0 semantics: all its h bits are set in R).  Two mark arrays of R's byte size, M[0] (before) and
+ * M[1] (after), start zeroed; marking a present k-mer sets bit filter_slot(R, fh + rh) -- its first probe into R -- of
+ * M[which].  Marking is an OR: M[which] is a function of the SET of present k-mers marked since the last reset, whatever the
+ * batches, their order or the launch geometry.
+ * NTEDIT_HIP_APPLY_SHARED (ntedit_hip_set_apply, beside EDITED and QV): ntedit_hip_polish_batch does everything APPLY_QV
+ * does (ntedit_hip_result_qv still answers only with APPLY_QV), begins the marks if that was not done, and marks the batch
+ * into M[0] and the edited bases into M[1].
+ * The marks belong to the PRIMARY filter they were sized for: every call that gives the slot another filter or releases it
+ * (ntedit_hip_set_filter*, _load_filter_file, _filter_alloc*, the reads and genome builds that allocate PRIMARY) releases
+ * them too; ntedit_hip_destroy frees them.  A counting PRIMARY filter: NTEDIT_E_UNSUPPORTED (its "present" is a threshold
+ * on counters, its slots are no bits); no PRIMARY filter: NTEDIT_E_ARG.  A secondary filter plays no part. */
+#define NTEDIT_HIP_APPLY_SHARED 4u
+int ntedit_hip_shared_begin(ntedit_hip_ctx* ctx); /* allocate + zero M[0], M[1] for the current PRIMARY filter; idempotent */
+int ntedit_hip_shared_reset(ntedit_hip_ctx* ctx); /* zero both, and the counters of ntedit_hip_shared_counts */
+void ntedit_hip_shared_free(ntedit_hip_ctx* ctx);
+/* stand-alone: screens `bases` (a batch: entries + separators; host or device bytes) against PRIMARY the way a batch of
+ * that size is screened, with -s 0 semantics, then marks its present k-mers into M[which] (begins the marks if need be) */
+int ntedit_hip_shared_mark(ntedit_hip_ctx* ctx, int which, const char* bases, uint64_t n, int on_device);
+int ntedit_hip_shared_download(ntedit_hip_ctx* ctx, int which, uint8_t* bits); /* R's byte size */
+typedef struct ntedit_hip_shared_stats
+{
+	uint64_t bits;
+	uint32_t hash_num, k;
+	uint64_t filter_set, shared_set[2]; /* popcounts: R, M[0], M[1] */
+	uint64_t marked_calls;              /* kernel launches since the last reset */
+	float ms_mark[2];                   /* HIP-event time of k_mark, summed since the last reset */
+} ntedit_hip_shared_stats;
+int ntedit_hip_shared_counts(ntedit_hip_ctx* ctx, ntedit_hip_shared_stats* st); /* NTEDIT_E_ARG while there are no marks */
+/* Distinct keys behind `set` occupied slots of `slots`, h slots per key: -(slots / h) * log1p(-set / slots); 0 for set == 0,
+ * +inf for set >= slots, NaN for slots == 0 or h == 0.  shared_kmers = (M's popcount, bits, 1), filter_kmers = (R's popcount,
+ * bits, h), completeness = their ratio (not clipped at 1).  Host arithmetic in double; the only place the formula lives. */
+double ntedit_hip_bloom_cardinality(uint64_t set, uint64_t slots, uint32_t h);
+/* <prefix>_completeness.tsv as the front ends write it: the header line, and one line per stage ("before", "after") --
+ * stage, filter_bits, filter_set, filter_kmers, shared_set, shared_kmers, completeness; estimates rounded to integers, the
+ * completeness a fraction with six decimals, "NA" where a value is not finite. */
+const char* ntedit_hip_completeness_header(void);
+int ntedit_hip_completeness_format_row(const char* stage, const ntedit_hip_shared_stats* st, int which, char* out, uint64_t cap);
+
 /* The reference's candidate tables -- num_tries, polish_bases_array / snv_bases_array, multi_possible_bases (ntedit.cpp:172,
  * 176-199, 203-348) -- as the device code holds them (one GPU thread runs the machine's own candidate_bases /
  * insertion_candidate), as text: "num_tries 0 1 5 21 85 341", "polish A TCG", ..., "snv N ATCG", "multi A A AA AC ...".

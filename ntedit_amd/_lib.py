@@ -149,7 +149,7 @@ class SettleStats(ctypes.Structure):
     _fields_ = [("events_seen", ctypes.c_uint64), ("events_settled", ctypes.c_uint64), ("ms", ctypes.c_float)]
 
 
-APPLY_EDITED, APPLY_QV = 1, 2
+APPLY_EDITED, APPLY_QV, APPLY_SHARED = 1, 2, 4
 
 
 class QvRow(ctypes.Structure):
@@ -165,6 +165,13 @@ class ApplyStats(ctypes.Structure):
     """ntedit_hip_apply_stats"""
     _fields_ = [("ms_apply", ctypes.c_float), ("ms_screen", ctypes.c_float), ("ms_count", ctypes.c_float),
                 ("pieces", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("events_applied", ctypes.c_uint64)]
+
+
+class SharedStats(ctypes.Structure):
+    """ntedit_hip_shared_stats: the popcounts behind the k-mer completeness (ntedit_hip_shared_counts)"""
+    _fields_ = [("bits", ctypes.c_uint64), ("hash_num", ctypes.c_uint32), ("k", ctypes.c_uint32),
+                ("filter_set", ctypes.c_uint64), ("shared_set", ctypes.c_uint64 * 2), ("marked_calls", ctypes.c_uint64),
+                ("ms_mark", ctypes.c_float * 2)]
 
 
 class ReadsParseStats(ctypes.Structure):
@@ -279,6 +286,9 @@ EXPORTS = [
     "ntedit_hip_set_apply", "ntedit_hip_result_edited_device", "ntedit_hip_result_edited",
     "ntedit_hip_result_last_error", "ntedit_hip_result_qv", "ntedit_hip_qv_value", "ntedit_hip_qv_header",
     "ntedit_hip_qv_format_row", "ntedit_hip_apply_info", "ntedit_hip_apply_tile",
+    "ntedit_hip_shared_begin", "ntedit_hip_shared_reset", "ntedit_hip_shared_free", "ntedit_hip_shared_mark",
+    "ntedit_hip_shared_download", "ntedit_hip_shared_counts", "ntedit_hip_bloom_cardinality",
+    "ntedit_hip_completeness_header", "ntedit_hip_completeness_format_row",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -462,5 +472,19 @@ def load():
     lib.ntedit_hip_apply_tile.argtypes = []
     lib.ntedit_hip_apply_tile.restype = u32
     del pu32
+    # the completeness marks (k_mark) and their estimator
+    lib.ntedit_hip_shared_begin.argtypes = [vp]
+    lib.ntedit_hip_shared_reset.argtypes = [vp]
+    lib.ntedit_hip_shared_free.argtypes = [vp]
+    lib.ntedit_hip_shared_free.restype = None
+    lib.ntedit_hip_shared_mark.argtypes = [vp, ctypes.c_int, vp, u64, ctypes.c_int]
+    lib.ntedit_hip_shared_download.argtypes = [vp, ctypes.c_int, vp]
+    lib.ntedit_hip_shared_counts.argtypes = [vp, ctypes.POINTER(SharedStats)]
+    lib.ntedit_hip_bloom_cardinality.argtypes = [u64, u64, u32]
+    lib.ntedit_hip_bloom_cardinality.restype = ctypes.c_double
+    lib.ntedit_hip_completeness_header.argtypes = []
+    lib.ntedit_hip_completeness_header.restype = ctypes.c_char_p
+    lib.ntedit_hip_completeness_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(SharedStats), ctypes.c_int,
+                                                       ctypes.c_char_p, u64]
     _lib = lib
     return lib

@@ -150,6 +150,13 @@ struct ntedit_hip_ctx
 	DevBuf ap_ev, ap_place, ap_range, ap_contig, ap_tabs, ap_pieces, ap_edited, ap_bitmap, ap_rows;
 	hipEvent_t ap_evt[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 	ntedit_hip_apply_stats apply_last = { 0.f, 0.f, 0.f, 0, 0, 0 };
+	// linear counting of the draft's present k-mers (k_mark; ntedit_hip_shared_*): two mark arrays of the PRIMARY filter's
+	// size, before and after; they go when the slot gets another filter (drop_filter)
+	DevBuf sh_marks[2];
+	u64 sh_bytes = 0;                 // the filter's byte size the marks were made for (0: none)
+	u64 sh_calls = 0;                 // k_mark launches since the last reset
+	float sh_ms[2] = { 0.f, 0.f };    // their HIP-event time, per array
+	hipEvent_t sh_evt[4] = { nullptr, nullptr, nullptr, nullptr };
 	u32 cu_count = 256;
 	size_t lds_per_block = 160 * 1024;
 	double alloc_ms = 0.0;            // host time spent in hipFree + hipMalloc of the grow-only buffers (ensure())

@@ -96,7 +96,8 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 	DevBuf* bufs[] = { &c->seq,      &c->bitmap,   &c->block_counts, &c->block_offsets, &c->events,
 		               &c->first_chunk, &c->arena, &c->counters, &c->deferred,     &c->ws_nodes,      &c->ws_ov_pos,
 		               &c->ws_ov_chr, &c->ws_prev, &c->ws_lps, &c->ws_win, &c->runmap, &c->candmap, &c->packed, &c->bin_records, &c->bin_fill, &c->bin_ctl, &c->bin_ovf, &c->bin_state, &c->ev_cover, &c->ev_before, &c->ev_flags, &c->ev_list, &c->ev_bmax, &c->ev_rest,       &c->offs,          &c->lens,
-		               &c->ap_ev, &c->ap_place, &c->ap_range, &c->ap_contig, &c->ap_tabs, &c->ap_pieces, &c->ap_edited, &c->ap_bitmap, &c->ap_rows };
+		               &c->ap_ev, &c->ap_place, &c->ap_range, &c->ap_contig, &c->ap_tabs, &c->ap_pieces, &c->ap_edited, &c->ap_bitmap, &c->ap_rows,
+		               &c->sh_marks[0], &c->sh_marks[1] };
 	for (DevBuf* b : bufs) {
 		release(*b);
 	}
@@ -123,6 +124,11 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 		}
 	}
 	for (auto& e : c->ap_evt) {
+		if (e) {
+			(void)hipEventDestroy(e);
+		}
+	}
+	for (auto& e : c->sh_evt) {
 		if (e) {
 			(void)hipEventDestroy(e);
 		}
@@ -166,6 +172,9 @@ drop_filter(ntedit_hip_ctx* c, int slot)
 	}
 	f = DevFilter();
 	c->dp_valid = false;
+	if (slot == 0) {
+		shared_release(c); // (the completeness marks were this filter's)
+	}
 	return 0;
 }
 

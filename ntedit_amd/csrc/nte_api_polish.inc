@@ -1074,8 +1074,12 @@ PolishRun::apply()
 	int rc;
 	hipStream_t s = c->stream;
 	const u32 k = c->dp.k;
-	if ((flags & NTEDIT_HIP_APPLY_QV) && k > QV_MAX_K) {
+	if ((flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED)) && k > QV_MAX_K) {
 		return fail(c, NTEDIT_E_UNSUPPORTED, "apply: the QV counts take k up to %u", QV_MAX_K);
+	}
+	const bool shared = (flags & NTEDIT_HIP_APPLY_SHARED) != 0;
+	if (shared && (rc = shared_begin(c, "polish_batch"))) { // (the completeness marks: begun here if that was not done)
+		return rc;
 	}
 	for (auto& e : c->ap_evt) {
 		if (!e) {
@@ -1159,29 +1163,15 @@ PolishRun::apply()
 	if (he == hipSuccess) {
 		he = hipMemcpyAsync(r->e_lens.data(), a.out_lens, nc * 4, hipMemcpyDeviceToHost, s);
 	}
-	bool qv = (flags & NTEDIT_HIP_APPLY_QV) != 0;
+	// (APPLY_SHARED runs everything APPLY_QV runs and marks the present k-mers of both screenings: k_mark)
+	bool qv = (flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED)) != 0;
 	int qrc = 0;
 	float ms_rescreen = 0.f;
 	if (he == hipSuccess && qv) {
 		// before: the batch and step 1's bitmap; after: the edited bases, screened the way a batch of that size is.  With
 		// -s 1 step 1 marks every k-mer of accepted bases (k_screen: "no probe decides that"), so c->bitmap is not the plain
 		// answer: both screenings then run with the flag down, the batch's into the second bitmap first.
-		struct PlainScreen
-		{
-			ntedit_hip_ctx* c;
-			int hp_snv;
-			u32 dp_snv;
-			explicit PlainScreen(ntedit_hip_ctx* c_) : c(c_), hp_snv(c_->hp.snv), dp_snv(c_->dp.snv)
-			{
-				c->hp.snv = 0;
-				c->dp.snv = 0;
-			}
-			~PlainScreen()
-			{
-				c->hp.snv = hp_snv;
-				c->dp.snv = dp_snv;
-			}
-		} plain(c);
+		PlainScreen plain(c);
 		const bool rescreen = plain.dp_snv != 0;
 		const u64 nw2 = (total_bytes + 63) / 64;
 		const u64 nw_max = rescreen && n_words > nw2 ? n_words : nw2;
@@ -1208,6 +1198,10 @@ PolishRun::apply()
 				launch_qv_rows(s, rows, a.lens, a.out_lens, n_contigs);
 				launch_qv_count(s, d_seq, n, a.offs, a.lens, n_contigs, bm_before, k, rows, 0);
 				(void)hipEventRecord(c->ap_evt[3], s);
+				// (with -s 1 bm_before is bm2, which the screening below overwrites: the before-mark is queued here)
+				qrc = shared ? launch_mark(c, s, d_seq, n, f0, bm_before, n_words, 0) : 0;
+			}
+			if (!qrc) {
 				qrc = rescreen ? bin_reset(c, s) : 0;
 			}
 			if (!qrc) {
@@ -1224,6 +1218,9 @@ PolishRun::apply()
 				(void)hipEventRecord(c->ap_evt[7], s);
 				r->qv.resize(nc);
 				he = hipMemcpyAsync(r->qv.data(), rows, nc * sizeof(QvRow), hipMemcpyDeviceToHost, s);
+				if (shared && he == hipSuccess) {
+					qrc = launch_mark(c, s, a.out, total_bytes, f0, bm2, nw2, 1);
+				}
 			}
 		}
 	}
@@ -1248,6 +1245,10 @@ PolishRun::apply()
 		(void)hipEventElapsedTime(&t0, c->ap_evt[2], c->ap_evt[3]);
 		(void)hipEventElapsedTime(&t1, c->ap_evt[6], c->ap_evt[7]);
 		as.ms_count = t0 + t1;
+	}
+	if (shared) {
+		mark_timed(c, 0);
+		mark_timed(c, 1);
 	}
 	c->apply_last = as;
 	r->edited_bytes = total_bytes;
@@ -1285,6 +1286,9 @@ ntedit_hip_polish_batch(
 	int rc = refresh_params(c);
 	if (rc) {
 		return rc;
+	}
+	if ((c->apply_flags & NTEDIT_HIP_APPLY_SHARED) && (rc = shared_refuse(c, "polish_batch"))) {
+		return rc; // (a counting filter: before anything is polished)
 	}
 	for (u32 i = 0; i < n_contigs; i++) {
 		if (offsets[i] + lens[i] > n || (i + 1 < n_contigs && offsets[i] + lens[i] >= offsets[i + 1])) {
@@ -1407,8 +1411,14 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		}
 		c->tune.force_rounds = 1;
 		c->tune.no_rounds = 0;
+		// (the warm-up batch is no part of the draft: it leaves no completeness marks; APPLY_QV runs the same screenings)
+		const u32 keep_flags = c->apply_flags;
+		if (keep_flags & NTEDIT_HIP_APPLY_SHARED) {
+			c->apply_flags = (keep_flags & ~NTEDIT_HIP_APPLY_SHARED) | NTEDIT_HIP_APPLY_QV;
+		}
 		ntedit_hip_result* wr = nullptr;
 		rc = ntedit_hip_polish_batch(c, buf.data(), wn, offs.data(), lens.data(), wc, NTEDIT_HIP_BASES_HOST, &wr);
+		c->apply_flags = keep_flags;
 		c->tune = keep;
 		if (wr) {
 			ntedit_hip_result_free(wr);
@@ -1491,7 +1501,7 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		    (rc = ensure(c, c->ap_edited, (size_t)(n + n / 64 + 4096)))) {
 			return rc;
 		}
-		if ((c->apply_flags & NTEDIT_HIP_APPLY_QV) && (rc = ensure(c, c->ap_bitmap, (size_t)(n_words + n_words / 64 + 64) * 8))) {
+		if ((c->apply_flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED)) && (rc = ensure(c, c->ap_bitmap, (size_t)(n_words + n_words / 64 + 64) * 8))) {
 			return rc;
 		}
 	}

@@ -50,7 +50,7 @@ result_refuse(const ntedit_hip_result* r, const char* what)
 int
 ntedit_hip_set_apply(ntedit_hip_ctx* c, uint32_t flags)
 {
-	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV))) {
+	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED))) {
 		return fail(c, NTEDIT_E_ARG, "set_apply: unknown flag");
 	}
 	c->apply_flags = flags;
@@ -137,6 +137,122 @@ uint32_t
 ntedit_hip_apply_tile(void)
 {
 	return APPLY_TILE;
+}
+
+// ---- the completeness marks (k_mark, nte_kernels.hip; the helpers are in nte_api_screen.inc)
+
+int
+ntedit_hip_shared_begin(ntedit_hip_ctx* c)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	return shared_begin(c, "shared_begin");
+}
+
+int
+ntedit_hip_shared_reset(ntedit_hip_ctx* c)
+{
+	if (!c || !c->sh_bytes) {
+		return fail(c, NTEDIT_E_ARG, "shared_reset: no marks (ntedit_hip_shared_begin)");
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	return shared_zero(c);
+}
+
+void
+ntedit_hip_shared_free(ntedit_hip_ctx* c)
+{
+	if (c && hipSetDevice(c->device) == hipSuccess) {
+		(void)hipStreamSynchronize(c->stream);
+		shared_release(c);
+	}
+}
+
+int
+ntedit_hip_shared_mark(ntedit_hip_ctx* c, int which, const char* bases, uint64_t n, int on_device)
+{
+	if (!c || which < 0 || which > 1 || (n && !bases)) {
+		return fail(c, NTEDIT_E_ARG, "shared_mark: bad argument");
+	}
+	if (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) {
+		return fail(c, NTEDIT_E_ARG, "shared_mark: bases must be host or device bytes");
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc = shared_begin(c, "shared_mark");
+	if (rc || (rc = refresh_params(c))) {
+		return rc;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const u64 n_words = (n + 63) / 64;
+	const u8* d_seq = nullptr;
+	if ((rc = stage_bases(c, bases, n, on_device, &d_seq)) || (rc = ensure(c, c->bitmap, (n_words + 8) * 8))) {
+		return rc;
+	}
+	u64* d_bitmap = (u64*)c->bitmap.p;
+	const Filter f0 = dev_filter(c->filt[0]);
+	PlainScreen plain(c);
+	u32 recovered = 0;
+	if ((rc = bin_reset(c, c->stream)) || (rc = launch_screen<false>(c, d_seq, n, f0, d_bitmap, n_words)) ||
+	    (rc = bin_recover(c, c->stream, d_seq, n, f0, d_bitmap, n_words, 0, n, &recovered)) ||
+	    (rc = launch_mark(c, c->stream, d_seq, n, f0, d_bitmap, n_words, which))) {
+		(void)hipStreamSynchronize(c->stream);
+		return rc;
+	}
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	mark_timed(c, which);
+	return 0;
+}
+
+int
+ntedit_hip_shared_download(ntedit_hip_ctx* c, int which, uint8_t* bits)
+{
+	if (!c || which < 0 || which > 1 || !bits || !c->sh_bytes) {
+		return fail(c, NTEDIT_E_ARG, "shared_download: bad argument, or no marks (ntedit_hip_shared_begin)");
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	HIP_TRY(c, hipMemcpy(bits, c->sh_marks[which].p, c->sh_bytes, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int
+ntedit_hip_shared_counts(ntedit_hip_ctx* c, ntedit_hip_shared_stats* st)
+{
+	if (!c || !st || !c->sh_bytes || !c->filt[0].set || c->filt[0].nbytes != c->sh_bytes) {
+		return fail(c, NTEDIT_E_ARG, "shared_counts: bad argument, or no marks (ntedit_hip_shared_begin)");
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	const DevFilter& f = c->filt[0];
+	int rc = ensure(c, c->counters, 256);
+	if (rc) {
+		return rc;
+	}
+	unsigned long long* d_total = (unsigned long long*)c->counters.p;
+	HIP_TRY(c, hipMemsetAsync(d_total, 0, 24, c->stream));
+	const u64 n_words = (f.nbytes + 7) / 8; // (all three allocations are whole 64-bit words, zero behind nbytes)
+	const u64* arrays[3] = { (const u64*)f.data, (const u64*)c->sh_marks[0].p, (const u64*)c->sh_marks[1].p };
+	for (int i = 0; i < 3; i++) {
+		hipLaunchKernelGGL(k_popcount, dim3((unsigned)(c->cu_count * 8)), dim3(256), 0, c->stream, arrays[i], n_words, 0, d_total + i);
+	}
+	HIP_TRY(c, hipGetLastError());
+	unsigned long long h[3] = { 0, 0, 0 };
+	HIP_TRY(c, hipMemcpyAsync(h, d_total, 24, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	memset(st, 0, sizeof *st);
+	st->bits = f.nbytes * 8;
+	st->hash_num = f.hash_num;
+	st->k = f.k;
+	st->filter_set = h[0];
+	st->shared_set[0] = h[1];
+	st->shared_set[1] = h[2];
+	st->marked_calls = c->sh_calls;
+	st->ms_mark[0] = c->sh_ms[0];
+	st->ms_mark[1] = c->sh_ms[1];
+	return 0;
 }
 
 int

@@ -88,6 +88,138 @@ launch_screen(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u64* d
 	return launch_screen_tiles<INSERT>(c, c->stream, d_seq, n, f, d_bitmap, n_words, 0, blocks, 0);
 }
 
+// -s 0 semantics for the screenings of a scope: with -s 1 k_screen marks every k-mer of accepted bases, which is not the
+// filter's answer (the QV counts, the completeness marks)
+struct PlainScreen
+{
+	ntedit_hip_ctx* c;
+	int hp_snv;
+	u32 dp_snv;
+	explicit PlainScreen(ntedit_hip_ctx* c_) : c(c_), hp_snv(c_->hp.snv), dp_snv(c_->dp.snv)
+	{
+		c->hp.snv = 0;
+		c->dp.snv = 0;
+	}
+	~PlainScreen()
+	{
+		c->hp.snv = hp_snv;
+		c->dp.snv = dp_snv;
+	}
+};
+
+// ---- the completeness marks (k_mark): two arrays of the PRIMARY filter's size
+void
+shared_release(ntedit_hip_ctx* c)
+{
+	release(c->sh_marks[0]);
+	release(c->sh_marks[1]);
+	c->sh_bytes = 0;
+	c->sh_calls = 0;
+	c->sh_ms[0] = c->sh_ms[1] = 0.f;
+}
+
+// why the context cannot hold marks (0: it can)
+int
+shared_refuse(ntedit_hip_ctx* c, const char* who)
+{
+	const DevFilter& f = c->filt[0];
+	if (!f.set) {
+		return fail(c, NTEDIT_E_ARG, "%s: no primary Bloom filter to measure completeness against", who);
+	}
+	if (f.counting) {
+		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: completeness takes a plain primary filter; a counting filter's slots are counters", who);
+	}
+	if (f.k > QV_MAX_K) {
+		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: the completeness marks take k up to %u", who, QV_MAX_K);
+	}
+	return 0;
+}
+
+int
+shared_zero(ntedit_hip_ctx* c)
+{
+	const size_t padded = (size_t)((c->sh_bytes + 7) / 8 * 8);
+	for (auto& m : c->sh_marks) {
+		HIP_TRY(c, hipMemsetAsync(m.p, 0, padded, c->stream));
+	}
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	c->sh_calls = 0;
+	c->sh_ms[0] = c->sh_ms[1] = 0.f;
+	return 0;
+}
+
+int
+shared_begin(ntedit_hip_ctx* c, const char* who)
+{
+	int rc = shared_refuse(c, who);
+	if (rc) {
+		return rc;
+	}
+	if (c->sh_bytes) {
+		return 0; // (the marks of this filter: drop_filter releases them with it)
+	}
+	for (auto& e : c->sh_evt) {
+		if (!e) {
+			HIP_TRY(c, hipEventCreate(&e));
+		}
+	}
+	// (whole 64-bit words, as the filter's own allocation: k_popcount reads words, k_mark ORs into 32-bit ones)
+	const size_t padded = (size_t)((c->filt[0].nbytes + 7) / 8 * 8);
+	for (auto& m : c->sh_marks) {
+		release(m);
+		if (hipMalloc(&m.p, padded) != hipSuccess) {
+			(void)hipGetLastError();
+			shared_release(c);
+			return fail(c, NTEDIT_E_DEVICE, "%s: no device memory for two mark arrays of %llu bytes", who, (unsigned long long)padded);
+		}
+		m.cap = padded;
+	}
+	c->sh_bytes = c->filt[0].nbytes;
+	if ((rc = shared_zero(c))) {
+		shared_release(c);
+	}
+	return rc;
+}
+
+// k_mark over a batch and its absent bitmap into M[which], on `stream`, between the two events of that array
+int
+launch_mark(ntedit_hip_ctx* c, hipStream_t stream, const u8* d_seq, u64 n, const Filter& f, const u64* d_bitmap, u64 n_words, int which)
+{
+	const u64 blocks = (n + SCREEN_TILE - 1) / SCREEN_TILE;
+	if (blocks == 0) {
+		return 0;
+	}
+	if (blocks > 0x7FFFFFFFull) {
+		return fail(c, NTEDIT_E_ARG, "batch too large");
+	}
+	if (!c->sh_bytes || c->sh_bytes != c->filt[0].nbytes || f.counting) {
+		return fail(c, NTEDIT_E_INTERNAL, "mark: the marks are not those of the primary filter");
+	}
+	u32* marks = (u32*)c->sh_marks[which].p;
+	HIP_TRY(c, hipEventRecord(c->sh_evt[2 * which], stream));
+	if (f.mask) {
+		hipLaunchKernelGGL((k_mark<true>), dim3((unsigned)blocks), dim3(SCREEN_TPB), 0, stream, d_seq, n, f, c->dp.k, c->d_tab, d_bitmap, n_words, marks);
+	} else {
+		hipLaunchKernelGGL((k_mark<false>), dim3((unsigned)blocks), dim3(SCREEN_TPB), 0, stream, d_seq, n, f, c->dp.k, c->d_tab, d_bitmap, n_words, marks);
+	}
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipEventRecord(c->sh_evt[2 * which + 1], stream));
+	c->sh_calls++;
+	return 0;
+}
+
+// after `stream` has been waited for: the launch's time goes to its array's sum
+void
+mark_timed(ntedit_hip_ctx* c, int which)
+{
+	float ms = 0.f;
+	if (hipEventElapsedTime(&ms, c->sh_evt[2 * which], c->sh_evt[2 * which + 1]) == hipSuccess) {
+		c->sh_ms[which] += ms;
+	} else {
+		(void)hipGetLastError();
+	}
+}
+
 // ---- L2-partitioned ("binned") screening; see nte_kernels.hip / nte_bin_wc.inc
 // screen_mode 1 forces the direct gather kernel, 2 the binned pipeline (tests run it on small inputs); 0 picks:
 // the binned pipeline pays when the filter is far larger than the L2s (the direct kernel then runs at the

@@ -266,6 +266,84 @@ k_screen(
 	}
 }
 
+// -------------------------------------------------------------------- k_mark
+// Linear counting of the batch's PRESENT k-mers (ntedit --completeness): every k-mer of ACGTacgt whose
+// bit in the screening's absent bitmap is clear sets ONE bit, filter_slot(f, fh + rh) -- its first probe into the filter --,
+// in a mark array of the filter's geometry.  k_screen<., ., INSERT>'s tile, staging, look-up table (a code above 3 ends a
+// k-mer) and rolling hash; a lane's 64 starts are exactly word tile * 256 + tid of the bitmap, loaded once.  The store is
+// the reads filter's (nte_reads.hip): a plain read of the containing word, an atomicOr only while the bit is clear --
+// bits only get set, so a stale read costs one atomic more and never skips one; a satellite's one k-mer, repeated
+// millions of times, is read from the L2 and not serialised on its line.  4 starts per iteration: their reads are in
+// flight together.  The result is an OR: it does not depend on batching, order or launch geometry.
+template<bool POW2>
+__global__ __launch_bounds__(SCREEN_TPB) void
+k_mark(const u8* __restrict__ seq, u64 n, Filter f, u32 k, const u64* __restrict__ tabs, const u64* __restrict__ bitmap, u64 n_words, u32* marks)
+{
+	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
+	__shared__ u8 s_lut[256];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[SCREEN_LDS_BYTES];
+
+	const u32 tid = threadIdx.x;
+	const u64 w = (u64)blockIdx.x * SCREEN_TPB + tid;
+	const u64 absent = w < n_words ? bitmap[w] : 0; // (behind the batch nothing is a k-mer)
+	if (tid < TAB_WORDS) {
+		s_tab[tid] = tabs[tid];
+	}
+	{
+		const u8 code = char_code((u8)tid);
+		s_lut[tid] = code > 3 ? CODE_BAD : code;
+	}
+	__syncthreads();
+
+	const u64 tile_base = (u64)blockIdx.x * SCREEN_TILE;
+	stage_tile(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
+	__syncthreads();
+
+	const u32 x0 = tid * SCREEN_L;
+	HashState hs = { 0, 0 };
+	u32 good = 0;
+	for (u32 i = 0; i < k; i++) {
+		const u8 in = s_codes[lds_phys(x0 + i)];
+		hash_roll(hs, s_tab, CODE_BAD, in);
+		good = in == CODE_BAD ? 0 : good + 1;
+	}
+
+	const u32 ksh = (k & 3) * 8;
+	u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[lds_phys((x0 + k) & ~3u)]);
+	for (u32 j0 = 0; j0 < SCREEN_L; j0 += 4) {
+		const u32 outw = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + j0)]);
+		const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[lds_phys(((x0 + j0 + k) & ~3u) + 4)]);
+		const u32 inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
+		in_lo = in_hi;
+
+		u64 slot[4];
+		bool mark[4];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			mark[u] = good >= k && !((absent >> (j0 + u)) & 1);
+			const u64 hv = hs.fh + hs.rh;
+			slot[u] = POW2 ? (hv & f.mask) : filter_slot(f, hv);
+			const u8 out = (outw >> (8 * u)) & 0xFF;
+			const u8 in = (inw >> (8 * u)) & 0xFF;
+			hash_roll(hs, s_tab, out, in);
+			good = in == CODE_BAD ? 0 : good + 1;
+		}
+		u32 seen[4];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			// (a start that marks nothing reads word 0 instead of branching: the four reads stay independent)
+			seen[u] = __hip_atomic_load(marks + (mark[u] ? (slot[u] >> 5) : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const u32 bit = 1u << (slot[u] & 31);
+			if (mark[u] && !(seen[u] & bit)) {
+				atomicOr(marks + (slot[u] >> 5), bit);
+			}
+		}
+	}
+}
+
 // ------------------------------------------------------- binned screening
 // The direct kernel above is bound by the L2-miss path: every 1-byte probe of a multi-GiB filter costs one
 // 64-byte fabric request (~51 G requests/s measured, the same as a pure random-gather micro-benchmark),

@@ -71,6 +71,10 @@ static const char USAGE[] = PROGRAM
     "			<prefix>_qv.tsv (name, len_before, len_after, kmers_before, absent_before, qv_before, kmers_after,\n"
     "			absent_after, qv_after per contig and a last row #total) and prints one summary line.  The edited contigs are\n"
     "			built and screened in HBM; no second pass over reads or k-mer database.  Not with --shard\n"
+    "	--completeness,	with --qv: k-mer completeness before and after the polish -- the share of the filter's k-mers that the\n"
+    "			draft holds, by linear counting of the draft's distinct present k-mers in HBM.  Writes\n"
+    "			<prefix>_completeness.tsv (stage, filter_bits, filter_set, filter_kmers, shared_set, shared_kmers, completeness;\n"
+    "			a row `before' and a row `after') and prints one summary line.  A plain filter only.  Not with --shard\n"
     "	--shard I/N,	polish share I of N of the contigs, split by BASES (greedy longest-first over whole contigs, the\n"
     "			same on every process); writes <prefix>.index.tsv for `python -m ntedit_amd.merge`.\n"
     "			(`python -m ntedit_amd.run` is the full multi-GPU driver: one filter broadcast, large contigs cut)\n"
@@ -129,6 +133,7 @@ enum
 	OPT_SHARD,
 	OPT_REPORT,
 	OPT_QV,
+	OPT_COMPLETENESS,
 	OPT_START_GRID,
 	OPT_EVENT_BUDGET,
 	OPT_NO_MAP,
@@ -185,6 +190,7 @@ static const struct option longopts[] = {
 	{ "pack", no_argument, nullptr, OPT_PACK }, // batches cross PCIe in the packed form (off: packing costs the reader stage more than the link saves)
 	{ "report", no_argument, nullptr, OPT_REPORT },
 	{ "qv", no_argument, nullptr, OPT_QV },
+	{ "completeness", no_argument, nullptr, OPT_COMPLETENESS },
 	// --reads (taken out of argv before getopt: it takes one or more files) and the reads filter's options
 	{ "cutoff", required_argument, nullptr, OPT_CUTOFF },
 	{ "solid", no_argument, nullptr, OPT_SOLID },
@@ -474,7 +480,7 @@ main(int argc, char** argv)
 	argc = (int)args.size() - 1;
 	argv = args.data();
 	std::string hist_given, save_bf_given, save_reject_bf_given; // (as given: a round of a cascade puts its k in place of {k})
-	bool counts = false, shard_given = false, qv = false;
+	bool counts = false, shard_given = false, qv = false, completeness = false;
 	ntedit_hip_reads_options ro = {}; // the reads options as given; refused at the option where the rules say so
 	std::vector<ntedit_hip_reads_rules> rounds(1); // the rules of each round (one, unless -k is a list); zeros without --reads
 	std::vector<std::string> k_list;               // -k K1,K2,...: its k as given, in order
@@ -645,6 +651,9 @@ main(int argc, char** argv)
 		case OPT_QV:
 			qv = true;
 			break;
+		case OPT_COMPLETENESS:
+			completeness = true;
+			break;
 		case OPT_NO_MAP:
 			no_map = true;
 			break;
@@ -688,6 +697,14 @@ main(int argc, char** argv)
 		die = true;
 	} else {
 		die_unreadable(draft_given);
+	}
+	if (completeness && (!qv || shard_given || counts)) {
+		// (before the device is opened and before any file is written)
+		fprintf(stderr, PROGRAM ": error: --completeness%s\n",
+		        !qv           ? ": only with --qv (it marks the k-mers the QV screenings find present)"
+		        : shard_given ? " and --shard: the marks of the shards would need a merge of their own; run it on the whole draft"
+		                      : " and --counts: completeness takes a plain filter; a counting filter's slots are counters");
+		exit(EXIT_FAILURE);
 	}
 	if (qv && shard_given) {
 		// (before the device is opened and before any file is written)
@@ -1014,6 +1031,11 @@ main(int argc, char** argv)
 		ntedit_hip_filter_info(ctx, NTEDIT_FILTER_PRIMARY, &k, &h, &nbytes, &counting);
 		printf("BLOOM::\tcounting: %s\tsize: %llu\tnumber hash functions: %u\tkmer size: %u\n", counting ? "YES" : "NO",
 		       (unsigned long long)nbytes, h, k);
+		if (completeness && counting) {
+			// (before any output file is opened and before a batch is polished)
+			fprintf(stderr, PROGRAM ": error: --completeness: `%s' is a counting filter; completeness takes a plain filter\n", bf.c_str());
+			fatal();
+		}
 		if (!counting && p.min_threshold != 1) {
 			// ntedit.cpp:2453-2458
 			fprintf(stderr, PROGRAM ": warning: Bloom filter is not counting, min k-mer presence threshold will be set to 1.\n");
@@ -1071,7 +1093,12 @@ main(int argc, char** argv)
 		}
 		// start-up, like the filter load: the context's buffers for the largest batch + one internal warm-up batch, so that
 		// the first polish_batch call costs what the later ones do (ntedit_hip_reserve)
-		if (qv && ntedit_hip_set_apply(ctx, NTEDIT_HIP_APPLY_QV) != 0) {
+		if (qv && ntedit_hip_set_apply(ctx, NTEDIT_HIP_APPLY_QV | (completeness ? NTEDIT_HIP_APPLY_SHARED : 0u)) != 0) {
+			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
+			fatal();
+		}
+		// --completeness: the two mark arrays of this round's filter, mapped here and not inside the first batch
+		if (completeness && ntedit_hip_shared_begin(ctx) != 0) {
 			fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
 			fatal();
 		}
@@ -1563,6 +1590,59 @@ main(int argc, char** argv)
 			       k, qv_text(qv_tot.absent_before, qv_tot.kmers_before).c_str(), (unsigned long long)qv_tot.absent_before,
 			       (unsigned long long)qv_tot.kmers_before, qv_text(qv_tot.absent_after, qv_tot.kmers_after).c_str(),
 			       (unsigned long long)qv_tot.absent_after, (unsigned long long)qv_tot.kmers_after, fpr, qv_path.c_str());
+		}
+		if (completeness) {
+			// --completeness: <prefix>_completeness.tsv and one line, from the marks of all batches of this round
+			const std::string cp_path = prefix + "_completeness.tsv";
+			ntedit_hip_shared_stats ss;
+			if (ntedit_hip_shared_counts(ctx, &ss) != 0) {
+				fprintf(stderr, PROGRAM ": error: %s\n", ntedit_hip_last_error(ctx));
+				exit(EXIT_FAILURE);
+			}
+			char rows[2][512];
+			FILE* cf = fopen(cp_path.c_str(), "wb");
+			bool ok = cf != nullptr && ntedit_hip_completeness_format_row("before", &ss, 0, rows[0], sizeof rows[0]) == 0 &&
+			          ntedit_hip_completeness_format_row("after", &ss, 1, rows[1], sizeof rows[1]) == 0 &&
+			          fputs(ntedit_hip_completeness_header(), cf) >= 0 && fputs(rows[0], cf) >= 0 && fputs(rows[1], cf) >= 0;
+			if (cf) {
+				ok = fclose(cf) == 0 && ok;
+			}
+			if (!ok) {
+				fprintf(stderr, PROGRAM ": error: cannot write `%s'\n", cp_path.c_str());
+				exit(EXIT_FAILURE);
+			}
+			const double filter_kmers = ntedit_hip_bloom_cardinality(ss.filter_set, ss.bits, ss.hash_num);
+			const double shared_kmers[2] = { ntedit_hip_bloom_cardinality(ss.shared_set[0], ss.bits, 1),
+				                             ntedit_hip_bloom_cardinality(ss.shared_set[1], ss.bits, 1) };
+			auto share = [&](int w) { // (the ratio of two estimates; NaN where the table says NA)
+				return std::isfinite(filter_kmers) && std::isfinite(shared_kmers[w]) && filter_kmers != 0 ? shared_kmers[w] / filter_kmers : std::nan("");
+			};
+			auto count_text = [](double v) { return std::isfinite(v) ? std::to_string(std::llround(v)) : std::string("NA"); };
+			auto percent_text = [](double v) {
+				char t[32];
+				snprintf(t, sizeof t, "%.4f %%", 100.0 * v);
+				return std::isfinite(v) ? std::string(t) : std::string("NA");
+			};
+			auto json_num = [](double v, const char* fmt) {
+				char t[48];
+				snprintf(t, sizeof t, fmt, v);
+				return std::isfinite(v) ? std::string(t) : std::string("null");
+			};
+			const double fpr = ss.bits ? pow((double)ss.filter_set / (double)ss.bits, (double)ss.hash_num) : 0.0;
+			printf("k-mer completeness (k=%u): before %s (%s of the filter's %s k-mers in the draft), after %s (%s); draft k-mers the filter "
+			       "holds only as false positives are counted too, at most about fpr / (1 - fpr) of the absent k-mers (occupancy^h = %.3g); "
+			       "table: %s\n",
+			       k, percent_text(share(0)).c_str(), count_text(shared_kmers[0]).c_str(), count_text(filter_kmers).c_str(),
+			       percent_text(share(1)).c_str(), count_text(shared_kmers[1]).c_str(), fpr, cp_path.c_str());
+			if (report) {
+				printf("{\"completeness\": {\"filter_bits\": %llu, \"filter_set\": %llu, \"filter_kmers\": %s, \"shared_set_before\": %llu, "
+				       "\"shared_kmers_before\": %s, \"shared_set_after\": %llu, \"shared_kmers_after\": %s, \"completeness_before\": %s, "
+				       "\"completeness_after\": %s, \"ms_mark\": [%.3f, %.3f]}}\n",
+				       (unsigned long long)ss.bits, (unsigned long long)ss.filter_set, json_num(std::round(filter_kmers), "%.0f").c_str(),
+				       (unsigned long long)ss.shared_set[0], json_num(std::round(shared_kmers[0]), "%.0f").c_str(), (unsigned long long)ss.shared_set[1],
+				       json_num(std::round(shared_kmers[1]), "%.0f").c_str(), json_num(share(0), "%.6f").c_str(), json_num(share(1), "%.6f").c_str(),
+				       ss.ms_mark[0], ss.ms_mark[1]);
+			}
 		}
 		if (report && qv) {
 			printf("{\"qv\": {\"kmers_before\": %llu, \"absent_before\": %llu, \"kmers_after\": %llu, \"absent_after\": %llu, \"apply_ms\": %.3f, "

@@ -77,4 +77,55 @@ ntedit_hip_qv_format_row(const char* name, const ntedit_hip_qv_row* row, uint32_
 	return 0;
 }
 
+// ---- k-mer completeness (linear counting: the marks come from k_mark through ntedit_hip_shared_counts)
+
+double
+ntedit_hip_bloom_cardinality(uint64_t set, uint64_t slots, uint32_t h)
+{
+	if (slots == 0 || h == 0) {
+		return std::numeric_limits<double>::quiet_NaN();
+	}
+	if (set == 0) {
+		return 0.0;
+	}
+	if (set >= slots) {
+		return std::numeric_limits<double>::infinity();
+	}
+	return -((double)slots / (double)h) * std::log1p(-(double)set / (double)slots);
+}
+
+const char*
+ntedit_hip_completeness_header(void)
+{
+	return "stage\tfilter_bits\tfilter_set\tfilter_kmers\tshared_set\tshared_kmers\tcompleteness\n";
+}
+
+int
+ntedit_hip_completeness_format_row(const char* stage, const ntedit_hip_shared_stats* st, int which, char* out, uint64_t cap)
+{
+	if (!stage || !st || !out || which < 0 || which > 1) {
+		return NTEDIT_E_ARG;
+	}
+	const double filter_kmers = ntedit_hip_bloom_cardinality(st->filter_set, st->bits, st->hash_num);
+	const double shared_kmers = ntedit_hip_bloom_cardinality(st->shared_set[which], st->bits, 1);
+	const bool both = std::isfinite(filter_kmers) && std::isfinite(shared_kmers) && filter_kmers != 0.0;
+	auto rounded = [](double v) { return std::isfinite(v) ? std::to_string(std::llround(v)) : std::string("NA"); };
+	std::string s(stage);
+	s += '\t' + std::to_string(st->bits) + '\t' + std::to_string(st->filter_set) + '\t' + rounded(filter_kmers);
+	s += '\t' + std::to_string(st->shared_set[which]) + '\t' + rounded(shared_kmers) + '\t';
+	if (both) {
+		char b[64];
+		snprintf(b, sizeof b, "%.6f", shared_kmers / filter_kmers);
+		s += b;
+	} else {
+		s += "NA";
+	}
+	s.push_back('\n');
+	if (s.size() + 1 > cap) {
+		return NTEDIT_E_OVERFLOW;
+	}
+	memcpy(out, s.c_str(), s.size() + 1);
+	return 0;
+}
+
 } // extern "C"

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, APPLY_EDITED, APPLY_QV
+from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, APPLY_EDITED, APPLY_QV, APPLY_SHARED  # noqa: F401
 
 PRIMARY, SECONDARY = 0, 1
 
@@ -341,7 +341,9 @@ class Polisher:
 
     def set_apply(self, flags):
         """ntedit_hip_set_apply: 0, APPLY_EDITED (the result keeps the edited contigs in HBM: Result.edited()),
-        APPLY_QV (k-mer counts before and after: Result.qv()) or both, for the polish_batch calls that follow"""
+        APPLY_QV (k-mer counts before and after: Result.qv()), APPLY_SHARED (what APPLY_QV runs, and the present k-mers
+        of the batch and of the edited bases marked for the completeness: shared_counts()) or any of them together, for
+        the polish_batch calls that follow"""
         self._check(self._lib.ntedit_hip_set_apply(self._h, int(flags)), "set_apply")
 
     def apply_info(self):
@@ -373,6 +375,39 @@ class Polisher:
             self._lib.ntedit_hip_qv_format_row(b"#total", ctypes.byref(total), k, buf, len(buf))
             f.write(buf.value)
         return total
+
+    # ---- k-mer completeness: the draft's distinct k-mers that the PRIMARY filter holds
+    def shared_begin(self):
+        """allocate and zero the two mark arrays (before, after) for the current PRIMARY filter; idempotent"""
+        self._check(self._lib.ntedit_hip_shared_begin(self._h), "shared_begin")
+
+    def shared_reset(self):
+        self._check(self._lib.ntedit_hip_shared_reset(self._h), "shared_reset")
+
+    def shared_free(self):
+        self._lib.ntedit_hip_shared_free(self._h)
+
+    def shared_mark(self, blob, which=0):
+        """screen a host batch (entries + separators) with -s 0 semantics and mark its present k-mers into array `which`"""
+        self._check(self._lib.ntedit_hip_shared_mark(self._h, int(which), ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p),
+                                                     len(blob), 0), "shared_mark")
+
+    def shared_download(self, which=0):
+        """mark array `which` as uint8 bytes of the PRIMARY filter's size"""
+        nb = self.filter_info(PRIMARY)[2]
+        out = np.empty(nb, dtype=np.uint8)
+        self._check(self._lib.ntedit_hip_shared_download(self._h, int(which), out.ctypes.data_as(ctypes.c_void_p)),
+                    "shared_download")
+        return out
+
+    def shared_counts(self):
+        """ntedit_hip_shared_counts: _lib.SharedStats (the popcounts of the filter and of both mark arrays)"""
+        st = _lib.SharedStats()
+        self._check(self._lib.ntedit_hip_shared_counts(self._h, ctypes.byref(st)), "shared_counts")
+        return st
+
+    def bloom_cardinality(self, set_bits, slots, h=1):
+        return self._lib.ntedit_hip_bloom_cardinality(int(set_bits), int(slots), int(h))
 
     def polish_records(self, records, out_prefix, draft_name="", annot_path=None, qv=False):
         """readAndCorrect at -t 1 for an in-memory list of (header, sequence): writes

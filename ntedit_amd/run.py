@@ -260,6 +260,7 @@ def parse(argv=None):
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--qv", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
+    ap.add_argument("--completeness", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     g = ap.add_argument_group("polishing straight from reads (--reads replaces -r; the options of `ntedit --reads`, "
                               "the same filter; every rank builds its share and holds the whole filter)")
     g.add_argument("--reads", nargs="*", metavar="FILE", help="input reads, FASTA or FASTQ, plain or gzip")
@@ -289,6 +290,9 @@ def parse(argv=None):
     g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
     g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
     args = ap.parse_args(argv)
+    if args.completeness:
+        raise Refused("--completeness: the marks of several GPUs would need a merge of their own, which is out of scope; "
+                      "run `ntedit --qv --completeness` on one GPU")
     if args.qv:
         raise Refused("--qv: this driver cuts large contigs into segments, and per-contig rows over cut contigs are out of "
                       "scope; run `ntedit --qv` on one GPU")
