@@ -1,0 +1,637 @@
+// cli_options.cpp -- the `ntedit` command line: its usage text, its option tables, the getopt loop and every refusal that
+// happens before the device is opened and before any file is written.  Nothing here takes a live context.
+//
+// Keeps the reference's command-line surface (ntedit.cpp:135-169, 2276-2364):
+//   -t -f -r -e -b -z -i -d -x -y -X -Y -c -j -m -s -l -a -v -p -q -k --help --version
+// (-k is accepted and ignored: k comes from the Bloom filter header.  The reference lists -k in its
+// option string but has no `case 'k'`, so `-k N` trips its "invalid option" check, ntedit.cpp:2360-2363;
+// being lenient here keeps old command lines working.  -c is parsed and overwritten by k*1.5; -t sets the host
+// threads that render the output, contigs themselves are polished on the GPU and
+// the output order is the input order, i.e. the reference at -t 1).
+#include "cli_options.h"
+#include "cli_common.h"
+#include "k_list.h"
+
+#include <cerrno>
+#include <cstring>
+#include <getopt.h>
+#include <sstream>
+
+namespace nte_cli {
+
+static const char USAGE[] = PROGRAM
+    " (MI355X HIP hot path)\n\n"
+    " Options:\n"
+    "	-t,	number of host threads rendering the output (contigs are polished on the GPU)\n"
+    "	-f,	draft genome assembly (FASTA, Multi-FASTA, and/or gzipped compatible), REQUIRED\n"
+    "	-r,	Bloom filter (BF) or counting BF (CBF) file (btllib format, e.g. from ntStat v1.0.0+), REQUIRED unless --reads\n"
+    "	-e,	secondary BF with k-mers to reject, OPTIONAL\n"
+    "	-b,	output file prefix, OPTIONAL\n"
+    "	-z,	minimum contig length [default=100]\n"
+    "	-i,	maximum number of insertion bases to try, range 0-5, [default=5]\n"
+    "	-d,	maximum number of deletions bases to try, range 0-10, [default=5]\n"
+    "	-x,	k/x ratio for the number of k-mers that should be missing, [default=5.000]\n"
+    "	-y, 	k/y ratio for the number of edited k-mers that should be present, [default=9.000]\n"
+    "	-X, 	ratio of number of k-mers in the k subset that should be missing, [default=0.5]\n"
+    "	-Y, 	ratio of number of k-mers in the k subset that should be present, [default=0.5]\n"
+    "	-c,	cap for the number of base insertions at one position (parsed; k*1.5 is used)\n"
+    "	-j, 	controls size of k-mer subset, check every jth k-mer, [default=3]\n"
+    "	-m,	mode of editing, range 0-2, [default=0]\n"
+    "	-s,     SNV mode. Overrides draft k-mer checks, forcing reassessment at each position (-s 1 = yes, default = 0, no)\n"
+    "	-l,	input VCF file with annotated variants (e.g., clinvar.vcf[.gz]), OPTIONAL\n"
+    "	-a,	soft masks missing k-mer positions having no fix (1 = yes, default = 0, no)\n"
+    "	-v,	verbose mode (accepted)\n"
+    "	-p,	minimum k-mer coverage threshold (CBF only) [default=1]\n"
+    "	-q,	maximum k-mer coverage threshold (CBF only) [default=255]\n"
+    "	--gpu N,	HIP device index [default=0]\n"
+    "	--batch-bases N,	bases per GPU batch [default: the first batch 134217728, doubling up to 536870912]\n"
+    "	--tune KEY=VALUE,	library tuning knob (ntedit_hip_set_tuning; repeatable; none of them changes a result)\n"
+    "	--qv,	k-mer QV of the draft before and after the polish, against the filter the run polishes with: writes\n"
+    "			<prefix>_qv.tsv (name, len_before, len_after, kmers_before, absent_before, qv_before, kmers_after,\n"
+    "			absent_after, qv_after per contig and a last row #total) and prints one summary line.  The edited contigs are\n"
+    "			built and screened in HBM; no second pass over reads or k-mer database.  Not with --shard\n"
+    "	--completeness,	with --qv: k-mer completeness before and after the polish -- the share of the filter's k-mers that the\n"
+    "			draft holds, by linear counting of the draft's distinct present k-mers in HBM.  Writes\n"
+    "			<prefix>_completeness.tsv (stage, filter_bits, filter_set, filter_kmers, shared_set, shared_kmers, completeness;\n"
+    "			a row `before' and a row `after') and prints one summary line.  A plain filter only.  Not with --shard\n"
+    "	--shard I/N,	polish share I of N of the contigs, split by BASES (greedy longest-first over whole contigs, the\n"
+    "			same on every process); writes <prefix>.index.tsv for `python -m ntedit_amd.merge`.\n"
+    "			(`python -m ntedit_amd.run` is the full multi-GPU driver: one filter broadcast, large contigs cut)\n"
+    "\n Polishing straight from reads (--reads replaces -r; the filter is the one ntedit-make-reads-bf builds with the\n"
+    " same settings, built on the GPU into the context that polishes, no filter file needed):\n"
+    "	--reads FILE...,	input reads, FASTA or FASTQ, plain or gzip (1 or more files)\n"
+    "	-k,	k-mer size (bp), 12 to 200, REQUIRED with --reads (accepted and ignored without it)\n"
+    "	-k K1,K2,...,	a list of 2 to 8 different k: polish in a cascade of rounds, in that order (needs -b).  Round i builds\n"
+    "			the filter for Ki and polishes round i-1's _edited.fa; the last round writes <prefix>_edited.fa, an\n"
+    "			earlier one <prefix>_k<Ki>_edited.fa (and _changes.tsv, _variants.vcf).  The read files are parsed\n"
+    "			once: from round 2 on every pass reads the reads kept in HBM.  --hist, --save_bf and\n"
+    "			--save_reject_bf then need {k} in the name (each round puts its k there)\n"
+    "	--cutoff C,	minimum k-mer count of the filter, 1 to 255 (ntedit-make-reads-bf -c)\n"
+    "	--solid,	take the minimum count from the k-mer histogram instead (give --cutoff or --solid)\n"
+    "	--counts,	build a counting filter (enables -p / -q)\n"
+    "	--hashes H,	number of hash functions, 1 to 8 [default=3]\n"
+    "	--fpr F,	false positive rate of the filter (with --num_elements) [default=0.01]\n"
+    "	--bf BYTES,	filter size in bytes\n"
+    "	--num_elements N,	approximate number of solid k-mers (one of --bf / --num_elements is required, unless\n"
+    "			--solid or --hist: then the filter is sized from the k-mer histogram)\n"
+    "	--sketch_bytes S,	counters of the count-min sketch [default: as ntedit-make-reads-bf]\n"
+    "	--hist FILE,	write the k-mer histogram (ntCard's text format)\n"
+    "	--save_bf FILE,	write the filter that was built (the same bytes as ntedit-make-reads-bf -o); its name is the\n"
+    "			_r part of the default prefix [default name: reads_k<K>.bf, not written]\n"
+    "	--gpu_parse,	parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes, BGZF\n"
+    "			still compressed, and the device inflates them (same outputs; single-stream gzip files and files\n"
+    "			outside the clean FASTA / 4-line FASTQ grammar stay with the host parser)\n"
+    "	--reject_cutoff R,	also build the -e filter (k-mers to reject, e.g. repeats) from the same pass over the reads: a\n"
+    "			plain filter of the k-mers seen at least R times, 2 to 255 and above the cutoff (replaces -e;\n"
+    "			not with --counts)\n"
+    "	--reject_bf BYTES,	reject filter size in bytes\n"
+    "	--reject_num_elements N,	approximate number of k-mers in the reject filter (one of the two is required with\n"
+    "			--reject_cutoff, unless --solid or --hist: then it is sized from the k-mer histogram)\n"
+    "	--save_reject_bf FILE,	write the reject filter that was built (the bytes ntedit-make-reads-bf -c R would write)\n"
+    "			[default name: reads_k<K>_reject.bf, not written]\n"
+    "\n Polishing straight from genome assemblies (--genome replaces -r; the filter is the one ntedit-make-genome-bf builds\n"
+    " with the same settings, built on the GPU into the context that polishes, no filter file needed):\n"
+    "	--genome FILE...,	genome FASTA, plain or gzip (1 or more files)\n"
+    "	-k,	k-mer size (bp), 12 to 200, REQUIRED with --genome\n"
+    "	--hashes H, --fpr F,	as above [defaults 3, 0.01]\n"
+    "	--bf BYTES | --num_elements N,	the filter's size [default: from the genome's size, as the tool sizes it]\n"
+    "	--save_bf FILE,	write the filter that was built (the same bytes as ntedit-make-genome-bf -o); its name is the _r\n"
+    "			part of the default prefix [default name: genome_bf.bf, not written]\n"
+    "	--gpu_parse,	parse plain and bgzip-compressed (BGZF) genome FASTA on the GPU, records of any length (same\n"
+    "			outputs; single-stream gzip files stay with the host parser)\n"
+    "	--help,		display this message and exit \n"
+    "	--version,	output version information and exit\n\n";
+
+static const char shortopts[] = "t:f:s:k:z:b:r:v:d:i:X:Y:x:y:m:c:j:s:e:a:l:p:q:";
+enum
+{
+	OPT_HELP = 1000,
+	OPT_VERSION,
+	OPT_GPU,
+	OPT_BATCH,
+	OPT_SHARD,
+	OPT_REPORT,
+	OPT_QV,
+	OPT_COMPLETENESS,
+	OPT_START_GRID,
+	OPT_EVENT_BUDGET,
+	OPT_NO_MAP,
+	OPT_PACK,
+	OPT_TUNE,
+	OPT_CUTOFF,
+	OPT_SOLID,
+	OPT_COUNTS,
+	OPT_HASHES,
+	OPT_FPR,
+	OPT_BF,
+	OPT_NUM_ELEMENTS,
+	OPT_SKETCH_BYTES,
+	OPT_HIST,
+	OPT_SAVE_BF,
+	OPT_REJECT_CUTOFF,
+	OPT_REJECT_BF,
+	OPT_REJECT_NUM_ELEMENTS,
+	OPT_SAVE_REJECT_BF,
+	OPT_READS_BATCH,
+	OPT_STORE_CAP,
+	OPT_GPU_PARSE
+};
+static const struct option longopts[] = {
+	{ "threads", required_argument, nullptr, 't' },
+	{ "draft_file", required_argument, nullptr, 'f' },
+	{ "k", required_argument, nullptr, 'k' },
+	{ "minimum_contig_length", required_argument, nullptr, 'z' },
+	{ "maximum_insertions", required_argument, nullptr, 'i' },
+	{ "maximum_deletions", required_argument, nullptr, 'd' },
+	{ "insertion_cap", required_argument, nullptr, 'c' },
+	{ "edit_threshold", required_argument, nullptr, 'y' },
+	{ "missing_threshold", required_argument, nullptr, 'x' },
+	{ "edit_ratio", required_argument, nullptr, 'Y' },
+	{ "missing_ratio", required_argument, nullptr, 'X' },
+	{ "jump", required_argument, nullptr, 'j' },
+	{ "bloom_filename", required_argument, nullptr, 'r' },
+	{ "bloomrep_filename", required_argument, nullptr, 'e' },
+	{ "outfile_prefix", required_argument, nullptr, 'b' },
+	{ "mode", required_argument, nullptr, 'm' },
+	{ "snv", required_argument, nullptr, 's' },
+	{ "vcf_file", required_argument, nullptr, 'l' },
+	{ "mask", required_argument, nullptr, 'a' },
+	{ "verbose", required_argument, nullptr, 'v' },
+	{ "minimum_kmer_coverage", required_argument, nullptr, 'p' },
+	{ "maximum_kmer_coverage", required_argument, nullptr, 'q' },
+	{ "gpu", required_argument, nullptr, OPT_GPU },
+	{ "batch-bases", required_argument, nullptr, OPT_BATCH },
+	{ "start-grid", required_argument, nullptr, OPT_START_GRID },     // tuning / tests: ntedit_hip_params.start_grid
+	{ "event-budget", required_argument, nullptr, OPT_EVENT_BUDGET }, // tuning / tests: ntedit_hip_params.event_budget
+	{ "shard", required_argument, nullptr, OPT_SHARD },
+	{ "tune", required_argument, nullptr, OPT_TUNE },                 // tuning / tests: ntedit_hip_set_tuning key=value (repeatable)
+	{ "no-map", no_argument, nullptr, OPT_NO_MAP }, // tests: plain FASTA through the streaming reader as well
+	{ "pack", no_argument, nullptr, OPT_PACK }, // batches cross PCIe in the packed form (off: packing costs the reader stage more than the link saves)
+	{ "report", no_argument, nullptr, OPT_REPORT },
+	{ "qv", no_argument, nullptr, OPT_QV },
+	{ "completeness", no_argument, nullptr, OPT_COMPLETENESS },
+	// --reads (taken out of argv before getopt: it takes one or more files) and the reads filter's options
+	{ "cutoff", required_argument, nullptr, OPT_CUTOFF },
+	{ "solid", no_argument, nullptr, OPT_SOLID },
+	{ "counts", no_argument, nullptr, OPT_COUNTS },
+	{ "hashes", required_argument, nullptr, OPT_HASHES },
+	{ "fpr", required_argument, nullptr, OPT_FPR },
+	{ "bf", required_argument, nullptr, OPT_BF },
+	{ "num_elements", required_argument, nullptr, OPT_NUM_ELEMENTS },
+	{ "sketch_bytes", required_argument, nullptr, OPT_SKETCH_BYTES },
+	{ "hist", required_argument, nullptr, OPT_HIST },
+	{ "save_bf", required_argument, nullptr, OPT_SAVE_BF },
+	{ "reject_cutoff", required_argument, nullptr, OPT_REJECT_CUTOFF },
+	{ "reject_bf", required_argument, nullptr, OPT_REJECT_BF },
+	{ "reject_num_elements", required_argument, nullptr, OPT_REJECT_NUM_ELEMENTS },
+	{ "save_reject_bf", required_argument, nullptr, OPT_SAVE_REJECT_BF },
+	{ "batch_bytes", required_argument, nullptr, OPT_READS_BATCH }, // tests: many small read batches
+	{ "resident_cap", required_argument, nullptr, OPT_STORE_CAP }, // tests: the resident store's cap (0: off)
+	{ "gpu_parse", no_argument, nullptr, OPT_GPU_PARSE },
+	{ "help", no_argument, nullptr, OPT_HELP },
+	{ "version", no_argument, nullptr, OPT_VERSION },
+	{ nullptr, 0, nullptr, 0 }
+};
+
+// The options of the reads filter, each named once: `with_genome` says that --genome shares it (genome_rules and the "only
+// with --reads [or --genome]" message read that), `text` is where an option with a value leaves it for the library's rules
+// (reads_options.cpp), which refuse at the option what they refuse there.
+struct ReadsOption
+{
+	int opt;
+	const char* name;
+	bool with_genome;
+	const char* ntedit_hip_reads_options::* text;
+};
+static const ReadsOption READS_OPTIONS[] = {
+	{ OPT_CUTOFF, "--cutoff", false, &ntedit_hip_reads_options::cutoff },
+	{ OPT_SOLID, "--solid", false, nullptr },
+	{ OPT_COUNTS, "--counts", false, nullptr },
+	{ OPT_HASHES, "--hashes", true, &ntedit_hip_reads_options::hashes },
+	{ OPT_FPR, "--fpr", true, &ntedit_hip_reads_options::fpr },
+	{ OPT_BF, "--bf", true, &ntedit_hip_reads_options::bf },
+	{ OPT_NUM_ELEMENTS, "--num_elements", true, &ntedit_hip_reads_options::num_elements },
+	{ OPT_SKETCH_BYTES, "--sketch_bytes", false, &ntedit_hip_reads_options::sketch_bytes },
+	{ OPT_HIST, "--hist", false, nullptr },
+	{ OPT_SAVE_BF, "--save_bf", true, nullptr },
+	{ OPT_REJECT_CUTOFF, "--reject_cutoff", false, &ntedit_hip_reads_options::reject_cutoff },
+	{ OPT_REJECT_BF, "--reject_bf", false, &ntedit_hip_reads_options::reject_bf },
+	{ OPT_REJECT_NUM_ELEMENTS, "--reject_num_elements", false, &ntedit_hip_reads_options::reject_num_elements },
+	{ OPT_SAVE_REJECT_BF, "--save_reject_bf", false, nullptr },
+	{ OPT_READS_BATCH, "--batch_bytes", true, &ntedit_hip_reads_options::batch_bytes },
+	{ OPT_STORE_CAP, "--resident_cap", false, &ntedit_hip_reads_options::store_cap },
+	{ OPT_GPU_PARSE, "--gpu_parse", true, nullptr },
+};
+
+static void
+die_unreadable(const std::string& path)
+{
+	// ntedit.cpp:476-483
+	if (access(path.c_str(), R_OK) == -1) {
+		fail("`%s': %s", path.c_str(), strerror(errno));
+	}
+}
+
+template<typename T>
+static void
+parse(int c, const char* arg, T& out)
+{
+	std::istringstream ss(arg ? arg : "");
+	ss >> out;
+	if (arg && (!ss.eof() || ss.fail())) {
+		fail_plain("invalid option: `-%c%s'", (char)c, arg); // ntedit.cpp:2360-2363
+	}
+}
+
+static void
+refuse(const std::string& why)
+{
+	fail("%s\nTry `" PROGRAM " --help' for more information.", why.c_str());
+}
+
+// the reads options through the library's rules (reads_options.cpp); a refusal ends the run, in the words and the form it
+// always had: a malformed number as getopt's invalid options are
+static ntedit_hip_reads_rules
+reads_rules(const ntedit_hip_reads_options& ro, int final)
+{
+	ntedit_hip_reads_rules rr;
+	const int rc = ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_POLISHER, final, &rr);
+	if (rc == NTEDIT_READS_NOT_A_NUMBER) {
+		fail_plain("%s", ntedit_hip_reads_last_error(nullptr));
+	}
+	if (rc != 0) {
+		refuse(ntedit_hip_reads_last_error(nullptr));
+	}
+	return rr;
+}
+
+// The rules of ntedit --genome, apart from the reads options' (reads_options.cpp knows nothing of them).  The numbers arrive
+// well-formed (reads_rules refuses a malformed one at its option); -k is checked here.  Returns the refusal, or "" and the
+// settings.
+static std::string
+genome_rules(const CliOptions& o, const std::vector<const ReadsOption*>& given, GenomeRules* g)
+{
+	const ntedit_hip_reads_options& ro = o.ro;
+	if (!o.bf.empty()) {
+		return "--genome and -r: give one of them (--genome builds the filter that -r would load)";
+	}
+	if (o.reads_mode) {
+		return "--genome and --reads: give one of them (each builds the filter that -r would load)";
+	}
+	if (o.shard_given) {
+		return "--genome and --shard: every shard would build the whole filter again; build it once with "
+		       "ntedit-make-genome-bf and give each shard -r";
+	}
+	if (o.genome_files.empty()) {
+		return "--genome: 1 or more files expected";
+	}
+	for (const ReadsOption* r : given) {
+		if (!r->with_genome) {
+			return std::string(r->name) + ": only with --reads (--genome builds the plain filter of every k-mer of the assemblies)";
+		}
+	}
+	if (!ro.k) {
+		return "-k: required with --genome";
+	}
+	char* end = nullptr;
+	const unsigned long long k = strtoull(ro.k, &end, 10);
+	if (!*ro.k || *end || ro.k[0] == '-' || k < 12 || k > 200) {
+		return std::string("-k ") + ro.k + ": k must be between 12 and 200";
+	}
+	g->k = (uint32_t)k;
+	if (ro.hashes) {
+		const unsigned long long h = strtoull(ro.hashes, nullptr, 10);
+		if (h < 1 || h > 8) {
+			return "--hashes " + std::to_string(h) + ": the number of hash functions must be between 1 and 8";
+		}
+		g->hash_num = (uint32_t)h;
+	}
+	if (ro.fpr) {
+		g->fpr = strtod(ro.fpr, nullptr);
+	}
+	if (ro.bf) {
+		g->have_bf = true;
+		g->bf_bytes = strtoull(ro.bf, nullptr, 10);
+	}
+	if (ro.num_elements) {
+		g->have_ne = true;
+		g->num_elements = strtoull(ro.num_elements, nullptr, 10);
+	}
+	if ((g->have_bf && g->bf_bytes == 0) ||
+	    (!g->have_bf && g->have_ne && ntedit_hip_reads_bf_size(g->num_elements, g->hash_num, g->fpr) == 0)) {
+		return "--bf / --num_elements: the filter would be empty";
+	}
+	if (ro.batch_bytes) {
+		g->batch_bytes = strtoull(ro.batch_bytes, nullptr, 10);
+		if (g->batch_bytes == 0) {
+			return "--batch_bytes: at least 1";
+		}
+	}
+	g->gpu_parse = ro.gpu_parse ? 1 : 0;
+	return "";
+}
+
+// --reads FILE... and --genome FILE...: the files up to the next option, taken out of argv (getopt takes one argument per
+// option); returns what is left for getopt
+static std::vector<char*>
+take_file_lists(int argc, char** argv, CliOptions* o)
+{
+	std::vector<char*> args;
+	for (int i = 0; i < argc; i++) {
+		const bool reads = i > 0 && strcmp(argv[i], "--reads") == 0, genome = i > 0 && strcmp(argv[i], "--genome") == 0;
+		if (!reads && !genome) {
+			args.push_back(argv[i]);
+			continue;
+		}
+		(reads ? o->reads_mode : o->genome_mode) = true;
+		while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] != 0)) {
+			(reads ? o->read_files : o->genome_files).push_back(argv[++i]);
+		}
+	}
+	args.push_back(nullptr);
+	return args;
+}
+
+// --tune KEY=VALUE (the value through the option parser: trailing garbage is an error, not a silent 0)
+static void
+parse_tune(const char* arg, CliOptions* o)
+{
+	const char* eq = strchr(arg, '=');
+	unsigned long long tv = 0;
+	std::istringstream ss(eq ? eq + 1 : "");
+	ss >> tv;
+	if (!eq || eq == arg || !ss.eof() || ss.fail() || eq[1] == '-') {
+		fail_plain("invalid option: `--tune %s'", arg);
+	}
+	o->tunes.emplace_back(std::string(arg, eq - arg), tv);
+}
+
+// the getopt loop; returns whether getopt met an option it does not know.  `given`: the reads options, in the order given
+static bool
+parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOption*>* given)
+{
+	bool die = false;
+	unsigned ignored_u = 0;
+	ntedit_hip_params& p = o->params;
+	for (int c; (c = getopt_long(argc, argv, shortopts, longopts, nullptr)) != -1;) {
+		for (const ReadsOption& r : READS_OPTIONS) {
+			if (r.opt == c) {
+				given->push_back(&r);
+				if (r.text) {
+					o->ro.*r.text = optarg;
+					reads_rules(o->ro, 0);
+				}
+			}
+		}
+		switch (c) {
+		case '?':
+			die = true;
+			break;
+		case 't':
+			parse(c, optarg, o->nthreads);
+			o->threads_given = true;
+			break;
+		case 'f':
+			parse(c, optarg, o->draft);
+			break;
+		case 'z':
+			parse(c, optarg, p.min_contig_len);
+			break;
+		case 'b':
+			parse(c, optarg, o->prefix);
+			break;
+		case 'r':
+			parse(c, optarg, o->bf);
+			break;
+		case 'e':
+			parse(c, optarg, o->bfrep);
+			break;
+		case 'd':
+			parse(c, optarg, p.max_deletions);
+			break;
+		case 'i':
+			parse(c, optarg, p.max_insertions);
+			break;
+		case 'x':
+			parse(c, optarg, p.missing_threshold);
+			break;
+		case 'y':
+			parse(c, optarg, p.edit_threshold);
+			break;
+		case 'X':
+			parse(c, optarg, p.missing_ratio);
+			p.use_ratio = 1;
+			break;
+		case 'Y':
+			parse(c, optarg, p.edit_ratio);
+			p.use_ratio = 1;
+			break;
+		case 'c':
+			parse(c, optarg, ignored_u); // overwritten by k*1.5 (ntedit.cpp:2450)
+			break;
+		case 'j':
+			parse(c, optarg, p.jump);
+			break;
+		case 'm':
+			parse(c, optarg, p.mode);
+			break;
+		case 's':
+			parse(c, optarg, p.snv);
+			break;
+		case 'l':
+			parse(c, optarg, o->vcf);
+			break;
+		case 'a':
+			parse(c, optarg, p.mask);
+			break;
+		case 'v':
+			parse(c, optarg, o->verbose);
+			break;
+		case 'p':
+			parse(c, optarg, p.min_threshold);
+			break;
+		case 'q':
+			parse(c, optarg, p.max_threshold);
+			break;
+		case 'k':
+			// without --reads: accepted and ignored (the reference rejects it: no `case 'k'`, ntedit.cpp:2360-2363)
+			o->ro.k = optarg;
+			break;
+		case OPT_SOLID:
+			o->ro.solid = 1;
+			break;
+		case OPT_COUNTS:
+			o->counts = true;
+			break;
+		case OPT_HIST:
+			o->hist = optarg;
+			o->ro.hist = 1;
+			break;
+		case OPT_SAVE_BF:
+			o->save_bf = optarg;
+			break;
+		case OPT_SAVE_REJECT_BF:
+			o->save_reject_bf = optarg;
+			o->ro.reject_out = 1;
+			break;
+		case OPT_GPU_PARSE:
+			o->ro.gpu_parse = 1;
+			break;
+		case OPT_GPU:
+			parse(c, optarg, o->gpu);
+			break;
+		case OPT_BATCH:
+			parse(c, optarg, o->batch_bases);
+			o->batch_given = true;
+			break;
+		case OPT_START_GRID:
+			parse(c, optarg, p.start_grid);
+			break;
+		case OPT_EVENT_BUDGET:
+			parse(c, optarg, p.event_budget);
+			break;
+		case OPT_SHARD:
+			if (sscanf(optarg, "%u/%u", &o->shard_i, &o->shard_n) != 2 || o->shard_n == 0 || o->shard_i >= o->shard_n) {
+				fail_plain("invalid option: `--shard %s'", optarg);
+			}
+			o->shard_given = true;
+			break;
+		case OPT_REPORT:
+			o->report = 1;
+			break;
+		case OPT_QV:
+			o->qv = true;
+			break;
+		case OPT_COMPLETENESS:
+			o->completeness = true;
+			break;
+		case OPT_NO_MAP:
+			o->no_map = true;
+			break;
+		case OPT_PACK:
+			o->no_pack = false;
+			break;
+		case OPT_TUNE:
+			parse_tune(optarg, o);
+			break;
+		case OPT_HELP:
+			fputs(USAGE, stderr);
+			exit(EXIT_SUCCESS);
+		case OPT_VERSION:
+			fputs(PROGRAM " (MI355X HIP hot path)\n", stderr);
+			exit(EXIT_SUCCESS);
+		default:
+			break;
+		}
+	}
+	return die;
+}
+
+// every refusal of --reads, and the rules of each round
+static void
+reads_mode_rules(CliOptions* o, const std::vector<std::string>& k_list)
+{
+	if (!o->bf.empty()) {
+		refuse("--reads and -r: give one of them (--reads builds the filter that -r would load)");
+	}
+	if (o->read_files.empty()) {
+		refuse("--reads: 1 or more files expected");
+	}
+	if (o->shard_given) {
+		refuse("--reads and --shard: every shard would build the whole filter again; build it once with "
+		       "ntedit-make-reads-bf and give each shard -r");
+	}
+	if (o->ro.reject_cutoff && !o->bfrep.empty()) {
+		refuse("--reject_cutoff and -e: give one of them (--reject_cutoff builds the filter that -e would load)");
+	}
+	for (const std::string& r : o->read_files) {
+		o->paths.push_back(r.c_str());
+	}
+	o->ro.counts = o->counts;
+	o->ro.files = o->paths.data(); // (for the default sketch: their sizes)
+	o->ro.n_files = (uint32_t)o->paths.size();
+	if (k_list.empty()) {
+		o->rounds[0] = reads_rules(o->ro, 1);
+	} else {
+		// (every option but -k applies to every round alike; sizes taken from the histogram are found per round)
+		o->rounds.clear();
+		for (const std::string& kt : k_list) {
+			ntedit_hip_reads_options one = o->ro;
+			one.k = kt.c_str();
+			o->rounds.push_back(reads_rules(one, 1));
+		}
+	}
+	for (const std::string& r : o->read_files) {
+		die_unreadable(r);
+	}
+}
+
+CliOptions
+parse_cli(int argc, char** argv)
+{
+	CliOptions o;
+	ntedit_hip_params_default(&o.params);
+	std::vector<char*> args = take_file_lists(argc, argv, &o);
+	std::vector<const ReadsOption*> given; // reads options given (refused without --reads)
+	bool die = parse_options((int)args.size() - 1, args.data(), &o, &given);
+	printf("---------- initializing                             : %s", now_text());
+	if (o.draft.empty()) {
+		fprintf(stderr, PROGRAM ": error: need to specify assembly draft file (-f)\n");
+		die = true;
+	} else {
+		die_unreadable(o.draft);
+	}
+	if (o.completeness && (!o.qv || o.shard_given || o.counts)) {
+		fail("--completeness%s",
+		     !o.qv           ? ": only with --qv (it marks the k-mers the QV screenings find present)"
+		     : o.shard_given ? " and --shard: the marks of the shards would need a merge of their own; run it on the whole draft"
+		                     : " and --counts: completeness takes a plain filter; a counting filter's slots are counters");
+	}
+	if (o.qv && o.shard_given) {
+		fail("--qv and --shard: a table per shard would need a merge of its own; run --qv on the whole draft");
+	}
+	std::vector<std::string> k_list; // -k K1,K2,...: its k as given, in order
+	if (o.ro.k && strchr(o.ro.k, ',')) {
+		const std::string why = nte_host::k_list_rules(
+		    o.ro.k, o.reads_mode, o.shard_given, !o.prefix.empty(),
+		    { { "--save_bf", o.save_bf }, { "--save_reject_bf", o.save_reject_bf }, { "--hist", o.hist } }, &k_list);
+		if (!why.empty()) {
+			refuse(why);
+		}
+	}
+	if (o.genome_mode) {
+		const std::string why = genome_rules(o, given, &o.genome);
+		if (!why.empty()) {
+			refuse(why);
+		}
+		for (const std::string& g : o.genome_files) {
+			die_unreadable(g);
+			o.paths.push_back(g.c_str());
+		}
+	} else if (o.reads_mode) {
+		reads_mode_rules(&o, k_list);
+	} else if (!given.empty()) {
+		// (the options --genome shares with --reads say so)
+		refuse(std::string(given[0]->name) + (given[0]->with_genome ? ": only with --reads or --genome" : ": only with --reads"));
+	} else if (o.bf.empty()) {
+		fprintf(stderr, PROGRAM ": error: need to specify the Bloom filter file (-r)\n");
+		die = true;
+	} else {
+		die_unreadable(o.bf);
+	}
+	if (!o.bfrep.empty()) {
+		die_unreadable(o.bfrep);
+	}
+	if (die) {
+		fprintf(stderr, "Try `" PROGRAM " --help' for more information.\n");
+		exit(EXIT_FAILURE);
+	}
+	if (o.params.snv) {
+		// ntedit.cpp:2411-2417
+		fprintf(stderr, "\nSNV mode ON\nTracking all single-base variants\nNote: -i and -d both set to 0 when -s is set to 1\n"
+		                "Consider -l clinvar.vcf to identify SNVs with putative clinical significance\n\n");
+	}
+	return o;
+}
+
+} // namespace nte_cli

@@ -1,0 +1,160 @@
+// cli_report.cpp -- see cli_report.h
+#include "cli_report.h"
+#include "cli_common.h"
+
+#include <cmath>
+
+namespace nte_cli {
+
+void
+RoundTotals::add(const ntedit_hip_stats& st)
+{
+	ms_gpu += st.ms_total;
+	ms_screen += st.ms_screen;
+	n_batches_binned += st.screen_binned ? 1 : 0;
+	n_batches_direct += st.screen_binned ? 0 : 1;
+	n_chunks_direct += st.screen_chunks_direct;
+	n_ovf_records += st.screen_overflow_records;
+	ms_machine += st.ms_machine;
+	events.events += st.events;
+	events.events_applied += st.events_applied;
+	events.absent_kmers += st.absent_kmers;
+	events.substitutions += st.substitutions;
+	events.insertions += st.insertions;
+	events.deletions += st.deletions;
+}
+
+void
+RoundTotals::add(const ntedit_hip_qv_row& row)
+{
+	qv.len_before += row.len_before;
+	qv.len_after += row.len_after;
+	qv.kmers_before += row.kmers_before;
+	qv.absent_before += row.absent_before;
+	qv.kmers_after += row.kmers_after;
+	qv.absent_after += row.absent_after;
+}
+
+static std::string
+qv_text(uint64_t absent, uint64_t kmers, uint32_t k)
+{
+	const double q = ntedit_hip_qv_value(absent, kmers, k);
+	char t[32];
+	if (q != q) {
+		return "NA";
+	}
+	snprintf(t, sizeof t, "%.2f", q);
+	return q > 1e300 ? "inf" : t;
+}
+
+static std::string
+count_text(double v)
+{
+	return std::isfinite(v) ? std::to_string(std::llround(v)) : std::string("NA");
+}
+
+static std::string
+percent_text(double v)
+{
+	char t[32];
+	snprintf(t, sizeof t, "%.4f %%", 100.0 * v);
+	return std::isfinite(v) ? std::string(t) : std::string("NA");
+}
+
+static std::string
+json_num(double v, const char* fmt)
+{
+	char t[48];
+	snprintf(t, sizeof t, fmt, v);
+	return std::isfinite(v) ? std::string(t) : std::string("null");
+}
+
+void
+finish_qv(ntedit_hip_ctx* ctx, FILE* qv_f, const std::string& qv_path, uint32_t k, const RoundTotals& t)
+{
+	char line[512];
+	bool ok = ntedit_hip_qv_format_row("#total", &t.qv, k, line, sizeof line) == 0 && fputs(line, qv_f) >= 0;
+	ok = fclose(qv_f) == 0 && ok;
+	if (!ok) {
+		fail("cannot write `%s'", qv_path.c_str());
+	}
+	uint64_t occ = 0, slots = 0;
+	uint32_t hn = 0;
+	ntedit_hip_filter_info(ctx, NTEDIT_FILTER_PRIMARY, nullptr, &hn, nullptr, nullptr);
+	double fpr = 0;
+	if (ntedit_hip_filter_occupancy(ctx, NTEDIT_FILTER_PRIMARY, &occ, &slots) == 0 && slots) {
+		fpr = pow((double)occ / (double)slots, (double)hn);
+	}
+	printf("k-mer QV (k=%u): before %s (%llu of %llu k-mers absent), after %s (%llu of %llu); Bloom false positives make "
+	       "`absent' an undercount by about the filter's false-positive rate (occupancy^h = %.3g); table: %s\n",
+	       k, qv_text(t.qv.absent_before, t.qv.kmers_before, k).c_str(), (unsigned long long)t.qv.absent_before,
+	       (unsigned long long)t.qv.kmers_before, qv_text(t.qv.absent_after, t.qv.kmers_after, k).c_str(),
+	       (unsigned long long)t.qv.absent_after, (unsigned long long)t.qv.kmers_after, fpr, qv_path.c_str());
+}
+
+void
+finish_completeness(ntedit_hip_ctx* ctx, const std::string& prefix, uint32_t k, bool report)
+{
+	const std::string cp_path = prefix + "_completeness.tsv";
+	ntedit_hip_shared_stats ss;
+	if (ntedit_hip_shared_counts(ctx, &ss) != 0) {
+		fail("%s", ntedit_hip_last_error(ctx));
+	}
+	char rows[2][512];
+	FILE* cf = fopen(cp_path.c_str(), "wb");
+	bool ok = cf != nullptr && ntedit_hip_completeness_format_row("before", &ss, 0, rows[0], sizeof rows[0]) == 0 &&
+	          ntedit_hip_completeness_format_row("after", &ss, 1, rows[1], sizeof rows[1]) == 0 &&
+	          fputs(ntedit_hip_completeness_header(), cf) >= 0 && fputs(rows[0], cf) >= 0 && fputs(rows[1], cf) >= 0;
+	if (cf) {
+		ok = fclose(cf) == 0 && ok;
+	}
+	if (!ok) {
+		fail("cannot write `%s'", cp_path.c_str());
+	}
+	const double filter_kmers = ntedit_hip_bloom_cardinality(ss.filter_set, ss.bits, ss.hash_num);
+	const double shared_kmers[2] = { ntedit_hip_bloom_cardinality(ss.shared_set[0], ss.bits, 1),
+		                             ntedit_hip_bloom_cardinality(ss.shared_set[1], ss.bits, 1) };
+	auto share = [&](int w) { // (the ratio of two estimates; NaN where the table says NA)
+		return std::isfinite(filter_kmers) && std::isfinite(shared_kmers[w]) && filter_kmers != 0 ? shared_kmers[w] / filter_kmers : std::nan("");
+	};
+	const double fpr = ss.bits ? pow((double)ss.filter_set / (double)ss.bits, (double)ss.hash_num) : 0.0;
+	printf("k-mer completeness (k=%u): before %s (%s of the filter's %s k-mers in the draft), after %s (%s); draft k-mers the filter "
+	       "holds only as false positives are counted too, at most about fpr / (1 - fpr) of the absent k-mers (occupancy^h = %.3g); "
+	       "table: %s\n",
+	       k, percent_text(share(0)).c_str(), count_text(shared_kmers[0]).c_str(), count_text(filter_kmers).c_str(),
+	       percent_text(share(1)).c_str(), count_text(shared_kmers[1]).c_str(), fpr, cp_path.c_str());
+	if (report) {
+		printf("{\"completeness\": {\"filter_bits\": %llu, \"filter_set\": %llu, \"filter_kmers\": %s, \"shared_set_before\": %llu, "
+		       "\"shared_kmers_before\": %s, \"shared_set_after\": %llu, \"shared_kmers_after\": %s, \"completeness_before\": %s, "
+		       "\"completeness_after\": %s, \"ms_mark\": [%.3f, %.3f]}}\n",
+		       (unsigned long long)ss.bits, (unsigned long long)ss.filter_set, json_num(std::round(filter_kmers), "%.0f").c_str(),
+		       (unsigned long long)ss.shared_set[0], json_num(std::round(shared_kmers[0]), "%.0f").c_str(), (unsigned long long)ss.shared_set[1],
+		       json_num(std::round(shared_kmers[1]), "%.0f").c_str(), json_num(share(0), "%.6f").c_str(), json_num(share(1), "%.6f").c_str(),
+		       ss.ms_mark[0], ss.ms_mark[1]);
+	}
+}
+
+void
+report_qv(const RoundTotals& t)
+{
+	printf("{\"qv\": {\"kmers_before\": %llu, \"absent_before\": %llu, \"kmers_after\": %llu, \"absent_after\": %llu, \"apply_ms\": %.3f, "
+	       "\"screen_ms\": %.3f, \"count_ms\": %.3f}}\n",
+	       (unsigned long long)t.qv.kmers_before, (unsigned long long)t.qv.absent_before, (unsigned long long)t.qv.kmers_after,
+	       (unsigned long long)t.qv.absent_after, t.ms_apply, t.ms_qv_screen, t.ms_qv_count);
+}
+
+void
+report_round(const RoundTotals& t)
+{
+	printf("{\"bases\": %llu, \"seconds\": %.6f, \"open_outputs_s\": %.3f, \"index_s\": %.3f, \"read_s\": %.3f, \"polish_call_s\": %.3f, \"write_s\": %.3f, \"gpu_ms\": %.3f, \"screen_ms\": %.3f, \"machine_ms\": %.3f, "
+	       "\"screening\": {\"batches_partitioned\": %u, \"batches_direct_kernel\": %u, \"record_chunks_rescreened_direct\": %u, \"overflow_records\": %llu}, \"events\": %llu, "
+	       "\"events_applied\": %llu, \"absent_kmers\": %llu, \"substitutions\": %llu, \"insertions\": %llu, "
+	       "\"deletions\": %llu}\n",
+	       t.bases, t.seconds, t.s_before_index, t.s_index, t.s_read, t.s_call, t.s_write, t.ms_gpu, t.ms_screen, t.ms_machine,
+	       t.n_batches_binned, t.n_batches_direct, t.n_chunks_direct, t.n_ovf_records, (unsigned long long)t.events.events,
+	       (unsigned long long)t.events.events_applied, (unsigned long long)t.events.absent_kmers,
+	       (unsigned long long)t.events.substitutions, (unsigned long long)t.events.insertions,
+	       (unsigned long long)t.events.deletions);
+}
+
+} // namespace nte_cli

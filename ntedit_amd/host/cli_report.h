@@ -1,0 +1,39 @@
+// cli_report.h -- what a polishing round says at its end: the QV table's total and summary line, the completeness table and
+// line, and the --report JSON lines.
+#pragma once
+
+#include "../../include/ntedit_hip.h"
+
+#include <cstdio>
+#include <string>
+
+namespace nte_cli {
+
+// the totals of a round, summed over its batches
+struct RoundTotals
+{
+	unsigned long long bases = 0;
+	double seconds = 0, s_before_index = 0, s_index = 0, s_read = 0, s_call = 0, s_write = 0;
+	double ms_gpu = 0, ms_screen = 0, ms_machine = 0;
+	// which screening kernels ran: batches on the partitioned pipeline / on the direct kernel, record chunks the direct
+	// kernel had to screen again, overflow-list entries
+	unsigned n_batches_binned = 0, n_batches_direct = 0, n_chunks_direct = 0;
+	unsigned long long n_ovf_records = 0;
+	ntedit_hip_stats events = {};
+	// --qv
+	ntedit_hip_qv_row qv = {};
+	double ms_apply = 0, ms_qv_screen = 0, ms_qv_count = 0;
+
+	void add(const ntedit_hip_stats& st);
+	void add(const ntedit_hip_qv_row& row);
+};
+
+// --qv: the "#total" row, the table closed, the summary line
+void finish_qv(ntedit_hip_ctx* ctx, FILE* qv_f, const std::string& qv_path, uint32_t k, const RoundTotals& t);
+// --completeness: <prefix>_completeness.tsv and one line, from the marks of all batches of the round; with --report its JSON
+void finish_completeness(ntedit_hip_ctx* ctx, const std::string& prefix, uint32_t k, bool report);
+// --report
+void report_qv(const RoundTotals& t);
+void report_round(const RoundTotals& t);
+
+} // namespace nte_cli
