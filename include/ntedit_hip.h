@@ -1020,6 +1020,50 @@ double ntedit_hip_bloom_cardinality(uint64_t set, uint64_t slots, uint32_t h);
 const char* ntedit_hip_completeness_header(void);
 int ntedit_hip_completeness_format_row(const char* stage, const ntedit_hip_shared_stats* st, int which, char* out, uint64_t cap);
 
+/* ---- the edited draft as BGZF, compressed on the device (no counterpart in the reference) ----------------
+ * BGZF (the SAM specification, section 4.1) is a series of gzip members of at most 64 KiB, each with an extra subfield
+ * 'B','C' that holds the member's size - 1; a file ends in the 28-byte member of no bytes (ntedit_hip_bgzf_eof).  The
+ * writer cuts its input into blocks of 65,280 bytes and makes one member of each: one final DEFLATE block of literals
+ * under a dynamic Huffman code limited to 15 bits (no matches: a draft is four letters, which such a code holds at a
+ * little over two bits a base), or a stored block where that is not smaller.  A member is a function of its block's
+ * bytes alone: the device and the serial host model give the same bytes.  gzip, bgzip, zlib and this library's own
+ * readers (ntedit_hip_fasta_*, ntedit_hip_reads_inflate_*) read the result; its bytes are not those bgzip would write.
+ *
+ * NTEDIT_HIP_APPLY_BGZF (ntedit_hip_set_apply, beside the other flags): the applier runs, and behind it, on the same
+ * stream, the _edited.fa text of the batch is laid out in device memory -- for entry i '>' names[i] '\n', the edited
+ * bases, '\n': byte for byte what ntedit_hip_write_outputs_ex() appends to fa_path for the batch -- and compressed;
+ * only the members cross to the host, into page-locked memory the result owns.  The edited bases go with the call
+ * unless APPLY_EDITED is set too.  Segments (ntedit_hip_segment) are not supported.
+ * ntedit_hip_set_fa_names copies the header lines (without '>' and newline) for the NEXT polish call; a polish call with
+ * the flag and without names, or with another number of names than entries, fails with NTEDIT_E_ARG before anything
+ * runs and leaves the names set.  A call whose arguments are accepted uses the names up, whatever becomes of it. */
+#define NTEDIT_HIP_APPLY_BGZF 8u
+int ntedit_hip_set_fa_names(ntedit_hip_ctx* ctx, const char* const* names, uint32_t n);
+/* The members of a result polished with APPLY_BGZF (NTEDIT_E_ARG otherwise; ntedit_hip_result_last_error() says why).
+ * *host: *n_bytes bytes, valid until ntedit_hip_result_free(); *n_plain: the bytes they inflate to; *n_members: their
+ * number (0 members and 0 bytes for an empty batch).  The outputs may be NULL. */
+int ntedit_hip_result_fa_bgzf(const ntedit_hip_result* r, const uint8_t** host, uint64_t* n_bytes, uint64_t* n_plain, uint32_t* n_members);
+/* Stand-alone: src[0 .. n) (host bytes, or device bytes with on_device = NTEDIT_HIP_BASES_DEVICE) into members in
+ * out[0 .. cap), host memory.  *n_out = the bytes needed; NTEDIT_E_OVERFLOW when cap is less.  n == 0 gives 0 bytes
+ * (no EOF member: the caller ends a file with ntedit_hip_bgzf_eof). */
+int ntedit_hip_bgzf_deflate(ntedit_hip_ctx* ctx, const void* src, uint64_t n, int on_device, uint8_t* out, uint64_t cap, uint64_t* n_out);
+/* the serial host model of the same encoder: no context, no device; arguments and codes as above */
+int ntedit_hip_bgzf_deflate_model(const void* src, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* n_out);
+/* no n bytes take more: every block as a stored member */
+uint64_t ntedit_hip_bgzf_bound(uint64_t n);
+/* the member that ends a BGZF file; *n (may be NULL) = 28 */
+const uint8_t* ntedit_hip_bgzf_eof(uint32_t* n);
+/* The context's last call that compressed (a polish call with APPLY_BGZF, ntedit_hip_bgzf_deflate): HIP-event times of
+ * the image kernel, of the deflate and scan kernels, and of the packing kernel with the copy to the host; the bytes in
+ * and out, the members, and those among them that hold a stored block. */
+typedef struct ntedit_hip_bgzf_stats
+{
+	float ms_image, ms_deflate, ms_copy;
+	uint64_t plain_bytes, bgzf_bytes;
+	uint32_t members, stored_members;
+} ntedit_hip_bgzf_stats;
+int ntedit_hip_bgzf_info(ntedit_hip_ctx* ctx, ntedit_hip_bgzf_stats* st);
+
 /* The reference's candidate tables -- num_tries, polish_bases_array / snv_bases_array, multi_possible_bases (ntedit.cpp:172,
  * 176-199, 203-348) -- as the device code holds them (one GPU thread runs the machine's own candidate_bases /
  * insertion_candidate), as text: "num_tries 0 1 5 21 85 341", "polish A TCG", ..., "snv N ATCG", "multi A A AA AC ...".

@@ -149,7 +149,7 @@ class SettleStats(ctypes.Structure):
     _fields_ = [("events_seen", ctypes.c_uint64), ("events_settled", ctypes.c_uint64), ("ms", ctypes.c_float)]
 
 
-APPLY_EDITED, APPLY_QV, APPLY_SHARED = 1, 2, 4
+APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF = 1, 2, 4, 8
 
 
 class QvRow(ctypes.Structure):
@@ -165,6 +165,16 @@ class ApplyStats(ctypes.Structure):
     """ntedit_hip_apply_stats"""
     _fields_ = [("ms_apply", ctypes.c_float), ("ms_screen", ctypes.c_float), ("ms_count", ctypes.c_float),
                 ("pieces", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("events_applied", ctypes.c_uint64)]
+
+
+class BgzfStats(ctypes.Structure):
+    """ntedit_hip_bgzf_stats: the context's last call that compressed (APPLY_BGZF, ntedit_hip_bgzf_deflate)"""
+    _fields_ = [("ms_image", ctypes.c_float), ("ms_deflate", ctypes.c_float), ("ms_copy", ctypes.c_float),
+                ("plain_bytes", ctypes.c_uint64), ("bgzf_bytes", ctypes.c_uint64), ("members", ctypes.c_uint32),
+                ("stored_members", ctypes.c_uint32)]
+
+
+BGZF_BLOCK = 65280  # plain bytes of a member
 
 
 class SharedStats(ctypes.Structure):
@@ -289,6 +299,8 @@ EXPORTS = [
     "ntedit_hip_shared_begin", "ntedit_hip_shared_reset", "ntedit_hip_shared_free", "ntedit_hip_shared_mark",
     "ntedit_hip_shared_download", "ntedit_hip_shared_counts", "ntedit_hip_bloom_cardinality",
     "ntedit_hip_completeness_header", "ntedit_hip_completeness_format_row",
+    "ntedit_hip_set_fa_names", "ntedit_hip_result_fa_bgzf", "ntedit_hip_bgzf_deflate", "ntedit_hip_bgzf_deflate_model",
+    "ntedit_hip_bgzf_bound", "ntedit_hip_bgzf_eof", "ntedit_hip_bgzf_info",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -486,5 +498,16 @@ def load():
     lib.ntedit_hip_completeness_header.restype = ctypes.c_char_p
     lib.ntedit_hip_completeness_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(SharedStats), ctypes.c_int,
                                                        ctypes.c_char_p, u64]
+    # the edited draft as BGZF (nte_bgzf_deflate.hip)
+    pu32 = ctypes.POINTER(u32)
+    lib.ntedit_hip_set_fa_names.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), u32]
+    lib.ntedit_hip_result_fa_bgzf.argtypes = [vp, ctypes.POINTER(vp), pu64, pu64, pu32]
+    lib.ntedit_hip_bgzf_deflate.argtypes = [vp, vp, u64, ci, vp, u64, pu64]
+    lib.ntedit_hip_bgzf_deflate_model.argtypes = [vp, u64, vp, u64, pu64]
+    lib.ntedit_hip_bgzf_bound.argtypes = [u64]
+    lib.ntedit_hip_bgzf_bound.restype = u64
+    lib.ntedit_hip_bgzf_eof.argtypes = [pu32]
+    lib.ntedit_hip_bgzf_eof.restype = vp
+    lib.ntedit_hip_bgzf_info.argtypes = [vp, ctypes.POINTER(BgzfStats)]
     _lib = lib
     return lib

@@ -6,6 +6,7 @@
 #include "nte_kernels.hip"
 #include "nte_settle.h"
 #include "nte_apply.h"
+#include "nte_bgzf_launch.h"
 
 #include "../../include/ntedit_hip.h"
 #include "../host/bfio.h"
@@ -150,6 +151,11 @@ struct ntedit_hip_ctx
 	DevBuf ap_ev, ap_place, ap_range, ap_contig, ap_tabs, ap_pieces, ap_edited, ap_bitmap, ap_rows;
 	hipEvent_t ap_evt[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 	ntedit_hip_apply_stats apply_last = { 0.f, 0.f, 0.f, 0, 0, 0 };
+	// the BGZF writer (nte_bgzf_deflate.hip): the header lines of the next polish call, the last call's figures
+	std::vector<std::string> fa_names;
+	bool fa_names_set = false;
+	ntedit_hip_bgzf_stats bgzf_last = { 0.f, 0.f, 0.f, 0, 0, 0, 0 };
+	std::vector<PinBuf> bgzf_pool; // page-locked buffers for the members, apart from pin_pool (under pin_mu): filled by reserve
 	// linear counting of the draft's present k-mers (k_mark; ntedit_hip_shared_*): two mark arrays of the PRIMARY filter's
 	// size, before and after; they go when the slot gets another filter (drop_filter)
 	DevBuf sh_marks[2];
@@ -188,6 +194,10 @@ struct ntedit_hip_result
 	std::vector<uint64_t> e_offs;
 	std::vector<uint32_t> e_lens;
 	std::vector<ntedit_hip_qv_row> qv;
+	// NTEDIT_HIP_APPLY_BGZF: the batch's _edited.fa text as BGZF members, page-locked
+	PinBuf bgzf_buf;
+	u64 bgzf_bytes = 0, bgzf_plain = 0;
+	u32 bgzf_members = 0;
 };
 
 namespace {
@@ -282,6 +292,64 @@ pin_give(ntedit_hip_ctx* c, PinBuf& b)
 		std::lock_guard<std::mutex> lk(c->pin_mu);
 		c->pin_pool.push_back(b);
 	} else {
+		(void)hipHostFree(b.p);
+	}
+	b.p = nullptr;
+	b.cap = 0;
+}
+
+// The page-locked buffers of the BGZF members have a pool of their own: in pin_pool the best-fit rule would hand the
+// buffers that ntedit_hip_reserve sized for the members to the arena copies, and a batch would pin a new one.
+int
+bgzf_pin_take(ntedit_hip_ctx* c, size_t bytes, PinBuf* out)
+{
+	{
+		std::lock_guard<std::mutex> lk(c->pin_mu);
+		int best = -1;
+		for (size_t i = 0; i < c->bgzf_pool.size(); i++) {
+			if (c->bgzf_pool[i].cap >= bytes && (best < 0 || c->bgzf_pool[i].cap < c->bgzf_pool[best].cap)) {
+				best = (int)i;
+			}
+		}
+		if (best >= 0) {
+			*out = c->bgzf_pool[best];
+			c->bgzf_pool.erase(c->bgzf_pool.begin() + best);
+			return 0;
+		}
+	}
+	const size_t want = bytes + bytes / 4 + 4096;
+	void* p = nullptr;
+	HIP_TRY(c, hipHostMalloc(&p, want, hipHostMallocDefault));
+	out->p = p;
+	out->cap = want;
+	return 0;
+}
+
+void
+bgzf_pin_give(ntedit_hip_ctx* c, PinBuf& b)
+{
+	if (!b.p) {
+		return;
+	}
+	bool kept = false;
+	if (c && ctx_alive(c)) {
+		std::lock_guard<std::mutex> lk(c->pin_mu);
+		if (c->bgzf_pool.size() >= 3) { // (the smallest goes: the pool keeps what the largest batches need)
+			size_t least = 0;
+			for (size_t i = 1; i < c->bgzf_pool.size(); i++) {
+				if (c->bgzf_pool[i].cap < c->bgzf_pool[least].cap) {
+					least = i;
+				}
+			}
+			if (c->bgzf_pool[least].cap < b.cap) {
+				std::swap(c->bgzf_pool[least], b);
+			}
+		} else {
+			c->bgzf_pool.push_back(b);
+			kept = true;
+		}
+	}
+	if (!kept) {
 		(void)hipHostFree(b.p);
 	}
 	b.p = nullptr;

@@ -105,6 +105,11 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 		(void)hipHostFree(pb.p);
 	}
 	c->pin_pool.clear();
+	for (auto& pb : c->bgzf_pool) {
+		(void)hipHostFree(pb.p);
+	}
+	c->bgzf_pool.clear();
+	bgzf_release(c); // (the BGZF writer's buffers: nte_bgzf_deflate.hip)
 	if (c->d_tab) {
 		(void)hipFree(c->d_tab);
 	}

@@ -30,6 +30,7 @@ struct PolishRun
 	u32 n_contigs;
 	int on_device;
 	ntedit_hip_result* r;
+	const std::vector<std::string>* fa_names = nullptr; // NTEDIT_HIP_APPLY_BGZF: the entries' header lines
 
 	// plan
 	struct Chunk
@@ -104,6 +105,7 @@ struct PolishRun
 	int collect(bool* redo);
 	int finish();
 	int apply();
+	int bgzf(const u8* d_edited);
 };
 
 int
@@ -1252,6 +1254,11 @@ PolishRun::apply()
 	}
 	c->apply_last = as;
 	r->edited_bytes = total_bytes;
+	if ((flags & NTEDIT_HIP_APPLY_BGZF) && (rc = bgzf(a.out))) {
+		release(eb);
+		r->qv.clear();
+		return rc;
+	}
 	if (flags & NTEDIT_HIP_APPLY_EDITED) {
 		r->edited = eb; // the result's own until ntedit_hip_result_free()
 	} else {
@@ -1262,6 +1269,44 @@ PolishRun::apply()
 			c->ap_edited = eb;
 		}
 	}
+	return 0;
+}
+
+// The BGZF writer (nte_bgzf_deflate.hip) behind the applier, on its stream: the batch's _edited.fa text laid out in HBM from
+// the edited bases and the header lines, compressed block by block, the members packed and copied into page-locked memory
+// of the result's.  Crosses PCIe: the image's tables and the names down, two words of totals and the members up.
+int
+PolishRun::bgzf(const u8* d_edited)
+{
+	std::vector<u64> name_offs(n_contigs + 1, 0);
+	std::string blob;
+	for (u32 i = 0; i < n_contigs; i++) {
+		blob += (*fa_names)[i];
+		name_offs[i + 1] = blob.size();
+	}
+	const FaImage im = { d_edited, r->e_offs.data(), r->e_lens.data(), n_contigs, blob.data(), name_offs.data() };
+	const u8* d_image = nullptr;
+	u64 n_image = 0;
+	BgzfTotals t;
+	std::string why;
+	int rc = bgzf_image(c, c->device, c->stream, im, &d_image, &n_image, &t.ms_image, &why);
+	if (!rc) {
+		rc = bgzf_encode(c, c->device, c->stream, d_image, n_image, &t, &why);
+	}
+	if (!rc && (rc = bgzf_pin_take(c, (size_t)t.bytes + 16, &r->bgzf_buf))) {
+		return rc;
+	}
+	if (!rc) {
+		rc = bgzf_fetch(c, c->stream, r->bgzf_buf.p, t.bytes, &t.ms_copy, &why);
+	}
+	if (rc) {
+		bgzf_pin_give(c, r->bgzf_buf);
+		return fail(c, rc, "apply: %s", why.c_str());
+	}
+	r->bgzf_bytes = t.bytes;
+	r->bgzf_plain = t.plain;
+	r->bgzf_members = t.members;
+	c->bgzf_last = { t.ms_image, t.ms_deflate, t.ms_copy, t.plain, t.bytes, t.members, t.stored };
 	return 0;
 }
 
@@ -1290,10 +1335,19 @@ ntedit_hip_polish_batch(
 	if ((c->apply_flags & NTEDIT_HIP_APPLY_SHARED) && (rc = shared_refuse(c, "polish_batch"))) {
 		return rc; // (a counting filter: before anything is polished)
 	}
+	if ((c->apply_flags & NTEDIT_HIP_APPLY_BGZF) && (!c->fa_names_set || c->fa_names.size() != n_contigs)) {
+		return fail(c, NTEDIT_E_ARG, "polish_batch: APPLY_BGZF needs the header line of every entry (ntedit_hip_set_fa_names): %u entries, %s",
+		            n_contigs, c->fa_names_set ? "another number of names" : "no names");
+	}
 	for (u32 i = 0; i < n_contigs; i++) {
 		if (offsets[i] + lens[i] > n || (i + 1 < n_contigs && offsets[i] + lens[i] >= offsets[i + 1])) {
 			return fail(c, NTEDIT_E_ARG, "polish_batch: contig %u breaks the batch layout", i);
 		}
+	}
+	std::vector<std::string> fa_names; // (the header lines serve this call alone: used up once its arguments are accepted)
+	if (c->apply_flags & NTEDIT_HIP_APPLY_BGZF) {
+		fa_names.swap(c->fa_names);
+		c->fa_names_set = false;
 	}
 	ntedit_hip_result* r = new ntedit_hip_result();
 	r->owner = c;
@@ -1316,6 +1370,7 @@ ntedit_hip_polish_batch(
 	run.n_contigs = n_contigs;
 	run.on_device = on_device;
 	run.r = r;
+	run.fa_names = &fa_names;
 	if ((rc = run.plan())) {
 		return run.bail(rc);
 	}
@@ -1416,6 +1471,10 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		if (keep_flags & NTEDIT_HIP_APPLY_SHARED) {
 			c->apply_flags = (keep_flags & ~NTEDIT_HIP_APPLY_SHARED) | NTEDIT_HIP_APPLY_QV;
 		}
+		c->apply_flags &= ~NTEDIT_HIP_APPLY_BGZF; // (the writer has a warm-up of its own, below; this batch has no names)
+		if ((keep_flags & NTEDIT_HIP_APPLY_BGZF) && !c->apply_flags) {
+			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
+		}
 		ntedit_hip_result* wr = nullptr;
 		rc = ntedit_hip_polish_batch(c, buf.data(), wn, offs.data(), lens.data(), wc, NTEDIT_HIP_BASES_HOST, &wr);
 		c->apply_flags = keep_flags;
@@ -1503,6 +1562,23 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		}
 		if ((c->apply_flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED)) && (rc = ensure(c, c->ap_bitmap, (size_t)(n_words + n_words / 64 + 64) * 8))) {
 			return rc;
+		}
+		if (c->apply_flags & NTEDIT_HIP_APPLY_BGZF) { // (the image: the edited bases, and per entry '>', a header line, '\n')
+			std::string why;
+			const u64 image = n + n / 64 + 4096 + (u64)(max_contigs ? max_contigs : 1) * 64;
+			if ((rc = bgzf_reserve(c, c->device, c->stream, image, max_contigs, &why))) {
+				return fail(c, rc, "reserve: %s", why.c_str());
+			}
+			// two results hold members at a time: the one a writer is writing out and the one being polished
+			PinBuf z[2];
+			for (PinBuf& b : z) {
+				if ((rc = bgzf_pin_take(c, (size_t)(image / 3), &b))) {
+					bgzf_pin_give(c, z[0]);
+					return rc;
+				}
+			}
+			bgzf_pin_give(c, z[0]);
+			bgzf_pin_give(c, z[1]);
 		}
 	}
 	// ---- page-locked result buffers (an event's records are about one 128-byte chunk; the pool hands out the best fit)

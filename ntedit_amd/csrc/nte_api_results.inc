@@ -11,6 +11,7 @@ ntedit_hip_result_free(ntedit_hip_result* r)
 	// (a result may outlive its context: its pinned buffers are then released directly)
 	pin_give(r->owner, r->arena_buf);
 	pin_give(r->owner, r->first_buf);
+	bgzf_pin_give(r->owner, r->bgzf_buf);
 	if (r->edited.p) {
 		// the edited bases go back to a context that has no buffer of its own by now, or to the device
 		bool kept = false;
@@ -50,7 +51,7 @@ result_refuse(const ntedit_hip_result* r, const char* what)
 int
 ntedit_hip_set_apply(ntedit_hip_ctx* c, uint32_t flags)
 {
-	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED))) {
+	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_BGZF))) {
 		return fail(c, NTEDIT_E_ARG, "set_apply: unknown flag");
 	}
 	c->apply_flags = flags;
@@ -137,6 +138,89 @@ uint32_t
 ntedit_hip_apply_tile(void)
 {
 	return APPLY_TILE;
+}
+
+// ---- the BGZF writer (nte_bgzf_deflate.hip)
+
+int
+ntedit_hip_set_fa_names(ntedit_hip_ctx* c, const char* const* names, uint32_t n)
+{
+	if (!c || (n && !names)) {
+		return fail(c, NTEDIT_E_ARG, "set_fa_names: bad argument");
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (!names[i]) {
+			return fail(c, NTEDIT_E_ARG, "set_fa_names: name %u is NULL", i);
+		}
+	}
+	c->fa_names.assign(names, names + n);
+	c->fa_names_set = true;
+	return 0;
+}
+
+int
+ntedit_hip_result_fa_bgzf(const ntedit_hip_result* r, const uint8_t** host, uint64_t* n_bytes, uint64_t* n_plain, uint32_t* n_members)
+{
+	if (!r) {
+		return result_refuse(r, "result_fa_bgzf: bad argument");
+	}
+	if (!(r->apply_flags & NTEDIT_HIP_APPLY_BGZF)) {
+		return result_refuse(r, "result_fa_bgzf: the batch was polished without the APPLY_BGZF flag (ntedit_hip_set_apply)");
+	}
+	if (host) {
+		*host = (const uint8_t*)r->bgzf_buf.p;
+	}
+	if (n_bytes) {
+		*n_bytes = r->bgzf_bytes;
+	}
+	if (n_plain) {
+		*n_plain = r->bgzf_plain;
+	}
+	if (n_members) {
+		*n_members = r->bgzf_members;
+	}
+	return 0;
+}
+
+int
+ntedit_hip_bgzf_deflate(ntedit_hip_ctx* c, const void* src, uint64_t n, int on_device, uint8_t* out, uint64_t cap, uint64_t* n_out)
+{
+	if (!c || !n_out || (n && !src) || (cap && !out) || (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE)) {
+		return fail(c, NTEDIT_E_ARG, "bgzf_deflate: bad argument");
+	}
+	*n_out = 0;
+	std::string why;
+	BgzfTotals t;
+	const u8* d_src = (const u8*)src;
+	int rc = 0;
+	if (on_device == NTEDIT_HIP_BASES_HOST && n) {
+		rc = bgzf_upload(c, c->device, c->stream, src, n, &d_src, &why);
+	}
+	if (!rc) {
+		rc = bgzf_encode(c, c->device, c->stream, d_src, n, &t, &why);
+	}
+	if (rc) {
+		return fail(c, rc, "bgzf_deflate: %s", why.c_str());
+	}
+	*n_out = t.bytes;
+	c->bgzf_last = { 0.f, t.ms_deflate, 0.f, t.plain, t.bytes, t.members, t.stored };
+	if (t.bytes > cap) {
+		return fail(c, NTEDIT_E_OVERFLOW, "bgzf_deflate: the members take %llu bytes, the buffer has %llu", (unsigned long long)t.bytes, (unsigned long long)cap);
+	}
+	if ((rc = bgzf_fetch(c, c->stream, out, t.bytes, &c->bgzf_last.ms_copy, &why))) {
+		return fail(c, rc, "bgzf_deflate: %s", why.c_str());
+	}
+	return 0;
+}
+
+int
+ntedit_hip_bgzf_info(ntedit_hip_ctx* c, ntedit_hip_bgzf_stats* st)
+{
+	if (!c || !st) {
+		return fail(c, NTEDIT_E_ARG, "bgzf_info: bad argument");
+	}
+	*st = c->bgzf_last;
+	return 0;
 }
 
 // ---- the completeness marks (k_mark, nte_kernels.hip; the helpers are in nte_api_screen.inc)

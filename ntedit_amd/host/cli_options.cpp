@@ -102,6 +102,20 @@ static const char USAGE[] = PROGRAM
     "	--help,		display this message and exit \n"
     "	--version,	output version information and exit\n\n";
 
+// (--help is pinned whole by the transcripts: an option added since has a paragraph of its own)
+static const char HELP_BGZIP[] = PROGRAM
+    " --bgzip\n\n"
+    "	--bgzip,	write the edited draft as <prefix>_edited.fa.gz (BGZF, the blocked gzip that bgzip writes and that gzip, zcat,\n"
+    "			samtools faidx and this program's -f read) in place of <prefix>_edited.fa.  The edited contigs are laid out\n"
+    "			as FASTA text and compressed on the GPU, 65,280 bytes to a member, literal-only dynamic Huffman blocks (about\n"
+    "			2.2 bits a base), stored blocks where that is not smaller; only the compressed bytes cross to the host.  The\n"
+    "			decompressed text is byte for byte the _edited.fa of a run without the option; _changes.tsv and\n"
+    "			_variants.vcf are unchanged.  The file ends in the 28-byte BGZF end-of-file member; a run in which no contig\n"
+    "			passes -z writes that member alone.  With -k K1,K2,... an earlier round writes <prefix>_k<Ki>_edited.fa.gz and\n"
+    "			the next round reads it.  One summary line reports plain bytes, BGZF bytes, their ratio, members and stored\n"
+    "			members; --report adds {\"bgzip\": {...}}.  Not with --shard\n"
+    "	--help-bgzip,	display this paragraph and exit\n\n";
+
 static const char shortopts[] = "t:f:s:k:z:b:r:v:d:i:X:Y:x:y:m:c:j:s:e:a:l:p:q:";
 enum
 {
@@ -134,7 +148,9 @@ enum
 	OPT_SAVE_REJECT_BF,
 	OPT_READS_BATCH,
 	OPT_STORE_CAP,
-	OPT_GPU_PARSE
+	OPT_GPU_PARSE,
+	OPT_BGZIP,
+	OPT_HELP_BGZIP
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -188,6 +204,8 @@ static const struct option longopts[] = {
 	{ "batch_bytes", required_argument, nullptr, OPT_READS_BATCH }, // tests: many small read batches
 	{ "resident_cap", required_argument, nullptr, OPT_STORE_CAP }, // tests: the resident store's cap (0: off)
 	{ "gpu_parse", no_argument, nullptr, OPT_GPU_PARSE },
+	{ "bgzip", no_argument, nullptr, OPT_BGZIP },
+	{ "help-bgzip", no_argument, nullptr, OPT_HELP_BGZIP },
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -514,6 +532,12 @@ parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOptio
 		case OPT_TUNE:
 			parse_tune(optarg, o);
 			break;
+		case OPT_BGZIP:
+			o->bgzip = true;
+			break;
+		case OPT_HELP_BGZIP:
+			fputs(HELP_BGZIP, stderr);
+			exit(EXIT_SUCCESS);
 		case OPT_HELP:
 			fputs(USAGE, stderr);
 			exit(EXIT_SUCCESS);
@@ -625,6 +649,10 @@ parse_cli(int argc, char** argv)
 	if (die) {
 		fprintf(stderr, "Try `" PROGRAM " --help' for more information.\n");
 		exit(EXIT_FAILURE);
+	}
+	if (o.bgzip && o.shard_given) {
+		// (behind every older refusal)
+		fail("--bgzip and --shard: the byte index of the shards and the gather that merges them know plain text only; run --bgzip on the whole draft");
 	}
 	if (o.params.snv) {
 		// ntedit.cpp:2411-2417

@@ -35,6 +35,18 @@ RoundTotals::add(const ntedit_hip_qv_row& row)
 	qv.absent_after += row.absent_after;
 }
 
+void
+RoundTotals::add(const ntedit_hip_bgzf_stats& bs)
+{
+	ms_bgzf_image += bs.ms_image;
+	ms_bgzf_deflate += bs.ms_deflate;
+	ms_bgzf_copy += bs.ms_copy;
+	bgzf_plain += bs.plain_bytes;
+	bgzf_bytes += bs.bgzf_bytes;
+	bgzf_members += bs.members;
+	bgzf_stored += bs.stored_members;
+}
+
 static std::string
 qv_text(uint64_t absent, uint64_t kmers, uint32_t k)
 {
@@ -131,6 +143,19 @@ finish_completeness(ntedit_hip_ctx* ctx, const std::string& prefix, uint32_t k, 
 		       (unsigned long long)ss.shared_set[0], json_num(std::round(shared_kmers[0]), "%.0f").c_str(), (unsigned long long)ss.shared_set[1],
 		       json_num(std::round(shared_kmers[1]), "%.0f").c_str(), json_num(share(0), "%.6f").c_str(), json_num(share(1), "%.6f").c_str(),
 		       ss.ms_mark[0], ss.ms_mark[1]);
+	}
+}
+
+void
+finish_bgzip(const RoundTotals& t, const std::string& fa_path, bool report)
+{
+	const double ratio = t.bgzf_bytes ? (double)t.bgzf_plain / (double)t.bgzf_bytes : 0.0;
+	printf("BGZF: %llu plain bytes in %llu BGZF bytes (ratio %.3f), %llu members, %llu of them stored; file: %s\n", t.bgzf_plain, t.bgzf_bytes,
+	       ratio, t.bgzf_members, t.bgzf_stored, fa_path.c_str());
+	if (report) {
+		printf("{\"bgzip\": {\"plain_bytes\": %llu, \"bgzf_bytes\": %llu, \"members\": %llu, \"stored_members\": %llu, \"image_ms\": %.3f, "
+		       "\"deflate_ms\": %.3f, \"copy_ms\": %.3f}}\n",
+		       t.bgzf_plain, t.bgzf_bytes, t.bgzf_members, t.bgzf_stored, t.ms_bgzf_image, t.ms_bgzf_deflate, t.ms_bgzf_copy);
 	}
 }
 

@@ -23,8 +23,12 @@ struct RoundTotals
 	// --qv
 	ntedit_hip_qv_row qv = {};
 	double ms_apply = 0, ms_qv_screen = 0, ms_qv_count = 0;
+	// --bgzip: the sums of ntedit_hip_bgzf_info over the batches
+	double ms_bgzf_image = 0, ms_bgzf_deflate = 0, ms_bgzf_copy = 0;
+	unsigned long long bgzf_plain = 0, bgzf_bytes = 0, bgzf_members = 0, bgzf_stored = 0;
 
 	void add(const ntedit_hip_stats& st);
+	void add(const ntedit_hip_bgzf_stats& bs);
 	void add(const ntedit_hip_qv_row& row);
 };
 
@@ -32,6 +36,8 @@ struct RoundTotals
 void finish_qv(ntedit_hip_ctx* ctx, FILE* qv_f, const std::string& qv_path, uint32_t k, const RoundTotals& t);
 // --completeness: <prefix>_completeness.tsv and one line, from the marks of all batches of the round; with --report its JSON
 void finish_completeness(ntedit_hip_ctx* ctx, const std::string& prefix, uint32_t k, bool report);
+// --bgzip: the summary line (the file's end-of-file member is counted in neither figure); with --report its JSON
+void finish_bgzip(const RoundTotals& t, const std::string& fa_path, bool report);
 // --report
 void report_qv(const RoundTotals& t);
 void report_round(const RoundTotals& t);

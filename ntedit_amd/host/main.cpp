@@ -5,7 +5,8 @@
 // echo, the device set-up, then the draft through three pipeline stages that share a pool of three batches
 // (cli_batches.h) -- a reader with kseq semantics, the GPU through the C ABI (include/ntedit_hip.h), and a writer of
 // <prefix>_edited.fa and <prefix>_changes.tsv byte-identical to the reference's, plus <prefix>_variants.vcf (the
-// ##fileDate line carries today's date, as in the reference) -- and the summaries (cli_report.cpp).
+// ##fileDate line carries today's date, as in the reference) -- and the summaries (cli_report.cpp).  With --bgzip the
+// edited draft is <prefix>_edited.fa.gz: the GPU stage's results hold its BGZF members, the writer stage appends them.
 #include "../../include/ntedit_hip.h"
 #include "cli_batches.h"
 #include "cli_common.h"
@@ -18,6 +19,7 @@
 
 #include <cerrno>
 #include <cstring>
+#include <fcntl.h>
 #include <memory>
 #include <sstream>
 #include <thread>
@@ -41,6 +43,7 @@ struct Round
 	uint32_t k = 0;
 	std::string fa_path, tsv_path, vcf_path, qv_path;
 	FILE *qv_f = nullptr, *index_f = nullptr;
+	int fa_fd = -1; // --bgzip: <prefix>_edited.fa.gz, open for the writer stage
 	ntedit_hip_annot* annot = nullptr;
 	Channel free_q, gpu_q, write_q;
 	RoundTotals tot;
@@ -142,7 +145,8 @@ prepare_device(Run& run, const CliOptions& opt, const ntedit_hip_params& p, bool
 	if (ntedit_hip_set_params(ctx, &p) != 0) {
 		fail("%s", ntedit_hip_last_error(ctx));
 	}
-	if (opt.qv && ntedit_hip_set_apply(ctx, NTEDIT_HIP_APPLY_QV | (opt.completeness ? NTEDIT_HIP_APPLY_SHARED : 0u)) != 0) {
+	const uint32_t apply = (opt.qv ? NTEDIT_HIP_APPLY_QV | (opt.completeness ? NTEDIT_HIP_APPLY_SHARED : 0u) : 0u) | (opt.bgzip ? NTEDIT_HIP_APPLY_BGZF : 0u);
+	if (apply && ntedit_hip_set_apply(ctx, apply) != 0) {
 		fail("%s", ntedit_hip_last_error(ctx));
 	}
 	// --completeness: the two mark arrays of this round's filter, mapped here and not inside the first batch
@@ -179,6 +183,9 @@ open_outputs(Round& r, const ntedit_hip_params& p, int counting, const std::stri
 		fail("cannot write `%s'", r.fa_path.c_str());
 	}
 	fclose(f);
+	if (opt.bgzip && (r.fa_fd = open(r.fa_path.c_str(), O_WRONLY | O_APPEND)) < 0) {
+		fail("cannot write `%s'", r.fa_path.c_str());
+	}
 	if (ntedit_hip_write_tsv_header(r.tsv_path.c_str(), r.k, p.jump, counting) != 0) {
 		fail("cannot write `%s'", r.tsv_path.c_str());
 	}
@@ -388,6 +395,23 @@ read_streamed(Round& r, nte_host::FastaReader& reader, Admission adm)
 	feed.finish(adm);
 }
 
+// --bgzip: all of p[0 .. n) to the edited draft
+static void
+write_bgzf(Round& r, const uint8_t* p, uint64_t n)
+{
+	while (n) {
+		const ssize_t w = write(r.fa_fd, p, n < (1u << 30) ? (size_t)n : (size_t)1 << 30);
+		if (w < 0 && errno == EINTR) {
+			continue;
+		}
+		if (w <= 0) {
+			fail("cannot write `%s'", r.fa_path.c_str());
+		}
+		p += w;
+		n -= (uint64_t)w;
+	}
+}
+
 // Writer stage: renders the batches the GPU stage hands over, in order, and sums their statistics.
 static void
 write_batches(Round& r)
@@ -401,7 +425,7 @@ write_batches(Round& r)
 		}
 		ntedit_hip_write_options wo;
 		memset(&wo, 0, sizeof wo);
-		wo.fa_path = r.fa_path.c_str();
+		wo.fa_path = r.opt.bgzip ? nullptr : r.fa_path.c_str(); // (--bgzip: the result holds the FASTA text, compressed)
 		wo.tsv_path = r.tsv_path.c_str();
 		wo.vcf_path = r.vcf_path.c_str();
 		wo.append = 1;
@@ -413,6 +437,14 @@ write_batches(Round& r)
 		}
 		if (ntedit_hip_write_outputs_ex(w->res, b.data(), b.offs.data(), b.lens.data(), names.data(), (uint32_t)names.size(), &wo) != 0) {
 			fail("cannot write outputs");
+		}
+		if (r.opt.bgzip) {
+			const uint8_t* members = nullptr;
+			uint64_t n_bytes = 0;
+			if (ntedit_hip_result_fa_bgzf(w->res, &members, &n_bytes, nullptr, nullptr) != 0) {
+				fail("%s", ntedit_hip_result_last_error());
+			}
+			write_bgzf(r, members, n_bytes);
 		}
 		for (size_t i = 0; r.index_f && i < names.size(); i++) {
 			fprintf(r.index_f, "%llu\t%llu\t%llu\t%llu\n", (unsigned long long)b.ordinals[i], (unsigned long long)sizes[3 * i],
@@ -454,6 +486,15 @@ polish_batches(Round& r)
 			continue;
 		}
 		const Stopwatch clock;
+		if (r.opt.bgzip) {
+			std::vector<const char*> names(b.names.size());
+			for (size_t i = 0; i < b.names.size(); i++) {
+				names[i] = b.names[i].c_str();
+			}
+			if (ntedit_hip_set_fa_names(r.ctx, names.data(), (uint32_t)names.size()) != 0) {
+				fail("%s", ntedit_hip_last_error(r.ctx));
+			}
+		}
 		if (ntedit_hip_polish_batch(r.ctx, b.is_packed ? b.packed.data() : b.data(), b.size(), b.offs.data(), b.lens.data(),
 		                            (uint32_t)b.names.size(), b.is_packed ? NTEDIT_HIP_BASES_PACKED : NTEDIT_HIP_BASES_HOST, &w->res) != 0) {
 			fail("%s", ntedit_hip_last_error(r.ctx));
@@ -464,6 +505,10 @@ polish_batches(Round& r)
 			r.tot.ms_apply += as.ms_apply;
 			r.tot.ms_qv_screen += as.ms_screen;
 			r.tot.ms_qv_count += as.ms_count;
+		}
+		ntedit_hip_bgzf_stats bs;
+		if (r.opt.bgzip && ntedit_hip_bgzf_info(r.ctx, &bs) == 0) {
+			r.tot.add(bs);
 		}
 		r.write_q.push(w);
 	}
@@ -502,7 +547,7 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	// ---- the outputs (--report: from this stamp to "process complete")
 	printf("---------- reading/processing input sequence        : %s", now_text());
 	const Stopwatch run_clock;
-	r.fa_path = prefix + "_edited.fa";
+	r.fa_path = prefix + (opt.bgzip ? "_edited.fa.gz" : "_edited.fa");
 	r.tsv_path = prefix + "_changes.tsv";
 	r.vcf_path = prefix + "_variants.vcf";
 	r.qv_path = prefix + "_qv.tsv";
@@ -563,6 +608,14 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	polish_batches(r);
 	reader_thread.join();
 	writer_thread.join();
+	if (opt.bgzip) {
+		uint32_t n_eof = 0;
+		const uint8_t* eof = ntedit_hip_bgzf_eof(&n_eof);
+		write_bgzf(r, eof, n_eof);
+		if (close(r.fa_fd) != 0) {
+			fail("cannot write `%s'", r.fa_path.c_str());
+		}
+	}
 	if (r.index_f && fclose(r.index_f) != 0) {
 		fail("cannot write `%s.index.tsv'", prefix.c_str());
 	}
@@ -579,6 +632,9 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	}
 	if (opt.completeness) {
 		finish_completeness(ctx, prefix, r.k, opt.report != 0);
+	}
+	if (opt.bgzip) {
+		finish_bgzip(r.tot, r.fa_path, opt.report != 0);
 	}
 	if (opt.report && opt.qv) {
 		report_qv(r.tot);

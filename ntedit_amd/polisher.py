@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, APPLY_EDITED, APPLY_QV, APPLY_SHARED  # noqa: F401
+from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF  # noqa: F401
 
 PRIMARY, SECONDARY = 0, 1
 
@@ -185,6 +185,16 @@ class Result:
             self._result_error("result_qv", rc)
         return rows[:n_contigs]
 
+    def fa_bgzf(self):
+        """(bytes, plain bytes, members): the batch's _edited.fa text as BGZF members, copied out of the result's
+        page-locked buffer; needs set_apply(APPLY_BGZF) and set_fa_names() before the polish call"""
+        ptr, nb, plain, members = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._lib.ntedit_hip_result_fa_bgzf(self._h, ctypes.byref(ptr), ctypes.byref(nb), ctypes.byref(plain),
+                                                 ctypes.byref(members))
+        if rc:
+            self._result_error("result_fa_bgzf", rc)
+        return (ctypes.string_at(ptr.value, nb.value) if nb.value else b""), plain.value, members.value
+
     def free(self):
         if self._h:
             self._lib.ntedit_hip_result_free(self._h)
@@ -342,9 +352,35 @@ class Polisher:
     def set_apply(self, flags):
         """ntedit_hip_set_apply: 0, APPLY_EDITED (the result keeps the edited contigs in HBM: Result.edited()),
         APPLY_QV (k-mer counts before and after: Result.qv()), APPLY_SHARED (what APPLY_QV runs, and the present k-mers
-        of the batch and of the edited bases marked for the completeness: shared_counts()) or any of them together, for
-        the polish_batch calls that follow"""
+        of the batch and of the edited bases marked for the completeness: shared_counts()), APPLY_BGZF (the batch's
+        _edited.fa text compressed on the device: set_fa_names(), Result.fa_bgzf()) or any of them together, for the
+        polish_batch calls that follow"""
         self._check(self._lib.ntedit_hip_set_apply(self._h, int(flags)), "set_apply")
+
+    def set_fa_names(self, names):
+        """the header lines (bytes, without '>') of the entries of the NEXT polish_batch call: APPLY_BGZF needs them"""
+        arr = (ctypes.c_char_p * max(len(names), 1))(*[bytes(n) for n in names])
+        self._check(self._lib.ntedit_hip_set_fa_names(self._h, arr, len(names)), "set_fa_names")
+
+    def bgzf_deflate(self, data=None, device_ptr=None, n=None):
+        """bytes (or n device bytes at device_ptr) as BGZF members without the EOF member (ntedit_hip_bgzf_deflate)"""
+        if device_ptr is not None:
+            ptr, on_device = ctypes.c_void_p(device_ptr), 1
+        else:
+            keep, ptr = Result._blob_ptr(data)
+            n, on_device = len(data), 0
+        cap = int(self._lib.ntedit_hip_bgzf_bound(n))
+        out = ctypes.create_string_buffer(max(cap, 1))
+        need = ctypes.c_uint64()
+        self._check(self._lib.ntedit_hip_bgzf_deflate(self._h, ptr, n, on_device, out, cap, ctypes.byref(need)),
+                    "bgzf_deflate")
+        return out.raw[:need.value]
+
+    def bgzf_info(self):
+        """ntedit_hip_bgzf_info of the last call that compressed: _lib.BgzfStats"""
+        st = _lib.BgzfStats()
+        self._check(self._lib.ntedit_hip_bgzf_info(self._h, ctypes.byref(st)), "bgzf_info")
+        return st
 
     def apply_info(self):
         """ntedit_hip_apply_info of the last polish_batch: _lib.ApplyStats"""

@@ -261,6 +261,7 @@ def parse(argv=None):
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--qv", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     ap.add_argument("--completeness", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
+    ap.add_argument("--bgzip", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     g = ap.add_argument_group("polishing straight from reads (--reads replaces -r; the options of `ntedit --reads`, "
                               "the same filter; every rank builds its share and holds the whole filter)")
     g.add_argument("--reads", nargs="*", metavar="FILE", help="input reads, FASTA or FASTQ, plain or gzip")
@@ -304,6 +305,9 @@ def parse(argv=None):
         for flag, dest in READS_OPTIONS:
             if getattr(args, dest) not in (None, False):
                 raise Refused(flag + ": only with --reads")
+    if args.bgzip:  # (behind every older refusal)
+        raise Refused("--bgzip: the gather that merges the ranks' pieces by their byte index knows plain text only; run "
+                      "`ntedit --bgzip` on one GPU")
     return args
 
 
