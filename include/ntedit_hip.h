@@ -1064,6 +1064,48 @@ typedef struct ntedit_hip_bgzf_stats
 } ntedit_hip_bgzf_stats;
 int ntedit_hip_bgzf_info(ntedit_hip_ctx* ctx, ntedit_hip_bgzf_stats* st);
 
+/* ---- the unsupported regions of a polish as intervals (no counterpart in the reference) -----------------
+ * Where the QV rows say how many k-mers of an entry the filter does not hold, the track says where they lie.  A batch has n
+ * positions and entries e in batch order, entry e at [offs[e], offs[e] + lens[e]); entries do not overlap and may abut.  An
+ * absent bitmap has one bit per k-mer start: position p is bit p % 64 of word p / 64 (ntedit_hip_screen's layout).
+ *   A position p is a MARKED START of entry e iff its bit is set and offs[e] <= p < offs[e] + lens[e] - k + 1 -- the starts
+ *   ntedit_hip_qv_row counts as absent.  Bits anywhere else are ignored: separators, the last k - 1 positions of an entry,
+ *   padding behind n, entries shorter than k.
+ *   An INTERVAL of entry e is a maximal sequence of its marked starts p1 < ... < pm in which consecutive starts are at most
+ *   k apart: what `bedtools merge` makes of the k-mers' spans [p, p + k), overlapping and book-ended spans joined.  An
+ *   interval never continues into another entry, whatever the gap.
+ *   Its record: entry = e, begin = p1 - offs[e], end = pm - offs[e] + k, absent = m.  Records are ordered by entry, then by
+ *   begin.  Per entry the absent counts sum to the QV row's absent count; end - begin sums to the unsupported bases.
+ * NTEDIT_HIP_APPLY_TRACK (ntedit_hip_set_apply, beside the other flags): ntedit_hip_polish_batch does everything APPLY_QV
+ * does (ntedit_hip_result_qv still answers only with APPLY_QV; the same limits: k, no segments) and extracts the intervals
+ * of both bitmaps: before, in the batch's coordinates; after, in those of the edited entries. */
+#define NTEDIT_HIP_APPLY_TRACK 16u
+typedef struct ntedit_hip_track_interval
+{
+	uint32_t entry, begin, end, absent;
+} ntedit_hip_track_interval;
+/* The intervals of a result polished with APPLY_TRACK (NTEDIT_E_ARG otherwise; ntedit_hip_result_last_error() says why).
+ * which: 0 before, 1 after.  *n = their number; they are copied into out[0 .. cap) (NTEDIT_E_OVERFLOW when cap is less,
+ * with *n set).  The result keeps them in host memory of its own until ntedit_hip_result_free(). */
+int ntedit_hip_result_track(const ntedit_hip_result* r, int which, ntedit_hip_track_interval* out, uint64_t cap, uint64_t* n);
+/* Stand-alone: the intervals of any bitmap.  bitmap: ceil(n_positions / 64) words; offs, lens: n_entries entries as above,
+ * inside [0, n_positions); all host arrays, copied in and out by the call.  k: 1 .. 1024.  *n = the number of intervals;
+ * NTEDIT_E_OVERFLOW when cap is less. */
+int ntedit_hip_track_extract(ntedit_hip_ctx* ctx, const uint64_t* bitmap, uint64_t n_positions, const uint64_t* offs, const uint32_t* lens,
+                             uint32_t n_entries, uint32_t k, ntedit_hip_track_interval* out, uint64_t cap, uint64_t* n);
+/* The context's last call that extracted (a polish call with APPLY_TRACK: [0] before, [1] after; ntedit_hip_track_extract:
+ * [0], and [1] zero): HIP-event time of the extraction's kernels, the intervals, the bases they cover. */
+typedef struct ntedit_hip_track_stats
+{
+	float ms[2];
+	uint64_t intervals[2];
+	uint64_t bases[2];
+} ntedit_hip_track_stats;
+int ntedit_hip_track_info(ntedit_hip_ctx* ctx, ntedit_hip_track_stats* st);
+/* One BED row, "name<TAB>begin<TAB>end<TAB>absent\n"; name is cut at its first space or tab (the sequence name as faidx
+ * and IGV understand it).  Host only: no context, no device. */
+int ntedit_hip_track_format_row(const char* name, const ntedit_hip_track_interval* iv, char* out, uint64_t cap);
+
 /* The reference's candidate tables -- num_tries, polish_bases_array / snv_bases_array, multi_possible_bases (ntedit.cpp:172,
  * 176-199, 203-348) -- as the device code holds them (one GPU thread runs the machine's own candidate_bases /
  * insertion_candidate), as text: "num_tries 0 1 5 21 85 341", "polish A TCG", ..., "snv N ATCG", "multi A A AA AC ...".

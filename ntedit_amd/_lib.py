@@ -149,7 +149,7 @@ class SettleStats(ctypes.Structure):
     _fields_ = [("events_seen", ctypes.c_uint64), ("events_settled", ctypes.c_uint64), ("ms", ctypes.c_float)]
 
 
-APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF = 1, 2, 4, 8
+APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF, APPLY_TRACK = 1, 2, 4, 8, 16
 
 
 class QvRow(ctypes.Structure):
@@ -175,6 +175,20 @@ class BgzfStats(ctypes.Structure):
 
 
 BGZF_BLOCK = 65280  # plain bytes of a member
+
+
+class TrackInterval(ctypes.Structure):
+    """ntedit_hip_track_interval: one unsupported region of an entry (APPLY_TRACK, ntedit_hip_track_extract)"""
+    _fields_ = [("entry", ctypes.c_uint32), ("begin", ctypes.c_uint32), ("end", ctypes.c_uint32),
+                ("absent", ctypes.c_uint32)]
+
+
+TRACK_DTYPE = [(name, "<u4") for name, _ in TrackInterval._fields_]
+
+
+class TrackStats(ctypes.Structure):
+    """ntedit_hip_track_stats: the context's last call that extracted intervals; [0] before, [1] after"""
+    _fields_ = [("ms", ctypes.c_float * 2), ("intervals", ctypes.c_uint64 * 2), ("bases", ctypes.c_uint64 * 2)]
 
 
 class SharedStats(ctypes.Structure):
@@ -235,6 +249,7 @@ class Segment(ctypes.Structure):
 
 SEG_NO_HEADER, SEG_NO_NEWLINE, SEG_SKIP = 1, 2, 4
 E_ARG, E_SEGMENT = -1, -7
+E_OVERFLOW = -4
 EDIT_SUB, EDIT_INS, EDIT_DEL, EDIT_SNV_KEPT = 1, 2, 3, 4
 
 
@@ -301,6 +316,7 @@ EXPORTS = [
     "ntedit_hip_completeness_header", "ntedit_hip_completeness_format_row",
     "ntedit_hip_set_fa_names", "ntedit_hip_result_fa_bgzf", "ntedit_hip_bgzf_deflate", "ntedit_hip_bgzf_deflate_model",
     "ntedit_hip_bgzf_bound", "ntedit_hip_bgzf_eof", "ntedit_hip_bgzf_info",
+    "ntedit_hip_result_track", "ntedit_hip_track_extract", "ntedit_hip_track_info", "ntedit_hip_track_format_row",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -509,5 +525,10 @@ def load():
     lib.ntedit_hip_bgzf_eof.argtypes = [pu32]
     lib.ntedit_hip_bgzf_eof.restype = vp
     lib.ntedit_hip_bgzf_info.argtypes = [vp, ctypes.POINTER(BgzfStats)]
+    # the unsupported regions as intervals (nte_track.hip)
+    lib.ntedit_hip_result_track.argtypes = [vp, ci, vp, u64, pu64]
+    lib.ntedit_hip_track_extract.argtypes = [vp, vp, u64, vp, vp, u32, u32, vp, u64, pu64]
+    lib.ntedit_hip_track_info.argtypes = [vp, ctypes.POINTER(TrackStats)]
+    lib.ntedit_hip_track_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(TrackInterval), ctypes.c_char_p, u64]
     _lib = lib
     return lib

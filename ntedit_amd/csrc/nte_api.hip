@@ -7,6 +7,7 @@
 #include "nte_settle.h"
 #include "nte_apply.h"
 #include "nte_bgzf_launch.h"
+#include "nte_track.h"
 
 #include "../../include/ntedit_hip.h"
 #include "../host/bfio.h"
@@ -156,6 +157,10 @@ struct ntedit_hip_ctx
 	bool fa_names_set = false;
 	ntedit_hip_bgzf_stats bgzf_last = { 0.f, 0.f, 0.f, 0, 0, 0, 0 };
 	std::vector<PinBuf> bgzf_pool; // page-locked buffers for the members, apart from pin_pool (under pin_mu): filled by reserve
+	// the interval extractor (nte_track.hip): the tiles' counts, the records and their side array, four words of totals
+	DevBuf tr_tiles, tr_recs, tr_upto, tr_totals;
+	hipEvent_t tr_evt[4] = { nullptr, nullptr, nullptr, nullptr };
+	ntedit_hip_track_stats track_last = { { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
 	// linear counting of the draft's present k-mers (k_mark; ntedit_hip_shared_*): two mark arrays of the PRIMARY filter's
 	// size, before and after; they go when the slot gets another filter (drop_filter)
 	DevBuf sh_marks[2];
@@ -198,6 +203,14 @@ struct ntedit_hip_result
 	PinBuf bgzf_buf;
 	u64 bgzf_bytes = 0, bgzf_plain = 0;
 	u32 bgzf_members = 0;
+	// NTEDIT_HIP_APPLY_TRACK: the intervals before and after (malloc)
+	ntedit_hip_track_interval* track[2] = { nullptr, nullptr };
+	u64 track_n[2] = { 0, 0 };
+	~ntedit_hip_result()
+	{
+		free(track[0]);
+		free(track[1]);
+	}
 };
 
 namespace {

@@ -1060,6 +1060,90 @@ PolishRun::finish()
 	return 0;
 }
 
+// The interval extractor (nte_track.hip) over a bitmap and the entries of its batch, all in device memory, on stream s:
+// count and scan, three words to the host, the record buffer sized from them, emit and finish, the records to host memory
+// (malloc, *out; null for none).  The stream is idle when it returns.  Crosses PCIe: four words and the records.
+int
+track_run(ntedit_hip_ctx* c, hipStream_t s, const u64* d_bitmap, u64 n, const u64* d_offs, const u32* d_lens, u32 n_entries, u32 k, int which,
+          ntedit_hip_track_interval** out, u64* n_out)
+{
+	int rc;
+	free(*out);
+	*out = nullptr;
+	*n_out = 0;
+	c->track_last.ms[which] = 0.f;
+	c->track_last.intervals[which] = c->track_last.bases[which] = 0;
+	const u64 n_tiles = track_tiles(n);
+	if (n_tiles == 0 || n_entries == 0) {
+		return 0;
+	}
+	if (n_tiles > 0x7FFFFFFFull) {
+		return fail(c, NTEDIT_E_ARG, "track: batch too large");
+	}
+	for (auto& e : c->tr_evt) {
+		if (!e) {
+			HIP_TRY(c, hipEventCreate(&e));
+		}
+	}
+	if ((rc = ensure(c, c->tr_tiles, (size_t)n_tiles * sizeof(TrackTile))) || (rc = ensure(c, c->tr_totals, 64))) {
+		return rc;
+	}
+	const TrackArgs a = { d_bitmap, n, d_offs, d_lens, n_entries, k };
+	TrackTile* tiles = (TrackTile*)c->tr_tiles.p;
+	u64* totals = (u64*)c->tr_totals.p;
+	u64 h_tot[4] = { 0, 0, 0, 0 };
+	HIP_TRY(c, hipEventRecord(c->tr_evt[0], s));
+	launch_track_count(s, a, tiles, totals);
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipEventRecord(c->tr_evt[1], s));
+	HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 32, hipMemcpyDeviceToHost, s));
+	HIP_TRY(c, hipStreamSynchronize(s));
+	if (h_tot[0] != h_tot[1] || h_tot[0] > h_tot[2]) {
+		return fail(c, NTEDIT_E_INTERNAL, "track: %llu interval starts, %llu ends, %llu marked starts", (unsigned long long)h_tot[0],
+		            (unsigned long long)h_tot[1], (unsigned long long)h_tot[2]);
+	}
+	float t0 = 0.f, t1 = 0.f;
+	(void)hipEventElapsedTime(&t0, c->tr_evt[0], c->tr_evt[1]);
+	const u64 n_recs = h_tot[0];
+	if (n_recs) {
+		if ((rc = ensure(c, c->tr_recs, (size_t)n_recs * sizeof(TrackInterval))) || (rc = ensure(c, c->tr_upto, (size_t)n_recs * 4))) {
+			return rc;
+		}
+		ntedit_hip_track_interval* host = (ntedit_hip_track_interval*)malloc((size_t)n_recs * sizeof(ntedit_hip_track_interval));
+		if (!host) {
+			return fail(c, NTEDIT_E_OVERFLOW, "track: no host memory for %llu intervals", (unsigned long long)n_recs);
+		}
+		hipError_t he = hipEventRecord(c->tr_evt[2], s);
+		launch_track_emit(s, a, tiles, (TrackInterval*)c->tr_recs.p, (u32*)c->tr_upto.p, n_recs, totals);
+		if (he == hipSuccess) {
+			he = hipGetLastError();
+		}
+		if (he == hipSuccess) {
+			he = hipEventRecord(c->tr_evt[3], s);
+		}
+		if (he == hipSuccess) {
+			he = hipMemcpyAsync(host, c->tr_recs.p, (size_t)n_recs * sizeof(TrackInterval), hipMemcpyDeviceToHost, s);
+		}
+		if (he == hipSuccess) {
+			he = hipMemcpyAsync(h_tot, totals, 32, hipMemcpyDeviceToHost, s);
+		}
+		if (he == hipSuccess) {
+			he = hipStreamSynchronize(s);
+		}
+		if (he != hipSuccess) {
+			free(host);
+			return fail(c, NTEDIT_E_DEVICE, "track: %s", hipGetErrorString(he));
+		}
+		(void)hipEventElapsedTime(&t1, c->tr_evt[2], c->tr_evt[3]);
+		*out = host;
+		*n_out = n_recs;
+	}
+	c->track_last.ms[which] = t0 + t1;
+	c->track_last.intervals[which] = n_recs;
+	c->track_last.bases[which] = h_tot[3];
+	return 0;
+}
+
 // The device applier and the QV counts (nte_apply.hip), behind everything a plain call does: the streams are idle, the
 // arena and the first-chunk table in HBM are what collect() copied (the re-runs of parked events write both on the
 // device), c->bitmap still holds step 1's answer (k_assess writes a map of its own, c->runmap).  Crosses PCIe: five
@@ -1076,10 +1160,14 @@ PolishRun::apply()
 	int rc;
 	hipStream_t s = c->stream;
 	const u32 k = c->dp.k;
-	if ((flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED)) && k > QV_MAX_K) {
+	if ((flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) && k > QV_MAX_K) {
 		return fail(c, NTEDIT_E_UNSUPPORTED, "apply: the QV counts take k up to %u", QV_MAX_K);
 	}
 	const bool shared = (flags & NTEDIT_HIP_APPLY_SHARED) != 0;
+	const bool track = (flags & NTEDIT_HIP_APPLY_TRACK) != 0;
+	if (track) {
+		c->track_last = ntedit_hip_track_stats{ { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
+	}
 	if (shared && (rc = shared_begin(c, "polish_batch"))) { // (the completeness marks: begun here if that was not done)
 		return rc;
 	}
@@ -1165,8 +1253,9 @@ PolishRun::apply()
 	if (he == hipSuccess) {
 		he = hipMemcpyAsync(r->e_lens.data(), a.out_lens, nc * 4, hipMemcpyDeviceToHost, s);
 	}
-	// (APPLY_SHARED runs everything APPLY_QV runs and marks the present k-mers of both screenings: k_mark)
-	bool qv = (flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED)) != 0;
+	// (APPLY_SHARED runs everything APPLY_QV runs and marks the present k-mers of both screenings: k_mark; APPLY_TRACK
+	// runs it too and extracts the intervals of both bitmaps: nte_track.hip)
+	bool qv = (flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) != 0;
 	int qrc = 0;
 	float ms_rescreen = 0.f;
 	if (he == hipSuccess && qv) {
@@ -1200,8 +1289,12 @@ PolishRun::apply()
 				launch_qv_rows(s, rows, a.lens, a.out_lens, n_contigs);
 				launch_qv_count(s, d_seq, n, a.offs, a.lens, n_contigs, bm_before, k, rows, 0);
 				(void)hipEventRecord(c->ap_evt[3], s);
-				// (with -s 1 bm_before is bm2, which the screening below overwrites: the before-mark is queued here)
-				qrc = shared ? launch_mark(c, s, d_seq, n, f0, bm_before, n_words, 0) : 0;
+				// (with -s 1 bm_before is bm2, which the screening below overwrites: the before-extraction and the before-mark
+				// are queued here)
+				qrc = track ? track_run(c, s, bm_before, n, a.offs, a.lens, n_contigs, k, 0, &r->track[0], &r->track_n[0]) : 0;
+				if (!qrc) {
+					qrc = shared ? launch_mark(c, s, d_seq, n, f0, bm_before, n_words, 0) : 0;
+				}
 			}
 			if (!qrc) {
 				qrc = rescreen ? bin_reset(c, s) : 0;
@@ -1222,6 +1315,9 @@ PolishRun::apply()
 				he = hipMemcpyAsync(r->qv.data(), rows, nc * sizeof(QvRow), hipMemcpyDeviceToHost, s);
 				if (shared && he == hipSuccess) {
 					qrc = launch_mark(c, s, a.out, total_bytes, f0, bm2, nw2, 1);
+				}
+				if (track && he == hipSuccess && !qrc) {
+					qrc = track_run(c, s, bm2, total_bytes, a.out_offs, a.out_lens, n_contigs, k, 1, &r->track[1], &r->track_n[1]);
 				}
 			}
 		}
@@ -1560,8 +1656,15 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		    (rc = ensure(c, c->ap_edited, (size_t)(n + n / 64 + 4096)))) {
 			return rc;
 		}
-		if ((c->apply_flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED)) && (rc = ensure(c, c->ap_bitmap, (size_t)(n_words + n_words / 64 + 64) * 8))) {
+		if ((c->apply_flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) &&
+		    (rc = ensure(c, c->ap_bitmap, (size_t)(n_words + n_words / 64 + 64) * 8))) {
 			return rc;
+		}
+		if (c->apply_flags & NTEDIT_HIP_APPLY_TRACK) { // (the tiles' counts; about as many intervals as events)
+			if ((rc = ensure(c, c->tr_tiles, (size_t)track_tiles(n + n / 64 + 4096) * sizeof(TrackTile))) || (rc = ensure(c, c->tr_totals, 64)) ||
+			    (rc = ensure(c, c->tr_recs, (size_t)n_ev * sizeof(TrackInterval))) || (rc = ensure(c, c->tr_upto, (size_t)n_ev * 4))) {
+				return rc;
+			}
 		}
 		if (c->apply_flags & NTEDIT_HIP_APPLY_BGZF) { // (the image: the edited bases, and per entry '>', a header line, '\n')
 			std::string why;

@@ -51,7 +51,7 @@ result_refuse(const ntedit_hip_result* r, const char* what)
 int
 ntedit_hip_set_apply(ntedit_hip_ctx* c, uint32_t flags)
 {
-	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_BGZF))) {
+	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_BGZF | NTEDIT_HIP_APPLY_TRACK))) {
 		return fail(c, NTEDIT_E_ARG, "set_apply: unknown flag");
 	}
 	c->apply_flags = flags;
@@ -138,6 +138,89 @@ uint32_t
 ntedit_hip_apply_tile(void)
 {
 	return APPLY_TILE;
+}
+
+// ---- the interval extractor (nte_track.hip)
+static_assert(sizeof(ntedit_hip_track_interval) == sizeof(TrackInterval) && sizeof(TrackInterval) == 16, "the records are copied as they stand");
+
+int
+ntedit_hip_result_track(const ntedit_hip_result* r, int which, ntedit_hip_track_interval* out, uint64_t cap, uint64_t* n)
+{
+	if (!r || !n || which < 0 || which > 1 || (cap && !out)) {
+		return result_refuse(r, "result_track: bad argument");
+	}
+	if (!(r->apply_flags & NTEDIT_HIP_APPLY_TRACK)) {
+		return result_refuse(r, "result_track: the batch was polished without the APPLY_TRACK flag (ntedit_hip_set_apply)");
+	}
+	*n = r->track_n[which];
+	if (*n > cap) {
+		g_result_err = "result_track: the buffer is too small";
+		return NTEDIT_E_OVERFLOW;
+	}
+	if (*n) {
+		memcpy(out, r->track[which], (size_t)*n * sizeof(ntedit_hip_track_interval));
+	}
+	return 0;
+}
+
+int
+ntedit_hip_track_extract(ntedit_hip_ctx* c, const uint64_t* bitmap, uint64_t n_positions, const uint64_t* offs, const uint32_t* lens,
+                         uint32_t n_entries, uint32_t k, ntedit_hip_track_interval* out, uint64_t cap, uint64_t* n)
+{
+	if (!c || !n || (n_positions && !bitmap) || (n_entries && (!offs || !lens)) || (cap && !out)) {
+		return fail(c, NTEDIT_E_ARG, "track_extract: bad argument");
+	}
+	*n = 0;
+	if (k == 0 || k > TRACK_MAX_K) {
+		return fail(c, NTEDIT_E_UNSUPPORTED, "track_extract: k from 1 to %u", TRACK_MAX_K);
+	}
+	for (u32 i = 0; i < n_entries; i++) {
+		if (offs[i] > n_positions || lens[i] > n_positions - offs[i] || (i + 1 < n_entries && offs[i] + lens[i] > offs[i + 1])) {
+			return fail(c, NTEDIT_E_ARG, "track_extract: entry %u breaks the batch layout", i);
+		}
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	c->track_last = ntedit_hip_track_stats{ { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
+	if (n_positions == 0 || n_entries == 0) {
+		return 0;
+	}
+	int rc;
+	const u64 n_words = (n_positions + 63) / 64;
+	if ((rc = ensure(c, c->ap_bitmap, (size_t)(n_words + 8) * 8)) || (rc = ensure(c, c->offs, (size_t)n_entries * 8)) ||
+	    (rc = ensure(c, c->lens, (size_t)n_entries * 4))) {
+		return rc;
+	}
+	hipStream_t s = c->stream;
+	HIP_TRY(c, hipMemcpyAsync(c->ap_bitmap.p, bitmap, (size_t)n_words * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(c, hipMemcpyAsync(c->offs.p, offs, (size_t)n_entries * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(c, hipMemcpyAsync(c->lens.p, lens, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+	ntedit_hip_track_interval* recs = nullptr;
+	u64 n_recs = 0;
+	rc = track_run(c, s, (const u64*)c->ap_bitmap.p, n_positions, (const u64*)c->offs.p, (const u32*)c->lens.p, n_entries, k, 0, &recs, &n_recs);
+	if (rc) {
+		(void)hipStreamSynchronize(s);
+		return rc;
+	}
+	*n = n_recs;
+	if (n_recs > cap) {
+		free(recs);
+		return fail(c, NTEDIT_E_OVERFLOW, "track_extract: %llu intervals, the buffer has room for %llu", (unsigned long long)n_recs, (unsigned long long)cap);
+	}
+	if (n_recs) {
+		memcpy(out, recs, (size_t)n_recs * sizeof(ntedit_hip_track_interval));
+	}
+	free(recs);
+	return 0;
+}
+
+int
+ntedit_hip_track_info(ntedit_hip_ctx* c, ntedit_hip_track_stats* st)
+{
+	if (!c || !st) {
+		return fail(c, NTEDIT_E_ARG, "track_info: bad argument");
+	}
+	*st = c->track_last;
+	return 0;
 }
 
 // ---- the BGZF writer (nte_bgzf_deflate.hip)

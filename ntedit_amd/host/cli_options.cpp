@@ -116,6 +116,21 @@ static const char HELP_BGZIP[] = PROGRAM
     "			members; --report adds {\"bgzip\": {...}}.  Not with --shard\n"
     "	--help-bgzip,	display this paragraph and exit\n\n";
 
+static const char HELP_BED[] = PROGRAM
+    " --qv --bed\n\n"
+    "	--bed,		with --qv: where the k-mers that --qv counts as absent lie, as two BED tracks -- <prefix>_absent_before.bed in\n"
+    "			the draft's names and coordinates, <prefix>_absent_after.bed in those of <prefix>_edited.fa.  A row is a\n"
+    "			region the filter does not support: the k-mer spans [p, p + k) of a contig's absent k-mers, overlapping and\n"
+    "			book-ended spans merged (as bedtools merge does), never across contigs.  Four columns, no header line: the\n"
+    "			sequence name (the header line up to its first space or tab), begin, end (0-based, half open) and the number\n"
+    "			of absent k-mers in the region; per contig that column sums to absent_before / absent_after of\n"
+    "			<prefix>_qv.tsv.  A single wrong base shows as a region of 2k - 1 bases with k absent k-mers.  Rows are in\n"
+    "			_edited.fa's order.  The regions are extracted on the GPU from the bitmaps --qv screens anyway; only the\n"
+    "			intervals cross to the host.  With -k K1,K2,... an earlier round writes <prefix>_k<Ki>_absent_*.bed.  One\n"
+    "			summary line reports intervals and covered bases before and after; --report adds {\"bed\": {...}}.  Not\n"
+    "			with --shard\n"
+    "	--help-bed,	display this paragraph and exit\n\n";
+
 static const char shortopts[] = "t:f:s:k:z:b:r:v:d:i:X:Y:x:y:m:c:j:s:e:a:l:p:q:";
 enum
 {
@@ -150,7 +165,9 @@ enum
 	OPT_STORE_CAP,
 	OPT_GPU_PARSE,
 	OPT_BGZIP,
-	OPT_HELP_BGZIP
+	OPT_HELP_BGZIP,
+	OPT_BED,
+	OPT_HELP_BED
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -206,6 +223,8 @@ static const struct option longopts[] = {
 	{ "gpu_parse", no_argument, nullptr, OPT_GPU_PARSE },
 	{ "bgzip", no_argument, nullptr, OPT_BGZIP },
 	{ "help-bgzip", no_argument, nullptr, OPT_HELP_BGZIP },
+	{ "bed", no_argument, nullptr, OPT_BED },
+	{ "help-bed", no_argument, nullptr, OPT_HELP_BED },
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -538,6 +557,12 @@ parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOptio
 		case OPT_HELP_BGZIP:
 			fputs(HELP_BGZIP, stderr);
 			exit(EXIT_SUCCESS);
+		case OPT_BED:
+			o->bed = true;
+			break;
+		case OPT_HELP_BED:
+			fputs(HELP_BED, stderr);
+			exit(EXIT_SUCCESS);
 		case OPT_HELP:
 			fputs(USAGE, stderr);
 			exit(EXIT_SUCCESS);
@@ -653,6 +678,10 @@ parse_cli(int argc, char** argv)
 	if (o.bgzip && o.shard_given) {
 		// (behind every older refusal)
 		fail("--bgzip and --shard: the byte index of the shards and the gather that merges them know plain text only; run --bgzip on the whole draft");
+	}
+	if (o.bed && !o.qv) {
+		// (--bed with --shard: --qv's refusal above has answered)
+		fail("--bed: only with --qv (the tracks are made of the bitmaps the QV screenings leave)");
 	}
 	if (o.params.snv) {
 		// ntedit.cpp:2411-2417

@@ -160,6 +160,18 @@ finish_bgzip(const RoundTotals& t, const std::string& fa_path, bool report)
 }
 
 void
+finish_bed(const RoundTotals& t, const std::string paths[2], bool report)
+{
+	printf("unsupported regions: before %llu intervals over %llu bases, after %llu over %llu; tracks: %s, %s\n", t.bed_intervals[0],
+	       t.bed_bases[0], t.bed_intervals[1], t.bed_bases[1], paths[0].c_str(), paths[1].c_str());
+	if (report) {
+		printf("{\"bed\": {\"intervals_before\": %llu, \"bases_before\": %llu, \"intervals_after\": %llu, \"bases_after\": %llu, "
+		       "\"extract_before_ms\": %.3f, \"extract_after_ms\": %.3f}}\n",
+		       t.bed_intervals[0], t.bed_bases[0], t.bed_intervals[1], t.bed_bases[1], t.ms_track[0], t.ms_track[1]);
+	}
+}
+
+void
 report_qv(const RoundTotals& t)
 {
 	printf("{\"qv\": {\"kmers_before\": %llu, \"absent_before\": %llu, \"kmers_after\": %llu, \"absent_after\": %llu, \"apply_ms\": %.3f, "

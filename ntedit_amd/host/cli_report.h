@@ -1,5 +1,5 @@
 // cli_report.h -- what a polishing round says at its end: the QV table's total and summary line, the completeness table and
-// line, and the --report JSON lines.
+// line, the --bgzip and --bed lines, and the --report JSON lines.
 #pragma once
 
 #include "../../include/ntedit_hip.h"
@@ -27,6 +27,10 @@ struct RoundTotals
 	double ms_bgzf_image = 0, ms_bgzf_deflate = 0, ms_bgzf_copy = 0;
 	unsigned long long bgzf_plain = 0, bgzf_bytes = 0, bgzf_members = 0, bgzf_stored = 0;
 
+	// --bed: intervals and covered bases before [0] and after [1], the extraction's times
+	unsigned long long bed_intervals[2] = { 0, 0 }, bed_bases[2] = { 0, 0 };
+	double ms_track[2] = { 0, 0 };
+
 	void add(const ntedit_hip_stats& st);
 	void add(const ntedit_hip_bgzf_stats& bs);
 	void add(const ntedit_hip_qv_row& row);
@@ -38,6 +42,8 @@ void finish_qv(ntedit_hip_ctx* ctx, FILE* qv_f, const std::string& qv_path, uint
 void finish_completeness(ntedit_hip_ctx* ctx, const std::string& prefix, uint32_t k, bool report);
 // --bgzip: the summary line (the file's end-of-file member is counted in neither figure); with --report its JSON
 void finish_bgzip(const RoundTotals& t, const std::string& fa_path, bool report);
+// --bed: the summary line; with --report its JSON
+void finish_bed(const RoundTotals& t, const std::string paths[2], bool report);
 // --report
 void report_qv(const RoundTotals& t);
 void report_round(const RoundTotals& t);

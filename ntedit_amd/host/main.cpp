@@ -7,6 +7,8 @@
 // <prefix>_edited.fa and <prefix>_changes.tsv byte-identical to the reference's, plus <prefix>_variants.vcf (the
 // ##fileDate line carries today's date, as in the reference) -- and the summaries (cli_report.cpp).  With --bgzip the
 // edited draft is <prefix>_edited.fa.gz: the GPU stage's results hold its BGZF members, the writer stage appends them.
+// With --qv --bed the results hold the unsupported regions before and after as intervals, and the writer stage appends
+// them to <prefix>_absent_before.bed and <prefix>_absent_after.bed.
 #include "../../include/ntedit_hip.h"
 #include "cli_batches.h"
 #include "cli_common.h"
@@ -35,14 +37,15 @@ struct Run
 };
 
 // what the three pipeline stages of a round share.  Each total has one writer: the reader stage `bases` and `s_read`, the
-// GPU stage `s_call` and the --qv times, the writer stage the rest; they are read after the stages are joined.
+// GPU stage `s_call` and the --qv and --bed times, the writer stage the rest; they are read after the stages are joined.
 struct Round
 {
 	const CliOptions& opt;
 	ntedit_hip_ctx* ctx;
 	uint32_t k = 0;
-	std::string fa_path, tsv_path, vcf_path, qv_path;
+	std::string fa_path, tsv_path, vcf_path, qv_path, bed_path[2];
 	FILE *qv_f = nullptr, *index_f = nullptr;
+	FILE* bed_f[2] = { nullptr, nullptr }; // --bed: <prefix>_absent_before.bed, _absent_after.bed
 	int fa_fd = -1; // --bgzip: <prefix>_edited.fa.gz, open for the writer stage
 	ntedit_hip_annot* annot = nullptr;
 	Channel free_q, gpu_q, write_q;
@@ -145,7 +148,8 @@ prepare_device(Run& run, const CliOptions& opt, const ntedit_hip_params& p, bool
 	if (ntedit_hip_set_params(ctx, &p) != 0) {
 		fail("%s", ntedit_hip_last_error(ctx));
 	}
-	const uint32_t apply = (opt.qv ? NTEDIT_HIP_APPLY_QV | (opt.completeness ? NTEDIT_HIP_APPLY_SHARED : 0u) : 0u) | (opt.bgzip ? NTEDIT_HIP_APPLY_BGZF : 0u);
+	const uint32_t apply = (opt.qv ? NTEDIT_HIP_APPLY_QV | (opt.completeness ? NTEDIT_HIP_APPLY_SHARED : 0u) : 0u) | (opt.bgzip ? NTEDIT_HIP_APPLY_BGZF : 0u) |
+	                       (opt.bed ? NTEDIT_HIP_APPLY_TRACK : 0u);
 	if (apply && ntedit_hip_set_apply(ctx, apply) != 0) {
 		fail("%s", ntedit_hip_last_error(ctx));
 	}
@@ -199,6 +203,13 @@ open_outputs(Round& r, const ntedit_hip_params& p, int counting, const std::stri
 			fail("cannot write `%s'", r.qv_path.c_str());
 		}
 		fputs(ntedit_hip_qv_header(), r.qv_f);
+	}
+	// --bed: the two tracks, the rows of a batch as it comes back
+	for (int which = 0; opt.bed && which < 2; which++) {
+		r.bed_f[which] = fopen(r.bed_path[which].c_str(), "wb");
+		if (!r.bed_f[which]) {
+			fail("cannot write `%s'", r.bed_path[which].c_str());
+		}
 	}
 	if (!opt.vcf.empty()) {
 		// -l: annotated variants (e.g. clinvar.vcf[.gz]), ntedit.cpp:2524-2562
@@ -412,6 +423,35 @@ write_bgzf(Round& r, const uint8_t* p, uint64_t n)
 	}
 }
 
+// --bed: the rows of one batch's intervals, before or after, under the names of its entries
+static void
+write_bed_rows(Round& r, const ntedit_hip_result* res, const std::vector<const char*>& names, int which)
+{
+	uint64_t n = 0;
+	int rc = ntedit_hip_result_track(res, which, nullptr, 0, &n);
+	std::vector<ntedit_hip_track_interval> ivs((size_t)n);
+	if (rc == NTEDIT_E_OVERFLOW) {
+		rc = ntedit_hip_result_track(res, which, ivs.data(), n, &n);
+	}
+	if (rc != 0) {
+		fail("%s", ntedit_hip_result_last_error());
+	}
+	std::string line;
+	bool ok = true;
+	for (size_t i = 0; ok && i < ivs.size(); i++) {
+		ok = ivs[i].entry < names.size();
+		if (ok) {
+			line.resize(strlen(names[ivs[i].entry]) + 64);
+			ok = ntedit_hip_track_format_row(names[ivs[i].entry], &ivs[i], &line[0], line.size()) == 0 && fputs(line.c_str(), r.bed_f[which]) >= 0;
+			r.tot.bed_bases[which] += ivs[i].end - ivs[i].begin;
+		}
+	}
+	r.tot.bed_intervals[which] += ivs.size();
+	if (!ok) {
+		fail("cannot write `%s'", r.bed_path[which].c_str());
+	}
+}
+
 // Writer stage: renders the batches the GPU stage hands over, in order, and sums their statistics.
 static void
 write_batches(Round& r)
@@ -463,6 +503,9 @@ write_batches(Round& r)
 				fail("cannot write `%s'", r.qv_path.c_str());
 			}
 		}
+		for (int which = 0; r.opt.bed && which < 2; which++) {
+			write_bed_rows(r, w->res, names, which);
+		}
 		ntedit_hip_stats st;
 		ntedit_hip_result_stats(w->res, &st);
 		r.tot.add(st);
@@ -505,6 +548,11 @@ polish_batches(Round& r)
 			r.tot.ms_apply += as.ms_apply;
 			r.tot.ms_qv_screen += as.ms_screen;
 			r.tot.ms_qv_count += as.ms_count;
+		}
+		ntedit_hip_track_stats ts;
+		if (r.opt.bed && ntedit_hip_track_info(r.ctx, &ts) == 0) {
+			r.tot.ms_track[0] += ts.ms[0];
+			r.tot.ms_track[1] += ts.ms[1];
 		}
 		ntedit_hip_bgzf_stats bs;
 		if (r.opt.bgzip && ntedit_hip_bgzf_info(r.ctx, &bs) == 0) {
@@ -551,6 +599,8 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	r.tsv_path = prefix + "_changes.tsv";
 	r.vcf_path = prefix + "_variants.vcf";
 	r.qv_path = prefix + "_qv.tsv";
+	r.bed_path[0] = prefix + "_absent_before.bed";
+	r.bed_path[1] = prefix + "_absent_after.bed";
 	open_outputs(r, p, counting, draft);
 
 	// ---- the draft.  Plain multi-FASTA files are taken apart by several threads from a mapping of the file (fasta_map.h);
@@ -616,6 +666,11 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 			fail("cannot write `%s'", r.fa_path.c_str());
 		}
 	}
+	for (int which = 0; which < 2; which++) {
+		if (r.bed_f[which] && fclose(r.bed_f[which]) != 0) {
+			fail("cannot write `%s'", r.bed_path[which].c_str());
+		}
+	}
 	if (r.index_f && fclose(r.index_f) != 0) {
 		fail("cannot write `%s.index.tsv'", prefix.c_str());
 	}
@@ -635,6 +690,9 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	}
 	if (opt.bgzip) {
 		finish_bgzip(r.tot, r.fa_path, opt.report != 0);
+	}
+	if (opt.bed) {
+		finish_bed(r.tot, r.bed_path, opt.report != 0);
 	}
 	if (opt.report && opt.qv) {
 		report_qv(r.tot);

@@ -77,6 +77,23 @@ ntedit_hip_qv_format_row(const char* name, const ntedit_hip_qv_row* row, uint32_
 	return 0;
 }
 
+// ---- the unsupported regions as BED rows (the intervals come from nte_track.hip through ntedit_hip_result_track)
+
+int
+ntedit_hip_track_format_row(const char* name, const ntedit_hip_track_interval* iv, char* out, uint64_t cap)
+{
+	if (!name || !iv || !out) {
+		return NTEDIT_E_ARG;
+	}
+	std::string s(name, strcspn(name, " \t")); // (the sequence name as faidx and IGV understand it)
+	s += '\t' + std::to_string(iv->begin) + '\t' + std::to_string(iv->end) + '\t' + std::to_string(iv->absent) + '\n';
+	if (s.size() + 1 > cap) {
+		return NTEDIT_E_OVERFLOW;
+	}
+	memcpy(out, s.c_str(), s.size() + 1);
+	return 0;
+}
+
 // ---- k-mer completeness (linear counting: the marks come from k_mark through ntedit_hip_shared_counts)
 
 double

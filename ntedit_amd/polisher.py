@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF  # noqa: F401
+from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, TRACK_DTYPE, APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF, APPLY_TRACK  # noqa: F401
 
 PRIMARY, SECONDARY = 0, 1
 
@@ -185,6 +185,19 @@ class Result:
             self._result_error("result_qv", rc)
         return rows[:n_contigs]
 
+    def track(self, which):
+        """the unsupported regions before (which = 0) or after (1) the polish, one record per interval (dtype
+        _lib.TRACK_DTYPE: entry, begin, end, absent), ordered by entry, then begin; needs set_apply(APPLY_TRACK)"""
+        n = ctypes.c_uint64()
+        rc = self._lib.ntedit_hip_result_track(self._h, int(which), None, 0, ctypes.byref(n))
+        if rc and rc != _lib.E_OVERFLOW:
+            self._result_error("result_track", rc)
+        recs = np.zeros(max(n.value, 1), dtype=np.dtype(TRACK_DTYPE))
+        rc = self._lib.ntedit_hip_result_track(self._h, int(which), recs.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n))
+        if rc:
+            self._result_error("result_track", rc)
+        return recs[:n.value]
+
     def fa_bgzf(self):
         """(bytes, plain bytes, members): the batch's _edited.fa text as BGZF members, copied out of the result's
         page-locked buffer; needs set_apply(APPLY_BGZF) and set_fa_names() before the polish call"""
@@ -353,7 +366,8 @@ class Polisher:
         """ntedit_hip_set_apply: 0, APPLY_EDITED (the result keeps the edited contigs in HBM: Result.edited()),
         APPLY_QV (k-mer counts before and after: Result.qv()), APPLY_SHARED (what APPLY_QV runs, and the present k-mers
         of the batch and of the edited bases marked for the completeness: shared_counts()), APPLY_BGZF (the batch's
-        _edited.fa text compressed on the device: set_fa_names(), Result.fa_bgzf()) or any of them together, for the
+        _edited.fa text compressed on the device: set_fa_names(), Result.fa_bgzf()), APPLY_TRACK (what APPLY_QV runs, and
+        the unsupported regions before and after as intervals: Result.track()) or any of them together, for the
         polish_batch calls that follow"""
         self._check(self._lib.ntedit_hip_set_apply(self._h, int(flags)), "set_apply")
 
@@ -412,6 +426,49 @@ class Polisher:
             f.write(buf.value)
         return total
 
+    # ---- the unsupported regions as intervals (nte_track.hip)
+    def track_extract(self, bitmap, offs, lens, k, n=None):
+        """the intervals of any absent bitmap (uint64 words, position p = bit p % 64 of word p / 64) over the entries
+        offs / lens of a batch of n positions (default: 64 * len(bitmap)): records of dtype _lib.TRACK_DTYPE
+        (ntedit_hip_track_extract)"""
+        bitmap = np.ascontiguousarray(bitmap, dtype=np.uint64)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None  # noqa: E731
+        n = 64 * len(bitmap) if n is None else int(n)
+        if n > 64 * len(bitmap):
+            raise NtEditHipError("track_extract: %d positions need more than %d bitmap words" % (n, len(bitmap)))
+        args = (self._h, ptr(bitmap), n, ptr(offs), ptr(lens), len(offs), int(k))
+        found = ctypes.c_uint64()
+        rc = self._lib.ntedit_hip_track_extract(*args, None, 0, ctypes.byref(found))
+        if rc != _lib.E_OVERFLOW:
+            self._check(rc, "track_extract")
+        recs = np.zeros(max(found.value, 1), dtype=np.dtype(TRACK_DTYPE))
+        if found.value:
+            self._check(self._lib.ntedit_hip_track_extract(*args, recs.ctypes.data_as(ctypes.c_void_p), found.value,
+                                                           ctypes.byref(found)), "track_extract")
+        return recs[:found.value]
+
+    def track_info(self):
+        """ntedit_hip_track_info of the last call that extracted intervals: _lib.TrackStats"""
+        st = _lib.TrackStats()
+        self._check(self._lib.ntedit_hip_track_info(self._h, ctypes.byref(st)), "track_info")
+        return st
+
+    def write_track_bed(self, path, names, intervals):
+        """a four-column BED file without a header: name (cut at its first space or tab), begin, end, absent k-mers of
+        every interval, in the intervals' order (ntedit_hip_track_format_row); returns the bases they cover"""
+        buf = ctypes.create_string_buffer(1 << 16)
+        covered = 0
+        with open(path, "wb") as f:
+            for r in intervals:
+                iv = _lib.TrackInterval(int(r["entry"]), int(r["begin"]), int(r["end"]), int(r["absent"]))
+                if self._lib.ntedit_hip_track_format_row(bytes(names[iv.entry]), ctypes.byref(iv), buf, len(buf)):
+                    raise NtEditHipError("bed row of %r does not fit" % names[iv.entry])
+                f.write(buf.value)
+                covered += iv.end - iv.begin
+        return covered
+
     # ---- k-mer completeness: the draft's distinct k-mers that the PRIMARY filter holds (DESIGN.md 9.10)
     def shared_begin(self):
         """allocate and zero the two mark arrays (before, after) for the current PRIMARY filter; idempotent"""
@@ -445,10 +502,12 @@ class Polisher:
     def bloom_cardinality(self, set_bits, slots, h=1):
         return self._lib.ntedit_hip_bloom_cardinality(int(set_bits), int(slots), int(h))
 
-    def polish_records(self, records, out_prefix, draft_name="", annot_path=None, qv=False):
+    def polish_records(self, records, out_prefix, draft_name="", annot_path=None, qv=False, bed=False):
         """readAndCorrect at -t 1 for an in-memory list of (header, sequence): writes
         <prefix>_edited.fa, <prefix>_changes.tsv and <prefix>_variants.vcf; returns Stats.
-        qv: also <prefix>_qv.tsv, the k-mer QV of every contig before and after (set_apply(APPLY_QV) for this call)."""
+        qv: also <prefix>_qv.tsv, the k-mer QV of every contig before and after (set_apply(APPLY_QV) for this call).
+        bed: also <prefix>_absent_before.bed (the draft's coordinates) and <prefix>_absent_after.bed (those of
+        _edited.fa), the regions the filter does not support (set_apply(APPLY_TRACK) for this call)."""
         blob, offs, lens, names = pack_batch(records, self.params.min_contig_len)
         tsv = out_prefix + "_changes.tsv"
         fa = out_prefix + "_edited.fa"
@@ -462,16 +521,19 @@ class Polisher:
                 raise NtEditHipError("cannot read %s" % annot_path)
         # (send_packed: the batch crosses PCIe as 4-bit codes + case bits when it can; the renderer keeps the bytes)
         packed = self.pack_bases(blob) if getattr(self, "send_packed", False) and len(blob) else None
-        if qv:
-            self.set_apply(APPLY_QV)
+        if qv or bed:
+            self.set_apply((APPLY_QV if qv else 0) | (APPLY_TRACK if bed else 0))
         try:
             res = self.polish_batch(blob, offs, lens, packed=packed)
         finally:
-            if qv:
+            if qv or bed:
                 self.set_apply(0)
         res.write(blob, offs, lens, names, fa, tsv, append=True, vcf_path=vcf, snv=bool(self.params.snv), annot=annot)
         if qv:
             self.write_qv_table(out_prefix + "_qv.tsv", names, res.qv(len(names)))
+        if bed:
+            for which, stage in enumerate(("before", "after")):
+                self.write_track_bed("%s_absent_%s.bed" % (out_prefix, stage), names, res.track(which))
         if annot_path:
             self._lib.ntedit_hip_annot_free(annot)
         st = res.stats()
