@@ -1106,6 +1106,59 @@ int ntedit_hip_track_info(ntedit_hip_ctx* ctx, ntedit_hip_track_stats* st);
  * and IGV understand it).  Host only: no context, no device. */
 int ntedit_hip_track_format_row(const char* name, const ntedit_hip_track_interval* iv, char* out, uint64_t cap);
 
+/* ---- the k-mer multiplicity spectrum of a polish (no counterpart in the reference) ----------------------
+ * How often the reads hold the draft's k-mers, before and after, from a COUNTING filter.
+ *   F is the context's PRIMARY filter: a counting filter of `bits` 8-bit counters and h hashes (1 .. 8).
+ *   A K-MER is k bytes of ACGTacgt inside one entry -- exactly the `kmers` of ntedit_hip_qv_row; a window that holds N,
+ *   another IUPAC code, a separator or padding, or that leaves its entry, is none.
+ *   Its MULTIPLICITY is m = min over i < h of F.data[slot_i], slot_i the i-th probe of its canonical ntHash: the value -p
+ *   and the event machine see.  0 .. 255, and 255 means "255 or more": the counters saturate.
+ *   The SPECTRUM of a batch is bins[256], 64-bit: bins[c] = the k-mer OCCURRENCES with m = c (not distinct k-mers).
+ *   The DEPTH ROW of entry e: kmers, its occurrences; sum, the sum of their m; saturated, those with m = 255.
+ *   BEFORE is the batch as it came, AFTER the edited entries (the applier's buffer).  -p, -q, -s and the secondary filter
+ *   play no part; no absent bitmap is read.
+ * So sum(bins) = sum of kmers; kmers = the QV row's kmers_before / kmers_after; sum of sum = sum of c * bins[c]; sum of
+ * saturated = bins[255]; and on a draft of A, C, G, T, N only, sum(bins[0 .. max(1, p))) = the QV rows' absent counts.
+ * ntedit_hip_set_spectrum(ctx, on): a switch of its own beside ntedit_hip_set_apply's flags, for the polish calls that
+ * follow.  ON: ntedit_hip_polish_batch runs the applier whatever the flags (the edited bases go with the call unless
+ * APPLY_EDITED is set too) and counts both spectra; it fails before anything is polished with NTEDIT_E_UNSUPPORTED when
+ * the PRIMARY filter is plain and NTEDIT_E_ARG when there is none.  Segments (ntedit_hip_segment) are not supported: the
+ * call takes none.  OFF (the default): nothing runs.  ntedit_hip_reserve's warm-up batch leaves no trace in any figure. */
+int ntedit_hip_set_spectrum(ntedit_hip_ctx* ctx, int on);
+typedef struct ntedit_hip_depth_row
+{
+	uint64_t kmers_before, sum_before, saturated_before;
+	uint64_t kmers_after, sum_after, saturated_after;
+} ntedit_hip_depth_row;
+/* The spectrum (which: 0 before, 1 after) and the depth rows of a result polished with the switch on (NTEDIT_E_ARG
+ * otherwise; ntedit_hip_result_last_error() names ntedit_hip_set_spectrum).  The result keeps them in host memory of its
+ * own until ntedit_hip_result_free(). */
+int ntedit_hip_result_spectrum(const ntedit_hip_result* r, int which, uint64_t bins[256]);
+int ntedit_hip_result_depth(const ntedit_hip_result* r, ntedit_hip_depth_row* rows, uint32_t n_contigs);
+/* Stand-alone: the spectrum of any batch against the PRIMARY counting filter.  bases: n bytes, host (on_device 0) or
+ * device (1, 16-byte aligned); offs, lens: n_entries entries in batch order, host arrays; entries do not overlap and may
+ * abut.  bins: 256 words; rows: three words per entry {kmers, sum, saturated}, or NULL.  n == 0 or n_entries == 0 gives
+ * zeros. */
+int ntedit_hip_spectrum_count(ntedit_hip_ctx* ctx, const char* bases, uint64_t n, int on_device, const uint64_t* offs, const uint32_t* lens,
+                              uint32_t n_entries, uint64_t* bins, uint64_t* rows);
+/* The context's last call that counted (a polish call with the switch on: [0] before, [1] after; ntedit_hip_spectrum_count:
+ * [0], and [1] zero): HIP-event time of the k_spectrum launch, the k-mers it counted. */
+typedef struct ntedit_hip_spectrum_stats
+{
+	float ms[2];
+	uint64_t kmers[2];
+} ntedit_hip_spectrum_stats;
+int ntedit_hip_spectrum_info(ntedit_hip_ctx* ctx, ntedit_hip_spectrum_stats* st);
+/* <prefix>_spectrum.tsv: "multiplicity<TAB>before<TAB>after\n" and one row per multiplicity 0 .. 255.
+ * <prefix>_depth.tsv: name (cut at its first space or tab), kmers_before, mean_before, saturated_before, kmers_after,
+ * mean_after, saturated_after; mean = sum / kmers with two decimals, "NA" when kmers is 0 -- a saturated counter counts as
+ * 255, so the mean is a lower bound.  A last row "#total" (the caller's sum of the rows) closes the table.  Host only: no
+ * context, no device; NTEDIT_E_OVERFLOW when the row does not fit out[0 .. cap). */
+const char* ntedit_hip_spectrum_header(void);
+int ntedit_hip_spectrum_format_row(uint32_t multiplicity, uint64_t before, uint64_t after, char* out, uint64_t cap);
+const char* ntedit_hip_depth_header(void);
+int ntedit_hip_depth_format_row(const char* name, const ntedit_hip_depth_row* row, char* out, uint64_t cap);
+
 /* The reference's candidate tables -- num_tries, polish_bases_array / snv_bases_array, multi_possible_bases (ntedit.cpp:172,
  * 176-199, 203-348) -- as the device code holds them (one GPU thread runs the machine's own candidate_bases /
  * insertion_candidate), as text: "num_tries 0 1 5 21 85 341", "polish A TCG", ..., "snv N ATCG", "multi A A AA AC ...".

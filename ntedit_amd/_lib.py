@@ -191,6 +191,22 @@ class TrackStats(ctypes.Structure):
     _fields_ = [("ms", ctypes.c_float * 2), ("intervals", ctypes.c_uint64 * 2), ("bases", ctypes.c_uint64 * 2)]
 
 
+class DepthRow(ctypes.Structure):
+    """ntedit_hip_depth_row: an entry's k-mer occurrences, the sum of their multiplicities and the saturated ones, before
+    and after (ntedit_hip_set_spectrum)"""
+    _fields_ = [("kmers_before", ctypes.c_uint64), ("sum_before", ctypes.c_uint64), ("saturated_before", ctypes.c_uint64),
+                ("kmers_after", ctypes.c_uint64), ("sum_after", ctypes.c_uint64), ("saturated_after", ctypes.c_uint64)]
+
+
+DEPTH_DTYPE = [(name, "<u8") for name, _ in DepthRow._fields_]
+SPECTRUM_ROW_DTYPE = [("kmers", "<u8"), ("sum", "<u8"), ("saturated", "<u8")]  # ntedit_hip_spectrum_count's rows
+
+
+class SpectrumStats(ctypes.Structure):
+    """ntedit_hip_spectrum_stats: the context's last call that counted a spectrum; [0] before, [1] after"""
+    _fields_ = [("ms", ctypes.c_float * 2), ("kmers", ctypes.c_uint64 * 2)]
+
+
 class SharedStats(ctypes.Structure):
     """ntedit_hip_shared_stats: the popcounts behind the k-mer completeness (ntedit_hip_shared_counts)"""
     _fields_ = [("bits", ctypes.c_uint64), ("hash_num", ctypes.c_uint32), ("k", ctypes.c_uint32),
@@ -317,6 +333,9 @@ EXPORTS = [
     "ntedit_hip_set_fa_names", "ntedit_hip_result_fa_bgzf", "ntedit_hip_bgzf_deflate", "ntedit_hip_bgzf_deflate_model",
     "ntedit_hip_bgzf_bound", "ntedit_hip_bgzf_eof", "ntedit_hip_bgzf_info",
     "ntedit_hip_result_track", "ntedit_hip_track_extract", "ntedit_hip_track_info", "ntedit_hip_track_format_row",
+    "ntedit_hip_set_spectrum", "ntedit_hip_result_spectrum", "ntedit_hip_result_depth", "ntedit_hip_spectrum_count",
+    "ntedit_hip_spectrum_info", "ntedit_hip_spectrum_header", "ntedit_hip_spectrum_format_row", "ntedit_hip_depth_header",
+    "ntedit_hip_depth_format_row",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -530,5 +549,15 @@ def load():
     lib.ntedit_hip_track_extract.argtypes = [vp, vp, u64, vp, vp, u32, u32, vp, u64, pu64]
     lib.ntedit_hip_track_info.argtypes = [vp, ctypes.POINTER(TrackStats)]
     lib.ntedit_hip_track_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(TrackInterval), ctypes.c_char_p, u64]
+    # the k-mer spectrum against a counting filter (k_spectrum)
+    lib.ntedit_hip_set_spectrum.argtypes = [vp, ci]
+    lib.ntedit_hip_result_spectrum.argtypes = [vp, ci, vp]
+    lib.ntedit_hip_result_depth.argtypes = [vp, vp, u32]
+    lib.ntedit_hip_spectrum_count.argtypes = [vp, vp, u64, ci, vp, vp, u32, vp, vp]
+    lib.ntedit_hip_spectrum_info.argtypes = [vp, ctypes.POINTER(SpectrumStats)]
+    lib.ntedit_hip_spectrum_header.restype = ctypes.c_char_p
+    lib.ntedit_hip_spectrum_format_row.argtypes = [u32, u64, u64, ctypes.c_char_p, u64]
+    lib.ntedit_hip_depth_header.restype = ctypes.c_char_p
+    lib.ntedit_hip_depth_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(DepthRow), ctypes.c_char_p, u64]
     _lib = lib
     return lib

@@ -161,6 +161,12 @@ struct ntedit_hip_ctx
 	DevBuf tr_tiles, tr_recs, tr_upto, tr_totals;
 	hipEvent_t tr_evt[4] = { nullptr, nullptr, nullptr, nullptr };
 	ntedit_hip_track_stats track_last = { { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
+	// the k-mer spectrum (k_spectrum; ntedit_hip_set_spectrum): the switch, the bins and rows of a call in HBM, the last
+	// call's figures
+	bool spectrum_on = false;
+	DevBuf sp_buf;
+	hipEvent_t sp_evt[4] = { nullptr, nullptr, nullptr, nullptr };
+	ntedit_hip_spectrum_stats spectrum_last = { { 0.f, 0.f }, { 0, 0 } };
 	// linear counting of the draft's present k-mers (k_mark; ntedit_hip_shared_*): two mark arrays of the PRIMARY filter's
 	// size, before and after; they go when the slot gets another filter (drop_filter)
 	DevBuf sh_marks[2];
@@ -206,6 +212,10 @@ struct ntedit_hip_result
 	// NTEDIT_HIP_APPLY_TRACK: the intervals before and after (malloc)
 	ntedit_hip_track_interval* track[2] = { nullptr, nullptr };
 	u64 track_n[2] = { 0, 0 };
+	// ntedit_hip_set_spectrum: the bins before and after, a depth row per entry
+	bool spectrum = false;
+	std::vector<uint64_t> sp_bins;
+	std::vector<ntedit_hip_depth_row> depth;
 	~ntedit_hip_result()
 	{
 		free(track[0]);

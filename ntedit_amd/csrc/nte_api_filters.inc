@@ -97,7 +97,7 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 		               &c->first_chunk, &c->arena, &c->counters, &c->deferred,     &c->ws_nodes,      &c->ws_ov_pos,
 		               &c->ws_ov_chr, &c->ws_prev, &c->ws_lps, &c->ws_win, &c->runmap, &c->candmap, &c->packed, &c->bin_records, &c->bin_fill, &c->bin_ctl, &c->bin_ovf, &c->bin_state, &c->ev_cover, &c->ev_before, &c->ev_flags, &c->ev_list, &c->ev_bmax, &c->ev_rest,       &c->offs,          &c->lens,
 		               &c->ap_ev, &c->ap_place, &c->ap_range, &c->ap_contig, &c->ap_tabs, &c->ap_pieces, &c->ap_edited, &c->ap_bitmap, &c->ap_rows,
-		               &c->tr_tiles, &c->tr_recs, &c->tr_upto, &c->tr_totals,
+		               &c->tr_tiles, &c->tr_recs, &c->tr_upto, &c->tr_totals, &c->sp_buf,
 		               &c->sh_marks[0], &c->sh_marks[1] };
 	for (DevBuf* b : bufs) {
 		release(*b);
@@ -140,6 +140,11 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 		}
 	}
 	for (auto& e : c->tr_evt) {
+		if (e) {
+			(void)hipEventDestroy(e);
+		}
+	}
+	for (auto& e : c->sp_evt) {
 		if (e) {
 			(void)hipEventDestroy(e);
 		}

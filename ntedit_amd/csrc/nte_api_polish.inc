@@ -1154,7 +1154,8 @@ PolishRun::apply()
 	const u32 flags = c->apply_flags;
 	r->apply_flags = flags;
 	r->device = c->device;
-	if (!flags) {
+	const bool spectrum = c->spectrum_on;
+	if (!flags && !spectrum) {
 		return 0;
 	}
 	int rc;
@@ -1322,6 +1323,17 @@ PolishRun::apply()
 			}
 		}
 	}
+	// The k-mer spectrum (ntedit_hip_set_spectrum; k_spectrum): the counters under the batch's k-mers and under those of the
+	// edited bases, behind the applier and whatever the QV counts queued.  No bitmap is read: -s 1 changes nothing here.
+	std::vector<uint64_t> sp_host;
+	if (he == hipSuccess && !qrc && spectrum) {
+		sp_host.resize(2 * (size_t)SPECTRUM_BINS + 2 * nc * 3);
+		if ((qrc = spectrum_begin(c, s, n_contigs)) == 0 &&
+		    (qrc = launch_spectrum(c, s, d_seq, n, f0, a.offs, a.lens, n_contigs, 0, true)) == 0 &&
+		    (qrc = launch_spectrum(c, s, a.out, total_bytes, f0, a.out_offs, a.out_lens, n_contigs, 1, true)) == 0) {
+			he = hipMemcpyAsync(sp_host.data(), c->sp_buf.p, sp_host.size() * 8, hipMemcpyDeviceToHost, s);
+		}
+	}
 	if (he == hipSuccess) {
 		he = hipStreamSynchronize(s);
 	}
@@ -1333,6 +1345,18 @@ PolishRun::apply()
 		release(eb);
 		r->qv.clear();
 		return qrc ? qrc : fail(c, NTEDIT_E_DEVICE, "apply: %s", hipGetErrorString(he));
+	}
+	if (spectrum) {
+		r->sp_bins.assign(sp_host.begin(), sp_host.begin() + 2 * SPECTRUM_BINS);
+		r->depth.resize(nc);
+		const uint64_t* rows0 = sp_host.data() + 2 * SPECTRUM_BINS;
+		const uint64_t* rows1 = rows0 + nc * 3;
+		for (size_t i = 0; i < nc; i++) {
+			r->depth[i] = { rows0[3 * i], rows0[3 * i + 1], rows0[3 * i + 2], rows1[3 * i], rows1[3 * i + 1], rows1[3 * i + 2] };
+		}
+		spectrum_timed(c, 0, r->sp_bins.data());
+		spectrum_timed(c, 1, r->sp_bins.data() + SPECTRUM_BINS);
+		r->spectrum = true;
 	}
 	ntedit_hip_apply_stats as = { 0.f, 0.f, 0.f, total_pieces, total_bytes, h_tot[2] };
 	(void)hipEventElapsedTime(&as.ms_apply, c->ap_evt[0], c->ap_evt[1]);
@@ -1424,8 +1448,11 @@ ntedit_hip_polish_batch(
 	}
 	*out = nullptr;
 	HIP_TRY(c, hipSetDevice(c->device));
-	int rc = refresh_params(c);
-	if (rc) {
+	int rc;
+	if (c->spectrum_on && (rc = spectrum_refuse(c, "polish_batch"))) {
+		return rc; // (a plain filter, or none -- NTEDIT_E_ARG, ahead of the general answer below: before anything is polished)
+	}
+	if ((rc = refresh_params(c))) {
 		return rc;
 	}
 	if ((c->apply_flags & NTEDIT_HIP_APPLY_SHARED) && (rc = shared_refuse(c, "polish_batch"))) {
@@ -1454,6 +1481,12 @@ ntedit_hip_polish_batch(
 	r->apply_flags = c->apply_flags;
 	r->device = c->device;
 	if (n == 0 || n_contigs == 0) {
+		if (c->spectrum_on) { // (nothing to count: zeros)
+			r->spectrum = true;
+			r->sp_bins.assign(2 * (size_t)SPECTRUM_BINS, 0);
+			r->depth.assign(n_contigs, ntedit_hip_depth_row{ 0, 0, 0, 0, 0, 0 });
+			c->spectrum_last = ntedit_hip_spectrum_stats{ { 0.f, 0.f }, { 0, 0 } };
+		}
 		*out = r;
 		return 0;
 	}
@@ -1571,8 +1604,16 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		if ((keep_flags & NTEDIT_HIP_APPLY_BGZF) && !c->apply_flags) {
 			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
 		}
+		// (nor does it leave a spectrum: the switch stays down for it, spectrum_last as it was; k_spectrum's code object loads
+		// with the library's others)
+		const bool keep_spectrum = c->spectrum_on;
+		c->spectrum_on = false;
+		if (keep_spectrum && !c->apply_flags) {
+			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
+		}
 		ntedit_hip_result* wr = nullptr;
 		rc = ntedit_hip_polish_batch(c, buf.data(), wn, offs.data(), lens.data(), wc, NTEDIT_HIP_BASES_HOST, &wr);
+		c->spectrum_on = keep_spectrum;
 		c->apply_flags = keep_flags;
 		c->tune = keep;
 		if (wr) {
@@ -1650,7 +1691,7 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 			return rc;
 		}
 	}
-	if (c->apply_flags) { // (the applier: an event's summary and place, the edited bases, the piece table; the QV bitmap)
+	if (c->apply_flags || c->spectrum_on) { // (the applier: an event's summary and place, the edited bases, the piece table; the QV bitmap)
 		if ((rc = ensure(c, c->ap_ev, (size_t)(n_ev + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, c->ap_place, (size_t)(n_ev + 1) * sizeof(ApplyPlace))) ||
 		    (rc = ensure(c, c->ap_pieces, (size_t)(2 * n_ev + 2 * (u64)max_contigs + 1024) * sizeof(ApplyPiece))) ||
 		    (rc = ensure(c, c->ap_edited, (size_t)(n + n / 64 + 4096)))) {
@@ -1665,6 +1706,9 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 			    (rc = ensure(c, c->tr_recs, (size_t)n_ev * sizeof(TrackInterval))) || (rc = ensure(c, c->tr_upto, (size_t)n_ev * 4))) {
 				return rc;
 			}
+		}
+		if (c->spectrum_on && (rc = ensure(c, c->sp_buf, (2 * (size_t)SPECTRUM_BINS + 6 * (size_t)(max_contigs ? max_contigs : 1)) * 8))) {
+			return rc;
 		}
 		if (c->apply_flags & NTEDIT_HIP_APPLY_BGZF) { // (the image: the edited bases, and per entry '>', a header line, '\n')
 			std::string why;

@@ -223,6 +223,109 @@ ntedit_hip_track_info(ntedit_hip_ctx* c, ntedit_hip_track_stats* st)
 	return 0;
 }
 
+// ---- the k-mer spectrum (k_spectrum, nte_kernels.hip; the helpers are in nte_api_screen.inc)
+
+int
+ntedit_hip_set_spectrum(ntedit_hip_ctx* c, int on)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	c->spectrum_on = on != 0;
+	return 0;
+}
+
+int
+ntedit_hip_result_spectrum(const ntedit_hip_result* r, int which, uint64_t bins[256])
+{
+	if (!r || !bins || which < 0 || which > 1) {
+		return result_refuse(r, "result_spectrum: bad argument");
+	}
+	if (!r->spectrum) {
+		return result_refuse(r, "result_spectrum: the batch was polished with the spectrum switched off (ntedit_hip_set_spectrum)");
+	}
+	memcpy(bins, r->sp_bins.data() + (size_t)which * SPECTRUM_BINS, SPECTRUM_BINS * 8);
+	return 0;
+}
+
+int
+ntedit_hip_result_depth(const ntedit_hip_result* r, ntedit_hip_depth_row* rows, uint32_t n_contigs)
+{
+	if (!r || (n_contigs && !rows)) {
+		return result_refuse(r, "result_depth: bad argument");
+	}
+	if (!r->spectrum) {
+		return result_refuse(r, "result_depth: the batch was polished with the spectrum switched off (ntedit_hip_set_spectrum)");
+	}
+	if (n_contigs != r->depth.size()) {
+		return result_refuse(r, "result_depth: the batch had another number of entries");
+	}
+	if (n_contigs) {
+		memcpy(rows, r->depth.data(), (size_t)n_contigs * sizeof(ntedit_hip_depth_row));
+	}
+	return 0;
+}
+
+int
+ntedit_hip_spectrum_count(ntedit_hip_ctx* c, const char* bases, uint64_t n, int on_device, const uint64_t* offs, const uint32_t* lens,
+                          uint32_t n_entries, uint64_t* bins, uint64_t* rows)
+{
+	if (!c || !bins || (n && !bases) || (n_entries && (!offs || !lens))) {
+		return fail(c, NTEDIT_E_ARG, "spectrum_count: bad argument");
+	}
+	if (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) {
+		return fail(c, NTEDIT_E_ARG, "spectrum_count: bases must be host or device bytes");
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc = spectrum_refuse(c, "spectrum_count");
+	if (rc || (rc = refresh_params(c))) {
+		return rc;
+	}
+	for (u32 i = 0; i < n_entries; i++) {
+		if (offs[i] > n || lens[i] > n - offs[i] || (i + 1 < n_entries && offs[i] + lens[i] > offs[i + 1])) {
+			return fail(c, NTEDIT_E_ARG, "spectrum_count: entry %u breaks the batch layout", i);
+		}
+	}
+	memset(bins, 0, SPECTRUM_BINS * 8);
+	if (rows && n_entries) {
+		memset(rows, 0, (size_t)n_entries * 24);
+	}
+	c->spectrum_last = ntedit_hip_spectrum_stats{ { 0.f, 0.f }, { 0, 0 } };
+	if (n == 0 || n_entries == 0) {
+		return 0;
+	}
+	hipStream_t s = c->stream;
+	const u8* d_seq = nullptr;
+	if ((rc = stage_bases(c, bases, n, on_device, &d_seq)) || (rc = ensure(c, c->offs, (size_t)n_entries * 8)) ||
+	    (rc = ensure(c, c->lens, (size_t)n_entries * 4)) || (rc = spectrum_begin(c, s, n_entries))) {
+		return rc;
+	}
+	HIP_TRY(c, hipMemcpyAsync(c->offs.p, offs, (size_t)n_entries * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(c, hipMemcpyAsync(c->lens.p, lens, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+	const Filter f0 = dev_filter(c->filt[0]);
+	if ((rc = launch_spectrum(c, s, d_seq, n, f0, (const u64*)c->offs.p, (const u32*)c->lens.p, n_entries, 0, rows != nullptr))) {
+		(void)hipStreamSynchronize(s);
+		return rc;
+	}
+	HIP_TRY(c, hipMemcpyAsync(bins, spectrum_bins(c, 0), SPECTRUM_BINS * 8, hipMemcpyDeviceToHost, s));
+	if (rows) {
+		HIP_TRY(c, hipMemcpyAsync(rows, spectrum_rows(c, 0, n_entries), (size_t)n_entries * 24, hipMemcpyDeviceToHost, s));
+	}
+	HIP_TRY(c, hipStreamSynchronize(s));
+	spectrum_timed(c, 0, bins);
+	return 0;
+}
+
+int
+ntedit_hip_spectrum_info(ntedit_hip_ctx* c, ntedit_hip_spectrum_stats* st)
+{
+	if (!c || !st) {
+		return fail(c, NTEDIT_E_ARG, "spectrum_info: bad argument");
+	}
+	*st = c->spectrum_last;
+	return 0;
+}
+
 // ---- the BGZF writer (nte_bgzf_deflate.hip)
 
 int

@@ -220,6 +220,135 @@ mark_timed(ntedit_hip_ctx* c, int which)
 	}
 }
 
+// ---- the k-mer spectrum (k_spectrum): the PRIMARY filter's counters under a batch's k-mers
+// why the context cannot count a spectrum (0: it can)
+int
+spectrum_refuse(ntedit_hip_ctx* c, const char* who)
+{
+	const DevFilter& f = c->filt[0];
+	if (!f.set) {
+		return fail(c, NTEDIT_E_ARG, "%s: no primary filter to take the k-mer spectrum from", who);
+	}
+	if (!f.counting) {
+		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: the k-mer spectrum takes a counting primary filter; a plain filter's slots are bits", who);
+	}
+	if (f.k > (u32)SCREEN_MAXK || f.hash_num < 1 || f.hash_num > MAX_HASHES) {
+		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: the k-mer spectrum takes k up to %d and 1 to %u hashes", who, SCREEN_MAXK, MAX_HASHES);
+	}
+	return 0;
+}
+
+// bins[256] and rows[n_entries][3] of one launch, inside sp_buf: [which][256] bins, then [which][n_entries][3] rows
+unsigned long long*
+spectrum_bins(ntedit_hip_ctx* c, int which)
+{
+	return (unsigned long long*)c->sp_buf.p + (size_t)which * SPECTRUM_BINS;
+}
+
+unsigned long long*
+spectrum_rows(ntedit_hip_ctx* c, int which, u32 n_entries)
+{
+	return (unsigned long long*)c->sp_buf.p + 2 * SPECTRUM_BINS + (size_t)which * n_entries * 3;
+}
+
+// sp_buf for a call over n_entries entries, zeroed on `stream`; the events
+int
+spectrum_begin(ntedit_hip_ctx* c, hipStream_t stream, u32 n_entries)
+{
+	for (auto& e : c->sp_evt) {
+		if (!e) {
+			HIP_TRY(c, hipEventCreate(&e));
+		}
+	}
+	const size_t bytes = (2 * (size_t)SPECTRUM_BINS + 2 * (size_t)n_entries * 3) * 8;
+	int rc = ensure(c, c->sp_buf, bytes);
+	if (rc) {
+		return rc;
+	}
+	HIP_TRY(c, hipMemsetAsync(c->sp_buf.p, 0, bytes, stream));
+	c->spectrum_last = ntedit_hip_spectrum_stats{ { 0.f, 0.f }, { 0, 0 } };
+	return 0;
+}
+
+// k_spectrum over a batch in device memory and its entries into launch `which`'s bins and rows, on `stream`, between the
+// two events of that launch
+int
+launch_spectrum(ntedit_hip_ctx* c, hipStream_t stream, const u8* d_seq, u64 n, const Filter& f, const u64* d_offs, const u32* d_lens, u32 n_entries,
+                int which, bool want_rows)
+{
+	const u64 blocks = (n + SCREEN_TILE - 1) / SCREEN_TILE;
+	if (blocks > 0x7FFFFFFFull) {
+		return fail(c, NTEDIT_E_ARG, "batch too large");
+	}
+	if (!f.counting || c->dp.k > (u32)SCREEN_MAXK || c->dp.k == 0) {
+		return fail(c, NTEDIT_E_INTERNAL, "spectrum: not a counting filter, or k beyond the tile's halo");
+	}
+	unsigned long long* bins = spectrum_bins(c, which);
+	unsigned long long* rows = want_rows ? spectrum_rows(c, which, n_entries) : nullptr;
+	HIP_TRY(c, hipEventRecord(c->sp_evt[2 * which], stream));
+	if (blocks && n_entries) {
+		dim3 grid((unsigned)blocks), block(SCREEN_TPB);
+		const bool pow2 = f.mask != 0;
+#define NTE_LAUNCH(H)                                                                                                              \
+	do {                                                                                                                           \
+		if (pow2) {                                                                                                                \
+			hipLaunchKernelGGL((k_spectrum<H, true>), grid, block, 0, stream, d_seq, n, f, c->dp, c->d_tab, d_offs, d_lens, n_entries, bins, rows);  \
+		} else {                                                                                                                   \
+			hipLaunchKernelGGL((k_spectrum<H, false>), grid, block, 0, stream, d_seq, n, f, c->dp, c->d_tab, d_offs, d_lens, n_entries, bins, rows); \
+		}                                                                                                                          \
+	} while (0)
+		switch (f.hash_num) {
+		case 1:
+			NTE_LAUNCH(1);
+			break;
+		case 2:
+			NTE_LAUNCH(2);
+			break;
+		case 3:
+			NTE_LAUNCH(3);
+			break;
+		case 4:
+			NTE_LAUNCH(4);
+			break;
+		case 5:
+			NTE_LAUNCH(5);
+			break;
+		case 6:
+			NTE_LAUNCH(6);
+			break;
+		case 7:
+			NTE_LAUNCH(7);
+			break;
+		case 8:
+			NTE_LAUNCH(8);
+			break;
+		default:
+			return fail(c, NTEDIT_E_UNSUPPORTED, "spectrum: 1 to %u hashes", MAX_HASHES);
+		}
+#undef NTE_LAUNCH
+		HIP_TRY(c, hipGetLastError());
+	}
+	HIP_TRY(c, hipEventRecord(c->sp_evt[2 * which + 1], stream));
+	return 0;
+}
+
+// after `stream` has been waited for: the launch's time and, from its bins on the host, its k-mers
+void
+spectrum_timed(ntedit_hip_ctx* c, int which, const uint64_t* bins)
+{
+	float ms = 0.f;
+	if (hipEventElapsedTime(&ms, c->sp_evt[2 * which], c->sp_evt[2 * which + 1]) != hipSuccess) {
+		(void)hipGetLastError();
+		ms = 0.f;
+	}
+	u64 total = 0;
+	for (int i = 0; i < SPECTRUM_BINS; i++) {
+		total += bins[i];
+	}
+	c->spectrum_last.ms[which] = ms;
+	c->spectrum_last.kmers[which] = total;
+}
+
 // ---- L2-partitioned ("binned") screening; see nte_kernels.hip / nte_bin_wc.inc
 // screen_mode 1 forces the direct gather kernel, 2 the binned pipeline (tests run it on small inputs); 0 picks:
 // the binned pipeline pays when the filter is far larger than the L2s (the direct kernel then runs at the

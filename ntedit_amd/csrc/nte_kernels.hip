@@ -344,6 +344,215 @@ k_mark(const u8* __restrict__ seq, u64 n, Filter f, u32 k, const u64* __restrict
 	}
 }
 
+// ---------------------------------------------------------------- k_spectrum
+// The k-mer multiplicity spectrum of a batch against a COUNTING filter (ntedit --spectrum).  A k-mer is k
+// bytes of ACGTacgt inside one entry -- k_mark's look-up table, a code above 3 ends a k-mer; its multiplicity is
+// m = min over i < h of f.data[filter_slot(f, hash_extend(fh + rh, p, i))], filter_min_count()'s value, 0..255 (255: the
+// counters saturate).  bins[c] counts the k-mer OCCURRENCES with m = c; per entry the row holds {occurrences, sum of m,
+// occurrences with m = 255}.  k_screen's tile, staging and rolling hash, four starts per iteration: all 4 x H counter
+// gathers are issued before the first is used, a start that is no k-mer reads byte 0 instead of branching, and no probe
+// ends at a zero counter (the minimum needs them all; in a lock-step wavefront the early exit saves nothing).
+// The histogram: one 256-bin u32 histogram per wavefront in LDS (a tile has 16,384 starts) -- a real draft puts most
+// k-mers into a handful of bins around the coverage peak, which a single histogram would serialise all four wavefronts
+// on --, combined at the end, the non-zero bins flushed with one 64-bit atomic each.
+// The rows, k_qv_count's scheme: a thread finds the entry of its first start by binary search and steps on when its
+// stream passes the entry's end; what belongs to the entry the tile begins in is reduced over the workgroup into one
+// atomic per field, every other entry begins inside the tile and takes the atomics of the threads that met it.  Entries
+// may abut (no separator: the entry's bounds end a k-mer, not the byte) and may be shorter than k.  All results are sums
+// of integers: they do not depend on geometry or order.
+__device__ __forceinline__ u32
+spectrum_entry(const u64* __restrict__ offs, const u32* __restrict__ lens, u32 n, u64 x)
+{
+	// the first entry whose end lies behind position x (entries are in batch order)
+	u32 lo = 0, hi = n;
+	while (lo < hi) {
+		const u32 mid = (lo + hi) >> 1;
+		if (offs[mid] + lens[mid] <= x) {
+			lo = mid + 1;
+		} else {
+			hi = mid;
+		}
+	}
+	return lo;
+}
+
+constexpr int SPECTRUM_BINS = 256;
+
+template<int H, bool POW2>
+__global__ __launch_bounds__(SCREEN_TPB) void
+k_spectrum(
+    const u8* __restrict__ seq,
+    u64 n,
+    Filter f,
+    DevParams p,
+    const u64* __restrict__ tabs,
+    const u64* __restrict__ offs,
+    const u32* __restrict__ lens,
+    u32 n_entries,
+    unsigned long long* __restrict__ bins, // [256]
+    unsigned long long* __restrict__ rows) // [n_entries][3], or null
+{
+	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
+	__shared__ u8 s_lut[256];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[SCREEN_LDS_BYTES];
+	__shared__ u32 s_hist[SCREEN_TPB / 64][SPECTRUM_BINS];
+	__shared__ u32 s_row[3];
+
+	const u32 tid = threadIdx.x;
+	if (tid < TAB_WORDS) {
+		s_tab[tid] = tabs[tid];
+	}
+	{
+		const u8 code = char_code((u8)tid);
+		s_lut[tid] = code > 3 ? CODE_BAD : code;
+	}
+#pragma unroll
+	for (int w = 0; w < SCREEN_TPB / 64; w++) {
+		s_hist[w][tid] = 0;
+	}
+	if (tid < 3) {
+		s_row[tid] = 0;
+	}
+	__syncthreads();
+
+	const u64 tile_base = (u64)blockIdx.x * SCREEN_TILE;
+	const u32 k = p.k;
+	stage_tile(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
+	__syncthreads();
+
+	const u32 x0 = tid * SCREEN_L;
+	HashState hs = { 0, 0 };
+	u32 good = 0;
+	for (u32 i = 0; i < k; i++) {
+		const u8 in = s_codes[lds_phys(x0 + i)];
+		hash_roll(hs, s_tab, CODE_BAD, in);
+		good = in == CODE_BAD ? 0 : good + 1;
+	}
+
+	// the entry of the stream's position: [eb, ee), both ~0 behind the last entry (then nothing is a k-mer)
+	const u64 pos0 = tile_base + x0;
+	const u32 e_tile = spectrum_entry(offs, lens, n_entries, tile_base);
+	u32 e = spectrum_entry(offs, lens, n_entries, pos0);
+	u64 eb = ~0ULL, ee = ~0ULL;
+	if (e < n_entries) {
+		eb = offs[e];
+		ee = eb + lens[e];
+	}
+	// the row of the entry the thread is counting (e_acc), and what it has counted of the tile's own entry
+	u32 e_acc = e, a_k = 0, a_s = 0, a_sat = 0;
+	u32 t_k = 0, t_s = 0, t_sat = 0;
+	auto flush = [&]() {
+		if (a_k) {
+			if (e_acc == e_tile) {
+				t_k += a_k;
+				t_s += a_s;
+				t_sat += a_sat;
+			} else {
+				unsigned long long* r = rows + (u64)e_acc * 3;
+				atomicAdd(r, (unsigned long long)a_k);
+				if (a_s) {
+					atomicAdd(r + 1, (unsigned long long)a_s);
+				}
+				if (a_sat) {
+					atomicAdd(r + 2, (unsigned long long)a_sat);
+				}
+			}
+		}
+		a_k = a_s = a_sat = 0;
+	};
+
+	u32* hist = s_hist[tid >> 6];
+	const u32 ksh = (k & 3) * 8;
+	u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[lds_phys((x0 + k) & ~3u)]);
+	for (u32 j0 = 0; j0 < SCREEN_L; j0 += 4) {
+		const u32 outw = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + j0)]);
+		const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[lds_phys(((x0 + j0 + k) & ~3u) + 4)]);
+		const u32 inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
+		in_lo = in_hi;
+
+		u64 slot[4][H];
+		bool valid[4];
+		u32 ent[4];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const u64 pos = pos0 + j0 + u;
+			while (pos >= ee) { // (ee = ~0 behind the last entry: the loop ends there)
+				e++;
+				eb = ee = ~0ULL;
+				if (e < n_entries) {
+					eb = offs[e];
+					ee = eb + lens[e];
+				}
+			}
+			valid[u] = good >= k && pos >= eb && pos + k <= ee;
+			ent[u] = e;
+			const u64 base = hs.fh + hs.rh;
+#pragma unroll
+			for (int i = 0; i < H; i++) {
+				const u64 hv = hash_extend(base, p, i);
+				slot[u][i] = POW2 ? (hv & f.mask) : filter_slot(f, hv);
+			}
+			const u8 out = (outw >> (8 * u)) & 0xFF;
+			const u8 in = (inw >> (8 * u)) & 0xFF;
+			hash_roll(hs, s_tab, out, in);
+			good = in == CODE_BAD ? 0 : good + 1;
+		}
+		u8 byte[4][H];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+#pragma unroll
+			for (int i = 0; i < H; i++) {
+				byte[u][i] = f.data[valid[u] ? slot[u][i] : 0];
+			}
+		}
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			u32 m = 255;
+#pragma unroll
+			for (int i = 0; i < H; i++) {
+				m = byte[u][i] < m ? byte[u][i] : m;
+			}
+			if (valid[u]) {
+				atomicAdd(&hist[m], 1u);
+				if (rows) {
+					if (ent[u] != e_acc) {
+						flush();
+						e_acc = ent[u];
+					}
+					a_k++;
+					a_s += m;
+					a_sat += m == 255;
+				}
+			}
+		}
+	}
+	if (rows) {
+		flush();
+		for (int o = 32; o > 0; o >>= 1) {
+			t_k += __shfl_down(t_k, o);
+			t_s += __shfl_down(t_s, o);
+			t_sat += __shfl_down(t_sat, o);
+		}
+		if ((tid & 63) == 0 && t_k) {
+			atomicAdd(&s_row[0], t_k);
+			atomicAdd(&s_row[1], t_s);
+			atomicAdd(&s_row[2], t_sat);
+		}
+	}
+	__syncthreads();
+	u32 total = 0;
+#pragma unroll
+	for (int w = 0; w < SCREEN_TPB / 64; w++) {
+		total += s_hist[w][tid];
+	}
+	if (total) {
+		atomicAdd(bins + tid, (unsigned long long)total);
+	}
+	if (rows && tid < 3 && s_row[tid] && e_tile < n_entries) {
+		atomicAdd(rows + (u64)e_tile * 3 + tid, (unsigned long long)s_row[tid]);
+	}
+}
+
 // ------------------------------------------------------- binned screening
 // The direct kernel above is bound by the L2-miss path: every 1-byte probe of a multi-GiB filter costs one
 // 64-byte fabric request (~51 G requests/s measured, the same as a pure random-gather micro-benchmark),

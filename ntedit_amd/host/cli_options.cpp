@@ -131,6 +131,23 @@ static const char HELP_BED[] = PROGRAM
     "			with --shard\n"
     "	--help-bed,	display this paragraph and exit\n\n";
 
+static const char HELP_SPECTRUM[] = PROGRAM
+    " --spectrum\n\n"
+    "	--spectrum,	with a counting filter (-r counts.bf, or --reads --counts): the k-mer multiplicity spectrum of the draft\n"
+    "			before and after the polish.  A k-mer's multiplicity is the smallest of its h counters -- what -p and -q\n"
+    "			compare --, 0..255, 255 meaning 255 or more.  Writes <prefix>_spectrum.tsv (multiplicity, before, after:\n"
+    "			always 256 rows, every k-mer occurrence of the draft counted at its multiplicity) and <prefix>_depth.tsv\n"
+    "			(name, kmers_before, mean_before, saturated_before, kmers_after, mean_after, saturated_after: one row per\n"
+    "			contig in <prefix>_edited.fa's order, then #total; mean is NA without k-mers and a lower bound where\n"
+    "			counters saturate).  A contig at half or double the peak is a haplotig or a collapsed repeat, one at 0 is\n"
+    "			not in the reads.  The counters over-estimate (a count-min minimum), and a filter built with -c C holds\n"
+    "			nothing below C: multiplicities 1..C-1 show as 0.  Both spectra are counted on the GPU from the batch and\n"
+    "			the edited contigs in HBM; -p, -q, -s and -e play no part.  With or without --qv.  With -k K1,K2,... an\n"
+    "			earlier round writes <prefix>_k<Ki>_spectrum.tsv and _depth.tsv.  One summary line reports k-mers, the\n"
+    "			share at 0, the mean, the peak and the saturated share before and after; --report adds\n"
+    "			{\"spectrum\": {...}}.  Not with a plain filter, --genome, --reads without --counts, or --shard\n"
+    "	--help-spectrum,	display this paragraph and exit\n\n";
+
 static const char shortopts[] = "t:f:s:k:z:b:r:v:d:i:X:Y:x:y:m:c:j:s:e:a:l:p:q:";
 enum
 {
@@ -167,7 +184,9 @@ enum
 	OPT_BGZIP,
 	OPT_HELP_BGZIP,
 	OPT_BED,
-	OPT_HELP_BED
+	OPT_HELP_BED,
+	OPT_SPECTRUM,
+	OPT_HELP_SPECTRUM
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -225,6 +244,8 @@ static const struct option longopts[] = {
 	{ "help-bgzip", no_argument, nullptr, OPT_HELP_BGZIP },
 	{ "bed", no_argument, nullptr, OPT_BED },
 	{ "help-bed", no_argument, nullptr, OPT_HELP_BED },
+	{ "spectrum", no_argument, nullptr, OPT_SPECTRUM },
+	{ "help-spectrum", no_argument, nullptr, OPT_HELP_SPECTRUM },
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -563,6 +584,12 @@ parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOptio
 		case OPT_HELP_BED:
 			fputs(HELP_BED, stderr);
 			exit(EXIT_SUCCESS);
+		case OPT_SPECTRUM:
+			o->spectrum = true;
+			break;
+		case OPT_HELP_SPECTRUM:
+			fputs(HELP_SPECTRUM, stderr);
+			exit(EXIT_SUCCESS);
 		case OPT_HELP:
 			fputs(USAGE, stderr);
 			exit(EXIT_SUCCESS);
@@ -638,6 +665,13 @@ parse_cli(int argc, char** argv)
 	}
 	if (o.qv && o.shard_given) {
 		fail("--qv and --shard: a table per shard would need a merge of its own; run --qv on the whole draft");
+	}
+	if (o.spectrum && (o.shard_given || o.genome_mode || (o.reads_mode && !o.counts))) {
+		// (behind the older refusals above; before the device is opened and before a file is written)
+		fail("--spectrum%s",
+		     o.shard_given   ? " and --shard: the spectra of the shards would need a merge of their own; run --spectrum on the whole draft"
+		     : o.genome_mode ? " and --genome: the spectrum takes a counting filter; a genome filter is plain"
+		                     : " and --reads without --counts: the spectrum takes a counting filter; add --counts");
 	}
 	std::vector<std::string> k_list; // -k K1,K2,...: its k as given, in order
 	if (o.ro.k && strchr(o.ro.k, ',')) {

@@ -30,7 +30,7 @@ struct CliOptions
 	unsigned long long batch_bases = 1ull << 30;
 	bool batch_given = false;
 	unsigned shard_i = 0, shard_n = 1;
-	bool shard_given = false, no_map = false, no_pack = true, qv = false, completeness = false, bgzip = false, bed = false;
+	bool shard_given = false, no_map = false, no_pack = true, qv = false, completeness = false, bgzip = false, bed = false, spectrum = false;
 	std::vector<std::pair<std::string, unsigned long long>> tunes;
 	// --reads FILE... / --genome FILE...: `paths` are the files of whichever was given
 	bool reads_mode = false, genome_mode = false;

@@ -171,6 +171,73 @@ finish_bed(const RoundTotals& t, const std::string paths[2], bool report)
 	}
 }
 
+// the figures of one spectrum: occurrences, those at 0 and at 255, the sum of the multiplicities, and the peak -- the
+// smallest multiplicity in 1..254 with the largest bin (-1: all of those bins are empty)
+struct SpectrumFigures
+{
+	unsigned long long kmers = 0, zero = 0, saturated = 0, sum = 0;
+	int peak = -1;
+};
+
+static SpectrumFigures
+spectrum_figures(const unsigned long long bins[256])
+{
+	SpectrumFigures f;
+	unsigned long long best = 0;
+	for (int c = 0; c < 256; c++) {
+		f.kmers += bins[c];
+		f.sum += bins[c] * (unsigned long long)c;
+		if (c >= 1 && c <= 254 && bins[c] > best) {
+			best = bins[c];
+			f.peak = c;
+		}
+	}
+	f.zero = bins[0];
+	f.saturated = bins[255];
+	return f;
+}
+
+void
+finish_spectrum(const RoundTotals& t, FILE* depth_f, const std::string paths[2], uint32_t k, bool report)
+{
+	char line[512];
+	bool ok = ntedit_hip_depth_format_row("#total", &t.depth, line, sizeof line) == 0 && fputs(line, depth_f) >= 0;
+	ok = fclose(depth_f) == 0 && ok;
+	if (!ok) {
+		fail("cannot write `%s'", paths[1].c_str());
+	}
+	FILE* sf = fopen(paths[0].c_str(), "wb");
+	ok = sf != nullptr && fputs(ntedit_hip_spectrum_header(), sf) >= 0;
+	for (uint32_t c = 0; ok && c < 256; c++) {
+		ok = ntedit_hip_spectrum_format_row(c, t.spectrum[0][c], t.spectrum[1][c], line, sizeof line) == 0 && fputs(line, sf) >= 0;
+	}
+	if (sf) {
+		ok = fclose(sf) == 0 && ok;
+	}
+	if (!ok) {
+		fail("cannot write `%s'", paths[0].c_str());
+	}
+	const SpectrumFigures f[2] = { spectrum_figures(t.spectrum[0]), spectrum_figures(t.spectrum[1]) };
+	auto share = [](unsigned long long part, unsigned long long all) { return all ? (double)part / (double)all : std::nan(""); };
+	auto mean = [](const SpectrumFigures& g) { return g.kmers ? (double)g.sum / (double)g.kmers : std::nan(""); };
+	auto mean_text = [&](const SpectrumFigures& g) { return g.kmers ? json_num(mean(g), "%.2f") : std::string("NA"); };
+	auto peak_text = [](const SpectrumFigures& g) { return g.peak < 0 ? std::string("NA") : std::to_string(g.peak); };
+	printf("k-mer spectrum (k=%u): before %llu k-mers, %s at multiplicity 0, mean %s, peak %s, %s saturated; after %llu k-mers, %s at "
+	       "multiplicity 0, mean %s, peak %s, %s saturated; tables: %s, %s\n",
+	       k, f[0].kmers, percent_text(share(f[0].zero, f[0].kmers)).c_str(), mean_text(f[0]).c_str(), peak_text(f[0]).c_str(),
+	       percent_text(share(f[0].saturated, f[0].kmers)).c_str(), f[1].kmers, percent_text(share(f[1].zero, f[1].kmers)).c_str(),
+	       mean_text(f[1]).c_str(), peak_text(f[1]).c_str(), percent_text(share(f[1].saturated, f[1].kmers)).c_str(), paths[0].c_str(),
+	       paths[1].c_str());
+	if (report) {
+		auto peak_json = [](const SpectrumFigures& g) { return g.peak < 0 ? std::string("null") : std::to_string(g.peak); };
+		printf("{\"spectrum\": {\"kmers_before\": %llu, \"zero_before\": %llu, \"mean_before\": %s, \"peak_before\": %s, \"saturated_before\": %llu, "
+		       "\"kmers_after\": %llu, \"zero_after\": %llu, \"mean_after\": %s, \"peak_after\": %s, \"saturated_after\": %llu, "
+		       "\"spectrum_before_ms\": %.3f, \"spectrum_after_ms\": %.3f}}\n",
+		       f[0].kmers, f[0].zero, json_num(mean(f[0]), "%.4f").c_str(), peak_json(f[0]).c_str(), f[0].saturated, f[1].kmers, f[1].zero,
+		       json_num(mean(f[1]), "%.4f").c_str(), peak_json(f[1]).c_str(), f[1].saturated, t.ms_spectrum[0], t.ms_spectrum[1]);
+	}
+}
+
 void
 report_qv(const RoundTotals& t)
 {

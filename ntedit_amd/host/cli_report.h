@@ -1,5 +1,5 @@
 // cli_report.h -- what a polishing round says at its end: the QV table's total and summary line, the completeness table and
-// line, the --bgzip and --bed lines, and the --report JSON lines.
+// line, the --bgzip and --bed lines, the --spectrum table and line, and the --report JSON lines.
 #pragma once
 
 #include "../../include/ntedit_hip.h"
@@ -31,6 +31,11 @@ struct RoundTotals
 	unsigned long long bed_intervals[2] = { 0, 0 }, bed_bases[2] = { 0, 0 };
 	double ms_track[2] = { 0, 0 };
 
+	// --spectrum: the bins before [0] and after [1] and the depth rows, summed; the two launches' times
+	unsigned long long spectrum[2][256] = {};
+	ntedit_hip_depth_row depth = {};
+	double ms_spectrum[2] = { 0, 0 };
+
 	void add(const ntedit_hip_stats& st);
 	void add(const ntedit_hip_bgzf_stats& bs);
 	void add(const ntedit_hip_qv_row& row);
@@ -44,6 +49,9 @@ void finish_completeness(ntedit_hip_ctx* ctx, const std::string& prefix, uint32_
 void finish_bgzip(const RoundTotals& t, const std::string& fa_path, bool report);
 // --bed: the summary line; with --report its JSON
 void finish_bed(const RoundTotals& t, const std::string paths[2], bool report);
+// --spectrum: <prefix>_spectrum.tsv from the summed bins, the "#total" row and the depth table closed, the summary line;
+// with --report its JSON
+void finish_spectrum(const RoundTotals& t, FILE* depth_f, const std::string paths[2], uint32_t k, bool report);
 // --report
 void report_qv(const RoundTotals& t);
 void report_round(const RoundTotals& t);

@@ -8,7 +8,9 @@
 // ##fileDate line carries today's date, as in the reference) -- and the summaries (cli_report.cpp).  With --bgzip the
 // edited draft is <prefix>_edited.fa.gz: the GPU stage's results hold its BGZF members, the writer stage appends them.
 // With --qv --bed the results hold the unsupported regions before and after as intervals, and the writer stage appends
-// them to <prefix>_absent_before.bed and <prefix>_absent_after.bed.
+// them to <prefix>_absent_before.bed and <prefix>_absent_after.bed.  With --spectrum they hold the k-mer spectrum before
+// and after and a depth row per contig: the writer stage sums the bins and appends the rows to <prefix>_depth.tsv,
+// <prefix>_spectrum.tsv is written at the round's end.
 #include "../../include/ntedit_hip.h"
 #include "cli_batches.h"
 #include "cli_common.h"
@@ -37,7 +39,7 @@ struct Run
 };
 
 // what the three pipeline stages of a round share.  Each total has one writer: the reader stage `bases` and `s_read`, the
-// GPU stage `s_call` and the --qv and --bed times, the writer stage the rest; they are read after the stages are joined.
+// GPU stage `s_call` and the --qv, --bed and --spectrum times, the writer stage the rest; they are read after the stages are joined.
 struct Round
 {
 	const CliOptions& opt;
@@ -46,6 +48,8 @@ struct Round
 	std::string fa_path, tsv_path, vcf_path, qv_path, bed_path[2];
 	FILE *qv_f = nullptr, *index_f = nullptr;
 	FILE* bed_f[2] = { nullptr, nullptr }; // --bed: <prefix>_absent_before.bed, _absent_after.bed
+	std::string spectrum_path[2];          // --spectrum: <prefix>_spectrum.tsv, <prefix>_depth.tsv
+	FILE* depth_f = nullptr;
 	int fa_fd = -1; // --bgzip: <prefix>_edited.fa.gz, open for the writer stage
 	ntedit_hip_annot* annot = nullptr;
 	Channel free_q, gpu_q, write_q;
@@ -78,6 +82,10 @@ describe_filter(ntedit_hip_ctx* ctx, const CliOptions& opt, const std::string& b
 	if (opt.completeness && *counting) {
 		// (before any output file is opened and before a batch is polished)
 		fail("--completeness: `%s' is a counting filter; completeness takes a plain filter", bf.c_str());
+	}
+	if (opt.spectrum && !*counting) {
+		// (the same, the other way round)
+		fail("--spectrum: `%s' is a plain filter; the spectrum takes a counting filter", bf.c_str());
 	}
 	if (!*counting && p->min_threshold != 1) {
 		// ntedit.cpp:2453-2458
@@ -153,6 +161,9 @@ prepare_device(Run& run, const CliOptions& opt, const ntedit_hip_params& p, bool
 	if (apply && ntedit_hip_set_apply(ctx, apply) != 0) {
 		fail("%s", ntedit_hip_last_error(ctx));
 	}
+	if (opt.spectrum && ntedit_hip_set_spectrum(ctx, 1) != 0) {
+		fail("%s", ntedit_hip_last_error(ctx));
+	}
 	// --completeness: the two mark arrays of this round's filter, mapped here and not inside the first batch
 	if (opt.completeness && ntedit_hip_shared_begin(ctx) != 0) {
 		fail("%s", ntedit_hip_last_error(ctx));
@@ -210,6 +221,14 @@ open_outputs(Round& r, const ntedit_hip_params& p, int counting, const std::stri
 		if (!r.bed_f[which]) {
 			fail("cannot write `%s'", r.bed_path[which].c_str());
 		}
+	}
+	// --spectrum: the depth table, a row per written contig as the batches come back, "#total" at the end
+	if (opt.spectrum) {
+		r.depth_f = fopen(r.spectrum_path[1].c_str(), "wb");
+		if (!r.depth_f) {
+			fail("cannot write `%s'", r.spectrum_path[1].c_str());
+		}
+		fputs(ntedit_hip_depth_header(), r.depth_f);
 	}
 	if (!opt.vcf.empty()) {
 		// -l: annotated variants (e.g. clinvar.vcf[.gz]), ntedit.cpp:2524-2562
@@ -452,6 +471,37 @@ write_bed_rows(Round& r, const ntedit_hip_result* res, const std::vector<const c
 	}
 }
 
+// --spectrum: one batch's bins into the round's, its depth rows under the names of its entries
+static void
+write_spectrum_rows(Round& r, const ntedit_hip_result* res, const std::vector<const char*>& names)
+{
+	for (int which = 0; which < 2; which++) {
+		uint64_t bins[256];
+		if (ntedit_hip_result_spectrum(res, which, bins) != 0) {
+			fail("%s", ntedit_hip_result_last_error());
+		}
+		for (int c = 0; c < 256; c++) {
+			r.tot.spectrum[which][c] += bins[c];
+		}
+	}
+	std::vector<ntedit_hip_depth_row> rows(names.size());
+	std::string line;
+	bool ok = ntedit_hip_result_depth(res, rows.data(), (uint32_t)rows.size()) == 0;
+	for (size_t i = 0; ok && i < rows.size(); i++) {
+		line.resize(strlen(names[i]) + 256);
+		ok = ntedit_hip_depth_format_row(names[i], &rows[i], &line[0], line.size()) == 0 && fputs(line.c_str(), r.depth_f) >= 0;
+		r.tot.depth.kmers_before += rows[i].kmers_before;
+		r.tot.depth.sum_before += rows[i].sum_before;
+		r.tot.depth.saturated_before += rows[i].saturated_before;
+		r.tot.depth.kmers_after += rows[i].kmers_after;
+		r.tot.depth.sum_after += rows[i].sum_after;
+		r.tot.depth.saturated_after += rows[i].saturated_after;
+	}
+	if (!ok) {
+		fail("cannot write `%s'", r.spectrum_path[1].c_str());
+	}
+}
+
 // Writer stage: renders the batches the GPU stage hands over, in order, and sums their statistics.
 static void
 write_batches(Round& r)
@@ -506,6 +556,9 @@ write_batches(Round& r)
 		for (int which = 0; r.opt.bed && which < 2; which++) {
 			write_bed_rows(r, w->res, names, which);
 		}
+		if (r.depth_f) {
+			write_spectrum_rows(r, w->res, names);
+		}
 		ntedit_hip_stats st;
 		ntedit_hip_result_stats(w->res, &st);
 		r.tot.add(st);
@@ -554,6 +607,11 @@ polish_batches(Round& r)
 			r.tot.ms_track[0] += ts.ms[0];
 			r.tot.ms_track[1] += ts.ms[1];
 		}
+		ntedit_hip_spectrum_stats ss;
+		if (r.opt.spectrum && ntedit_hip_spectrum_info(r.ctx, &ss) == 0) {
+			r.tot.ms_spectrum[0] += ss.ms[0];
+			r.tot.ms_spectrum[1] += ss.ms[1];
+		}
 		ntedit_hip_bgzf_stats bs;
 		if (r.opt.bgzip && ntedit_hip_bgzf_info(r.ctx, &bs) == 0) {
 			r.tot.add(bs);
@@ -601,6 +659,8 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	r.qv_path = prefix + "_qv.tsv";
 	r.bed_path[0] = prefix + "_absent_before.bed";
 	r.bed_path[1] = prefix + "_absent_after.bed";
+	r.spectrum_path[0] = prefix + "_spectrum.tsv";
+	r.spectrum_path[1] = prefix + "_depth.tsv";
 	open_outputs(r, p, counting, draft);
 
 	// ---- the draft.  Plain multi-FASTA files are taken apart by several threads from a mapping of the file (fasta_map.h);
@@ -693,6 +753,9 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	}
 	if (opt.bed) {
 		finish_bed(r.tot, r.bed_path, opt.report != 0);
+	}
+	if (r.depth_f) {
+		finish_spectrum(r.tot, r.depth_f, r.spectrum_path, r.k, opt.report != 0);
 	}
 	if (opt.report && opt.qv) {
 		report_qv(r.tot);

@@ -94,6 +94,61 @@ ntedit_hip_track_format_row(const char* name, const ntedit_hip_track_interval* i
 	return 0;
 }
 
+// ---- the k-mer spectrum and the depth rows (the counts come from k_spectrum through ntedit_hip_result_spectrum / _depth)
+
+const char*
+ntedit_hip_spectrum_header(void)
+{
+	return "multiplicity\tbefore\tafter\n";
+}
+
+int
+ntedit_hip_spectrum_format_row(uint32_t multiplicity, uint64_t before, uint64_t after, char* out, uint64_t cap)
+{
+	if (!out || multiplicity > 255) {
+		return NTEDIT_E_ARG;
+	}
+	const std::string s = std::to_string(multiplicity) + '\t' + std::to_string(before) + '\t' + std::to_string(after) + '\n';
+	if (s.size() + 1 > cap) {
+		return NTEDIT_E_OVERFLOW;
+	}
+	memcpy(out, s.c_str(), s.size() + 1);
+	return 0;
+}
+
+const char*
+ntedit_hip_depth_header(void)
+{
+	return "name\tkmers_before\tmean_before\tsaturated_before\tkmers_after\tmean_after\tsaturated_after\n";
+}
+
+static std::string
+mean_text(uint64_t sum, uint64_t kmers)
+{
+	if (kmers == 0) {
+		return "NA";
+	}
+	char b[64];
+	snprintf(b, sizeof b, "%.2f", (double)sum / (double)kmers);
+	return b;
+}
+
+int
+ntedit_hip_depth_format_row(const char* name, const ntedit_hip_depth_row* row, char* out, uint64_t cap)
+{
+	if (!name || !row || !out) {
+		return NTEDIT_E_ARG;
+	}
+	std::string s(name, strcspn(name, " \t")); // (the sequence name as faidx understands it)
+	s += '\t' + std::to_string(row->kmers_before) + '\t' + mean_text(row->sum_before, row->kmers_before) + '\t' + std::to_string(row->saturated_before);
+	s += '\t' + std::to_string(row->kmers_after) + '\t' + mean_text(row->sum_after, row->kmers_after) + '\t' + std::to_string(row->saturated_after) + '\n';
+	if (s.size() + 1 > cap) {
+		return NTEDIT_E_OVERFLOW;
+	}
+	memcpy(out, s.c_str(), s.size() + 1);
+	return 0;
+}
+
 // ---- k-mer completeness (linear counting: the marks come from k_mark through ntedit_hip_shared_counts)
 
 double

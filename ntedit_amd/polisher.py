@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, TRACK_DTYPE, APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF, APPLY_TRACK  # noqa: F401
+from ._lib import NtEditHipError, Params, Stats, Segment, WriteOptions, EDIT_DTYPE, QV_DTYPE, TRACK_DTYPE, DEPTH_DTYPE, APPLY_EDITED, APPLY_QV, APPLY_SHARED, APPLY_BGZF, APPLY_TRACK  # noqa: F401
 
 PRIMARY, SECONDARY = 0, 1
 
@@ -197,6 +197,24 @@ class Result:
         if rc:
             self._result_error("result_track", rc)
         return recs[:n.value]
+
+    def spectrum(self, which):
+        """uint64[256]: the k-mer occurrences at every multiplicity 0 .. 255 before (which = 0) or after (1) the polish,
+        against the counting PRIMARY filter; needs set_spectrum(True)"""
+        bins = np.zeros(256, dtype=np.uint64)
+        rc = self._lib.ntedit_hip_result_spectrum(self._h, int(which), bins.ctypes.data_as(ctypes.c_void_p))
+        if rc:
+            self._result_error("result_spectrum", rc)
+        return bins
+
+    def depth(self, n_contigs):
+        """one record per entry (dtype _lib.DEPTH_DTYPE): k-mer occurrences, the sum of their multiplicities and the
+        saturated ones, before and after; needs set_spectrum(True)"""
+        rows = np.zeros(max(n_contigs, 1), dtype=np.dtype(DEPTH_DTYPE))
+        rc = self._lib.ntedit_hip_result_depth(self._h, rows.ctypes.data_as(ctypes.c_void_p), n_contigs)
+        if rc:
+            self._result_error("result_depth", rc)
+        return rows[:n_contigs]
 
     def fa_bgzf(self):
         """(bytes, plain bytes, members): the batch's _edited.fa text as BGZF members, copied out of the result's
@@ -469,6 +487,60 @@ class Polisher:
                 covered += iv.end - iv.begin
         return covered
 
+    # ---- the k-mer multiplicity spectrum against a counting PRIMARY filter (k_spectrum)
+    def set_spectrum(self, on):
+        """ntedit_hip_set_spectrum: the polish_batch calls that follow count the spectrum before and after
+        (Result.spectrum(), Result.depth()); a switch of its own beside set_apply's flags"""
+        self._check(self._lib.ntedit_hip_set_spectrum(self._h, int(bool(on))), "set_spectrum")
+
+    def spectrum_count(self, blob, offs, lens, device_ptr=None, n=None, rows=True):
+        """(bins uint64[256], rows of dtype _lib.SPECTRUM_ROW_DTYPE or None) of any batch -- host bytes, or n device
+        bytes at device_ptr -- over the entries offs / lens (ntedit_hip_spectrum_count)"""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None  # noqa: E731
+        bins = np.zeros(256, dtype=np.uint64)
+        out = np.zeros(max(len(offs), 1), dtype=np.dtype(_lib.SPECTRUM_ROW_DTYPE)) if rows else None
+        if device_ptr is not None:
+            keep, bases, n, on_device = None, ctypes.c_void_p(device_ptr), int(n), 1
+        else:
+            keep, bases = Result._blob_ptr(blob)
+            n, on_device = len(blob), 0
+        rc = self._lib.ntedit_hip_spectrum_count(self._h, bases, n, on_device, ptr(offs), ptr(lens), len(offs),
+                                                 bins.ctypes.data_as(ctypes.c_void_p), ptr(out) if rows else None)
+        del keep
+        self._check(rc, "spectrum_count")
+        return bins, (out[:len(offs)] if rows else None)
+
+    def spectrum_info(self):
+        """ntedit_hip_spectrum_info of the last call that counted a spectrum: _lib.SpectrumStats"""
+        st = _lib.SpectrumStats()
+        self._check(self._lib.ntedit_hip_spectrum_info(self._h, ctypes.byref(st)), "spectrum_info")
+        return st
+
+    def write_spectrum_tables(self, out_prefix, names, bins_before, bins_after, depth):
+        """<prefix>_spectrum.tsv (the header, 256 rows) and <prefix>_depth.tsv (the header, one row per entry, "#total"),
+        through the library's formatters"""
+        buf = ctypes.create_string_buffer(1 << 16)
+        with open(out_prefix + "_spectrum.tsv", "wb") as f:
+            f.write(self._lib.ntedit_hip_spectrum_header())
+            for c in range(256):
+                self._lib.ntedit_hip_spectrum_format_row(c, int(bins_before[c]), int(bins_after[c]), buf, len(buf))
+                f.write(buf.value)
+        total = _lib.DepthRow()
+        with open(out_prefix + "_depth.tsv", "wb") as f:
+            f.write(self._lib.ntedit_hip_depth_header())
+            for name, r in zip(names, depth):
+                row = _lib.DepthRow(*[int(r[fld]) for fld, _ in _lib.DepthRow._fields_])
+                for fld, _ in _lib.DepthRow._fields_:
+                    setattr(total, fld, getattr(total, fld) + getattr(row, fld))
+                if self._lib.ntedit_hip_depth_format_row(bytes(name), ctypes.byref(row), buf, len(buf)):
+                    raise NtEditHipError("depth row of %r does not fit" % name)
+                f.write(buf.value)
+            self._lib.ntedit_hip_depth_format_row(b"#total", ctypes.byref(total), buf, len(buf))
+            f.write(buf.value)
+        return total
+
     # ---- k-mer completeness: the draft's distinct k-mers that the PRIMARY filter holds (DESIGN.md 9.10)
     def shared_begin(self):
         """allocate and zero the two mark arrays (before, after) for the current PRIMARY filter; idempotent"""
@@ -502,12 +574,14 @@ class Polisher:
     def bloom_cardinality(self, set_bits, slots, h=1):
         return self._lib.ntedit_hip_bloom_cardinality(int(set_bits), int(slots), int(h))
 
-    def polish_records(self, records, out_prefix, draft_name="", annot_path=None, qv=False, bed=False):
+    def polish_records(self, records, out_prefix, draft_name="", annot_path=None, qv=False, bed=False, spectrum=False):
         """readAndCorrect at -t 1 for an in-memory list of (header, sequence): writes
         <prefix>_edited.fa, <prefix>_changes.tsv and <prefix>_variants.vcf; returns Stats.
         qv: also <prefix>_qv.tsv, the k-mer QV of every contig before and after (set_apply(APPLY_QV) for this call).
         bed: also <prefix>_absent_before.bed (the draft's coordinates) and <prefix>_absent_after.bed (those of
-        _edited.fa), the regions the filter does not support (set_apply(APPLY_TRACK) for this call)."""
+        _edited.fa), the regions the filter does not support (set_apply(APPLY_TRACK) for this call).
+        spectrum: also <prefix>_spectrum.tsv and <prefix>_depth.tsv, the k-mer multiplicity spectrum and the depth of every
+        contig before and after, against a counting PRIMARY filter (set_spectrum(True) for this call)."""
         blob, offs, lens, names = pack_batch(records, self.params.min_contig_len)
         tsv = out_prefix + "_changes.tsv"
         fa = out_prefix + "_edited.fa"
@@ -523,17 +597,23 @@ class Polisher:
         packed = self.pack_bases(blob) if getattr(self, "send_packed", False) and len(blob) else None
         if qv or bed:
             self.set_apply((APPLY_QV if qv else 0) | (APPLY_TRACK if bed else 0))
+        if spectrum:
+            self.set_spectrum(True)
         try:
             res = self.polish_batch(blob, offs, lens, packed=packed)
         finally:
             if qv or bed:
                 self.set_apply(0)
+            if spectrum:
+                self.set_spectrum(False)
         res.write(blob, offs, lens, names, fa, tsv, append=True, vcf_path=vcf, snv=bool(self.params.snv), annot=annot)
         if qv:
             self.write_qv_table(out_prefix + "_qv.tsv", names, res.qv(len(names)))
         if bed:
             for which, stage in enumerate(("before", "after")):
                 self.write_track_bed("%s_absent_%s.bed" % (out_prefix, stage), names, res.track(which))
+        if spectrum:
+            self.write_spectrum_tables(out_prefix, names, res.spectrum(0), res.spectrum(1), res.depth(len(names)))
         if annot_path:
             self._lib.ntedit_hip_annot_free(annot)
         st = res.stats()

@@ -263,6 +263,7 @@ def parse(argv=None):
     ap.add_argument("--completeness", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     ap.add_argument("--bgzip", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     ap.add_argument("--bed", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
+    ap.add_argument("--spectrum", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     g = ap.add_argument_group("polishing straight from reads (--reads replaces -r; the options of `ntedit --reads`, "
                               "the same filter; every rank builds its share and holds the whole filter)")
     g.add_argument("--reads", nargs="*", metavar="FILE", help="input reads, FASTA or FASTQ, plain or gzip")
@@ -312,6 +313,9 @@ def parse(argv=None):
     if args.bed:
         raise Refused("--bed: the tracks of cut contigs on several GPUs would need a merge of their own, which is out of "
                       "scope; run `ntedit --qv --bed` on one GPU")
+    if args.spectrum:
+        raise Refused("--spectrum: the spectra and depth rows of cut contigs on several GPUs would need a merge of their own, "
+                      "which is out of scope; run `ntedit --spectrum` on one GPU")
     return args
 
 
