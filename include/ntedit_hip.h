@@ -1159,6 +1159,87 @@ int ntedit_hip_spectrum_format_row(uint32_t multiplicity, uint64_t before, uint6
 const char* ntedit_hip_depth_header(void);
 int ntedit_hip_depth_format_row(const char* name, const ntedit_hip_depth_row* row, char* out, uint64_t cap);
 
+/* ---- the spectrum split by assembly copy number (Merqury's spectra-cn; no counterpart in the reference) --
+ * The spectrum above, split by how many times the ASSEMBLY holds each k-mer.
+ *   F, a K-MER and its MULTIPLICITY m are as above.  A SIDE is `before` (0: every batch as it came) or `after` (1: every
+ *   batch's edited entries), accumulated over all calls since the last reset: copy number is a property of the whole draft,
+ *   so the bytes of both sides stay in device memory (the DRAFT STORE) until ntedit_hip_cn_finish.
+ *   For one side, the SKETCH S has `counters` 8-bit counters, a power of two.  It uses the filter's h and the filter's hash
+ *   values: every k-mer occurrence of the side adds 1 to all h counters S[hv_i & (counters - 1)], saturating at 255 -- plain
+ *   count-min, the same whatever the batching or order.  The COPY NUMBER cn(x) = min_i S[slot_i(x)], 1 .. 255; 255 means "255
+ *   or more"; it is never below the true count.  The CLASS c = min(cn, 5): 1, 2, 3, 4, 5plus.
+ *   occ[c - 1][m]: the k-mer occurrences of class c with multiplicity m.  w5[m]: the sum of RECIP[cn] over the class-5
+ *   occurrences with multiplicity m, RECIP[cn] = (2^32 + cn / 2) / cn in integer arithmetic, cn = 5 .. 255.
+ *   A ROW per entry, in the order the entries were appended: kmers and the five class counts of its occurrences.
+ *   DISTINCT k-mers (host): distinct[c - 1][m] = (occ[c - 1][m] + c / 2) / c for c = 1 .. 4, distinct[4][m] = (w5[m] + 2^31)
+ *   >> 32.
+ * So sum over c of occ[c][m] = the spectrum's bins[m] of that side; a row's five classes sum to its kmers = the depth row's
+ * kmers; the rows' class counts sum to sum over m of occ[c][m]; and without sketch collisions occ[c - 1][m] is a multiple of c.
+ * There is no "read-only" row (a filter cannot be enumerated; --completeness gives that total for plain filters), and copy
+ * numbers are count-min estimates: the expected inflated share is (nonzero counters / counters)^h.  h = 1 gives a poor sketch.
+ * ntedit_hip_set_cn(ctx, on, store_cap_bytes): a switch of its own, as ntedit_hip_set_spectrum is.  ON: the store begins
+ * empty with that cap on the bytes of both sides together; ntedit_hip_polish_batch runs the applier whatever the flags and
+ * appends both sides (device-to-device copies), and refuses as ntedit_hip_set_spectrum does before anything is polished:
+ * NTEDIT_E_UNSUPPORTED on a plain PRIMARY filter, NTEDIT_E_ARG without one.  A batch that would pass the cap, or an
+ * allocation that fails, releases the whole store (NTEDIT_CN_OVER_CAP / NTEDIT_CN_NO_MEMORY) and fails nothing: the polish
+ * goes on.  Another PRIMARY filter empties the store (every round of a cascade starts clean); ntedit_hip_reserve's warm-up
+ * batch leaves nothing in it.  OFF (the default): nothing runs, the store is released. */
+#define NTEDIT_CN_OFF 0
+#define NTEDIT_CN_ON 1
+#define NTEDIT_CN_OVER_CAP 2
+#define NTEDIT_CN_NO_MEMORY 3
+#define NTEDIT_CN_STORE_DEFAULT (32ull << 30)
+#define NTEDIT_CN_SKETCH_MIN (1ull << 20)
+#define NTEDIT_CN_SKETCH_MAX (1ull << 36)
+#define NTEDIT_CN_SKETCH_FLOOR (1ull << 6) /* what the library itself takes: a sketch this small is all collisions (the tests' way to force them) */
+int ntedit_hip_set_cn(ntedit_hip_ctx* ctx, int on, uint64_t store_cap_bytes);
+/* Stand-alone: one batch to side `which`.  bases: n bytes, host (on_device 0) or device (1); offs, lens: n_entries entries
+ * in batch order, host arrays; entries do not overlap and may abut.  NTEDIT_E_ARG while the switch is off. */
+int ntedit_hip_cn_append(ntedit_hip_ctx* ctx, int which, const char* bases, uint64_t n, int on_device, const uint64_t* offs, const uint32_t* lens,
+                         uint32_t n_entries);
+/* Both sides from the store: per side the sketch zeroed, k_cn_count over every stored batch, the non-zero counters,
+ * k_spectrum_cn over every stored batch; then one copy to the host.  The store stays as it is.  sketch_counters = 0: the
+ * smallest power of two at or above 8 times the larger side's stored bytes, within [2^20, 2^36]; anything else must be a
+ * power of two (NTEDIT_E_ARG) -- in that range for any use (`ntedit --cn_sketch` takes no other); the call itself also
+ * takes the sizes from NTEDIT_CN_SKETCH_FLOOR up to 2^20, where most copy numbers are inflated, so that a test can force
+ * collisions.  NTEDIT_E_OVERFLOW with a one-line message when the store was released. */
+int ntedit_hip_cn_finish(ntedit_hip_ctx* ctx, uint64_t sketch_counters);
+/* The raw results of one side after ntedit_hip_cn_finish (NTEDIT_E_ARG before it): occ[5][256], w5[256]. */
+int ntedit_hip_cn_table(ntedit_hip_ctx* ctx, int which, uint64_t* occ, uint64_t* w5);
+typedef struct ntedit_hip_cn_row
+{
+	uint64_t kmers, cn1, cn2, cn3, cn4, cn5plus;
+} ntedit_hip_cn_row;
+/* The rows of one side, n = the entries appended to it (NTEDIT_E_ARG otherwise, and before ntedit_hip_cn_finish). */
+int ntedit_hip_cn_rows(ntedit_hip_ctx* ctx, int which, ntedit_hip_cn_row* rows, uint64_t n);
+/* distinct[5][256] from occ[5][256] and w5[256].  Host only: no context, no device. */
+int ntedit_hip_cn_distinct(const uint64_t* occ, const uint64_t* w5, uint64_t* distinct);
+typedef struct ntedit_hip_cn_stats
+{
+	uint32_t state;      /* NTEDIT_CN_* */
+	uint32_t finished;   /* 1 after ntedit_hip_cn_finish, 0 again after an append or a reset */
+	uint64_t batches[2]; /* stored, per side */
+	uint64_t bytes[2];
+	uint64_t entries[2];
+	uint64_t cap;
+	uint64_t counters;   /* of the last ntedit_hip_cn_finish */
+	uint64_t nonzero[2]; /* its non-zero counters per side */
+	float ms[4];         /* HIP-event sums: k_cn_count before, k_spectrum_cn before, k_cn_count after, k_spectrum_cn after */
+} ntedit_hip_cn_stats;
+int ntedit_hip_cn_info(ntedit_hip_ctx* ctx, ntedit_hip_cn_stats* st);
+/* ntedit_hip_cn_reset: the batches and results go, the switch stays.  ntedit_hip_cn_free: the sketch and the result
+ * buffers go as well. */
+int ntedit_hip_cn_reset(ntedit_hip_ctx* ctx);
+int ntedit_hip_cn_free(ntedit_hip_ctx* ctx);
+/* <prefix>_spectrum_cn.tsv: "multiplicity", before_cn1 .. before_cn4, before_cn5plus, after_cn1 .. after_cn5plus, in
+ * DISTINCT k-mers; one row per multiplicity 0 .. 255 from the two distinct[5][256].  <prefix>_cn_contigs.tsv: name (cut at
+ * its first space or tab), then kmers and the five class counts of occurrences before and after; a last row "#total" (the
+ * caller's sum) closes it.  Host only; NTEDIT_E_OVERFLOW when the row does not fit out[0 .. cap). */
+const char* ntedit_hip_cn_header(void);
+int ntedit_hip_cn_format_row(uint32_t multiplicity, const uint64_t* distinct_before, const uint64_t* distinct_after, char* out, uint64_t cap);
+const char* ntedit_hip_cn_contig_header(void);
+int ntedit_hip_cn_contig_format_row(const char* name, const ntedit_hip_cn_row* before, const ntedit_hip_cn_row* after, char* out, uint64_t cap);
+
 /* The reference's candidate tables -- num_tries, polish_bases_array / snv_bases_array, multi_possible_bases (ntedit.cpp:172,
  * 176-199, 203-348) -- as the device code holds them (one GPU thread runs the machine's own candidate_bases /
  * insertion_candidate), as text: "num_tries 0 1 5 21 85 341", "polish A TCG", ..., "snv N ATCG", "multi A A AA AC ...".

@@ -207,6 +207,26 @@ class SpectrumStats(ctypes.Structure):
     _fields_ = [("ms", ctypes.c_float * 2), ("kmers", ctypes.c_uint64 * 2)]
 
 
+class CnRow(ctypes.Structure):
+    """ntedit_hip_cn_row: an entry's k-mer occurrences and those of assembly copy number 1, 2, 3, 4 and 5 or more on one
+    side (ntedit_hip_set_cn)"""
+    _fields_ = [("kmers", ctypes.c_uint64), ("cn1", ctypes.c_uint64), ("cn2", ctypes.c_uint64), ("cn3", ctypes.c_uint64),
+                ("cn4", ctypes.c_uint64), ("cn5plus", ctypes.c_uint64)]
+
+
+CN_ROW_DTYPE = [(name, "<u8") for name, _ in CnRow._fields_]
+CN_OFF, CN_ON, CN_OVER_CAP, CN_NO_MEMORY = 0, 1, 2, 3
+CN_STORE_DEFAULT = 32 << 30
+
+
+class CnStats(ctypes.Structure):
+    """ntedit_hip_cn_stats: the draft store and the last ntedit_hip_cn_finish; [0] before, [1] after; ms: k_cn_count
+    before, k_spectrum_cn before, k_cn_count after, k_spectrum_cn after"""
+    _fields_ = [("state", ctypes.c_uint32), ("finished", ctypes.c_uint32), ("batches", ctypes.c_uint64 * 2),
+                ("bytes", ctypes.c_uint64 * 2), ("entries", ctypes.c_uint64 * 2), ("cap", ctypes.c_uint64),
+                ("counters", ctypes.c_uint64), ("nonzero", ctypes.c_uint64 * 2), ("ms", ctypes.c_float * 4)]
+
+
 class SharedStats(ctypes.Structure):
     """ntedit_hip_shared_stats: the popcounts behind the k-mer completeness (ntedit_hip_shared_counts)"""
     _fields_ = [("bits", ctypes.c_uint64), ("hash_num", ctypes.c_uint32), ("k", ctypes.c_uint32),
@@ -336,6 +356,9 @@ EXPORTS = [
     "ntedit_hip_set_spectrum", "ntedit_hip_result_spectrum", "ntedit_hip_result_depth", "ntedit_hip_spectrum_count",
     "ntedit_hip_spectrum_info", "ntedit_hip_spectrum_header", "ntedit_hip_spectrum_format_row", "ntedit_hip_depth_header",
     "ntedit_hip_depth_format_row",
+    "ntedit_hip_set_cn", "ntedit_hip_cn_append", "ntedit_hip_cn_finish", "ntedit_hip_cn_table", "ntedit_hip_cn_rows",
+    "ntedit_hip_cn_distinct", "ntedit_hip_cn_info", "ntedit_hip_cn_reset", "ntedit_hip_cn_free", "ntedit_hip_cn_header",
+    "ntedit_hip_cn_format_row", "ntedit_hip_cn_contig_header", "ntedit_hip_cn_contig_format_row",
 ]
 # ... and the declared names that hold a digit (a scan of the header for names of letters and underscores, as
 # tests/test_abi.py makes one, does not see them)
@@ -559,5 +582,19 @@ def load():
     lib.ntedit_hip_spectrum_format_row.argtypes = [u32, u64, u64, ctypes.c_char_p, u64]
     lib.ntedit_hip_depth_header.restype = ctypes.c_char_p
     lib.ntedit_hip_depth_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(DepthRow), ctypes.c_char_p, u64]
+    # the spectrum by assembly copy number (nte_cn.hip)
+    lib.ntedit_hip_set_cn.argtypes = [vp, ci, u64]
+    lib.ntedit_hip_cn_append.argtypes = [vp, ci, vp, u64, ci, vp, vp, u32]
+    lib.ntedit_hip_cn_finish.argtypes = [vp, u64]
+    lib.ntedit_hip_cn_table.argtypes = [vp, ci, vp, vp]
+    lib.ntedit_hip_cn_rows.argtypes = [vp, ci, vp, u64]
+    lib.ntedit_hip_cn_distinct.argtypes = [vp, vp, vp]
+    lib.ntedit_hip_cn_info.argtypes = [vp, ctypes.POINTER(CnStats)]
+    lib.ntedit_hip_cn_reset.argtypes = [vp]
+    lib.ntedit_hip_cn_free.argtypes = [vp]
+    lib.ntedit_hip_cn_header.restype = ctypes.c_char_p
+    lib.ntedit_hip_cn_format_row.argtypes = [u32, vp, vp, ctypes.c_char_p, u64]
+    lib.ntedit_hip_cn_contig_header.restype = ctypes.c_char_p
+    lib.ntedit_hip_cn_contig_format_row.argtypes = [ctypes.c_char_p, ctypes.POINTER(CnRow), ctypes.POINTER(CnRow), ctypes.c_char_p, u64]
     _lib = lib
     return lib

@@ -8,6 +8,7 @@
 #include "nte_apply.h"
 #include "nte_bgzf_launch.h"
 #include "nte_track.h"
+#include "nte_cn.h"
 
 #include "../../include/ntedit_hip.h"
 #include "../host/bfio.h"
@@ -167,6 +168,9 @@ struct ntedit_hip_ctx
 	DevBuf sp_buf;
 	hipEvent_t sp_evt[4] = { nullptr, nullptr, nullptr, nullptr };
 	ntedit_hip_spectrum_stats spectrum_last = { { 0.f, 0.f }, { 0, 0 } };
+	// the spectrum by copy number (nte_cn.hip; ntedit_hip_set_cn): the switch is the store's state; both sides of the draft
+	// stay in HBM until ntedit_hip_cn_finish
+	CnStore cn;
 	// linear counting of the draft's present k-mers (k_mark; ntedit_hip_shared_*): two mark arrays of the PRIMARY filter's
 	// size, before and after; they go when the slot gets another filter (drop_filter)
 	DevBuf sh_marks[2];

@@ -149,6 +149,7 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 			(void)hipEventDestroy(e);
 		}
 	}
+	cn_free(c->cn);
 	for (auto& e : c->chunk_ev) {
 		(void)hipEventDestroy(e);
 	}
@@ -190,6 +191,7 @@ drop_filter(ntedit_hip_ctx* c, int slot)
 	c->dp_valid = false;
 	if (slot == 0) {
 		shared_release(c); // (the completeness marks were this filter's)
+		cn_reset(c->cn);   // (and the draft store's copy numbers belong to one round: every round of a cascade starts clean)
 	}
 	return 0;
 }

@@ -1155,7 +1155,8 @@ PolishRun::apply()
 	r->apply_flags = flags;
 	r->device = c->device;
 	const bool spectrum = c->spectrum_on;
-	if (!flags && !spectrum) {
+	const bool cn = c->cn.state != CN_OFF;
+	if (!flags && !spectrum && !cn) {
 		return 0;
 	}
 	int rc;
@@ -1334,6 +1335,17 @@ PolishRun::apply()
 			he = hipMemcpyAsync(sp_host.data(), c->sp_buf.p, sp_host.size() * 8, hipMemcpyDeviceToHost, s);
 		}
 	}
+	// The spectrum by copy number (ntedit_hip_set_cn; nte_cn.hip): both sides go into the draft store, device to device;
+	// nothing is counted before ntedit_hip_cn_finish.  A store that passes its cap releases itself and fails nothing.
+	if (he == hipSuccess && !qrc && cn) {
+		std::string why;
+		if ((qrc = cn_append(c->cn, 0, s, d_seq, n, a.offs, a.lens, n_contigs, &why)) == 0) {
+			qrc = cn_append(c->cn, 1, s, a.out, total_bytes, a.out_offs, a.out_lens, n_contigs, &why);
+		}
+		if (qrc) {
+			qrc = fail(c, qrc, "apply: %s", why.c_str());
+		}
+	}
 	if (he == hipSuccess) {
 		he = hipStreamSynchronize(s);
 	}
@@ -1449,7 +1461,7 @@ ntedit_hip_polish_batch(
 	*out = nullptr;
 	HIP_TRY(c, hipSetDevice(c->device));
 	int rc;
-	if (c->spectrum_on && (rc = spectrum_refuse(c, "polish_batch"))) {
+	if ((c->spectrum_on || c->cn.state != CN_OFF) && (rc = spectrum_refuse(c, "polish_batch"))) {
 		return rc; // (a plain filter, or none -- NTEDIT_E_ARG, ahead of the general answer below: before anything is polished)
 	}
 	if ((rc = refresh_params(c))) {
@@ -1611,8 +1623,15 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 		if (keep_spectrum && !c->apply_flags) {
 			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
 		}
+		// (nor anything in the draft store: its state is OFF for the warm-up)
+		const int keep_cn = c->cn.state;
+		c->cn.state = CN_OFF;
+		if (keep_cn != CN_OFF && !c->apply_flags) {
+			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
+		}
 		ntedit_hip_result* wr = nullptr;
 		rc = ntedit_hip_polish_batch(c, buf.data(), wn, offs.data(), lens.data(), wc, NTEDIT_HIP_BASES_HOST, &wr);
+		c->cn.state = keep_cn;
 		c->spectrum_on = keep_spectrum;
 		c->apply_flags = keep_flags;
 		c->tune = keep;
@@ -1691,7 +1710,7 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 			return rc;
 		}
 	}
-	if (c->apply_flags || c->spectrum_on) { // (the applier: an event's summary and place, the edited bases, the piece table; the QV bitmap)
+	if (c->apply_flags || c->spectrum_on || c->cn.state != CN_OFF) { // (the applier: an event's summary and place, the edited bases, the piece table; the QV bitmap)
 		if ((rc = ensure(c, c->ap_ev, (size_t)(n_ev + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, c->ap_place, (size_t)(n_ev + 1) * sizeof(ApplyPlace))) ||
 		    (rc = ensure(c, c->ap_pieces, (size_t)(2 * n_ev + 2 * (u64)max_contigs + 1024) * sizeof(ApplyPiece))) ||
 		    (rc = ensure(c, c->ap_edited, (size_t)(n + n / 64 + 4096)))) {

@@ -326,6 +326,162 @@ ntedit_hip_spectrum_info(ntedit_hip_ctx* c, ntedit_hip_spectrum_stats* st)
 	return 0;
 }
 
+// ---- the spectrum by copy number (nte_cn.hip: the draft store, k_cn_count, k_spectrum_cn)
+
+int
+ntedit_hip_set_cn(ntedit_hip_ctx* c, int on, uint64_t store_cap_bytes)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	cn_switch(c->cn, on != 0, store_cap_bytes);
+	return 0;
+}
+
+int
+ntedit_hip_cn_append(ntedit_hip_ctx* c, int which, const char* bases, uint64_t n, int on_device, const uint64_t* offs, const uint32_t* lens,
+                     uint32_t n_entries)
+{
+	if (!c || which < 0 || which > 1 || (n && !bases) || (n_entries && (!offs || !lens))) {
+		return fail(c, NTEDIT_E_ARG, "cn_append: bad argument");
+	}
+	if (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) {
+		return fail(c, NTEDIT_E_ARG, "cn_append: bases must be host or device bytes");
+	}
+	if (c->cn.state == CN_OFF) {
+		return fail(c, NTEDIT_E_ARG, "cn_append: the copy numbers are switched off (ntedit_hip_set_cn)");
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc = spectrum_refuse(c, "cn_append");
+	if (rc) {
+		return rc;
+	}
+	for (u32 i = 0; i < n_entries; i++) {
+		if (offs[i] > n || lens[i] > n - offs[i] || (i + 1 < n_entries && offs[i] + lens[i] > offs[i + 1])) {
+			return fail(c, NTEDIT_E_ARG, "cn_append: entry %u breaks the batch layout", i);
+		}
+	}
+	std::string why;
+	if ((rc = cn_append(c->cn, which, c->stream, bases, n, offs, lens, n_entries, &why))) {
+		return fail(c, rc, "%s", why.c_str());
+	}
+	HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the caller's arrays are free again)
+	return 0;
+}
+
+int
+ntedit_hip_cn_finish(ntedit_hip_ctx* c, uint64_t sketch_counters)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	if (sketch_counters && ((sketch_counters & (sketch_counters - 1)) || sketch_counters < CN_FLOOR_COUNTERS || sketch_counters > CN_MAX_COUNTERS)) {
+		return fail(c, NTEDIT_E_ARG, "cn_finish: the sketch takes a power of two of 2^20 to 2^36 counters (from 2^6 to force collisions), or 0 for the default");
+	}
+	switch (c->cn.state) {
+	case CN_OFF:
+		return fail(c, NTEDIT_E_ARG, "cn_finish: the copy numbers are switched off (ntedit_hip_set_cn)");
+	case CN_OVER_CAP:
+		return fail(c, NTEDIT_E_OVERFLOW, "cn_finish: the draft passed the store's cap of %llu bytes and the store was released", (unsigned long long)c->cn.cap);
+	case CN_NO_MEMORY:
+		return fail(c, NTEDIT_E_OVERFLOW, "cn_finish: the device had no memory for the draft and the store was released");
+	default:
+		break;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc = spectrum_refuse(c, "cn_finish");
+	if (rc || (rc = refresh_params(c))) {
+		return rc;
+	}
+	std::string why;
+	const u64 counters = sketch_counters ? sketch_counters : cn_default_counters(c->cn);
+	if ((rc = cn_finish(c->cn, c->stream, dev_filter(c->filt[0]), c->dp, c->d_tab, counters, &why))) {
+		return fail(c, rc, "%s", why.c_str());
+	}
+	return 0;
+}
+
+int
+ntedit_hip_cn_table(ntedit_hip_ctx* c, int which, uint64_t* occ, uint64_t* w5)
+{
+	if (!c || which < 0 || which > 1 || !occ || !w5) {
+		return fail(c, NTEDIT_E_ARG, "cn_table: bad argument");
+	}
+	if (!c->cn.finished) {
+		return fail(c, NTEDIT_E_ARG, "cn_table: no results: ntedit_hip_set_cn, the batches, then ntedit_hip_cn_finish");
+	}
+	const u64* t = c->cn.table[which].data();
+	memcpy(occ, t, (size_t)CN_CLASSES * CN_BINS * 8);
+	memcpy(w5, t + CN_CLASSES * CN_BINS, (size_t)CN_BINS * 8);
+	return 0;
+}
+
+int
+ntedit_hip_cn_rows(ntedit_hip_ctx* c, int which, ntedit_hip_cn_row* rows, uint64_t n)
+{
+	if (!c || which < 0 || which > 1 || (n && !rows)) {
+		return fail(c, NTEDIT_E_ARG, "cn_rows: bad argument");
+	}
+	if (!c->cn.finished) {
+		return fail(c, NTEDIT_E_ARG, "cn_rows: no results: ntedit_hip_set_cn, the batches, then ntedit_hip_cn_finish");
+	}
+	if (n != c->cn.entries[which]) {
+		return fail(c, NTEDIT_E_ARG, "cn_rows: the side holds %llu entries", (unsigned long long)c->cn.entries[which]);
+	}
+	static_assert(sizeof(ntedit_hip_cn_row) == CN_ROW_WORDS * 8, "a row is six words");
+	if (n) {
+		memcpy(rows, c->cn.rows[which].data(), (size_t)n * sizeof(ntedit_hip_cn_row));
+	}
+	return 0;
+}
+
+int
+ntedit_hip_cn_info(ntedit_hip_ctx* c, ntedit_hip_cn_stats* st)
+{
+	if (!c || !st) {
+		return fail(c, NTEDIT_E_ARG, "cn_info: bad argument");
+	}
+	const CnStore& s = c->cn;
+	memset(st, 0, sizeof *st);
+	st->state = (uint32_t)s.state;
+	st->finished = s.finished ? 1 : 0;
+	for (int w = 0; w < 2; w++) {
+		st->batches[w] = s.side[w].size();
+		st->bytes[w] = s.bytes[w];
+		st->entries[w] = s.entries[w];
+		st->nonzero[w] = s.nonzero[w];
+	}
+	st->cap = s.cap;
+	st->counters = s.counters;
+	for (int i = 0; i < 4; i++) {
+		st->ms[i] = s.ms[i];
+	}
+	return 0;
+}
+
+int
+ntedit_hip_cn_reset(ntedit_hip_ctx* c)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	cn_reset(c->cn);
+	return 0;
+}
+
+int
+ntedit_hip_cn_free(ntedit_hip_ctx* c)
+{
+	if (!c) {
+		return NTEDIT_E_ARG;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	cn_free(c->cn);
+	return 0;
+}
+
 // ---- the BGZF writer (nte_bgzf_deflate.hip)
 
 int

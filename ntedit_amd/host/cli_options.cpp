@@ -148,6 +148,29 @@ static const char HELP_SPECTRUM[] = PROGRAM
     "			{\"spectrum\": {...}}.  Not with a plain filter, --genome, --reads without --counts, or --shard\n"
     "	--help-spectrum,	display this paragraph and exit\n\n";
 
+static const char HELP_CN[] = PROGRAM
+    " --spectrum --cn\n\n"
+    "	--cn,		with --spectrum: the spectrum split by how many times the ASSEMBLY holds each k-mer (Merqury's spectra-cn).\n"
+    "			A k-mer's copy number is counted over the whole draft, so the draft and the edited contigs stay in HBM\n"
+    "			until the round ends; then a count-min sketch of 8-bit counters (the filter's h hashes) is counted over\n"
+    "			each side and read back per k-mer together with the filter.  Writes <prefix>_spectrum_cn.tsv\n"
+    "			(multiplicity, before_cn1 .. before_cn4, before_cn5plus, after_cn1 .. after_cn5plus: always 256 rows, in\n"
+    "			DISTINCT k-mers) and <prefix>_cn_contigs.tsv (name, then kmers and the five class counts of k-mer\n"
+    "			occurrences before and after: one row per contig in <prefix>_edited.fa's order, then #total).  A half-depth\n"
+    "			peak of copy-number-2 k-mers means retained haplotigs, a double-depth peak of copy-number-1 k-mers a\n"
+    "			collapsed repeat, a contig made mostly of copy-number-2 k-mers a duplicate.  Copy numbers are count-min\n"
+    "			estimates, never below the truth; the summary line prints the expected inflated share, (non-zero\n"
+    "			counters / counters)^h.  A filter with one hash (h = 1) gives a poor sketch.  There is no read-only row: a\n"
+    "			filter cannot be enumerated (--completeness gives that total for plain filters).  With -k K1,K2,... an\n"
+    "			earlier round writes <prefix>_k<Ki>_spectrum_cn.tsv and _cn_contigs.tsv.  --report adds {\"cn\": {...}}.\n"
+    "			Not without --spectrum, and with nothing --spectrum refuses\n"
+    "	--cn_store BYTES,	the most bases of both sides the store may hold [34359738368].  A draft that passes it releases\n"
+    "			the store: the polish and every other output finish as usual, no cn file is written, one line on\n"
+    "			standard error says so, the exit status is 0\n"
+    "	--cn_sketch COUNTERS,	the sketch's size, a power of two from 2^20 to 2^36 [the smallest at or above 8 times the\n"
+    "			stored bytes of the larger side]\n"
+    "	--help-cn,	display this paragraph and exit\n\n";
+
 static const char shortopts[] = "t:f:s:k:z:b:r:v:d:i:X:Y:x:y:m:c:j:s:e:a:l:p:q:";
 enum
 {
@@ -186,7 +209,11 @@ enum
 	OPT_BED,
 	OPT_HELP_BED,
 	OPT_SPECTRUM,
-	OPT_HELP_SPECTRUM
+	OPT_HELP_SPECTRUM,
+	OPT_CN,
+	OPT_CN_STORE,
+	OPT_CN_SKETCH,
+	OPT_HELP_CN
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -246,6 +273,10 @@ static const struct option longopts[] = {
 	{ "help-bed", no_argument, nullptr, OPT_HELP_BED },
 	{ "spectrum", no_argument, nullptr, OPT_SPECTRUM },
 	{ "help-spectrum", no_argument, nullptr, OPT_HELP_SPECTRUM },
+	{ "cn", no_argument, nullptr, OPT_CN },
+	{ "cn_store", required_argument, nullptr, OPT_CN_STORE },
+	{ "cn_sketch", required_argument, nullptr, OPT_CN_SKETCH },
+	{ "help-cn", no_argument, nullptr, OPT_HELP_CN },
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -590,6 +621,18 @@ parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOptio
 		case OPT_HELP_SPECTRUM:
 			fputs(HELP_SPECTRUM, stderr);
 			exit(EXIT_SUCCESS);
+		case OPT_CN:
+			o->cn = true;
+			break;
+		case OPT_CN_STORE:
+			o->cn_store_text = optarg;
+			break;
+		case OPT_CN_SKETCH:
+			o->cn_sketch_text = optarg;
+			break;
+		case OPT_HELP_CN:
+			fputs(HELP_CN, stderr);
+			exit(EXIT_SUCCESS);
 		case OPT_HELP:
 			fputs(USAGE, stderr);
 			exit(EXIT_SUCCESS);
@@ -672,6 +715,28 @@ parse_cli(int argc, char** argv)
 		     o.shard_given   ? " and --shard: the spectra of the shards would need a merge of their own; run --spectrum on the whole draft"
 		     : o.genome_mode ? " and --genome: the spectrum takes a counting filter; a genome filter is plain"
 		                     : " and --reads without --counts: the spectrum takes a counting filter; add --counts");
+	}
+	// --cn and its two settings: behind everything --spectrum refuses
+	if (o.cn && !o.spectrum) {
+		fail("--cn: only with --spectrum (the copy numbers split the spectrum)");
+	}
+	if ((o.cn_store_text || o.cn_sketch_text) && !o.cn) {
+		fail("%s: only with --cn", o.cn_store_text ? "--cn_store" : "--cn_sketch");
+	}
+	if (o.cn_store_text) {
+		char* end = nullptr;
+		o.cn_store = strtoull(o.cn_store_text, &end, 10);
+		if (!*o.cn_store_text || *end || o.cn_store_text[0] == '-') {
+			fail("--cn_store %s: a number of bytes", o.cn_store_text);
+		}
+	}
+	if (o.cn_sketch_text) {
+		char* end = nullptr;
+		o.cn_sketch = strtoull(o.cn_sketch_text, &end, 10);
+		if (!*o.cn_sketch_text || *end || o.cn_sketch_text[0] == '-' || (o.cn_sketch & (o.cn_sketch - 1)) || o.cn_sketch < NTEDIT_CN_SKETCH_MIN ||
+		    o.cn_sketch > NTEDIT_CN_SKETCH_MAX) {
+			fail("--cn_sketch %s: the sketch takes a power of two from 2^20 (1048576) to 2^36 counters", o.cn_sketch_text);
+		}
 	}
 	std::vector<std::string> k_list; // -k K1,K2,...: its k as given, in order
 	if (o.ro.k && strchr(o.ro.k, ',')) {

@@ -31,6 +31,10 @@ struct CliOptions
 	bool batch_given = false;
 	unsigned shard_i = 0, shard_n = 1;
 	bool shard_given = false, no_map = false, no_pack = true, qv = false, completeness = false, bgzip = false, bed = false, spectrum = false;
+	// --cn (with --spectrum): the cap of the draft store in bytes, the sketch's counters (0: the library picks)
+	bool cn = false;
+	const char *cn_store_text = nullptr, *cn_sketch_text = nullptr;
+	unsigned long long cn_store = 32ull << 30, cn_sketch = 0;
 	std::vector<std::pair<std::string, unsigned long long>> tunes;
 	// --reads FILE... / --genome FILE...: `paths` are the files of whichever was given
 	bool reads_mode = false, genome_mode = false;

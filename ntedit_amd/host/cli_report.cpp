@@ -3,6 +3,8 @@
 #include "cli_common.h"
 
 #include <cmath>
+#include <cstring>
+#include <vector>
 
 namespace nte_cli {
 
@@ -235,6 +237,123 @@ finish_spectrum(const RoundTotals& t, FILE* depth_f, const std::string paths[2],
 		       "\"spectrum_before_ms\": %.3f, \"spectrum_after_ms\": %.3f}}\n",
 		       f[0].kmers, f[0].zero, json_num(mean(f[0]), "%.4f").c_str(), peak_json(f[0]).c_str(), f[0].saturated, f[1].kmers, f[1].zero,
 		       json_num(mean(f[1]), "%.4f").c_str(), peak_json(f[1]).c_str(), f[1].saturated, t.ms_spectrum[0], t.ms_spectrum[1]);
+	}
+}
+
+// --cn: counts the draft store, writes both tables and says what they hold.  A store that was released (its cap, or no
+// memory) costs one line on standard error and no file; the run goes on.
+void
+finish_cn(ntedit_hip_ctx* ctx, const std::vector<std::string>& names, const std::string paths[2], uint32_t k, unsigned long long sketch,
+          bool report)
+{
+	ntedit_hip_cn_stats st;
+	const int rc = ntedit_hip_cn_finish(ctx, sketch);
+	if (ntedit_hip_cn_info(ctx, &st) != 0) {
+		fail("%s", ntedit_hip_last_error(ctx));
+	}
+	static const char* const STATES[] = { "off", "on", "over_cap", "no_memory" };
+	const char* state = st.state < 4 ? STATES[st.state] : "unknown";
+	if (rc == NTEDIT_E_OVERFLOW) {
+		fprintf(stderr, PROGRAM ": --cn: %s; no copy-number table is written (--cn_store BYTES raises the cap)\n", ntedit_hip_last_error(ctx));
+		if (report) {
+			printf("{\"cn\": {\"state\": \"%s\", \"store_cap\": %llu}}\n", state, (unsigned long long)st.cap);
+		}
+		return;
+	}
+	if (rc != 0) {
+		fail("%s", ntedit_hip_last_error(ctx));
+	}
+	std::vector<uint64_t> occ[2], w5[2], distinct[2];
+	std::vector<ntedit_hip_cn_row> rows[2];
+	for (int which = 0; which < 2; which++) {
+		occ[which].resize(5 * 256);
+		w5[which].resize(256);
+		distinct[which].resize(5 * 256);
+		rows[which].resize(names.size());
+		if (ntedit_hip_cn_table(ctx, which, occ[which].data(), w5[which].data()) != 0 ||
+		    ntedit_hip_cn_rows(ctx, which, rows[which].data(), names.size()) != 0 ||
+		    ntedit_hip_cn_distinct(occ[which].data(), w5[which].data(), distinct[which].data()) != 0) {
+			fail("%s", ntedit_hip_last_error(ctx));
+		}
+	}
+	char line[1024];
+	FILE* f = fopen(paths[0].c_str(), "wb");
+	bool ok = f != nullptr && fputs(ntedit_hip_cn_header(), f) >= 0;
+	for (uint32_t m = 0; ok && m < 256; m++) {
+		ok = ntedit_hip_cn_format_row(m, distinct[0].data(), distinct[1].data(), line, sizeof line) == 0 && fputs(line, f) >= 0;
+	}
+	if (f) {
+		ok = fclose(f) == 0 && ok;
+	}
+	if (!ok) {
+		fail("cannot write `%s'", paths[0].c_str());
+	}
+	f = fopen(paths[1].c_str(), "wb");
+	ok = f != nullptr && fputs(ntedit_hip_cn_contig_header(), f) >= 0;
+	ntedit_hip_cn_row total[2] = {};
+	std::string text;
+	for (size_t i = 0; ok && i <= names.size(); i++) {
+		const bool last = i == names.size();
+		for (int which = 0; which < 2 && !last; which++) {
+			total[which].kmers += rows[which][i].kmers;
+			total[which].cn1 += rows[which][i].cn1;
+			total[which].cn2 += rows[which][i].cn2;
+			total[which].cn3 += rows[which][i].cn3;
+			total[which].cn4 += rows[which][i].cn4;
+			total[which].cn5plus += rows[which][i].cn5plus;
+		}
+		const char* name = last ? "#total" : names[i].c_str();
+		text.resize(strlen(name) + 512);
+		ok = ntedit_hip_cn_contig_format_row(name, last ? &total[0] : &rows[0][i], last ? &total[1] : &rows[1][i], &text[0], text.size()) == 0 &&
+		     fputs(text.c_str(), f) >= 0;
+	}
+	if (f) {
+		ok = fclose(f) == 0 && ok;
+	}
+	if (!ok) {
+		fail("cannot write `%s'", paths[1].c_str());
+	}
+	// per side: the distinct k-mers, the single-copy share of them, the share of occurrences with cn >= 2, and the share of
+	// copy numbers a collision is expected to have inflated, (non-zero counters / counters)^h
+	unsigned long long n_distinct[2] = { 0, 0 }, single[2] = { 0, 0 }, n_occ[2] = { 0, 0 }, multi[2] = { 0, 0 };
+	double inflated[2];
+	uint32_t fk = 0, h = 1;
+	uint64_t fbytes = 0;
+	int fcounting = 0;
+	if (ntedit_hip_filter_info(ctx, 0, &fk, &h, &fbytes, &fcounting) != 0) {
+		fail("%s", ntedit_hip_last_error(ctx));
+	}
+	for (int which = 0; which < 2; which++) {
+		for (int c = 0; c < 5; c++) {
+			for (int m = 0; m < 256; m++) {
+				n_distinct[which] += distinct[which][c * 256 + m];
+				n_occ[which] += occ[which][c * 256 + m];
+				if (c == 0) {
+					single[which] += distinct[which][m];
+				} else {
+					multi[which] += occ[which][c * 256 + m];
+				}
+			}
+		}
+		inflated[which] = st.counters ? std::pow((double)st.nonzero[which] / (double)st.counters, (double)h) : std::nan("");
+	}
+	auto share = [](unsigned long long part, unsigned long long all) { return all ? (double)part / (double)all : std::nan(""); };
+	printf("k-mer copy numbers (k=%u): before %llu distinct k-mers, %s single-copy, %s of occurrences at copy number 2 or more; after %llu "
+	       "distinct k-mers, %s single-copy, %s of occurrences at copy number 2 or more; sketch %llu counters, expected inflated %s before, %s "
+	       "after; tables: %s, %s\n",
+	       k, n_distinct[0], percent_text(share(single[0], n_distinct[0])).c_str(), percent_text(share(multi[0], n_occ[0])).c_str(), n_distinct[1],
+	       percent_text(share(single[1], n_distinct[1])).c_str(), percent_text(share(multi[1], n_occ[1])).c_str(), (unsigned long long)st.counters,
+	       percent_text(inflated[0]).c_str(), percent_text(inflated[1]).c_str(), paths[0].c_str(), paths[1].c_str());
+	if (report) {
+		printf("{\"cn\": {\"state\": \"%s\", \"store_cap\": %llu, \"store_bytes_before\": %llu, \"store_bytes_after\": %llu, "
+		       "\"distinct_before\": %llu, \"single_copy_before\": %llu, \"occurrences_before\": %llu, \"multi_copy_occurrences_before\": %llu, "
+		       "\"distinct_after\": %llu, \"single_copy_after\": %llu, \"occurrences_after\": %llu, \"multi_copy_occurrences_after\": %llu, "
+		       "\"sketch_counters\": %llu, \"nonzero_before\": %llu, \"nonzero_after\": %llu, \"inflated_before\": %s, \"inflated_after\": %s, "
+		       "\"cn_count_before_ms\": %.3f, \"spectrum_cn_before_ms\": %.3f, \"cn_count_after_ms\": %.3f, \"spectrum_cn_after_ms\": %.3f}}\n",
+		       state, (unsigned long long)st.cap, (unsigned long long)st.bytes[0], (unsigned long long)st.bytes[1], n_distinct[0], single[0], n_occ[0],
+		       multi[0], n_distinct[1], single[1], n_occ[1], multi[1], (unsigned long long)st.counters, (unsigned long long)st.nonzero[0],
+		       (unsigned long long)st.nonzero[1], json_num(inflated[0], "%.6g").c_str(), json_num(inflated[1], "%.6g").c_str(), st.ms[0], st.ms[1],
+		       st.ms[2], st.ms[3]);
 	}
 }
 

@@ -6,6 +6,7 @@
 
 #include <cstdio>
 #include <string>
+#include <vector>
 
 namespace nte_cli {
 
@@ -52,6 +53,10 @@ void finish_bed(const RoundTotals& t, const std::string paths[2], bool report);
 // --spectrum: <prefix>_spectrum.tsv from the summed bins, the "#total" row and the depth table closed, the summary line;
 // with --report its JSON
 void finish_spectrum(const RoundTotals& t, FILE* depth_f, const std::string paths[2], uint32_t k, bool report);
+// --cn: ntedit_hip_cn_finish, <prefix>_spectrum_cn.tsv and <prefix>_cn_contigs.tsv under the names of the round's entries, the
+// summary line; with --report its JSON.  A released store: one line on standard error, no file
+void finish_cn(ntedit_hip_ctx* ctx, const std::vector<std::string>& names, const std::string paths[2], uint32_t k, unsigned long long sketch,
+               bool report);
 // --report
 void report_qv(const RoundTotals& t);
 void report_round(const RoundTotals& t);

@@ -10,7 +10,8 @@
 // With --qv --bed the results hold the unsupported regions before and after as intervals, and the writer stage appends
 // them to <prefix>_absent_before.bed and <prefix>_absent_after.bed.  With --spectrum they hold the k-mer spectrum before
 // and after and a depth row per contig: the writer stage sums the bins and appends the rows to <prefix>_depth.tsv,
-// <prefix>_spectrum.tsv is written at the round's end.
+// <prefix>_spectrum.tsv is written at the round's end.  With --spectrum --cn the library keeps the batches and their edited
+// entries in HBM; at the round's end they are counted once and <prefix>_spectrum_cn.tsv and <prefix>_cn_contigs.tsv written.
 #include "../../include/ntedit_hip.h"
 #include "cli_batches.h"
 #include "cli_common.h"
@@ -50,6 +51,7 @@ struct Round
 	FILE* bed_f[2] = { nullptr, nullptr }; // --bed: <prefix>_absent_before.bed, _absent_after.bed
 	std::string spectrum_path[2];          // --spectrum: <prefix>_spectrum.tsv, <prefix>_depth.tsv
 	FILE* depth_f = nullptr;
+	std::vector<std::string> cn_names; // --cn: the entries in the order the GPU stage polished them (= the store's rows)
 	int fa_fd = -1; // --bgzip: <prefix>_edited.fa.gz, open for the writer stage
 	ntedit_hip_annot* annot = nullptr;
 	Channel free_q, gpu_q, write_q;
@@ -162,6 +164,10 @@ prepare_device(Run& run, const CliOptions& opt, const ntedit_hip_params& p, bool
 		fail("%s", ntedit_hip_last_error(ctx));
 	}
 	if (opt.spectrum && ntedit_hip_set_spectrum(ctx, 1) != 0) {
+		fail("%s", ntedit_hip_last_error(ctx));
+	}
+	// --cn: the draft store begins empty in every round
+	if (opt.cn && ntedit_hip_set_cn(ctx, 1, opt.cn_store) != 0) {
 		fail("%s", ntedit_hip_last_error(ctx));
 	}
 	// --completeness: the two mark arrays of this round's filter, mapped here and not inside the first batch
@@ -596,6 +602,9 @@ polish_batches(Round& r)
 			fail("%s", ntedit_hip_last_error(r.ctx));
 		}
 		r.tot.s_call += clock.s();
+		if (r.opt.cn) {
+			r.cn_names.insert(r.cn_names.end(), b.names.begin(), b.names.end());
+		}
 		ntedit_hip_apply_stats as;
 		if (r.opt.qv && ntedit_hip_apply_info(r.ctx, &as) == 0) {
 			r.tot.ms_apply += as.ms_apply;
@@ -756,6 +765,10 @@ polish_round(Run& run, const CliOptions& opt, size_t round, const std::string& d
 	}
 	if (r.depth_f) {
 		finish_spectrum(r.tot, r.depth_f, r.spectrum_path, r.k, opt.report != 0);
+	}
+	if (opt.cn) {
+		const std::string cn_path[2] = { prefix + "_spectrum_cn.tsv", prefix + "_cn_contigs.tsv" };
+		finish_cn(ctx, r.cn_names, cn_path, r.k, opt.cn_sketch, opt.report != 0);
 	}
 	if (opt.report && opt.qv) {
 		report_qv(r.tot);

@@ -149,6 +149,81 @@ ntedit_hip_depth_format_row(const char* name, const ntedit_hip_depth_row* row, c
 	return 0;
 }
 
+// ---- the spectrum by copy number (the counts come from k_spectrum_cn through ntedit_hip_cn_table / _rows)
+
+// Distinct k-mers from occurrences, beside ntedit_hip_reads_hist_summary's rule f[e] = round(occ[e] / e): a k-mer of copy
+// number c occurs c times, so class c holds occ / c of them, rounded (exact without sketch collisions); class 5plus mixes
+// copy numbers, so the kernel summed 2^32 / cn per occurrence instead and the sum is rounded here.
+int
+ntedit_hip_cn_distinct(const uint64_t* occ, const uint64_t* w5, uint64_t* distinct)
+{
+	if (!occ || !w5 || !distinct) {
+		return NTEDIT_E_ARG;
+	}
+	for (uint64_t c = 1; c <= 4; c++) {
+		for (int m = 0; m < 256; m++) {
+			distinct[(c - 1) * 256 + m] = (occ[(c - 1) * 256 + m] + c / 2) / c;
+		}
+	}
+	for (int m = 0; m < 256; m++) {
+		distinct[4 * 256 + m] = (w5[m] + (1ull << 31)) >> 32;
+	}
+	return 0;
+}
+
+const char*
+ntedit_hip_cn_header(void)
+{
+	return "multiplicity\tbefore_cn1\tbefore_cn2\tbefore_cn3\tbefore_cn4\tbefore_cn5plus\tafter_cn1\tafter_cn2\tafter_cn3\tafter_cn4\tafter_cn5plus\n";
+}
+
+int
+ntedit_hip_cn_format_row(uint32_t multiplicity, const uint64_t* distinct_before, const uint64_t* distinct_after, char* out, uint64_t cap)
+{
+	if (!out || !distinct_before || !distinct_after || multiplicity > 255) {
+		return NTEDIT_E_ARG;
+	}
+	std::string s = std::to_string(multiplicity);
+	for (const uint64_t* d : { distinct_before, distinct_after }) {
+		for (int c = 0; c < 5; c++) {
+			s += '\t' + std::to_string(d[c * 256 + multiplicity]);
+		}
+	}
+	s += '\n';
+	if (s.size() + 1 > cap) {
+		return NTEDIT_E_OVERFLOW;
+	}
+	memcpy(out, s.c_str(), s.size() + 1);
+	return 0;
+}
+
+const char*
+ntedit_hip_cn_contig_header(void)
+{
+	return "name\tkmers_before\tbefore_cn1\tbefore_cn2\tbefore_cn3\tbefore_cn4\tbefore_cn5plus\tkmers_after\tafter_cn1\tafter_cn2\tafter_cn3\tafter_cn4\t"
+	       "after_cn5plus\n";
+}
+
+int
+ntedit_hip_cn_contig_format_row(const char* name, const ntedit_hip_cn_row* before, const ntedit_hip_cn_row* after, char* out, uint64_t cap)
+{
+	if (!name || !before || !after || !out) {
+		return NTEDIT_E_ARG;
+	}
+	std::string s(name, strcspn(name, " \t")); // (the sequence name as faidx understands it)
+	for (const ntedit_hip_cn_row* r : { before, after }) {
+		for (uint64_t v : { r->kmers, r->cn1, r->cn2, r->cn3, r->cn4, r->cn5plus }) {
+			s += '\t' + std::to_string(v);
+		}
+	}
+	s += '\n';
+	if (s.size() + 1 > cap) {
+		return NTEDIT_E_OVERFLOW;
+	}
+	memcpy(out, s.c_str(), s.size() + 1);
+	return 0;
+}
+
 // ---- k-mer completeness (linear counting: the marks come from k_mark through ntedit_hip_shared_counts)
 
 double

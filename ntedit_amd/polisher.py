@@ -541,6 +541,93 @@ class Polisher:
             f.write(buf.value)
         return total
 
+    # ---- the spectrum split by assembly copy number (nte_cn.hip)
+    def set_cn(self, on, store_cap_bytes=_lib.CN_STORE_DEFAULT):
+        """ntedit_hip_set_cn: the polish_batch calls that follow append the batch and its edited entries to the draft
+        store in HBM (at most store_cap_bytes of bases); cn_finish() then counts both sides"""
+        self._check(self._lib.ntedit_hip_set_cn(self._h, int(bool(on)), int(store_cap_bytes)), "set_cn")
+
+    def cn_append(self, which, blob, offs, lens, device_ptr=None, n=None):
+        """one batch -- host bytes, or n device bytes at device_ptr -- to side `which` (0 before, 1 after) of the store"""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None  # noqa: E731
+        if device_ptr is not None:
+            keep, bases, n, on_device = None, ctypes.c_void_p(device_ptr), int(n), 1
+        else:
+            keep, bases = Result._blob_ptr(blob)
+            n, on_device = len(blob), 0
+        rc = self._lib.ntedit_hip_cn_append(self._h, int(which), bases, n, on_device, ptr(offs), ptr(lens), len(offs))
+        del keep
+        self._check(rc, "cn_append")
+
+    def cn_finish(self, sketch_counters=0):
+        """ntedit_hip_cn_finish: both sides counted from the store; sketch_counters 0 picks the size"""
+        self._check(self._lib.ntedit_hip_cn_finish(self._h, int(sketch_counters)), "cn_finish")
+
+    def cn_table(self, which):
+        """(occ uint64[5][256], w5 uint64[256]) of one side: occurrences by class (copy number 1, 2, 3, 4, 5 or more) and
+        multiplicity, and the class-5 weights"""
+        occ = np.zeros((5, 256), dtype=np.uint64)
+        w5 = np.zeros(256, dtype=np.uint64)
+        rc = self._lib.ntedit_hip_cn_table(self._h, int(which), occ.ctypes.data_as(ctypes.c_void_p), w5.ctypes.data_as(ctypes.c_void_p))
+        self._check(rc, "cn_table")
+        return occ, w5
+
+    def cn_rows(self, which, n):
+        """one record per entry of side `which` in the order appended (dtype _lib.CN_ROW_DTYPE)"""
+        rows = np.zeros(max(n, 1), dtype=np.dtype(_lib.CN_ROW_DTYPE))
+        self._check(self._lib.ntedit_hip_cn_rows(self._h, int(which), rows.ctypes.data_as(ctypes.c_void_p), int(n)), "cn_rows")
+        return rows[:n]
+
+    def cn_distinct(self, occ, w5):
+        """uint64[5][256] distinct k-mers from a side's table (host only)"""
+        occ = np.ascontiguousarray(occ, dtype=np.uint64)
+        w5 = np.ascontiguousarray(w5, dtype=np.uint64)
+        out = np.zeros((5, 256), dtype=np.uint64)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        if self._lib.ntedit_hip_cn_distinct(ptr(occ), ptr(w5), ptr(out)):
+            raise NtEditHipError("cn_distinct: bad argument")
+        return out
+
+    def cn_info(self):
+        """ntedit_hip_cn_info: _lib.CnStats"""
+        st = _lib.CnStats()
+        self._check(self._lib.ntedit_hip_cn_info(self._h, ctypes.byref(st)), "cn_info")
+        return st
+
+    def cn_reset(self):
+        self._check(self._lib.ntedit_hip_cn_reset(self._h), "cn_reset")
+
+    def cn_free(self):
+        self._check(self._lib.ntedit_hip_cn_free(self._h), "cn_free")
+
+    def write_cn_tables(self, out_prefix, names, distinct_before, distinct_after, rows_before, rows_after):
+        """<prefix>_spectrum_cn.tsv (the header, 256 rows of distinct k-mers) and <prefix>_cn_contigs.tsv (the header, one
+        row per entry, "#total"), through the library's formatters; returns the two total rows"""
+        buf = ctypes.create_string_buffer(1 << 16)
+        d0 = np.ascontiguousarray(distinct_before, dtype=np.uint64)
+        d1 = np.ascontiguousarray(distinct_after, dtype=np.uint64)
+        with open(out_prefix + "_spectrum_cn.tsv", "wb") as f:
+            f.write(self._lib.ntedit_hip_cn_header())
+            for m in range(256):
+                self._lib.ntedit_hip_cn_format_row(m, d0.ctypes.data_as(ctypes.c_void_p), d1.ctypes.data_as(ctypes.c_void_p), buf, len(buf))
+                f.write(buf.value)
+        total = _lib.CnRow(), _lib.CnRow()
+        with open(out_prefix + "_cn_contigs.tsv", "wb") as f:
+            f.write(self._lib.ntedit_hip_cn_contig_header())
+            for name, rb, ra in zip(names, rows_before, rows_after):
+                pair = [_lib.CnRow(*[int(r[fld]) for fld, _ in _lib.CnRow._fields_]) for r in (rb, ra)]
+                for t, row in zip(total, pair):
+                    for fld, _ in _lib.CnRow._fields_:
+                        setattr(t, fld, getattr(t, fld) + getattr(row, fld))
+                if self._lib.ntedit_hip_cn_contig_format_row(bytes(name), ctypes.byref(pair[0]), ctypes.byref(pair[1]), buf, len(buf)):
+                    raise NtEditHipError("cn row of %r does not fit" % name)
+                f.write(buf.value)
+            self._lib.ntedit_hip_cn_contig_format_row(b"#total", ctypes.byref(total[0]), ctypes.byref(total[1]), buf, len(buf))
+            f.write(buf.value)
+        return total
+
     # ---- k-mer completeness: the draft's distinct k-mers that the PRIMARY filter holds (DESIGN.md 9.10)
     def shared_begin(self):
         """allocate and zero the two mark arrays (before, after) for the current PRIMARY filter; idempotent"""

@@ -264,6 +264,7 @@ def parse(argv=None):
     ap.add_argument("--bgzip", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     ap.add_argument("--bed", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     ap.add_argument("--spectrum", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
+    ap.add_argument("--cn", action="store_true", help=argparse.SUPPRESS)  # (refused: see parse())
     g = ap.add_argument_group("polishing straight from reads (--reads replaces -r; the options of `ntedit --reads`, "
                               "the same filter; every rank builds its share and holds the whole filter)")
     g.add_argument("--reads", nargs="*", metavar="FILE", help="input reads, FASTA or FASTQ, plain or gzip")
@@ -316,6 +317,9 @@ def parse(argv=None):
     if args.spectrum:
         raise Refused("--spectrum: the spectra and depth rows of cut contigs on several GPUs would need a merge of their own, "
                       "which is out of scope; run `ntedit --spectrum` on one GPU")
+    if args.cn:
+        raise Refused("--cn: copy numbers belong to the whole draft, and the rows of cut contigs on several GPUs would need a "
+                      "merge of their own, which is out of scope; run `ntedit --spectrum --cn` on one GPU")
     return args
 
 
