@@ -11,6 +11,7 @@
 #include "nte_cn.h"
 
 #include "../../include/ntedit_hip.h"
+#include "../host/batch_layout.h"
 #include "../host/bfio.h"
 #include "../host/params.h"
 #include "../host/render.h"
@@ -72,6 +73,12 @@ struct PinBuf
 {
 	void* p = nullptr;
 	size_t cap = 0;
+};
+
+// the two HIP events around a timed piece of work on one stream (ensure_events creates them on first use)
+struct EventPair
+{
+	hipEvent_t begin = nullptr, end = nullptr;
 };
 
 struct ntedit_hip_ctx
@@ -151,7 +158,9 @@ struct ntedit_hip_ctx
 	// the device applier and the QV counts (nte_apply.hip): ntedit_hip_set_apply()
 	u32 apply_flags = 0;
 	DevBuf ap_ev, ap_place, ap_range, ap_contig, ap_tabs, ap_pieces, ap_edited, ap_bitmap, ap_rows;
-	hipEvent_t ap_evt[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+	// the apply stage's windows (nte_api_apply.inc; ntedit_hip_apply_info): the applier, and per side of the draft (0 the batch,
+	// 1 the edited bases) the plain screening and the QV count
+	EventPair ap_window[1], ap_screen[2], ap_count[2];
 	ntedit_hip_apply_stats apply_last = { 0.f, 0.f, 0.f, 0, 0, 0 };
 	// the BGZF writer (nte_bgzf_deflate.hip): the header lines of the next polish call, the last call's figures
 	std::vector<std::string> fa_names;
@@ -279,6 +288,72 @@ ensure(ntedit_hip_ctx* c, DevBuf& b, size_t bytes)
 		fprintf(stderr, "[ntedit_hip] device buffer of %.1f MB: %.2f ms of hipFree + hipMalloc\n", want / 1e6, ms);
 	}
 	return 0;
+}
+
+// the events of a fixed array that do not exist yet (the arrays of the reports are filled by the first call that times one)
+int
+ensure_event(ntedit_hip_ctx* c, hipEvent_t& e)
+{
+	if (!e) {
+		HIP_TRY(c, hipEventCreate(&e));
+	}
+	return 0;
+}
+
+int
+ensure_event(ntedit_hip_ctx* c, EventPair& p)
+{
+	int rc = ensure_event(c, p.begin);
+	return rc ? rc : ensure_event(c, p.end);
+}
+
+template<class E, size_t N>
+int
+ensure_events(ntedit_hip_ctx* c, E (&evs)[N])
+{
+	for (E& e : evs) {
+		int rc = ensure_event(c, e);
+		if (rc) {
+			return rc;
+		}
+	}
+	return 0;
+}
+
+// a list that grows with the batch (two events per pipeline chunk): at least `count` events
+int
+ensure_events(ntedit_hip_ctx* c, std::vector<hipEvent_t>& evs, size_t count)
+{
+	while (evs.size() < count) {
+		hipEvent_t e;
+		HIP_TRY(c, hipEventCreate(&e));
+		evs.push_back(e);
+	}
+	return 0;
+}
+
+void
+destroy_event(hipEvent_t e)
+{
+	if (e) {
+		(void)hipEventDestroy(e);
+	}
+}
+
+void
+destroy_event(const EventPair& p)
+{
+	destroy_event(p.begin);
+	destroy_event(p.end);
+}
+
+template<class E, size_t N>
+void
+destroy_events(E (&evs)[N])
+{
+	for (E& e : evs) {
+		destroy_event(e);
+	}
 }
 
 int
@@ -466,4 +541,5 @@ refresh_params(ntedit_hip_ctx* c)
 
 #include "nte_api_filters.inc"
 #include "nte_api_polish.inc"
+#include "nte_api_apply.inc"
 #include "nte_api_results.inc"

@@ -114,41 +114,15 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 	if (c->d_tab) {
 		(void)hipFree(c->d_tab);
 	}
-	for (auto& e : c->ev) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
-	for (auto& e : c->ev_assess) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
-	for (auto& e : c->ev_settle) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
-	for (auto& e : c->ap_evt) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
-	for (auto& e : c->sh_evt) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
-	for (auto& e : c->tr_evt) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
-	for (auto& e : c->sp_evt) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
+	destroy_events(c->ev);
+	destroy_events(c->ev_assess);
+	destroy_events(c->ev_settle);
+	destroy_events(c->ap_window);
+	destroy_events(c->ap_screen);
+	destroy_events(c->ap_count);
+	destroy_events(c->sh_evt);
+	destroy_events(c->tr_evt);
+	destroy_events(c->sp_evt);
 	cn_free(c->cn);
 	for (auto& e : c->chunk_ev) {
 		(void)hipEventDestroy(e);
@@ -538,22 +512,10 @@ ntedit_hip_screen(ntedit_hip_ctx* c, const char* bases, uint64_t n, int on_devic
 		}
 		d_bitmap = (u64*)c->bitmap.p;
 	}
-	{
-		if ((rc = bin_reset(c, c->stream))) {
-			return rc;
-		}
-		HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
-		rc = launch_screen<false>(c, d_seq, n, dev_filter(c->filt[0]), d_bitmap, n_words);
-		if (rc) {
-			return rc;
-		}
-		HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
-		u32 recovered = 0;
-		if ((rc = bin_recover(c, c->stream, d_seq, n, dev_filter(c->filt[0]), d_bitmap, n_words, 0, n, &recovered))) {
-			return rc;
-		}
-		HIP_TRY(c, hipStreamSynchronize(c->stream));
+	if ((rc = screen_whole(c, d_seq, n, dev_filter(c->filt[0]), d_bitmap, n_words, c->ev[0], c->ev[1]))) {
+		return rc;
 	}
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	if (!on_device) {
 		HIP_TRY(c, hipMemcpy(bitmap, d_bitmap, n_words * 8, hipMemcpyDeviceToHost));
 	}

@@ -1,5 +1,5 @@
 // nte_api_polish.inc -- part of nte_api.hip: ntedit_hip_polish_batch in stages (plan, screening, run map, event rounds,
-// collection of the edit records, resolution of parked events).
+// collection of the edit records, resolution of parked events, the hand-off to the apply stage), and ntedit_hip_reserve.
 // ---- ntedit_hip_polish_batch, in stages --------------------------------------------------------------------
 // plan()              chunk plan (whole contigs per pipeline chunk), staging of the batch, grow-only buffers
 // launch_screening()  stream A: step 1 for every k-mer of the batch (direct or binned; H2D pieces underneath)
@@ -7,6 +7,8 @@
 // collect()           edit records to page-locked host memory; events parked by the budget are resolved in serial
 //                     order and re-run (host/resolve.h)
 // finish()            timings
+// apply()             returns at once unless a report is on; else hands the batch to the apply stage (nte_api_apply.inc: the
+//                     device applier, the reports behind it, the interval extractor's host side, the BGZF hand-off)
 namespace {
 
 // k_settle runs on lists of at least this many events.  It costs a launch, a stream synchronisation and the read-back of
@@ -105,8 +107,22 @@ struct PolishRun
 	int collect(bool* redo);
 	int finish();
 	int apply();
-	int bgzf(const u8* d_edited);
 };
+
+// what the apply stage (nte_api_apply.inc) reads from the polish of a batch
+struct ApplyInput
+{
+	ntedit_hip_ctx* c;
+	ntedit_hip_result* r;
+	const u8* d_seq; // the batch in HBM: n bytes, n_words bitmap words, n_contigs entries (c->offs, c->lens)
+	u64 n, n_words;
+	u32 n_contigs;
+	const u64* d_bitmap; // step 1's answer
+	Filter f0;
+	u64 n_events; // the events of the batch (c->arena, c->first_chunk; r->arena_items)
+	const std::vector<std::string>* fa_names; // NTEDIT_HIP_APPLY_BGZF: the entries' header lines
+};
+int apply_stage(const ApplyInput& in);
 
 int
 PolishRun::plan()
@@ -183,10 +199,8 @@ PolishRun::plan()
 	}
 	n_ch = chunks.size();
 	pipelined = n_ch > 1;
-	while (c->chunk_ev.size() < 2 * n_ch) {
-		hipEvent_t e;
-		HIP_TRY(c, hipEventCreate(&e));
-		c->chunk_ev.push_back(e);
+	if ((rc = ensure_events(c, c->chunk_ev, 2 * n_ch))) {
+		return rc;
 	}
 	grid = c->dp.start_grid;
 	grid_lo = 0;
@@ -1060,386 +1074,19 @@ PolishRun::finish()
 	return 0;
 }
 
-// The interval extractor (nte_track.hip) over a bitmap and the entries of its batch, all in device memory, on stream s:
-// count and scan, three words to the host, the record buffer sized from them, emit and finish, the records to host memory
-// (malloc, *out; null for none).  The stream is idle when it returns.  Crosses PCIe: four words and the records.
-int
-track_run(ntedit_hip_ctx* c, hipStream_t s, const u64* d_bitmap, u64 n, const u64* d_offs, const u32* d_lens, u32 n_entries, u32 k, int which,
-          ntedit_hip_track_interval** out, u64* n_out)
-{
-	int rc;
-	free(*out);
-	*out = nullptr;
-	*n_out = 0;
-	c->track_last.ms[which] = 0.f;
-	c->track_last.intervals[which] = c->track_last.bases[which] = 0;
-	const u64 n_tiles = track_tiles(n);
-	if (n_tiles == 0 || n_entries == 0) {
-		return 0;
-	}
-	if (n_tiles > 0x7FFFFFFFull) {
-		return fail(c, NTEDIT_E_ARG, "track: batch too large");
-	}
-	for (auto& e : c->tr_evt) {
-		if (!e) {
-			HIP_TRY(c, hipEventCreate(&e));
-		}
-	}
-	if ((rc = ensure(c, c->tr_tiles, (size_t)n_tiles * sizeof(TrackTile))) || (rc = ensure(c, c->tr_totals, 64))) {
-		return rc;
-	}
-	const TrackArgs a = { d_bitmap, n, d_offs, d_lens, n_entries, k };
-	TrackTile* tiles = (TrackTile*)c->tr_tiles.p;
-	u64* totals = (u64*)c->tr_totals.p;
-	u64 h_tot[4] = { 0, 0, 0, 0 };
-	HIP_TRY(c, hipEventRecord(c->tr_evt[0], s));
-	launch_track_count(s, a, tiles, totals);
-	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipEventRecord(c->tr_evt[1], s));
-	HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 32, hipMemcpyDeviceToHost, s));
-	HIP_TRY(c, hipStreamSynchronize(s));
-	if (h_tot[0] != h_tot[1] || h_tot[0] > h_tot[2]) {
-		return fail(c, NTEDIT_E_INTERNAL, "track: %llu interval starts, %llu ends, %llu marked starts", (unsigned long long)h_tot[0],
-		            (unsigned long long)h_tot[1], (unsigned long long)h_tot[2]);
-	}
-	float t0 = 0.f, t1 = 0.f;
-	(void)hipEventElapsedTime(&t0, c->tr_evt[0], c->tr_evt[1]);
-	const u64 n_recs = h_tot[0];
-	if (n_recs) {
-		if ((rc = ensure(c, c->tr_recs, (size_t)n_recs * sizeof(TrackInterval))) || (rc = ensure(c, c->tr_upto, (size_t)n_recs * 4))) {
-			return rc;
-		}
-		ntedit_hip_track_interval* host = (ntedit_hip_track_interval*)malloc((size_t)n_recs * sizeof(ntedit_hip_track_interval));
-		if (!host) {
-			return fail(c, NTEDIT_E_OVERFLOW, "track: no host memory for %llu intervals", (unsigned long long)n_recs);
-		}
-		hipError_t he = hipEventRecord(c->tr_evt[2], s);
-		launch_track_emit(s, a, tiles, (TrackInterval*)c->tr_recs.p, (u32*)c->tr_upto.p, n_recs, totals);
-		if (he == hipSuccess) {
-			he = hipGetLastError();
-		}
-		if (he == hipSuccess) {
-			he = hipEventRecord(c->tr_evt[3], s);
-		}
-		if (he == hipSuccess) {
-			he = hipMemcpyAsync(host, c->tr_recs.p, (size_t)n_recs * sizeof(TrackInterval), hipMemcpyDeviceToHost, s);
-		}
-		if (he == hipSuccess) {
-			he = hipMemcpyAsync(h_tot, totals, 32, hipMemcpyDeviceToHost, s);
-		}
-		if (he == hipSuccess) {
-			he = hipStreamSynchronize(s);
-		}
-		if (he != hipSuccess) {
-			free(host);
-			return fail(c, NTEDIT_E_DEVICE, "track: %s", hipGetErrorString(he));
-		}
-		(void)hipEventElapsedTime(&t1, c->tr_evt[2], c->tr_evt[3]);
-		*out = host;
-		*n_out = n_recs;
-	}
-	c->track_last.ms[which] = t0 + t1;
-	c->track_last.intervals[which] = n_recs;
-	c->track_last.bases[which] = h_tot[3];
-	return 0;
-}
-
-// The device applier and the QV counts (nte_apply.hip), behind everything a plain call does: the streams are idle, the
-// arena and the first-chunk table in HBM are what collect() copied (the re-runs of parked events write both on the
-// device), c->bitmap still holds step 1's answer (k_assess writes a map of its own, c->runmap).  Crosses PCIe: five
-// words of totals, the entries' offsets and lengths, the QV rows.
+// The apply stage (nte_api_apply.inc), behind everything a plain call does: the streams are idle, the arena and the first-chunk
+// table in HBM are what collect() copied (the re-runs of parked events write both on the device), c->bitmap still holds step
+// 1's answer (k_assess writes a map of its own, c->runmap).  With no flag, no spectrum and no store on, nothing of it runs.
 int
 PolishRun::apply()
 {
-	const u32 flags = c->apply_flags;
-	r->apply_flags = flags;
+	r->apply_flags = c->apply_flags;
 	r->device = c->device;
-	const bool spectrum = c->spectrum_on;
-	const bool cn = c->cn.state != CN_OFF;
-	if (!flags && !spectrum && !cn) {
+	if (!c->apply_flags && !c->spectrum_on && c->cn.state == CN_OFF) {
 		return 0;
 	}
-	int rc;
-	hipStream_t s = c->stream;
-	const u32 k = c->dp.k;
-	if ((flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) && k > QV_MAX_K) {
-		return fail(c, NTEDIT_E_UNSUPPORTED, "apply: the QV counts take k up to %u", QV_MAX_K);
-	}
-	const bool shared = (flags & NTEDIT_HIP_APPLY_SHARED) != 0;
-	const bool track = (flags & NTEDIT_HIP_APPLY_TRACK) != 0;
-	if (track) {
-		c->track_last = ntedit_hip_track_stats{ { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
-	}
-	if (shared && (rc = shared_begin(c, "polish_batch"))) { // (the completeness marks: begun here if that was not done)
-		return rc;
-	}
-	for (auto& e : c->ap_evt) {
-		if (!e) {
-			HIP_TRY(c, hipEventCreate(&e));
-		}
-	}
-	const u64 n_ev = ev_total;
-	const size_t nc = n_contigs;
-	// ap_tabs: out_offs u64[nc] | piece_base u64[nc + 1] | totals u64[3] | status (8 bytes) | out_lens u32[nc]
-	const size_t tabs_bytes = nc * 8 + (nc + 1) * 8 + 32 + nc * 4;
-	if ((rc = ensure(c, c->ap_ev, (size_t)(n_ev + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, c->ap_place, (size_t)(n_ev + 1) * sizeof(ApplyPlace))) ||
-	    (rc = ensure(c, c->ap_range, nc * 8)) || (rc = ensure(c, c->ap_contig, nc * sizeof(ApplyContig))) || (rc = ensure(c, c->ap_tabs, tabs_bytes))) {
-		return rc;
-	}
-	ApplyArgs a;
-	memset(&a, 0, sizeof a);
-	a.seq = d_seq;
-	a.n_seq = n;
-	a.offs = (const u64*)c->offs.p;
-	a.lens = (const u32*)c->lens.p;
-	a.n_contigs = n_contigs;
-	a.arena = (const Item*)c->arena.p;
-	a.arena_items = r->arena_items;
-	a.ev_first = (const u32*)c->first_chunk.p;
-	a.n_events = (u32)n_ev;
-	a.ev = (ApplyEvent*)c->ap_ev.p;
-	a.place = (ApplyPlace*)c->ap_place.p;
-	a.ev_begin = (u32*)c->ap_range.p;
-	a.ev_end = a.ev_begin + nc;
-	a.contig = (ApplyContig*)c->ap_contig.p;
-	a.out_offs = (u64*)c->ap_tabs.p;
-	a.piece_base = a.out_offs + nc;
-	a.totals = a.piece_base + nc + 1;
-	a.status = (u32*)(a.totals + 3);
-	a.out_lens = (u32*)(a.totals + 4);
-	HIP_TRY(c, hipMemsetAsync(a.place, 0, (size_t)(n_ev + 1) * sizeof(ApplyPlace), s));
-	HIP_TRY(c, hipMemsetAsync(a.ev_begin, 0xFF, nc * 4, s));
-	HIP_TRY(c, hipMemsetAsync(a.ev_end, 0, nc * 4, s));
-	HIP_TRY(c, hipMemsetAsync(a.totals, 0, 32, s));
-	HIP_TRY(c, hipEventRecord(c->ap_evt[0], s));
-	launch_apply_plan(s, a);
-	HIP_TRY(c, hipGetLastError());
-	u64 h_tot[4] = { 0, 0, 0, 0 };
-	HIP_TRY(c, hipMemcpyAsync(h_tot, a.totals, 32, hipMemcpyDeviceToHost, s));
-	HIP_TRY(c, hipStreamSynchronize(s));
-	const u32 st = (u32)h_tot[3];
-	if (st) {
-		const int code = (st & AP_BAD_INDEX) ? -1 : (st & AP_BAD_ORDER) ? -2 : (st & AP_BAD_COUNT) ? -3 : (st & AP_BAD_ITEM) ? -4 : (st & AP_UNFINISHED) ? -6 : 0;
-		if (!code) {
-			return fail(c, NTEDIT_E_OVERFLOW, "apply: an edited contig of 4 GiB or more");
-		}
-		return fail(c, NTEDIT_E_INTERNAL, "apply: malformed event records (the renderer's code %d)", code);
-	}
-	const u64 total_bytes = h_tot[0], total_pieces = h_tot[1];
-	DevBuf eb;
-	{
-		std::lock_guard<std::mutex> lk(c->pin_mu); // (a result that is freed hands its buffer back from another thread)
-		eb = c->ap_edited;
-		c->ap_edited = DevBuf();
-	}
-	rc = ensure(c, eb, (size_t)((total_bytes + 15) / 16 * 16 + 64));
-	if (!rc) {
-		rc = ensure(c, c->ap_pieces, (size_t)(total_pieces + 1) * sizeof(ApplyPiece));
-	}
-	if (rc) {
-		release(eb);
-		return rc;
-	}
-	a.pieces = (ApplyPiece*)c->ap_pieces.p;
-	a.out = (u8*)eb.p;
-	launch_apply_write(s, a, total_bytes, total_pieces);
-	hipError_t he = hipGetLastError();
-	if (he == hipSuccess) {
-		he = hipEventRecord(c->ap_evt[1], s);
-	}
-	r->e_offs.resize(nc);
-	r->e_lens.resize(nc);
-	if (he == hipSuccess) {
-		he = hipMemcpyAsync(r->e_offs.data(), a.out_offs, nc * 8, hipMemcpyDeviceToHost, s);
-	}
-	if (he == hipSuccess) {
-		he = hipMemcpyAsync(r->e_lens.data(), a.out_lens, nc * 4, hipMemcpyDeviceToHost, s);
-	}
-	// (APPLY_SHARED runs everything APPLY_QV runs and marks the present k-mers of both screenings: k_mark; APPLY_TRACK
-	// runs it too and extracts the intervals of both bitmaps: nte_track.hip)
-	bool qv = (flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) != 0;
-	int qrc = 0;
-	float ms_rescreen = 0.f;
-	if (he == hipSuccess && qv) {
-		// before: the batch and step 1's bitmap; after: the edited bases, screened the way a batch of that size is.  With
-		// -s 1 step 1 marks every k-mer of accepted bases (k_screen: "no probe decides that"), so c->bitmap is not the plain
-		// answer: both screenings then run with the flag down, the batch's into the second bitmap first.
-		PlainScreen plain(c);
-		const bool rescreen = plain.dp_snv != 0;
-		const u64 nw2 = (total_bytes + 63) / 64;
-		const u64 nw_max = rescreen && n_words > nw2 ? n_words : nw2;
-		if ((qrc = ensure(c, c->ap_rows, nc * sizeof(QvRow))) == 0 && (qrc = ensure(c, c->ap_bitmap, (size_t)(nw_max + 8) * 8)) == 0 &&
-		    (qrc = bin_reset(c, s)) == 0) {
-			QvRow* rows = (QvRow*)c->ap_rows.p;
-			u64* bm2 = (u64*)c->ap_bitmap.p;
-			u32 recovered = 0;
-			const u64* bm_before = d_bitmap;
-			if (rescreen) {
-				(void)hipEventRecord(c->ap_evt[4], s);
-				qrc = launch_screen<false>(c, d_seq, n, f0, bm2, n_words);
-				(void)hipEventRecord(c->ap_evt[5], s);
-				if (!qrc) {
-					qrc = bin_recover(c, s, d_seq, n, f0, bm2, n_words, 0, n, &recovered);
-				}
-				if (!qrc && hipStreamSynchronize(s) == hipSuccess) {
-					(void)hipEventElapsedTime(&ms_rescreen, c->ap_evt[4], c->ap_evt[5]);
-				}
-				bm_before = bm2;
-			}
-			if (!qrc) {
-				(void)hipEventRecord(c->ap_evt[2], s);
-				launch_qv_rows(s, rows, a.lens, a.out_lens, n_contigs);
-				launch_qv_count(s, d_seq, n, a.offs, a.lens, n_contigs, bm_before, k, rows, 0);
-				(void)hipEventRecord(c->ap_evt[3], s);
-				// (with -s 1 bm_before is bm2, which the screening below overwrites: the before-extraction and the before-mark
-				// are queued here)
-				qrc = track ? track_run(c, s, bm_before, n, a.offs, a.lens, n_contigs, k, 0, &r->track[0], &r->track_n[0]) : 0;
-				if (!qrc) {
-					qrc = shared ? launch_mark(c, s, d_seq, n, f0, bm_before, n_words, 0) : 0;
-				}
-			}
-			if (!qrc) {
-				qrc = rescreen ? bin_reset(c, s) : 0;
-			}
-			if (!qrc) {
-				(void)hipEventRecord(c->ap_evt[4], s);
-				qrc = launch_screen<false>(c, a.out, total_bytes, f0, bm2, nw2);
-				(void)hipEventRecord(c->ap_evt[5], s);
-			}
-			if (!qrc) {
-				qrc = bin_recover(c, s, a.out, total_bytes, f0, bm2, nw2, 0, total_bytes, &recovered);
-			}
-			if (!qrc) {
-				(void)hipEventRecord(c->ap_evt[6], s);
-				launch_qv_count(s, a.out, total_bytes, a.out_offs, a.out_lens, n_contigs, bm2, k, rows, 1);
-				(void)hipEventRecord(c->ap_evt[7], s);
-				r->qv.resize(nc);
-				he = hipMemcpyAsync(r->qv.data(), rows, nc * sizeof(QvRow), hipMemcpyDeviceToHost, s);
-				if (shared && he == hipSuccess) {
-					qrc = launch_mark(c, s, a.out, total_bytes, f0, bm2, nw2, 1);
-				}
-				if (track && he == hipSuccess && !qrc) {
-					qrc = track_run(c, s, bm2, total_bytes, a.out_offs, a.out_lens, n_contigs, k, 1, &r->track[1], &r->track_n[1]);
-				}
-			}
-		}
-	}
-	// The k-mer spectrum (ntedit_hip_set_spectrum; k_spectrum): the counters under the batch's k-mers and under those of the
-	// edited bases, behind the applier and whatever the QV counts queued.  No bitmap is read: -s 1 changes nothing here.
-	std::vector<uint64_t> sp_host;
-	if (he == hipSuccess && !qrc && spectrum) {
-		sp_host.resize(2 * (size_t)SPECTRUM_BINS + 2 * nc * 3);
-		if ((qrc = spectrum_begin(c, s, n_contigs)) == 0 &&
-		    (qrc = launch_spectrum(c, s, d_seq, n, f0, a.offs, a.lens, n_contigs, 0, true)) == 0 &&
-		    (qrc = launch_spectrum(c, s, a.out, total_bytes, f0, a.out_offs, a.out_lens, n_contigs, 1, true)) == 0) {
-			he = hipMemcpyAsync(sp_host.data(), c->sp_buf.p, sp_host.size() * 8, hipMemcpyDeviceToHost, s);
-		}
-	}
-	// The spectrum by copy number (ntedit_hip_set_cn; nte_cn.hip): both sides go into the draft store, device to device;
-	// nothing is counted before ntedit_hip_cn_finish.  A store that passes its cap releases itself and fails nothing.
-	if (he == hipSuccess && !qrc && cn) {
-		std::string why;
-		if ((qrc = cn_append(c->cn, 0, s, d_seq, n, a.offs, a.lens, n_contigs, &why)) == 0) {
-			qrc = cn_append(c->cn, 1, s, a.out, total_bytes, a.out_offs, a.out_lens, n_contigs, &why);
-		}
-		if (qrc) {
-			qrc = fail(c, qrc, "apply: %s", why.c_str());
-		}
-	}
-	if (he == hipSuccess) {
-		he = hipStreamSynchronize(s);
-	}
-	if (he == hipSuccess) {
-		he = hipGetLastError();
-	}
-	if (he != hipSuccess || qrc) {
-		(void)hipDeviceSynchronize();
-		release(eb);
-		r->qv.clear();
-		return qrc ? qrc : fail(c, NTEDIT_E_DEVICE, "apply: %s", hipGetErrorString(he));
-	}
-	if (spectrum) {
-		r->sp_bins.assign(sp_host.begin(), sp_host.begin() + 2 * SPECTRUM_BINS);
-		r->depth.resize(nc);
-		const uint64_t* rows0 = sp_host.data() + 2 * SPECTRUM_BINS;
-		const uint64_t* rows1 = rows0 + nc * 3;
-		for (size_t i = 0; i < nc; i++) {
-			r->depth[i] = { rows0[3 * i], rows0[3 * i + 1], rows0[3 * i + 2], rows1[3 * i], rows1[3 * i + 1], rows1[3 * i + 2] };
-		}
-		spectrum_timed(c, 0, r->sp_bins.data());
-		spectrum_timed(c, 1, r->sp_bins.data() + SPECTRUM_BINS);
-		r->spectrum = true;
-	}
-	ntedit_hip_apply_stats as = { 0.f, 0.f, 0.f, total_pieces, total_bytes, h_tot[2] };
-	(void)hipEventElapsedTime(&as.ms_apply, c->ap_evt[0], c->ap_evt[1]);
-	if (qv) {
-		float t0 = 0.f, t1 = 0.f;
-		(void)hipEventElapsedTime(&as.ms_screen, c->ap_evt[4], c->ap_evt[5]);
-		as.ms_screen += ms_rescreen;
-		(void)hipEventElapsedTime(&t0, c->ap_evt[2], c->ap_evt[3]);
-		(void)hipEventElapsedTime(&t1, c->ap_evt[6], c->ap_evt[7]);
-		as.ms_count = t0 + t1;
-	}
-	if (shared) {
-		mark_timed(c, 0);
-		mark_timed(c, 1);
-	}
-	c->apply_last = as;
-	r->edited_bytes = total_bytes;
-	if ((flags & NTEDIT_HIP_APPLY_BGZF) && (rc = bgzf(a.out))) {
-		release(eb);
-		r->qv.clear();
-		return rc;
-	}
-	if (flags & NTEDIT_HIP_APPLY_EDITED) {
-		r->edited = eb; // the result's own until ntedit_hip_result_free()
-	} else {
-		std::lock_guard<std::mutex> lk(c->pin_mu);
-		if (c->ap_edited.p) {
-			release(eb);
-		} else {
-			c->ap_edited = eb;
-		}
-	}
-	return 0;
-}
-
-// The BGZF writer (nte_bgzf_deflate.hip) behind the applier, on its stream: the batch's _edited.fa text laid out in HBM from
-// the edited bases and the header lines, compressed block by block, the members packed and copied into page-locked memory
-// of the result's.  Crosses PCIe: the image's tables and the names down, two words of totals and the members up.
-int
-PolishRun::bgzf(const u8* d_edited)
-{
-	std::vector<u64> name_offs(n_contigs + 1, 0);
-	std::string blob;
-	for (u32 i = 0; i < n_contigs; i++) {
-		blob += (*fa_names)[i];
-		name_offs[i + 1] = blob.size();
-	}
-	const FaImage im = { d_edited, r->e_offs.data(), r->e_lens.data(), n_contigs, blob.data(), name_offs.data() };
-	const u8* d_image = nullptr;
-	u64 n_image = 0;
-	BgzfTotals t;
-	std::string why;
-	int rc = bgzf_image(c, c->device, c->stream, im, &d_image, &n_image, &t.ms_image, &why);
-	if (!rc) {
-		rc = bgzf_encode(c, c->device, c->stream, d_image, n_image, &t, &why);
-	}
-	if (!rc && (rc = bgzf_pin_take(c, (size_t)t.bytes + 16, &r->bgzf_buf))) {
-		return rc;
-	}
-	if (!rc) {
-		rc = bgzf_fetch(c, c->stream, r->bgzf_buf.p, t.bytes, &t.ms_copy, &why);
-	}
-	if (rc) {
-		bgzf_pin_give(c, r->bgzf_buf);
-		return fail(c, rc, "apply: %s", why.c_str());
-	}
-	r->bgzf_bytes = t.bytes;
-	r->bgzf_plain = t.plain;
-	r->bgzf_members = t.members;
-	c->bgzf_last = { t.ms_image, t.ms_deflate, t.ms_copy, t.plain, t.bytes, t.members, t.stored };
-	return 0;
+	const ApplyInput in = { c, r, d_seq, n, n_words, n_contigs, d_bitmap, f0, ev_total, fa_names };
+	return apply_stage(in);
 }
 
 } // namespace
@@ -1474,10 +1121,8 @@ ntedit_hip_polish_batch(
 		return fail(c, NTEDIT_E_ARG, "polish_batch: APPLY_BGZF needs the header line of every entry (ntedit_hip_set_fa_names): %u entries, %s",
 		            n_contigs, c->fa_names_set ? "another number of names" : "no names");
 	}
-	for (u32 i = 0; i < n_contigs; i++) {
-		if (offsets[i] + lens[i] > n || (i + 1 < n_contigs && offsets[i] + lens[i] >= offsets[i + 1])) {
-			return fail(c, NTEDIT_E_ARG, "polish_batch: contig %u breaks the batch layout", i);
-		}
+	if (const u32 bad = nte_host::first_layout_break(n, offsets, lens, n_contigs, true); bad != nte_host::LAYOUT_OK) {
+		return fail(c, NTEDIT_E_ARG, "polish_batch: contig %u breaks the batch layout", bad);
 	}
 	std::vector<std::string> fa_names; // (the header lines serve this call alone: used up once its arguments are accepted)
 	if (c->apply_flags & NTEDIT_HIP_APPLY_BGZF) {
@@ -1601,40 +1246,11 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 			lens[i] = (uint32_t)(wn / wc - 1);
 			buf[offs[i] + lens[i]] = '\n';
 		}
-		const auto keep = c->tune;
-		if (binned) {
-			c->tune.screen_mode = 2;
-		}
-		c->tune.force_rounds = 1;
-		c->tune.no_rounds = 0;
-		// (the warm-up batch is no part of the draft: it leaves no completeness marks; APPLY_QV runs the same screenings)
-		const u32 keep_flags = c->apply_flags;
-		if (keep_flags & NTEDIT_HIP_APPLY_SHARED) {
-			c->apply_flags = (keep_flags & ~NTEDIT_HIP_APPLY_SHARED) | NTEDIT_HIP_APPLY_QV;
-		}
-		c->apply_flags &= ~NTEDIT_HIP_APPLY_BGZF; // (the writer has a warm-up of its own, below; this batch has no names)
-		if ((keep_flags & NTEDIT_HIP_APPLY_BGZF) && !c->apply_flags) {
-			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
-		}
-		// (nor does it leave a spectrum: the switch stays down for it, spectrum_last as it was; k_spectrum's code object loads
-		// with the library's others)
-		const bool keep_spectrum = c->spectrum_on;
-		c->spectrum_on = false;
-		if (keep_spectrum && !c->apply_flags) {
-			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
-		}
-		// (nor anything in the draft store: its state is OFF for the warm-up)
-		const int keep_cn = c->cn.state;
-		c->cn.state = CN_OFF;
-		if (keep_cn != CN_OFF && !c->apply_flags) {
-			c->apply_flags = NTEDIT_HIP_APPLY_EDITED; // (the applier's kernels)
-		}
 		ntedit_hip_result* wr = nullptr;
-		rc = ntedit_hip_polish_batch(c, buf.data(), wn, offs.data(), lens.data(), wc, NTEDIT_HIP_BASES_HOST, &wr);
-		c->cn.state = keep_cn;
-		c->spectrum_on = keep_spectrum;
-		c->apply_flags = keep_flags;
-		c->tune = keep;
+		{
+			WarmupSwitches warmup(c, binned); // (the batch is no part of the draft: it leaves nothing in any report)
+			rc = ntedit_hip_polish_batch(c, buf.data(), wn, offs.data(), lens.data(), wc, NTEDIT_HIP_BASES_HOST, &wr);
+		}
 		if (wr) {
 			ntedit_hip_result_free(wr);
 		}

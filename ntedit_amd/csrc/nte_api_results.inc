@@ -174,10 +174,8 @@ ntedit_hip_track_extract(ntedit_hip_ctx* c, const uint64_t* bitmap, uint64_t n_p
 	if (k == 0 || k > TRACK_MAX_K) {
 		return fail(c, NTEDIT_E_UNSUPPORTED, "track_extract: k from 1 to %u", TRACK_MAX_K);
 	}
-	for (u32 i = 0; i < n_entries; i++) {
-		if (offs[i] > n_positions || lens[i] > n_positions - offs[i] || (i + 1 < n_entries && offs[i] + lens[i] > offs[i + 1])) {
-			return fail(c, NTEDIT_E_ARG, "track_extract: entry %u breaks the batch layout", i);
-		}
+	if (const u32 bad = nte_host::first_layout_break(n_positions, offs, lens, n_entries, false); bad != nte_host::LAYOUT_OK) {
+		return fail(c, NTEDIT_E_ARG, "track_extract: entry %u breaks the batch layout", bad);
 	}
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->track_last = ntedit_hip_track_stats{ { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
@@ -199,6 +197,7 @@ ntedit_hip_track_extract(ntedit_hip_ctx* c, const uint64_t* bitmap, uint64_t n_p
 	rc = track_run(c, s, (const u64*)c->ap_bitmap.p, n_positions, (const u64*)c->offs.p, (const u32*)c->lens.p, n_entries, k, 0, &recs, &n_recs);
 	if (rc) {
 		(void)hipStreamSynchronize(s);
+		free(recs);
 		return rc;
 	}
 	*n = n_recs;
@@ -281,10 +280,8 @@ ntedit_hip_spectrum_count(ntedit_hip_ctx* c, const char* bases, uint64_t n, int 
 	if (rc || (rc = refresh_params(c))) {
 		return rc;
 	}
-	for (u32 i = 0; i < n_entries; i++) {
-		if (offs[i] > n || lens[i] > n - offs[i] || (i + 1 < n_entries && offs[i] + lens[i] > offs[i + 1])) {
-			return fail(c, NTEDIT_E_ARG, "spectrum_count: entry %u breaks the batch layout", i);
-		}
+	if (const u32 bad = nte_host::first_layout_break(n, offs, lens, n_entries, false); bad != nte_host::LAYOUT_OK) {
+		return fail(c, NTEDIT_E_ARG, "spectrum_count: entry %u breaks the batch layout", bad);
 	}
 	memset(bins, 0, SPECTRUM_BINS * 8);
 	if (rows && n_entries) {
@@ -357,10 +354,8 @@ ntedit_hip_cn_append(ntedit_hip_ctx* c, int which, const char* bases, uint64_t n
 	if (rc) {
 		return rc;
 	}
-	for (u32 i = 0; i < n_entries; i++) {
-		if (offs[i] > n || lens[i] > n - offs[i] || (i + 1 < n_entries && offs[i] + lens[i] > offs[i + 1])) {
-			return fail(c, NTEDIT_E_ARG, "cn_append: entry %u breaks the batch layout", i);
-		}
+	if (const u32 bad = nte_host::first_layout_break(n, offs, lens, n_entries, false); bad != nte_host::LAYOUT_OK) {
+		return fail(c, NTEDIT_E_ARG, "cn_append: entry %u breaks the batch layout", bad);
 	}
 	std::string why;
 	if ((rc = cn_append(c->cn, which, c->stream, bases, n, offs, lens, n_entries, &why))) {
@@ -621,10 +616,7 @@ ntedit_hip_shared_mark(ntedit_hip_ctx* c, int which, const char* bases, uint64_t
 	u64* d_bitmap = (u64*)c->bitmap.p;
 	const Filter f0 = dev_filter(c->filt[0]);
 	PlainScreen plain(c);
-	u32 recovered = 0;
-	if ((rc = bin_reset(c, c->stream)) || (rc = launch_screen<false>(c, d_seq, n, f0, d_bitmap, n_words)) ||
-	    (rc = bin_recover(c, c->stream, d_seq, n, f0, d_bitmap, n_words, 0, n, &recovered)) ||
-	    (rc = launch_mark(c, c->stream, d_seq, n, f0, d_bitmap, n_words, which))) {
+	if ((rc = screen_whole(c, d_seq, n, f0, d_bitmap, n_words)) || (rc = launch_mark(c, c->stream, d_seq, n, f0, d_bitmap, n_words, which))) {
 		(void)hipStreamSynchronize(c->stream);
 		return rc;
 	}

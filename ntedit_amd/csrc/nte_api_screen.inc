@@ -88,6 +88,30 @@ launch_screen(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u64* d
 	return launch_screen_tiles<INSERT>(c, c->stream, d_seq, n, f, d_bitmap, n_words, 0, blocks, 0);
 }
 
+// One screening of a whole buffer on the context's stream: the previous call's record chunks are forgotten, the n bytes at
+// d_seq are screened into d_bitmap -- between `begin` and `end` where the caller times it --, record chunks that lost probes
+// are screened again (bin_recover: the stream is waited for where the binned pipeline ran).  Whether the screening is a plain
+// one (PlainScreen) is the caller's business.
+int
+screen_whole(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u64* d_bitmap, u64 n_words, hipEvent_t begin = nullptr, hipEvent_t end = nullptr)
+{
+	int rc;
+	if ((rc = bin_reset(c, c->stream))) {
+		return rc;
+	}
+	if (begin) {
+		HIP_TRY(c, hipEventRecord(begin, c->stream));
+	}
+	if ((rc = launch_screen<false>(c, d_seq, n, f, d_bitmap, n_words))) {
+		return rc;
+	}
+	if (end) {
+		HIP_TRY(c, hipEventRecord(end, c->stream));
+	}
+	u32 recovered = 0;
+	return bin_recover(c, c->stream, d_seq, n, f, d_bitmap, n_words, 0, n, &recovered);
+}
+
 // -s 0 semantics for the screenings of a scope: with -s 1 k_screen marks every k-mer of accepted bases, which is not the
 // filter's answer (the QV counts, the completeness marks)
 struct PlainScreen
@@ -104,6 +128,43 @@ struct PlainScreen
 	{
 		c->hp.snv = hp_snv;
 		c->dp.snv = dp_snv;
+	}
+};
+
+// The switches of a scope that polishes ntedit_hip_reserve's warm-up batch, put back when it ends.  Tuning: screened the way
+// the big batches will be, event rounds forced so that their kernels load too.  Reports: the batch is no part of the draft,
+// so it leaves no completeness marks (SHARED becomes QV, which runs the same screenings), no spectrum and nothing in the draft
+// store (k_spectrum's code object loads with the library's others), and it has no names (BGZF is off: the writer has a warm-up
+// of its own); if that leaves no flag although something was on, APPLY_EDITED runs the applier's kernels.
+struct WarmupSwitches
+{
+	ntedit_hip_ctx* c;
+	ntedit_hip_ctx::Tuning tune;
+	u32 apply_flags;
+	bool spectrum_on;
+	int cn_state;
+	WarmupSwitches(ntedit_hip_ctx* c_, bool binned) : c(c_), tune(c_->tune), apply_flags(c_->apply_flags), spectrum_on(c_->spectrum_on), cn_state(c_->cn.state)
+	{
+		if (binned) {
+			c->tune.screen_mode = 2;
+		}
+		c->tune.force_rounds = 1;
+		c->tune.no_rounds = 0;
+		u32 flags = apply_flags & ~NTEDIT_HIP_APPLY_BGZF;
+		if (flags & NTEDIT_HIP_APPLY_SHARED) {
+			flags = (flags & ~NTEDIT_HIP_APPLY_SHARED) | NTEDIT_HIP_APPLY_QV;
+		}
+		const bool something_on = apply_flags || spectrum_on || cn_state != CN_OFF;
+		c->apply_flags = !flags && something_on ? NTEDIT_HIP_APPLY_EDITED : flags;
+		c->spectrum_on = false;
+		c->cn.state = CN_OFF;
+	}
+	~WarmupSwitches()
+	{
+		c->tune = tune;
+		c->apply_flags = apply_flags;
+		c->spectrum_on = spectrum_on;
+		c->cn.state = cn_state;
 	}
 };
 
@@ -158,10 +219,8 @@ shared_begin(ntedit_hip_ctx* c, const char* who)
 	if (c->sh_bytes) {
 		return 0; // (the marks of this filter: drop_filter releases them with it)
 	}
-	for (auto& e : c->sh_evt) {
-		if (!e) {
-			HIP_TRY(c, hipEventCreate(&e));
-		}
+	if ((rc = ensure_events(c, c->sh_evt))) {
+		return rc;
 	}
 	// (whole 64-bit words, as the filter's own allocation: k_popcount reads words, k_mark ORs into 32-bit ones)
 	const size_t padded = (size_t)((c->filt[0].nbytes + 7) / 8 * 8);
@@ -255,14 +314,9 @@ spectrum_rows(ntedit_hip_ctx* c, int which, u32 n_entries)
 int
 spectrum_begin(ntedit_hip_ctx* c, hipStream_t stream, u32 n_entries)
 {
-	for (auto& e : c->sp_evt) {
-		if (!e) {
-			HIP_TRY(c, hipEventCreate(&e));
-		}
-	}
 	const size_t bytes = (2 * (size_t)SPECTRUM_BINS + 2 * (size_t)n_entries * 3) * 8;
-	int rc = ensure(c, c->sp_buf, bytes);
-	if (rc) {
+	int rc;
+	if ((rc = ensure_events(c, c->sp_evt)) || (rc = ensure(c, c->sp_buf, bytes))) {
 		return rc;
 	}
 	HIP_TRY(c, hipMemsetAsync(c->sp_buf.p, 0, bytes, stream));

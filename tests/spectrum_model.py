@@ -80,3 +80,31 @@ def counting_filter(seqs, k, h, counters, est_of, cmin=1, pinned=()):
 def check_not_degenerate(bins):
     """a filter that gave everything one multiplicity would let a test pass vacuously"""
     assert bins[0] > 0 and bins[255] > 0 and int((bins[1:255] > 0).sum()) >= 5, bins
+
+
+def polish_case(tmp):
+    """The small polish case of the spectrum, copy-number and apply tests, written under tmp (needs a GPU: the filter is saved
+    through the library): H.make_case(.., 32001, "N lower") with a numpy counting filter over the truth's k-mers, every one
+    entered with a count of 1 or more (1: absent at -p 2), one stretch at 255; the filter as a .bf file"""
+    import os
+
+    import helpers as H
+    import ntedit_amd
+    case = H.make_case(tmp, 32001, flavor="N lower")
+    truth = [s for _, s in H.read_fasta(case["truth"])]
+    k, h = 25, 3
+    data = counting_filter(truth, k, h, 1 << 20, lambda i: 1 + (i * 7) % 60, pinned=[(truth[1][700:1400], 255)])
+    hv = np.concatenate([RM.kmer_hashes(t, k, h) for t in truth])
+    assert data[(hv % np.uint64(len(data))).astype(np.int64)].min() >= 1  # (all at least 1 on the truth's k-mers)
+    recs = H.read_fasta(case["draft"])
+    assert set(b"".join(s for _, s in recs)) <= set(b"ACGTNacgtn")
+    pol = ntedit_amd.Polisher(0)
+    try:
+        pol.set_filter(data, h, k, counting=True)
+        case["counts_bf"] = os.path.join(tmp, "counts.bf")
+        pol.filter_save_file(case["counts_bf"])
+    finally:
+        pol.close()
+    assert H.load_bf(case["counts_bf"])["counting"]
+    case.update(tmp=tmp, recs=recs, k=k, h=h, data=data)
+    return case

@@ -275,3 +275,153 @@ def test_second_batch_does_not_alias_the_first(tmp_path, oracle_build):
             res.free()
     finally:
         pol.close()
+
+
+# ------------------------------------------------------------------------------------- the reports together
+CN_COUNTERS = 1 << 20
+TOGETHER_CASES = {
+    "plain": ("plain", [dict()]),
+    "plain_snv": ("plain", [dict(snv=1)]),
+    "counting_p2": ("counting", [dict(min_threshold=2), dict(min_threshold=2, snv=1)]),
+}
+
+
+@pytest.fixture(scope="module")
+def together_cases(tmp_path_factory, oracle_build):
+    """the drafts of H.make_case (60 kbp, three contigs): one with its plain filter, one with spectrum_model's counting filter"""
+    import spectrum_model as SM
+    plain = H.make_case(str(tmp_path_factory.mktemp("together_plain")), 31004, flavor="N lower")
+    plain["recs"] = H.read_fasta(plain["draft"])
+    counting = SM.polish_case(str(tmp_path_factory.mktemp("together_counting")))
+    counting["bf"] = counting["counts_bf"]
+    return dict(plain=plain, counting=counting)
+
+
+def _reports_of(kind):
+    """the reports a filter of that kind takes: name -> apply flag (None: a switch of its own)"""
+    import ntedit_amd
+    reports = dict(edited=ntedit_amd.APPLY_EDITED, qv=ntedit_amd.APPLY_QV, track=ntedit_amd.APPLY_TRACK, bgzf=ntedit_amd.APPLY_BGZF)
+    if kind == "plain":
+        reports["shared"] = ntedit_amd.APPLY_SHARED
+    else:
+        reports.update(spectrum=None, cn=None)
+    return reports
+
+
+def _polish_with(pol, batch, on):
+    """one polish_batch with the reports `on` (a dict of _reports_of) and no other; returns what each of them gives, the
+    events of the call and the applier's byte count"""
+    blob, offs, lens, names = batch
+    n = len(names)
+    pol.set_apply(sum(f for f in on.values() if f))
+    pol.set_spectrum("spectrum" in on)
+    pol.set_cn("cn" in on)  # (switching it on or off empties the store)
+    if "shared" in on:
+        pol.shared_begin()
+        pol.shared_reset()
+    if "bgzf" in on:
+        pol.set_fa_names(names)
+    res = pol.polish_batch(blob, offs, lens)
+    return _gather(pol, res, n, on)
+
+
+def _gather(pol, res, n, on):
+    got = dict(events=int(res.stats().events), bytes=int(pol.apply_info().bytes))
+    if "edited" in on:
+        got["edited"] = [x.tobytes() for x in res.edited(n)]
+    if "qv" in on:
+        got["qv"] = res.qv(n).tobytes()
+    if "track" in on:
+        got["track"] = [res.track(0).tobytes(), res.track(1).tobytes()]
+    if "bgzf" in on:
+        got["bgzf"] = res.fa_bgzf()
+    if "shared" in on:
+        got["shared"] = [pol.shared_download(0).tobytes(), pol.shared_download(1).tobytes()]
+    if "spectrum" in on:
+        got["spectrum"] = [res.spectrum(0).tobytes(), res.spectrum(1).tobytes(), res.depth(n).tobytes()]
+    if "cn" in on:
+        pol.cn_finish(CN_COUNTERS)
+        got["cn"] = [x.tobytes() for which in (0, 1) for x in pol.cn_table(which) + (pol.cn_rows(which, n),)]
+    res.free()
+    return got
+
+
+_together = {}
+
+
+def _everything_on(case, kind, par_kw):
+    """the results of one batch polished with every report of its filter's kind on; computed once per configuration"""
+    import ntedit_amd
+    key = (kind,) + tuple(sorted(par_kw.items()))
+    if key not in _together:
+        pol = _polisher(case["bf"], **par_kw)
+        try:
+            batch = ntedit_amd.pack_batch(case["recs"], pol.params.min_contig_len)
+            _together[key] = _polish_with(pol, batch, _reports_of(kind))
+        finally:
+            pol.close()
+    return _together[key]
+
+
+@pytest.mark.parametrize("name", list(TOGETHER_CASES))
+def test_reports_together_equal_each_alone(together_cases, name):
+    """every report alone, then all of them in one call: each gives the same bytes either way, the polish finds the same
+    events, and the applier writes as many bytes as edited() holds"""
+    import ntedit_amd
+    kind, configs = TOGETHER_CASES[name]
+    case = together_cases[kind]
+    for par_kw in configs:
+        reports = _reports_of(kind)
+        together = _everything_on(case, kind, par_kw)
+        edited_size = len(together["edited"][0])
+        assert edited_size > 0 and together["bytes"] == edited_size and together["events"] > 0
+        assert sorted(together) == sorted(list(reports) + ["events", "bytes"])
+        pol = _polisher(case["bf"], **par_kw)
+        try:
+            batch = ntedit_amd.pack_batch(case["recs"], pol.params.min_contig_len)
+            for report, flag in reports.items():
+                alone = _polish_with(pol, batch, {report: flag})
+                assert sorted(alone) == sorted([report, "events", "bytes"])
+                assert alone[report] == together[report], "%s %s: alone and together differ" % (par_kw, report)
+                assert alone["events"] == together["events"], (par_kw, report)
+                assert alone["bytes"] == edited_size, (par_kw, report)
+        finally:
+            pol.close()
+        # the reports say something: intervals on both sides, marks, a non-empty BGZF text
+        assert all(len(x) > 0 for x in together["track"]) and together["bgzf"][1] > edited_size
+        if kind == "plain":
+            assert all(any(x) for x in together["shared"])
+
+
+@pytest.mark.parametrize("kind", ["plain", "counting"])
+def test_reserve_with_everything_on_leaves_no_trace(together_cases, kind):
+    """every switch on and the names set, then reserve(): its warm-up batch leaves no mark, nothing in the store and no
+    spectrum, and the next polish_batch runs with the switches and the names as they were set"""
+    import ntedit_amd
+    case = together_cases[kind]
+    par_kw = dict() if kind == "plain" else dict(min_threshold=2)
+    reports = _reports_of(kind)
+    want = _everything_on(case, kind, par_kw)
+    pol = _polisher(case["bf"], **par_kw)
+    try:
+        blob, offs, lens, names = ntedit_amd.pack_batch(case["recs"], pol.params.min_contig_len)
+        pol.set_apply(sum(f for f in reports.values() if f))
+        pol.set_spectrum("spectrum" in reports)
+        pol.set_cn("cn" in reports)
+        if kind == "plain":
+            pol.shared_begin()
+        pol.set_fa_names(names)
+        pol.reserve(1 << 20, 16)
+        if kind == "plain":
+            st = pol.shared_counts()
+            assert (st.marked_calls, st.shared_set[0], st.shared_set[1]) == (0, 0, 0)
+        else:
+            info = pol.cn_info()
+            assert (info.state, info.batches[0], info.batches[1], info.bytes[0], info.bytes[1]) == (1, 0, 0, 0, 0)
+            sp = pol.spectrum_info()
+            assert (sp.kmers[0], sp.kmers[1], sp.ms[0], sp.ms[1]) == (0, 0, 0.0, 0.0)
+        # the flags are what they were, and so are the names: every report of the next call is there and equals the reference
+        res = pol.polish_batch(blob, offs, lens)
+        assert _gather(pol, res, len(names), reports) == want
+    finally:
+        pol.close()

@@ -10,7 +10,6 @@ import numpy as np
 import pytest
 
 import helpers as H
-import reads_model as RM
 import spectrum_model as SM
 from test_gpu_reads_cascade import case as cascade_case  # noqa: F401  (the small read set of that file, built once here)
 
@@ -224,28 +223,8 @@ def depth_of(before, after):
 
 @pytest.fixture(scope="module")
 def polish_case(tmp_path_factory, oracle_build):
-    """H.make_case(.., 32001, "N lower") with a numpy counting filter over the truth's k-mers, every one entered with a
-    count of 1 or more (1: absent at -p 2), one stretch at 255; the filter as a .bf file"""
-    import ntedit_amd
-    tmp = str(tmp_path_factory.mktemp("spectrum"))
-    case = H.make_case(tmp, 32001, flavor="N lower")
-    truth = [s for _, s in H.read_fasta(case["truth"])]
-    k, h = 25, 3
-    data = SM.counting_filter(truth, k, h, 1 << 20, lambda i: 1 + (i * 7) % 60, pinned=[(truth[1][700:1400], 255)])
-    hv = np.concatenate([RM.kmer_hashes(t, k, h) for t in truth])
-    assert data[(hv % np.uint64(len(data))).astype(np.int64)].min() >= 1  # (all at least 1 on the truth's k-mers)
-    recs = H.read_fasta(case["draft"])
-    assert set(b"".join(s for _, s in recs)) <= set(b"ACGTNacgtn")
-    pol = ntedit_amd.Polisher(0)
-    try:
-        pol.set_filter(data, h, k, counting=True)
-        case["counts_bf"] = os.path.join(tmp, "counts.bf")
-        pol.filter_save_file(case["counts_bf"])
-    finally:
-        pol.close()
-    assert H.load_bf(case["counts_bf"])["counting"]
-    case.update(tmp=tmp, recs=recs, k=k, h=h, data=data)
-    return case
+    """spectrum_model.polish_case: the draft of H.make_case(.., 32001, "N lower") and a numpy counting filter over the truth"""
+    return SM.polish_case(str(tmp_path_factory.mktemp("spectrum")))
 
 
 def check_polish(tmp, recs, bf_path, tag, made_here=True, **par_kw):
