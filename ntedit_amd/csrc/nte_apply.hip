@@ -2,6 +2,7 @@
 // Stages and data: nte_apply.h.  The specification of the applier is host/render.cpp (render_contig and the FASTA part
 // of write_contig); every rule below names the line of thought it restates.
 #include "nte_apply.h"
+#include "nte_tile.h" // (entry_behind, bit_range)
 
 namespace nte {
 
@@ -608,33 +609,6 @@ accepted(u32 c)
 	const u32 u = (c & 0xDF) - 'A';
 	constexpr u32 SET = (1u << 0) | (1u << 2) | (1u << 6) | (1u << 19);
 	return u < 26 && ((SET >> u) & 1);
-}
-
-// bits [lo, hi) of a word, 0 <= lo <= hi <= 64
-__device__ __forceinline__ u64
-bit_range(u32 lo, u32 hi)
-{
-	if (hi <= lo) {
-		return 0;
-	}
-	const u64 upto = hi >= 64 ? ~0ULL : (1ULL << hi) - 1;
-	return upto & ~((1ULL << lo) - 1);
-}
-
-// the first entry whose end lies behind position x (entries are in batch order)
-__device__ __forceinline__ u32
-entry_behind(const u64* __restrict__ offs, const u32* __restrict__ lens, u32 n, u64 x)
-{
-	u32 lo = 0, hi = n;
-	while (lo < hi) {
-		const u32 mid = (lo + hi) >> 1;
-		if (offs[mid] + lens[mid] <= x) {
-			lo = mid + 1;
-		} else {
-			hi = mid;
-		}
-	}
-	return lo;
 }
 
 // One workgroup per tile of QV_TILE positions of the batch, one bitmap word per thread -- whatever entries the tile holds:

@@ -263,20 +263,20 @@ k_wc_scatter(WcArgs a)
 
 	for (u64 wt = (u64)blockIdx.x * WC_WAVES + wave; wt < a.n_wtiles; wt += (u64)n_wg * WC_WAVES) {
 		const u64 tile_base = a.b.chunk_begin + wt * WC_WTILE;
-		stage_tile(a.b.seq, a.b.n, tile_base, WC_WTILE + 8, k, s_lut, s_codes, lane, 64);
+		tile_stage(a.b.seq, a.b.n, tile_base, WC_WTILE + 8, k, s_lut, s_codes, lane, 64);
 		wave_lds_fence();
 		HashState hs = { 0, 0 };
 		u32 good = 0;
 		for (u32 i = 0; i < k; i++) {
-			const u8 in = s_codes[lds_phys(x0 + i)];
+			const u8 in = s_codes[tile_phys(x0 + i)];
 			hash_roll(hs, s_tab, CODE_BAD, in);
 			good = in == CODE_BAD ? 0 : good + 1;
 		}
-		u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[lds_phys((x0 + k) & ~3u)]);
+		u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[tile_phys((x0 + k) & ~3u)]);
 #pragma unroll 1
 		for (u32 jw = 0; jw < WC_L; jw += 4) {
-			const u32 outw = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + jw)]);
-			const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[lds_phys(((x0 + jw + k) & ~3u) + 4)]);
+			const u32 outw = *reinterpret_cast<const u32*>(&s_codes[tile_phys(x0 + jw)]);
+			const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[tile_phys(((x0 + jw + k) & ~3u) + 4)]);
 			const u32 inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
 			in_lo = in_hi;
 #pragma unroll
@@ -475,11 +475,11 @@ wcb_round(int h)
 // h = 5 the groups that complete in one round are 640 +- 21
 constexpr int WCB_MAX_TOKENS = WCB_TPB * 6 / WC_GROUP + 8 + 256;
 static_assert(WCB_TILE == SCREEN_TILE && WCB_TILE % WC_WTILE == 0, "tiles of the two partition kernels nest");
-constexpr size_t WCB_LDS_BYTES = WC_LDS_RING + (size_t)WC_MAX_SLICES * 8 + (size_t)WCB_MAX_TOKENS * 4 + SCREEN_LDS_BYTES;
+constexpr size_t WCB_LDS_BYTES = WC_LDS_RING + (size_t)WC_MAX_SLICES * 8 + (size_t)WCB_MAX_TOKENS * 4 + TILE_LDS_BYTES;
 constexpr size_t WCB_LDS_STATIC = ((size_t)TAB_WORDS * 8 + 256 + 8 + 15) / 16 * 16; // s_tab, s_lut, s_ntok
 static_assert((size_t)WCB_WIDE_SLICES * WCB_WIDE_CAP * 8 == WC_LDS_RING && (size_t)WCB_WIDE_SLICES * 4 == (size_t)WC_MAX_SLICES * 8,
               "the wide layout (8-slot rings, 32-bit state words) takes the LDS of the narrow one");
-// (SCREEN_LDS_BYTES holds the codes of k = SCREEN_MAXK: the worst case is the only case)
+// (TILE_LDS_BYTES holds the codes of k = SCREEN_MAXK: the worst case is the only case)
 static_assert(WCB_LDS_BYTES + WCB_LDS_STATIC + 1024 <= 160 * 1024, "k_wc_scatter_b: LDS of a CU, with 1 KiB to spare");
 // a token: slice | first << IDX | index of the record that completed the group (< 2^IDX: the run limit), slice above
 // them; first = first lane of the group whose record is still in the ring (the ones below were stored directly).
@@ -562,14 +562,14 @@ k_wc_scatter_b(WcArgs a)
 	OvfCursor ovc = { 0, 0 };
 	for (u64 tile = blockIdx.x; tile < n_tiles; tile += n_wg) {
 		const u64 tile_base = a.b.chunk_begin + tile * WCB_TILE;
-		stage_tile(a.b.seq, a.b.n, tile_base, WCB_TILE + 8, k, s_lut, s_codes, tid, WCB_TPB);
+		tile_stage(a.b.seq, a.b.n, tile_base, WCB_TILE + 8, k, s_lut, s_codes, tid, WCB_TPB);
 		__syncthreads();
 		const u32 x0 = tid * WCB_L;
 		HashState hs = { 0, 0 };
 		u32 good = 0;
 		u32 last_code = CODE_BAD; // (MODE 1) the last base of the k-mer under the cursor
 		for (u32 i = 0; i < k; i += 4) {
-			const u32 w4 = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + i)]);
+			const u32 w4 = *reinterpret_cast<const u32*>(&s_codes[tile_phys(x0 + i)]);
 #pragma unroll
 			for (u32 b = 0; b < 4; b++) {
 				if (i + b < k) {
@@ -582,12 +582,12 @@ k_wc_scatter_b(WcArgs a)
 		}
 		// (codes are read as words of four, like k_screen: one LDS read per four k-mer starts for each of the two streams)
 		const u32 ksh = (k & 3) * 8;
-		u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[lds_phys((x0 + k) & ~3u)]);
+		u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[tile_phys((x0 + k) & ~3u)]);
 		u32 outw = 0, inw = 0;
 		for (u32 j0 = 0; j0 < WCB_L; j0 += R, round++) {
 			if ((j0 & 3u) == 0) {
-				outw = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + j0)]);
-				const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[lds_phys(((x0 + j0 + k) & ~3u) + 4)]);
+				outw = *reinterpret_cast<const u32*>(&s_codes[tile_phys(x0 + j0)]);
+				const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[tile_phys(((x0 + j0 + k) & ~3u) + 4)]);
 				inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
 				in_lo = in_hi;
 			}

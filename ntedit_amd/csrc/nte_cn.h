@@ -27,7 +27,7 @@ namespace nte {
 constexpr int CN_CLASSES = 5;
 constexpr int CN_BINS = 256;
 constexpr int CN_ROW_WORDS = 6; // kmers, cn1, cn2, cn3, cn4, cn5plus
-constexpr int CN_MAXK = 256;    // = SCREEN_MAXK (the tile's halo)
+constexpr int CN_MAXK = 256;    // = TILE_MAXK (nte_tile.h: the tile's halo)
 constexpr u64 CN_MIN_COUNTERS = 1ull << 20, CN_MAX_COUNTERS = 1ull << 36; // the default's range, and --cn_sketch's
 constexpr u64 CN_FLOOR_COUNTERS = 1ull << 6; // what cn_finish takes (eight words for k_cn_nonzero): collisions on purpose
 // one side's words on the device and in the host copy: occ[5][256] | w5[256] | nonzero counters | pad

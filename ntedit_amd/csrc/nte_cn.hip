@@ -7,11 +7,9 @@
 //   k_spectrum_cn<H, POW2>    pass 2: per k-mer H gathers into the counting filter (the multiplicity m) and H into the
 //                             sketch (the copy number cn); occ[min(cn, 5)][m], w5[m] and the entry's row
 //
-// The tile, its staging and the walk are k_spectrum's (nte_kernels.hip): 256 threads x 64 consecutive starts, the bytes
-// (+ k - 1 halo) staged once as one code per byte in LDS, rows of 64 codes padded to 68 bytes.  That code lives in a file
-// the polish's build id covers and nte_reads.hip keeps its own in an unnamed namespace, so this unit restates the
-// forty lines it needs, as nte_reads.hip does, instead of moving either.
+// The tile, its staging, the walk and the entry cursor are nte_tile.h's, as k_spectrum's are.
 #include "nte_cn.h"
+#include "nte_tile.h"
 
 #include "../../include/ntedit_hip.h"
 
@@ -19,17 +17,8 @@ namespace nte {
 
 namespace {
 
-constexpr int CN_TPB = 256;
-constexpr int CN_L = 64;
-constexpr int CN_TILE = CN_TPB * CN_L;
-constexpr int CN_LDS_BYTES = ((CN_TILE + CN_MAXK + 63) / 64) * 68 + 16;
-constexpr int CN_WAVES = CN_TPB / 64;
-
-__device__ __forceinline__ u32
-cn_lds(u32 x)
-{
-	return x + ((x >> 6) << 2);
-}
+constexpr int CN_WAVES = TILE_TPB / 64;
+static_assert(CN_MAXK <= TILE_MAXK, "the tile's halo holds the unit's largest k");
 
 // seed tables and the look-up table into LDS, then the tile's codes: CODE_BAD for every byte that is not one of ACGTacgt
 // and for every position past n
@@ -37,132 +26,45 @@ __device__ __forceinline__ void
 cn_stage(const u8* __restrict__ seq, u64 n, u32 k, const u64* __restrict__ tabs, u64* s_tab, u8* s_lut, u8* s_codes)
 {
 	const u32 tid = threadIdx.x;
-	if (tid < TAB_WORDS) {
-		s_tab[tid] = tabs[tid];
-	}
-	{
-		const u8 code = char_code((u8)tid);
-		s_lut[tid] = code > 3 ? CODE_BAD : code;
-	}
+	tile_load_tabs(tabs, s_tab, tid);
+	tile_fill_lut(s_lut, true, tid);
 	__syncthreads();
-	const u64 tile_base = (u64)blockIdx.x * CN_TILE;
-	const u32 n_chunks = (CN_TILE + k - 1 + 15) / 16;
-	for (u32 c = tid; c < n_chunks; c += CN_TPB) {
-		const u64 g = tile_base + (u64)c * 16;
-		u32 w[4];
-		if (g + 16 <= n) {
-			const uint4 v = *reinterpret_cast<const uint4*>(seq + g);
-			w[0] = v.x;
-			w[1] = v.y;
-			w[2] = v.z;
-			w[3] = v.w;
-		} else {
-#pragma unroll
-			for (int q = 0; q < 4; q++) {
-				u32 x = 0;
-#pragma unroll
-				for (int b = 0; b < 4; b++) {
-					const u64 gg = g + q * 4 + b;
-					x |= (u32)(gg < n ? seq[gg] : (u8)'\n') << (8 * b);
-				}
-				w[q] = x;
-			}
-		}
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const u32 x = w[q];
-			const u32 codes = (u32)s_lut[x & 0xFF] | ((u32)s_lut[(x >> 8) & 0xFF] << 8) | ((u32)s_lut[(x >> 16) & 0xFF] << 16) |
-			                  ((u32)s_lut[x >> 24] << 24);
-			*reinterpret_cast<u32*>(&s_codes[cn_lds(c * 16 + q * 4)]) = codes;
-		}
-	}
+	tile_stage(seq, n, (u64)blockIdx.x * TILE_STARTS, TILE_STARTS, k, s_lut, s_codes, tid, TILE_TPB);
 	__syncthreads();
-}
-
-// the first entry whose end lies behind position x (entries are in batch order)
-__device__ __forceinline__ u32
-cn_entry(const u64* __restrict__ offs, const u32* __restrict__ lens, u32 n, u64 x)
-{
-	u32 lo = 0, hi = n;
-	while (lo < hi) {
-		const u32 mid = (lo + hi) >> 1;
-		if (offs[mid] + lens[mid] <= x) {
-			lo = mid + 1;
-		} else {
-			hi = mid;
-		}
-	}
-	return lo;
-}
-
-// saturating +1 of counter s: a plain read of the containing word, the compare-and-swap only while the byte is below 255
-// (gfx950 has no byte atomics).  Counters only grow, so a stale read costs at most one more round.  A satellite k-mer
-// repeated a million times is answered from L2 after its 255th occurrence instead of serialising on one line.
-__device__ __forceinline__ void
-cn_sat_inc(u32* words, u64 s)
-{
-	u32* w = words + (s >> 2);
-	const u32 sh = (u32)(s & 3) * 8;
-	u32 old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	while (((old >> sh) & 0xFFu) != 0xFFu) {
-		const u32 prev = atomicCAS(w, old, old + (1u << sh));
-		if (prev == old) {
-			break;
-		}
-		old = prev;
-	}
 }
 
 // ------------------------------------------------------------------ k_cn_count
 // One thread walks 64 consecutive starts; a start is a k-mer when k good codes have entered and the window lies inside
-// the entry of its position (k_spectrum's bounds: entries may abut, a window never spans two).
+// the entry of its position (k_spectrum's bounds: entries may abut, a window never spans two).  Each k-mer adds 1 to its
+// H counters by k_count's store rule (byte_sat_inc).
 template<int H>
-__global__ __launch_bounds__(CN_TPB) void
+__global__ __launch_bounds__(TILE_TPB) void
 k_cn_count(const u8* __restrict__ seq, u64 n, DevParams p, const u64* __restrict__ tabs, const u64* __restrict__ offs,
            const u32* __restrict__ lens, u32 n_entries, u32* __restrict__ sketch, u64 smask)
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
-	__shared__ __attribute__((aligned(16))) u8 s_codes[CN_LDS_BYTES];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[TILE_LDS_BYTES];
 	const u32 k = p.k;
 	cn_stage(seq, n, k, tabs, s_tab, s_lut, s_codes);
 
-	const u32 x0 = threadIdx.x * CN_L;
-	HashState hs = { 0, 0 };
-	u32 good = 0;
-	for (u32 i = 0; i < k; i++) {
-		const u8 in = s_codes[cn_lds(x0 + i)];
-		hash_roll(hs, s_tab, CODE_BAD, in);
-		good = in == CODE_BAD ? 0 : good + 1;
-	}
-	const u64 pos0 = (u64)blockIdx.x * CN_TILE + x0;
-	u32 e = cn_entry(offs, lens, n_entries, pos0);
-	u64 eb = ~0ULL, ee = ~0ULL;
-	if (e < n_entries) {
-		eb = offs[e];
-		ee = eb + lens[e];
-	}
-	for (u32 j = 0; j < CN_L; j++) {
+	const u32 x0 = threadIdx.x * TILE_L;
+	TileWalk walk;
+	walk.prime(s_codes, s_tab, x0, k);
+	const u64 pos0 = (u64)blockIdx.x * TILE_STARTS + x0;
+	EntryCursor cur;
+	cur.start(offs, lens, n_entries, pos0);
+	for (u32 j = 0; j < TILE_L; j++) {
 		const u64 pos = pos0 + j;
-		while (pos >= ee) { // (ee = ~0 behind the last entry: the loop ends there)
-			e++;
-			eb = ee = ~0ULL;
-			if (e < n_entries) {
-				eb = offs[e];
-				ee = eb + lens[e];
-			}
-		}
-		if (good >= k && pos >= eb && pos + k <= ee) {
-			const u64 base = hs.fh + hs.rh;
+		cur.advance(offs, lens, n_entries, pos);
+		if (walk.valid() && cur.holds(pos, k)) {
+			const u64 base = walk.base();
 #pragma unroll
 			for (int i = 0; i < H; i++) {
-				cn_sat_inc(sketch, hash_extend(base, p, i) & smask);
+				byte_sat_inc(sketch, hash_extend(base, p, i) & smask);
 			}
 		}
-		const u8 out = s_codes[cn_lds(x0 + j)];
-		const u8 in = s_codes[cn_lds(x0 + j + k)];
-		hash_roll(hs, s_tab, out, in);
-		good = in == CODE_BAD ? 0 : good + 1;
+		walk.roll_bytes(s_codes, s_tab, j);
 	}
 }
 
@@ -204,7 +106,7 @@ k_cn_nonzero(const u64* __restrict__ w, u64 n_words, unsigned long long* total)
 // that met it.  The class counters of a thread are five named sums updated by comparison, never an array indexed by
 // the class: that would live in scratch.
 template<int H, bool POW2>
-__global__ __launch_bounds__(CN_TPB) void
+__global__ __launch_bounds__(TILE_TPB) void
 k_spectrum_cn(const u8* __restrict__ seq, u64 n, Filter f, DevParams p, const u64* __restrict__ tabs, const u64* __restrict__ offs,
               const u32* __restrict__ lens, u32 n_entries, const u8* __restrict__ sketch, u64 smask,
               unsigned long long* __restrict__ occ,  // [5][256]
@@ -213,7 +115,7 @@ k_spectrum_cn(const u8* __restrict__ seq, u64 n, Filter f, DevParams p, const u6
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
-	__shared__ __attribute__((aligned(16))) u8 s_codes[CN_LDS_BYTES];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[TILE_LDS_BYTES];
 	__shared__ u32 s_hist[CN_WAVES][CN_CLASSES * CN_BINS];
 	__shared__ unsigned long long s_w5[CN_BINS];
 	__shared__ u32 s_recip[CN_BINS];
@@ -235,27 +137,18 @@ k_spectrum_cn(const u8* __restrict__ seq, u64 n, Filter f, DevParams p, const u6
 	const u32 k = p.k;
 	cn_stage(seq, n, k, tabs, s_tab, s_lut, s_codes); // (its barriers order the zeroing before any add)
 
-	const u64 tile_base = (u64)blockIdx.x * CN_TILE;
-	const u32 x0 = tid * CN_L;
-	HashState hs = { 0, 0 };
-	u32 good = 0;
-	for (u32 i = 0; i < k; i++) {
-		const u8 in = s_codes[cn_lds(x0 + i)];
-		hash_roll(hs, s_tab, CODE_BAD, in);
-		good = in == CODE_BAD ? 0 : good + 1;
-	}
+	const u64 tile_base = (u64)blockIdx.x * TILE_STARTS;
+	const u32 x0 = tid * TILE_L;
+	TileWalk walk;
+	walk.prime(s_codes, s_tab, x0, k);
 
-	// the entry of the stream's position: [eb, ee), both ~0 behind the last entry (then nothing is a k-mer)
+	// the entry of the stream's position
 	const u64 pos0 = tile_base + x0;
-	const u32 e_tile = cn_entry(offs, lens, n_entries, tile_base);
-	u32 e = cn_entry(offs, lens, n_entries, pos0);
-	u64 eb = ~0ULL, ee = ~0ULL;
-	if (e < n_entries) {
-		eb = offs[e];
-		ee = eb + lens[e];
-	}
+	const u32 e_tile = entry_behind(offs, lens, n_entries, tile_base);
+	EntryCursor cur;
+	cur.start(offs, lens, n_entries, pos0);
 	// the row of the entry the thread is counting (e_acc), and what it has counted of the tile's own entry
-	u32 e_acc = e, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0;
+	u32 e_acc = cur.e, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0;
 	u32 t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
 	auto flush = [&]() {
 		const u32 all = a1 + a2 + a3 + a4 + a5;
@@ -290,13 +183,11 @@ k_spectrum_cn(const u8* __restrict__ seq, u64 n, Filter f, DevParams p, const u6
 	};
 
 	u32* hist = s_hist[tid >> 6];
-	const u32 ksh = (k & 3) * 8;
-	u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[cn_lds((x0 + k) & ~3u)]);
-	for (u32 j0 = 0; j0 < CN_L; j0 += 4) {
-		const u32 outw = *reinterpret_cast<const u32*>(&s_codes[cn_lds(x0 + j0)]);
-		const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[cn_lds(((x0 + j0 + k) & ~3u) + 4)]);
-		const u32 inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
-		in_lo = in_hi;
+	TileQuad quad;
+	quad.begin(s_codes, walk);
+	for (u32 j0 = 0; j0 < TILE_L; j0 += 4) {
+		u32 outw, inw;
+		quad.read(s_codes, walk, j0, outw, inw);
 
 		u64 fslot[4][H], sslot[4][H];
 		bool valid[4];
@@ -304,27 +195,17 @@ k_spectrum_cn(const u8* __restrict__ seq, u64 n, Filter f, DevParams p, const u6
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
 			const u64 pos = pos0 + j0 + u;
-			while (pos >= ee) { // (ee = ~0 behind the last entry: the loop ends there)
-				e++;
-				eb = ee = ~0ULL;
-				if (e < n_entries) {
-					eb = offs[e];
-					ee = eb + lens[e];
-				}
-			}
-			valid[u] = good >= k && pos >= eb && pos + k <= ee;
-			ent[u] = e;
-			const u64 base = hs.fh + hs.rh;
+			cur.advance(offs, lens, n_entries, pos);
+			valid[u] = walk.valid() && cur.holds(pos, k);
+			ent[u] = cur.e;
+			const u64 base = walk.base();
 #pragma unroll
 			for (int i = 0; i < H; i++) {
 				const u64 hv = hash_extend(base, p, i);
 				fslot[u][i] = POW2 ? (hv & f.mask) : filter_slot(f, hv);
 				sslot[u][i] = hv & smask;
 			}
-			const u8 out = (outw >> (8 * u)) & 0xFF;
-			const u8 in = (inw >> (8 * u)) & 0xFF;
-			hash_roll(hs, s_tab, out, in);
-			good = in == CODE_BAD ? 0 : good + 1;
+			walk.roll_quad(s_tab, outw, inw, u);
 		}
 		u8 fb[4][H], sb[4][H];
 #pragma unroll
@@ -378,7 +259,7 @@ k_spectrum_cn(const u8* __restrict__ seq, u64 n, Filter f, DevParams p, const u6
 		atomicAdd(&s_row[4], t5);
 	}
 	__syncthreads();
-	static_assert(CN_TPB == CN_BINS, "one thread per multiplicity flushes");
+	static_assert(TILE_TPB == CN_BINS, "one thread per multiplicity flushes");
 #pragma unroll
 	for (int c = 0; c < CN_CLASSES; c++) {
 		u32 total = 0;
@@ -458,7 +339,7 @@ template<int H>
 void
 cn_launch_count(dim3 grid, hipStream_t s, const CnBatch& b, const DevParams& p, const u64* d_tab, u32* sketch, u64 smask)
 {
-	hipLaunchKernelGGL((k_cn_count<H>), grid, dim3(CN_TPB), 0, s, b.bases, b.n, p, d_tab, b.offs, b.lens, b.n_entries, sketch, smask);
+	hipLaunchKernelGGL((k_cn_count<H>), grid, dim3(TILE_TPB), 0, s, b.bases, b.n, p, d_tab, b.offs, b.lens, b.n_entries, sketch, smask);
 }
 
 template<int H>
@@ -467,9 +348,9 @@ cn_launch_spectrum(dim3 grid, hipStream_t s, const CnBatch& b, const Filter& f, 
                    unsigned long long* occ, unsigned long long* w5, unsigned long long* rows)
 {
 	if (f.mask) {
-		hipLaunchKernelGGL((k_spectrum_cn<H, true>), grid, dim3(CN_TPB), 0, s, b.bases, b.n, f, p, d_tab, b.offs, b.lens, b.n_entries, sketch, smask, occ, w5, rows);
+		hipLaunchKernelGGL((k_spectrum_cn<H, true>), grid, dim3(TILE_TPB), 0, s, b.bases, b.n, f, p, d_tab, b.offs, b.lens, b.n_entries, sketch, smask, occ, w5, rows);
 	} else {
-		hipLaunchKernelGGL((k_spectrum_cn<H, false>), grid, dim3(CN_TPB), 0, s, b.bases, b.n, f, p, d_tab, b.offs, b.lens, b.n_entries, sketch, smask, occ, w5, rows);
+		hipLaunchKernelGGL((k_spectrum_cn<H, false>), grid, dim3(TILE_TPB), 0, s, b.bases, b.n, f, p, d_tab, b.offs, b.lens, b.n_entries, sketch, smask, occ, w5, rows);
 	}
 }
 
@@ -613,7 +494,7 @@ cn_finish(CnStore& st, hipStream_t stream, const Filter& f, const DevParams& p, 
 			CN_TRY(hipEventRecord(ev[2 * pass], stream), "cn_finish");
 			u64 row_base = 0;
 			for (const CnBatch& b : st.side[which]) {
-				const u64 blocks = (b.n + CN_TILE - 1) / CN_TILE;
+				const u64 blocks = (b.n + TILE_STARTS - 1) / TILE_STARTS;
 				if (blocks > 0x7FFFFFFFull) {
 					if (why) {
 						*why = "cn_finish: a stored batch is too large";

@@ -15,6 +15,7 @@
 // multi-GiB bit array => HBM random-read bound; no MFMA anywhere.
 #include "nte_machine.h"
 #include "nte_machine_launch.h"
+#include "nte_tile.h"
 
 #include <hip/hip_runtime.h>
 
@@ -24,19 +25,10 @@ namespace nte {
 // Tile: 256 threads x 64 consecutive k-mer starts per thread = 16384 starts per
 // workgroup.  The tile's bases (+ k-1 halo) are loaded once, coalesced 16 B per
 // lane, translated to 4-bit character codes through an LDS LUT and parked in
-// LDS as one code per byte.  Rows of 64 codes are padded to 68 bytes so that
-// the per-thread streams (lane stride = one row) hit 32 different banks.
-constexpr int SCREEN_TPB = 256;
-constexpr int SCREEN_L = 64;
-constexpr int SCREEN_TILE = SCREEN_TPB * SCREEN_L;
-constexpr int SCREEN_MAXK = 256;
-constexpr int SCREEN_LDS_BYTES = ((SCREEN_TILE + SCREEN_MAXK + 63) / 64) * 68 + 16;
-
-__device__ __forceinline__ u32
-lds_phys(u32 x)
-{
-	return x + ((x >> 6) << 2);
-}
+// LDS as one code per byte: nte_tile.h, whose geometry the screening's names stand for.
+constexpr int SCREEN_TPB = TILE_TPB;
+constexpr int SCREEN_TILE = TILE_STARTS;
+constexpr int SCREEN_MAXK = TILE_MAXK;
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding
 // global store (s_waitcnt vmcnt(0)); the scatter's stores are write-only streams nobody in the kernel
@@ -46,44 +38,6 @@ lds_barrier()
 {
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-
-// stage one tile of the batch as 4-bit codes in LDS (padded rows, see k_screen)
-__device__ __forceinline__ void
-stage_tile(const u8* __restrict__ seq, u64 n, u64 tile_base, u32 tile_len, u32 k, const u8* s_lut, u8* s_codes, u32 tid, u32 tpb)
-{
-	const u32 n_chunks = (tile_len + k - 1 + 15) / 16;
-	for (u32 c = tid; c < n_chunks; c += tpb) {
-		const u64 g = tile_base + (u64)c * 16;
-		u32 w[4];
-		if (g + 16 <= n) {
-			const uint4 v = *reinterpret_cast<const uint4*>(seq + g);
-			w[0] = v.x;
-			w[1] = v.y;
-			w[2] = v.z;
-			w[3] = v.w;
-		} else {
-#pragma unroll
-			for (int q = 0; q < 4; q++) {
-				u32 x = 0;
-#pragma unroll
-				for (int b = 0; b < 4; b++) {
-					const u64 gg = g + q * 4 + b;
-					const u32 ch = gg < n ? seq[gg] : (u32)'\n';
-					x |= ch << (8 * b);
-				}
-				w[q] = x;
-			}
-		}
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const u32 x = w[q];
-			const u32 codes = (u32)s_lut[x & 0xFF] | ((u32)s_lut[(x >> 8) & 0xFF] << 8) |
-			                  ((u32)s_lut[(x >> 16) & 0xFF] << 16) | ((u32)s_lut[x >> 24] << 24);
-			*reinterpret_cast<u32*>(&s_codes[lds_phys(c * 16 + q * 4)]) = codes;
-		}
-	}
-}
-
 
 // ------------------------------------------------------------------ k_unpack
 // A batch that crossed PCIe in the packed form (include/ntedit_hip.h: 4-bit codes + a case bit per base) back into
@@ -129,54 +83,39 @@ k_screen(
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
-	__shared__ __attribute__((aligned(16))) u8 s_codes[SCREEN_LDS_BYTES];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[TILE_LDS_BYTES];
 	extern __shared__ u8 s_occupancy_pad[]; // launch-time LDS pad: leaves CU room for k_machine
 
 	const u32 tid = threadIdx.x;
-	if (tid < TAB_WORDS) {
-		s_tab[tid] = tabs[tid];
-	}
-	{
-		u8 code = char_code((u8)tid);
-		if (INSERT && code > 3) {
-			code = CODE_BAD; // the filter build takes ACGT-only k-mers
-		}
-		s_lut[tid] = code;
-	}
+	tile_load_tabs(tabs, s_tab, tid);
+	tile_fill_lut(s_lut, INSERT, tid); // (the filter build takes ACGT-only k-mers)
 	__syncthreads();
 
 	const u64 tile_base = (first_tile + blockIdx.x) * SCREEN_TILE;
 	const u32 k = p.k;
-	stage_tile(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
+	tile_stage(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
 	__syncthreads();
 
 	// ---- per-thread stream of 64 k-mer starts
-	const u32 x0 = tid * SCREEN_L;
-	HashState hs = { 0, 0 };
-	u32 good = 0;
-	for (u32 i = 0; i < k; i++) {
-		const u8 in = s_codes[lds_phys(x0 + i)];
-		hash_roll(hs, s_tab, CODE_BAD, in);
-		good = in == CODE_BAD ? 0 : good + 1;
-	}
+	const u32 x0 = tid * TILE_L;
+	TileWalk walk;
+	walk.prime(s_codes, s_tab, x0, k);
 
-	const u32 ksh = (k & 3) * 8;
 	const u32 count_lo = p.min_thr > 1 ? p.min_thr : 1;
 	u64 bits = 0;
-	u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[lds_phys((x0 + k) & ~3u)]);
-	for (u32 j0 = 0; j0 < SCREEN_L; j0 += 4) {
-		const u32 outw = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + j0)]);
-		const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[lds_phys(((x0 + j0 + k) & ~3u) + 4)]);
-		const u32 inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
-		in_lo = in_hi;
+	TileQuad quad;
+	quad.begin(s_codes, walk);
+	for (u32 j0 = 0; j0 < TILE_L; j0 += 4) {
+		u32 outw, inw;
+		quad.read(s_codes, walk, j0, outw, inw);
 
 		u64 slot[4][H > 0 ? H : 1];
 		bool valid[4];
 		u64 base4[4];
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
-			valid[u] = good >= k;
-			const u64 base = hs.fh + hs.rh;
+			valid[u] = walk.valid();
+			const u64 base = walk.base();
 			base4[u] = base;
 			if (H > 0) {
 #pragma unroll
@@ -185,10 +124,7 @@ k_screen(
 					slot[u][i] = POW2 ? (hv & f.mask) : filter_slot(f, hv);
 				}
 			}
-			const u8 out = (outw >> (8 * u)) & 0xFF;
-			const u8 in = (inw >> (8 * u)) & 0xFF;
-			hash_roll(hs, s_tab, out, in);
-			good = in == CODE_BAD ? 0 : good + 1;
+			walk.roll_quad(s_tab, outw, inw, u);
 		}
 
 		if (INSERT) {
@@ -281,52 +217,37 @@ k_mark(const u8* __restrict__ seq, u64 n, Filter f, u32 k, const u64* __restrict
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
-	__shared__ __attribute__((aligned(16))) u8 s_codes[SCREEN_LDS_BYTES];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[TILE_LDS_BYTES];
 
 	const u32 tid = threadIdx.x;
 	const u64 w = (u64)blockIdx.x * SCREEN_TPB + tid;
 	const u64 absent = w < n_words ? bitmap[w] : 0; // (behind the batch nothing is a k-mer)
-	if (tid < TAB_WORDS) {
-		s_tab[tid] = tabs[tid];
-	}
-	{
-		const u8 code = char_code((u8)tid);
-		s_lut[tid] = code > 3 ? CODE_BAD : code;
-	}
+	tile_load_tabs(tabs, s_tab, tid);
+	tile_fill_lut(s_lut, true, tid);
 	__syncthreads();
 
 	const u64 tile_base = (u64)blockIdx.x * SCREEN_TILE;
-	stage_tile(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
+	tile_stage(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
 	__syncthreads();
 
-	const u32 x0 = tid * SCREEN_L;
-	HashState hs = { 0, 0 };
-	u32 good = 0;
-	for (u32 i = 0; i < k; i++) {
-		const u8 in = s_codes[lds_phys(x0 + i)];
-		hash_roll(hs, s_tab, CODE_BAD, in);
-		good = in == CODE_BAD ? 0 : good + 1;
-	}
+	const u32 x0 = tid * TILE_L;
+	TileWalk walk;
+	walk.prime(s_codes, s_tab, x0, k);
 
-	const u32 ksh = (k & 3) * 8;
-	u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[lds_phys((x0 + k) & ~3u)]);
-	for (u32 j0 = 0; j0 < SCREEN_L; j0 += 4) {
-		const u32 outw = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + j0)]);
-		const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[lds_phys(((x0 + j0 + k) & ~3u) + 4)]);
-		const u32 inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
-		in_lo = in_hi;
+	TileQuad quad;
+	quad.begin(s_codes, walk);
+	for (u32 j0 = 0; j0 < TILE_L; j0 += 4) {
+		u32 outw, inw;
+		quad.read(s_codes, walk, j0, outw, inw);
 
 		u64 slot[4];
 		bool mark[4];
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
-			mark[u] = good >= k && !((absent >> (j0 + u)) & 1);
-			const u64 hv = hs.fh + hs.rh;
+			mark[u] = walk.valid() && !((absent >> (j0 + u)) & 1);
+			const u64 hv = walk.base();
 			slot[u] = POW2 ? (hv & f.mask) : filter_slot(f, hv);
-			const u8 out = (outw >> (8 * u)) & 0xFF;
-			const u8 in = (inw >> (8 * u)) & 0xFF;
-			hash_roll(hs, s_tab, out, in);
-			good = in == CODE_BAD ? 0 : good + 1;
+			walk.roll_quad(s_tab, outw, inw, u);
 		}
 		u32 seen[4];
 #pragma unroll
@@ -360,22 +281,6 @@ k_mark(const u8* __restrict__ seq, u64 n, Filter f, u32 k, const u64* __restrict
 // atomic per field, every other entry begins inside the tile and takes the atomics of the threads that met it.  Entries
 // may abut (no separator: the entry's bounds end a k-mer, not the byte) and may be shorter than k.  All results are sums
 // of integers: they do not depend on geometry or order.
-__device__ __forceinline__ u32
-spectrum_entry(const u64* __restrict__ offs, const u32* __restrict__ lens, u32 n, u64 x)
-{
-	// the first entry whose end lies behind position x (entries are in batch order)
-	u32 lo = 0, hi = n;
-	while (lo < hi) {
-		const u32 mid = (lo + hi) >> 1;
-		if (offs[mid] + lens[mid] <= x) {
-			lo = mid + 1;
-		} else {
-			hi = mid;
-		}
-	}
-	return lo;
-}
-
 constexpr int SPECTRUM_BINS = 256;
 
 template<int H, bool POW2>
@@ -394,18 +299,13 @@ k_spectrum(
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
-	__shared__ __attribute__((aligned(16))) u8 s_codes[SCREEN_LDS_BYTES];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[TILE_LDS_BYTES];
 	__shared__ u32 s_hist[SCREEN_TPB / 64][SPECTRUM_BINS];
 	__shared__ u32 s_row[3];
 
 	const u32 tid = threadIdx.x;
-	if (tid < TAB_WORDS) {
-		s_tab[tid] = tabs[tid];
-	}
-	{
-		const u8 code = char_code((u8)tid);
-		s_lut[tid] = code > 3 ? CODE_BAD : code;
-	}
+	tile_load_tabs(tabs, s_tab, tid);
+	tile_fill_lut(s_lut, true, tid);
 #pragma unroll
 	for (int w = 0; w < SCREEN_TPB / 64; w++) {
 		s_hist[w][tid] = 0;
@@ -417,29 +317,20 @@ k_spectrum(
 
 	const u64 tile_base = (u64)blockIdx.x * SCREEN_TILE;
 	const u32 k = p.k;
-	stage_tile(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
+	tile_stage(seq, n, tile_base, SCREEN_TILE, k, s_lut, s_codes, tid, SCREEN_TPB);
 	__syncthreads();
 
-	const u32 x0 = tid * SCREEN_L;
-	HashState hs = { 0, 0 };
-	u32 good = 0;
-	for (u32 i = 0; i < k; i++) {
-		const u8 in = s_codes[lds_phys(x0 + i)];
-		hash_roll(hs, s_tab, CODE_BAD, in);
-		good = in == CODE_BAD ? 0 : good + 1;
-	}
+	const u32 x0 = tid * TILE_L;
+	TileWalk walk;
+	walk.prime(s_codes, s_tab, x0, k);
 
-	// the entry of the stream's position: [eb, ee), both ~0 behind the last entry (then nothing is a k-mer)
+	// the entry of the stream's position
 	const u64 pos0 = tile_base + x0;
-	const u32 e_tile = spectrum_entry(offs, lens, n_entries, tile_base);
-	u32 e = spectrum_entry(offs, lens, n_entries, pos0);
-	u64 eb = ~0ULL, ee = ~0ULL;
-	if (e < n_entries) {
-		eb = offs[e];
-		ee = eb + lens[e];
-	}
+	const u32 e_tile = entry_behind(offs, lens, n_entries, tile_base);
+	EntryCursor cur;
+	cur.start(offs, lens, n_entries, pos0);
 	// the row of the entry the thread is counting (e_acc), and what it has counted of the tile's own entry
-	u32 e_acc = e, a_k = 0, a_s = 0, a_sat = 0;
+	u32 e_acc = cur.e, a_k = 0, a_s = 0, a_sat = 0;
 	u32 t_k = 0, t_s = 0, t_sat = 0;
 	auto flush = [&]() {
 		if (a_k) {
@@ -462,13 +353,11 @@ k_spectrum(
 	};
 
 	u32* hist = s_hist[tid >> 6];
-	const u32 ksh = (k & 3) * 8;
-	u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[lds_phys((x0 + k) & ~3u)]);
-	for (u32 j0 = 0; j0 < SCREEN_L; j0 += 4) {
-		const u32 outw = *reinterpret_cast<const u32*>(&s_codes[lds_phys(x0 + j0)]);
-		const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[lds_phys(((x0 + j0 + k) & ~3u) + 4)]);
-		const u32 inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
-		in_lo = in_hi;
+	TileQuad quad;
+	quad.begin(s_codes, walk);
+	for (u32 j0 = 0; j0 < TILE_L; j0 += 4) {
+		u32 outw, inw;
+		quad.read(s_codes, walk, j0, outw, inw);
 
 		u64 slot[4][H];
 		bool valid[4];
@@ -476,26 +365,16 @@ k_spectrum(
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
 			const u64 pos = pos0 + j0 + u;
-			while (pos >= ee) { // (ee = ~0 behind the last entry: the loop ends there)
-				e++;
-				eb = ee = ~0ULL;
-				if (e < n_entries) {
-					eb = offs[e];
-					ee = eb + lens[e];
-				}
-			}
-			valid[u] = good >= k && pos >= eb && pos + k <= ee;
-			ent[u] = e;
-			const u64 base = hs.fh + hs.rh;
+			cur.advance(offs, lens, n_entries, pos);
+			valid[u] = walk.valid() && cur.holds(pos, k);
+			ent[u] = cur.e;
+			const u64 base = walk.base();
 #pragma unroll
 			for (int i = 0; i < H; i++) {
 				const u64 hv = hash_extend(base, p, i);
 				slot[u][i] = POW2 ? (hv & f.mask) : filter_slot(f, hv);
 			}
-			const u8 out = (outw >> (8 * u)) & 0xFF;
-			const u8 in = (inw >> (8 * u)) & 0xFF;
-			hash_roll(hs, s_tab, out, in);
-			good = in == CODE_BAD ? 0 : good + 1;
+			walk.roll_quad(s_tab, outw, inw, u);
 		}
 		u8 byte[4][H];
 #pragma unroll

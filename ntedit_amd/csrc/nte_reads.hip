@@ -28,8 +28,7 @@
 //
 // This unit does not see the context's internals (nte_api.hip): the sketch lives in a small per-context state of its
 // own, the output filter is reached through the public calls (ntedit_hip_filter_device_ptr / _info / _set_filter).
-// That keeps nte_api.hip and the kernels it compiles -- and with them ntedit_hip_build_id() -- unchanged.
-#include "nte_common.h"
+#include "nte_tile.h"
 
 #include "../../include/ntedit_hip.h"
 #include "../host/bfio.h"
@@ -48,21 +47,13 @@ using namespace nte;
 
 namespace {
 
-// Tile: 256 threads x 64 consecutive k-mer starts; the tile's bytes (+ k - 1 halo) are staged once, coalesced 16 B
-// per lane, as one 2-bit code (or RD_BAD) per byte in LDS.  Rows of 64 codes are padded to 68 bytes so that the
-// per-thread streams (lane stride = one row) fall into different banks.
-constexpr int RD_TPB = 256;
-constexpr int RD_L = 64;
-constexpr int RD_TILE = RD_TPB * RD_L;
+// The tile (256 threads x 64 consecutive k-mer starts, one 2-bit code or RD_BAD per byte in LDS), its staging from bytes
+// and the walk are nte_tile.h's; the k limit is this unit's own.
+constexpr int RD_TPB = TILE_TPB;
+constexpr int RD_TILE = TILE_STARTS;
 constexpr int RD_MAXK = 200;
-constexpr int RD_LDS_BYTES = ((RD_TILE + RD_MAXK + 63) / 64) * 68 + 16;
+static_assert(RD_MAXK <= TILE_MAXK, "the tile's halo holds the unit's largest k");
 constexpr u8 RD_BAD = CODE_BAD;
-
-__device__ __forceinline__ u32
-rd_lds(u32 x)
-{
-	return x + ((x >> 6) << 2);
-}
 
 struct RdFilter // one filter as the reads kernels address it
 {
@@ -87,17 +78,14 @@ rd_stage(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __res
          u8* s_codes)
 {
 	const u32 tid = threadIdx.x;
-	if (tid < TAB_WORDS) {
-		s_tab[tid] = tabs[tid];
-	}
+	tile_load_tabs(tabs, s_tab, tid);
 	if (!PACKED) {
-		const u8 code = char_code((u8)tid);
-		s_lut[tid] = code <= 3 ? code : RD_BAD; // k-mers of ACGTacgt only (as the filter build)
+		tile_fill_lut(s_lut, true, tid); // k-mers of ACGTacgt only (as the filter build)
 	}
 	__syncthreads();
 	const u64 tile_base = (u64)blockIdx.x * RD_TILE;
-	const u32 n_chunks = (RD_TILE + k - 1 + 15) / 16;
 	if (PACKED) {
+		const u32 n_chunks = (RD_TILE + k - 1 + 15) / 16;
 		// one group of 16 bases per lane: 6 bytes in, 16 LDS codes out (RD_TILE is a multiple of 16, so a tile starts
 		// on a group); groups past the batch are all RD_BAD, as the byte path pads with '\n'
 		const u64 groups = (n + 15) / 16;
@@ -117,41 +105,13 @@ rd_stage(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __res
 					const u32 code = (valid >> j) & 1u ? (codes >> (2 * j)) & 3u : (u32)RD_BAD;
 					x |= code << (8 * b);
 				}
-				*reinterpret_cast<u32*>(&s_codes[rd_lds(c * 16 + q * 4)]) = x;
+				*reinterpret_cast<u32*>(&s_codes[tile_phys(c * 16 + q * 4)]) = x;
 			}
 		}
 		__syncthreads();
 		return;
 	}
-	for (u32 c = tid; c < n_chunks; c += RD_TPB) {
-		const u64 g = tile_base + (u64)c * 16;
-		u32 w[4];
-		if (g + 16 <= n) {
-			const uint4 v = *reinterpret_cast<const uint4*>(seq + g);
-			w[0] = v.x;
-			w[1] = v.y;
-			w[2] = v.z;
-			w[3] = v.w;
-		} else {
-#pragma unroll
-			for (int q = 0; q < 4; q++) {
-				u32 x = 0;
-#pragma unroll
-				for (int b = 0; b < 4; b++) {
-					const u64 gg = g + q * 4 + b;
-					x |= (u32)(gg < n ? seq[gg] : (u8)'\n') << (8 * b);
-				}
-				w[q] = x;
-			}
-		}
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const u32 x = w[q];
-			const u32 codes = (u32)s_lut[x & 0xFF] | ((u32)s_lut[(x >> 8) & 0xFF] << 8) |
-			                  ((u32)s_lut[(x >> 16) & 0xFF] << 16) | ((u32)s_lut[x >> 24] << 24);
-			*reinterpret_cast<u32*>(&s_codes[rd_lds(c * 16 + q * 4)]) = codes;
-		}
-	}
+	tile_stage(seq, n, tile_base, RD_TILE, k, s_lut, s_codes, tid, RD_TPB);
 	__syncthreads();
 }
 
@@ -160,22 +120,6 @@ __device__ __forceinline__ u64
 rd_slot(const Filter& f, u64 hv)
 {
 	return POW2 ? (hv & f.mask) : filter_slot(f, hv);
-}
-
-// saturating +1 of byte s of the counter array
-__device__ __forceinline__ void
-sat_inc(u32* words, u64 s)
-{
-	u32* w = words + (s >> 2);
-	const u32 sh = (u32)(s & 3) * 8;
-	u32 old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	while (((old >> sh) & 0xFFu) != 0xFFu) {
-		const u32 prev = atomicCAS(w, old, old + (1u << sh));
-		if (prev == old) {
-			break;
-		}
-		old = prev;
-	}
 }
 
 // byte s of the counter array := max(byte, v)
@@ -236,21 +180,15 @@ rd_walk(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __rest
 {
 	__shared__ __attribute__((aligned(16))) u64 s_tab[TAB_WORDS];
 	__shared__ u8 s_lut[256];
-	__shared__ __attribute__((aligned(16))) u8 s_codes[RD_LDS_BYTES];
+	__shared__ __attribute__((aligned(16))) u8 s_codes[TILE_LDS_BYTES];
 	rd_stage<PACKED>(seq, pk, n, k, tabs, s_tab, s_lut, s_codes);
 
-	const u32 x0 = threadIdx.x * RD_L;
-	HashState hs = { 0, 0 };
-	u32 good = 0;
-	for (u32 i = 0; i < k; i++) {
-		const u8 in = s_codes[rd_lds(x0 + i)];
-		hash_roll(hs, s_tab, RD_BAD, in);
-		good = in == RD_BAD ? 0 : good + 1;
-	}
+	TileWalk walk;
+	walk.prime(s_codes, s_tab, threadIdx.x * TILE_L, k);
 	const u8* sk_bytes = reinterpret_cast<const u8*>(sk.words);
-	for (u32 j = 0; j < RD_L; j++) {
-		if (good >= k) {
-			const u64 base = hs.fh + hs.rh;
+	for (u32 j = 0; j < TILE_L; j++) {
+		if (walk.valid()) {
+			const u64 base = walk.base();
 			u64 hv[H];
 #pragma unroll
 			for (int i = 0; i < H; i++) {
@@ -259,7 +197,7 @@ rd_walk(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __rest
 			if (PASS == 0) {
 #pragma unroll
 				for (int i = 0; i < H; i++) {
-					sat_inc(sk.words, rd_slot<POW2>(sk.f, hv[i]));
+					byte_sat_inc(sk.words, rd_slot<POW2>(sk.f, hv[i]));
 				}
 			} else if (PASS == 3) {
 				atomicAdd(&s_hist[rd_est<H, POW2>(sk_bytes, sk.f, hv)], 1u);
@@ -290,10 +228,7 @@ rd_walk(const u8* __restrict__ seq, RdPacked pk, u64 n, u32 k, const u64* __rest
 				}
 			}
 		}
-		const u8 o = s_codes[rd_lds(x0 + j)];
-		const u8 in = s_codes[rd_lds(x0 + j + k)];
-		hash_roll(hs, s_tab, o, in);
-		good = in == RD_BAD ? 0 : good + 1;
+		walk.roll_bytes(s_codes, s_tab, j);
 	}
 }
 

@@ -1,37 +1,11 @@
 // nte_track.hip -- the unsupported regions of a batch as intervals, from an absent bitmap and the batch's entries
 // (nte_track.h has the definition and the stages).
 #include "nte_track.h"
+#include "nte_tile.h" // (entry_behind, bit_range)
 
 namespace nte {
 
 namespace {
-
-// bits [lo, hi) of a word, 0 <= lo <= hi <= 64
-__device__ __forceinline__ u64
-bit_range(u32 lo, u32 hi)
-{
-	if (hi <= lo) {
-		return 0;
-	}
-	const u64 upto = hi >= 64 ? ~0ULL : (1ULL << hi) - 1;
-	return upto & ~((1ULL << lo) - 1);
-}
-
-// the first entry whose end lies behind position x (entries are in batch order)
-__device__ __forceinline__ u32
-entry_behind(const u64* __restrict__ offs, const u32* __restrict__ lens, u32 n, u64 x)
-{
-	u32 lo = 0, hi = n;
-	while (lo < hi) {
-		const u32 mid = (lo + hi) >> 1;
-		if (offs[mid] + lens[mid] <= x) {
-			lo = mid + 1;
-		} else {
-			hi = mid;
-		}
-	}
-	return lo;
-}
 
 // where entry e's k-mer starts end (its own begin: it has none)
 __device__ __forceinline__ u64
