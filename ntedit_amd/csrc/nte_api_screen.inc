@@ -589,7 +589,9 @@ plan_wc(const ntedit_hip_ctx* c, u64 kmers, u32 hash_num, u32 n_slices, bool gat
 {
 	WcPlan w;
 	w.n_wtiles = (kmers + WC_WTILE - 1) / WC_WTILE;
-	const u64 per_wg_tiles = WC_WAVES; // a workgroup below that would idle wavefronts
+	// the tile a workgroup of the kernel that will run walks at a time, in wavefront tiles: k_wc_scatter_b's WCB_TILE, or one
+	// wavefront tile per wavefront of k_wc_scatter (a workgroup below that would idle wavefronts)
+	const u64 per_wg_tiles = !gate && c->tune.bin_scatter == 1 ? (u64)WC_WAVES : (u64)WCB_TILE / WC_WTILE;
 	u64 n_wg = (w.n_wtiles + per_wg_tiles - 1) / per_wg_tiles;
 	if (n_wg > c->cu_count) {
 		n_wg = c->cu_count; // persistent workgroups, one per CU (the rings take nearly all of a CU's LDS)
@@ -603,7 +605,7 @@ plan_wc(const ntedit_hip_ctx* c, u64 kmers, u32 hash_num, u32 n_slices, bool gat
 	// what is not distinct but spread out all the same (a satellite family that makes up 3 % of a genome sends its
 	// probes to ~500 slices: +3 % for those).  What exceeds the run (few k-mers repeated over and over: simple-sequence
 	// arrays) goes to the overflow list.  Only the used part of a run is ever read: the slack costs address space.
-	const u64 tiles_per_wg = (w.n_wtiles + (u64)w.n_wg * WC_WAVES - 1) / ((u64)w.n_wg * WC_WAVES) * WC_WAVES;
+	const u64 tiles_per_wg = (w.n_wtiles + (u64)w.n_wg * per_wg_tiles - 1) / ((u64)w.n_wg * per_wg_tiles) * per_wg_tiles;
 	const double mean = (double)tiles_per_wg * WC_WTILE * hash_num / (double)n_slices;
 	double cap = mean + mean / 16.0 + 6.0 * sqrt(mean) + 64.0;
 	if (c->tune.bin_cap_percent) {
@@ -746,7 +748,7 @@ binned_buffers(ntedit_hip_ctx* c, const Filter& f, u64 span, u32 n_slices, u32 p
 		HIP_TRY(c, hipMemset(c->bin_state.p, 0, (BIN_LOST_FLAGS + BIN_MAX_CHUNKS) * 4));
 	}
 	if ((rc = ensure(c, c->bin_records, plan0.record_bytes)) || (rc = ensure(c, c->bin_fill, (size_t)n_slices * plan0.n_wg * 4)) ||
-	    (rc = ensure(c, c->bin_ctl, (ctl_words + 8) * 4)) ||
+	    (rc = ensure(c, c->bin_ctl, (ctl_words + 8 + n_slices) * 4)) || // (+ the overflow counter's words, + longest[])
 	    (rc = ensure(c, c->bin_ovf, (size_t)ovf_capacity(c, span < chunk ? span : chunk, hn) * sizeof(WcOvf)))) {
 		return rc;
 	}
@@ -874,6 +876,7 @@ run_screen_binned(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u6
 		}
 		u32* d_ctl = (u32*)c->bin_ctl.p;
 		u32* d_ovf_count = d_ctl + ctl_words;
+		u32* d_longest = d_ctl + ctl_words + 8; // [n_slices]: zeroed with ctl[], the partition kernel's drain fills it
 		WcArgs w;
 		w.b.seq = d_seq;
 		w.b.n = n;
@@ -886,6 +889,7 @@ run_screen_binned(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u6
 		w.b.slice_log2 = slog;
 		w.b.records = (u64*)c->bin_records.p;
 		w.fill = (u32*)c->bin_fill.p;
+		w.longest = d_longest;
 		w.ovf = (WcOvf*)c->bin_ovf.p;
 		w.ovf_count = d_ovf_count;
 		w.ovf_cap = ovf_cap;
@@ -903,7 +907,7 @@ run_screen_binned(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u6
 			}
 			HIP_TRY(c, hipStreamWaitEvent(stream, c->h2d_ev[piece], 0));
 		}
-		HIP_TRY(c, hipMemsetAsync(d_ctl, 0, (ctl_words + 8) * 4, stream));
+		HIP_TRY(c, hipMemsetAsync(d_ctl, 0, (ctl_words + 8 + n_slices) * 4, stream));
 		HIP_TRY(c, hipEventRecord(tev[0], stream));
 		if ((rc = run_wc_partition(c, stream, w, gate))) {
 			return rc;
@@ -914,6 +918,7 @@ run_screen_binned(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u6
 		pa.filter = f.data;
 		pa.records = (const u64*)c->bin_records.p;
 		pa.fill = (const u32*)c->bin_fill.p;
+		pa.longest = d_longest;
 		pa.n_slices = n_slices;
 		pa.slog = slog;
 		pa.n_wg = plan.n_wg;

@@ -12,8 +12,10 @@
 //                 sized as a share of the chunk's records and handed out in blocks of WC_OVF_BLOCK entries, one
 //                 global atomic per block and wavefront (OvfCursor); a list that runs out all the same costs the
 //                 CHUNK its binned screening (k_ovf_check: the host screens that chunk again with k_screen).
-//   k_wc_scatter_b  (default; further down) the barrier-phased partition kernel: rounds of one k-mer per thread, records
-//                 into the rings, barrier, complete 64-byte groups out, barrier.
+//   k_wc_scatter_b  (default; further down) the barrier-phased partition kernel: tiles of 1,024 threads x 32 k-mer starts,
+//                 staged as 4-bit codes, two per byte (the packed tile of nte_tile.h: one staging, one barrier and one
+//                 prime of k rolls per 32 starts, in the LDS 16 starts per thread took as bytes); rounds of one k-mer
+//                 per thread, records into the rings, barrier, complete 64-byte groups out, barrier.
 //   k_wc_scatter  (tuning knob bin_scatter = 1) the same partition without workgroup barriers in the main loop:
 //                 persistent workgroups, one per CU, whose WAVEFRONTS run independently: a wavefront
 //                 stages its own 64 x WC_L k-mer starts as codes in its corner of the LDS, every lane
@@ -32,9 +34,13 @@
 //                 records and groups of the wavefront, and no step depends on a group that is younger or in
 //                 another half, so no wavefront ever blocks another (progress: the oldest group of a half that
 //                 has not left can always be completed by the lanes that own its indices, and flushed).
-//   k_bin_probe   every XCD takes slices from a shared counter and walks the runs of its current
-//                 slice: the slice's 2 MiB of filter (4 MiB parts of the slices of filters beyond 4 GiB) stay in that
-//                 XCD's L2 (nte_kernels.hip).
+//   longest[]     one word per slice, zeroed with the probe stage's control words before every record chunk: the drain of
+//                 either partition kernel leaves the largest fill[] of the slice's runs there (one atomicMax per (slice,
+//                 workgroup) pair).  It is where the probe stage's counter for the slice ends.
+//   k_bin_probe   every XCD takes slices from a shared counter and probes its current slice step by step, 512 records
+//                 of one run at a time, the run index fastest, up to the last step of the slice's longest run
+//                 (nte_probe_draw.h): the slice's 2 MiB of filter (4 MiB parts of the slices of filters beyond 4 GiB)
+//                 stay in that XCD's L2 (nte_kernels.hip).
 //   k_ovf_probe   the overflow list, probed directly.
 //
 // Bit-exact by construction: the same hashes, the same records, only their order inside a slice
@@ -158,6 +164,7 @@ struct WcArgs
 {
 	BinArgs b;
 	u32* fill;      // [n_slices][n_wg] records of the pair's run, padding of its last group included (multiple of 8)
+	u32* longest;   // [n_slices] the largest fill[] of the slice (zeroed before the launch): where the probe stage's counter ends
 	WcOvf* ovf;     // records of pairs whose run is full
 	u32* ovf_count; // entries handed out, in blocks (may exceed ovf_cap: then records were lost, k_ovf_check)
 	u32 ovf_cap;
@@ -443,6 +450,7 @@ k_wc_scatter(WcArgs a)
 			}
 			if (j == 0) {
 				a.fill[(size_t)b * n_wg + blockIdx.x] = left ? hd + WC_GROUP : hd;
+				atomicMax(&a.longest[b], left ? hd + WC_GROUP : hd);
 			}
 		}
 	}
@@ -459,8 +467,8 @@ k_wc_scatter(WcArgs a)
 // the record stream and the bitmap atomics): rings of 8 slots -- a slice's ninth record of a round is stored directly, as
 // its seventeenth is otherwise -- and a 32-bit state word per slice (below).
 constexpr int WCB_TPB = 1024;
-constexpr int WCB_L = 16;                      // k-mer starts per thread per tile
-constexpr int WCB_TILE = WCB_TPB * WCB_L;      // = SCREEN_TILE
+constexpr int WCB_L = 32;                      // k-mer starts per thread per tile: one staging, one barrier, one prime of k rolls for 32 starts
+constexpr int WCB_TILE = WCB_TPB * WCB_L;      // = TILE_PACKED_STARTS: the tile in the packed form (nte_tile.h), in the LDS of the byte tile
 // k-mer starts per thread and round: two while the tokens of a round fit the LDS next to the rings (h <= 2; at h = 3 two per
 // round were measured and lost: more of a ring's 16 slots arrive per round than leave)
 #ifndef NTE_WCB_R3
@@ -474,7 +482,8 @@ wcb_round(int h)
 // tokens of a round: a group per 8 records on average (R x H <= 6: 768) + what the LDS has left -- with 2048 slices and
 // h = 5 the groups that complete in one round are 640 +- 21
 constexpr int WCB_MAX_TOKENS = WCB_TPB * 6 / WC_GROUP + 8 + 256;
-static_assert(WCB_TILE == SCREEN_TILE && WCB_TILE % WC_WTILE == 0, "tiles of the two partition kernels nest");
+static_assert(WCB_TILE == TILE_PACKED_STARTS && WCB_TILE % SCREEN_TILE == 0 && WCB_TILE % WC_WTILE == 0 && WCB_L % 8 == 0,
+              "tiles of the two partition kernels and of the screening nest; a thread reads words of eight codes");
 constexpr size_t WCB_LDS_BYTES = WC_LDS_RING + (size_t)WC_MAX_SLICES * 8 + (size_t)WCB_MAX_TOKENS * 4 + TILE_LDS_BYTES;
 constexpr size_t WCB_LDS_STATIC = ((size_t)TAB_WORDS * 8 + 256 + 8 + 15) / 16 * 16; // s_tab, s_lut, s_ntok
 static_assert((size_t)WCB_WIDE_SLICES * WCB_WIDE_CAP * 8 == WC_LDS_RING && (size_t)WCB_WIDE_SLICES * 4 == (size_t)WC_MAX_SLICES * 8,
@@ -562,32 +571,33 @@ k_wc_scatter_b(WcArgs a)
 	OvfCursor ovc = { 0, 0 };
 	for (u64 tile = blockIdx.x; tile < n_tiles; tile += n_wg) {
 		const u64 tile_base = a.b.chunk_begin + tile * WCB_TILE;
-		tile_stage(a.b.seq, a.b.n, tile_base, WCB_TILE + 8, k, s_lut, s_codes, tid, WCB_TPB);
+		// (positions at or beyond chunk_end are staged -- a chunk is whole SCREEN_TILEs, half of this tile -- and never emitted)
+		tile_stage_packed(a.b.seq, a.b.n, tile_base, WCB_TILE + 8, k, s_lut, s_codes, tid, WCB_TPB);
 		__syncthreads();
 		const u32 x0 = tid * WCB_L;
 		HashState hs = { 0, 0 };
 		u32 good = 0;
 		u32 last_code = CODE_BAD; // (MODE 1) the last base of the k-mer under the cursor
-		for (u32 i = 0; i < k; i += 4) {
-			const u32 w4 = *reinterpret_cast<const u32*>(&s_codes[tile_phys(x0 + i)]);
+		for (u32 i = 0; i < k; i += 8) {
+			const u32 w8 = tile_packed_word(s_codes, x0 + i);
 #pragma unroll
-			for (u32 b = 0; b < 4; b++) {
+			for (u32 b = 0; b < 8; b++) {
 				if (i + b < k) {
-					const u8 in = (w4 >> (8 * b)) & 0xFF;
+					const u8 in = (w8 >> (4 * b)) & 15u;
 					hash_roll(hs, s_tab, CODE_BAD, in);
 					good = in == CODE_BAD ? 0 : good + 1;
 					last_code = in;
 				}
 			}
 		}
-		// (codes are read as words of four, like k_screen: one LDS read per four k-mer starts for each of the two streams)
-		const u32 ksh = (k & 3) * 8;
-		u32 in_lo = *reinterpret_cast<const u32*>(&s_codes[tile_phys((x0 + k) & ~3u)]);
+		// (codes are read as words of eight, TileOct's way: one LDS read per eight k-mer starts for each of the two streams)
+		const u32 ksh = (k & 7) * 4;
+		u32 in_lo = tile_packed_word(s_codes, (x0 + k) & ~7u);
 		u32 outw = 0, inw = 0;
 		for (u32 j0 = 0; j0 < WCB_L; j0 += R, round++) {
-			if ((j0 & 3u) == 0) {
-				outw = *reinterpret_cast<const u32*>(&s_codes[tile_phys(x0 + j0)]);
-				const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[tile_phys(((x0 + j0 + k) & ~3u) + 4)]);
+			if ((j0 & 7u) == 0) {
+				outw = tile_packed_word(s_codes, x0 + j0);
+				const u32 in_hi = tile_packed_word(s_codes, ((x0 + j0 + k) & ~7u) + 8);
 				inw = ksh ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
 				in_lo = in_hi;
 			}
@@ -626,9 +636,9 @@ k_wc_scatter_b(WcArgs a)
 						rec[u * H + i] = ((pos * 4 + (u64)i) << slog) | (slot & slice_mask);
 					}
 				}
-				const u32 sh = 8 * ((j0 + u) & 3u);
-				const u8 out = (outw >> sh) & 0xFF;
-				const u8 in = (inw >> sh) & 0xFF;
+				const u32 sh = 4 * ((j0 + u) & 7u);
+				const u8 out = (outw >> sh) & 15u;
+				const u8 in = (inw >> sh) & 15u;
 				hash_roll(hs, s_tab, out, in);
 				good = in == CODE_BAD ? 0 : good + 1;
 				last_code = in;
@@ -771,6 +781,7 @@ k_wc_scatter_b(WcArgs a)
 			}
 			if (j == 0) {
 				a.fill[(size_t)b * n_wg + blockIdx.x] = end;
+				atomicMax(&a.longest[b], end);
 			}
 		}
 	}

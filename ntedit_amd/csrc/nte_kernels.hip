@@ -16,6 +16,7 @@
 #include "nte_machine.h"
 #include "nte_machine_launch.h"
 #include "nte_tile.h"
+#include "nte_probe_draw.h"
 
 #include <hip/hip_runtime.h>
 
@@ -476,8 +477,8 @@ struct BinArgs
 // however fast each one is; placement only affects speed, never the result.
 // ctl[] (zeroed before the launch): [0] next unclaimed slice, [1..16] current slice of XCD x (0 = none yet,
 // 1 = being claimed, s + 2 = slice s), [32 + s] records of slice s handed out so far.
-// A slice's records: n_wg runs of `cap` records; in the counter's coordinates every run takes capr = cap rounded up to
-// whole steps, so no step crosses runs.
+// A slice's records: n_wg runs of up to `cap` records; the counter's coordinates enumerate steps, run index fastest, up to
+// the last step of the slice's longest run (nte_probe_draw.h, where the constants, the coordinates and the claim live).
 // Filters beyond 2048 x 2 MiB: the partition kernel has rings for 2048 slices (its LDS), so the slices grow: 4 MiB up to
 // 8 GiB, then past what an XCD's L2 holds -- 8 MiB at 16 GiB, where half the gathers would miss.  Such a slice is probed in
 // 2^plog PARTS of 4 MiB:
@@ -487,18 +488,6 @@ struct BinArgs
 #ifndef NTE_PROBE_LOAD
 #define NTE_PROBE_LOAD 1 // record loads: 0 = 8 bytes per lane, non-temporal; 1 = 16 bytes, non-temporal; 2 = 16 bytes, plain
 #endif
-#ifndef NTE_PROBE_TPB
-#define NTE_PROBE_TPB 512
-#endif
-constexpr int PROBE_TPB = NTE_PROBE_TPB;
-constexpr int PROBE_WAVES = PROBE_TPB / 64;
-#ifndef NTE_PROBE_PER
-#define NTE_PROBE_PER 8
-#endif
-constexpr int PROBE_PER = NTE_PROBE_PER;      // records per lane and step, all in flight together
-constexpr int PROBE_STEP = 64 * PROBE_PER;    // records per step of a wavefront
-constexpr u32 PROBE_DRAW = PROBE_STEP * PROBE_WAVES; // records per draw of a workgroup
-constexpr u32 CTL_NEXT = 0, CTL_CUR = 1, CTL_WORK = 32;
 constexpr u32 PROBE_XCC_ANY = 0xFFFFFFFFu;
 
 struct ProbeArgs
@@ -506,6 +495,7 @@ struct ProbeArgs
 	const u8* filter;
 	const u64* records;
 	const u32* fill; // [n_slices][n_wg]
+	const u32* longest; // [n_slices] the largest fill of the slice's runs (the partition kernel's drain)
 	u32 n_slices;
 	u32 slog;
 	u32 n_wg;
@@ -532,65 +522,73 @@ ctl_load(const u32* p)
 	return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// One thread: the next stretch [p, p + PROBE_DRAW) of the XCD's current slice, moving on to further slices as they run
-// out.  On entry {sl, p} is a draw already made from slice `sl` (or sl == NONE32: none yet).  Returns false when no
-// slice is left.
-__device__ __forceinline__ bool
-probe_claim(u32* __restrict__ ctl, u32 xcd, u32 n_slices, u32 total, u32& sl, u32& p)
+// the control words as probe_claim_try (nte_probe_draw.h) reaches them
+struct ProbeCtl
 {
-	u32* cur = ctl + CTL_CUR + xcd;
+	u32* ctl;
+	const u32* lng;
+
+	__device__ __forceinline__ u32
+	add(u32 i, u32 v)
+	{
+		return atomicAdd(&ctl[i], v);
+	}
+	__device__ __forceinline__ u32
+	cas(u32 i, u32 expect, u32 v)
+	{
+		return atomicCAS(&ctl[i], expect, v);
+	}
+	__device__ __forceinline__ u32
+	load(u32 i)
+	{
+		return ctl_load(&ctl[i]);
+	}
+	__device__ __forceinline__ void
+	store(u32 i, u32 v)
+	{
+		__hip_atomic_store(&ctl[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	__device__ __forceinline__ u32
+	longest(u32 slice)
+	{
+		return lng[slice]; // (written by the partition kernel, a launch ago)
+	}
+};
+
+// One thread: the next stretch [p, p + PROBE_DRAW) of the XCD's current slice, whose counter ends at `total`, moving on to
+// further slices as they run out.  Returns false when no slice is left.
+__device__ __forceinline__ bool
+probe_claim(ProbeCtl& c, u32 xcd, u32 n_units, u32 plog, u32 n_wg, u32& sl, u32& p, u32& total)
+{
 	for (;;) {
-		if (sl != NONE32 && p < total) {
-			if (total - p <= PROBE_DRAW) {
-				// this draw reaches the end of the slice: open the next one for the whole XCD
-				const u32 nx = atomicAdd(&ctl[CTL_NEXT], 1u);
-				__hip_atomic_store(cur, nx + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			}
-			return true;
+		const u32 r = probe_claim_try(c, xcd, n_units, plog, n_wg, sl, p, total);
+		if (r != CLAIM_WAIT) {
+			return r == CLAIM_DRAW;
 		}
-		// the XCD's current slice (another workgroup may be switching it right now)
-		u32 v = ctl_load(cur);
-		for (;;) {
-			if (v == 0) {
-				if (atomicCAS(cur, 0u, 1u) == 0u) {
-					const u32 nx = atomicAdd(&ctl[CTL_NEXT], 1u);
-					__hip_atomic_store(cur, nx + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				}
-			} else if (v >= 2 && v - 2 != sl) {
-				break;
-			} else {
-				__builtin_amdgcn_s_sleep(4);
-			}
-			v = ctl_load(cur);
-		}
-		sl = v - 2;
-		if (sl >= n_slices) {
-			return false;
-		}
-		p = atomicAdd(&ctl[CTL_WORK + sl], PROBE_DRAW);
+		__builtin_amdgcn_s_sleep(4);
 	}
 }
 
 __global__ __launch_bounds__(PROBE_TPB) void
 k_bin_probe(ProbeArgs a)
 {
-	__shared__ u32 s_draw[2][4]; // {ok, slice, start}, double-buffered: one barrier per draw
+	__shared__ u32 s_draw[2][4]; // {ok, slice, start, end of the slice's counter}, double-buffered: one barrier per draw
 	const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const u64 off_mask = (1ULL << a.slog) - 1;
 	const u32 xcd = a.force_xcc == PROBE_XCC_ANY ? xcc_id() : (a.force_xcc & 15u);
-	const u32 capr = (a.cap + PROBE_STEP - 1) / PROBE_STEP * PROBE_STEP; // a run in the counter's coordinates
-	const u32 total = a.n_wg * capr;
 	const u32 bsh = a.counting ? 0u : 3u; // slots per byte, as a shift
 	const u32 n_units = a.n_slices << a.plog; // (slice, part) pairs
 	const u32 part_shift = a.slog - a.plog;
-	u32 sl = NONE32, p = 0; // (thread 0: the draw made ahead; sl counts (slice, part) pairs)
+	ProbeCtl ctl = { a.ctl, a.longest };
+	u32 sl = DRAW_NONE, p = 0, sl_total = 0; // (thread 0: the draw made ahead; sl counts (slice, part) pairs)
 	for (u32 it = 0;; it++) {
 		u32* d = s_draw[it & 1];
 		if (threadIdx.x == 0) {
-			const bool ok = probe_claim(a.ctl, xcd, n_units, total, sl, p);
+			const bool ok = probe_claim(ctl, xcd, n_units, a.plog, a.n_wg, sl, p, sl_total);
 			d[0] = ok ? 1u : 0u;
 			d[1] = sl;
 			d[2] = p;
+			d[3] = sl_total;
 			if (ok) {
 				// draw the stretch after this one now: its round trip hides behind the probes
 				p = atomicAdd(&a.ctl[CTL_WORK + sl], PROBE_DRAW);
@@ -602,14 +600,14 @@ k_bin_probe(ProbeArgs a)
 		}
 		const u32 dsl = d[1];
 		const u32 at = d[2] + wave * PROBE_STEP;
-		if (at >= total) {
+		if (at >= d[3]) {
 			continue;
 		}
 		const u32 rsl = dsl >> a.plog; // the slice of the record array
 		const u32 part = dsl & ((1u << a.plog) - 1u);
 		const u8* __restrict__ fs = a.filter + ((u64)rsl << (a.slog - bsh));
-		const u32 w = at / capr;
-		const u32 i0 = at - w * capr;
+		u32 w, i0; // the run and the step's first record in it
+		draw_unit(at, a.n_wg, w, i0);
 		const u32 fill = a.fill[(size_t)rsl * a.n_wg + w];
 		if (i0 >= fill) {
 			continue;

@@ -6,16 +6,18 @@
 //   the staging    16-byte loads, bytes past the batch as '\n', the table applied (tile_stage)
 //   the walk       a thread's rolling hash over its stream: prime from k codes, roll one start, fh + rh, "k good codes"
 //                  (TileWalk), fed a byte at a time (roll_bytes) or four starts per LDS word (TileQuad)
+//   the packed tile  two 4-bit codes per byte: twice the starts in the same LDS (tile_stage_packed, tile_prime_packed, and
+//                  TileOct, eight starts per LDS word), for the partition kernel's 1,024 threads x 32 starts
 //   the entries    of a batch: the first entry whose end lies behind a position (entry_behind), a stream's cursor along
 //                  them (EntryCursor), the bits of a word (bit_range)
 //   byte_sat_inc   saturating +1 of a byte counter
 //
 // Users: k_screen, k_mark, k_spectrum (nte_kernels.hip), k_cn_count, k_spectrum_cn (nte_cn.hip), the reads passes
-// (nte_reads.hip), the entries alone in nte_apply.hip and nte_track.hip, staging and padding in nte_bin_wc.inc.
+// (nte_reads.hip), the entries alone in nte_apply.hip and nte_track.hip, the packed tile in nte_bin_wc.inc.
 // What a kernel gathers, its histograms and row flushes, and every barrier stay in the kernel: nothing here synchronises
 // or reads threadIdx, and all state is a handful of registers (no array indexed by a run-time value).
 // Includes nte_common.h and nothing of the context; compiles under hipcc and under a plain host compiler
-// (tests/tile/tile_host.cpp plays a workgroup's threads one after the other).
+// (tests/tile/tile_host.cpp and tile_packed_host.cpp play a workgroup's threads one after the other).
 #pragma once
 #include "nte_common.h"
 
@@ -190,6 +192,113 @@ struct TileQuad
 		const u32 in_hi = *reinterpret_cast<const u32*>(&s_codes[tile_phys(((w.x0 + j0 + w.k) & ~3u) + 4)]);
 		inw = (w.k & 3) ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
 		in_lo = in_hi;
+	}
+};
+
+// ---------------------------------------------------------------- the packed tile
+// Codes are 4 bits (CODE_BAD = 15): two per byte, the even start in the low nibble, hold twice the starts in the same
+// LDS -- TILE_PACKED_STARTS + the TILE_MAXK halo are 16,512 bytes, 17,560 with the row padding, inside TILE_LDS_BYTES.
+// A thread of 32 consecutive starts begins 16 bytes behind its neighbour, as a thread of 16 starts does in the byte
+// form, so tile_phys and its bank pattern stay.  User: k_wc_scatter_b (nte_bin_wc.inc); tests/tile/tile_packed_host.cpp
+// plays it against the byte walk.
+constexpr int TILE_PACKED_STARTS = 2 * TILE_STARTS;
+constexpr int TILE_PACKED_BYTES = (TILE_PACKED_STARTS + 8 + TILE_MAXK + 15) / 16 * 8; // staged, before the row padding
+static_assert(TILE_PACKED_BYTES + TILE_PACKED_BYTES / 64 * 4 + 8 <= TILE_LDS_BYTES, "the packed tile (and the word the last read takes) fits the byte tile's LDS");
+
+NTE_DEV u32
+tile_pack4(const u8* s_lut, u32 x) // the codes of four bytes, 16 bits
+{
+	return (u32)s_lut[x & 0xFF] | ((u32)s_lut[(x >> 8) & 0xFF] << 4) | ((u32)s_lut[(x >> 16) & 0xFF] << 8) | ((u32)s_lut[x >> 24] << 12);
+}
+
+// tile_stage in the packed form: code x of the tile is nibble x & 1 of byte tile_phys(x >> 1)
+NTE_DEV void
+tile_stage_packed(const u8* __restrict__ seq, u64 n, u64 tile_base, u32 tile_len, u32 k, const u8* s_lut, u8* s_codes, u32 tid, u32 tpb)
+{
+	const u32 n_chunks = (tile_len + k - 1 + 15) / 16;
+	for (u32 c = tid; c < n_chunks; c += tpb) {
+		const u64 g = tile_base + (u64)c * 16;
+		u32 w[4];
+		if (g + 16 <= n) {
+			const TileChunk v = *reinterpret_cast<const TileChunk*>(seq + g);
+			w[0] = v.w[0];
+			w[1] = v.w[1];
+			w[2] = v.w[2];
+			w[3] = v.w[3];
+		} else {
+			NTE_UNROLL
+			for (int q = 0; q < 4; q++) {
+				u32 x = 0;
+				NTE_UNROLL
+				for (int b = 0; b < 4; b++) {
+					const u64 gg = g + q * 4 + b;
+					const u32 ch = gg < n ? seq[gg] : (u32)'\n';
+					x |= ch << (8 * b);
+				}
+				w[q] = x;
+			}
+		}
+		NTE_UNROLL
+		for (int q = 0; q < 2; q++) {
+			*reinterpret_cast<u32*>(&s_codes[tile_phys(c * 8 + q * 4)]) = tile_pack4(s_lut, w[2 * q]) | (tile_pack4(s_lut, w[2 * q + 1]) << 16);
+		}
+	}
+}
+
+NTE_DEV u32
+tile_packed_word(const u8* s_codes, u32 x) // the eight codes x .. x + 7 (x a multiple of 8)
+{
+	return *reinterpret_cast<const u32*>(&s_codes[tile_phys(x >> 1)]);
+}
+
+// prime a walk from the packed tile (x0 a multiple of 8): as TileWalk::prime, eight codes per LDS word
+NTE_DEV void
+tile_prime_packed(TileWalk& w, const u8* s_codes, const u64* s_tab, u32 x0, u32 k)
+{
+	w.hs = HashState{ 0, 0 };
+	w.good = 0;
+	w.x0 = x0;
+	w.k = k;
+	for (u32 i = 0; i < k; i += 8) {
+		const u32 w8 = tile_packed_word(s_codes, x0 + i);
+		NTE_UNROLL
+		for (u32 b = 0; b < 8; b++) {
+			if (i + b < k) {
+				w.roll(s_tab, CODE_BAD, (u8)((w8 >> (4 * b)) & 15u));
+			}
+		}
+	}
+}
+
+// The eight-start reader: TileQuad on nibbles.  The codes that enter at starts j0 .. j0 + 7 (x0 and j0 multiples of 8) are
+// nibbles x0 + j0 + k .. + 7: funnelled out of two aligned words by k & 7 nibbles, the upper word carried into the next
+// read.  (With k % 8 == 0 the upper word is read and not used; at k = TILE_MAXK the last one lies behind what the staging
+// wrote, inside TILE_LDS_BYTES.)
+struct TileOct
+{
+	u32 in_lo, ksh;
+
+	NTE_DEV void
+	begin(const u8* s_codes, const TileWalk& w)
+	{
+		ksh = (w.k & 7) * 4;
+		in_lo = tile_packed_word(s_codes, (w.x0 + w.k) & ~7u);
+	}
+
+	NTE_DEV void
+	read(const u8* s_codes, const TileWalk& w, u32 j0, u32& outw, u32& inw)
+	{
+		outw = tile_packed_word(s_codes, w.x0 + j0);
+		const u32 in_hi = tile_packed_word(s_codes, ((w.x0 + j0 + w.k) & ~7u) + 8);
+		inw = (w.k & 7) ? ((in_lo >> ksh) | (in_hi << (32 - ksh))) : in_lo;
+		in_lo = in_hi;
+	}
+
+	// start u of the eight that were read
+	static NTE_DEV void
+	roll(TileWalk& w, const u64* s_tab, u32 outw, u32 inw, u32 u)
+	{
+		w.roll(s_tab, (u8)((outw >> (4 * u)) & 15u), (u8)((inw >> (4 * u)) & 15u));
 	}
 };
 
