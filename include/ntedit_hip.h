@@ -539,6 +539,64 @@ int ntedit_hip_reads_inflate_model(const void* comp, uint64_t n_comp, const nted
 uint64_t ntedit_hip_reads_last_record_start(const char* buf, uint64_t n, int kind);
 int ntedit_hip_reads_last_start_device(ntedit_hip_ctx* ctx, const void* buf, uint64_t n, int on_device, uint64_t* cut);
 int ntedit_hip_reads_inflate_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_inflate_stats* st);
+/* --gpu_parse on BAM reads, unaligned or aligned (SAM specification 4.2; a BAM is a BGZF container).  ntedit_hip_reads_pass
+ * ships the file compressed and inflates its members as for BGZF FASTQ; kernels (nte_reads_bam.hip; the grammar is
+ * nte_bam_grammar.h) then find the records of the inflated chunk and unpack the 4-bit bases of the kept ones into the
+ * batch text.  A record is kept when (flag & 0x900) == 0 (secondary and supplementary alignments repeat bases the primary
+ * record holds) and l_seq >= min_len; the strand flag 0x10 is not applied (the k-mers are canonical).  The text is every
+ * kept record's bases followed by '\n', in file order: exactly the host parser's text for the FASTQ of the same reads.
+ * The chain of block_size fields is walked speculatively: the chunk is cut into segments, every segment guesses its
+ * first record start and walks from it, and a stitch step keeps a segment's table only when the chain before it arrives
+ * at its guess, and walks it again from the true entry otherwise.  The result is the chain from the true entry.
+ *   ntedit_hip_reads_is_bam: 1 if the file starts with BGZF members that inflate to "BAM\1" (host only, the inflate
+ *           model: members are inflated until four bytes are at hand, so a first member of one to three bytes, or of
+ *           none, is taken; those members have to lie in the file's first 68 KiB), else 0.
+ *   ntedit_hip_reads_bam_device: one chunk.  raw: n_raw host or device bytes (device: 16-byte aligned) that start at
+ *           the file's first byte (at_header = 1) or at a record start (0); text_device: 16-byte aligned device memory
+ *           of text_cap >= n_raw bytes (the text is never longer than the raw bytes).  res->clean = 1, `cut` (the offset
+ *           of the first record that does not lie completely inside the chunk: the bytes from there on belong in front
+ *           of the next chunk; 0 when the header does not fit) and the counts of the records before the cut; or
+ *           clean = 0, `broken` (NTEDIT_BAM_BAD_*), `cut` the offset of the header or record that breaks the rule, the
+ *           counts 0 and the text undefined.  At most 2^31 - 1 bytes, else NTEDIT_BAM_BAD_SIZE.
+ *   ntedit_hip_reads_bam_model: the same grammar functions run serially on the host (no device; failures through
+ *           ntedit_hip_reads_last_error(NULL)): the text into out[0 .. cap), NTEDIT_E_OVERFLOW when it does not fit.
+ *   ntedit_hip_reads_bam_set_segment: the segment size of the walk, in bytes (0: the default, NTEDIT_BAM_SEGMENT; at
+ *           least 64; a size of the chunk's or more makes the walk one chain).  A tuning knob: no result depends on it.
+ *   ntedit_hip_reads_bam_info: the context's counters since ntedit_hip_reads_pass last began (the pass zeroes them;
+ *           ntedit_hip_reads_bam_device adds to them too). */
+#define NTEDIT_BAM_SEGMENT 8192
+#define NTEDIT_BAM_BAD_MAGIC 1
+#define NTEDIT_BAM_BAD_HEADER 2
+#define NTEDIT_BAM_BAD_RECORD 4
+#define NTEDIT_BAM_BAD_SIZE 8
+typedef struct ntedit_hip_reads_bam_result
+{
+	int clean;
+	uint32_t broken;       /* 0 when clean */
+	uint64_t header_len;   /* at_header and the header fits: its bytes; else 0 */
+	uint32_t n_ref, reserved;
+	uint64_t cut;
+	uint64_t records;      /* before the cut */
+	uint64_t kept, skipped_flag, skipped_short;
+	uint64_t bases;        /* of the kept records */
+	uint64_t text_len;     /* bases + kept */
+} ntedit_hip_reads_bam_result;
+typedef struct ntedit_hip_reads_bam_stats
+{
+	uint64_t files, chunks;
+	uint64_t records, kept, skipped_flag, skipped_short;
+	uint64_t segments;     /* walked speculatively */
+	uint64_t rewalked;     /* ... of which the stitch walked again from the true entry */
+	double ms_walk;        /* in the walk and stitch kernels (the one-lane header kernel, once per file, is not timed) */
+	double ms_decode;      /* in the length, scan and unpack kernels */
+} ntedit_hip_reads_bam_stats;
+int ntedit_hip_reads_is_bam(const char* path);
+int ntedit_hip_reads_bam_device(ntedit_hip_ctx* ctx, const void* raw, uint64_t n_raw, int on_device, int at_header, uint32_t min_len,
+                                char* text_device, uint64_t text_cap, ntedit_hip_reads_bam_result* res);
+int ntedit_hip_reads_bam_model(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, char* out, uint64_t cap,
+                               ntedit_hip_reads_bam_result* res);
+int ntedit_hip_reads_bam_set_segment(ntedit_hip_ctx* ctx, uint64_t bytes);
+int ntedit_hip_reads_bam_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_bam_stats* st);
 /* --gpu_parse for genome FASTA (ntedit-make-genome-bf --gpu_parse, ntedit --genome --gpu_parse).  A chromosome does not
  * fit a chunk that has to start at a record start, so a genome chunk is any run of raw bytes of a FASTA file, cut
  * anywhere, entered in a state (nte_genome_grammar.h): at a line start, inside a '>' line, or inside a sequence line.

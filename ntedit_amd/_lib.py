@@ -258,6 +258,27 @@ class ReadsInflateStats(ctypes.Structure):
 BGZF_END, BGZF_CUT, BGZF_NOT, BGZF_FULL = 0, 1, 2, 3
 
 
+# --gpu_parse on BAM reads (ntedit_hip_reads_bam_device / _model): the default segment of the walk and the rules
+BAM_SEGMENT = 8192
+BAM_BAD_MAGIC, BAM_BAD_HEADER, BAM_BAD_RECORD, BAM_BAD_SIZE = 1, 2, 4, 8
+
+
+class ReadsBamResult(ctypes.Structure):
+    """ntedit_hip_reads_bam_result"""
+    _fields_ = [("clean", ctypes.c_int), ("broken", ctypes.c_uint32), ("header_len", ctypes.c_uint64),
+                ("n_ref", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("cut", ctypes.c_uint64),
+                ("records", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("skipped_flag", ctypes.c_uint64),
+                ("skipped_short", ctypes.c_uint64), ("bases", ctypes.c_uint64), ("text_len", ctypes.c_uint64)]
+
+
+class ReadsBamStats(ctypes.Structure):
+    """ntedit_hip_reads_bam_stats: --gpu_parse on BAM inputs, since the context's last pass began"""
+    _fields_ = [("files", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("records", ctypes.c_uint64),
+                ("kept", ctypes.c_uint64), ("skipped_flag", ctypes.c_uint64), ("skipped_short", ctypes.c_uint64),
+                ("segments", ctypes.c_uint64), ("rewalked", ctypes.c_uint64), ("ms_walk", ctypes.c_double),
+                ("ms_decode", ctypes.c_double)]
+
+
 # --gpu_parse for genome FASTA (ntedit_hip_genome_parse_device / _model): the entry and exit states of a chunk
 GENOME_LINE_START, GENOME_IN_HEADER, GENOME_IN_SEQ = 0, 1, 2
 
@@ -340,6 +361,8 @@ EXPORTS = [
     "ntedit_hip_reads_parse_info", "ntedit_hip_reads_set_reject_cutoff",
     "ntedit_hip_bgzf_walk", "ntedit_hip_reads_inflate_device", "ntedit_hip_reads_inflate_model",
     "ntedit_hip_reads_last_record_start", "ntedit_hip_reads_last_start_device", "ntedit_hip_reads_inflate_info",
+    "ntedit_hip_reads_is_bam", "ntedit_hip_reads_bam_device", "ntedit_hip_reads_bam_model",
+    "ntedit_hip_reads_bam_set_segment", "ntedit_hip_reads_bam_info",
     "ntedit_hip_genome_parse_device", "ntedit_hip_genome_parse_model", "ntedit_hip_genome_pass",
     "ntedit_hip_genome_pass_get_info", "ntedit_hip_genome_pass_line",
     "ntedit_hip_sketch_reset", "ntedit_hip_resident_count", "ntedit_hip_reads_set_min_read",
@@ -513,6 +536,13 @@ def load():
     lib.ntedit_hip_reads_last_record_start.restype = u64
     lib.ntedit_hip_reads_last_start_device.argtypes = [vp, vp, u64, ci, pu64]
     lib.ntedit_hip_reads_inflate_info.argtypes = [vp, ctypes.POINTER(ReadsInflateStats)]
+    # --gpu_parse on BAM reads
+    bres = ctypes.POINTER(ReadsBamResult)
+    lib.ntedit_hip_reads_is_bam.argtypes = [ctypes.c_char_p]
+    lib.ntedit_hip_reads_bam_device.argtypes = [vp, vp, u64, ci, ci, u32, vp, u64, bres]
+    lib.ntedit_hip_reads_bam_model.argtypes = [vp, u64, ci, u32, vp, u64, bres]
+    lib.ntedit_hip_reads_bam_set_segment.argtypes = [vp, u64]
+    lib.ntedit_hip_reads_bam_info.argtypes = [vp, ctypes.POINTER(ReadsBamStats)]
     # --gpu_parse for genome FASTA
     gres = ctypes.POINTER(GenomeParseResult)
     lib.ntedit_hip_genome_parse_device.argtypes = [vp, vp, u64, ci, ci, ci, vp, u64, gres]

@@ -1,0 +1,359 @@
+// nte_bam_grammar.h -- the BAM grammar of --gpu_parse, written once (SAM specification 4.2, little-endian): what a clean
+// header is, what a clean record is, which records are kept, and what their text is.  The kernels (nte_reads_bam.hip)
+// and the serial host model (bam_model below: ntedit_hip_reads_bam_model) are both built from these functions, as
+// nte_reads_grammar.h serves the text parser.  No length from the file is trusted: every read is checked against the
+// bytes at hand before it is made.
+//
+// A chunk is a run of inflated bytes that starts at the file's first byte (at_header) or at a record start.
+//   header   "BAM\1", l_text (i32), the text, n_ref (i32), n_ref x { l_name (i32), the name, l_ref (i32) }; clean when
+//            the magic matches, l_text >= 0, n_ref >= 0 and every l_name >= 1.  A header that ends behind the bytes at
+//            hand is not unclean: the chunk's cut is 0 and it grows.
+//   record   block_size (i32), 32 fixed bytes (refID, pos, l_read_name u8, mapq, bin, n_cigar_op u16, flag u16, l_seq
+//            u32, next_refID, next_pos, tlen), read_name, cigar (4 bytes each), seq ((l_seq + 1) / 2 bytes, the high
+//            nibble first), qual (l_seq bytes), aux up to block_size (not interpreted).  Clean when block_size < 2^30,
+//            l_read_name >= 1 and 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= block_size.
+//   the cut  the offset of the first record that does not lie completely inside the chunk; a record is judged as soon
+//            as its fields are inside (block_size alone: its range; the fixed bytes: the rest), so an unclean record
+//            makes the chunk unclean even when its end is not.
+//   kept     (flag & 0x900) == 0 (neither secondary nor supplementary) and l_seq >= min_len.  The strand flag 0x10 is not
+//            applied: the sketch and the filter hash canonical k-mers (nte_reads.hip).
+//   text     every kept record's bases (codes "=ACMGRSVTWYHKDBN") followed by '\n', in file order.
+#pragma once
+
+#include <stdint.h>
+
+#include "nte_bgzf_inflate.h"
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define BAM_HD __host__ __device__ __forceinline__
+#else
+#define BAM_HD inline
+#endif
+
+namespace nte_bam {
+
+// the rules, as bits of `broken` (NTEDIT_BAM_BAD_* in ntedit_hip.h)
+enum : uint32_t {
+	BAM_BAD_MAGIC = 1,  // the first bytes are not "BAM\1"
+	BAM_BAD_HEADER = 2, // l_text < 0, n_ref < 0 or an l_name < 1
+	BAM_BAD_RECORD = 4, // l_read_name < 1, or the record's parts do not fit its block_size
+	BAM_BAD_SIZE = 8,   // block_size < 0 or >= 2^30, or a chunk of 2^31 bytes or more
+};
+// what a hop or a header ends with, besides the bits above
+enum : uint32_t {
+	BAM_NEXT = 0,     // a whole clean record (header): go on behind it
+	BAM_END = 1u << 8 // it ends behind the bytes at hand
+};
+
+constexpr uint64_t BAM_MAX_RAW = 1ull << 31;
+constexpr uint32_t BAM_MAX_BLOCK = 1u << 30;
+constexpr uint32_t BAM_MIN_RECORD = 4 + 32 + 1; // block_size, the fixed bytes, a read name of one byte
+constexpr uint32_t BAM_NO_GUESS = ~0u;
+constexpr int BAM_GUESS_HOPS = 3;               // records a guess's chain has to stay clean for behind its first
+
+BAM_HD uint32_t
+bam_ld16(const uint8_t* p)
+{
+	return (uint32_t)p[0] | (uint32_t)p[1] << 8;
+}
+
+BAM_HD uint32_t
+bam_ld32(const uint8_t* p)
+{
+	return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+// the header of raw[0 .. n): BAM_NEXT and its length and n_ref, BAM_END, or the rule it breaks
+BAM_HD uint32_t
+bam_header(const uint8_t* raw, uint64_t n, uint64_t* header_len, uint32_t* n_ref)
+{
+	const uint8_t magic[4] = { 'B', 'A', 'M', 1 };
+	for (uint64_t i = 0; i < 4 && i < n; i++) {
+		if (raw[i] != magic[i]) {
+			return BAM_BAD_MAGIC;
+		}
+	}
+	if (n < 8) {
+		return BAM_END;
+	}
+	const uint32_t l_text = bam_ld32(raw + 4);
+	if (l_text >> 31) {
+		return BAM_BAD_HEADER;
+	}
+	uint64_t p = 8 + (uint64_t)l_text;
+	if (n < p + 4) {
+		return BAM_END;
+	}
+	const uint32_t refs = bam_ld32(raw + p);
+	if (refs >> 31) {
+		return BAM_BAD_HEADER;
+	}
+	p += 4;
+	for (uint32_t i = 0; i < refs; i++) {
+		if (n < p + 4) {
+			return BAM_END;
+		}
+		const uint32_t l_name = bam_ld32(raw + p);
+		if (l_name >> 31 || l_name < 1) {
+			return BAM_BAD_HEADER;
+		}
+		p += 4 + (uint64_t)l_name + 4; // the name and l_ref
+		if (n < p) {
+			return BAM_END;
+		}
+	}
+	*header_len = p;
+	*n_ref = refs;
+	return BAM_NEXT;
+}
+
+struct BamRecord
+{
+	uint32_t next;    // the offset behind the record
+	uint32_t flag;
+	uint32_t l_seq;
+	uint32_t seq_off; // of its packed bases
+};
+
+// the record at raw[p], p <= n < 2^31: BAM_NEXT and its fields, BAM_END (it does not lie completely inside), or the rule
+// it breaks
+BAM_HD uint32_t
+bam_hop(const uint8_t* raw, uint32_t n, uint32_t p, BamRecord* r)
+{
+	const uint32_t left = n - p;
+	if (left < 4) {
+		return BAM_END;
+	}
+	const uint32_t block = bam_ld32(raw + p);
+	if (block >= BAM_MAX_BLOCK) {
+		return BAM_BAD_SIZE;
+	}
+	if (block < 32) {
+		return BAM_BAD_RECORD;
+	}
+	if (left < 36) {
+		return BAM_END;
+	}
+	const uint32_t l_read_name = raw[p + 12], n_cigar = bam_ld16(raw + p + 16), l_seq = bam_ld32(raw + p + 20);
+	const uint64_t head = 32ull + l_read_name + 4ull * n_cigar;
+	if (l_read_name < 1 || head + ((uint64_t)l_seq + 1) / 2 + l_seq > block) {
+		return BAM_BAD_RECORD;
+	}
+	if (left - 4 < block) {
+		return BAM_END;
+	}
+	r->next = p + 4 + block;
+	r->flag = bam_ld16(raw + p + 18);
+	r->l_seq = l_seq;
+	r->seq_off = p + 4 + (uint32_t)head;
+	return BAM_NEXT;
+}
+
+BAM_HD bool
+bam_kept(uint32_t flag, uint32_t l_seq, uint32_t min_len)
+{
+	return (flag & 0x900u) == 0 && l_seq >= min_len;
+}
+
+// base j of the packed bases at seq_off
+BAM_HD char
+bam_base(const uint8_t* raw, uint32_t seq_off, uint32_t j)
+{
+	const uint32_t b = raw[seq_off + (j >> 1)];
+	return "=ACMGRSVTWYHKDBN"[(j & 1) ? (b & 15u) : (b >> 4)];
+}
+
+// The chain from p (< end <= n) while it starts records below `end`: their offsets into table[0 .. cap), *count of them,
+// *exit where the chain left [.., end) (BAM_NEXT), or where it stopped: the cut (BAM_END) or the unclean record.  The
+// walk is a function of (raw, n, p, end): whoever enters at p writes the same table.
+BAM_HD uint32_t
+bam_walk(const uint8_t* raw, uint32_t n, uint32_t p, uint32_t end, uint32_t* table, uint32_t cap, uint32_t* count, uint32_t* exit)
+{
+	uint32_t c = 0, st = BAM_NEXT;
+	while (p < end) {
+		BamRecord r;
+		st = bam_hop(raw, n, p, &r);
+		if (st != BAM_NEXT) {
+			break;
+		}
+		if (c < cap) {
+			table[c] = p;
+		}
+		c++;
+		p = r.next;
+	}
+	*count = c;
+	*exit = p;
+	return st;
+}
+
+// a guess: a whole clean record at q whose chain stays clean for BAM_GUESS_HOPS more whole records, or until fewer
+// bytes are left than a record's fixed part.  A record whose fields are inside and whose end is not ends the guess: a
+// block_size of hundreds of megabytes read from the middle of a sequence would pass as "cut by the chunk's end"
+// otherwise, and the images of clean records it follows are common ("\xff\x09\x01\0" one byte before a true start is
+// one).  The price is no guess in the last few records of a chunk, which the stitch then walks.
+BAM_HD bool
+bam_guess_ok(const uint8_t* raw, uint32_t n, uint32_t q)
+{
+	BamRecord r;
+	if (bam_hop(raw, n, q, &r) != BAM_NEXT) {
+		return false;
+	}
+	for (int h = 0; h < BAM_GUESS_HOPS && r.next < n; h++) {
+		const uint32_t at = r.next, st = bam_hop(raw, n, at, &r);
+		if (st == BAM_END) {
+			return n - at < 36;
+		}
+		if (st != BAM_NEXT) {
+			return false;
+		}
+	}
+	return true;
+}
+
+// the slots a segment's slice of the offset table needs: no record is shorter than BAM_MIN_RECORD
+BAM_HD uint32_t
+bam_slice_cap(uint32_t segment)
+{
+	return segment / BAM_MIN_RECORD + 2;
+}
+
+struct BamResult // (ntedit_hip_reads_bam_result, field for field)
+{
+	int clean;
+	uint32_t broken;
+	uint64_t header_len;
+	uint32_t n_ref, reserved;
+	uint64_t cut, records, kept, skipped_flag, skipped_short, bases, text_len;
+};
+
+BAM_HD BamResult
+bam_unclean(uint32_t broken, uint64_t at)
+{
+	BamResult r = BamResult();
+	r.broken = broken;
+	r.cut = at; // where the rule is broken
+	return r;
+}
+
+// (host only from here on)
+// The model: one chain from the true entry, one pass over its records.  The text into out[0 .. cap) as far as it fits;
+// res->text_len is its whole length either way.
+inline void
+bam_model(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, char* out, uint64_t cap, BamResult* res)
+{
+	*res = BamResult();
+	if (n >= BAM_MAX_RAW) {
+		*res = bam_unclean(BAM_BAD_SIZE, 0);
+		return;
+	}
+	uint64_t entry = 0;
+	if (at_header) {
+		const uint32_t st = bam_header(raw, n, &res->header_len, &res->n_ref);
+		if (st == BAM_END) {
+			res->clean = 1; // cut 0: the chunk grows
+			return;
+		}
+		if (st != BAM_NEXT) {
+			*res = bam_unclean(st, 0);
+			return;
+		}
+		entry = res->header_len;
+	}
+	uint32_t p = (uint32_t)entry;
+	uint64_t text = 0;
+	while (p < n) {
+		BamRecord r;
+		const uint32_t st = bam_hop(raw, (uint32_t)n, p, &r);
+		if (st == BAM_END) {
+			break;
+		}
+		if (st != BAM_NEXT) {
+			*res = bam_unclean(st, p);
+			return;
+		}
+		res->records++;
+		if (r.flag & 0x900u) {
+			res->skipped_flag++;
+		} else if (r.l_seq < min_len) {
+			res->skipped_short++;
+		} else {
+			res->kept++;
+			res->bases += r.l_seq;
+			for (uint32_t j = 0; j <= r.l_seq; j++, text++) {
+				if (text < cap) {
+					out[text] = j < r.l_seq ? bam_base(raw, r.seq_off, j) : '\n';
+				}
+			}
+		}
+		p = r.next;
+	}
+	res->clean = 1;
+	res->cut = p;
+	res->text_len = text;
+}
+
+// The first BGZF member of buf[0 .. n) (a gzip member with FEXTRA and a 'B','C' subfield of the member's size - 1): where
+// its DEFLATE data lies, its ISIZE and CRC-32; false when there is none that lies completely inside.
+inline bool
+bam_first_member(const uint8_t* buf, uint64_t n, uint64_t* in_off, uint32_t* n_in, uint32_t* n_out, uint32_t* crc)
+{
+	if (n < 12 + 8 || buf[0] != 0x1f || buf[1] != 0x8b || buf[2] != 8 || buf[3] != 4) {
+		return false;
+	}
+	const uint64_t xlen = bam_ld16(buf + 10);
+	if (n < 12 + xlen) {
+		return false;
+	}
+	uint64_t member = 0;
+	for (uint64_t x = 12; x + 4 <= 12 + xlen;) {
+		const uint64_t slen = bam_ld16(buf + x + 2);
+		if (buf[x] == 'B' && buf[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen) {
+			member = (uint64_t)bam_ld16(buf + x + 4) + 1;
+		}
+		x += 4 + slen;
+	}
+	if (member < 12 + xlen + 8 || member > n) {
+		return false;
+	}
+	*in_off = 12 + xlen;
+	*n_in = (uint32_t)(member - 12 - xlen - 8);
+	*crc = bam_ld32(buf + member - 8);
+	*n_out = bam_ld32(buf + member - 4);
+	return *n_out <= 65536;
+}
+
+// whether buf[0 .. n), the start of a file, begins with BGZF members that inflate to "BAM\1" (the inflate model, one
+// lane; the members' CRCs are not looked at: the pass checks them on the device).  Members are inflated, one after the
+// other, until four bytes are at hand: a first member of one to three bytes, or of none, is legal BGZF.  The members that
+// hold those four bytes have to lie completely inside buf.
+inline bool
+bam_starts_bam(const uint8_t* buf, uint64_t n)
+{
+	const uint8_t magic[4] = { 'B', 'A', 'M', 1 };
+	nte_bgzf::BzTables* t = new nte_bgzf::BzTables();
+	uint64_t at = 0;
+	uint32_t have = 0;
+	bool bam = true;
+	while (bam && have < 4) {
+		uint64_t in_off = 0;
+		uint32_t n_in = 0, n_out = 0, crc = 0;
+		if (!bam_first_member(buf + at, n - at, &in_off, &n_in, &n_out, &crc)) {
+			bam = false;
+			break;
+		}
+		if (n_out) {
+			uint8_t* out = new uint8_t[n_out];
+			bam = nte_bgzf::bz_inflate(buf + at + in_off, n_in, out, n_out, t, 0, 1) == nte_bgzf::BZ_OK;
+			for (uint32_t i = 0; bam && i < n_out && have < 4; i++, have++) {
+				bam = out[i] == magic[have];
+			}
+			delete[] out;
+		}
+		at += in_off + n_in + 8;
+	}
+	delete t;
+	return bam;
+}
+
+} // namespace nte_bam

@@ -1,0 +1,736 @@
+// nte_reads_bam.hip -- gfx950 kernels and C ABI of --gpu_parse on BAM reads: in an inflated chunk (nte_reads_inflate.hip)
+// the records are found and the kept ones' 4-bit bases unpacked into the batch text the passes consume.  The grammar is
+// nte_bam_grammar.h, written once for the kernels and for the serial host model (ntedit_hip_reads_bam_model, below).
+//
+// The chain of block_size fields is serial, so it is walked speculatively and stitched:
+//   k_bam_header   one lane: the header's length and n_ref (once per file: the reference list is a chain of its own).
+//   k_bam_walk     one wavefront per segment, four per workgroup.  The 64 lanes test 64 offsets at a time for a clean
+//                  record (coalesced reads of the segment, which stays in the CU's L1 for what follows), the first whose
+//                  chain stays clean for a few hops is the segment's guess, and lane 0 walks from it, writing record
+//                  offsets to the segment's slice of the table and where the chain left the segment.  The segment that
+//                  holds the true entry starts from it.
+//   k_bam_stitch   one wavefront.  64 segments' guesses and exits at a time are loaded coalesced into LDS; lane 0 follows
+//                  the true chain through them at LDS latency: exit == the next segment's guess keeps that segment's
+//                  table (the walk is a function of its entry), anything else walks that segment again from the true
+//                  entry.  It marks the segments on the chain, and ends with the cut or the rule a record broke.
+//   k_bam_sums     one wavefront per segment on the chain, a lane per record: kept records and text bytes of the segment.
+//   k_bam_scan     one workgroup: the exclusive scan of those over the segments.
+//   k_bam_compact  as k_bam_sums, with a wavefront scan: each kept record's packed-bases offset and text offset, dense.
+//   k_bam_decode   one lane per 16 text bytes, whatever the records' lengths: a search in the text-offset table for the
+//                  record its first byte lies in, then nibbles to bytes across record ends, one 16-byte store.
+//
+// Like nte_reads_inflate.hip this unit is outside KSRC and sees no context internals: its state hangs off the context
+// pointer, its scratch grows only and goes with ntedit_hip_sketch_free.  It works on the parse unit's stream.
+#include "nte_common.h"
+#include "nte_bam_grammar.h"
+#include "nte_bgzf_inflate.h"
+
+#include "../../include/ntedit_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace nte;
+using namespace nte_bam;
+
+namespace nte_reads {
+int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
+int parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream);
+int parse_text_buffer(const ntedit_hip_ctx* c, uint64_t n, char** text, uint64_t* cap);
+}
+
+namespace {
+
+constexpr int BAM_TPB = 256;
+constexpr int BAM_WAVES = BAM_TPB / 64;
+constexpr u32 BAM_WINDOW = 64; // segments the stitch resolves per load
+
+static_assert(NTEDIT_BAM_BAD_MAGIC == BAM_BAD_MAGIC && NTEDIT_BAM_BAD_HEADER == BAM_BAD_HEADER && NTEDIT_BAM_BAD_RECORD == BAM_BAD_RECORD &&
+                  NTEDIT_BAM_BAD_SIZE == BAM_BAD_SIZE,
+              "the header names the grammar's rules");
+static_assert(sizeof(ntedit_hip_reads_bam_result) == sizeof(BamResult), "the result is the grammar's, field for field");
+
+struct BamInfo // the small result the device keeps per chunk
+{
+	u32 hdr_status, n_ref;
+	u64 header_len;
+	u32 broken, cut, rewalked, reserved;
+	u64 records, kept, skipped_flag, skipped_short;
+};
+
+struct SegTables // per segment
+{
+	u32 *guess, *exit, *count, *status, *valid;
+	u32* table; // cap offsets per segment
+	u64* pack;  // (kept records << 32 | text bytes) of the segment, then their exclusive scan; [nseg]: the totals
+};
+
+__global__ void
+k_bam_header(const u8* __restrict__ raw, u32 n, BamInfo* info)
+{
+	if (threadIdx.x == 0 && blockIdx.x == 0) {
+		u64 len = 0;
+		u32 refs = 0;
+		info->hdr_status = bam_header(raw, n, &len, &refs);
+		info->header_len = len;
+		info->n_ref = refs;
+	}
+}
+
+__global__ __launch_bounds__(BAM_TPB) void
+k_bam_walk(const u8* __restrict__ raw, u32 n, u32 seg_bytes, u32 nseg, u32 entry, u32 cap, SegTables t)
+{
+	const u32 lane = threadIdx.x & 63, seg = blockIdx.x * BAM_WAVES + (threadIdx.x >> 6);
+	if (seg >= nseg) {
+		return;
+	}
+	const u64 a64 = (u64)seg * seg_bytes, b64 = a64 + seg_bytes;
+	const u32 a = (u32)a64, b = b64 < n ? (u32)b64 : n;
+	u32 g = BAM_NO_GUESS;
+	if (entry >= b) {
+		// in front of the true entry: nothing starts here
+	} else if (entry >= a) {
+		g = entry;
+	} else {
+		for (u32 base = a; base < b && g == BAM_NO_GUESS; base += 64) {
+			const u32 q = base + lane;
+			BamRecord r;
+			const bool ok = q < b && bam_hop(raw, n, q, &r) == BAM_NEXT;
+			u64 m = __ballot(ok);
+			while (m) { // (uniform: every lane follows the same candidate)
+				const u32 i = (u32)__ffsll((unsigned long long)m) - 1;
+				m &= m - 1;
+				if (bam_guess_ok(raw, n, base + i)) {
+					g = base + i;
+					break;
+				}
+			}
+		}
+	}
+	if (lane == 0) {
+		u32 count = 0, exit = 0, st = BAM_NEXT;
+		if (g != BAM_NO_GUESS) {
+			st = bam_walk(raw, n, g, b, t.table + (u64)seg * cap, cap, &count, &exit);
+		}
+		t.guess[seg] = g;
+		t.exit[seg] = exit;
+		t.count[seg] = count;
+		t.status[seg] = st;
+	}
+}
+
+__global__ __launch_bounds__(64) void
+k_bam_stitch(const u8* __restrict__ raw, u32 n, u32 seg_bytes, u32 nseg, u32 entry, u32 cap, SegTables t, BamInfo* info)
+{
+	__shared__ u32 s_guess[BAM_WINDOW], s_exit[BAM_WINDOW], s_status[BAM_WINDOW];
+	__shared__ u32 s_cur, s_done;
+	const u32 lane = threadIdx.x;
+	if (lane == 0) {
+		s_cur = entry;
+		s_done = 0;
+	}
+	__syncthreads();
+	u32 rewalked = 0;
+	for (;;) {
+		const u32 cur = s_cur;
+		if (s_done) {
+			break;
+		}
+		if (cur >= n) { // the chain ends with the chunk
+			if (lane == 0) {
+				info->cut = n;
+			}
+			break;
+		}
+		const u32 w0 = cur / seg_bytes;
+		if (w0 + lane < nseg) {
+			s_guess[lane] = t.guess[w0 + lane];
+			s_exit[lane] = t.exit[w0 + lane];
+			s_status[lane] = t.status[w0 + lane];
+		}
+		__syncthreads();
+		if (lane == 0) {
+			u32 p = cur;
+			while (p < n) {
+				const u32 seg = p / seg_bytes;
+				if (seg >= w0 + BAM_WINDOW) {
+					break;
+				}
+				u32 st, next;
+				if (s_guess[seg - w0] == p) {
+					st = s_status[seg - w0];
+					next = s_exit[seg - w0];
+				} else {
+					const u64 b64 = ((u64)seg + 1) * seg_bytes;
+					u32 count = 0;
+					st = bam_walk(raw, n, p, b64 < n ? (u32)b64 : n, t.table + (u64)seg * cap, cap, &count, &next);
+					t.count[seg] = count;
+					rewalked++;
+				}
+				t.valid[seg] = 1;
+				p = next;
+				if (st != BAM_NEXT) {
+					info->cut = next; // the first record not completely inside, or the unclean one
+					info->broken = st == BAM_END ? 0 : st;
+					s_done = 1;
+					break;
+				}
+			}
+			s_cur = p;
+		}
+		__syncthreads();
+	}
+	if (lane == 0) {
+		info->rewalked = rewalked;
+	}
+}
+
+__device__ __forceinline__ u64
+wave_sum(u64 v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		v += __shfl_xor(v, d, 64);
+	}
+	return v;
+}
+
+__global__ __launch_bounds__(BAM_TPB) void
+k_bam_sums(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, SegTables t, BamInfo* info)
+{
+	const u32 lane = threadIdx.x & 63, seg = blockIdx.x * BAM_WAVES + (threadIdx.x >> 6);
+	if (seg >= nseg) {
+		return;
+	}
+	const u32 count = t.valid[seg] ? t.count[seg] : 0;
+	u64 kept = 0, text = 0, by_flag = 0, by_len = 0;
+	for (u32 j = lane; j < count; j += 64) {
+		BamRecord r;
+		(void)bam_hop(raw, n, t.table[(u64)seg * cap + j], &r); // (BAM_NEXT: the walk stored it)
+		if (r.flag & 0x900u) {
+			by_flag++;
+		} else if (r.l_seq < min_len) {
+			by_len++;
+		} else {
+			kept++;
+			text += (u64)r.l_seq + 1;
+		}
+	}
+	kept = wave_sum(kept);
+	text = wave_sum(text);
+	by_flag = wave_sum(by_flag);
+	by_len = wave_sum(by_len);
+	if (lane == 0) {
+		t.pack[seg] = kept << 32 | text;
+		if (count) {
+			atomicAdd((unsigned long long*)&info->records, (unsigned long long)count);
+			atomicAdd((unsigned long long*)&info->kept, (unsigned long long)kept);
+			atomicAdd((unsigned long long*)&info->skipped_flag, (unsigned long long)by_flag);
+			atomicAdd((unsigned long long*)&info->skipped_short, (unsigned long long)by_len);
+		}
+	}
+}
+
+// pack[0 .. nseg) to its exclusive scan in place, pack[nseg] = the totals; krec_text[kept] = the text's length
+__global__ __launch_bounds__(BAM_TPB) void
+k_bam_scan(u64* pack, u32 nseg, u32* krec_text)
+{
+	__shared__ u64 s[BAM_TPB];
+	const u32 tid = threadIdx.x;
+	u64 carry = 0;
+	for (u32 base = 0; base < nseg; base += BAM_TPB) {
+		const u64 v = base + tid < nseg ? pack[base + tid] : 0;
+		s[tid] = v;
+		__syncthreads();
+		for (u32 d = 1; d < BAM_TPB; d <<= 1) {
+			const u64 add = tid >= d ? s[tid - d] : 0;
+			__syncthreads();
+			s[tid] += add;
+			__syncthreads();
+		}
+		if (base + tid < nseg) {
+			pack[base + tid] = carry + s[tid] - v;
+		}
+		carry += s[BAM_TPB - 1];
+		__syncthreads();
+	}
+	if (tid == 0) {
+		pack[nseg] = carry;
+		krec_text[carry >> 32] = (u32)carry;
+	}
+}
+
+__global__ __launch_bounds__(BAM_TPB) void
+k_bam_compact(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, SegTables t, u32* __restrict__ krec_seq,
+              u32* __restrict__ krec_text)
+{
+	const u32 lane = threadIdx.x & 63, seg = blockIdx.x * BAM_WAVES + (threadIdx.x >> 6);
+	if (seg >= nseg) {
+		return;
+	}
+	const u32 count = t.valid[seg] ? t.count[seg] : 0;
+	u32 kb = (u32)(t.pack[seg] >> 32), tb = (u32)t.pack[seg];
+	for (u32 j0 = 0; j0 < count; j0 += 64) {
+		const u32 j = j0 + lane;
+		BamRecord r = BamRecord();
+		bool keep = false;
+		if (j < count) {
+			(void)bam_hop(raw, n, t.table[(u64)seg * cap + j], &r);
+			keep = bam_kept(r.flag, r.l_seq, min_len);
+		}
+		const u32 len = keep ? r.l_seq + 1 : 0;
+		u32 ik = keep ? 1 : 0, il = len; // inclusive scans over the lanes
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const u32 uk = __shfl_up(ik, d, 64), ul = __shfl_up(il, d, 64);
+			if (lane >= (u32)d) {
+				ik += uk;
+				il += ul;
+			}
+		}
+		if (keep) {
+			krec_seq[kb + ik - 1] = r.seq_off;
+			krec_text[kb + ik - 1] = tb + il - len;
+		}
+		kb += __shfl(ik, 63, 64);
+		tb += __shfl(il, 63, 64);
+	}
+}
+
+__global__ __launch_bounds__(BAM_TPB) void
+k_bam_decode(const u8* __restrict__ raw, const u32* __restrict__ krec_seq, const u32* __restrict__ krec_text, u32 kept, u8* text,
+             u32 text_len)
+{
+	const u64 t0 = ((u64)blockIdx.x * BAM_TPB + threadIdx.x) * 16;
+	if (t0 >= text_len) {
+		return;
+	}
+	// the last record whose text starts at or before t0 (text offsets rise strictly: every kept record has its '\n')
+	u32 lo = 0, hi = kept;
+	while (hi - lo > 1) {
+		const u32 mid = lo + (hi - lo) / 2;
+		if (krec_text[mid] <= (u32)t0) {
+			lo = mid;
+		} else {
+			hi = mid;
+		}
+	}
+	u32 rec = lo, start = krec_text[rec], end = krec_text[rec + 1], seq = krec_seq[rec];
+	const u32 todo = text_len - (u32)t0 < 16 ? text_len - (u32)t0 : 16;
+	u32 w[4] = { 0, 0, 0, 0 };
+	for (u32 i = 0; i < todo; i++) {
+		const u32 at = (u32)t0 + i;
+		if (at == end) {
+			rec++;
+			start = end;
+			end = krec_text[rec + 1];
+			seq = krec_seq[rec];
+		}
+		const u32 ch = at + 1 == end ? (u32)'\n' : (u32)(u8)bam_base(raw, seq, at - start);
+		w[i >> 2] |= ch << ((i & 3) * 8);
+	}
+	if (todo == 16) {
+		*(uint4*)(text + t0) = make_uint4(w[0], w[1], w[2], w[3]);
+	} else {
+		for (u32 i = 0; i < todo; i++) {
+			text[t0 + i] = (u8)(w[i >> 2] >> ((i & 3) * 8));
+		}
+	}
+}
+
+// ------------------------------------------------------------------ host side
+struct BamState
+{
+	const ntedit_hip_ctx* owner = nullptr;
+	ntedit_hip_reads_bam_stats info = {};
+	u64 segment = 0; // ntedit_hip_reads_bam_set_segment (0: the default)
+	int device = -1;
+	hipStream_t stream = nullptr; // the parse unit's
+	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+	// device scratch, grow-only, released by ntedit_hip_sketch_free
+	u8* d_seg = nullptr; // the per-segment arrays and the table
+	u64 seg_cap = 0;
+	u8* d_rec = nullptr; // the kept records' two arrays
+	u64 rec_cap = 0;
+	u8* d_in = nullptr; // a chunk given as host bytes
+	u64 in_cap = 0;
+	BamInfo* d_info = nullptr;
+	BamInfo* h_info = nullptr; // page-locked
+	u64* h_total = nullptr;    // page-locked
+};
+
+std::mutex g_bam_mu;
+std::vector<BamState*> g_bam;
+
+BamState*
+bam_state(const ntedit_hip_ctx* c, bool create)
+{
+	std::lock_guard<std::mutex> lk(g_bam_mu);
+	for (BamState* s : g_bam) {
+		if (s->owner == c) {
+			return s;
+		}
+	}
+	if (!create) {
+		return nullptr;
+	}
+	BamState* s = new BamState();
+	s->owner = c;
+	g_bam.push_back(s);
+	return s;
+}
+
+int
+pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
+{
+	return nte_reads::set_error(c, code, why);
+}
+
+#define BAM_TRY(ctx, expr)                                                                        \
+	do {                                                                                          \
+		hipError_t e_ = (expr);                                                                   \
+		if (e_ != hipSuccess) {                                                                   \
+			return pfail((ctx), NTEDIT_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
+		}                                                                                         \
+	} while (0)
+
+int
+ensure_device(const ntedit_hip_ctx* c, BamState* s)
+{
+	if (s->device >= 0) {
+		BAM_TRY(c, hipSetDevice(s->device));
+		return 0;
+	}
+	void *stream = nullptr, *copy_stream = nullptr;
+	const int rc = nte_reads::parse_streams(c, &stream, &copy_stream);
+	if (rc) {
+		return rc;
+	}
+	int device = 0;
+	BAM_TRY(c, hipGetDevice(&device));
+	s->stream = (hipStream_t)stream;
+	for (hipEvent_t& e : s->ev) {
+		BAM_TRY(c, hipEventCreate(&e));
+	}
+	BAM_TRY(c, hipMalloc((void**)&s->d_info, sizeof(BamInfo)));
+	BAM_TRY(c, hipHostMalloc((void**)&s->h_info, sizeof(BamInfo), hipHostMallocDefault));
+	BAM_TRY(c, hipHostMalloc((void**)&s->h_total, sizeof(u64), hipHostMallocDefault));
+	s->device = device;
+	return 0;
+}
+
+int
+grow(const ntedit_hip_ctx* c, BamState* s, u8** p, u64* cap, u64 need)
+{
+	if (need <= *cap && *p) {
+		return 0;
+	}
+	if (*p) {
+		BAM_TRY(c, hipStreamSynchronize(s->stream));
+		BAM_TRY(c, hipFree(*p));
+		*p = nullptr;
+		*cap = 0;
+	}
+	const u64 want = (need + need / 4 + (1u << 16)) / 256 * 256;
+	BAM_TRY(c, hipMalloc((void**)p, want));
+	*cap = want;
+	return 0;
+}
+
+void
+release_scratch(BamState* s)
+{
+	if (s->device < 0) {
+		return;
+	}
+	(void)hipSetDevice(s->device);
+	if (s->stream) {
+		(void)hipStreamSynchronize(s->stream);
+	}
+	for (hipEvent_t e : s->ev) {
+		if (e) {
+			(void)hipEventDestroy(e);
+		}
+	}
+	for (void* p : { (void*)s->d_seg, (void*)s->d_rec, (void*)s->d_in, (void*)s->d_info }) {
+		if (p) {
+			(void)hipFree(p);
+		}
+	}
+	for (void* p : { (void*)s->h_info, (void*)s->h_total }) {
+		if (p) {
+			(void)hipHostFree(p);
+		}
+	}
+	const ntedit_hip_ctx* owner = s->owner;
+	const ntedit_hip_reads_bam_stats info = s->info;
+	const u64 segment = s->segment;
+	*s = BamState();
+	s->owner = owner;
+	s->info = info;
+	s->segment = segment;
+}
+
+u64
+up256(u64 x)
+{
+	return (x + 255) / 256 * 256;
+}
+
+// the per-segment arrays of nseg segments with `cap` table slots each, carved from one allocation
+SegTables
+carve(u8* base, u64 nseg, u64 cap, u64* bytes)
+{
+	SegTables t;
+	u64 at = 0;
+	auto take = [&](u64 n) {
+		u8* p = base + at;
+		at += up256(n);
+		return p;
+	};
+	t.guess = (u32*)take(nseg * 4);
+	t.exit = (u32*)take(nseg * 4);
+	t.count = (u32*)take(nseg * 4);
+	t.status = (u32*)take(nseg * 4);
+	t.valid = (u32*)take(nseg * 4);
+	t.pack = (u64*)take((nseg + 1) * 8);
+	t.table = (u32*)take(nseg * cap * 4);
+	*bytes = at;
+	return t;
+}
+
+void
+to_result(const BamResult& r, ntedit_hip_reads_bam_result* res)
+{
+	memcpy(res, &r, sizeof r);
+}
+
+// one chunk of device bytes: the walk, then the decode of the records before the cut
+int
+bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, int at_header, u32 min_len, u8* d_text, u64 text_cap,
+              ntedit_hip_reads_bam_result* res)
+{
+	BamResult out = BamResult();
+	if (n64 >= BAM_MAX_RAW) {
+		to_result(bam_unclean(BAM_BAD_SIZE, 0), res);
+		return 0;
+	}
+	out.clean = 1;
+	if (n64 == 0) {
+		to_result(out, res);
+		return 0;
+	}
+	const u32 n = (u32)n64;
+	float ms = 0;
+	BAM_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(BamInfo), s->stream));
+	u32 entry = 0;
+	if (at_header) {
+		hipLaunchKernelGGL(k_bam_header, dim3(1), dim3(64), 0, s->stream, d_raw, n, s->d_info);
+		BAM_TRY(c, hipGetLastError());
+		BAM_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(BamInfo), hipMemcpyDeviceToHost, s->stream));
+		BAM_TRY(c, hipStreamSynchronize(s->stream));
+		const u32 st = s->h_info->hdr_status;
+		if (st != BAM_NEXT) {
+			to_result(st == BAM_END ? out : bam_unclean(st, 0), res); // (BAM_END: cut 0, the chunk grows)
+			return 0;
+		}
+		out.header_len = s->h_info->header_len;
+		out.n_ref = s->h_info->n_ref;
+		entry = (u32)out.header_len; // (inside the chunk: at most n)
+	}
+	u64 seg_bytes = s->segment ? s->segment : (u64)NTEDIT_BAM_SEGMENT;
+	seg_bytes = seg_bytes > n ? n : seg_bytes;
+	seg_bytes = seg_bytes < 64 ? 64 : seg_bytes;
+	const u32 nseg = (u32)((n + seg_bytes - 1) / seg_bytes), cap = bam_slice_cap((u32)seg_bytes);
+	u64 bytes = 0;
+	(void)carve(nullptr, nseg, cap, &bytes);
+	int rc = grow(c, s, &s->d_seg, &s->seg_cap, bytes);
+	if (rc) {
+		return rc;
+	}
+	const SegTables t = carve(s->d_seg, nseg, cap, &bytes);
+	const unsigned seg_blocks = (nseg + BAM_WAVES - 1) / BAM_WAVES;
+	// ms_walk: the walk and the stitch (the header kernel, one lane once per file, and its round trip to the host are not in it)
+	BAM_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	BAM_TRY(c, hipMemsetAsync(t.valid, 0, (u64)nseg * 4, s->stream));
+	hipLaunchKernelGGL(k_bam_walk, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, (u32)seg_bytes, nseg, entry, cap, t);
+	hipLaunchKernelGGL(k_bam_stitch, dim3(1), dim3(64), 0, s->stream, d_raw, n, (u32)seg_bytes, nseg, entry, cap, t, s->d_info);
+	BAM_TRY(c, hipGetLastError());
+	BAM_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	// the lengths of the records on the chain (a chunk that turns out unclean has paid for them: it fails the pass anyway)
+	BAM_TRY(c, hipEventRecord(s->ev[2], s->stream));
+	const u64 max_records = (u64)n / BAM_MIN_RECORD + 2;
+	if ((rc = grow(c, s, &s->d_rec, &s->rec_cap, 2 * up256(max_records * 4))) != 0) {
+		return rc;
+	}
+	u32 *krec_seq = (u32*)s->d_rec, *krec_text = (u32*)(s->d_rec + up256(max_records * 4));
+	hipLaunchKernelGGL(k_bam_sums, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, s->d_info);
+	hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(BAM_TPB), 0, s->stream, t.pack, nseg, krec_text);
+	BAM_TRY(c, hipGetLastError());
+	BAM_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(BamInfo), hipMemcpyDeviceToHost, s->stream));
+	BAM_TRY(c, hipMemcpyAsync(s->h_total, t.pack + nseg, sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+	BAM_TRY(c, hipStreamSynchronize(s->stream));
+	BAM_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	s->info.ms_walk += ms;
+	s->info.chunks++;
+	s->info.segments += nseg;
+	s->info.rewalked += s->h_info->rewalked;
+	if (s->h_info->broken) {
+		to_result(bam_unclean(s->h_info->broken, s->h_info->cut), res);
+		return 0;
+	}
+	out.cut = s->h_info->cut;
+	out.records = s->h_info->records;
+	out.kept = s->h_info->kept;
+	out.skipped_flag = s->h_info->skipped_flag;
+	out.skipped_short = s->h_info->skipped_short;
+	out.text_len = (u32)*s->h_total;
+	out.bases = out.text_len - out.kept;
+	if (out.kept != *s->h_total >> 32 || out.text_len > text_cap) {
+		return pfail(c, NTEDIT_E_DEVICE, "reads_bam: the text does not fit its buffer");
+	}
+	if (out.text_len) {
+		hipLaunchKernelGGL(k_bam_compact, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, krec_seq, krec_text);
+		const unsigned blocks = (unsigned)((out.text_len + BAM_TPB * 16 - 1) / (BAM_TPB * 16));
+		hipLaunchKernelGGL(k_bam_decode, dim3(blocks), dim3(BAM_TPB), 0, s->stream, d_raw, krec_seq, krec_text, (u32)out.kept, d_text,
+		                   (u32)out.text_len);
+		BAM_TRY(c, hipGetLastError());
+	}
+	BAM_TRY(c, hipEventRecord(s->ev[3], s->stream));
+	BAM_TRY(c, hipStreamSynchronize(s->stream));
+	BAM_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+	s->info.ms_decode += ms;
+	s->info.records += out.records;
+	s->info.kept += out.kept;
+	s->info.skipped_flag += out.skipped_flag;
+	s->info.skipped_short += out.skipped_short;
+	to_result(out, res);
+	return 0;
+}
+
+} // namespace
+
+// what the pass loop of reads_pass.cpp needs beyond the public calls
+namespace nte_reads {
+
+void
+bam_release(const ntedit_hip_ctx* c)
+{
+	BamState* s = bam_state(c, false);
+	if (s) {
+		release_scratch(s);
+	}
+}
+
+ntedit_hip_reads_bam_stats*
+bam_info(const ntedit_hip_ctx* c)
+{
+	return &bam_state(c, true)->info;
+}
+
+// the first n bytes of the inflated chunk d_raw: walked, and the records before the cut decoded into the context's text
+// buffer (the one parse_buffer fills)
+int
+bam_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, int at_header, uint32_t min_len, const char** text,
+           ntedit_hip_reads_bam_result* res)
+{
+	BamState* s = bam_state(c, true);
+	int rc = ensure_device(c, s);
+	char* d_text = nullptr;
+	uint64_t cap = 0;
+	if (rc == 0) {
+		rc = parse_text_buffer(c, n, &d_text, &cap);
+	}
+	if (rc) {
+		return rc;
+	}
+	*text = d_text;
+	return bam_on_device(c, s, (const u8*)d_raw, n, at_header, min_len, (u8*)d_text, cap, res);
+}
+
+} // namespace nte_reads
+
+extern "C" {
+
+int
+ntedit_hip_reads_is_bam(const char* path)
+{
+	if (!path) {
+		return 0;
+	}
+	std::vector<u8> buf(65536 + 4096); // (a member is at most 64 KiB)
+	FILE* fp = fopen(path, "rb");
+	const size_t got = fp ? fread(buf.data(), 1, buf.size(), fp) : 0;
+	if (fp) {
+		fclose(fp);
+	}
+	return bam_starts_bam(buf.data(), got) ? 1 : 0;
+}
+
+int
+ntedit_hip_reads_bam_set_segment(ntedit_hip_ctx* c, uint64_t bytes)
+{
+	if (!c || (bytes && bytes < 64)) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_set_segment: a segment has at least 64 bytes") : NTEDIT_E_ARG;
+	}
+	bam_state(c, true)->segment = bytes;
+	return 0;
+}
+
+int
+ntedit_hip_reads_bam_info(ntedit_hip_ctx* c, ntedit_hip_reads_bam_stats* st)
+{
+	if (!c || !st) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_info: bad argument") : NTEDIT_E_ARG;
+	}
+	*st = bam_state(c, true)->info;
+	return 0;
+}
+
+int
+ntedit_hip_reads_bam_device(ntedit_hip_ctx* c, const void* raw, uint64_t n_raw, int on_device, int at_header, uint32_t min_len,
+                            char* text_device, uint64_t text_cap, ntedit_hip_reads_bam_result* res)
+{
+	if (!c || !res || (n_raw && (!raw || !text_device)) || text_cap < n_raw || ((uintptr_t)text_device & 15) ||
+	    (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) ||
+	    (on_device == NTEDIT_HIP_BASES_DEVICE && ((uintptr_t)raw & 15))) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_device: bad argument") : NTEDIT_E_ARG;
+	}
+	BamState* s = bam_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc) {
+		return rc;
+	}
+	const u8* d_raw = (const u8*)raw;
+	if (on_device == NTEDIT_HIP_BASES_HOST && n_raw && n_raw < BAM_MAX_RAW) {
+		if ((rc = grow(c, s, &s->d_in, &s->in_cap, n_raw)) != 0) {
+			return rc;
+		}
+		BAM_TRY(c, hipMemcpyAsync(s->d_in, raw, n_raw, hipMemcpyHostToDevice, s->stream));
+		d_raw = s->d_in;
+	}
+	return bam_on_device(c, s, d_raw, n_raw, at_header, min_len, (u8*)text_device, text_cap, res);
+}
+
+int
+ntedit_hip_reads_bam_model(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, char* out, uint64_t cap,
+                           ntedit_hip_reads_bam_result* res)
+{
+	if (!res || (n_raw && !raw) || (cap && !out)) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_bam_model: bad argument");
+	}
+	BamResult r;
+	bam_model((const u8*)raw, n_raw, at_header, min_len, out, cap, &r);
+	to_result(r, res);
+	if (r.clean && r.text_len > cap) {
+		return pfail(nullptr, NTEDIT_E_OVERFLOW, "reads_bam_model: the text does not fit the buffer");
+	}
+	return 0;
+}
+
+} // extern "C"

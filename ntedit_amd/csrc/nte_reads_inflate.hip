@@ -33,6 +33,7 @@ int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
 int parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream);
 int parse_lines(const ntedit_hip_ctx* c, const unsigned char* d_raw, uint64_t n, const uint32_t** line_end, uint64_t* n_lines,
                 uint32_t* broken);
+void bam_release(const ntedit_hip_ctx* c);
 }
 
 namespace {
@@ -333,6 +334,7 @@ namespace nte_reads {
 void
 inflate_release(const ntedit_hip_ctx* c)
 {
+	bam_release(c); // (nte_reads_bam.hip works on the same streams, behind this unit's chunks)
 	InflateState* s = inflate_state(c, false);
 	if (s) {
 		release_scratch(s);

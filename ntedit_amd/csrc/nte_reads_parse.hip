@@ -924,6 +924,23 @@ parse_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint32_t k,
 	return parse_on_device(c, s, (const u8*)d_raw, n, k, s->d_text, s->text_cap, res);
 }
 
+// the BAM unit (nte_reads_bam.hip) decodes into the same text buffer: room for a chunk of n raw bytes
+int
+parse_text_buffer(const ntedit_hip_ctx* c, uint64_t n, char** text, uint64_t* cap)
+{
+	ParseState* s = parse_state(c, true);
+	int rc = ensure_device(c, s);
+	if (rc == 0) {
+		rc = grow(c, &s->d_text, &s->text_cap, n);
+	}
+	if (rc) {
+		return rc;
+	}
+	*text = (char*)s->d_text;
+	*cap = s->text_cap;
+	return 0;
+}
+
 // ------------------------------------------------------------------ what genome_pass.cpp needs
 // The pass's text buffer: GP_PAD bytes that end with the last k - 1 text bytes of the file so far ('\n' before them),
 // then the chunk's text; the whole is one device batch for ntedit_hip_filter_insert.

@@ -54,7 +54,8 @@ usage(const char* why)
 	       "ntCard nor ntStat: --solid's cutoff is the first c with f[c+1] > f[c], this tool's own rule, not a model fit.\n\n"
 	       "Optional arguments:\n"
 	       "  -h, --help      shows help message and exits\n"
-	       "  --reads         Input reads, FASTA or FASTQ, plain or gzip [nargs: 1 or more] [required]\n"
+	       "  --reads         Input reads, FASTA or FASTQ, plain or gzip, or BAM, unaligned or aligned (BAM needs\n"
+	       "                  --gpu_parse) [nargs: 1 or more] [required]\n"
 	       "  -k              k-mer size (bp), 12 to 200 [required]\n"
 	       "  -c              Minimum k-mer count (cmin), 1 to 255 [required, unless --solid]\n"
 	       "  --solid         Take cmin from the k-mer histogram: the first c with f[c+1] > f[c] (the valley after\n"
@@ -73,7 +74,8 @@ usage(const char* why)
 	       "  --gpu_parse     Parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes,\n"
 	       "                  BGZF still compressed, and the device inflates them.  The output is the same; single-stream\n"
 	       "                  gzip files and files outside the clean FASTA / 4-line FASTQ grammar stay with the host\n"
-	       "                  parser (recompress with `bgzip -@ 16 reads.fq`)\n"
+	       "                  parser (recompress with `bgzip -@ 16 reads.fq`).  BAM files are inflated, walked and decoded\n"
+	       "                  on the device: every primary record's bases (flags 0x100 and 0x800 are left out), as stored\n"
 	       "  -o              Name for output filter [default: \"reads_k<K>.bf\"]\n"
 	       "  -t              Number of threads (accepted; the k-mers are counted on the GPU) [default: 12]\n"
 	       "  --reject_cutoff Also write the reject filter for ntedit -e (k-mers to reject, e.g. repeats): a plain filter of\n"

@@ -93,6 +93,13 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 	if (!final) {
 		return 0;
 	}
+	// a BAM has no host parser (kseq would read whatever '@' and '>' bytes the binary stream holds): one line, the same in
+	// both dialects
+	for (uint32_t i = 0; !o->gpu_parse && i < o->n_files; i++) {
+		if (o->files[i] && ntedit_hip_reads_is_bam(o->files[i])) {
+			return refuse(NTEDIT_READS_REFUSED, std::string("--reads ") + o->files[i] + ": BAM needs --gpu_parse");
+		}
+	}
 	// the rules between the options
 	if (o->cutoff && o->solid) {
 		return refuse(NTEDIT_READS_REFUSED, (tool ? "--solid and -c" : "--cutoff and --solid") +

@@ -52,6 +52,10 @@ int inflate_copied(const ntedit_hip_ctx* c, int which, uint64_t n_comp, const nt
                    uint64_t tail, uint64_t n_out, const char** raw, uint64_t* bad, uint32_t* reason);
 int inflate_last_start(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint64_t* cut, uint32_t* broken);
 int inflate_carry(const ntedit_hip_ctx* c, uint64_t cut, uint64_t total);
+// ... and on BAM files (nte_reads_bam.hip): its counters, and the walk and decode of an inflated chunk
+ntedit_hip_reads_bam_stats* bam_info(const ntedit_hip_ctx* c);
+int bam_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, int at_header, uint32_t min_len, const char** text,
+               ntedit_hip_reads_bam_result* res);
 }
 
 namespace {
@@ -885,6 +889,11 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 		}
 	};
 	if (!nte_reads::parse_is_on(ctx)) {
+		for (const Range& r : ranges) { // (the host parser would read whatever '@' and '>' bytes the binary stream holds)
+			if (ntedit_hip_reads_is_bam(r.path)) {
+				return pfail(ctx, NTEDIT_E_ARG, std::string("--reads ") + r.path + ": BAM needs --gpu_parse");
+			}
+		}
 		const int rc = host_pass(ranges, starts, nexts);
 		if (rc) {
 			return rc;
@@ -894,6 +903,8 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 		info = ntedit_hip_reads_parse_stats();
 		ntedit_hip_reads_inflate_stats& zinfo = *nte_reads::inflate_info(ctx);
 		zinfo = ntedit_hip_reads_inflate_stats();
+		ntedit_hip_reads_bam_stats& binfo = *nte_reads::bam_info(ctx);
+		binfo = ntedit_hip_reads_bam_stats();
 		for (uint32_t i = 0; i < n; i++) {
 			const Range& r = ranges[i];
 			struct stat sb;
@@ -902,6 +913,16 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 				// a BGZF file, whole: shipped compressed, inflated and cut on the device.  `base` is the inflated
 				// offset of the raw buffer's first byte, always a record start; `tail` the bytes carried behind a cut.
 				zinfo.files++;
+				// a BAM takes the same loop: its walk in place of the last record start, its decode in place of the
+				// text parser.  There is no host parser to hand it back to: what the BGZF path hands back fails the pass.
+				const bool bam = ntedit_hip_reads_is_bam(r.path) != 0;
+				bool bam_header_done = false;
+				auto bam_fail = [&](const std::string& what, uint64_t at) {
+					return pfail(ctx, NTEDIT_E_IO, std::string(r.path) + ": BAM: " + what + " at inflated offset " + std::to_string(at));
+				};
+				if (bam) {
+					binfo.files++;
+				}
 				uint64_t base = 0, tail = 0;
 				bool handed_back = false;
 				{
@@ -943,7 +964,7 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 							                                   " is damaged (" + nte_reads::inflate_reason(reason) + ")");
 						}
 						// the chunk's cut: the end of the file's bytes, else the last record start on the device
-						if (rc == 0) {
+						if (rc == 0 && !bam) {
 							if (last && whole) {
 								cut = total;
 							} else {
@@ -953,7 +974,15 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 						ntedit_hip_reads_parse_result res = ntedit_hip_reads_parse_result();
 						res.clean = 1;
 						const char* text = nullptr;
-						if (rc == 0 && broken) {
+						ntedit_hip_reads_bam_result bres = ntedit_hip_reads_bam_result();
+						if (rc == 0 && bam) {
+							// the first record that does not lie completely inside is the cut; the records before it are the text
+							rc = nte_reads::bam_buffer(ctx, raw, total, bam_header_done ? 0 : 1, keep, &text, &bres);
+							res.clean = bres.clean;
+							res.text_len = bres.text_len;
+							res.bases = bres.bases;
+							cut = bres.cut;
+						} else if (rc == 0 && broken) {
 							res.clean = 0;
 							res.broken = broken;
 						} else if (rc == 0 && cut) {
@@ -967,6 +996,14 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 							return pfail(ctx, rc, ntedit_hip_reads_last_error(ctx));
 						}
 						gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
+						if (bam && !res.clean) {
+							(void)nte_reads::inflate_copy_wait(ctx, which ^ 1);
+							return bam_fail(bres.broken & NTEDIT_BAM_BAD_MAGIC    ? "the header does not start with the BAM magic"
+							                : bres.broken & NTEDIT_BAM_BAD_HEADER ? "a header with a negative length or an empty reference name"
+							                : bres.broken & NTEDIT_BAM_BAD_SIZE   ? "a record with a block_size outside [0, 2^30), or a chunk of 2 GiB"
+							                                                      : "a record whose parts do not fit its block_size",
+							                base + bres.cut);
+						}
 						if (!res.clean) {
 							info.fallback_chunks++;
 							info.broken |= res.broken;
@@ -974,10 +1011,12 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 							(void)nte_reads::inflate_copy_wait(ctx, which ^ 1); // (before the feeder frees the buffer it reads)
 							break;
 						}
-						if (cut) {
+						if (cut && !bam) { // (a BAM's chunks are the BAM counters': the text parser saw none of them)
 							info.device_chunks++;
 							info.raw_bytes += cut;
 							info.text_bytes += res.text_len;
+						}
+						if (cut) {
 							bases += res.bases;
 						}
 						// a chunk without a record start past its first byte grows by the next one (cut = 0: all is tail)
@@ -987,6 +1026,14 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 						}
 						base += cut;
 						tail = total - cut;
+						bam_header_done = bam_header_done || cut > 0; // (a header that does not fit gives cut 0)
+						if (bam && last && !whole) {
+							return bam_fail("what follows the last whole BGZF member is not one (a damaged or truncated file); the records end",
+							                base);
+						}
+						if (bam && last && tail) {
+							return bam_fail(std::to_string(tail) + " bytes are left over behind the last whole record (a truncated file)", base);
+						}
 						if (last && !whole) {
 							handed_back = true; // what follows the members is not BGZF: the host parser's, from `base`
 						}
@@ -1010,6 +1057,9 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 					nexts[i] = base;
 				}
 				continue;
+			}
+			if (regular && ntedit_hip_reads_is_bam(r.path)) {
+				return pfail(ctx, NTEDIT_E_ARG, std::string(r.path) + ": a BAM file is read whole, not in ranges");
 			}
 			if (!regular || is_gzip(r.path)) { // a gzip file (or what the host parser will refuse in its own words)
 				info.host_files++;
@@ -1282,6 +1332,17 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 			}
 			l += "; " + std::to_string(ps.host_files) + " gzip inputs stay with the host parser";
 			lg.rank_info(l);
+		}
+		ntedit_hip_reads_bam_stats bs;
+		if (ntedit_hip_reads_bam_info(ctx, &bs) == 0 && bs.files) {
+			// ... and one about its BAM inputs (the tests read it)
+			l = "--gpu_parse: BAM: " + std::to_string(bs.records) + " records of " + std::to_string(bs.files) +
+			    (bs.files == 1 ? " file" : " files") + " walked on the device (" + std::to_string(bs.kept) + " kept, " +
+			    std::to_string(bs.skipped_flag) + " secondary or supplementary, " + std::to_string(bs.skipped_short) + " too short; " +
+			    std::to_string(bs.chunks) + " chunks, " + std::to_string(bs.segments) + " segments, " + std::to_string(bs.rewalked) +
+			    " walked again by the stitch, ";
+			snprintf(line, sizeof line, "%.1f ms in the walk kernels, %.1f ms in the decode kernels)", bs.ms_walk, bs.ms_decode);
+			lg.rank_info(l + line);
 		}
 	}
 	return 0;

@@ -45,7 +45,8 @@ USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR 
          "                  the same pass 2; --reject_bf / --reject_num_elements size it, --reject_out names it\n"
          "                  [default: reads_k<K>_reject.bf]\n"
          "  --gpu_parse     parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes,\n"
-         "                  BGZF still compressed; same output (single-stream gzip stays with the host parser)\n"
+         "                  BGZF still compressed; same output (single-stream gzip stays with the host parser).  BAM files,\n"
+         "                  unaligned or aligned, need it; a BAM is read whole by one process, as gzip files are\n"
          "  --backend       torch.distributed backend (default nccl = RCCL; gloo: N ranks may share a GPU)\n"
          "ntedit-make-reads-bf --help describes the other flags.\n")
 
@@ -369,6 +370,12 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
                 parsed[key]["bgzf"] = dict(files=zs.files, members=zs.members, compressed_bytes=zs.comp_bytes,
                                            inflated_bytes=zs.raw_bytes, kernel_ms=round(zs.ms_kernels, 3),
                                            handed_back=zs.handed_back)
+            bs = _lib.ReadsBamStats()  # ... and, of BAM inputs, what it walked and decoded there
+            if lib.ntedit_hip_reads_bam_info(b.h, bs) == 0 and bs.files:
+                parsed[key]["bam"] = dict(files=bs.files, chunks=bs.chunks, records=bs.records, kept=bs.kept,
+                                          skipped_flag=bs.skipped_flag, skipped_short=bs.skipped_short,
+                                          segments=bs.segments, rewalked=bs.rewalked, walk_ms=round(bs.ms_walk, 3),
+                                          decode_ms=round(bs.ms_decode, 3))
     try:
         k, hashes = a["k"], a["hashes"]
         counters = (sketch + 7) // 8 * 8

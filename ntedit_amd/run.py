@@ -290,7 +290,8 @@ def parse(argv=None):
                    help="read every input file whole (by one rank); gzip files always are")
     g.add_argument("--gpu_parse", action="store_true",
                    help="parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes, BGZF still "
-                        "compressed; same outputs (single-stream gzip stays with the host parser)")
+                        "compressed; same outputs (single-stream gzip stays with the host parser).  BAM reads, unaligned or "
+                        "aligned, need it; a BAM is read whole by one rank, as gzip files are")
     g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
     g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
     args = ap.parse_args(argv)
