@@ -9,7 +9,7 @@
 //                     the wave that inflated the member has its bytes in the caches, each lane takes a contiguous piece,
 //                     and the pieces are combined in GF(2).  One status word per member, an ordinary store.
 //   k_bz_last_start   the chunk cut: over the line table of nte_reads_parse.hip, the last record start by the rule of
-//                     last_record_start (reads_pass.cpp), an atomic max over the lines; 0: none.
+//                     last_record_start (host/chunk_feed.h), an atomic max over the lines; 0: none.
 //
 // Like nte_reads_parse.hip this unit is outside KSRC and sees no context internals: its state hangs off the context
 // pointer, its scratch grows only and goes with ntedit_hip_sketch_free.  It works on the parse unit's two streams.
@@ -17,6 +17,7 @@
 #include "nte_bgzf_inflate.h"
 
 #include "../../include/ntedit_hip.h"
+#include "../host/bgzf_walk.h"
 
 #include <hip/hip_runtime.h>
 
@@ -314,18 +315,6 @@ reason_text(u32 st)
 	return st < sizeof names / sizeof names[0] ? names[st] : "unknown";
 }
 
-uint32_t
-le16(const unsigned char* d)
-{
-	return (uint32_t)d[0] | (uint32_t)d[1] << 8;
-}
-
-uint32_t
-le32(const unsigned char* d)
-{
-	return le16(d) | le16(d + 2) << 16;
-}
-
 } // namespace
 
 // what the pass loop of reads_pass.cpp needs beyond the public calls
@@ -446,7 +435,7 @@ inflate_last_start(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint6
 	BZ_TRY(c, hipMemcpyAsync(&kind, d_raw, 1, hipMemcpyDeviceToHost, s->stream));
 	BZ_TRY(c, hipStreamSynchronize(s->stream));
 	if (kind != '>' && kind != '@') {
-		*cut = n; // (unclean anyway, as RawFeeder has it)
+		*cut = n; // (unclean anyway, as RawProducer has it)
 		return 0;
 	}
 	BZ_TRY(c, hipEventRecord(s->ev[0], s->stream));
@@ -574,74 +563,14 @@ ntedit_hip_reads_inflate_model(const void* comp, uint64_t n_comp, const ntedit_h
 	return 0;
 }
 
-// BGZF (the SAM specification, section 4.1), as FastaMap::inflate_bgzf walks it: gzip members with FLG = FEXTRA and
-// an extra subfield 'B','C' of two bytes holding the member's total size - 1; CRC-32 and ISIZE close each member.
+// the member walk itself is host/bgzf_walk.h, which the chunk feeders (host/chunk_feed.h) call too
 int
 ntedit_hip_bgzf_walk(const void* bytes, uint64_t n, ntedit_hip_bgzf_member* members, uint64_t cap, uint64_t* n_members, uint64_t* consumed)
 {
 	if ((n && !bytes) || (cap && !members) || !n_members || !consumed) {
 		return pfail(nullptr, NTEDIT_E_ARG, "bgzf_walk: bad argument");
 	}
-	const unsigned char* d = (const unsigned char*)bytes;
-	uint64_t o = 0, count = 0, total = 0;
-	int rc = NTEDIT_BGZF_END;
-	while (o < n) {
-		static const unsigned char magic[4] = { 0x1f, 0x8b, 8, 4 };
-		const uint64_t left = n - o;
-		if (memcmp(d + o, magic, left < 4 ? left : 4) != 0) {
-			rc = NTEDIT_BGZF_NOT;
-			break;
-		}
-		if (left < 12) {
-			rc = NTEDIT_BGZF_CUT;
-			break;
-		}
-		const uint32_t xlen = le16(d + o + 10);
-		if (left < 12 + (uint64_t)xlen) {
-			rc = NTEDIT_BGZF_CUT;
-			break;
-		}
-		uint32_t bsize = 0;
-		bool have = false;
-		for (uint64_t x = o + 12; x + 4 <= o + 12 + xlen;) {
-			const uint32_t slen = le16(d + x + 2);
-			if (d[x] == 'B' && d[x + 1] == 'C' && slen == 2 && x + 6 <= o + 12 + xlen) {
-				bsize = le16(d + x + 4);
-				have = true;
-			}
-			x += 4 + (uint64_t)slen;
-		}
-		const uint64_t member = (uint64_t)bsize + 1;
-		if (!have || member < 12 + (uint64_t)xlen + 8) {
-			rc = NTEDIT_BGZF_NOT;
-			break;
-		}
-		if (member > left) {
-			rc = NTEDIT_BGZF_CUT;
-			break;
-		}
-		const uint32_t n_out = le32(d + o + member - 4);
-		if (n_out > 65536) {
-			rc = NTEDIT_BGZF_NOT;
-			break;
-		}
-		if (count == cap) {
-			rc = NTEDIT_BGZF_FULL;
-			break;
-		}
-		ntedit_hip_bgzf_member& m = members[count++];
-		m.in_off = o + 12 + xlen;
-		m.out_off = total;
-		m.n_in = (uint32_t)(member - 12 - xlen - 8);
-		m.n_out = n_out;
-		m.crc = le32(d + o + member - 8);
-		m.reserved = 0;
-		total += n_out;
-		o += member;
-	}
-	*n_members = count;
-	*consumed = o;
-	return rc;
+	return nte_host::bgzf_walk(bytes, n, members, cap, n_members, consumed);
 }
 
 int

@@ -23,7 +23,7 @@ struct FilterStage
 
 // --genome: the filter ntedit-make-genome-bf would write (genome_pass.cpp)
 FilterStage filter_from_genome(ntedit_hip_ctx* ctx, const CliOptions& o, const RoundNames& names);
-// --reads: the filter ntedit-make-reads-bf would write (reads_pass.cpp), and with --reject_cutoff the secondary filter from
+// --reads: the filter ntedit-make-reads-bf would write (reads_build.cpp), and with --reject_cutoff the secondary filter from
 // the same pass.  `store_lost`: a cascade's store was released (over its cap, no memory, the polish buffers); no round
 // tries it again
 FilterStage filter_from_reads(ntedit_hip_ctx* ctx, const CliOptions& o, size_t round, const RoundNames& names, bool* store_lost);

@@ -6,9 +6,9 @@
 // k-mers across a cut are in the batch that ntedit_hip_filter_insert gets; insertion is idempotent, so the overlap
 // changes no bit.
 //
-//   plain files   pread into two page-locked buffers and copied on the copy stream by a reader thread while the chunk
-//                 before is parsed and inserted
-//   BGZF files    shipped compressed, in whole members whose ISIZE sum stays within batch_bytes, and inflated on the
+//   plain files   pread into two page-locked buffers by a reader thread (chunk_feed.h: RawProducer, cut anywhere); the
+//                 copy of a chunk runs on the copy stream while the chunk before is parsed and inserted (overlap)
+//   BGZF files    shipped compressed, in whole members whose ISIZE sum stays within batch_bytes (BgzfGather), and inflated on the
 //                 device (ntedit_hip_reads_inflate_device); no cut is looked for, the state carries over
 //   hand-back     from the first unclean chunk of a file on the host parser takes the file, from the last record start
 //                 known from the clean chunks before it (their last_header), or from offset 0; the sizing pass reads
@@ -16,19 +16,16 @@
 //   host files    single-stream .gz files and files that do not start with '>' take the host parser whole, and with
 //                 batch_bytes 0 every file does (the pass without --gpu_parse)
 #include "../../include/ntedit_hip.h"
+#include "chunk_feed.h"
 #include "fasta.h"
 
 #include <chrono>
 #include <cstdio>
-#include <cstring>
-#include <future>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include <fcntl.h>
 #include <sys/stat.h>
-#include <unistd.h>
 
 namespace nte_reads {
 int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
@@ -48,7 +45,6 @@ int genome_carry(const ntedit_hip_ctx* c, uint64_t text_len, uint32_t keep);
 namespace {
 
 const uint64_t NO_START = NTEDIT_READS_NO_START;
-const uint64_t CHUNK_MAX = 1u << 30;    // (the device parser takes chunks below 2^31 bytes)
 const size_t HOST_FLUSH = 512u << 20;   // the host parser's batches, as ntedit-make-genome-bf makes them
 
 int
@@ -57,42 +53,12 @@ pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
 	return nte_reads::set_error(c, code, why);
 }
 
-bool
-pread_whole(int fd, char* p, uint64_t off, size_t n)
+// why a feed (chunk_feed.h) gave up: no page-locked memory, or the file
+int
+feed_fail(const ntedit_hip_ctx* c, const std::string& why)
 {
-	while (n) {
-		const ssize_t got = pread(fd, p, n, (off_t)off);
-		if (got <= 0) {
-			return false;
-		}
-		p += got, off += (uint64_t)got, n -= (size_t)got;
-	}
-	return true;
+	return pfail(c, why == nte_host::NO_PINNED ? NTEDIT_E_DEVICE : NTEDIT_E_IO, why);
 }
-
-struct Pinned
-{
-	char* p = nullptr;
-	size_t cap = 0;
-	~Pinned() { ntedit_hip_host_free(p); }
-	bool reserve(size_t need, size_t keep)
-	{
-		if (need <= cap) {
-			return true;
-		}
-		char* q = (char*)ntedit_hip_host_alloc(need);
-		if (!q) {
-			return false;
-		}
-		if (keep) {
-			memcpy(q, p, keep);
-		}
-		ntedit_hip_host_free(p);
-		p = q;
-		cap = need;
-		return true;
-	}
-};
 
 struct Pass
 {
@@ -187,55 +153,35 @@ struct Pass
 		return 0;
 	}
 
+	// chunk i: the file's bytes [i * batch_bytes, ...), read by the feed's thread; its copy runs while the chunk before is
+	// parsed and inserted
 	int plain_file(const char* path, uint64_t size)
 	{
-		const int fd = open(path, O_RDONLY);
-		if (fd < 0) {
-			return pfail(ctx, NTEDIT_E_IO, std::string("cannot open ") + path);
-		}
-		Pinned buf[2];
 		const uint64_t bases_before = bases;
 		uint64_t rec_start = NO_START;
 		bool unclean = false;
+		int state = NTEDIT_GENOME_LINE_START;
 		int rc = nte_reads::genome_begin_file(ctx);
-		// chunk i: bytes [i * batch, ...) through buffer i & 1; read and queued for its copy by this
-		auto feed = [&](uint64_t off, int which) -> int {
-			const size_t len = (size_t)(size - off < batch_bytes ? size - off : batch_bytes);
-			if (!buf[which].reserve(len, 0)) {
-				return pfail(ctx, NTEDIT_E_DEVICE, "cannot allocate page-locked host memory");
-			}
-			if (!pread_whole(fd, buf[which].p, off, len)) {
-				return pfail(ctx, NTEDIT_E_IO, std::string(path) + ": read error");
-			}
-			return nte_reads::parse_copy_begin(ctx, which, buf[which].p, len);
-		};
 		if (rc == 0) {
-			rc = feed(0, 0);
+			nte_host::Feed<nte_host::RawChunk> feed(nte_host::RawProducer{ path, 0, size, (size_t)batch_bytes, nte_host::CUT_ANYWHERE });
+			auto begin = [&](const nte_host::RawChunk& c, int which) { return nte_reads::parse_copy_begin(ctx, which, c.buf.p, c.len); };
+			auto work = [&](const nte_host::RawChunk& c, int which, auto release) {
+				const auto g0 = std::chrono::steady_clock::now();
+				const char* batch = nullptr;
+				ntedit_hip_genome_parse_result res = ntedit_hip_genome_parse_result();
+				const uint64_t off = c.off, len = c.len;
+				int rc = nte_reads::genome_parse_buffer(ctx, which, 1, len, state, off == 0, &batch, &res);
+				if (rc == 0) {
+					release(); // (its copy is done: the reader may fill it again)
+					rc = chunk_done(res, batch, len, off, &rec_start, &unclean);
+				}
+				gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
+				state = res.state_out;
+				return rc ? rc : unclean ? (int)nte_host::OVERLAP_STOP : 0;
+			};
+			rc = nte_host::overlap(feed, begin, work, [&](int which) { return nte_reads::parse_copy_wait(ctx, which); });
+			rc = rc == nte_host::OVERLAP_FEED ? feed_fail(ctx, feed.error()) : rc == nte_host::OVERLAP_STOP ? 0 : rc;
 		}
-		int state = NTEDIT_GENOME_LINE_START, which = 0;
-		for (uint64_t off = 0; rc == 0 && off < size && !unclean; off += batch_bytes, which ^= 1) {
-			const uint64_t len = size - off < batch_bytes ? size - off : batch_bytes;
-			// chunk i + 1 is read and copied while chunk i is parsed and inserted
-			std::future<int> next;
-			if (off + batch_bytes < size) {
-				next = std::async(std::launch::async, feed, off + batch_bytes, which ^ 1);
-			}
-			const auto g0 = std::chrono::steady_clock::now();
-			const char* batch = nullptr;
-			ntedit_hip_genome_parse_result res = ntedit_hip_genome_parse_result();
-			rc = nte_reads::genome_parse_buffer(ctx, which, 1, len, state, off == 0, &batch, &res);
-			if (rc == 0) {
-				rc = chunk_done(res, batch, len, off, &rec_start, &unclean);
-			}
-			gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
-			state = res.state_out;
-			if (next.valid()) {
-				const int rc_next = next.get();
-				(void)nte_reads::parse_copy_wait(ctx, which ^ 1); // (before the buffer it reads may go)
-				rc = rc ? rc : rc_next;
-			}
-		}
-		close(fd);
 		if (rc == 0 && unclean) {
 			info->handed_back++;
 			if (!insert) {
@@ -246,106 +192,64 @@ struct Pass
 		return rc;
 	}
 
-	int bgzf_file(const char* path, uint64_t size)
+	// serial: a chunk is gathered, then inflated from its page-locked buffer, parsed and inserted
+	int bgzf_file(const char* path)
 	{
-		const int fd = open(path, O_RDONLY);
-		if (fd < 0) {
-			return pfail(ctx, NTEDIT_E_IO, std::string("cannot open ") + path);
+		nte_host::BgzfGather gather(path, (size_t)batch_bytes);
+		if (!gather.error().empty()) {
+			return pfail(ctx, NTEDIT_E_IO, gather.error());
 		}
 		info->bgzf_files++;
-		Pinned comp;
-		std::vector<ntedit_hip_bgzf_member> members;
+		nte_host::BgzfChunk c;
 		std::vector<uint32_t> status;
-		const size_t slab = (size_t)(batch_bytes / 4 + (128u << 10)); // compressed bytes read at a time
 		const uint64_t bases_before = bases;
-		uint64_t pos = 0, have = 0;     // comp holds the file's bytes [pos, pos + have)
-		uint64_t out_off = 0;           // inflated bytes before the chunk
-		uint64_t rec_start = NO_START;  // an inflated offset
-		uint64_t first_member = 0;
-		bool unclean = false, done = false;
+		uint64_t out_off = 0;          // inflated bytes before the chunk
+		uint64_t rec_start = NO_START; // an inflated offset
+		bool unclean = false;
 		int state = NTEDIT_GENOME_LINE_START;
 		int rc = nte_reads::genome_begin_file(ctx);
-		while (rc == 0 && !done && !unclean) {
-			// whole members whose ISIZE sum stays within batch_bytes (at least one)
-			members.clear();
-			uint64_t walked = 0, n_out = 0;
-			for (;;) {
-				ntedit_hip_bgzf_member one;
-				uint64_t found = 0, used = 0;
-				const int why = ntedit_hip_bgzf_walk(comp.p + walked, have - walked, &one, 1, &found, &used);
-				if (found) {
-					if (!members.empty() && n_out + one.n_out > batch_bytes) {
-						break;
-					}
-					one.in_off += walked;
-					one.out_off = n_out;
-					members.push_back(one);
-					n_out += one.n_out;
-					walked += used;
-					continue;
-				}
-				if (why == NTEDIT_BGZF_NOT || pos + have >= size) {
-					// no member starts here, or the file ends inside one: what is left is the host parser's
-					done = true;
-					unclean = have != walked;
-					break;
-				}
-				const size_t more = (size_t)(size - (pos + have) < slab ? size - (pos + have) : slab);
-				if (!comp.reserve((size_t)have + more, (size_t)have)) {
-					rc = pfail(ctx, NTEDIT_E_DEVICE, "cannot allocate page-locked host memory");
-					break;
-				}
-				if (!pread_whole(fd, comp.p + have, pos + have, more)) {
-					rc = pfail(ctx, NTEDIT_E_IO, std::string(path) + ": read error");
-					break;
-				}
-				have += more;
-			}
-			if (rc || members.empty()) {
+		while (rc == 0 && !unclean && gather.next(&c)) {
+			unclean = c.last && !c.whole; // no member starts there, or the file ends inside one: what is left is the host parser's
+			if (!c.n_members) {
 				break;
 			}
 			const auto g0 = std::chrono::steady_clock::now();
 			bool bad = false; // the chunk is unclean
-			if (n_out) {
+			if (c.n_out) {
 				char* d_raw = nullptr;
-				status.assign(members.size(), 0);
-				rc = nte_reads::genome_raw_buffer(ctx, 0, n_out, &d_raw);
+				status.assign(c.n_members, 0);
+				rc = nte_reads::genome_raw_buffer(ctx, 0, c.n_out, &d_raw);
 				if (rc == 0) {
-					rc = ntedit_hip_reads_inflate_device(ctx, comp.p, walked, NTEDIT_HIP_BASES_HOST, members.data(), members.size(), d_raw,
-					                                     n_out, status.data());
+					rc = ntedit_hip_reads_inflate_device(ctx, c.buf.p, c.len, NTEDIT_HIP_BASES_HOST, c.m(), c.n_members, d_raw, c.n_out,
+					                                     status.data());
 				}
-				for (size_t m = 0; rc == 0 && m < members.size(); m++) {
+				for (size_t m = 0; rc == 0 && m < c.n_members; m++) {
 					if (status[m]) {
-						rc = pfail(ctx, NTEDIT_E_IO, std::string(path) + ": BGZF member " + std::to_string(first_member + m) +
+						rc = pfail(ctx, NTEDIT_E_IO, std::string(path) + ": BGZF member " + std::to_string(c.first_member + m) +
 						                                 " is damaged (" + nte_reads::inflate_reason(status[m]) + ")");
 					}
 				}
 				const char* batch = nullptr;
 				ntedit_hip_genome_parse_result res = ntedit_hip_genome_parse_result();
 				if (rc == 0) {
-					rc = nte_reads::genome_parse_buffer(ctx, 0, 0, n_out, state, out_off == 0, &batch, &res);
+					rc = nte_reads::genome_parse_buffer(ctx, 0, 0, c.n_out, state, out_off == 0, &batch, &res);
 				}
 				if (rc == 0) {
-					rc = chunk_done(res, batch, n_out, out_off, &rec_start, &bad);
+					rc = chunk_done(res, batch, c.n_out, out_off, &rec_start, &bad);
 					state = res.state_out;
 				}
 			}
 			if (bad) {
 				unclean = true;
-				done = true;
 			} else if (rc == 0) {
-				info->bgzf_members += members.size(); // (the empty member at the file's end included)
+				info->bgzf_members += c.n_members; // (the empty member at the file's end included)
 			}
 			gpu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
-			out_off += n_out;
-			first_member += members.size();
-			if (have > walked) {
-				memmove(comp.p, comp.p + walked, (size_t)(have - walked));
-			}
-			pos += walked;
-			have -= walked;
+			out_off += c.n_out;
 		}
-		close(fd);
+		if (rc == 0 && !gather.error().empty()) {
+			rc = feed_fail(ctx, gather.error());
+		}
 		if (rc == 0 && unclean) {
 			info->handed_back++;
 			if (!insert) {
@@ -356,25 +260,6 @@ struct Pass
 		return rc;
 	}
 };
-
-// 0: plain, 1: a single-stream gzip file, 2: BGZF; *first: the file's first byte (-1: empty or unreadable)
-int
-file_kind(const char* path, int* first)
-{
-	unsigned char head[4096];
-	FILE* fp = fopen(path, "rb");
-	const size_t got = fp ? fread(head, 1, sizeof head, fp) : 0;
-	if (fp) {
-		fclose(fp);
-	}
-	*first = got ? (int)head[0] : -1;
-	if (got < 2 || head[0] != 0x1f || head[1] != 0x8b) {
-		return 0;
-	}
-	uint64_t found = 0, used = 0;
-	const int why = ntedit_hip_bgzf_walk(head, got, nullptr, 0, &found, &used);
-	return got >= 28 && (why == NTEDIT_BGZF_FULL || (why == NTEDIT_BGZF_CUT && got == sizeof head)) ? 2 : 1;
-}
 
 } // namespace
 
@@ -391,7 +276,7 @@ ntedit_hip_genome_pass(ntedit_hip_ctx* ctx, int slot, const char* const* files, 
 	p.ctx = ctx;
 	p.slot = slot;
 	p.insert = insert ? 1 : 0;
-	p.batch_bytes = batch_bytes < CHUNK_MAX ? batch_bytes : CHUNK_MAX;
+	p.batch_bytes = batch_bytes < nte_host::CHUNK_MAX ? batch_bytes : nte_host::CHUNK_MAX;
 	p.info = nte_reads::genome_info(ctx);
 	*p.info = ntedit_hip_genome_pass_info();
 	if (insert) {
@@ -410,10 +295,10 @@ ntedit_hip_genome_pass(ntedit_hip_ctx* ctx, int slot, const char* const* files, 
 			return pfail(ctx, NTEDIT_E_IO, std::string("cannot open ") + (files[i] ? files[i] : "(null)"));
 		}
 		int first = -1;
-		const int kind = S_ISREG(sb.st_mode) ? file_kind(files[i], &first) : 1;
+		const int kind = S_ISREG(sb.st_mode) ? nte_host::file_kind(files[i], &first) : 1;
 		int rc;
 		if (kind == 2 && batch_bytes) {
-			rc = p.bgzf_file(files[i], (uint64_t)sb.st_size);
+			rc = p.bgzf_file(files[i]);
 		} else if (batch_bytes == 0 || kind == 1 || first != '>') {
 			p.info->host_files++;
 			rc = p.host_parse(files[i], 0, 0);

@@ -35,8 +35,8 @@
 
 using nte_host::log_info;
 
-// (the option rules, the sizing, the passes and the --hist writer live in the library: reads_options.cpp and
-// reads_pass.cpp, shared with the sharded driver and `ntedit --reads`)
+// (the option rules, the sizing, the passes, the build and the --hist writer live in the library: reads_options.cpp,
+// reads_pass.cpp and reads_build.cpp, shared with the sharded driver and `ntedit --reads`)
 static void
 usage(const char* why)
 {
@@ -261,7 +261,7 @@ main(int argc, char** argv)
 		std::cerr << "make_reads_bf: error: " << (ctx ? ntedit_hip_last_error(ctx) : "no HIP device") << std::endl;
 		return 1;
 	}
-	// sketch, pass 1, the histogram pass, the output filter, pass 2 (reads_pass.cpp, shared with `ntedit --reads`)
+	// sketch, pass 1, the histogram pass, the output filter, pass 2 (reads_build.cpp, shared with `ntedit --reads`)
 	ntedit_hip_reads_build_args ba = {};
 	ba.files = paths.data();
 	ba.n_files = (uint32_t)paths.size();
