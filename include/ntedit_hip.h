@@ -284,6 +284,24 @@ void ntedit_hip_resident_free(ntedit_hip_ctx* ctx);
 int ntedit_hip_sketch_reset(ntedit_hip_ctx* ctx, uint64_t counters, uint32_t hash_num, uint32_t k);
 int ntedit_hip_resident_count(ntedit_hip_ctx* ctx);
 int ntedit_hip_reads_set_min_read(ntedit_hip_ctx* ctx, uint32_t len);
+/* --min_qual Q: a base whose Phred quality is below Q enters the batch text as 'N' (Phred+33: a FASTQ quality byte below
+ * 33 + Q, a BAM quality byte below Q; Phred+64 is not built).  Only byte values change: the text has the same length, the
+ * same reads and the same order as without it (records are kept by their length, masked bases included), and since every
+ * kernel behind the parse breaks its k-mer walk at a non-ACGT byte, the sketch, the histogram, the filters and the
+ * resident store all follow.  Records without qualities -- FASTA records, BAM records whose first quality byte is 0xFF --
+ * pass unmasked.  The host parser masks by kseq's rules (multi-line FASTQ: the i-th quality character after
+ * concatenation belongs to the i-th base); the device parser by nte_reads_grammar.h's rp_mask_base, the same function.
+ *   ntedit_hip_reads_set_min_qual: the context's setting, 0 (off) to 93, that ntedit_hip_reads_pass,
+ *           ntedit_hip_reads_parse_device and ntedit_hip_reads_bam_device follow; above 93: NTEDIT_E_ARG.  It needs no
+ *           sketch and outlives ntedit_hip_sketch_reset and ntedit_hip_sketch_free: a cascade masks alike in every round.
+ *   ntedit_hip_reads_min_qual_info: the context's last ntedit_hip_reads_pass (the pass zeroes them; the two device calls
+ *           add to them): the bases that had a quality, and those of them below the minimum.  0, 0 with the setting off.
+ *   ntedit_hip_reads_parse_model_q, _bam_model_q, _range_text_q: the host-only calls with min_qual as one more argument;
+ *           the old names are these with 0. */
+int ntedit_hip_reads_set_min_qual(ntedit_hip_ctx* ctx, uint32_t min_qual);
+int ntedit_hip_reads_min_qual_info(ntedit_hip_ctx* ctx, uint64_t* qual_bases, uint64_t* masked_bases);
+int ntedit_hip_reads_range_text_q(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, char* out, uint64_t cap,
+                                  uint64_t* len, uint64_t* reads, uint64_t* start, uint64_t* next);
 /* The whole filter build of ntedit-make-reads-bf, shared by it and `ntedit --reads`: the sketch (sketch_counters, as
  * sized by the caller), pass 1, with solid or hist_path the histogram pass (the --hist file, the --solid cutoff, and
  * with bf_bytes = 0 the output size from the histogram), the output filter allocated in the PRIMARY slot (counting
@@ -349,6 +367,7 @@ typedef struct ntedit_hip_reads_build_args
 	uint64_t reject_num_elements; /* as given (the parameter echo) */
 	uint32_t min_read;        /* ntedit_hip_reads_set_min_read for this build's passes over the files; 0: k */
 	int keep_store;           /* the build ends with the sketch released and the store, if it is ON, kept for the next build */
+	uint32_t min_qual;        /* --min_qual: ntedit_hip_reads_set_min_qual for this build's passes over the files; 0: off */
 } ntedit_hip_reads_build_args;
 typedef struct ntedit_hip_reads_build_result
 {
@@ -376,7 +395,8 @@ int ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_bu
  * can ask while it walks its arguments; with final = 1 every rule, in that dialect's order: -k required and 12..200,
  * the cutoff xor --solid and 1..255, hashes 1..8, a size unless the histogram gives it, the filter would be empty,
  * batch_bytes >= 4096, then the reject filter's: --reject_cutoff 2..255 and above the cutoff given, not with --counts, a
- * size (--reject_bf or --reject_num_elements) unless the histogram gives it, no size without it, not empty.  (Under
+ * size (--reject_bf or --reject_num_elements) unless the histogram gives it, no size without it, not empty, then
+ * --min_qual 1..93 (a malformed one is refused at the option, like every number).  (Under
  * --solid "above the cutoff" waits for ntedit_hip_reads_stage_decide.)  Returns 0 and the normalised arguments, or the first refusal: NTEDIT_READS_REFUSED,
  * NTEDIT_READS_NOT_A_NUMBER (a malformed number), NTEDIT_READS_EMPTY (TOOL dialect: the filter would be empty; the
  * tool prints its parameters before it says so, and *out is filled), its message in ntedit_hip_reads_last_error(NULL). */
@@ -398,6 +418,7 @@ typedef struct ntedit_hip_reads_options
 	const char *reject_cutoff, *reject_bf, *reject_num_elements;
 	int counts;     /* --counts (refused with --reject_cutoff) */
 	int reject_out; /* an output option of the reject filter was given (--reject_out / --save_reject_bf) */
+	const char* min_qual; /* --min_qual (1 to 93) */
 } ntedit_hip_reads_options;
 typedef struct ntedit_hip_reads_rules
 {
@@ -414,6 +435,7 @@ typedef struct ntedit_hip_reads_rules
 	uint64_t reject_bf_bytes;      /* --reject_bf, or from --reject_num_elements; 0: sized from the histogram */
 	uint64_t reject_num_elements;
 	int reject_size_from_hist;
+	uint32_t min_qual;             /* 0: off */
 } ntedit_hip_reads_rules;
 int ntedit_hip_reads_options_check(const ntedit_hip_reads_options* opts, int dialect, int final, ntedit_hip_reads_rules* out);
 /* --gpu_parse: plain (not gzip) read files parsed on the device.  The host ships raw file bytes, cut at record starts
@@ -468,6 +490,8 @@ typedef struct ntedit_hip_reads_parse_stats
 int ntedit_hip_reads_parse_device(ntedit_hip_ctx* ctx, const char* raw, uint64_t n_raw, int on_device, uint32_t k, char* text_device,
                                   uint64_t text_cap, ntedit_hip_reads_parse_result* res);
 int ntedit_hip_reads_parse_model(const char* raw, uint64_t n_raw, uint32_t k, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res);
+int ntedit_hip_reads_parse_model_q(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* out, uint64_t cap,
+                                   ntedit_hip_reads_parse_result* res);
 int ntedit_hip_reads_set_device_parse(ntedit_hip_ctx* ctx, int on);
 int ntedit_hip_reads_parse_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_parse_stats* st);
 /* --gpu_parse on BGZF reads (the output of bgzip: independent gzip members of at most 64 KiB inflated each, their
@@ -595,6 +619,8 @@ int ntedit_hip_reads_bam_device(ntedit_hip_ctx* ctx, const void* raw, uint64_t n
                                 char* text_device, uint64_t text_cap, ntedit_hip_reads_bam_result* res);
 int ntedit_hip_reads_bam_model(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, char* out, uint64_t cap,
                                ntedit_hip_reads_bam_result* res);
+int ntedit_hip_reads_bam_model_q(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, uint32_t min_qual, char* out,
+                                 uint64_t cap, ntedit_hip_reads_bam_result* res);
 int ntedit_hip_reads_bam_set_segment(ntedit_hip_ctx* ctx, uint64_t bytes);
 int ntedit_hip_reads_bam_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_bam_stats* st);
 /* --gpu_parse for genome FASTA (ntedit-make-genome-bf --gpu_parse, ntedit --genome --gpu_parse).  A chromosome does not

@@ -91,7 +91,8 @@ class ReadsBuildArgs(ctypes.Structure):
                 ("log", READS_LOG_FN), ("user", ctypes.c_void_p), ("begins", ctypes.POINTER(ctypes.c_uint64)),
                 ("ends", ctypes.POINTER(ctypes.c_uint64)), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32),
                 ("device_parse", ctypes.c_int), ("reject_cmin", ctypes.c_uint32), ("reject_bf_bytes", ctypes.c_uint64),
-                ("reject_num_elements", ctypes.c_uint64), ("min_read", ctypes.c_uint32), ("keep_store", ctypes.c_int)]
+                ("reject_num_elements", ctypes.c_uint64), ("min_read", ctypes.c_uint32), ("keep_store", ctypes.c_int),
+                ("min_qual", ctypes.c_uint32)]
 
 
 class ReadsBuildResult(ctypes.Structure):
@@ -117,7 +118,7 @@ class ReadsOptions(ctypes.Structure):
                 [("solid", ctypes.c_int), ("hist", ctypes.c_int), ("files", ctypes.POINTER(ctypes.c_char_p)),
                  ("n_files", ctypes.c_uint32), ("gpu_parse", ctypes.c_int)] +
                 [(name, ctypes.c_char_p) for name in READS_REJECT_OPTION_TEXTS] +
-                [("counts", ctypes.c_int), ("reject_out", ctypes.c_int)])
+                [("counts", ctypes.c_int), ("reject_out", ctypes.c_int), ("min_qual", ctypes.c_char_p)])
 
 
 class ReadsRules(ctypes.Structure):
@@ -128,7 +129,8 @@ class ReadsRules(ctypes.Structure):
                 ("batch_bytes", ctypes.c_uint64), ("store_cap", ctypes.c_uint64), ("threads", ctypes.c_uint64),
                 ("gather_hist", ctypes.c_int), ("size_from_hist", ctypes.c_int), ("gpu_parse", ctypes.c_int),
                 ("reject_cmin", ctypes.c_uint32), ("reject_bf_bytes", ctypes.c_uint64),
-                ("reject_num_elements", ctypes.c_uint64), ("reject_size_from_hist", ctypes.c_int)]
+                ("reject_num_elements", ctypes.c_uint64), ("reject_size_from_hist", ctypes.c_int),
+                ("min_qual", ctypes.c_uint32)]
 
 
 # --gpu_parse (ntedit_hip_reads_parse_device / _model): the tile size and the rules of the clean grammar
@@ -367,6 +369,8 @@ EXPORTS = [
     "ntedit_hip_genome_pass_get_info", "ntedit_hip_genome_pass_line",
     "ntedit_hip_sketch_reset", "ntedit_hip_resident_count", "ntedit_hip_reads_set_min_read",
     "ntedit_hip_settle_info",
+    "ntedit_hip_reads_set_min_qual", "ntedit_hip_reads_min_qual_info", "ntedit_hip_reads_parse_model_q",
+    "ntedit_hip_reads_bam_model_q", "ntedit_hip_reads_range_text_q",
     "ntedit_hip_set_apply", "ntedit_hip_result_edited_device", "ntedit_hip_result_edited",
     "ntedit_hip_result_last_error", "ntedit_hip_result_qv", "ntedit_hip_qv_value", "ntedit_hip_qv_header",
     "ntedit_hip_qv_format_row", "ntedit_hip_apply_info", "ntedit_hip_apply_tile",
@@ -555,6 +559,12 @@ def load():
     lib.ntedit_hip_sketch_reset.argtypes = [vp, u64, u32, u32]
     lib.ntedit_hip_resident_count.argtypes = [vp]
     lib.ntedit_hip_reads_set_min_read.argtypes = [vp, u32]
+    # --min_qual: the context's setting, the last pass's counts, and the host-only calls with min_qual as one more argument
+    lib.ntedit_hip_reads_set_min_qual.argtypes = [vp, u32]
+    lib.ntedit_hip_reads_min_qual_info.argtypes = [vp, pu64, pu64]
+    lib.ntedit_hip_reads_parse_model_q.argtypes = [vp, u64, u32, u32, vp, u64, pres]
+    lib.ntedit_hip_reads_bam_model_q.argtypes = [vp, u64, ci, u32, u32, vp, u64, bres]
+    lib.ntedit_hip_reads_range_text_q.argtypes = [ctypes.c_char_p, u64, u64, u32, vp, u64, pu64, pu64, pu64, pu64]
     # the edited draft in HBM and the k-mer QV (nte_apply.hip)
     pu32 = ctypes.POINTER(u32)
     lib.ntedit_hip_set_apply.argtypes = [vp, u32]

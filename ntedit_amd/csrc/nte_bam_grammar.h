@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "nte_bgzf_inflate.h"
+#include "nte_reads_grammar.h"
 
 #if defined(__HIP__) || defined(__HIPCC__)
 #define BAM_HD __host__ __device__ __forceinline__
@@ -163,6 +164,30 @@ bam_base(const uint8_t* raw, uint32_t seq_off, uint32_t j)
 	return "=ACMGRSVTWYHKDBN"[(j & 1) ? (b & 15u) : (b >> 4)];
 }
 
+// --min_qual: the record's l_seq quality bytes (Phred, as stored) lie right behind its packed bases
+BAM_HD uint32_t
+bam_qual_off(uint32_t seq_off, uint32_t l_seq)
+{
+	return seq_off + (l_seq + 1) / 2;
+}
+
+// SAM specification 4.2.3: a first quality byte of 0xFF says the record has no qualities (qual_off: bam_qual_off of it)
+BAM_HD bool
+bam_has_qual(const uint8_t* raw, uint32_t qual_off, uint32_t l_seq)
+{
+	return l_seq > 0 && raw[qual_off] != 0xFFu;
+}
+
+// base j of a record that has qualities, as it enters the text under --min_qual: the one rule of nte_reads_grammar.h on
+// the quality byte as stored; *n_masked += 1 when it is masked (whatever the base was)
+BAM_HD char
+bam_base_q(const uint8_t* raw, uint32_t seq_off, uint32_t qual_off, uint32_t j, uint32_t min_qual, uint32_t* n_masked)
+{
+	const bool low = nte_parse::rp_masked((int)raw[qual_off + j], min_qual);
+	*n_masked += low;
+	return (char)nte_parse::rp_mask_base((uint8_t)bam_base(raw, seq_off, j), low);
+}
+
 // The chain from p (< end <= n) while it starts records below `end`: their offsets into table[0 .. cap), *count of them,
 // *exit where the chain left [.., end) (BAM_NEXT), or where it stopped: the cut (BAM_END) or the unclean record.  The
 // walk is a function of (raw, n, p, end): whoever enters at p writes the same table.
@@ -239,8 +264,11 @@ bam_unclean(uint32_t broken, uint64_t at)
 // (host only from here on)
 // The model: one chain from the true entry, one pass over its records.  The text into out[0 .. cap) as far as it fits;
 // res->text_len is its whole length either way.
+// With min_qual > 0 the bases of the records that have qualities are masked (bam_base_q); counts[0] += those bases,
+// counts[1] += the masked ones (counts may be NULL).
 inline void
-bam_model(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, char* out, uint64_t cap, BamResult* res)
+bam_model_q(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, uint32_t min_qual, char* out, uint64_t cap, BamResult* res,
+            uint64_t* counts)
 {
 	*res = BamResult();
 	if (n >= BAM_MAX_RAW) {
@@ -280,10 +308,21 @@ bam_model(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, char*
 		} else {
 			res->kept++;
 			res->bases += r.l_seq;
+			const uint32_t qual_off = bam_qual_off(r.seq_off, r.l_seq);
+			const bool mask = min_qual && bam_has_qual(raw, qual_off, r.l_seq);
+			uint32_t masked = 0;
 			for (uint32_t j = 0; j <= r.l_seq; j++, text++) {
-				if (text < cap) {
-					out[text] = j < r.l_seq ? bam_base(raw, r.seq_off, j) : '\n';
+				char ch = '\n';
+				if (j < r.l_seq) {
+					ch = mask ? bam_base_q(raw, r.seq_off, qual_off, j, min_qual, &masked) : bam_base(raw, r.seq_off, j);
 				}
+				if (text < cap) {
+					out[text] = ch;
+				}
+			}
+			if (mask && counts) {
+				counts[0] += r.l_seq;
+				counts[1] += masked;
 			}
 		}
 		p = r.next;
@@ -291,6 +330,12 @@ bam_model(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, char*
 	res->clean = 1;
 	res->cut = p;
 	res->text_len = text;
+}
+
+inline void
+bam_model(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, char* out, uint64_t cap, BamResult* res)
+{
+	bam_model_q(raw, n, at_header, min_len, 0, out, cap, res, nullptr);
 }
 
 // The first BGZF member of buf[0 .. n) (a gzip member with FEXTRA and a 'B','C' subfield of the member's size - 1): where

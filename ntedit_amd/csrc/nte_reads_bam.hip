@@ -18,6 +18,8 @@
 //   k_bam_compact  as k_bam_sums, with a wavefront scan: each kept record's packed-bases offset and text offset, dense.
 //   k_bam_decode   one lane per 16 text bytes, whatever the records' lengths: a search in the text-offset table for the
 //                  record its first byte lies in, then nibbles to bytes across record ends, one 16-byte store.
+//                  k_bam_decode<true> (--min_qual) also masks each base by its quality byte, which lies behind the
+//                  record's packed bases.
 //
 // Like nte_reads_inflate.hip this unit is outside KSRC and sees no context internals: its state hangs off the context
 // pointer, its scratch grows only and goes with ntedit_hip_sketch_free.  It works on the parse unit's stream.
@@ -42,6 +44,8 @@ namespace nte_reads {
 int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
 int parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream);
 int parse_text_buffer(const ntedit_hip_ctx* c, uint64_t n, char** text, uint64_t* cap);
+uint32_t min_qual(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_min_qual (nte_reads_parse.hip), and the pass's counts
+void min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases);
 }
 
 namespace {
@@ -61,6 +65,7 @@ struct BamInfo // the small result the device keeps per chunk
 	u64 header_len;
 	u32 broken, cut, rewalked, reserved;
 	u64 records, kept, skipped_flag, skipped_short;
+	u64 qual_bases, masked_bases; // --min_qual (k_bam_decode<true>): the bases decoded that had a quality, and those masked
 };
 
 struct SegTables // per segment
@@ -302,43 +307,73 @@ k_bam_compact(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len,
 	}
 }
 
+// MASK (--min_qual): base i of a record is masked by the quality byte at krec_seq[r] + (l_seq + 1) / 2 + i (bam_base_q),
+// l_seq from the text offsets; a record whose first quality byte is 0xFF has none.  Every record in the tables passed
+// bam_hop, so its quality bytes lie inside the chunk.  The counts are summed per wavefront, one atomic each per wavefront.
+template <bool MASK>
 __global__ __launch_bounds__(BAM_TPB) void
 k_bam_decode(const u8* __restrict__ raw, const u32* __restrict__ krec_seq, const u32* __restrict__ krec_text, u32 kept, u8* text,
-             u32 text_len)
+             u32 text_len, u32 min_qual, BamInfo* info)
 {
 	const u64 t0 = ((u64)blockIdx.x * BAM_TPB + threadIdx.x) * 16;
-	if (t0 >= text_len) {
-		return;
-	}
-	// the last record whose text starts at or before t0 (text offsets rise strictly: every kept record has its '\n')
-	u32 lo = 0, hi = kept;
-	while (hi - lo > 1) {
-		const u32 mid = lo + (hi - lo) / 2;
-		if (krec_text[mid] <= (u32)t0) {
-			lo = mid;
-		} else {
-			hi = mid;
+	u32 n_qual = 0, n_masked = 0;
+	if (t0 < text_len) {
+		// the last record whose text starts at or before t0 (text offsets rise strictly: every kept record has its '\n')
+		u32 lo = 0, hi = kept;
+		while (hi - lo > 1) {
+			const u32 mid = lo + (hi - lo) / 2;
+			if (krec_text[mid] <= (u32)t0) {
+				lo = mid;
+			} else {
+				hi = mid;
+			}
 		}
-	}
-	u32 rec = lo, start = krec_text[rec], end = krec_text[rec + 1], seq = krec_seq[rec];
-	const u32 todo = text_len - (u32)t0 < 16 ? text_len - (u32)t0 : 16;
-	u32 w[4] = { 0, 0, 0, 0 };
-	for (u32 i = 0; i < todo; i++) {
-		const u32 at = (u32)t0 + i;
-		if (at == end) {
-			rec++;
-			start = end;
-			end = krec_text[rec + 1];
-			seq = krec_seq[rec];
-		}
-		const u32 ch = at + 1 == end ? (u32)'\n' : (u32)(u8)bam_base(raw, seq, at - start);
-		w[i >> 2] |= ch << ((i & 3) * 8);
-	}
-	if (todo == 16) {
-		*(uint4*)(text + t0) = make_uint4(w[0], w[1], w[2], w[3]);
-	} else {
+		u32 rec = lo, start = krec_text[rec], end = krec_text[rec + 1], seq = krec_seq[rec];
+		// the record's quality bytes and whether it has any: derived where the lane enters a record, not per base
+		u32 qual = MASK ? bam_qual_off(seq, end - start - 1) : 0;
+		bool has_qual = MASK && bam_has_qual(raw, qual, end - start - 1);
+		const u32 todo = text_len - (u32)t0 < 16 ? text_len - (u32)t0 : 16;
+		u32 w[4] = { 0, 0, 0, 0 };
 		for (u32 i = 0; i < todo; i++) {
-			text[t0 + i] = (u8)(w[i >> 2] >> ((i & 3) * 8));
+			const u32 at = (u32)t0 + i;
+			if (at == end) {
+				rec++;
+				start = end;
+				end = krec_text[rec + 1];
+				seq = krec_seq[rec];
+				if (MASK) {
+					qual = bam_qual_off(seq, end - start - 1);
+					has_qual = bam_has_qual(raw, qual, end - start - 1);
+				}
+			}
+			u32 ch = (u32)'\n';
+			if (at + 1 != end) {
+				if (MASK && has_qual) {
+					n_qual++;
+					ch = (u32)(u8)bam_base_q(raw, seq, qual, at - start, min_qual, &n_masked);
+				} else {
+					ch = (u32)(u8)bam_base(raw, seq, at - start);
+				}
+			}
+			w[i >> 2] |= ch << ((i & 3) * 8);
+		}
+		if (todo == 16) {
+			*(uint4*)(text + t0) = make_uint4(w[0], w[1], w[2], w[3]);
+		} else {
+			for (u32 i = 0; i < todo; i++) {
+				text[t0 + i] = (u8)(w[i >> 2] >> ((i & 3) * 8));
+			}
+		}
+	}
+	if (MASK) {
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			n_qual += __shfl_xor(n_qual, d, 64);
+			n_masked += __shfl_xor(n_masked, d, 64);
+		}
+		if ((threadIdx.x & 63) == 0 && n_qual) {
+			atomicAdd((unsigned long long*)&info->qual_bases, (unsigned long long)n_qual);
+			atomicAdd((unsigned long long*)&info->masked_bases, (unsigned long long)n_masked);
 		}
 	}
 }
@@ -597,12 +632,22 @@ bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, in
 	if (out.text_len) {
 		hipLaunchKernelGGL(k_bam_compact, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, krec_seq, krec_text);
 		const unsigned blocks = (unsigned)((out.text_len + BAM_TPB * 16 - 1) / (BAM_TPB * 16));
-		hipLaunchKernelGGL(k_bam_decode, dim3(blocks), dim3(BAM_TPB), 0, s->stream, d_raw, krec_seq, krec_text, (u32)out.kept, d_text,
-		                   (u32)out.text_len);
+		const u32 min_qual = nte_reads::min_qual(c);
+		if (min_qual) {
+			hipLaunchKernelGGL(k_bam_decode<true>, dim3(blocks), dim3(BAM_TPB), 0, s->stream, d_raw, krec_seq, krec_text, (u32)out.kept,
+			                   d_text, (u32)out.text_len, min_qual, s->d_info);
+		} else {
+			hipLaunchKernelGGL(k_bam_decode<false>, dim3(blocks), dim3(BAM_TPB), 0, s->stream, d_raw, krec_seq, krec_text, (u32)out.kept,
+			                   d_text, (u32)out.text_len, 0u, s->d_info);
+		}
 		BAM_TRY(c, hipGetLastError());
+		if (min_qual) { // (the counts come back with the sync below)
+			BAM_TRY(c, hipMemcpyAsync(&s->h_info->qual_bases, &s->d_info->qual_bases, 2 * sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+		}
 	}
 	BAM_TRY(c, hipEventRecord(s->ev[3], s->stream));
 	BAM_TRY(c, hipStreamSynchronize(s->stream));
+	nte_reads::min_qual_count(c, 0, s->h_info->qual_bases, s->h_info->masked_bases); // (zero unless the mask ran: the info is zeroed per chunk)
 	BAM_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
 	s->info.ms_decode += ms;
 	s->info.records += out.records;
@@ -721,11 +766,18 @@ int
 ntedit_hip_reads_bam_model(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, char* out, uint64_t cap,
                            ntedit_hip_reads_bam_result* res)
 {
-	if (!res || (n_raw && !raw) || (cap && !out)) {
+	return ntedit_hip_reads_bam_model_q(raw, n_raw, at_header, min_len, 0, out, cap, res);
+}
+
+int
+ntedit_hip_reads_bam_model_q(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, uint32_t min_qual, char* out, uint64_t cap,
+                             ntedit_hip_reads_bam_result* res)
+{
+	if (!res || (n_raw && !raw) || (cap && !out) || min_qual > nte_parse::RP_MAX_MIN_QUAL) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_bam_model: bad argument");
 	}
 	BamResult r;
-	bam_model((const u8*)raw, n_raw, at_header, min_len, out, cap, &r);
+	bam_model_q((const u8*)raw, n_raw, at_header, min_len, min_qual, out, cap, &r, nullptr);
 	to_result(r, res);
 	if (r.clean && r.text_len > cap) {
 		return pfail(nullptr, NTEDIT_E_OVERFLOW, "reads_bam_model: the text does not fit the buffer");

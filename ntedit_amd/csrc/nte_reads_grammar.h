@@ -1,6 +1,7 @@
 // nte_reads_grammar.h -- the clean grammar of --gpu_parse, written once: the class of a line, what makes a chunk clean,
-// and which records are kept.  The parse kernels (nte_reads_parse.hip) and the serial host model
-// (ntedit_hip_reads_parse_model, same unit) are both built from these functions, as nte_lanes.h serves the machine.
+// which records are kept, and what --min_qual makes of a base.  The parse kernels (nte_reads_parse.hip) and the serial
+// host model (rp_model of nte_reads_model.h: ntedit_hip_reads_parse_model) are both built from these functions, as
+// nte_lanes.h serves the machine.
 //
 // A chunk is a run of raw file bytes that starts at a record start.  Its kind is its first byte, '>' (FASTA) or '@'
 // (4-line FASTQ).  Lines are the runs between '\n'; bytes behind the last '\n' are a last line of their own.  The
@@ -20,7 +21,7 @@
 #include <stdint.h>
 
 #if defined(__HIP__) || defined(__HIPCC__)
-#define RP_HD __host__ __device__ __forceinline__
+#define RP_HD __host__ __device__ inline __attribute__((always_inline)) // (spelled out: a host source may see no HIP runtime header)
 #else
 #define RP_HD inline
 #endif
@@ -122,6 +123,33 @@ RP_HD bool
 rp_record_kept(uint64_t len, uint32_t k)
 {
 	return len >= k;
+}
+
+// --min_qual Q (1..93, 0: off): the byte a base enters the text as, given its quality -- 'N' below the minimum, else the
+// base.  `qual` is the Phred quality itself (a FASTQ byte less RP_QUAL_OFFSET, Phred+33; a BAM byte as stored); a FASTQ
+// byte below the offset is below every minimum.  Written once: the copy and decode kernels, the two models and the host
+// parser (FastaReader) all call it.
+constexpr int RP_QUAL_OFFSET = 33;
+constexpr uint32_t RP_MAX_MIN_QUAL = 93;
+
+// the one comparison: whether a base of this quality is masked
+RP_HD bool
+rp_masked(int qual, uint32_t min_qual)
+{
+	return qual < (int)min_qual;
+}
+
+// ... and the one place a masked base becomes 'N' (for a caller that counts what rp_masked said)
+RP_HD uint8_t
+rp_mask_base(uint8_t base, bool masked)
+{
+	return masked ? (uint8_t)'N' : base;
+}
+
+RP_HD uint8_t
+rp_mask_base(uint8_t base, int qual, uint32_t min_qual)
+{
+	return rp_mask_base(base, rp_masked(qual, min_qual));
 }
 
 } // namespace nte_parse

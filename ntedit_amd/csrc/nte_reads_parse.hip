@@ -1,7 +1,8 @@
 // nte_reads_parse.hip -- gfx950 kernels and C ABI of --gpu_parse: raw FASTA / FASTQ bytes in HBM to the batch text the
 // host parser (reads_pass.cpp) hands the reads kernels -- every read of k bases or more followed by '\n', in file order.
 // The grammar (line class, clean predicate, kept rule) is nte_reads_grammar.h; a chunk that breaks it is reported
-// unclean and left to the host parser.  ntedit_hip_reads_parse_model is the serial host model of the same functions.
+// unclean and left to the host parser.  ntedit_hip_reads_parse_model is the serial host model of the same functions
+// (rp_model of nte_reads_model.h).
 //
 // Phases, ordered by kernel boundaries on one stream (no hand-off between workgroups inside a launch):
 //   k_rp_tiles       per tile of 16 KiB (16-byte loads per lane): its number of '\n', and whether it holds a '\r'
@@ -16,7 +17,8 @@
 //   k_rp_line_out    each sequence line's offset in the text, and the '\n' behind each kept record
 //   k_rp_copy        byte-parallel over the raw tiles: each lane finds the line of its 16 bytes from the tile base and
 //                    the newline ranks, and writes them to that line's place (a line longer than a tile costs what
-//                    its bytes cost)
+//                    its bytes cost).  k_rp_copy<true> (--min_qual, FASTQ chunks) also masks each base of a sequence
+//                    line by the byte at the same offset of its quality line, two lines on
 // The scans are count / scan / write over blocks of 2048 items (as k_count_starts / k_scan_counts / k_write_starts).
 //
 // Genome FASTA (nte_genome_grammar.h: chunks cut anywhere, entered in a state) shares the line table and the copy:
@@ -30,6 +32,7 @@
 // Like nte_reads.hip this unit is outside KSRC and sees no context internals: its state hangs off the context pointer.
 #include "nte_common.h"
 #include "nte_reads_grammar.h"
+#include "nte_reads_model.h"
 #include "nte_genome_grammar.h"
 
 #include "../../include/ntedit_hip.h"
@@ -77,6 +80,8 @@ struct RpInfo // the small result the device keeps per chunk
 	// genome chunks only
 	u32 last_header1; // 1 + the raw offset of the last header line that begins in the chunk, 0: none
 	u32 state_out;
+	// --min_qual (k_rp_copy<true>): the bases copied that had a quality byte, and those of them masked
+	u64 qual_bases, masked_bases;
 };
 
 __host__ __device__ __forceinline__ u32
@@ -402,10 +407,16 @@ k_rp_line_out(const u8* __restrict__ cls, const u64* __restrict__ sr, const u32*
 	line_out[line] = out;
 }
 
+// MASK (--min_qual on a FASTQ chunk): a byte at offset j of sequence line L (L % 4 == 1, copied) is masked by the byte at
+// offset j of line L + 2 (rp_mask_base).  The copy is queued before the chunk is known clean, so nothing the grammar
+// promises is relied on for memory safety: line L + 2 has to be in the table and the quality address below n, else the
+// base passes as it is.  The counts are summed per wavefront and added to info by one atomic each per wavefront.
+template <bool MASK>
 __global__ __launch_bounds__(RP_TPB) void
 k_rp_copy(const u8* __restrict__ raw, u64 n, const u64* __restrict__ tile_base, const u32* __restrict__ line_end,
-          const u32* __restrict__ line_out, u64 n_lines, u8* __restrict__ text, u64 text_cap)
+          const u32* __restrict__ line_out, u64 n_lines, u8* __restrict__ text, u64 text_cap, u32 min_qual, RpInfo* info)
 {
+	u32 n_qual = 0, n_masked = 0;
 	u32 mask[RP_IT], before[RP_IT];
 	uint4 bytes[RP_IT];
 	const u64 tile_off = (u64)blockIdx.x * RP_TILE;
@@ -424,7 +435,15 @@ k_rp_copy(const u8* __restrict__ raw, u64 n, const u64* __restrict__ tile_base, 
 		const u32 w[4] = { bytes[j].x, bytes[j].y, bytes[j].z, bytes[j].w };
 		u32 out = line_out[line];
 		// text position of raw byte p of this line: p + delta (32-bit wrap-around is exact: the result is in range)
-		u32 delta = out - rp_line_start(line_end, line);
+		const u32 start = rp_line_start(line_end, line);
+		u32 delta = out - start;
+		// quality address of raw byte p of this line: p + qdelta (the quality line lies behind: no wrap-around)
+		bool has_qual = false;
+		u32 qdelta = 0;
+		if (MASK && out != RP_NONE && (line & 3) == 1 && line + 2 < n_lines) {
+			has_qual = true;
+			qdelta = rp_line_start(line_end, line + 2) - start;
+		}
 		const u32 m = mask[j];
 #pragma unroll
 		for (int b = 0; b < 16; b++) {
@@ -438,14 +457,40 @@ k_rp_copy(const u8* __restrict__ raw, u64 n, const u64* __restrict__ tile_base, 
 				}
 				out = line_out[line];
 				delta = out - (u32)(off + b + 1);
+				if (MASK) {
+					has_qual = out != RP_NONE && (line & 3) == 1 && line + 2 < n_lines;
+					qdelta = has_qual ? rp_line_start(line_end, line + 2) - (u32)(off + b + 1) : 0;
+				}
 				continue;
 			}
 			if (out != RP_NONE) {
 				const u32 at = (u32)(off + b) + delta;
+				u8 ch = (u8)(w[b >> 2] >> (8 * (b & 3)));
+				if (MASK && has_qual) {
+					const u64 qa = off + b + (u64)qdelta;
+					if (qa < n) {
+						const int q = (int)raw[qa] - RP_QUAL_OFFSET;
+						const bool low = rp_masked(q, min_qual);
+						n_qual++;
+						n_masked += low;
+						ch = rp_mask_base(ch, low);
+					}
+				}
 				if (at < text_cap) {
-					text[at] = (u8)(w[b >> 2] >> (8 * (b & 3)));
+					text[at] = ch;
 				}
 			}
+		}
+	}
+	if (MASK) {
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			n_qual += __shfl_xor(n_qual, d, 64);
+			n_masked += __shfl_xor(n_masked, d, 64);
+		}
+		if ((threadIdx.x & 63) == 0 && n_qual) {
+			atomicAdd((unsigned long long*)&info->qual_bases, (unsigned long long)n_qual);
+			atomicAdd((unsigned long long*)&info->masked_bases, (unsigned long long)n_masked);
 		}
 	}
 }
@@ -502,6 +547,8 @@ struct ParseState
 {
 	const ntedit_hip_ctx* owner = nullptr;
 	int on = 0; // ntedit_hip_reads_set_device_parse
+	u32 min_qual = 0;                        // ntedit_hip_reads_set_min_qual (0: off)
+	u64 qual_bases = 0, masked_bases = 0;    // ntedit_hip_reads_min_qual_info: the last pass, host parser and device
 	ntedit_hip_reads_parse_stats info = {};
 	ntedit_hip_genome_pass_info ginfo = {}; // ntedit_hip_genome_pass
 	// device scratch, grow-only, released by ntedit_hip_sketch_free
@@ -587,9 +634,14 @@ release_scratch(ParseState* s)
 	const int on = s->on;
 	const ntedit_hip_reads_parse_stats info = s->info;
 	const ntedit_hip_genome_pass_info ginfo = s->ginfo;
+	const u32 min_qual = s->min_qual;
+	const u64 qual_bases = s->qual_bases, masked_bases = s->masked_bases;
 	*s = ParseState();
 	s->owner = owner;
 	s->on = on;
+	s->min_qual = min_qual;
+	s->qual_bases = qual_bases;
+	s->masked_bases = masked_bases;
 	s->info = info;
 	s->ginfo = ginfo;
 }
@@ -738,8 +790,13 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 	scan(s, t.rec, lines, t.bsum);
 	hipLaunchKernelGGL(k_rp_line_out, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, t.head_line, t.rec, lines, t.line_out,
 	                   d_text, text_cap, s->d_info);
-	hipLaunchKernelGGL(k_rp_copy, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out, lines,
-	                   d_text, text_cap);
+	if (s->min_qual && res->kind == '@') { // (a FASTA chunk has no qualities: the copy without the mask)
+		hipLaunchKernelGGL(k_rp_copy<true>, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out,
+		                   lines, d_text, text_cap, s->min_qual, s->d_info);
+	} else {
+		hipLaunchKernelGGL(k_rp_copy<false>, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out,
+		                   lines, d_text, text_cap, 0u, s->d_info);
+	}
 	RP_TRY(c, hipGetLastError());
 	RP_TRY(c, hipEventRecord(s->ev[3], s->stream));
 	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(RpInfo), hipMemcpyDeviceToHost, s->stream));
@@ -750,6 +807,8 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 	if (res->broken) {
 		return 0;
 	}
+	s->qual_bases += s->h_info->qual_bases; // (zero without --min_qual: the chunk's info is zeroed, and only the mask adds)
+	s->masked_bases += s->h_info->masked_bases;
 	res->clean = 1;
 	res->text_len = lo32(s->h_info->records);
 	res->reads = hi32(s->h_info->records);
@@ -814,8 +873,8 @@ genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n,
 	scan(s, t.sr, lines, t.bsum);
 	hipLaunchKernelGGL(k_gp_line_out, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, lines, t.line_out, d_text, text_cap,
 	                   s->d_info);
-	hipLaunchKernelGGL(k_rp_copy, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out, lines,
-	                   d_text, text_cap);
+	hipLaunchKernelGGL(k_rp_copy<false>, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out,
+	                   lines, d_text, text_cap, 0u, s->d_info); // (a genome is never masked)
 	RP_TRY(c, hipGetLastError());
 	RP_TRY(c, hipEventRecord(s->ev[3], s->stream));
 	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(RpInfo), hipMemcpyDeviceToHost, s->stream));
@@ -1111,6 +1170,26 @@ ntedit_hip_genome_parse_model(const char* raw, uint64_t n_raw, int state_in, int
 
 namespace nte_reads {
 
+// --min_qual: the context's setting, and the counts of the last pass (the pass zeroes them; the host parser and the BAM
+// unit add theirs)
+uint32_t
+min_qual(const ntedit_hip_ctx* c)
+{
+	ParseState* s = parse_state(c, false);
+	return s ? s->min_qual : 0;
+}
+
+void
+min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases)
+{
+	ParseState* s = parse_state(c, true);
+	if (reset) {
+		s->qual_bases = s->masked_bases = 0;
+	}
+	s->qual_bases += qual_bases;
+	s->masked_bases += masked_bases;
+}
+
 int
 parse_is_on(const ntedit_hip_ctx* c)
 {
@@ -1185,6 +1264,28 @@ ntedit_hip_reads_set_device_parse(ntedit_hip_ctx* c, int on)
 }
 
 int
+ntedit_hip_reads_set_min_qual(ntedit_hip_ctx* c, uint32_t q)
+{
+	if (!c || q > RP_MAX_MIN_QUAL) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_set_min_qual: the minimum base quality is 0 (off) or between 1 and 93") : NTEDIT_E_ARG;
+	}
+	parse_state(c, true)->min_qual = q;
+	return 0;
+}
+
+int
+ntedit_hip_reads_min_qual_info(ntedit_hip_ctx* c, uint64_t* qual_bases, uint64_t* masked_bases)
+{
+	if (!c || !qual_bases || !masked_bases) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_min_qual_info: bad argument") : NTEDIT_E_ARG;
+	}
+	ParseState* s = parse_state(c, true);
+	*qual_bases = s->qual_bases;
+	*masked_bases = s->masked_bases;
+	return 0;
+}
+
+int
 ntedit_hip_reads_parse_info(ntedit_hip_ctx* c, ntedit_hip_reads_parse_stats* st)
 {
 	if (!c || !st) {
@@ -1224,63 +1325,25 @@ ntedit_hip_reads_parse_device(ntedit_hip_ctx* c, const char* raw, uint64_t n_raw
 	return parse_on_device(c, s, d_raw, n_raw, k, (u8*)text_device, text_cap, res);
 }
 
-// the serial model: the same grammar functions, one line after the other
 int
 ntedit_hip_reads_parse_model(const char* raw, uint64_t n_raw, uint32_t k, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res)
 {
-	if (!res || (n_raw && !raw) || (cap && !out) || k == 0) {
+	return ntedit_hip_reads_parse_model_q(raw, n_raw, k, 0, out, cap, res);
+}
+
+// the serial model (rp_model, nte_reads_model.h): the same grammar functions, one line after the other
+int
+ntedit_hip_reads_parse_model_q(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* out, uint64_t cap,
+                               ntedit_hip_reads_parse_result* res)
+{
+	if (!res || (n_raw && !raw) || (cap && !out) || k == 0 || min_qual > RP_MAX_MIN_QUAL) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_parse_model: bad argument");
 	}
-	*res = ntedit_hip_reads_parse_result();
-	if (n_raw == 0) {
-		res->clean = 1;
-		return 0;
-	}
-	const int kind = (unsigned char)raw[0];
-	uint32_t broken = memchr(raw, '\r', n_raw) ? (uint32_t)RP_BAD_CR : 0u;
-	uint64_t lines = 0, used = 0, reads = 0, bases = 0, seq_len = 0;
-	std::string cur;
-	bool open = false;
-	auto flush = [&]() {
-		if (open && rp_record_kept(cur.size(), k)) {
-			if (used + cur.size() + 1 <= cap) {
-				memcpy(out + used, cur.data(), cur.size());
-				out[used + cur.size()] = '\n';
-			}
-			used += cur.size() + 1;
-			reads++;
-			bases += cur.size();
-		}
-		cur.clear();
-	};
-	for (uint64_t s = 0; s < n_raw; lines++) {
-		const char* nl = (const char*)memchr(raw + s, '\n', n_raw - s);
-		const uint64_t e = nl ? (uint64_t)(nl - raw) : n_raw;
-		const int c = rp_line_class(kind, lines, e > s ? (int)(unsigned char)raw[s] : -1, &broken);
-		if (c == RP_HEADER) {
-			flush();
-			open = true;
-		} else if (c == RP_SEQ) {
-			cur.append(raw + s, e - s);
-			seq_len = e - s;
-		} else if (kind == '@' && lines % 4 == 3) {
-			broken |= rp_quality_broken(seq_len, e - s);
-		}
-		s = e + 1;
-	}
-	flush();
-	broken |= rp_chunk_broken(kind, n_raw, lines);
-	res->kind = kind;
-	res->lines = lines;
-	res->broken = broken;
-	if (broken) {
-		return 0;
-	}
-	res->clean = 1;
-	res->text_len = used;
-	res->reads = reads;
-	res->bases = bases;
-	return used > cap ? NTEDIT_E_OVERFLOW : 0;
+	RpResult m;
+	const bool fits = rp_model(raw, n_raw, k, min_qual, out, cap, &m);
+	static_assert(sizeof(ntedit_hip_reads_parse_result) == sizeof(RpResult), "the result is the grammar's, field for field");
+	memcpy(res, &m, sizeof m);
+	return fits ? 0 : NTEDIT_E_OVERFLOW;
 }
 
 } // extern "C"

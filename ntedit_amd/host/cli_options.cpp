@@ -116,6 +116,22 @@ static const char HELP_BGZIP[] = PROGRAM
     "			members; --report adds {\"bgzip\": {...}}.  Not with --shard\n"
     "	--help-bgzip,	display this paragraph and exit\n\n";
 
+static const char HELP_MIN_QUAL[] = PROGRAM
+    " --reads --min_qual\n\n"
+    "	--min_qual Q,	with --reads: the minimum base quality, 1 to 93.  A base whose Phred quality is below Q enters the reads\n"
+    "			filter's build as N, so no k-mer that spans it is counted, and none is kept: a defence against sequencing\n"
+    "			errors beside --cutoff / --solid, for low-coverage reads, ONT reads and the 3' tails of Illumina reads.\n"
+    "			Phred+33: in FASTQ a quality character below 33 + Q, in BAM (--gpu_parse) a quality byte below Q; Phred+64\n"
+    "			is not built.  Reads are kept by their length as before, masked bases included; records without qualities\n"
+    "			(FASTA records, BAM records whose qualities are absent) pass as they are, and mixed inputs are legal.  The\n"
+    "			host parser and --gpu_parse (plain, BGZF and BAM, where the copy and decode kernels mask in HBM) give the\n"
+    "			same filter: the one ntedit-make-reads-bf --min_qual Q writes, and the one a build without the option\n"
+    "			makes of the same reads with those bases rewritten to N.  With -k K1,K2,... every round masks alike (the\n"
+    "			reads kept in HBM are the masked ones).  Each pass over the files reports `--min_qual Q: M of B bases with\n"
+    "			a quality masked'; --report adds \"min_qual\" to each pass of the reads build.  Not with --genome or -r.\n"
+    "			Not built: trimming instead of masking, per-read mean-quality filters, BAM tag filters such as rq\n"
+    "	--help-min-qual,	display this paragraph and exit\n\n";
+
 static const char HELP_BED[] = PROGRAM
     " --qv --bed\n\n"
     "	--bed,		with --qv: where the k-mers that --qv counts as absent lie, as two BED tracks -- <prefix>_absent_before.bed in\n"
@@ -213,7 +229,9 @@ enum
 	OPT_CN,
 	OPT_CN_STORE,
 	OPT_CN_SKETCH,
-	OPT_HELP_CN
+	OPT_HELP_CN,
+	OPT_MIN_QUAL,
+	OPT_HELP_MIN_QUAL
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -277,6 +295,8 @@ static const struct option longopts[] = {
 	{ "cn_store", required_argument, nullptr, OPT_CN_STORE },
 	{ "cn_sketch", required_argument, nullptr, OPT_CN_SKETCH },
 	{ "help-cn", no_argument, nullptr, OPT_HELP_CN },
+	{ "min_qual", required_argument, nullptr, OPT_MIN_QUAL },
+	{ "help-min-qual", no_argument, nullptr, OPT_HELP_MIN_QUAL },
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -310,6 +330,7 @@ static const ReadsOption READS_OPTIONS[] = {
 	{ OPT_READS_BATCH, "--batch_bytes", true, &ntedit_hip_reads_options::batch_bytes },
 	{ OPT_STORE_CAP, "--resident_cap", false, &ntedit_hip_reads_options::store_cap },
 	{ OPT_GPU_PARSE, "--gpu_parse", true, nullptr },
+	{ OPT_MIN_QUAL, "--min_qual", false, &ntedit_hip_reads_options::min_qual },
 };
 
 static void
@@ -632,6 +653,9 @@ parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOptio
 			break;
 		case OPT_HELP_CN:
 			fputs(HELP_CN, stderr);
+			exit(EXIT_SUCCESS);
+		case OPT_HELP_MIN_QUAL:
+			fputs(HELP_MIN_QUAL, stderr);
 			exit(EXIT_SUCCESS);
 		case OPT_HELP:
 			fputs(USAGE, stderr);

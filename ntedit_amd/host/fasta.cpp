@@ -1,5 +1,6 @@
 #include "fasta.h"
 #include "gunzip.h"
+#include "../csrc/nte_reads_grammar.h" // (rp_mask_base: the one rule of --min_qual)
 
 #include <atomic>
 #include <cctype>
@@ -328,6 +329,7 @@ bool
 FastaReader::next(std::string& header, std::string& seq)
 {
 	int c;
+	qual_bases_ = masked_bases_ = 0;
 	if (failed_ || !ok()) {
 		return false;
 	}
@@ -402,6 +404,15 @@ FastaReader::next(std::string& header, std::string& seq)
 			next_start_ = ~0ull;
 			seq.resize(base);
 			return false;
+		}
+		if (min_qual_) {
+			for (size_t i = 0; i < want; i++) {
+				const int q = (int)(unsigned char)line_[i] - nte_parse::RP_QUAL_OFFSET;
+				const bool low = nte_parse::rp_masked(q, min_qual_);
+				masked_bases_ += low;
+				seq[base + i] = (char)nte_parse::rp_mask_base((uint8_t)seq[base + i], low);
+			}
+			qual_bases_ = want;
 		}
 	}
 	return true;

@@ -41,8 +41,17 @@ class FastaReader
 	unsigned long long next_start() const { return next_start_; }
 	// before the first next(): n bytes of the (inflated) input are read and dropped; offsets keep counting them
 	void skip(unsigned long long n);
+	// --min_qual (the reads passes alone; off by default, and a draft or a genome never sets it): next() masks the bases
+	// of a FASTQ record by the quality string it walks anyway, the i-th quality character after concatenation against
+	// the i-th base (nte_reads_grammar.h: rp_mask_base, Phred+33); a FASTA record passes as it is
+	void set_min_qual(unsigned q) { min_qual_ = q; }
+	// of the record the last next() returned: the bases that had a quality, and those of them below the minimum
+	unsigned long long qual_bases() const { return qual_bases_; }
+	unsigned long long masked_bases() const { return masked_bases_; }
 
   private:
+	unsigned min_qual_ = 0;
+	unsigned long long qual_bases_ = 0, masked_bases_ = 0;
 	bool fill_();
 	int getc_();
 	bool getline_(std::string& out, size_t base, bool strip_cr);

@@ -2,7 +2,7 @@
 //
 //   --reads FILE [FILE ...]  -k K  (-c CMIN | --solid)  [--hist FILE]  [--counts]  [--hashes 3]  [--fpr 0.01]
 //   [--bf BYTES | --num_elements N]  [--sketch_bytes S]  [-o reads_kK.bf]  [-t THREADS]
-//   [--reject_cutoff R  [--reject_bf BYTES | --reject_num_elements N]  [--reject_out reads_kK_reject.bf]]
+//   [--reject_cutoff R  [--reject_bf BYTES | --reject_num_elements N]  [--reject_out reads_kK_reject.bf]]  [--min_qual Q]
 //
 // The reference leaves this step to ntHits / ntStat on the CPU (ntedit-make: `nthits -c<cutoff> --outbloom`;
 // ntedit_run_pipeline.smk: `ntstat filter -cmin C`).  This tool is neither: it counts in a plain count-min sketch of
@@ -46,7 +46,7 @@ usage(const char* why)
 	std::cerr
 	    << "Usage: make_reads_bf [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] [--counts] [--hashes VAR] "
 	       "[--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] [-t VAR] "
-	       "[--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR]\n\n"
+	       "[--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR] [--min_qual VAR]\n\n"
 	       "Builds the k-mer filter of a read set on the GPU: pass 1 counts every k-mer in a count-min sketch of 8-bit\n"
 	       "counters, pass 2 keeps the k-mers whose estimate (the minimum of their counters) is at least -c.  Neither\n"
 	       "ntHits nor ntStat: the counts (plain count-min, no conservative update) and the sizing are this tool's own.\n"
@@ -85,7 +85,11 @@ usage(const char* why)
 	       "  --reject_num_elements  Approximate number of k-mers in the reject filter (sized as --num_elements, with\n"
 	       "                  --fpr) (one of the two is required with --reject_cutoff, unless --solid or --hist: then by\n"
 	       "                  default it is the number of k-mers the histogram puts at the reject cutoff or above)\n"
-	       "  --reject_out    Name for the reject filter [default: \"reads_k<K>_reject.bf\"]\n";
+	       "  --reject_out    Name for the reject filter [default: \"reads_k<K>_reject.bf\"]\n"
+	       "  --min_qual      Minimum base quality, 1 to 93 (Phred+33; Phred+64 is not built): a base whose quality is below\n"
+	       "                  it counts as N, so no k-mer that spans it is counted or kept.  FASTQ: a quality character below\n"
+	       "                  33 + Q; BAM: a quality byte below Q.  Reads are still kept by their length; records without\n"
+	       "                  qualities (FASTA, BAM records whose qualities are absent) pass as they are [default: off]\n";
 }
 
 static bool
@@ -169,6 +173,8 @@ main(int argc, char** argv)
 			given("--reject_bf", ro.reject_bf);
 		} else if (a == "--reject_num_elements") {
 			given("--reject_num_elements", ro.reject_num_elements);
+		} else if (a == "--min_qual") {
+			given("--min_qual", ro.min_qual);
 		} else if (a == "--reject_out") {
 			reject_out = value("--reject_out");
 			ro.reject_out = 1;
@@ -240,6 +246,9 @@ main(int argc, char** argv)
 			std::cout << "\t\t--reject_num_elements " << rr.reject_num_elements << std::endl;
 		}
 	}
+	if (rr.min_qual) {
+		std::cout << "\t\t--min_qual " << rr.min_qual << std::endl;
+	}
 	if (refused) { // (the output filter would be empty)
 		usage(ntedit_hip_reads_last_error(nullptr));
 		return 1;
@@ -281,6 +290,7 @@ main(int argc, char** argv)
 	ba.reject_cmin = rr.reject_cmin;
 	ba.reject_bf_bytes = rr.reject_bf_bytes;
 	ba.reject_num_elements = rr.reject_num_elements;
+	ba.min_qual = rr.min_qual;
 	ntedit_hip_reads_build_result br;
 	if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));

@@ -91,6 +91,12 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 	         (unsigned long long)st.bases, st.ms_wall, st.ms_wall > 0 ? st.bases / st.ms_wall / 1e6 : 0.0, st.ms_gpu,
 	         st.ms_gpu > 0 ? st.bases / st.ms_gpu / 1e6 : 0.0);
 	lg.rank_info(lg.ranged() || from_store ? line + (", " + what) : line);
+	uint64_t qual_bases = 0, masked_bases = 0;
+	if (a->min_qual && read_files && ntedit_hip_reads_min_qual_info(ctx, &qual_bases, &masked_bases) == 0) {
+		// the pass's one line about --min_qual (the tests read it)
+		lg.rank_info("--min_qual " + std::to_string(a->min_qual) + ": " + std::to_string(masked_bases) + " of " + std::to_string(qual_bases) +
+		             " bases with a quality masked");
+	}
 	ntedit_hip_reads_parse_stats ps;
 	if (a->device_parse && read_files && ntedit_hip_reads_parse_info(ctx, &ps) == 0) {
 		// the pass's one line about --gpu_parse (the tests read it)
@@ -159,7 +165,7 @@ end_build(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, const ntedi
 bool
 bad_build_args(const ntedit_hip_reads_build_args* a, const ntedit_hip_reads_build_result* r)
 {
-	return !a || !r || (a->n_files && !a->files) || (a->begins && !a->ends) || a->batch_bytes < 4096 ||
+	return !a || !r || (a->n_files && !a->files) || (a->begins && !a->ends) || a->batch_bytes < 4096 || a->min_qual > 93 ||
 	       (!a->solid && (a->cmin < 1 || a->cmin > 255)) || (a->bf_bytes == 0 && !a->solid && !a->hist_path) ||
 	       (a->reject_cmin && (a->reject_cmin > 255 || a->counts || (a->reject_bf_bytes == 0 && !a->solid && !a->hist_path)));
 }
@@ -178,6 +184,7 @@ ntedit_hip_reads_stage_count(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_a
 	const BuildLog lg{ a };
 	*r = ntedit_hip_reads_build_result();
 	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
+	ntedit_hip_reads_set_min_qual(ctx, a->min_qual);
 	// a store an earlier build left ON (keep_store): this build's three passes read it, and no file is opened
 	ntedit_hip_resident_stats at_entry;
 	const bool from_store = !lg.ranged() && a->use_store && ntedit_hip_resident_info(ctx, &at_entry) == 0 &&
@@ -238,6 +245,7 @@ ntedit_hip_reads_stage_histogram(ntedit_hip_ctx* ctx, const ntedit_hip_reads_bui
 	}
 	const BuildLog lg{ a };
 	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
+	ntedit_hip_reads_set_min_qual(ctx, a->min_qual);
 	lg.rank_info("Histogram pass: the k-mer histogram of the sketch's estimates");
 	if (build_pass(ctx, a, NTEDIT_READS_PASS_HIST, r, nullptr, nullptr) != 0) {
 		return NTEDIT_E_IO;
@@ -342,6 +350,7 @@ ntedit_hip_reads_stage_insert(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_
 		return NTEDIT_E_ARG;
 	}
 	ntedit_hip_reads_set_device_parse(ctx, a->device_parse);
+	ntedit_hip_reads_set_min_qual(ctx, a->min_qual);
 	lg.rank_info("Pass 2: inserting k-mers seen at least " + std::to_string(r->cmin) + " times" +
 	             (a->reject_cmin ? ", and into the reject filter those seen at least " + std::to_string(a->reject_cmin) + " times" : ""));
 	const int rc = build_pass(ctx, a, NTEDIT_READS_PASS_SOLID, r, nullptr, nullptr);

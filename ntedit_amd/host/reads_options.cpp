@@ -58,7 +58,7 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 	r->store_cap = NTEDIT_READS_RESIDENT_CAP_DEFAULT;
 	r->threads = 12;
 	r->gpu_parse = o->gpu_parse ? 1 : 0; // (the one rule about it, "only with --reads", is the polisher front ends': they know)
-	uint64_t k = 0, cmin = 0, hashes = r->hash_num, reject = 0;
+	uint64_t k = 0, cmin = 0, hashes = r->hash_num, reject = 0, min_qual = 0;
 	// -k: the tool refuses a malformed one at the option, the polisher takes it as out of range
 	if (final && !o->k) {
 		return refuse(NTEDIT_READS_REFUSED, "-k: required" + with_reads);
@@ -87,7 +87,7 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 	    malformed("--sketch_bytes", o->sketch_bytes, &r->sketch_bytes) || malformed("--batch_bytes", o->batch_bytes, &r->batch_bytes) ||
 	    malformed("--resident_cap", o->store_cap, &r->store_cap) || malformed("-t", o->threads, &r->threads) ||
 	    malformed("--reject_cutoff", o->reject_cutoff, &reject) || malformed("--reject_bf", o->reject_bf, &r->reject_bf_bytes) ||
-	    malformed("--reject_num_elements", o->reject_num_elements, &r->reject_num_elements)) {
+	    malformed("--reject_num_elements", o->reject_num_elements, &r->reject_num_elements) || malformed("--min_qual", o->min_qual, &min_qual)) {
 		return NTEDIT_READS_NOT_A_NUMBER;
 	}
 	if (!final) {
@@ -168,6 +168,11 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 			return refuse(NTEDIT_READS_REFUSED, "--reject_bf / --reject_num_elements: the reject filter would be empty" + dot);
 		}
 	}
+	// --min_qual: a Phred quality, Phred+33 in FASTQ (a quality byte from '!' to '~')
+	if (o->min_qual && (min_qual < 1 || min_qual > 93)) {
+		return refuse(NTEDIT_READS_REFUSED, "--min_qual " + std::to_string(min_qual) + ": the minimum base quality must be between 1 and 93" + dot);
+	}
+	r->min_qual = (uint32_t)min_qual;
 	if (empty) { // (the tool has printed its parameters by then)
 		return refuse(NTEDIT_READS_EMPTY, "The output filter would be empty (--bf 0 or --num_elements too small).");
 	}

@@ -51,6 +51,9 @@ int inflate_carry(const ntedit_hip_ctx* c, uint64_t cut, uint64_t total);
 ntedit_hip_reads_bam_stats* bam_info(const ntedit_hip_ctx* c);
 int bam_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, int at_header, uint32_t min_len, const char** text,
                ntedit_hip_reads_bam_result* res);
+// --min_qual (nte_reads_parse.hip): the context's setting, which the device parsers read themselves, and the pass's counts
+uint32_t min_qual(const ntedit_hip_ctx* c);
+void min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases);
 }
 
 namespace {
@@ -146,10 +149,13 @@ find_record_start(const char* path, uint64_t begin, uint64_t* out, std::string* 
 	return true;
 }
 
-// every record of one range, in order: seq(record) for each; *start / *next as ntedit_hip_reads_pass reports them
+// every record of one range, in order: seq_fn(record, its bases that had a quality, those of them masked) for each, the
+// record masked by min_qual (0: off, and the two counts are 0); *start / *next as ntedit_hip_reads_pass reports them
+using SeqFn = std::function<bool(const std::string&, uint64_t, uint64_t)>;
+
 bool
-read_range(const char* path, uint64_t begin, uint64_t end, const std::function<bool(const std::string&)>& seq_fn,
-           uint64_t* start, uint64_t* next, std::string* why, bool exact = false, uint64_t skip = 0)
+read_range(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, const SeqFn& seq_fn, uint64_t* start, uint64_t* next,
+           std::string* why, bool exact = false, uint64_t skip = 0)
 {
 	uint64_t s = exact ? begin : 0; // exact: begin is a record start (where --gpu_parse hands a range back)
 	if (skip) {
@@ -182,13 +188,14 @@ read_range(const char* path, uint64_t begin, uint64_t end, const std::function<b
 		return false;
 	}
 	reader.skip(skip);
+	reader.set_min_qual(min_qual);
 	std::string hdr, seq;
 	for (;;) {
 		seq.clear();
 		if (!reader.next(hdr, seq)) {
 			break;
 		}
-		if (!seq_fn(seq)) {
+		if (!seq_fn(seq, reader.qual_bases(), reader.masked_bases())) {
 			return false;
 		}
 	}
@@ -215,6 +222,8 @@ struct BatchProducer
 	unsigned k;
 	size_t batch_bytes;
 	uint64_t *starts, *nexts;
+	unsigned min_qual;
+	uint64_t* qual_counts; // [2], of the records kept: with a quality, masked (read once the feed has ended)
 
 	void operator()(Feed<Batch>& feed) const
 	{
@@ -227,11 +236,15 @@ struct BatchProducer
 			uint64_t start = 0, next = 0;
 			bool stopped = false;
 			std::string why;
-			auto add = [&](const std::string& seq) {
+			auto add = [&](const std::string& seq, uint64_t with_qual, uint64_t masked) {
 				stopped = !nte_host::batch_add(feed, b, seq, k, batch_bytes);
+				if (seq.size() >= k) { // (what batch_add keeps)
+					qual_counts[0] += with_qual;
+					qual_counts[1] += masked;
+				}
 				return !stopped;
 			};
-			const bool ok = read_range(r.path, r.begin, r.end, add, &start, &next, &why, r.exact, r.skip);
+			const bool ok = read_range(r.path, r.begin, r.end, min_qual, add, &start, &next, &why, r.exact, r.skip);
 			if (stopped) {
 				return; // (batch_add failed the feed, or it is being torn down)
 			}
@@ -267,6 +280,7 @@ struct Pass
 	uint32_t cmin, rmin; // SOLID: the cutoff, and the reject cutoff when one is set (both slots are filled then)
 	uint32_t keep;       // the shortest record the parsers keep: the sketch's k, or below it what ntedit_hip_reads_set_min_read asks for
 	uint64_t batch_bytes;
+	uint32_t min_qual;   // ntedit_hip_reads_set_min_qual (the host parser's part: the device parsers read the context's setting)
 	uint64_t bases = 0;
 	double gpu_ms = 0.0;
 	ntedit_hip_reads_parse_stats* info;
@@ -285,7 +299,8 @@ struct Pass
 	// the host parser over some ranges (all of them, without --gpu_parse)
 	int host_ranges(const std::vector<Range>& rs, uint64_t* rs_starts, uint64_t* rs_nexts)
 	{
-		Feed<Batch> feed(BatchProducer{ rs, keep, (size_t)batch_bytes, rs_starts, rs_nexts });
+		uint64_t counts[2] = { 0, 0 };
+		Feed<Batch> feed(BatchProducer{ rs, keep, (size_t)batch_bytes, rs_starts, rs_nexts, min_qual, counts });
 		for (;;) {
 			Batch* b = feed.take();
 			if (!b) {
@@ -301,6 +316,7 @@ struct Pass
 			const bool last = b->last;
 			feed.give_back(b);
 			if (last) {
+				nte_reads::min_qual_count(ctx, 0, counts[0], counts[1]); // (the producer is through: its last batch came after them)
 				return 0;
 			}
 		}
@@ -544,7 +560,9 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 		return pfail(ctx, NTEDIT_E_ARG, "reads_pass: no sketch (ntedit_hip_sketch_alloc / _set_device)");
 	}
 	const auto t0 = std::chrono::steady_clock::now();
-	Pass p{ ctx, pass, cmin, pass == NTEDIT_READS_PASS_SOLID ? nte_reads::reject_cutoff(ctx) : 0, nte_reads::min_read(ctx, k), batch_bytes };
+	Pass p{ ctx, pass, cmin, pass == NTEDIT_READS_PASS_SOLID ? nte_reads::reject_cutoff(ctx) : 0, nte_reads::min_read(ctx, k), batch_bytes,
+		    nte_reads::min_qual(ctx) };
+	nte_reads::min_qual_count(ctx, 1, 0, 0);
 	if (!nte_reads::parse_is_on(ctx)) {
 		for (const Range& r : ranges) { // (the host parser would read whatever '@' and '>' bytes the binary stream holds)
 			if (ntedit_hip_reads_is_bam(r.path)) {
@@ -593,12 +611,19 @@ int
 ntedit_hip_reads_range_text(const char* path, uint64_t begin, uint64_t end, char* out, uint64_t cap, uint64_t* len,
                             uint64_t* reads, uint64_t* start, uint64_t* next)
 {
-	if (!path || !len || !reads || !start || !next || begin > end || (cap && !out)) {
+	return ntedit_hip_reads_range_text_q(path, begin, end, 0, out, cap, len, reads, start, next);
+}
+
+int
+ntedit_hip_reads_range_text_q(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, char* out, uint64_t cap, uint64_t* len,
+                              uint64_t* reads, uint64_t* start, uint64_t* next)
+{
+	if (!path || !len || !reads || !start || !next || begin > end || (cap && !out) || min_qual > 93) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_range_text: bad argument");
 	}
 	uint64_t used = 0, count = 0;
 	std::string why;
-	const bool ok = read_range(path, begin, end, [&](const std::string& seq) {
+	const bool ok = read_range(path, begin, end, min_qual, [&](const std::string& seq, uint64_t, uint64_t) {
 		if (used + seq.size() + 1 <= cap) {
 			memcpy(out + used, seq.data(), seq.size());
 			out[used + seq.size()] = '\n';

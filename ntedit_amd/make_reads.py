@@ -36,7 +36,8 @@ RESIDENT_CAP_DEFAULT = _lib.READS_RESIDENT_CAP_DEFAULT  # the resident store's c
 
 USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] "
          "[--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] "
-         "[-t VAR] [--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR] [--no-split] "
+         "[-t VAR] [--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR] [--min_qual VAR] "
+         "[--no-split] "
          "[--backend VAR]\n\n"
          "ntedit-make-reads-bf on N processes (python -m torch.distributed.run --nproc-per-node N -m "
          "ntedit_amd.make_reads ...): the same flags, the same output bytes.\n"
@@ -47,6 +48,8 @@ USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR 
          "  --gpu_parse     parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes,\n"
          "                  BGZF still compressed; same output (single-stream gzip stays with the host parser).  BAM files,\n"
          "                  unaligned or aligned, need it; a BAM is read whole by one process, as gzip files are\n"
+         "  --min_qual      minimum base quality, 1 to 93 (Phred+33; Phred+64 is not built): a base below it counts as N in\n"
+         "                  every rank alike, so the output bytes are the same for every world size\n"
          "  --backend       torch.distributed backend (default nccl = RCCL; gloo: N ranks may share a GPU)\n"
          "ntedit-make-reads-bf --help describes the other flags.\n")
 
@@ -79,7 +82,8 @@ def check_options(dialect, given, final, reads=(), solid=False, hist="", gpu_par
                 batch_bytes=r.batch_bytes, store_cap=r.store_cap, threads=r.threads, gather_hist=bool(r.gather_hist),
                 size_from_hist=bool(r.size_from_hist), bf_bytes=r.bf_bytes, sketch=r.sketch_counters, empty=why,
                 gpu_parse=bool(r.gpu_parse), reject_cmin=r.reject_cmin, reject_bf_bytes=r.reject_bf_bytes,
-                reject_num_elements=r.reject_num_elements, reject_size_from_hist=bool(r.reject_size_from_hist))
+                reject_num_elements=r.reject_num_elements, reject_size_from_hist=bool(r.reject_size_from_hist),
+                min_qual=r.min_qual)
 
 
 def parse(argv):
@@ -87,7 +91,7 @@ def parse(argv):
     texts = {"-k": "k", "-c": "cutoff", "--hashes": "hashes", "--fpr": "fpr", "--bf": "bf",
              "--num_elements": "num_elements", "--sketch_bytes": "sketch_bytes", "-t": "threads",
              "--batch_bytes": "batch_bytes", "--reject_cutoff": "reject_cutoff", "--reject_bf": "reject_bf",
-             "--reject_num_elements": "reject_num_elements"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
+             "--reject_num_elements": "reject_num_elements", "--min_qual": "min_qual"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
     own = dict(counts=False, out="", reject_out="", no_split=False, backend=None, help=False)
     given, reads, solid, hist, gpu_parse = {}, [], False, "", False
     i = 0
@@ -354,17 +358,23 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         hash_num=a["hashes"], cmin=a["cmin"] or 0, solid=a["solid"], counts=a["counts"], bf_bytes=bf, fpr=a["fpr"],
         batch_bytes=a["batch_bytes"], hist_path=a["hist"].encode() or None, use_store=use_store, store_cap=store_cap,
         log=_log_line, device_parse=bool(a.get("gpu_parse")), reject_cmin=reject,
-        reject_bf_bytes=a.get("reject_bf_bytes") or 0, reject_num_elements=a.get("reject_num_elements") or 0)
+        reject_bf_bytes=a.get("reject_bf_bytes") or 0, reject_num_elements=a.get("reject_num_elements") or 0,
+        min_qual=a.get("min_qual") or 0)
     res = _lib.ReadsBuildResult()
     parsed = {}
 
     def note_parse(key):
+        # --min_qual: what the pass that just ran masked (ntedit_hip_reads_min_qual_info: the last pass)
+        with_qual, masked = ctypes.c_uint64(), ctypes.c_uint64()
+        if a.get("min_qual") and lib.ntedit_hip_reads_min_qual_info(b.h, with_qual, masked) == 0:
+            parsed.setdefault(key, {})["min_qual"] = dict(q=a["min_qual"], qual_bases=with_qual.value,
+                                                          masked_bases=masked.value)
         # --gpu_parse: what the pass that just ran parsed where (ntedit_hip_reads_parse_info: the last pass)
         st = _lib.ReadsParseStats()
         if a.get("gpu_parse") and lib.ntedit_hip_reads_parse_info(b.h, st) == 0:
-            parsed[key] = dict(device_chunks=st.device_chunks, fallback_chunks=st.fallback_chunks,
-                               raw_bytes=st.raw_bytes, text_bytes=st.text_bytes, kernel_ms=round(st.ms_kernels, 3),
-                               broken=st.broken, host_files=st.host_files)
+            parsed.setdefault(key, {}).update(device_chunks=st.device_chunks, fallback_chunks=st.fallback_chunks,
+                                              raw_bytes=st.raw_bytes, text_bytes=st.text_bytes,
+                                              kernel_ms=round(st.ms_kernels, 3), broken=st.broken, host_files=st.host_files)
             zs = _lib.ReadsInflateStats()  # ... and, of BGZF inputs, what it inflated on the device
             if lib.ntedit_hip_reads_inflate_info(b.h, zs) == 0 and zs.files:
                 parsed[key]["bgzf"] = dict(files=zs.files, members=zs.members, compressed_bytes=zs.comp_bytes,
@@ -436,7 +446,7 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
                                    fallback=use_store and not on),
                cmin=res.cmin, filter_bytes=nbytes, passes=passes, exchanges=b.exchanges, exchange_bytes=b.xbytes,
                exchange_ms=round(b.xsec * 1e3, 3))
-    if a.get("gpu_parse"):
+    if a.get("gpu_parse") or a.get("min_qual"):
         rep["parse"] = parsed
     if reject:
         rep["reject"] = dict(cutoff=reject, filter_bytes=nbytes2, merge_ms=b.exchanges[-1]["ms"] if group is not None else 0.0)

@@ -226,7 +226,8 @@ READS_OPTIONS = [("--cutoff", "cutoff"), ("--solid", "solid"), ("--counts", "cou
                  ("--sketch_bytes", "sketch_bytes"), ("--hist", "hist"), ("--save_bf", "save_bf"),
                  ("--batch_bytes", "batch_bytes"), ("--resident_cap", "resident_cap"), ("--no-split", "no_split"),
                  ("--gpu_parse", "gpu_parse"), ("--reject_cutoff", "reject_cutoff"), ("--reject_bf", "reject_bf"),
-                 ("--reject_num_elements", "reject_num_elements"), ("--save_reject_bf", "save_reject_bf")]
+                 ("--reject_num_elements", "reject_num_elements"), ("--save_reject_bf", "save_reject_bf"),
+                 ("--min_qual", "min_qual")]
 
 
 def parse(argv=None):
@@ -292,6 +293,10 @@ def parse(argv=None):
                    help="parse plain and bgzip-compressed (BGZF) read files on the GPU: the host ships the file's bytes, BGZF still "
                         "compressed; same outputs (single-stream gzip stays with the host parser).  BAM reads, unaligned or "
                         "aligned, need it; a BAM is read whole by one rank, as gzip files are")
+    g.add_argument("--min_qual", metavar="Q",
+                   help="minimum base quality, 1 to 93 (Phred+33; Phred+64 is not built): a base whose quality is below Q "
+                        "enters the filter build as N, on every rank alike (FASTQ: a quality character below 33 + Q; BAM: a "
+                        "quality byte below Q; records without qualities pass as they are)")
     g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
     g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
     args = ap.parse_args(argv)
@@ -337,7 +342,7 @@ def reads_args(args):
              (("k", "k_ignored"), ("cutoff", "cutoff"), ("hashes", "hashes"), ("fpr", "fpr"), ("bf", "bf_bytes"),
               ("num_elements", "num_elements"), ("sketch_bytes", "sketch_bytes"), ("batch_bytes", "batch_bytes"),
               ("store_cap", "resident_cap"), ("reject_cutoff", "reject_cutoff"), ("reject_bf", "reject_bf"),
-              ("reject_num_elements", "reject_num_elements")) if getattr(args, dest) is not None}
+              ("reject_num_elements", "reject_num_elements"), ("min_qual", "min_qual")) if getattr(args, dest) is not None}
     a = make_reads.check_options(_lib.READS_DIALECT_POLISHER, given, True, args.reads, args.solid, args.hist or "",
                                  args.gpu_parse, args.counts, args.save_reject_bf is not None)
     a.update(counts=args.counts, no_split=args.no_split)
