@@ -302,6 +302,53 @@ int ntedit_hip_reads_set_min_qual(ntedit_hip_ctx* ctx, uint32_t min_qual);
 int ntedit_hip_reads_min_qual_info(ntedit_hip_ctx* ctx, uint64_t* qual_bases, uint64_t* masked_bases);
 int ntedit_hip_reads_range_text_q(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, char* out, uint64_t cap,
                                   uint64_t* len, uint64_t* reads, uint64_t* start, uint64_t* next);
+/* --min_read_len L, --min_mean_qual Q, --min_rq R: which reads go into the batch text.  A record goes in when it passes
+ * every rule below; otherwise it is absent, as a record shorter than k is without them.  They hold for every pass over
+ * the files, so the resident store only ever holds reads that passed.  (nte_reads_grammar.h, nte_bam_grammar.h: the one
+ * place each rule is written; the host parser, the two models and the record kernels call them.)
+ *   length        L is 1 to 2^31 - 1; the shortest record kept is max(L, what it is without: k, or what
+ *                 ntedit_hip_reads_set_min_read set).
+ *   rq            R is above 0 and at most 1.  A BAM record whose rq aux field of type f holds v is kept iff v >= R, as two
+ *                 IEEE floats compare: a NaN is dropped.  A record without an rq:f field passes: every FASTA and FASTQ
+ *                 record does.  The aux walk follows the SAM specification's types (A c C 1 byte, s S 2, i I f 4, Z H to a
+ *                 NUL, B subtype + count * size), runs over [qual_off + l_seq, record end) and reads no byte outside it;
+ *                 a field that does not fit, or of an unknown type, ends it: the record counts as having no tag, and as
+ *                 aux_malformed.
+ *   mean quality  Q is 1 to 60.  A read's mean quality is the Phred value of its mean error probability (as NanoFilt,
+ *                 chopper and fastplong take it), not the mean of the Phred values, computed in integers: a base of Phred
+ *                 quality q adds E[min(q, 93)], E[q] = round(2^31 * 10^(-q/10)) (a table of literals; a FASTQ byte below
+ *                 33 counts as q = 0), S is the sum over the read as 64 bits, and the read is kept iff S <= len * E[Q].
+ *                 Records without qualities pass: FASTA records, and BAM records whose first quality byte is 0xFF.  With
+ *                 --min_qual the mean is taken over the qualities as stored, not over the masked text, and --min_qual's
+ *                 counts cover the bases of the reads that were copied.
+ * A dropped record is counted under the first rule that drops it, in the order flag (BAM, as before and in no count here),
+ * length, rq, mean quality.
+ *   ntedit_hip_reads_set_read_filter: the context's setting, with the lifetime of ntedit_hip_reads_set_min_qual; 0 turns a
+ *           rule off (a min_rq that is not above 0 is off, -0.0 included), and with all three off every launch and every
+ *           output is what it was before.  Out of range: NTEDIT_E_ARG.
+ *           ntedit_hip_reads_build and its stages leave it as it is (it is no field of their arguments): their passes follow
+ *           it, and report `read filter: D of N records dropped (length a, rq b, mean quality c)' per pass over the files.
+ *   ntedit_hip_reads_get_read_filter: the setting back.
+ *   ntedit_hip_reads_read_filter_info: the context's last ntedit_hip_reads_pass (the pass zeroes the counts; the device
+ *           calls add to them).  All 0 with the setting off.
+ *   ntedit_hip_reads_parse_model_f, _bam_model_f, _range_text_f: the host-only calls with the filter as further arguments
+ *           (the text calls take no rq: no text record has the tag) and their counts (st may be NULL); the _q names are
+ *           these with the filter off.  _range_text_f's min_len is the shortest record it returns. */
+typedef struct ntedit_hip_reads_read_filter_stats
+{
+	uint64_t records;           /* the records the rules saw (BAM: those the flag rule let through) */
+	uint64_t dropped_length;
+	uint64_t dropped_rq;
+	uint64_t dropped_mean_qual;
+	uint64_t rq_tagged;         /* with --min_rq: records that reached the rq rule (neither flag nor length dropped them) and had an rq:f field */
+	uint64_t aux_malformed;     /* ... and those whose aux walk ended at a field that does not fit or has an unknown type */
+} ntedit_hip_reads_read_filter_stats;
+int ntedit_hip_reads_set_read_filter(ntedit_hip_ctx* ctx, uint32_t min_len, uint32_t min_mean_qual, float min_rq);
+int ntedit_hip_reads_get_read_filter(ntedit_hip_ctx* ctx, uint32_t* min_len, uint32_t* min_mean_qual, float* min_rq);
+int ntedit_hip_reads_read_filter_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_read_filter_stats* st);
+int ntedit_hip_reads_range_text_f(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, uint32_t min_len,
+                                  uint32_t min_mean_qual, char* out, uint64_t cap, uint64_t* len, uint64_t* reads, uint64_t* start,
+                                  uint64_t* next, ntedit_hip_reads_read_filter_stats* st);
 /* The whole filter build of ntedit-make-reads-bf, shared by it and `ntedit --reads`: the sketch (sketch_counters, as
  * sized by the caller), pass 1, with solid or hist_path the histogram pass (the --hist file, the --solid cutoff, and
  * with bf_bytes = 0 the output size from the histogram), the output filter allocated in the PRIMARY slot (counting
@@ -438,6 +485,24 @@ typedef struct ntedit_hip_reads_rules
 	uint32_t min_qual;             /* 0: off */
 } ntedit_hip_reads_rules;
 int ntedit_hip_reads_options_check(const ntedit_hip_reads_options* opts, int dialect, int final, ntedit_hip_reads_rules* out);
+/* The rules of --min_read_len, --min_mean_qual and --min_rq, in the same two dialects and with the same meaning of
+ * `final`; a front end asks them behind ntedit_hip_reads_options_check.  They have structs of their own: the three above
+ * end where they ended before, so a caller built against them is untouched.  A malformed number is refused at the option
+ * (NTEDIT_READS_NOT_A_NUMBER; --min_rq is read with strtof); with final = 1 the ranges, one sentence each: --min_read_len
+ * 1..2147483647, --min_rq above 0 and at most 1, --min_mean_qual 1..60 (NTEDIT_READS_REFUSED).  The build takes the
+ * outcome as the context's setting: ntedit_hip_reads_set_read_filter before ntedit_hip_reads_build or its stages. */
+typedef struct ntedit_hip_reads_filter_options
+{
+	const char *min_read_len, *min_mean_qual, *min_rq;
+} ntedit_hip_reads_filter_options;
+typedef struct ntedit_hip_reads_filter_rules
+{
+	uint32_t min_read_len;  /* 0: off */
+	uint32_t min_mean_qual; /* 0: off */
+	float min_rq;           /* 0: off */
+} ntedit_hip_reads_filter_rules;
+int ntedit_hip_reads_filter_options_check(const ntedit_hip_reads_filter_options* opts, int dialect, int final,
+                                          ntedit_hip_reads_filter_rules* out);
 /* --gpu_parse: plain (not gzip) read files parsed on the device.  The host ships raw file bytes, cut at record starts
  * into chunks of about batch_bytes; kernels (nte_reads_parse.hip) make of each chunk, in HBM, exactly the batch text the
  * host parser makes -- every read of k bases or more followed by '\n', in file order -- and that text goes to the passes
@@ -492,6 +557,9 @@ int ntedit_hip_reads_parse_device(ntedit_hip_ctx* ctx, const char* raw, uint64_t
 int ntedit_hip_reads_parse_model(const char* raw, uint64_t n_raw, uint32_t k, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res);
 int ntedit_hip_reads_parse_model_q(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* out, uint64_t cap,
                                    ntedit_hip_reads_parse_result* res);
+int ntedit_hip_reads_parse_model_f(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, uint32_t min_len, uint32_t min_mean_qual,
+                                   float min_rq, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res,
+                                   ntedit_hip_reads_read_filter_stats* st);
 int ntedit_hip_reads_set_device_parse(ntedit_hip_ctx* ctx, int on);
 int ntedit_hip_reads_parse_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_parse_stats* st);
 /* --gpu_parse on BGZF reads (the output of bgzip: independent gzip members of at most 64 KiB inflated each, their
@@ -621,6 +689,14 @@ int ntedit_hip_reads_bam_model(const void* raw, uint64_t n_raw, int at_header, u
                                ntedit_hip_reads_bam_result* res);
 int ntedit_hip_reads_bam_model_q(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, uint32_t min_qual, char* out,
                                  uint64_t cap, ntedit_hip_reads_bam_result* res);
+int ntedit_hip_reads_bam_model_f(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, uint32_t min_qual, uint32_t min_read_len,
+                                 uint32_t min_mean_qual, float min_rq, char* out, uint64_t cap, ntedit_hip_reads_bam_result* res,
+                                 ntedit_hip_reads_read_filter_stats* st);
+/* k_bam_facts (--min_rq, --min_mean_qual on BAM) gives each record a group of 8, 16 or 64 lanes, chosen by the mean length
+ * of the reads the chunk before kept; _set_group_width forces one (0: back to the choice), _group_width tells the width
+ * the last chunk ran at (0: the kernel has not run). */
+int ntedit_hip_reads_bam_set_group_width(ntedit_hip_ctx* ctx, uint32_t lanes);
+int ntedit_hip_reads_bam_group_width(ntedit_hip_ctx* ctx);
 int ntedit_hip_reads_bam_set_segment(ntedit_hip_ctx* ctx, uint64_t bytes);
 int ntedit_hip_reads_bam_info(ntedit_hip_ctx* ctx, ntedit_hip_reads_bam_stats* st);
 /* --gpu_parse for genome FASTA (ntedit-make-genome-bf --gpu_parse, ntedit --genome --gpu_parse).  A chromosome does not

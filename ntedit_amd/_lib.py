@@ -133,6 +133,28 @@ class ReadsRules(ctypes.Structure):
                 ("min_qual", ctypes.c_uint32)]
 
 
+READS_FILTER_OPTION_TEXTS = ("min_read_len", "min_mean_qual", "min_rq")
+
+
+class ReadsFilterOptions(ctypes.Structure):
+    """ntedit_hip_reads_filter_options: --min_read_len, --min_mean_qual, --min_rq as given (None: not given)"""
+    _fields_ = [(name, ctypes.c_char_p) for name in READS_FILTER_OPTION_TEXTS]
+
+
+class ReadsFilterRules(ctypes.Structure):
+    """ntedit_hip_reads_filter_rules: what ntedit_hip_reads_filter_options_check makes of them (0: off)"""
+    _fields_ = [("min_read_len", ctypes.c_uint32), ("min_mean_qual", ctypes.c_uint32), ("min_rq", ctypes.c_float)]
+
+
+class ReadsReadFilterStats(ctypes.Structure):
+    """ntedit_hip_reads_read_filter_stats: what the last pass's records came to under --min_read_len, --min_mean_qual, --min_rq"""
+    _fields_ = [("records", ctypes.c_uint64), ("dropped_length", ctypes.c_uint64), ("dropped_rq", ctypes.c_uint64),
+                ("dropped_mean_qual", ctypes.c_uint64), ("rq_tagged", ctypes.c_uint64), ("aux_malformed", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # --gpu_parse (ntedit_hip_reads_parse_device / _model): the tile size and the rules of the clean grammar
 PARSE_TILE = 16384
 PARSE_BAD = dict(first=1, cr=2, empty=4, seq_start=8, fq_lines=16, fq_header=32, fq_plus=64, fq_qual=128, table=256,
@@ -371,6 +393,10 @@ EXPORTS = [
     "ntedit_hip_settle_info",
     "ntedit_hip_reads_set_min_qual", "ntedit_hip_reads_min_qual_info", "ntedit_hip_reads_parse_model_q",
     "ntedit_hip_reads_bam_model_q", "ntedit_hip_reads_range_text_q",
+    "ntedit_hip_reads_set_read_filter", "ntedit_hip_reads_get_read_filter", "ntedit_hip_reads_filter_options_check",
+    "ntedit_hip_reads_read_filter_info", "ntedit_hip_reads_parse_model_f",
+    "ntedit_hip_reads_bam_model_f", "ntedit_hip_reads_range_text_f", "ntedit_hip_reads_bam_set_group_width",
+    "ntedit_hip_reads_bam_group_width",
     "ntedit_hip_set_apply", "ntedit_hip_result_edited_device", "ntedit_hip_result_edited",
     "ntedit_hip_result_last_error", "ntedit_hip_result_qv", "ntedit_hip_qv_value", "ntedit_hip_qv_header",
     "ntedit_hip_qv_format_row", "ntedit_hip_apply_info", "ntedit_hip_apply_tile",
@@ -565,6 +591,18 @@ def load():
     lib.ntedit_hip_reads_parse_model_q.argtypes = [vp, u64, u32, u32, vp, u64, pres]
     lib.ntedit_hip_reads_bam_model_q.argtypes = [vp, u64, ci, u32, u32, vp, u64, bres]
     lib.ntedit_hip_reads_range_text_q.argtypes = [ctypes.c_char_p, u64, u64, u32, vp, u64, pu64, pu64, pu64, pu64]
+    # --min_read_len, --min_mean_qual, --min_rq: the context's setting, the last pass's counts, the host-only calls with the
+    # filter as further arguments, and the lanes k_bam_facts gives a record
+    pfs = ctypes.POINTER(ReadsReadFilterStats)
+    lib.ntedit_hip_reads_set_read_filter.argtypes = [vp, u32, u32, ctypes.c_float]
+    lib.ntedit_hip_reads_get_read_filter.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_float)]
+    lib.ntedit_hip_reads_filter_options_check.argtypes = [ctypes.POINTER(ReadsFilterOptions), ci, ci, ctypes.POINTER(ReadsFilterRules)]
+    lib.ntedit_hip_reads_read_filter_info.argtypes = [vp, pfs]
+    lib.ntedit_hip_reads_parse_model_f.argtypes = [vp, u64, u32, u32, u32, u32, ctypes.c_float, vp, u64, pres, pfs]
+    lib.ntedit_hip_reads_bam_model_f.argtypes = [vp, u64, ci, u32, u32, u32, u32, ctypes.c_float, vp, u64, bres, pfs]
+    lib.ntedit_hip_reads_range_text_f.argtypes = [ctypes.c_char_p, u64, u64, u32, u32, u32, vp, u64, pu64, pu64, pu64, pu64, pfs]
+    lib.ntedit_hip_reads_bam_set_group_width.argtypes = [vp, u32]
+    lib.ntedit_hip_reads_bam_group_width.argtypes = [vp]
     # the edited draft in HBM and the k-mer QV (nte_apply.hip)
     pu32 = ctypes.POINTER(u32)
     lib.ntedit_hip_set_apply.argtypes = [vp, u32]

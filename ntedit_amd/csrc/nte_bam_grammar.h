@@ -17,6 +17,8 @@
 //            makes the chunk unclean even when its end is not.
 //   kept     (flag & 0x900) == 0 (neither secondary nor supplementary) and l_seq >= min_len.  The strand flag 0x10 is not
 //            applied: the sketch and the filter hash canonical k-mers (nte_reads.hip).
+//            With a read filter (--min_read_len, --min_rq, --min_mean_qual: bam_reason) also by its rq:f aux field and
+//            the mean of its qualities, which are the only reads this grammar makes of the aux fields.
 //   text     every kept record's bases (codes "=ACMGRSVTWYHKDBN") followed by '\n', in file order.
 #pragma once
 
@@ -188,6 +190,126 @@ bam_base_q(const uint8_t* raw, uint32_t seq_off, uint32_t qual_off, uint32_t j, 
 	return (char)nte_parse::rp_mask_base((uint8_t)bam_base(raw, seq_off, j), low);
 }
 
+// --min_rq: the record's `rq` aux field of type f.  The aux fields lie in raw[aux_off .. rec_end), aux_off = qual_off +
+// l_seq, and the walk reads no byte outside that range.  The SAM specification's types: A c C 1 byte, s S 2, i I f 4,
+// Z H to a NUL, B a subtype, a count and count * size.  A field that does not fit, or of an unknown type, ends the walk:
+// BAM_RQ_MALFORMED, and the record counts as having no tag.  An rq of another type than f is walked past like any field.
+enum : uint32_t { BAM_RQ_FOUND = 0, BAM_RQ_ABSENT = 1, BAM_RQ_MALFORMED = 2 };
+
+BAM_HD uint32_t
+bam_aux_size(uint32_t type) // of a fixed-size value, 0: none
+{
+	switch (type) {
+	case 'A': case 'c': case 'C': return 1;
+	case 's': case 'S': return 2;
+	case 'i': case 'I': case 'f': return 4;
+	default: return 0;
+	}
+}
+
+BAM_HD uint32_t
+bam_aux_rq(const uint8_t* raw, uint32_t aux_off, uint32_t rec_end, uint32_t* value_bits)
+{
+	uint32_t p = aux_off;
+	while (p < rec_end) {
+		if (rec_end - p < 3) {
+			return BAM_RQ_MALFORMED;
+		}
+		const uint32_t t0 = raw[p], t1 = raw[p + 1], type = raw[p + 2];
+		p += 3;
+		uint32_t size = bam_aux_size(type);
+		if (size) {
+			if (rec_end - p < size) {
+				return BAM_RQ_MALFORMED;
+			}
+			if (type == 'f' && t0 == 'r' && t1 == 'q') {
+				*value_bits = bam_ld32(raw + p);
+				return BAM_RQ_FOUND;
+			}
+		} else if (type == 'Z' || type == 'H') {
+			while (p + size < rec_end && raw[p + size] != 0) {
+				size++;
+			}
+			if (p + size >= rec_end) {
+				return BAM_RQ_MALFORMED; // no NUL inside the record
+			}
+			size++;
+		} else if (type == 'B') {
+			if (rec_end - p < 5) {
+				return BAM_RQ_MALFORMED;
+			}
+			const uint32_t each = raw[p] == 'A' ? 0u : bam_aux_size(raw[p]); // (the subtypes are c C s S i I f)
+			const uint64_t bytes = (uint64_t)each * bam_ld32(raw + p + 1);
+			if (each == 0 || bytes > rec_end - p - 5) {
+				return BAM_RQ_MALFORMED;
+			}
+			size = 5 + (uint32_t)bytes;
+		} else {
+			return BAM_RQ_MALFORMED;
+		}
+		p += size;
+	}
+	return BAM_RQ_ABSENT;
+}
+
+// `value` (the bits of an IEEE float) >= `min` (alike), as the floats compare: a NaN is below everything
+BAM_HD bool
+bam_rq_kept(uint32_t value_bits, uint32_t min_bits)
+{
+	union { uint32_t u; float f; } v, m;
+	v.u = value_bits;
+	m.u = min_bits;
+	return v.f >= m.f;
+}
+
+// what the filter needs to know of a record besides its flag and length
+struct BamFacts
+{
+	uint32_t rq_status; // bam_aux_rq's
+	uint32_t rq_bits;
+	bool has_qual;      // bam_has_qual
+	uint64_t qual_sum;  // of rp_qual_weight over its quality bytes
+};
+
+// RP_KEPT, or the first rule that drops the record: flag, length, rq, mean quality
+BAM_HD uint32_t
+bam_reason(uint32_t flag, uint32_t l_seq, uint32_t min_len, const nte_parse::ReadFilter& f, const BamFacts& x)
+{
+	if (flag & 0x900u) {
+		return nte_parse::RP_DROP_FLAG;
+	}
+	if (l_seq < nte_parse::rp_min_len(f, min_len)) {
+		return nte_parse::RP_DROP_LENGTH;
+	}
+	if (f.rq_bits && x.rq_status == BAM_RQ_FOUND && !bam_rq_kept(x.rq_bits, f.rq_bits)) {
+		return nte_parse::RP_DROP_RQ;
+	}
+	if (f.min_mean_qual && x.has_qual && !nte_parse::rp_mean_qual_kept(x.qual_sum, l_seq, f.min_mean_qual)) {
+		return nte_parse::RP_DROP_MEAN_QUAL;
+	}
+	return nte_parse::RP_KEPT;
+}
+
+BAM_HD bool
+bam_kept(uint32_t flag, uint32_t l_seq, uint32_t min_len, const nte_parse::ReadFilter& f, const BamFacts& x)
+{
+	return bam_reason(flag, l_seq, min_len, f, x) == nte_parse::RP_KEPT;
+}
+
+// ... and for a caller that holds the reason k_bam_facts stored for the record's table slot (RP_KEPT, RP_DROP_RQ or
+// RP_DROP_MEAN_QUAL: the rules that need the record's bytes), the flag and length rules in front of it as above
+BAM_HD uint32_t
+bam_reason(uint32_t flag, uint32_t l_seq, uint32_t min_len, const nte_parse::ReadFilter& f, uint32_t stored)
+{
+	if (flag & 0x900u) {
+		return nte_parse::RP_DROP_FLAG;
+	}
+	if (l_seq < nte_parse::rp_min_len(f, min_len)) {
+		return nte_parse::RP_DROP_LENGTH;
+	}
+	return stored;
+}
+
 // The chain from p (< end <= n) while it starts records below `end`: their offsets into table[0 .. cap), *count of them,
 // *exit where the chain left [.., end) (BAM_NEXT), or where it stopped: the cut (BAM_END) or the unclean record.  The
 // walk is a function of (raw, n, p, end): whoever enters at p writes the same table.
@@ -266,9 +388,12 @@ bam_unclean(uint32_t broken, uint64_t at)
 // res->text_len is its whole length either way.
 // With min_qual > 0 the bases of the records that have qualities are masked (bam_base_q); counts[0] += those bases,
 // counts[1] += the masked ones (counts may be NULL).
+// With a filter (bam_reason) a record dropped by rq or by its mean quality is in res->records and in no other field of
+// res; fc (may be NULL) += what the records came to: those the flag rule let through, the drops per rule, the records
+// that reached the rq rule and had an rq:f field, and those of them whose aux fields were malformed.  --min_qual's counts cover the records copied.
 inline void
-bam_model_q(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, uint32_t min_qual, char* out, uint64_t cap, BamResult* res,
-            uint64_t* counts)
+bam_model_f(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, uint32_t min_qual, const nte_parse::ReadFilter& f, char* out,
+            uint64_t cap, BamResult* res, uint64_t* counts, nte_parse::ReadFilterCounts* fc)
 {
 	*res = BamResult();
 	if (n >= BAM_MAX_RAW) {
@@ -301,14 +426,36 @@ bam_model_q(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, uin
 			return;
 		}
 		res->records++;
-		if (r.flag & 0x900u) {
+		const uint32_t qual_off = bam_qual_off(r.seq_off, r.l_seq);
+		BamFacts x = BamFacts();
+		x.rq_status = BAM_RQ_ABSENT;
+		const bool filtered = nte_parse::rp_filter_on(f) && !(r.flag & 0x900u);
+		// (a record the length rule drops is not looked into: its tag and its qualities decide nothing)
+		const bool look = filtered && bam_reason(r.flag, r.l_seq, min_len, f, (uint32_t)nte_parse::RP_KEPT) == nte_parse::RP_KEPT;
+		if (look && f.rq_bits) {
+			x.rq_status = bam_aux_rq(raw, qual_off + r.l_seq, r.next, &x.rq_bits);
+		}
+		if (look && f.min_mean_qual && (x.has_qual = bam_has_qual(raw, qual_off, r.l_seq))) {
+			for (uint32_t j = 0; j < r.l_seq; j++) {
+				x.qual_sum += nte_parse::rp_qual_weight((int)raw[qual_off + j]);
+			}
+		}
+		const uint32_t why = bam_reason(r.flag, r.l_seq, min_len, f, x);
+		if (filtered && fc) {
+			fc->records++;
+			fc->by_length += why == nte_parse::RP_DROP_LENGTH;
+			fc->by_rq += why == nte_parse::RP_DROP_RQ;
+			fc->by_mean_qual += why == nte_parse::RP_DROP_MEAN_QUAL;
+			fc->rq_tagged += x.rq_status == BAM_RQ_FOUND;
+			fc->aux_malformed += x.rq_status == BAM_RQ_MALFORMED;
+		}
+		if (why == nte_parse::RP_DROP_FLAG) {
 			res->skipped_flag++;
-		} else if (r.l_seq < min_len) {
+		} else if (why == nte_parse::RP_DROP_LENGTH) {
 			res->skipped_short++;
-		} else {
+		} else if (why == nte_parse::RP_KEPT) {
 			res->kept++;
 			res->bases += r.l_seq;
-			const uint32_t qual_off = bam_qual_off(r.seq_off, r.l_seq);
 			const bool mask = min_qual && bam_has_qual(raw, qual_off, r.l_seq);
 			uint32_t masked = 0;
 			for (uint32_t j = 0; j <= r.l_seq; j++, text++) {
@@ -330,6 +477,13 @@ bam_model_q(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, uin
 	res->clean = 1;
 	res->cut = p;
 	res->text_len = text;
+}
+
+inline void
+bam_model_q(const uint8_t* raw, uint64_t n, int at_header, uint32_t min_len, uint32_t min_qual, char* out, uint64_t cap, BamResult* res,
+            uint64_t* counts)
+{
+	bam_model_f(raw, n, at_header, min_len, min_qual, nte_parse::ReadFilter(), out, cap, res, counts, nullptr);
 }
 
 inline void

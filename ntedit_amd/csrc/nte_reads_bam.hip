@@ -13,7 +13,11 @@
 //                  the true chain through them at LDS latency: exit == the next segment's guess keeps that segment's
 //                  table (the walk is a function of its entry), anything else walks that segment again from the true
 //                  entry.  It marks the segments on the chain, and ends with the cut or the rule a record broke.
-//   k_bam_sums     one wavefront per segment on the chain, a lane per record: kept records and text bytes of the segment.
+//   k_bam_facts    (--min_rq, --min_mean_qual) one wavefront per segment on the chain, a group of 8, 16 or 64 lanes per
+//                  record: the weights of its quality bytes summed over the group, its aux fields walked for rq by the
+//                  group's first lane; one byte per table slot, the rule that drops the record or 0.
+//   k_bam_sums     one wavefront per segment on the chain, a lane per record: kept records and text bytes of the segment
+//                  (k_bam_sums<true>, k_bam_compact<true>: with the read filter, by bam_reason and the slot bytes).
 //   k_bam_scan     one workgroup: the exclusive scan of those over the segments.
 //   k_bam_compact  as k_bam_sums, with a wavefront scan: each kept record's packed-bases offset and text offset, dense.
 //   k_bam_decode   one lane per 16 text bytes, whatever the records' lengths: a search in the text-offset table for the
@@ -46,6 +50,8 @@ int parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream);
 int parse_text_buffer(const ntedit_hip_ctx* c, uint64_t n, char** text, uint64_t* cap);
 uint32_t min_qual(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_min_qual (nte_reads_parse.hip), and the pass's counts
 void min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases);
+nte_parse::ReadFilter read_filter(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_read_filter, and the pass's counts
+void read_filter_count(const ntedit_hip_ctx* c, int reset, const nte_parse::ReadFilterCounts* add);
 }
 
 namespace {
@@ -66,12 +72,16 @@ struct BamInfo // the small result the device keeps per chunk
 	u32 broken, cut, rewalked, reserved;
 	u64 records, kept, skipped_flag, skipped_short;
 	u64 qual_bases, masked_bases; // --min_qual (k_bam_decode<true>): the bases decoded that had a quality, and those masked
+	// --min_rq, --min_mean_qual (k_bam_facts, k_bam_sums<true>): the drops by those rules, the records that had an rq:f
+	// field, and those whose aux fields were malformed
+	u64 by_rq, by_mean_qual, rq_tagged, aux_malformed;
 };
 
 struct SegTables // per segment
 {
 	u32 *guess, *exit, *count, *status, *valid;
 	u32* table; // cap offsets per segment
+	u8* reason; // --min_rq, --min_mean_qual: one byte per table slot (k_bam_facts)
 	u64* pack;  // (kept records << 32 | text bytes) of the segment, then their exclusive scan; [nseg]: the totals
 };
 
@@ -205,19 +215,118 @@ wave_sum(u64 v)
 	return v;
 }
 
+__device__ __forceinline__ u64
+group_sum(u64 v, int width) // over each aligned group of `width` lanes (a power of two)
+{
+	for (int d = 1; d < width; d <<= 1) {
+		const u32 lo = __shfl_xor((u32)v, d, 64), hi = __shfl_xor((u32)(v >> 32), d, 64);
+		v += ((u64)hi << 32) | lo;
+	}
+	return v;
+}
+
+// --min_rq, --min_mean_qual: the rules that need a record's bytes, ahead of k_bam_sums.  One wavefront per segment on the
+// chain, as k_bam_sums walks them; a group of WIDTH lanes (8, 16 or 64: the host chooses by the reads' mean length) per
+// record, 64 / WIDTH records at a time.  The group's lanes share the record's l_seq quality bytes -- the unaligned head
+// and tail a byte per lane, the body in aligned 16-byte loads -- and sum the weights over the
+// group; the group's first lane walks the aux fields for rq (tens of bytes; arrays are skipped by their counts) and
+// stores the slot's byte: RP_KEPT, RP_DROP_RQ or RP_DROP_MEAN_QUAL.  A record the flag or the length rule drops is not
+// looked into (its byte is RP_KEPT; k_bam_sums and k_bam_compact apply those two rules in front of it: bam_reason).
+// Every record in the tables passed bam_hop, so its quality bytes and r.next lie inside the chunk.
+template <int WIDTH>
 __global__ __launch_bounds__(BAM_TPB) void
-k_bam_sums(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, SegTables t, BamInfo* info)
+k_bam_facts(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, nte_parse::ReadFilter f, SegTables t, BamInfo* info)
+{
+	__shared__ u32 s_weight[nte_parse::RP_MAX_QUAL + 1];
+	if (threadIdx.x <= nte_parse::RP_MAX_QUAL) {
+		s_weight[threadIdx.x] = nte_parse::RP_QUAL_WEIGHT[threadIdx.x];
+	}
+	__syncthreads();
+	const u32 lane = threadIdx.x & 63, seg = blockIdx.x * BAM_WAVES + (threadIdx.x >> 6);
+	if (seg >= nseg) { // (a whole wavefront: the shuffles below stay among lanes that are all here)
+		return;
+	}
+	constexpr u32 GROUPS = 64 / WIDTH;
+	const u32 g = lane / WIDTH, gl = lane % WIDTH;
+	const u32 count = t.valid[seg] ? t.count[seg] : 0;
+	u64 tagged = 0, malformed = 0;
+	for (u32 j0 = 0; j0 < count; j0 += GROUPS) { // (uniform over the wavefront)
+		const u32 j = j0 + g;
+		BamRecord r = BamRecord();
+		bool look = false;
+		if (j < count) {
+			(void)bam_hop(raw, n, t.table[(u64)seg * cap + j], &r); // (BAM_NEXT: the walk stored it)
+			look = bam_reason(r.flag, r.l_seq, min_len, f, (u32)nte_parse::RP_KEPT) == nte_parse::RP_KEPT;
+		}
+		const u32 q0 = bam_qual_off(r.seq_off, r.l_seq), q1 = q0 + r.l_seq;
+		BamFacts x = BamFacts();
+		x.rq_status = BAM_RQ_ABSENT;
+		x.has_qual = look && f.min_mean_qual && bam_has_qual(raw, q0, r.l_seq);
+		u64 sum = 0;
+		if (x.has_qual) {
+			const u32 mis = (u32)((uintptr_t)raw & 15u); // (0 for a chunk that starts its buffer)
+			u32 a0 = ((q0 + mis + 15u) & ~15u) - mis; // the aligned body is [a0, a1)
+			a0 = a0 < q1 ? a0 : q1;
+			const u32 a1 = a0 + ((q1 - a0) & ~15u);
+			for (u32 p = q0 + gl; p < a0; p += WIDTH) {
+				sum += s_weight[nte_parse::rp_qual_index((int)raw[p])];
+			}
+			for (u32 p = a0 + gl * 16; p < a1; p += WIDTH * 16) {
+				const uint4 v = *reinterpret_cast<const uint4*>(raw + p);
+				const u32 w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+				for (int b = 0; b < 16; b++) {
+					sum += s_weight[nte_parse::rp_qual_index((int)((w[b >> 2] >> (8 * (b & 3))) & 0xFFu))];
+				}
+			}
+			for (u32 p = a1 + gl; p < q1; p += WIDTH) {
+				sum += s_weight[nte_parse::rp_qual_index((int)raw[p])];
+			}
+		}
+		x.qual_sum = group_sum(sum, WIDTH);
+		if (gl == 0 && j < count) {
+			if (look && f.rq_bits) {
+				x.rq_status = bam_aux_rq(raw, q1, r.next, &x.rq_bits);
+				tagged += x.rq_status == BAM_RQ_FOUND;
+				malformed += x.rq_status == BAM_RQ_MALFORMED;
+			}
+			t.reason[(u64)seg * cap + j] = look ? (u8)bam_reason(r.flag, r.l_seq, min_len, f, x) : (u8)nte_parse::RP_KEPT;
+		}
+	}
+	tagged = wave_sum(tagged);
+	malformed = wave_sum(malformed);
+	if (lane == 0 && (tagged || malformed)) {
+		atomicAdd((unsigned long long*)&info->rq_tagged, (unsigned long long)tagged);
+		atomicAdd((unsigned long long*)&info->aux_malformed, (unsigned long long)malformed);
+	}
+}
+
+// FILTER: the slot bytes of k_bam_facts behind the flag and the length rule (bam_reason); f.min_len alone needs no bytes
+template <bool FILTER>
+__global__ __launch_bounds__(BAM_TPB) void
+k_bam_sums(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, SegTables t, BamInfo* info, nte_parse::ReadFilter f,
+           const u8* __restrict__ reason)
 {
 	const u32 lane = threadIdx.x & 63, seg = blockIdx.x * BAM_WAVES + (threadIdx.x >> 6);
 	if (seg >= nseg) {
 		return;
 	}
 	const u32 count = t.valid[seg] ? t.count[seg] : 0;
-	u64 kept = 0, text = 0, by_flag = 0, by_len = 0;
+	u64 kept = 0, text = 0, by_flag = 0, by_len = 0, by_rq = 0, by_mq = 0;
 	for (u32 j = lane; j < count; j += 64) {
 		BamRecord r;
 		(void)bam_hop(raw, n, t.table[(u64)seg * cap + j], &r); // (BAM_NEXT: the walk stored it)
-		if (r.flag & 0x900u) {
+		if (FILTER) {
+			const u32 why = bam_reason(r.flag, r.l_seq, min_len, f, reason ? (u32)reason[(u64)seg * cap + j] : (u32)nte_parse::RP_KEPT);
+			by_flag += why == nte_parse::RP_DROP_FLAG;
+			by_len += why == nte_parse::RP_DROP_LENGTH;
+			by_rq += why == nte_parse::RP_DROP_RQ;
+			by_mq += why == nte_parse::RP_DROP_MEAN_QUAL;
+			if (why == nte_parse::RP_KEPT) {
+				kept++;
+				text += (u64)r.l_seq + 1;
+			}
+		} else if (r.flag & 0x900u) {
 			by_flag++;
 		} else if (r.l_seq < min_len) {
 			by_len++;
@@ -230,6 +339,10 @@ k_bam_sums(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, Se
 	text = wave_sum(text);
 	by_flag = wave_sum(by_flag);
 	by_len = wave_sum(by_len);
+	if (FILTER) {
+		by_rq = wave_sum(by_rq);
+		by_mq = wave_sum(by_mq);
+	}
 	if (lane == 0) {
 		t.pack[seg] = kept << 32 | text;
 		if (count) {
@@ -237,6 +350,10 @@ k_bam_sums(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, Se
 			atomicAdd((unsigned long long*)&info->kept, (unsigned long long)kept);
 			atomicAdd((unsigned long long*)&info->skipped_flag, (unsigned long long)by_flag);
 			atomicAdd((unsigned long long*)&info->skipped_short, (unsigned long long)by_len);
+			if (FILTER && (by_rq || by_mq)) {
+				atomicAdd((unsigned long long*)&info->by_rq, (unsigned long long)by_rq);
+				atomicAdd((unsigned long long*)&info->by_mean_qual, (unsigned long long)by_mq);
+			}
 		}
 	}
 }
@@ -270,9 +387,10 @@ k_bam_scan(u64* pack, u32 nseg, u32* krec_text)
 	}
 }
 
+template <bool FILTER>
 __global__ __launch_bounds__(BAM_TPB) void
 k_bam_compact(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len, SegTables t, u32* __restrict__ krec_seq,
-              u32* __restrict__ krec_text)
+              u32* __restrict__ krec_text, nte_parse::ReadFilter f, const u8* __restrict__ reason)
 {
 	const u32 lane = threadIdx.x & 63, seg = blockIdx.x * BAM_WAVES + (threadIdx.x >> 6);
 	if (seg >= nseg) {
@@ -286,7 +404,12 @@ k_bam_compact(const u8* __restrict__ raw, u32 n, u32 nseg, u32 cap, u32 min_len,
 		bool keep = false;
 		if (j < count) {
 			(void)bam_hop(raw, n, t.table[(u64)seg * cap + j], &r);
-			keep = bam_kept(r.flag, r.l_seq, min_len);
+			if (FILTER) {
+				keep = bam_reason(r.flag, r.l_seq, min_len, f, reason ? (u32)reason[(u64)seg * cap + j] : (u32)nte_parse::RP_KEPT) ==
+				       nte_parse::RP_KEPT;
+			} else {
+				keep = bam_kept(r.flag, r.l_seq, min_len);
+			}
 		}
 		const u32 len = keep ? r.l_seq + 1 : 0;
 		u32 ik = keep ? 1 : 0, il = len; // inclusive scans over the lanes
@@ -384,6 +507,9 @@ struct BamState
 	const ntedit_hip_ctx* owner = nullptr;
 	ntedit_hip_reads_bam_stats info = {};
 	u64 segment = 0; // ntedit_hip_reads_bam_set_segment (0: the default)
+	u32 last_width = 0;  // the width the last k_bam_facts ran at (ntedit_hip_reads_bam_group_width)
+	u32 group_width = 0; // ntedit_hip_reads_bam_set_group_width (0: by the reads' mean length)
+	u32 mean_l_seq = 0;  // of the records the last chunk kept (0: no chunk yet): what the next chunk's width goes by
 	int device = -1;
 	hipStream_t stream = nullptr; // the parse unit's
 	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
@@ -505,7 +631,9 @@ release_scratch(BamState* s)
 	const ntedit_hip_ctx* owner = s->owner;
 	const ntedit_hip_reads_bam_stats info = s->info;
 	const u64 segment = s->segment;
+	const u32 group_width = s->group_width;
 	*s = BamState();
+	s->group_width = group_width;
 	s->owner = owner;
 	s->info = info;
 	s->segment = segment;
@@ -535,6 +663,7 @@ carve(u8* base, u64 nseg, u64 cap, u64* bytes)
 	t.valid = (u32*)take(nseg * 4);
 	t.pack = (u64*)take((nseg + 1) * 8);
 	t.table = (u32*)take(nseg * cap * 4);
+	t.reason = take(nseg * cap);
 	*bytes = at;
 	return t;
 }
@@ -604,7 +733,30 @@ bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, in
 		return rc;
 	}
 	u32 *krec_seq = (u32*)s->d_rec, *krec_text = (u32*)(s->d_rec + up256(max_records * 4));
-	hipLaunchKernelGGL(k_bam_sums, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, s->d_info);
+	const nte_parse::ReadFilter f = nte_reads::read_filter(c);
+	const bool filtered = nte_parse::rp_filter_on(f), facts = f.rq_bits || f.min_mean_qual;
+	if (facts) {
+		// the lanes per record: a whole wavefront for long reads, where one record's quality bytes are thousands and a
+		// narrower group would leave a few lanes with a long loop; 16 for reads of hundreds of bases (a lane has one or two
+		// 16-byte loads); 8 for short reads, where wider groups idle behind the aligned body
+		const u32 width = s->group_width ? s->group_width : s->mean_l_seq >= 2048 ? 64u : s->mean_l_seq >= 256 ? 16u : s->mean_l_seq ? 8u : 16u;
+		if (width == 64) {
+			hipLaunchKernelGGL(k_bam_facts<64>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, f, t, s->d_info);
+		} else if (width == 16) {
+			hipLaunchKernelGGL(k_bam_facts<16>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, f, t, s->d_info);
+		} else {
+			hipLaunchKernelGGL(k_bam_facts<8>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, f, t, s->d_info);
+		}
+		s->last_width = width;
+	}
+	const u8* reason = facts ? t.reason : nullptr;
+	if (filtered) {
+		hipLaunchKernelGGL(k_bam_sums<true>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, s->d_info, f,
+		                   reason);
+	} else {
+		hipLaunchKernelGGL(k_bam_sums<false>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, s->d_info, f,
+		                   reason);
+	}
 	hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(BAM_TPB), 0, s->stream, t.pack, nseg, krec_text);
 	BAM_TRY(c, hipGetLastError());
 	BAM_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(BamInfo), hipMemcpyDeviceToHost, s->stream));
@@ -626,11 +778,30 @@ bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, in
 	out.skipped_short = s->h_info->skipped_short;
 	out.text_len = (u32)*s->h_total;
 	out.bases = out.text_len - out.kept;
+	if (out.kept) {
+		s->mean_l_seq = (u32)(out.bases / out.kept);
+	}
+	if (filtered) {
+		nte_parse::ReadFilterCounts fc = nte_parse::ReadFilterCounts();
+		fc.records = out.records - out.skipped_flag;
+		fc.by_length = out.skipped_short;
+		fc.by_rq = s->h_info->by_rq;
+		fc.by_mean_qual = s->h_info->by_mean_qual;
+		fc.rq_tagged = s->h_info->rq_tagged;
+		fc.aux_malformed = s->h_info->aux_malformed;
+		nte_reads::read_filter_count(c, 0, &fc);
+	}
 	if (out.kept != *s->h_total >> 32 || out.text_len > text_cap) {
 		return pfail(c, NTEDIT_E_DEVICE, "reads_bam: the text does not fit its buffer");
 	}
 	if (out.text_len) {
-		hipLaunchKernelGGL(k_bam_compact, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, krec_seq, krec_text);
+		if (filtered) {
+			hipLaunchKernelGGL(k_bam_compact<true>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, krec_seq,
+			                   krec_text, f, reason);
+		} else {
+			hipLaunchKernelGGL(k_bam_compact<false>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, t, krec_seq,
+			                   krec_text, f, reason);
+		}
 		const unsigned blocks = (unsigned)((out.text_len + BAM_TPB * 16 - 1) / (BAM_TPB * 16));
 		const u32 min_qual = nte_reads::min_qual(c);
 		if (min_qual) {
@@ -728,6 +899,22 @@ ntedit_hip_reads_bam_set_segment(ntedit_hip_ctx* c, uint64_t bytes)
 }
 
 int
+ntedit_hip_reads_bam_set_group_width(ntedit_hip_ctx* c, uint32_t lanes)
+{
+	if (!c || (lanes != 0 && lanes != 8 && lanes != 16 && lanes != 64)) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_set_group_width: 0 (by the reads' mean length), 8, 16 or 64 lanes per record") : NTEDIT_E_ARG;
+	}
+	bam_state(c, true)->group_width = lanes;
+	return 0;
+}
+
+int
+ntedit_hip_reads_bam_group_width(ntedit_hip_ctx* c)
+{
+	return c ? (int)bam_state(c, true)->last_width : NTEDIT_E_ARG;
+}
+
+int
 ntedit_hip_reads_bam_info(ntedit_hip_ctx* c, ntedit_hip_reads_bam_stats* st)
 {
 	if (!c || !st) {
@@ -776,9 +963,29 @@ ntedit_hip_reads_bam_model_q(const void* raw, uint64_t n_raw, int at_header, uin
 	if (!res || (n_raw && !raw) || (cap && !out) || min_qual > nte_parse::RP_MAX_MIN_QUAL) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_bam_model: bad argument");
 	}
+	return ntedit_hip_reads_bam_model_f(raw, n_raw, at_header, min_len, min_qual, 0, 0, 0.0f, out, cap, res, nullptr);
+}
+
+int
+ntedit_hip_reads_bam_model_f(const void* raw, uint64_t n_raw, int at_header, uint32_t min_len, uint32_t min_qual, uint32_t min_read_len,
+                             uint32_t min_mean_qual, float min_rq, char* out, uint64_t cap, ntedit_hip_reads_bam_result* res,
+                             ntedit_hip_reads_read_filter_stats* st)
+{
+	if (!res || (n_raw && !raw) || (cap && !out) || min_qual > nte_parse::RP_MAX_MIN_QUAL || min_read_len > nte_parse::RP_MAX_MIN_READ_LEN ||
+	    min_mean_qual > nte_parse::RP_MAX_MEAN_QUAL || !(min_rq >= 0.0f && min_rq <= 1.0f)) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_bam_model: bad argument");
+	}
+	nte_parse::ReadFilter f = nte_parse::ReadFilter();
+	f.min_len = min_read_len;
+	f.min_mean_qual = min_mean_qual;
+	f.rq_bits = nte_parse::rp_rq_bits(min_rq);
 	BamResult r;
-	bam_model_q((const u8*)raw, n_raw, at_header, min_len, min_qual, out, cap, &r, nullptr);
+	nte_parse::ReadFilterCounts fc = nte_parse::ReadFilterCounts();
+	bam_model_f((const u8*)raw, n_raw, at_header, min_len, min_qual, f, out, cap, &r, nullptr, &fc);
 	to_result(r, res);
+	if (st) {
+		memcpy(st, &fc, sizeof fc);
+	}
 	if (r.clean && r.text_len > cap) {
 		return pfail(nullptr, NTEDIT_E_OVERFLOW, "reads_bam_model: the text does not fit the buffer");
 	}

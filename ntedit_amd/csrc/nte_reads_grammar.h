@@ -1,7 +1,7 @@
 // nte_reads_grammar.h -- the clean grammar of --gpu_parse, written once: the class of a line, what makes a chunk clean,
-// which records are kept, and what --min_qual makes of a base.  The parse kernels (nte_reads_parse.hip) and the serial
-// host model (rp_model of nte_reads_model.h: ntedit_hip_reads_parse_model) are both built from these functions, as
-// nte_lanes.h serves the machine.
+// which records are kept (by length, and by the read filter's rules), and what --min_qual makes of a base.  The parse
+// kernels (nte_reads_parse.hip) and the serial host model (rp_model of nte_reads_model.h: ntedit_hip_reads_parse_model)
+// are both built from these functions, as nte_lanes.h serves the machine.
 //
 // A chunk is a run of raw file bytes that starts at a record start.  Its kind is its first byte, '>' (FASTA) or '@'
 // (4-line FASTQ).  Lines are the runs between '\n'; bytes behind the last '\n' are a last line of their own.  The
@@ -150,6 +150,103 @@ RP_HD uint8_t
 rp_mask_base(uint8_t base, int qual, uint32_t min_qual)
 {
 	return rp_mask_base(base, rp_masked(qual, min_qual));
+}
+
+// --min_read_len L, --min_mean_qual Q, --min_rq R: which records are kept, beyond their length against k.  A record goes
+// into the text when it passes every rule; a dropped one is counted under the first rule that drops it, in the order
+// flag (BAM), length, rq, mean quality.  Written once: the record kernels, the two models and the host parser call these.
+struct ReadFilter
+{
+	uint32_t min_len;       // --min_read_len (0: off): the shortest record kept is max(min_len, what it is without)
+	uint32_t min_mean_qual; // --min_mean_qual (0: off), 1 to RP_MAX_MEAN_QUAL
+	uint32_t rq_bits;       // --min_rq R as the bits of the float (0: off); nte_bam_grammar.h applies it
+};
+
+enum : uint32_t { RP_KEPT = 0, RP_DROP_FLAG = 1, RP_DROP_LENGTH = 2, RP_DROP_RQ = 3, RP_DROP_MEAN_QUAL = 4 };
+
+// what the last pass's records came to (ntedit_hip_reads_read_filter_stats, field for field)
+struct ReadFilterCounts
+{
+	uint64_t records, by_length, by_rq, by_mean_qual, rq_tagged, aux_malformed;
+};
+
+constexpr uint32_t RP_MAX_MEAN_QUAL = 60;
+constexpr uint32_t RP_MAX_MIN_READ_LEN = 0x7FFFFFFFu;
+constexpr uint32_t RP_MAX_QUAL = 93;
+
+// R as ReadFilter keeps it: the float's bits, and 0 (off) for every value that is not above 0, -0.0 among them (host only)
+inline uint32_t
+rp_rq_bits(float min_rq)
+{
+	union { float f; uint32_t u; } v;
+	v.f = min_rq;
+	return min_rq > 0.0f ? v.u : 0u;
+}
+
+RP_HD bool
+rp_filter_on(const ReadFilter& f)
+{
+	return f.min_len || f.min_mean_qual || f.rq_bits;
+}
+
+// the shortest record kept: max(L, what it is without the option)
+RP_HD uint32_t
+rp_min_len(const ReadFilter& f, uint32_t k)
+{
+	return f.min_len > k ? f.min_len : k;
+}
+
+// A read's mean quality is the Phred value of its mean error probability (as NanoFilt, chopper and fastplong take it),
+// not the mean of the Phred values, and it is computed in integers so that every adder agrees to the bit whatever its
+// order: E[q] = round(2^31 * 10^(-q/10)) for q = 0 .. 93, no entry a rounding tie (computed with 60 decimal digits).
+constexpr uint32_t RP_QUAL_WEIGHT[94] = {
+	2147483648u, 1705806895u, 1354970580u, 1076291389u, 854928639u, 679093957u, 539423504u, 428479319u,
+	340353221u, 270352174u, 214748365u, 170580690u, 135497058u, 107629139u, 85492864u, 67909396u,
+	53942350u, 42847932u, 34035322u, 27035217u, 21474836u, 17058069u, 13549706u, 10762914u,
+	8549286u, 6790940u, 5394235u, 4284793u, 3403532u, 2703522u, 2147484u, 1705807u,
+	1354971u, 1076291u, 854929u, 679094u, 539424u, 428479u, 340353u, 270352u,
+	214748u, 170581u, 135497u, 107629u, 85493u, 67909u, 53942u, 42848u,
+	34035u, 27035u, 21475u, 17058u, 13550u, 10763u, 8549u, 6791u,
+	5394u, 4285u, 3404u, 2704u, 2147u, 1706u, 1355u, 1076u,
+	855u, 679u, 539u, 428u, 340u, 270u, 215u, 171u,
+	135u, 108u, 85u, 68u, 54u, 43u, 34u, 27u,
+	21u, 17u, 14u, 11u, 9u, 7u, 5u, 4u,
+	3u, 3u, 2u, 2u, 1u, 1u,
+};
+
+// the table's index for a Phred quality: a FASTQ byte below the offset counts as 0, a quality above 93 as 93
+RP_HD uint32_t
+rp_qual_index(int qual)
+{
+	return qual < 0 ? 0u : qual > (int)RP_MAX_QUAL ? RP_MAX_QUAL : (uint32_t)qual;
+}
+
+// what a base of Phred quality `qual` adds to its read's sum (a kernel reads its own copy of the table at rp_qual_index)
+RP_HD uint32_t
+rp_qual_weight(int qual)
+{
+	return RP_QUAL_WEIGHT[rp_qual_index(qual)];
+}
+
+// the one comparison: a read of `len` bases (< 2^31, so sum < 2^62) whose weights sum to `sum` has a mean quality of
+// Q or more
+RP_HD bool
+rp_mean_qual_kept(uint64_t sum, uint64_t len, uint32_t min_mean_qual)
+{
+	return sum <= len * (uint64_t)RP_QUAL_WEIGHT[min_mean_qual];
+}
+
+// a text record (FASTA: has_qual false) of len bases whose quality weights sum to `sum`: RP_KEPT or the rule that drops it
+RP_HD uint32_t
+rp_record_reason(uint64_t len, uint32_t k, const ReadFilter& f, bool has_qual, uint64_t sum)
+{
+	if (!rp_record_kept(len, rp_min_len(f, k))) {
+		return RP_DROP_LENGTH;
+	}
+	if (f.min_mean_qual && has_qual && !rp_mean_qual_kept(sum, len, f.min_mean_qual)) {
+		return RP_DROP_MEAN_QUAL;
+	}
+	return RP_KEPT;
 }
 
 } // namespace nte_parse

@@ -23,8 +23,11 @@ struct RpResult // (ntedit_hip_reads_parse_result, field for field)
 // out[0 .. cap) as far as it fits; res->text_len is its whole length either way (false: it did not fit).  With min_qual a
 // FASTQ record's bases are masked by its quality line as far as that line reaches: in a clean chunk all of them, and an
 // unclean chunk has no text.
+// With a filter (rp_record_reason) a FASTQ record's quality weights are summed over its quality line as stored, whatever
+// min_qual masks; fc (may be NULL) += what the records of a clean chunk came to.
 inline bool
-rp_model(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* out, uint64_t cap, RpResult* res)
+rp_model_f(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, const ReadFilter& f, char* out, uint64_t cap, RpResult* res,
+           ReadFilterCounts* fc)
 {
 	*res = RpResult();
 	if (n_raw == 0) {
@@ -33,11 +36,20 @@ rp_model(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* o
 	}
 	const int kind = (unsigned char)raw[0];
 	uint32_t broken = memchr(raw, '\r', n_raw) ? (uint32_t)RP_BAD_CR : 0u;
-	uint64_t lines = 0, used = 0, reads = 0, bases = 0, seq_len = 0;
+	uint64_t lines = 0, used = 0, reads = 0, bases = 0, seq_len = 0, qual_sum = 0;
 	std::string cur;
-	bool open = false;
+	bool open = false, has_qual = false;
+	ReadFilterCounts seen = ReadFilterCounts();
 	auto flush = [&]() {
-		if (open && rp_record_kept(cur.size(), k)) {
+		const uint32_t why = open ? rp_record_reason(cur.size(), k, f, has_qual, qual_sum) : (uint32_t)RP_DROP_LENGTH;
+		if (open && rp_filter_on(f)) {
+			seen.records++;
+			seen.by_length += why == RP_DROP_LENGTH;
+			seen.by_mean_qual += why == RP_DROP_MEAN_QUAL;
+		}
+		qual_sum = 0;
+		has_qual = false;
+		if (open && why == RP_KEPT) {
 			if (used + cur.size() + 1 <= cap) {
 				memcpy(out + used, cur.data(), cur.size());
 				out[used + cur.size()] = '\n';
@@ -61,6 +73,10 @@ rp_model(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* o
 			seq_len = e - s;
 		} else if (kind == '@' && lines % 4 == 3) {
 			broken |= rp_quality_broken(seq_len, e - s);
+			has_qual = true;
+			for (uint64_t j = 0; f.min_mean_qual && j < e - s; j++) {
+				qual_sum += rp_qual_weight((int)(unsigned char)raw[s + j] - RP_QUAL_OFFSET);
+			}
 			for (uint64_t j = 0; min_qual && j < seq_len && j < e - s; j++) { // (cur ends with the sequence line's seq_len bytes)
 				char& base = cur[cur.size() - seq_len + j];
 				base = (char)rp_mask_base((uint8_t)base, (int)(unsigned char)raw[s + j] - RP_QUAL_OFFSET, min_qual);
@@ -80,7 +96,18 @@ rp_model(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* o
 	res->text_len = used;
 	res->reads = reads;
 	res->bases = bases;
+	if (fc) {
+		fc->records += seen.records;
+		fc->by_length += seen.by_length;
+		fc->by_mean_qual += seen.by_mean_qual;
+	}
 	return used <= cap;
+}
+
+inline bool
+rp_model(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, char* out, uint64_t cap, RpResult* res)
+{
+	return rp_model_f(raw, n_raw, k, min_qual, ReadFilter(), out, cap, res, nullptr);
 }
 
 } // namespace nte_parse

@@ -12,7 +12,10 @@
 //   k_rp_classify    one lane per line: class and grammar checks (violations OR into one status word), and per line
 //                    (record heads, sequence bytes) packed in 64 bits
 //   scan             over the lines: each line's record and its offset in the record's sequence
-//   k_rp_heads / k_rp_records   each record's head line and length; kept records emit (1, length + 1)
+//   k_rp_qsum        (--min_mean_qual, FASTQ chunks) byte-parallel over the raw tiles: the quality weights of each quality
+//                    line summed into a table indexed by line, one atomic per (wavefront, line)
+//   k_rp_heads / k_rp_records   each record's head line and length; kept records emit (1, length + 1).  k_rp_records<true>
+//                    (--min_read_len, --min_mean_qual) keeps by rp_record_reason and counts the drops per rule
 //   scan             over the records: each kept record's offset in the text
 //   k_rp_line_out    each sequence line's offset in the text, and the '\n' behind each kept record
 //   k_rp_copy        byte-parallel over the raw tiles: each lane finds the line of its 16 bytes from the tile base and
@@ -82,6 +85,8 @@ struct RpInfo // the small result the device keeps per chunk
 	u32 state_out;
 	// --min_qual (k_rp_copy<true>): the bases copied that had a quality byte, and those of them masked
 	u64 qual_bases, masked_bases;
+	// --min_read_len, --min_mean_qual (k_rp_records<true>): the chunk's records and its drops per rule
+	ReadFilterCounts filter;
 };
 
 __host__ __device__ __forceinline__ u32
@@ -357,22 +362,133 @@ k_rp_heads(const u8* __restrict__ cls, const u64* __restrict__ sr, u64 n_lines, 
 	}
 }
 
-// per record r: (1 << 32 | length + 1) when it is kept, else 0 (and 0 for r at or past the number of records)
-__global__ __launch_bounds__(RP_TPB) void
-k_rp_records(const u64* __restrict__ sr, const u32* __restrict__ head_line, u64 n_lines, u32 k, u64* __restrict__ rec)
+// --min_mean_qual on a FASTQ chunk: qsum[L] += the quality weights (rp_qual_weight) of the bytes of every line L with
+// L % 4 == 3, the table indexed by line so that a chunk not yet known clean cannot index out of it (qsum is zeroed per
+// chunk and has n_lines entries).  Byte-parallel over the raw tiles like k_rp_copy: a lane holds 16 bytes and the line
+// each lies in.  The sums are integers, so atomics give the same result in any order, but not one per byte: a lane sums
+// its bytes per line in registers, the lanes of a wavefront that hold pieces of one line combine by a segmented scan
+// keyed on the line (a lane's piece opens a segment where it holds a '\n'), and one atomicAdd per (wavefront, line)
+// reaches memory -- from the lane that holds the line's '\n', or from lane 63 for the line that runs on.
+__device__ __forceinline__ u64
+rp_shfl_up64(u64 v, int d)
 {
-	const u64 r = (u64)blockIdx.x * RP_TPB + threadIdx.x;
-	if (r >= n_lines) {
-		return;
+	const u32 lo = __shfl_up((u32)v, d, 64), hi = __shfl_up((u32)(v >> 32), d, 64);
+	return ((u64)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_qsum(const u8* __restrict__ raw, u64 n, const u64* __restrict__ tile_base, u64 n_lines, u64* __restrict__ qsum)
+{
+	__shared__ u32 s_weight[RP_MAX_QUAL + 1];
+	if (threadIdx.x <= RP_MAX_QUAL) {
+		s_weight[threadIdx.x] = RP_QUAL_WEIGHT[threadIdx.x];
 	}
-	u64 v = 0;
-	if (r < hi32(sr[n_lines])) {
-		const u32 len = lo32(sr[head_line[r + 1]]) - lo32(sr[head_line[r]]);
-		if (rp_record_kept(len, k)) {
-			v = (1ull << 32) | ((u64)len + 1);
+	u32 mask[RP_IT], before[RP_IT];
+	uint4 bytes[RP_IT];
+	const u64 tile_off = (u64)blockIdx.x * RP_TILE;
+	rp_tile_ranks(raw, n, tile_off, mask, before, bytes); // (its barrier also publishes s_weight)
+	const u64 base = tile_base[blockIdx.x];
+	const u32 lane = threadIdx.x & 63;
+#pragma unroll
+	for (int j = 0; j < RP_IT; j++) {
+		const u64 off = tile_off + (u64)j * (RP_TPB * 16) + threadIdx.x * 16;
+		const u32 w[4] = { bytes[j].x, bytes[j].y, bytes[j].z, bytes[j].w };
+		const u32 m = mask[j];
+		const u64 line0 = base + before[j]; // the line of this lane's first byte
+		u64 line = line0;
+		u64 head = 0, run = 0; // the sum up to the first '\n' (the line that came in), and of the line being walked
+		bool closed = false;   // a '\n' seen: `head` is final
+#pragma unroll
+		for (int b = 0; b < 16; b++) {
+			if ((m >> b) & 1u) { // (bytes past n read as 0: no '\n' among them)
+				if (!closed) {
+					head = run;
+					closed = true;
+				} else if (run && line < n_lines) { // a line that lies wholly in these 16 bytes
+					atomicAdd((unsigned long long*)&qsum[line], (unsigned long long)run);
+				}
+				run = 0;
+				line++;
+			} else if ((line & 3) == 3 && off + b < n) {
+				run += s_weight[rp_qual_index((int)((w[b >> 2] >> (8 * (b & 3))) & 0xFFu) - RP_QUAL_OFFSET)];
+			}
+		}
+		// `run` now belongs to the line that leaves the lane.  Inclusive segmented scan of it over the lanes: a lane with
+		// a '\n' opens a segment (what came before belongs to other lines)
+		u64 acc = run;
+		bool opened = closed;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const u64 up = rp_shfl_up64(acc, d);
+			const bool up_opened = __shfl_up((int)opened, d, 64) != 0;
+			if (lane >= (u32)d) {
+				if (!opened) {
+					acc += up;
+				}
+				opened = opened || up_opened;
+			}
+		}
+		// the line that came into a lane with a '\n' ends there: what the lanes before hold of it, and this lane's head
+		const u64 before_me = rp_shfl_up64(acc, 1);
+		if (closed) {
+			const u64 total = head + (lane ? before_me : 0);
+			if (total && line0 < n_lines) {
+				atomicAdd((unsigned long long*)&qsum[line0], (unsigned long long)total);
+			}
+		}
+		if (lane == 63 && acc && line < n_lines) { // the line that runs on behind the wavefront's bytes
+			atomicAdd((unsigned long long*)&qsum[line], (unsigned long long)acc);
 		}
 	}
-	rec[r] = v;
+}
+
+// per record r: (1 << 32 | length + 1) when it is kept, else 0 (and 0 for r at or past the number of records).
+// FILTER (--min_read_len, --min_mean_qual): the rule is rp_record_reason, k the shortest record kept without the options;
+// a FASTQ record's weights are qsum[head_line[r] + 3], read only when that line is in the table (qsum: NULL without
+// --min_mean_qual and for a FASTA chunk).  The records and the drops per rule are summed per wavefront and added to info
+// by one atomic each per wavefront.
+template <bool FILTER>
+__global__ __launch_bounds__(RP_TPB) void
+k_rp_records(const u64* __restrict__ sr, const u32* __restrict__ head_line, u64 n_lines, u32 k, u64* __restrict__ rec, ReadFilter f,
+             const u64* __restrict__ qsum, RpInfo* info)
+{
+	const u64 r = (u64)blockIdx.x * RP_TPB + threadIdx.x;
+	u32 seen = 0, by_len = 0, by_mq = 0;
+	if (r < n_lines) {
+		u64 v = 0;
+		if (r < hi32(sr[n_lines])) {
+			const u32 len = lo32(sr[head_line[r + 1]]) - lo32(sr[head_line[r]]);
+			bool keep;
+			if (FILTER) {
+				const u64 qline = (u64)head_line[r] + 3;
+				const bool has_qual = qsum != nullptr && qline < n_lines;
+				const u32 why = rp_record_reason(len, k, f, has_qual, has_qual ? qsum[qline] : 0);
+				seen = 1;
+				by_len = why == RP_DROP_LENGTH;
+				by_mq = why == RP_DROP_MEAN_QUAL;
+				keep = why == RP_KEPT;
+			} else {
+				keep = rp_record_kept(len, k);
+			}
+			if (keep) {
+				v = (1ull << 32) | ((u64)len + 1);
+			}
+		}
+		rec[r] = v;
+	}
+	if (FILTER) {
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			seen += __shfl_xor(seen, d, 64);
+			by_len += __shfl_xor(by_len, d, 64);
+			by_mq += __shfl_xor(by_mq, d, 64);
+		}
+		if ((threadIdx.x & 63) == 0 && seen) {
+			atomicAdd((unsigned long long*)&info->filter.records, (unsigned long long)seen);
+			atomicAdd((unsigned long long*)&info->filter.by_length, (unsigned long long)by_len);
+			atomicAdd((unsigned long long*)&info->filter.by_mean_qual, (unsigned long long)by_mq);
+		}
+	}
 }
 
 // rec[r]: hi = kept records before r, lo = their text bytes: record r's place.  Each sequence line's place, the '\n'
@@ -549,6 +665,8 @@ struct ParseState
 	int on = 0; // ntedit_hip_reads_set_device_parse
 	u32 min_qual = 0;                        // ntedit_hip_reads_set_min_qual (0: off)
 	u64 qual_bases = 0, masked_bases = 0;    // ntedit_hip_reads_min_qual_info: the last pass, host parser and device
+	ReadFilter filter = ReadFilter();        // ntedit_hip_reads_set_read_filter (all 0: off)
+	ReadFilterCounts fcounts = ReadFilterCounts(); // ntedit_hip_reads_read_filter_info: the last pass, host parser and device
 	ntedit_hip_reads_parse_stats info = {};
 	ntedit_hip_genome_pass_info ginfo = {}; // ntedit_hip_genome_pass
 	// device scratch, grow-only, released by ntedit_hip_sketch_free
@@ -564,6 +682,7 @@ struct ParseState
 	u8* d_gstage = nullptr; // GP_PAD bytes
 	u8* d_table = nullptr; // the line table and the scans' block sums, for chunks of up to table_raw bytes
 	u64 table_raw = 0;
+	bool table_qsum = false; // the allocation has room for the quality sums (k_rp_qsum)
 	RpInfo* d_info = nullptr;
 	RpInfo* h_info = nullptr; // page-locked
 };
@@ -636,12 +755,16 @@ release_scratch(ParseState* s)
 	const ntedit_hip_genome_pass_info ginfo = s->ginfo;
 	const u32 min_qual = s->min_qual;
 	const u64 qual_bases = s->qual_bases, masked_bases = s->masked_bases;
+	const ReadFilter filter = s->filter;
+	const ReadFilterCounts fcounts = s->fcounts;
 	*s = ParseState();
 	s->owner = owner;
 	s->on = on;
 	s->min_qual = min_qual;
 	s->qual_bases = qual_bases;
 	s->masked_bases = masked_bases;
+	s->filter = filter;
+	s->fcounts = fcounts;
 	s->info = info;
 	s->ginfo = ginfo;
 }
@@ -695,14 +818,14 @@ up256(u64 x)
 // the line table of a chunk of up to n raw bytes, carved from one allocation
 struct Table
 {
-	u64 *tile, *sr, *rec, *bsum;
+	u64 *tile, *sr, *rec, *bsum, *qsum;
 	u32 *line_end, *head_line, *line_out;
 	u8* cls;
 	u64 bytes;
 };
 
 Table
-carve(u8* base, u64 n_raw)
+carve(u8* base, u64 n_raw, bool with_qsum = false)
 {
 	const u64 tiles = (n_raw + RP_TILE - 1) / RP_TILE + 1, lines = rp_max_lines(n_raw) + 2;
 	const u64 blocks = (lines > tiles ? lines : tiles) / SC_BLOCK + 2;
@@ -721,6 +844,7 @@ carve(u8* base, u64 n_raw)
 	t.head_line = (u32*)take(lines * 4);
 	t.line_out = (u32*)take(lines * 4);
 	t.cls = take(lines);
+	t.qsum = with_qsum ? (u64*)take(lines * 8) : nullptr; // (--min_mean_qual alone pays for k_rp_qsum's table: it lies last)
 	t.bytes = at;
 	return t;
 }
@@ -748,17 +872,20 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 		res->broken = RP_BAD_SIZE;
 		return 0;
 	}
-	if (n > s->table_raw || !s->d_table) {
-		const u64 want = n + (1u << 20);
+	const bool need_qsum = s->filter.min_mean_qual != 0;
+	if (n > s->table_raw || !s->d_table || (need_qsum && !s->table_qsum)) {
+		const u64 want = n > s->table_raw ? n + (1u << 20) : s->table_raw;
 		if (s->d_table) {
+			RP_TRY(c, hipStreamSynchronize(s->stream));
 			RP_TRY(c, hipFree(s->d_table));
 			s->d_table = nullptr;
 			s->table_raw = 0;
 		}
-		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
+		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want, need_qsum).bytes));
 		s->table_raw = want;
+		s->table_qsum = need_qsum;
 	}
-	const Table t = carve(s->d_table, s->table_raw);
+	const Table t = carve(s->d_table, s->table_raw, s->table_qsum);
 	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
 	RP_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
 	RP_TRY(c, hipEventRecord(s->ev[0], s->stream));
@@ -786,7 +913,19 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 	hipLaunchKernelGGL(k_rp_classify, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, d_raw, n, t.line_end, lines, t.cls, t.sr, s->d_info);
 	scan(s, t.sr, lines, t.bsum);
 	hipLaunchKernelGGL(k_rp_heads, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, lines, t.head_line);
-	hipLaunchKernelGGL(k_rp_records, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.sr, t.head_line, lines, k, t.rec);
+	if (rp_filter_on(s->filter)) {
+		// (rq is the BAM unit's; a FASTA chunk has no qualities: the length rule alone, and no sums)
+		const bool sums = s->filter.min_mean_qual && res->kind == '@';
+		if (sums) {
+			RP_TRY(c, hipMemsetAsync(t.qsum, 0, lines * 8, s->stream));
+			hipLaunchKernelGGL(k_rp_qsum, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, lines, t.qsum);
+		}
+		hipLaunchKernelGGL(k_rp_records<true>, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.sr, t.head_line, lines, k, t.rec, s->filter,
+		                   sums ? t.qsum : nullptr, s->d_info);
+	} else {
+		hipLaunchKernelGGL(k_rp_records<false>, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.sr, t.head_line, lines, k, t.rec,
+		                   ReadFilter(), nullptr, s->d_info);
+	}
 	scan(s, t.rec, lines, t.bsum);
 	hipLaunchKernelGGL(k_rp_line_out, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, t.head_line, t.rec, lines, t.line_out,
 	                   d_text, text_cap, s->d_info);
@@ -809,6 +948,9 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 	}
 	s->qual_bases += s->h_info->qual_bases; // (zero without --min_qual: the chunk's info is zeroed, and only the mask adds)
 	s->masked_bases += s->h_info->masked_bases;
+	s->fcounts.records += s->h_info->filter.records; // (zero without a read filter, alike)
+	s->fcounts.by_length += s->h_info->filter.by_length;
+	s->fcounts.by_mean_qual += s->h_info->filter.by_mean_qual;
 	res->clean = 1;
 	res->text_len = lo32(s->h_info->records);
 	res->reads = hi32(s->h_info->records);
@@ -842,6 +984,7 @@ genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n,
 		}
 		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
 		s->table_raw = want;
+		s->table_qsum = false;
 	}
 	const Table t = carve(s->d_table, s->table_raw);
 	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
@@ -945,6 +1088,7 @@ parse_lines(const ntedit_hip_ctx* c, const unsigned char* d_raw, uint64_t n, con
 		}
 		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
 		s->table_raw = want;
+		s->table_qsum = false;
 	}
 	const Table t = carve(s->d_table, s->table_raw);
 	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
@@ -1190,6 +1334,32 @@ min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t
 	s->masked_bases += masked_bases;
 }
 
+// --min_read_len, --min_mean_qual, --min_rq: the context's setting, and what the last pass's records came to (the pass
+// zeroes the counts; the host parser and the BAM unit add theirs)
+ReadFilter
+read_filter(const ntedit_hip_ctx* c)
+{
+	ParseState* s = parse_state(c, false);
+	return s ? s->filter : ReadFilter();
+}
+
+void
+read_filter_count(const ntedit_hip_ctx* c, int reset, const ReadFilterCounts* add)
+{
+	ParseState* s = parse_state(c, true);
+	if (reset) {
+		s->fcounts = ReadFilterCounts();
+	}
+	if (add) {
+		s->fcounts.records += add->records;
+		s->fcounts.by_length += add->by_length;
+		s->fcounts.by_rq += add->by_rq;
+		s->fcounts.by_mean_qual += add->by_mean_qual;
+		s->fcounts.rq_tagged += add->rq_tagged;
+		s->fcounts.aux_malformed += add->aux_malformed;
+	}
+}
+
 int
 parse_is_on(const ntedit_hip_ctx* c)
 {
@@ -1286,6 +1456,47 @@ ntedit_hip_reads_min_qual_info(ntedit_hip_ctx* c, uint64_t* qual_bases, uint64_t
 }
 
 int
+ntedit_hip_reads_set_read_filter(ntedit_hip_ctx* c, uint32_t min_len, uint32_t min_mean_qual, float min_rq)
+{
+	// (written so that a NaN is refused)
+	if (!c || min_len > RP_MAX_MIN_READ_LEN || min_mean_qual > RP_MAX_MEAN_QUAL || !(min_rq >= 0.0f && min_rq <= 1.0f)) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_set_read_filter: the minimum read length is 0 (off) or up to 2^31 - 1, the minimum mean "
+		                                  "quality 0 (off) or between 1 and 60, the minimum rq 0 (off) or above 0 and at most 1")
+		         : NTEDIT_E_ARG;
+	}
+	ReadFilter f = ReadFilter();
+	f.min_len = min_len;
+	f.min_mean_qual = min_mean_qual;
+	f.rq_bits = rp_rq_bits(min_rq);
+	parse_state(c, true)->filter = f;
+	return 0;
+}
+
+int
+ntedit_hip_reads_get_read_filter(ntedit_hip_ctx* c, uint32_t* min_len, uint32_t* min_mean_qual, float* min_rq)
+{
+	if (!c || !min_len || !min_mean_qual || !min_rq) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_get_read_filter: bad argument") : NTEDIT_E_ARG;
+	}
+	const ReadFilter f = parse_state(c, true)->filter;
+	*min_len = f.min_len;
+	*min_mean_qual = f.min_mean_qual;
+	memcpy(min_rq, &f.rq_bits, 4);
+	return 0;
+}
+
+int
+ntedit_hip_reads_read_filter_info(ntedit_hip_ctx* c, ntedit_hip_reads_read_filter_stats* st)
+{
+	if (!c || !st) {
+		return c ? pfail(c, NTEDIT_E_ARG, "reads_read_filter_info: bad argument") : NTEDIT_E_ARG;
+	}
+	static_assert(sizeof(ntedit_hip_reads_read_filter_stats) == sizeof(ReadFilterCounts), "the counts are the grammar's, field for field");
+	memcpy(st, &parse_state(c, true)->fcounts, sizeof *st);
+	return 0;
+}
+
+int
 ntedit_hip_reads_parse_info(ntedit_hip_ctx* c, ntedit_hip_reads_parse_stats* st)
 {
 	if (!c || !st) {
@@ -1339,10 +1550,30 @@ ntedit_hip_reads_parse_model_q(const char* raw, uint64_t n_raw, uint32_t k, uint
 	if (!res || (n_raw && !raw) || (cap && !out) || k == 0 || min_qual > RP_MAX_MIN_QUAL) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_parse_model: bad argument");
 	}
+	return ntedit_hip_reads_parse_model_f(raw, n_raw, k, min_qual, 0, 0, 0.0f, out, cap, res, nullptr);
+}
+
+int
+ntedit_hip_reads_parse_model_f(const char* raw, uint64_t n_raw, uint32_t k, uint32_t min_qual, uint32_t min_len, uint32_t min_mean_qual,
+                               float min_rq, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res,
+                               ntedit_hip_reads_read_filter_stats* st)
+{
+	if (!res || (n_raw && !raw) || (cap && !out) || k == 0 || min_qual > RP_MAX_MIN_QUAL || min_len > RP_MAX_MIN_READ_LEN ||
+	    min_mean_qual > RP_MAX_MEAN_QUAL || !(min_rq >= 0.0f && min_rq <= 1.0f)) {
+		return pfail(nullptr, NTEDIT_E_ARG, "reads_parse_model: bad argument");
+	}
+	ReadFilter f = ReadFilter();
+	f.min_len = min_len;
+	f.min_mean_qual = min_mean_qual;
+	f.rq_bits = rp_rq_bits(min_rq);
 	RpResult m;
-	const bool fits = rp_model(raw, n_raw, k, min_qual, out, cap, &m);
+	ReadFilterCounts fc = ReadFilterCounts();
+	const bool fits = rp_model_f(raw, n_raw, k, min_qual, f, out, cap, &m, &fc);
 	static_assert(sizeof(ntedit_hip_reads_parse_result) == sizeof(RpResult), "the result is the grammar's, field for field");
 	memcpy(res, &m, sizeof m);
+	if (st) {
+		memcpy(st, &fc, sizeof fc);
+	}
 	return fits ? 0 : NTEDIT_E_OVERFLOW;
 }
 

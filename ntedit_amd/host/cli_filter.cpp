@@ -117,6 +117,7 @@ filter_from_reads(ntedit_hip_ctx* ctx, const CliOptions& o, size_t round, const 
 	ba.reject_bf_bytes = rr.reject_bf_bytes;
 	ba.reject_num_elements = rr.reject_num_elements;
 	ba.min_qual = rr.min_qual;
+	ntedit_hip_reads_set_read_filter(ctx, o.filter_rules.min_read_len, o.filter_rules.min_mean_qual, o.filter_rules.min_rq); // (every round alike)
 	if (cascade) {
 		// round 1 fills the store with every read a later round has to count (the shortest k decides) and every
 		// round but the last leaves it to the next; a round that finds it ON reads nothing else

@@ -129,8 +129,32 @@ static const char HELP_MIN_QUAL[] = PROGRAM
     "			makes of the same reads with those bases rewritten to N.  With -k K1,K2,... every round masks alike (the\n"
     "			reads kept in HBM are the masked ones).  Each pass over the files reports `--min_qual Q: M of B bases with\n"
     "			a quality masked'; --report adds \"min_qual\" to each pass of the reads build.  Not with --genome or -r.\n"
-    "			Not built: trimming instead of masking, per-read mean-quality filters, BAM tag filters such as rq\n"
+    "			Not built: trimming instead of masking.  Which reads are kept at all: --help-read-filter\n"
     "	--help-min-qual,	display this paragraph and exit\n\n";
+
+static const char HELP_READ_FILTER[] = PROGRAM
+    " --reads --min_read_len --min_mean_qual --min_rq\n\n"
+    "	Which reads go into the reads filter's build.  A record goes in when it passes every rule below; otherwise it is\n"
+    "	absent, as a record shorter than k is without them.  The rules hold for every pass over the files and every round\n"
+    "	of -k K1,K2,...: the reads kept in HBM are those that passed.\n"
+    "	--min_read_len L,	L is 1 to 2147483647: the shortest record kept is the larger of L and what it is without\n"
+    "	--min_rq R,	R is above 0 and at most 1.  A BAM record whose rq aux field of type f holds v is kept iff v >= R, as two\n"
+    "			IEEE floats compare: a NaN is dropped.  A record without an rq:f field passes: every FASTA and FASTQ\n"
+    "			record does.  The aux walk follows the SAM specification's types (A c C 1 byte, s S 2, i I f 4, Z H to a\n"
+    "			NUL, B subtype + count * size) and never leaves the record; a field that does not fit, or of an unknown\n"
+    "			type, ends it: the record counts as having no tag, and as malformed in the pass line\n"
+    "	--min_mean_qual Q,	Q is 1 to 60.  A read's mean quality is the Phred value of its mean error probability (as NanoFilt,\n"
+    "			chopper and fastplong take it), not the mean of the Phred values, computed in integers: a base of Phred\n"
+    "			quality q adds E[min(q, 93)], E[q] = round(2^31 * 10^(-q/10)) (a FASTQ byte below 33 counts as q = 0), S\n"
+    "			is the sum over the read, and the read is kept iff S <= len * E[Q].  Records without qualities pass: FASTA\n"
+    "			records, and BAM records whose qualities are absent.  With --min_qual the mean is taken over the\n"
+    "			qualities as stored, not over the masked text, and --min_qual's counts cover the reads that were copied\n"
+    "	A dropped record is counted under the first rule that drops it, in the order flag (BAM), length, rq, mean quality.\n"
+    "	Each pass over the files reports `read filter: D of N records dropped (length a, rq b, mean quality c)'; --report\n"
+    "	adds \"read_filter\" to each pass of the reads build.  The host parser and --gpu_parse (plain, BGZF and BAM) give the\n"
+    "	same filter: the one a build without the options makes of the same reads with the dropped ones deleted.  Not with\n"
+    "	--genome or -r.  Not built: Phred+64, trimming, other BAM tags (np, ec), a maximum read length\n"
+    "	--help-read-filter,	display this paragraph and exit\n\n";
 
 static const char HELP_BED[] = PROGRAM
     " --qv --bed\n\n"
@@ -231,7 +255,11 @@ enum
 	OPT_CN_SKETCH,
 	OPT_HELP_CN,
 	OPT_MIN_QUAL,
-	OPT_HELP_MIN_QUAL
+	OPT_HELP_MIN_QUAL,
+	OPT_MIN_READ_LEN,
+	OPT_MIN_MEAN_QUAL,
+	OPT_MIN_RQ,
+	OPT_HELP_READ_FILTER
 };
 static const struct option longopts[] = {
 	{ "threads", required_argument, nullptr, 't' },
@@ -297,6 +325,10 @@ static const struct option longopts[] = {
 	{ "help-cn", no_argument, nullptr, OPT_HELP_CN },
 	{ "min_qual", required_argument, nullptr, OPT_MIN_QUAL },
 	{ "help-min-qual", no_argument, nullptr, OPT_HELP_MIN_QUAL },
+	{ "min_read_len", required_argument, nullptr, OPT_MIN_READ_LEN },
+	{ "min_mean_qual", required_argument, nullptr, OPT_MIN_MEAN_QUAL },
+	{ "min_rq", required_argument, nullptr, OPT_MIN_RQ },
+	{ "help-read-filter", no_argument, nullptr, OPT_HELP_READ_FILTER },
 	{ "help", no_argument, nullptr, OPT_HELP },
 	{ "version", no_argument, nullptr, OPT_VERSION },
 	{ nullptr, 0, nullptr, 0 }
@@ -311,6 +343,7 @@ struct ReadsOption
 	const char* name;
 	bool with_genome;
 	const char* ntedit_hip_reads_options::* text;
+	const char* ntedit_hip_reads_filter_options::* filter_text = nullptr; // (the read filter's options have a struct of their own)
 };
 static const ReadsOption READS_OPTIONS[] = {
 	{ OPT_CUTOFF, "--cutoff", false, &ntedit_hip_reads_options::cutoff },
@@ -331,6 +364,9 @@ static const ReadsOption READS_OPTIONS[] = {
 	{ OPT_STORE_CAP, "--resident_cap", false, &ntedit_hip_reads_options::store_cap },
 	{ OPT_GPU_PARSE, "--gpu_parse", true, nullptr },
 	{ OPT_MIN_QUAL, "--min_qual", false, &ntedit_hip_reads_options::min_qual },
+	{ OPT_MIN_READ_LEN, "--min_read_len", false, nullptr, &ntedit_hip_reads_filter_options::min_read_len },
+	{ OPT_MIN_MEAN_QUAL, "--min_mean_qual", false, nullptr, &ntedit_hip_reads_filter_options::min_mean_qual },
+	{ OPT_MIN_RQ, "--min_rq", false, nullptr, &ntedit_hip_reads_filter_options::min_rq },
 };
 
 static void
@@ -373,6 +409,21 @@ reads_rules(const ntedit_hip_reads_options& ro, int final)
 		refuse(ntedit_hip_reads_last_error(nullptr));
 	}
 	return rr;
+}
+
+// ... and the read filter's options through theirs, behind them
+static ntedit_hip_reads_filter_rules
+filter_rules(const ntedit_hip_reads_filter_options& fo, int final)
+{
+	ntedit_hip_reads_filter_rules fr;
+	const int rc = ntedit_hip_reads_filter_options_check(&fo, NTEDIT_READS_DIALECT_POLISHER, final, &fr);
+	if (rc == NTEDIT_READS_NOT_A_NUMBER) {
+		fail_plain("%s", ntedit_hip_reads_last_error(nullptr));
+	}
+	if (rc != 0) {
+		refuse(ntedit_hip_reads_last_error(nullptr));
+	}
+	return fr;
 }
 
 // The rules of ntedit --genome, apart from the reads options' (reads_options.cpp knows nothing of them).  The numbers arrive
@@ -490,6 +541,10 @@ parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOptio
 				if (r.text) {
 					o->ro.*r.text = optarg;
 					reads_rules(o->ro, 0);
+				}
+				if (r.filter_text) {
+					o->fo.*r.filter_text = optarg;
+					filter_rules(o->fo, 0);
 				}
 			}
 		}
@@ -657,6 +712,9 @@ parse_options(int argc, char** argv, CliOptions* o, std::vector<const ReadsOptio
 		case OPT_HELP_MIN_QUAL:
 			fputs(HELP_MIN_QUAL, stderr);
 			exit(EXIT_SUCCESS);
+		case OPT_HELP_READ_FILTER:
+			fputs(HELP_READ_FILTER, stderr);
+			exit(EXIT_SUCCESS);
 		case OPT_HELP:
 			fputs(USAGE, stderr);
 			exit(EXIT_SUCCESS);
@@ -704,6 +762,7 @@ reads_mode_rules(CliOptions* o, const std::vector<std::string>& k_list)
 			o->rounds.push_back(reads_rules(one, 1));
 		}
 	}
+	o->filter_rules = filter_rules(o->fo, 1);
 	for (const std::string& r : o->read_files) {
 		die_unreadable(r);
 	}

@@ -42,6 +42,8 @@ struct CliOptions
 	std::vector<const char*> paths;
 	bool counts = false;
 	ntedit_hip_reads_options ro = {};                 // the reads options as given
+	ntedit_hip_reads_filter_options fo = {};          // --min_read_len, --min_mean_qual, --min_rq as given ...
+	ntedit_hip_reads_filter_rules filter_rules = {};  // ... and their rules' outcome (zeros: off)
 	std::vector<ntedit_hip_reads_rules> rounds = std::vector<ntedit_hip_reads_rules>(1); // the rules of each round (one, unless -k is a list); zeros without --reads
 	std::string hist, save_bf, save_reject_bf;        // as given: a round of a cascade puts its k in place of {k}
 	GenomeRules genome;

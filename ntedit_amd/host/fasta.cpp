@@ -330,6 +330,7 @@ FastaReader::next(std::string& header, std::string& seq)
 {
 	int c;
 	qual_bases_ = masked_bases_ = 0;
+	drop_reason_ = nte_parse::RP_KEPT;
 	if (failed_ || !ok()) {
 		return false;
 	}
@@ -371,6 +372,8 @@ FastaReader::next(std::string& header, std::string& seq)
 		}
 	}
 	const size_t base = seq.size();
+	bool has_qual = false;
+	unsigned long long qual_sum = 0;
 	last_char_ = 0;
 	while ((c = getc_()) != -1 && c != '>' && c != '+' && c != '@') {
 		if (c == '\n') {
@@ -405,6 +408,12 @@ FastaReader::next(std::string& header, std::string& seq)
 			seq.resize(base);
 			return false;
 		}
+		if (filter_.min_mean_qual) { // (over the qualities as stored, whatever --min_qual masks below)
+			for (size_t i = 0; i < want; i++) {
+				qual_sum += nte_parse::rp_qual_weight((int)(unsigned char)line_[i] - nte_parse::RP_QUAL_OFFSET);
+			}
+		}
+		has_qual = true;
 		if (min_qual_) {
 			for (size_t i = 0; i < want; i++) {
 				const int q = (int)(unsigned char)line_[i] - nte_parse::RP_QUAL_OFFSET;
@@ -414,6 +423,9 @@ FastaReader::next(std::string& header, std::string& seq)
 			}
 			qual_bases_ = want;
 		}
+	}
+	if (nte_parse::rp_filter_on(filter_)) {
+		drop_reason_ = nte_parse::rp_record_reason(seq.size() - base, 0, filter_, has_qual, qual_sum);
 	}
 	return true;
 }

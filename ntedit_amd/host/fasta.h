@@ -13,6 +13,8 @@
 #include <thread>
 #include <zlib.h>
 
+#include "../csrc/nte_reads_grammar.h" // (ReadFilter)
+
 namespace nte_host {
 
 class Gunzip;
@@ -48,8 +50,15 @@ class FastaReader
 	// of the record the last next() returned: the bases that had a quality, and those of them below the minimum
 	unsigned long long qual_bases() const { return qual_bases_; }
 	unsigned long long masked_bases() const { return masked_bases_; }
+	// --min_read_len, --min_mean_qual (the reads passes alone, like set_min_qual; min_len is the shortest record kept,
+	// rq_bits is not the text parser's): next() still returns every record, and says of it whether the filter drops it
+	// and under which rule (nte_reads_grammar.h: rp_record_reason; multi-line FASTQ is concatenated first)
+	void set_read_filter(const nte_parse::ReadFilter& f) { filter_ = f; }
+	unsigned drop_reason() const { return drop_reason_; } // RP_KEPT, RP_DROP_LENGTH or RP_DROP_MEAN_QUAL
 
   private:
+	nte_parse::ReadFilter filter_ = nte_parse::ReadFilter();
+	unsigned drop_reason_ = 0;
 	unsigned min_qual_ = 0;
 	unsigned long long qual_bases_ = 0, masked_bases_ = 0;
 	bool fill_();

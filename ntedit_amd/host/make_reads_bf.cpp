@@ -3,6 +3,7 @@
 //   --reads FILE [FILE ...]  -k K  (-c CMIN | --solid)  [--hist FILE]  [--counts]  [--hashes 3]  [--fpr 0.01]
 //   [--bf BYTES | --num_elements N]  [--sketch_bytes S]  [-o reads_kK.bf]  [-t THREADS]
 //   [--reject_cutoff R  [--reject_bf BYTES | --reject_num_elements N]  [--reject_out reads_kK_reject.bf]]  [--min_qual Q]
+//   [--min_read_len L]  [--min_mean_qual Q]  [--min_rq R]
 //
 // The reference leaves this step to ntHits / ntStat on the CPU (ntedit-make: `nthits -c<cutoff> --outbloom`;
 // ntedit_run_pipeline.smk: `ntstat filter -cmin C`).  This tool is neither: it counts in a plain count-min sketch of
@@ -46,7 +47,8 @@ usage(const char* why)
 	std::cerr
 	    << "Usage: make_reads_bf [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] [--counts] [--hashes VAR] "
 	       "[--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] [-t VAR] "
-	       "[--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR] [--min_qual VAR]\n\n"
+	       "[--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR] [--min_qual VAR] "
+	       "[--min_read_len VAR] [--min_mean_qual VAR] [--min_rq VAR]\n\n"
 	       "Builds the k-mer filter of a read set on the GPU: pass 1 counts every k-mer in a count-min sketch of 8-bit\n"
 	       "counters, pass 2 keeps the k-mers whose estimate (the minimum of their counters) is at least -c.  Neither\n"
 	       "ntHits nor ntStat: the counts (plain count-min, no conservative update) and the sizing are this tool's own.\n"
@@ -89,7 +91,14 @@ usage(const char* why)
 	       "  --min_qual      Minimum base quality, 1 to 93 (Phred+33; Phred+64 is not built): a base whose quality is below\n"
 	       "                  it counts as N, so no k-mer that spans it is counted or kept.  FASTQ: a quality character below\n"
 	       "                  33 + Q; BAM: a quality byte below Q.  Reads are still kept by their length; records without\n"
-	       "                  qualities (FASTA, BAM records whose qualities are absent) pass as they are [default: off]\n";
+	       "                  qualities (FASTA, BAM records whose qualities are absent) pass as they are [default: off]\n"
+	       "  --min_read_len  Minimum read length, 1 to 2147483647: the shortest read kept is the larger of it and k\n"
+	       "                  [default: off]\n"
+	       "  --min_mean_qual Minimum mean read quality, 1 to 60: the Phred value of the read's mean error probability (as\n"
+	       "                  NanoFilt, chopper and fastplong take it, not the mean of the Phred values), over the qualities\n"
+	       "                  as stored.  Reads without qualities pass [default: off]\n"
+	       "  --min_rq        Minimum read accuracy, above 0 and at most 1: a BAM read whose rq tag (type f) is below it is\n"
+	       "                  dropped; reads without the tag pass, so every FASTA and FASTQ read does [default: off]\n";
 }
 
 static bool
@@ -115,6 +124,8 @@ main(int argc, char** argv)
 	std::vector<const char*> paths;
 	ntedit_hip_reads_options ro = {};
 	ntedit_hip_reads_rules rr;
+	ntedit_hip_reads_filter_options fo = {}; // --min_read_len, --min_mean_qual, --min_rq
+	ntedit_hip_reads_filter_rules fr = {};
 	bool counts = false;
 	std::string out_file, sketch_out, hist_out, reject_out;
 	for (int i = 1; i < argc; i++) {
@@ -129,7 +140,8 @@ main(int argc, char** argv)
 		// an option of the shared rules: what they refuse at the option itself is refused here
 		auto given = [&](const char* name, const char*& text) {
 			text = value(name);
-			if (ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_TOOL, 0, &rr) != 0) {
+			if (ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_TOOL, 0, &rr) != 0 ||
+			    ntedit_hip_reads_filter_options_check(&fo, NTEDIT_READS_DIALECT_TOOL, 0, &fr) != 0) {
 				usage(ntedit_hip_reads_last_error(nullptr));
 				exit(1);
 			}
@@ -175,6 +187,12 @@ main(int argc, char** argv)
 			given("--reject_num_elements", ro.reject_num_elements);
 		} else if (a == "--min_qual") {
 			given("--min_qual", ro.min_qual);
+		} else if (a == "--min_read_len") {
+			given("--min_read_len", fo.min_read_len);
+		} else if (a == "--min_mean_qual") {
+			given("--min_mean_qual", fo.min_mean_qual);
+		} else if (a == "--min_rq") {
+			given("--min_rq", fo.min_rq);
 		} else if (a == "--reject_out") {
 			reject_out = value("--reject_out");
 			ro.reject_out = 1;
@@ -197,6 +215,10 @@ main(int argc, char** argv)
 	ro.n_files = (uint32_t)paths.size();
 	const int refused = ntedit_hip_reads_options_check(&ro, NTEDIT_READS_DIALECT_TOOL, 1, &rr);
 	if (refused && refused != NTEDIT_READS_EMPTY) {
+		usage(ntedit_hip_reads_last_error(nullptr));
+		return 1;
+	}
+	if (ntedit_hip_reads_filter_options_check(&fo, NTEDIT_READS_DIALECT_TOOL, 1, &fr) != 0) { // (behind --min_qual's rules)
 		usage(ntedit_hip_reads_last_error(nullptr));
 		return 1;
 	}
@@ -249,6 +271,15 @@ main(int argc, char** argv)
 	if (rr.min_qual) {
 		std::cout << "\t\t--min_qual " << rr.min_qual << std::endl;
 	}
+	if (fr.min_read_len) {
+		std::cout << "\t\t--min_read_len " << fr.min_read_len << std::endl;
+	}
+	if (fr.min_mean_qual) {
+		std::cout << "\t\t--min_mean_qual " << fr.min_mean_qual << std::endl;
+	}
+	if (fr.min_rq > 0.0f) {
+		std::cout << "\t\t--min_rq " << fo.min_rq << std::endl;
+	}
 	if (refused) { // (the output filter would be empty)
 		usage(ntedit_hip_reads_last_error(nullptr));
 		return 1;
@@ -291,6 +322,7 @@ main(int argc, char** argv)
 	ba.reject_bf_bytes = rr.reject_bf_bytes;
 	ba.reject_num_elements = rr.reject_num_elements;
 	ba.min_qual = rr.min_qual;
+	ntedit_hip_reads_set_read_filter(ctx, fr.min_read_len, fr.min_mean_qual, fr.min_rq);
 	ntedit_hip_reads_build_result br;
 	if (ntedit_hip_reads_build(ctx, &ba, &br) != 0) {
 		die(ctx, ntedit_hip_reads_last_error(ctx));

@@ -97,6 +97,18 @@ build_pass(ntedit_hip_ctx* ctx, const ntedit_hip_reads_build_args* a, int pass, 
 		lg.rank_info("--min_qual " + std::to_string(a->min_qual) + ": " + std::to_string(masked_bases) + " of " + std::to_string(qual_bases) +
 		             " bases with a quality masked");
 	}
+	ntedit_hip_reads_read_filter_stats fs;
+	uint32_t f_len = 0, f_mean = 0;
+	float f_rq = 0.0f;
+	if (read_files && ntedit_hip_reads_get_read_filter(ctx, &f_len, &f_mean, &f_rq) == 0 && (f_len || f_mean || f_rq > 0.0f) &&
+	    ntedit_hip_reads_read_filter_info(ctx, &fs) == 0) {
+		// the pass's one line about the read filter (the tests read it)
+		lg.rank_info("read filter: " + std::to_string(fs.dropped_length + fs.dropped_rq + fs.dropped_mean_qual) + " of " +
+		             std::to_string(fs.records) + " records dropped (length " + std::to_string(fs.dropped_length) + ", rq " +
+		             std::to_string(fs.dropped_rq) + ", mean quality " + std::to_string(fs.dropped_mean_qual) + ")" +
+		             (f_rq > 0.0f && fs.rq_tagged == 0 ? "; --min_rq: no record had an rq tag" : "") +
+		             (fs.aux_malformed ? "; " + std::to_string(fs.aux_malformed) + " records with malformed aux fields" : ""));
+	}
 	ntedit_hip_reads_parse_stats ps;
 	if (a->device_parse && read_files && ntedit_hip_reads_parse_info(ctx, &ps) == 0) {
 		// the pass's one line about --gpu_parse (the tests read it)

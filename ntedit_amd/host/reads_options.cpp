@@ -6,6 +6,7 @@
 
 #include <cerrno>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 
 namespace nte_reads {
@@ -177,5 +178,55 @@ ntedit_hip_reads_options_check(const ntedit_hip_reads_options* o, int dialect, i
 		return refuse(NTEDIT_READS_EMPTY, "The output filter would be empty (--bf 0 or --num_elements too small).");
 	}
 	r->sketch_counters = r->sketch_bytes ? r->sketch_bytes : ntedit_hip_reads_default_sketch(o->files, o->n_files, r->bf_bytes);
+	return 0;
+}
+
+// --min_read_len, --min_rq, --min_mean_qual: which reads go into the build (ntedit_hip_reads_set_read_filter)
+extern "C" int
+ntedit_hip_reads_filter_options_check(const ntedit_hip_reads_filter_options* o, int dialect, int final, ntedit_hip_reads_filter_rules* r)
+{
+	if (!o || !r || (dialect != NTEDIT_READS_DIALECT_TOOL && dialect != NTEDIT_READS_DIALECT_POLISHER)) {
+		return nte_reads::set_error(nullptr, NTEDIT_E_ARG, "reads_filter_options_check: bad argument");
+	}
+	const bool tool = dialect == NTEDIT_READS_DIALECT_TOOL;
+	const std::string dot = tool ? "." : "";
+	auto refuse = [](int code, const std::string& why) { return nte_reads::set_error(nullptr, code, why); };
+	auto not_a_number = [&](const std::string& name, const char* text) {
+		refuse(0, tool ? name + ": not a number: '" + text + "'" : "invalid option: `" + name + " " + text + "'");
+		return NTEDIT_READS_NOT_A_NUMBER;
+	};
+	*r = ntedit_hip_reads_filter_rules();
+	uint64_t min_read_len = 0, min_mean_qual = 0;
+	float min_rq = 0.0f;
+	if (o->min_read_len && !parse_u64(o->min_read_len, &min_read_len)) {
+		return not_a_number("--min_read_len", o->min_read_len);
+	}
+	if (o->min_mean_qual && !parse_u64(o->min_mean_qual, &min_mean_qual)) {
+		return not_a_number("--min_mean_qual", o->min_mean_qual);
+	}
+	if (o->min_rq) { // a decimal, read with strtof: digits, at most a point and an exponent (strtof alone would take leading blanks, a sign, hex floats, "inf" and "nan")
+		char* end = nullptr;
+		min_rq = strtof(o->min_rq, &end);
+		const char c0 = o->min_rq[0];
+		const bool decimal = ((c0 >= '0' && c0 <= '9') || c0 == '.') && strspn(o->min_rq, "0123456789.eE+-") == strlen(o->min_rq);
+		if (!decimal || *end || end == o->min_rq) {
+			return not_a_number("--min_rq", o->min_rq);
+		}
+	}
+	if (!final) {
+		return 0;
+	}
+	if (o->min_read_len && (min_read_len < 1 || min_read_len > 2147483647ull)) {
+		return refuse(NTEDIT_READS_REFUSED, "--min_read_len " + std::string(o->min_read_len) + ": the minimum read length must be between 1 and 2147483647" + dot);
+	}
+	if (o->min_rq && !(min_rq > 0.0f && min_rq <= 1.0f)) { // (written so that a NaN is refused)
+		return refuse(NTEDIT_READS_REFUSED, "--min_rq " + std::string(o->min_rq) + ": the minimum read accuracy must be above 0 and at most 1" + dot);
+	}
+	if (o->min_mean_qual && (min_mean_qual < 1 || min_mean_qual > 60)) {
+		return refuse(NTEDIT_READS_REFUSED, "--min_mean_qual " + std::string(o->min_mean_qual) + ": the minimum mean read quality must be between 1 and 60" + dot);
+	}
+	r->min_read_len = (uint32_t)min_read_len;
+	r->min_mean_qual = (uint32_t)min_mean_qual;
+	r->min_rq = min_rq;
 	return 0;
 }

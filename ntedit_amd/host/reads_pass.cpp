@@ -54,6 +54,9 @@ int bam_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, int at_he
 // --min_qual (nte_reads_parse.hip): the context's setting, which the device parsers read themselves, and the pass's counts
 uint32_t min_qual(const ntedit_hip_ctx* c);
 void min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases);
+// --min_read_len, --min_mean_qual, --min_rq (nte_reads_parse.hip): the context's setting, alike, and the pass's counts
+nte_parse::ReadFilter read_filter(const ntedit_hip_ctx* c);
+void read_filter_count(const ntedit_hip_ctx* c, int reset, const nte_parse::ReadFilterCounts* add);
 }
 
 namespace {
@@ -153,8 +156,18 @@ find_record_start(const char* path, uint64_t begin, uint64_t* out, std::string* 
 // record masked by min_qual (0: off, and the two counts are 0); *start / *next as ntedit_hip_reads_pass reports them
 using SeqFn = std::function<bool(const std::string&, uint64_t, uint64_t)>;
 
+// what the reads passes ask of the host parser beyond kseq's rules: --min_qual, and the read filter (filter.min_len: the
+// shortest record kept, the caller's k already in it).  A record the filter drops never reaches seq_fn; *counts (may be
+// NULL) += what the records came to.  Only the reads passes set these: a draft or a genome is never filtered.
+struct HostRules
+{
+	uint32_t min_qual = 0;
+	nte_parse::ReadFilter filter = nte_parse::ReadFilter();
+	nte_parse::ReadFilterCounts* counts = nullptr;
+};
+
 bool
-read_range(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, const SeqFn& seq_fn, uint64_t* start, uint64_t* next,
+read_range(const char* path, uint64_t begin, uint64_t end, const HostRules& rules, const SeqFn& seq_fn, uint64_t* start, uint64_t* next,
            std::string* why, bool exact = false, uint64_t skip = 0)
 {
 	uint64_t s = exact ? begin : 0; // exact: begin is a record start (where --gpu_parse hands a range back)
@@ -188,12 +201,25 @@ read_range(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, co
 		return false;
 	}
 	reader.skip(skip);
-	reader.set_min_qual(min_qual);
+	reader.set_min_qual(rules.min_qual);
+	reader.set_read_filter(rules.filter);
+	const bool filtered = nte_parse::rp_filter_on(rules.filter);
 	std::string hdr, seq;
 	for (;;) {
 		seq.clear();
 		if (!reader.next(hdr, seq)) {
 			break;
+		}
+		if (filtered) {
+			const unsigned why = reader.drop_reason();
+			if (rules.counts) {
+				rules.counts->records++;
+				rules.counts->by_length += why == nte_parse::RP_DROP_LENGTH;
+				rules.counts->by_mean_qual += why == nte_parse::RP_DROP_MEAN_QUAL;
+			}
+			if (why != nte_parse::RP_KEPT) {
+				continue;
+			}
 		}
 		if (!seq_fn(seq, reader.qual_bases(), reader.masked_bases())) {
 			return false;
@@ -222,7 +248,7 @@ struct BatchProducer
 	unsigned k;
 	size_t batch_bytes;
 	uint64_t *starts, *nexts;
-	unsigned min_qual;
+	HostRules rules;       // (rules.counts: read once the feed has ended, like qual_counts)
 	uint64_t* qual_counts; // [2], of the records kept: with a quality, masked (read once the feed has ended)
 
 	void operator()(Feed<Batch>& feed) const
@@ -244,7 +270,7 @@ struct BatchProducer
 				}
 				return !stopped;
 			};
-			const bool ok = read_range(r.path, r.begin, r.end, min_qual, add, &start, &next, &why, r.exact, r.skip);
+			const bool ok = read_range(r.path, r.begin, r.end, rules, add, &start, &next, &why, r.exact, r.skip);
 			if (stopped) {
 				return; // (batch_add failed the feed, or it is being torn down)
 			}
@@ -281,6 +307,7 @@ struct Pass
 	uint32_t keep;       // the shortest record the parsers keep: the sketch's k, or below it what ntedit_hip_reads_set_min_read asks for
 	uint64_t batch_bytes;
 	uint32_t min_qual;   // ntedit_hip_reads_set_min_qual (the host parser's part: the device parsers read the context's setting)
+	nte_parse::ReadFilter filter; // ntedit_hip_reads_set_read_filter, alike
 	uint64_t bases = 0;
 	double gpu_ms = 0.0;
 	ntedit_hip_reads_parse_stats* info;
@@ -300,7 +327,13 @@ struct Pass
 	int host_ranges(const std::vector<Range>& rs, uint64_t* rs_starts, uint64_t* rs_nexts)
 	{
 		uint64_t counts[2] = { 0, 0 };
-		Feed<Batch> feed(BatchProducer{ rs, keep, (size_t)batch_bytes, rs_starts, rs_nexts, min_qual, counts });
+		nte_parse::ReadFilterCounts fcounts = nte_parse::ReadFilterCounts();
+		HostRules rules;
+		rules.min_qual = min_qual;
+		rules.filter = filter;
+		rules.filter.min_len = nte_parse::rp_filter_on(filter) ? nte_parse::rp_min_len(filter, keep) : 0;
+		rules.counts = &fcounts;
+		Feed<Batch> feed(BatchProducer{ rs, keep, (size_t)batch_bytes, rs_starts, rs_nexts, rules, counts });
 		for (;;) {
 			Batch* b = feed.take();
 			if (!b) {
@@ -317,6 +350,7 @@ struct Pass
 			feed.give_back(b);
 			if (last) {
 				nte_reads::min_qual_count(ctx, 0, counts[0], counts[1]); // (the producer is through: its last batch came after them)
+				nte_reads::read_filter_count(ctx, 0, &fcounts);
 				return 0;
 			}
 		}
@@ -561,8 +595,9 @@ ntedit_hip_reads_pass(ntedit_hip_ctx* ctx, int pass, const char* const* files, c
 	}
 	const auto t0 = std::chrono::steady_clock::now();
 	Pass p{ ctx, pass, cmin, pass == NTEDIT_READS_PASS_SOLID ? nte_reads::reject_cutoff(ctx) : 0, nte_reads::min_read(ctx, k), batch_bytes,
-		    nte_reads::min_qual(ctx) };
+		    nte_reads::min_qual(ctx), nte_reads::read_filter(ctx) };
 	nte_reads::min_qual_count(ctx, 1, 0, 0);
+	nte_reads::read_filter_count(ctx, 1, nullptr);
 	if (!nte_reads::parse_is_on(ctx)) {
 		for (const Range& r : ranges) { // (the host parser would read whatever '@' and '>' bytes the binary stream holds)
 			if (ntedit_hip_reads_is_bam(r.path)) {
@@ -618,12 +653,28 @@ int
 ntedit_hip_reads_range_text_q(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, char* out, uint64_t cap, uint64_t* len,
                               uint64_t* reads, uint64_t* start, uint64_t* next)
 {
-	if (!path || !len || !reads || !start || !next || begin > end || (cap && !out) || min_qual > 93) {
+	return ntedit_hip_reads_range_text_f(path, begin, end, min_qual, 0, 0, out, cap, len, reads, start, next, nullptr);
+}
+
+int
+ntedit_hip_reads_range_text_f(const char* path, uint64_t begin, uint64_t end, uint32_t min_qual, uint32_t min_len, uint32_t min_mean_qual,
+                              char* out, uint64_t cap, uint64_t* len, uint64_t* reads, uint64_t* start, uint64_t* next,
+                              ntedit_hip_reads_read_filter_stats* st)
+{
+	if (!path || !len || !reads || !start || !next || begin > end || (cap && !out) || min_qual > 93 ||
+	    min_len > nte_parse::RP_MAX_MIN_READ_LEN || min_mean_qual > nte_parse::RP_MAX_MEAN_QUAL) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_range_text: bad argument");
 	}
 	uint64_t used = 0, count = 0;
 	std::string why;
-	const bool ok = read_range(path, begin, end, min_qual, [&](const std::string& seq, uint64_t, uint64_t) {
+	nte_parse::ReadFilterCounts fcounts = nte_parse::ReadFilterCounts();
+	HostRules rules;
+	rules.min_qual = min_qual;
+	rules.filter.min_len = min_len;
+	rules.filter.min_mean_qual = min_mean_qual;
+	rules.counts = &fcounts;
+	static_assert(sizeof(ntedit_hip_reads_read_filter_stats) == sizeof(nte_parse::ReadFilterCounts), "field for field");
+	const bool ok = read_range(path, begin, end, rules, [&](const std::string& seq, uint64_t, uint64_t) {
 		if (used + seq.size() + 1 <= cap) {
 			memcpy(out + used, seq.data(), seq.size());
 			out[used + seq.size()] = '\n';
@@ -637,6 +688,9 @@ ntedit_hip_reads_range_text_q(const char* path, uint64_t begin, uint64_t end, ui
 	}
 	*len = used;
 	*reads = count;
+	if (st) {
+		memcpy(st, &fcounts, sizeof fcounts);
+	}
 	return used > cap ? NTEDIT_E_OVERFLOW : 0;
 }
 

@@ -37,7 +37,7 @@ RESIDENT_CAP_DEFAULT = _lib.READS_RESIDENT_CAP_DEFAULT  # the resident store's c
 USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR (-c VAR | --solid) [--hist VAR] "
          "[--counts] [--hashes VAR] [--fpr VAR] [--bf VAR] [--num_elements VAR] [--sketch_bytes VAR] [--gpu_parse] [-o VAR] "
          "[-t VAR] [--reject_cutoff VAR] [--reject_bf VAR] [--reject_num_elements VAR] [--reject_out VAR] [--min_qual VAR] "
-         "[--no-split] "
+         "[--min_read_len VAR] [--min_mean_qual VAR] [--min_rq VAR] [--no-split] "
          "[--backend VAR]\n\n"
          "ntedit-make-reads-bf on N processes (python -m torch.distributed.run --nproc-per-node N -m "
          "ntedit_amd.make_reads ...): the same flags, the same output bytes.\n"
@@ -50,6 +50,10 @@ USAGE = ("Usage: python -m ntedit_amd.make_reads [--help] --reads VAR... -k VAR 
          "                  unaligned or aligned, need it; a BAM is read whole by one process, as gzip files are\n"
          "  --min_qual      minimum base quality, 1 to 93 (Phred+33; Phred+64 is not built): a base below it counts as N in\n"
          "                  every rank alike, so the output bytes are the same for every world size\n"
+         "  --min_read_len  minimum read length, 1 to 2147483647 (the shortest read kept is the larger of it and k)\n"
+         "  --min_mean_qual minimum mean read quality, 1 to 60: the Phred value of the read's mean error probability\n"
+         "  --min_rq        minimum read accuracy, above 0 and at most 1: a BAM read whose rq tag is below it is dropped;\n"
+         "                  reads without the tag pass.  The three drop the same reads on every rank\n"
          "  --backend       torch.distributed backend (default nccl = RCCL; gloo: N ranks may share a GPU)\n"
          "ntedit-make-reads-bf --help describes the other flags.\n")
 
@@ -68,14 +72,20 @@ def check_options(dialect, given, final, reads=(), solid=False, hist="", gpu_par
     Refused with the library's message; the tool's "would be empty" is kept in the dict for sizes() to refuse."""
     lib = _lib.load()
     files = (ctypes.c_char_p * max(1, len(reads)))(*[os.fsencode(f) for f in reads])
+    own = {name: text for name, text in given.items() if name not in _lib.READS_FILTER_OPTION_TEXTS}
     o = _lib.ReadsOptions(solid=solid, hist=bool(hist), files=files, n_files=len(reads), gpu_parse=bool(gpu_parse),
                           counts=bool(counts), reject_out=bool(reject_out),
-                          **{name: os.fsencode(text) for name, text in given.items()})
+                          **{name: os.fsencode(text) for name, text in own.items()})
     r = _lib.ReadsRules()
     rc = lib.ntedit_hip_reads_options_check(o, dialect, int(final), r)
     why = os.fsdecode(lib.ntedit_hip_reads_last_error(None)) if rc else None
     if rc not in (0, _lib.READS_EMPTY):
         raise Refused(why)
+    # the read filter's options, behind them (a struct and a call of their own)
+    fo = _lib.ReadsFilterOptions(**{name: os.fsencode(given[name]) for name in _lib.READS_FILTER_OPTION_TEXTS if name in given})
+    fr = _lib.ReadsFilterRules()
+    if lib.ntedit_hip_reads_filter_options_check(fo, dialect, int(final), fr) != 0:
+        raise Refused(os.fsdecode(lib.ntedit_hip_reads_last_error(None)))
     return dict(reads=list(reads), k=r.k, cmin=r.cmin if "cutoff" in given else None, solid=solid, hist=hist,
                 hashes=r.hash_num, fpr=r.fpr, bf=r.bf_bytes if "bf" in given else None,
                 num_elements=r.num_elements if "num_elements" in given else None, sketch_bytes=r.sketch_bytes,
@@ -83,7 +93,12 @@ def check_options(dialect, given, final, reads=(), solid=False, hist="", gpu_par
                 size_from_hist=bool(r.size_from_hist), bf_bytes=r.bf_bytes, sketch=r.sketch_counters, empty=why,
                 gpu_parse=bool(r.gpu_parse), reject_cmin=r.reject_cmin, reject_bf_bytes=r.reject_bf_bytes,
                 reject_num_elements=r.reject_num_elements, reject_size_from_hist=bool(r.reject_size_from_hist),
-                min_qual=r.min_qual)
+                min_qual=r.min_qual, min_read_len=fr.min_read_len, min_mean_qual=fr.min_mean_qual, min_rq=fr.min_rq)
+
+
+def read_filter_on(a):
+    """--min_read_len, --min_mean_qual or --min_rq was given"""
+    return bool(a.get("min_read_len") or a.get("min_mean_qual") or a.get("min_rq"))
 
 
 def parse(argv):
@@ -91,7 +106,8 @@ def parse(argv):
     texts = {"-k": "k", "-c": "cutoff", "--hashes": "hashes", "--fpr": "fpr", "--bf": "bf",
              "--num_elements": "num_elements", "--sketch_bytes": "sketch_bytes", "-t": "threads",
              "--batch_bytes": "batch_bytes", "--reject_cutoff": "reject_cutoff", "--reject_bf": "reject_bf",
-             "--reject_num_elements": "reject_num_elements", "--min_qual": "min_qual"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
+             "--reject_num_elements": "reject_num_elements", "--min_qual": "min_qual",
+             "--min_read_len": "min_read_len", "--min_mean_qual": "min_mean_qual", "--min_rq": "min_rq"}  # (--batch_bytes is not in the usage text: tests force small batches with it)
     own = dict(counts=False, out="", reject_out="", no_split=False, backend=None, help=False)
     given, reads, solid, hist, gpu_parse = {}, [], False, "", False
     i = 0
@@ -360,6 +376,9 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         log=_log_line, device_parse=bool(a.get("gpu_parse")), reject_cmin=reject,
         reject_bf_bytes=a.get("reject_bf_bytes") or 0, reject_num_elements=a.get("reject_num_elements") or 0,
         min_qual=a.get("min_qual") or 0)
+    # the read filter is the context's setting (no field of the build's arguments): every pass of this build follows it
+    if lib.ntedit_hip_reads_set_read_filter(b.h, a.get("min_read_len") or 0, a.get("min_mean_qual") or 0, a.get("min_rq") or 0.0):
+        raise RuntimeError("reads_set_read_filter: " + os.fsdecode(lib.ntedit_hip_reads_last_error(b.h)))
     res = _lib.ReadsBuildResult()
     parsed = {}
 
@@ -369,6 +388,12 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
         if a.get("min_qual") and lib.ntedit_hip_reads_min_qual_info(b.h, with_qual, masked) == 0:
             parsed.setdefault(key, {})["min_qual"] = dict(q=a["min_qual"], qual_bases=with_qual.value,
                                                           masked_bases=masked.value)
+        # the read filter: what the records of the pass that just ran came to (ntedit_hip_reads_read_filter_info)
+        fs = _lib.ReadsReadFilterStats()
+        if read_filter_on(a) and lib.ntedit_hip_reads_read_filter_info(b.h, fs) == 0:
+            parsed.setdefault(key, {})["read_filter"] = dict(
+                min_read_len=a.get("min_read_len") or 0, min_mean_qual=a.get("min_mean_qual") or 0,
+                min_rq=a.get("min_rq") or 0.0, **fs.as_dict())
         # --gpu_parse: what the pass that just ran parsed where (ntedit_hip_reads_parse_info: the last pass)
         st = _lib.ReadsParseStats()
         if a.get("gpu_parse") and lib.ntedit_hip_reads_parse_info(b.h, st) == 0:
@@ -446,7 +471,7 @@ def build_rank(pol, a, rank, world, group, slot=0, use_store=False, store_cap=RE
                                    fallback=use_store and not on),
                cmin=res.cmin, filter_bytes=nbytes, passes=passes, exchanges=b.exchanges, exchange_bytes=b.xbytes,
                exchange_ms=round(b.xsec * 1e3, 3))
-    if a.get("gpu_parse") or a.get("min_qual"):
+    if a.get("gpu_parse") or a.get("min_qual") or read_filter_on(a):
         rep["parse"] = parsed
     if reject:
         rep["reject"] = dict(cutoff=reject, filter_bytes=nbytes2, merge_ms=b.exchanges[-1]["ms"] if group is not None else 0.0)

@@ -227,7 +227,8 @@ READS_OPTIONS = [("--cutoff", "cutoff"), ("--solid", "solid"), ("--counts", "cou
                  ("--batch_bytes", "batch_bytes"), ("--resident_cap", "resident_cap"), ("--no-split", "no_split"),
                  ("--gpu_parse", "gpu_parse"), ("--reject_cutoff", "reject_cutoff"), ("--reject_bf", "reject_bf"),
                  ("--reject_num_elements", "reject_num_elements"), ("--save_reject_bf", "save_reject_bf"),
-                 ("--min_qual", "min_qual")]
+                 ("--min_qual", "min_qual"), ("--min_read_len", "min_read_len"), ("--min_mean_qual", "min_mean_qual"),
+                 ("--min_rq", "min_rq")]
 
 
 def parse(argv=None):
@@ -297,6 +298,14 @@ def parse(argv=None):
                    help="minimum base quality, 1 to 93 (Phred+33; Phred+64 is not built): a base whose quality is below Q "
                         "enters the filter build as N, on every rank alike (FASTQ: a quality character below 33 + Q; BAM: a "
                         "quality byte below Q; records without qualities pass as they are)")
+    g.add_argument("--min_read_len", metavar="L",
+                   help="minimum read length, 1 to 2147483647: the shortest read kept is the larger of L and k")
+    g.add_argument("--min_mean_qual", metavar="Q",
+                   help="minimum mean read quality, 1 to 60: the Phred value of the read's mean error probability (not the mean "
+                        "of the Phred values), over the qualities as stored; reads without qualities pass")
+    g.add_argument("--min_rq", metavar="R",
+                   help="minimum read accuracy, above 0 and at most 1: a BAM read whose rq tag (type f) is below R is dropped; "
+                        "reads without the tag pass, so every FASTA and FASTQ read does")
     g.add_argument("--batch_bytes", help=argparse.SUPPRESS)  # (tests: many small read batches)
     g.add_argument("--resident_cap", help=argparse.SUPPRESS)  # (tests: the resident store's cap; 0: off)
     args = ap.parse_args(argv)
@@ -342,7 +351,8 @@ def reads_args(args):
              (("k", "k_ignored"), ("cutoff", "cutoff"), ("hashes", "hashes"), ("fpr", "fpr"), ("bf", "bf_bytes"),
               ("num_elements", "num_elements"), ("sketch_bytes", "sketch_bytes"), ("batch_bytes", "batch_bytes"),
               ("store_cap", "resident_cap"), ("reject_cutoff", "reject_cutoff"), ("reject_bf", "reject_bf"),
-              ("reject_num_elements", "reject_num_elements"), ("min_qual", "min_qual")) if getattr(args, dest) is not None}
+              ("reject_num_elements", "reject_num_elements"), ("min_qual", "min_qual"), ("min_read_len", "min_read_len"),
+              ("min_mean_qual", "min_mean_qual"), ("min_rq", "min_rq")) if getattr(args, dest) is not None}
     a = make_reads.check_options(_lib.READS_DIALECT_POLISHER, given, True, args.reads, args.solid, args.hist or "",
                                  args.gpu_parse, args.counts, args.save_reject_bf is not None)
     a.update(counts=args.counts, no_split=args.no_split)
