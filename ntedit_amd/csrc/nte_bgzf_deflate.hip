@@ -27,8 +27,7 @@ __device__ unsigned long long g_dz_phase[8];
 	} while (0)
 #endif
 #include "nte_bgzf_deflate.h"
-
-#include "../../include/ntedit_hip.h"
+#include "nte_reads_internal.h"
 
 #include <cstring>
 #include <mutex>
@@ -36,10 +35,6 @@ __device__ unsigned long long g_dz_phase[8];
 
 using namespace nte;
 using namespace nte_bgzf;
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-}
 
 namespace {
 

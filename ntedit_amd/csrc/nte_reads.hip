@@ -29,8 +29,8 @@
 // This unit does not see the context's internals (nte_api.hip): the sketch lives in a small per-context state of its
 // own, the output filter is reached through the public calls (ntedit_hip_filter_device_ptr / _info / _set_filter).
 #include "nte_tile.h"
+#include "nte_reads_internal.h"
 
-#include "../../include/ntedit_hip.h"
 #include "../host/bfio.h"
 #include "../host/params.h"
 
@@ -772,22 +772,17 @@ solid2_targets(const ntedit_hip_ctx* c, const ReadsState* s, u32 cmin, u32 rmin,
 } // namespace
 
 namespace nte_reads {
-void parse_release(const ntedit_hip_ctx* c);
-// the failures of the host side (reads_pass.cpp) go to the same store as this unit's
 int
 set_error(const ntedit_hip_ctx* c, int code, const std::string& why)
 {
 	return rfail(c, code, "%s", why.c_str());
 }
-// the context's reject cutoff (ntedit_hip_reads_set_reject_cutoff); 0: none, and none without a sketch
 uint32_t
 reject_cutoff(const ntedit_hip_ctx* c)
 {
 	const ReadsState* s = find_state(c);
 	return s ? s->reject_cmin : 0;
 }
-// the shortest record the parsers keep for a sketch at k (ntedit_hip_reads_set_min_read): never above k, so that no
-// read with a k-mer is dropped
 uint32_t
 min_read(const ntedit_hip_ctx* c, uint32_t k)
 {

@@ -31,28 +31,19 @@
 #include "nte_bam_grammar.h"
 #include "nte_bgzf_inflate.h"
 
-#include "../../include/ntedit_hip.h"
+#include "nte_reads_internal.h"
+#include "nte_reads_unit.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 using namespace nte;
 using namespace nte_bam;
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-int parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream);
-int parse_text_buffer(const ntedit_hip_ctx* c, uint64_t n, char** text, uint64_t* cap);
-uint32_t min_qual(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_min_qual (nte_reads_parse.hip), and the pass's counts
-void min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases);
-nte_parse::ReadFilter read_filter(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_read_filter, and the pass's counts
-void read_filter_count(const ntedit_hip_ctx* c, int reset, const nte_parse::ReadFilterCounts* add);
-}
+using namespace nte_unit;
 
 namespace {
 
@@ -502,69 +493,38 @@ k_bam_decode(const u8* __restrict__ raw, const u32* __restrict__ krec_seq, const
 }
 
 // ------------------------------------------------------------------ host side
-struct BamState
+// what the calls set and the last pass counted: survives ntedit_hip_sketch_free
+struct BamKeep
 {
-	const ntedit_hip_ctx* owner = nullptr;
 	ntedit_hip_reads_bam_stats info = {};
-	u64 segment = 0; // ntedit_hip_reads_bam_set_segment (0: the default)
-	u32 last_width = 0;  // the width the last k_bam_facts ran at (ntedit_hip_reads_bam_group_width)
+	u64 segment = 0;     // ntedit_hip_reads_bam_set_segment (0: the default)
 	u32 group_width = 0; // ntedit_hip_reads_bam_set_group_width (0: by the reads' mean length)
-	u32 mean_l_seq = 0;  // of the records the last chunk kept (0: no chunk yet): what the next chunk's width goes by
+};
+
+// device scratch, grow-only, released by ntedit_hip_sketch_free
+struct BamScratch
+{
+	u32 last_width = 0; // the width the last k_bam_facts ran at (ntedit_hip_reads_bam_group_width)
+	u32 mean_l_seq = 0; // of the records the last chunk kept (0: no chunk yet): what the next chunk's width goes by
 	int device = -1;
 	hipStream_t stream = nullptr; // the parse unit's
 	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-	// device scratch, grow-only, released by ntedit_hip_sketch_free
-	u8* d_seg = nullptr; // the per-segment arrays and the table
-	u64 seg_cap = 0;
-	u8* d_rec = nullptr; // the kept records' two arrays
-	u64 rec_cap = 0;
-	u8* d_in = nullptr; // a chunk given as host bytes
-	u64 in_cap = 0;
+	DevBuf seg; // the per-segment arrays and the table
+	DevBuf rec; // the kept records' two arrays
+	DevBuf in;  // a chunk given as host bytes
 	BamInfo* d_info = nullptr;
 	BamInfo* h_info = nullptr; // page-locked
 	u64* h_total = nullptr;    // page-locked
 };
 
-std::mutex g_bam_mu;
-std::vector<BamState*> g_bam;
-
-BamState*
-bam_state(const ntedit_hip_ctx* c, bool create)
-{
-	std::lock_guard<std::mutex> lk(g_bam_mu);
-	for (BamState* s : g_bam) {
-		if (s->owner == c) {
-			return s;
-		}
-	}
-	if (!create) {
-		return nullptr;
-	}
-	BamState* s = new BamState();
-	s->owner = c;
-	g_bam.push_back(s);
-	return s;
-}
+typedef State<BamKeep, BamScratch> BamState;
+Registry<BamState> g_bam;
 
 int
-pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
-{
-	return nte_reads::set_error(c, code, why);
-}
-
-#define BAM_TRY(ctx, expr)                                                                        \
-	do {                                                                                          \
-		hipError_t e_ = (expr);                                                                   \
-		if (e_ != hipSuccess) {                                                                   \
-			return pfail((ctx), NTEDIT_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-		}                                                                                         \
-	} while (0)
-
-int
-ensure_device(const ntedit_hip_ctx* c, BamState* s)
+ensure_device(const ntedit_hip_ctx* c, BamScratch* s)
 {
 	if (s->device >= 0) {
-		BAM_TRY(c, hipSetDevice(s->device));
+		NTE_TRY(c, hipSetDevice(s->device));
 		return 0;
 	}
 	void *stream = nullptr, *copy_stream = nullptr;
@@ -573,38 +533,35 @@ ensure_device(const ntedit_hip_ctx* c, BamState* s)
 		return rc;
 	}
 	int device = 0;
-	BAM_TRY(c, hipGetDevice(&device));
+	NTE_TRY(c, hipGetDevice(&device));
 	s->stream = (hipStream_t)stream;
 	for (hipEvent_t& e : s->ev) {
-		BAM_TRY(c, hipEventCreate(&e));
+		NTE_TRY(c, hipEventCreate(&e));
 	}
-	BAM_TRY(c, hipMalloc((void**)&s->d_info, sizeof(BamInfo)));
-	BAM_TRY(c, hipHostMalloc((void**)&s->h_info, sizeof(BamInfo), hipHostMallocDefault));
-	BAM_TRY(c, hipHostMalloc((void**)&s->h_total, sizeof(u64), hipHostMallocDefault));
+	NTE_TRY(c, hipMalloc((void**)&s->d_info, sizeof(BamInfo)));
+	NTE_TRY(c, hipHostMalloc((void**)&s->h_info, sizeof(BamInfo), hipHostMallocDefault));
+	NTE_TRY(c, hipHostMalloc((void**)&s->h_total, sizeof(u64), hipHostMallocDefault));
 	s->device = device;
 	return 0;
 }
 
+// the entry of every call: the context's state, its device and the parse unit's stream
 int
-grow(const ntedit_hip_ctx* c, BamState* s, u8** p, u64* cap, u64 need)
+ready(const ntedit_hip_ctx* c, BamState** state)
 {
-	if (need <= *cap && *p) {
-		return 0;
-	}
-	if (*p) {
-		BAM_TRY(c, hipStreamSynchronize(s->stream));
-		BAM_TRY(c, hipFree(*p));
-		*p = nullptr;
-		*cap = 0;
-	}
-	const u64 want = (need + need / 4 + (1u << 16)) / 256 * 256;
-	BAM_TRY(c, hipMalloc((void**)p, want));
-	*cap = want;
-	return 0;
+	*state = g_bam.find(c, true);
+	return ensure_device(c, &(*state)->scr);
+}
+
+// buf to at least `need` bytes, by this unit's sizing rule (a quarter and 64 KiB of slack)
+int
+room(const ntedit_hip_ctx* c, BamScratch* s, DevBuf* buf, u64 need)
+{
+	return grow(c, s->stream, buf, need, (need + need / 4 + (1u << 16)) / 256 * 256);
 }
 
 void
-release_scratch(BamState* s)
+release_scratch(BamScratch* s)
 {
 	if (s->device < 0) {
 		return;
@@ -618,7 +575,7 @@ release_scratch(BamState* s)
 			(void)hipEventDestroy(e);
 		}
 	}
-	for (void* p : { (void*)s->d_seg, (void*)s->d_rec, (void*)s->d_in, (void*)s->d_info }) {
+	for (void* p : { (void*)s->seg.p, (void*)s->rec.p, (void*)s->in.p, (void*)s->d_info }) {
 		if (p) {
 			(void)hipFree(p);
 		}
@@ -628,21 +585,7 @@ release_scratch(BamState* s)
 			(void)hipHostFree(p);
 		}
 	}
-	const ntedit_hip_ctx* owner = s->owner;
-	const ntedit_hip_reads_bam_stats info = s->info;
-	const u64 segment = s->segment;
-	const u32 group_width = s->group_width;
-	*s = BamState();
-	s->group_width = group_width;
-	s->owner = owner;
-	s->info = info;
-	s->segment = segment;
-}
-
-u64
-up256(u64 x)
-{
-	return (x + 255) / 256 * 256;
+	*s = BamScratch();
 }
 
 // the per-segment arrays of nseg segments with `cap` table slots each, carved from one allocation
@@ -650,21 +593,16 @@ SegTables
 carve(u8* base, u64 nseg, u64 cap, u64* bytes)
 {
 	SegTables t;
-	u64 at = 0;
-	auto take = [&](u64 n) {
-		u8* p = base + at;
-		at += up256(n);
-		return p;
-	};
-	t.guess = (u32*)take(nseg * 4);
-	t.exit = (u32*)take(nseg * 4);
-	t.count = (u32*)take(nseg * 4);
-	t.status = (u32*)take(nseg * 4);
-	t.valid = (u32*)take(nseg * 4);
-	t.pack = (u64*)take((nseg + 1) * 8);
-	t.table = (u32*)take(nseg * cap * 4);
-	t.reason = take(nseg * cap);
-	*bytes = at;
+	Carver cut(base);
+	t.guess = (u32*)cut.take(nseg * 4);
+	t.exit = (u32*)cut.take(nseg * 4);
+	t.count = (u32*)cut.take(nseg * 4);
+	t.status = (u32*)cut.take(nseg * 4);
+	t.valid = (u32*)cut.take(nseg * 4);
+	t.pack = (u64*)cut.take((nseg + 1) * 8);
+	t.table = (u32*)cut.take(nseg * cap * 4);
+	t.reason = cut.take(nseg * cap);
+	*bytes = cut.at;
 	return t;
 }
 
@@ -676,9 +614,11 @@ to_result(const BamResult& r, ntedit_hip_reads_bam_result* res)
 
 // one chunk of device bytes: the walk, then the decode of the records before the cut
 int
-bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, int at_header, u32 min_len, u8* d_text, u64 text_cap,
+bam_on_device(const ntedit_hip_ctx* c, BamState* state, const u8* d_raw, u64 n64, int at_header, u32 min_len, u8* d_text, u64 text_cap,
               ntedit_hip_reads_bam_result* res)
 {
+	BamKeep& keep = state->keep;
+	BamScratch* s = &state->scr;
 	BamResult out = BamResult();
 	if (n64 >= BAM_MAX_RAW) {
 		to_result(bam_unclean(BAM_BAD_SIZE, 0), res);
@@ -691,13 +631,13 @@ bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, in
 	}
 	const u32 n = (u32)n64;
 	float ms = 0;
-	BAM_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(BamInfo), s->stream));
+	NTE_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(BamInfo), s->stream));
 	u32 entry = 0;
 	if (at_header) {
 		hipLaunchKernelGGL(k_bam_header, dim3(1), dim3(64), 0, s->stream, d_raw, n, s->d_info);
-		BAM_TRY(c, hipGetLastError());
-		BAM_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(BamInfo), hipMemcpyDeviceToHost, s->stream));
-		BAM_TRY(c, hipStreamSynchronize(s->stream));
+		NTE_TRY(c, hipGetLastError());
+		NTE_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(BamInfo), hipMemcpyDeviceToHost, s->stream));
+		NTE_TRY(c, hipStreamSynchronize(s->stream));
 		const u32 st = s->h_info->hdr_status;
 		if (st != BAM_NEXT) {
 			to_result(st == BAM_END ? out : bam_unclean(st, 0), res); // (BAM_END: cut 0, the chunk grows)
@@ -707,39 +647,39 @@ bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, in
 		out.n_ref = s->h_info->n_ref;
 		entry = (u32)out.header_len; // (inside the chunk: at most n)
 	}
-	u64 seg_bytes = s->segment ? s->segment : (u64)NTEDIT_BAM_SEGMENT;
+	u64 seg_bytes = keep.segment ? keep.segment : (u64)NTEDIT_BAM_SEGMENT;
 	seg_bytes = seg_bytes > n ? n : seg_bytes;
 	seg_bytes = seg_bytes < 64 ? 64 : seg_bytes;
 	const u32 nseg = (u32)((n + seg_bytes - 1) / seg_bytes), cap = bam_slice_cap((u32)seg_bytes);
 	u64 bytes = 0;
 	(void)carve(nullptr, nseg, cap, &bytes);
-	int rc = grow(c, s, &s->d_seg, &s->seg_cap, bytes);
+	int rc = room(c, s, &s->seg, bytes);
 	if (rc) {
 		return rc;
 	}
-	const SegTables t = carve(s->d_seg, nseg, cap, &bytes);
+	const SegTables t = carve(s->seg.p, nseg, cap, &bytes);
 	const unsigned seg_blocks = (nseg + BAM_WAVES - 1) / BAM_WAVES;
 	// ms_walk: the walk and the stitch (the header kernel, one lane once per file, and its round trip to the host are not in it)
-	BAM_TRY(c, hipEventRecord(s->ev[0], s->stream));
-	BAM_TRY(c, hipMemsetAsync(t.valid, 0, (u64)nseg * 4, s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	NTE_TRY(c, hipMemsetAsync(t.valid, 0, (u64)nseg * 4, s->stream));
 	hipLaunchKernelGGL(k_bam_walk, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, (u32)seg_bytes, nseg, entry, cap, t);
 	hipLaunchKernelGGL(k_bam_stitch, dim3(1), dim3(64), 0, s->stream, d_raw, n, (u32)seg_bytes, nseg, entry, cap, t, s->d_info);
-	BAM_TRY(c, hipGetLastError());
-	BAM_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	NTE_TRY(c, hipGetLastError());
+	NTE_TRY(c, hipEventRecord(s->ev[1], s->stream));
 	// the lengths of the records on the chain (a chunk that turns out unclean has paid for them: it fails the pass anyway)
-	BAM_TRY(c, hipEventRecord(s->ev[2], s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[2], s->stream));
 	const u64 max_records = (u64)n / BAM_MIN_RECORD + 2;
-	if ((rc = grow(c, s, &s->d_rec, &s->rec_cap, 2 * up256(max_records * 4))) != 0) {
+	if ((rc = room(c, s, &s->rec, 2 * up256(max_records * 4))) != 0) {
 		return rc;
 	}
-	u32 *krec_seq = (u32*)s->d_rec, *krec_text = (u32*)(s->d_rec + up256(max_records * 4));
+	u32 *krec_seq = (u32*)s->rec.p, *krec_text = (u32*)(s->rec.p + up256(max_records * 4));
 	const nte_parse::ReadFilter f = nte_reads::read_filter(c);
 	const bool filtered = nte_parse::rp_filter_on(f), facts = f.rq_bits || f.min_mean_qual;
 	if (facts) {
 		// the lanes per record: a whole wavefront for long reads, where one record's quality bytes are thousands and a
 		// narrower group would leave a few lanes with a long loop; 16 for reads of hundreds of bases (a lane has one or two
 		// 16-byte loads); 8 for short reads, where wider groups idle behind the aligned body
-		const u32 width = s->group_width ? s->group_width : s->mean_l_seq >= 2048 ? 64u : s->mean_l_seq >= 256 ? 16u : s->mean_l_seq ? 8u : 16u;
+		const u32 width = keep.group_width ? keep.group_width : s->mean_l_seq >= 2048 ? 64u : s->mean_l_seq >= 256 ? 16u : s->mean_l_seq ? 8u : 16u;
 		if (width == 64) {
 			hipLaunchKernelGGL(k_bam_facts<64>, dim3(seg_blocks), dim3(BAM_TPB), 0, s->stream, d_raw, n, nseg, cap, min_len, f, t, s->d_info);
 		} else if (width == 16) {
@@ -758,15 +698,15 @@ bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, in
 		                   reason);
 	}
 	hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(BAM_TPB), 0, s->stream, t.pack, nseg, krec_text);
-	BAM_TRY(c, hipGetLastError());
-	BAM_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(BamInfo), hipMemcpyDeviceToHost, s->stream));
-	BAM_TRY(c, hipMemcpyAsync(s->h_total, t.pack + nseg, sizeof(u64), hipMemcpyDeviceToHost, s->stream));
-	BAM_TRY(c, hipStreamSynchronize(s->stream));
-	BAM_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-	s->info.ms_walk += ms;
-	s->info.chunks++;
-	s->info.segments += nseg;
-	s->info.rewalked += s->h_info->rewalked;
+	NTE_TRY(c, hipGetLastError());
+	NTE_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(BamInfo), hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipMemcpyAsync(s->h_total, t.pack + nseg, sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
+	NTE_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	keep.info.ms_walk += ms;
+	keep.info.chunks++;
+	keep.info.segments += nseg;
+	keep.info.rewalked += s->h_info->rewalked;
 	if (s->h_info->broken) {
 		to_result(bam_unclean(s->h_info->broken, s->h_info->cut), res);
 		return 0;
@@ -811,20 +751,20 @@ bam_on_device(const ntedit_hip_ctx* c, BamState* s, const u8* d_raw, u64 n64, in
 			hipLaunchKernelGGL(k_bam_decode<false>, dim3(blocks), dim3(BAM_TPB), 0, s->stream, d_raw, krec_seq, krec_text, (u32)out.kept,
 			                   d_text, (u32)out.text_len, 0u, s->d_info);
 		}
-		BAM_TRY(c, hipGetLastError());
+		NTE_TRY(c, hipGetLastError());
 		if (min_qual) { // (the counts come back with the sync below)
-			BAM_TRY(c, hipMemcpyAsync(&s->h_info->qual_bases, &s->d_info->qual_bases, 2 * sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+			NTE_TRY(c, hipMemcpyAsync(&s->h_info->qual_bases, &s->d_info->qual_bases, 2 * sizeof(u64), hipMemcpyDeviceToHost, s->stream));
 		}
 	}
-	BAM_TRY(c, hipEventRecord(s->ev[3], s->stream));
-	BAM_TRY(c, hipStreamSynchronize(s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[3], s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
 	nte_reads::min_qual_count(c, 0, s->h_info->qual_bases, s->h_info->masked_bases); // (zero unless the mask ran: the info is zeroed per chunk)
-	BAM_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-	s->info.ms_decode += ms;
-	s->info.records += out.records;
-	s->info.kept += out.kept;
-	s->info.skipped_flag += out.skipped_flag;
-	s->info.skipped_short += out.skipped_short;
+	NTE_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+	keep.info.ms_decode += ms;
+	keep.info.records += out.records;
+	keep.info.kept += out.kept;
+	keep.info.skipped_flag += out.skipped_flag;
+	keep.info.skipped_short += out.skipped_short;
 	to_result(out, res);
 	return 0;
 }
@@ -837,26 +777,24 @@ namespace nte_reads {
 void
 bam_release(const ntedit_hip_ctx* c)
 {
-	BamState* s = bam_state(c, false);
+	BamState* s = g_bam.find(c, false);
 	if (s) {
-		release_scratch(s);
+		release_scratch(&s->scr);
 	}
 }
 
 ntedit_hip_reads_bam_stats*
 bam_info(const ntedit_hip_ctx* c)
 {
-	return &bam_state(c, true)->info;
+	return &g_bam.find(c, true)->keep.info;
 }
 
-// the first n bytes of the inflated chunk d_raw: walked, and the records before the cut decoded into the context's text
-// buffer (the one parse_buffer fills)
 int
 bam_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, int at_header, uint32_t min_len, const char** text,
            ntedit_hip_reads_bam_result* res)
 {
-	BamState* s = bam_state(c, true);
-	int rc = ensure_device(c, s);
+	BamState* s;
+	int rc = ready(c, &s);
 	char* d_text = nullptr;
 	uint64_t cap = 0;
 	if (rc == 0) {
@@ -894,7 +832,7 @@ ntedit_hip_reads_bam_set_segment(ntedit_hip_ctx* c, uint64_t bytes)
 	if (!c || (bytes && bytes < 64)) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_set_segment: a segment has at least 64 bytes") : NTEDIT_E_ARG;
 	}
-	bam_state(c, true)->segment = bytes;
+	g_bam.find(c, true)->keep.segment = bytes;
 	return 0;
 }
 
@@ -904,14 +842,14 @@ ntedit_hip_reads_bam_set_group_width(ntedit_hip_ctx* c, uint32_t lanes)
 	if (!c || (lanes != 0 && lanes != 8 && lanes != 16 && lanes != 64)) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_set_group_width: 0 (by the reads' mean length), 8, 16 or 64 lanes per record") : NTEDIT_E_ARG;
 	}
-	bam_state(c, true)->group_width = lanes;
+	g_bam.find(c, true)->keep.group_width = lanes;
 	return 0;
 }
 
 int
 ntedit_hip_reads_bam_group_width(ntedit_hip_ctx* c)
 {
-	return c ? (int)bam_state(c, true)->last_width : NTEDIT_E_ARG;
+	return c ? (int)g_bam.find(c, true)->scr.last_width : NTEDIT_E_ARG;
 }
 
 int
@@ -920,7 +858,7 @@ ntedit_hip_reads_bam_info(ntedit_hip_ctx* c, ntedit_hip_reads_bam_stats* st)
 	if (!c || !st) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_info: bad argument") : NTEDIT_E_ARG;
 	}
-	*st = bam_state(c, true)->info;
+	*st = g_bam.find(c, true)->keep.info;
 	return 0;
 }
 
@@ -933,20 +871,21 @@ ntedit_hip_reads_bam_device(ntedit_hip_ctx* c, const void* raw, uint64_t n_raw, 
 	    (on_device == NTEDIT_HIP_BASES_DEVICE && ((uintptr_t)raw & 15))) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_bam_device: bad argument") : NTEDIT_E_ARG;
 	}
-	BamState* s = bam_state(c, true);
-	int rc = ensure_device(c, s);
+	BamState* st;
+	int rc = ready(c, &st);
 	if (rc) {
 		return rc;
 	}
+	BamScratch* s = &st->scr;
 	const u8* d_raw = (const u8*)raw;
-	if (on_device == NTEDIT_HIP_BASES_HOST && n_raw && n_raw < BAM_MAX_RAW) {
-		if ((rc = grow(c, s, &s->d_in, &s->in_cap, n_raw)) != 0) {
+	if (on_device == NTEDIT_HIP_BASES_HOST && n_raw && n_raw < BAM_MAX_RAW) { // (its own buffer and sizing rule: not the parse unit's staging)
+		if ((rc = room(c, s, &s->in, n_raw)) != 0) {
 			return rc;
 		}
-		BAM_TRY(c, hipMemcpyAsync(s->d_in, raw, n_raw, hipMemcpyHostToDevice, s->stream));
-		d_raw = s->d_in;
+		NTE_TRY(c, hipMemcpyAsync(s->in.p, raw, n_raw, hipMemcpyHostToDevice, s->stream));
+		d_raw = s->in.p;
 	}
-	return bam_on_device(c, s, d_raw, n_raw, at_header, min_len, (u8*)text_device, text_cap, res);
+	return bam_on_device(c, st, d_raw, n_raw, at_header, min_len, (u8*)text_device, text_cap, res);
 }
 
 int
@@ -971,14 +910,11 @@ ntedit_hip_reads_bam_model_f(const void* raw, uint64_t n_raw, int at_header, uin
                              uint32_t min_mean_qual, float min_rq, char* out, uint64_t cap, ntedit_hip_reads_bam_result* res,
                              ntedit_hip_reads_read_filter_stats* st)
 {
-	if (!res || (n_raw && !raw) || (cap && !out) || min_qual > nte_parse::RP_MAX_MIN_QUAL || min_read_len > nte_parse::RP_MAX_MIN_READ_LEN ||
-	    min_mean_qual > nte_parse::RP_MAX_MEAN_QUAL || !(min_rq >= 0.0f && min_rq <= 1.0f)) {
+	nte_parse::ReadFilter f = nte_parse::ReadFilter();
+	if (!res || (n_raw && !raw) || (cap && !out) || min_qual > nte_parse::RP_MAX_MIN_QUAL ||
+	    !nte_parse::rp_make_filter(min_read_len, min_mean_qual, min_rq, &f)) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_bam_model: bad argument");
 	}
-	nte_parse::ReadFilter f = nte_parse::ReadFilter();
-	f.min_len = min_read_len;
-	f.min_mean_qual = min_mean_qual;
-	f.rq_bits = nte_parse::rp_rq_bits(min_rq);
 	BamResult r;
 	nte_parse::ReadFilterCounts fc = nte_parse::ReadFilterCounts();
 	bam_model_f((const u8*)raw, n_raw, at_header, min_len, min_qual, f, out, cap, &r, nullptr, &fc);

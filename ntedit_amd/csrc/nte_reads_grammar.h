@@ -183,6 +183,32 @@ rp_rq_bits(float min_rq)
 	return min_rq > 0.0f ? v.u : 0u;
 }
 
+// the filter of (L, Q, R) as the options and the calls give them; false when one is out of range: L above
+// RP_MAX_MIN_READ_LEN, Q above RP_MAX_MEAN_QUAL, R not within [0, 1] (written so that a NaN is refused) (host only)
+inline bool
+rp_make_filter(uint32_t min_len, uint32_t min_mean_qual, float min_rq, ReadFilter* f)
+{
+	if (min_len > RP_MAX_MIN_READ_LEN || min_mean_qual > RP_MAX_MEAN_QUAL || !(min_rq >= 0.0f && min_rq <= 1.0f)) {
+		return false;
+	}
+	f->min_len = min_len;
+	f->min_mean_qual = min_mean_qual;
+	f->rq_bits = rp_rq_bits(min_rq);
+	return true;
+}
+
+// a chunk's counts onto the pass's (host only)
+inline void
+rp_counts_add(ReadFilterCounts* to, const ReadFilterCounts& add)
+{
+	to->records += add.records;
+	to->by_length += add.by_length;
+	to->by_rq += add.by_rq;
+	to->by_mean_qual += add.by_mean_qual;
+	to->rq_tagged += add.rq_tagged;
+	to->aux_malformed += add.aux_malformed;
+}
+
 RP_HD bool
 rp_filter_on(const ReadFilter& f)
 {

@@ -16,26 +16,19 @@
 #include "nte_common.h"
 #include "nte_bgzf_inflate.h"
 
-#include "../../include/ntedit_hip.h"
+#include "nte_reads_internal.h"
+#include "nte_reads_unit.h"
+
 #include "../host/bgzf_walk.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <mutex>
 #include <string>
-#include <vector>
 
 using namespace nte;
 using namespace nte_bgzf;
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-int parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream);
-int parse_lines(const ntedit_hip_ctx* c, const unsigned char* d_raw, uint64_t n, const uint32_t** line_end, uint64_t* n_lines,
-                uint32_t* broken);
-void bam_release(const ntedit_hip_ctx* c);
-}
+using namespace nte_unit;
 
 namespace {
 
@@ -103,69 +96,35 @@ k_bz_last_start(const u8* __restrict__ raw, const u32* __restrict__ line_end, u6
 }
 
 // ------------------------------------------------------------------ host side
-struct InflateState
+struct InflateKeep // survives ntedit_hip_sketch_free
 {
-	const ntedit_hip_ctx* owner = nullptr;
 	ntedit_hip_reads_inflate_stats info = {};
+};
+
+// device scratch, grow-only, released by ntedit_hip_sketch_free
+struct InflateScratch
+{
 	int device = -1;
 	hipStream_t stream = nullptr, copy_stream = nullptr; // the parse unit's
 	hipEvent_t ev[2] = { nullptr, nullptr }, copied[2] = { nullptr, nullptr };
-	// device scratch, grow-only, released by ntedit_hip_sketch_free
-	u8* d_comp[2] = { nullptr, nullptr };
-	u64 comp_cap[2] = { 0, 0 };
-	u8* d_members[2] = { nullptr, nullptr };
-	u64 members_cap[2] = { 0, 0 };
-	u8* d_raw[2] = { nullptr, nullptr }; // the inflated chunk (a carried tail, then the members) and the next one's
-	u64 raw_cap[2] = { 0, 0 };
+	DevBuf comp[2], members[2];
+	DevBuf raw[2]; // the inflated chunk (a carried tail, then the members) and the next one's
 	int cur = 0;
-	u8* d_status = nullptr;
-	u64 status_cap = 0;
+	DevBuf status;
 	u32* h_status = nullptr; // page-locked
 	u64 h_status_cap = 0;
 	u32* d_cut = nullptr;
 	u32* h_cut = nullptr; // page-locked
 };
 
-std::mutex g_inflate_mu;
-std::vector<InflateState*> g_inflate;
-
-InflateState*
-inflate_state(const ntedit_hip_ctx* c, bool create)
-{
-	std::lock_guard<std::mutex> lk(g_inflate_mu);
-	for (InflateState* s : g_inflate) {
-		if (s->owner == c) {
-			return s;
-		}
-	}
-	if (!create) {
-		return nullptr;
-	}
-	InflateState* s = new InflateState();
-	s->owner = c;
-	g_inflate.push_back(s);
-	return s;
-}
+typedef State<InflateKeep, InflateScratch> InflateState;
+Registry<InflateState> g_inflate;
 
 int
-pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
-{
-	return nte_reads::set_error(c, code, why);
-}
-
-#define BZ_TRY(ctx, expr)                                                                         \
-	do {                                                                                          \
-		hipError_t e_ = (expr);                                                                   \
-		if (e_ != hipSuccess) {                                                                   \
-			return pfail((ctx), NTEDIT_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-		}                                                                                         \
-	} while (0)
-
-int
-ensure_device(const ntedit_hip_ctx* c, InflateState* s)
+ensure_device(const ntedit_hip_ctx* c, InflateScratch* s)
 {
 	if (s->device >= 0) {
-		BZ_TRY(c, hipSetDevice(s->device));
+		NTE_TRY(c, hipSetDevice(s->device));
 		return 0;
 	}
 	void *stream = nullptr, *copy_stream = nullptr;
@@ -174,61 +133,54 @@ ensure_device(const ntedit_hip_ctx* c, InflateState* s)
 		return rc;
 	}
 	int device = 0;
-	BZ_TRY(c, hipGetDevice(&device));
+	NTE_TRY(c, hipGetDevice(&device));
 	s->stream = (hipStream_t)stream;
 	s->copy_stream = (hipStream_t)copy_stream;
 	for (hipEvent_t& e : s->ev) {
-		BZ_TRY(c, hipEventCreate(&e));
+		NTE_TRY(c, hipEventCreate(&e));
 	}
 	for (hipEvent_t& e : s->copied) {
-		BZ_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		NTE_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
 	}
-	BZ_TRY(c, hipMalloc((void**)&s->d_cut, sizeof(u32)));
-	BZ_TRY(c, hipHostMalloc((void**)&s->h_cut, sizeof(u32), hipHostMallocDefault));
+	NTE_TRY(c, hipMalloc((void**)&s->d_cut, sizeof(u32)));
+	NTE_TRY(c, hipHostMalloc((void**)&s->h_cut, sizeof(u32), hipHostMallocDefault));
 	s->device = device;
 	return 0;
 }
 
-// *p to at least `need` bytes, the first `keep` bytes kept (copied on the stream, which is then drained)
+// the entry of every call: the context's state, its device and the parse unit's streams
 int
-grow(const ntedit_hip_ctx* c, InflateState* s, u8** p, u64* cap, u64 need, u64 keep)
+ready(const ntedit_hip_ctx* c, InflateState** state)
 {
-	if (need <= *cap && *p) {
-		return 0;
-	}
-	const u64 want = (need + need / 4 + (1u << 20)) / 256 * 256;
-	u8* q = nullptr;
-	BZ_TRY(c, hipMalloc((void**)&q, want));
-	if (*p) {
-		if (keep) {
-			BZ_TRY(c, hipMemcpyAsync(q, *p, keep, hipMemcpyDeviceToDevice, s->stream));
-		}
-		BZ_TRY(c, hipStreamSynchronize(s->stream));
-		BZ_TRY(c, hipFree(*p));
-	}
-	*p = q;
-	*cap = want;
-	return 0;
+	*state = g_inflate.find(c, true);
+	return ensure_device(c, &(*state)->scr);
+}
+
+// buf to at least `need` bytes, by this unit's sizing rule (a quarter and a MiB of slack), the first `keep` bytes kept
+int
+room(const ntedit_hip_ctx* c, InflateScratch* s, DevBuf* buf, u64 need, u64 keep = 0)
+{
+	return grow(c, s->stream, buf, need, (need + need / 4 + (1u << 20)) / 256 * 256, keep);
 }
 
 int
-grow_status(const ntedit_hip_ctx* c, InflateState* s, u64 n_members)
+room_status(const ntedit_hip_ctx* c, InflateScratch* s, u64 n_members)
 {
-	int rc = grow(c, s, &s->d_status, &s->status_cap, n_members * 4, 0);
+	int rc = room(c, s, &s->status, n_members * 4);
 	if (rc == 0 && n_members > s->h_status_cap) {
 		if (s->h_status) {
-			BZ_TRY(c, hipHostFree(s->h_status));
+			NTE_TRY(c, hipHostFree(s->h_status));
 			s->h_status = nullptr;
 		}
 		const u64 want = n_members + n_members / 4 + 1024;
-		BZ_TRY(c, hipHostMalloc((void**)&s->h_status, want * 4, hipHostMallocDefault));
+		NTE_TRY(c, hipHostMalloc((void**)&s->h_status, want * 4, hipHostMallocDefault));
 		s->h_status_cap = want;
 	}
 	return rc;
 }
 
 void
-release_scratch(InflateState* s)
+release_scratch(InflateScratch* s)
 {
 	if (s->device < 0) {
 		return;
@@ -244,8 +196,8 @@ release_scratch(InflateState* s)
 			(void)hipEventDestroy(e);
 		}
 	}
-	for (void* p : { (void*)s->d_comp[0], (void*)s->d_comp[1], (void*)s->d_members[0], (void*)s->d_members[1], (void*)s->d_raw[0],
-	                 (void*)s->d_raw[1], (void*)s->d_status, (void*)s->d_cut }) {
+	for (void* p : { (void*)s->comp[0].p, (void*)s->comp[1].p, (void*)s->members[0].p, (void*)s->members[1].p, (void*)s->raw[0].p,
+	                 (void*)s->raw[1].p, (void*)s->status.p, (void*)s->d_cut }) {
 		if (p) {
 			(void)hipFree(p);
 		}
@@ -255,11 +207,7 @@ release_scratch(InflateState* s)
 			(void)hipHostFree(p);
 		}
 	}
-	const ntedit_hip_ctx* owner = s->owner;
-	const ntedit_hip_reads_inflate_stats info = s->info;
-	*s = InflateState();
-	s->owner = owner;
-	s->info = info;
+	*s = InflateScratch();
 }
 
 // every member inside its buffers: what the kernel relies on
@@ -276,25 +224,26 @@ members_fit(const Member* m, u64 n_members, u64 n_comp, u64 out_cap)
 
 // the members of d_comp (table d_members) into d_out, their statuses to s->h_status; the stream is drained
 int
-inflate_on_device(const ntedit_hip_ctx* c, InflateState* s, const u8* d_comp, const Member* d_members, u64 n_members, u8* d_out)
+inflate_on_device(const ntedit_hip_ctx* c, InflateState* st, const u8* d_comp, const Member* d_members, u64 n_members, u8* d_out)
 {
+	InflateScratch* s = &st->scr;
 	if (n_members == 0) {
 		return 0;
 	}
-	int rc = grow_status(c, s, n_members);
+	int rc = room_status(c, s, n_members);
 	if (rc) {
 		return rc;
 	}
-	BZ_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[0], s->stream));
 	const unsigned blocks = (unsigned)((n_members + BZ_WAVES - 1) / BZ_WAVES);
-	hipLaunchKernelGGL(k_bz_inflate, dim3(blocks), dim3(BZ_TPB), 0, s->stream, d_comp, d_members, (u32)n_members, d_out, (u32*)s->d_status);
-	BZ_TRY(c, hipGetLastError());
-	BZ_TRY(c, hipEventRecord(s->ev[1], s->stream));
-	BZ_TRY(c, hipMemcpyAsync(s->h_status, s->d_status, n_members * 4, hipMemcpyDeviceToHost, s->stream));
-	BZ_TRY(c, hipStreamSynchronize(s->stream));
+	hipLaunchKernelGGL(k_bz_inflate, dim3(blocks), dim3(BZ_TPB), 0, s->stream, d_comp, d_members, (u32)n_members, d_out, (u32*)s->status.p);
+	NTE_TRY(c, hipGetLastError());
+	NTE_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	NTE_TRY(c, hipMemcpyAsync(s->h_status, s->status.p, n_members * 4, hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
 	float ms = 0;
-	BZ_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-	s->info.ms_kernels += ms;
+	NTE_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	st->keep.info.ms_kernels += ms;
 	return 0;
 }
 
@@ -317,23 +266,23 @@ reason_text(u32 st)
 
 } // namespace
 
-// what the pass loop of reads_pass.cpp needs beyond the public calls
+// what the pass loop of reads_pass.cpp needs beyond the public calls (nte_reads_internal.h says what each does)
 namespace nte_reads {
 
 void
 inflate_release(const ntedit_hip_ctx* c)
 {
 	bam_release(c); // (nte_reads_bam.hip works on the same streams, behind this unit's chunks)
-	InflateState* s = inflate_state(c, false);
+	InflateState* s = g_inflate.find(c, false);
 	if (s) {
-		release_scratch(s);
+		release_scratch(&s->scr);
 	}
 }
 
 ntedit_hip_reads_inflate_stats*
 inflate_info(const ntedit_hip_ctx* c)
 {
-	return &inflate_state(c, true)->info;
+	return &g_inflate.find(c, true)->keep.info;
 }
 
 const char*
@@ -342,52 +291,51 @@ inflate_reason(uint32_t st)
 	return reason_text(st);
 }
 
-// a chunk's compressed bytes and member table -> buffers `which`, on the copy stream; returns at once
 int
 inflate_copy_begin(const ntedit_hip_ctx* c, int which, const char* comp, uint64_t n_comp, const ntedit_hip_bgzf_member* members,
                    uint64_t n_members)
 {
-	InflateState* s = inflate_state(c, true);
-	int rc = ensure_device(c, s);
+	InflateState* st;
+	int rc = ready(c, &st);
+	InflateScratch* s = &st->scr;
 	if (rc == 0) {
-		rc = grow(c, s, &s->d_comp[which], &s->comp_cap[which], n_comp, 0);
+		rc = room(c, s, &s->comp[which], n_comp);
 	}
 	if (rc == 0) {
-		rc = grow(c, s, &s->d_members[which], &s->members_cap[which], n_members * sizeof(Member), 0);
+		rc = room(c, s, &s->members[which], n_members * sizeof(Member));
 	}
 	if (rc) {
 		return rc;
 	}
 	if (n_comp) {
-		BZ_TRY(c, hipMemcpyAsync(s->d_comp[which], comp, n_comp, hipMemcpyHostToDevice, s->copy_stream));
+		NTE_TRY(c, hipMemcpyAsync(s->comp[which].p, comp, n_comp, hipMemcpyHostToDevice, s->copy_stream));
 	}
 	if (n_members) {
-		BZ_TRY(c, hipMemcpyAsync(s->d_members[which], members, n_members * sizeof(Member), hipMemcpyHostToDevice, s->copy_stream));
+		NTE_TRY(c, hipMemcpyAsync(s->members[which].p, members, n_members * sizeof(Member), hipMemcpyHostToDevice, s->copy_stream));
 	}
-	BZ_TRY(c, hipEventRecord(s->copied[which], s->copy_stream));
+	NTE_TRY(c, hipEventRecord(s->copied[which], s->copy_stream));
 	return 0;
 }
 
 int
 inflate_copy_wait(const ntedit_hip_ctx* c, int which)
 {
-	InflateState* s = inflate_state(c, false);
-	if (s && s->copied[which]) {
-		BZ_TRY(c, hipEventSynchronize(s->copied[which]));
+	InflateState* s = g_inflate.find(c, false);
+	if (s && s->scr.copied[which]) {
+		NTE_TRY(c, hipEventSynchronize(s->scr.copied[which]));
 	}
 	return 0;
 }
 
-// Waits for that copy, then inflates its members (the host's copy of the table: `members`, checked here) behind the
-// `tail` bytes the current raw buffer already holds.  *raw: the buffer.  *bad: the first refused member, or n_members.
 int
 inflate_copied(const ntedit_hip_ctx* c, int which, uint64_t n_comp, const ntedit_hip_bgzf_member* members, uint64_t n_members,
                uint64_t tail, uint64_t n_out, const char** raw, uint64_t* bad, uint32_t* reason)
 {
-	InflateState* s = inflate_state(c, true);
-	int rc = ensure_device(c, s);
+	InflateState* st;
+	int rc = ready(c, &st);
+	InflateScratch* s = &st->scr;
 	if (rc == 0) {
-		rc = grow(c, s, &s->d_raw[s->cur], &s->raw_cap[s->cur], tail + n_out + 16, tail);
+		rc = room(c, s, &s->raw[s->cur], tail + n_out + 16, tail); // (a carried tail moves with the buffer)
 	}
 	if (rc) {
 		return rc;
@@ -395,11 +343,11 @@ inflate_copied(const ntedit_hip_ctx* c, int which, uint64_t n_comp, const ntedit
 	if (!members_fit(members, n_members, n_comp, n_out)) {
 		return pfail(c, NTEDIT_E_ARG, "reads_inflate: a member outside its buffers");
 	}
-	BZ_TRY(c, hipEventSynchronize(s->copied[which]));
-	*raw = (const char*)s->d_raw[s->cur];
+	NTE_TRY(c, hipEventSynchronize(s->copied[which]));
+	*raw = (const char*)s->raw[s->cur].p;
 	*bad = n_members;
 	*reason = 0;
-	rc = inflate_on_device(c, s, s->d_comp[which], (const Member*)s->d_members[which], n_members, s->d_raw[s->cur] + tail);
+	rc = inflate_on_device(c, st, s->comp[which].p, (const Member*)s->members[which].p, n_members, s->raw[s->cur].p + tail);
 	if (rc) {
 		return rc;
 	}
@@ -410,35 +358,34 @@ inflate_copied(const ntedit_hip_ctx* c, int which, uint64_t n_comp, const ntedit
 			break;
 		}
 	}
-	s->info.members += n_members;
-	s->info.comp_bytes += n_comp;
-	s->info.raw_bytes += n_out;
+	st->keep.info.members += n_members;
+	st->keep.info.comp_bytes += n_comp;
+	st->keep.info.raw_bytes += n_out;
 	return 0;
 }
 
-// the last record start of the current raw buffer's first n bytes; *cut = 0: none.  *broken: the line table cannot
-// hold the bytes (the chunk is unclean then, whatever the cut)
 int
 inflate_last_start(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint64_t* cut, uint32_t* broken)
 {
-	InflateState* s = inflate_state(c, true);
-	int rc = ensure_device(c, s);
+	InflateState* st;
+	int rc = ready(c, &st);
 	if (rc) {
 		return rc;
 	}
+	InflateScratch* s = &st->scr;
 	*cut = 0;
 	*broken = 0;
 	if (n < 2) {
 		return 0;
 	}
 	unsigned char kind = 0;
-	BZ_TRY(c, hipMemcpyAsync(&kind, d_raw, 1, hipMemcpyDeviceToHost, s->stream));
-	BZ_TRY(c, hipStreamSynchronize(s->stream));
+	NTE_TRY(c, hipMemcpyAsync(&kind, d_raw, 1, hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
 	if (kind != '>' && kind != '@') {
 		*cut = n; // (unclean anyway, as RawProducer has it)
 		return 0;
 	}
-	BZ_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[0], s->stream));
 	const uint32_t* line_end = nullptr;
 	uint64_t n_lines = 0;
 	if ((rc = nte_reads::parse_lines(c, (const unsigned char*)d_raw, n, &line_end, &n_lines, broken)) != 0) {
@@ -447,35 +394,34 @@ inflate_last_start(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint6
 	if (*broken) {
 		return 0;
 	}
-	BZ_TRY(c, hipMemsetAsync(s->d_cut, 0, sizeof(u32), s->stream));
+	NTE_TRY(c, hipMemsetAsync(s->d_cut, 0, sizeof(u32), s->stream));
 	if (n_lines > 1) {
 		const unsigned blocks = (unsigned)((n_lines - 1 + BZ_TPB - 1) / BZ_TPB);
 		hipLaunchKernelGGL(k_bz_last_start, dim3(blocks), dim3(BZ_TPB), 0, s->stream, (const u8*)d_raw, line_end, n_lines, (int)kind, s->d_cut);
-		BZ_TRY(c, hipGetLastError());
+		NTE_TRY(c, hipGetLastError());
 	}
-	BZ_TRY(c, hipEventRecord(s->ev[1], s->stream));
-	BZ_TRY(c, hipMemcpyAsync(s->h_cut, s->d_cut, sizeof(u32), hipMemcpyDeviceToHost, s->stream));
-	BZ_TRY(c, hipStreamSynchronize(s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	NTE_TRY(c, hipMemcpyAsync(s->h_cut, s->d_cut, sizeof(u32), hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
 	float ms = 0;
-	BZ_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-	s->info.ms_kernels += ms;
+	NTE_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	st->keep.info.ms_kernels += ms;
 	*cut = *s->h_cut;
 	return 0;
 }
 
-// the bytes [cut, total) of the current raw buffer to the front of the other one, which becomes the current
 int
 inflate_carry(const ntedit_hip_ctx* c, uint64_t cut, uint64_t total)
 {
-	InflateState* s = inflate_state(c, true);
+	InflateScratch* s = &g_inflate.find(c, true)->scr;
 	const int other = s->cur ^ 1;
 	const uint64_t tail = total - cut;
-	int rc = grow(c, s, &s->d_raw[other], &s->raw_cap[other], tail + 16, 0);
+	int rc = room(c, s, &s->raw[other], tail + 16);
 	if (rc) {
 		return rc;
 	}
 	if (tail) {
-		BZ_TRY(c, hipMemcpyAsync(s->d_raw[other], s->d_raw[s->cur] + cut, tail, hipMemcpyDeviceToDevice, s->stream));
+		NTE_TRY(c, hipMemcpyAsync(s->raw[other].p, s->raw[s->cur].p + cut, tail, hipMemcpyDeviceToDevice, s->stream));
 	}
 	s->cur = other;
 	return 0;
@@ -491,7 +437,7 @@ ntedit_hip_reads_inflate_info(ntedit_hip_ctx* c, ntedit_hip_reads_inflate_stats*
 	if (!c || !st) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_inflate_info: bad argument") : NTEDIT_E_ARG;
 	}
-	*st = inflate_state(c, true)->info;
+	*st = g_inflate.find(c, true)->keep.info;
 	return 0;
 }
 
@@ -506,26 +452,27 @@ ntedit_hip_reads_inflate_device(ntedit_hip_ctx* c, const void* comp, uint64_t n_
 	if (!members_fit(members, n_members, n_comp, out_cap)) {
 		return pfail(c, NTEDIT_E_ARG, "reads_inflate_device: a member outside comp[0 .. n_comp) or out[0 .. out_cap)");
 	}
-	InflateState* s = inflate_state(c, true);
-	int rc = ensure_device(c, s);
+	InflateState* st;
+	int rc = ready(c, &st);
 	if (rc || n_members == 0) {
 		return rc;
 	}
+	InflateScratch* s = &st->scr;
 	const u8* d_comp = (const u8*)comp;
 	if (on_device == NTEDIT_HIP_BASES_HOST) {
-		if ((rc = grow(c, s, &s->d_comp[0], &s->comp_cap[0], n_comp, 0)) != 0) {
+		if ((rc = room(c, s, &s->comp[0], n_comp)) != 0) {
 			return rc;
 		}
 		if (n_comp) {
-			BZ_TRY(c, hipMemcpyAsync(s->d_comp[0], comp, n_comp, hipMemcpyHostToDevice, s->stream));
+			NTE_TRY(c, hipMemcpyAsync(s->comp[0].p, comp, n_comp, hipMemcpyHostToDevice, s->stream));
 		}
-		d_comp = s->d_comp[0];
+		d_comp = s->comp[0].p;
 	}
-	if ((rc = grow(c, s, &s->d_members[0], &s->members_cap[0], n_members * sizeof(Member), 0)) != 0) {
+	if ((rc = room(c, s, &s->members[0], n_members * sizeof(Member))) != 0) {
 		return rc;
 	}
-	BZ_TRY(c, hipMemcpyAsync(s->d_members[0], members, n_members * sizeof(Member), hipMemcpyHostToDevice, s->stream));
-	if ((rc = inflate_on_device(c, s, d_comp, (const Member*)s->d_members[0], n_members, (u8*)out_device)) != 0) {
+	NTE_TRY(c, hipMemcpyAsync(s->members[0].p, members, n_members * sizeof(Member), hipMemcpyHostToDevice, s->stream));
+	if ((rc = inflate_on_device(c, st, d_comp, (const Member*)s->members[0].p, n_members, (u8*)out_device)) != 0) {
 		return rc;
 	}
 	memcpy(status, s->h_status, n_members * 4);
@@ -580,20 +527,21 @@ ntedit_hip_reads_last_start_device(ntedit_hip_ctx* c, const void* buf, uint64_t 
 	    (on_device == NTEDIT_HIP_BASES_DEVICE && ((uintptr_t)buf & 15))) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_last_start_device: bad argument") : NTEDIT_E_ARG;
 	}
-	InflateState* s = inflate_state(c, true);
-	int rc = ensure_device(c, s);
+	InflateState* st;
+	int rc = ready(c, &st);
 	if (rc) {
 		return rc;
 	}
+	InflateScratch* s = &st->scr;
 	const char* d_buf = (const char*)buf;
 	if (on_device == NTEDIT_HIP_BASES_HOST) {
-		if ((rc = grow(c, s, &s->d_raw[s->cur], &s->raw_cap[s->cur], n + 16, 0)) != 0) {
+		if ((rc = room(c, s, &s->raw[s->cur], n + 16)) != 0) {
 			return rc;
 		}
 		if (n) {
-			BZ_TRY(c, hipMemcpyAsync(s->d_raw[s->cur], buf, n, hipMemcpyHostToDevice, s->stream));
+			NTE_TRY(c, hipMemcpyAsync(s->raw[s->cur].p, buf, n, hipMemcpyHostToDevice, s->stream));
 		}
-		d_buf = (const char*)s->d_raw[s->cur];
+		d_buf = (const char*)s->raw[s->cur].p;
 	}
 	uint32_t broken = 0;
 	uint64_t at = 0;

@@ -37,23 +37,17 @@
 #include "nte_reads_grammar.h"
 #include "nte_reads_model.h"
 #include "nte_genome_grammar.h"
-
-#include "../../include/ntedit_hip.h"
+#include "nte_reads_internal.h"
+#include "nte_reads_unit.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <mutex>
 #include <string>
-#include <vector>
 
 using namespace nte;
 using namespace nte_parse;
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-void inflate_release(const ntedit_hip_ctx* c); // (nte_reads_inflate.hip: its scratch works on this unit's streams)
-}
+using namespace nte_unit;
 
 namespace {
 
@@ -659,71 +653,42 @@ k_gp_line_out(const u8* __restrict__ cls, const u64* __restrict__ sr, u64 n_line
 }
 
 // ------------------------------------------------------------------ host side
-struct ParseState
+// what the calls set and the last pass counted: survives ntedit_hip_sketch_free
+struct ParseKeep
 {
-	const ntedit_hip_ctx* owner = nullptr;
-	int on = 0; // ntedit_hip_reads_set_device_parse
-	u32 min_qual = 0;                        // ntedit_hip_reads_set_min_qual (0: off)
-	u64 qual_bases = 0, masked_bases = 0;    // ntedit_hip_reads_min_qual_info: the last pass, host parser and device
-	ReadFilter filter = ReadFilter();        // ntedit_hip_reads_set_read_filter (all 0: off)
+	int on = 0;                                    // ntedit_hip_reads_set_device_parse
+	u32 min_qual = 0;                              // ntedit_hip_reads_set_min_qual (0: off)
+	u64 qual_bases = 0, masked_bases = 0;          // ntedit_hip_reads_min_qual_info: the last pass, host parser and device
+	ReadFilter filter = ReadFilter();              // ntedit_hip_reads_set_read_filter (all 0: off)
 	ReadFilterCounts fcounts = ReadFilterCounts(); // ntedit_hip_reads_read_filter_info: the last pass, host parser and device
 	ntedit_hip_reads_parse_stats info = {};
 	ntedit_hip_genome_pass_info ginfo = {}; // ntedit_hip_genome_pass
-	// device scratch, grow-only, released by ntedit_hip_sketch_free
+};
+
+enum { BUF_RAW0 = 0, BUF_RAW1 = 1, BUF_TEXT, BUF_GTEXT, N_BUFS, NO_BUF = -1 };
+
+// device scratch, grow-only, released by ntedit_hip_sketch_free
+struct ParseScratch
+{
 	int device = -1;
 	hipStream_t stream = nullptr, copy_stream = nullptr;
 	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr }, copied[2] = { nullptr, nullptr };
-	u8* d_raw[2] = { nullptr, nullptr };
-	u64 raw_cap[2] = { 0, 0 };
-	u8* d_text = nullptr;
-	u64 text_cap = 0;
-	u8* d_gtext = nullptr; // a genome pass: GP_PAD bytes of carried text, then the chunk's text
-	u64 gtext_cap = 0;
+	// the two raw buffers, the text, and a genome pass's text: GP_PAD bytes of carried text, then the chunk's (each is
+	// allocated with RP_TILE bytes behind its cap)
+	DevBuf buf[N_BUFS];
 	u8* d_gstage = nullptr; // GP_PAD bytes
-	u8* d_table = nullptr; // the line table and the scans' block sums, for chunks of up to table_raw bytes
+	u8* d_table = nullptr;  // the line table and the scans' block sums, for chunks of up to table_raw bytes
 	u64 table_raw = 0;
 	bool table_qsum = false; // the allocation has room for the quality sums (k_rp_qsum)
 	RpInfo* d_info = nullptr;
 	RpInfo* h_info = nullptr; // page-locked
 };
 
-std::mutex g_parse_mu;
-std::vector<ParseState*> g_parse;
-
-ParseState*
-parse_state(const ntedit_hip_ctx* c, bool create)
-{
-	std::lock_guard<std::mutex> lk(g_parse_mu);
-	for (ParseState* s : g_parse) {
-		if (s->owner == c) {
-			return s;
-		}
-	}
-	if (!create) {
-		return nullptr;
-	}
-	ParseState* s = new ParseState();
-	s->owner = c;
-	g_parse.push_back(s);
-	return s;
-}
-
-int
-pfail(const ntedit_hip_ctx* c, int code, const std::string& why)
-{
-	return nte_reads::set_error(c, code, why);
-}
-
-#define RP_TRY(ctx, expr)                                                                         \
-	do {                                                                                          \
-		hipError_t e_ = (expr);                                                                   \
-		if (e_ != hipSuccess) {                                                                   \
-			return pfail((ctx), NTEDIT_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-		}                                                                                         \
-	} while (0)
+typedef State<ParseKeep, ParseScratch> ParseState;
+Registry<ParseState> g_parse;
 
 void
-release_scratch(ParseState* s)
+release_scratch(ParseScratch* s)
 {
 	if (s->device < 0) {
 		return;
@@ -740,8 +705,8 @@ release_scratch(ParseState* s)
 			(void)hipEventDestroy(e);
 		}
 	}
-	for (void* p : { (void*)s->d_raw[0], (void*)s->d_raw[1], (void*)s->d_text, (void*)s->d_table, (void*)s->d_info, (void*)s->d_gtext,
-		                (void*)s->d_gstage }) {
+	for (void* p : { (void*)s->buf[BUF_RAW0].p, (void*)s->buf[BUF_RAW1].p, (void*)s->buf[BUF_TEXT].p, (void*)s->d_table, (void*)s->d_info,
+		                (void*)s->buf[BUF_GTEXT].p, (void*)s->d_gstage }) {
 		if (p) {
 			(void)hipFree(p);
 		}
@@ -749,70 +714,49 @@ release_scratch(ParseState* s)
 	if (s->h_info) {
 		(void)hipHostFree(s->h_info);
 	}
-	const ntedit_hip_ctx* owner = s->owner;
-	const int on = s->on;
-	const ntedit_hip_reads_parse_stats info = s->info;
-	const ntedit_hip_genome_pass_info ginfo = s->ginfo;
-	const u32 min_qual = s->min_qual;
-	const u64 qual_bases = s->qual_bases, masked_bases = s->masked_bases;
-	const ReadFilter filter = s->filter;
-	const ReadFilterCounts fcounts = s->fcounts;
-	*s = ParseState();
-	s->owner = owner;
-	s->on = on;
-	s->min_qual = min_qual;
-	s->qual_bases = qual_bases;
-	s->masked_bases = masked_bases;
-	s->filter = filter;
-	s->fcounts = fcounts;
-	s->info = info;
-	s->ginfo = ginfo;
+	*s = ParseScratch();
 }
 
 int
-ensure_device(const ntedit_hip_ctx* c, ParseState* s)
+ensure_device(const ntedit_hip_ctx* c, ParseScratch* s)
 {
 	if (s->device >= 0) {
-		RP_TRY(c, hipSetDevice(s->device));
+		NTE_TRY(c, hipSetDevice(s->device));
 		return 0;
 	}
 	int device = 0;
-	RP_TRY(c, hipGetDevice(&device));
+	NTE_TRY(c, hipGetDevice(&device));
 	s->device = device;
-	RP_TRY(c, hipStreamCreate(&s->stream));
-	RP_TRY(c, hipStreamCreate(&s->copy_stream));
+	NTE_TRY(c, hipStreamCreate(&s->stream));
+	NTE_TRY(c, hipStreamCreate(&s->copy_stream));
 	for (hipEvent_t& e : s->ev) {
-		RP_TRY(c, hipEventCreate(&e));
+		NTE_TRY(c, hipEventCreate(&e));
 	}
 	for (hipEvent_t& e : s->copied) {
-		RP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		NTE_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
 	}
-	RP_TRY(c, hipMalloc((void**)&s->d_info, sizeof(RpInfo)));
-	RP_TRY(c, hipHostMalloc((void**)&s->h_info, sizeof(RpInfo), hipHostMallocDefault));
+	NTE_TRY(c, hipMalloc((void**)&s->d_info, sizeof(RpInfo)));
+	NTE_TRY(c, hipHostMalloc((void**)&s->h_info, sizeof(RpInfo), hipHostMallocDefault));
 	return 0;
 }
 
-int
-grow(const ntedit_hip_ctx* c, u8** p, u64* cap, u64 need)
-{
-	if (need <= *cap && *p) {
-		return 0;
-	}
-	if (*p) {
-		RP_TRY(c, hipFree(*p));
-		*p = nullptr;
-		*cap = 0;
-	}
-	const u64 want = (need + (1u << 20)) / 16 * 16;
-	RP_TRY(c, hipMalloc((void**)p, want + RP_TILE));
-	*cap = want;
-	return 0;
-}
-
+// this unit's buffers: a MiB of slack, a multiple of 16 (and RP_TILE bytes behind that, which cap does not count)
 u64
-up256(u64 x)
+buf_want(u64 need)
 {
-	return (x + 255) / 256 * 256;
+	return (need + (1u << 20)) / 16 * 16;
+}
+
+// the entry of every call: the context's state, its device and streams, and (but for NO_BUF) room for `need` bytes in a buffer
+int
+ready(const ntedit_hip_ctx* c, ParseState** state, int buf = NO_BUF, u64 need = 0)
+{
+	ParseState* s = *state = g_parse.find(c, true);
+	int rc = ensure_device(c, &s->scr);
+	if (rc == 0 && buf != NO_BUF) {
+		rc = grow(c, s->scr.stream, &s->scr.buf[buf], need, buf_want(need), 0, RP_TILE);
+	}
+	return rc;
 }
 
 // the line table of a chunk of up to n raw bytes, carved from one allocation
@@ -830,28 +774,23 @@ carve(u8* base, u64 n_raw, bool with_qsum = false)
 	const u64 tiles = (n_raw + RP_TILE - 1) / RP_TILE + 1, lines = rp_max_lines(n_raw) + 2;
 	const u64 blocks = (lines > tiles ? lines : tiles) / SC_BLOCK + 2;
 	Table t;
-	u64 at = 0;
-	auto take = [&](u64 bytes) {
-		u8* p = base + at;
-		at += up256(bytes);
-		return p;
-	};
-	t.tile = (u64*)take(tiles * 8);
-	t.sr = (u64*)take(lines * 8);
-	t.rec = (u64*)take(lines * 8);
-	t.bsum = (u64*)take(blocks * 8);
-	t.line_end = (u32*)take(lines * 4);
-	t.head_line = (u32*)take(lines * 4);
-	t.line_out = (u32*)take(lines * 4);
-	t.cls = take(lines);
-	t.qsum = with_qsum ? (u64*)take(lines * 8) : nullptr; // (--min_mean_qual alone pays for k_rp_qsum's table: it lies last)
-	t.bytes = at;
+	Carver cut(base);
+	t.tile = (u64*)cut.take(tiles * 8);
+	t.sr = (u64*)cut.take(lines * 8);
+	t.rec = (u64*)cut.take(lines * 8);
+	t.bsum = (u64*)cut.take(blocks * 8);
+	t.line_end = (u32*)cut.take(lines * 4);
+	t.head_line = (u32*)cut.take(lines * 4);
+	t.line_out = (u32*)cut.take(lines * 4);
+	t.cls = cut.take(lines);
+	t.qsum = with_qsum ? (u64*)cut.take(lines * 8) : nullptr; // (--min_mean_qual alone pays for k_rp_qsum's table: it lies last)
+	t.bytes = cut.at;
 	return t;
 }
 
 // data[0 .. n) to its exclusive scan in place, data[n] = the total
 void
-scan(ParseState* s, u64* data, u64 n, u64* bsum)
+scan(ParseScratch* s, u64* data, u64 n, u64* bsum)
 {
 	const u64 nb = (n + SC_BLOCK - 1) / SC_BLOCK;
 	hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nb), dim3(RP_TPB), 0, s->stream, data, n, bsum);
@@ -859,10 +798,73 @@ scan(ParseState* s, u64* data, u64 n, u64* bsum)
 	hipLaunchKernelGGL(k_scan_write, dim3((unsigned)nb), dim3(RP_TPB), 0, s->stream, data, n, bsum, data);
 }
 
+struct Lines
+{
+	Table t;
+	u64 tiles, lines;
+};
+
+// The front phase of every chunk (n > 0 raw bytes): the line table, reallocated for `want` raw bytes (with_qsum: and the
+// quality sums) unless it `fits` by the caller's rule; the info zeroed; the newlines per tile and their scan; the number of
+// lines and the first words of the info read back (the one host sync in the middle).  *ms (when given) += the kernels' time.
 int
-parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, u32 k, u8* d_text, u64 text_cap,
+line_table(const ntedit_hip_ctx* c, ParseScratch* s, const u8* d_raw, u64 n, bool fits, u64 want, bool with_qsum, double* ms, Lines* out)
+{
+	if (!fits || !s->d_table) {
+		if (s->d_table) {
+			NTE_TRY(c, hipStreamSynchronize(s->stream));
+			NTE_TRY(c, hipFree(s->d_table));
+			s->d_table = nullptr;
+			s->table_raw = 0;
+		}
+		NTE_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want, with_qsum).bytes));
+		s->table_raw = want;
+		s->table_qsum = with_qsum;
+	}
+	const Table t = out->t = carve(s->d_table, s->table_raw, s->table_qsum);
+	const u64 tiles = out->tiles = (n + RP_TILE - 1) / RP_TILE;
+	NTE_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
+	if (ms) {
+		NTE_TRY(c, hipEventRecord(s->ev[0], s->stream));
+	}
+	hipLaunchKernelGGL(k_rp_tiles, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, s->d_info);
+	scan(s, t.tile, tiles, t.bsum);
+	NTE_TRY(c, hipGetLastError());
+	if (ms) {
+		NTE_TRY(c, hipEventRecord(s->ev[1], s->stream));
+	}
+	NTE_TRY(c, hipMemcpyAsync(&s->h_info->newlines, t.tile + tiles, 8, hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, 16, hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
+	if (ms) {
+		float front = 0;
+		NTE_TRY(c, hipEventElapsedTime(&front, s->ev[0], s->ev[1]));
+		*ms += front;
+	}
+	out->lines = s->h_info->newlines + (s->h_info->last_nl ? 0 : 1);
+	return 0;
+}
+
+// the closing phase of a chunk whose later kernels were queued behind ev[2]: the chunk's info read back, *ms += their time
+int
+finish(const ntedit_hip_ctx* c, ParseScratch* s, double* ms)
+{
+	NTE_TRY(c, hipGetLastError());
+	NTE_TRY(c, hipEventRecord(s->ev[3], s->stream));
+	NTE_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(RpInfo), hipMemcpyDeviceToHost, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
+	float back = 0;
+	NTE_TRY(c, hipEventElapsedTime(&back, s->ev[2], s->ev[3]));
+	*ms += back;
+	return 0;
+}
+
+int
+parse_on_device(const ntedit_hip_ctx* c, ParseState* st, const u8* d_raw, u64 n, u32 k, u8* d_text, u64 text_cap,
                 ntedit_hip_reads_parse_result* res)
 {
+	ParseKeep& keep = st->keep;
+	ParseScratch* s = &st->scr;
 	*res = ntedit_hip_reads_parse_result();
 	if (n == 0) {
 		res->clean = 1;
@@ -872,34 +874,16 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 		res->broken = RP_BAD_SIZE;
 		return 0;
 	}
-	const bool need_qsum = s->filter.min_mean_qual != 0;
-	if (n > s->table_raw || !s->d_table || (need_qsum && !s->table_qsum)) {
-		const u64 want = n > s->table_raw ? n + (1u << 20) : s->table_raw;
-		if (s->d_table) {
-			RP_TRY(c, hipStreamSynchronize(s->stream));
-			RP_TRY(c, hipFree(s->d_table));
-			s->d_table = nullptr;
-			s->table_raw = 0;
-		}
-		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want, need_qsum).bytes));
-		s->table_raw = want;
-		s->table_qsum = need_qsum;
+	// the table holds the chunk, and the quality sums when --min_mean_qual is on (they alone: the same size again)
+	const bool need_qsum = keep.filter.min_mean_qual != 0;
+	Lines l;
+	int rc = line_table(c, s, d_raw, n, n <= s->table_raw && (!need_qsum || s->table_qsum), n > s->table_raw ? n + (1u << 20) : s->table_raw,
+	                    need_qsum, &keep.info.ms_kernels, &l);
+	if (rc) {
+		return rc;
 	}
-	const Table t = carve(s->d_table, s->table_raw, s->table_qsum);
-	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
-	RP_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
-	RP_TRY(c, hipEventRecord(s->ev[0], s->stream));
-	hipLaunchKernelGGL(k_rp_tiles, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, s->d_info);
-	scan(s, t.tile, tiles, t.bsum);
-	RP_TRY(c, hipGetLastError());
-	RP_TRY(c, hipEventRecord(s->ev[1], s->stream));
-	RP_TRY(c, hipMemcpyAsync(&s->h_info->newlines, t.tile + tiles, 8, hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, 16, hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipStreamSynchronize(s->stream));
-	float ms = 0;
-	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-	s->info.ms_kernels += ms;
-	const u64 lines = s->h_info->newlines + (s->h_info->last_nl ? 0 : 1);
+	const Table& t = l.t;
+	const u64 tiles = l.tiles, lines = l.lines;
 	res->kind = (int)s->h_info->kind;
 	res->lines = lines;
 	// what is known by now ends the chunk here: over the table's bound nothing more may run
@@ -908,19 +892,19 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 		return 0;
 	}
 	const unsigned line_blocks = (unsigned)((lines + RP_TPB - 1) / RP_TPB);
-	RP_TRY(c, hipEventRecord(s->ev[2], s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[2], s->stream));
 	hipLaunchKernelGGL(k_rp_line_ends, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, lines, s->d_info);
 	hipLaunchKernelGGL(k_rp_classify, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, d_raw, n, t.line_end, lines, t.cls, t.sr, s->d_info);
 	scan(s, t.sr, lines, t.bsum);
 	hipLaunchKernelGGL(k_rp_heads, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, lines, t.head_line);
-	if (rp_filter_on(s->filter)) {
+	if (rp_filter_on(keep.filter)) {
 		// (rq is the BAM unit's; a FASTA chunk has no qualities: the length rule alone, and no sums)
-		const bool sums = s->filter.min_mean_qual && res->kind == '@';
+		const bool sums = keep.filter.min_mean_qual && res->kind == '@';
 		if (sums) {
-			RP_TRY(c, hipMemsetAsync(t.qsum, 0, lines * 8, s->stream));
+			NTE_TRY(c, hipMemsetAsync(t.qsum, 0, lines * 8, s->stream));
 			hipLaunchKernelGGL(k_rp_qsum, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, lines, t.qsum);
 		}
-		hipLaunchKernelGGL(k_rp_records<true>, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.sr, t.head_line, lines, k, t.rec, s->filter,
+		hipLaunchKernelGGL(k_rp_records<true>, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.sr, t.head_line, lines, k, t.rec, keep.filter,
 		                   sums ? t.qsum : nullptr, s->d_info);
 	} else {
 		hipLaunchKernelGGL(k_rp_records<false>, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.sr, t.head_line, lines, k, t.rec,
@@ -929,28 +913,23 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 	scan(s, t.rec, lines, t.bsum);
 	hipLaunchKernelGGL(k_rp_line_out, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, t.cls, t.sr, t.head_line, t.rec, lines, t.line_out,
 	                   d_text, text_cap, s->d_info);
-	if (s->min_qual && res->kind == '@') { // (a FASTA chunk has no qualities: the copy without the mask)
+	if (keep.min_qual && res->kind == '@') { // (a FASTA chunk has no qualities: the copy without the mask)
 		hipLaunchKernelGGL(k_rp_copy<true>, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out,
-		                   lines, d_text, text_cap, s->min_qual, s->d_info);
+		                   lines, d_text, text_cap, keep.min_qual, s->d_info);
 	} else {
 		hipLaunchKernelGGL(k_rp_copy<false>, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out,
 		                   lines, d_text, text_cap, 0u, s->d_info);
 	}
-	RP_TRY(c, hipGetLastError());
-	RP_TRY(c, hipEventRecord(s->ev[3], s->stream));
-	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(RpInfo), hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipStreamSynchronize(s->stream));
-	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-	s->info.ms_kernels += ms;
+	if ((rc = finish(c, s, &keep.info.ms_kernels)) != 0) {
+		return rc;
+	}
 	res->broken = s->h_info->broken;
 	if (res->broken) {
 		return 0;
 	}
-	s->qual_bases += s->h_info->qual_bases; // (zero without --min_qual: the chunk's info is zeroed, and only the mask adds)
-	s->masked_bases += s->h_info->masked_bases;
-	s->fcounts.records += s->h_info->filter.records; // (zero without a read filter, alike)
-	s->fcounts.by_length += s->h_info->filter.by_length;
-	s->fcounts.by_mean_qual += s->h_info->filter.by_mean_qual;
+	keep.qual_bases += s->h_info->qual_bases; // (zero without --min_qual: the chunk's info is zeroed, and only the mask adds)
+	keep.masked_bases += s->h_info->masked_bases;
+	rp_counts_add(&keep.fcounts, s->h_info->filter); // (zero without a read filter, alike; by_rq and the aux counts are the BAM unit's: zero here)
 	res->clean = 1;
 	res->text_len = lo32(s->h_info->records);
 	res->reads = hi32(s->h_info->records);
@@ -960,9 +939,11 @@ parse_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, 
 
 // one genome chunk of device bytes: the line table as parse_on_device builds it, then the genome phases
 int
-genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n, int state_in, int first_chunk, u8* d_text, u64 text_cap,
+genome_on_device(const ntedit_hip_ctx* c, ParseState* st, const u8* d_raw, u64 n, int state_in, int first_chunk, u8* d_text, u64 text_cap,
                  ntedit_hip_genome_parse_result* res)
 {
+	ParseKeep& keep = st->keep;
+	ParseScratch* s = &st->scr;
 	*res = ntedit_hip_genome_parse_result();
 	res->last_header = NTEDIT_READS_NO_START;
 	res->state_out = state_in;
@@ -975,32 +956,14 @@ genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n,
 		res->state_out = 0;
 		return 0;
 	}
-	if (n + GP_TABLE_SLACK > s->table_raw || !s->d_table) { // (the table holds what gp_stops lets through)
-		const u64 want = n + 2 * GP_TABLE_SLACK;
-		if (s->d_table) {
-			RP_TRY(c, hipFree(s->d_table));
-			s->d_table = nullptr;
-			s->table_raw = 0;
-		}
-		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
-		s->table_raw = want;
-		s->table_qsum = false;
+	Lines l;
+	int rc = line_table(c, s, d_raw, n, n + GP_TABLE_SLACK <= s->table_raw, n + 2 * GP_TABLE_SLACK, false, &keep.ginfo.ms_kernels,
+	                    &l); // (the table holds what gp_stops lets through)
+	if (rc) {
+		return rc;
 	}
-	const Table t = carve(s->d_table, s->table_raw);
-	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
-	RP_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
-	RP_TRY(c, hipEventRecord(s->ev[0], s->stream));
-	hipLaunchKernelGGL(k_rp_tiles, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, s->d_info);
-	scan(s, t.tile, tiles, t.bsum);
-	RP_TRY(c, hipGetLastError());
-	RP_TRY(c, hipEventRecord(s->ev[1], s->stream));
-	RP_TRY(c, hipMemcpyAsync(&s->h_info->newlines, t.tile + tiles, 8, hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, 16, hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipStreamSynchronize(s->stream));
-	float ms = 0;
-	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-	s->ginfo.ms_kernels += ms;
-	const u64 lines = s->h_info->newlines + (s->h_info->last_nl ? 0 : 1);
+	const Table& t = l.t;
+	const u64 tiles = l.tiles, lines = l.lines;
 	// over the table's bound nothing more may run
 	if (gp_stops(n, lines)) {
 		res->broken = gp_chunk_broken(0, 0, n, lines);
@@ -1009,7 +972,7 @@ genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n,
 		return 0;
 	}
 	const unsigned line_blocks = (unsigned)((lines + RP_TPB - 1) / RP_TPB);
-	RP_TRY(c, hipEventRecord(s->ev[2], s->stream));
+	NTE_TRY(c, hipEventRecord(s->ev[2], s->stream));
 	hipLaunchKernelGGL(k_rp_line_ends, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, lines, s->d_info);
 	hipLaunchKernelGGL(k_gp_classify, dim3(line_blocks), dim3(RP_TPB), 0, s->stream, d_raw, n, t.line_end, lines, state_in, first_chunk,
 	                   t.cls, t.sr, s->d_info);
@@ -1018,12 +981,9 @@ genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n,
 	                   s->d_info);
 	hipLaunchKernelGGL(k_rp_copy<false>, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, t.line_out,
 	                   lines, d_text, text_cap, 0u, s->d_info); // (a genome is never masked)
-	RP_TRY(c, hipGetLastError());
-	RP_TRY(c, hipEventRecord(s->ev[3], s->stream));
-	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, sizeof(RpInfo), hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipStreamSynchronize(s->stream));
-	RP_TRY(c, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-	s->ginfo.ms_kernels += ms;
+	if ((rc = finish(c, s, &keep.ginfo.ms_kernels)) != 0) {
+		return rc;
+	}
 	res->broken = s->h_info->broken;
 	res->clean = res->broken == 0;
 	res->state_out = (int)s->h_info->state_out;
@@ -1034,125 +994,117 @@ genome_on_device(const ntedit_hip_ctx* c, ParseState* s, const u8* d_raw, u64 n,
 	return 0;
 }
 
+// raw as a *_parse_device call gives it: device bytes as they are, host bytes through raw buffer 0, copied on the stream
+int
+stage(const ntedit_hip_ctx* c, ParseState** state, const char* raw, u64 n_raw, int on_device, const u8** d_raw)
+{
+	const bool host = on_device == NTEDIT_HIP_BASES_HOST && n_raw;
+	const int rc = ready(c, state, host ? BUF_RAW0 : NO_BUF, n_raw);
+	if (rc) {
+		return rc;
+	}
+	*d_raw = (const u8*)raw;
+	if (host) {
+		ParseScratch* s = &(*state)->scr;
+		NTE_TRY(c, hipMemcpyAsync(s->buf[BUF_RAW0].p, raw, n_raw, hipMemcpyHostToDevice, s->stream));
+		*d_raw = s->buf[BUF_RAW0].p;
+	}
+	return 0;
+}
+
 } // namespace
 
-// what the pass loop of reads_pass.cpp needs beyond the public calls: the two raw buffers and the copy stream
+// what the other units and the pass loops need beyond the public calls (nte_reads_internal.h says what each does)
 namespace nte_reads {
 
 void
 parse_release(const ntedit_hip_ctx* c)
 {
 	inflate_release(c);
-	ParseState* s = parse_state(c, false);
+	ParseState* s = g_parse.find(c, false);
 	if (s) {
-		release_scratch(s);
+		release_scratch(&s->scr);
 	}
 }
 
-// the inflate unit (nte_reads_inflate.hip) works on this unit's two streams ...
 int
 parse_streams(const ntedit_hip_ctx* c, void** stream, void** copy_stream)
 {
-	ParseState* s = parse_state(c, true);
-	const int rc = ensure_device(c, s);
+	ParseState* s;
+	const int rc = ready(c, &s);
 	if (rc == 0) {
-		*stream = (void*)s->stream;
-		*copy_stream = (void*)s->copy_stream;
+		*stream = (void*)s->scr.stream;
+		*copy_stream = (void*)s->scr.copy_stream;
 	}
 	return rc;
 }
 
-// ... cuts a chunk on the line table: the first phases of parse_on_device over device bytes, queued on the stream.
-// *broken: RP_BAD_SIZE / RP_BAD_TABLE when the table cannot hold the chunk (nothing is queued then).
 int
 parse_lines(const ntedit_hip_ctx* c, const unsigned char* d_raw, uint64_t n, const uint32_t** line_end, uint64_t* n_lines,
             uint32_t* broken)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
+	ParseState* st;
+	int rc = ready(c, &st);
 	if (rc) {
 		return rc;
 	}
+	ParseScratch* s = &st->scr;
 	*line_end = nullptr;
 	*n_lines = 0;
 	*broken = n >= RP_MAX_RAW ? (uint32_t)RP_BAD_SIZE : 0u;
 	if (n == 0 || *broken) {
 		return 0;
 	}
-	if (n > s->table_raw || !s->d_table) {
-		const u64 want = n + (1u << 20);
-		if (s->d_table) {
-			RP_TRY(c, hipFree(s->d_table));
-			s->d_table = nullptr;
-			s->table_raw = 0;
-		}
-		RP_TRY(c, hipMalloc((void**)&s->d_table, carve(nullptr, want).bytes));
-		s->table_raw = want;
-		s->table_qsum = false;
+	// (no time is added: the caller's event pair has these kernels inside, inflate_last_start)
+	Lines l;
+	if ((rc = line_table(c, s, d_raw, n, n <= s->table_raw, n + (1u << 20), false, nullptr, &l)) != 0) {
+		return rc;
 	}
-	const Table t = carve(s->d_table, s->table_raw);
-	const u64 tiles = (n + RP_TILE - 1) / RP_TILE;
-	RP_TRY(c, hipMemsetAsync(s->d_info, 0, sizeof(RpInfo), s->stream));
-	hipLaunchKernelGGL(k_rp_tiles, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, s->d_info);
-	scan(s, t.tile, tiles, t.bsum);
-	RP_TRY(c, hipGetLastError());
-	RP_TRY(c, hipMemcpyAsync(&s->h_info->newlines, t.tile + tiles, 8, hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipMemcpyAsync(s->h_info, s->d_info, 16, hipMemcpyDeviceToHost, s->stream));
-	RP_TRY(c, hipStreamSynchronize(s->stream));
-	const u64 lines = s->h_info->newlines + (s->h_info->last_nl ? 0 : 1);
-	if (lines > rp_max_lines(n)) {
+	if (l.lines > rp_max_lines(n)) {
 		*broken = RP_BAD_TABLE;
 		return 0;
 	}
-	hipLaunchKernelGGL(k_rp_line_ends, dim3((unsigned)tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, t.tile, t.line_end, lines, s->d_info);
-	RP_TRY(c, hipGetLastError());
-	*line_end = t.line_end;
-	*n_lines = lines;
+	hipLaunchKernelGGL(k_rp_line_ends, dim3((unsigned)l.tiles), dim3(RP_TPB), 0, s->stream, d_raw, n, l.t.tile, l.t.line_end, l.lines,
+	                   s->d_info);
+	NTE_TRY(c, hipGetLastError());
+	*line_end = l.t.line_end;
+	*n_lines = l.lines;
 	return 0;
 }
 
-// ... and has device bytes parsed into the context's text buffer, as parse_copied does for a copied chunk
 int
 parse_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
-	if (rc == 0) {
-		rc = grow(c, &s->d_text, &s->text_cap, n);
-	}
+	ParseState* s;
+	const int rc = ready(c, &s, BUF_TEXT, n);
 	if (rc) {
 		return rc;
 	}
-	*text = (const char*)s->d_text;
-	return parse_on_device(c, s, (const u8*)d_raw, n, k, s->d_text, s->text_cap, res);
+	const DevBuf& t = s->scr.buf[BUF_TEXT];
+	*text = (const char*)t.p;
+	return parse_on_device(c, s, (const u8*)d_raw, n, k, t.p, t.cap, res);
 }
 
-// the BAM unit (nte_reads_bam.hip) decodes into the same text buffer: room for a chunk of n raw bytes
 int
 parse_text_buffer(const ntedit_hip_ctx* c, uint64_t n, char** text, uint64_t* cap)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
-	if (rc == 0) {
-		rc = grow(c, &s->d_text, &s->text_cap, n);
-	}
+	ParseState* s;
+	const int rc = ready(c, &s, BUF_TEXT, n);
 	if (rc) {
 		return rc;
 	}
-	*text = (char*)s->d_text;
-	*cap = s->text_cap;
+	*text = (char*)s->scr.buf[BUF_TEXT].p;
+	*cap = s->scr.buf[BUF_TEXT].cap;
 	return 0;
 }
 
 // ------------------------------------------------------------------ what genome_pass.cpp needs
-// The pass's text buffer: GP_PAD bytes that end with the last k - 1 text bytes of the file so far ('\n' before them),
-// then the chunk's text; the whole is one device batch for ntedit_hip_filter_insert.
-constexpr u64 GP_PAD = 256;
+constexpr u64 GP_PAD = 256; // genome_pad()
 
 ntedit_hip_genome_pass_info*
 genome_info(const ntedit_hip_ctx* c)
 {
-	return &parse_state(c, true)->ginfo;
+	return &g_parse.find(c, true)->keep.ginfo;
 }
 
 int
@@ -1161,58 +1113,50 @@ genome_pad(void)
 	return (int)GP_PAD;
 }
 
-// a file begins: nothing is carried
 int
 genome_begin_file(const ntedit_hip_ctx* c)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
-	if (rc == 0) {
-		rc = grow(c, &s->d_gtext, &s->gtext_cap, GP_PAD);
-	}
+	ParseState* st;
+	const int rc = ready(c, &st, BUF_GTEXT, GP_PAD);
 	if (rc) {
 		return rc;
 	}
+	ParseScratch* s = &st->scr;
 	if (!s->d_gstage) {
-		RP_TRY(c, hipMalloc((void**)&s->d_gstage, GP_PAD));
+		NTE_TRY(c, hipMalloc((void**)&s->d_gstage, GP_PAD));
 	}
-	RP_TRY(c, hipMemsetAsync(s->d_gtext, '\n', GP_PAD, s->stream));
-	RP_TRY(c, hipStreamSynchronize(s->stream));
+	NTE_TRY(c, hipMemsetAsync(s->buf[BUF_GTEXT].p, '\n', GP_PAD, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
 	return 0;
 }
 
-// raw buffer `which` with room for n bytes (a BGZF chunk is inflated into it)
 int
 genome_raw_buffer(const ntedit_hip_ctx* c, int which, uint64_t n, char** d_raw)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
-	if (rc == 0) {
-		rc = grow(c, &s->d_raw[which], &s->raw_cap[which], n);
-	}
-	*d_raw = rc ? nullptr : (char*)s->d_raw[which];
+	ParseState* s;
+	const int rc = ready(c, &s, BUF_RAW0 + which, n);
+	*d_raw = rc ? nullptr : (char*)s->scr.buf[BUF_RAW0 + which].p;
 	return rc;
 }
 
-// raw buffer `which` (copied: after parse_copy_begin, waits for that copy) parsed behind the pad; *batch: the pad's first
-// byte, the text is at *batch + genome_pad()
 int
 genome_parse_buffer(const ntedit_hip_ctx* c, int which, int copied, uint64_t n, int state_in, int first_chunk, const char** batch,
                     ntedit_hip_genome_parse_result* res)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
+	ParseState* st;
+	int rc = ready(c, &st);
 	if (rc) {
 		return rc;
 	}
-	if (GP_PAD + n > s->gtext_cap || !s->d_gtext) {
-		// (grow frees: the pad moves with a copy through the stage)
-		u8* old = s->d_gtext;
-		s->d_gtext = nullptr;
-		s->gtext_cap = 0;
-		rc = grow(c, &s->d_gtext, &s->gtext_cap, GP_PAD + n);
+	ParseScratch* s = &st->scr;
+	DevBuf& gtext = s->buf[BUF_GTEXT];
+	if (GP_PAD + n > gtext.cap || !gtext.p) {
+		// (grow would free it: the pad moves to the new buffer with a synchronous copy, and the old one goes after it)
+		u8* old = gtext.p;
+		gtext = DevBuf();
+		rc = grow(c, s->stream, &gtext, GP_PAD + n, buf_want(GP_PAD + n), 0, RP_TILE);
 		if (rc == 0 && old) {
-			RP_TRY(c, hipMemcpy(s->d_gtext, old, GP_PAD, hipMemcpyDeviceToDevice));
+			NTE_TRY(c, hipMemcpy(gtext.p, old, GP_PAD, hipMemcpyDeviceToDevice));
 		}
 		if (old) {
 			(void)hipFree(old);
@@ -1222,26 +1166,27 @@ genome_parse_buffer(const ntedit_hip_ctx* c, int which, int copied, uint64_t n, 
 		}
 	}
 	if (copied) {
-		RP_TRY(c, hipEventSynchronize(s->copied[which]));
+		NTE_TRY(c, hipEventSynchronize(s->copied[which]));
 	}
-	*batch = (const char*)s->d_gtext;
-	return genome_on_device(c, s, s->d_raw[which], n, state_in, first_chunk, s->d_gtext + GP_PAD, s->gtext_cap - GP_PAD, res);
+	*batch = (const char*)gtext.p;
+	return genome_on_device(c, st, s->buf[BUF_RAW0 + which].p, n, state_in, first_chunk, gtext.p + GP_PAD, gtext.cap - GP_PAD, res);
 }
 
-// the chunk's text is inserted: the pad becomes the last `keep` (< GP_PAD) bytes of pad + text, '\n' before them
 int
 genome_carry(const ntedit_hip_ctx* c, uint64_t text_len, uint32_t keep)
 {
-	ParseState* s = parse_state(c, false);
-	if (!s || !s->d_gtext || keep >= GP_PAD) {
+	ParseState* st = g_parse.find(c, false);
+	if (!st || !st->scr.buf[BUF_GTEXT].p || keep >= GP_PAD) {
 		return pfail(c, NTEDIT_E_ARG, "genome_carry: bad argument");
 	}
+	ParseScratch* s = &st->scr;
+	u8* d_gtext = s->buf[BUF_GTEXT].p;
 	if (text_len) {
-		RP_TRY(c, hipMemcpyAsync(s->d_gstage, s->d_gtext + text_len, GP_PAD, hipMemcpyDeviceToDevice, s->stream));
-		RP_TRY(c, hipMemcpyAsync(s->d_gtext, s->d_gstage, GP_PAD, hipMemcpyDeviceToDevice, s->stream));
+		NTE_TRY(c, hipMemcpyAsync(s->d_gstage, d_gtext + text_len, GP_PAD, hipMemcpyDeviceToDevice, s->stream));
+		NTE_TRY(c, hipMemcpyAsync(d_gtext, s->d_gstage, GP_PAD, hipMemcpyDeviceToDevice, s->stream));
 	}
-	RP_TRY(c, hipMemsetAsync(s->d_gtext, '\n', GP_PAD - keep, s->stream));
-	RP_TRY(c, hipStreamSynchronize(s->stream));
+	NTE_TRY(c, hipMemsetAsync(d_gtext, '\n', GP_PAD - keep, s->stream));
+	NTE_TRY(c, hipStreamSynchronize(s->stream));
 	return 0;
 }
 
@@ -1255,7 +1200,7 @@ ntedit_hip_genome_pass_get_info(ntedit_hip_ctx* c, ntedit_hip_genome_pass_info* 
 	if (!c || !info) {
 		return c ? pfail(c, NTEDIT_E_ARG, "genome_pass_get_info: bad argument") : NTEDIT_E_ARG;
 	}
-	*info = parse_state(c, true)->ginfo;
+	*info = g_parse.find(c, true)->keep.ginfo;
 	return 0;
 }
 
@@ -1273,18 +1218,11 @@ ntedit_hip_genome_parse_device(ntedit_hip_ctx* c, const char* raw, uint64_t n_ra
 	if (text_cap < n_raw) {
 		return pfail(c, NTEDIT_E_ARG, "genome_parse_device: text_cap must be at least n_raw (the text is never longer than the raw bytes)");
 	}
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
+	ParseState* s;
+	const u8* d_raw = nullptr;
+	const int rc = stage(c, &s, raw, n_raw, on_device, &d_raw);
 	if (rc) {
 		return rc;
-	}
-	const u8* d_raw = (const u8*)raw;
-	if (on_device == NTEDIT_HIP_BASES_HOST && n_raw) {
-		if ((rc = grow(c, &s->d_raw[0], &s->raw_cap[0], n_raw)) != 0) {
-			return rc;
-		}
-		RP_TRY(c, hipMemcpyAsync(s->d_raw[0], raw, n_raw, hipMemcpyHostToDevice, s->stream));
-		d_raw = s->d_raw[0];
 	}
 	return genome_on_device(c, s, d_raw, n_raw, state_in, first_chunk != 0, (u8*)text_device, text_cap, res);
 }
@@ -1314,109 +1252,94 @@ ntedit_hip_genome_parse_model(const char* raw, uint64_t n_raw, int state_in, int
 
 namespace nte_reads {
 
-// --min_qual: the context's setting, and the counts of the last pass (the pass zeroes them; the host parser and the BAM
-// unit add theirs)
 uint32_t
 min_qual(const ntedit_hip_ctx* c)
 {
-	ParseState* s = parse_state(c, false);
-	return s ? s->min_qual : 0;
+	ParseState* s = g_parse.find(c, false);
+	return s ? s->keep.min_qual : 0;
 }
 
 void
 min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases)
 {
-	ParseState* s = parse_state(c, true);
+	ParseKeep& keep = g_parse.find(c, true)->keep;
 	if (reset) {
-		s->qual_bases = s->masked_bases = 0;
+		keep.qual_bases = keep.masked_bases = 0;
 	}
-	s->qual_bases += qual_bases;
-	s->masked_bases += masked_bases;
+	keep.qual_bases += qual_bases;
+	keep.masked_bases += masked_bases;
 }
 
-// --min_read_len, --min_mean_qual, --min_rq: the context's setting, and what the last pass's records came to (the pass
-// zeroes the counts; the host parser and the BAM unit add theirs)
 ReadFilter
 read_filter(const ntedit_hip_ctx* c)
 {
-	ParseState* s = parse_state(c, false);
-	return s ? s->filter : ReadFilter();
+	ParseState* s = g_parse.find(c, false);
+	return s ? s->keep.filter : ReadFilter();
 }
 
 void
 read_filter_count(const ntedit_hip_ctx* c, int reset, const ReadFilterCounts* add)
 {
-	ParseState* s = parse_state(c, true);
+	ParseKeep& keep = g_parse.find(c, true)->keep;
 	if (reset) {
-		s->fcounts = ReadFilterCounts();
+		keep.fcounts = ReadFilterCounts();
 	}
 	if (add) {
-		s->fcounts.records += add->records;
-		s->fcounts.by_length += add->by_length;
-		s->fcounts.by_rq += add->by_rq;
-		s->fcounts.by_mean_qual += add->by_mean_qual;
-		s->fcounts.rq_tagged += add->rq_tagged;
-		s->fcounts.aux_malformed += add->aux_malformed;
+		rp_counts_add(&keep.fcounts, *add);
 	}
 }
 
 int
 parse_is_on(const ntedit_hip_ctx* c)
 {
-	ParseState* s = parse_state(c, false);
-	return s ? s->on : 0;
+	ParseState* s = g_parse.find(c, false);
+	return s ? s->keep.on : 0;
 }
 
 ntedit_hip_reads_parse_stats*
 parse_info(const ntedit_hip_ctx* c)
 {
-	return &parse_state(c, true)->info;
+	return &g_parse.find(c, true)->keep.info;
 }
 
-// host chunk -> raw buffer `which`, on the copy stream; returns at once
 int
 parse_copy_begin(const ntedit_hip_ctx* c, int which, const char* host, uint64_t n)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
-	if (rc == 0) {
-		rc = grow(c, &s->d_raw[which], &s->raw_cap[which], n);
-	}
+	ParseState* st;
+	const int rc = ready(c, &st, BUF_RAW0 + which, n);
 	if (rc) {
 		return rc;
 	}
+	ParseScratch* s = &st->scr;
 	if (n) {
-		RP_TRY(c, hipMemcpyAsync(s->d_raw[which], host, n, hipMemcpyHostToDevice, s->copy_stream));
+		NTE_TRY(c, hipMemcpyAsync(s->buf[BUF_RAW0 + which].p, host, n, hipMemcpyHostToDevice, s->copy_stream));
 	}
-	RP_TRY(c, hipEventRecord(s->copied[which], s->copy_stream));
+	NTE_TRY(c, hipEventRecord(s->copied[which], s->copy_stream));
 	return 0;
 }
 
 int
 parse_copy_wait(const ntedit_hip_ctx* c, int which)
 {
-	ParseState* s = parse_state(c, false);
-	if (s && s->copied[which]) {
-		RP_TRY(c, hipEventSynchronize(s->copied[which]));
+	ParseState* s = g_parse.find(c, false);
+	if (s && s->scr.copied[which]) {
+		NTE_TRY(c, hipEventSynchronize(s->scr.copied[which]));
 	}
 	return 0;
 }
 
-// waits for that copy, then parses the buffer into the context's text buffer (*text: where, 16-byte aligned)
 int
 parse_copied(const ntedit_hip_ctx* c, int which, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res)
 {
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
-	if (rc == 0) {
-		rc = grow(c, &s->d_text, &s->text_cap, n);
-	}
+	ParseState* s;
+	const int rc = ready(c, &s, BUF_TEXT, n);
 	if (rc) {
 		return rc;
 	}
-	RP_TRY(c, hipEventSynchronize(s->copied[which]));
-	*text = (const char*)s->d_text;
-	return parse_on_device(c, s, s->d_raw[which], n, k, s->d_text, s->text_cap, res);
+	NTE_TRY(c, hipEventSynchronize(s->scr.copied[which]));
+	const DevBuf& t = s->scr.buf[BUF_TEXT];
+	*text = (const char*)t.p;
+	return parse_on_device(c, s, s->scr.buf[BUF_RAW0 + which].p, n, k, t.p, t.cap, res);
 }
 
 } // namespace nte_reads
@@ -1429,7 +1352,7 @@ ntedit_hip_reads_set_device_parse(ntedit_hip_ctx* c, int on)
 	if (!c) {
 		return NTEDIT_E_ARG;
 	}
-	parse_state(c, true)->on = on ? 1 : 0;
+	g_parse.find(c, true)->keep.on = on ? 1 : 0;
 	return 0;
 }
 
@@ -1439,7 +1362,7 @@ ntedit_hip_reads_set_min_qual(ntedit_hip_ctx* c, uint32_t q)
 	if (!c || q > RP_MAX_MIN_QUAL) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_set_min_qual: the minimum base quality is 0 (off) or between 1 and 93") : NTEDIT_E_ARG;
 	}
-	parse_state(c, true)->min_qual = q;
+	g_parse.find(c, true)->keep.min_qual = q;
 	return 0;
 }
 
@@ -1449,26 +1372,22 @@ ntedit_hip_reads_min_qual_info(ntedit_hip_ctx* c, uint64_t* qual_bases, uint64_t
 	if (!c || !qual_bases || !masked_bases) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_min_qual_info: bad argument") : NTEDIT_E_ARG;
 	}
-	ParseState* s = parse_state(c, true);
-	*qual_bases = s->qual_bases;
-	*masked_bases = s->masked_bases;
+	const ParseKeep& keep = g_parse.find(c, true)->keep;
+	*qual_bases = keep.qual_bases;
+	*masked_bases = keep.masked_bases;
 	return 0;
 }
 
 int
 ntedit_hip_reads_set_read_filter(ntedit_hip_ctx* c, uint32_t min_len, uint32_t min_mean_qual, float min_rq)
 {
-	// (written so that a NaN is refused)
-	if (!c || min_len > RP_MAX_MIN_READ_LEN || min_mean_qual > RP_MAX_MEAN_QUAL || !(min_rq >= 0.0f && min_rq <= 1.0f)) {
+	ReadFilter f = ReadFilter();
+	if (!c || !rp_make_filter(min_len, min_mean_qual, min_rq, &f)) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_set_read_filter: the minimum read length is 0 (off) or up to 2^31 - 1, the minimum mean "
 		                                  "quality 0 (off) or between 1 and 60, the minimum rq 0 (off) or above 0 and at most 1")
 		         : NTEDIT_E_ARG;
 	}
-	ReadFilter f = ReadFilter();
-	f.min_len = min_len;
-	f.min_mean_qual = min_mean_qual;
-	f.rq_bits = rp_rq_bits(min_rq);
-	parse_state(c, true)->filter = f;
+	g_parse.find(c, true)->keep.filter = f;
 	return 0;
 }
 
@@ -1478,7 +1397,7 @@ ntedit_hip_reads_get_read_filter(ntedit_hip_ctx* c, uint32_t* min_len, uint32_t*
 	if (!c || !min_len || !min_mean_qual || !min_rq) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_get_read_filter: bad argument") : NTEDIT_E_ARG;
 	}
-	const ReadFilter f = parse_state(c, true)->filter;
+	const ReadFilter f = g_parse.find(c, true)->keep.filter;
 	*min_len = f.min_len;
 	*min_mean_qual = f.min_mean_qual;
 	memcpy(min_rq, &f.rq_bits, 4);
@@ -1492,7 +1411,7 @@ ntedit_hip_reads_read_filter_info(ntedit_hip_ctx* c, ntedit_hip_reads_read_filte
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_read_filter_info: bad argument") : NTEDIT_E_ARG;
 	}
 	static_assert(sizeof(ntedit_hip_reads_read_filter_stats) == sizeof(ReadFilterCounts), "the counts are the grammar's, field for field");
-	memcpy(st, &parse_state(c, true)->fcounts, sizeof *st);
+	memcpy(st, &g_parse.find(c, true)->keep.fcounts, sizeof *st);
 	return 0;
 }
 
@@ -1502,7 +1421,7 @@ ntedit_hip_reads_parse_info(ntedit_hip_ctx* c, ntedit_hip_reads_parse_stats* st)
 	if (!c || !st) {
 		return c ? pfail(c, NTEDIT_E_ARG, "reads_parse_info: bad argument") : NTEDIT_E_ARG;
 	}
-	*st = parse_state(c, true)->info;
+	*st = g_parse.find(c, true)->keep.info;
 	return 0;
 }
 
@@ -1520,18 +1439,11 @@ ntedit_hip_reads_parse_device(ntedit_hip_ctx* c, const char* raw, uint64_t n_raw
 	if (text_cap < n_raw) {
 		return pfail(c, NTEDIT_E_ARG, "reads_parse_device: text_cap must be at least n_raw (the text is never longer than the raw bytes)");
 	}
-	ParseState* s = parse_state(c, true);
-	int rc = ensure_device(c, s);
+	ParseState* s;
+	const u8* d_raw = nullptr;
+	const int rc = stage(c, &s, raw, n_raw, on_device, &d_raw);
 	if (rc) {
 		return rc;
-	}
-	const u8* d_raw = (const u8*)raw;
-	if (on_device == NTEDIT_HIP_BASES_HOST && n_raw) {
-		if ((rc = grow(c, &s->d_raw[0], &s->raw_cap[0], n_raw)) != 0) {
-			return rc;
-		}
-		RP_TRY(c, hipMemcpyAsync(s->d_raw[0], raw, n_raw, hipMemcpyHostToDevice, s->stream));
-		d_raw = s->d_raw[0];
 	}
 	return parse_on_device(c, s, d_raw, n_raw, k, (u8*)text_device, text_cap, res);
 }
@@ -1558,14 +1470,10 @@ ntedit_hip_reads_parse_model_f(const char* raw, uint64_t n_raw, uint32_t k, uint
                                float min_rq, char* out, uint64_t cap, ntedit_hip_reads_parse_result* res,
                                ntedit_hip_reads_read_filter_stats* st)
 {
-	if (!res || (n_raw && !raw) || (cap && !out) || k == 0 || min_qual > RP_MAX_MIN_QUAL || min_len > RP_MAX_MIN_READ_LEN ||
-	    min_mean_qual > RP_MAX_MEAN_QUAL || !(min_rq >= 0.0f && min_rq <= 1.0f)) {
+	ReadFilter f = ReadFilter();
+	if (!res || (n_raw && !raw) || (cap && !out) || k == 0 || min_qual > RP_MAX_MIN_QUAL || !rp_make_filter(min_len, min_mean_qual, min_rq, &f)) {
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_parse_model: bad argument");
 	}
-	ReadFilter f = ReadFilter();
-	f.min_len = min_len;
-	f.min_mean_qual = min_mean_qual;
-	f.rq_bits = rp_rq_bits(min_rq);
 	RpResult m;
 	ReadFilterCounts fc = ReadFilterCounts();
 	const bool fits = rp_model_f(raw, n_raw, k, min_qual, f, out, cap, &m, &fc);

@@ -15,7 +15,7 @@
 //                 such a file again from its start, so that no base is counted twice
 //   host files    single-stream .gz files and files that do not start with '>' take the host parser whole, and with
 //                 batch_bytes 0 every file does (the pass without --gpu_parse)
-#include "../../include/ntedit_hip.h"
+#include "../csrc/nte_reads_internal.h"
 #include "chunk_feed.h"
 #include "fasta.h"
 
@@ -26,21 +26,6 @@
 #include <vector>
 
 #include <sys/stat.h>
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-const char* inflate_reason(uint32_t st);
-int parse_copy_begin(const ntedit_hip_ctx* c, int which, const char* host, uint64_t n);
-int parse_copy_wait(const ntedit_hip_ctx* c, int which);
-// the genome chunks of nte_reads_parse.hip
-ntedit_hip_genome_pass_info* genome_info(const ntedit_hip_ctx* c);
-int genome_pad(void);
-int genome_begin_file(const ntedit_hip_ctx* c);
-int genome_raw_buffer(const ntedit_hip_ctx* c, int which, uint64_t n, char** d_raw);
-int genome_parse_buffer(const ntedit_hip_ctx* c, int which, int copied, uint64_t n, int state_in, int first_chunk, const char** batch,
-                        ntedit_hip_genome_parse_result* res);
-int genome_carry(const ntedit_hip_ctx* c, uint64_t text_len, uint32_t keep);
-}
 
 namespace {
 

@@ -2,17 +2,13 @@
 // `ntedit --reads` run it: the sketch, pass 1, the histogram pass, the decision about cutoff and sizes, and pass 2, in four
 // stages that the tool walks in one call (ntedit_hip_reads_build) and the driver one by one with its merges in between; the
 // build's console lines; and the --hist writer.  The passes themselves are ntedit_hip_reads_pass (reads_pass.cpp).
-#include "../../include/ntedit_hip.h"
+#include "../csrc/nte_reads_internal.h"
 
 #include <chrono>
 #include <cstdio>
 #include <sstream>
 #include <string>
 #include <vector>
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-}
 
 namespace {
 

@@ -2,16 +2,12 @@
 // and python -m ntedit_amd.make_reads (the TOOL dialect: -c, sentences that end in a period), ntedit --reads and
 // python -m ntedit_amd.run --reads (the POLISHER dialect: --cutoff, "with --reads").  Host only.  A front end keeps how it
 // walks its arguments and what only it has; what is refused, in which order and in which words is here.
-#include "../../include/ntedit_hip.h"
+#include "../csrc/nte_reads_internal.h"
 
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-}
 
 namespace {
 

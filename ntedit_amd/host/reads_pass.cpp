@@ -12,7 +12,7 @@
 // the range started (`starts`).  Only when every range's stop is the next range's start did the ranges parse the file
 // exactly as one reader would: the driver checks that after pass 1 (multi-line FASTQ can break it).  Gzip files are
 // single units.
-#include "../../include/ntedit_hip.h"
+#include "../csrc/nte_reads_internal.h"
 #include "chunk_feed.h"
 #include "fasta.h"
 
@@ -25,39 +25,6 @@
 #include <vector>
 
 #include <sys/stat.h>
-
-namespace nte_reads {
-int set_error(const ntedit_hip_ctx* c, int code, const std::string& why);
-uint32_t reject_cutoff(const ntedit_hip_ctx* c); // ntedit_hip_reads_set_reject_cutoff (nte_reads.hip)
-uint32_t min_read(const ntedit_hip_ctx* c, uint32_t k); // ntedit_hip_reads_set_min_read: the shortest record kept, k at most
-// --gpu_parse (nte_reads_parse.hip): the context's setting and counters, its two raw buffers and its copy stream
-int parse_is_on(const ntedit_hip_ctx* c);
-ntedit_hip_reads_parse_stats* parse_info(const ntedit_hip_ctx* c);
-int parse_copy_begin(const ntedit_hip_ctx* c, int which, const char* host, uint64_t n);
-int parse_copy_wait(const ntedit_hip_ctx* c, int which);
-int parse_copied(const ntedit_hip_ctx* c, int which, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res);
-int parse_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint32_t k, const char** text, ntedit_hip_reads_parse_result* res);
-// --gpu_parse on BGZF files (nte_reads_inflate.hip): its counters, its two compressed buffers, the inflated chunk
-ntedit_hip_reads_inflate_stats* inflate_info(const ntedit_hip_ctx* c);
-const char* inflate_reason(uint32_t st);
-int inflate_copy_begin(const ntedit_hip_ctx* c, int which, const char* comp, uint64_t n_comp, const ntedit_hip_bgzf_member* members,
-                       uint64_t n_members);
-int inflate_copy_wait(const ntedit_hip_ctx* c, int which);
-int inflate_copied(const ntedit_hip_ctx* c, int which, uint64_t n_comp, const ntedit_hip_bgzf_member* members, uint64_t n_members,
-                   uint64_t tail, uint64_t n_out, const char** raw, uint64_t* bad, uint32_t* reason);
-int inflate_last_start(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, uint64_t* cut, uint32_t* broken);
-int inflate_carry(const ntedit_hip_ctx* c, uint64_t cut, uint64_t total);
-// ... and on BAM files (nte_reads_bam.hip): its counters, and the walk and decode of an inflated chunk
-ntedit_hip_reads_bam_stats* bam_info(const ntedit_hip_ctx* c);
-int bam_buffer(const ntedit_hip_ctx* c, const char* d_raw, uint64_t n, int at_header, uint32_t min_len, const char** text,
-               ntedit_hip_reads_bam_result* res);
-// --min_qual (nte_reads_parse.hip): the context's setting, which the device parsers read themselves, and the pass's counts
-uint32_t min_qual(const ntedit_hip_ctx* c);
-void min_qual_count(const ntedit_hip_ctx* c, int reset, uint64_t qual_bases, uint64_t masked_bases);
-// --min_read_len, --min_mean_qual, --min_rq (nte_reads_parse.hip): the context's setting, alike, and the pass's counts
-nte_parse::ReadFilter read_filter(const ntedit_hip_ctx* c);
-void read_filter_count(const ntedit_hip_ctx* c, int reset, const nte_parse::ReadFilterCounts* add);
-}
 
 namespace {
 
@@ -661,17 +628,15 @@ ntedit_hip_reads_range_text_f(const char* path, uint64_t begin, uint64_t end, ui
                               char* out, uint64_t cap, uint64_t* len, uint64_t* reads, uint64_t* start, uint64_t* next,
                               ntedit_hip_reads_read_filter_stats* st)
 {
+	HostRules rules;
 	if (!path || !len || !reads || !start || !next || begin > end || (cap && !out) || min_qual > 93 ||
-	    min_len > nte_parse::RP_MAX_MIN_READ_LEN || min_mean_qual > nte_parse::RP_MAX_MEAN_QUAL) {
+	    !nte_parse::rp_make_filter(min_len, min_mean_qual, 0.0f, &rules.filter)) { // (rq is a BAM field: the host parser reads none)
 		return pfail(nullptr, NTEDIT_E_ARG, "reads_range_text: bad argument");
 	}
 	uint64_t used = 0, count = 0;
 	std::string why;
 	nte_parse::ReadFilterCounts fcounts = nte_parse::ReadFilterCounts();
-	HostRules rules;
 	rules.min_qual = min_qual;
-	rules.filter.min_len = min_len;
-	rules.filter.min_mean_qual = min_mean_qual;
 	rules.counts = &fcounts;
 	static_assert(sizeof(ntedit_hip_reads_read_filter_stats) == sizeof(nte_parse::ReadFilterCounts), "field for field");
 	const bool ok = read_range(path, begin, end, rules, [&](const std::string& seq, uint64_t, uint64_t) {
