@@ -81,6 +81,171 @@ struct EventPair
 	hipEvent_t begin = nullptr, end = nullptr;
 };
 
+// A window that has been waited for, in ms: the one reader of HIP-event times for figures that are only reported: 0, and the
+// runtime's last error left clear, where the events cannot say (never recorded, or the runtime refuses).
+static float
+elapsed_ms(hipEvent_t begin, hipEvent_t end)
+{
+	float ms = 0.f;
+	if (hipEventElapsedTime(&ms, begin, end) != hipSuccess) {
+		(void)hipGetLastError();
+		return 0.f;
+	}
+	return ms;
+}
+static float elapsed_ms(const EventPair& p) { return elapsed_ms(p.begin, p.end); }
+
+namespace {
+
+int ensure(ntedit_hip_ctx* c, DevBuf& b, size_t bytes);
+
+void
+release(DevBuf& b)
+{
+	if (b.p) {
+		(void)hipFree(b.p);
+	}
+	b.p = nullptr;
+	b.cap = 0;
+}
+
+void
+destroy_event(hipEvent_t e)
+{
+	if (e) {
+		(void)hipEventDestroy(e);
+	}
+}
+
+void
+destroy_event(const EventPair& p)
+{
+	destroy_event(p.begin);
+	destroy_event(p.end);
+}
+
+void
+release_all(std::initializer_list<DevBuf*> bufs, std::initializer_list<const EventPair*> windows)
+{
+	for (DevBuf* b : bufs) {
+		release(*b);
+	}
+	for (const EventPair* w : windows) {
+		destroy_event(*w);
+	}
+}
+
+// ---- The reports behind the device applier, one state struct each (helpers and entry points: nte_api_reports.inc): its device
+// buffers, its windows (created by the first call that times one), its switch, the last call's figures.  size*() are the only
+// place a buffer's size is written: the stage passes the batch's values, ntedit_hip_reserve its estimates.
+struct ApplyReport // the device applier and the QV counts (nte_apply.hip)
+{
+	DevBuf ev, place, range, contig, tabs, pieces, bitmap, rows;
+	DevBuf edited; // (under pin_mu: a result that is freed hands it back from another thread)
+	// the applier, and per side of the draft (0 the batch, 1 the edited bases) the plain screening and the QV count
+	EventPair window[1], screen[2], count[2];
+	ntedit_hip_apply_stats last = { 0.f, 0.f, 0.f, 0, 0, 0 };
+	// before launch_apply_plan: an event's summary and place, per entry its event range, its contig record and the tables
+	// (tabs: out_offs u64[nc] | piece_base u64[nc + 1] | totals u64[3] | status (8 bytes) | out_lens u32[nc])
+	int size_plan(ntedit_hip_ctx* c, u64 events, u64 nc)
+	{
+		int rc;
+		if ((rc = ensure(c, ev, (size_t)(events + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, place, (size_t)(events + 1) * sizeof(ApplyPlace))) ||
+		    (rc = ensure(c, range, nc * 8)) || (rc = ensure(c, contig, nc * sizeof(ApplyContig)))) {
+			return rc;
+		}
+		return ensure(c, tabs, nc * 8 + (nc + 1) * 8 + 32 + nc * 4);
+	}
+	// once the plan's totals are known: the edited bases (eb: wherever they are held just now) and the piece table
+	int size_write(ntedit_hip_ctx* c, DevBuf& eb, u64 edited_bytes, u64 n_pieces)
+	{
+		const int rc = ensure(c, eb, (size_t)((edited_bytes + 15) / 16 * 16 + 64));
+		return rc ? rc : ensure(c, pieces, (size_t)(n_pieces + 1) * sizeof(ApplyPiece));
+	}
+	// before either side is assessed: the QV rows (none for ntedit_hip_track_extract), a plain bitmap for the larger side
+	int size_assess(ntedit_hip_ctx* c, u64 positions, u64 entries)
+	{
+		const int rc = ensure(c, rows, (size_t)entries * sizeof(QvRow));
+		return rc ? rc : ensure(c, bitmap, (size_t)((positions + 63) / 64 + 8) * 8);
+	}
+	void release() { release_all({ &ev, &place, &range, &contig, &tabs, &pieces, &bitmap, &rows, &edited }, { window, screen, screen + 1, count, count + 1 }); }
+};
+
+struct TrackReport // the interval extractor (nte_track.hip)
+{
+	DevBuf tiles, recs, upto, totals;
+	EventPair window[2]; // the count and scan, the emit
+	ntedit_hip_track_stats last = { { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
+	// the tiles' counts and the totals for a bitmap of `positions`; the records and their side array for `intervals`
+	int size(ntedit_hip_ctx* c, u64 positions, u64 intervals)
+	{
+		int rc;
+		if ((rc = ensure(c, tiles, (size_t)track_tiles(positions) * sizeof(TrackTile))) || (rc = ensure(c, totals, 64)) ||
+		    (rc = ensure(c, recs, (size_t)intervals * sizeof(TrackInterval)))) {
+			return rc;
+		}
+		return ensure(c, upto, (size_t)intervals * 4);
+	}
+	void release() { release_all({ &tiles, &recs, &upto, &totals }, { window, window + 1 }); }
+};
+
+struct SpectrumReport // the k-mer spectrum (k_spectrum; ntedit_hip_set_spectrum)
+{
+	bool on = false;
+	DevBuf buf; // [which][256] bins, then [which][n_entries][3] rows
+	EventPair window[2]; // per side
+	ntedit_hip_spectrum_stats last = { { 0.f, 0.f }, { 0, 0 } };
+	static size_t bytes(u64 entries) { return (2 * (size_t)SPECTRUM_BINS + 2 * (size_t)entries * 3) * 8; }
+	unsigned long long* bins(int which) const { return (unsigned long long*)buf.p + (size_t)which * SPECTRUM_BINS; }
+	unsigned long long* rows(int which, u32 n_entries) const { return bins(2) + (size_t)which * n_entries * 3; }
+	void release() { release_all({ &buf }, { window, window + 1 }); }
+};
+
+// linear counting of the draft's present k-mers (k_mark; ntedit_hip_shared_*): two mark arrays of the PRIMARY filter's size,
+// before and after; they go when the slot gets another filter (drop_filter)
+struct SharedReport
+{
+	DevBuf marks[2];
+	u64 bytes = 0;                 // the filter's byte size the marks were made for (0: none)
+	u64 calls = 0;                 // k_mark launches since the last reset
+	float ms[2] = { 0.f, 0.f };    // their HIP-event time, per array
+	EventPair window[2];           // per array
+	void release_marks()           // (the events stay: drop_filter, ntedit_hip_shared_free)
+	{
+		release_all({ marks, marks + 1 }, {});
+		bytes = calls = 0;
+		ms[0] = ms[1] = 0.f;
+	}
+	void release() { release_all({ marks, marks + 1 }, { window, window + 1 }); }
+};
+
+struct BgzfReport // the BGZF writer (nte_bgzf_deflate.hip): the header lines of the next polish call, the last call's figures
+{
+	std::vector<std::string> fa_names;
+	bool fa_names_set = false;
+	ntedit_hip_bgzf_stats last = { 0.f, 0.f, 0.f, 0, 0, 0, 0 };
+	std::vector<PinBuf> pool; // page-locked buffers for the members, apart from pin_pool (under pin_mu): filled by reserve
+	void release()
+	{
+		for (PinBuf& pb : pool) {
+			(void)hipHostFree(pb.p);
+		}
+		pool.clear();
+	}
+};
+
+struct Reports
+{
+	ApplyReport ap;
+	TrackReport tr;
+	SpectrumReport sp;
+	SharedReport sh;
+	BgzfReport bz;
+	void release() { ap.release(), tr.release(), sp.release(), sh.release(), bz.release(); } // (ntedit_hip_destroy)
+};
+
+} // namespace
+
 struct ntedit_hip_ctx
 {
 	int device = 0;
@@ -155,38 +320,9 @@ struct ntedit_hip_ctx
 	} tune;
 	DevBuf ev_cover, ev_before, ev_flags, ev_list, ev_bmax; // event rounds
 	DevBuf ev_rest; // the events of a round k_settle declined (nte_settle.hip)
-	// the device applier and the QV counts (nte_apply.hip): ntedit_hip_set_apply()
-	u32 apply_flags = 0;
-	DevBuf ap_ev, ap_place, ap_range, ap_contig, ap_tabs, ap_pieces, ap_edited, ap_bitmap, ap_rows;
-	// the apply stage's windows (nte_api_apply.inc; ntedit_hip_apply_info): the applier, and per side of the draft (0 the batch,
-	// 1 the edited bases) the plain screening and the QV count
-	EventPair ap_window[1], ap_screen[2], ap_count[2];
-	ntedit_hip_apply_stats apply_last = { 0.f, 0.f, 0.f, 0, 0, 0 };
-	// the BGZF writer (nte_bgzf_deflate.hip): the header lines of the next polish call, the last call's figures
-	std::vector<std::string> fa_names;
-	bool fa_names_set = false;
-	ntedit_hip_bgzf_stats bgzf_last = { 0.f, 0.f, 0.f, 0, 0, 0, 0 };
-	std::vector<PinBuf> bgzf_pool; // page-locked buffers for the members, apart from pin_pool (under pin_mu): filled by reserve
-	// the interval extractor (nte_track.hip): the tiles' counts, the records and their side array, four words of totals
-	DevBuf tr_tiles, tr_recs, tr_upto, tr_totals;
-	hipEvent_t tr_evt[4] = { nullptr, nullptr, nullptr, nullptr };
-	ntedit_hip_track_stats track_last = { { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
-	// the k-mer spectrum (k_spectrum; ntedit_hip_set_spectrum): the switch, the bins and rows of a call in HBM, the last
-	// call's figures
-	bool spectrum_on = false;
-	DevBuf sp_buf;
-	hipEvent_t sp_evt[4] = { nullptr, nullptr, nullptr, nullptr };
-	ntedit_hip_spectrum_stats spectrum_last = { { 0.f, 0.f }, { 0, 0 } };
-	// the spectrum by copy number (nte_cn.hip; ntedit_hip_set_cn): the switch is the store's state; both sides of the draft
-	// stay in HBM until ntedit_hip_cn_finish
-	CnStore cn;
-	// linear counting of the draft's present k-mers (k_mark; ntedit_hip_shared_*): two mark arrays of the PRIMARY filter's
-	// size, before and after; they go when the slot gets another filter (drop_filter)
-	DevBuf sh_marks[2];
-	u64 sh_bytes = 0;                 // the filter's byte size the marks were made for (0: none)
-	u64 sh_calls = 0;                 // k_mark launches since the last reset
-	float sh_ms[2] = { 0.f, 0.f };    // their HIP-event time, per array
-	hipEvent_t sh_evt[4] = { nullptr, nullptr, nullptr, nullptr };
+	u32 apply_flags = 0; // ntedit_hip_set_apply()
+	Reports rep;
+	CnStore cn; // the spectrum by copy number (nte_cn.hip): the switch is the store's state; both sides stay in HBM until ntedit_hip_cn_finish
 	u32 cu_count = 256;
 	size_t lds_per_block = 160 * 1024;
 	double alloc_ms = 0.0;            // host time spent in hipFree + hipMalloc of the grow-only buffers (ensure())
@@ -260,12 +396,6 @@ fail(ntedit_hip_ctx* c, int code, const char* fmt, ...)
 		}                                                                                        \
 	} while (0)
 
-// take a pinned buffer of at least `bytes` from the pool (or allocate one)
-int
-pin_take(ntedit_hip_ctx* c, size_t bytes, PinBuf* out);
-void
-pin_give(ntedit_hip_ctx* c, PinBuf& b);
-
 int
 ensure(ntedit_hip_ctx* c, DevBuf& b, size_t bytes)
 {
@@ -332,21 +462,6 @@ ensure_events(ntedit_hip_ctx* c, std::vector<hipEvent_t>& evs, size_t count)
 	return 0;
 }
 
-void
-destroy_event(hipEvent_t e)
-{
-	if (e) {
-		(void)hipEventDestroy(e);
-	}
-}
-
-void
-destroy_event(const EventPair& p)
-{
-	destroy_event(p.begin);
-	destroy_event(p.end);
-}
-
 template<class E, size_t N>
 void
 destroy_events(E (&evs)[N])
@@ -356,19 +471,41 @@ destroy_events(E (&evs)[N])
 	}
 }
 
+// the best fit for `bytes` among a pool's buffers, taken out of the pool (false: none holds that much); under pin_mu
+bool
+pool_best_fit(std::vector<PinBuf>& pool, size_t bytes, PinBuf* out)
+{
+	int best = -1;
+	for (size_t i = 0; i < pool.size(); i++) {
+		if (pool[i].cap >= bytes && (best < 0 || pool[i].cap < pool[best].cap)) {
+			best = (int)i;
+		}
+	}
+	if (best < 0) {
+		return false;
+	}
+	*out = pool[best];
+	pool.erase(pool.begin() + best);
+	return true;
+}
+
+// a new page-locked buffer for `bytes`, with a quarter to spare
+int
+pin_alloc(ntedit_hip_ctx* c, size_t bytes, PinBuf* out)
+{
+	const size_t want = bytes + bytes / 4 + 4096;
+	void* p = nullptr;
+	HIP_TRY(c, hipHostMalloc(&p, want, hipHostMallocDefault));
+	out->p = p;
+	out->cap = want;
+	return 0;
+}
+
 int
 pin_take(ntedit_hip_ctx* c, size_t bytes, PinBuf* out)
 {
 	std::lock_guard<std::mutex> lk(c->pin_mu); // results are freed from other threads
-	int best = -1;
-	for (size_t i = 0; i < c->pin_pool.size(); i++) {
-		if (c->pin_pool[i].cap >= bytes && (best < 0 || c->pin_pool[i].cap < c->pin_pool[best].cap)) {
-			best = (int)i;
-		}
-	}
-	if (best >= 0) {
-		*out = c->pin_pool[best];
-		c->pin_pool.erase(c->pin_pool.begin() + best);
+	if (pool_best_fit(c->pin_pool, bytes, out)) {
 		return 0;
 	}
 	// drop the oldest pooled buffer if the pool is getting large
@@ -376,12 +513,7 @@ pin_take(ntedit_hip_ctx* c, size_t bytes, PinBuf* out)
 		(void)hipHostFree(c->pin_pool.front().p);
 		c->pin_pool.erase(c->pin_pool.begin());
 	}
-	size_t want = bytes + bytes / 4 + 4096;
-	void* p = nullptr;
-	HIP_TRY(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-	out->p = p;
-	out->cap = want;
-	return 0;
+	return pin_alloc(c, bytes, out);
 }
 
 void
@@ -407,24 +539,11 @@ bgzf_pin_take(ntedit_hip_ctx* c, size_t bytes, PinBuf* out)
 {
 	{
 		std::lock_guard<std::mutex> lk(c->pin_mu);
-		int best = -1;
-		for (size_t i = 0; i < c->bgzf_pool.size(); i++) {
-			if (c->bgzf_pool[i].cap >= bytes && (best < 0 || c->bgzf_pool[i].cap < c->bgzf_pool[best].cap)) {
-				best = (int)i;
-			}
-		}
-		if (best >= 0) {
-			*out = c->bgzf_pool[best];
-			c->bgzf_pool.erase(c->bgzf_pool.begin() + best);
+		if (pool_best_fit(c->rep.bz.pool, bytes, out)) {
 			return 0;
 		}
 	}
-	const size_t want = bytes + bytes / 4 + 4096;
-	void* p = nullptr;
-	HIP_TRY(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-	out->p = p;
-	out->cap = want;
-	return 0;
+	return pin_alloc(c, bytes, out);
 }
 
 void
@@ -436,33 +555,24 @@ bgzf_pin_give(ntedit_hip_ctx* c, PinBuf& b)
 	bool kept = false;
 	if (c && ctx_alive(c)) {
 		std::lock_guard<std::mutex> lk(c->pin_mu);
-		if (c->bgzf_pool.size() >= 3) { // (the smallest goes: the pool keeps what the largest batches need)
+		std::vector<PinBuf>& pool = c->rep.bz.pool;
+		if (pool.size() >= 3) { // (the smallest goes: the pool keeps what the largest batches need)
 			size_t least = 0;
-			for (size_t i = 1; i < c->bgzf_pool.size(); i++) {
-				if (c->bgzf_pool[i].cap < c->bgzf_pool[least].cap) {
+			for (size_t i = 1; i < pool.size(); i++) {
+				if (pool[i].cap < pool[least].cap) {
 					least = i;
 				}
 			}
-			if (c->bgzf_pool[least].cap < b.cap) {
-				std::swap(c->bgzf_pool[least], b);
+			if (pool[least].cap < b.cap) {
+				std::swap(pool[least], b);
 			}
 		} else {
-			c->bgzf_pool.push_back(b);
+			pool.push_back(b);
 			kept = true;
 		}
 	}
 	if (!kept) {
 		(void)hipHostFree(b.p);
-	}
-	b.p = nullptr;
-	b.cap = 0;
-}
-
-void
-release(DevBuf& b)
-{
-	if (b.p) {
-		(void)hipFree(b.p);
 	}
 	b.p = nullptr;
 	b.cap = 0;
@@ -507,21 +617,16 @@ refresh_params(ntedit_hip_ctx* c)
 		c->dp.debug_stop = (u32)atoi(e); // timing ablations; results are NOT valid (ablation build only)
 	}
 #endif
-	if (c->tune.inline_tries != ~0u) { // tuning / tests (any value gives the same results)
-		c->dp.inline_tries = c->tune.inline_tries;
-	}
-	if (c->tune.lanes != ~0u) {
-		c->dp.lanes = c->tune.lanes;
-	}
-	if (c->tune.defer_run != ~0u) {
-		c->dp.defer_run = c->tune.defer_run;
-	}
-	if (c->tune.defer_fail != ~0u) {
-		c->dp.defer_fail = c->tune.defer_fail;
-	}
-	if (c->tune.defer_fail_snv != ~0u) {
-		c->dp.defer_fail_snv = c->tune.defer_fail_snv;
-	}
+	auto tuned = [](u32 knob, u32& param) { // tuning / tests (any value gives the same results)
+		if (knob != ~0u) {
+			param = knob;
+		}
+	};
+	tuned(c->tune.inline_tries, c->dp.inline_tries);
+	tuned(c->tune.lanes, c->dp.lanes);
+	tuned(c->tune.defer_run, c->dp.defer_run);
+	tuned(c->tune.defer_fail, c->dp.defer_fail);
+	tuned(c->tune.defer_fail_snv, c->dp.defer_fail_snv);
 	if (!c->d_tab) {
 		HIP_TRY(c, hipMalloc((void**)&c->d_tab, TAB_WORDS * sizeof(u64)));
 	}
@@ -539,6 +644,7 @@ refresh_params(ntedit_hip_ctx* c)
 
 } // namespace
 
+#include "nte_api_reports.inc"
 #include "nte_api_filters.inc"
 #include "nte_api_polish.inc"
 #include "nte_api_apply.inc"

@@ -1,76 +1,11 @@
 // nte_api_apply.inc -- part of nte_api.hip: the apply stage of ntedit_hip_polish_batch, behind the polish of a batch
-// (PolishRun::apply() in nte_api_polish.inc hands it an ApplyInput when a report is on).
-// track_run()         the interval extractor's host side (nte_track.hip), also behind ntedit_hip_track_extract
+// (PolishRun::apply() in nte_api_polish.inc hands it an ApplyInput when a report is on).  The reports' own state, sizes,
+// helpers and entry points are in nte_api_reports.inc; this file queues them.
 // ApplyStage::run()   the device applier (nte_apply.hip), then both sides of the draft -- the batch, the edited bases --
 //                     through the reports: assess() per side, the spectrum and the draft store per side, the BGZF writer
 // ApplyStage::assess() one side through the reports that read a bitmap: plain screening, QV count, marks, intervals
 // apply_stage()       owns the edited bases while the stage runs: the one place a failure is cleaned up
 namespace {
-
-// The interval extractor (nte_track.hip) over a bitmap and the entries of its batch, all in device memory, on stream s:
-// count and scan, three words to the host, the record buffer sized from them, emit and finish, the records to host memory
-// (malloc, *out; null for none; the caller's to free whatever is returned).  The stream is idle when it returns 0.  Crosses
-// PCIe: four words and the records.
-int
-track_run(ntedit_hip_ctx* c, hipStream_t s, const u64* d_bitmap, u64 n, const u64* d_offs, const u32* d_lens, u32 n_entries, u32 k, int which,
-          ntedit_hip_track_interval** out, u64* n_out)
-{
-	int rc;
-	free(*out);
-	*out = nullptr;
-	*n_out = 0;
-	c->track_last.ms[which] = 0.f;
-	c->track_last.intervals[which] = c->track_last.bases[which] = 0;
-	const u64 n_tiles = track_tiles(n);
-	if (n_tiles == 0 || n_entries == 0) {
-		return 0;
-	}
-	if (n_tiles > 0x7FFFFFFFull) {
-		return fail(c, NTEDIT_E_ARG, "track: batch too large");
-	}
-	if ((rc = ensure_events(c, c->tr_evt)) || (rc = ensure(c, c->tr_tiles, (size_t)n_tiles * sizeof(TrackTile))) || (rc = ensure(c, c->tr_totals, 64))) {
-		return rc;
-	}
-	const TrackArgs a = { d_bitmap, n, d_offs, d_lens, n_entries, k };
-	TrackTile* tiles = (TrackTile*)c->tr_tiles.p;
-	u64* totals = (u64*)c->tr_totals.p;
-	u64 h_tot[4] = { 0, 0, 0, 0 };
-	HIP_TRY(c, hipEventRecord(c->tr_evt[0], s));
-	launch_track_count(s, a, tiles, totals);
-	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipEventRecord(c->tr_evt[1], s));
-	HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 32, hipMemcpyDeviceToHost, s));
-	HIP_TRY(c, hipStreamSynchronize(s));
-	if (h_tot[0] != h_tot[1] || h_tot[0] > h_tot[2]) {
-		return fail(c, NTEDIT_E_INTERNAL, "track: %llu interval starts, %llu ends, %llu marked starts", (unsigned long long)h_tot[0],
-		            (unsigned long long)h_tot[1], (unsigned long long)h_tot[2]);
-	}
-	float t0 = 0.f, t1 = 0.f;
-	(void)hipEventElapsedTime(&t0, c->tr_evt[0], c->tr_evt[1]);
-	const u64 n_recs = h_tot[0];
-	if (n_recs) {
-		if ((rc = ensure(c, c->tr_recs, (size_t)n_recs * sizeof(TrackInterval))) || (rc = ensure(c, c->tr_upto, (size_t)n_recs * 4))) {
-			return rc;
-		}
-		*out = (ntedit_hip_track_interval*)malloc((size_t)n_recs * sizeof(ntedit_hip_track_interval));
-		if (!*out) {
-			return fail(c, NTEDIT_E_OVERFLOW, "track: no host memory for %llu intervals", (unsigned long long)n_recs);
-		}
-		HIP_TRY(c, hipEventRecord(c->tr_evt[2], s));
-		launch_track_emit(s, a, tiles, (TrackInterval*)c->tr_recs.p, (u32*)c->tr_upto.p, n_recs, totals);
-		HIP_TRY(c, hipGetLastError());
-		HIP_TRY(c, hipEventRecord(c->tr_evt[3], s));
-		HIP_TRY(c, hipMemcpyAsync(*out, c->tr_recs.p, (size_t)n_recs * sizeof(TrackInterval), hipMemcpyDeviceToHost, s));
-		HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 32, hipMemcpyDeviceToHost, s));
-		HIP_TRY(c, hipStreamSynchronize(s));
-		(void)hipEventElapsedTime(&t1, c->tr_evt[2], c->tr_evt[3]);
-		*n_out = n_recs;
-	}
-	c->track_last.ms[which] = t0 + t1;
-	c->track_last.intervals[which] = n_recs;
-	c->track_last.bases[which] = h_tot[3];
-	return 0;
-}
 
 // one side of the draft in HBM: the batch as it came (which = 0) or its edited bases (1), and the entries of either
 struct DraftSide
@@ -83,20 +18,12 @@ struct DraftSide
 	u32 n_entries;
 };
 
-// a window that has been waited for, in ms (a figure that is only reported: 0 where the events cannot say)
-float
-elapsed_ms(const EventPair& p)
-{
-	float ms = 0.f;
-	(void)hipEventElapsedTime(&ms, p.begin, p.end);
-	return ms;
-}
-
 struct ApplyStage
 {
 	const ApplyInput& in;
 	ntedit_hip_ctx* const c;
 	ntedit_hip_result* const r;
+	ApplyReport& ap;
 	const hipStream_t s;
 	const u32 flags, k;
 	// (APPLY_SHARED runs everything APPLY_QV runs and marks the present k-mers of both screenings: k_mark; APPLY_TRACK runs it
@@ -109,13 +36,14 @@ struct ApplyStage
 	  : in(in_)
 	  , c(in_.c)
 	  , r(in_.r)
+	  , ap(in_.c->rep.ap)
 	  , s(in_.c->stream)
 	  , flags(in_.c->apply_flags)
 	  , k(in_.c->dp.k)
 	  , qv((flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) != 0)
 	  , shared((flags & NTEDIT_HIP_APPLY_SHARED) != 0)
 	  , track((flags & NTEDIT_HIP_APPLY_TRACK) != 0)
-	  , spectrum(in_.c->spectrum_on)
+	  , spectrum(in_.c->rep.sp.on)
 	  , cn(in_.c->cn.state != CN_OFF)
 	{}
 
@@ -124,7 +52,7 @@ struct ApplyStage
 	int bgzf(const u8* d_edited);
 };
 
-// One side through the reports that read a bitmap, in one order for both sides: the plain screening into c->ap_bitmap where
+// One side through the reports that read a bitmap, in one order for both sides: the plain screening into ap.bitmap where
 // the side has no plain bitmap yet, the QV count, the completeness marks, the intervals -- each under its flag, inside the
 // caller's PlainScreen.  Everything that reads the side's bitmap is queued when this returns (track_run waits for it).
 int
@@ -135,21 +63,21 @@ ApplyStage::assess(int which, const u64* plain_bitmap)
 	const u64 n_words = (sd.n + 63) / 64;
 	const u64* bitmap = plain_bitmap;
 	if (!bitmap) {
-		const EventPair& ev = c->ap_screen[sd.which];
-		if ((rc = screen_whole(c, sd.bases, sd.n, in.f0, (u64*)c->ap_bitmap.p, n_words, ev.begin, ev.end))) {
+		const EventPair& ev = ap.screen[sd.which];
+		if ((rc = screen_whole(c, sd.bases, sd.n, in.f0, (u64*)ap.bitmap.p, n_words, ev.begin, ev.end))) {
 			return rc;
 		}
 		screened[sd.which] = true;
-		bitmap = (const u64*)c->ap_bitmap.p;
+		bitmap = (const u64*)ap.bitmap.p;
 	}
-	QvRow* rows = (QvRow*)c->ap_rows.p;
-	HIP_TRY(c, hipEventRecord(c->ap_count[sd.which].begin, s));
+	QvRow* rows = (QvRow*)ap.rows.p;
+	HIP_TRY(c, hipEventRecord(ap.count[sd.which].begin, s));
 	if (sd.which == 0) { // (the rows are laid out once, before the first count: both sides' lengths)
 		launch_qv_rows(s, rows, side[0].lens, side[1].lens, sd.n_entries);
 	}
 	launch_qv_count(s, sd.bases, sd.n, sd.offs, sd.lens, sd.n_entries, bitmap, k, rows, sd.which);
 	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipEventRecord(c->ap_count[sd.which].end, s));
+	HIP_TRY(c, hipEventRecord(ap.count[sd.which].end, s));
 	if (sd.which == 1) { // (both counts are in: the rows go to the result)
 		r->qv.resize(sd.n_entries);
 		HIP_TRY(c, hipMemcpyAsync(r->qv.data(), rows, (size_t)sd.n_entries * sizeof(QvRow), hipMemcpyDeviceToHost, s));
@@ -174,21 +102,15 @@ ApplyStage::run(DevBuf& eb)
 		return fail(c, NTEDIT_E_UNSUPPORTED, "apply: the QV counts take k up to %u", QV_MAX_K);
 	}
 	if (track) {
-		c->track_last = ntedit_hip_track_stats{ { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
+		c->rep.tr.last = ntedit_hip_track_stats{ { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
 	}
 	if (shared && (rc = shared_begin(c, "polish_batch"))) { // (the completeness marks: begun here if that was not done)
-		return rc;
-	}
-	if ((rc = ensure_events(c, c->ap_window)) || (rc = ensure_events(c, c->ap_screen)) || (rc = ensure_events(c, c->ap_count))) {
 		return rc;
 	}
 	const u64 n_ev = in.n_events;
 	const u32 n_contigs = in.n_contigs;
 	const size_t nc = n_contigs;
-	// ap_tabs: out_offs u64[nc] | piece_base u64[nc + 1] | totals u64[3] | status (8 bytes) | out_lens u32[nc]
-	const size_t tabs_bytes = nc * 8 + (nc + 1) * 8 + 32 + nc * 4;
-	if ((rc = ensure(c, c->ap_ev, (size_t)(n_ev + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, c->ap_place, (size_t)(n_ev + 1) * sizeof(ApplyPlace))) ||
-	    (rc = ensure(c, c->ap_range, nc * 8)) || (rc = ensure(c, c->ap_contig, nc * sizeof(ApplyContig))) || (rc = ensure(c, c->ap_tabs, tabs_bytes))) {
+	if ((rc = ensure_events(c, ap.window)) || (rc = ensure_events(c, ap.screen)) || (rc = ensure_events(c, ap.count)) || (rc = ap.size_plan(c, n_ev, nc))) {
 		return rc;
 	}
 	ApplyArgs a;
@@ -202,12 +124,12 @@ ApplyStage::run(DevBuf& eb)
 	a.arena_items = r->arena_items;
 	a.ev_first = (const u32*)c->first_chunk.p;
 	a.n_events = (u32)n_ev;
-	a.ev = (ApplyEvent*)c->ap_ev.p;
-	a.place = (ApplyPlace*)c->ap_place.p;
-	a.ev_begin = (u32*)c->ap_range.p;
+	a.ev = (ApplyEvent*)ap.ev.p;
+	a.place = (ApplyPlace*)ap.place.p;
+	a.ev_begin = (u32*)ap.range.p;
 	a.ev_end = a.ev_begin + nc;
-	a.contig = (ApplyContig*)c->ap_contig.p;
-	a.out_offs = (u64*)c->ap_tabs.p;
+	a.contig = (ApplyContig*)ap.contig.p;
+	a.out_offs = (u64*)ap.tabs.p;
 	a.piece_base = a.out_offs + nc;
 	a.totals = a.piece_base + nc + 1;
 	a.status = (u32*)(a.totals + 3);
@@ -216,7 +138,7 @@ ApplyStage::run(DevBuf& eb)
 	HIP_TRY(c, hipMemsetAsync(a.ev_begin, 0xFF, nc * 4, s));
 	HIP_TRY(c, hipMemsetAsync(a.ev_end, 0, nc * 4, s));
 	HIP_TRY(c, hipMemsetAsync(a.totals, 0, 32, s));
-	HIP_TRY(c, hipEventRecord(c->ap_window[0].begin, s));
+	HIP_TRY(c, hipEventRecord(ap.window[0].begin, s));
 	launch_apply_plan(s, a);
 	HIP_TRY(c, hipGetLastError());
 	u64 h_tot[4] = { 0, 0, 0, 0 };
@@ -233,17 +155,17 @@ ApplyStage::run(DevBuf& eb)
 	const u64 total_bytes = h_tot[0], total_pieces = h_tot[1];
 	{
 		std::lock_guard<std::mutex> lk(c->pin_mu); // (a result that is freed hands its buffer back from another thread)
-		eb = c->ap_edited;
-		c->ap_edited = DevBuf();
+		eb = ap.edited;
+		ap.edited = DevBuf();
 	}
-	if ((rc = ensure(c, eb, (size_t)((total_bytes + 15) / 16 * 16 + 64))) || (rc = ensure(c, c->ap_pieces, (size_t)(total_pieces + 1) * sizeof(ApplyPiece)))) {
+	if ((rc = ap.size_write(c, eb, total_bytes, total_pieces))) {
 		return rc;
 	}
-	a.pieces = (ApplyPiece*)c->ap_pieces.p;
+	a.pieces = (ApplyPiece*)ap.pieces.p;
 	a.out = (u8*)eb.p;
 	launch_apply_write(s, a, total_bytes, total_pieces);
 	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipEventRecord(c->ap_window[0].end, s));
+	HIP_TRY(c, hipEventRecord(ap.window[0].end, s));
 	r->e_offs.resize(nc);
 	r->e_lens.resize(nc);
 	HIP_TRY(c, hipMemcpyAsync(r->e_offs.data(), a.out_offs, nc * 8, hipMemcpyDeviceToHost, s));
@@ -253,13 +175,11 @@ ApplyStage::run(DevBuf& eb)
 	if (qv) {
 		// before: the batch and step 1's bitmap; after: the edited bases, screened the way a batch of that size is.  With
 		// -s 1 step 1 marks every k-mer of accepted bases (k_screen: "no probe decides that"), so c->bitmap is not the plain
-		// answer: both screenings then run with the flag down, the batch's into c->ap_bitmap first.  The screening of the
+		// answer: both screenings then run with the flag down, the batch's into ap.bitmap first.  The screening of the
 		// edited bases overwrites that bitmap: assess() has queued everything that reads the batch's by then.
 		PlainScreen plain(c);
 		const bool rescreen = plain.dp_snv != 0;
-		const u64 nw2 = (total_bytes + 63) / 64;
-		const u64 nw_max = rescreen && in.n_words > nw2 ? in.n_words : nw2;
-		if ((rc = ensure(c, c->ap_rows, nc * sizeof(QvRow))) || (rc = ensure(c, c->ap_bitmap, (size_t)(nw_max + 8) * 8))) {
+		if ((rc = ap.size_assess(c, rescreen && in.n > total_bytes ? in.n : total_bytes, nc))) { // (the larger side, before either is assessed)
 			return rc;
 		}
 		if (!rescreen && (rc = bin_reset(c, s))) { // (the record chunks of step 1's screening; each screening here forgets the last one's)
@@ -282,7 +202,7 @@ ApplyStage::run(DevBuf& eb)
 				return rc;
 			}
 		}
-		HIP_TRY(c, hipMemcpyAsync(sp_host.data(), c->sp_buf.p, sp_host.size() * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(c, hipMemcpyAsync(sp_host.data(), c->rep.sp.buf.p, sp_host.size() * 8, hipMemcpyDeviceToHost, s));
 	}
 	// The spectrum by copy number (ntedit_hip_set_cn; nte_cn.hip): both sides go into the draft store, device to device;
 	// nothing is counted before ntedit_hip_cn_finish.  A store that passes its cap releases itself and fails nothing.
@@ -309,16 +229,16 @@ ApplyStage::run(DevBuf& eb)
 		r->spectrum = true;
 	}
 	// ntedit_hip_apply_info: the applier's window, the screenings the stage ran, the two count windows
-	ntedit_hip_apply_stats as = { elapsed_ms(c->ap_window[0]), 0.f, 0.f, total_pieces, total_bytes, h_tot[2] };
+	ntedit_hip_apply_stats as = { elapsed_ms(ap.window[0]), 0.f, 0.f, total_pieces, total_bytes, h_tot[2] };
 	for (int which = 0; which < 2; which++) {
-		as.ms_screen += screened[which] ? elapsed_ms(c->ap_screen[which]) : 0.f;
-		as.ms_count += qv ? elapsed_ms(c->ap_count[which]) : 0.f;
+		as.ms_screen += screened[which] ? elapsed_ms(ap.screen[which]) : 0.f;
+		as.ms_count += qv ? elapsed_ms(ap.count[which]) : 0.f;
 	}
 	if (shared) {
 		mark_timed(c, 0);
 		mark_timed(c, 1);
 	}
-	c->apply_last = as;
+	ap.last = as;
 	r->edited_bytes = total_bytes;
 	if ((flags & NTEDIT_HIP_APPLY_BGZF) && (rc = bgzf(a.out))) {
 		return rc;
@@ -327,10 +247,10 @@ ApplyStage::run(DevBuf& eb)
 		r->edited = eb; // the result's own until ntedit_hip_result_free()
 	} else {
 		std::lock_guard<std::mutex> lk(c->pin_mu);
-		if (c->ap_edited.p) {
+		if (ap.edited.p) {
 			release(eb);
 		} else {
-			c->ap_edited = eb;
+			ap.edited = eb;
 		}
 	}
 	return 0;
@@ -371,7 +291,7 @@ ApplyStage::bgzf(const u8* d_edited)
 	r->bgzf_bytes = t.bytes;
 	r->bgzf_plain = t.plain;
 	r->bgzf_members = t.members;
-	c->bgzf_last = { t.ms_image, t.ms_deflate, t.ms_copy, t.plain, t.bytes, t.members, t.stored };
+	c->rep.bz.last = { t.ms_image, t.ms_deflate, t.ms_copy, t.plain, t.bytes, t.members, t.stored };
 	return 0;
 }
 

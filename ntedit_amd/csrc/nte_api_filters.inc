@@ -45,23 +45,9 @@ ntedit_hip_create(int device, ntedit_hip_ctx** out)
 		delete c;
 		return NTEDIT_E_DEVICE;
 	}
-	for (auto& e : c->ev) {
-		if (hipEventCreate(&e) != hipSuccess) {
-			delete c;
-			return NTEDIT_E_DEVICE;
-		}
-	}
-	for (auto& e : c->ev_assess) {
-		if (hipEventCreate(&e) != hipSuccess) {
-			delete c;
-			return NTEDIT_E_DEVICE;
-		}
-	}
-	for (auto& e : c->ev_settle) {
-		if (hipEventCreate(&e) != hipSuccess) {
-			delete c;
-			return NTEDIT_E_DEVICE;
-		}
+	if (ensure_events(c, c->ev) || ensure_events(c, c->ev_assess) || ensure_events(c, c->ev_settle)) {
+		delete c;
+		return NTEDIT_E_DEVICE;
 	}
 	{
 		std::lock_guard<std::mutex> lk(g_live_mu);
@@ -95,10 +81,7 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 	}
 	DevBuf* bufs[] = { &c->seq,      &c->bitmap,   &c->block_counts, &c->block_offsets, &c->events,
 		               &c->first_chunk, &c->arena, &c->counters, &c->deferred,     &c->ws_nodes,      &c->ws_ov_pos,
-		               &c->ws_ov_chr, &c->ws_prev, &c->ws_lps, &c->ws_win, &c->runmap, &c->candmap, &c->packed, &c->bin_records, &c->bin_fill, &c->bin_ctl, &c->bin_ovf, &c->bin_state, &c->ev_cover, &c->ev_before, &c->ev_flags, &c->ev_list, &c->ev_bmax, &c->ev_rest,       &c->offs,          &c->lens,
-		               &c->ap_ev, &c->ap_place, &c->ap_range, &c->ap_contig, &c->ap_tabs, &c->ap_pieces, &c->ap_edited, &c->ap_bitmap, &c->ap_rows,
-		               &c->tr_tiles, &c->tr_recs, &c->tr_upto, &c->tr_totals, &c->sp_buf,
-		               &c->sh_marks[0], &c->sh_marks[1] };
+		               &c->ws_ov_chr, &c->ws_prev, &c->ws_lps, &c->ws_win, &c->runmap, &c->candmap, &c->packed, &c->bin_records, &c->bin_fill, &c->bin_ctl, &c->bin_ovf, &c->bin_state, &c->ev_cover, &c->ev_before, &c->ev_flags, &c->ev_list, &c->ev_bmax, &c->ev_rest,       &c->offs,          &c->lens };
 	for (DevBuf* b : bufs) {
 		release(*b);
 	}
@@ -106,32 +89,19 @@ ntedit_hip_destroy(ntedit_hip_ctx* c)
 		(void)hipHostFree(pb.p);
 	}
 	c->pin_pool.clear();
-	for (auto& pb : c->bgzf_pool) {
-		(void)hipHostFree(pb.p);
-	}
-	c->bgzf_pool.clear();
+	c->rep.release(); // (every report's buffers and events)
 	bgzf_release(c); // (the BGZF writer's buffers: nte_bgzf_deflate.hip)
+	cn_free(c->cn);
 	if (c->d_tab) {
 		(void)hipFree(c->d_tab);
 	}
 	destroy_events(c->ev);
 	destroy_events(c->ev_assess);
 	destroy_events(c->ev_settle);
-	destroy_events(c->ap_window);
-	destroy_events(c->ap_screen);
-	destroy_events(c->ap_count);
-	destroy_events(c->sh_evt);
-	destroy_events(c->tr_evt);
-	destroy_events(c->sp_evt);
-	cn_free(c->cn);
-	for (auto& e : c->chunk_ev) {
-		(void)hipEventDestroy(e);
-	}
-	for (auto& e : c->h2d_ev) {
-		(void)hipEventDestroy(e);
-	}
-	for (auto& e : c->bin_ev) {
-		(void)hipEventDestroy(e);
+	for (auto* evs : { &c->chunk_ev, &c->h2d_ev, &c->bin_ev }) {
+		for (auto& e : *evs) {
+			(void)hipEventDestroy(e);
+		}
 	}
 	if (c->stream_copy) {
 		(void)hipStreamSynchronize(c->stream_copy);
@@ -164,7 +134,7 @@ drop_filter(ntedit_hip_ctx* c, int slot)
 	f = DevFilter();
 	c->dp_valid = false;
 	if (slot == 0) {
-		shared_release(c); // (the completeness marks were this filter's)
+		c->rep.sh.release_marks(); // (the completeness marks were this filter's)
 		cn_reset(c->cn);   // (and the draft store's copy numbers belong to one round: every round of a cascade starts clean)
 	}
 	return 0;

@@ -144,8 +144,7 @@ PolishRun::plan()
 	if ((rc = stage_bases(c, bases, n, on_device, &d_seq, !h2d_overlap))) {
 		return rc;
 	}
-	if ((rc = ensure(c, c->bitmap, (n_words + 8) * 8)) || (rc = ensure(c, c->counters, 256)) ||
-	    (rc = ensure(c, c->offs, (size_t)n_contigs * 8)) || (rc = ensure(c, c->lens, (size_t)n_contigs * 4))) {
+	if ((rc = ensure(c, c->bitmap, (n_words + 8) * 8)) || (rc = ensure(c, c->counters, 256))) {
 		return rc;
 	}
 	d_bitmap = (u64*)c->bitmap.p;
@@ -155,8 +154,9 @@ PolishRun::plan()
 	HIP_TRY(c, hipMemsetAsync(d_bitmap + n_words, 0, 8 * 8, c->stream));
 	sA = c->stream;
 	sB = c->stream2;
-	HIP_TRY(c, hipMemcpyAsync(c->offs.p, offsets, (size_t)n_contigs * 8, hipMemcpyHostToDevice, sA));
-	HIP_TRY(c, hipMemcpyAsync(c->lens.p, lens, (size_t)n_contigs * 4, hipMemcpyHostToDevice, sA));
+	if ((rc = upload_entries(c, sA, offsets, lens, n_contigs))) {
+		return rc;
+	}
 
 	// ---- chunk plan: whole contigs, cut at SCREEN_TILE boundaries of the screening pass.
 	// Chunk j's screening covers tiles [t0, t1) with t1 = ceil(end of its last contig / TILE),
@@ -721,8 +721,7 @@ PolishRun::run_chunk_events(size_t j)
 			HIP_TRY(c, hipMemcpyAsync(h_t, (char*)c->counters.p + 32, 16, hipMemcpyDeviceToHost, sB));
 			HIP_TRY(c, hipStreamSynchronize(sB));
 			status = h_t[2];
-			float t = 0.f;
-			(void)hipEventElapsedTime(&t, c->ev[5], c->ev[2]);
+			const float t = elapsed_ms(c->ev[5], c->ev[2]);
 			p2_ms += t;
 			return 0;
 		}
@@ -741,8 +740,7 @@ PolishRun::run_chunk_events(size_t j)
 			u32 n_rest = 0;
 			HIP_TRY(c, hipMemcpyAsync(&n_rest, d_nrest, 4, hipMemcpyDeviceToHost, sB));
 			HIP_TRY(c, hipStreamSynchronize(sB));
-			float t = 0.f;
-			(void)hipEventElapsedTime(&t, c->ev_settle[0], c->ev_settle[1]);
+			const float t = elapsed_ms(c->ev_settle[0], c->ev_settle[1]);
 			c->settle_last.ms += t;
 			c->settle_last.events_seen += count;
 			c->settle_last.events_settled += count - n_rest;
@@ -788,8 +786,7 @@ PolishRun::run_chunk_events(size_t j)
 			HIP_TRY(c, hipMemcpyAsync(h_tail, (char*)c->counters.p + 32, 16, hipMemcpyDeviceToHost, sB));
 			HIP_TRY(c, hipStreamSynchronize(sB));
 			status = h_tail[2];
-			float t = 0.f;
-			(void)hipEventElapsedTime(&t, c->ev[5], c->ev[2]);
+			const float t = elapsed_ms(c->ev[5], c->ev[2]);
 			p2_ms += t;
 		}
 		return 0;
@@ -856,8 +853,7 @@ PolishRun::run_chunk_events(size_t j)
 	status = h_tail[2];
 	deferred_total += n_def;
 	skipped_total += rounds ? (u64)n32 - n_A - n_B - n_C : 0;
-	float p_all = 0.f;
-	(void)hipEventElapsedTime(&p_all, c->ev[3], c->ev[4]);
+	const float p_all = elapsed_ms(c->ev[3], c->ev[4]);
 	ms_machine += p_all;
 	if (getenv("NTEDIT_HIP_DEBUG")) {
 		fprintf(
@@ -1044,8 +1040,7 @@ PolishRun::finish()
 	float ms_screen = 0.f;
 	const size_t n_scr = pipelined ? n_ch : 1;
 	for (size_t j = 0; j < n_scr; j++) {
-		float t = 0.f;
-		(void)hipEventElapsedTime(&t, c->chunk_ev[2 * j], c->chunk_ev[2 * j + 1]);
+		const float t = elapsed_ms(c->chunk_ev[2 * j], c->chunk_ev[2 * j + 1]);
 		ms_screen += t;
 	}
 	r->st.ms_screen = ms_screen;
@@ -1054,9 +1049,7 @@ PolishRun::finish()
 		r->st.screen_binned = 1;
 		r->st.screen_launches = c->bin_chunks_last;
 		for (u32 q = 0; q < c->bin_chunks_last; q++) {
-			float tp = 0.f, tq = 0.f;
-			(void)hipEventElapsedTime(&tp, c->bin_ev[4 * q], c->bin_ev[4 * q + 1]);
-			(void)hipEventElapsedTime(&tq, c->bin_ev[4 * q + 2], c->bin_ev[4 * q + 3]);
+			const float tp = elapsed_ms(c->bin_ev[4 * q], c->bin_ev[4 * q + 1]), tq = elapsed_ms(c->bin_ev[4 * q + 2], c->bin_ev[4 * q + 3]);
 			r->st.ms_partition += tp;
 			r->st.ms_probe += tq;
 		}
@@ -1067,7 +1060,7 @@ PolishRun::finish()
 	r->st.ms_machine = ms_machine;
 	r->st.ms_extract = 0.f;
 	if (use_assess) {
-		(void)hipEventElapsedTime(&r->st.ms_extract, c->ev_assess[0], c->ev_assess[1]); // (the run map, k_assess)
+		r->st.ms_extract = elapsed_ms(c->ev_assess[0], c->ev_assess[1]); // (the run map, k_assess)
 	}
 	HIP_TRY(c, hipEventElapsedTime(&r->st.ms_total, c->ev[0], c->ev[4]));
 	c->last_ms = ms_screen;
@@ -1082,7 +1075,7 @@ PolishRun::apply()
 {
 	r->apply_flags = c->apply_flags;
 	r->device = c->device;
-	if (!c->apply_flags && !c->spectrum_on && c->cn.state == CN_OFF) {
+	if (!c->apply_flags && !c->rep.sp.on && c->cn.state == CN_OFF) {
 		return 0;
 	}
 	const ApplyInput in = { c, r, d_seq, n, n_words, n_contigs, d_bitmap, f0, ev_total, fa_names };
@@ -1108,7 +1101,7 @@ ntedit_hip_polish_batch(
 	*out = nullptr;
 	HIP_TRY(c, hipSetDevice(c->device));
 	int rc;
-	if ((c->spectrum_on || c->cn.state != CN_OFF) && (rc = spectrum_refuse(c, "polish_batch"))) {
+	if ((c->rep.sp.on || c->cn.state != CN_OFF) && (rc = spectrum_refuse(c, "polish_batch"))) {
 		return rc; // (a plain filter, or none -- NTEDIT_E_ARG, ahead of the general answer below: before anything is polished)
 	}
 	if ((rc = refresh_params(c))) {
@@ -1117,17 +1110,17 @@ ntedit_hip_polish_batch(
 	if ((c->apply_flags & NTEDIT_HIP_APPLY_SHARED) && (rc = shared_refuse(c, "polish_batch"))) {
 		return rc; // (a counting filter: before anything is polished)
 	}
-	if ((c->apply_flags & NTEDIT_HIP_APPLY_BGZF) && (!c->fa_names_set || c->fa_names.size() != n_contigs)) {
+	if ((c->apply_flags & NTEDIT_HIP_APPLY_BGZF) && (!c->rep.bz.fa_names_set || c->rep.bz.fa_names.size() != n_contigs)) {
 		return fail(c, NTEDIT_E_ARG, "polish_batch: APPLY_BGZF needs the header line of every entry (ntedit_hip_set_fa_names): %u entries, %s",
-		            n_contigs, c->fa_names_set ? "another number of names" : "no names");
+		            n_contigs, c->rep.bz.fa_names_set ? "another number of names" : "no names");
 	}
 	if (const u32 bad = nte_host::first_layout_break(n, offsets, lens, n_contigs, true); bad != nte_host::LAYOUT_OK) {
 		return fail(c, NTEDIT_E_ARG, "polish_batch: contig %u breaks the batch layout", bad);
 	}
 	std::vector<std::string> fa_names; // (the header lines serve this call alone: used up once its arguments are accepted)
 	if (c->apply_flags & NTEDIT_HIP_APPLY_BGZF) {
-		fa_names.swap(c->fa_names);
-		c->fa_names_set = false;
+		fa_names.swap(c->rep.bz.fa_names);
+		c->rep.bz.fa_names_set = false;
 	}
 	ntedit_hip_result* r = new ntedit_hip_result();
 	r->owner = c;
@@ -1138,11 +1131,11 @@ ntedit_hip_polish_batch(
 	r->apply_flags = c->apply_flags;
 	r->device = c->device;
 	if (n == 0 || n_contigs == 0) {
-		if (c->spectrum_on) { // (nothing to count: zeros)
+		if (c->rep.sp.on) { // (nothing to count: zeros)
 			r->spectrum = true;
 			r->sp_bins.assign(2 * (size_t)SPECTRUM_BINS, 0);
 			r->depth.assign(n_contigs, ntedit_hip_depth_row{ 0, 0, 0, 0, 0, 0 });
-			c->spectrum_last = ntedit_hip_spectrum_stats{ { 0.f, 0.f }, { 0, 0 } };
+			c->rep.sp.last = ntedit_hip_spectrum_stats{};
 		}
 		*out = r;
 		return 0;
@@ -1326,61 +1319,54 @@ ntedit_hip_reserve(ntedit_hip_ctx* c, uint64_t max_batch_bytes, uint32_t max_con
 			return rc;
 		}
 	}
-	if (c->apply_flags || c->spectrum_on || c->cn.state != CN_OFF) { // (the applier: an event's summary and place, the edited bases, the piece table; the QV bitmap)
-		if ((rc = ensure(c, c->ap_ev, (size_t)(n_ev + 1) * sizeof(ApplyEvent))) || (rc = ensure(c, c->ap_place, (size_t)(n_ev + 1) * sizeof(ApplyPlace))) ||
-		    (rc = ensure(c, c->ap_pieces, (size_t)(2 * n_ev + 2 * (u64)max_contigs + 1024) * sizeof(ApplyPiece))) ||
-		    (rc = ensure(c, c->ap_edited, (size_t)(n + n / 64 + 4096)))) {
+	if (c->apply_flags || c->rep.sp.on || c->cn.state != CN_OFF) {
+		// (assumptions about a draft, not sizes: the edited bases and the longer side n + n / 64 + 4096, two pieces per event
+		// and entry, about as many intervals as events; the sizes themselves are the reports': their structs in nte_api.hip)
+		const u64 n_after = n + n / 64 + 4096, n_entries = max_contigs ? max_contigs : 1;
+		Reports& rep = c->rep;
+		if ((rc = rep.ap.size_plan(c, n_ev, n_entries)) || (rc = rep.ap.size_write(c, rep.ap.edited, n_after, 2 * n_ev + 2 * (u64)max_contigs + 1024))) {
 			return rc;
 		}
-		if ((c->apply_flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) &&
-		    (rc = ensure(c, c->ap_bitmap, (size_t)(n_words + n_words / 64 + 64) * 8))) {
+		if ((c->apply_flags & (NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_TRACK)) && (rc = rep.ap.size_assess(c, n_after, n_entries))) {
 			return rc;
 		}
-		if (c->apply_flags & NTEDIT_HIP_APPLY_TRACK) { // (the tiles' counts; about as many intervals as events)
-			if ((rc = ensure(c, c->tr_tiles, (size_t)track_tiles(n + n / 64 + 4096) * sizeof(TrackTile))) || (rc = ensure(c, c->tr_totals, 64)) ||
-			    (rc = ensure(c, c->tr_recs, (size_t)n_ev * sizeof(TrackInterval))) || (rc = ensure(c, c->tr_upto, (size_t)n_ev * 4))) {
-				return rc;
-			}
+		if ((c->apply_flags & NTEDIT_HIP_APPLY_TRACK) && (rc = rep.tr.size(c, n_after, n_ev))) {
+			return rc;
 		}
-		if (c->spectrum_on && (rc = ensure(c, c->sp_buf, (2 * (size_t)SPECTRUM_BINS + 6 * (size_t)(max_contigs ? max_contigs : 1)) * 8))) {
+		if (rep.sp.on && (rc = ensure(c, rep.sp.buf, SpectrumReport::bytes(n_entries)))) {
 			return rc;
 		}
 		if (c->apply_flags & NTEDIT_HIP_APPLY_BGZF) { // (the image: the edited bases, and per entry '>', a header line, '\n')
 			std::string why;
-			const u64 image = n + n / 64 + 4096 + (u64)(max_contigs ? max_contigs : 1) * 64;
+			const u64 image = n_after + n_entries * 64;
 			if ((rc = bgzf_reserve(c, c->device, c->stream, image, max_contigs, &why))) {
 				return fail(c, rc, "reserve: %s", why.c_str());
 			}
 			// two results hold members at a time: the one a writer is writing out and the one being polished
 			PinBuf z[2];
-			for (PinBuf& b : z) {
-				if ((rc = bgzf_pin_take(c, (size_t)(image / 3), &b))) {
-					bgzf_pin_give(c, z[0]);
-					return rc;
-				}
-			}
-			bgzf_pin_give(c, z[0]);
+			rc = bgzf_pin_take(c, (size_t)(image / 3), &z[0]);
+			rc = rc ? rc : bgzf_pin_take(c, (size_t)(image / 3), &z[1]);
+			bgzf_pin_give(c, z[0]); // (an empty one is ignored)
 			bgzf_pin_give(c, z[1]);
+			if (rc) {
+				return rc;
+			}
 		}
 	}
 	// ---- page-locked result buffers (an event's records are about one 128-byte chunk; the pool hands out the best fit)
 	{
-		PinBuf a, b, e;
-		if ((rc = pin_take(c, (size_t)(n_ev + n_ev / 4 + 4096) * CHUNK_ITEMS * sizeof(Item) + 16, &a))) {
+		const size_t want[3] = { (size_t)(n_ev + n_ev / 4 + 4096) * CHUNK_ITEMS * sizeof(Item) + 16, (size_t)(n_ev + n_ev / 4) * 4 + 16,
+			                     (size_t)(n_ev + n_ev / 2 + 4096) * CHUNK_ITEMS * sizeof(Item) + 16 };
+		PinBuf taken[3];
+		for (int i = 0; i < 3 && !rc; i++) {
+			rc = pin_take(c, want[i], &taken[i]);
+		}
+		for (PinBuf& b : taken) {
+			pin_give(c, b); // (an empty one is ignored)
+		}
+		if (rc) {
 			return rc;
 		}
-		if ((rc = pin_take(c, (size_t)(n_ev + n_ev / 4) * 4 + 16, &b))) {
-			pin_give(c, a);
-			return rc;
-		}
-		if ((rc = pin_take(c, (size_t)(n_ev + n_ev / 2 + 4096) * CHUNK_ITEMS * sizeof(Item) + 16, &e))) {
-			pin_give(c, a);
-			pin_give(c, b);
-			return rc;
-		}
-		pin_give(c, a);
-		pin_give(c, b);
-		pin_give(c, e);
 	}
 	HIP_TRY(c, hipDeviceSynchronize());
 	return 0;

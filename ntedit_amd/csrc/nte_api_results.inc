@@ -1,5 +1,6 @@
 // nte_api_results.inc -- part of nte_api.hip: the C ABI of results (statistics, edit records, rendering through
-// host/render.cpp), host helpers (page-locked memory, NUMA binding), tuning knobs and the gather micro-benchmark.
+// host/render.cpp; what the reports put into a result is read through nte_api_reports.inc), host helpers (page-locked
+// memory, NUMA binding), tuning knobs and the gather micro-benchmark.
 extern "C" {
 
 void
@@ -17,8 +18,8 @@ ntedit_hip_result_free(ntedit_hip_result* r)
 		bool kept = false;
 		if (r->owner && ctx_alive(r->owner)) {
 			std::lock_guard<std::mutex> lk(r->owner->pin_mu);
-			if (!r->owner->ap_edited.p) {
-				r->owner->ap_edited = r->edited;
+			if (!r->owner->rep.ap.edited.p) {
+				r->owner->rep.ap.edited = r->edited;
 				kept = true;
 			}
 		}
@@ -30,647 +31,10 @@ ntedit_hip_result_free(ntedit_hip_result* r)
 	delete r;
 }
 
-static thread_local std::string g_result_err;
-
 const char*
 ntedit_hip_result_last_error(void)
 {
 	return g_result_err.c_str();
-}
-
-static int
-result_refuse(const ntedit_hip_result* r, const char* what)
-{
-	g_result_err = what;
-	if (r && r->owner && ctx_alive(r->owner)) {
-		r->owner->err = what;
-	}
-	return NTEDIT_E_ARG;
-}
-
-int
-ntedit_hip_set_apply(ntedit_hip_ctx* c, uint32_t flags)
-{
-	if (!c || (flags & ~(NTEDIT_HIP_APPLY_EDITED | NTEDIT_HIP_APPLY_QV | NTEDIT_HIP_APPLY_SHARED | NTEDIT_HIP_APPLY_BGZF | NTEDIT_HIP_APPLY_TRACK))) {
-		return fail(c, NTEDIT_E_ARG, "set_apply: unknown flag");
-	}
-	c->apply_flags = flags;
-	return 0;
-}
-
-int
-ntedit_hip_result_edited_device(const ntedit_hip_result* r, const char** dev_ptr, uint64_t* n_bytes, uint64_t* offsets_out, uint32_t* lens_out,
-                                uint32_t n_contigs)
-{
-	if (!r || !dev_ptr || !n_bytes) {
-		return result_refuse(r, "result_edited: bad argument");
-	}
-	if (!(r->apply_flags & NTEDIT_HIP_APPLY_EDITED)) {
-		return result_refuse(r, "result_edited: the batch was polished without the APPLY_EDITED flag (ntedit_hip_set_apply)");
-	}
-	if (n_contigs != r->e_offs.size() && (offsets_out || lens_out)) {
-		return result_refuse(r, "result_edited: the batch had another number of entries");
-	}
-	*dev_ptr = (const char*)r->edited.p;
-	*n_bytes = r->edited_bytes;
-	if (offsets_out && n_contigs) {
-		memcpy(offsets_out, r->e_offs.data(), (size_t)n_contigs * 8);
-	}
-	if (lens_out && n_contigs) {
-		memcpy(lens_out, r->e_lens.data(), (size_t)n_contigs * 4);
-	}
-	return 0;
-}
-
-int
-ntedit_hip_result_edited(const ntedit_hip_result* r, char* host_buf, uint64_t cap, uint64_t* n_bytes, uint64_t* offsets_out, uint32_t* lens_out,
-                         uint32_t n_contigs)
-{
-	const char* d = nullptr;
-	uint64_t nb = 0;
-	const int rc = ntedit_hip_result_edited_device(r, &d, &nb, offsets_out, lens_out, n_contigs);
-	if (rc) {
-		return rc;
-	}
-	if (n_bytes) {
-		*n_bytes = nb;
-	}
-	if (nb > cap || (nb && !host_buf)) {
-		g_result_err = "result_edited: the buffer is too small";
-		return NTEDIT_E_OVERFLOW;
-	}
-	if (nb && (hipSetDevice(r->device) != hipSuccess || hipMemcpy(host_buf, d, nb, hipMemcpyDeviceToHost) != hipSuccess)) {
-		g_result_err = "result_edited: the download failed";
-		return NTEDIT_E_DEVICE;
-	}
-	return 0;
-}
-
-int
-ntedit_hip_result_qv(const ntedit_hip_result* r, ntedit_hip_qv_row* rows, uint32_t n_contigs)
-{
-	if (!r || (n_contigs && !rows)) {
-		return result_refuse(r, "result_qv: bad argument");
-	}
-	if (!(r->apply_flags & NTEDIT_HIP_APPLY_QV)) {
-		return result_refuse(r, "result_qv: the batch was polished without the APPLY_QV flag (ntedit_hip_set_apply)");
-	}
-	if (n_contigs != r->qv.size()) {
-		return result_refuse(r, "result_qv: the batch had another number of entries");
-	}
-	if (n_contigs) {
-		memcpy(rows, r->qv.data(), (size_t)n_contigs * sizeof(ntedit_hip_qv_row));
-	}
-	return 0;
-}
-
-int
-ntedit_hip_apply_info(ntedit_hip_ctx* c, ntedit_hip_apply_stats* st)
-{
-	if (!c || !st) {
-		return fail(c, NTEDIT_E_ARG, "apply_info: bad argument");
-	}
-	*st = c->apply_last;
-	return 0;
-}
-
-uint32_t
-ntedit_hip_apply_tile(void)
-{
-	return APPLY_TILE;
-}
-
-// ---- the interval extractor (nte_track.hip)
-static_assert(sizeof(ntedit_hip_track_interval) == sizeof(TrackInterval) && sizeof(TrackInterval) == 16, "the records are copied as they stand");
-
-int
-ntedit_hip_result_track(const ntedit_hip_result* r, int which, ntedit_hip_track_interval* out, uint64_t cap, uint64_t* n)
-{
-	if (!r || !n || which < 0 || which > 1 || (cap && !out)) {
-		return result_refuse(r, "result_track: bad argument");
-	}
-	if (!(r->apply_flags & NTEDIT_HIP_APPLY_TRACK)) {
-		return result_refuse(r, "result_track: the batch was polished without the APPLY_TRACK flag (ntedit_hip_set_apply)");
-	}
-	*n = r->track_n[which];
-	if (*n > cap) {
-		g_result_err = "result_track: the buffer is too small";
-		return NTEDIT_E_OVERFLOW;
-	}
-	if (*n) {
-		memcpy(out, r->track[which], (size_t)*n * sizeof(ntedit_hip_track_interval));
-	}
-	return 0;
-}
-
-int
-ntedit_hip_track_extract(ntedit_hip_ctx* c, const uint64_t* bitmap, uint64_t n_positions, const uint64_t* offs, const uint32_t* lens,
-                         uint32_t n_entries, uint32_t k, ntedit_hip_track_interval* out, uint64_t cap, uint64_t* n)
-{
-	if (!c || !n || (n_positions && !bitmap) || (n_entries && (!offs || !lens)) || (cap && !out)) {
-		return fail(c, NTEDIT_E_ARG, "track_extract: bad argument");
-	}
-	*n = 0;
-	if (k == 0 || k > TRACK_MAX_K) {
-		return fail(c, NTEDIT_E_UNSUPPORTED, "track_extract: k from 1 to %u", TRACK_MAX_K);
-	}
-	if (const u32 bad = nte_host::first_layout_break(n_positions, offs, lens, n_entries, false); bad != nte_host::LAYOUT_OK) {
-		return fail(c, NTEDIT_E_ARG, "track_extract: entry %u breaks the batch layout", bad);
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	c->track_last = ntedit_hip_track_stats{ { 0.f, 0.f }, { 0, 0 }, { 0, 0 } };
-	if (n_positions == 0 || n_entries == 0) {
-		return 0;
-	}
-	int rc;
-	const u64 n_words = (n_positions + 63) / 64;
-	if ((rc = ensure(c, c->ap_bitmap, (size_t)(n_words + 8) * 8)) || (rc = ensure(c, c->offs, (size_t)n_entries * 8)) ||
-	    (rc = ensure(c, c->lens, (size_t)n_entries * 4))) {
-		return rc;
-	}
-	hipStream_t s = c->stream;
-	HIP_TRY(c, hipMemcpyAsync(c->ap_bitmap.p, bitmap, (size_t)n_words * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(c, hipMemcpyAsync(c->offs.p, offs, (size_t)n_entries * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(c, hipMemcpyAsync(c->lens.p, lens, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
-	ntedit_hip_track_interval* recs = nullptr;
-	u64 n_recs = 0;
-	rc = track_run(c, s, (const u64*)c->ap_bitmap.p, n_positions, (const u64*)c->offs.p, (const u32*)c->lens.p, n_entries, k, 0, &recs, &n_recs);
-	if (rc) {
-		(void)hipStreamSynchronize(s);
-		free(recs);
-		return rc;
-	}
-	*n = n_recs;
-	if (n_recs > cap) {
-		free(recs);
-		return fail(c, NTEDIT_E_OVERFLOW, "track_extract: %llu intervals, the buffer has room for %llu", (unsigned long long)n_recs, (unsigned long long)cap);
-	}
-	if (n_recs) {
-		memcpy(out, recs, (size_t)n_recs * sizeof(ntedit_hip_track_interval));
-	}
-	free(recs);
-	return 0;
-}
-
-int
-ntedit_hip_track_info(ntedit_hip_ctx* c, ntedit_hip_track_stats* st)
-{
-	if (!c || !st) {
-		return fail(c, NTEDIT_E_ARG, "track_info: bad argument");
-	}
-	*st = c->track_last;
-	return 0;
-}
-
-// ---- the k-mer spectrum (k_spectrum, nte_kernels.hip; the helpers are in nte_api_screen.inc)
-
-int
-ntedit_hip_set_spectrum(ntedit_hip_ctx* c, int on)
-{
-	if (!c) {
-		return NTEDIT_E_ARG;
-	}
-	c->spectrum_on = on != 0;
-	return 0;
-}
-
-int
-ntedit_hip_result_spectrum(const ntedit_hip_result* r, int which, uint64_t bins[256])
-{
-	if (!r || !bins || which < 0 || which > 1) {
-		return result_refuse(r, "result_spectrum: bad argument");
-	}
-	if (!r->spectrum) {
-		return result_refuse(r, "result_spectrum: the batch was polished with the spectrum switched off (ntedit_hip_set_spectrum)");
-	}
-	memcpy(bins, r->sp_bins.data() + (size_t)which * SPECTRUM_BINS, SPECTRUM_BINS * 8);
-	return 0;
-}
-
-int
-ntedit_hip_result_depth(const ntedit_hip_result* r, ntedit_hip_depth_row* rows, uint32_t n_contigs)
-{
-	if (!r || (n_contigs && !rows)) {
-		return result_refuse(r, "result_depth: bad argument");
-	}
-	if (!r->spectrum) {
-		return result_refuse(r, "result_depth: the batch was polished with the spectrum switched off (ntedit_hip_set_spectrum)");
-	}
-	if (n_contigs != r->depth.size()) {
-		return result_refuse(r, "result_depth: the batch had another number of entries");
-	}
-	if (n_contigs) {
-		memcpy(rows, r->depth.data(), (size_t)n_contigs * sizeof(ntedit_hip_depth_row));
-	}
-	return 0;
-}
-
-int
-ntedit_hip_spectrum_count(ntedit_hip_ctx* c, const char* bases, uint64_t n, int on_device, const uint64_t* offs, const uint32_t* lens,
-                          uint32_t n_entries, uint64_t* bins, uint64_t* rows)
-{
-	if (!c || !bins || (n && !bases) || (n_entries && (!offs || !lens))) {
-		return fail(c, NTEDIT_E_ARG, "spectrum_count: bad argument");
-	}
-	if (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) {
-		return fail(c, NTEDIT_E_ARG, "spectrum_count: bases must be host or device bytes");
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc = spectrum_refuse(c, "spectrum_count");
-	if (rc || (rc = refresh_params(c))) {
-		return rc;
-	}
-	if (const u32 bad = nte_host::first_layout_break(n, offs, lens, n_entries, false); bad != nte_host::LAYOUT_OK) {
-		return fail(c, NTEDIT_E_ARG, "spectrum_count: entry %u breaks the batch layout", bad);
-	}
-	memset(bins, 0, SPECTRUM_BINS * 8);
-	if (rows && n_entries) {
-		memset(rows, 0, (size_t)n_entries * 24);
-	}
-	c->spectrum_last = ntedit_hip_spectrum_stats{ { 0.f, 0.f }, { 0, 0 } };
-	if (n == 0 || n_entries == 0) {
-		return 0;
-	}
-	hipStream_t s = c->stream;
-	const u8* d_seq = nullptr;
-	if ((rc = stage_bases(c, bases, n, on_device, &d_seq)) || (rc = ensure(c, c->offs, (size_t)n_entries * 8)) ||
-	    (rc = ensure(c, c->lens, (size_t)n_entries * 4)) || (rc = spectrum_begin(c, s, n_entries))) {
-		return rc;
-	}
-	HIP_TRY(c, hipMemcpyAsync(c->offs.p, offs, (size_t)n_entries * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(c, hipMemcpyAsync(c->lens.p, lens, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
-	const Filter f0 = dev_filter(c->filt[0]);
-	if ((rc = launch_spectrum(c, s, d_seq, n, f0, (const u64*)c->offs.p, (const u32*)c->lens.p, n_entries, 0, rows != nullptr))) {
-		(void)hipStreamSynchronize(s);
-		return rc;
-	}
-	HIP_TRY(c, hipMemcpyAsync(bins, spectrum_bins(c, 0), SPECTRUM_BINS * 8, hipMemcpyDeviceToHost, s));
-	if (rows) {
-		HIP_TRY(c, hipMemcpyAsync(rows, spectrum_rows(c, 0, n_entries), (size_t)n_entries * 24, hipMemcpyDeviceToHost, s));
-	}
-	HIP_TRY(c, hipStreamSynchronize(s));
-	spectrum_timed(c, 0, bins);
-	return 0;
-}
-
-int
-ntedit_hip_spectrum_info(ntedit_hip_ctx* c, ntedit_hip_spectrum_stats* st)
-{
-	if (!c || !st) {
-		return fail(c, NTEDIT_E_ARG, "spectrum_info: bad argument");
-	}
-	*st = c->spectrum_last;
-	return 0;
-}
-
-// ---- the spectrum by copy number (nte_cn.hip: the draft store, k_cn_count, k_spectrum_cn)
-
-int
-ntedit_hip_set_cn(ntedit_hip_ctx* c, int on, uint64_t store_cap_bytes)
-{
-	if (!c) {
-		return NTEDIT_E_ARG;
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	cn_switch(c->cn, on != 0, store_cap_bytes);
-	return 0;
-}
-
-int
-ntedit_hip_cn_append(ntedit_hip_ctx* c, int which, const char* bases, uint64_t n, int on_device, const uint64_t* offs, const uint32_t* lens,
-                     uint32_t n_entries)
-{
-	if (!c || which < 0 || which > 1 || (n && !bases) || (n_entries && (!offs || !lens))) {
-		return fail(c, NTEDIT_E_ARG, "cn_append: bad argument");
-	}
-	if (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) {
-		return fail(c, NTEDIT_E_ARG, "cn_append: bases must be host or device bytes");
-	}
-	if (c->cn.state == CN_OFF) {
-		return fail(c, NTEDIT_E_ARG, "cn_append: the copy numbers are switched off (ntedit_hip_set_cn)");
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc = spectrum_refuse(c, "cn_append");
-	if (rc) {
-		return rc;
-	}
-	if (const u32 bad = nte_host::first_layout_break(n, offs, lens, n_entries, false); bad != nte_host::LAYOUT_OK) {
-		return fail(c, NTEDIT_E_ARG, "cn_append: entry %u breaks the batch layout", bad);
-	}
-	std::string why;
-	if ((rc = cn_append(c->cn, which, c->stream, bases, n, offs, lens, n_entries, &why))) {
-		return fail(c, rc, "%s", why.c_str());
-	}
-	HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the caller's arrays are free again)
-	return 0;
-}
-
-int
-ntedit_hip_cn_finish(ntedit_hip_ctx* c, uint64_t sketch_counters)
-{
-	if (!c) {
-		return NTEDIT_E_ARG;
-	}
-	if (sketch_counters && ((sketch_counters & (sketch_counters - 1)) || sketch_counters < CN_FLOOR_COUNTERS || sketch_counters > CN_MAX_COUNTERS)) {
-		return fail(c, NTEDIT_E_ARG, "cn_finish: the sketch takes a power of two of 2^20 to 2^36 counters (from 2^6 to force collisions), or 0 for the default");
-	}
-	switch (c->cn.state) {
-	case CN_OFF:
-		return fail(c, NTEDIT_E_ARG, "cn_finish: the copy numbers are switched off (ntedit_hip_set_cn)");
-	case CN_OVER_CAP:
-		return fail(c, NTEDIT_E_OVERFLOW, "cn_finish: the draft passed the store's cap of %llu bytes and the store was released", (unsigned long long)c->cn.cap);
-	case CN_NO_MEMORY:
-		return fail(c, NTEDIT_E_OVERFLOW, "cn_finish: the device had no memory for the draft and the store was released");
-	default:
-		break;
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc = spectrum_refuse(c, "cn_finish");
-	if (rc || (rc = refresh_params(c))) {
-		return rc;
-	}
-	std::string why;
-	const u64 counters = sketch_counters ? sketch_counters : cn_default_counters(c->cn);
-	if ((rc = cn_finish(c->cn, c->stream, dev_filter(c->filt[0]), c->dp, c->d_tab, counters, &why))) {
-		return fail(c, rc, "%s", why.c_str());
-	}
-	return 0;
-}
-
-int
-ntedit_hip_cn_table(ntedit_hip_ctx* c, int which, uint64_t* occ, uint64_t* w5)
-{
-	if (!c || which < 0 || which > 1 || !occ || !w5) {
-		return fail(c, NTEDIT_E_ARG, "cn_table: bad argument");
-	}
-	if (!c->cn.finished) {
-		return fail(c, NTEDIT_E_ARG, "cn_table: no results: ntedit_hip_set_cn, the batches, then ntedit_hip_cn_finish");
-	}
-	const u64* t = c->cn.table[which].data();
-	memcpy(occ, t, (size_t)CN_CLASSES * CN_BINS * 8);
-	memcpy(w5, t + CN_CLASSES * CN_BINS, (size_t)CN_BINS * 8);
-	return 0;
-}
-
-int
-ntedit_hip_cn_rows(ntedit_hip_ctx* c, int which, ntedit_hip_cn_row* rows, uint64_t n)
-{
-	if (!c || which < 0 || which > 1 || (n && !rows)) {
-		return fail(c, NTEDIT_E_ARG, "cn_rows: bad argument");
-	}
-	if (!c->cn.finished) {
-		return fail(c, NTEDIT_E_ARG, "cn_rows: no results: ntedit_hip_set_cn, the batches, then ntedit_hip_cn_finish");
-	}
-	if (n != c->cn.entries[which]) {
-		return fail(c, NTEDIT_E_ARG, "cn_rows: the side holds %llu entries", (unsigned long long)c->cn.entries[which]);
-	}
-	static_assert(sizeof(ntedit_hip_cn_row) == CN_ROW_WORDS * 8, "a row is six words");
-	if (n) {
-		memcpy(rows, c->cn.rows[which].data(), (size_t)n * sizeof(ntedit_hip_cn_row));
-	}
-	return 0;
-}
-
-int
-ntedit_hip_cn_info(ntedit_hip_ctx* c, ntedit_hip_cn_stats* st)
-{
-	if (!c || !st) {
-		return fail(c, NTEDIT_E_ARG, "cn_info: bad argument");
-	}
-	const CnStore& s = c->cn;
-	memset(st, 0, sizeof *st);
-	st->state = (uint32_t)s.state;
-	st->finished = s.finished ? 1 : 0;
-	for (int w = 0; w < 2; w++) {
-		st->batches[w] = s.side[w].size();
-		st->bytes[w] = s.bytes[w];
-		st->entries[w] = s.entries[w];
-		st->nonzero[w] = s.nonzero[w];
-	}
-	st->cap = s.cap;
-	st->counters = s.counters;
-	for (int i = 0; i < 4; i++) {
-		st->ms[i] = s.ms[i];
-	}
-	return 0;
-}
-
-int
-ntedit_hip_cn_reset(ntedit_hip_ctx* c)
-{
-	if (!c) {
-		return NTEDIT_E_ARG;
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	cn_reset(c->cn);
-	return 0;
-}
-
-int
-ntedit_hip_cn_free(ntedit_hip_ctx* c)
-{
-	if (!c) {
-		return NTEDIT_E_ARG;
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	cn_free(c->cn);
-	return 0;
-}
-
-// ---- the BGZF writer (nte_bgzf_deflate.hip)
-
-int
-ntedit_hip_set_fa_names(ntedit_hip_ctx* c, const char* const* names, uint32_t n)
-{
-	if (!c || (n && !names)) {
-		return fail(c, NTEDIT_E_ARG, "set_fa_names: bad argument");
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (!names[i]) {
-			return fail(c, NTEDIT_E_ARG, "set_fa_names: name %u is NULL", i);
-		}
-	}
-	c->fa_names.assign(names, names + n);
-	c->fa_names_set = true;
-	return 0;
-}
-
-int
-ntedit_hip_result_fa_bgzf(const ntedit_hip_result* r, const uint8_t** host, uint64_t* n_bytes, uint64_t* n_plain, uint32_t* n_members)
-{
-	if (!r) {
-		return result_refuse(r, "result_fa_bgzf: bad argument");
-	}
-	if (!(r->apply_flags & NTEDIT_HIP_APPLY_BGZF)) {
-		return result_refuse(r, "result_fa_bgzf: the batch was polished without the APPLY_BGZF flag (ntedit_hip_set_apply)");
-	}
-	if (host) {
-		*host = (const uint8_t*)r->bgzf_buf.p;
-	}
-	if (n_bytes) {
-		*n_bytes = r->bgzf_bytes;
-	}
-	if (n_plain) {
-		*n_plain = r->bgzf_plain;
-	}
-	if (n_members) {
-		*n_members = r->bgzf_members;
-	}
-	return 0;
-}
-
-int
-ntedit_hip_bgzf_deflate(ntedit_hip_ctx* c, const void* src, uint64_t n, int on_device, uint8_t* out, uint64_t cap, uint64_t* n_out)
-{
-	if (!c || !n_out || (n && !src) || (cap && !out) || (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE)) {
-		return fail(c, NTEDIT_E_ARG, "bgzf_deflate: bad argument");
-	}
-	*n_out = 0;
-	std::string why;
-	BgzfTotals t;
-	const u8* d_src = (const u8*)src;
-	int rc = 0;
-	if (on_device == NTEDIT_HIP_BASES_HOST && n) {
-		rc = bgzf_upload(c, c->device, c->stream, src, n, &d_src, &why);
-	}
-	if (!rc) {
-		rc = bgzf_encode(c, c->device, c->stream, d_src, n, &t, &why);
-	}
-	if (rc) {
-		return fail(c, rc, "bgzf_deflate: %s", why.c_str());
-	}
-	*n_out = t.bytes;
-	c->bgzf_last = { 0.f, t.ms_deflate, 0.f, t.plain, t.bytes, t.members, t.stored };
-	if (t.bytes > cap) {
-		return fail(c, NTEDIT_E_OVERFLOW, "bgzf_deflate: the members take %llu bytes, the buffer has %llu", (unsigned long long)t.bytes, (unsigned long long)cap);
-	}
-	if ((rc = bgzf_fetch(c, c->stream, out, t.bytes, &c->bgzf_last.ms_copy, &why))) {
-		return fail(c, rc, "bgzf_deflate: %s", why.c_str());
-	}
-	return 0;
-}
-
-int
-ntedit_hip_bgzf_info(ntedit_hip_ctx* c, ntedit_hip_bgzf_stats* st)
-{
-	if (!c || !st) {
-		return fail(c, NTEDIT_E_ARG, "bgzf_info: bad argument");
-	}
-	*st = c->bgzf_last;
-	return 0;
-}
-
-// ---- the completeness marks (k_mark, nte_kernels.hip; the helpers are in nte_api_screen.inc)
-
-int
-ntedit_hip_shared_begin(ntedit_hip_ctx* c)
-{
-	if (!c) {
-		return NTEDIT_E_ARG;
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	return shared_begin(c, "shared_begin");
-}
-
-int
-ntedit_hip_shared_reset(ntedit_hip_ctx* c)
-{
-	if (!c || !c->sh_bytes) {
-		return fail(c, NTEDIT_E_ARG, "shared_reset: no marks (ntedit_hip_shared_begin)");
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	return shared_zero(c);
-}
-
-void
-ntedit_hip_shared_free(ntedit_hip_ctx* c)
-{
-	if (c && hipSetDevice(c->device) == hipSuccess) {
-		(void)hipStreamSynchronize(c->stream);
-		shared_release(c);
-	}
-}
-
-int
-ntedit_hip_shared_mark(ntedit_hip_ctx* c, int which, const char* bases, uint64_t n, int on_device)
-{
-	if (!c || which < 0 || which > 1 || (n && !bases)) {
-		return fail(c, NTEDIT_E_ARG, "shared_mark: bad argument");
-	}
-	if (on_device != NTEDIT_HIP_BASES_HOST && on_device != NTEDIT_HIP_BASES_DEVICE) {
-		return fail(c, NTEDIT_E_ARG, "shared_mark: bases must be host or device bytes");
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc = shared_begin(c, "shared_mark");
-	if (rc || (rc = refresh_params(c))) {
-		return rc;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const u64 n_words = (n + 63) / 64;
-	const u8* d_seq = nullptr;
-	if ((rc = stage_bases(c, bases, n, on_device, &d_seq)) || (rc = ensure(c, c->bitmap, (n_words + 8) * 8))) {
-		return rc;
-	}
-	u64* d_bitmap = (u64*)c->bitmap.p;
-	const Filter f0 = dev_filter(c->filt[0]);
-	PlainScreen plain(c);
-	if ((rc = screen_whole(c, d_seq, n, f0, d_bitmap, n_words)) || (rc = launch_mark(c, c->stream, d_seq, n, f0, d_bitmap, n_words, which))) {
-		(void)hipStreamSynchronize(c->stream);
-		return rc;
-	}
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	mark_timed(c, which);
-	return 0;
-}
-
-int
-ntedit_hip_shared_download(ntedit_hip_ctx* c, int which, uint8_t* bits)
-{
-	if (!c || which < 0 || which > 1 || !bits || !c->sh_bytes) {
-		return fail(c, NTEDIT_E_ARG, "shared_download: bad argument, or no marks (ntedit_hip_shared_begin)");
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	HIP_TRY(c, hipMemcpy(bits, c->sh_marks[which].p, c->sh_bytes, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-int
-ntedit_hip_shared_counts(ntedit_hip_ctx* c, ntedit_hip_shared_stats* st)
-{
-	if (!c || !st || !c->sh_bytes || !c->filt[0].set || c->filt[0].nbytes != c->sh_bytes) {
-		return fail(c, NTEDIT_E_ARG, "shared_counts: bad argument, or no marks (ntedit_hip_shared_begin)");
-	}
-	HIP_TRY(c, hipSetDevice(c->device));
-	const DevFilter& f = c->filt[0];
-	int rc = ensure(c, c->counters, 256);
-	if (rc) {
-		return rc;
-	}
-	unsigned long long* d_total = (unsigned long long*)c->counters.p;
-	HIP_TRY(c, hipMemsetAsync(d_total, 0, 24, c->stream));
-	const u64 n_words = (f.nbytes + 7) / 8; // (all three allocations are whole 64-bit words, zero behind nbytes)
-	const u64* arrays[3] = { (const u64*)f.data, (const u64*)c->sh_marks[0].p, (const u64*)c->sh_marks[1].p };
-	for (int i = 0; i < 3; i++) {
-		hipLaunchKernelGGL(k_popcount, dim3((unsigned)(c->cu_count * 8)), dim3(256), 0, c->stream, arrays[i], n_words, 0, d_total + i);
-	}
-	HIP_TRY(c, hipGetLastError());
-	unsigned long long h[3] = { 0, 0, 0 };
-	HIP_TRY(c, hipMemcpyAsync(h, d_total, 24, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	memset(st, 0, sizeof *st);
-	st->bits = f.nbytes * 8;
-	st->hash_num = f.hash_num;
-	st->k = f.k;
-	st->filter_set = h[0];
-	st->shared_set[0] = h[1];
-	st->shared_set[1] = h[2];
-	st->marked_calls = c->sh_calls;
-	st->ms_mark[0] = c->sh_ms[0];
-	st->ms_mark[1] = c->sh_ms[1];
-	return 0;
 }
 
 int
@@ -740,34 +104,24 @@ ntedit_hip_write_outputs_ex(
 	if (!r || !wo || (n_contigs && (!bases || !offsets || !lens || !names))) {
 		return NTEDIT_E_ARG;
 	}
-	const char* fa_path = wo->fa_path;
-	const char* tsv_path = wo->tsv_path;
-	const char* vcf_path = wo->vcf_path;
-	const int append = wo->append;
-	FILE* fa = fa_path ? fopen(fa_path, append ? "ab" : "wb") : nullptr;
-	FILE* tsv = tsv_path ? fopen(tsv_path, append ? "ab" : "wb") : nullptr;
-	FILE* vcf = vcf_path ? fopen(vcf_path, append ? "ab" : "wb") : nullptr;
-	if ((fa_path && !fa) || (tsv_path && !tsv) || (vcf_path && !vcf)) {
-		if (fa) {
-			fclose(fa);
+	const char* const paths[3] = { wo->fa_path, wo->tsv_path, wo->vcf_path };
+	FILE* out[3] = { nullptr, nullptr, nullptr }; // fa, tsv, vcf
+	bool opened = true;
+	for (int i = 0; i < 3; i++) {
+		out[i] = paths[i] ? fopen(paths[i], wo->append ? "ab" : "wb") : nullptr;
+		opened = opened && (!paths[i] || out[i]);
+	}
+	for (int i = 0; i < 3; i++) {
+		if (out[i] && !opened) {
+			fclose(out[i]);
+		} else if (out[i]) {
+			setvbuf(out[i], nullptr, _IOFBF, i == 0 ? 4 << 20 : 1 << 20);
 		}
-		if (tsv) {
-			fclose(tsv);
-		}
-		if (vcf) {
-			fclose(vcf);
-		}
+	}
+	if (!opened) {
 		return NTEDIT_E_IO;
 	}
-	if (fa) {
-		setvbuf(fa, nullptr, _IOFBF, 4 << 20);
-	}
-	if (tsv) {
-		setvbuf(tsv, nullptr, _IOFBF, 1 << 20);
-	}
-	if (vcf) {
-		setvbuf(vcf, nullptr, _IOFBF, 1 << 20);
-	}
+	FILE *fa = out[0], *tsv = out[1], *vcf = out[2];
 	ntedit_hip_result* rw = const_cast<ntedit_hip_result*>(r);
 	rw->rst = nte_host::RenderStats();
 	nte_host::RenderOptions opt;
@@ -795,14 +149,10 @@ ntedit_hip_write_outputs_ex(
 	    &rw->rst,
 	    vcf,
 	    &opt);
-	if (fa && fclose(fa) != 0) {
-		rc = rc ? rc : -5;
-	}
-	if (tsv && fclose(tsv) != 0) {
-		rc = rc ? rc : -5;
-	}
-	if (vcf && fclose(vcf) != 0) {
-		rc = rc ? rc : -5;
+	for (FILE* f : out) {
+		if (f && fclose(f) != 0) {
+			rc = rc ? rc : -5;
+		}
 	}
 	if (rc == -7 || rc == -8) {
 		return NTEDIT_E_SEGMENT;

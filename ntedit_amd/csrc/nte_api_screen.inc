@@ -1,5 +1,6 @@
 // nte_api_screen.inc -- part of nte_api.hip (inside its anonymous namespace): launches of the screening kernels -- direct
-// (k_screen) and L2-partitioned (nte_bin_wc.inc + k_bin_probe) --, staging of a batch in HBM (bytes, or the packed form).
+// (k_screen) and L2-partitioned (nte_bin_wc.inc + k_bin_probe) --, staging of a batch in HBM (bytes, or the packed form),
+// PlainScreen and WarmupSwitches.  (The reports' helpers -- marks, spectrum -- are in nte_api_reports.inc.)
 bool binned_applicable(const ntedit_hip_ctx* c, const Filter& f, u64 n, u32* slice_log2, u32* n_slices);
 bool candmap_applicable(const ntedit_hip_ctx* c, const Filter& f, u64 n, u32* slice_log2, u32* n_slices);
 int bin_reset(ntedit_hip_ctx* c, hipStream_t stream);
@@ -43,26 +44,14 @@ launch_screen_tiles(
 			    c->d_tab, d_bitmap, n_words, first_tile);                                        \
 		}                                                                                        \
 	} while (0)
+#define NTE_CASE(H) case H: NTE_LAUNCH(H); break;
 	switch (f.hash_num) {
-	case 1:
-		NTE_LAUNCH(1);
-		break;
-	case 2:
-		NTE_LAUNCH(2);
-		break;
-	case 3:
-		NTE_LAUNCH(3);
-		break;
-	case 4:
-		NTE_LAUNCH(4);
-		break;
-	case 5:
-		NTE_LAUNCH(5);
-		break;
+		NTE_CASE(1) NTE_CASE(2) NTE_CASE(3) NTE_CASE(4) NTE_CASE(5)
 	default:
 		NTE_LAUNCH(0);
 		break;
 	}
+#undef NTE_CASE
 #undef NTE_LAUNCH
 	HIP_TRY(c, hipGetLastError());
 	return 0;
@@ -81,8 +70,6 @@ launch_screen(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u64* d
 		if (binned_applicable(c, f, n, &slog, &n_slices)) {
 			return run_screen_binned(c, d_seq, n, f, d_bitmap, n_words, slog, n_slices);
 		}
-	}
-	if (!INSERT) {
 		c->bin_chunks_last = 0;
 	}
 	return launch_screen_tiles<INSERT>(c, c->stream, d_seq, n, f, d_bitmap, n_words, 0, blocks, 0);
@@ -143,7 +130,7 @@ struct WarmupSwitches
 	u32 apply_flags;
 	bool spectrum_on;
 	int cn_state;
-	WarmupSwitches(ntedit_hip_ctx* c_, bool binned) : c(c_), tune(c_->tune), apply_flags(c_->apply_flags), spectrum_on(c_->spectrum_on), cn_state(c_->cn.state)
+	WarmupSwitches(ntedit_hip_ctx* c_, bool binned) : c(c_), tune(c_->tune), apply_flags(c_->apply_flags), spectrum_on(c_->rep.sp.on), cn_state(c_->cn.state)
 	{
 		if (binned) {
 			c->tune.screen_mode = 2;
@@ -156,252 +143,17 @@ struct WarmupSwitches
 		}
 		const bool something_on = apply_flags || spectrum_on || cn_state != CN_OFF;
 		c->apply_flags = !flags && something_on ? NTEDIT_HIP_APPLY_EDITED : flags;
-		c->spectrum_on = false;
+		c->rep.sp.on = false;
 		c->cn.state = CN_OFF;
 	}
 	~WarmupSwitches()
 	{
 		c->tune = tune;
 		c->apply_flags = apply_flags;
-		c->spectrum_on = spectrum_on;
+		c->rep.sp.on = spectrum_on;
 		c->cn.state = cn_state;
 	}
 };
-
-// ---- the completeness marks (k_mark): two arrays of the PRIMARY filter's size
-void
-shared_release(ntedit_hip_ctx* c)
-{
-	release(c->sh_marks[0]);
-	release(c->sh_marks[1]);
-	c->sh_bytes = 0;
-	c->sh_calls = 0;
-	c->sh_ms[0] = c->sh_ms[1] = 0.f;
-}
-
-// why the context cannot hold marks (0: it can)
-int
-shared_refuse(ntedit_hip_ctx* c, const char* who)
-{
-	const DevFilter& f = c->filt[0];
-	if (!f.set) {
-		return fail(c, NTEDIT_E_ARG, "%s: no primary Bloom filter to measure completeness against", who);
-	}
-	if (f.counting) {
-		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: completeness takes a plain primary filter; a counting filter's slots are counters", who);
-	}
-	if (f.k > QV_MAX_K) {
-		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: the completeness marks take k up to %u", who, QV_MAX_K);
-	}
-	return 0;
-}
-
-int
-shared_zero(ntedit_hip_ctx* c)
-{
-	const size_t padded = (size_t)((c->sh_bytes + 7) / 8 * 8);
-	for (auto& m : c->sh_marks) {
-		HIP_TRY(c, hipMemsetAsync(m.p, 0, padded, c->stream));
-	}
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	c->sh_calls = 0;
-	c->sh_ms[0] = c->sh_ms[1] = 0.f;
-	return 0;
-}
-
-int
-shared_begin(ntedit_hip_ctx* c, const char* who)
-{
-	int rc = shared_refuse(c, who);
-	if (rc) {
-		return rc;
-	}
-	if (c->sh_bytes) {
-		return 0; // (the marks of this filter: drop_filter releases them with it)
-	}
-	if ((rc = ensure_events(c, c->sh_evt))) {
-		return rc;
-	}
-	// (whole 64-bit words, as the filter's own allocation: k_popcount reads words, k_mark ORs into 32-bit ones)
-	const size_t padded = (size_t)((c->filt[0].nbytes + 7) / 8 * 8);
-	for (auto& m : c->sh_marks) {
-		release(m);
-		if (hipMalloc(&m.p, padded) != hipSuccess) {
-			(void)hipGetLastError();
-			shared_release(c);
-			return fail(c, NTEDIT_E_DEVICE, "%s: no device memory for two mark arrays of %llu bytes", who, (unsigned long long)padded);
-		}
-		m.cap = padded;
-	}
-	c->sh_bytes = c->filt[0].nbytes;
-	if ((rc = shared_zero(c))) {
-		shared_release(c);
-	}
-	return rc;
-}
-
-// k_mark over a batch and its absent bitmap into M[which], on `stream`, between the two events of that array
-int
-launch_mark(ntedit_hip_ctx* c, hipStream_t stream, const u8* d_seq, u64 n, const Filter& f, const u64* d_bitmap, u64 n_words, int which)
-{
-	const u64 blocks = (n + SCREEN_TILE - 1) / SCREEN_TILE;
-	if (blocks == 0) {
-		return 0;
-	}
-	if (blocks > 0x7FFFFFFFull) {
-		return fail(c, NTEDIT_E_ARG, "batch too large");
-	}
-	if (!c->sh_bytes || c->sh_bytes != c->filt[0].nbytes || f.counting) {
-		return fail(c, NTEDIT_E_INTERNAL, "mark: the marks are not those of the primary filter");
-	}
-	u32* marks = (u32*)c->sh_marks[which].p;
-	HIP_TRY(c, hipEventRecord(c->sh_evt[2 * which], stream));
-	if (f.mask) {
-		hipLaunchKernelGGL((k_mark<true>), dim3((unsigned)blocks), dim3(SCREEN_TPB), 0, stream, d_seq, n, f, c->dp.k, c->d_tab, d_bitmap, n_words, marks);
-	} else {
-		hipLaunchKernelGGL((k_mark<false>), dim3((unsigned)blocks), dim3(SCREEN_TPB), 0, stream, d_seq, n, f, c->dp.k, c->d_tab, d_bitmap, n_words, marks);
-	}
-	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipEventRecord(c->sh_evt[2 * which + 1], stream));
-	c->sh_calls++;
-	return 0;
-}
-
-// after `stream` has been waited for: the launch's time goes to its array's sum
-void
-mark_timed(ntedit_hip_ctx* c, int which)
-{
-	float ms = 0.f;
-	if (hipEventElapsedTime(&ms, c->sh_evt[2 * which], c->sh_evt[2 * which + 1]) == hipSuccess) {
-		c->sh_ms[which] += ms;
-	} else {
-		(void)hipGetLastError();
-	}
-}
-
-// ---- the k-mer spectrum (k_spectrum): the PRIMARY filter's counters under a batch's k-mers
-// why the context cannot count a spectrum (0: it can)
-int
-spectrum_refuse(ntedit_hip_ctx* c, const char* who)
-{
-	const DevFilter& f = c->filt[0];
-	if (!f.set) {
-		return fail(c, NTEDIT_E_ARG, "%s: no primary filter to take the k-mer spectrum from", who);
-	}
-	if (!f.counting) {
-		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: the k-mer spectrum takes a counting primary filter; a plain filter's slots are bits", who);
-	}
-	if (f.k > (u32)SCREEN_MAXK || f.hash_num < 1 || f.hash_num > MAX_HASHES) {
-		return fail(c, NTEDIT_E_UNSUPPORTED, "%s: the k-mer spectrum takes k up to %d and 1 to %u hashes", who, SCREEN_MAXK, MAX_HASHES);
-	}
-	return 0;
-}
-
-// bins[256] and rows[n_entries][3] of one launch, inside sp_buf: [which][256] bins, then [which][n_entries][3] rows
-unsigned long long*
-spectrum_bins(ntedit_hip_ctx* c, int which)
-{
-	return (unsigned long long*)c->sp_buf.p + (size_t)which * SPECTRUM_BINS;
-}
-
-unsigned long long*
-spectrum_rows(ntedit_hip_ctx* c, int which, u32 n_entries)
-{
-	return (unsigned long long*)c->sp_buf.p + 2 * SPECTRUM_BINS + (size_t)which * n_entries * 3;
-}
-
-// sp_buf for a call over n_entries entries, zeroed on `stream`; the events
-int
-spectrum_begin(ntedit_hip_ctx* c, hipStream_t stream, u32 n_entries)
-{
-	const size_t bytes = (2 * (size_t)SPECTRUM_BINS + 2 * (size_t)n_entries * 3) * 8;
-	int rc;
-	if ((rc = ensure_events(c, c->sp_evt)) || (rc = ensure(c, c->sp_buf, bytes))) {
-		return rc;
-	}
-	HIP_TRY(c, hipMemsetAsync(c->sp_buf.p, 0, bytes, stream));
-	c->spectrum_last = ntedit_hip_spectrum_stats{ { 0.f, 0.f }, { 0, 0 } };
-	return 0;
-}
-
-// k_spectrum over a batch in device memory and its entries into launch `which`'s bins and rows, on `stream`, between the
-// two events of that launch
-int
-launch_spectrum(ntedit_hip_ctx* c, hipStream_t stream, const u8* d_seq, u64 n, const Filter& f, const u64* d_offs, const u32* d_lens, u32 n_entries,
-                int which, bool want_rows)
-{
-	const u64 blocks = (n + SCREEN_TILE - 1) / SCREEN_TILE;
-	if (blocks > 0x7FFFFFFFull) {
-		return fail(c, NTEDIT_E_ARG, "batch too large");
-	}
-	if (!f.counting || c->dp.k > (u32)SCREEN_MAXK || c->dp.k == 0) {
-		return fail(c, NTEDIT_E_INTERNAL, "spectrum: not a counting filter, or k beyond the tile's halo");
-	}
-	unsigned long long* bins = spectrum_bins(c, which);
-	unsigned long long* rows = want_rows ? spectrum_rows(c, which, n_entries) : nullptr;
-	HIP_TRY(c, hipEventRecord(c->sp_evt[2 * which], stream));
-	if (blocks && n_entries) {
-		dim3 grid((unsigned)blocks), block(SCREEN_TPB);
-		const bool pow2 = f.mask != 0;
-#define NTE_LAUNCH(H)                                                                                                              \
-	do {                                                                                                                           \
-		if (pow2) {                                                                                                                \
-			hipLaunchKernelGGL((k_spectrum<H, true>), grid, block, 0, stream, d_seq, n, f, c->dp, c->d_tab, d_offs, d_lens, n_entries, bins, rows);  \
-		} else {                                                                                                                   \
-			hipLaunchKernelGGL((k_spectrum<H, false>), grid, block, 0, stream, d_seq, n, f, c->dp, c->d_tab, d_offs, d_lens, n_entries, bins, rows); \
-		}                                                                                                                          \
-	} while (0)
-		switch (f.hash_num) {
-		case 1:
-			NTE_LAUNCH(1);
-			break;
-		case 2:
-			NTE_LAUNCH(2);
-			break;
-		case 3:
-			NTE_LAUNCH(3);
-			break;
-		case 4:
-			NTE_LAUNCH(4);
-			break;
-		case 5:
-			NTE_LAUNCH(5);
-			break;
-		case 6:
-			NTE_LAUNCH(6);
-			break;
-		case 7:
-			NTE_LAUNCH(7);
-			break;
-		case 8:
-			NTE_LAUNCH(8);
-			break;
-		default:
-			return fail(c, NTEDIT_E_UNSUPPORTED, "spectrum: 1 to %u hashes", MAX_HASHES);
-		}
-#undef NTE_LAUNCH
-		HIP_TRY(c, hipGetLastError());
-	}
-	HIP_TRY(c, hipEventRecord(c->sp_evt[2 * which + 1], stream));
-	return 0;
-}
-
-// after `stream` has been waited for: the launch's time and, from its bins on the host, its k-mers
-void
-spectrum_timed(ntedit_hip_ctx* c, int which, const uint64_t* bins)
-{
-	float ms = 0.f;
-	if (hipEventElapsedTime(&ms, c->sp_evt[2 * which], c->sp_evt[2 * which + 1]) != hipSuccess) {
-		(void)hipGetLastError();
-		ms = 0.f;
-	}
-	u64 total = 0;
-	for (int i = 0; i < SPECTRUM_BINS; i++) {
-		total += bins[i];
-	}
-	c->spectrum_last.ms[which] = ms;
-	c->spectrum_last.kmers[which] = total;
-}
 
 // ---- L2-partitioned ("binned") screening; see nte_kernels.hip / nte_bin_wc.inc
 // screen_mode 1 forces the direct gather kernel, 2 the binned pipeline (tests run it on small inputs); 0 picks:
@@ -951,9 +703,7 @@ run_screen_binned(ntedit_hip_ctx* c, const u8* d_seq, u64 n, const Filter& f, u6
 		}
 		if (c->tune.bin_timing) {
 			HIP_TRY(c, hipStreamSynchronize(stream));
-			float t_part = 0.f, t_probe = 0.f;
-			(void)hipEventElapsedTime(&t_part, tev[0], tev[1]);
-			(void)hipEventElapsedTime(&t_probe, tev[2], tev[3]);
+			const float t_part = elapsed_ms(tev[0], tev[1]), t_probe = elapsed_ms(tev[2], tev[3]);
 			u32 ovf_n = 0;
 			(void)hipMemcpy(&ovf_n, d_ovf_count, 4, hipMemcpyDeviceToHost);
 			fprintf(stderr, "[ntedit_hip] binned chunk %llu k-mers, %u slices of 2^%u bits (rings of %u) probed in %u part(s), %u x %u-record runs per slice (%.2f GB), %u overflow records: partition %.3f ms, probe %.3f ms (stages timed alone)\n",
